@@ -8,7 +8,7 @@ and every visible object (+ fg/bg mask integration on every 30th frame, as in th
 on a deterministic synthetic RGB-D stream whose depth maps are resident in HBM before the timed
 region starts.  Poses and masks are supplied (tracking and Mask R-CNN are outside this path).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N = 1 runs BASELINE.json configs[1]: background 512^3 @ 1 cm + 4 object volumes 128^3, 640x480.
 N > 1 (launched by torch.distributed.run, one rank per GPU) is the object-sharded layout of
@@ -16,14 +16,19 @@ configs[3]: every rank holds a replica of the background and `--objects-per-gpu`
 of its own; ranks exchange one RCCL all-reduce per E-step (normaliser) and one per raycast
 (nearest-hit merge).  Weak scaling: per-GPU work is fixed, the scene grows with N.
 
-The timed region holds the product path plus a HIP-event pair around every 4th launch of the long kernels
-(raycast, background integration, tracking stage; --event-stride) and nothing else: the march-sample counters the byte model of `roofline` needs are
-collected afterwards, in an untimed replay of the same frames from a cleared state (--no-stats-replay skips it).
+A plain run sets up, runs W untimed frames and K timed ones, writes the last timed frame's outputs
+(--dump-outputs DIR: DIR/<name>.npy, float32, see dump_outputs) and prints the headline line: the timed
+region holds the product path and nothing else.  An RCCL failure exits non-zero (--allow-fallback: gloo, labelled).
 
-Behind the headline, in the same line (bench_extras.py): `target_config`, `steady_state`, `entry_point` (the reference's
-processFrame(RGBD) on a staged TUM-layout scene), `strong_scaling` (configs[3]'s 64-object scene, fixed, split over the
-ranks) and -- N > 1 -- `rccl` (ranks / devices the transport saw), `sharded_parity` (replicas and joint images against a
-single-rank re-run) and `per_rank_roofline`.  An RCCL failure exits non-zero (--allow-fallback: gloo, labelled).
+--full adds everything else the benchmark measures, in the same process.  Its timed region also holds a
+HIP-event pair around every 4th launch of the long kernels (raycast, background integration, tracking stage;
+--event-stride) for the per-kernel `kernels` / `roofline` objects; the march-sample counters the byte model of
+`roofline` needs are collected afterwards, in an untimed replay of the same frames from a cleared state
+(--no-stats-replay skips it), beside a copy-bandwidth and an L1 probe.  Behind the headline, in the same line
+(bench_extras.py): `target_config`, `steady_state`, `entry_point` (the reference's processFrame(RGBD) on a staged
+TUM-layout scene), `strong_scaling` (configs[3]'s 64-object scene, fixed, split over the ranks), `cpu_baseline`
+and -- N > 1 -- `rccl` (ranks / devices the transport saw), `sharded_parity` (replicas and joint images against a
+single-rank re-run) and `per_rank_roofline`.
 
 Rank 0 prints ONE JSON line (see README / DESIGN.md for the `roofline` and `cpu_baseline` objects).
 torch is used for torch.distributed only (gloo rendezvous, barriers, max-reduce of the time); all
@@ -52,6 +57,14 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed frames, write what the last one computed (images, and a fixed seeded sample of "
+                         "every volume) as DIR/<name>.npy in float32, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-kernel HIP events in the timed region, the untimed replay "
+                         "with the march counters, copy / L1 probes and `roofline`, target_config, steady_state, "
+                         "entry_point, strong_scaling, cpu_baseline and, N > 1, rccl / sharded_parity / per_rank_roofline. "
+                         "The --no-* switches below select among them")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--bg-res", type=int, default=512)
@@ -76,21 +89,21 @@ def parse_args():
     ap.add_argument("--track-spheres", action="store_true",
                     help="rounds 2-5's tracked figure: configs[1]'s sphere scene with poses tracked instead of supplied "
                          "(under-constrained: an object stage often burns its whole budget on unobservable motion; a footnote)")
-    ap.add_argument("--no-entry", action="store_true", help="skip the `entry_point` sub-line of the default N = 1 run")
-    ap.add_argument("--no-strong", action="store_true", help="skip the `strong_scaling` sub-run (configs[3]'s scene, fixed, "
-                                                             "split over the ranks)")
+    ap.add_argument("--no-entry", action="store_true", help="skip the `entry_point` sub-line of --full with N = 1")
+    ap.add_argument("--no-strong", action="store_true", help="skip the `strong_scaling` sub-run of --full (configs[3]'s scene, "
+                                                             "fixed, split over the ranks)")
     ap.add_argument("--strong-objects", type=int, default=None,
                     help="objects of the strong-scaling scene (default: configs[3]'s 64 when the run has configs[1] / [3]'s "
                          "geometry -- 640x480, background 512^3, objects 128^3 --, none for other geometries unless given)")
-    ap.add_argument("--no-parity", action="store_true", help="N > 1: skip `sharded_parity` (replicas / joint images against a "
-                                                             "single-rank re-run on rank 0)")
+    ap.add_argument("--no-parity", action="store_true", help="N > 1: skip `sharded_parity` of --full (replicas / joint images "
+                                                             "against a single-rank re-run on rank 0)")
     ap.add_argument("--parity-frames", type=int, default=4)
     ap.add_argument("--allow-fallback", action="store_true",
                     help="N > 1: if RCCL cannot be brought up, fall back to host-staged collectives over gloo (loudly labelled) "
                          "instead of exiting non-zero")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the `cpu_baseline` of --full")
     ap.add_argument("--no-target", action="store_true",
-                    help="skip the two further measurements the default N = 1 run appends: `target_config` (north_star's "
+                    help="skip the two further measurements --full appends with N = 1: `target_config` (north_star's "
                          "target configuration, bg 512^3 + 8 x 128^3) and `steady_state` (the headline's workload over "
                          "frames 25..124, a window that holds four mask frames)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
@@ -103,7 +116,7 @@ def parse_args():
                     help="bracket every N-th launch of the long kernels with a HIP-event pair (default 4; 1 = every "
                          "launch).  The records sit on the streams they time: all of them cost 2.6 %% of the frame rate")
     ap.add_argument("--no-kernel-events", action="store_true",
-                    help="do not bracket kernel launches with HIP events in the timed region")
+                    help="do not bracket kernel launches with HIP events in the timed region of --full, --track or --entry")
     ap.add_argument("--no-depth-broadcast", action="store_true",
                     help="multi-GPU: every rank already holds the frame; skip the per-frame "
                          "ncclBroadcast of the depth image from rank 0")
@@ -140,6 +153,8 @@ def dist_setup(n_gpus):
 
 def main():
     args = parse_args()
+    if args.dump_outputs and (args.track or args.entry):
+        raise SystemExit("--dump-outputs writes the outputs of the sphere scene's frames, not those of --track / --entry")
     # torch FIRST: its wheel bundles libamdhip64.so.7 / librccl.so.1 under the same SONAMEs as
     # /opt/rocm, so whichever copy is loaded first serves the whole process.  Importing torch
     # before the product libraries gives one HIP runtime (and one RCCL) for torch.distributed,
@@ -284,7 +299,8 @@ def main():
 
     # ---- timed region: exactly K frames, barrier + device sync on both sides ---------------------
     launches_per_frame = 8 * (1 + len(mine)) + 12
-    if not args.no_kernel_events:
+    kernel_events = args.full and not args.no_kernel_events  # only the per-kernel figures of --full need them
+    if kernel_events:
         fus.kernel_timers_enable(launches_per_frame * args.steps + 64)
         if not args.all_kernel_events:
             fus.kernel_timers_select(["raycast", "integrate_bg", "track"] if fus.background_overlap() else ["raycast", "integrate", "track"])
@@ -322,10 +338,11 @@ def main():
 
     if os.environ.get("BENCH_PER_STEP"):
         print("PER_STEP_US " + " ".join("%.0f" % (1e6 * v) for v in per_step), file=sys.stderr, flush=True)
-    kern = None if args.no_kernel_events else fus.kernel_timers_collect()
+    kern = fus.kernel_timers_collect() if kernel_events else None
     visible = fus.visible_objects()
     chunks = fus.batched_chunks()
-
+    if args.dump_outputs and rank == 0:
+        dump_outputs(fus, mine, args.dump_outputs)
 
     track_steps = []
 
@@ -336,7 +353,7 @@ def main():
         deterministic: same frames from a cleared state, same launches."""
         if args.no_stats_replay:
             return None
-        if not args.no_kernel_events:
+        if kernel_events:
             fus.kernel_timers_enable(0)  # no event pairs in the replay
         if args.track:
             fus.set_tracking(camera=False, objects=False)
@@ -357,13 +374,15 @@ def main():
         fus.synchronize()
         return fus.raycast_stats()
 
-    # the copy-bandwidth probe comes first: its kernel also marks, in a kernel trace of this command, where
-    # the measured run ends and the replay begins (scripts/summarize_profile.py)
-    copy_gbs = copy_bandwidth(devmem, ops)  # every rank: its own device (the rehearsal's ranks share one)
-    l1p = l1_probe(devmem, ops)
-    barrier()
-    stats = replay_with_counters()
-    barrier()
+    copy_gbs = l1p = stats = None
+    if args.full:
+        # the copy-bandwidth probe comes first: its kernel also marks, in a kernel trace of this command, where
+        # the measured run ends and the replay begins (scripts/summarize_profile.py)
+        copy_gbs = copy_bandwidth(devmem, ops)  # every rank: its own device (the rehearsal's ranks share one)
+        l1p = l1_probe(devmem, ops)
+        barrier()
+        stats = replay_with_counters()
+        barrier()
 
     # ---- every rank prices ITS kernels with the committed profile of its share; rank 0 gathers the summaries ----
     share_key = workload_key(W, H, args.bg_res, args.obj_res, len(mine), args.track)
@@ -371,7 +390,7 @@ def main():
     if kern is not None:
         my_roof, my_rows = roofline(kern, stats, P, copy_gbs, share_key, args.steps, l1p)
     per_rank = None
-    if comm is not None:
+    if comm is not None and args.full:
         ray = next((r for r in (my_rows or []) if r["kind"] == "raycast"), None)
         integ = next((r for r in (my_rows or []) if r["kind"] in ("integrate_bg", "integrate")), None)
         brief = {"rank": rank, "objects": len(mine), "workload_key": share_key,
@@ -447,16 +466,17 @@ def main():
         # priced by the newest committed PMC summary of THIS workload (profiles/*_counters.json carry a workload key);
         # with N > 1 every rank is priced with the profile of its SHARE (its objects + the background on one GPU)
         result["config"]["workload_key"] = share_key
-        result["roofline"] = my_roof
-        if my_rows is not None:
-            result["kernels"] = my_rows
-        if world > 1 or comm is not None:
-            result["per_rank_roofline"] = per_rank
-            if my_roof is not None:
-                my_roof["share_note"] = ("counters of the committed profile of this rank's share run UNSHARDED on one GPU "
-                                         f"({share_key}); the sharded launch marches 1/{world} of the background's rows and adds "
-                                         "the exchanges, durations are this run's HIP events on this rank")
-        result["hbm_copy_GBs"] = copy_gbs  # attainable D2D stream bandwidth of THIS box (read + write)
+        if args.full:
+            result["roofline"] = my_roof
+            if my_rows is not None:
+                result["kernels"] = my_rows
+            if world > 1 or comm is not None:
+                result["per_rank_roofline"] = per_rank
+                if my_roof is not None:
+                    my_roof["share_note"] = ("counters of the committed profile of this rank's share run UNSHARDED on one GPU "
+                                             f"({share_key}); the sharded launch marches 1/{world} of the background's rows and adds "
+                                             "the exchanges, durations are this run's HIP events on this rank")
+            result["hbm_copy_GBs"] = copy_gbs  # attainable D2D stream bandwidth of THIS box (read + write)
         # work aggregate for the scaling curves: every rank's volumes advance one frame per step
         result["volume_frames_per_s"] = round(fps * (world + nobj_total), 1)
         result["scaling_note"] = ("weak scaling of ONE RGB-D stream: every GPU adds --objects-per-gpu "
@@ -465,7 +485,66 @@ def main():
                                   "= the N=1 value); volume_frames_per_s is the aggregate work rate, which "
                                   "grows with N")
     fus.close()
+    if args.full:
+        full_extras(args, result, pipeline, ops, DeviceArray, prm, K, comm, dist, rank, world, nobj_total, synth,
+                    synth_factory, ids, depth_broadcast)
+
+    synth.close()
+    if comm is not None:
+        comm.close()
+    if rank == 0:
+        # libraries (RCCL's version banner) write to C stdio: flush that first so that the JSON line
+        # is the last line of the output whatever the buffering
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+        print(json.dumps(result), flush=True)
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+DUMP_BYTES = 64 << 20         # --dump-outputs writes at most this much
+DUMP_VOLUME_SAMPLE = 1 << 19  # voxels kept of every volume
+
+
+def _sample(a, k):
+    """k elements of `a` (flattened) at indices drawn from a generator seeded with a.size: the same voxels of every volume
+    of one size, in every run."""
+    if k >= a.size:
+        return a
+    return a.reshape(-1)[np.sort(np.random.default_rng(a.size).integers(0, a.size, k))]
+
+
+def dump_outputs(fus, obj_ids, directory):
+    """What a caller of the timed path holds after its last frame, as DIR/<name>.npy in float32: the composite raycast
+    (ray lengths, vertices, normals, model segmentation), every model's association weights and ray lengths, the visible
+    objects, and a fixed sample of DUMP_VOLUME_SAMPLE voxels of every volume (TSDF and weights; the objects' foreground
+    probabilities too).  Were that more than DUMP_BYTES (many objects, large images), every array would be sampled down
+    by one common factor."""
+    images = {name: (name, 0) for name in ("raylengths", "vertices", "normals", "segmentation", "bg_assoc", "bg_raylengths")}
+    volumes = {"bg_tsdf": ("tsdf", 0), "bg_weights": ("weights", 0)}
+    for i in obj_ids:
+        images.update({f"obj{i}_assoc": ("obj_assoc", i), f"obj{i}_raylengths": ("obj_raylengths", i)})
+        volumes.update({f"obj{i}_{v}": (v, i) for v in ("tsdf", "weights", "fgprobs")})
+    arrays = {name: fus.image(*sel) for name, sel in images.items()}
+    visible = np.array(sorted(fus.visible_objects()), np.float32)
+    elements = sum(a.size for a in arrays.values()) + len(volumes) * DUMP_VOLUME_SAMPLE + visible.size
+    keep = min(1.0, DUMP_BYTES / 4.0 / elements)
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "visible_objects.npy"), visible)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), _sample(a, int(a.size * keep)).astype(np.float32))
+    for name, sel in volumes.items():
+        v = fus.volume(*sel)
+        np.save(os.path.join(directory, name + ".npy"), _sample(v, int(DUMP_VOLUME_SAMPLE * keep)).astype(np.float32))
+
+
+def full_extras(args, result, pipeline, ops, DeviceArray, prm, K, comm, dist, rank, world, nobj_total, synth, synth_factory, ids,
+                depth_broadcast):
+    """What --full measures behind the headline run, into rank 0's `result`: the transport report and the sharded parity
+    check (N > 1), strong scaling, the target configuration, the steady-state window, the entry point and the CPU baseline."""
     import bench_extras
+    W, H = args.width, args.height
     if args.strong_objects is None:
         args.strong_objects = 64 if (W, H, args.bg_res, args.obj_res) == (640, 480, 512, 128) else 0
     if comm is not None:
@@ -499,19 +578,6 @@ def main():
         result["entry_point"] = bench_extras.entry_point(pipeline, ops, DeviceArray)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args, prm, K, synth, ids)
-
-    synth.close()
-    if comm is not None:
-        comm.close()
-    if rank == 0:
-        # libraries (RCCL's version banner) write to C stdio: flush that first so that the JSON line
-        # is the last line of the output whatever the buffering
-        import ctypes
-        ctypes.CDLL(None).fflush(None)
-        print(json.dumps(result), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 def measure_window(args, pipeline, ops, DeviceArray, prm, nobj, first, count):

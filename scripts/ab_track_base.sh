@@ -6,7 +6,7 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 P=emfusion_amd
 mkdir -p /tmp/ab_new && cp $P/libemf_hip.so $P/libemf_fusion.so /tmp/ab_new/
 run() {
-  python bench.py --steps ${STEPS:-100} --warmup 30 --no-cpu-baseline --no-stats-replay --no-target ${BENCH_ARGS:---track} 2>/dev/null | grep '^{' | python -c "
+  python bench.py --full --steps ${STEPS:-100} --warmup 30 --no-cpu-baseline --no-stats-replay --no-target ${BENCH_ARGS:---track} 2>/dev/null | grep '^{' | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = [x for x in d['kernels'] if x['kind'] == 'track']

@@ -5,7 +5,7 @@ tag=$1; shift
 out=gpurun_out/pmc_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-PMCBENCH="python bench.py --steps 10 --warmup 30 --no-cpu-baseline --no-kernel-events"
+PMCBENCH="python bench.py --full --steps 10 --warmup 30 --no-cpu-baseline --no-kernel-events"
 i=0
 for group in "$@"; do
   i=$((i+1))

@@ -10,6 +10,6 @@ EMF_PAIR_PROBE=1 timeout 900 python -m pytest tests/test_gpu_pipeline.py tests/t
 echo "pairs tests rc $?"; tail -2 gpurun_out/r05b/tests_pairs.log
 bash scripts/ab_env.sh "rows1:EMF_MARCH_ROWS=1" "rows2:EMF_MARCH_ROWS=2" "rows4:EMF_MARCH_ROWS=4" "pairs:EMF_PAIR_PROBE=1" "rows1:EMF_MARCH_ROWS=1" "rows2:EMF_MARCH_ROWS=2" "pairs:EMF_PAIR_PROBE=1" 2>&1 | tee gpurun_out/r05b/ab.log
 for rows in 1 2 4; do
-EMF_MARCH_ROWS=$rows timeout 150 python bench.py --steps 100 --warmup 30 --no-cpu-baseline --no-target 2>/dev/null | python -c "
+EMF_MARCH_ROWS=$rows timeout 150 python bench.py --full --steps 100 --warmup 30 --no-cpu-baseline --no-target 2>/dev/null | python -c "
 import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('ROWS $rows samples', r.get('march_samples_per_launch'), 'gathered', r.get('march_gathered_per_launch'))"
 done 2>&1 | tee -a gpurun_out/r05b/ab.log

@@ -3,7 +3,7 @@
 cd /root/repo
 mkdir -p gpurun_out/r05f
 ab() { name=$1; shift; envs=$1; shift
-  env $envs timeout 150 python bench.py --steps 100 --warmup 30 --no-cpu-baseline --no-stats-replay --no-target "$@" 2>&1 | grep -v amdgpu.ids | python -c "
+  env $envs timeout 150 python bench.py --full --steps 100 --warmup 30 --no-cpu-baseline --no-stats-replay --no-target "$@" 2>&1 | grep -v amdgpu.ids | python -c "
 import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k={x['kind']:x['avg_ms'] for x in d['kernels']}; print('ENV $name', d['value'], 'fps', d['ms_per_step'], 'ms; raycast', k['raycast'], 'integrate', k.get('integrate'), 'integrate_bg', k.get('integrate_bg'))"; }
 for rows in 1 2 4; do
 ab "noobj-rows$rows-serial" "EMF_MARCH_ROWS=$rows EMF_BG_OVERLAP=0" --objects-per-gpu 0

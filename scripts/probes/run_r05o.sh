@@ -8,7 +8,7 @@ BENCH_ARGS="--no-target" bash scripts/sweep_variants.sh "full86:-DEMF_GRAD_FULL"
 for v in "full86:-DEMF_GRAD_FULL" "lean71:" "lean-wpe8:-DEMF_RAY_WPE=8"; do
   name=${v%%:*}; flags=${v#*:}
   touch emfusion_amd/csrc/batched.hip; make -s -C emfusion_amd/csrc -j8 EXTRA="$flags" >/dev/null 2>&1
-  EMF_BG_OVERLAP=0 timeout 150 python bench.py --steps 100 --warmup 30 --no-cpu-baseline --no-stats-replay --no-target 2>&1 | grep -v amdgpu.ids | python -c "
+  EMF_BG_OVERLAP=0 timeout 150 python bench.py --full --steps 100 --warmup 30 --no-cpu-baseline --no-stats-replay --no-target 2>&1 | grep -v amdgpu.ids | python -c "
 import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k={x['kind']:x['avg_ms'] for x in d['kernels']}; print('SERIAL $name', d['value'], 'fps', d['ms_per_step'], 'ms; raycast', k['raycast'], 'integrate', k.get('integrate'))"
 done 2>&1 | tee -a gpurun_out/r05o/ab.log
 git checkout scripts/sweep_variants.sh 2>/dev/null

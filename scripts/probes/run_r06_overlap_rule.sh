@@ -5,7 +5,7 @@
 cd /root/repo
 mkdir -p gpurun_out/r06_rule
 run() { name=$1; envs=$2; shift 2
-  env $envs timeout 200 python bench.py --no-cpu-baseline --no-stats-replay --no-target --no-strong --no-entry "$@" 2>&1 | grep -v amdgpu.ids | tail -1 | python -c "
+  env $envs timeout 200 python bench.py --full --no-cpu-baseline --no-stats-replay --no-target --no-strong --no-entry "$@" 2>&1 | grep -v amdgpu.ids | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); k={x['kind']:x['avg_ms'] for x in d.get('kernels',[])}; print('RULE $name [$envs]', d['value'], 'fps', d['ms_per_step'], 'ms', k)"; }
 for size in "640 480 4 128" "1280 960 2 256"; do
   set -- $size; W=$1; H=$2; NOBJ=$3; ORES=$4

@@ -32,7 +32,7 @@ def test_bench_runs_with_several_ranks(dev, world):
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), str(ROOT / "bench.py"),
            "--gpus", str(world), "--steps", "6", "--warmup", "3", "--bg-res", "128", "--bg-voxel", "0.04",
            "--obj-res", "32", "--objects-per-gpu", "2", "--width", "320", "--height", "240",
-           "--no-cpu-baseline", "--comm", "gloo", "--strong-objects", str(STRONG[world])]
+           "--no-cpu-baseline", "--comm", "gloo", "--strong-objects", str(STRONG[world]), "--full"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
