@@ -7,6 +7,10 @@
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
 //                  [--bg-res R] [--bg-voxel M] [--obj-res R] [--volumes] --out DIR
 //   emfusion_synth --dir BASE/ [--colordir colour] [--depthdir depth] [--intrinsics fx fy cx cy] ... --out DIR
+// --3d-vis (needs --out): the reference's 3D view (apps/EM-Fusion.cpp:118-131) -- every frame is rendered (render())
+// together with the whole map seen from a viewer 1 m behind the world origin at 1024 x 768, and writeResults writes
+// those views as DIR/mesh_vis_out/%04d.png.  --3d-vis-eye x y z --3d-vis-target x y z place the viewer instead
+// (looking from eye at target, world -y up).
 // --configfile FILE (-c): with --sequence / --dir, take every parameter from one of the reference's configuration files
 // (config/default.cfg, tum.cfg ...; core/Config.hpp) instead of the sizing options above.
 // --dir: the same loop on a Co-Fusion style dataset (ColorNNNN.png + DepthNNNN.exr), the reference's ImageReader
@@ -36,12 +40,42 @@
 #include "Readers.hpp"
 #include "SyntheticScene.hpp"
 
+// --3d-vis: the viewer of the reference's window (apps/EM-Fusion.cpp:127-130: setCamera(intr, frameSize),
+// setViewerPose(translate(0, 0, -1)), 1024 x 768), or a camera at `eye` looking at `target`
+struct View3d {
+    bool on = false, placed = false;
+    float eye[3] = {0.f, 0.f, -1.f}, target[3] = {0.f, 0.f, 0.f};
+};
+static void set3dView(emf::EMFusion& emf, const emf::Params& params, const View3d& v) {
+    if (!v.on) return;
+    const emf::Size size(1024, 768);
+    const float sx = static_cast<float>(size.width) / static_cast<float>(params.frameSize.width),
+                sy = static_cast<float>(size.height) / static_cast<float>(params.frameSize.height);
+    const float K[9] = {params.intr(0, 0) * sx, 0.f, params.intr(0, 2) * sx, 0.f, params.intr(1, 1) * sy,
+                        params.intr(1, 2) * sy, 0.f, 0.f, 1.f};
+    emf::Matx33f R = emf::Matx33f::eye();
+    if (v.placed) {  // OpenCV camera axes in world coordinates: z forward, x = down x z, y = z x x (down = +y)
+        float z[3] = {v.target[0] - v.eye[0], v.target[1] - v.eye[1], v.target[2] - v.eye[2]};
+        const float zn = std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]);
+        float x[3] = {z[2], 0.f, -z[0]};  // (0, 1, 0) x z
+        const float xn = std::sqrt(x[0] * x[0] + x[2] * x[2]);
+        if (!(zn > 0.f) || !(xn > 1e-6f * zn)) throw std::runtime_error("--3d-vis-eye / --3d-vis-target: no usable direction");
+        for (int k = 0; k < 3; ++k) {
+            z[k] /= zn;
+            x[k] /= xn;
+        }
+        const float y[3] = {z[1] * x[2] - z[2] * x[1], z[2] * x[0] - z[0] * x[2], z[0] * x[1] - z[1] * x[0]};
+        R = emf::Matx33f(x[0], y[0], z[0], x[1], y[1], z[1], x[2], y[2], z[2]);
+    }
+    emf.set3dView(emf::Affine3f(R, emf::Vec3f(v.eye[0], v.eye[1], v.eye[2])), K, size);
+}
+
 // The reference's main loop on a dataset (apps/EM-Fusion.cpp:100-156): a TUM sequence (`--sequence`, TUMRGBDReader) or a
 // Co-Fusion style directory (`--dir`, ImageReader: ColorNNNN.png + DepthNNNN.exr), as apps/EM-Fusion.cpp:118-131 chooses
 static int runSequence(const std::string& seq, bool cofusion, const std::string& colordir, const std::string& depthdir,
                        const float* intrinsics, const std::string& configFile, const std::string& masks,
                        const std::string& outDir, int frames, int bgRes, float bgVoxel, int objRes, int maskFrames,
-                       int visibilityThresh, bool volumes) {
+                       int visibilityThresh, bool volumes, const View3d& view3d) {
     std::unique_ptr<emf::TUMRGBDReader> tum;
     std::unique_ptr<emf::ImageReader> dir;
     size_t available = 0;
@@ -94,6 +128,8 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     emf::EMFusion emf(params);
     if (!masks.empty()) emf.usePreprocMasks(masks);   // apps/EM-Fusion.cpp:115
     emf.setupOutput(false, volumes);                  // apps/EM-Fusion.cpp:112
+    set3dView(emf, params, view3d);
+    std::vector<uint8_t> rendered(3 * params.frameSize.area());
     const auto t0 = std::chrono::steady_clock::now();
     for (size_t f = 0; f < n; ++f) {                  // while (reader->moreFrames())
         readDepth(f);                                 // frame = reader->getNextFrame()
@@ -107,6 +143,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
         frame.size = size;
         frame.depth = depth.data();
         emf.processFrame(frame);                      // apps/EM-Fusion.cpp:152
+        if (view3d.on) emf.render(rendered.data());   // apps/EM-Fusion.cpp:156: the rendering and the 3D view
         if (f % 50 == 0) {
             std::vector<uint8_t> maskim;
             const int inst = emf.getLastMasks(maskim);  // apps/EM-Fusion.cpp:162
@@ -131,6 +168,7 @@ int main(int argc, char** argv) {
     int maskFrames = 30, visThresh = 0, framesGiven = 0;
     float bgVoxel = 0.f;
     bool volumes = false;
+    View3d view3d;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() { return i + 1 < argc ? std::atoi(argv[++i]) : 0; };
@@ -157,10 +195,24 @@ int main(int argc, char** argv) {
         else if (a == "--materialize-gradients") materialize = true;
         else if (a == "--autonomous") autonomous = true;
         else if (a == "--out" && i + 1 < argc) outDir = argv[++i];
+        else if (a == "--3d-vis") view3d.on = true;
+        else if ((a == "--3d-vis-eye" || a == "--3d-vis-target") && i + 3 < argc) {
+            float* dst = a == "--3d-vis-eye" ? view3d.eye : view3d.target;
+            for (int k = 0; k < 3; ++k) dst[k] = static_cast<float>(std::atof(argv[++i]));
+            view3d.placed = true;
+        }
         else {
             std::fprintf(stderr, "unknown argument %s\n", a.c_str());
             return 2;
         }
+    }
+    if (view3d.placed && !view3d.on) {
+        std::fprintf(stderr, "emfusion_synth: --3d-vis-eye / --3d-vis-target need --3d-vis\n");
+        return 2;
+    }
+    if (view3d.on && outDir.empty()) {  // (before any device is touched)
+        std::fprintf(stderr, "emfusion_synth: --3d-vis writes DIR/mesh_vis_out/ and needs --out DIR\n");
+        return 2;
     }
     try {
         if (!sequence.empty() || !dataDir.empty()) {
@@ -168,7 +220,7 @@ int main(int argc, char** argv) {
             const bool cofusion = !dataDir.empty();
             return runSequence(cofusion ? dataDir : sequence, cofusion, colordir, depthdir, haveIntrinsics ? intrinsics : nullptr,
                                configFile, maskDir, outDir, framesGiven, bgRes, bgVoxel > 0 ? bgVoxel : 5.12f / static_cast<float>(bgRes),
-                               objRes, maskFrames, visThresh, volumes);
+                               objRes, maskFrames, visThresh, volumes, view3d);
         }
         emf::Params params;  // reference defaults (config/default.cfg)
         params.frameSize = emf::Size(width, height);
@@ -195,6 +247,8 @@ int main(int argc, char** argv) {
         for (int k = 0; k < objects; ++k) maskDev.emplace_back(params.frameSize);
         emf.enableTimings(true);
         if (!outDir.empty()) emf.setupOutput(false, true);  // apps/EM-Fusion.cpp:112
+        set3dView(emf, params, view3d);
+        std::vector<uint8_t> rendered(3 * P);
 
         double gpuMs = 0;
         int spawned = 0;
@@ -230,6 +284,7 @@ int main(int argc, char** argv) {
             frame.depth = depth.data();
             emf.processFrame(frame);  // reference EMFusion.cpp:70
             gpuMs += emf.lastTimings().total;
+            if (view3d.on) emf.render(rendered.data());  // apps/EM-Fusion.cpp:156: the rendering and the 3D view
             if (autonomous)
                 for (int id : emf.lastCreatedObjects()) spawned += id >= 0;
         }

@@ -32,7 +32,14 @@ def main():
     ap.add_argument("--ignore-person", action="store_true",
                     help="Params.ignore_person of config/tum.cfg: person objects stay out of renderings and meshes")
     ap.add_argument("--masks", help="directory with Mask%%04d.plk files of the reference's preprocessing")
-    ap.add_argument("--out", default="emfusion_out")
+    ap.add_argument("--out", default=None, help="results directory (default emfusion_out)")
+    ap.add_argument("--3d-vis", dest="vis3d", action="store_true",
+                    help="the reference's 3D view: every frame also seen from a viewer 1 m behind the origin at "
+                         "1024 x 768, written to OUT/mesh_vis_out/%%04d.png (needs --out)")
+    ap.add_argument("--3d-vis-eye", dest="vis3d_eye", nargs=3, type=float, metavar=("X", "Y", "Z"),
+                    help="place the 3D viewer at this world point instead (with --3d-vis-target)")
+    ap.add_argument("--3d-vis-target", dest="vis3d_target", nargs=3, type=float, metavar=("X", "Y", "Z"),
+                    default=(0.0, 0.0, 0.0), help="the world point the 3D viewer looks at (default the origin)")
     ap.add_argument("--frames", type=int, default=0, help="0 = all")
     ap.add_argument("--bg-res", type=int, default=512)
     ap.add_argument("--bg-voxel", type=float, default=0.01)
@@ -41,6 +48,10 @@ def main():
     ap.add_argument("--visibility-thresh", type=int, default=0, help="0 = 1600 scaled by the image area")
     ap.add_argument("--mask-frames", type=int, default=30, help="Mask R-CNN every n-th frame (maskRCNNFrames)")
     args = ap.parse_args()
+    if args.vis3d and args.out is None:  # (before the device is opened)
+        ap.error("--3d-vis writes OUT/mesh_vis_out/ and needs --out")
+    if args.vis3d_eye and not args.vis3d:
+        ap.error("--3d-vis-eye needs --3d-vis")
 
     import torch  # noqa: F401  (one HIP runtime, see bench.py)
     from emfusion_amd import pipeline, readers
@@ -68,6 +79,11 @@ def main():
     fus.set_preprocess(True)
     fus.set_cleanup(True)
     fus.setup_output(False, args.volumes)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
+    if args.vis3d:  # the reference's window (apps/EM-Fusion.cpp:118-131), or a viewer placed with look_at
+        R3, t3, K3, size3 = pipeline.default_3d_view(prm)
+        if args.vis3d_eye:
+            R3, t3 = pipeline.look_at(args.vis3d_eye, args.vis3d_target)
+        fus.set_3d_view(R3, t3, K3, size3)
     eye, zero = np.eye(3, dtype=np.float32).reshape(-1), np.zeros(3, np.float32)
     t0 = time.time()
     for f in range(n):
@@ -87,12 +103,14 @@ def main():
             fus.set_tracking(camera=True, objects=True)  # frame 0 defines the world frame
         fus.process_frame(image_view(d), eye, zero, {}, {}, False)
         fus.synchronize()
+        if args.vis3d:
+            fus.render()  # apps/EM-Fusion.cpp:156: the rendering and, logged, the 3D view
         if f % 50 == 0:
             r = fus.track_result(0) if f else None
             print(f"frame {f}/{n}: objects {sorted(fus.visible_objects())}"
                   + (f", camera LM steps {r['iterations']} ({r['accepted']} accepted)" if r else ""),
                   flush=True)
-    out = Path(args.out)
+    out = Path(args.out or "emfusion_out")
     out.mkdir(parents=True, exist_ok=True)
     fus.write_results(out, volumes=args.volumes)
     print(f"{n} frames in {time.time() - t0:.1f} s (incl. PNG decoding on the host); results in {out}/")

@@ -167,6 +167,7 @@ EMFusion::~EMFusion() {
     if (trackStatesHost) (void)hipHostFree(trackStatesHost);
     if (trackWatch) (void)hipHostFree(trackWatch);
     if (lifecycleHost) (void)hipHostFree(lifecycleHost);
+    if (viewPosesHost) (void)hipHostFree(viewPosesHost);
 }
 
 void EMFusion::reset() {

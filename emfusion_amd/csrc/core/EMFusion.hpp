@@ -217,6 +217,24 @@ public:
     void render(uint8_t* rgb);
     const std::array<uint8_t, 768>& getColorMap() const { return colorMap; }
     /**
+     * Free-viewpoint view of the whole map (the reference's --3d-vis view, EMFusion.cpp:162-231, ray-cast from the
+     * viewer instead of meshed): the background and every live object at its current pose, composited and
+     * Phong-shaded as render() does for the tracked camera (ignore_person hides the same objects), light at the
+     * viewer.  viewerPose: viewer -> world (OpenCV camera: +z forward, +y down); K: the viewer's intrinsics.
+     * Host outputs: rgb = size.area() x 3 bytes (required), raylengths (f32) and seg (u8) may be NULL.  Ordered
+     * after every write of the last frame; reads the volumes only (one launch, emf_hip_renderView) and touches no
+     * image, statistic or log of the frame path.  Black / zeros before the first frame.  Not on the sharded path.
+     */
+    void renderView(const Affine3f& viewerPose, const float K[9], Size size, uint8_t* rgb, float* raylengths = nullptr,
+                    uint8_t* seg = nullptr);
+    /**
+     * The logged 3D view (reference --3d-vis): from now on render() also renders this view and, with the log on
+     * (setupOutput), keeps it as frame frameCount - 1's PNG; writeResults() then writes <dir>/mesh_vis_out/%04d.png
+     * (EMFusion.cpp:1018-1025).  clear3dView() turns it off (no mesh_vis_out/ unless it was set).
+     */
+    void set3dView(const Affine3f& viewerPose, const float K[9], Size size);
+    void clear3dView() { view3d = false; }
+    /**
      * Multi-GPU: the depth image enters the node on ONE rank.  With a root >= 0 every frame starts
      * with a broadcast of the depth buffer handed to processFrame (source on `root`, destination on
      * the other ranks: same size and pitch everywhere) over the communicator -- the per-frame
@@ -407,11 +425,25 @@ private:
     std::map<int, std::map<int, Vec3f>> obj_pose_offsets;  // id -> frame -> centre shift of resize()
     std::array<uint8_t, 768> colorMap = io::randomColors();
     DeviceImage<uint8_t, 3> image;  // rendering
+    // ---- free-viewpoint view (EMFusionView.cpp) ----
+    emf_pose_t* viewPosesHost = nullptr;  // pinned, EMF_MAX_MODELS viewer -> volume poses
+    DeviceBuffer viewPosesDev;
+    DeviceBuffer viewTableDev;  // per-volume path: the host table uploaded for the view (no device table there)
+    DeviceImage<uint8_t, 3> viewImage;
+    DeviceImage<float> viewRay;
+    DeviceImage<uint8_t> viewSeg;
+    bool view3d = false;  // set3dView: render() renders (and logs) this view too
+    Affine3f view3dPose;
+    float view3dK[9] = {};
+    Size view3dSize;
+    std::vector<uint8_t> view3dRgb;
+    void render3dView();  // render()'s part: the 3D view of set3dView, logged under frameCount - 1
     std::map<int, Mesh> meshes;                            // id -> last mesh (deleted objects keep theirs)
     bool expVols = false;                                  // setupOutput: keep / dump volumes too
     // ---- per-frame debug images of the reference's saveOutput mode, kept as encoded PNGs ----
     bool saveOutput = false;
     using ImageLog = std::map<int, std::vector<uint8_t>>;  // frame -> PNG bytes
+    ImageLog meshVis;  // the 3D view of each rendered frame (mesh_vis_out/, set3dView)
     ImageLog renderings, bg_assocWeight_preTrack, bg_assocWeight_postTrack, bg_huberWeights, bg_trackWeights;
     std::map<int, ImageLog> obj_assocWeights_preTrack, obj_assocWeights_postTrack, obj_huberWeights, obj_trackWeights,
         obj_fgProbs;                                       // id -> frame -> PNG bytes

@@ -37,6 +37,7 @@ void EMFusion::writeResults(const std::string& dir, bool volumes) {
     // writeRenderings / writeAssocs / writeHuberWeights / writeTrackWeights / writeFgProbs (EMFusion.cpp:1009-1145):
     // directories are created whether or not the log holds anything, like the reference's
     io::writeImageLog(dir + "/output", renderings);
+    if (view3d || !meshVis.empty()) io::writeImageLog(dir + "/mesh_vis_out", meshVis);  // writeMeshVis, EMFusion.cpp:1018-1025
     io::writeImageLog(dir + "/assoc_weights/bg/preTrack", bg_assocWeight_preTrack);
     io::writeImageLog(dir + "/assoc_weights/bg/postTrack", bg_assocWeight_postTrack);
     for (const auto& o : obj_assocWeights_preTrack)
@@ -124,6 +125,7 @@ void EMFusion::render(uint8_t* rgb) {
     main.waitForCompletion();
     if (saveOutput)  // `rendered.copyTo ( renderings[frameCount-1] )`, EMFusion.cpp:158-160
         renderings[frameCount - 1] = io::encodePng(rgb, params.frameSize.width, params.frameSize.height, 3);
+    render3dView();  // the viz window's view (EMFusion.cpp:162-231), when set3dView turned it on
 }
 
 // ---- per-frame debug images (reference saveOutput mode) ---------------------------------------------------

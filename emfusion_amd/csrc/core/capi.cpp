@@ -500,6 +500,32 @@ int emf_fusion_render(emf_fusion_t* h, uint8_t* rgb, uint8_t* color_map) {
     });
 }
 
+int emf_fusion_render_view(emf_fusion_t* h, const float R[9], const float t[3], const float K[9], int32_t width,
+                           int32_t height, uint8_t* rgb, float* raylengths, uint8_t* seg) {
+    REQ(h);
+    REQ(R);
+    REQ(t);
+    REQ(K);
+    REQ(rgb);
+    return guarded([&] {
+        h->impl->renderView(Affine3f(m33(R), Vec3f(t[0], t[1], t[2])), K, Size(width, height), rgb, raylengths, seg);
+    });
+}
+
+int emf_fusion_set_3d_view(emf_fusion_t* h, const float R[9], const float t[3], const float K[9], int32_t width,
+                           int32_t height) {
+    REQ(h);
+    REQ(R);
+    REQ(t);
+    REQ(K);
+    return guarded([&] { h->impl->set3dView(Affine3f(m33(R), Vec3f(t[0], t[1], t[2])), K, Size(width, height)); });
+}
+
+int emf_fusion_clear_3d_view(emf_fusion_t* h) {
+    REQ(h);
+    return guarded([&] { h->impl->clear3dView(); });
+}
+
 int emf_fusion_set_depth_broadcast(emf_fusion_t* h, int root) {
     REQ(h);
     return guarded([&] { h->impl->setDepthBroadcastRoot(root); });

@@ -641,6 +641,14 @@ def object_extent_stats(points, mask, R, t, tsdf, weights, fg_mask, voxel_size, 
     return int(raw.view(np.uint32)[0]), raw[1:4].copy(), raw[4:7].copy()
 
 
+def hide_label(segmentation, label, vertices, normals, bg_vertices, bg_normals, stream=None):
+    """ignore_person in EMFusion::render: pixels of `label` become 0 and show the background's vertex / normal."""
+    check("emf_hip_hideLabel",
+          _L.emf_hip_hideLabel(C.byref(image_view(segmentation)), int(label), C.byref(image_view(vertices)),
+                               C.byref(image_view(normals)), C.byref(image_view(bg_vertices)),
+                               C.byref(image_view(bg_normals)), _stream(stream)))
+
+
 def render_phong(vertices, normals, segmentation, color_map, image, light=(0.0, 0.0, 0.0), stream=None):
     """renderGPU: Phong-shaded RGB image (H, W, 3) u8 of the composited raycast; color_map (256, 3) u8 host."""
     cm = np.ascontiguousarray(color_map, np.uint8)
@@ -650,6 +658,45 @@ def render_phong(vertices, normals, segmentation, color_map, image, light=(0.0, 
                                  C.byref(image_view(segmentation)), cm.ctypes.data, _f(light, 3),
                                  C.byref(image_view(image)), _stream(stream)))
     return image
+
+
+def upload_poses(poses) -> DeviceArray:
+    """emf_pose_t[n] on the device from [(R, t), ...] (the pose array of render_view)."""
+    arr = _poses(poses)
+    return DeviceArray.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8)[:len(poses) * C.sizeof(_lib.EmfPose)].copy())
+
+
+def hide_mask(labels) -> np.ndarray:
+    """The 32-byte label mask of render_view: bit s (byte s // 8, bit s % 8) hides label s."""
+    m = np.zeros(32, np.uint8)
+    for s in labels:
+        assert 1 <= int(s) <= 255, f"label {s}"
+        m[int(s) >> 3] |= np.uint8(1 << (int(s) & 7))
+    return m
+
+
+def render_view(models_dev, poses_vo, ids, width, height, K, rgb, raylengths=None, segmentation=None, vertices=None,
+                normals=None, color_map=None, light=(0.0, 0.0, 0.0), hide=(), stats=None, stream=None):
+    """emf_hip_renderView: the whole table (slot 0 = background) seen from a viewer in one launch -- raycast, composite
+    (zeroed diff), hide, Phong.  poses_vo: viewer -> volume per slot, [(R, t), ...] or upload_poses()'s array.
+    ids: the labels of slots 1.. .  rgb (H, W, 3) u8 is required; the other outputs may be None."""
+    if not isinstance(poses_vo, DeviceArray):
+        poses_vo = upload_poses(poses_vo)
+    n = poses_vo.nbytes // C.sizeof(_lib.EmfPose)
+    ids_arr = (C.c_int32 * max(n - 1, 1))(*[int(i) for i in ids]) if n > 1 else None
+    assert n <= 1 or len(ids) == n - 1, "one label per object slot"
+    cm = np.ascontiguousarray(np.zeros((256, 3), np.uint8) if color_map is None else color_map, np.uint8)
+    assert cm.size == 768
+    hm = hide_mask(hide)
+
+    def view(t):
+        return None if t is None else C.byref(image_view(t))
+
+    check("emf_hip_renderView",
+          _L.emf_hip_renderView(_ptr(models_dev), _ptr(poses_vo), ids_arr, n, int(width), int(height), _f(K, 9),
+                                _f(light, 3), cm.ctypes.data, hm.ctypes.data, view(rgb), view(raylengths),
+                                view(segmentation), view(vertices), view(normals), _ptr(stats), _stream(stream)))
+    return rgb
 
 
 def extract_mesh(tsdf, weights, voxel_size, fg_mask=None, grads=None, stream=None):

@@ -127,6 +127,9 @@ def load() -> C.CDLL:
         "emf_fusion_set_ignore_person": [vp, C.c_int],
         "emf_fusion_object_info": [vp, C.c_int, ip, fp, fp, fp],
         "emf_fusion_render": [vp, C.c_void_p, C.c_void_p],
+        "emf_fusion_render_view": [vp, fp, fp, fp, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+        "emf_fusion_set_3d_view": [vp, fp, fp, fp, C.c_int32, C.c_int32],
+        "emf_fusion_clear_3d_view": [vp],
         "emf_fusion_extract_mesh": [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
         "emf_fusion_copy_mesh": [vp, C.c_void_p, C.c_void_p, C.c_void_p],
         "emf_io_write_mesh": [C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
@@ -195,6 +198,39 @@ def _farr(v, n):
     a = np.ascontiguousarray(np.asarray(v, np.float32).reshape(-1))
     assert a.size == n
     return (C.c_float * n)(*a.tolist())
+
+
+def look_at(eye, target, up=(0.0, -1.0, 0.0)):
+    """Viewer -> world (R, t) of a camera at `eye` looking at `target`, in the OpenCV camera convention (+z forward,
+    +y down, +x right): R's columns are the camera axes in world coordinates, t = eye.  `up` is the world direction
+    that appears up in the image (default -y: the world is an OpenCV camera frame, like the first frame's)."""
+    eye, target, up = (np.asarray(v, np.float64).reshape(3) for v in (eye, target, up))
+    z = target - eye
+    if not np.linalg.norm(z) > 0:
+        raise ValueError("look_at: eye and target coincide")
+    z = z / np.linalg.norm(z)
+    x = np.cross(-up, z)  # image right = down x forward
+    if not np.linalg.norm(x) > 1e-9:
+        raise ValueError("look_at: the viewing direction is parallel to `up`")
+    x = x / np.linalg.norm(x)
+    y = np.cross(z, x)
+    return np.stack([x, y, z], axis=1).astype(np.float32), eye.astype(np.float32)
+
+
+DEFAULT_3D_VIEW_SIZE = (1024, 768)
+
+
+def default_3d_view(params: FusionParams):
+    """The reference's 3D window (apps/EM-Fusion.cpp:118-131): viewer at (0, 0, -1) with the world's axes, 1024 x 768,
+    the frame intrinsics scaled by 1024 / W and 768 / H.  Returns (R, t, K, size)."""
+    w, h = DEFAULT_3D_VIEW_SIZE
+    K = np.array(params.K, np.float32).reshape(3, 3)
+    sx, sy = np.float32(w / params.width), np.float32(h / params.height)
+    K[0, 0] *= sx
+    K[0, 2] *= sx
+    K[1, 1] *= sy
+    K[1, 2] *= sy
+    return np.eye(3, dtype=np.float32), np.array([0, 0, -1], np.float32), K, (w, h)
 
 
 def default_params() -> FusionParams:
@@ -569,6 +605,35 @@ class Fusion:
         cmap = np.empty((256, 3), np.uint8)
         _check("emf_fusion_render", load().emf_fusion_render(self._h, rgb.ctypes.data, cmap.ctypes.data))
         return rgb, cmap
+
+    def _view_args(self, R, t, K, size):
+        K = np.array(self.params.K, np.float32) if K is None else K
+        w, h = (self.params.width, self.params.height) if size is None else (int(size[0]), int(size[1]))
+        return _farr(R, 9), _farr(t, 3), _farr(K, 9), w, h
+
+    def render_view(self, R, t, K=None, size=None):
+        """EMFusion::renderView: the map seen from a free viewpoint -- viewer -> world (R, t) (OpenCV camera, see
+        look_at), intrinsics K (default: the frame's), size (width, height) (default: the frame's).  Returns
+        (rgb (H, W, 3) u8, raylengths (H, W) f32, segmentation (H, W) u8)."""
+        Rc, tc, Kc, w, h = self._view_args(R, t, K, size)
+        rgb = np.empty((h, w, 3), np.uint8)
+        ray = np.empty((h, w), np.float32)
+        seg = np.empty((h, w), np.uint8)
+        _check("emf_fusion_render_view",
+               load().emf_fusion_render_view(self._h, Rc, tc, Kc, w, h, rgb.ctypes.data, ray.ctypes.data,
+                                             seg.ctypes.data))
+        return rgb, ray, seg
+
+    def set_3d_view(self, R=None, t=None, K=None, size=None):
+        """EMFusion::set3dView (the reference's --3d-vis): render() also renders this view, and with setup_output
+        write_results writes mesh_vis_out/%04d.png.  All None: the reference window's default (default_3d_view)."""
+        if R is None and t is None and K is None and size is None:
+            R, t, K, size = default_3d_view(self.params)
+        Rc, tc, Kc, w, h = self._view_args(R, t, K, size)
+        _check("emf_fusion_set_3d_view", load().emf_fusion_set_3d_view(self._h, Rc, tc, Kc, w, h))
+
+    def clear_3d_view(self):
+        _check("emf_fusion_clear_3d_view", load().emf_fusion_clear_3d_view(self._h))
 
     def mesh(self, obj_id: int = 0):
         """TSDF::getMesh / ObjTSDF::getMesh: (vertices (n, 3), normals (n, 3), triangles (m, 4))."""

@@ -160,6 +160,17 @@ int emf_io_write_mesh(const char* filename, uint32_t num_vertices, const float* 
 /* EMFusion::render (EMFusion.cpp:131-160): Phong-shaded RGB view of the models, width*height*3 bytes
  * into host memory; color_map (may be NULL) receives the 256 x RGB label colours. */
 int emf_fusion_render(emf_fusion_t* h, uint8_t* rgb, uint8_t* color_map);
+/* EMFusion::renderView: the map seen from a free viewpoint (the reference's --3d-vis view, ray-cast): viewer -> world
+ * (R row-major, t; OpenCV camera: +z forward, +y down), intrinsics K, width x height.  Host outputs, NULL = not
+ * wanted (rgb is required): rgb width*height*3 bytes, raylengths f32, seg u8.  Ordered after the last frame; changes
+ * nothing of the frame path.  EMF_E_ARG on the sharded path. */
+int emf_fusion_render_view(emf_fusion_t* h, const float R[9], const float t[3], const float K[9], int32_t width,
+                           int32_t height, uint8_t* rgb, float* raylengths, uint8_t* seg);
+/* EMFusion::set3dView: from now on render() also renders this view and, with setup_output's log on, keeps it for
+ * write_results' mesh_vis_out/%04d.png.  emf_fusion_clear_3d_view turns it off. */
+int emf_fusion_set_3d_view(emf_fusion_t* h, const float R[9], const float t[3], const float K[9], int32_t width,
+                           int32_t height);
+int emf_fusion_clear_3d_view(emf_fusion_t* h);
 /* Multi-GPU: broadcast the depth image of every frame from rank `root` (whose process_frame argument
  * is the source; on the other ranks it is the destination and must have the same size and pitch)
  * before anything else runs.  root < 0 (default): every rank is handed the frame itself. */

@@ -460,6 +460,25 @@ int emf_hip_raycastBatched(const emf_model_t* models_dev, const emf_pose_t* pose
                            const float K[9], int useBrickFlags, int bgBandRow0, int bgBandRows,
                            const float* farBounds_dev, const float* voxelSizes_host, uint64_t* stats,
                            emf_stream_t stream);
+/* Free-viewpoint view of a whole model table in ONE launch (the reference's 3D view, EMFusion.cpp:162-231, ray-cast
+ * instead of meshed): per pixel, every model is marched (TSDF.cu:466-601 arithmetic, fgVolMask-gated weights for
+ * objects as in ObjTSDF.cpp:203-216), the hits are composited in table order with EMFusion.cpp:760-794's rule as
+ * emf_hip_compositeRaycast applies it (diff starts at 0: no history), the labels in hideMask are hidden as
+ * emf_hip_hideLabel does, and the result is Phong-shaded as emf_hip_renderPhong does (light at lightPos, viewer
+ * frame).  Reads tsdf / weights / grads / fgVolMask only; writes nothing of the table.  Same bits as that chain.
+ *   poseVO_dev: DEVICE emf_pose_t[nmodels], viewer -> volume of each slot (slot 0: the background)
+ *   ids_host:   HOST int32[nmodels - 1], the labels of slots 1.. (compositeRaycast's ids); NULL if nmodels == 1
+ *   colorMap:   label -> u8 x 3 colour;  hideMask: bit s (byte s / 8, bit s % 8) hides label s, or NULL: none
+ *   rgb:        u8 x 3 width x height, required; raylengths (f32), segmentation (u8), vertices / normals (f32 x 3):
+ *               width x height or NULL (not written).  Pitched images are accepted.
+ *   stats_dev:  NULL or u64[4] accumulating samples / hits / gathered / 0 as the raycast counts them.
+ * 1 <= nmodels <= EMF_MAX_MODELS in one launch (no EMF_MAX_BATCH chunking).  No far bounds, no brick flags; volumes
+ * above 32-bit byte offsets take the 64-bit march. */
+int emf_hip_renderView(const emf_model_t* models_dev, const emf_pose_t* poseVO_dev, const int32_t* ids_host,
+                       int nmodels, int width, int height, const float K[9], const float lightPos[3],
+                       const uint8_t colorMap[768], const uint8_t hideMask[32], const emf_image_t* rgb,
+                       const emf_image_t* raylengths, const emf_image_t* segmentation, const emf_image_t* vertices,
+                       const emf_image_t* normals, uint64_t* stats_dev, emf_stream_t stream);
 /* emf_hip_raycastBatched with the BACKGROUND's rays marched by lanesPerBgRay = 1, 2 or 4 lanes each (march_quad,
  * march_wave.hpp: the lanes of a ray take consecutive samples speculatively; same images, same sample count; measured
  * slower beside the background's integration, hence not the default).  Ignored (1) with brick flags or volumes above
