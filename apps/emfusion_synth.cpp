@@ -3,10 +3,13 @@
 // stream instead of a dataset reader.  Prints frames/s and per-stage GPU milliseconds.
 //
 //   emfusion_synth [--frames N] [--objects K] [--bg-res R] [--obj-res R] [--width W --height H]
-//                  [--materialize-gradients] [--autonomous] [--out DIR]
+//                  [--materialize-gradients] [--autonomous] [--out DIR] [--export-frame-meshes] [--3d-vis]
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
 //                  [--bg-res R] [--bg-voxel M] [--obj-res R] [--volumes] --out DIR
 //   emfusion_synth --dir BASE/ [--colordir colour] [--depthdir depth] [--intrinsics fx fy cx cy] ... --out DIR
+// --export-frame-meshes (needs --out): the reference's per-frame mesh export (apps/EM-Fusion.cpp:240-242) -- every
+// frame ends by meshing the background and every shown object, and writeResults writes them as
+// DIR/frame_meshes/bg/%04d.ply and DIR/frame_meshes/<id>/%04d.ply.
 // --3d-vis (needs --out): the reference's 3D view (apps/EM-Fusion.cpp:118-131) -- every frame is rendered (render())
 // together with the whole map seen from a viewer 1 m behind the world origin at 1024 x 768, and writeResults writes
 // those views as DIR/mesh_vis_out/%04d.png.  --3d-vis-eye x y z --3d-vis-target x y z place the viewer instead
@@ -75,7 +78,7 @@ static void set3dView(emf::EMFusion& emf, const emf::Params& params, const View3
 static int runSequence(const std::string& seq, bool cofusion, const std::string& colordir, const std::string& depthdir,
                        const float* intrinsics, const std::string& configFile, const std::string& masks,
                        const std::string& outDir, int frames, int bgRes, float bgVoxel, int objRes, int maskFrames,
-                       int visibilityThresh, bool volumes, const View3d& view3d) {
+                       int visibilityThresh, bool volumes, const View3d& view3d, bool frameMeshes) {
     std::unique_ptr<emf::TUMRGBDReader> tum;
     std::unique_ptr<emf::ImageReader> dir;
     size_t available = 0;
@@ -127,7 +130,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     }
     emf::EMFusion emf(params);
     if (!masks.empty()) emf.usePreprocMasks(masks);   // apps/EM-Fusion.cpp:115
-    emf.setupOutput(false, volumes);                  // apps/EM-Fusion.cpp:112
+    emf.setupOutput(frameMeshes, volumes);            // apps/EM-Fusion.cpp:112
     set3dView(emf, params, view3d);
     std::vector<uint8_t> rendered(3 * params.frameSize.area());
     const auto t0 = std::chrono::steady_clock::now();
@@ -169,6 +172,7 @@ int main(int argc, char** argv) {
     float bgVoxel = 0.f;
     bool volumes = false;
     View3d view3d;
+    bool frameMeshes = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() { return i + 1 < argc ? std::atoi(argv[++i]) : 0; };
@@ -196,6 +200,7 @@ int main(int argc, char** argv) {
         else if (a == "--autonomous") autonomous = true;
         else if (a == "--out" && i + 1 < argc) outDir = argv[++i];
         else if (a == "--3d-vis") view3d.on = true;
+        else if (a == "--export-frame-meshes") frameMeshes = true;
         else if ((a == "--3d-vis-eye" || a == "--3d-vis-target") && i + 3 < argc) {
             float* dst = a == "--3d-vis-eye" ? view3d.eye : view3d.target;
             for (int k = 0; k < 3; ++k) dst[k] = static_cast<float>(std::atof(argv[++i]));
@@ -210,7 +215,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "emfusion_synth: --3d-vis-eye / --3d-vis-target need --3d-vis\n");
         return 2;
     }
-    if (view3d.on && outDir.empty()) {  // (before any device is touched)
+    if (frameMeshes && outDir.empty()) {  // (before any device is touched)
+        std::fprintf(stderr, "emfusion_synth: --export-frame-meshes writes DIR/frame_meshes/ and needs --out DIR\n");
+        return 2;
+    }
+    if (view3d.on && outDir.empty()) {
         std::fprintf(stderr, "emfusion_synth: --3d-vis writes DIR/mesh_vis_out/ and needs --out DIR\n");
         return 2;
     }
@@ -220,7 +229,7 @@ int main(int argc, char** argv) {
             const bool cofusion = !dataDir.empty();
             return runSequence(cofusion ? dataDir : sequence, cofusion, colordir, depthdir, haveIntrinsics ? intrinsics : nullptr,
                                configFile, maskDir, outDir, framesGiven, bgRes, bgVoxel > 0 ? bgVoxel : 5.12f / static_cast<float>(bgRes),
-                               objRes, maskFrames, visThresh, volumes, view3d);
+                               objRes, maskFrames, visThresh, volumes, view3d, frameMeshes);
         }
         emf::Params params;  // reference defaults (config/default.cfg)
         params.frameSize = emf::Size(width, height);
@@ -246,7 +255,7 @@ int main(int argc, char** argv) {
         std::vector<emf::DeviceImage<uint8_t>> maskDev;
         for (int k = 0; k < objects; ++k) maskDev.emplace_back(params.frameSize);
         emf.enableTimings(true);
-        if (!outDir.empty()) emf.setupOutput(false, true);  // apps/EM-Fusion.cpp:112
+        if (!outDir.empty()) emf.setupOutput(frameMeshes, true);  // apps/EM-Fusion.cpp:112
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);
 

@@ -40,6 +40,10 @@ def main():
                     help="place the 3D viewer at this world point instead (with --3d-vis-target)")
     ap.add_argument("--3d-vis-target", dest="vis3d_target", nargs=3, type=float, metavar=("X", "Y", "Z"),
                     default=(0.0, 0.0, 0.0), help="the world point the 3D viewer looks at (default the origin)")
+    ap.add_argument("--export-frame-meshes", dest="frame_meshes", action="store_true",
+                    help="the reference's per-frame mesh export: the background and every shown object meshed at the "
+                         "end of every frame, written to OUT/frame_meshes/bg/%%04d.ply and OUT/frame_meshes/<id>/ "
+                         "(needs --out)")
     ap.add_argument("--frames", type=int, default=0, help="0 = all")
     ap.add_argument("--bg-res", type=int, default=512)
     ap.add_argument("--bg-voxel", type=float, default=0.01)
@@ -50,6 +54,8 @@ def main():
     args = ap.parse_args()
     if args.vis3d and args.out is None:  # (before the device is opened)
         ap.error("--3d-vis writes OUT/mesh_vis_out/ and needs --out")
+    if args.frame_meshes and args.out is None:
+        ap.error("--export-frame-meshes writes OUT/frame_meshes/ and needs --out")
     if args.vis3d_eye and not args.vis3d:
         ap.error("--3d-vis-eye needs --3d-vis")
 
@@ -78,7 +84,7 @@ def main():
     fus.set_ignore_person(args.ignore_person)
     fus.set_preprocess(True)
     fus.set_cleanup(True)
-    fus.setup_output(False, args.volumes)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
+    fus.setup_output(args.frame_meshes, args.volumes)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
     if args.vis3d:  # the reference's window (apps/EM-Fusion.cpp:118-131), or a viewer placed with look_at
         R3, t3, K3, size3 = pipeline.default_3d_view(prm)
         if args.vis3d_eye:

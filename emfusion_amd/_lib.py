@@ -124,6 +124,9 @@ SIGNATURES = {
     "emf_hip_renderPhong": [_IMG, _IMG, _IMG, C.c_void_p, _F9, _IMG, _STREAM],
     "emf_hip_meshCount": [_FP, _FP, _FP, _I3, _FP, _FP, _STREAM],
     "emf_hip_meshEmit": [_FP, _FP, _FP, _FP, _I3, C.c_float, _FP, _FP, _FP, _FP, _STREAM],
+    "emf_hip_meshScratchBytesBatched": [_I3, C.c_int],
+    "emf_hip_meshCountBatched": [_FP, _I3, C.c_int, _FP, _FP, _FP, _STREAM],
+    "emf_hip_meshEmitBatched": [_FP, _I3, C.c_int, _FP, _FP, _FP, _FP, _STREAM],
     "emf_hip_trackScratchBytes": [C.c_int, C.c_int],
     "emf_hip_trackPrepare": [_FP, _FP, C.c_int, C.c_float, _STREAM],
     "emf_hip_trackIterate": [_FP, _FP, C.c_int, _IMG, C.c_void_p, _FP, C.c_size_t,
@@ -244,6 +247,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.emf_hip_unseenTileBytes.restype = C.c_size_t
     lib.emf_hip_pointStatsScratchBytes.restype = C.c_size_t
     lib.emf_hip_meshScratchBytes.restype = C.c_size_t
+    lib.emf_hip_meshScratchBytesBatched.restype = C.c_size_t
     lib.emf_hip_integrateCullScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateDirtyMapBytes.restype = C.c_size_t
     lib.emf_hip_signMapBytes.restype = C.c_size_t

@@ -168,6 +168,8 @@ EMFusion::~EMFusion() {
     if (trackWatch) (void)hipHostFree(trackWatch);
     if (lifecycleHost) (void)hipHostFree(lifecycleHost);
     if (viewPosesHost) (void)hipHostFree(viewPosesHost);
+    if (meshHost) (void)hipHostFree(meshHost);
+    if (meshStage) (void)hipHostFree(meshStage);
 }
 
 void EMFusion::reset() {
@@ -664,6 +666,7 @@ void EMFusion::runSchedule(const emf_image_t& depthDev, const FrameInputs& in) {
         timings.masks = ms(kIntegrate, kMasks);
         timings.total = ms(kStart, kMasks);
     }
+    if (expFrameMeshes_) storeFrameMeshes();  // EMFusion.cpp:110-125, after cleanUpObjs and outside the timings
     ++frameCount;
 }
 

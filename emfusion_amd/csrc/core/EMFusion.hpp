@@ -167,8 +167,11 @@ public:
     /**
      * Reference EMFusion::setupOutput (EMFusion.cpp:243-247): turns the log on (saveOutput) and
      * chooses whether the volumes are exported too.  With exp_vols the volumes of objects deleted
-     * during the run are kept on the host like their mesh (EMFusion.cpp:966-973).  The per-frame
-     * mesh export of exp_frame_meshes belongs to the viz path and is not kept.
+     * during the run are kept on the host like their mesh (EMFusion.cpp:966-973).  With exp_frame_meshes every
+     * frame ends (after cleanUpObjs) by meshing the background and every live object not hidden by ignore_person
+     * (EMFusion.cpp:110-125) in one pass (extractMeshes); the meshes are kept on the host under the frame's number and
+     * writeResults() writes them as frame_meshes/bg/%04d.ply and frame_meshes/<id>/%04d.ply (EMFusion.cpp:1158-1185).
+     * Not on the sharded path: refused there.
      * From here on every frame also keeps the reference's per-frame debug images (as PNG bytes, not as raw
      * images): association weights before and after tracking (storeAssocs, EMFusion.cpp:79-91, 307-320), Huber
      * and combined tracking weights of the stages that ran (EMFusion.cpp:110-118; TSDF.cpp:346-354), the
@@ -178,7 +181,9 @@ public:
      * and a synchronisation per image: a debugging mode, as in the reference.  One-rank path only.
      */
     void setupOutput(bool expFrameMeshes, bool exp_vols) {
-        (void)expFrameMeshes;
+        if (expFrameMeshes && sharded)  // like renderView: remote objects are not on this rank
+            throw HipError("EMFusion::setupOutput: per-frame meshes are not available on the sharded path", EMF_E_ARG);
+        expFrameMeshes_ = expFrameMeshes;
         poseLog = true;
         saveOutput = true;
         expVols = exp_vols;
@@ -244,6 +249,13 @@ public:
     void setDepthBroadcastRoot(int root) { depthRoot = root; }
     /** getMesh() of the background (id 0) or of an object held by this rank. */
     Mesh getMesh(int id);
+    /**
+     * getMesh() of each listed model (0 = background, else a live object id), in list order, in one pass over the
+     * current model table: one count launch, one read-back of the counts (the only wait before the emit), one emit
+     * launch into a pooled device arena grown when needed, three device-to-host copies.  Same bytes as getMesh().
+     * Ordered after every write of the last frame.  On the sharded path: this rank's models.
+     */
+    std::vector<Mesh> extractMeshes(const std::vector<int>& ids);
 
     /**
      * Create an object volume centred at `center` (world) with edge length `volSize` metres --
@@ -439,6 +451,15 @@ private:
     std::vector<uint8_t> view3dRgb;
     void render3dView();  // render()'s part: the 3D view of set3dView, logged under frameCount - 1
     std::map<int, Mesh> meshes;                            // id -> last mesh (deleted objects keep theirs)
+    // ---- per-frame meshes (setupOutput's exp_frame_meshes, EMFusionCapture.cpp) ----
+    bool expFrameMeshes_ = false;
+    std::map<int, Mesh> frame_meshes;                      // frame -> background mesh
+    std::map<int, std::map<int, Mesh>> frame_obj_meshes;   // id -> frame -> mesh
+    void storeFrameMeshes();                               // the end of a frame with exp_frame_meshes
+    DeviceBuffer meshTableDev, meshCountsDev, meshScratch, meshArena;  // extractMeshes' pooled buffers
+    void* meshHost = nullptr;       // pinned: EMF_MAX_MODELS emf_model_t, then the counts and bases read back
+    void* meshStage = nullptr;      // pinned staging of the meshes' bytes (grown when needed)
+    size_t meshStageBytes = 0;
     bool expVols = false;                                  // setupOutput: keep / dump volumes too
     // ---- per-frame debug images of the reference's saveOutput mode, kept as encoded PNGs ----
     bool saveOutput = false;

@@ -7,6 +7,8 @@
 
 #include <cerrno>
 #include <cmath>
+#include <cstdio>
+#include <cstring>
 #include <stdexcept>
 
 namespace emf {
@@ -30,10 +32,25 @@ void EMFusion::writeResults(const std::string& dir, bool volumes) {
     // writeMeshes (EMFusion.cpp:1147-1156) runs whether or not volumes are exported: the background,
     // the live objects, and the objects that were deleted while the log was on (their last mesh,
     // EMFusion.cpp:966)
-    io::writeMesh(dir + "/mesh_bg.ply", background.getMesh());
-    for (auto& obj : objects)
-        if (!(ignorePerson && isPerson(obj))) meshes[obj.getID()] = obj.getMesh();
+    std::vector<int> ids{0};
+    for (const auto& obj : objects)
+        if (!(ignorePerson && isPerson(obj))) ids.push_back(obj.getID());
+    std::vector<Mesh> live = extractMeshes(ids);  // one pass over the table, the bytes getMesh() gives
+    io::writeMesh(dir + "/mesh_bg.ply", live[0]);
+    for (size_t k = 1; k < ids.size(); ++k) meshes[ids[k]] = std::move(live[k]);
     for (const auto& m : meshes) io::writeMesh(dir + "/mesh_" + std::to_string(m.first) + ".ply", m.second);
+    if (expFrameMeshes_) {  // writeFrameMeshes (EMFusion.cpp:1158-1185); the reference creates frame_meshes/ always
+        auto writeAll = [](const std::string& d, const std::map<int, Mesh>& log) {
+            io::createDirectories(d);
+            char name[32];
+            for (const auto& fm : log) {
+                std::snprintf(name, sizeof(name), "/%04d.ply", fm.first);
+                io::writeMesh(d + name, fm.second);
+            }
+        };
+        writeAll(dir + "/frame_meshes/bg", frame_meshes);
+        for (const auto& o : frame_obj_meshes) writeAll(dir + "/frame_meshes/" + std::to_string(o.first), o.second);
+    }
     // writeRenderings / writeAssocs / writeHuberWeights / writeTrackWeights / writeFgProbs (EMFusion.cpp:1009-1145):
     // directories are created whether or not the log holds anything, like the reference's
     io::writeImageLog(dir + "/output", renderings);
@@ -206,6 +223,99 @@ void EMFusion::storeFgProbs() {
                  "getVolumeVals(fgProbs)");
         obj_fgProbs[obj.getID()][frameCount] = pngOf(logScratch.as<float>(), out.pitch);
     }
+}
+
+// ---- meshes of many models at once (emf_hip_meshCountBatched / emf_hip_meshEmitBatched) --------------------
+
+std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
+    const int n = static_cast<int>(ids.size());
+    std::vector<Mesh> out(ids.size());
+    if (n == 0) return out;
+    if (n > EMF_MAX_MODELS) throw HipError("EMFusion::extractMeshes: " + std::to_string(n) + " models", EMF_E_LIMIT);
+    if (!meshHost)
+        hipCheck(hipHostMalloc(&meshHost, EMF_MAX_MODELS * sizeof(emf_model_t) + EMF_MAX_MODELS * sizeof(emf_mesh_counts_t) +
+                                              2 * (EMF_MAX_MODELS + 1) * sizeof(uint64_t),
+                               hipHostMallocDefault),
+                 "hipHostMalloc(mesh table)");
+    emf_model_t* table = static_cast<emf_model_t*>(meshHost);
+    auto* counts = reinterpret_cast<emf_mesh_counts_t*>(table + EMF_MAX_MODELS);
+    auto* bases = reinterpret_cast<uint64_t*>(counts + EMF_MAX_MODELS);
+    std::vector<int32_t> res(3 * ids.size());
+    for (int k = 0; k < n; ++k) {  // the volumes' current copies (describe() follows the background's flips)
+        const int id = ids[k];
+        emf_model_t& m = table[k];
+        m = emf_model_t{};
+        if (id == 0) {
+            background.describe(m);
+        } else {
+            const ObjTSDF* obj = getObject(id);
+            if (!obj) throw HipError("EMFusion::extractMeshes: no object " + std::to_string(id) + " on this rank", EMF_E_ARG);
+            obj->describe(m);
+        }
+        std::copy(m.res, m.res + 3, res.begin() + 3 * k);
+    }
+    // ordered after every write of the last frame, as renderView is
+    if (bgInFlight) joinBackground();
+    main.waitFor(aux);
+    for (auto& kv : streams) main.waitFor(kv.second);
+    if (meshTableDev.empty()) meshTableDev = DeviceBuffer(EMF_MAX_MODELS * sizeof(emf_model_t));
+    if (meshCountsDev.empty())
+        meshCountsDev = DeviceBuffer(EMF_MAX_MODELS * sizeof(emf_mesh_counts_t) + 2 * (EMF_MAX_MODELS + 1) * sizeof(uint64_t));
+    const size_t scratchBytes = emf_hip_meshScratchBytesBatched(res.data(), n);
+    if (scratchBytes == 0) throw HipError("EMFusion::extractMeshes: bad volume resolution", EMF_E_SHAPE);
+    if (meshScratch.bytes() < scratchBytes) meshScratch = DeviceBuffer(scratchBytes);
+    hipCheck(hipMemcpyAsync(meshTableDev.data(), table, n * sizeof(emf_model_t), hipMemcpyHostToDevice, main.get()),
+             "mesh table upload");
+    auto* countsDev = meshCountsDev.as<emf_mesh_counts_t>();
+    auto* basesDev = reinterpret_cast<uint64_t*>(countsDev + EMF_MAX_MODELS);
+    emfCheck(emf_hip_meshCountBatched(meshTableDev.as<emf_model_t>(), res.data(), n, meshScratch.data(), countsDev, basesDev,
+                                      main.abi()),
+             "meshCountBatched");
+    hipCheck(hipMemcpyAsync(counts, countsDev, meshCountsDev.bytes(), hipMemcpyDeviceToHost, main.get()), "mesh counts D2H");
+    main.waitForCompletion();  // the one wait before the emit: the outputs' sizes
+    const uint64_t nv = bases[2 * n], nt = bases[2 * n + 1];
+    if (nv == 0) return out;
+    const size_t vb = 3 * sizeof(float) * nv, tb = 4 * sizeof(int32_t) * std::max<uint64_t>(nt, 1);
+    if (meshArena.bytes() < 2 * vb + tb) meshArena = DeviceBuffer(2 * vb + tb);
+    float* vDev = meshArena.as<float>();
+    float* nDev = vDev + 3 * nv;
+    int32_t* tDev = reinterpret_cast<int32_t*>(nDev + 3 * nv);
+    emfCheck(emf_hip_meshEmitBatched(meshTableDev.as<emf_model_t>(), res.data(), n, meshScratch.data(), vDev, nDev, tDev,
+                                     main.abi()),
+             "meshEmitBatched");
+    if (meshStageBytes < 2 * vb + tb) {
+        if (meshStage) hipCheck(hipHostFree(meshStage), "hipHostFree(mesh staging)");
+        meshStage = nullptr;
+        meshStageBytes = 0;
+        hipCheck(hipHostMalloc(&meshStage, 2 * vb + tb, hipHostMallocDefault), "hipHostMalloc(mesh staging)");
+        meshStageBytes = 2 * vb + tb;
+    }
+    float* vHost = static_cast<float*>(meshStage);
+    float* nHost = vHost + 3 * nv;
+    int32_t* tHost = reinterpret_cast<int32_t*>(nHost + 3 * nv);
+    hipCheck(hipMemcpyAsync(vHost, vDev, vb, hipMemcpyDeviceToHost, main.get()), "mesh vertices D2H");
+    hipCheck(hipMemcpyAsync(nHost, nDev, vb, hipMemcpyDeviceToHost, main.get()), "mesh normals D2H");
+    if (nt) hipCheck(hipMemcpyAsync(tHost, tDev, 4 * sizeof(int32_t) * nt, hipMemcpyDeviceToHost, main.get()), "mesh triangles D2H");
+    main.waitForCompletion();
+    for (int k = 0; k < n; ++k) {  // model k's slice is its own mesh (local triangle indices)
+        const size_t v0 = bases[2 * k], t0 = bases[2 * k + 1];
+        Mesh& m = out[k];
+        m.cloud.assign(vHost + 3 * v0, vHost + 3 * (v0 + counts[k].vertices));
+        m.normals.assign(nHost + 3 * v0, nHost + 3 * (v0 + counts[k].vertices));
+        m.polygons.assign(tHost + 4 * t0, tHost + 4 * (t0 + counts[k].triangles));
+    }
+    return out;
+}
+
+// EMFusion.cpp:110-125 (exp_frame_meshes): the background and every live object not hidden by ignore_person, meshed
+// from the current table at the end of the frame and kept under the frame's number
+void EMFusion::storeFrameMeshes() {
+    std::vector<int> ids{0};
+    for (const auto& obj : objects)
+        if (!(ignorePerson && isPerson(obj))) ids.push_back(obj.getID());
+    std::vector<Mesh> all = extractMeshes(ids);
+    frame_meshes[frameCount] = std::move(all[0]);
+    for (size_t k = 1; k < ids.size(); ++k) frame_obj_meshes[ids[k]][frameCount] = std::move(all[k]);
 }
 
 Mesh EMFusion::getMesh(int id) {

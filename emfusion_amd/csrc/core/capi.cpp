@@ -22,6 +22,7 @@ struct emf_fusion {
     std::vector<emf_image_t> queuedMasks, queuedInstances;
     std::vector<std::vector<double>> queuedScores;
     emf::Mesh mesh;  // result of the last emf_fusion_extract_mesh
+    std::vector<emf::Mesh> meshList;  // result of the last emf_fusion_extract_meshes
 };
 struct emf_synth {
     std::unique_ptr<SyntheticScene> impl;
@@ -471,6 +472,34 @@ int emf_fusion_copy_mesh(emf_fusion_t* h, float* vertices, float* normals, int32
         if (vertices) std::copy(m.cloud.begin(), m.cloud.end(), vertices);
         if (normals) std::copy(m.normals.begin(), m.normals.end(), normals);
         if (triangles) std::copy(m.polygons.begin(), m.polygons.end(), triangles);
+    });
+}
+
+int emf_fusion_extract_meshes(emf_fusion_t* h, const int32_t* ids, int n, uint32_t* counts) {
+    REQ(h);
+    REQ(ids);
+    REQ(counts);
+    if (n < 1 || n > EMF_MAX_MODELS) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_extract_meshes: %d models (1 .. %d)", n, EMF_MAX_MODELS);
+        return EMF_E_LIMIT;
+    }
+    return guarded([&] {
+        h->meshList = h->impl->extractMeshes(std::vector<int>(ids, ids + n));
+        for (int k = 0; k < n; ++k) {
+            counts[2 * k] = static_cast<uint32_t>(h->meshList[k].vertices());
+            counts[2 * k + 1] = static_cast<uint32_t>(h->meshList[k].triangles());
+        }
+    });
+}
+
+int emf_fusion_copy_meshes(emf_fusion_t* h, float* vertices, float* normals, int32_t* triangles) {
+    REQ(h);
+    return guarded([&] {
+        for (const emf::Mesh& m : h->meshList) {
+            if (vertices) vertices = std::copy(m.cloud.begin(), m.cloud.end(), vertices);
+            if (normals) normals = std::copy(m.normals.begin(), m.normals.end(), normals);
+            if (triangles) triangles = std::copy(m.polygons.begin(), m.polygons.end(), triangles);
+        }
     });
 }
 

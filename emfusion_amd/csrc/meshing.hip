@@ -21,7 +21,12 @@
 //   k_mesh_emit   a fixed grid walks list[]: classify the chunk again, scan inside the workgroup (wave
 //                 shuffles + LDS) on top of blockSums[g / 8] + the chunk totals before it, and write
 //                 vertices, normals and triangles where the reference puts them
-// so the volume is streamed once (count) plus the surface chunks once more (emit; a workgroup per
+// A launch covers a TABLE of volumes (emf_hip_mesh*Batched; the level-1 entries are its one-volume case): model m
+// owns a contiguous range of counting workgroups (its own chunks-per-workgroup choice and XCD banding inside it),
+// of per-workgroup sums and of chunks; the scan restarts at every model and yields its counts and 64-bit bases in
+// the concatenated outputs, so model m's slice is exactly the mesh of that volume alone.  The ranges travel in the
+// kernel arguments (MeshArgs), the volumes' pointers in the device model table.
+// Each volume is streamed once (count) plus its surface chunks once more (emit; a workgroup per
 // chunk that returns when its total is 0 measured 0.57 ms at 512^3 for launching 0.5 M workgroups
 // alone).  Counting workgroups are mapped so that each XCD walks a contiguous eighth of the volume
 // (its own z-slabs stay in its L2).
@@ -45,7 +50,7 @@ constexpr int kMcChunk = kMcWaveCubes * (kMcBlock / 64);       // 252 positions 
 // otherwise be 260 workgroups of 32 serial steps: 0.020 -> 0.055 ms)
 constexpr int kMcChunksLarge = 32, kMcChunksSmall = 8;
 constexpr size_t kMcLargeVoxels = size_t(1) << 24;
-inline int chunks_for(size_t nvox) { return nvox >= kMcLargeVoxels ? kMcChunksLarge : kMcChunksSmall; }
+__host__ __device__ inline int chunks_for(size_t nvox) { return nvox >= kMcLargeVoxels ? kMcChunksLarge : kMcChunksSmall; }
 constexpr unsigned kXcds = 8;
 
 // Workgroups are dealt round-robin to the 8 XCDs, each with its own 4 MiB L2.  A cube needs the
@@ -53,29 +58,62 @@ constexpr unsigned kXcds = 8;
 // tsdf + weights per 512^2 plane, which does not survive in an L2 that streams the whole plane.
 // Each XCD therefore takes the same BAND of every plane (an eighth of its rows) and walks z: the data
 // it has to keep between the two uses is an eighth of a plane.  `wpp` = workgroups per plane.
-__device__ __forceinline__ unsigned logical_block(unsigned nblocks, unsigned wpp) {
+__device__ __forceinline__ unsigned logical_block(unsigned block, unsigned nblocks, unsigned wpp) {
     const unsigned band = (wpp + kXcds - 1) / kXcds;
-    const unsigned k = blockIdx.x % kXcds, i = blockIdx.x / kXcds;
+    const unsigned k = block % kXcds, i = block / kXcds;  // (a model's range starts at a multiple of kXcds)
     const unsigned col = k * band + i % band;
     const unsigned b = (i / band) * wpp + col;
     return col < wpp ? b : nblocks;  // nblocks = nothing to do
 }
 
+// One launch = a table of n volumes.  Per model m (host-computed, see plan()): counting workgroups
+// [launchStart[m], launchStart[m + 1]) of the grid, per-workgroup sums blockSums[blockBase[m] ..] and chunks
+// chunkTot[chunkBase[m] ..]; chunk ids in list[] are global (chunkBase[m] + the model's own chunk index).
 struct MeshArgs {
-    MeshSource src;
-    const float* grads;  // N^3 x 3 gradient volume, or nullptr: forward differences on the fly
-    uint2* blockSums;    // per counting workgroup (vertices, triangles); after k_mesh_scan their exclusive scan
+    const emf_model_t* models;  // device table (tsdf, weights, grads, fgVolMask, res, voxelSize), or nullptr:
+    MeshSource one;             // the single volume of a level-1 call (kTable = false), with
+    const float* oneGrads;      // its N^3 x 3 gradient volume or nullptr (forward differences on the fly)
+    uint2* blockSums;    // per counting workgroup (vertices, triangles); after k_mesh_scan their exclusive scan per model
     unsigned* chunkTot;  // per chunk: vertices | triangles << 16 (at most 3072 and 1280)
     unsigned* list;      // ids of the chunks with a non-zero total, in no particular order
     unsigned* listCount;
-    emf_mesh_counts_t* counts;
+    unsigned long long* bases;  // 2 per model: its first vertex / triangle in the concatenated outputs
+    emf_mesh_counts_t* counts;  // n, written by k_mesh_scan
+    unsigned long long* basesOut;  // 2 (n + 1) or nullptr: a copy of `bases` plus the totals
     float* vertices;
     float* normals;
     int32_t* triangles;
-    unsigned nblocks;
-    unsigned wpp;     // counting workgroups per z plane (at least 1)
-    unsigned chunks;  // chunks per counting workgroup (kMcChunksLarge or kMcChunksSmall)
+    unsigned n;
+    unsigned launchStart[EMF_MAX_MODELS + 1];
+    unsigned blockBase[EMF_MAX_MODELS + 1];
+    unsigned chunkBase[EMF_MAX_MODELS + 1];
 };
+static_assert(sizeof(MeshArgs) <= 4096, "MeshArgs travels in the kernel arguments");
+
+// the model whose range [start[m], start[m + 1]) holds x (wave-uniform; no step at all for one model)
+__device__ __forceinline__ unsigned model_of(const unsigned* start, unsigned n, unsigned x) {
+    unsigned lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (x >= start[mid]) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// kTable: the volumes come from the device table (level 3), else from the arguments (level 1).  Both are
+// instances of the same kernels; one kernel choosing at run time held the volume's pointers in VGPRs (count:
+// 68 -> 90, emit: 74 -> 93 VGPRs, 7 -> 5 waves per SIMD).
+template <bool kTable>
+__device__ __forceinline__ MeshSource source_of(const MeshArgs& a, unsigned m, const float*& grads) {
+    if constexpr (!kTable) {
+        grads = a.oneGrads;
+        return a.one;
+    }
+    const emf_model_t& md = a.models[m];
+    grads = md.grads;
+    return MeshSource{md.tsdf, md.weights, md.fgVolMask, I3{md.res[0], md.res[1], md.res[2]}, md.voxelSize};
+}
 
 struct Cube {
     int x, y, z;
@@ -256,13 +294,13 @@ __device__ __forceinline__ uint2 block_scan(uint2 v, uint2& total, uint2* lds /*
     return make_uint2(before.x + inc.x - v.x, before.y + inc.y - v.y);
 }
 
+// the counting work of one workgroup: logical workgroup b of a volume with kMcChunks chunks per workgroup
 template <int kMcChunks>
-__global__ __launch_bounds__(kMcBlock) void k_mesh_count(const MeshArgs a) {
+__device__ __forceinline__ void count_chunks(const MeshArgs& a, const MeshSource& src, unsigned b,
+                                             unsigned blockBase, unsigned chunkBase,
+                                             unsigned (*lds)[kMcChunksLarge]) {
     constexpr int kMcSpan = kMcChunk * kMcChunks;
-    __shared__ unsigned lds[kMcBlock / 64][kMcChunks];
-    const unsigned b = logical_block(a.nblocks, a.wpp);
-    if (b >= a.nblocks) return;
-    const I3 n = a.src.n;
+    const I3 n = src.n;
     const size_t nvox = static_cast<size_t>(n.x) * n.y * n.z;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     unsigned p[kMcChunks];
@@ -270,7 +308,7 @@ __global__ __launch_bounds__(kMcBlock) void k_mesh_count(const MeshArgs a) {
     Origin o = origin_of(n, pw);
 #pragma unroll
     for (int c = 0; c < kMcChunks; ++c) {
-        const unsigned cls = classify_wave(a.src, o, pw, nvox, lane);
+        const unsigned cls = classify_wave(src, o, pw, nvox, lane);
         p[c] = cls ? __popc(active_edges(cls)) | (triangles_of(cls) << 16) : 0u;
         pw += kMcChunk;
         o = advanced(n, o, kMcChunk);
@@ -288,7 +326,7 @@ __global__ __launch_bounds__(kMcBlock) void k_mesh_count(const MeshArgs a) {
         unsigned t = 0;
 #pragma unroll
         for (int w = 0; w < kMcBlock / 64; ++w) t += lds[w][threadIdx.x];
-        const unsigned g = b * kMcChunks + threadIdx.x;
+        const unsigned g = chunkBase + b * kMcChunks + threadIdx.x;
         a.chunkTot[g] = t;
         if (t) a.list[atomicAdd(a.listCount, 1u)] = g;
         uint2 sum = make_uint2(t & 0xffffu, t >> 16);
@@ -297,58 +335,103 @@ __global__ __launch_bounds__(kMcBlock) void k_mesh_count(const MeshArgs a) {
             sum.x += __shfl_xor(sum.x, o2);
             sum.y += __shfl_xor(sum.y, o2);
         }
-        if (threadIdx.x == 0) a.blockSums[b] = sum;
+        if (threadIdx.x == 0) a.blockSums[blockBase + b] = sum;
     }
 }
 
-// one workgroup walks the per-workgroup sums in chunks of 1024 (a 512^3 volume has 65 k of them)
+template <bool kTable>
+__global__ __launch_bounds__(kMcBlock) void k_mesh_count(const MeshArgs a) {
+    __shared__ unsigned lds[kMcBlock / 64][kMcChunksLarge];
+    const unsigned m = kTable ? model_of(a.launchStart, a.n, blockIdx.x) : 0u;
+    const unsigned blockBase = a.blockBase[m], nblocks = a.blockBase[m + 1] - blockBase;
+    const float* grads;
+    const MeshSource src = source_of<kTable>(a, m, grads);
+    const size_t nvox = static_cast<size_t>(src.n.x) * src.n.y * src.n.z;
+    const unsigned chunks = static_cast<unsigned>(chunks_for(nvox));
+    const size_t plane = static_cast<size_t>(src.n.x) * src.n.y, span = static_cast<size_t>(kMcChunk) * chunks;
+    const unsigned wpp = plane >= span ? static_cast<unsigned>(plane / span) : 1u;  // counting workgroups per z plane
+    const unsigned b = logical_block(blockIdx.x - a.launchStart[m], nblocks, wpp);
+    if (b >= nblocks) return;
+    if (chunks == static_cast<unsigned>(kMcChunksLarge))
+        count_chunks<kMcChunksLarge>(a, src, b, blockBase, a.chunkBase[m], lds);
+    else
+        count_chunks<kMcChunksSmall>(a, src, b, blockBase, a.chunkBase[m], lds);
+}
+
+// one workgroup walks each model's per-workgroup sums in chunks of 1024 (a 512^3 volume has 17 k of them), the
+// carry restarting at every model; the models' totals become their counts and, summed in 64 bits, their bases
 __global__ __launch_bounds__(1024) void k_mesh_scan(const MeshArgs a) {
     __shared__ uint2 lds[16];
     __shared__ uint2 carry;
-    if (threadIdx.x == 0) carry = make_uint2(0u, 0u);
-    __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (unsigned start = 0; start < a.nblocks; start += 1024) {
-        const unsigned i = start + threadIdx.x;
-        const uint2 v = i < a.nblocks ? a.blockSums[i] : make_uint2(0u, 0u);
-        uint2 inc = v;
+    unsigned long long vbase = 0, tbase = 0;  // (thread 0's)
+    for (unsigned m = 0; m < a.n; ++m) {
+        if (threadIdx.x == 0) carry = make_uint2(0u, 0u);
+        __syncthreads();
+        const unsigned hi = a.blockBase[m + 1];
+        for (unsigned start = a.blockBase[m]; start < hi; start += 1024) {
+            const unsigned i = start + threadIdx.x;
+            const uint2 v = i < hi ? a.blockSums[i] : make_uint2(0u, 0u);
+            uint2 inc = v;
 #pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned ax = __shfl_up(inc.x, o), ay = __shfl_up(inc.y, o);
-            if (lane >= o) {
-                inc.x += ax;
-                inc.y += ay;
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned ax = __shfl_up(inc.x, o), ay = __shfl_up(inc.y, o);
+                if (lane >= o) {
+                    inc.x += ax;
+                    inc.y += ay;
+                }
             }
-        }
-        if (lane == 63) lds[wave] = inc;
-        __syncthreads();
-        uint2 before = carry, total = make_uint2(0u, 0u);
-        for (int w = 0; w < 16; ++w) {
-            const uint2 t = lds[w];
-            if (w < wave) {
-                before.x += t.x;
-                before.y += t.y;
+            if (lane == 63) lds[wave] = inc;
+            __syncthreads();
+            uint2 before = carry, total = make_uint2(0u, 0u);
+            for (int w = 0; w < 16; ++w) {
+                const uint2 t = lds[w];
+                if (w < wave) {
+                    before.x += t.x;
+                    before.y += t.y;
+                }
+                total.x += t.x;
+                total.y += t.y;
             }
-            total.x += t.x;
-            total.y += t.y;
+            if (i < hi) a.blockSums[i] = make_uint2(before.x + inc.x - v.x, before.y + inc.y - v.y);
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                carry.x += total.x;
+                carry.y += total.y;
+            }
+            __syncthreads();
         }
-        if (i < a.nblocks) a.blockSums[i] = make_uint2(before.x + inc.x - v.x, before.y + inc.y - v.y);
-        __syncthreads();
         if (threadIdx.x == 0) {
-            carry.x += total.x;
-            carry.y += total.y;
+            a.counts[m].vertices = carry.x;
+            a.counts[m].triangles = carry.y;
+            a.bases[2 * m] = vbase;
+            a.bases[2 * m + 1] = tbase;
+            if (a.basesOut) {
+                a.basesOut[2 * m] = vbase;
+                a.basesOut[2 * m + 1] = tbase;
+            }
+            vbase += carry.x;
+            tbase += carry.y;
         }
-        __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        a.counts->vertices = carry.x;
-        a.counts->triangles = carry.y;
+    if (threadIdx.x == 0 && a.basesOut) {
+        a.basesOut[2 * a.n] = vbase;
+        a.basesOut[2 * a.n + 1] = tbase;
     }
 }
 
+// where one model's mesh goes: its slice of the concatenated outputs
+struct MeshOut {
+    MeshSource src;
+    const float* grads;
+    float* vertices;
+    float* normals;
+    int32_t* triangles;
+};
+
 // gradient of the corner voxel: the gradient volume if there is one, else what
 // kernel_computeTSDFGrads would have stored there (forward differences, zero on the last planes)
-__device__ __forceinline__ V3 corner_gradient(const MeshArgs& a, size_t idx, int x, int y, int z) {
+__device__ __forceinline__ V3 corner_gradient(const MeshOut& a, size_t idx, int x, int y, int z) {
     if (a.grads) return v3(a.grads[3 * idx], a.grads[3 * idx + 1], a.grads[3 * idx + 2]);
     const I3 n = a.src.n;
     if (x >= n.x - 1 || y >= n.y - 1 || z >= n.z - 1) return v3(0.f, 0.f, 0.f);
@@ -357,37 +440,50 @@ __device__ __forceinline__ V3 corner_gradient(const MeshArgs& a, size_t idx, int
     return v3(a.src.tsdf[idx + 1] - t, a.src.tsdf[idx + sy] - t, a.src.tsdf[idx + sz] - t);
 }
 
-__device__ __forceinline__ void emit_cube(const MeshArgs& a, const Cube& q, unsigned edges, unsigned ntris,
+__device__ __forceinline__ void emit_cube(const MeshOut& a, const Cube& q, unsigned edges, unsigned ntris,
                                           unsigned vertBase, unsigned triBase);
 
-__global__ __launch_bounds__(kMcBlock) void k_mesh_emit(const MeshArgs a) {
+// 6 waves per SIMD like the one-volume kernel before the table (74 VGPRs); uncapped the slice offsets take the
+// argument form to 81 = 5 waves
+template <bool kTable>
+__global__ __launch_bounds__(kMcBlock) __attribute__((amdgpu_waves_per_eu(6))) void k_mesh_emit(const MeshArgs a) {
     __shared__ uint2 lds[8];
-    const I3 n = a.src.n;
-    const size_t nvox = static_cast<size_t>(n.x) * n.y * n.z;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned todo = *a.listCount;
     for (unsigned i = blockIdx.x; i < todo; i += gridDim.x) {
-        const unsigned g = a.list[i];
-        const unsigned first = g & ~(a.chunks - 1u);
-        uint2 base = a.blockSums[g / a.chunks];
+        const unsigned gg = a.list[i];
+        const unsigned m = kTable ? model_of(a.chunkBase, a.n, gg) : 0u;
+        MeshOut out;
+        out.src = source_of<kTable>(a, m, out.grads);
+        const unsigned long long vb = a.bases[2 * m], tb = a.bases[2 * m + 1];
+        out.vertices = a.vertices + 3 * vb;
+        out.normals = a.normals + 3 * vb;
+        out.triangles = a.triangles + 4 * tb;
+        const I3 n = out.src.n;
+        const size_t nvox = static_cast<size_t>(n.x) * n.y * n.z;
+        const unsigned chunks = static_cast<unsigned>(chunks_for(nvox));
+        const unsigned* tot = a.chunkTot + a.chunkBase[m];
+        const unsigned g = gg - a.chunkBase[m];  // the model's own chunk index
+        const unsigned first = g & ~(chunks - 1u);
+        uint2 base = a.blockSums[a.blockBase[m] + g / chunks];
         for (unsigned c = first; c < g; ++c) {
-            const unsigned t = a.chunkTot[c];
+            const unsigned t = tot[c];
             base.x += t & 0xffffu;
             base.y += t >> 16;
         }
         const size_t p = static_cast<size_t>(g) * kMcChunk + static_cast<size_t>(wave) * kMcWaveCubes + lane;
-        const Cube q = classify(a.src, origin_of(n, p), lane < kMcWaveCubes && p < nvox);
+        const Cube q = classify(out.src, origin_of(n, p), lane < kMcWaveCubes && p < nvox);
         const unsigned edges = q.cls ? active_edges(q.cls) : 0u;
         uint2 v = make_uint2(0u, 0u);
         if (q.cls) v = make_uint2(__popc(edges), triangles_of(q.cls));
         uint2 total;
         const uint2 mine = block_scan(v, total, lds);
         // (3, i0, i1, i2) per triangle
-        if (q.cls) emit_cube(a, q, edges, v.y, base.x + mine.x, 4u * (base.y + mine.y));
+        if (q.cls) emit_cube(out, q, edges, v.y, base.x + mine.x, 4u * (base.y + mine.y));
     }
 }
 
-__device__ __forceinline__ void emit_cube(const MeshArgs& a, const Cube& q, unsigned edges, unsigned ntris,
+__device__ __forceinline__ void emit_cube(const MeshOut& a, const Cube& q, unsigned edges, unsigned ntris,
                                           unsigned vertBase, unsigned triBase) {
     const I3 n = a.src.n;
     const size_t sy = static_cast<size_t>(n.x), sz = sy * n.y;
@@ -433,42 +529,106 @@ __device__ __forceinline__ void emit_cube(const MeshArgs& a, const Cube& q, unsi
             int o = 0;  // offsets[e] without a dynamically indexed register array
 #pragma unroll
             for (int i = 0; i < 12; ++i) o = e == i ? offsets[i] : o;
-            to[1 + j] = static_cast<int32_t>(vertBase) + o;
+            to[1 + j] = static_cast<int32_t>(vertBase) + o;  // model-local: the slice is the volume's own mesh
         }
     }
 }
 
-// grid of the counting pass: 8 XCDs x ceil(wpp / 8) columns x planes (see logical_block)
+// grid of one volume's counting pass: 8 XCDs x ceil(wpp / 8) columns x planes (see logical_block)
 unsigned launch_blocks(unsigned nblocks, unsigned wpp) {
     const unsigned band = (wpp + kXcds - 1) / kXcds, rows = (nblocks + wpp - 1) / wpp;
     return kXcds * band * rows;
 }
 
-int fill_args(MeshArgs& a, const float* tsdf, const float* weights, const uint8_t* fg,
-              const int32_t res[3], float voxelSize, void* scratch) {
+// The ranges of a table of n volumes (res: 3 per model) and the scratch they need:
+//   [bases: 2n u64][blockSums: uint2 per counting workgroup][chunkTot, list: u32 per chunk][listCount][pad]
+int plan(MeshArgs& a, const int32_t* res, int n, size_t& scratchBytes) {
+    EMF_REQUIRE_PTR(res);
+    if (n < 1 || n > EMF_MAX_MODELS)
+        return fail(EMF_E_LIMIT, "mesh: %d models (1 .. %d per launch)", n, EMF_MAX_MODELS);
+    unsigned long long grid = 0, blocks = 0, chunks = 0;
+    for (int m = 0; m < n; ++m) {
+        EMF_TRY(check_res(res + 3 * m));
+        const size_t nvox = static_cast<size_t>(res[3 * m]) * res[3 * m + 1] * res[3 * m + 2];
+        const unsigned per = static_cast<unsigned>(chunks_for(nvox));
+        const size_t span = static_cast<size_t>(kMcChunk) * per;
+        const unsigned long long nb = (nvox + span - 1) / span;
+        const size_t plane = static_cast<size_t>(res[3 * m]) * res[3 * m + 1];
+        const unsigned wpp = static_cast<unsigned>(plane >= span ? plane / span : 1);
+        a.launchStart[m] = static_cast<unsigned>(grid);
+        a.blockBase[m] = static_cast<unsigned>(blocks);
+        a.chunkBase[m] = static_cast<unsigned>(chunks);
+        // the XCD banding pads a model's grid to whole bands: at most 8 wpp workgroups more than it has
+        grid += launch_blocks(static_cast<unsigned>(nb), wpp);
+        blocks += nb;
+        chunks += nb * per;
+        if (chunks > 0x7ffffff0ull || grid > 0xffffffull)  // chunk ids in 32 bits, 256-lane workgroups in one grid
+            return fail(EMF_E_LIMIT, "mesh: %d volumes of %llu chunks exceed one launch", m + 1, chunks);
+    }
+    a.launchStart[n] = static_cast<unsigned>(grid);
+    a.blockBase[n] = static_cast<unsigned>(blocks);
+    a.chunkBase[n] = static_cast<unsigned>(chunks);
+    a.n = static_cast<unsigned>(n);
+    scratchBytes = 16 * static_cast<size_t>(n) + blocks * sizeof(uint2) + 2 * chunks * sizeof(unsigned) + 16;
+    return EMF_OK;
+}
+
+void place(MeshArgs& a, void* scratch) {
+    a.bases = static_cast<unsigned long long*>(scratch);
+    a.blockSums = reinterpret_cast<uint2*>(a.bases + 2 * a.n);
+    a.chunkTot = reinterpret_cast<unsigned*>(a.blockSums + a.blockBase[a.n]);
+    a.list = a.chunkTot + a.chunkBase[a.n];
+    a.listCount = a.list + a.chunkBase[a.n];
+}
+
+int launch_count(MeshArgs& a, emf_stream_t stream, const char* what) {
+    const hipError_t e = hipMemsetAsync(a.listCount, 0, sizeof(unsigned), as_stream(stream));
+    if (e != hipSuccess) {
+        set_error("%s: memset: %s", what, hipGetErrorString(e));
+        return static_cast<int>(e);
+    }
+    if (a.models)
+        hipLaunchKernelGGL(k_mesh_count<true>, dim3(a.launchStart[a.n]), dim3(kMcBlock), 0, as_stream(stream), a);
+    else
+        hipLaunchKernelGGL(k_mesh_count<false>, dim3(a.launchStart[a.n]), dim3(kMcBlock), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(1024), 0, as_stream(stream), a);
+    return launch_status(what);
+}
+
+int launch_emit(MeshArgs& a, emf_stream_t stream, const char* what) {
+    const unsigned nchunks = a.chunkBase[a.n];  // fixed grid over the list of surface chunks
+    const dim3 grid(nchunks < 4096u ? nchunks : 4096u);
+    if (a.models)
+        hipLaunchKernelGGL(k_mesh_emit<true>, grid, dim3(kMcBlock), 0, as_stream(stream), a);
+    else
+        hipLaunchKernelGGL(k_mesh_emit<false>, grid, dim3(kMcBlock), 0, as_stream(stream), a);
+    return launch_status(what);
+}
+
+// the level-1 form: a one-volume table whose volume travels in the arguments
+int single(MeshArgs& a, const float* tsdf, const float* weights, const uint8_t* fg, const float* grads,
+           const int32_t res[3], float voxelSize, void* scratch) {
     EMF_REQUIRE_PTR(tsdf);
     EMF_REQUIRE_PTR(weights);
     EMF_REQUIRE_PTR(scratch);
     EMF_TRY(check_res(res));
-    const size_t nvox = static_cast<size_t>(res[0]) * res[1] * res[2];
-    if ((nvox + kMcChunk - 1) / kMcChunk > 0x7ffffff0ull)
-        return fail(EMF_E_LIMIT, "mesh: %zu voxels exceed one launch", nvox);
-    const unsigned chunks = static_cast<unsigned>(chunks_for(nvox));
-    const size_t span = static_cast<size_t>(kMcChunk) * chunks;
-    const unsigned nblocks = static_cast<unsigned>((nvox + span - 1) / span);
-    a.src = MeshSource{tsdf, weights, fg, i3_from(res), voxelSize};
-    a.grads = nullptr;
-    a.blockSums = static_cast<uint2*>(scratch);
-    a.chunkTot = reinterpret_cast<unsigned*>(a.blockSums + nblocks);
-    a.list = a.chunkTot + static_cast<size_t>(nblocks) * chunks;
-    a.listCount = a.list + static_cast<size_t>(nblocks) * chunks;
-    a.chunks = chunks;
-    a.counts = nullptr;
-    a.vertices = a.normals = nullptr;
-    a.triangles = nullptr;
-    a.nblocks = nblocks;
-    const size_t plane = static_cast<size_t>(res[0]) * res[1];
-    a.wpp = static_cast<unsigned>(plane / span > 0 ? plane / span : 1);
+    size_t bytes = 0;
+    a = MeshArgs{};
+    EMF_TRY(plan(a, res, 1, bytes));
+    a.one = MeshSource{tsdf, weights, fg, i3_from(res), voxelSize};
+    a.oneGrads = grads;
+    place(a, scratch);
+    return EMF_OK;
+}
+
+int table(MeshArgs& a, const emf_model_t* models, const int32_t* res, int n, void* scratch) {
+    EMF_REQUIRE_PTR(models);
+    size_t bytes = 0;
+    a = MeshArgs{};
+    EMF_TRY(plan(a, res, n, bytes));
+    EMF_REQUIRE_PTR(scratch);
+    a.models = models;
+    place(a, scratch);
     return EMF_OK;
 }
 
@@ -479,33 +639,25 @@ using namespace emf_hip;
 
 extern "C" {
 
-size_t emf_hip_meshScratchBytes(const int32_t res[3]) {
-    if (!res || res[0] < 2 || res[1] < 2 || res[2] < 2) return 0;
-    const size_t nvox = static_cast<size_t>(res[0]) * res[1] * res[2];
-    const size_t chunks = static_cast<size_t>(chunks_for(nvox)), span = kMcChunk * chunks;
-    return ((nvox + span - 1) / span) * (sizeof(uint2) + 2 * chunks * sizeof(unsigned)) + 16;
+size_t emf_hip_meshScratchBytes(const int32_t res[3]) { return emf_hip_meshScratchBytesBatched(res, 1); }
+
+size_t emf_hip_meshScratchBytesBatched(const int32_t* res_host, int n) {
+    if (!res_host || n < 1 || n > EMF_MAX_MODELS) return 0;
+    for (int m = 0; m < n; ++m)
+        if (res_host[3 * m] < 2 || res_host[3 * m + 1] < 2 || res_host[3 * m + 2] < 2) return 0;
+    MeshArgs a;
+    size_t bytes = 0;
+    return plan(a, res_host, n, bytes) == EMF_OK ? bytes : 0;
 }
 
 int emf_hip_meshCount(const float* tsdf, const float* weights, const uint8_t* fgVolMask,
                       const int32_t res[3], void* scratch_dev, emf_mesh_counts_t* counts_dev,
                       emf_stream_t stream) {
     MeshArgs a;
-    EMF_TRY(fill_args(a, tsdf, weights, fgVolMask, res, 1.f, scratch_dev));
+    EMF_TRY(single(a, tsdf, weights, fgVolMask, nullptr, res, 1.f, scratch_dev));
     EMF_REQUIRE_PTR(counts_dev);
     a.counts = counts_dev;
-    const hipError_t e = hipMemsetAsync(a.listCount, 0, sizeof(unsigned), as_stream(stream));
-    if (e != hipSuccess) {
-        set_error("meshCount: memset: %s", hipGetErrorString(e));
-        return static_cast<int>(e);
-    }
-    if (a.chunks == static_cast<unsigned>(kMcChunksLarge))
-        hipLaunchKernelGGL(k_mesh_count<kMcChunksLarge>, dim3(launch_blocks(a.nblocks, a.wpp)), dim3(kMcBlock), 0,
-                           as_stream(stream), a);
-    else
-        hipLaunchKernelGGL(k_mesh_count<kMcChunksSmall>, dim3(launch_blocks(a.nblocks, a.wpp)), dim3(kMcBlock), 0,
-                           as_stream(stream), a);
-    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(1024), 0, as_stream(stream), a);
-    return launch_status("meshCount");
+    return launch_count(a, stream, "meshCount");
 }
 
 int emf_hip_meshEmit(const float* tsdf, const float* grads, const float* weights,
@@ -513,17 +665,37 @@ int emf_hip_meshEmit(const float* tsdf, const float* grads, const float* weights
                      const void* scratch_dev, float* vertices, float* normals, int32_t* triangles,
                      emf_stream_t stream) {
     MeshArgs a;
-    EMF_TRY(fill_args(a, tsdf, weights, fgVolMask, res, voxelSize, const_cast<void*>(scratch_dev)));
+    EMF_TRY(single(a, tsdf, weights, fgVolMask, grads, res, voxelSize, const_cast<void*>(scratch_dev)));
     EMF_REQUIRE_PTR(vertices);
     EMF_REQUIRE_PTR(normals);
     EMF_REQUIRE_PTR(triangles);
-    a.grads = grads;
     a.vertices = vertices;
     a.normals = normals;
     a.triangles = triangles;
-    const unsigned nchunks = a.nblocks * a.chunks;  // fixed grid over the list of surface chunks
-    hipLaunchKernelGGL(k_mesh_emit, dim3(nchunks < 4096u ? nchunks : 4096u), dim3(kMcBlock), 0, as_stream(stream), a);
-    return launch_status("meshEmit");
+    return launch_emit(a, stream, "meshEmit");
+}
+
+int emf_hip_meshCountBatched(const emf_model_t* models_dev, const int32_t* res_host, int n, void* scratch_dev,
+                             emf_mesh_counts_t* counts_dev, uint64_t* bases_dev, emf_stream_t stream) {
+    MeshArgs a;
+    EMF_TRY(table(a, models_dev, res_host, n, scratch_dev));
+    EMF_REQUIRE_PTR(counts_dev);
+    a.counts = counts_dev;
+    a.basesOut = reinterpret_cast<unsigned long long*>(bases_dev);
+    return launch_count(a, stream, "meshCountBatched");
+}
+
+int emf_hip_meshEmitBatched(const emf_model_t* models_dev, const int32_t* res_host, int n, const void* scratch_dev,
+                            float* vertices, float* normals, int32_t* triangles, emf_stream_t stream) {
+    MeshArgs a;
+    EMF_TRY(table(a, models_dev, res_host, n, const_cast<void*>(scratch_dev)));
+    EMF_REQUIRE_PTR(vertices);
+    EMF_REQUIRE_PTR(normals);
+    EMF_REQUIRE_PTR(triangles);
+    a.vertices = vertices;
+    a.normals = normals;
+    a.triangles = triangles;
+    return launch_emit(a, stream, "meshEmitBatched");
 }
 
 }  // extern "C"

@@ -719,6 +719,55 @@ def extract_mesh(tsdf, weights, voxel_size, fg_mask=None, grads=None, stream=Non
     return verts.numpy()[:nv], norms.numpy()[:nv], tris.numpy()[:nt]
 
 
+def mesh_table(volumes):
+    """The device model table (only what meshing reads) and the host resolutions of extract_meshes' volumes."""
+    n = len(volumes)
+    models = []
+    res = (C.c_int32 * (3 * max(n, 1)))()
+    for k, v in enumerate(volumes):
+        tsdf = v["tsdf"]
+        m = _lib.EmfModel()
+        m.tsdf, m.weights = tsdf.ptr, v["weights"].ptr
+        m.grads = v["grads"].ptr if v.get("grads") is not None else None
+        m.fgVolMask = v["fg_mask"].ptr if v.get("fg_mask") is not None else None
+        nz, ny, nx = tsdf.shape[:3]
+        m.res[:] = [nx, ny, nz]
+        m.voxelSize = float(v["voxel_size"])
+        res[3 * k:3 * k + 3] = [nx, ny, nz]
+        models.append(m)
+    return (upload_models(models) if n else None), res
+
+
+def extract_meshes(volumes, stream=None):
+    """emf_hip_meshCountBatched / emf_hip_meshEmitBatched: the meshes of a table of volumes in one pass (one count
+    launch, one read-back of the counts, one emit launch).  volumes: [dict(tsdf=, weights=, voxel_size=, fg_mask=None,
+    grads=None), ...] of device arrays, at most EMF_MAX_MODELS.  Returns [(vertices (n, 3) f32, normals (n, 3) f32,
+    triangles (m, 4) i32), ...] in table order, each what extract_mesh gives for that volume alone."""
+    n = len(volumes)
+    table, res = mesh_table(volumes)
+    scratch_bytes = int(_L.emf_hip_meshScratchBytesBatched(res, n))
+    scratch = DeviceArray.zeros((max(scratch_bytes // 4, 2),), np.uint32)
+    counts = DeviceArray.zeros((max(n, 1), 2), np.uint32)
+    bases = DeviceArray.zeros((n + 1, 2), np.uint64)
+    check("emf_hip_meshCountBatched",
+          _L.emf_hip_meshCountBatched(_ptr(table), res, n, _ptr(scratch), _ptr(counts), _ptr(bases), _stream(stream)))
+    cnt, bs = counts.numpy(), bases.numpy()
+    nv, nt = int(bs[n, 0]), int(bs[n, 1])
+    verts = DeviceArray.zeros((max(nv, 1), 3), np.float32)
+    norms = DeviceArray.zeros((max(nv, 1), 3), np.float32)
+    tris = DeviceArray.zeros((max(nt, 1), 4), np.int32)
+    if nv:
+        check("emf_hip_meshEmitBatched",
+              _L.emf_hip_meshEmitBatched(_ptr(table), res, n, _ptr(scratch), _ptr(verts), _ptr(norms), _ptr(tris),
+                                         _stream(stream)))
+    hv, hn, ht = verts.numpy(), norms.numpy(), tris.numpy()
+    out = []
+    for k in range(n):
+        v0, t0, cv, ct = int(bs[k, 0]), int(bs[k, 1]), int(cnt[k, 0]), int(cnt[k, 1])
+        out.append((hv[v0:v0 + cv], hn[v0:v0 + cv], ht[t0:t0 + ct]))
+    return out
+
+
 def copy_values(src, dst, offset, stream=None):
     """dst(v) = src(v + offset) inside src, else 0 (kernel_copyValues); volumes (Nz, Ny, Nx[, C])."""
     ch = 1 if len(src.shape) == 3 else src.shape[3]

@@ -132,6 +132,8 @@ def load() -> C.CDLL:
         "emf_fusion_clear_3d_view": [vp],
         "emf_fusion_extract_mesh": [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
         "emf_fusion_copy_mesh": [vp, C.c_void_p, C.c_void_p, C.c_void_p],
+        "emf_fusion_extract_meshes": [vp, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_uint32)],
+        "emf_fusion_copy_meshes": [vp, C.c_void_p, C.c_void_p, C.c_void_p],
         "emf_io_write_mesh": [C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
         "emf_fusion_queue_new_object_masks": [vp, C.c_int, img],
         "emf_fusion_last_created": [vp, ip, C.c_int, ip],
@@ -647,11 +649,39 @@ class Fusion:
                load().emf_fusion_copy_mesh(self._h, v.ctypes.data, n.ctypes.data, t.ctypes.data))
         return v, n, t
 
+    def meshes(self, ids=None):
+        """EMFusion::extractMeshes: {id: (vertices (n, 3), normals (n, 3), triangles (m, 4))} of the listed models
+        (0 = background; None: the background and every live object) in one pass over the model table -- the same
+        arrays as mesh(id) for each."""
+        ids = [0] + self.object_ids() if ids is None else [int(i) for i in ids]
+        if not ids:
+            return {}
+        n = len(ids)
+        id_arr = (C.c_int32 * n)(*ids)
+        counts = np.zeros((n, 2), np.uint32)
+        _check("emf_fusion_extract_meshes",
+               load().emf_fusion_extract_meshes(self._h, id_arr, n,
+                                                counts.ctypes.data_as(C.POINTER(C.c_uint32))))
+        nv, nt = int(counts[:, 0].sum()), int(counts[:, 1].sum())
+        v = np.empty((nv, 3), np.float32)
+        nrm = np.empty((nv, 3), np.float32)
+        t = np.empty((nt, 4), np.int32)
+        _check("emf_fusion_copy_meshes",
+               load().emf_fusion_copy_meshes(self._h, v.ctypes.data, nrm.ctypes.data, t.ctypes.data))
+        out, v0, t0 = {}, 0, 0
+        for k, i in enumerate(ids):
+            cv, ct = int(counts[k, 0]), int(counts[k, 1])
+            out[i] = (v[v0:v0 + cv], nrm[v0:v0 + cv], t[t0:t0 + ct])
+            v0, t0 = v0 + cv, t0 + ct
+        return out
+
     def enable_pose_log(self, on=True):
         _check("emf_fusion_enable_pose_log", load().emf_fusion_enable_pose_log(self._h, int(on)))
 
     def setup_output(self, exp_frame_meshes=False, exp_vols=False):
-        """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too."""
+        """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
+        the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
+        the sharded path)."""
         _check("emf_fusion_setup_output",
                load().emf_fusion_setup_output(self._h, int(exp_frame_meshes), int(exp_vols)))
 

@@ -155,6 +155,12 @@ int emf_fusion_last_deleted(emf_fusion_t* h, int32_t* ids, int capacity, int32_t
  * triangles: 4 int32 per triangle = 3, i0, i1, i2).  emf_io_write_mesh writes the reference's PLY. */
 int emf_fusion_extract_mesh(emf_fusion_t* h, int id, uint32_t* num_vertices, uint32_t* num_triangles);
 int emf_fusion_copy_mesh(emf_fusion_t* h, float* vertices, float* normals, int32_t* triangles);
+/* EMFusion::extractMeshes: the meshes of n models at once (ids[k]: 0 = background or a live object of this rank;
+ * emf_fusion_object_ids lists them), one pass over the model table; the same bytes as emf_fusion_extract_mesh per id.
+ * counts: 2 n uint32 (vertices, triangles of model k).  copy hands them out concatenated in list order (NULL: not
+ * wanted), each model's triangle indices local to its own vertices. */
+int emf_fusion_extract_meshes(emf_fusion_t* h, const int32_t* ids, int n, uint32_t* counts);
+int emf_fusion_copy_meshes(emf_fusion_t* h, float* vertices, float* normals, int32_t* triangles);
 int emf_io_write_mesh(const char* filename, uint32_t num_vertices, const float* vertices,
                       const float* normals, uint32_t num_triangles, const int32_t* triangles);
 /* EMFusion::render (EMFusion.cpp:131-160): Phong-shaded RGB view of the models, width*height*3 bytes
@@ -177,7 +183,9 @@ int emf_fusion_clear_3d_view(emf_fusion_t* h);
 int emf_fusion_set_depth_broadcast(emf_fusion_t* h, int root);
 int emf_fusion_enable_pose_log(emf_fusion_t* h, int on);
 /* EMFusion::setupOutput (EMFusion.cpp:243-247): log on; exp_vols != 0 also keeps the volumes of
- * objects deleted during the run for write_results.  exp_frame_meshes is accepted and ignored. */
+ * objects deleted during the run for write_results.  exp_frame_meshes != 0 meshes the background and every live
+ * object not hidden by ignore_person at the end of every frame (one pass over the table) and keeps the meshes for
+ * write_results' frame_meshes/bg/%04d.ply and frame_meshes/<id>/%04d.ply; EMF_E_ARG on the sharded path. */
 int emf_fusion_setup_output(emf_fusion_t* h, int exp_frame_meshes, int exp_vols);
 /* EMFusion::writeResults (EMFusion.cpp:248-292): pose files, mesh_bg.ply and mesh_<id>.ply always;
  * tsdfs/ *.bin only if volumes != 0 or setup_output asked for them. */

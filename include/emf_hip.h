@@ -742,6 +742,25 @@ int emf_hip_meshEmit(const float* tsdf, const float* grads, const float* weights
                      const void* scratch_dev, float* vertices, float* normals, int32_t* triangles,
                      emf_stream_t stream);
 
+/* The two passes over a TABLE of volumes (level 3): one count launch, one scan launch and one emit launch mesh every
+ * model of models_dev[0 .. n) (tsdf, weights, grads, fgVolMask, res, voxelSize are read; NULL grads = on-the-fly
+ * differences, NULL fgVolMask = no foreground gate).  1 <= n <= EMF_MAX_MODELS (no EMF_MAX_BATCH chunking).
+ * res_host: HOST int32[3 n], the resolutions stored in the table.  Model m's mesh is written to the concatenated
+ * outputs at its bases, and that slice is byte for byte what emf_hip_meshCount + emf_hip_meshEmit give for the volume
+ * alone: the same order, triangle indices local to the model (its first vertex is 0).  The level-1 calls above are
+ * the one-volume case of the same kernels.
+ *   scratch: emf_hip_meshScratchBytesBatched(res_host, n) bytes (0 returned for bad arguments)
+ *   counts_dev: n emf_mesh_counts_t
+ *   bases_dev:  NULL, or 2 (n + 1) uint64: model m's first vertex and first triangle in the outputs, entry n = the
+ *               totals (the size of the emit's outputs) */
+size_t emf_hip_meshScratchBytesBatched(const int32_t* res_host, int n);
+int emf_hip_meshCountBatched(const emf_model_t* models_dev, const int32_t* res_host, int n, void* scratch_dev,
+                             emf_mesh_counts_t* counts_dev, uint64_t* bases_dev, emf_stream_t stream);
+/* vertices / normals: 3 floats per vertex of all models, triangles: 4 int32 per triangle of all models (sized by the
+ * totals); the same scratch, table and res_host as the count. */
+int emf_hip_meshEmitBatched(const emf_model_t* models_dev, const int32_t* res_host, int n, const void* scratch_dev,
+                            float* vertices, float* normals, int32_t* triangles, emf_stream_t stream);
+
 /* The ignore_person block of EMFusion::render (EMFusion.cpp:139-150: compare, setTo, two masked
  * copyTo) in one launch: pixels labelled `id` get label 0 and the background's vertex / normal. */
 int emf_hip_hideLabel(const emf_image_t* segmentation, int id, const emf_image_t* vertices,
