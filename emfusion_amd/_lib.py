@@ -116,6 +116,9 @@ SIGNATURES = {
     "emf_hip_maskOverlap": [_IMG, _IMG, _FP, _STREAM],
     "emf_hip_maskAssociationMassBytes": [],
     "emf_hip_maskAssociationMass": [_IMG, _IMG, _IMG, _FP, _STREAM],
+    "emf_hip_maskAssociationMassScratchBytes": [C.c_int],
+    "emf_hip_maskAssociationMassBatched": [_FP, C.c_int, C.c_int, C.c_int, C.c_int, _IMG, _FP, _FP, _FP, C.c_int, _I3,
+                                           _FP, C.POINTER(C.c_uint8), C.c_float, _STREAM],
     "emf_hip_carveMask": [_IMG, _IMG, C.c_int, _IMG, _FP, _STREAM],
     "emf_hip_objectExtentStats": [_IMG, _IMG, _F9, _F9, _FP, _FP, _FP, _I3, C.c_float, _FP, _FP, _STREAM],
     "emf_hip_copyValues": [_FP, _FP, C.c_int, _I3, _I3, _I3, _STREAM],
@@ -256,6 +259,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.emf_hip_peerBufferBytes.restype = C.c_size_t
     lib.emf_hip_peerRaycastSlotBytes.restype = C.c_size_t
     lib.emf_hip_maskAssociationMassBytes.restype = C.c_size_t
+    lib.emf_hip_maskAssociationMassScratchBytes.restype = C.c_size_t
     lib.emf_hip_last_error_string.argtypes = []
     lib.emf_hip_last_error_string.restype = C.c_char_p
     return lib

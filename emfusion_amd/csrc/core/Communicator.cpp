@@ -352,6 +352,12 @@ public:
     LocalCommunicator(std::shared_ptr<LocalGroup> g, int rank) : g_(std::move(g)), rank_(rank) {}
     int rank() const override { return rank_; }
     int size() const override { return g_->world; }
+    // (the collectives of a group still run one by one here; the group counts once, as on the other transports)
+    void groupStart() override { ++groupDepth_; }
+    void groupEnd() override {
+        if (groupDepth_ > 0 && --groupDepth_ == 0) ++exchanges_;
+    }
+    uint64_t exchangesIssued() const override { return exchanges_; }
 
     void allReduceSumF32(float* dev, size_t count, Stream& s) override {
         publish(dev, count * sizeof(float), s);
@@ -394,6 +400,7 @@ public:
 private:
     // device -> this rank's slot, then wait until every rank has published
     void publish(const void* dev, size_t bytes, Stream& s) {
+        if (groupDepth_ == 0) ++exchanges_;
         auto& slot = g_->slots[rank_];
         slot.resize(bytes);
         hipCheck(hipMemcpyAsync(slot.data(), dev, bytes, hipMemcpyDeviceToHost, s.get()), "local comm D2H");
@@ -408,6 +415,8 @@ private:
     }
     std::shared_ptr<LocalGroup> g_;
     int rank_;
+    int groupDepth_ = 0;
+    uint64_t exchanges_ = 0;
 };
 
 class HostStagedCommunicator final : public Communicator {

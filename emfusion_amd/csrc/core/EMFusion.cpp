@@ -334,10 +334,12 @@ void EMFusion::rebuildModelTable() {
         bgCullScratch = DeviceBuffer(emf_hip_integrateCullScratchBytes(resHost.data(), 1));
     }
     tableSel = 0;
+    // (the per-volume path uploads the table too: cleanUpObjs reads the objects' raycast masks and association
+    // weights through it, emf_hip_maskAssociationMassBatched)
+    hipCheck(hipMemcpy(modelTable.data(), modelsHost.data(),
+                       modelsHost.size() * sizeof(emf_model_t), hipMemcpyHostToDevice),
+             "model table upload");
     if (batched) {
-        hipCheck(hipMemcpy(modelTable.data(), modelsHost.data(),
-                           modelsHost.size() * sizeof(emf_model_t), hipMemcpyHostToDevice),
-                 "model table upload");
         if (background.doubleBuffered()) {
             std::vector<emf_model_t> alt = modelsHost;
             const emf_volume_out_t back = background.backBuffers();

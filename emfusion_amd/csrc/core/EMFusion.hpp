@@ -106,6 +106,20 @@ public:
      * instance mask (device u8 W x H, non-zero = inside) of the CURRENT frame's points.  Returns
      * the new object id, or -1 if the mask has too few valid points (visibilityThresh), overlaps an
      * existing volume too much (volIOUThresh) or lies too far away (distanceThresh).
+     *
+     * Object life cycle on the sharded path (this call, initOrMatchObjs, updateObject, cleanUpObjs, and the frame
+     * inputs instanceMasks / newObjectMasks / cleanUp that drive them).  ASSUMPTION: every rank receives the same
+     * instance masks and scores -- through FrameInputs, or because each rank reads the same Mask%04d.plk file
+     * (usePreprocMasks) -- and every rank makes the same calls.  Decisions that need only replicated data (points,
+     * camera pose, the joint modelSegmentation and visible set after the composite, allIds) are taken by every rank
+     * alone; owner-only facts travel in fixed exchanges, so that lastCreated / lastMaskAssignment / lastDeleted come
+     * out identical on every rank:
+     *   - here, when the point count passes and objects exist: every rank tests the volume IoU of ITS objects, ONE
+     *     allReduceSumF32 of 16 bytes says whether any owner blocks the mask, then all ranks call addObject or none;
+     *   - resizes (updateObj), class scores and existence probabilities stay with the owner; updateObject(id, mask)
+     *     is called on every rank and the owner broadcasts the 16-byte offset, so every rank returns it;
+     *   - cleanUpObjs: ONE allReduceSumF32 of the per-object delete verdicts (round_up(nall, 4) floats, written by
+     *     the owners' mass kernel) whenever the job has objects, then every rank deletes the same ids.
      */
     int initNewObjVolume(const emf_image_t& mask);
     /** Reference EMFusion::volumeIOU (EMFusion.cpp:559-611). */
@@ -135,14 +149,19 @@ public:
     /**
      * Reference EMFusion::updateObj (EMFusion.cpp:827-863): grow / recentre a matched object's
      * volume around its surface and the newly matched points; returns the centre shift (0: none).
-     * updateObject(id, mask) is the stand-alone form (looks the object up, refreshes the model table).
+     * updateObject(id, mask) is the stand-alone form (looks the object up, refreshes the model table); on the
+     * sharded path every rank calls it, the owner resizes and broadcasts the shift, all ranks return it.
      */
     Vec3f updateObj(ObjTSDF& obj, const emf_image_t& mask);
     Vec3f updateObject(int id, const emf_image_t& mask);
     static std::map<int, std::map<int, Affine3f>> addPoseOffsets(
         const std::map<int, std::map<int, Affine3f>>& poses,
         const std::map<int, std::map<int, Vec3f>>& offsets);
-    /** Reference EMFusion::cleanUpObjs (EMFusion.cpp:922-980); returns the deleted ids. */
+    /**
+     * Reference EMFusion::cleanUpObjs (EMFusion.cpp:922-980); returns the deleted ids.  The association masses of all
+     * objects of this rank come from two launches over the model table (emf_hip_maskAssociationMassBatched) and one
+     * wait; on the sharded path the same launch writes the delete verdicts, which one all-reduce joins (see above).
+     */
     std::vector<int> cleanUpObjs(bool maskFrame, const std::map<int, emf_image_t>& matches);
     const std::vector<int>& lastDeletedObjects() const { return lastDeleted; }
     /** Reference EMFusion::preprocessDepth (EMFusion.cpp:294-305), one launch. */
@@ -480,10 +499,18 @@ private:
     };
     static SavedVolumes saveVolumes(ObjTSDF& obj);
     std::map<int, SavedVolumes> savedVolumes;              // id -> volumes of objects deleted while the log was on
-    DeviceBuffer massDev;                      // one emf_hip_maskAssociationMassBytes() block per object (cleanUpObjs)
+    DeviceBuffer massDev;       // cleanUpObjs: EMF_MAX_MODELS emf_mask_mass_t, one answer per object
+    DeviceBuffer massScratch;   // ... the row-band partials (emf_hip_maskAssociationMassScratchBytes)
+    DeviceBuffer verdictDev;    // ... sharded: EMF_MAX_MODELS float verdicts by list position (all-reduced)
+    DeviceBuffer lifecycleMsg;  // sharded: the 16-byte messages of initNewObjVolume / updateObject
     void deleteObj(int id);
+    void deleteOwned(std::list<ObjTSDF>::iterator it);  // cleanUpObjs' removal of an object of this rank
     void ensureLifecycleBuffers();
-    void* lifecycleHost = nullptr;  // pinned: emf_point_stats_t / 513 x u32 / EMF_MAX_MODELS x emf_mask_mass_t
+    void* lifecycleHost = nullptr;  // pinned: emf_point_stats_t / 513 x u32 / EMF_MAX_MODELS x emf_mask_mass_t, then
+                                    // EMF_MAX_MODELS floats (verdicts, messages), then EMF_MAX_MODELS int32 (gate)
+    static constexpr size_t kLcVerdictOff = EMF_MAX_MODELS * sizeof(emf_mask_mass_t);
+    static constexpr size_t kLcGateOff = kLcVerdictOff + EMF_MAX_MODELS * sizeof(float);
+    static constexpr size_t kLcHostBytes = kLcGateOff + EMF_MAX_MODELS * sizeof(int32_t);
 
     // ---- tracking (SURVEY f-1) ----
     void trackModels(int first, int count);    // LM-ICP of table slots [first, first + count)

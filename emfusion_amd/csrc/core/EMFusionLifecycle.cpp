@@ -62,10 +62,11 @@ void EMFusion::ensureLifecycleBuffers() {
     statsScratch = DeviceBuffer(emf_hip_pointStatsScratchBytes());
     statsDev = DeviceBuffer(sizeof(emf_point_stats_t));
     overlapDev = DeviceBuffer(513 * sizeof(uint32_t));
-    massDev = DeviceBuffer(8 * emf_hip_maskAssociationMassBytes());
+    massDev = DeviceBuffer(EMF_MAX_MODELS * sizeof(emf_mask_mass_t));
+    verdictDev = DeviceBuffer(EMF_MAX_MODELS * sizeof(float));
+    lifecycleMsg = DeviceBuffer(4 * sizeof(float));
     static_assert(EMF_MAX_MODELS * sizeof(emf_mask_mass_t) >= 513 * sizeof(uint32_t), "the larger of the two uses");
-    hipCheck(hipHostMalloc(&lifecycleHost, EMF_MAX_MODELS * sizeof(emf_mask_mass_t), hipHostMallocDefault),
-             "hipHostMalloc");
+    hipCheck(hipHostMalloc(&lifecycleHost, kLcHostBytes, hipHostMallocDefault), "hipHostMalloc");
 }
 
 emf_point_stats_t EMFusion::maskedStats(const emf_image_t& mask, const Affine3f& frame) {
@@ -104,18 +105,33 @@ float EMFusion::volumeIOU(const ObjTSDF& obj, const Vec3f& p10, const Vec3f& p90
 }
 
 int EMFusion::initNewObjVolume(const emf_image_t& mask) {
-    if (sharded)
-        throw HipError("EMFusion::initNewObjVolume: not available on the sharded path (an overlap "
-                       "test needs every object's geometry on every rank)", EMF_E_ARG);
     // world frame first: the count decides whether anything else is needed (EMFusion.cpp:501-503)
     const emf_point_stats_t world_stats = maskedStats(mask, pose);
     if (static_cast<int>(world_stats.count) < params.visibilityThresh) return -1;
-    for (const auto& obj : objects) {  // EMFusion.cpp:508-524
+    bool blocked = false;
+    for (const auto& obj : objects) {  // EMFusion.cpp:508-524 (sharded: this rank's objects)
         const emf_point_stats_t s = maskedStats(mask, obj.getPose().inv() * pose);
         const float iou = volumeIOU(obj, Vec3f(s.p10[0], s.p10[1], s.p10[2]),
                                     Vec3f(s.p90[0], s.p90[1], s.p90[2]));
-        if (iou > params.volIOUThresh) return -1;
+        if (iou > params.volIOUThresh) {
+            blocked = true;
+            break;
+        }
     }
+    if (sharded && !allIds.empty()) {
+        // the owners' verdicts joined: ONE all-reduce of a 16-byte message (a flag and padding), issued by every rank
+        // whatever its own objects said, so that every rank creates the object or none does
+        lifecycleMsg.setZero(main);
+        if (blocked) hipCheck(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lifecycleMsg.data()), 0x3f800000, 1, main.get()),
+                              "hipMemsetD32Async");
+        comm->allReduceSumF32(lifecycleMsg.as<float>(), 4, main);
+        float* h = reinterpret_cast<float*>(static_cast<char*>(lifecycleHost) + kLcVerdictOff);
+        hipCheck(hipMemcpyAsync(h, lifecycleMsg.data(), 4 * sizeof(float), hipMemcpyDeviceToHost, main.get()),
+                 "hipMemcpyAsync");
+        main.waitForCompletion();
+        blocked = h[0] > 0.f;
+    }
+    if (blocked) return -1;
     const Vec3f p10(world_stats.p10[0], world_stats.p10[1], world_stats.p10[2]);
     const Vec3f p90(world_stats.p90[0], world_stats.p90[1], world_stats.p90[2]);
     const Vec3f center = (p10 + p90) / 2.f;
@@ -132,7 +148,7 @@ int EMFusion::initNewObjVolume(const emf_image_t& mask) {
                      static_cast<int>(allIds.size()));
         return -1;
     }
-    return addObject(center, volSize);
+    return addObject(center, volSize);  // every rank; the owner allocates
 }
 
 int EMFusion::matchSegmentation(const emf_image_t& mask, float& match_iou) {
@@ -146,8 +162,7 @@ int EMFusion::matchSegmentation(const emf_image_t& mask, float& match_iou) {
     main.waitForCompletion();
     const uint32_t* c = static_cast<const uint32_t*>(lifecycleHost);
     int match_id = -1;
-    for (const auto& obj : objects) {
-        const int id = obj.getID();
+    for (const int id : allIds) {  // (every rank: the joint segmentation and visible set cover all objects)
         if (!vis_objs.count(id) || id > 255) continue;
         const float inter = static_cast<float>(c[1 + id]);
         const float uni = static_cast<float>(c[0] + c[257 + id] - c[1 + id]);
@@ -163,7 +178,6 @@ int EMFusion::matchSegmentation(const emf_image_t& mask, float& match_iou) {
 std::map<int, emf_image_t> EMFusion::initOrMatchObjs(std::vector<emf_image_t>& segs,
                                                      std::vector<int>& assigned,
                                                      const std::vector<std::vector<double>>& scores) {
-    if (sharded) throw HipError("EMFusion::initOrMatchObjs: not available on the sharded path", EMF_E_ARG);
     ensureLifecycleBuffers();
     std::map<int, emf_image_t> matches;
     std::vector<int> unmatched;
@@ -210,9 +224,9 @@ std::map<int, emf_image_t> EMFusion::initOrMatchObjs(std::vector<emf_image_t>& s
         }
     }
     // ---- initObjsFromUnmatched (EMFusion.cpp:446-494) ----
+    // (the carving loops over the job's ids, objects created earlier in this loop included: the same on every rank)
     for (int i : unmatched) {
-        for (const auto& obj : objects) {
-            const int id = obj.getID();
+        for (const int id : allIds) {
             if (id > 255) continue;
             auto it = matches.find(id);
             emfCheck(emf_hip_carveMask(&segs[i], &modelSeg, id, it == matches.end() ? nullptr : &it->second,
@@ -235,7 +249,7 @@ std::map<int, emf_image_t> EMFusion::initOrMatchObjs(std::vector<emf_image_t>& s
         if (assigned[i] < 0) assigned[i] = id;        // a replacing mask keeps scoring its model (score_matches)
     }
     bool resized = false;
-    for (auto& obj : objects) {  // EMFusion.cpp:358-369
+    for (auto& obj : objects) {  // EMFusion.cpp:358-369 (sharded: the owner's part, no exchange)
         auto it = matches.find(obj.getID());
         if (it != matches.end()) {
             // score_matches (EMFusion.cpp:442, 492): the scores of the mask that ended up with this object
@@ -281,20 +295,37 @@ Vec3f EMFusion::updateObj(ObjTSDF& obj, const emf_image_t& mask) {
 }
 
 Vec3f EMFusion::updateObject(int id, const emf_image_t& mask) {
-    if (sharded) throw HipError("EMFusion::updateObject: not available on the sharded path", EMF_E_ARG);
-    for (auto& obj : objects)
-        if (obj.getID() == id) {
-            quiesce();
-            refreshVisibleFromDevice();  // rebuildModelTable below uploads the gate from the host set
-            const Vec3f offset = updateObj(obj, mask);
-            if (poseLog) {  // several calls between two frames add up
-                Vec3f& logged = obj_pose_offsets[id][frameCount];
-                logged = logged + offset;
-            }
-            rebuildModelTable();
-            return offset;
+    if (std::find(allIds.begin(), allIds.end(), id) == allIds.end())
+        throw HipError("EMFusion::updateObject: no object " + std::to_string(id), EMF_E_ARG);
+    Vec3f offset = Vec3f::all(0.f);
+    if (ObjTSDF* obj = findObject(id)) {
+        quiesce();
+        refreshVisibleFromDevice();  // rebuildModelTable below uploads the gate from the host set
+        offset = updateObj(*obj, mask);
+        if (poseLog) {  // several calls between two frames add up
+            Vec3f& logged = obj_pose_offsets[id][frameCount];
+            logged = logged + offset;
         }
-    throw HipError("EMFusion::updateObject: no object " + std::to_string(id), EMF_E_ARG);
+        rebuildModelTable();
+    }
+    if (sharded) {  // every rank returns the owner's shift: ONE 16-byte broadcast from the owner
+        ensureLifecycleBuffers();
+        float* h = reinterpret_cast<float*>(static_cast<char*>(lifecycleHost) + kLcVerdictOff);
+        if (ownsObject(id)) {
+            h[0] = offset[0];
+            h[1] = offset[1];
+            h[2] = offset[2];
+            h[3] = 0.f;
+            hipCheck(hipMemcpyAsync(lifecycleMsg.data(), h, 4 * sizeof(float), hipMemcpyHostToDevice, main.get()),
+                     "hipMemcpyAsync");
+        }
+        comm->broadcast(lifecycleMsg.data(), 4 * sizeof(float), ownerOf(id, world), main);
+        hipCheck(hipMemcpyAsync(h, lifecycleMsg.data(), 4 * sizeof(float), hipMemcpyDeviceToHost, main.get()),
+                 "hipMemcpyAsync");
+        main.waitForCompletion();
+        offset = Vec3f(h[0], h[1], h[2]);
+    }
+    return offset;
 }
 
 void EMFusion::deleteObj(int id) {  // reference EMFusion.cpp:982-989
@@ -307,57 +338,106 @@ void EMFusion::deleteObj(int id) {  // reference EMFusion.cpp:982-989
     trackResults.erase(id);
 }
 
+// The deletion of an object of this rank (EMFusion.cpp:951-976); the caller rebuilds the table afterwards.
+void EMFusion::deleteOwned(std::list<ObjTSDF>::iterator it) {
+    const int id = it->getID();
+    quiesce();  // nothing in flight may still use the volume
+    deleteObj(id);
+    if (poseLog && !(ignorePerson && isPerson(*it))) {
+        meshes[id] = it->getMesh();  // saveOutput: EMFusion.cpp:962-966
+        if (expVols) savedVolumes[id] = saveVolumes(*it);  // EMFusion.cpp:967-973
+    }
+    objects.erase(it);
+}
+
 std::vector<int> EMFusion::cleanUpObjs(bool maskFrame, const std::map<int, emf_image_t>& matches) {
-    if (sharded) throw HipError("EMFusion::cleanUpObjs: not available on the sharded path", EMF_E_ARG);
-    std::set<int> spurious;
-    if (maskFrame)
-        for (const auto& obj : objects)
-            if (obj.getExProb() < params.existenceThresh) spurious.insert(obj.getID());
     ensureLifecycleBuffers();
-    // The association mass of EVERY object of this rank is enqueued before the host waits for anything: ONE
-    // synchronisation per frame then yields both the visible set (it decides whose mass counts, EMFusion.cpp:936) and
-    // the masses (rounds 3-5: one wait for the visible set, then a launch, a copy and a wait per visible object).
-    const size_t nobj = objects.size();
-    const size_t stride = emf_hip_maskAssociationMassBytes();
-    if (massDev.bytes() < nobj * stride) massDev = DeviceBuffer(std::max(nobj, size_t(8)) * stride);
-    emf_mask_mass_t* const massHost = static_cast<emf_mask_mass_t*>(lifecycleHost);  // pinned, EMF_MAX_MODELS entries
-    size_t k = 0;
+    // The association masses of EVERY object of this rank in two launches over the model table (slots 1 .. n), before
+    // the host waits for anything: ONE synchronisation per frame then yields both the visible set (it decides whose
+    // mass counts, EMFusion.cpp:936) and the masses (rounds 3-5: a wait for the visible set, then a launch, a copy and
+    // a wait per visible object; until the batched entry: two launches per object).
+    const int nobj = static_cast<int>(objects.size());
+    const int nall = static_cast<int>(allIds.size());
+    const int w = params.frameSize.width, h = params.frameSize.height;
+    std::vector<emf_image_t> matchImgs(static_cast<size_t>(nobj), emf_image_t{});
+    std::vector<uint8_t> exLow(static_cast<size_t>(nobj), 0);
+    std::vector<int32_t> listPos(static_cast<size_t>(nobj), 0);
+    int k = 0;
     for (const auto& obj : objects) {
-        const ObjImages& im = objImages.at(obj.getID());
-        const emf_image_t seg = im.modelSegmentation.view(), assoc = im.associationWeights.view();
         auto it = matches.find(obj.getID());
-        emfCheck(emf_hip_maskAssociationMass(&seg, it == matches.end() ? nullptr : &it->second, &assoc,
-                                             reinterpret_cast<emf_mask_mass_t*>(static_cast<char*>(massDev.data()) + k * stride),
-                                             main.abi()),
-                 "maskAssociationMass");
+        if (it != matches.end()) matchImgs[k] = it->second;
+        exLow[k] = maskFrame && obj.getExProb() < params.existenceThresh;  // (owner-only fact, mask frames)
+        listPos[k] = static_cast<int32_t>(std::find(allIds.begin(), allIds.end(), obj.getID()) - allIds.begin());
         ++k;
     }
-    if (nobj)  // the answers (first entry of every object's block) in one strided copy
-        hipCheck(hipMemcpy2DAsync(massHost, sizeof(emf_mask_mass_t), massDev.data(), stride, sizeof(emf_mask_mass_t), nobj,
-                                  hipMemcpyDeviceToHost, main.get()),
-                 "hipMemcpy2DAsync(mask masses)");
-    main.waitForCompletion();
-    refreshVisibleFromDevice();  // the host copy of vis_objs decides (the stream is idle: no further wait)
-    k = 0;
-    for (const auto& obj : objects) {
-        const emf_mask_mass_t mm = massHost[k++];
-        if (vis_objs.count(obj.getID()) && params.assocThresh * static_cast<float>(mm.count) > mm.sum) spurious.insert(obj.getID());
-    }
+    const size_t scratchBytes = emf_hip_maskAssociationMassScratchBytes(nobj);
+    if (massScratch.bytes() < scratchBytes) massScratch = DeviceBuffer(scratchBytes);
     std::vector<int> deleted;
-    for (auto it = objects.begin(); it != objects.end();) {
-        const int id = it->getID();
-        if (spurious.count(id) || !vis_objs.count(id)) {
-            deleted.push_back(id);
-            quiesce();  // nothing in flight may still use the volume
-            deleteObj(id);
-            if (poseLog && !(ignorePerson && isPerson(*it))) {
-                meshes[id] = it->getMesh();  // saveOutput: EMFusion.cpp:962-966
-                if (expVols) savedVolumes[id] = saveVolumes(*it);  // EMFusion.cpp:967-973
-            }
-            it = objects.erase(it);
-        } else {
-            ++it;
+    if (!sharded) {
+        if (nobj) {
+            emfCheck(emf_hip_maskAssociationMassBatched(currentTable(), 1, nobj, w, h, matchImgs.data(), massScratch.data(),
+                                                        massDev.as<emf_mask_mass_t>(), nullptr, 0, nullptr, nullptr,
+                                                        nullptr, 0.f, main.abi()),
+                     "maskAssociationMassBatched");
+            hipCheck(hipMemcpyAsync(lifecycleHost, massDev.data(), nobj * sizeof(emf_mask_mass_t), hipMemcpyDeviceToHost,
+                                    main.get()),
+                     "hipMemcpyAsync(mask masses)");
         }
+        main.waitForCompletion();
+        refreshVisibleFromDevice();  // the host copy of vis_objs decides (the stream is idle: no further wait)
+        const emf_mask_mass_t* const massHost = static_cast<const emf_mask_mass_t*>(lifecycleHost);
+        std::set<int> spurious;
+        k = 0;
+        for (const auto& obj : objects) {
+            const emf_mask_mass_t mm = massHost[k];
+            if (exLow[k] || (vis_objs.count(obj.getID()) && params.assocThresh * static_cast<float>(mm.count) > mm.sum))
+                spurious.insert(obj.getID());
+            ++k;
+        }
+        for (auto it = objects.begin(); it != objects.end();) {
+            const int id = it->getID();
+            if (spurious.count(id) || !vis_objs.count(id)) {
+                deleted.push_back(id);
+                deleteOwned(it++);
+            } else {
+                ++it;
+            }
+        }
+        if (!deleted.empty()) rebuildModelTable();
+        return deleted;
+    }
+    // Sharded: the owners' verdicts by list position, joined by ONE all-reduce -- issued whenever the job has objects,
+    // also by a rank that owns none -- one copy back and one wait; every rank then deletes the same ids in list order.
+    if (nall == 0) return deleted;
+    if (!batched) {
+        // the per-volume composite decides visibility on the host and leaves the device gate alone: make it current
+        int32_t* gate = reinterpret_cast<int32_t*>(static_cast<char*>(lifecycleHost) + kLcGateOff);
+        gate[0] = 1;
+        k = 1;
+        for (const auto& obj : objects) gate[k++] = vis_objs.count(obj.getID()) ? 1 : 0;
+        hipCheck(hipMemcpyAsync(visibleDev.data(), gate, (nobj + 1) * sizeof(int32_t), hipMemcpyHostToDevice, main.get()),
+                 "hipMemcpyAsync(gate)");
+    }
+    const int nslots = (nall + 3) / 4 * 4;
+    emfCheck(emf_hip_maskAssociationMassBatched(currentTable(), 1, nobj, w, h, matchImgs.data(), massScratch.data(),
+                                                massDev.as<emf_mask_mass_t>(), verdictDev.as<float>(), nall,
+                                                listPos.data(), visibleDev.as<int32_t>(), exLow.data(),
+                                                params.assocThresh, main.abi()),
+             "maskAssociationMassBatched");
+    comm->allReduceSumF32(verdictDev.as<float>(), static_cast<size_t>(nslots), main);
+    float* verdict = reinterpret_cast<float*>(static_cast<char*>(lifecycleHost) + kLcVerdictOff);
+    hipCheck(hipMemcpyAsync(verdict, verdictDev.data(), nall * sizeof(float), hipMemcpyDeviceToHost, main.get()),
+             "hipMemcpyAsync(verdicts)");
+    main.waitForCompletion();
+    refreshVisibleFromDevice();
+    const std::vector<int> ids = allIds;
+    for (int p = 0; p < nall; ++p) {
+        if (!(verdict[p] > 0.f)) continue;
+        const int id = ids[p];
+        deleted.push_back(id);
+        auto it = std::find_if(objects.begin(), objects.end(), [&](const ObjTSDF& o) { return o.getID() == id; });
+        if (it != objects.end()) deleteOwned(it);
+        else deleteObj(id);
     }
     if (!deleted.empty()) rebuildModelTable();
     return deleted;

@@ -14,6 +14,8 @@
 // round trips per object) is one kernel that counts intersection and union for all objects.
 #include "mesh_core.hpp"
 
+#include <algorithm>
+
 namespace emf_hip {
 namespace {
 
@@ -299,32 +301,49 @@ __global__ __launch_bounds__(kLcBlock) void k_carve_mask(const CarveArgs a) {
 
 // ---- association mass under an object's mask (cleanUpObjs, EMFusion.cpp:936-949) ----------------
 
+// Where a model's two images come from: the model table (slot first + k: emf_model_t::hitMask / ::assoc, continuous
+// W x H) or, for the level-1 entry, the arguments (one object, any pitch).
+struct MassSource {
+    const emf_model_t* models;  // table slots [first, first + n), or nullptr
+    Img<const uint8_t> objSeg;  // models == nullptr: the object's own raycast mask (0 / 1)
+    Img<const float> assoc;     // ... and its association weights
+};
+
 struct MassArgs {
-    Img<const uint8_t> objSeg;  // the object's own raycast mask (0 / 1)
-    Img<const uint8_t> match;   // matched instance mask or data == nullptr
-    Img<const float> assoc;     // the object's association weights
+    MassSource src;
+    Img<const uint8_t> match[EMF_MAX_BATCH];  // matched instance mask of object k of this chunk, data == nullptr: none
     int w, h;
-    emf_mask_mass_t* out;
+    emf_mask_mass_t* partials;                // object k of this chunk: kMassBlocks partials at partials + k * kMassBlocks
 };
 
 // Two launches, fixed summation order (deterministic).  cleanUpObjs runs in EVERY frame of the reference's entry point,
 // once per visible object, with the host waiting for the answer: the one-workgroup form of rounds 3-5 (1024 lanes x 300
 // pixels each, an integer division per pixel) took 199 us of a 2.1 ms tracked frame (round 6, kernel trace of
-// `bench.py --track`).  Now kMassBlocks workgroups take bands of whole image rows (no division; a lane's pixels in row
-// order, a wave's lanes by the xor tree, the block's waves in index order) and leave a partial each behind out[0];
-// k_mask_mass_finish adds the partials in block order.
+// `bench.py --track`).  Now kMassBlocks workgroups per object take bands of whole image rows (no division; a lane's
+// pixels in row order, a wave's lanes by the xor tree, the block's waves in index order) and leave a partial each;
+// k_mask_mass_finish adds each object's partials in block order.  blockIdx.y = the object within the launch's chunk
+// (at most EMF_MAX_BATCH: the match masks travel in the arguments); the level-1 entry is the one-object case.
 constexpr int kMassBlocks = 240;
 __global__ __launch_bounds__(256) void k_mask_mass(const MassArgs a) {
     __shared__ double sums[4];
     __shared__ unsigned counts[4];
+    const int k = blockIdx.y;
+    Img<const uint8_t> objSeg = a.src.objSeg;
+    Img<const float> assoc = a.src.assoc;
+    if (a.src.models) {
+        const emf_model_t* m = a.src.models + k;
+        objSeg = Img<const uint8_t>{m->hitMask, static_cast<size_t>(a.w)};
+        assoc = Img<const float>{m->assoc, static_cast<size_t>(a.w) * sizeof(float)};
+    }
+    const Img<const uint8_t> match = a.match[k];
     const int rows = (a.h + kMassBlocks - 1) / kMassBlocks;
     const int y0 = blockIdx.x * rows, y1 = min(y0 + rows, a.h);
     double s = 0.0;
     unsigned c = 0;
     for (int y = y0; y < y1; ++y) {
-        const uint8_t* seg = a.objSeg.row(y);
-        const uint8_t* mt = a.match.data ? a.match.row(y) : nullptr;
-        const float* as = a.assoc.row(y);
+        const uint8_t* seg = objSeg.row(y);
+        const uint8_t* mt = match.data ? match.row(y) : nullptr;
+        const float* as = assoc.row(y);
         for (int x = threadIdx.x; x < a.w; x += 256)
             if (seg[x] != 0 || (mt && mt[x] != 0)) {
                 s += static_cast<double>(as[x]);
@@ -348,16 +367,46 @@ __global__ __launch_bounds__(256) void k_mask_mass(const MassArgs a) {
             ts += sums[i];
             tc += counts[i];
         }
-        a.out[1 + blockIdx.x].count = tc;
-        a.out[1 + blockIdx.x].sum = ts;
+        emf_mask_mass_t* p = a.partials + static_cast<size_t>(k) * kMassBlocks + blockIdx.x;
+        p->count = tc;
+        p->sum = ts;
     }
 }
-__global__ __launch_bounds__(64) void k_mask_mass_finish(emf_mask_mass_t* out) {
+
+// cleanUpObjs' verdict per object, written at its position in the job's creation-order list (allIds): 1 = delete.
+// Every other position of the array (objects of other ranks, the padding to a multiple of 4) gets 0, so the ranks'
+// arrays can be summed.
+struct MassVerdictArgs {
+    float* verdict;                         // nslots floats, or nullptr: no verdicts
+    int nslots;                             // round_up(nall, 4)
+    const int32_t* visible;                 // the integrate gate of slots [first, first + n) (visibleDev + first)
+    float assocThresh;
+    uint32_t exLow[EMF_MAX_MODELS / 32];    // bit k: object k's existence probability is below the threshold
+    uint32_t local[EMF_MAX_MODELS / 32];    // bit p: list position p is one of the n objects
+    uint8_t listPos[EMF_MAX_MODELS];        // object k's list position
+};
+
+struct MassFinishArgs {
+    const emf_mask_mass_t* partials;  // n x kMassBlocks
+    emf_mask_mass_t* out;             // n answers
+    int n;
+    MassVerdictArgs v;
+};
+
+// blocks [0, n): object blockIdx.x; block n (verdicts only): the zeros at the positions no object of this call holds
+__global__ __launch_bounds__(64) void k_mask_mass_finish(const MassFinishArgs a) {
+    const int k = blockIdx.x;
+    if (k == a.n) {
+        for (int p = threadIdx.x; p < a.v.nslots; p += 64)
+            if (!((a.v.local[p >> 5] >> (p & 31)) & 1u)) a.v.verdict[p] = 0.f;
+        return;
+    }
+    const emf_mask_mass_t* part = a.partials + static_cast<size_t>(k) * kMassBlocks;
     double s = 0.0;
     unsigned c = 0;
     for (int b = threadIdx.x; b < kMassBlocks; b += 64) {  // (a lane's partials in block order, then the xor tree)
-        s += out[1 + b].sum;
-        c += out[1 + b].count;
+        s += part[b].sum;
+        c += part[b].count;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -365,8 +414,17 @@ __global__ __launch_bounds__(64) void k_mask_mass_finish(emf_mask_mass_t* out) {
         c += __shfl_xor(c, o);
     }
     if (threadIdx.x == 0) {
-        out[0].count = c;
-        out[0].sum = s;
+        a.out[k].count = c;
+        a.out[k].sum = s;
+        if (a.v.verdict) {
+            // the host rule of cleanUpObjs (EMFusion.cpp:936-951): spurious by existence probability (mask frames), or
+            // visible with too little mass -- assocThresh * count is a float product, compared in double -- or invisible
+            const float need = a.v.assocThresh * static_cast<float>(c);
+            const bool light = static_cast<double>(need) > s;
+            const bool exLow = (a.v.exLow[k >> 5] >> (k & 31)) & 1u;
+            const bool vis = a.v.visible[k] != 0;
+            a.v.verdict[a.v.listPos[k]] = (exLow || !vis || light) ? 1.f : 0.f;
+        }
     }
 }
 
@@ -505,19 +563,93 @@ int emf_hip_maskAssociationMass(const emf_image_t* objSeg, const emf_image_t* ma
         EMF_TRY(check_same_size(objSeg, matchMask, "objSeg", "matchMask"));
     }
     EMF_REQUIRE_PTR(out_dev);
-    MassArgs a;
-    a.objSeg = img<const uint8_t>(objSeg);
-    a.match = matchMask ? img<const uint8_t>(matchMask) : Img<const uint8_t>{nullptr, 0};
-    a.assoc = img<const float>(assoc);
+    // the one-object case of the batched kernels: the answer in out_dev[0], the partials behind it
+    MassArgs a{};
+    a.src.models = nullptr;
+    a.src.objSeg = img<const uint8_t>(objSeg);
+    a.src.assoc = img<const float>(assoc);
+    a.match[0] = matchMask ? img<const uint8_t>(matchMask) : Img<const uint8_t>{nullptr, 0};
     a.w = objSeg->width;
     a.h = objSeg->height;
-    a.out = out_dev;
-    hipLaunchKernelGGL(k_mask_mass, dim3(kMassBlocks), dim3(256), 0, as_stream(stream), a);
-    hipLaunchKernelGGL(k_mask_mass_finish, dim3(1), dim3(64), 0, as_stream(stream), out_dev);
+    a.partials = out_dev + 1;
+    MassFinishArgs f{};
+    f.partials = out_dev + 1;
+    f.out = out_dev;
+    f.n = 1;
+    hipLaunchKernelGGL(k_mask_mass, dim3(kMassBlocks, 1), dim3(256), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(k_mask_mass_finish, dim3(1), dim3(64), 0, as_stream(stream), f);
     return launch_status("maskAssociationMass");
 }
 
 size_t emf_hip_maskAssociationMassBytes(void) { return (1 + static_cast<size_t>(kMassBlocks)) * sizeof(emf_mask_mass_t); }
+
+size_t emf_hip_maskAssociationMassScratchBytes(int n) {
+    if (n < 0 || n > EMF_MAX_MODELS) return 0;
+    return static_cast<size_t>(std::max(n, 1)) * kMassBlocks * sizeof(emf_mask_mass_t);
+}
+
+int emf_hip_maskAssociationMassBatched(const emf_model_t* models_dev, int first, int n, int width, int height,
+                                       const emf_image_t* matchMasks_host, void* scratch_dev, emf_mask_mass_t* out_dev,
+                                       float* verdict_dev, int nall, const int32_t* listPos_host,
+                                       const int32_t* visible_dev, const uint8_t* exLow_host, float assocThresh,
+                                       emf_stream_t stream) {
+    if (n < 0 || first < 0 || first + n > EMF_MAX_MODELS)
+        return fail(EMF_E_ARG, "maskAssociationMassBatched: slots [%d, %d + %d) outside the table", first, first, n);
+    if (width < 1 || height < 1) return fail(EMF_E_SHAPE, "maskAssociationMassBatched: %d x %d images", width, height);
+    if (n > 0) {
+        EMF_REQUIRE_PTR(models_dev);
+        EMF_REQUIRE_PTR(scratch_dev);
+        EMF_REQUIRE_PTR(out_dev);
+    }
+    MassFinishArgs f{};
+    f.partials = static_cast<const emf_mask_mass_t*>(scratch_dev);
+    f.out = out_dev;
+    f.n = n;
+    if (verdict_dev) {
+        if (nall < n || nall > EMF_MAX_MODELS - 1)
+            return fail(EMF_E_ARG, "maskAssociationMassBatched: %d objects in the job, %d in the call", nall, n);
+        if (n > 0) {
+            EMF_REQUIRE_PTR(listPos_host);
+            EMF_REQUIRE_PTR(visible_dev);
+        }
+        f.v.verdict = verdict_dev;
+        f.v.nslots = (nall + 3) / 4 * 4;
+        f.v.visible = visible_dev ? visible_dev + first : nullptr;
+        f.v.assocThresh = assocThresh;
+        for (int k = 0; k < n; ++k) {
+            const int p = listPos_host[k];
+            if (p < 0 || p >= nall) return fail(EMF_E_ARG, "maskAssociationMassBatched: list position %d of %d", p, nall);
+            f.v.listPos[k] = static_cast<uint8_t>(p);
+            f.v.local[p >> 5] |= 1u << (p & 31);
+            if (exLow_host && exLow_host[k]) f.v.exLow[k >> 5] |= 1u << (k & 31);
+        }
+    }
+    const int w = width, h = height;
+    if (matchMasks_host)
+        for (int k = 0; k < n; ++k)
+            if (matchMasks_host[k].data) {
+                EMF_TRY(check_image(&matchMasks_host[k], 1, "maskAssociationMassBatched: matchMask"));
+                if (matchMasks_host[k].width != w || matchMasks_host[k].height != h)
+                    return fail(EMF_E_SHAPE, "maskAssociationMassBatched: match mask %d is %d x %d, not %d x %d", k,
+                                matchMasks_host[k].width, matchMasks_host[k].height, w, h);
+            }
+    hipStream_t s = as_stream(stream);
+    for (int c0 = 0; c0 < n; c0 += EMF_MAX_BATCH) {  // the match masks travel in the arguments: chunks of EMF_MAX_BATCH
+        const int cn = std::min(EMF_MAX_BATCH, n - c0);
+        MassArgs a{};
+        a.src.models = models_dev + first + c0;
+        for (int k = 0; k < cn; ++k)
+            a.match[k] = matchMasks_host && matchMasks_host[c0 + k].data ? img<const uint8_t>(&matchMasks_host[c0 + k])
+                                                                          : Img<const uint8_t>{nullptr, 0};
+        a.w = w;
+        a.h = h;
+        a.partials = static_cast<emf_mask_mass_t*>(scratch_dev) + static_cast<size_t>(c0) * kMassBlocks;
+        hipLaunchKernelGGL(k_mask_mass, dim3(kMassBlocks, cn), dim3(256), 0, s, a);
+    }
+    const int blocks = n + (verdict_dev ? 1 : 0);
+    if (blocks) hipLaunchKernelGGL(k_mask_mass_finish, dim3(blocks), dim3(64), 0, s, f);
+    return launch_status("maskAssociationMassBatched");
+}
 
 int emf_hip_maskOverlap(const emf_image_t* seg, const emf_image_t* modelSeg, uint32_t* counts_dev,
                         emf_stream_t stream) {

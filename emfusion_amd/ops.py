@@ -768,6 +768,49 @@ def extract_meshes(volumes, stream=None):
     return out
 
 
+def mask_association_masses(hit_masks, assocs, match_masks=None, verdict=None, stream=None):
+    """emf_hip_maskAssociationMassBatched: cleanUpObjs' (count, sum) for n objects in one pass over a model table.
+    hit_masks / assocs: n unpadded device images (u8 / f32 W x H), the objects' raycast masks and association weights,
+    placed at table slots 1 .. n behind an empty slot 0 (as in the product's table); match_masks: None or n entries,
+    each a device image or None.  verdict: None, or dict(nall=, list_pos=[n ints], visible=[n 0/1], ex_low=[n 0/1],
+    assoc_thresh=) for the delete verdicts by list position.  Returns (counts (n,) uint32, sums (n,) float64,
+    verdicts (round_up(nall, 4),) float32 or None); synchronises."""
+    n = len(hit_masks)
+    assert len(assocs) == n and (match_masks is None or len(match_masks) == n)
+    h, w = hit_masks[0].shape[:2] if n else (1, 1)
+    models = [_lib.EmfModel()]
+    for hm, a in zip(hit_masks, assocs):
+        assert not hm.padded and not a.padded and hm.shape[:2] == (h, w) and a.shape[:2] == (h, w)
+        m = _lib.EmfModel()
+        m.hitMask, m.assoc = hm.ptr, a.ptr
+        models.append(m)
+    table = upload_models(models)
+    imgs = (EmfImage * max(n, 1))()
+    for k in range(n):
+        mm = None if match_masks is None else match_masks[k]
+        if mm is not None:
+            imgs[k] = image_view(mm)
+    scratch = DeviceArray.zeros((max(int(_L.emf_hip_maskAssociationMassScratchBytes(n)) // 8, 2),), np.float64)
+    out = DeviceArray.zeros((max(n, 1), 2), np.float64)
+    vd, nall, lp, vis, ex, thr = None, 0, None, None, None, 0.0
+    if verdict is not None:
+        nall = int(verdict["nall"])
+        vd = DeviceArray.full(((nall + 3) // 4 * 4 or 4,), 7.0, np.float32)  # all of it must be overwritten
+        lp = (C.c_int32 * max(n, 1))(*[int(p) for p in verdict["list_pos"]])
+        slots = np.zeros(n + 1, np.int32)
+        slots[1:] = np.asarray(verdict["visible"], np.int32)
+        vis = DeviceArray.from_numpy(slots)
+        ex = (C.c_uint8 * max(n, 1))(*[int(bool(e)) for e in verdict.get("ex_low", [0] * n)])
+        thr = float(verdict["assoc_thresh"])
+    check("emf_hip_maskAssociationMassBatched",
+          _L.emf_hip_maskAssociationMassBatched(_ptr(table), 1, n, w, h, imgs if match_masks is not None else None,
+                                                _ptr(scratch), _ptr(out), _ptr(vd), nall, lp, _ptr(vis), ex, thr,
+                                                _stream(stream)))
+    raw = out.numpy()[:n]
+    counts = raw[:, 1].copy().view(np.uint32)[::2] if n else np.zeros(0, np.uint32)
+    return counts, raw[:, 0].copy(), (None if vd is None else vd.numpy()[:(nall + 3) // 4 * 4])
+
+
 def copy_values(src, dst, offset, stream=None):
     """dst(v) = src(v + offset) inside src, else 0 (kernel_copyValues); volumes (Nz, Ny, Nx[, C])."""
     ch = 1 if len(src.shape) == 3 else src.shape[3]

@@ -393,7 +393,8 @@ class Communicator:
         return _json.loads(buf.value.decode())
 
     def exchanges(self) -> int:
-        """Exchanges issued so far through a delayed() communicator (0 for the others)."""
+        """Exchanges issued so far (a group counts once) through a delayed(), peer or local-group communicator (0 for the
+        others)."""
         n = C.c_uint64(0)
         _check("emf_comm_exchanges", load().emf_comm_exchanges(self._h, C.byref(n)))
         return int(n.value)

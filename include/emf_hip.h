@@ -798,6 +798,26 @@ int emf_hip_maskAssociationMass(const emf_image_t* objSeg, const emf_image_t* ma
                                 const emf_image_t* assoc, emf_mask_mass_t* out_dev,
                                 emf_stream_t stream);
 
+/* The association test of EMFusion::cleanUpObjs (EMFusion.cpp:922-980) over a model TABLE (level 3): the objects are
+ * the slots [first, first + n) of models_dev (emf_model_t::hitMask = the object's raycast mask, ::assoc = its
+ * association weights, both continuous width x height).  matchMasks_host: HOST array of n images, the mask matched
+ * to object k this frame (data == NULL: none), or NULL = no masks.  One launch per EMF_MAX_BATCH objects (the masks
+ * travel in the arguments), one finish launch for all.  out_dev[k] is byte for byte what emf_hip_maskAssociationMass
+ * gives for object k alone (the level-1 entry is the one-object case of the same kernels).
+ *   scratch_dev: emf_hip_maskAssociationMassScratchBytes(n) bytes (the row-band partials; 0 returned for a bad n)
+ *   0 <= n <= EMF_MAX_MODELS - 1; n == 0 launches nothing unless verdicts are asked for.
+ * Verdicts (verdict_dev != NULL): round_up(nall, 4) floats, all written: at listPos_host[k] (object k's position in
+ * the job's creation-order list of nall objects) 1 if cleanUpObjs deletes it, else 0; 0 at every other position.  The
+ * host rule (EMFusion.cpp:930-951): exLow_host[k] != 0 (existence probability below the threshold on a mask frame;
+ * NULL = none) or visible_dev[first + k] == 0 (the integrate gate of the table, int32 per slot) or
+ * double(assocThresh * float(count)) > sum.  Sharded ranks all-reduce (sum) the arrays: the joint verdicts. */
+size_t emf_hip_maskAssociationMassScratchBytes(int n);
+int emf_hip_maskAssociationMassBatched(const emf_model_t* models_dev, int first, int n, int width, int height,
+                                       const emf_image_t* matchMasks_host, void* scratch_dev, emf_mask_mass_t* out_dev,
+                                       float* verdict_dev, int nall, const int32_t* listPos_host,
+                                       const int32_t* visible_dev, const uint8_t* exLow_host, float assocThresh,
+                                       emf_stream_t stream);
+
 /* The counts behind EMFusion::matchSegmentation (EMFusion.cpp:797-825) for ALL objects at once:
  * counts_dev[0] = pixels of `seg`; counts_dev[1 + id] = |seg AND (modelSeg == id)|;
  * counts_dev[257 + id] = |modelSeg == id|, id = 1..255 (513 uint32, cleared by the call).
