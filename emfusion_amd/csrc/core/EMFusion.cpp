@@ -943,22 +943,9 @@ void EMFusion::compositeAndVisibility(bool deviceGate) {
         compositeAcrossRanks(deviceGate);
         return;
     }
-    std::vector<int32_t> ids;
-    std::vector<emf_image_t> oray, overt, onorm, oseg;
-    for (auto& obj : objects) {
-        ObjImages& im = objImages.at(obj.getID());
-        ids.push_back(obj.getID());
-        oray.push_back(im.raylengths.view());
-        overt.push_back(im.vertices.view());
-        onorm.push_back(im.normals.view());
-        oseg.push_back(im.modelSegmentation.view());
-    }
-    const emf_image_t v_bgRay = bg_raylengths.view(), v_bgVert = bg_vertices.view(),
-                      v_bgNorm = bg_normals.view(), v_bgMask = bg_mask.view(),
-                      v_ray = raylengths.view(), v_vert = vertices.view(),
-                      v_norm = normals.view(), v_seg = modelSegmentation.view(),
-                      v_diff = diffRaylengths.view(), v_noObj = noObjMask.view();
-    const int nobj = static_cast<int>(ids.size());
+    const ObjectViews o = objectViews(false);
+    const FrameViews f = frameViews();
+    const int nobj = static_cast<int>(o.index.size());
     {
         auto kt = ktimers.scope(KernelTimers::Composite, pixels() * (1.0 + nobj), main);
         if (deviceGate && fuseVisibility) {
@@ -966,18 +953,17 @@ void EMFusion::compositeAndVisibility(bool deviceGate) {
             // the flag kernel, which leaves visCounts cleared for the next frame
             if (!visCountsClear) visCounts.setZero(main);  // (another path left its numbers there)
             visCountsClear = true;
-            emfCheck(emf_hip_compositeVisibility(nobj, ids.data(), oray.data(), overt.data(), onorm.data(),
-                                                 oseg.data(), &v_bgRay, &v_bgVert, &v_bgNorm, &v_bgMask, &v_ray,
-                                                 &v_vert, &v_norm, &v_seg, &v_diff, &v_noObj, params.boundary,
+            emfCheck(emf_hip_compositeVisibility(nobj, o.index.data(), o.ray.data(), o.vert.data(), o.norm.data(),
+                                                 o.seg.data(), &f.bgRay, &f.bgVert, &f.bgNorm, &f.bgMask, &f.ray,
+                                                 &f.vert, &f.norm, &f.seg, &f.diff, &f.noObj, params.boundary,
                                                  visCounts.as<int32_t>(), params.visibilityThresh,
                                                  visibleDev.as<int32_t>(), visibleHost, main.abi()),
                      "compositeVisibility");
         } else {
             visCountsClear = false;
-            emfCheck(emf_hip_compositeRaycast(nobj, ids.data(), oray.data(), overt.data(),
-                                              onorm.data(), oseg.data(), &v_bgRay, &v_bgVert,
-                                              &v_bgNorm, &v_bgMask, &v_ray, &v_vert, &v_norm, &v_seg,
-                                              &v_diff, &v_noObj, params.boundary,
+            emfCheck(emf_hip_compositeRaycast(nobj, o.index.data(), o.ray.data(), o.vert.data(), o.norm.data(),
+                                              o.seg.data(), &f.bgRay, &f.bgVert, &f.bgNorm, &f.bgMask, &f.ray,
+                                              &f.vert, &f.norm, &f.seg, &f.diff, &f.noObj, params.boundary,
                                               visCounts.as<int32_t>(), main.abi()),
                      "compositeRaycast");
             if (deviceGate)  // the counts also go to pinned host memory straight from the kernel
@@ -988,19 +974,47 @@ void EMFusion::compositeAndVisibility(bool deviceGate) {
         }
     }
     stamp(kComposite);
+    visibleFromCounts(o.index, deviceGate, deviceGate);  // (the device gate's kernels have mirrored the counts)
+}
+
+EMFusion::ObjectViews EMFusion::objectViews(bool byListPosition) {
+    ObjectViews o;
+    for (auto& obj : objects) {
+        const int id = obj.getID();
+        ObjImages& im = objImages.at(id);
+        o.index.push_back(byListPosition ? static_cast<int32_t>(std::find(allIds.begin(), allIds.end(), id) - allIds.begin())
+                                         : id);
+        o.ray.push_back(im.raylengths.view());
+        o.vert.push_back(im.vertices.view());
+        o.norm.push_back(im.normals.view());
+        o.seg.push_back(im.modelSegmentation.view());
+    }
+    return o;
+}
+
+EMFusion::FrameViews EMFusion::frameViews() {
+    return {bg_raylengths.view(), bg_vertices.view(), bg_normals.view(), bg_mask.view(), raylengths.view(),
+            vertices.view(), normals.view(), modelSegmentation.view(), diffRaylengths.view(), noObjMask.view()};
+}
+
+// The visibility counts of the objects `ids` (visCounts, in that order) become the visible set.  deviceGate: the
+// gate was made on the device, the counts are read from the pinned mirror when somebody asks (visPending);
+// otherwise wait for them here (the reference's behaviour).  mirrored: a kernel has written them to that mirror.
+void EMFusion::visibleFromCounts(const std::vector<int32_t>& ids, bool deviceGate, bool mirrored) {
     vis_objs.clear();
     visPending = false;
-    if (nobj == 0) return;
+    if (ids.empty()) return;
+    if (!mirrored)
+        hipCheck(hipMemcpyAsync(deviceGate ? visibleHost : visCountsHost, visCounts.data(), sizeof(int32_t) * ids.size(),
+                                hipMemcpyDeviceToHost, main.get()),
+                 "visCounts D2H");
     if (deviceGate) {
         visIds = ids;
         visPending = true;
         return;
     }
-    hipCheck(hipMemcpyAsync(visCountsHost, visCounts.data(), sizeof(int32_t) * nobj,
-                            hipMemcpyDeviceToHost, main.get()),
-             "visCounts D2H");
     main.waitForCompletion();  // the visible set gates integrateDepth (EMFusion.cpp:869-872)
-    for (int k = 0; k < nobj; ++k)
+    for (size_t k = 0; k < ids.size(); ++k)
         if (visCountsHost[k] > params.visibilityThresh) vis_objs.insert(ids[k]);
 }
 

@@ -378,6 +378,17 @@ private:
     void integrateBatched();
     void compositeAndVisibility(bool deviceGate);
     void compositeAcrossRanks(bool deviceGate);
+    struct ObjectViews {  // the owned objects' raycast images, creation order
+        std::vector<int32_t> index;  // per object: its id, or its position in allIds
+        std::vector<emf_image_t> ray, vert, norm, seg;
+    };
+    ObjectViews objectViews(bool byListPosition);
+    struct FrameViews {  // the composite's ten frame images, in the order of the ABI's arguments
+        emf_image_t bgRay, bgVert, bgNorm, bgMask, ray, vert, norm, seg, diff, noObj;
+    };
+    FrameViews frameViews();
+    void visibleFromCounts(const std::vector<int32_t>& ids, bool deviceGate, bool mirrored);
+    void reduceAndNormalize(const std::vector<emf_image_t>& maps, bool timed);
     void refreshVisibleFromDevice();
     // legacy path: one stream per volume, host-side visibility gate (reference structure)
     void estepPerVolume();

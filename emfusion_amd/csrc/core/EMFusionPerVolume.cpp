@@ -58,10 +58,7 @@ void EMFusion::estepPerVolume() {
     } else {
         objPartialSum.setZero(main);
     }
-    comm->allReduceSumF32(objPartialSum.ptr(), params.frameSize.area(), main);
-    emfCheck(emf_hip_normalizeAssociation(maps.data(), static_cast<int>(maps.size()), 1, &sv, &nv,
-                                          main.abi()),
-             "normalizeAssociation");
+    reduceAndNormalize(maps, false);  // (inside the bracket above)
 }
 
 void EMFusion::raycastPerVolume() {

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <exception>
+#include <optional>
 
 namespace emf {
 
@@ -46,12 +47,19 @@ void EMFusion::estepSharded(const std::vector<emf_pose_t>& co, bool fromDepth) {
     // (Measured and dropped, round 3: the frame's LAST all-reduce + normalisation on a stream of their own beside
     // the raycast -- they feed the integrations only.  With a 30 us latency model the frame got no shorter: the
     // background's sweep needs the normalised weights and is as long as the raycast it runs beside.)
+    reduceAndNormalize(maps, true);
+}
+
+// objPartialSum holds this rank's sum of its object maps: ONE all-reduce makes it the joint sum, with which the rank
+// normalises its own maps (maps[0] = the background's).  timed: bracket the normalisation for the kernel timers
+// (the per-volume path brackets the whole sequence itself).
+void EMFusion::reduceAndNormalize(const std::vector<emf_image_t>& maps, bool timed) {
+    const emf_image_t nv = associationNorm.view(), sv = objPartialSum.view();
     comm->allReduceSumF32(objPartialSum.ptr(), params.frameSize.area(), main);
-    {
-        auto kt = ktimers.scope(KernelTimers::Normalize, pixels() * maps.size(), main);
-        emfCheck(emf_hip_normalizeAssociation(maps.data(), static_cast<int>(maps.size()), 1, &sv, &nv, main.abi()),
-                 "normalizeAssociation");
-    }
+    std::optional<KernelTimers::Scope> kt;
+    if (timed) kt.emplace(&ktimers, KernelTimers::Normalize, pixels() * maps.size(), main.get());
+    emfCheck(emf_hip_normalizeAssociation(maps.data(), static_cast<int>(maps.size()), 1, &sv, &nv, main.abi()),
+             "normalizeAssociation");
 }
 
 // Object volumes are sharded over ranks: merge the nearest hit of ALL objects with one
@@ -59,24 +67,11 @@ void EMFusion::estepSharded(const std::vector<emf_pose_t>& co, bool fromDepth) {
 // Every rank ends up with the same segmentation and the visibility counts of all objects.
 void EMFusion::compositeAcrossRanks(bool deviceGate) {
     const int w = params.frameSize.width, h = params.frameSize.height;
-    std::vector<int32_t> listPos;
-    std::vector<emf_image_t> oray, overt, onorm, oseg;
-    for (auto& obj : objects) {
-        ObjImages& im = objImages.at(obj.getID());
-        const auto it = std::find(allIds.begin(), allIds.end(), obj.getID());
-        listPos.push_back(static_cast<int32_t>(it - allIds.begin()));
-        oray.push_back(im.raylengths.view());
-        overt.push_back(im.vertices.view());
-        onorm.push_back(im.normals.view());
-        oseg.push_back(im.modelSegmentation.view());
-    }
+    const ObjectViews o = objectViews(true);
+    const FrameViews f = frameViews();
+    const std::vector<int32_t>& listPos = o.index;
     const int nlocal = static_cast<int>(listPos.size());
     const int nall = static_cast<int>(allIds.size());
-    const emf_image_t v_bgRay = bg_raylengths.view(), v_bgVert = bg_vertices.view(),
-                      v_bgNorm = bg_normals.view(), v_bgMask = bg_mask.view(),
-                      v_ray = raylengths.view(), v_vert = vertices.view(),
-                      v_norm = normals.view(), v_seg = modelSegmentation.view(),
-                      v_diff = diffRaylengths.view(), v_noObj = noObjMask.view();
     std::vector<int32_t> countIndex(1, 0);
     countIndex.insert(countIndex.end(), listPos.begin(), listPos.end());
     if (peerFused) {
@@ -87,13 +82,13 @@ void EMFusion::compositeAcrossRanks(bool deviceGate) {
         const uint32_t seq = comm->beginPeerExchange(main);
         const int band = bandRowsPending;
         const int row0 = std::min(rank * band, h);
-        emfCheck(emf_hip_packHitKeysPeer(nlocal, listPos.data(), oray.data(), oseg.data(), &v_bgRay, &v_bgMask, row0,
+        emfCheck(emf_hip_packHitKeysPeer(nlocal, listPos.data(), o.ray.data(), o.seg.data(), &f.bgRay, &f.bgMask, row0,
                                          band ? std::min(band, h - row0) : 0, comm->peerGroup(), seq, main.abi()),
                  "packHitKeysPeer");
         if (!visCountsClear) visCounts.setZero(main);
         emfCheck(emf_hip_compositeFromKeysPeer(comm->peerGroup(), seq, band, nall, allIds.data(), nlocal, listPos.data(),
-                                               oray.data(), overt.data(), onorm.data(), &v_bgRay, &v_bgVert, &v_bgNorm,
-                                               &v_bgMask, &v_ray, &v_vert, &v_norm, &v_seg, &v_diff, &v_noObj,
+                                               o.ray.data(), o.vert.data(), o.norm.data(), &f.bgRay, &f.bgVert, &f.bgNorm,
+                                               &f.bgMask, &f.ray, &f.vert, &f.norm, &f.seg, &f.diff, &f.noObj,
                                                params.boundary, visCounts.as<int32_t>(), main.abi()),
                  "compositeFromKeysPeer");
         bandRowsPending = 0;
@@ -104,7 +99,7 @@ void EMFusion::compositeAcrossRanks(bool deviceGate) {
         visCountsClear = true;
     } else {
         auto kt = ktimers.scope(KernelTimers::Composite, pixels() * (1.0 + nlocal), main);
-        emfCheck(emf_hip_packHitKeys(nlocal, listPos.data(), oray.data(), oseg.data(),
+        emfCheck(emf_hip_packHitKeys(nlocal, listPos.data(), o.ray.data(), o.seg.data(),
                                      hitKeys.as<uint64_t>(), w, h, main.abi()),
                  "packHitKeys");
         // ONE exchange per raycast: nearest-hit keys of the objects + the ranks' bands of the background's
@@ -131,12 +126,10 @@ void EMFusion::compositeAcrossRanks(bool deviceGate) {
         }
         bandRowsPending = 0;
         visCountsClear = false;
-        emfCheck(emf_hip_compositeFromKeys(hitKeys.as<uint64_t>(), nall, allIds.data(), nlocal,
-                                           listPos.data(), oray.data(), overt.data(),
-                                           onorm.data(), &v_bgRay, &v_bgVert, &v_bgNorm,
-                                           &v_bgMask, &v_ray, &v_vert, &v_norm, &v_seg, &v_diff,
-                                           &v_noObj, params.boundary, visCounts.as<int32_t>(),
-                                           main.abi()),
+        emfCheck(emf_hip_compositeFromKeys(hitKeys.as<uint64_t>(), nall, allIds.data(), nlocal, listPos.data(),
+                                           o.ray.data(), o.vert.data(), o.norm.data(), &f.bgRay, &f.bgVert, &f.bgNorm,
+                                           &f.bgMask, &f.ray, &f.vert, &f.norm, &f.seg, &f.diff, &f.noObj,
+                                           params.boundary, visCounts.as<int32_t>(), main.abi()),
                  "compositeFromKeys");
         if (deviceGate) {
             emfCheck(emf_hip_visibilityFlagsIndexed(visCounts.as<int32_t>(), nlocal + 1,
@@ -146,23 +139,7 @@ void EMFusion::compositeAcrossRanks(bool deviceGate) {
         }
     }
     stamp(kComposite);
-    vis_objs.clear();
-    visPending = false;
-    if (nall == 0) return;
-    if (!peerFused) {  // (the fused path's flag kernel has mirrored the counts already)
-        int32_t* dst = deviceGate ? visibleHost : visCountsHost;
-        hipCheck(hipMemcpyAsync(dst, visCounts.data(), sizeof(int32_t) * nall, hipMemcpyDeviceToHost,
-                                main.get()),
-                 "visCounts D2H");
-    }
-    if (deviceGate) {
-        visIds = allIds;
-        visPending = true;
-        return;
-    }
-    main.waitForCompletion();
-    for (int k = 0; k < nall; ++k)
-        if (visCountsHost[k] > params.visibilityThresh) vis_objs.insert(allIds[k]);
+    visibleFromCounts(allIds, deviceGate, peerFused);  // (the fused path's flag kernel has mirrored the counts)
 }
 
 }  // namespace emf

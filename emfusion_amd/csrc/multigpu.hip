@@ -35,11 +35,8 @@ struct KeyPackTable {
     int count;
 };
 
-__global__ __launch_bounds__(256) void k_pack_keys(const KeyPackTable t,
-                                                   unsigned long long* __restrict__ keys, int w,
-                                                   int h) {
-    int x, y;
-    if (!pixel_of(w, h, x, y)) return;
+// nearest hit of a pixel over the objects of this rank, as a key
+__device__ __forceinline__ unsigned long long nearest_key(const KeyPackTable& t, int x, int y) {
     unsigned long long key = kNoHit;
     for (int k = 0; k < t.count; ++k) {
         if (t.seg[k].row(y)[x] == 0) continue;
@@ -49,7 +46,15 @@ __global__ __launch_bounds__(256) void k_pack_keys(const KeyPackTable t,
         const unsigned long long cand = (static_cast<unsigned long long>(bits) << 32) | t.pos[k];
         key = cand < key ? cand : key;
     }
-    keys[static_cast<size_t>(y) * w + x] = key;
+    return key;
+}
+
+__global__ __launch_bounds__(256) void k_pack_keys(const KeyPackTable t,
+                                                   unsigned long long* __restrict__ keys, int w,
+                                                   int h) {
+    int x, y;
+    if (!pixel_of(w, h, x, y)) return;
+    keys[static_cast<size_t>(y) * w + x] = nearest_key(t, x, y);
 }
 
 struct IdTable {
@@ -62,20 +67,20 @@ struct LocalTable {
     int count;
 };
 
-struct FromKeysArgs {
-    const unsigned long long* keys;
-    Img<const float> bgRay, bgVert, bgNorm;
-    Img<const uint8_t> bgMask;
+// what a pixel of the composite reads and writes beside the background's raylength and hit mask
+struct CompositeImages {
+    Img<const float> bgVert, bgNorm;
     Img<float> ray, vert, nrm, diff;
     Img<uint8_t> seg, noObj;
-    int w, h;
 };
 
-__global__ __launch_bounds__(256) void k_composite_keys(const FromKeysArgs a, const IdTable ids,
-                                                        const LocalTable loc) {
-    int x, y;
-    if (!pixel_of(a.w, a.h, x, y)) return;
-    const unsigned long long key = a.keys[static_cast<size_t>(y) * a.w + x];
+// One pixel of the composite from its merged key; returns the segmentation value it stored.  bgR / bgM: the
+// background's raylength and hit mask at the pixel (a rank of the peer transport has just fetched them from a slot).
+// (The single-GPU k_composite of pixel_ops.hip keeps a copy of the tail of its own: the committed profiles price
+// that file as it stands.)
+__device__ __forceinline__ uint8_t composite_pixel(unsigned long long key, float bgR, uint8_t bgM,
+                                                   const CompositeImages& a, const IdTable& ids,
+                                                   const LocalTable& loc, int x, int y) {
     float r = 0.f;
     V3 vv = v3(0.f, 0.f, 0.f), nn = v3(0.f, 0.f, 0.f);
     uint8_t s = 0;
@@ -96,8 +101,8 @@ __global__ __launch_bounds__(256) void k_composite_keys(const FromKeysArgs a, co
     }
     // from here on identical to the single-GPU composite (EMFusion.cpp:773-794)
     float d = a.diff.row(y)[x];
-    if (a.bgMask.row(y)[x]) {
-        d = r - a.bgRay.row(y)[x];
+    if (bgM) {
+        d = r - bgR;
         a.diff.row(y)[x] = d;
     }
     if (d > 0.05f) s = 0;
@@ -119,13 +124,40 @@ __global__ __launch_bounds__(256) void k_composite_keys(const FromKeysArgs a, co
     on[1] = nn.y;
     on[2] = nn.z;
     a.seg.row(y)[x] = s;
+    return s;
+}
+
+struct FromKeysArgs {
+    const unsigned long long* keys;
+    Img<const float> bgRay;
+    Img<const uint8_t> bgMask;
+    CompositeImages im;
+    int w, h;
+};
+
+__global__ __launch_bounds__(256) void k_composite_keys(const FromKeysArgs a, const IdTable ids,
+                                                        const LocalTable loc) {
+    int x, y;
+    if (!pixel_of(a.w, a.h, x, y)) return;
+    composite_pixel(a.keys[static_cast<size_t>(y) * a.w + x], a.bgRay.row(y)[x], a.bgMask.row(y)[x], a.im, ids, loc,
+                    x, y);
 }
 
 struct SlotTable {
     int16_t slot[256];
 };
 
-// same counting scheme as pixel_ops.hip's k_vis_counts (EMFusion.cpp:778-791)
+// The visibility counts, the counting scheme of pixel_ops.hip's k_vis_counts (EMFusion.cpp:778-791): a workgroup
+// counts the segmentation values inside the boundary inset in an LDS histogram lh[256] and adds it to the counts
+// of the objects once (barriers around the two belong to the kernel).
+__device__ __forceinline__ void count_visible(int* lh, uint8_t s, int x, int y, int w, int h, int boundary) {
+    if (s && x >= boundary && x < w - boundary && y >= boundary && y < h - boundary) atomicAdd(&lh[s], 1);
+}
+__device__ __forceinline__ void flush_visible(const int* lh, int tid, const SlotTable& slots, int* counts) {
+    const int k = slots.slot[tid];
+    if (k >= 0 && lh[tid]) atomicAdd(&counts[k], lh[tid]);
+}
+
 __global__ __launch_bounds__(256) void k_vis_counts_all(Img<const uint8_t> seg, int w, int h,
                                                         int boundary, const SlotTable slots,
                                                         int* __restrict__ counts) {
@@ -134,14 +166,9 @@ __global__ __launch_bounds__(256) void k_vis_counts_all(Img<const uint8_t> seg, 
     lh[tid] = 0;
     __syncthreads();
     int x, y;
-    if (pixel_of(w, h, x, y) && x >= boundary && x < w - boundary && y >= boundary &&
-        y < h - boundary) {
-        const uint8_t s = seg.row(y)[x];
-        if (s) atomicAdd(&lh[s], 1);
-    }
+    if (pixel_of(w, h, x, y)) count_visible(lh, seg.row(y)[x], x, y, w, h, boundary);
     __syncthreads();
-    const int k = slots.slot[tid];
-    if (k >= 0 && lh[tid]) atomicAdd(&counts[k], lh[tid]);
+    flush_visible(lh, tid, slots, counts);
 }
 
 struct GateTable {
@@ -172,14 +199,7 @@ struct PackPeer {
 __global__ __launch_bounds__(256) void k_pack_keys_peer(const KeyPackTable t, const PackPeer pp, int w, int h) {
     int x, y;
     if (!pixel_of(w, h, x, y)) return;
-    unsigned long long key = kNoHit;
-    for (int k = 0; k < t.count; ++k) {
-        if (t.seg[k].row(y)[x] == 0) continue;
-        const float r = t.ray[k].row(y)[x];
-        const unsigned bits = r > 0.f ? __float_as_uint(r) : 0xFFFFFFFEu;  // as k_pack_keys
-        const unsigned long long cand = (static_cast<unsigned long long>(bits) << 32) | t.pos[k];
-        key = cand < key ? cand : key;
-    }
+    const unsigned long long key = nearest_key(t, x, y);
     const size_t pix = static_cast<size_t>(y) * w + x;
     for (int p = 0; p < pp.world; ++p)
         __builtin_nontemporal_store(key, reinterpret_cast<unsigned long long*>(pp.slots[p] + pp.off) + pix);
@@ -197,9 +217,7 @@ __global__ __launch_bounds__(256) void k_pack_keys_peer(const KeyPackTable t, co
 struct FromKeysPeerArgs {
     Img<float> bgRay;     // foreign bands are filled in from their owners' slots
     Img<uint8_t> bgMask;
-    Img<const float> bgVert, bgNorm;
-    Img<float> ray, vert, nrm, diff;
-    Img<uint8_t> seg, noObj;
+    CompositeImages im;
     int w, h;
     int bandRowsPerRank;  // 0: the background images are complete locally
     int boundary;
@@ -241,54 +259,11 @@ __global__ __launch_bounds__(256) void k_composite_keys_peer(const PeerArgs pa, 
             bgR = a.bgRay.row(y)[x];
             bgM = a.bgMask.row(y)[x];
         }
-        uint8_t s = 0;
-        float r = 0.f;
-        V3 vv = v3(0.f, 0.f, 0.f), nn = v3(0.f, 0.f, 0.f);
-        if (key != kNoHit) {
-            const unsigned pos = static_cast<unsigned>(key & 0xFFFFFFFFull);
-            const unsigned bits = static_cast<unsigned>(key >> 32);
-            s = ids.id[pos];
-            r = __uint_as_float(bits);
-            for (int k = 0; k < loc.count; ++k) {
-                if (loc.pos[k] != pos) continue;
-                r = loc.ray[k].row(y)[x];  // the winner lives on this rank (as k_composite_keys)
-                const float* pv = loc.vert[k].row(y) + 3 * x;
-                const float* pn = loc.nrm[k].row(y) + 3 * x;
-                vv = v3(pv[0], pv[1], pv[2]);
-                nn = v3(pn[0], pn[1], pn[2]);
-            }
-        }
-        // from here on identical to the single-GPU composite (EMFusion.cpp:773-794)
-        float d = a.diff.row(y)[x];
-        if (bgM) {
-            d = r - bgR;
-            a.diff.row(y)[x] = d;
-        }
-        if (d > 0.05f) s = 0;
-        const uint8_t no = s == 0 ? 255 : 0;
-        if (no) {
-            const float* pv = a.bgVert.row(y) + 3 * x;
-            const float* pn = a.bgNorm.row(y) + 3 * x;
-            vv = v3(pv[0], pv[1], pv[2]);
-            nn = v3(pn[0], pn[1], pn[2]);
-        }
-        a.noObj.row(y)[x] = no;
-        a.ray.row(y)[x] = r;
-        float* ov = a.vert.row(y) + 3 * x;
-        float* on = a.nrm.row(y) + 3 * x;
-        ov[0] = vv.x;
-        ov[1] = vv.y;
-        ov[2] = vv.z;
-        on[0] = nn.x;
-        on[1] = nn.y;
-        on[2] = nn.z;
-        a.seg.row(y)[x] = s;
-        // visibility counts on the values just written (k_vis_counts_all's scheme, EMFusion.cpp:778-791)
-        if (s && x >= a.boundary && x < a.w - a.boundary && y >= a.boundary && y < a.h - a.boundary) atomicAdd(&lh[s], 1);
+        // visibility counts on the values just written
+        count_visible(lh, composite_pixel(key, bgR, bgM, a.im, ids, loc, x, y), x, y, a.w, a.h, a.boundary);
     }
     __syncthreads();
-    const int k = slots.slot[tid];
-    if (k >= 0 && lh[tid]) atomicAdd(&a.counts[k], lh[tid]);
+    flush_visible(lh, tid, slots, a.counts);
 }
 
 // gate of the owned objects (as k_vis_flags_indexed) + the counts of ALL objects mirrored to host-visible memory,
@@ -312,34 +287,138 @@ __global__ __launch_bounds__(256) void k_vis_flags_mirror(int32_t* __restrict__ 
 
 using namespace emf_hip;
 
+namespace {
+
+// EMF_REQUIRE_PTR for a helper that reports under its entry's name fn
+#define REQUIRE_PTR_OF(fn, p)                                                   \
+    do {                                                                        \
+        if ((p) == nullptr) return fail(EMF_E_NULL, "%s: %s is NULL", fn, #p); \
+    } while (0)
+
+int check_named(const emf_image_t* im, size_t elem_bytes, const char* fn, const char* what) {
+    char name[64];
+    snprintf(name, sizeof(name), "%s: %s", fn, what);
+    return check_image(im, elem_bytes, name);
+}
+
+int fill_pack_table(KeyPackTable& t, int nlocal, const int32_t* listPos_host, const emf_image_t* objRay_host,
+                    const emf_image_t* objSeg_host, int width, int height, const char* fn) {
+    if (nlocal < 0 || nlocal > kLocalMax) return fail(EMF_E_LIMIT, "%s: nlocal = %d, expected 0..%d", fn, nlocal, kLocalMax);
+    if (width <= 0 || height <= 0) return fail(EMF_E_SHAPE, "%s: bad image size", fn);
+    t.count = nlocal;
+    if (nlocal > 0 && (!listPos_host || !objRay_host || !objSeg_host)) return fail(EMF_E_NULL, "%s: NULL object table", fn);
+    for (int k = 0; k < nlocal; ++k) {
+        EMF_TRY(check_named(&objRay_host[k], 4, fn, "objRay"));
+        EMF_TRY(check_named(&objSeg_host[k], 1, fn, "objSeg"));
+        if (objRay_host[k].width != width || objRay_host[k].height != height ||
+            objSeg_host[k].width != width || objSeg_host[k].height != height)
+            return fail(EMF_E_SHAPE, "%s: image %d is not %d x %d", fn, k, width, height);
+        if (listPos_host[k] < 0 || listPos_host[k] >= EMF_MAX_MODELS)
+            return fail(EMF_E_ARG, "%s: list position %d out of range", fn, listPos_host[k]);
+        t.ray[k] = img<const float>(&objRay_host[k]);
+        t.seg[k] = img<const uint8_t>(&objSeg_host[k]);
+        t.pos[k] = static_cast<unsigned>(listPos_host[k]);
+    }
+    return EMF_OK;
+}
+
+// the ten images of a frame's composite, in the order of the entries' arguments
+struct FrameImages {
+    const emf_image_t *bgRay, *bgVert, *bgNorm, *bgMask, *ray, *vert, *norm, *seg, *diff, *noObj;
+};
+
+// limits, table pointers and frame images of a composite from keys
+int check_composite(const char* fn, int nall, const int32_t* ids_host, const int32_t* visCounts, int nlocal,
+                    const int32_t* listPos_host, const emf_image_t* objRay_host, const emf_image_t* objVert_host,
+                    const emf_image_t* objNorm_host, const FrameImages& f) {
+    if (nall < 0 || nall > EMF_MAX_MODELS - 1) return fail(EMF_E_LIMIT, "%s: nall = %d", fn, nall);
+    if (nlocal < 0 || nlocal > kLocalMax || nlocal > nall) return fail(EMF_E_LIMIT, "%s: nlocal = %d", fn, nlocal);
+    if (nall > 0) {
+        REQUIRE_PTR_OF(fn, ids_host);
+        REQUIRE_PTR_OF(fn, visCounts);
+    }
+    if (nlocal > 0) {
+        REQUIRE_PTR_OF(fn, listPos_host);
+        REQUIRE_PTR_OF(fn, objRay_host);
+        REQUIRE_PTR_OF(fn, objVert_host);
+        REQUIRE_PTR_OF(fn, objNorm_host);
+    }
+    EMF_TRY(check_named(f.bgRay, 4, fn, "bgRay"));
+    EMF_TRY(check_named(f.bgVert, 12, fn, "bgVert"));
+    EMF_TRY(check_named(f.bgNorm, 12, fn, "bgNorm"));
+    EMF_TRY(check_named(f.bgMask, 1, fn, "bgMask"));
+    EMF_TRY(check_named(f.ray, 4, fn, "ray"));
+    EMF_TRY(check_named(f.vert, 12, fn, "vert"));
+    EMF_TRY(check_named(f.norm, 12, fn, "norm"));
+    EMF_TRY(check_named(f.seg, 1, fn, "seg"));
+    EMF_TRY(check_named(f.diff, 4, fn, "diff"));
+    EMF_TRY(check_named(f.noObj, 1, fn, "noObj"));
+    const emf_image_t* all[] = {f.bgVert, f.bgNorm, f.bgMask, f.ray, f.vert, f.norm, f.seg, f.diff, f.noObj};
+    for (const emf_image_t* im : all) EMF_TRY(check_same_size(im, f.bgRay, "image", "bgRay"));
+    return EMF_OK;
+}
+
+CompositeImages composite_images(const FrameImages& f) {
+    return {img<const float>(f.bgVert), img<const float>(f.bgNorm), img<float>(f.ray), img<float>(f.vert),
+            img<float>(f.norm), img<float>(f.diff), img<uint8_t>(f.seg), img<uint8_t>(f.noObj)};
+}
+
+// saturated id by list position, and the first list position (= slot of the counts) of every id
+void fill_id_tables(IdTable& ids, SlotTable& slots, int nall, const int32_t* ids_host) {
+    for (int v = 0; v < 256; ++v) {
+        ids.id[v] = 0;
+        slots.slot[v] = -1;
+    }
+    for (int k = 0; k < nall; ++k) {
+        const int id = ids_host[k];
+        ids.id[k] = static_cast<uint8_t>(id < 0 ? 0 : (id > 255 ? 255 : id));
+        if (id >= 1 && id <= 255 && slots.slot[id] < 0) slots.slot[id] = static_cast<int16_t>(k);
+    }
+}
+
+int fill_local_table(LocalTable& loc, int nall, int nlocal, const int32_t* listPos_host, const emf_image_t* objRay_host,
+                     const emf_image_t* objVert_host, const emf_image_t* objNorm_host, const emf_image_t* bgRay,
+                     const char* fn) {
+    loc.count = nlocal;
+    for (int k = 0; k < nlocal; ++k) {
+        EMF_TRY(check_named(&objRay_host[k], 4, fn, "objRay"));
+        EMF_TRY(check_named(&objVert_host[k], 12, fn, "objVert"));
+        EMF_TRY(check_named(&objNorm_host[k], 12, fn, "objNorm"));
+        EMF_TRY(check_same_size(&objRay_host[k], bgRay, "objRay", "bgRay"));
+        EMF_TRY(check_same_size(&objVert_host[k], bgRay, "objVert", "bgRay"));
+        EMF_TRY(check_same_size(&objNorm_host[k], bgRay, "objNorm", "bgRay"));
+        if (listPos_host[k] < 0 || listPos_host[k] >= nall)
+            return fail(EMF_E_ARG, "%s: list position %d out of range", fn, listPos_host[k]);
+        loc.ray[k] = img<const float>(&objRay_host[k]);
+        loc.vert[k] = img<const float>(&objVert_host[k]);
+        loc.nrm[k] = img<const float>(&objNorm_host[k]);
+        loc.pos[k] = static_cast<unsigned>(listPos_host[k]);
+    }
+    return EMF_OK;
+}
+
+// nall < 0: the entry has no count to hold the indices against
+int fill_gate_table(GateTable& g, int nmodels, const int32_t* countIndex_host, int nall, const char* fn) {
+    for (int s = 0; s <= EMF_MAX_BATCH; ++s) g.idx[s] = 0;
+    if (nmodels > 1) REQUIRE_PTR_OF(fn, countIndex_host);
+    for (int s = 1; s < nmodels; ++s) {
+        if (nall >= 0 && (countIndex_host[s] < 0 || countIndex_host[s] >= nall))
+            return fail(EMF_E_ARG, "%s: count index %d out of range", fn, countIndex_host[s]);
+        g.idx[s] = countIndex_host[s];
+    }
+    return EMF_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int emf_hip_packHitKeys(int nlocal, const int32_t* listPos_host, const emf_image_t* objRay_host,
                         const emf_image_t* objSeg_host, uint64_t* keys, int width, int height,
                         emf_stream_t stream) {
     EMF_REQUIRE_PTR(keys);
-    if (nlocal < 0 || nlocal > kLocalMax)
-        return fail(EMF_E_LIMIT, "packHitKeys: nlocal = %d, expected 0..%d", nlocal, kLocalMax);
-    if (width <= 0 || height <= 0) return fail(EMF_E_SHAPE, "packHitKeys: bad image size");
     KeyPackTable t;
-    t.count = nlocal;
-    if (nlocal > 0) {
-        EMF_REQUIRE_PTR(listPos_host);
-        EMF_REQUIRE_PTR(objRay_host);
-        EMF_REQUIRE_PTR(objSeg_host);
-    }
-    for (int k = 0; k < nlocal; ++k) {
-        EMF_TRY(check_image(&objRay_host[k], 4, "packHitKeys: objRay"));
-        EMF_TRY(check_image(&objSeg_host[k], 1, "packHitKeys: objSeg"));
-        if (objRay_host[k].width != width || objRay_host[k].height != height ||
-            objSeg_host[k].width != width || objSeg_host[k].height != height)
-            return fail(EMF_E_SHAPE, "packHitKeys: image %d is not %d x %d", k, width, height);
-        if (listPos_host[k] < 0 || listPos_host[k] >= EMF_MAX_MODELS)
-            return fail(EMF_E_ARG, "packHitKeys: list position %d out of range", listPos_host[k]);
-        t.ray[k] = img<const float>(&objRay_host[k]);
-        t.seg[k] = img<const uint8_t>(&objSeg_host[k]);
-        t.pos[k] = static_cast<unsigned>(listPos_host[k]);
-    }
+    EMF_TRY(fill_pack_table(t, nlocal, listPos_host, objRay_host, objSeg_host, width, height, "packHitKeys"));
     hipLaunchKernelGGL(k_pack_keys, pixel_grid(width, height), pixel_block(), 0, as_stream(stream),
                        t, reinterpret_cast<unsigned long long*>(keys), width, height);
     return launch_status("packHitKeys");
@@ -355,77 +434,19 @@ int emf_hip_compositeFromKeys(const uint64_t* keys, int nall, const int32_t* ids
                               const emf_image_t* diff, const emf_image_t* noObj, int boundary,
                               int32_t* visCounts, emf_stream_t stream) {
     EMF_REQUIRE_PTR(keys);
-    if (nall < 0 || nall > EMF_MAX_MODELS - 1)
-        return fail(EMF_E_LIMIT, "compositeFromKeys: nall = %d", nall);
-    if (nlocal < 0 || nlocal > kLocalMax || nlocal > nall)
-        return fail(EMF_E_LIMIT, "compositeFromKeys: nlocal = %d", nlocal);
-    if (nall > 0) {
-        EMF_REQUIRE_PTR(ids_host);
-        EMF_REQUIRE_PTR(visCounts);
-    }
-    if (nlocal > 0) {
-        EMF_REQUIRE_PTR(listPos_host);
-        EMF_REQUIRE_PTR(objRay_host);
-        EMF_REQUIRE_PTR(objVert_host);
-        EMF_REQUIRE_PTR(objNorm_host);
-    }
-    EMF_TRY(check_image(bgRay, 4, "compositeFromKeys: bgRay"));
-    EMF_TRY(check_image(bgVert, 12, "compositeFromKeys: bgVert"));
-    EMF_TRY(check_image(bgNorm, 12, "compositeFromKeys: bgNorm"));
-    EMF_TRY(check_image(bgMask, 1, "compositeFromKeys: bgMask"));
-    EMF_TRY(check_image(ray, 4, "compositeFromKeys: ray"));
-    EMF_TRY(check_image(vert, 12, "compositeFromKeys: vert"));
-    EMF_TRY(check_image(norm, 12, "compositeFromKeys: norm"));
-    EMF_TRY(check_image(seg, 1, "compositeFromKeys: seg"));
-    EMF_TRY(check_image(diff, 4, "compositeFromKeys: diff"));
-    EMF_TRY(check_image(noObj, 1, "compositeFromKeys: noObj"));
-    const emf_image_t* all[] = {bgVert, bgNorm, bgMask, ray, vert, norm, seg, diff, noObj};
-    for (const emf_image_t* im : all) EMF_TRY(check_same_size(im, bgRay, "image", "bgRay"));
+    const FrameImages f = {bgRay, bgVert, bgNorm, bgMask, ray, vert, norm, seg, diff, noObj};
+    EMF_TRY(check_composite("compositeFromKeys", nall, ids_host, visCounts, nlocal, listPos_host, objRay_host,
+                            objVert_host, objNorm_host, f));
     if (boundary < 0) return fail(EMF_E_ARG, "compositeFromKeys: boundary < 0");
     const int w = bgRay->width, h = bgRay->height;
-
-    FromKeysArgs a;
-    a.keys = reinterpret_cast<const unsigned long long*>(keys);
-    a.bgRay = img<const float>(bgRay);
-    a.bgVert = img<const float>(bgVert);
-    a.bgNorm = img<const float>(bgNorm);
-    a.bgMask = img<const uint8_t>(bgMask);
-    a.ray = img<float>(ray);
-    a.vert = img<float>(vert);
-    a.nrm = img<float>(norm);
-    a.diff = img<float>(diff);
-    a.seg = img<uint8_t>(seg);
-    a.noObj = img<uint8_t>(noObj);
-    a.w = w;
-    a.h = h;
+    const FromKeysArgs a = {reinterpret_cast<const unsigned long long*>(keys), img<const float>(bgRay),
+                            img<const uint8_t>(bgMask), composite_images(f), w, h};
     IdTable ids;
     SlotTable slots;
-    for (int v = 0; v < 256; ++v) {
-        ids.id[v] = 0;
-        slots.slot[v] = -1;
-    }
-    for (int k = 0; k < nall; ++k) {
-        const int id = ids_host[k];
-        ids.id[k] = static_cast<uint8_t>(id < 0 ? 0 : (id > 255 ? 255 : id));
-        if (id >= 1 && id <= 255 && slots.slot[id] < 0) slots.slot[id] = static_cast<int16_t>(k);
-    }
+    fill_id_tables(ids, slots, nall, ids_host);
     LocalTable loc;
-    loc.count = nlocal;
-    for (int k = 0; k < nlocal; ++k) {
-        EMF_TRY(check_image(&objRay_host[k], 4, "compositeFromKeys: objRay"));
-        EMF_TRY(check_image(&objVert_host[k], 12, "compositeFromKeys: objVert"));
-        EMF_TRY(check_image(&objNorm_host[k], 12, "compositeFromKeys: objNorm"));
-        EMF_TRY(check_same_size(&objRay_host[k], bgRay, "objRay", "bgRay"));
-        EMF_TRY(check_same_size(&objVert_host[k], bgRay, "objVert", "bgRay"));
-        EMF_TRY(check_same_size(&objNorm_host[k], bgRay, "objNorm", "bgRay"));
-        if (listPos_host[k] < 0 || listPos_host[k] >= nall)
-            return fail(EMF_E_ARG, "compositeFromKeys: list position %d out of range",
-                        listPos_host[k]);
-        loc.ray[k] = img<const float>(&objRay_host[k]);
-        loc.vert[k] = img<const float>(&objVert_host[k]);
-        loc.nrm[k] = img<const float>(&objNorm_host[k]);
-        loc.pos[k] = static_cast<unsigned>(listPos_host[k]);
-    }
+    EMF_TRY(fill_local_table(loc, nall, nlocal, listPos_host, objRay_host, objVert_host, objNorm_host, bgRay,
+                             "compositeFromKeys"));
     const dim3 g = pixel_grid(w, h), b = pixel_block();
     hipLaunchKernelGGL(k_composite_keys, g, b, 0, as_stream(stream), a, ids, loc);
     EMF_TRY(launch_status("compositeFromKeys"));
@@ -448,13 +469,9 @@ int emf_hip_visibilityFlagsIndexed(const int32_t* visCounts, int nmodels,
     EMF_REQUIRE_PTR(visible_dev);
     if (nmodels < 1 || nmodels > EMF_MAX_BATCH + 1)
         return fail(EMF_E_LIMIT, "visibilityFlagsIndexed: nmodels = %d", nmodels);
+    if (nmodels > 1) EMF_REQUIRE_PTR(visCounts);
     GateTable g;
-    for (int s = 0; s <= EMF_MAX_BATCH; ++s) g.idx[s] = 0;
-    if (nmodels > 1) {
-        EMF_REQUIRE_PTR(visCounts);
-        EMF_REQUIRE_PTR(countIndex_host);
-        for (int s = 1; s < nmodels; ++s) g.idx[s] = countIndex_host[s];
-    }
+    EMF_TRY(fill_gate_table(g, nmodels, countIndex_host, -1, "visibilityFlagsIndexed"));
     hipLaunchKernelGGL(k_vis_flags_indexed, dim3(1), dim3(64), 0, as_stream(stream), visCounts,
                        nmodels, visibilityThresh, g, visible_dev);
     return launch_status("visibilityFlagsIndexed");
@@ -465,29 +482,6 @@ size_t emf_hip_peerRaycastSlotBytes(int width, int height) {
     const size_t P = static_cast<size_t>(width) * height;
     return (13 * P + 15) / 16 * 16;
 }
-
-namespace {
-int fill_pack_table(KeyPackTable& t, int nlocal, const int32_t* listPos_host, const emf_image_t* objRay_host,
-                    const emf_image_t* objSeg_host, int width, int height, const char* fn) {
-    if (nlocal < 0 || nlocal > kLocalMax) return fail(EMF_E_LIMIT, "%s: nlocal = %d, expected 0..%d", fn, nlocal, kLocalMax);
-    if (width <= 0 || height <= 0) return fail(EMF_E_SHAPE, "%s: bad image size", fn);
-    t.count = nlocal;
-    if (nlocal > 0 && (!listPos_host || !objRay_host || !objSeg_host)) return fail(EMF_E_NULL, "%s: NULL object table", fn);
-    for (int k = 0; k < nlocal; ++k) {
-        EMF_TRY(check_image(&objRay_host[k], 4, "packHitKeys: objRay"));
-        EMF_TRY(check_image(&objSeg_host[k], 1, "packHitKeys: objSeg"));
-        if (objRay_host[k].width != width || objRay_host[k].height != height ||
-            objSeg_host[k].width != width || objSeg_host[k].height != height)
-            return fail(EMF_E_SHAPE, "%s: image %d is not %d x %d", fn, k, width, height);
-        if (listPos_host[k] < 0 || listPos_host[k] >= EMF_MAX_MODELS)
-            return fail(EMF_E_ARG, "%s: list position %d out of range", fn, listPos_host[k]);
-        t.ray[k] = img<const float>(&objRay_host[k]);
-        t.seg[k] = img<const uint8_t>(&objSeg_host[k]);
-        t.pos[k] = static_cast<unsigned>(listPos_host[k]);
-    }
-    return EMF_OK;
-}
-}  // namespace
 
 int emf_hip_packHitKeysPeer(int nlocal, const int32_t* listPos_host, const emf_image_t* objRay_host,
                             const emf_image_t* objSeg_host, const emf_image_t* bgRay, const emf_image_t* bgMask,
@@ -529,75 +523,22 @@ int emf_hip_compositeFromKeysPeer(const emf_peer_t* group, uint32_t seq, int ban
     PeerArgs pa;
     EMF_TRY(peer_args(group, pa, "compositeFromKeysPeer"));
     EMF_REQUIRE_PTR(visCounts);
-    if (nall < 0 || nall > EMF_MAX_MODELS - 1) return fail(EMF_E_LIMIT, "compositeFromKeysPeer: nall = %d", nall);
-    if (nlocal < 0 || nlocal > kLocalMax || nlocal > nall) return fail(EMF_E_LIMIT, "compositeFromKeysPeer: nlocal = %d", nlocal);
-    if (nall > 0) EMF_REQUIRE_PTR(ids_host);
-    if (nlocal > 0) {
-        EMF_REQUIRE_PTR(listPos_host);
-        EMF_REQUIRE_PTR(objRay_host);
-        EMF_REQUIRE_PTR(objVert_host);
-        EMF_REQUIRE_PTR(objNorm_host);
-    }
-    EMF_TRY(check_image(bgRay, 4, "compositeFromKeysPeer: bgRay"));
-    EMF_TRY(check_image(bgVert, 12, "compositeFromKeysPeer: bgVert"));
-    EMF_TRY(check_image(bgNorm, 12, "compositeFromKeysPeer: bgNorm"));
-    EMF_TRY(check_image(bgMask, 1, "compositeFromKeysPeer: bgMask"));
-    EMF_TRY(check_image(ray, 4, "compositeFromKeysPeer: ray"));
-    EMF_TRY(check_image(vert, 12, "compositeFromKeysPeer: vert"));
-    EMF_TRY(check_image(norm, 12, "compositeFromKeysPeer: norm"));
-    EMF_TRY(check_image(seg, 1, "compositeFromKeysPeer: seg"));
-    EMF_TRY(check_image(diff, 4, "compositeFromKeysPeer: diff"));
-    EMF_TRY(check_image(noObj, 1, "compositeFromKeysPeer: noObj"));
-    const emf_image_t* all[] = {bgVert, bgNorm, bgMask, ray, vert, norm, seg, diff, noObj};
-    for (const emf_image_t* im : all) EMF_TRY(check_same_size(im, bgRay, "image", "bgRay"));
+    const FrameImages f = {bgRay, bgVert, bgNorm, bgMask, ray, vert, norm, seg, diff, noObj};
+    EMF_TRY(check_composite("compositeFromKeysPeer", nall, ids_host, visCounts, nlocal, listPos_host, objRay_host,
+                            objVert_host, objNorm_host, f));
     if (boundary < 0 || bandRowsPerRank < 0) return fail(EMF_E_ARG, "compositeFromKeysPeer: boundary / band rows < 0");
     const int w = bgRay->width, h = bgRay->height;
     if (emf_hip_peerRaycastSlotBytes(w, h) > pa.slotBytes)
         return fail(EMF_E_ARG, "compositeFromKeysPeer: a %d x %d raycast needs %zu-byte slots, the group has %zu", w, h,
                     emf_hip_peerRaycastSlotBytes(w, h), pa.slotBytes);
-    FromKeysPeerArgs a;
-    a.bgRay = img<float>(bgRay);
-    a.bgMask = img<uint8_t>(bgMask);
-    a.bgVert = img<const float>(bgVert);
-    a.bgNorm = img<const float>(bgNorm);
-    a.ray = img<float>(ray);
-    a.vert = img<float>(vert);
-    a.nrm = img<float>(norm);
-    a.diff = img<float>(diff);
-    a.seg = img<uint8_t>(seg);
-    a.noObj = img<uint8_t>(noObj);
-    a.w = w;
-    a.h = h;
-    a.bandRowsPerRank = bandRowsPerRank;
-    a.boundary = boundary;
-    a.counts = visCounts;
+    const FromKeysPeerArgs a = {img<float>(bgRay), img<uint8_t>(bgMask), composite_images(f), w, h, bandRowsPerRank,
+                                boundary, visCounts};
     IdTable ids;
     SlotTable slots;
-    for (int v = 0; v < 256; ++v) {
-        ids.id[v] = 0;
-        slots.slot[v] = -1;
-    }
-    for (int k = 0; k < nall; ++k) {
-        const int id = ids_host[k];
-        ids.id[k] = static_cast<uint8_t>(id < 0 ? 0 : (id > 255 ? 255 : id));
-        if (id >= 1 && id <= 255 && slots.slot[id] < 0) slots.slot[id] = static_cast<int16_t>(k);
-    }
+    fill_id_tables(ids, slots, nall, ids_host);
     LocalTable loc;
-    loc.count = nlocal;
-    for (int k = 0; k < nlocal; ++k) {
-        EMF_TRY(check_image(&objRay_host[k], 4, "compositeFromKeysPeer: objRay"));
-        EMF_TRY(check_image(&objVert_host[k], 12, "compositeFromKeysPeer: objVert"));
-        EMF_TRY(check_image(&objNorm_host[k], 12, "compositeFromKeysPeer: objNorm"));
-        EMF_TRY(check_same_size(&objRay_host[k], bgRay, "objRay", "bgRay"));
-        EMF_TRY(check_same_size(&objVert_host[k], bgRay, "objVert", "bgRay"));
-        EMF_TRY(check_same_size(&objNorm_host[k], bgRay, "objNorm", "bgRay"));
-        if (listPos_host[k] < 0 || listPos_host[k] >= nall)
-            return fail(EMF_E_ARG, "compositeFromKeysPeer: list position %d out of range", listPos_host[k]);
-        loc.ray[k] = img<const float>(&objRay_host[k]);
-        loc.vert[k] = img<const float>(&objVert_host[k]);
-        loc.nrm[k] = img<const float>(&objNorm_host[k]);
-        loc.pos[k] = static_cast<unsigned>(listPos_host[k]);
-    }
+    EMF_TRY(fill_local_table(loc, nall, nlocal, listPos_host, objRay_host, objVert_host, objNorm_host, bgRay,
+                             "compositeFromKeysPeer"));
     EMF_TRY(peer_wait_in_front(group, seq, stream));
     const unsigned tiles = ceil_div(w, kTileX) * ceil_div(h, kTileY);
     hipLaunchKernelGGL(k_composite_keys_peer, dim3(group->waitInFront || tiles < kPollGroups ? tiles : kPollGroups), pixel_block(), 0,
@@ -612,15 +553,7 @@ int emf_hip_visibilityFlagsMirror(int32_t* visCounts, int nall, int nmodels, con
     if (nmodels < 1 || nmodels > EMF_MAX_BATCH + 1) return fail(EMF_E_LIMIT, "visibilityFlagsMirror: nmodels = %d", nmodels);
     if (nall < 0 || nall > EMF_MAX_MODELS - 1) return fail(EMF_E_LIMIT, "visibilityFlagsMirror: nall = %d", nall);
     GateTable g;
-    for (int s = 0; s <= EMF_MAX_BATCH; ++s) g.idx[s] = 0;
-    if (nmodels > 1) {
-        EMF_REQUIRE_PTR(countIndex_host);
-        for (int s = 1; s < nmodels; ++s) {
-            if (countIndex_host[s] < 0 || countIndex_host[s] >= nall)
-                return fail(EMF_E_ARG, "visibilityFlagsMirror: count index %d out of range", countIndex_host[s]);
-            g.idx[s] = countIndex_host[s];
-        }
-    }
+    EMF_TRY(fill_gate_table(g, nmodels, countIndex_host, nall, "visibilityFlagsMirror"));
     hipLaunchKernelGGL(k_vis_flags_mirror, dim3(1), dim3(256), 0, as_stream(stream), visCounts, nall, nmodels,
                        visibilityThresh, g, visible_dev, countsMirror);
     return launch_status("visibilityFlagsMirror");

@@ -205,6 +205,12 @@ def sum_association(maps, out, stream=None):
     return out
 
 
+def _frame_refs(*images):
+    """The composite entries' ten frame images (background raycast, outputs) as the ABI's image pointers."""
+    assert len(images) == 10
+    return [C.byref(image_view(t)) for t in images]
+
+
 def composite_visibility(ids, obj_ray, obj_vert, obj_norm, obj_seg, bg_ray, bg_vert, bg_norm, bg_mask,
                          ray, vert, norm, seg, diff, no_obj, boundary, vis_counts, thresh, visible, mirror=None,
                          stream=None):
@@ -215,11 +221,7 @@ def composite_visibility(ids, obj_ray, obj_vert, obj_norm, obj_seg, bg_ray, bg_v
     check("emf_hip_compositeVisibility",
           _L.emf_hip_compositeVisibility(n, ids_arr, _views(obj_ray), _views(obj_vert),
                                          _views(obj_norm), _views(obj_seg),
-                                         C.byref(image_view(bg_ray)), C.byref(image_view(bg_vert)),
-                                         C.byref(image_view(bg_norm)), C.byref(image_view(bg_mask)),
-                                         C.byref(image_view(ray)), C.byref(image_view(vert)),
-                                         C.byref(image_view(norm)), C.byref(image_view(seg)),
-                                         C.byref(image_view(diff)), C.byref(image_view(no_obj)),
+                                         *_frame_refs(bg_ray, bg_vert, bg_norm, bg_mask, ray, vert, norm, seg, diff, no_obj),
                                          boundary, _ptr(vis_counts), int(thresh), _ptr(visible),
                                          _ptr(mirror) if mirror is not None else None, _stream(stream)))
 
@@ -233,11 +235,7 @@ def composite_raycast(ids, obj_ray, obj_vert, obj_norm, obj_seg, bg_ray, bg_vert
     check("emf_hip_compositeRaycast",
           _L.emf_hip_compositeRaycast(n, ids_arr, _views(obj_ray), _views(obj_vert),
                                       _views(obj_norm), _views(obj_seg),
-                                      C.byref(image_view(bg_ray)), C.byref(image_view(bg_vert)),
-                                      C.byref(image_view(bg_norm)), C.byref(image_view(bg_mask)),
-                                      C.byref(image_view(ray)), C.byref(image_view(vert)),
-                                      C.byref(image_view(norm)), C.byref(image_view(seg)),
-                                      C.byref(image_view(diff)), C.byref(image_view(no_obj)),
+                                      *_frame_refs(bg_ray, bg_vert, bg_norm, bg_mask, ray, vert, norm, seg, diff, no_obj),
                                       boundary, _ptr(vis_counts if n else None), _stream(stream)))
 
 
@@ -503,11 +501,7 @@ def composite_from_keys(keys, ids_all, list_pos, obj_ray, obj_vert, obj_norm, bg
     check("emf_hip_compositeFromKeys",
           _L.emf_hip_compositeFromKeys(_ptr(keys), nall, ids, n, pos, _views(obj_ray),
                                        _views(obj_vert), _views(obj_norm),
-                                       C.byref(image_view(bg_ray)), C.byref(image_view(bg_vert)),
-                                       C.byref(image_view(bg_norm)), C.byref(image_view(bg_mask)),
-                                       C.byref(image_view(ray)), C.byref(image_view(vert)),
-                                       C.byref(image_view(norm)), C.byref(image_view(seg)),
-                                       C.byref(image_view(diff)), C.byref(image_view(no_obj)),
+                                       *_frame_refs(bg_ray, bg_vert, bg_norm, bg_mask, ray, vert, norm, seg, diff, no_obj),
                                        boundary, _ptr(vis_counts if nall else None),
                                        _stream(stream)))
 
