@@ -1,7 +1,8 @@
 """numpy binding of the CPU oracle (oracle/emf_oracle.c).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline
-leg -- never by emfusion_amd/.  PARITY UNPINNED (see emf_oracle.h).
+leg -- never by emfusion_amd/.  The kernels are pinned to the reference's own (oracle/ref_binding.py,
+tests/test_oracle_pinned.py); the host-side chains are a restatement (see emf_oracle.h).
 
 Arrays follow the reference layout: images (H, W[, C]) float32/uint8 C-contiguous, volumes
 (Nz, Ny, Nx[, C]).  Functions that the reference runs in place modify their array arguments.

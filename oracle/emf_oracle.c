@@ -1,8 +1,9 @@
 /*
  * emf_oracle.c -- CPU restatement of EM-Fusion's per-frame volumetric hot path (plain C99).
  *
- * TEST INFRASTRUCTURE ONLY -- see emf_oracle.h.  PARITY UNPINNED (no reference tests / golden
- * vectors exist and the reference cannot be built in this image) -- see emf_oracle.h.
+ * TEST INFRASTRUCTURE ONLY -- see emf_oracle.h.  The kernel restatements are pinned bit for bit to
+ * the reference's own kernels built for the host (oracle/build_ref.py, tests/test_oracle_pinned.py);
+ * the host-side OpenCV chains remain a restatement -- see emf_oracle.h.
  *
  * Each function cites the reference lines (relative to the reference repository root) whose
  * behaviour it restates.  Nothing here is copied: the loops, names and structure are our own, the

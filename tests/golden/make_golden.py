@@ -2,8 +2,10 @@
 
 PROVENANCE -- read this before trusting the numbers: these vectors are outputs of THIS repository's
 CPU oracle (oracle/emf_oracle.c, built with -ffp-contract=off), not of the reference's CUDA build.
-The reference cannot be built or run here (no CUDA, no OpenCV; the oracle header says "parity
-unpinned"), it ships no tests and no golden data.  What the vectors pin is (a) the oracle against
+The reference ships no tests and no golden data.  Its kernels, built for the host, pin the oracle
+elsewhere (oracle/build_ref.py, tests/test_oracle_pinned.py, and the recorded reference outputs of
+make_reference_golden.py); its OpenCV host chains, which the frame vectors also pass through, have
+no kernel text and stay a restatement.  What THESE vectors pin is (a) the oracle against
 drift -- any edit that changes its results fails tests/test_golden.py -- and (b) the HIP path against
 a fixed, reviewable set of inputs and outputs that travels to the GPU box as plain data.
 

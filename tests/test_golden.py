@@ -1,7 +1,8 @@
 """Committed regression vectors (tests/golden/*.npz, made by tests/golden/make_golden.py).
 
-These are outputs of this repository's CPU oracle on fixed inputs -- NOT reference outputs (the
-reference cannot run here and ships none; see the generator's header).  They travel to the GPU
+These are outputs of this repository's CPU oracle on fixed inputs -- NOT reference outputs (those
+are tests/golden/reference_v1.npz, see tests/test_reference_golden.py; the oracle's kernels are
+pinned to the reference's own in tests/test_oracle_pinned.py).  They travel to the GPU
 box as data, so the HIP path is checked against numbers that were reviewed and committed rather
 than recomputed on the spot, and the oracle itself is pinned against drift.
 
