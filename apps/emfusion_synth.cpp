@@ -14,6 +14,9 @@
 // together with the whole map seen from a viewer 1 m behind the world origin at 1024 x 768, and writeResults writes
 // those views as DIR/mesh_vis_out/%04d.png.  --3d-vis-eye x y z --3d-vis-target x y z place the viewer instead
 // (looking from eye at target, world -y up).
+// --color (with --sequence / --dir): the sequence's colour images (8-bit RGB / RGBA PNG) are fused into per-voxel colour
+// volumes beside the TSDFs, and mesh_*.ply, frame_meshes/ and the volume dump carry colours.  Refused for the
+// synthetic stream, which has no colour image.
 // --configfile FILE (-c): with --sequence / --dir, take every parameter from one of the reference's configuration files
 // (config/default.cfg, tum.cfg ...; core/Config.hpp) instead of the sizing options above.
 // --dir: the same loop on a Co-Fusion style dataset (ColorNNNN.png + DepthNNNN.exr), the reference's ImageReader
@@ -78,7 +81,7 @@ static void set3dView(emf::EMFusion& emf, const emf::Params& params, const View3
 static int runSequence(const std::string& seq, bool cofusion, const std::string& colordir, const std::string& depthdir,
                        const float* intrinsics, const std::string& configFile, const std::string& masks,
                        const std::string& outDir, int frames, int bgRes, float bgVoxel, int objRes, int maskFrames,
-                       int visibilityThresh, bool volumes, const View3d& view3d, bool frameMeshes) {
+                       int visibilityThresh, bool volumes, const View3d& view3d, bool frameMeshes, bool color) {
     std::unique_ptr<emf::TUMRGBDReader> tum;
     std::unique_ptr<emf::ImageReader> dir;
     size_t available = 0;
@@ -129,6 +132,8 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
         params.maskRCNNFrames = maskFrames;
     }
     emf::EMFusion emf(params);
+    if (color) emf.enableColor(true);                 // --color: the sequence's colour images go into the models
+    std::vector<uint8_t> rgb;
     if (!masks.empty()) emf.usePreprocMasks(masks);   // apps/EM-Fusion.cpp:115
     emf.setupOutput(frameMeshes, volumes);            // apps/EM-Fusion.cpp:112
     set3dView(emf, params, view3d);
@@ -145,6 +150,14 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
         emf::RGBD frame;
         frame.size = size;
         frame.depth = depth.data();
+        if (color) {
+            const emf::Size cs = cofusion ? dir->readColor(dir->firstIndex() + static_cast<int>(f), rgb) : tum->readColor(f, rgb);
+            if (cs.width != size.width || cs.height != size.height)
+                throw std::runtime_error("frame " + std::to_string(f) + ": the colour image is " + std::to_string(cs.width) +
+                                         " x " + std::to_string(cs.height) + ", the depth image " +
+                                         std::to_string(size.width) + " x " + std::to_string(size.height));
+            frame.rgb = rgb.data();
+        }
         emf.processFrame(frame);                      // apps/EM-Fusion.cpp:152
         if (view3d.on) emf.render(rendered.data());   // apps/EM-Fusion.cpp:156: the rendering and the 3D view
         if (f % 50 == 0) {
@@ -172,7 +185,7 @@ int main(int argc, char** argv) {
     float bgVoxel = 0.f;
     bool volumes = false;
     View3d view3d;
-    bool frameMeshes = false;
+    bool frameMeshes = false, color = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() { return i + 1 < argc ? std::atoi(argv[++i]) : 0; };
@@ -201,6 +214,7 @@ int main(int argc, char** argv) {
         else if (a == "--out" && i + 1 < argc) outDir = argv[++i];
         else if (a == "--3d-vis") view3d.on = true;
         else if (a == "--export-frame-meshes") frameMeshes = true;
+        else if (a == "--color") color = true;
         else if ((a == "--3d-vis-eye" || a == "--3d-vis-target") && i + 3 < argc) {
             float* dst = a == "--3d-vis-eye" ? view3d.eye : view3d.target;
             for (int k = 0; k < 3; ++k) dst[k] = static_cast<float>(std::atof(argv[++i]));
@@ -219,6 +233,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "emfusion_synth: --export-frame-meshes writes DIR/frame_meshes/ and needs --out DIR\n");
         return 2;
     }
+    if (color && sequence.empty() && dataDir.empty()) {  // (before any device is touched)
+        std::fprintf(stderr, "emfusion_synth: --color needs the colour images of --sequence or --dir; the synthetic stream has none\n");
+        return 2;
+    }
     if (view3d.on && outDir.empty()) {
         std::fprintf(stderr, "emfusion_synth: --3d-vis writes DIR/mesh_vis_out/ and needs --out DIR\n");
         return 2;
@@ -229,7 +247,7 @@ int main(int argc, char** argv) {
             const bool cofusion = !dataDir.empty();
             return runSequence(cofusion ? dataDir : sequence, cofusion, colordir, depthdir, haveIntrinsics ? intrinsics : nullptr,
                                configFile, maskDir, outDir, framesGiven, bgRes, bgVoxel > 0 ? bgVoxel : 5.12f / static_cast<float>(bgRes),
-                               objRes, maskFrames, visThresh, volumes, view3d, frameMeshes);
+                               objRes, maskFrames, visThresh, volumes, view3d, frameMeshes, color);
         }
         emf::Params params;  // reference defaults (config/default.cfg)
         params.frameSize = emf::Size(width, height);

@@ -44,6 +44,9 @@ def main():
                     help="the reference's per-frame mesh export: the background and every shown object meshed at the "
                          "end of every frame, written to OUT/frame_meshes/bg/%%04d.ply and OUT/frame_meshes/<id>/ "
                          "(needs --out)")
+    ap.add_argument("--color", action="store_true",
+                    help="fuse the sequence's colour images into per-voxel colour: mesh_*.ply (and frame meshes, volume "
+                         "dumps) carry colours")
     ap.add_argument("--frames", type=int, default=0, help="0 = all")
     ap.add_argument("--bg-res", type=int, default=512)
     ap.add_argument("--bg-voxel", type=float, default=0.01)
@@ -81,6 +84,8 @@ def main():
         fx, fy, cx, cy = args.intrinsics
         prm.K[:] = [fx, 0, cx, 0, fy, cy, 0, 0, 1]
     fus = pipeline.Fusion(prm, None)
+    if args.color:
+        fus.enable_color()
     fus.set_ignore_person(args.ignore_person)
     fus.set_preprocess(True)
     fus.set_cleanup(True)
@@ -105,6 +110,13 @@ def main():
                 keep += dev_masks
                 fus.queue_instance_masks([image_view(m) for m in dev_masks])
                 fus.queue_instance_scores(scores)
+        if args.color:
+            rgb = reader.color_image(index0 + f) if args.cofusion else reader.color(f)
+            if rgb.shape[:2] != depth.shape:
+                raise SystemExit(f"frame {f}: the colour image is {rgb.shape[1]} x {rgb.shape[0]}, the depth image {w} x {h}")
+            c = DeviceArray.from_numpy(rgb)
+            keep.append(c)
+            fus.set_color_image(image_view(c))
         if f == 1:
             fus.set_tracking(camera=True, objects=True)  # frame 0 defines the world frame
         fus.process_frame(image_view(d), eye, zero, {}, {}, False)

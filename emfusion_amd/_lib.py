@@ -154,6 +154,12 @@ SIGNATURES = {
                                   _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, C.c_int, _FP,
                                   _STREAM],
     "emf_hip_visibilityFlagsIndexed": [_FP, C.c_int, _I3, C.c_int, _FP, _STREAM],
+    "emf_hip_integrateColorBatched": [_FP, _FP, _FP, _I3, C.c_int, _FP, _IMG, _IMG, _IMG, _F9, _FP, _STREAM],
+    "emf_hip_copyColorValues": [_FP, _FP, _I3, _I3, _I3, _STREAM],
+    "emf_hip_sampleColor": [_FP, _FP, _FP, _I3, C.c_int, _IMG, _IMG, C.c_void_p, _IMG, _STREAM],
+    "emf_hip_renderPhongColor": [_IMG, _IMG, _IMG, _F9, _IMG, _STREAM],
+    "emf_hip_meshColors": [_FP, _FP, _FP, _FP, _I3, _FP, _FP, _STREAM],
+    "emf_hip_meshColorsBatched": [_FP, _FP, _I3, C.c_int, _FP, _FP, _STREAM],
 }
 
 

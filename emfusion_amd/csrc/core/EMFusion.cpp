@@ -189,6 +189,7 @@ void EMFusion::reset() {
     bgBackStale = false;
     bgPrepared = false;
     bgListPending = false;
+    colorImageSet = false;
     trackPredicted[0] = trackPredicted[1] = 0;
     Stream& s = Stream::Null();
     bg_associationWeights.setTo(1.f, s);
@@ -332,6 +333,18 @@ void EMFusion::rebuildModelTable() {
         // the background gets its second copy the first time the two-level launch is usable
         background.enableDoubleBuffer();
         bgCullScratch = DeviceBuffer(emf_hip_integrateCullScratchBytes(resHost.data(), 1));
+    }
+    if (colorOn) {  // colour volumes for models created or resized since, and their pointers beside the table
+        std::vector<uint16_t*> ptrs;
+        background.enableColor();
+        ptrs.push_back(background.colorPtr());
+        for (auto& obj : objects) {
+            obj.enableColor();
+            ptrs.push_back(obj.colorPtr());
+        }
+        if (colorTable.empty()) colorTable = DeviceBuffer(sizeof(uint16_t*) * EMF_MAX_MODELS);
+        hipCheck(hipMemcpy(colorTable.data(), ptrs.data(), ptrs.size() * sizeof(uint16_t*), hipMemcpyHostToDevice),
+                 "colour table upload");
     }
     tableSel = 0;
     // (the per-volume path uploads the table too: cleanUpObjs reads the objects' raycast masks and association
@@ -478,6 +491,13 @@ void EMFusion::processFrame(const RGBD& frame) {
     const emf_image_t depthDev = stageDepth(frame.depth, slot);  // reference EMFusion.cpp:72
     uploadHostSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     ++uploads;
+    if (colorOn && frame.rgb) {  // pageable source on the frame's stream: ordered behind the previous frame's colour pass
+        const size_t bytes = static_cast<size_t>(params.frameSize.area()) * 3;
+        if (rgbUpload.empty()) rgbUpload = DeviceBuffer(bytes);
+        hipCheck(hipMemcpyAsync(rgbUpload.data(), frame.rgb, bytes, hipMemcpyHostToDevice, main.get()), "hipMemcpyAsync H2D (rgb)");
+        setColorImage(emf_image_t{rgbUpload.data(), static_cast<size_t>(params.frameSize.width) * 3, params.frameSize.width,
+                                  params.frameSize.height});
+    }
     FrameInputs in = pending;
     in.preprocessDepth = true;              // reference EMFusion.cpp:74
     if (!maskPath.empty() && frameCount % params.maskRCNNFrames == 0) loadPreprocMasks(in);  // EMFusion.cpp:99-101, 375-395
@@ -918,6 +938,7 @@ void EMFusion::integrateBatched() {
             }
         });
     }
+    integrateColor(oc);
     const bool overlapped = bgInFlight;
     joinBackground();
     if (useFarBounds && !farBounds.empty()) {
@@ -933,6 +954,72 @@ void EMFusion::integrateBatched() {
                      "updateRelevantTiles");
         });
     }
+}
+
+// Colour pass of the frame, every model of the table (background included: colour is kept once, not double
+// buffered) in one launch per table chunk.  It reads the frame's depth, pose, association maps and visibility
+// gate and nothing the TSDF integration writes, so any place behind the last E-step and the visibility counts
+// is correct.  It sits on `main` behind the objects' integration: there the raycast is over, so the
+// raycast || background-sweep overlap is left alone (the sweep on `aux` is at most still draining), and the
+// launch needs no event of its own -- `main` order puts it behind the E-step, the composite's counts and the
+// upload of the colour image, and in front of whatever reads the colour volumes next.
+void EMFusion::integrateColor(const std::vector<emf_pose_t>& oc) {
+    if (!colorOn || !colorImageSet) return;
+    colorImageSet = false;  // consumed by this frame
+    const emf_image_t il = invLambda.view();
+    const emf_image_t* ilp = useLambdaTable ? &il : nullptr;
+    forChunks(0, static_cast<int>(oc.size()), [&](int from, int count) {
+        emfCheck(emf_hip_integrateColorBatched(currentTable() + from, colorTable.as<uint16_t*>() + from, oc.data() + from,
+                                               resHost.data() + 3 * from, count, visibleDev.as<int32_t>() + from, &depth,
+                                               ilp, &colorImage, params.intr.val, colorStatsDev.as<uint64_t>(),
+                                               main.abi()),
+                 "integrateColorBatched");
+    });
+}
+
+void EMFusion::enableColor(bool on) {
+    if (on == colorOn) return;
+    if (frameCount != 0)
+        throw HipError("EMFusion::enableColor: only before the first frame or after reset()", EMF_E_ARG);
+    if (on && sharded)  // like the per-frame meshes: remote objects are not on this rank
+        throw HipError("EMFusion::enableColor: colour is not supported on the sharded path", EMF_E_ARG);
+    if (on && (forceLegacy || gradMode != TSDF::Gradients::OnTheFly))
+        throw HipError("EMFusion::enableColor: colour is not supported on the per-volume path", EMF_E_ARG);
+    if (on && !(params.tsdfParams.maxTSDFWeight < 256.f))
+        throw HipError("EMFusion::enableColor: maxTSDFWeight must be below 256 (8.8 fixed-point colour weight)", EMF_E_ARG);
+    quiesce();
+    colorOn = on;
+    colorImageSet = false;
+    if (on) {
+        if (colorStatsDev.empty()) colorStatsDev = DeviceBuffer(sizeof(uint64_t));
+        colorStatsDev.setZero(Stream::Null());
+        Stream::Null().waitForCompletion();
+    } else {
+        background.dropColor();
+        for (auto& obj : objects) obj.dropColor();
+    }
+    rebuildModelTable();
+}
+
+void EMFusion::setColorImage(const emf_image_t& rgbDev) {
+    if (!colorOn) throw HipError("EMFusion::setColorImage: colour is not enabled", EMF_E_ARG);
+    if (!rgbDev.data) throw HipError("EMFusion::setColorImage: image data is NULL", EMF_E_NULL);
+    if (rgbDev.width != params.frameSize.width || rgbDev.height != params.frameSize.height)
+        throw HipError("EMFusion::setColorImage: image size differs from Params::frameSize", EMF_E_SHAPE);
+    if (rgbDev.pitch < static_cast<size_t>(rgbDev.width) * 3)
+        throw HipError("EMFusion::setColorImage: pitch smaller than a row", EMF_E_PITCH);
+    colorImage = rgbDev;
+    colorImageSet = true;
+}
+
+uint64_t EMFusion::takeColoredVoxels() {
+    if (colorStatsDev.empty()) return 0;
+    synchronize();
+    uint64_t v = 0;
+    colorStatsDev.download(&v, main);
+    colorStatsDev.setZero(main);
+    main.waitForCompletion();
+    return v;
 }
 
 // Compositing in list (creation) order + visibility counts (reference EMFusion.cpp:760-794).

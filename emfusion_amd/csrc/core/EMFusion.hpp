@@ -32,7 +32,7 @@ namespace emf {
 struct RGBD {
     Size size;
     const float* depth = nullptr;   // metres, W x H, row-major, host memory
-    const uint8_t* rgb = nullptr;   // optional, unused by the volumetric path
+    const uint8_t* rgb = nullptr;   // optional u8 x 3, W x H: fused into the colour volumes when colour is on
 };
 
 /** What tracking and Mask R-CNN would have produced for one frame. */
@@ -208,6 +208,18 @@ public:
         expVols = exp_vols;
     }
     /**
+     * Per-voxel colour (include/emf_hip.h "Per-voxel colour"; new behaviour, off by default).  enableColor(true)
+     * gives every model a colour volume -- now, and at creation for later objects -- and a frame that was handed a
+     * colour image (setColorImage, or RGBD::rgb) fuses it behind its TSDF integration with the association
+     * weights that integration used.  Before the first frame / after reset() only; one-rank batched path only.
+     */
+    void enableColor(bool on);
+    bool colorEnabled() const { return colorOn; }
+    /** u8 x 3 device image of the frame size for the NEXT frame only; it must stay valid until that frame has run. */
+    void setColorImage(const emf_image_t& rgbDev);
+    /** Voxels the colour pass has updated since the last call (synchronises). */
+    uint64_t takeColoredVoxels();
+    /**
      * Reference EMFusion::writeResults (EMFusion.cpp:248-292): pose files and meshes always, the
      * tsdfs/ dumps only with `volumes` (or setupOutput's exp_vols).
      */
@@ -250,7 +262,11 @@ public:
      * image, statistic or log of the frame path.  Black / zeros before the first frame.  Not on the sharded path.
      */
     void renderView(const Affine3f& viewerPose, const float K[9], Size size, uint8_t* rgb, float* raylengths = nullptr,
-                    uint8_t* seg = nullptr);
+                    uint8_t* seg = nullptr, int shading = 0);
+    /** Shading of a view: the label colour of the model under the pixel (today's bytes), or the colour of the voxel
+     *  nearest to the pixel's vertex (enableColor; voxels nobody coloured fall back to the label colour). */
+    enum { ShadeLabel = 0, ShadeColor = 1 };
+    void set3dViewShading(int shading);
     /**
      * The logged 3D view (reference --3d-vis): from now on render() also renders this view and, with the log on
      * (setupOutput), keeps it as frame frameCount - 1's PNG; writeResults() then writes <dir>/mesh_vis_out/%04d.png
@@ -474,6 +490,9 @@ private:
     DeviceImage<uint8_t, 3> viewImage;
     DeviceImage<float> viewRay;
     DeviceImage<uint8_t> viewSeg;
+    DeviceImage<float, 3> viewVert, viewNorm;  // colour shading only: what the view kernel hit, for the pixel pass
+    DeviceImage<uint8_t, 3> viewColor;         // ... and the colour sampled under every pixel
+    int view3dShading = 0;
     bool view3d = false;  // set3dView: render() renders (and logs) this view too
     Affine3f view3dPose;
     float view3dK[9] = {};
@@ -505,6 +524,7 @@ private:
     DeviceBuffer logScratch;                                          // 2 x EMF_MAX_BATCH float images
     struct SavedVolumes {                                  // tsdfs / intWeights / fgProbs / meta of the reference
         std::vector<float> tsdf, weights, fgProbs;
+        std::vector<uint16_t> color;                       // colour on only: u16 x 4 per voxel
         Vec3i res;
         float voxelSize = 0.f;
     };
@@ -610,6 +630,14 @@ private:
     bool anyScan = false;
     DeviceBuffer visibleDev;        // int32 per model slot: integrate gate, written on the device
     DeviceBuffer integrateStatsDev; // u64: voxels swept by integrateBatched
+    // ---- per-voxel colour (enableColor) ----
+    bool colorOn = false;
+    bool colorImageSet = false;     // colorImage goes with the next integration, and with that one only
+    emf_image_t colorImage{};
+    DeviceBuffer colorTable;        // uint16_t* per table slot, parallel to the model table (emf_model_t keeps its layout)
+    DeviceBuffer colorStatsDev;     // u64: voxels coloured
+    DeviceBuffer rgbUpload;         // device copy of RGBD::rgb (processFrame(const RGBD&))
+    void integrateColor(const std::vector<emf_pose_t>& oc);
     int32_t* visibleHost = nullptr; // pinned mirror of visCounts for visibleObjects()
     bool visPending = false;
     std::vector<int32_t> visIds;    // object ids in the order of the pending counts

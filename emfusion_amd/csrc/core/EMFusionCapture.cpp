@@ -75,6 +75,11 @@ void EMFusion::writeResults(const std::string& dir, bool volumes) {
         io::writeVolume(t + "/" + name + ".bin", v.data(), sizeof(float), res, vox);
     };
     dump("bg_tsdf", background.getTSDF(), background.getVolumeRes(), background.getVoxelSize());
+    // colour on only: one colour volume per model in the same container, element = u16 x 4 (R, G, B, Wc in 8.8)
+    auto dumpColor = [&](const std::string& name, const std::vector<uint16_t>& v, const Vec3i& res, float vox) {
+        if (!v.empty()) io::writeVolume(t + "/" + name + ".bin", v.data(), 4 * sizeof(uint16_t), res, vox);
+    };
+    dumpColor("bg_color", background.getColorVol(), background.getVolumeRes(), background.getVoxelSize());
     for (auto& obj : objects) {
         if (ignorePerson && isPerson(obj)) continue;  // the same `continue` skips them (EMFusion.cpp:274-277)
         savedVolumes[obj.getID()] = saveVolumes(obj);
@@ -84,6 +89,7 @@ void EMFusion::writeResults(const std::string& dir, bool volumes) {
         dump("tsdf_" + id, sv.second.tsdf, sv.second.res, sv.second.voxelSize);
         dump("weights_" + id, sv.second.weights, sv.second.res, sv.second.voxelSize);
         dump("fgProbs_" + id, sv.second.fgProbs, sv.second.res, sv.second.voxelSize);
+        dumpColor("color_" + id, sv.second.color, sv.second.res, sv.second.voxelSize);
     }
 }
 
@@ -92,6 +98,7 @@ EMFusion::SavedVolumes EMFusion::saveVolumes(ObjTSDF& obj) {  // EMFusion.cpp:27
     sv.tsdf = obj.getTSDF();
     sv.weights = obj.getWeightsVol();
     sv.fgProbs = obj.getFgProbVol();
+    sv.color = obj.getColorVol();
     sv.res = obj.getVolumeRes();
     sv.voxelSize = obj.getVoxelSize();
     return sv;
@@ -230,6 +237,7 @@ void EMFusion::storeFgProbs() {
 std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
     const int n = static_cast<int>(ids.size());
     std::vector<Mesh> out(ids.size());
+    for (Mesh& m : out) m.colored = colorOn;
     if (n == 0) return out;
     if (n > EMF_MAX_MODELS) throw HipError("EMFusion::extractMeshes: " + std::to_string(n) + " models", EMF_E_LIMIT);
     if (!meshHost)
@@ -297,12 +305,27 @@ std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
     hipCheck(hipMemcpyAsync(nHost, nDev, vb, hipMemcpyDeviceToHost, main.get()), "mesh normals D2H");
     if (nt) hipCheck(hipMemcpyAsync(tHost, tDev, 4 * sizeof(int32_t) * nt, hipMemcpyDeviceToHost, main.get()), "mesh triangles D2H");
     main.waitForCompletion();
+    std::vector<uint8_t> cHost;
+    if (colorOn) {  // the same vertices, coloured: one more walk over the surface chunks the count listed
+        std::vector<uint16_t*> ptrs(n, nullptr);
+        for (int k = 0; k < n; ++k) ptrs[k] = ids[k] == 0 ? background.colorPtr() : getObject(ids[k])->colorPtr();
+        DeviceBuffer ptrsDev(sizeof(uint16_t*) * n), cDev(3 * nv);
+        hipCheck(hipMemcpyAsync(ptrsDev.data(), ptrs.data(), sizeof(uint16_t*) * n, hipMemcpyHostToDevice, main.get()),
+                 "mesh colour table upload");
+        emfCheck(emf_hip_meshColorsBatched(meshTableDev.as<emf_model_t>(), ptrsDev.as<uint16_t*>(), res.data(), n,
+                                           meshScratch.data(), cDev.as<uint8_t>(), main.abi()),
+                 "meshColorsBatched");
+        cHost.resize(3 * nv);
+        hipCheck(hipMemcpyAsync(cHost.data(), cDev.data(), 3 * nv, hipMemcpyDeviceToHost, main.get()), "mesh colours D2H");
+        main.waitForCompletion();
+    }
     for (int k = 0; k < n; ++k) {  // model k's slice is its own mesh (local triangle indices)
         const size_t v0 = bases[2 * k], t0 = bases[2 * k + 1];
         Mesh& m = out[k];
         m.cloud.assign(vHost + 3 * v0, vHost + 3 * (v0 + counts[k].vertices));
         m.normals.assign(nHost + 3 * v0, nHost + 3 * (v0 + counts[k].vertices));
         m.polygons.assign(tHost + 4 * t0, tHost + 4 * (t0 + counts[k].triangles));
+        if (!cHost.empty()) m.colors.assign(cHost.begin() + 3 * v0, cHost.begin() + 3 * (v0 + counts[k].vertices));
     }
     return out;
 }

@@ -15,7 +15,11 @@ namespace emf {
 using namespace detail;
 
 void EMFusion::renderView(const Affine3f& viewerPose, const float K[9], Size size, uint8_t* rgb, float* raylengths,
-                          uint8_t* seg) {
+                          uint8_t* seg, int shading) {
+    if (shading != ShadeLabel && shading != ShadeColor)
+        throw HipError("EMFusion::renderView: unknown shading " + std::to_string(shading), EMF_E_ARG);
+    if (shading == ShadeColor && !colorOn)
+        throw HipError("EMFusion::renderView: colour shading needs colour (enableColor)", EMF_E_ARG);
     if (sharded)  // like render(): remote objects are not on this rank
         throw HipError("EMFusion::renderView: not available on the sharded path (remote objects stay on their ranks)",
                        EMF_E_ARG);
@@ -73,13 +77,35 @@ void EMFusion::renderView(const Affine3f& viewerPose, const float K[9], Size siz
         viewImage = DeviceImage<uint8_t, 3>(size);
         viewRay = DeviceImage<float>(size);
         viewSeg = DeviceImage<uint8_t>(size);
+        viewVert = DeviceImage<float, 3>();
+    }
+    const bool shadeColor = shading == ShadeColor;
+    if (shadeColor && viewVert.empty()) {
+        viewVert = DeviceImage<float, 3>(size);
+        viewNorm = DeviceImage<float, 3>(size);
+        viewColor = DeviceImage<uint8_t, 3>(size);
     }
     const emf_image_t iv = viewImage.view(), rv = viewRay.view(), sv = viewSeg.view();
     const float light[3] = {0.f, 0.f, 0.f};  // at the viewer, as render() has it at the camera
+    emf_image_t vv{}, nv{}, cv{};
+    if (shadeColor) {
+        vv = viewVert.view();
+        nv = viewNorm.view();
+        cv = viewColor.view();
+    }
     emfCheck(emf_hip_renderView(table, viewPosesDev.as<emf_pose_t>(), ids.data(), n, size.width, size.height, K, light,
-                                colorMap.data(), hide, &iv, raylengths ? &rv : nullptr, seg ? &sv : nullptr, nullptr,
-                                nullptr, nullptr, main.abi()),
+                                colorMap.data(), hide, &iv, raylengths ? &rv : nullptr, (seg || shadeColor) ? &sv : nullptr,
+                                shadeColor ? &vv : nullptr, shadeColor ? &nv : nullptr, nullptr, main.abi()),
              "renderView");
+    if (shadeColor) {
+        // A pixel pass over what the view kernel hit (it stays as it is): the colour of the voxel nearest to each
+        // vertex in the model the segmentation names, then the same Phong terms fed with it.  Labels hidden by
+        // ignore_person were replaced by the background's hit in the view kernel, so they sample the background.
+        emfCheck(emf_hip_sampleColor(table, colorTable.as<uint16_t*>(), viewPosesDev.as<emf_pose_t>(), ids.data(), n, &vv,
+                                     &sv, colorMap.data(), &cv, main.abi()),
+                 "sampleColor");
+        emfCheck(emf_hip_renderPhongColor(&vv, &nv, &cv, light, &iv, main.abi()), "renderPhongColor");
+    }
     hipCheck(hipMemcpyAsync(rgb, viewImage.ptr(), 3 * px, hipMemcpyDeviceToHost, main.get()), "view D2H");
     if (raylengths)
         hipCheck(hipMemcpyAsync(raylengths, viewRay.ptr(), sizeof(float) * px, hipMemcpyDeviceToHost, main.get()),
@@ -97,11 +123,19 @@ void EMFusion::set3dView(const Affine3f& viewerPose, const float K[9], Size size
     view3dSize = size;
 }
 
+void EMFusion::set3dViewShading(int shading) {
+    if (shading != ShadeLabel && shading != ShadeColor)
+        throw HipError("EMFusion::set3dViewShading: unknown shading " + std::to_string(shading), EMF_E_ARG);
+    if (shading == ShadeColor && !colorOn)
+        throw HipError("EMFusion::set3dViewShading: colour shading needs colour (enableColor)", EMF_E_ARG);
+    view3dShading = shading;
+}
+
 // render()'s 3D view: EMFusion::render draws the viz window every frame and writeResults writes what it showed
 void EMFusion::render3dView() {
     if (!view3d) return;
     view3dRgb.resize(3 * view3dSize.area());
-    renderView(view3dPose, view3dK, view3dSize, view3dRgb.data());
+    renderView(view3dPose, view3dK, view3dSize, view3dRgb.data(), nullptr, nullptr, colorOn ? view3dShading : ShadeLabel);
     if (saveOutput)  // `mesh_vis[frameCount-1]`, EMFusion.cpp:228-230
         meshVis[frameCount - 1] = io::encodePng(view3dRgb.data(), view3dSize.width, view3dSize.height, 3);
 }

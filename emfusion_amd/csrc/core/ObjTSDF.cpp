@@ -115,7 +115,15 @@ Vec3f ObjTSDF::resize(const Vec3f& p10, const Vec3f& p90, float volPad, Stream& 
         newGrads = DeviceBuffer(nv * 3 * sizeof(float));
         shift(tsdfGrads, newGrads, 3);
     }
+    DeviceBuffer newColor;
+    if (!colorVol.empty()) {
+        newColor = DeviceBuffer(nv * 4 * sizeof(uint16_t));
+        emfCheck(emf_hip_copyColorValues(colorVol.as<uint16_t>(), newColor.as<uint16_t>(), pixOffset.val,
+                                         volumeRes.val, newRes.val, stream.abi()),
+                 "ObjTSDF::resize (colour)");
+    }
     stream.waitForCompletion();  // the old buffers are released below
+    colorVol = std::move(newColor);
     tsdfVol = std::move(newVol);
     tsdfWeights = std::move(newWeights);
     tsdfGrads = std::move(newGrads);

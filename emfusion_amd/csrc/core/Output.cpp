@@ -130,15 +130,27 @@ void writeMesh(const std::string& filename, const Mesh& mesh) {
     FILE* file = std::fopen(filename.c_str(), "w");
     if (!file) throw std::runtime_error("Could not write ply file: " + filename);
     const int nv = static_cast<int>(mesh.vertices()), nf = static_cast<int>(mesh.triangles());
+    // colour on only (Mesh::colored): red / green / blue behind the normals; without it the reference's bytes
+    const bool col = mesh.colored;
+    if (col && mesh.colors.size() != mesh.cloud.size()) {
+        std::fclose(file);
+        throw std::runtime_error("emf::io::writeMesh: " + std::to_string(mesh.colors.size() / 3) + " colours for " +
+                                 std::to_string(nv) + " vertices: " + filename);
+    }
     std::fprintf(file,
                  "ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
-                 "property float z\nproperty float nx\nproperty float ny\nproperty float nz\n"
+                 "property float z\nproperty float nx\nproperty float ny\nproperty float nz\n%s"
                  "element face %d\nproperty list uchar int vertex_index\nend_header\n",
-                 nv, nf);
+                 nv, col ? "property uchar red\nproperty uchar green\nproperty uchar blue\n" : "", nf);
     for (int i = 0; i < nv; ++i) {
         const float* v = &mesh.cloud[3 * static_cast<size_t>(i)];
         const float* n = &mesh.normals[3 * static_cast<size_t>(i)];
-        std::fprintf(file, "%f %f %f %f %f %f\n", v[0], v[1], v[2], n[0], n[1], n[2]);
+        if (col) {
+            const uint8_t* c = &mesh.colors[3 * static_cast<size_t>(i)];
+            std::fprintf(file, "%f %f %f %f %f %f %d %d %d\n", v[0], v[1], v[2], n[0], n[1], n[2], c[0], c[1], c[2]);
+        } else {
+            std::fprintf(file, "%f %f %f %f %f %f\n", v[0], v[1], v[2], n[0], n[1], n[2]);
+        }
     }
     for (int i = 0; i < nf; ++i) {
         const int32_t* t = &mesh.polygons[4 * static_cast<size_t>(i)];

@@ -33,7 +33,13 @@ uint32_t be32(const unsigned char* p) { return (uint32_t(p[0]) << 24) | (uint32_
 
 }  // namespace
 
-void readPngGray(const std::string& path, std::vector<uint16_t>& pixels, int& width, int& height) {
+namespace {
+
+// The PNG container, the zlib stream and the scan-line filters (PNG 9.2) behind both image readers: `img` receives
+// height x width x bpp reconstructed bytes.  `check` sees the header (bit depth, colour type, interlace method) before
+// anything is inflated and throws for what its caller does not read.
+template <typename Check>
+void decodePng(const std::string& path, std::vector<unsigned char>& img, int& width, int& height, int& bpp, Check check) {
     const std::string raw = slurp(path);
     static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
     if (raw.size() < 8 || std::memcmp(raw.data(), sig, 8) != 0) throw std::runtime_error(path + ": not a PNG file");
@@ -59,9 +65,7 @@ void readPngGray(const std::string& path, std::vector<uint16_t>& pixels, int& wi
         }
         pos += 12 + n;
     }
-    if (color != 0 || (depth != 8 && depth != 16) || interlace != 0 || width <= 0 || height <= 0)
-        throw std::runtime_error(path + ": only non-interlaced 8/16-bit grayscale PNGs are supported");
-    const int bpp = depth / 8;
+    bpp = check(depth, color, interlace);
     const size_t stride = static_cast<size_t>(width) * bpp;
     std::vector<unsigned char> rows((stride + 1) * height);
     uLongf got = rows.size();
@@ -69,7 +73,7 @@ void readPngGray(const std::string& path, std::vector<uint16_t>& pixels, int& wi
         throw std::runtime_error(path + ": cannot inflate the image data");
     // scan-line filters (PNG 9.2): Sub / Average / Paeth predict from the reconstructed bytes to the left (a),
     // above (b) and above-left (c)
-    std::vector<unsigned char> img(stride * height);
+    img.resize(stride * height);
     const unsigned char* prev = nullptr;
     for (int y = 0; y < height; ++y) {
         const unsigned char* in = rows.data() + static_cast<size_t>(y) * (stride + 1);
@@ -92,9 +96,42 @@ void readPngGray(const std::string& path, std::vector<uint16_t>& pixels, int& wi
         }
         prev = cur;
     }
+}
+
+}  // namespace
+
+void readPngGray(const std::string& path, std::vector<uint16_t>& pixels, int& width, int& height) {
+    std::vector<unsigned char> img;
+    int bpp = 0;
+    decodePng(path, img, width, height, bpp, [&](int depth, int color, int interlace) {
+        if (color != 0 || (depth != 8 && depth != 16) || interlace != 0 || width <= 0 || height <= 0)
+            throw std::runtime_error(path + ": only non-interlaced 8/16-bit grayscale PNGs are supported");
+        return depth / 8;
+    });
     pixels.resize(static_cast<size_t>(width) * height);
     for (size_t i = 0; i < pixels.size(); ++i)
         pixels[i] = bpp == 1 ? img[i] : static_cast<uint16_t>((img[2 * i] << 8) | img[2 * i + 1]);  // big endian
+}
+
+void readPngColor(const std::string& path, std::vector<uint8_t>& rgb, int& width, int& height) {
+    std::vector<unsigned char> img;
+    int bpp = 0;
+    decodePng(path, img, width, height, bpp, [&](int depth, int color, int interlace) {
+        if (width <= 0 || height <= 0) throw std::runtime_error(path + ": no PNG header");
+        if (width > kMaxColorSide || height > kMaxColorSide || static_cast<long long>(width) * height > kMaxColorPixels)
+            throw std::runtime_error(path + ": colour image of " + std::to_string(width) + " x " + std::to_string(height) +
+                                     " exceeds " + std::to_string(kMaxColorSide) + " pixels a side");
+        if (color == 3) throw std::runtime_error(path + ": palette PNGs are not supported as colour images");
+        if (interlace != 0) throw std::runtime_error(path + ": interlaced PNGs are not supported");
+        if ((color != 2 && color != 6) || depth != 8)
+            throw std::runtime_error(path + ": only 8-bit RGB / RGBA PNGs are supported as colour images (colour type " +
+                                     std::to_string(color) + ", " + std::to_string(depth) + " bits)");
+        return color == 2 ? 3 : 4;
+    });
+    const size_t n = static_cast<size_t>(width) * height;
+    rgb.resize(3 * n);
+    for (size_t i = 0; i < n; ++i)  // alpha dropped
+        for (int c = 0; c < 3; ++c) rgb[3 * i + c] = img[bpp * i + c];
 }
 
 // ---- TUM RGB-D sequences ---------------------------------------------------------------------------------------
@@ -139,6 +176,12 @@ Size TUMRGBDReader::readDepth(size_t i, std::vector<float>& depth) const {
     depth.resize(px.size());
     const float s = 1.f / 5000.f;  // TUM depth scale (TUMRGBDReader.cpp: convertTo(CV_32FC1, 1 / 5000.))
     for (size_t k = 0; k < px.size(); ++k) depth[k] = static_cast<float>(px[k]) * s;
+    return Size(w, h);
+}
+
+Size TUMRGBDReader::readColor(size_t i, std::vector<uint8_t>& rgb) const {
+    int w = 0, h = 0;
+    readPngColor(path + rgbFileNames.at(i), rgb, w, h);
     return Size(w, h);
 }
 
@@ -364,6 +407,11 @@ ImageReader::ImageReader(std::string basepath, std::string colordir, std::string
 }
 std::string ImageReader::depthFileName(int index) const { return indexed(depthpath, "Depth", index, ".exr"); }
 std::string ImageReader::colorFileName(int index) const { return indexed(colorpath, "Color", index, ".png"); }
+Size ImageReader::readColor(int index, std::vector<uint8_t>& rgb) const {
+    int w = 0, h = 0;
+    readPngColor(colorFileName(index), rgb, w, h);
+    return Size(w, h);
+}
 Size ImageReader::readDepth(int index, std::vector<float>& depth) const {
     const Size s = readExr(depthFileName(index), depth);
     for (float& d : depth)

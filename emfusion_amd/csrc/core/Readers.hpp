@@ -18,6 +18,15 @@ namespace emf {
 
 /** Non-interlaced 8- or 16-bit grayscale PNG -> pixel values, row-major.  Throws std::runtime_error. */
 void readPngGray(const std::string& path, std::vector<uint16_t>& pixels, int& width, int& height);
+/** What readPngColor accepts of an untrusted header: checked before anything is allocated or inflated. */
+constexpr int kMaxColorSide = 16384;
+constexpr long long kMaxColorPixels = 1ll << 26;  // 64 Mpx: at most ~0.5 GiB of row, image and output buffers
+/**
+ * Non-interlaced 8-bit PNG of colour type 2 (RGB) or 6 (RGBA, alpha dropped) -> u8 x 3, row-major: the colour images of
+ * the TUM and Co-Fusion sequences.  Palette, 16-bit, grayscale and interlaced files and images above kMaxColorSide
+ * pixels a side or kMaxColorPixels in all are rejected with a message.  Throws std::runtime_error.
+ */
+void readPngColor(const std::string& path, std::vector<uint8_t>& rgb, int& width, int& height);
 
 /** Keeps the reference's class name and the parts of its surface the main loop uses. */
 class TUMRGBDReader {
@@ -32,6 +41,8 @@ public:
     const std::string& depthFileName(size_t i) const { return depthFileNames[i]; }
     /** depth of frame i in metres (16-bit PNG / 5000, TUMRGBDReader.cpp readFrame); returns its size */
     Size readDepth(size_t i, std::vector<float>& depth) const;
+    /** colour image of frame i (u8 x 3, readPngColor); returns its size */
+    Size readColor(size_t i, std::vector<uint8_t>& rgb) const;
 
 private:
     std::string path;
@@ -63,6 +74,8 @@ public:
     std::string colorFileName(int index) const;
     /** depth of file index `index` (firstIndex() ... ); returns its size */
     Size readDepth(int index, std::vector<float>& depth) const;
+    /** colour image of file index `index` (u8 x 3, readPngColor); returns its size */
+    Size readColor(int index, std::vector<uint8_t>& rgb) const;
 
 private:
     std::string colorpath, depthpath;

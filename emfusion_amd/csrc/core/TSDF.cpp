@@ -140,6 +140,7 @@ void TSDF::reset(const Affine3f& _pose) {
     tsdfVol.setZero(s);
     tsdfWeights.setZero(s);
     if (!tsdfGrads.empty()) tsdfGrads.setZero(s);
+    if (!colorVol.empty()) colorVol.setZero(s);
     emfCheck(emf_hip_resetBrickFlags(brickFlags.as<uint8_t>(), volumeRes.val, s.abi()),
              "TSDF::reset");
     if (volumeRes[0] % 4 == 0) {  // an all-zero volume has neither sign anywhere
@@ -347,6 +348,7 @@ Mesh TSDF::extractMesh(const uint8_t* fgVolMask) {
     emf_mesh_counts_t counts{};
     countsDev.download(&counts, s);
     Mesh mesh;
+    mesh.colored = !colorVol.empty();
     if (counts.vertices == 0) return mesh;
     DeviceBuffer v(counts.vertices * 3 * sizeof(float)), n(counts.vertices * 3 * sizeof(float)),
         t(std::max<size_t>(counts.triangles, 1) * 4 * sizeof(int32_t));
@@ -359,6 +361,14 @@ Mesh TSDF::extractMesh(const uint8_t* fgVolMask) {
     mesh.polygons.resize(static_cast<size_t>(counts.triangles) * 4);
     v.download(mesh.cloud.data(), s);
     n.download(mesh.normals.data(), s);
+    if (!colorVol.empty()) {  // the same vertices, coloured
+        DeviceBuffer c(static_cast<size_t>(counts.vertices) * 3);
+        emfCheck(emf_hip_meshColors(tsdfVol.as<float>(), tsdfWeights.as<float>(), fgVolMask, colorVol.as<uint16_t>(),
+                                    volumeRes.val, scratch.data(), c.as<uint8_t>(), s.abi()),
+                 "TSDF::getMesh (colours)");
+        mesh.colors.resize(static_cast<size_t>(counts.vertices) * 3);
+        c.download(mesh.colors.data(), s);
+    }
     if (counts.triangles) {
         std::vector<int32_t> all(std::max<size_t>(counts.triangles, 1) * 4);
         t.download(all.data(), s);
@@ -378,6 +388,23 @@ std::vector<float> TSDF::getWeightsVol() const {
     hipCheck(hipDeviceSynchronize(), "hipDeviceSynchronize");
     std::vector<float> h(voxels());
     tsdfWeights.download(h.data(), Stream::Null());
+    return h;
+}
+
+void TSDF::enableColor() {
+    if (!colorVol.empty()) return;
+    colorVol = DeviceBuffer(voxels() * 4 * sizeof(uint16_t));
+    Stream& s = Stream::Null();
+    colorVol.setZero(s);
+    s.waitForCompletion();
+}
+
+std::vector<uint16_t> TSDF::getColorVol() const {
+    std::vector<uint16_t> h;
+    if (colorVol.empty()) return h;
+    hipCheck(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    h.resize(voxels() * 4);
+    colorVol.download(h.data(), Stream::Null());
     return h;
 }
 

@@ -95,6 +95,17 @@ public:
     Gradients gradientMode() const { return gradMode; }
 
     /**
+     * Colour volume (include/emf_hip.h "Per-voxel colour"): u16 x 4 per voxel, allocated and zeroed by
+     * enableColor() (a no-op when it exists), zeroed by reset(), shifted by ObjTSDF::resize.
+     */
+    void enableColor();
+    void dropColor() { colorVol = DeviceBuffer(); }
+    bool hasColor() const { return !colorVol.empty(); }
+    uint16_t* colorPtr() const { return colorVol.empty() ? nullptr : colorVol.as<uint16_t>(); }
+    /** Host copy, (Nz*Ny*Nx) x 4 u16; empty without a colour volume. */
+    std::vector<uint16_t> getColorVol() const;
+
+    /**
      * Keep the volume twice (MI355X has the memory: 1 GB more for a 512^3 background) so that a
      * frame's integration can run out of place, concurrently with the same frame's raycast
      * (emf_hip_integrateBatchedCulledOut; EMFusion::integrateBatched).  Everything else keeps reading
@@ -157,6 +168,7 @@ protected:
     DeviceBuffer tsdfWeights;  // N^3 f32
     DeviceBuffer tsdfGrads;    // N^3 x 3 f32, only in Materialized mode
     DeviceBuffer brickFlags;   // ceil(N/8)^3 u8 uniformity flags kept by integrate(), read by raycast()
+    DeviceBuffer colorVol;     // N^3 x 4 u16 (R, G, B, Wc in 8.8 fixed point), only after enableColor()
     // double buffering (enableDoubleBuffer): the other copy, and per 32x8x8 tile "the copies differ"
     DeviceBuffer tsdfBack, weightsBack;
     DeviceBuffer dirtyMaps[2];

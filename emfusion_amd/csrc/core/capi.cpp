@@ -226,6 +226,47 @@ int emf_fusion_process_rgbd(emf_fusion_t* h, const float* depth_host, int32_t wi
     });
 }
 
+int emf_fusion_set_color(emf_fusion_t* h, int on) {
+    REQ(h);
+    return guarded([&] { h->impl->enableColor(on != 0); });
+}
+
+int emf_fusion_set_color_image(emf_fusion_t* h, const emf_image_t* rgb_dev) {
+    REQ(h);
+    REQ(rgb_dev);
+    return guarded([&] { h->impl->setColorImage(*rgb_dev); });
+}
+
+int emf_fusion_process_rgbd_color(emf_fusion_t* h, const float* depth_host, const uint8_t* rgb_host, int32_t width,
+                                  int32_t height) {
+    REQ(h);
+    REQ(depth_host);
+    REQ(rgb_host);
+    return guarded([&] {
+        if (!h->impl->colorEnabled()) throw HipError("emf_fusion_process_rgbd_color: colour is not enabled", EMF_E_ARG);
+        FrameInputs in;  // as emf_fusion_process_rgbd
+        in.cam_pose = h->impl->getCameraPose();
+        in.trackCamera = h->trackCamera;
+        in.trackObjects = h->trackObjects;
+        in.cleanUp = h->cleanUp;
+        in.newObjectMasks.swap(h->queuedMasks);
+        in.instanceMasks.swap(h->queuedInstances);
+        in.instanceScores.swap(h->queuedScores);
+        h->impl->setFrameInputs(in);
+        RGBD frame;
+        frame.size = Size(width, height);
+        frame.depth = depth_host;
+        frame.rgb = rgb_host;
+        h->impl->processFrame(frame);
+    });
+}
+
+int emf_fusion_colored_voxels(emf_fusion_t* h, uint64_t* count) {
+    REQ(h);
+    REQ(count);
+    return guarded([&] { *count = h->impl->takeColoredVoxels(); });
+}
+
 int emf_fusion_use_preproc_masks(emf_fusion_t* h, const char* path) {
     REQ(h);
     REQ(path);
@@ -239,6 +280,21 @@ int emf_fusion_get_last_masks(emf_fusion_t* h, uint8_t* rgb, size_t capacity, in
         const int n = h->impl->getLastMasks(img);
         if (instances) *instances = n;
         if (rgb && capacity >= img.size() && !img.empty()) std::memcpy(rgb, img.data(), img.size());
+    });
+}
+
+int emf_io_read_color_png(const char* path, uint8_t* out, size_t capacity, int32_t* width, int32_t* height) {
+    REQ(path);
+    return guarded([&] {
+        std::vector<uint8_t> px;
+        int w = 0, hgt = 0;
+        readPngColor(path, px, w, hgt);
+        if (width) *width = w;
+        if (height) *height = hgt;
+        if (out) {
+            if (capacity < px.size()) throw HipError("emf_io_read_color_png: buffer too small", EMF_E_ARG);
+            std::memcpy(out, px.data(), px.size());
+        }
     });
 }
 
@@ -475,6 +531,29 @@ int emf_fusion_copy_mesh(emf_fusion_t* h, float* vertices, float* normals, int32
     });
 }
 
+int emf_fusion_copy_mesh_colors(emf_fusion_t* h, uint8_t* colors) {
+    REQ(h);
+    REQ(colors);
+    return guarded([&] {
+        const emf::Mesh& m = h->mesh;
+        if (m.colors.size() != m.cloud.size())
+            throw HipError("emf_fusion_copy_mesh_colors: the mesh has no colours (emf_fusion_set_color)", EMF_E_ARG);
+        std::copy(m.colors.begin(), m.colors.end(), colors);
+    });
+}
+
+int emf_fusion_copy_meshes_colors(emf_fusion_t* h, uint8_t* colors) {
+    REQ(h);
+    REQ(colors);
+    return guarded([&] {
+        for (const emf::Mesh& m : h->meshList) {
+            if (m.colors.size() != m.cloud.size())
+                throw HipError("emf_fusion_copy_meshes_colors: the meshes have no colours (emf_fusion_set_color)", EMF_E_ARG);
+            colors = std::copy(m.colors.begin(), m.colors.end(), colors);
+        }
+    });
+}
+
 int emf_fusion_extract_meshes(emf_fusion_t* h, const int32_t* ids, int n, uint32_t* counts) {
     REQ(h);
     REQ(ids);
@@ -520,6 +599,26 @@ int emf_io_write_mesh(const char* filename, uint32_t num_vertices, const float* 
     });
 }
 
+int emf_io_write_mesh_colors(const char* filename, uint32_t num_vertices, const float* vertices, const float* normals,
+                             const uint8_t* colors, uint32_t num_triangles, const int32_t* triangles) {
+    REQ(filename);
+    if (num_vertices) {
+        REQ(vertices);
+        REQ(normals);
+        REQ(colors);
+    }
+    if (num_triangles) REQ(triangles);
+    return guarded([&] {
+        emf::Mesh m;
+        m.cloud.assign(vertices, vertices + 3 * static_cast<size_t>(num_vertices));
+        m.normals.assign(normals, normals + 3 * static_cast<size_t>(num_vertices));
+        m.colors.assign(colors, colors + 3 * static_cast<size_t>(num_vertices));
+        m.colored = true;
+        m.polygons.assign(triangles, triangles + 4 * static_cast<size_t>(num_triangles));
+        io::writeMesh(filename, m);
+    });
+}
+
 int emf_fusion_render(emf_fusion_t* h, uint8_t* rgb, uint8_t* color_map) {
     REQ(h);
     REQ(rgb);
@@ -539,6 +638,23 @@ int emf_fusion_render_view(emf_fusion_t* h, const float R[9], const float t[3], 
     return guarded([&] {
         h->impl->renderView(Affine3f(m33(R), Vec3f(t[0], t[1], t[2])), K, Size(width, height), rgb, raylengths, seg);
     });
+}
+
+int emf_fusion_render_view_shaded(emf_fusion_t* h, const float R[9], const float t[3], const float K[9], int32_t width,
+                                  int32_t height, int shading, uint8_t* rgb, float* raylengths, uint8_t* seg) {
+    REQ(h);
+    REQ(R);
+    REQ(t);
+    REQ(K);
+    REQ(rgb);
+    return guarded([&] {
+        h->impl->renderView(Affine3f(m33(R), Vec3f(t[0], t[1], t[2])), K, Size(width, height), rgb, raylengths, seg, shading);
+    });
+}
+
+int emf_fusion_set_3d_view_shading(emf_fusion_t* h, int shading) {
+    REQ(h);
+    return guarded([&] { h->impl->set3dViewShading(shading); });
 }
 
 int emf_fusion_set_3d_view(emf_fusion_t* h, const float R[9], const float t[3], const float K[9], int32_t width,
@@ -604,7 +720,7 @@ int emf_io_write_pose_file(const char* filename, int n, const int32_t* frames, c
 int emf_io_png_unfilter(const uint8_t* rows, int height, int stride, int bpp, uint8_t* out) {
     REQ(rows);
     REQ(out);
-    if (height < 0 || stride <= 0 || (bpp != 1 && bpp != 2)) return EMF_E_ARG;
+    if (height < 0 || stride <= 0 || bpp < 1 || bpp > 4) return EMF_E_ARG;
     // PNG specification 9.2: each scan line is preceded by its filter type; Sub / Average / Paeth
     // predict from the reconstructed byte bpp positions to the left (a), above (b), above-left (c)
     const uint8_t* prev = nullptr;
@@ -830,6 +946,12 @@ int emf_fusion_get_volume(emf_fusion_t* h, int which, int obj_id, void** dev_ptr
             res[1] = (r[1] + 3) / 4;
             res[2] = (r[2] + 3) / 4;
             return EMF_OK;
+        case EMF_VOL_COLOR:
+            if (vol->colorPtr()) {
+                *dev_ptr = vol->colorPtr();
+                return EMF_OK;
+            }
+            break;
         case EMF_VOL_FGPROBS:
             if (obj) {
                 *dev_ptr = const_cast<float*>(obj->fgProbsPtr());

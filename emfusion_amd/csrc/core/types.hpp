@@ -109,6 +109,8 @@ struct Mesh {
     std::vector<float> cloud;       // 3 per vertex, volume frame
     std::vector<float> normals;     // 3 per vertex (interpolated gradients, not normalised)
     std::vector<int32_t> polygons;  // 4 per triangle
+    std::vector<uint8_t> colors;    // 3 per vertex (RGB) from the volume's colour volume; empty without one
+    bool colored = false;           // the volume has a colour volume (also when the mesh is empty): the PLY carries colours
     size_t vertices() const { return cloud.size() / 3; }
     size_t triangles() const { return polygons.size() / 4; }
 };

@@ -15,12 +15,23 @@ struct MeshSource {
     float voxelSize;
 };
 
+// vertexInterp's decision (TSDF.cu:909-920; the comparisons are against the double literal 0.00001): 1 = the first
+// corner's value outright, 2 = the second's (its three early returns), 0 = a1 + mu * (a2 - a1).  Shared by everything
+// that is interpolated along an edge: positions and normals (vertex_interp), vertex colours.
+__device__ __forceinline__ int vertex_interp_mu(float v1, float v2, float& mu) {
+    mu = 0.f;
+    if (static_cast<double>(fabsf(v1)) < 0.00001) return 1;
+    if (static_cast<double>(fabsf(v2)) < 0.00001) return 2;
+    if (static_cast<double>(fabsf(v1 - v2)) < 0.00001) return 1;
+    mu = -v1 / (v2 - v1);
+    return 0;
+}
+
 __device__ __forceinline__ V3 vertex_interp(const V3& p1, const V3& p2, float v1, float v2) {
-    // TSDF.cu:909-920; the comparisons are against the double literal 0.00001
-    if (static_cast<double>(fabsf(v1)) < 0.00001) return p1;
-    if (static_cast<double>(fabsf(v2)) < 0.00001) return p2;
-    if (static_cast<double>(fabsf(v1 - v2)) < 0.00001) return p1;
-    const float mu = -v1 / (v2 - v1);
+    float mu;
+    const int take = vertex_interp_mu(v1, v2, mu);
+    if (take == 1) return p1;
+    if (take == 2) return p2;
     const V3 d = v3(p2.x - p1.x, p2.y - p1.y, p2.z - p1.z);  // p1 + mu * (p2 - p1)
     return p1 + d * mu;
 }

@@ -443,43 +443,67 @@ __device__ __forceinline__ V3 corner_gradient(const MeshOut& a, size_t idx, int 
 __device__ __forceinline__ void emit_cube(const MeshOut& a, const Cube& q, unsigned edges, unsigned ntris,
                                           unsigned vertBase, unsigned triBase);
 
+// One entry of the list of surface chunks as the lanes of a workgroup see it: the model, its volume, the lane's cube
+// and where the cube's vertices and triangles go in the model's slice.  The emit kernel and the colour kernel both
+// walk the list through this, so a vertex has the same slot in both.  All lanes of the workgroup call it together.
+struct ChunkSlot {
+    unsigned m;          // model
+    MeshSource src;
+    const float* grads;
+    Cube q;              // q.cls == 0: nothing to write for this lane
+    unsigned edges, ntris;
+    unsigned vertBase, triBase;  // model-local first vertex / triangle of the lane's cube
+};
+
+template <bool kTable>
+__device__ __forceinline__ ChunkSlot chunk_slot(const MeshArgs& a, unsigned i, uint2* lds) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    ChunkSlot s;
+    const unsigned gg = a.list[i];
+    s.m = kTable ? model_of(a.chunkBase, a.n, gg) : 0u;
+    s.src = source_of<kTable>(a, s.m, s.grads);
+    const I3 n = s.src.n;
+    const size_t nvox = static_cast<size_t>(n.x) * n.y * n.z;
+    const unsigned chunks = static_cast<unsigned>(chunks_for(nvox));
+    const unsigned* tot = a.chunkTot + a.chunkBase[s.m];
+    const unsigned g = gg - a.chunkBase[s.m];  // the model's own chunk index
+    const unsigned first = g & ~(chunks - 1u);
+    uint2 base = a.blockSums[a.blockBase[s.m] + g / chunks];
+    for (unsigned c = first; c < g; ++c) {
+        const unsigned t = tot[c];
+        base.x += t & 0xffffu;
+        base.y += t >> 16;
+    }
+    const size_t p = static_cast<size_t>(g) * kMcChunk + static_cast<size_t>(wave) * kMcWaveCubes + lane;
+    s.q = classify(s.src, origin_of(n, p), lane < kMcWaveCubes && p < nvox);
+    s.edges = s.q.cls ? active_edges(s.q.cls) : 0u;
+    uint2 v = make_uint2(0u, 0u);
+    if (s.q.cls) v = make_uint2(__popc(s.edges), triangles_of(s.q.cls));
+    uint2 total;
+    const uint2 mine = block_scan(v, total, lds);
+    s.ntris = v.y;
+    s.vertBase = base.x + mine.x;
+    s.triBase = base.y + mine.y;
+    return s;
+}
+
 // 6 waves per SIMD like the one-volume kernel before the table (74 VGPRs); uncapped the slice offsets take the
 // argument form to 81 = 5 waves
 template <bool kTable>
 __global__ __launch_bounds__(kMcBlock) __attribute__((amdgpu_waves_per_eu(6))) void k_mesh_emit(const MeshArgs a) {
     __shared__ uint2 lds[8];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned todo = *a.listCount;
     for (unsigned i = blockIdx.x; i < todo; i += gridDim.x) {
-        const unsigned gg = a.list[i];
-        const unsigned m = kTable ? model_of(a.chunkBase, a.n, gg) : 0u;
+        const ChunkSlot s = chunk_slot<kTable>(a, i, lds);
         MeshOut out;
-        out.src = source_of<kTable>(a, m, out.grads);
-        const unsigned long long vb = a.bases[2 * m], tb = a.bases[2 * m + 1];
+        out.src = s.src;
+        out.grads = s.grads;
+        const unsigned long long vb = a.bases[2 * s.m], tb = a.bases[2 * s.m + 1];
         out.vertices = a.vertices + 3 * vb;
         out.normals = a.normals + 3 * vb;
         out.triangles = a.triangles + 4 * tb;
-        const I3 n = out.src.n;
-        const size_t nvox = static_cast<size_t>(n.x) * n.y * n.z;
-        const unsigned chunks = static_cast<unsigned>(chunks_for(nvox));
-        const unsigned* tot = a.chunkTot + a.chunkBase[m];
-        const unsigned g = gg - a.chunkBase[m];  // the model's own chunk index
-        const unsigned first = g & ~(chunks - 1u);
-        uint2 base = a.blockSums[a.blockBase[m] + g / chunks];
-        for (unsigned c = first; c < g; ++c) {
-            const unsigned t = tot[c];
-            base.x += t & 0xffffu;
-            base.y += t >> 16;
-        }
-        const size_t p = static_cast<size_t>(g) * kMcChunk + static_cast<size_t>(wave) * kMcWaveCubes + lane;
-        const Cube q = classify(out.src, origin_of(n, p), lane < kMcWaveCubes && p < nvox);
-        const unsigned edges = q.cls ? active_edges(q.cls) : 0u;
-        uint2 v = make_uint2(0u, 0u);
-        if (q.cls) v = make_uint2(__popc(edges), triangles_of(q.cls));
-        uint2 total;
-        const uint2 mine = block_scan(v, total, lds);
         // (3, i0, i1, i2) per triangle
-        if (q.cls) emit_cube(out, q, edges, v.y, base.x + mine.x, 4u * (base.y + mine.y));
+        if (s.q.cls) emit_cube(out, s.q, s.edges, s.ntris, s.vertBase, 4u * s.triBase);
     }
 }
 
@@ -531,6 +555,64 @@ __device__ __forceinline__ void emit_cube(const MeshOut& a, const Cube& q, unsig
             for (int i = 0; i < 12; ++i) o = e == i ? offsets[i] : o;
             to[1 + j] = static_cast<int32_t>(vertBase) + o;  // model-local: the slice is the volume's own mesh
         }
+    }
+}
+
+// ---- vertex colours (new behaviour: include/emf_hip.h "Per-voxel colour") ------------------------------------
+// The emit kernel's walk over the list of surface chunks once more (chunk_slot: the same function, hence the same
+// vertex slots), writing u8 x 3 per vertex from a colour volume instead of position and normal.  A pass of
+// its own so that the emit kernels stay what they are; it costs the surface chunks' corner gathers a second time.
+struct MeshColorArgs {
+    const uint16_t* one;           // colour volume of a level-1 call
+    uint16_t* const* table;        // device array parallel to the model table (level 3); NULL entry: black
+    uint8_t* colors;               // 3 per vertex, concatenated like the vertices
+};
+
+__device__ __forceinline__ void color_cube(const MeshSource& src, const ushort4* vol, const Cube& q, unsigned edges,
+                                           unsigned vertBase, uint8_t* colors) {
+#pragma clang fp contract(off)
+    const I3 n = src.n;
+    const size_t sy = static_cast<size_t>(n.x), sz = sy * n.y;
+    unsigned k = 0;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) {
+        if (!((edges >> e) & 1u)) continue;
+        float val[2];
+        ushort4 c[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            int dx, dy, dz;
+            cube_corner(emf_mc_edge_corner[e][s], dx, dy, dz);
+            const size_t idx = q.base + dx + dy * sy + dz * sz;
+            val[s] = src.tsdf[idx];
+            c[s] = vol ? vol[idx] : make_ushort4(0, 0, 0, 0);
+        }
+        // an uncoloured endpoint (Wc == 0) contributes the other endpoint's colour; both: black
+        if (c[0].w == 0) c[0] = c[1];
+        if (c[1].w == 0) c[1] = c[0];
+        const bool none = c[0].w == 0;
+        float mu;
+        const int take = vertex_interp_mu(val[0], val[1], mu);
+        const unsigned short a[3] = {c[0].x, c[0].y, c[0].z}, b[3] = {c[1].x, c[1].y, c[1].z};
+        uint8_t* o = colors + 3 * static_cast<size_t>(vertBase + k);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float c1 = static_cast<float>(a[j]) / 256.f, c2 = static_cast<float>(b[j]) / 256.f;
+            const float v = take == 1 ? c1 : (take == 2 ? c2 : c1 + mu * (c2 - c1));
+            o[j] = none ? 0 : static_cast<uint8_t>(fminf(fmaxf(rintf(v), 0.f), 255.f));
+        }
+        ++k;
+    }
+}
+
+template <bool kTable>
+__global__ __launch_bounds__(kMcBlock) void k_mesh_colors(const MeshArgs a, const MeshColorArgs ca) {
+    __shared__ uint2 lds[8];
+    const unsigned todo = *a.listCount;
+    for (unsigned i = blockIdx.x; i < todo; i += gridDim.x) {
+        const ChunkSlot s = chunk_slot<kTable>(a, i, lds);
+        const ushort4* vol = reinterpret_cast<const ushort4*>(kTable ? ca.table[s.m] : ca.one);
+        if (s.q.cls) color_cube(s.src, vol, s.q, s.edges, s.vertBase, ca.colors + 3 * a.bases[2 * s.m]);
     }
 }
 
@@ -696,6 +778,32 @@ int emf_hip_meshEmitBatched(const emf_model_t* models_dev, const int32_t* res_ho
     a.normals = normals;
     a.triangles = triangles;
     return launch_emit(a, stream, "meshEmitBatched");
+}
+
+int emf_hip_meshColors(const float* tsdf, const float* weights, const uint8_t* fgVolMask, const uint16_t* color,
+                       const int32_t res[3], const void* scratch_dev, uint8_t* colors, emf_stream_t stream) {
+    MeshArgs a;
+    EMF_TRY(single(a, tsdf, weights, fgVolMask, nullptr, res, 1.f, const_cast<void*>(scratch_dev)));
+    EMF_REQUIRE_PTR(color);
+    EMF_REQUIRE_PTR(colors);
+    const MeshColorArgs ca{color, nullptr, colors};
+    const unsigned nchunks = a.chunkBase[a.n];
+    hipLaunchKernelGGL(k_mesh_colors<false>, dim3(nchunks < 4096u ? nchunks : 4096u), dim3(kMcBlock), 0,
+                       as_stream(stream), a, ca);
+    return launch_status("meshColors");
+}
+
+int emf_hip_meshColorsBatched(const emf_model_t* models_dev, uint16_t* const* colors_dev, const int32_t* res_host, int n,
+                              const void* scratch_dev, uint8_t* colors, emf_stream_t stream) {
+    MeshArgs a;
+    EMF_TRY(table(a, models_dev, res_host, n, const_cast<void*>(scratch_dev)));
+    EMF_REQUIRE_PTR(colors_dev);
+    EMF_REQUIRE_PTR(colors);
+    const MeshColorArgs ca{nullptr, colors_dev, colors};
+    const unsigned nchunks = a.chunkBase[a.n];
+    hipLaunchKernelGGL(k_mesh_colors<true>, dim3(nchunks < 4096u ? nchunks : 4096u), dim3(kMcBlock), 0,
+                       as_stream(stream), a, ca);
+    return launch_status("meshColorsBatched");
 }
 
 }  // extern "C"

@@ -413,22 +413,17 @@ __device__ __forceinline__ uint8_t to_u8(float v) {
     return v >= 0.f ? static_cast<uint8_t>(v < 255.f ? static_cast<int>(v) : 255) : uint8_t{0};
 }
 
-__global__ __launch_bounds__(256) void k_render_phong(const PhongArgs a) {
-    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
-    if (x >= a.w || y >= a.h) return;
-    const float* pp = a.points.row(y) + 3 * x;
-    const float* np = a.normals.row(y) + 3 * x;
-    const V3 p = v3(pp[0], pp[1], pp[2]), n = v3(np[0], np[1], np[2]);
-    uint8_t* out = a.image.row(y) + 3 * x;
+// One pixel of kernel_renderPhong: vertex p, normal n, diffuse colour c (u8 x 3) -> out (u8 x 3).  Shared by the
+// label-coloured launch and the launch that shades from a per-pixel colour image.
+__device__ __forceinline__ void shade_pixel(const V3& p, const V3& n, const uint8_t* c, const V3& light, uint8_t* out) {
     if (p.x == 0.f && p.y == 0.f && p.z == 0.f) {
         out[0] = out[1] = out[2] = 0;
         return;
     }
-    const uint8_t* c = a.colors + 3 * a.seg.row(y)[x];
     const float ka = 0.3f, kd = 0.5f, ks = 0.2f;
     const V3 Rd = v3(static_cast<float>(c[0]) / 255.f, static_cast<float>(c[1]) / 255.f,
                      static_cast<float>(c[2]) / 255.f);
-    V3 l = v3(a.light.x - p.x, a.light.y - p.y, a.light.z - p.z);
+    V3 l = v3(light.x - p.x, light.y - p.y, light.z - p.z);
     l = l / norm(l);
     const V3 v = v3(-p.x, -p.y, -p.z) / norm(p);
     const V3 two = n * (2.f * dot(l, n));
@@ -441,6 +436,33 @@ __global__ __launch_bounds__(256) void k_render_phong(const PhongArgs a) {
     out[0] = to_u8(I.x * 255.f);
     out[1] = to_u8(I.y * 255.f);
     out[2] = to_u8(I.z * 255.f);
+}
+
+__global__ __launch_bounds__(256) void k_render_phong(const PhongArgs a) {
+    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
+    if (x >= a.w || y >= a.h) return;
+    const float* pp = a.points.row(y) + 3 * x;
+    const float* np = a.normals.row(y) + 3 * x;
+    shade_pixel(v3(pp[0], pp[1], pp[2]), v3(np[0], np[1], np[2]), a.colors + 3 * a.seg.row(y)[x], a.light,
+                a.image.row(y) + 3 * x);
+}
+
+// the same shading with the diffuse colour of every pixel taken from a u8 x 3 image (emf_hip_sampleColor's)
+struct PhongColorArgs {
+    Img<const float> points, normals;
+    Img<const uint8_t> colors;  // u8 x 3
+    Img<uint8_t> image;         // u8 x 3
+    int w, h;
+    V3 light;
+};
+
+__global__ __launch_bounds__(256) void k_render_phong_color(const PhongColorArgs a) {
+    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
+    if (x >= a.w || y >= a.h) return;
+    const float* pp = a.points.row(y) + 3 * x;
+    const float* np = a.normals.row(y) + 3 * x;
+    shade_pixel(v3(pp[0], pp[1], pp[2]), v3(np[0], np[1], np[2]), a.colors.row(y) + 3 * x, a.light,
+                a.image.row(y) + 3 * x);
 }
 
 }  // namespace
@@ -829,6 +851,30 @@ int emf_hip_renderPhong(const emf_image_t* vertices, const emf_image_t* normals,
                        dim3(static_cast<unsigned>(ceil_div(a.w, 32)), static_cast<unsigned>(ceil_div(a.h, 8))),
                        dim3(256), 0, as_stream(stream), a);
     return launch_status("renderPhong");
+}
+
+int emf_hip_renderPhongColor(const emf_image_t* vertices, const emf_image_t* normals, const emf_image_t* colors,
+                             const float lightPos[3], const emf_image_t* image, emf_stream_t stream) {
+    EMF_TRY(check_image(vertices, 12, "renderPhongColor: vertices"));
+    EMF_TRY(check_image(normals, 12, "renderPhongColor: normals"));
+    EMF_TRY(check_image(colors, 3, "renderPhongColor: colors"));
+    EMF_TRY(check_image(image, 3, "renderPhongColor: image"));
+    EMF_TRY(check_same_size(vertices, normals, "vertices", "normals"));
+    EMF_TRY(check_same_size(vertices, colors, "vertices", "colors"));
+    EMF_TRY(check_same_size(vertices, image, "vertices", "image"));
+    EMF_REQUIRE_PTR(lightPos);
+    PhongColorArgs a;
+    a.points = img<const float>(vertices);
+    a.normals = img<const float>(normals);
+    a.colors = img<const uint8_t>(colors);
+    a.image = img<uint8_t>(image);
+    a.w = vertices->width;
+    a.h = vertices->height;
+    a.light = v3_from(lightPos);
+    hipLaunchKernelGGL(k_render_phong_color,
+                       dim3(static_cast<unsigned>(ceil_div(a.w, 32)), static_cast<unsigned>(ceil_div(a.h, 8))),
+                       dim3(256), 0, as_stream(stream), a);
+    return launch_status("renderPhongColor");
 }
 
 }  // extern "C"

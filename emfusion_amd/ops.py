@@ -426,6 +426,29 @@ def integrate_batched(models_dev, poses_oc, res_list, visible, depth, K, stats=N
                                       _stream(stream)))
 
 
+def integrate_color_batched(models_dev, colors, poses_oc, res_list, visible, depth, rgb, K, stats=None, stream=None,
+                            inv_lambda=None):
+    """emf_hip_integrateColorBatched: colors = one (Nz, Ny, Nx, 4) u16 device array (or None: skipped) per model;
+    rgb an (H, W, 3) u8 device image.  The colour volumes are updated in place."""
+    res = (C.c_int32 * (3 * len(poses_oc)))(*[int(v) for r in res_list for v in r])
+    ptrs = DeviceArray.from_numpy(np.array([0 if c is None else c.ptr for c in colors], np.uint64))
+    check("emf_hip_integrateColorBatched",
+          _L.emf_hip_integrateColorBatched(_ptr(models_dev), _ptr(ptrs), _poses(poses_oc), res, len(poses_oc),
+                                           _ptr(visible), C.byref(image_view(depth)), _opt_view(inv_lambda),
+                                           C.byref(image_view(rgb)), _f(K, 9), _ptr(stats), _stream(stream)))
+    from .devmem import synchronize
+    synchronize()  # `ptrs` is released on return
+
+
+def copy_color_values(src: DeviceArray, dst: DeviceArray, offset, stream=None):
+    """dst(v) = src(v + offset) inside src, else 0, for colour volumes (Nz, Ny, Nx, 4) u16."""
+    sres = (C.c_int32 * 3)(src.shape[2], src.shape[1], src.shape[0])
+    dres = (C.c_int32 * 3)(dst.shape[2], dst.shape[1], dst.shape[0])
+    check("emf_hip_copyColorValues",
+          _L.emf_hip_copyColorValues(_ptr(src), _ptr(dst), (C.c_int32 * 3)(*[int(v) for v in offset]), sres, dres,
+                                     _stream(stream)))
+
+
 def integrate_batched_culled(models_dev, poses_oc, res_list, visible, depth, K, launch_boxes=0, survivors=None,
                              stats=None, stream=None, inv_lambda=None, scratch=None):
     """emf_hip_integrateBatchedCulled; returns the scratch buffer (reusable)."""
@@ -693,9 +716,43 @@ def render_view(models_dev, poses_vo, ids, width, height, K, rgb, raylengths=Non
     return rgb
 
 
-def extract_mesh(tsdf, weights, voxel_size, fg_mask=None, grads=None, stream=None):
+def sample_color(models_dev, colors, poses_vo, ids, vertices, segmentation, color_map, out, stream=None):
+    """emf_hip_sampleColor: per pixel of a view (vertices (H, W, 3) f32 in the viewer frame, segmentation (H, W) u8, as
+    render_view writes them) the colour of the nearest voxel of the model the label names, label colour where nobody
+    coloured it.  colors: one colour volume (or None) per table slot, or None for label colours only; poses_vo as
+    render_view; out (H, W, 3) u8."""
+    if not isinstance(poses_vo, DeviceArray):
+        poses_vo = upload_poses(poses_vo)
+    n = poses_vo.nbytes // C.sizeof(_lib.EmfPose)
+    ids_arr = (C.c_int32 * max(n - 1, 1))(*[int(i) for i in ids]) if n > 1 else None
+    ptrs = None
+    if colors is not None:
+        assert len(colors) == n
+        ptrs = DeviceArray.from_numpy(np.array([0 if c is None else c.ptr for c in colors], np.uint64))
+    cm = np.ascontiguousarray(color_map, np.uint8)
+    assert cm.size == 768
+    check("emf_hip_sampleColor",
+          _L.emf_hip_sampleColor(_ptr(models_dev), _ptr(ptrs), _ptr(poses_vo), ids_arr, n, C.byref(image_view(vertices)),
+                                 C.byref(image_view(segmentation)), cm.ctypes.data, C.byref(image_view(out)),
+                                 _stream(stream)))
+    from .devmem import synchronize
+    synchronize()  # `ptrs` is released on return
+    return out
+
+
+def render_phong_color(vertices, normals, colors, image, light=(0.0, 0.0, 0.0), stream=None):
+    """emf_hip_renderPhongColor: render_phong with each pixel's diffuse colour read from `colors` (H, W, 3) u8."""
+    check("emf_hip_renderPhongColor",
+          _L.emf_hip_renderPhongColor(C.byref(image_view(vertices)), C.byref(image_view(normals)),
+                                      C.byref(image_view(colors)), _f(light, 3), C.byref(image_view(image)),
+                                      _stream(stream)))
+    return image
+
+
+def extract_mesh(tsdf, weights, voxel_size, fg_mask=None, grads=None, stream=None, color=None):
     """TSDF::getMesh / ObjTSDF::getMesh: (vertices (n, 3) f32, normals (n, 3) f32, triangles (m, 4) i32)
-    as numpy arrays; two launches to count, one read-back, one launch to emit."""
+    as numpy arrays; two launches to count, one read-back, one launch to emit.  color: the volume's colour volume
+    ((Nz, Ny, Nx, 4) u16): a fourth array, the vertex colours (n, 3) u8 (emf_hip_meshColors)."""
     res = _res(tsdf)
     scratch = DeviceArray.zeros((max(int(_L.emf_hip_meshScratchBytes(res)) // 4, 2),), np.uint32)
     counts = DeviceArray.zeros((2,), np.uint32)
@@ -710,6 +767,13 @@ def extract_mesh(tsdf, weights, voxel_size, fg_mask=None, grads=None, stream=Non
         check("emf_hip_meshEmit",
               _L.emf_hip_meshEmit(_ptr(tsdf), _ptr(grads), _ptr(weights), _ptr(fg_mask), res, voxel_size,
                                   _ptr(scratch), _ptr(verts), _ptr(norms), _ptr(tris), _stream(stream)))
+    if color is not None:
+        cols = DeviceArray.zeros((max(nv, 1), 3), np.uint8)
+        if nv:
+            check("emf_hip_meshColors",
+                  _L.emf_hip_meshColors(_ptr(tsdf), _ptr(weights), _ptr(fg_mask), _ptr(color), res, _ptr(scratch),
+                                        _ptr(cols), _stream(stream)))
+        return verts.numpy()[:nv], norms.numpy()[:nv], tris.numpy()[:nt], cols.numpy()[:nv]
     return verts.numpy()[:nv], norms.numpy()[:nv], tris.numpy()[:nt]
 
 
@@ -755,10 +819,20 @@ def extract_meshes(volumes, stream=None):
               _L.emf_hip_meshEmitBatched(_ptr(table), res, n, _ptr(scratch), _ptr(verts), _ptr(norms), _ptr(tris),
                                          _stream(stream)))
     hv, hn, ht = verts.numpy(), norms.numpy(), tris.numpy()
+    hc = None
+    if any(v.get("color") is not None for v in volumes):  # emf_hip_meshColorsBatched: 4-tuples, colours last
+        ptrs = DeviceArray.from_numpy(np.array([0 if v.get("color") is None else v["color"].ptr for v in volumes],
+                                               np.uint64))
+        cols = DeviceArray.zeros((max(nv, 1), 3), np.uint8)
+        if nv:
+            check("emf_hip_meshColorsBatched",
+                  _L.emf_hip_meshColorsBatched(_ptr(table), _ptr(ptrs), res, n, _ptr(scratch), _ptr(cols),
+                                               _stream(stream)))
+        hc = cols.numpy()
     out = []
     for k in range(n):
         v0, t0, cv, ct = int(bs[k, 0]), int(bs[k, 1]), int(cnt[k, 0]), int(cnt[k, 1])
-        out.append((hv[v0:v0 + cv], hn[v0:v0 + cv], ht[t0:t0 + ct]))
+        out.append((hv[v0:v0 + cv], hn[v0:v0 + cv], ht[t0:t0 + ct]) + ((hc[v0:v0 + cv],) if hc is not None else ()))
     return out
 
 

@@ -55,7 +55,8 @@ IMG = dict(points=0, bg_assoc=1, obj_assoc=2, assoc_norm=3, raylengths=4, vertic
 _IMG_DTYPE = {0: ("float32", 3), 1: ("float32", 1), 2: ("float32", 1), 3: ("float32", 1),
               4: ("float32", 1), 5: ("float32", 3), 6: ("float32", 3), 7: ("uint8", 1),
               8: ("float32", 1), 9: ("float32", 1)}
-VOL = dict(tsdf=0, weights=1, fgprobs=2, fgmask=3, bricks=4)
+SHADING = dict(label=0, color=1)
+VOL = dict(tsdf=0, weights=1, fgprobs=2, fgmask=3, bricks=4, color=5)
 
 _lib = None
 
@@ -96,9 +97,14 @@ def load() -> C.CDLL:
         "emf_fusion_trim_pool": [C.POINTER(C.c_uint64)],
         "emf_fusion_process_rgbd": [vp, fp, C.c_int32, C.c_int32],
         "emf_fusion_use_preproc_masks": [vp, C.c_char_p],
+        "emf_fusion_set_color": [vp, C.c_int],
+        "emf_fusion_set_color_image": [vp, img],
+        "emf_fusion_process_rgbd_color": [vp, fp, C.c_void_p, C.c_int32, C.c_int32],
+        "emf_fusion_colored_voxels": [vp, C.POINTER(C.c_uint64)],
         "emf_fusion_get_last_masks": [vp, C.c_void_p, C.c_size_t, ip],
         "emf_io_read_depth_png": [C.c_char_p, C.c_float, fp, C.c_size_t, ip, ip],
         "emf_io_read_exr": [C.c_char_p, C.c_char_p, fp, C.c_size_t, ip, ip],
+        "emf_io_read_color_png": [C.c_char_p, C.c_void_p, C.c_size_t, ip, ip],
         "emf_io_load_config": [C.c_char_p, C.c_char_p, C.c_void_p, C.c_char_p, C.c_size_t],
         "emf_io_image_reader": [C.c_char_p, C.c_char_p, C.c_char_p, ip, ip],
         "emf_io_tum_associations": [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_double), ip],
@@ -130,11 +136,16 @@ def load() -> C.CDLL:
         "emf_fusion_render_view": [vp, fp, fp, fp, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
         "emf_fusion_set_3d_view": [vp, fp, fp, fp, C.c_int32, C.c_int32],
         "emf_fusion_clear_3d_view": [vp],
+        "emf_fusion_render_view_shaded": [vp, fp, fp, fp, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+        "emf_fusion_set_3d_view_shading": [vp, C.c_int],
         "emf_fusion_extract_mesh": [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
         "emf_fusion_copy_mesh": [vp, C.c_void_p, C.c_void_p, C.c_void_p],
         "emf_fusion_extract_meshes": [vp, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_uint32)],
         "emf_fusion_copy_meshes": [vp, C.c_void_p, C.c_void_p, C.c_void_p],
+        "emf_fusion_copy_mesh_colors": [vp, C.c_void_p],
+        "emf_fusion_copy_meshes_colors": [vp, C.c_void_p],
         "emf_io_write_mesh": [C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
+        "emf_io_write_mesh_colors": [C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
         "emf_fusion_queue_new_object_masks": [vp, C.c_int, img],
         "emf_fusion_last_created": [vp, ip, C.c_int, ip],
         "emf_fusion_queue_instance_masks": [vp, C.c_int, img],
@@ -508,11 +519,36 @@ class Fusion:
                                                _farr(cam_t, 3), n, ids, Rs, ts, m, mids, mviews,
                                                int(run_masks)))
 
-    def process_rgbd(self, depth: np.ndarray):
-        """EMFusion::processFrame(const RGBD&): a host depth image in metres (uploaded, filtered, fused)."""
+    def process_rgbd(self, depth: np.ndarray, rgb: Optional[np.ndarray] = None):
+        """EMFusion::processFrame(const RGBD&): a host depth image in metres (uploaded, filtered, fused).  rgb: the
+        frame's (H, W, 3) u8 colour image, fused into the colour volumes (needs enable_color())."""
         d = np.ascontiguousarray(depth, np.float32)
-        _check("emf_fusion_process_rgbd",
-               load().emf_fusion_process_rgbd(self._h, d.ctypes.data_as(C.POINTER(C.c_float)), d.shape[1], d.shape[0]))
+        if rgb is None:
+            _check("emf_fusion_process_rgbd",
+                   load().emf_fusion_process_rgbd(self._h, d.ctypes.data_as(C.POINTER(C.c_float)), d.shape[1], d.shape[0]))
+            return
+        c = np.ascontiguousarray(rgb, np.uint8)
+        if c.shape != d.shape + (3,):
+            raise ValueError(f"process_rgbd: rgb is {c.shape}, expected {d.shape + (3,)}")
+        _check("emf_fusion_process_rgbd_color",
+               load().emf_fusion_process_rgbd_color(self._h, d.ctypes.data_as(C.POINTER(C.c_float)), c.ctypes.data,
+                                                    d.shape[1], d.shape[0]))
+
+    def enable_color(self, on=True):
+        """Per-voxel colour: every model keeps a colour volume (volume("color", id): (Nz, Ny, Nx, 4) u16 = R, G, B and
+        the colour weight in 8.8 fixed point) that frames with a colour image fuse into.  Before the first frame or
+        after reset() only; refused on the sharded and per-volume paths."""
+        _check("emf_fusion_set_color", load().emf_fusion_set_color(self._h, int(on)))
+
+    def set_color_image(self, rgb_view: EmfImage):
+        """The u8 x 3 device image (frame size) that goes with the next frame, and with that one only."""
+        _check("emf_fusion_set_color_image", load().emf_fusion_set_color_image(self._h, C.byref(rgb_view)))
+
+    def colored_voxels(self) -> int:
+        """Voxels the colour pass has updated since the last call (synchronises)."""
+        n = C.c_uint64(0)
+        _check("emf_fusion_colored_voxels", load().emf_fusion_colored_voxels(self._h, C.byref(n)))
+        return int(n.value)
 
     def use_preproc_masks(self, path):
         """EMFusion::usePreprocMasks: <path>/Mask%04d.plk on every mask frame of process_rgbd."""
@@ -614,18 +650,29 @@ class Fusion:
         w, h = (self.params.width, self.params.height) if size is None else (int(size[0]), int(size[1]))
         return _farr(R, 9), _farr(t, 3), _farr(K, 9), w, h
 
-    def render_view(self, R, t, K=None, size=None):
+    def render_view(self, R, t, K=None, size=None, shading="label"):
         """EMFusion::renderView: the map seen from a free viewpoint -- viewer -> world (R, t) (OpenCV camera, see
-        look_at), intrinsics K (default: the frame's), size (width, height) (default: the frame's).  Returns
-        (rgb (H, W, 3) u8, raylengths (H, W) f32, segmentation (H, W) u8)."""
+        look_at), intrinsics K (default: the frame's), size (width, height) (default: the frame's).  shading: "label"
+        (every model in its label colour) or "color" (the fused colour of the voxel under each pixel, label colour
+        where nobody coloured it; needs enable_color()).  Returns (rgb (H, W, 3) u8, raylengths (H, W) f32,
+        segmentation (H, W) u8)."""
         Rc, tc, Kc, w, h = self._view_args(R, t, K, size)
         rgb = np.empty((h, w, 3), np.uint8)
         ray = np.empty((h, w), np.float32)
         seg = np.empty((h, w), np.uint8)
-        _check("emf_fusion_render_view",
-               load().emf_fusion_render_view(self._h, Rc, tc, Kc, w, h, rgb.ctypes.data, ray.ctypes.data,
-                                             seg.ctypes.data))
+        if shading == "label":
+            _check("emf_fusion_render_view",
+                   load().emf_fusion_render_view(self._h, Rc, tc, Kc, w, h, rgb.ctypes.data, ray.ctypes.data,
+                                                 seg.ctypes.data))
+        else:
+            _check("emf_fusion_render_view_shaded",
+                   load().emf_fusion_render_view_shaded(self._h, Rc, tc, Kc, w, h, SHADING[shading], rgb.ctypes.data,
+                                                        ray.ctypes.data, seg.ctypes.data))
         return rgb, ray, seg
+
+    def set_3d_view_shading(self, shading="label"):
+        """The shading ("label" / "color", see render_view) of the view of set_3d_view."""
+        _check("emf_fusion_set_3d_view_shading", load().emf_fusion_set_3d_view_shading(self._h, SHADING[shading]))
 
     def set_3d_view(self, R=None, t=None, K=None, size=None):
         """EMFusion::set3dView (the reference's --3d-vis): render() also renders this view, and with setup_output
@@ -638,8 +685,9 @@ class Fusion:
     def clear_3d_view(self):
         _check("emf_fusion_clear_3d_view", load().emf_fusion_clear_3d_view(self._h))
 
-    def mesh(self, obj_id: int = 0):
-        """TSDF::getMesh / ObjTSDF::getMesh: (vertices (n, 3), normals (n, 3), triangles (m, 4))."""
+    def mesh(self, obj_id: int = 0, colors=False):
+        """TSDF::getMesh / ObjTSDF::getMesh: (vertices (n, 3), normals (n, 3), triangles (m, 4)); colors=True: a fourth
+        array, the vertex colours (n, 3) u8 of the same extraction (needs enable_color())."""
         nv, nt = C.c_uint32(), C.c_uint32()
         _check("emf_fusion_extract_mesh",
                load().emf_fusion_extract_mesh(self._h, int(obj_id), C.byref(nv), C.byref(nt)))
@@ -648,12 +696,25 @@ class Fusion:
         t = np.empty((nt.value, 4), np.int32)
         _check("emf_fusion_copy_mesh",
                load().emf_fusion_copy_mesh(self._h, v.ctypes.data, n.ctypes.data, t.ctypes.data))
+        if colors:
+            c = np.empty((nv.value, 3), np.uint8)
+            _check("emf_fusion_copy_mesh_colors", load().emf_fusion_copy_mesh_colors(self._h, c.ctypes.data))
+            return v, n, t, c
         return v, n, t
 
-    def meshes(self, ids=None):
+    def mesh_colors(self, obj_id: int = 0):
+        """Vertex colours (n, 3) u8 RGB of model obj_id's mesh, in mesh(obj_id)'s vertex order (needs enable_color())."""
+        nv, nt = C.c_uint32(), C.c_uint32()
+        _check("emf_fusion_extract_mesh",
+               load().emf_fusion_extract_mesh(self._h, int(obj_id), C.byref(nv), C.byref(nt)))
+        c = np.empty((nv.value, 3), np.uint8)
+        _check("emf_fusion_copy_mesh_colors", load().emf_fusion_copy_mesh_colors(self._h, c.ctypes.data))
+        return c
+
+    def meshes(self, ids=None, colors=False):
         """EMFusion::extractMeshes: {id: (vertices (n, 3), normals (n, 3), triangles (m, 4))} of the listed models
         (0 = background; None: the background and every live object) in one pass over the model table -- the same
-        arrays as mesh(id) for each."""
+        arrays as mesh(id) for each.  colors=True: 4-tuples, with the vertex colours (n, 3) u8 last (enable_color())."""
         ids = [0] + self.object_ids() if ids is None else [int(i) for i in ids]
         if not ids:
             return {}
@@ -669,10 +730,14 @@ class Fusion:
         t = np.empty((nt, 4), np.int32)
         _check("emf_fusion_copy_meshes",
                load().emf_fusion_copy_meshes(self._h, v.ctypes.data, nrm.ctypes.data, t.ctypes.data))
+        c = None
+        if colors:
+            c = np.empty((nv, 3), np.uint8)
+            _check("emf_fusion_copy_meshes_colors", load().emf_fusion_copy_meshes_colors(self._h, c.ctypes.data))
         out, v0, t0 = {}, 0, 0
         for k, i in enumerate(ids):
             cv, ct = int(counts[k, 0]), int(counts[k, 1])
-            out[i] = (v[v0:v0 + cv], nrm[v0:v0 + cv], t[t0:t0 + ct])
+            out[i] = (v[v0:v0 + cv], nrm[v0:v0 + cv], t[t0:t0 + ct]) + ((c[v0:v0 + cv],) if colors else ())
             v0, t0 = v0 + cv, t0 + ct
         return out
 
@@ -797,8 +862,10 @@ class Fusion:
         res = (C.c_int32 * 3)()
         _check("emf_fusion_get_volume",
                load().emf_fusion_get_volume(self._h, VOL[which], obj_id, C.byref(ptr), res))
-        dt = np.uint8 if which in ("fgmask", "bricks") else np.float32
-        out = np.empty((res[2], res[1], res[0]), dt)
+        if which == "color":
+            out = np.empty((res[2], res[1], res[0], 4), np.uint16)
+        else:
+            out = np.empty((res[2], res[1], res[0]), np.uint8 if which in ("fgmask", "bricks") else np.float32)
         devmem.memcpy_d2h(out, ptr.value)
         return out
 
@@ -843,6 +910,16 @@ def read_depth_png(path, scale=1.0 / 5000.0) -> np.ndarray:
     out = np.empty((h.value, w.value), np.float32)
     _check("emf_io_read_depth_png", load().emf_io_read_depth_png(os.fspath(path).encode(), scale,
                                                                out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(w), C.byref(h)))
+    return out
+
+
+def read_color_png(path) -> np.ndarray:
+    """core/Readers.cpp readPngColor through the C API: uint8 (H, W, 3) of an 8-bit RGB / RGBA PNG (alpha dropped)."""
+    w, h = C.c_int32(), C.c_int32()
+    _check("emf_io_read_color_png", load().emf_io_read_color_png(os.fspath(path).encode(), None, 0, C.byref(w), C.byref(h)))
+    out = np.empty((h.value, w.value, 3), np.uint8)
+    _check("emf_io_read_color_png", load().emf_io_read_color_png(os.fspath(path).encode(), out.ctypes.data, out.nbytes,
+                                                               C.byref(w), C.byref(h)))
     return out
 
 
@@ -926,12 +1003,19 @@ def write_volume(filename, volume: np.ndarray, voxel_size: float):
                                       (C.c_int32 * 3)(nx, ny, nz), float(voxel_size)))
 
 
-def write_mesh(filename, vertices, normals, triangles):
-    """ASCII PLY of the reference (EMFusion::writeMesh)."""
+def write_mesh(filename, vertices, normals, triangles, colors=None):
+    """ASCII PLY of the reference (EMFusion::writeMesh); colors ((n, 3) u8): red / green / blue behind the normals."""
     v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
     n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
     t = np.ascontiguousarray(triangles, np.int32).reshape(-1, 4)
     assert len(v) == len(n)
+    if colors is not None:
+        c = np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+        assert len(c) == len(v)
+        _check("emf_io_write_mesh_colors",
+               load().emf_io_write_mesh_colors(os.fspath(filename).encode(), len(v), v.ctypes.data, n.ctypes.data,
+                                               c.ctypes.data, len(t), t.ctypes.data))
+        return
     _check("emf_io_write_mesh",
            load().emf_io_write_mesh(os.fspath(filename).encode(), len(v), v.ctypes.data, n.ctypes.data,
                                     len(t), t.ctypes.data))

@@ -20,17 +20,19 @@ import numpy as np
 _PNG_SIG = b"\x89PNG\r\n\x1a\n"
 
 
-def read_png_gray(path) -> np.ndarray:
-    """Decode a non-interlaced 8- or 16-bit grayscale PNG to uint8 / uint16 (H, W)."""
+def _png_chunks(path):
+    """The IHDR fields and the concatenated IDAT bytes of a PNG file (what both image readers start from)."""
     raw = Path(path).read_bytes()
     if raw[:8] != _PNG_SIG:
         raise ValueError(f"{path}: not a PNG file")
     pos, idat, hdr = 8, [], None
-    while pos < len(raw):
+    while pos + 12 <= len(raw):
         (n,), kind = struct.unpack(">I", raw[pos:pos + 4]), raw[pos + 4:pos + 8]
+        if pos + 12 + n > len(raw):
+            raise ValueError(f"{path}: truncated PNG chunk")
         body = raw[pos + 8:pos + 8 + n]
-        if kind == b"IHDR":
-            hdr = struct.unpack(">IIBBBBB", body)
+        if kind == b"IHDR" and n >= 13:
+            hdr = struct.unpack(">IIBBBBB", body[:13])
         elif kind == b"IDAT":
             idat.append(body)
         elif kind == b"IEND":
@@ -38,17 +40,55 @@ def read_png_gray(path) -> np.ndarray:
         pos += 12 + n
     if hdr is None:
         raise ValueError(f"{path}: no IHDR chunk")
-    w, h, depth, color, _, _, interlace = hdr
+    return hdr, b"".join(idat)
+
+
+def read_png_gray(path) -> np.ndarray:
+    """Decode a non-interlaced 8- or 16-bit grayscale PNG to uint8 / uint16 (H, W)."""
+    (w, h, depth, color, _, _, interlace), idat = _png_chunks(path)
     if color != 0 or depth not in (8, 16) or interlace != 0:
         raise ValueError(f"{path}: only non-interlaced 8/16-bit grayscale PNGs are supported "
                          f"(color type {color}, depth {depth}, interlace {interlace})")
     bpp = depth // 8
     stride = w * bpp
-    data = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8).reshape(h, stride + 1)
+    data = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, stride + 1)
     out = _unfilter(np.ascontiguousarray(data), h, stride, bpp, path)
     if bpp == 1:
         return out
     return out.reshape(h, w, 2).astype(np.uint16) @ np.array([256, 1], np.uint16)  # big endian
+
+
+MAX_COLOR_SIDE, MAX_COLOR_PIXELS = 16384, 1 << 26  # core/Readers.hpp kMaxColorSide, kMaxColorPixels
+
+
+def read_png_color(path) -> np.ndarray:
+    """Decode a non-interlaced 8-bit PNG of colour type 2 (RGB) or 6 (RGBA, alpha dropped) to uint8 (H, W, 3): the
+    colour images of the TUM / Co-Fusion sequences (core/Readers.cpp readPngColor).  Anything else -- palette, 16-bit,
+    grayscale, interlaced, more than MAX_COLOR_SIDE pixels a side -- raises ValueError before anything is inflated."""
+    hdr, idat = _png_chunks(path)
+    w, h, depth, color, _, _, interlace = hdr
+    if w <= 0 or h <= 0 or w > MAX_COLOR_SIDE or h > MAX_COLOR_SIDE or w * h > MAX_COLOR_PIXELS:
+        raise ValueError(f"{path}: colour image of {w} x {h} (1 .. {MAX_COLOR_SIDE} pixels a side, "
+                         f"{MAX_COLOR_PIXELS} in all)")
+    if color == 3:
+        raise ValueError(f"{path}: palette PNGs are not supported as colour images")
+    if interlace != 0:
+        raise ValueError(f"{path}: interlaced PNGs are not supported")
+    if color not in (2, 6) or depth != 8:
+        raise ValueError(f"{path}: only 8-bit RGB / RGBA PNGs are supported as colour images "
+                         f"(colour type {color}, {depth} bits)")
+    bpp = 3 if color == 2 else 4
+    stride = w * bpp
+    try:
+        z = zlib.decompressobj()
+        data = z.decompress(idat, h * (stride + 1) + 1)  # bounded: never more than the header promises
+    except zlib.error as e:
+        raise ValueError(f"{path}: cannot inflate the image data ({e})") from None
+    if len(data) != h * (stride + 1):
+        raise ValueError(f"{path}: cannot inflate the image data ({len(data)} bytes for {h} x {stride + 1})")
+    rows = np.frombuffer(data, np.uint8).reshape(h, stride + 1)
+    out = _unfilter(np.ascontiguousarray(rows), h, stride, bpp, path)
+    return np.ascontiguousarray(out.reshape(h, w, bpp)[..., :3])
 
 
 def _unfilter(data: np.ndarray, h: int, stride: int, bpp: int, path) -> np.ndarray:
@@ -169,6 +209,10 @@ class TUMReader:
     def depth(self, index: int) -> np.ndarray:
         raw = read_png_gray(self.path / self.depth_names[index])
         return raw.astype(np.float32) * np.float32(1 / 5000.0)
+
+    def color(self, index: int) -> np.ndarray:
+        """Colour image of frame `index`, uint8 (H, W, 3) (TUMRGBDReader::readColor)."""
+        return read_png_color(self.path / self.rgb_names[index])
 
     def __iter__(self) -> Iterator[Tuple[int, np.ndarray]]:
         for i in range(len(self)):
@@ -307,6 +351,10 @@ class ImageReader:
         d = read_exr(self._depth(index))
         d[d > 100] = 0
         return d
+
+    def color_image(self, index: int) -> np.ndarray:
+        """Colour image of file index `index`, uint8 (H, W, 3) (ImageReader::readColor)."""
+        return read_png_color(self._color(index))
 
     def __iter__(self) -> Iterator[Tuple[int, np.ndarray]]:
         for i in range(self.first, self.first + self.num_frames):

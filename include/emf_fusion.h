@@ -63,7 +63,8 @@ enum emf_fusion_volume {
     EMF_VOL_WEIGHTS = 1,  /* f32 */
     EMF_VOL_FGPROBS = 2,  /* f32, objects only */
     EMF_VOL_FGMASK = 3,   /* u8,  objects only */
-    EMF_VOL_BRICKS = 4    /* u8,  brick uniformity flags, ceil(N/4) per axis (res = brick grid) */
+    EMF_VOL_BRICKS = 4,   /* u8,  brick uniformity flags, ceil(N/4) per axis (res = brick grid) */
+    EMF_VOL_COLOR = 5     /* u16 x 4 (R, G, B, Wc in 8.8 fixed point), only after emf_fusion_set_color(on) */
 };
 
 const char* emf_fusion_last_error_string(void);
@@ -90,6 +91,23 @@ int emf_fusion_trim_pool(uint64_t* bytes_freed);
  * from <path>/Mask%04d.plk (EMFusion::usePreprocMasks, EMFusion.h:98).  emf_fusion_get_last_masks: EMFusion::
  * getLastMasks (EMFusion.h:83) -- W x H x 3 bytes (may be NULL), *instances of the last mask frame. */
 int emf_fusion_process_rgbd(emf_fusion_t* h, const float* depth_host, int32_t width, int32_t height);
+/* Per-voxel colour (include/emf_hip.h "Per-voxel colour"; off by default, and with it off nothing of a frame changes).
+ *   set_color          on != 0: every model gets a colour volume (EMF_VOL_COLOR), zeroed at creation and at reset,
+ *                      carried through ObjTSDF::resize, freed with its model; a frame that was handed a colour image
+ *                      fuses it behind its TSDF integration, weighted by the association maps of that integration.
+ *                      Before the first frame and after emf_fusion_reset only (EMF_E_ARG otherwise); refused as
+ *                      unsupported on the sharded path and on the per-volume path.
+ *   set_color_image    the u8 x 3 DEVICE image (frame size) that goes with the NEXT frame (emf_fusion_process_frame,
+ *                      emf_fusion_process_rgbd, emf_fusion_stage_integrate) and with that one only; it must stay
+ *                      valid until that frame has run.  A frame without one leaves the colour volumes untouched.
+ *   process_rgbd_color emf_fusion_process_rgbd with a HOST rgb image (width x height x 3 bytes): uploaded, handed to
+ *                      set_color_image, then the frame.
+ *   colored_voxels     voxels the colour pass has updated since the last call (waits for the device) */
+int emf_fusion_set_color(emf_fusion_t* h, int on);
+int emf_fusion_set_color_image(emf_fusion_t* h, const emf_image_t* rgb_dev);
+int emf_fusion_process_rgbd_color(emf_fusion_t* h, const float* depth_host, const uint8_t* rgb_host, int32_t width,
+                                  int32_t height);
+int emf_fusion_colored_voxels(emf_fusion_t* h, uint64_t* count);
 int emf_fusion_use_preproc_masks(emf_fusion_t* h, const char* path);
 int emf_fusion_get_last_masks(emf_fusion_t* h, uint8_t* rgb, size_t capacity, int32_t* instances);
 
@@ -161,8 +179,18 @@ int emf_fusion_copy_mesh(emf_fusion_t* h, float* vertices, float* normals, int32
  * wanted), each model's triangle indices local to its own vertices. */
 int emf_fusion_extract_meshes(emf_fusion_t* h, const int32_t* ids, int n, uint32_t* counts);
 int emf_fusion_copy_meshes(emf_fusion_t* h, float* vertices, float* normals, int32_t* triangles);
+/* The vertex colours (3 bytes per vertex, RGB; emf_hip_meshColors) of the mesh / meshes the last emf_fusion_extract_mesh
+ * / emf_fusion_extract_meshes kept, in copy_mesh's / copy_meshes' vertex order.  EMF_E_ARG unless colour was on
+ * (emf_fusion_set_color) when the mesh was extracted. */
+int emf_fusion_copy_mesh_colors(emf_fusion_t* h, uint8_t* colors);
+int emf_fusion_copy_meshes_colors(emf_fusion_t* h, uint8_t* colors);
 int emf_io_write_mesh(const char* filename, uint32_t num_vertices, const float* vertices,
                       const float* normals, uint32_t num_triangles, const int32_t* triangles);
+/* The same PLY with `property uchar red / green / blue` behind the normals (colors: 3 bytes per vertex) -- what
+ * write_results writes for mesh_*.ply and frame_meshes with colour on (emf_fusion_set_color); with colour off its files
+ * are emf_io_write_mesh's, byte for byte. */
+int emf_io_write_mesh_colors(const char* filename, uint32_t num_vertices, const float* vertices, const float* normals,
+                             const uint8_t* colors, uint32_t num_triangles, const int32_t* triangles);
 /* EMFusion::render (EMFusion.cpp:131-160): Phong-shaded RGB view of the models, width*height*3 bytes
  * into host memory; color_map (may be NULL) receives the 256 x RGB label colours. */
 int emf_fusion_render(emf_fusion_t* h, uint8_t* rgb, uint8_t* color_map);
@@ -177,6 +205,16 @@ int emf_fusion_render_view(emf_fusion_t* h, const float R[9], const float t[3], 
 int emf_fusion_set_3d_view(emf_fusion_t* h, const float R[9], const float t[3], const float K[9], int32_t width,
                            int32_t height);
 int emf_fusion_clear_3d_view(emf_fusion_t* h);
+/* Shading of the views: EMF_SHADE_LABEL (default; the bytes of emf_fusion_render_view) paints every model in its label
+ * colour, EMF_SHADE_COLOR gives each hit pixel the colour of the voxel nearest to its vertex in the model the
+ * segmentation names (no interpolation; voxels nobody coloured fall back to the label colour) and feeds it to the same
+ * Phong terms -- a pixel pass (emf_hip_sampleColor, emf_hip_renderPhongColor) behind the unchanged view kernel.
+ * EMF_SHADE_COLOR needs emf_fusion_set_color(on): EMF_E_ARG otherwise.  set_3d_view_shading: the shading of the
+ * view of emf_fusion_set_3d_view. */
+enum emf_fusion_shading { EMF_SHADE_LABEL = 0, EMF_SHADE_COLOR = 1 };
+int emf_fusion_render_view_shaded(emf_fusion_t* h, const float R[9], const float t[3], const float K[9], int32_t width,
+                                  int32_t height, int shading, uint8_t* rgb, float* raylengths, uint8_t* seg);
+int emf_fusion_set_3d_view_shading(emf_fusion_t* h, int shading);
 /* Multi-GPU: broadcast the depth image of every frame from rank `root` (whose process_frame argument
  * is the source; on the other ranks it is the destination and must have the same size and pitch)
  * before anything else runs.  root < 0 (default): every rank is handed the frame itself. */
@@ -195,7 +233,8 @@ int emf_io_write_pose_file(const char* filename, int n, const int32_t* frames, c
                            const float* t);
 /* Undo the PNG scan-line filters (PNG specification 9.2; what cv::imread does inside
  * TUMRGBDReader.cpp for the depth images): rows = height x (1 + stride) bytes, each line preceded by
- * its filter type 0..4; out = height x stride reconstructed bytes; bpp = bytes per pixel (1 or 2). */
+ * its filter type 0..4; out = height x stride reconstructed bytes; bpp = bytes per pixel (1 or 2: the depth images,
+ * 3 or 4: 8-bit RGB / RGBA colour images). */
 int emf_io_png_unfilter(const uint8_t* rows, int height, int stride, int bpp, uint8_t* out);
 /* The C++ dataset readers behind apps/emfusion_synth --sequence (core/Readers.hpp; reference
  * src/utils/TUMRGBDReader.cpp, src/core/MaskRCNN.cpp:250-282), exposed for tests and FFI users.
@@ -206,6 +245,11 @@ int emf_io_png_unfilter(const uint8_t* rows, int height, int stride, int bpp, ui
  *                      (n * height * width bytes, 0/1), boxes (n * 4) and scores (n * *nscores) are filled when
  *                      not NULL and large enough (mask_capacity in bytes, score_capacity in doubles) */
 int emf_io_read_depth_png(const char* path, float scale, float* out, size_t capacity, int32_t* width, int32_t* height);
+/*   read_color_png     an 8-bit RGB or RGBA (alpha dropped) PNG as width x height x 3 bytes (emf::readPngColor: the
+ *                      colour images of the TUM / Co-Fusion sequences); palette, 16-bit, grayscale, interlaced and
+ *                      oversized files are rejected with a message; out may be NULL to ask for the size only; capacity
+ *                      in bytes */
+int emf_io_read_color_png(const char* path, uint8_t* out, size_t capacity, int32_t* width, int32_t* height);
 /*   read_exr           one channel (NULL / "": the only one, else the first of Z, Y, R) of a single-part scan-line
  *                      OpenEXR file as float (emf::readExr; reference src/utils/ImageReader.cpp:105-110 reads its
  *                      depth files with cv::imread); out may be NULL to ask for the size only

@@ -985,6 +985,71 @@ int emf_hip_compositeFromKeysPeer(const emf_peer_t* group, uint32_t seq, int ban
 int emf_hip_visibilityFlagsMirror(int32_t* visCounts, int nall, int nmodels, const int32_t* countIndex_host,
                                   int visibilityThresh, int32_t* visible_dev, int32_t* countsMirror, emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Per-voxel colour (new behaviour: the reference hands its RGB frames to Mask R-CNN only).
+ * A COLOUR VOLUME holds uint16_t[4] per voxel, in the voxel order of the tsdf: R, G, B as 8.8 fixed
+ * point (q = rint(c * 256), c in [0, 255]) and the colour weight Wc as 8.8 fixed point.  Colour has a
+ * weight of its own: a voxel collects TSDF weight from free-space updates long before a surface
+ * reaches it, and 16 bits per channel because an 8-bit running average stalls near the weight cap.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Colour update of all models in one launch (level 3, 1 <= nmodels <= EMF_MAX_BATCH; longer tables in
+ * chunks).  A voxel of model m is VISITED under exactly the gates of the TSDF update (TSDF.cu:345-380:
+ * p_cam.z > 0, rounded pixel inside the image, depth > 0; same pose, same depth image, same
+ * visible_dev gate) and COLOURED iff |sdf| < truncdist and aw = models_dev[m].assoc(py, px) > 0.
+ * Then, in float32 without contraction, per channel k:
+ *     W = Wc_q / 256.f;  c_old = C_q[k] / 256.f;  c = (float) rgb(py, px)[k];
+ *     C_q[k] = (uint16_t) lrintf(((W * c_old + aw * c) / (W + aw)) * 256.f);
+ *     Wc_q   = (uint16_t) lrintf(fminf(W + aw, maxWeight) * 256.f);     (maxWeight < 256)
+ * with W read once, before any channel is written.  Every other voxel keeps its four values and is
+ * neither read nor written.  Projection, pixel rounding and the band decision are the TSDF update's own
+ * device functions.  Reads nothing the TSDF integration writes: it only has to follow the E-step that made
+ * the association maps and whatever wrote visible_dev.
+ *   colors_dev : DEVICE array of nmodels colour-volume pointers, parallel to models_dev (the model table
+ *                keeps its layout); a NULL entry skips that model
+ *   rgb        : u8 x 3 image of the depth image's size
+ *   invLambda  : NULL, or emf_hip_computeInvLambda's table (same values)
+ *   stats      : NULL, or one u64 device counter this call ADDS the number of coloured voxels to */
+int emf_hip_integrateColorBatched(const emf_model_t* models_dev, uint16_t* const* colors_dev,
+                                  const emf_pose_t* poseOC_host, const int32_t* res_host, int nmodels,
+                                  const int32_t* visible_dev, const emf_image_t* depth, const emf_image_t* invLambda,
+                                  const emf_image_t* rgb, const float K[9], uint64_t* stats, emf_stream_t stream);
+
+/* emf_hip_copyValues for a colour volume (ObjTSDF::resize): dst(v) = src(v + offset) inside the source,
+ * (0, 0, 0, 0) elsewhere; every voxel of dst is written. */
+int emf_hip_copyColorValues(const uint16_t* src, uint16_t* dst, const int32_t offset[3], const int32_t srcRes[3],
+                            const int32_t dstRes[3], emf_stream_t stream);
+
+/* Vertex colours of a mesh: u8 x 3 per vertex, in the vertex order of emf_hip_meshEmit / emf_hip_meshEmitBatched for
+ * the same volume(s) and the same scratch -- valid after the matching emf_hip_meshCount / ...Batched, before or after
+ * the emit, which it does not disturb.  A vertex on the edge between voxels 1 and 2 takes, per channel,
+ * rint(c1 + mu * (c2 - c1)) with c = C_q / 256.f and vertexInterp's mu (TSDF.cu:909-920) -- c1 or c2 outright in its
+ * three early-return cases.  An endpoint with Wc_q == 0 contributes the other endpoint's colour; if both are
+ * uncoloured the vertex is (0, 0, 0).
+ *   color      : the volume's colour volume;  colors_dev: DEVICE array of n colour-volume pointers parallel to
+ *                models_dev (a NULL entry: that model's vertices are (0, 0, 0))
+ *   colors     : 3 bytes per vertex (all models concatenated like the emit's vertices) */
+/* Coloured views: the colour under every pixel of a view, then the usual shading from it.
+ *   sampleColor      per pixel with a vertex (vertices != 0; f32 x 3 in the VIEWER frame, as emf_hip_renderView writes
+ *                    them) the colour of the voxel nearest to the vertex -- no interpolation -- in the model the
+ *                    segmentation names (label 0: slot 0, label of ids_host[s - 1]: slot s, ids saturated to u8 as the
+ *                    composite writes them), rounded from 8.8 fixed point to the nearest level; a voxel with
+ *                    Wc_q == 0, a vertex outside its volume, a model without a colour volume (NULL entry, or colors_dev
+ *                    NULL) and a label no slot carries fall back to colorMap[label].  Pixels without a vertex: 0.
+ *                    poseVO_dev: DEVICE emf_pose_t[nmodels], viewer -> volume, the array emf_hip_renderView took.
+ *                    Slots above 254 are not addressable by a u8 label and fall back too.
+ *   renderPhongColor emf_hip_renderPhong with the diffuse colour of each pixel read from `colors` (u8 x 3) instead of
+ *                    colorMap[segmentation]: the same terms, the same bits for the same colour. */
+int emf_hip_sampleColor(const emf_model_t* models_dev, uint16_t* const* colors_dev, const emf_pose_t* poseVO_dev,
+                        const int32_t* ids_host, int nmodels, const emf_image_t* vertices, const emf_image_t* segmentation,
+                        const uint8_t colorMap[768], const emf_image_t* colors, emf_stream_t stream);
+int emf_hip_renderPhongColor(const emf_image_t* vertices, const emf_image_t* normals, const emf_image_t* colors,
+                             const float lightPos[3], const emf_image_t* image, emf_stream_t stream);
+int emf_hip_meshColors(const float* tsdf, const float* weights, const uint8_t* fgVolMask, const uint16_t* color,
+                       const int32_t res[3], const void* scratch_dev, uint8_t* colors, emf_stream_t stream);
+int emf_hip_meshColorsBatched(const emf_model_t* models_dev, uint16_t* const* colors_dev, const int32_t* res_host, int n,
+                              const void* scratch_dev, uint8_t* colors, emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
