@@ -1,6 +1,8 @@
 // Communicator.cpp -- RCCL implementation of the cross-GPU exchanges.
 #include "Communicator.hpp"
 
+#include "Switches.hpp"
+
 #include <algorithm>
 
 #include <rccl/rccl.h>
@@ -100,7 +102,7 @@ private:
 struct PeerMemory {
     void* rx = nullptr;
     uint32_t* flags = nullptr;
-    uint32_t* error = nullptr;  // pinned host word
+    PinnedBuffer error;  // pinned host word (64 bytes), coherent and mapped: the waiting kernel writes it
     size_t rxBytes = 0;
     PeerMemory(int world, size_t slotBytes) : rxBytes(emf_hip_peerBufferBytes(world, slotBytes)) {
         // fine-grained: stores of another device must become visible without a cache flush of this one, and
@@ -122,15 +124,13 @@ struct PeerMemory {
         }
         flags = static_cast<uint32_t*>(f);
         hipCheck(hipMemset(flags, 0, 4096), "hipMemset(peer flags)");
-        hipCheck(hipHostMalloc(reinterpret_cast<void**>(&error), 64, hipHostMallocCoherent | hipHostMallocMapped),
-                 "hipHostMalloc(peer error word)");
-        *error = 0;
+        error = PinnedBuffer(64, hipHostMallocCoherent | hipHostMallocMapped);
+        *error.as<uint32_t>() = 0;
         hipCheck(hipDeviceSynchronize(), "hipDeviceSynchronize");
     }
     ~PeerMemory() {
         if (rx) (void)hipFree(rx);
         if (flags) (void)hipFree(flags);
-        if (error) (void)hipHostFree(error);
     }
     PeerMemory(const PeerMemory&) = delete;
     PeerMemory& operator=(const PeerMemory&) = delete;
@@ -154,13 +154,13 @@ public:
         // -- decided by "every rank on ONE device", not by "some two ranks share one": in a mixed layout (4 ranks over 2
         // GPUs) some pairs do sit on distinct devices
         g_.systemFences = (world > 1 && !oneDevice) ? 1u : 0u;
-        if (const char* w = debugEnv("EMF_PEER_WAIT_IN_FRONT")) g_.waitInFront = (w[0] == '0' && !waitInFront) ? 0u : 1u;
+        if (!switchValue(Switch::peerWaitInFront) && !waitInFront) g_.waitInFront = 0u;
         g_.rank = rank;
         g_.world = world;
         g_.slotBytes = slotBytes;
-        g_.error = own_->error;
+        g_.error = own_->error.as<uint32_t>();
         // EMF_PEER_TIMEOUT_MS: longer bound for rehearsals in which many ranks take turns on one GPU
-        if (const char* t = std::getenv("EMF_PEER_TIMEOUT_MS")) timeoutMs_ = static_cast<uint32_t>(std::max(1, std::atoi(t)));
+        timeoutMs_ = static_cast<uint32_t>(switchValue(Switch::peerTimeoutMs));
         g_.timeoutMs = timeoutMs_;
         for (int p = 0; p < world; ++p) {
             g_.slots[p] = slots[p];
@@ -236,14 +236,15 @@ public:
     const emf_peer_t* peerGroup() const override { return &g_; }
     uint32_t beginPeerExchange(Stream&) override { return begin(0); }
     void check() override {
-        if (*own_->error)
-            throw HipError("peer exchange " + std::to_string(*own_->error) + ": a peer's flag did not arrive within " +
-                           std::to_string(*own_->error == 1u ? std::max(timeoutMs_, 60000u) : timeoutMs_) + " ms (ranks disagree about the sequence of exchanges?); the "
+        const uint32_t failed = *own_->error.as<uint32_t>();
+        if (failed)
+            throw HipError("peer exchange " + std::to_string(failed) + ": a peer's flag did not arrive within " +
+                           std::to_string(failed == 1u ? std::max(timeoutMs_, 60000u) : timeoutMs_) + " ms (ranks disagree about the sequence of exchanges?); the "
                            "exchange's consumer left its outputs untouched", EMF_E_PEER_TIMEOUT);
     }
 
 private:
-    uint32_t timeoutMs_ = 5000;
+    uint32_t timeoutMs_ = 0;  // EMF_PEER_TIMEOUT_MS (default 5000), set by the constructor
     // every argument is validated BEFORE the sequence number moves: a rank that throws here has not taken part in
     // the exchange and its peers' counters stay in step with its own
     uint32_t begin(size_t bytes) {

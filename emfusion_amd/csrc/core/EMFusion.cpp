@@ -24,7 +24,6 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 
 namespace emf {
@@ -67,65 +66,20 @@ EMFusion::EMFusion(const Params& _params, TSDF::Gradients gradients,
         hitKeys = DeviceBuffer(params.frameSize.area() * sizeof(uint64_t));
     }
     ignorePerson = params.ignore_person;  // data.h:198; config/tum.cfg sets it
-    const char* env = std::getenv("EMF_PER_VOLUME");
-    forceLegacy = env && env[0] == '1';
-    // EMF_LAMBDA_TABLE=0: integrate with the inline 1 / lambda (A/B measurements; same results)
-    // EMF_BG_BANDS=0: every rank raycasts the whole (replicated) background itself
-    const char* bb = std::getenv("EMF_BG_BANDS");
-    bgBands = !(bb && bb[0] == '0');
-    // EMF_INT_CULL=0: one-level integration launch (every tile gets a workgroup and culls itself)
-    const char* ic = std::getenv("EMF_INT_CULL");
-    cullBoxes = !(ic && ic[0] == '0');
-    // Switches read through debugEnv() exist in builds with -DEMF_DEBUG_SWITCHES only: their A/B is on record as lost.
-    // EMF_OBJ_CULL=1: the two-level launch also for the objects alone (A/B: measured slower for 4 and for 8 volumes of 128^3)
-    const char* oc = debugEnv("EMF_OBJ_CULL");
-    objCull = oc && oc[0] == '1';
-    // EMF_TRACK_CHUNK: LM iterations enqueued between two polls of the convergence flags
-    if (const char* tc = debugEnv("EMF_TRACK_CHUNK")) trackChunk = std::atoi(tc);
-    if (const char* tw = debugEnv("EMF_TRACK_WINDOW")) trackWindow = std::atoi(tw);
-    if (const char* fp = debugEnv("EMF_FUSE_POINTS")) fusePoints = fp[0] != '0';
-    if (const char* fv = debugEnv("EMF_FUSE_VISIBILITY")) fuseVisibility = fv[0] != '0';
-    if (const char* ef = debugEnv("EMF_EARLY_FAR_BOUNDS")) earlyFarBounds = ef[0] != '0';
-    // EMF_BG_OVERLAP=0: integrate the background in place after the raycast, as the reference does
-    const char* bo = std::getenv("EMF_BG_OVERLAP");
-    bgOverlap = !(bo && bo[0] == '0');
-    // EMF_FAR_BOUNDS=0: no far bounds for the raycast (A/B measurements; same results)
-    const char* fb = std::getenv("EMF_FAR_BOUNDS");
-    useFarBounds = !(fb && fb[0] == '0');
-    // EMF_RAY_FOOTPRINTS=0: every object gets a marching workgroup for every tile of the image
-    const char* rf = debugEnv("EMF_RAY_FOOTPRINTS");
-    useFootprints = !(rf && rf[0] == '0');
-    // EMF_MARCH_ROWS = 1 (default) / 2 / 4 lanes per BACKGROUND ray (march_lane / march_quad<2> / march_quad<4>): same
-    // images (A/B measurements); read here, once -- anything else is refused, not silently marched with one lane
-    if (const char* mr = std::getenv("EMF_MARCH_ROWS")) {
-        marchLanes = std::atoi(mr);
-        if (marchLanes != 1 && marchLanes != 2 && marchLanes != 4)
-            throw HipError(std::string("EMFusion: EMF_MARCH_ROWS=") + mr + " (1, 2 or 4 lanes per background ray)", EMF_E_ARG);
-    }
-    const char* au = std::getenv("EMF_ASYNC_UPLOAD");
-    asyncUpload = !(au && au[0] == '0');
-    const char* lt = std::getenv("EMF_LAMBDA_TABLE");
-    useLambdaTable = !(lt && lt[0] == '0');
+    // the run-time switches were read into `sw`, once, before the first member was constructed (Switches.hpp)
     // sharded mode: the two cross-rank exchanges are used.  EMF_FORCE_SHARDED=1 turns it on for a
     // 1-rank communicator too, so the whole exchange path can be exercised on a single GPU.
-    const char* fs = std::getenv("EMF_FORCE_SHARDED");
-    sharded = comm && (world > 1 || (fs && fs[0] == '1'));
+    sharded = comm && (world > 1 || sw.forceSharded);
     // Over a direct peer-write transport the sharded path's exchanges are fused into the kernels around them
     // (Communicator::peerGroup); EMF_PEER_FUSED=0 keeps the transport's own two-launch collectives (A/B; same bits)
     if (sharded) {
-        const char* pf = debugEnv("EMF_PEER_FUSED");
         const emf_peer_t* pg = comm->peerGroup();
-        peerFused = pg && !(pf && pf[0] == '0') &&
+        peerFused = pg && sw.peerFused &&
                     pg->slotBytes >= emf_hip_peerRaycastSlotBytes(params.frameSize.width, params.frameSize.height);
     }
-    hipCheck(hipHostMalloc(reinterpret_cast<void**>(&visCountsHost),
-                           sizeof(int32_t) * EMF_MAX_MODELS, hipHostMallocDefault),
-             "hipHostMalloc");
-    hipCheck(hipHostMalloc(reinterpret_cast<void**>(&visibleHost),
-                           sizeof(int32_t) * EMF_MAX_MODELS, hipHostMallocDefault),
-             "hipHostMalloc");
-    stamps.resize(kNumStamps);
-    for (auto& e : stamps) hipCheck(hipEventCreate(&e), "hipEventCreate");
+    visCountsHost = PinnedBuffer(sizeof(int32_t) * EMF_MAX_MODELS);
+    visibleHost = PinnedBuffer(sizeof(int32_t) * EMF_MAX_MODELS);
+    for (int k = 0; k < kNumStamps; ++k) stamps.emplace_back(hipEventDefault);
     Stream& s = Stream::Null();
     // reference EMFusion.cpp:44-55: bg_mask = 0, noObjMask = 1, bg_associationWeights = 1;
     // diffRaylengths is uninitialised memory in the reference, defined as 0 here (Q12)
@@ -154,23 +108,7 @@ EMFusion::EMFusion(const Params& _params, TSDF::Gradients gradients,
     TSDF::deferReciprocalChecks(true);
 }
 
-EMFusion::~EMFusion() {
-    (void)hipDeviceSynchronize();
-    for (auto& e : stamps) (void)hipEventDestroy(e);
-    for (auto& u : uploadSlots) {
-        if (u.pinned) (void)hipHostFree(u.pinned);
-        if (u.copied) (void)hipEventDestroy(u.copied);
-        if (u.frameDone) (void)hipEventDestroy(u.frameDone);
-    }
-    if (visCountsHost) (void)hipHostFree(visCountsHost);
-    if (visibleHost) (void)hipHostFree(visibleHost);
-    if (trackStatesHost) (void)hipHostFree(trackStatesHost);
-    if (trackWatch) (void)hipHostFree(trackWatch);
-    if (lifecycleHost) (void)hipHostFree(lifecycleHost);
-    if (viewPosesHost) (void)hipHostFree(viewPosesHost);
-    if (meshHost) (void)hipHostFree(meshHost);
-    if (meshStage) (void)hipHostFree(meshStage);
-}
+EMFusion::~EMFusion() { (void)hipDeviceSynchronize(); }  // the members release themselves afterwards (EMFusion.hpp)
 
 void EMFusion::reset() {
     synchronize();
@@ -275,7 +213,7 @@ void EMFusion::rebuildModelTable() {
     resHost.clear();
     aux.waitForCompletion();  // the background's integration / the list rebuilds may still be running
     lists.waitForCompletion();
-    if (useFarBounds) {  // sign maps that something other than the tile integration made stale
+    if (sw.useFarBounds) {  // sign maps that something other than the tile integration made stale
         background.refreshSignMaps();
         for (auto& obj : objects) obj.refreshSignMaps();
     }
@@ -308,9 +246,7 @@ void EMFusion::rebuildModelTable() {
         // for far bounds; its rays are short anyway and the scan (23 us beside the E-steps, which it slows from
         // 12 to 37 us) costs the frame more than the cut saves the raycast: 0.6095 vs 0.5956 ms.  EMF_FAR_SCAN=1
         // scans them.
-        const char* fsc = debugEnv("EMF_FAR_SCAN");
-        const bool scanSmall = fsc && fsc[0] == '1';
-        scanSlot.push_back(md.signMaps && !md.relevantTiles && scanSmall);
+        scanSlot.push_back(md.signMaps && !md.relevantTiles && sw.farScan);
         listSlot.push_back(md.signMaps && md.relevantTiles);
         anyScan = anyScan || scanSlot.back();
         voxelHost.push_back(md.voxelSize);
@@ -320,16 +256,16 @@ void EMFusion::rebuildModelTable() {
     // scratch of the two-level integration launch (every model on float4 tiles, no brick flags to keep): for the
     // table chunk that holds the background -- the launch exists for the background's sake (integrateBatched)
     integrateCullScratch = DeviceBuffer();
-    if (cullBoxes && tiled && TSDF::brickFlagMode() == 0)
+    if (sw.cullBoxes && tiled && TSDF::brickFlagMode() == 0)
         integrateCullScratch = DeviceBuffer(emf_hip_integrateCullScratchBytes(
             resHost.data(), std::min(static_cast<int>(modelsHost.size()), EMF_MAX_BATCH)));
     // any number of models: stages are launched per chunk of EMF_MAX_BATCH table slots (forChunks)
-    batched = !forceLegacy && gradMode == TSDF::Gradients::OnTheFly;
+    batched = !sw.perVolume && gradMode == TSDF::Gradients::OnTheFly;
     farBounds = DeviceBuffer();
-    if (batched && useFarBounds)
+    if (batched && sw.useFarBounds)
         farBounds = DeviceBuffer(2 * emf_hip_raycastFarBoundBytes(static_cast<int>(modelsHost.size()),  // two halves, see computeFarBounds
                                                                   params.frameSize.width, params.frameSize.height));
-    if (batched && !integrateCullScratch.empty() && bgOverlap && bgCullScratch.empty()) {
+    if (batched && !integrateCullScratch.empty() && sw.bgOverlap && bgCullScratch.empty()) {
         // the background gets its second copy the first time the two-level launch is usable
         background.enableDoubleBuffer();
         bgCullScratch = DeviceBuffer(emf_hip_integrateCullScratchBytes(resHost.data(), 1));
@@ -370,7 +306,7 @@ void EMFusion::rebuildModelTable() {
         hipCheck(hipMemcpy(visibleDev.data(), vis.data(), vis.size() * sizeof(int32_t),
                            hipMemcpyHostToDevice),
                  "visibility upload");
-        if (useFarBounds) {  // lists of new / rebuilt sign maps
+        if (sw.useFarBounds) {  // lists of new / rebuilt sign maps
             forChunks(0, static_cast<int>(modelsHost.size()), [&](int first, int count) {
                 emfCheck(emf_hip_updateRelevantTiles(modelTable.as<emf_model_t>() + first, resHost.data() + 3 * first,
                                                      count, Stream::Null().abi()),
@@ -420,7 +356,7 @@ void EMFusion::posesOC(std::vector<emf_pose_t>& out) const {
 }
 
 float EMFusion::stamp(int slot) {
-    if (timingsOn) hipCheck(hipEventRecord(stamps[slot], main.get()), "hipEventRecord");
+    if (timingsOn) stamps[slot].record(main.get());
     return 0.f;
 }
 
@@ -473,7 +409,7 @@ void EMFusion::refreshVisibleFromDevice() {
     main.waitForCompletion();
     vis_objs.clear();
     for (size_t k = 0; k < visIds.size(); ++k)
-        if (visibleHost[k] > params.visibilityThresh) vis_objs.insert(visIds[k]);
+        if (visibleHost.as<int32_t>()[k] > params.visibilityThresh) vis_objs.insert(visIds[k]);
     visPending = false;
 }
 
@@ -504,10 +440,8 @@ void EMFusion::processFrame(const RGBD& frame) {
     // the slot's device image may be overwritten once this frame's kernels are through -- also those a frame that
     // throws half-way has already enqueued
     auto markDone = [&]() {
-        if (!asyncUpload) return;
-        UploadSlot& u = uploadSlots[slot];
-        if (hipEventRecord(u.frameDone, main.get()) == hipSuccess) u.frameDoneValid = true;
-        else (void)hipGetLastError();
+        if (!sw.asyncUpload) return;
+        (void)uploadSlots[slot].frameDone.tryRecord(main.get());
     };
     try {
         runSchedule(depthDev, in);
@@ -525,24 +459,23 @@ emf_image_t EMFusion::stageDepth(const float* host, int& slot) {
     const size_t bytes = static_cast<size_t>(params.frameSize.area()) * sizeof(float);
     if (u.dev.empty()) {
         u.dev = DeviceImage<float>(params.frameSize);
-        hipCheck(hipHostMalloc(reinterpret_cast<void**>(&u.pinned), bytes, hipHostMallocDefault), "hipHostMalloc(depth staging)");
-        hipCheck(hipEventCreateWithFlags(&u.copied, hipEventDisableTiming), "hipEventCreate");
-        hipCheck(hipEventCreateWithFlags(&u.frameDone, hipEventDisableTiming), "hipEventCreate");
+        u.pinned = PinnedBuffer(bytes);
+        u.copied = Event(hipEventDisableTiming);
+        u.frameDone = Event(hipEventDisableTiming);
     }
     const emf_image_t view = u.dev.view();
-    if (!asyncUpload) {  // pageable source on the frame's stream: the runtime stages it, this call blocks
+    if (!sw.asyncUpload) {  // pageable source on the frame's stream: the runtime stages it, this call blocks
         hipCheck(hipMemcpyAsync(u.dev.ptr(), host, bytes, hipMemcpyHostToDevice, main.get()), "hipMemcpyAsync H2D");
         return view;
     }
     // the staging buffer is free once the copy of two frames ago has left it (long ago: no wait in practice)
-    if (u.copiedValid) hipCheck(hipEventSynchronize(u.copied), "hipEventSynchronize(depth staging)");
-    std::memcpy(u.pinned, host, bytes);
+    if (u.copied.recorded()) hipCheck(hipEventSynchronize(u.copied.get()), "hipEventSynchronize(depth staging)");
+    std::memcpy(u.pinned.data(), host, bytes);
     // ... and the device image once the frame of two frames ago is through with it
-    if (u.frameDoneValid) hipCheck(hipStreamWaitEvent(copyStream.get(), u.frameDone, 0), "hipStreamWaitEvent(frame done)");
-    hipCheck(hipMemcpyAsync(u.dev.ptr(), u.pinned, bytes, hipMemcpyHostToDevice, copyStream.get()), "hipMemcpyAsync H2D (pinned)");
-    hipCheck(hipEventRecord(u.copied, copyStream.get()), "hipEventRecord(depth copied)");
-    u.copiedValid = true;
-    hipCheck(hipStreamWaitEvent(main.get(), u.copied, 0), "hipStreamWaitEvent(depth copied)");
+    if (u.frameDone.recorded()) hipCheck(hipStreamWaitEvent(copyStream.get(), u.frameDone.get(), 0), "hipStreamWaitEvent(frame done)");
+    hipCheck(hipMemcpyAsync(u.dev.ptr(), u.pinned.data(), bytes, hipMemcpyHostToDevice, copyStream.get()), "hipMemcpyAsync H2D (pinned)");
+    u.copied.record(copyStream.get());
+    hipCheck(hipStreamWaitEvent(main.get(), u.copied.get(), 0), "hipStreamWaitEvent(depth copied)");
     return view;
 }
 
@@ -573,7 +506,7 @@ void EMFusion::runSchedule(const emf_image_t& depthDev, const FrameInputs& in) {
     }
     // computePoints (EMFusion.cpp:73): on the batched path the first E-step of the frame forms the
     // points from the depth on its way and stores them (one launch less); frame 0 has no E-step
-    pointsPending = batched && frameCount > 0 && fusePoints;
+    pointsPending = batched && frameCount > 0 && sw.fusePoints;
     if (!pointsPending) {
         const emf_image_t pv = points.view();
         auto kt = ktimers.scope(KernelTimers::Points, pixels(), main);
@@ -674,10 +607,10 @@ void EMFusion::runSchedule(const emf_image_t& depthDev, const FrameInputs& in) {
     stamp(kMasks);
 
     if (timingsOn) {
-        hipCheck(hipEventSynchronize(stamps[kMasks]), "hipEventSynchronize");
+        hipCheck(hipEventSynchronize(stamps[kMasks].get()), "hipEventSynchronize");
         auto ms = [&](int a, int b) {
             float t = 0.f;
-            hipCheck(hipEventElapsedTime(&t, stamps[a], stamps[b]), "hipEventElapsedTime");
+            hipCheck(hipEventElapsedTime(&t, stamps[a].get(), stamps[b].get()), "hipEventElapsedTime");
             return t;
         };
         timings.points = ms(kStart, kPoints);
@@ -779,17 +712,17 @@ void EMFusion::raycastBatched() {
         // -- is split into row bands, one per rank (Plan A); raylengths and hit mask of
         // the bands are then gathered (1.5 MB at VGA).  Background vertices / normals stay
         // band-local: like the remote objects' they only feed rendering.
-        const int band = sharded && bgBands ? bgBandRows(h, world) : 0;
+        const int band = sharded && sw.bgBands ? bgBandRows(h, world) : 0;
         const float* far = farBoundsReady && !flags ? farBoundsHalf() : nullptr;
         farBoundsReady = false;
         const size_t cells = emf_hip_raycastFarBoundBytes(1, w, h) / sizeof(float);  // bounds per model
         forChunks(0, n, [&](int first, int count) {
             const float* farChunk = far ? far + cells * first : nullptr;
-            const float* vox = useFootprints ? voxelHost.data() + first : nullptr;
+            const float* vox = sw.useFootprints ? voxelHost.data() + first : nullptr;
             if (first == 0)
                 emfCheck(emf_hip_raycastBatchedLanes(table, co.data(), resHost.data(), count, w, h, params.intr.val,
                                                      flags, band ? std::min(rank * band, ((h + 15) / 16) * 16) : 0,
-                                                     band, farChunk, vox, marchLanes, stats, main.abi()),
+                                                     band, farChunk, vox, sw.marchLanes, stats, main.abi()),
                          "raycastBatched");
             else  // a chunk of objects only (more than EMF_MAX_BATCH models)
                 emfCheck(emf_hip_raycastBatchedObjects(table + first, co.data() + first, resHost.data() + 3 * first, count,
@@ -819,7 +752,7 @@ void EMFusion::computeFarBounds(const std::vector<emf_pose_t>& co) {
     // integration (integrateBackgroundAsync: behind its last E-step).  No event of its own behind every raycast
     // any more (a record costs the critical stream ~8 us per frame).
     farSel ^= 1;
-    if (earlyFarBounds && !anyScan && forkFrame == frameCount - 1 && overlapUsable() && !bgBackStale)
+    if (sw.earlyFarBounds && !anyScan && forkFrame == frameCount - 1 && overlapUsable() && !bgBackStale)
         lists.waitOn(main);
     else
         lists.waitFor(main);  // the previous raycast has read the bounds (and in-place paths rebuilt lists on main)
@@ -844,13 +777,13 @@ void EMFusion::joinFarBounds() {
 void EMFusion::rebuildBackgroundList() {
     if (!bgListPending) return;
     bgListPending = false;
-    if (!useFarBounds || farBounds.empty()) return;
+    if (!sw.useFarBounds || farBounds.empty()) return;
     lists.waitOn(aux);  // the record() behind the integration kernels (this frame's far bounds ran on `lists`)
     emfCheck(emf_hip_updateRelevantTiles(currentTable(), resHost.data(), 1, lists.abi()), "updateRelevantTiles");
 }
 
 bool EMFusion::overlapUsable() const {
-    return batched && bgOverlap && background.doubleBuffered() && !bgCullScratch.empty();
+    return batched && sw.bgOverlap && background.doubleBuffered() && !bgCullScratch.empty();
 }
 
 // Fork: the background's integration of this frame needs the pose, the depth map and the background
@@ -877,7 +810,7 @@ void EMFusion::integrateBackgroundAsync() {
     {
         auto kt = ktimers.scope(KernelTimers::IntegrateBg, vox, aux);
         emfCheck(emf_hip_integrateBatchedCulledOut(currentTable(), &oc, resHost.data(), 1, nullptr, &depth,
-                                                   useLambdaTable ? &il : nullptr, params.intr.val, &out,
+                                                   sw.useLambdaTable ? &il : nullptr, params.intr.val, &out,
                                                    bgPrepared ? 1 : 0, bgCullScratch.data(), 0, nullptr,
                                                    integrateStatsDev.as<uint64_t>(), aux.abi()),
                  "integrateBatchedCulledOut");
@@ -917,14 +850,14 @@ void EMFusion::integrateBatched() {
             vox += static_cast<double>(resHost[3 * m]) * resHost[3 * m + 1] * resHost[3 * m + 2];
         auto kt = ktimers.scope(KernelTimers::Integrate, vox, main);
         const emf_image_t il = invLambda.view();
-        const emf_image_t* ilp = useLambdaTable ? &il : nullptr;
+        const emf_image_t* ilp = sw.useLambdaTable ? &il : nullptr;
         forChunks(first, n, [&](int from, int count) {
             const emf_model_t* table = currentTable() + from;
             const int32_t* vis = visibleDev.as<int32_t>() + from;
             // two-level launch: the boxes of tiles outside the view cone never get a workgroup -- what the
             // background needs; object volumes alone are small and mostly in view, and the list's counter
             // reset + cull kernel cost them more (24 us of the frame) than the culled tiles would
-            if ((from == 0 || (objCull && from < EMF_MAX_BATCH)) && cullBoxes && !integrateCullScratch.empty()) {
+            if ((from == 0 || (sw.objCull && from < EMF_MAX_BATCH)) && sw.cullBoxes && !integrateCullScratch.empty()) {
                 emfCheck(emf_hip_integrateBatchedCulled(table, oc.data() + from, resHost.data() + 3 * from, count,
                                                         vis, &depth, ilp, params.intr.val,
                                                         integrateCullScratch.data(), 0, nullptr,
@@ -941,7 +874,7 @@ void EMFusion::integrateBatched() {
     integrateColor(oc);
     const bool overlapped = bgInFlight;
     joinBackground();
-    if (useFarBounds && !farBounds.empty()) {
+    if (sw.useFarBounds && !farBounds.empty()) {
         // The sign maps may have grown: rebuild the relevant-tile lists the NEXT frame's far bounds read.
         // Nothing of this frame needs them: with the streams in use they go to `lists`, behind the
         // integration above (the background's own list went there behind its integration already).
@@ -967,7 +900,7 @@ void EMFusion::integrateColor(const std::vector<emf_pose_t>& oc) {
     if (!colorOn || !colorImageSet) return;
     colorImageSet = false;  // consumed by this frame
     const emf_image_t il = invLambda.view();
-    const emf_image_t* ilp = useLambdaTable ? &il : nullptr;
+    const emf_image_t* ilp = sw.useLambdaTable ? &il : nullptr;
     forChunks(0, static_cast<int>(oc.size()), [&](int from, int count) {
         emfCheck(emf_hip_integrateColorBatched(currentTable() + from, colorTable.as<uint16_t*>() + from, oc.data() + from,
                                                resHost.data() + 3 * from, count, visibleDev.as<int32_t>() + from, &depth,
@@ -983,7 +916,7 @@ void EMFusion::enableColor(bool on) {
         throw HipError("EMFusion::enableColor: only before the first frame or after reset()", EMF_E_ARG);
     if (on && sharded)  // like the per-frame meshes: remote objects are not on this rank
         throw HipError("EMFusion::enableColor: colour is not supported on the sharded path", EMF_E_ARG);
-    if (on && (forceLegacy || gradMode != TSDF::Gradients::OnTheFly))
+    if (on && (sw.perVolume || gradMode != TSDF::Gradients::OnTheFly))
         throw HipError("EMFusion::enableColor: colour is not supported on the per-volume path", EMF_E_ARG);
     if (on && !(params.tsdfParams.maxTSDFWeight < 256.f))
         throw HipError("EMFusion::enableColor: maxTSDFWeight must be below 256 (8.8 fixed-point colour weight)", EMF_E_ARG);
@@ -1035,7 +968,7 @@ void EMFusion::compositeAndVisibility(bool deviceGate) {
     const int nobj = static_cast<int>(o.index.size());
     {
         auto kt = ktimers.scope(KernelTimers::Composite, pixels() * (1.0 + nobj), main);
-        if (deviceGate && fuseVisibility) {
+        if (deviceGate && sw.fuseVisibility) {
             // the composite's own launch counts; the counts also go to pinned host memory straight from
             // the flag kernel, which leaves visCounts cleared for the next frame
             if (!visCountsClear) visCounts.setZero(main);  // (another path left its numbers there)
@@ -1044,7 +977,7 @@ void EMFusion::compositeAndVisibility(bool deviceGate) {
                                                  o.seg.data(), &f.bgRay, &f.bgVert, &f.bgNorm, &f.bgMask, &f.ray,
                                                  &f.vert, &f.norm, &f.seg, &f.diff, &f.noObj, params.boundary,
                                                  visCounts.as<int32_t>(), params.visibilityThresh,
-                                                 visibleDev.as<int32_t>(), visibleHost, main.abi()),
+                                                 visibleDev.as<int32_t>(), visibleHost.as<int32_t>(), main.abi()),
                      "compositeVisibility");
         } else {
             visCountsClear = false;
@@ -1056,7 +989,7 @@ void EMFusion::compositeAndVisibility(bool deviceGate) {
             if (deviceGate)  // the counts also go to pinned host memory straight from the kernel
                 emfCheck(emf_hip_visibilityFlags(visCounts.as<int32_t>(), nobj + 1,
                                                  params.visibilityThresh, visibleDev.as<int32_t>(),
-                                                 visibleHost, main.abi()),
+                                                 visibleHost.as<int32_t>(), main.abi()),
                          "visibilityFlags");
         }
     }
@@ -1092,7 +1025,7 @@ void EMFusion::visibleFromCounts(const std::vector<int32_t>& ids, bool deviceGat
     visPending = false;
     if (ids.empty()) return;
     if (!mirrored)
-        hipCheck(hipMemcpyAsync(deviceGate ? visibleHost : visCountsHost, visCounts.data(), sizeof(int32_t) * ids.size(),
+        hipCheck(hipMemcpyAsync((deviceGate ? visibleHost : visCountsHost).data(), visCounts.data(), sizeof(int32_t) * ids.size(),
                                 hipMemcpyDeviceToHost, main.get()),
                  "visCounts D2H");
     if (deviceGate) {
@@ -1102,7 +1035,7 @@ void EMFusion::visibleFromCounts(const std::vector<int32_t>& ids, bool deviceGat
     }
     main.waitForCompletion();  // the visible set gates integrateDepth (EMFusion.cpp:869-872)
     for (size_t k = 0; k < ids.size(); ++k)
-        if (visCountsHost[k] > params.visibilityThresh) vis_objs.insert(ids[k]);
+        if (visCountsHost.as<int32_t>()[k] > params.visibilityThresh) vis_objs.insert(ids[k]);
 }
 
 }  // namespace emf

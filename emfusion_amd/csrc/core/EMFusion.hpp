@@ -24,6 +24,7 @@
 #include "KernelTimers.hpp"
 #include "ObjTSDF.hpp"
 #include "Output.hpp"
+#include "Switches.hpp"
 #include "TSDF.hpp"
 
 namespace emf {
@@ -386,10 +387,8 @@ private:
     void estepSharded(const std::vector<emf_pose_t>& co, bool fromDepth);
     void launchEstep(const std::vector<emf_pose_t>& co, int first, int count, bool fromDepth, int normalize,
                      const emf_image_t* norm, const emf_image_t* objSum);
-    bool fusePoints = true;       // the frame's first E-step makes the points (EMF_FUSE_POINTS=0: own launch)
-    bool pointsPending = false;   // ... and has not run yet
+    bool pointsPending = false;   // the frame's first E-step makes the points (sw.fusePoints) and has not run yet
     bool visCountsClear = true;   // visCounts holds zeros (cleared at construction, left so by the fused pair)
-    bool fuseVisibility = true;   // the composite's launch takes the visibility counts (EMF_FUSE_VISIBILITY=0: own launch)
     void raycastBatched();
     void integrateBatched();
     void compositeAndVisibility(bool deviceGate);
@@ -416,6 +415,14 @@ private:
     float stamp(int slot);
     double pixels() const;
 
+    // Member order.  `sw` comes first: the environment is read once per construction, in front of everything that needs
+    // a value (the streams' priorities) and of every allocation, so a refused value (EMF_MARCH_ROWS) throws with nothing
+    // to undo.  ~EMFusion only waits for the device; the members then go in reverse order of declaration: first the
+    // block at the END of this list -- pinned host memory that kernels of this instance write (visibleHost,
+    // trackWatch, the mirrors) and every event recorded on the streams below -- while all streams still exist, then
+    // device buffers, streams and volumes in the order they have always had.  A constructor that throws half-way
+    // releases what it had built the same way.
+    const Switches sw = Switches::fromEnvironment();
     Params params;
     TSDF::Gradients gradMode;
     std::shared_ptr<Communicator> comm;
@@ -432,7 +439,7 @@ private:
     // that class the frame took 0.76-0.91 ms instead of 0.57 for 2, 5, 6 or 9 live foreign streams, and was flat
     // over 0 .. 9 of them with main = high, aux = lists = low (scripts/stream_history_probe.py --matrix3,
     // DESIGN.md section 6; tests/test_gpu_stream_history.py)
-    Stream main{streamPriority("EMF_PRIO_MAIN", 1)};
+    Stream main{sw.prioMain};
     Affine3f pose;                       // current camera pose
     std::set<int> vis_objs;
     int frameCount = 0;
@@ -448,15 +455,12 @@ private:
     // `main` (rounds 1-5: the runtime stages it and the host blocks; A/B measurements).
     struct UploadSlot {
         DeviceImage<float> dev;
-        float* pinned = nullptr;
-        hipEvent_t copied = nullptr;     // the H2D copy out of `pinned` into `dev` is through
-        hipEvent_t frameDone = nullptr;  // the frame that read `dev` is through (recorded on `main` at its end)
-        bool copiedValid = false, frameDoneValid = false;
+        PinnedBuffer pinned;
+        Event copied;     // the H2D copy out of `pinned` into `dev` is through
+        Event frameDone;  // the frame that read `dev` is through (recorded on `main` at its end)
     };
-    UploadSlot uploadSlots[2];
-    Stream copyStream{streamPriority("EMF_PRIO_COPY", 1)};
+    Stream copyStream{sw.prioCopy};
     uint64_t uploads = 0;
-    bool asyncUpload = true;
     double uploadHostSeconds = 0.0;  // host time processFrame(RGBD) spent getting the depth map on its way (sum)
     emf_image_t stageDepth(const float* host, int& slotOut);
     std::string maskPath;                              // usePreprocMasks
@@ -464,14 +468,10 @@ private:
     std::vector<uint8_t> lastMaskVis;
     int lastMaskInstances = 0;
     DeviceImage<float> depthFiltered;  // output of preprocessDepth
-    DeviceImage<float> invLambda;  // per-pixel 1 / lambda of the integration, fixed by the intrinsics
-    bool useLambdaTable = true;
+    DeviceImage<float> invLambda;  // per-pixel 1 / lambda of the integration, fixed by the intrinsics (sw.useLambdaTable)
     DeviceBuffer integrateCullScratch;  // survivor list of emf_hip_integrateBatchedCulled (empty: plain launch)
-    bool cullBoxes = true;               // EMF_INT_CULL=0 keeps the one-level launch (A/B measurements)
-    bool objCull = false;                // EMF_OBJ_CULL=1: two-level launch for the objects alone too (A/B)
     bool ignorePerson = false;
     int depthRoot = -1;  // sharded path: rank whose depth image is broadcast each frame (-1: none)
-    bool bgBands = true;  // sharded path: split the background raycast into row bands per rank
 
     // ---- object creation / matching (SURVEY f-3) ----
     emf_point_stats_t maskedStats(const emf_image_t& mask, const Affine3f& frame);  // synchronises
@@ -484,7 +484,6 @@ private:
     std::array<uint8_t, 768> colorMap = io::randomColors();
     DeviceImage<uint8_t, 3> image;  // rendering
     // ---- free-viewpoint view (EMFusionView.cpp) ----
-    emf_pose_t* viewPosesHost = nullptr;  // pinned, EMF_MAX_MODELS viewer -> volume poses
     DeviceBuffer viewPosesDev;
     DeviceBuffer viewTableDev;  // per-volume path: the host table uploaded for the view (no device table there)
     DeviceImage<uint8_t, 3> viewImage;
@@ -506,9 +505,6 @@ private:
     std::map<int, std::map<int, Mesh>> frame_obj_meshes;   // id -> frame -> mesh
     void storeFrameMeshes();                               // the end of a frame with exp_frame_meshes
     DeviceBuffer meshTableDev, meshCountsDev, meshScratch, meshArena;  // extractMeshes' pooled buffers
-    void* meshHost = nullptr;       // pinned: EMF_MAX_MODELS emf_model_t, then the counts and bases read back
-    void* meshStage = nullptr;      // pinned staging of the meshes' bytes (grown when needed)
-    size_t meshStageBytes = 0;
     bool expVols = false;                                  // setupOutput: keep / dump volumes too
     // ---- per-frame debug images of the reference's saveOutput mode, kept as encoded PNGs ----
     bool saveOutput = false;
@@ -537,23 +533,19 @@ private:
     void deleteObj(int id);
     void deleteOwned(std::list<ObjTSDF>::iterator it);  // cleanUpObjs' removal of an object of this rank
     void ensureLifecycleBuffers();
-    void* lifecycleHost = nullptr;  // pinned: emf_point_stats_t / 513 x u32 / EMF_MAX_MODELS x emf_mask_mass_t, then
-                                    // EMF_MAX_MODELS floats (verdicts, messages), then EMF_MAX_MODELS int32 (gate)
+    // layout of lifecycleHost: emf_point_stats_t / 513 x u32 / EMF_MAX_MODELS x emf_mask_mass_t, then EMF_MAX_MODELS
+    // floats (verdicts, messages), then EMF_MAX_MODELS int32 (gate)
     static constexpr size_t kLcVerdictOff = EMF_MAX_MODELS * sizeof(emf_mask_mass_t);
     static constexpr size_t kLcGateOff = kLcVerdictOff + EMF_MAX_MODELS * sizeof(float);
     static constexpr size_t kLcHostBytes = kLcGateOff + EMF_MAX_MODELS * sizeof(int32_t);
 
     // ---- tracking (SURVEY f-1) ----
     void trackModels(int first, int count);    // LM-ICP of table slots [first, first + count)
-    int trackChunk = 8;                        // iterations per convergence poll (0: never poll)
     int trackPredicted[2] = {0, 0};            // iterations the camera / object stage took last frame
-    int trackWindow = 4;                       // launches kept ahead of the device's progress report (0: poll in chunks); 2 ... 6 measured: 4 leaves a stage 3 idle launches instead of 5
-    uint32_t* trackWatch = nullptr;            // pinned host words the step kernel reports to
-    uint32_t* trackWatchDev = nullptr;         // ... as the device addresses them
+    int trackWindow = sw.trackWindow;          // launches kept ahead of the device's progress report (0: poll in chunks; set to 0 when trackWatch cannot be allocated); 2 ... 6 measured: 4 leaves a stage 3 idle launches instead of 5
     uint32_t trackStageTag = 0;                // upper half of the words of the stage in flight (trackModels)
     DeviceBuffer trackStates;                  // emf_track_state_t[EMF_MAX_MODELS]
     DeviceBuffer trackScratch;                 // one emf_hip_trackScratchBytes block per table slot (grown on demand)
-    emf_track_state_t* trackStatesHost = nullptr;  // pinned mirror
     std::map<int, TrackResult> trackResults;   // by model id
     DeviceImage<float, 3> points;
     DeviceImage<float> raylengths, bg_raylengths, associationNorm, bg_associationWeights,
@@ -563,12 +555,10 @@ private:
     DeviceBuffer visCounts;      // int32 per object
     DeviceBuffer hitKeys;        // u64 W x H, multi-GPU composite merge
     DeviceBuffer raycastStatsDev;  // 2 x u64
-    int32_t* visCountsHost = nullptr;  // pinned
     bool statsOn = false;
 
     // device-resident model table for the batched launches (slot 0 = background)
-    bool batched = true;            // false: per-volume launches (see EMFusion.cpp)
-    bool forceLegacy = false;
+    bool batched = true;            // false: per-volume launches (sw.perVolume or materialised gradients, see EMFusion.cpp)
     bool sharded = false;           // objects sharded over ranks: use the cross-rank exchanges
     DeviceBuffer modelTable;        // 2 x emf_model_t[EMF_MAX_MODELS]: [1] has the background's two copies swapped
     int tableSel = 0;               // which of the two describes the background's current front copy
@@ -594,26 +584,21 @@ private:
     // Background kept twice (TSDF::enableDoubleBuffer): its integration runs out of place on `aux`,
     // concurrently with the raycast of the same frame, and the copies are flipped at the join.
     // EMF_BG_OVERLAP=0 keeps the reference's sequence raycast -> integrate (A/B measurements).
-    bool bgOverlap = true;
     bool bgInFlight = false;        // the out-of-place integration of this frame has been enqueued
     bool bgBackStale = false;       // the background was integrated in place: the copies differ
     // the background's sweep yields to the raycast when both have workgroups to place (its long chains should
     // start as early as they can): lowest queue priority for the second stream (+1 % frames/s)
-    Stream aux{streamPriority("EMF_PRIO_AUX", -1)};
+    Stream aux{sw.prioAux};
     // Raycast far bounds (emf_hip_raycastFarBounds): per model and 8x8-pixel cell, where a march may
     // stop because nothing can be hit any more.  EMF_FAR_BOUNDS=0 marches every ray to the end.
-    int marchLanes = 1;         // lanes per background ray (EMF_MARCH_ROWS, read by the constructor)
-    bool useFootprints = true;  // objects are marched only where their volume box projects to
-    bool useFarBounds = true;
     DeviceBuffer farBounds;       // two halves, written alternately (computeFarBounds)
     int farSel = 0;
     float* farBoundsHalf() const { return farBounds.as<float>() + static_cast<size_t>(farSel) * (farBounds.bytes() / 2 / sizeof(float)); }
     int forkFrame = -2;           // frame whose integrateBackgroundAsync forked `aux` (and re-recorded `main`'s event)
     bool farBoundsReady = false;
-    bool earlyFarBounds = true;    // far bounds wait for the previous raycast only (EMF_EARLY_FAR_BOUNDS=0: for `main`)
     bool peerFused = false;     // sharded over a direct peer-write transport: exchanges fused into the path's kernels
     int bandRowsPending = 0;    // background raycast bands waiting for the raycast's exchange
-    Stream lists{streamPriority("EMF_PRIO_LISTS", -1)};  // relevant-tile list rebuilds: behind the integrations, waited for by the next far bounds
+    Stream lists{sw.prioLists};  // relevant-tile list rebuilds: behind the integrations, waited for by the next far bounds
     bool bgListPending = false; // the background was forked; its list rebuild is not enqueued yet
     bool bgPrepared = false;    // bgCullScratch's counter and the next dirtyNext map are already cleared
     void rebuildBackgroundList();
@@ -638,14 +623,24 @@ private:
     DeviceBuffer colorStatsDev;     // u64: voxels coloured
     DeviceBuffer rgbUpload;         // device copy of RGBD::rgb (processFrame(const RGBD&))
     void integrateColor(const std::vector<emf_pose_t>& oc);
-    int32_t* visibleHost = nullptr; // pinned mirror of visCounts for visibleObjects()
     bool visPending = false;
     std::vector<int32_t> visIds;    // object ids in the order of the pending counts
 
     KernelTimers ktimers;
     bool timingsOn = false;
     FrameTimings timings;
-    std::vector<hipEvent_t> stamps;
+
+    // ---- pinned host memory and events: declared last, released first (see the top of the member list) ----
+    UploadSlot uploadSlots[2];
+    PinnedBuffer visCountsHost;    // int32 per object: the counts the host gate waits for
+    PinnedBuffer visibleHost;      // int32 per object: mirror of visCounts for visibleObjects(), written by the gate kernels
+    PinnedBuffer trackStatesHost;  // emf_track_state_t[EMF_MAX_MODELS]: mirror of trackStates
+    PinnedBuffer trackWatch;       // mapped: the words the step kernel reports to while the stream runs (empty: chunked polls)
+    PinnedBuffer lifecycleHost;    // kLcHostBytes, layout above
+    PinnedBuffer viewPosesHost;    // EMF_MAX_MODELS viewer -> volume poses
+    PinnedBuffer meshHost;         // EMF_MAX_MODELS emf_model_t, then the counts and bases read back
+    PinnedBuffer meshStage;        // staging of the meshes' bytes (grown when needed)
+    std::vector<Event> stamps;     // the frame timings' marks on `main`
 };
 
 }  // namespace emf

@@ -240,12 +240,10 @@ std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
     for (Mesh& m : out) m.colored = colorOn;
     if (n == 0) return out;
     if (n > EMF_MAX_MODELS) throw HipError("EMFusion::extractMeshes: " + std::to_string(n) + " models", EMF_E_LIMIT);
-    if (!meshHost)
-        hipCheck(hipHostMalloc(&meshHost, EMF_MAX_MODELS * sizeof(emf_model_t) + EMF_MAX_MODELS * sizeof(emf_mesh_counts_t) +
-                                              2 * (EMF_MAX_MODELS + 1) * sizeof(uint64_t),
-                               hipHostMallocDefault),
-                 "hipHostMalloc(mesh table)");
-    emf_model_t* table = static_cast<emf_model_t*>(meshHost);
+    if (meshHost.empty())
+        meshHost = PinnedBuffer(EMF_MAX_MODELS * sizeof(emf_model_t) + EMF_MAX_MODELS * sizeof(emf_mesh_counts_t) +
+                                2 * (EMF_MAX_MODELS + 1) * sizeof(uint64_t));
+    emf_model_t* table = meshHost.as<emf_model_t>();
     auto* counts = reinterpret_cast<emf_mesh_counts_t*>(table + EMF_MAX_MODELS);
     auto* bases = reinterpret_cast<uint64_t*>(counts + EMF_MAX_MODELS);
     std::vector<int32_t> res(3 * ids.size());
@@ -291,14 +289,8 @@ std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
     emfCheck(emf_hip_meshEmitBatched(meshTableDev.as<emf_model_t>(), res.data(), n, meshScratch.data(), vDev, nDev, tDev,
                                      main.abi()),
              "meshEmitBatched");
-    if (meshStageBytes < 2 * vb + tb) {
-        if (meshStage) hipCheck(hipHostFree(meshStage), "hipHostFree(mesh staging)");
-        meshStage = nullptr;
-        meshStageBytes = 0;
-        hipCheck(hipHostMalloc(&meshStage, 2 * vb + tb, hipHostMallocDefault), "hipHostMalloc(mesh staging)");
-        meshStageBytes = 2 * vb + tb;
-    }
-    float* vHost = static_cast<float*>(meshStage);
+    meshStage.grow(2 * vb + tb);
+    float* vHost = meshStage.as<float>();
     float* nHost = vHost + 3 * nv;
     int32_t* tHost = reinterpret_cast<int32_t*>(nHost + 3 * nv);
     hipCheck(hipMemcpyAsync(vHost, vDev, vb, hipMemcpyDeviceToHost, main.get()), "mesh vertices D2H");

@@ -66,7 +66,7 @@ void EMFusion::ensureLifecycleBuffers() {
     verdictDev = DeviceBuffer(EMF_MAX_MODELS * sizeof(float));
     lifecycleMsg = DeviceBuffer(4 * sizeof(float));
     static_assert(EMF_MAX_MODELS * sizeof(emf_mask_mass_t) >= 513 * sizeof(uint32_t), "the larger of the two uses");
-    hipCheck(hipHostMalloc(&lifecycleHost, kLcHostBytes, hipHostMallocDefault), "hipHostMalloc");
+    lifecycleHost = PinnedBuffer(kLcHostBytes);
 }
 
 emf_point_stats_t EMFusion::maskedStats(const emf_image_t& mask, const Affine3f& frame) {
@@ -76,11 +76,11 @@ emf_point_stats_t EMFusion::maskedStats(const emf_image_t& mask, const Affine3f&
                                       statsScratch.data(), statsDev.as<emf_point_stats_t>(),
                                       main.abi()),
              "maskedPointStats");
-    hipCheck(hipMemcpyAsync(lifecycleHost, statsDev.data(), sizeof(emf_point_stats_t),
+    hipCheck(hipMemcpyAsync(lifecycleHost.data(), statsDev.data(), sizeof(emf_point_stats_t),
                             hipMemcpyDeviceToHost, main.get()),
              "hipMemcpyAsync");
     main.waitForCompletion();
-    return *static_cast<emf_point_stats_t*>(lifecycleHost);
+    return *lifecycleHost.as<emf_point_stats_t>();
 }
 
 float EMFusion::volumeIOU(const ObjTSDF& obj, const Vec3f& p10, const Vec3f& p90) const {
@@ -125,7 +125,7 @@ int EMFusion::initNewObjVolume(const emf_image_t& mask) {
         if (blocked) hipCheck(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lifecycleMsg.data()), 0x3f800000, 1, main.get()),
                               "hipMemsetD32Async");
         comm->allReduceSumF32(lifecycleMsg.as<float>(), 4, main);
-        float* h = reinterpret_cast<float*>(static_cast<char*>(lifecycleHost) + kLcVerdictOff);
+        float* h = reinterpret_cast<float*>(lifecycleHost.as<char>() + kLcVerdictOff);
         hipCheck(hipMemcpyAsync(h, lifecycleMsg.data(), 4 * sizeof(float), hipMemcpyDeviceToHost, main.get()),
                  "hipMemcpyAsync");
         main.waitForCompletion();
@@ -156,11 +156,11 @@ int EMFusion::matchSegmentation(const emf_image_t& mask, float& match_iou) {
     ensureLifecycleBuffers();
     const emf_image_t seg = modelSegmentation.view();
     emfCheck(emf_hip_maskOverlap(&mask, &seg, overlapDev.as<uint32_t>(), main.abi()), "maskOverlap");
-    hipCheck(hipMemcpyAsync(lifecycleHost, overlapDev.data(), 513 * sizeof(uint32_t),
+    hipCheck(hipMemcpyAsync(lifecycleHost.data(), overlapDev.data(), 513 * sizeof(uint32_t),
                             hipMemcpyDeviceToHost, main.get()),
              "hipMemcpyAsync");
     main.waitForCompletion();
-    const uint32_t* c = static_cast<const uint32_t*>(lifecycleHost);
+    const uint32_t* c = lifecycleHost.as<const uint32_t>();
     int match_id = -1;
     for (const int id : allIds) {  // (every rank: the joint segmentation and visible set cover all objects)
         if (!vis_objs.count(id) || id > 255) continue;
@@ -185,11 +185,11 @@ std::map<int, emf_image_t> EMFusion::initOrMatchObjs(std::vector<emf_image_t>& s
     const emf_image_t modelSeg = modelSegmentation.view();
     auto overlapCounts = [&](const emf_image_t& seg) -> const uint32_t* {
         emfCheck(emf_hip_maskOverlap(&seg, &modelSeg, overlapDev.as<uint32_t>(), main.abi()), "maskOverlap");
-        hipCheck(hipMemcpyAsync(lifecycleHost, overlapDev.data(), 513 * sizeof(uint32_t),
+        hipCheck(hipMemcpyAsync(lifecycleHost.data(), overlapDev.data(), 513 * sizeof(uint32_t),
                                 hipMemcpyDeviceToHost, main.get()),
                  "hipMemcpyAsync");
         main.waitForCompletion();
-        return static_cast<const uint32_t*>(lifecycleHost);
+        return lifecycleHost.as<const uint32_t>();
     };
     // ---- matchSegmentation over all masks (EMFusion.cpp:417-444) ----
     for (size_t i = 0; i < segs.size(); ++i) {
@@ -232,11 +232,11 @@ std::map<int, emf_image_t> EMFusion::initOrMatchObjs(std::vector<emf_image_t>& s
             emfCheck(emf_hip_carveMask(&segs[i], &modelSeg, id, it == matches.end() ? nullptr : &it->second,
                                        overlapDev.as<uint32_t>(), main.abi()),
                      "carveMask");
-            hipCheck(hipMemcpyAsync(lifecycleHost, overlapDev.data(), 2 * sizeof(uint32_t),
+            hipCheck(hipMemcpyAsync(lifecycleHost.data(), overlapDev.data(), 2 * sizeof(uint32_t),
                                     hipMemcpyDeviceToHost, main.get()),
                      "hipMemcpyAsync");
             main.waitForCompletion();
-            const uint32_t* c = static_cast<const uint32_t*>(lifecycleHost);
+            const uint32_t* c = lifecycleHost.as<const uint32_t>();
             // more than half of the mask belonged to an existing object: no new volume from it
             if (static_cast<float>(c[1]) / static_cast<float>(c[0]) < .5f)
                 hipCheck(hipMemset2DAsync(segs[i].data, segs[i].pitch, 0, static_cast<size_t>(segs[i].width),
@@ -282,11 +282,11 @@ Vec3f EMFusion::updateObj(ObjTSDF& obj, const emf_image_t& mask) {
                                        obj.getVoxelSize(), statsScratch.data(),
                                        statsDev.as<emf_point_stats_t>(), main.abi()),
              "objectExtentStats");
-    hipCheck(hipMemcpyAsync(lifecycleHost, statsDev.data(), sizeof(emf_point_stats_t),
+    hipCheck(hipMemcpyAsync(lifecycleHost.data(), statsDev.data(), sizeof(emf_point_stats_t),
                             hipMemcpyDeviceToHost, main.get()),
              "hipMemcpyAsync");
     main.waitForCompletion();
-    const emf_point_stats_t s = *static_cast<emf_point_stats_t*>(lifecycleHost);
+    const emf_point_stats_t s = *lifecycleHost.as<emf_point_stats_t>();
     const Vec3f offset = obj.resize(Vec3f(s.p10[0], s.p10[1], s.p10[2]),
                                     Vec3f(s.p90[0], s.p90[1], s.p90[2]), params.volPad, main);
     // the pose may have moved with the volume centre (EMFusion.cpp:858-860)
@@ -310,7 +310,7 @@ Vec3f EMFusion::updateObject(int id, const emf_image_t& mask) {
     }
     if (sharded) {  // every rank returns the owner's shift: ONE 16-byte broadcast from the owner
         ensureLifecycleBuffers();
-        float* h = reinterpret_cast<float*>(static_cast<char*>(lifecycleHost) + kLcVerdictOff);
+        float* h = reinterpret_cast<float*>(lifecycleHost.as<char>() + kLcVerdictOff);
         if (ownsObject(id)) {
             h[0] = offset[0];
             h[1] = offset[1];
@@ -379,13 +379,13 @@ std::vector<int> EMFusion::cleanUpObjs(bool maskFrame, const std::map<int, emf_i
                                                         massDev.as<emf_mask_mass_t>(), nullptr, 0, nullptr, nullptr,
                                                         nullptr, 0.f, main.abi()),
                      "maskAssociationMassBatched");
-            hipCheck(hipMemcpyAsync(lifecycleHost, massDev.data(), nobj * sizeof(emf_mask_mass_t), hipMemcpyDeviceToHost,
+            hipCheck(hipMemcpyAsync(lifecycleHost.data(), massDev.data(), nobj * sizeof(emf_mask_mass_t), hipMemcpyDeviceToHost,
                                     main.get()),
                      "hipMemcpyAsync(mask masses)");
         }
         main.waitForCompletion();
         refreshVisibleFromDevice();  // the host copy of vis_objs decides (the stream is idle: no further wait)
-        const emf_mask_mass_t* const massHost = static_cast<const emf_mask_mass_t*>(lifecycleHost);
+        const emf_mask_mass_t* const massHost = lifecycleHost.as<const emf_mask_mass_t>();
         std::set<int> spurious;
         k = 0;
         for (const auto& obj : objects) {
@@ -411,7 +411,7 @@ std::vector<int> EMFusion::cleanUpObjs(bool maskFrame, const std::map<int, emf_i
     if (nall == 0) return deleted;
     if (!batched) {
         // the per-volume composite decides visibility on the host and leaves the device gate alone: make it current
-        int32_t* gate = reinterpret_cast<int32_t*>(static_cast<char*>(lifecycleHost) + kLcGateOff);
+        int32_t* gate = reinterpret_cast<int32_t*>(lifecycleHost.as<char>() + kLcGateOff);
         gate[0] = 1;
         k = 1;
         for (const auto& obj : objects) gate[k++] = vis_objs.count(obj.getID()) ? 1 : 0;
@@ -425,7 +425,7 @@ std::vector<int> EMFusion::cleanUpObjs(bool maskFrame, const std::map<int, emf_i
                                                 params.assocThresh, main.abi()),
              "maskAssociationMassBatched");
     comm->allReduceSumF32(verdictDev.as<float>(), static_cast<size_t>(nslots), main);
-    float* verdict = reinterpret_cast<float*>(static_cast<char*>(lifecycleHost) + kLcVerdictOff);
+    float* verdict = reinterpret_cast<float*>(lifecycleHost.as<char>() + kLcVerdictOff);
     hipCheck(hipMemcpyAsync(verdict, verdictDev.data(), nall * sizeof(float), hipMemcpyDeviceToHost, main.get()),
              "hipMemcpyAsync(verdicts)");
     main.waitForCompletion();

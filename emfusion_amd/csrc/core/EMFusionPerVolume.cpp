@@ -96,7 +96,7 @@ void EMFusion::integratePerVolume() {
     forkVolumeStreams();
     const bool grads = gradMode == TSDF::Gradients::Materialized;
     const emf_image_t il = invLambda.view();
-    const emf_image_t* ilp = useLambdaTable ? &il : nullptr;
+    const emf_image_t* ilp = sw.useLambdaTable ? &il : nullptr;
     {
         auto kt = ktimers.scope(KernelTimers::Integrate,
                                 static_cast<double>(background.voxels()), streamOf(0));

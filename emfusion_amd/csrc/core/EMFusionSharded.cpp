@@ -94,7 +94,7 @@ void EMFusion::compositeAcrossRanks(bool deviceGate) {
         bandRowsPending = 0;
         emfCheck(emf_hip_visibilityFlagsMirror(visCounts.as<int32_t>(), nall, nlocal + 1, countIndex.data(),
                                                params.visibilityThresh, visibleDev.as<int32_t>(),
-                                               deviceGate ? visibleHost : visCountsHost, main.abi()),
+                                               (deviceGate ? visibleHost : visCountsHost).as<int32_t>(), main.abi()),
                  "visibilityFlagsMirror");
         visCountsClear = true;
     } else {

@@ -65,20 +65,15 @@ void EMFusion::trackModels(int first, int count) {
     }
     if (trackStates.empty()) {
         trackStates = DeviceBuffer(sizeof(emf_track_state_t) * EMF_MAX_MODELS);
-        hipCheck(hipHostMalloc(reinterpret_cast<void**>(&trackStatesHost),
-                               sizeof(emf_track_state_t) * EMF_MAX_MODELS, hipHostMallocDefault),
-                 "hipHostMalloc");
+        trackStatesHost = PinnedBuffer(sizeof(emf_track_state_t) * EMF_MAX_MODELS);
         // progress words the step kernel writes while the stream runs (emf_hip_trackStep)
-        if (trackWindow > 0 &&
-            (hipHostMalloc(reinterpret_cast<void**>(&trackWatch), kTrackFinalOffset + sizeof(emf_track_state_t) * EMF_MAX_BATCH,
-                           hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
-             hipHostGetDevicePointer(reinterpret_cast<void**>(&trackWatchDev), trackWatch, 0) != hipSuccess)) {
-            (void)hipGetLastError();  // no device-visible host memory here: poll in chunks instead
-            if (trackWatch) (void)hipHostFree(trackWatch);
-            trackWatch = trackWatchDev = nullptr;
-            trackWindow = 0;
+        if (trackWindow > 0) {
+            trackWatch = PinnedBuffer::tryAllocate(kTrackFinalOffset + sizeof(emf_track_state_t) * EMF_MAX_BATCH,
+                                                   hipHostMallocCoherent | hipHostMallocMapped);
+            if (trackWatch.empty()) trackWindow = 0;  // no device-visible host memory here: poll in chunks instead
         }
     }
+    emf_track_state_t* const statesHost = trackStatesHost.as<emf_track_state_t>();
     std::vector<emf_pose_t> co;
     posesCO(co);
     for (int m = first; m < first + count; ++m) {  // prepareTracking: re-orthonormalised rel_pose_CO
@@ -106,12 +101,13 @@ void EMFusion::trackModels(int first, int count) {
             // stream runs -- how far it is and which models are done (LM converges in 20-60 of the
             // 100 iterations, differently in every frame).  The launches already enqueued when the
             // last model finishes return at once (~2 us each); the states are read back once.
-            volatile uint32_t* watch = trackWatch;
+            volatile uint32_t* watch = trackWatch.as<uint32_t>();
             for (int i = 0; i <= count; ++i) watch[i] = 0u;
             const emf_track_state_t* const finalHost =
-                reinterpret_cast<const emf_track_state_t*>(reinterpret_cast<const char*>(trackWatch) + kTrackFinalOffset);
+                reinterpret_cast<const emf_track_state_t*>(trackWatch.as<const char>() + kTrackFinalOffset);
+            uint32_t* const watchDev = static_cast<uint32_t*>(trackWatch.devicePtr());  // ... as the device addresses them
             emf_track_state_t* const finalDev =
-                reinterpret_cast<emf_track_state_t*>(reinterpret_cast<char*>(trackWatchDev) + kTrackFinalOffset);
+                reinterpret_cast<emf_track_state_t*>(reinterpret_cast<char*>(watchDev) + kTrackFinalOffset);
             const int maxLaunches = 2 * params.maxTrackingIter + 4;  // (every step a speculation miss)
             const auto t0 = std::chrono::steady_clock::now();
             int launch = 0;
@@ -131,7 +127,7 @@ void EMFusion::trackModels(int first, int count) {
                 for (int m = 0; m < count && all; ++m) all = done(m);
                 if (all) break;
                 emfCheck(emf_hip_trackStep(currentTable() + first, states, count, &pv, &tp, scratch, per, launch,
-                                           params.maxTrackingIter, trackWatchDev, tag | static_cast<uint32_t>(launch + 1),
+                                           params.maxTrackingIter, watchDev, tag | static_cast<uint32_t>(launch + 1),
                                            finalDev, main.abi()),
                          "trackStep");
             }
@@ -145,18 +141,18 @@ void EMFusion::trackModels(int first, int count) {
                 // every model's state arrived in front of its word: no copy command, no wait for the stream (the launches
                 // still queued pass the states on and return)
                 std::atomic_thread_fence(std::memory_order_acquire);
-                std::memcpy(trackStatesHost + first, finalHost, sizeof(emf_track_state_t) * count);
+                std::memcpy(statesHost + first, finalHost, sizeof(emf_track_state_t) * count);
             } else {  // (the launch budget ran out first)
-                hipCheck(hipMemcpyAsync(trackStatesHost + first, states, sizeof(emf_track_state_t) * count,
+                hipCheck(hipMemcpyAsync(statesHost + first, states, sizeof(emf_track_state_t) * count,
                                         hipMemcpyDeviceToHost, main.get()),
                          "hipMemcpyAsync");
                 main.waitForCompletion();
             }
-            if (debugEnv("EMF_TRACK_LOG")) {  // diagnosis: launches against judged steps
+            if (sw.trackLog) {  // diagnosis: launches against judged steps
                 int it = 0, acc = 0;
                 for (int m = first; m < first + count; ++m) {
-                    it = std::max(it, trackStatesHost[m].iterations);
-                    acc = std::max(acc, trackStatesHost[m].accepted);
+                    it = std::max(it, statesHost[m].iterations);
+                    acc = std::max(acc, statesHost[m].accepted);
                 }
                 std::fprintf(stderr, "track stage first %d count %d: launches %d, most steps %d, most accepted %d\n", first, count,
                              launch, it, acc);
@@ -170,18 +166,18 @@ void EMFusion::trackModels(int first, int count) {
         // back with the poll.
         // The first chunk is as long as the stage was in the last frame (+8): an idle launch costs
         // ~2 us, a poll ~50.
-        const int chunk = trackChunk > 0 ? trackChunk : params.maxTrackingIter;
+        const int chunk = sw.trackChunk > 0 ? sw.trackChunk : params.maxTrackingIter;
         int& predicted = trackPredicted[first == 0 ? 0 : 1];
         int taken = 0;
         // diagnosis (scripts/track_verdict_sequences.py): one line per poll and model, every chunk as long as asked
-        static const bool logVerdicts = debugEnv("EMF_TRACK_LOG") != nullptr;
+        const bool logVerdicts = sw.trackLog;
         for (int done = 0; done < params.maxTrackingIter;) {
-            const int want = done == 0 && predicted > 0 && trackChunk > 0 && !logVerdicts ? std::max(chunk, predicted + 8) : chunk;
+            const int want = done == 0 && predicted > 0 && sw.trackChunk > 0 && !logVerdicts ? std::max(chunk, predicted + 8) : chunk;
             const int n = std::min(want, params.maxTrackingIter - done);
             emfCheck(emf_hip_trackIterate(currentTable() + first, states, count, &pv, &tp, scratch, per, n,
                                           main.abi()),
                      "trackIterate");
-            hipCheck(hipMemcpyAsync(trackStatesHost + first, states,
+            hipCheck(hipMemcpyAsync(statesHost + first, states,
                                     sizeof(emf_track_state_t) * count, hipMemcpyDeviceToHost,
                                     main.get()),
                      "hipMemcpyAsync");
@@ -189,7 +185,7 @@ void EMFusion::trackModels(int first, int count) {
             bool all = true;
             done = params.maxTrackingIter;
             for (int m = first; m < first + count; ++m) {
-                const emf_track_state_t& st = trackStatesHost[m];
+                const emf_track_state_t& st = statesHost[m];
                 if (logVerdicts)
                     std::fprintf(stderr, "track model %d: iterations %d accepted %d rho %g mu %g nu %g converged %d\n", m,
                                  st.iterations, st.accepted, st.rho, st.mu, st.nu, st.converged);
@@ -206,7 +202,7 @@ void EMFusion::trackModels(int first, int count) {
 
 void EMFusion::trackCamera() {
     trackModels(0, 1);
-    const emf_track_state_t& st = trackStatesHost[0];
+    const emf_track_state_t& st = trackStatesHost.as<emf_track_state_t>()[0];
     const Affine3f rel(Matx33f(st.R), Vec3f(st.t[0], st.t[1], st.t[2]));
     pose = background.getPose() * rel;  // TSDF::syncTrack (TSDF.cpp:339-345)
     TrackResult r;
@@ -222,7 +218,7 @@ void EMFusion::trackObjects() {
     trackModels(1, n);
     int m = 1;
     for (auto& obj : objects) {
-        const emf_track_state_t& st = trackStatesHost[m++];
+        const emf_track_state_t& st = trackStatesHost.as<emf_track_state_t>()[m++];
         const Affine3f rel(Matx33f(st.R), Vec3f(st.t[0], st.t[1], st.t[2]));
         obj.setPose(pose * rel.inv());  // ObjTSDF::syncTrack (ObjTSDF.cpp:228-235)
         TrackResult r;

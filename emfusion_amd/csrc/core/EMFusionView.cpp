@@ -43,24 +43,22 @@ void EMFusion::renderView(const Affine3f& viewerPose, const float K[9], Size siz
 
     const int n = static_cast<int>(modelsHost.size());
     if (n < 1 || n > EMF_MAX_MODELS) throw HipError("EMFusion::renderView: " + std::to_string(n) + " models", EMF_E_LIMIT);
-    if (!viewPosesHost)
-        hipCheck(hipHostMalloc(reinterpret_cast<void**>(&viewPosesHost), sizeof(emf_pose_t) * EMF_MAX_MODELS,
-                               hipHostMallocDefault),
-                 "hipHostMalloc(view poses)");
+    if (viewPosesHost.empty()) viewPosesHost = PinnedBuffer(sizeof(emf_pose_t) * EMF_MAX_MODELS);
+    emf_pose_t* const posesHost = viewPosesHost.as<emf_pose_t>();
     if (viewPosesDev.empty()) viewPosesDev = DeviceBuffer(sizeof(emf_pose_t) * EMF_MAX_MODELS);
     // viewer -> volume in table order (reference TSDF.cpp:141,162 with the viewer as the camera)
     std::vector<int32_t> ids;
     uint8_t hide[32] = {};
-    viewPosesHost[0] = toPose(background.getPose().inv() * viewerPose);
+    posesHost[0] = toPose(background.getPose().inv() * viewerPose);
     int slot = 1;
     for (const auto& obj : objects) {
-        viewPosesHost[slot++] = toPose(obj.getPose().inv() * viewerPose);
+        posesHost[slot++] = toPose(obj.getPose().inv() * viewerPose);
         ids.push_back(obj.getID());
         if (ignorePerson && isPerson(obj) && obj.getID() >= 1 && obj.getID() <= 255)  // render(): EMFusion.cpp:139-150
             hide[obj.getID() >> 3] |= static_cast<uint8_t>(1u << (obj.getID() & 7));
     }
     if (slot != n) throw HipError("EMFusion::renderView: model table out of step with the object list", EMF_E_ARG);
-    hipCheck(hipMemcpyAsync(viewPosesDev.data(), viewPosesHost, sizeof(emf_pose_t) * n, hipMemcpyHostToDevice,
+    hipCheck(hipMemcpyAsync(viewPosesDev.data(), posesHost, sizeof(emf_pose_t) * n, hipMemcpyHostToDevice,
                             main.get()),
              "view poses upload");
     // the table that describes the volumes' current copies: the batched path's (after the ping-pong), or one built

@@ -2,22 +2,12 @@
 
 namespace emf {
 
-KernelTimers::~KernelTimers() {
-    for (auto& p : pairs) {
-        if (p.start) (void)hipEventDestroy(p.start);
-        if (p.stop) (void)hipEventDestroy(p.stop);
-    }
-}
-
 void KernelTimers::enable(size_t maxLaunches) {
+    pairs.clear();
+    pairs.resize(maxLaunches);
     for (auto& p : pairs) {
-        if (p.start) (void)hipEventDestroy(p.start);
-        if (p.stop) (void)hipEventDestroy(p.stop);
-    }
-    pairs.assign(maxLaunches, Pair{});
-    for (auto& p : pairs) {
-        hipCheck(hipEventCreate(&p.start), "hipEventCreate");
-        hipCheck(hipEventCreate(&p.stop), "hipEventCreate");
+        p.start = Event(hipEventDefault);
+        p.stop = Event(hipEventDefault);
     }
     used = dropped = 0;
     seen.fill(0u);
@@ -37,11 +27,11 @@ KernelTimers::Scope::Scope(KernelTimers* t, Kind k, double units, hipStream_t s)
     Pair& p = t->pairs[slot];
     p.kind = k;
     p.units = units;
-    hipCheck(hipEventRecord(p.start, stream), "hipEventRecord");
+    p.start.record(stream);
 }
 
 KernelTimers::Scope::~Scope() {
-    if (slot >= 0) (void)hipEventRecord(timers->pairs[slot].stop, stream);
+    if (slot >= 0) (void)timers->pairs[slot].stop.tryRecord(stream);
 }
 
 std::array<KernelTimers::Summary, KernelTimers::kNumKinds> KernelTimers::collect() const {
@@ -49,7 +39,7 @@ std::array<KernelTimers::Summary, KernelTimers::kNumKinds> KernelTimers::collect
     for (size_t i = 0; i < used; ++i) {
         const Pair& p = pairs[i];
         float ms = 0.f;
-        hipCheck(hipEventElapsedTime(&ms, p.start, p.stop), "hipEventElapsedTime");
+        hipCheck(hipEventElapsedTime(&ms, p.start.get(), p.stop.get()), "hipEventElapsedTime");
         Summary& s = out[p.kind];
         ++s.launches;
         s.total_ms += ms;

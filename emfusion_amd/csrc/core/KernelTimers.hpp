@@ -35,7 +35,6 @@ public:
         double units = 0.0;  // voxels (volume sweeps) or pixels (image kernels), summed
     };
 
-    ~KernelTimers();
     /** Allocate `maxLaunches` event pairs and start recording; 0 disables. */
     void enable(size_t maxLaunches);
     bool enabled() const { return !pairs.empty(); }
@@ -72,7 +71,7 @@ public:
 
 private:
     struct Pair {
-        hipEvent_t start = nullptr, stop = nullptr;
+        Event start, stop;
         Kind kind = Points;
         double units = 0.0;
     };

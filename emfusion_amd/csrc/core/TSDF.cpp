@@ -1,8 +1,9 @@
 // TSDF.cpp -- emf::TSDF over the emf_hip_* C ABI (see TSDF.hpp).
 #include "TSDF.hpp"
 
+#include "Switches.hpp"
+
 #include <algorithm>
-#include <cstdlib>
 #include <atomic>
 #include <mutex>
 
@@ -31,7 +32,9 @@ TSDF::TSDF(Vec3i _volumeRes, float _voxelSize, float _truncdist, Affine3f _pose,
 namespace {
 std::atomic<bool> g_deferReciprocal{false};
 std::mutex g_rcpSlotMutex;
-unsigned long long* g_rcpSlots = nullptr;  // pinned host words the verdicts are COPIED to, allocated once, never freed
+// Process-lifetime slots: pinned host words the verdicts are COPIED to, allocated once, never freed -- they live as long
+// as the process, by design, hence the raw hipHostMalloc below instead of a PinnedBuffer
+unsigned long long* g_rcpSlots = nullptr;
 unsigned long long* g_rcpSlotsDev = nullptr;  // the device counters the check adds into (no atomics across PCIe)
 constexpr int kRcpSlots = 256;
 bool g_rcpSlotUsed[kRcpSlots] = {};
@@ -76,26 +79,22 @@ void give_rcp_slot(int i) {
 
 struct TSDF::PendingReciprocal {
     int slot = -1;
-    hipEvent_t done = nullptr;
+    Event done;
 };
 void TSDF::PendingDeleter::operator()(PendingReciprocal* p) const {
     if (!p) return;
     // the check may still be running and will write its slot: wait for THAT kernel (rare: a volume
     // destroyed within milliseconds of its creation), then hand the slot back
-    if (p->done) {
-        (void)hipEventSynchronize(p->done);
-        (void)hipEventDestroy(p->done);
-    }
+    if (!p->done.empty()) (void)hipEventSynchronize(p->done.get());
     if (p->slot >= 0) give_rcp_slot(p->slot);
-    delete p;
+    delete p;  // (and the event with it)
 }
 
 void TSDF::deferReciprocalChecks(bool on) { g_deferReciprocal = on; }
 
 void TSDF::obtainReciprocal() {
     rcpVoxel = 0.f;
-    const char* vr = std::getenv("EMF_VOXEL_RCP");
-    if (vr && vr[0] == '0') return;
+    if (!switchValue(Switch::voxelRcp)) return;
     const int known = emf_hip_voxelReciprocalCached(voxelSize, &rcpVoxel);
     if (known == EMF_OK) return;            // this size has been checked in this process
     if (known != EMF_E_NOTREADY) return;    // outside the checked range: the march divides
@@ -104,12 +103,16 @@ void TSDF::obtainReciprocal() {
         if (slot >= 0) {
             std::unique_ptr<PendingReciprocal, PendingDeleter> p(new PendingReciprocal);
             p->slot = slot;
-            if (hipEventCreateWithFlags(&p->done, hipEventDisableTiming) == hipSuccess &&
+            try {
+                p->done = Event(hipEventDisableTiming);
+            } catch (const HipError&) {  // no event: the check below runs now instead
+            }
+            if (!p->done.empty() &&
                 emf_hip_voxelReciprocalBegin(voxelSize, g_rcpSlotsDev + slot,
                                              reinterpret_cast<emf_stream_t>(g_rcpStream)) == EMF_OK &&
                 hipMemcpyAsync(g_rcpSlots + slot, g_rcpSlotsDev + slot, sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                g_rcpStream) == hipSuccess &&
-                hipEventRecord(p->done, g_rcpStream) == hipSuccess) {
+                p->done.tryRecord(g_rcpStream)) {
                 pendingRcp = std::move(p);
                 return;  // rcpVoxel stays 0 until pollReciprocal() sees the verdict
             }
@@ -121,7 +124,7 @@ void TSDF::obtainReciprocal() {
 
 bool TSDF::pollReciprocal() {
     if (!pendingRcp) return false;
-    if (hipEventQuery(pendingRcp->done) != hipSuccess) {
+    if (hipEventQuery(pendingRcp->done.get()) != hipSuccess) {
         (void)hipGetLastError();  // not ready
         return false;
     }
@@ -132,7 +135,7 @@ bool TSDF::pollReciprocal() {
 }
 
 void TSDF::settleReciprocal() {
-    if (pendingRcp && pendingRcp->done) (void)hipEventSynchronize(pendingRcp->done);
+    if (pendingRcp && !pendingRcp->done.empty()) (void)hipEventSynchronize(pendingRcp->done.get());
 }
 
 void TSDF::reset(const Affine3f& _pose) {
@@ -290,8 +293,7 @@ void TSDF::computeAssociation(const emf_image_t& points, const Affine3f& cam_pos
 }
 
 int TSDF::brickFlagMode() {  // (read on every call: an instance picks the switch up when it is constructed)
-    const char* e = debugEnv("EMF_BRICK_FLAGS");
-    return e ? (e[0] == '2' ? 2 : (e[0] == '1' ? 1 : 0)) : 0;
+    return static_cast<int>(switchValue(Switch::brickFlags));
 }
 
 void TSDF::describe(emf_model_t& m) const {
@@ -328,8 +330,7 @@ void TSDF::describe(emf_model_t& m) const {
                           ? relevantTiles.as<uint32_t>()
                           : nullptr;
     // (kept valid together with the sign maps: the same launches maintain both)
-    const char* ut = std::getenv("EMF_UNSEEN_TILES");
-    const bool useUnseen = !(ut && ut[0] == '0');
+    const bool useUnseen = switchValue(Switch::unseenTiles) != 0;
     m.unseenTiles = useUnseen && m.signMaps && !unseenTiles.empty() ? unseenTiles.as<uint8_t>() : nullptr;
     m.pad_ = 0;
 }

@@ -154,6 +154,15 @@ int emf_fusion_trim_pool(uint64_t* bytes_freed) {
     });
 }
 
+int emf_fusion_describe_switches(char* json, size_t capacity) {
+    REQ(json);
+    return guarded([&] {
+        const std::string s = emf::describeSwitches();
+        if (s.size() + 1 > capacity) throw HipError("emf_fusion_describe_switches: buffer too small", EMF_E_ARG);
+        std::memcpy(json, s.c_str(), s.size() + 1);
+    });
+}
+
 int emf_fusion_reset(emf_fusion_t* h) {
     REQ(h);
     return guarded([&] { h->impl->reset(); });

@@ -1,6 +1,8 @@
 // types.cpp -- RAII wrappers over HIP streams / device memory used by the host classes.
 #include "types.hpp"
 
+#include "Switches.hpp"
+
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -110,10 +112,7 @@ uint64_t this_thread() {
 }
 
 size_t pool_cap() {  // bytes the pool may hold before a release really frees (EMF_POOL_MIB, default 16 GiB of 288)
-    static const size_t cap = [] {
-        const char* e = std::getenv("EMF_POOL_MIB");
-        return (e ? static_cast<size_t>(std::strtoull(e, nullptr, 10)) : size_t(16384)) << 20;
-    }();
+    static const size_t cap = static_cast<size_t>(switchValue(Switch::poolMiB)) << 20;
     return cap;
 }
 // fence `b` on every live stream of thread `me` and on the null stream (clears and uploads of constructors run
@@ -277,31 +276,26 @@ Stream::Stream(int priority) : owned_(true) {
     register_stream(s_);
 }
 Stream::Stream(hipStream_t s) : s_(s), owned_(false) {}
-Stream::~Stream() {
-    if (ev_) (void)hipEventDestroy(ev_);
+Stream::~Stream() { release(); }
+void Stream::release() {
+    ev_ = Event();  // in front of the stream it was recorded on
     if (owned_ && s_) {
         unregister_stream(s_);
         (void)hipStreamDestroy(s_);
     }
 }
-Stream::Stream(Stream&& o) noexcept : s_(o.s_), owned_(o.owned_), ev_(o.ev_) {
+Stream::Stream(Stream&& o) noexcept : s_(o.s_), owned_(o.owned_), ev_(std::move(o.ev_)) {
     o.s_ = nullptr;
     o.owned_ = false;
-    o.ev_ = nullptr;
 }
 Stream& Stream::operator=(Stream&& o) noexcept {
     if (this != &o) {
-        if (ev_) (void)hipEventDestroy(ev_);
-        if (owned_ && s_) {
-            unregister_stream(s_);
-            (void)hipStreamDestroy(s_);
-        }
+        release();
         s_ = o.s_;
         owned_ = o.owned_;
-        ev_ = o.ev_;
+        ev_ = std::move(o.ev_);
         o.s_ = nullptr;
         o.owned_ = false;
-        o.ev_ = nullptr;
     }
     return *this;
 }
@@ -311,11 +305,11 @@ Stream& Stream::Null() {
 }
 void Stream::waitForCompletion() const { hipCheck(hipStreamSynchronize(s_), "hipStreamSynchronize"); }
 void Stream::record() {
-    if (!ev_) hipCheck(hipEventCreateWithFlags(&ev_, hipEventDisableTiming), "hipEventCreate");
-    hipCheck(hipEventRecord(ev_, s_), "hipEventRecord");
+    if (ev_.empty()) ev_ = Event(hipEventDisableTiming);
+    ev_.record(s_);
 }
 void Stream::waitOn(const Stream& other) {
-    if (other.ev_) hipCheck(hipStreamWaitEvent(s_, other.ev_, 0), "hipStreamWaitEvent");
+    if (!other.ev_.empty()) hipCheck(hipStreamWaitEvent(s_, other.ev_.get(), 0), "hipStreamWaitEvent");
 }
 void Stream::waitFor(Stream& other) {
     other.record();
@@ -370,19 +364,84 @@ void DeviceBuffer::upload(const void* host, const Stream& s) const {
                      "hipMemcpyAsync H2D");
 }
 
-// A switch that only -DEMF_DEBUG_SWITCHES builds read (types.hpp debugEnv) is set in the environment of a product build:
-// one line on stderr per variable and process, then ignored.
-const char* demotedSwitchSet(const char* name) {
-    if (!std::getenv(name)) return nullptr;
-    static std::mutex m;
-    static std::vector<std::string> warned;
-    std::lock_guard<std::mutex> lock(m);
-    for (const auto& w : warned)
-        if (w == name) return nullptr;
-    warned.emplace_back(name);
-    std::fprintf(stderr, "emfusion_amd: %s is set, but this build ignores it (a switch whose A/B is on record as lost; "
-                         "`make -C emfusion_amd/csrc dbg` builds libemf_fusion_dbg.so, which reads it)\n", name);
-    return nullptr;
+// ---- events and pinned host memory ------------------------------------------------------------------------------
+// (the only calls of hipEventCreate* / hipEventDestroy / hipHostMalloc / hipHostFree / hipHostGetDevicePointer under
+// core/, next to the pool's fences above and the process-lifetime reciprocal slots of TSDF.cpp)
+Event::Event(unsigned flags) { hipCheck(hipEventCreateWithFlags(&e_, flags), "hipEventCreate"); }
+Event::~Event() {
+    if (e_) (void)hipEventDestroy(e_);
+}
+Event::Event(Event&& o) noexcept : e_(o.e_), recorded_(o.recorded_) {
+    o.e_ = nullptr;
+    o.recorded_ = false;
+}
+Event& Event::operator=(Event&& o) noexcept {
+    if (this != &o) {
+        if (e_) (void)hipEventDestroy(e_);
+        e_ = o.e_;
+        recorded_ = o.recorded_;
+        o.e_ = nullptr;
+        o.recorded_ = false;
+    }
+    return *this;
+}
+void Event::record(hipStream_t s) {
+    hipCheck(hipEventRecord(e_, s), "hipEventRecord");
+    recorded_ = true;
+}
+bool Event::tryRecord(hipStream_t s) noexcept {
+    if (hipEventRecord(e_, s) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    recorded_ = true;
+    return true;
+}
+
+hipError_t PinnedBuffer::allocate(PinnedBuffer& b, size_t bytes, unsigned flags) noexcept {
+    void* p = nullptr;
+    void* dev = nullptr;
+    hipError_t e = hipHostMalloc(&p, bytes, flags);
+    if (e == hipSuccess && (flags & hipHostMallocMapped)) {
+        e = hipHostGetDevicePointer(&dev, p, 0);
+        if (e != hipSuccess) (void)hipHostFree(p);
+    }
+    if (e != hipSuccess) return e;
+    b.p_ = p;
+    b.dev_ = dev;
+    b.n_ = bytes;
+    b.flags_ = flags;
+    return hipSuccess;
+}
+PinnedBuffer::PinnedBuffer(size_t bytes, unsigned flags) { hipCheck(allocate(*this, bytes, flags), "hipHostMalloc"); }
+PinnedBuffer PinnedBuffer::tryAllocate(size_t bytes, unsigned flags) noexcept {
+    PinnedBuffer b;
+    if (allocate(b, bytes, flags) != hipSuccess) (void)hipGetLastError();
+    return b;
+}
+PinnedBuffer::~PinnedBuffer() {
+    if (p_) (void)hipHostFree(p_);
+}
+PinnedBuffer::PinnedBuffer(PinnedBuffer&& o) noexcept : p_(o.p_), dev_(o.dev_), n_(o.n_), flags_(o.flags_) {
+    o.p_ = o.dev_ = nullptr;
+    o.n_ = 0;
+}
+PinnedBuffer& PinnedBuffer::operator=(PinnedBuffer&& o) noexcept {
+    if (this != &o) {
+        if (p_) (void)hipHostFree(p_);
+        p_ = o.p_;
+        dev_ = o.dev_;
+        n_ = o.n_;
+        flags_ = o.flags_;
+        o.p_ = o.dev_ = nullptr;
+        o.n_ = 0;
+    }
+    return *this;
+}
+void PinnedBuffer::grow(size_t bytes) {
+    if (n_ >= bytes) return;
+    PinnedBuffer bigger(bytes, flags_);  // throws with *this untouched
+    *this = std::move(bigger);
 }
 
 }  // namespace emf

@@ -10,7 +10,6 @@
 #include <array>
 #include <cstddef>
 #include <cstdint>
-#include <cstdlib>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -135,6 +134,28 @@ void hipCheck(hipError_t e, const char* what);
 // throws HipError carrying emf_hip_last_error_string() when an emf_hip_* call fails
 void emfCheck(int rc, const char* what);
 
+// A HIP event: RAII over hipEventCreateWithFlags / hipEventDestroy.  Move-only, empty by default and created by its
+// constructor; members that are created at first use say `if (ev.empty()) ev = Event(flags)`.
+class Event {
+public:
+    Event() = default;
+    explicit Event(unsigned flags);  // hipEventDefault (timing) or hipEventDisableTiming; throws HipError
+    ~Event();
+    Event(Event&& o) noexcept;
+    Event& operator=(Event&& o) noexcept;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    hipEvent_t get() const { return e_; }
+    bool empty() const { return e_ == nullptr; }
+    void record(hipStream_t s);               // throws HipError
+    bool tryRecord(hipStream_t s) noexcept;   // false (HIP error cleared) if it could not be recorded
+    bool recorded() const { return recorded_; }  // record() has succeeded at least once: there is something to wait for
+
+private:
+    hipEvent_t e_ = nullptr;
+    bool recorded_ = false;
+};
+
 // Stand-in for cv::cuda::Stream: owns (or borrows) a hipStream_t.
 class Stream {
 public:
@@ -158,31 +179,45 @@ public:
     void waitFor(Stream& other);
 
 private:
+    void release();
     hipStream_t s_ = nullptr;
     bool owned_ = false;
-    hipEvent_t ev_ = nullptr;  // lazily created by record()
+    Event ev_;  // created by the first record()
 };
 
-/** Environment switches whose A/B is on record as lost ("switchboard"): read only by builds with
- *  -DEMF_DEBUG_SWITCHES (make EXTRA_HOST=-DEMF_DEBUG_SWITCHES); the product build ignores them. */
-const char* demotedSwitchSet(const char* name);  // types.cpp: warns once per variable that is set, returns nullptr
-inline const char* debugEnv(const char* name) {
-#ifdef EMF_DEBUG_SWITCHES
-    return std::getenv(name);
-#else
-    return demotedSwitchSet(name);  // a script that still sets it A/Bs two identical configurations: say so, once
-#endif
-}
+// Pinned (page-locked) host memory: RAII over hipHostMalloc / hipHostFree.  Move-only, empty by default; members that
+// are allocated at first use say `if (buf.empty()) buf = PinnedBuffer(bytes)`.
+class PinnedBuffer {
+public:
+    PinnedBuffer() = default;
+    explicit PinnedBuffer(size_t bytes, unsigned flags = hipHostMallocDefault);  // throws HipError
+    // the same, for callers with a fall-back: a failed allocation clears the HIP error and gives an empty buffer
+    static PinnedBuffer tryAllocate(size_t bytes, unsigned flags) noexcept;
+    ~PinnedBuffer();
+    PinnedBuffer(PinnedBuffer&& o) noexcept;
+    PinnedBuffer& operator=(PinnedBuffer&& o) noexcept;
+    PinnedBuffer(const PinnedBuffer&) = delete;
+    PinnedBuffer& operator=(const PinnedBuffer&) = delete;
+    void* data() const { return p_; }
+    template <typename T>
+    T* as() const {
+        return static_cast<T*>(p_);
+    }
+    size_t bytes() const { return n_; }
+    bool empty() const { return p_ == nullptr; }
+    // the address kernels use for a buffer allocated with hipHostMallocMapped (resolved at allocation); else nullptr
+    void* devicePtr() const { return dev_; }
+    // at least `bytes` (same flags), contents not kept: the new block is allocated BEFORE the old one is released,
+    // so a failure throws with the old block still owned and usable
+    void grow(size_t bytes);
 
-/** Queue priority of one of the frame's streams: `dflt` unless the environment variable `env` says "high" / "+1",
- *  "normal" / "0" or "low" / "-1" (A/B measurements of the stream-to-queue mapping). */
-inline int streamPriority(const char* env, int dflt) {
-    const char* v = debugEnv(env);
-    if (!v || !v[0]) return dflt;
-    if (v[0] == 'h' || v[0] == '+' || v[0] == '1') return 1;
-    if (v[0] == 'l' || v[0] == '-') return -1;
-    return 0;
-}
+private:
+    static hipError_t allocate(PinnedBuffer& b, size_t bytes, unsigned flags) noexcept;
+    void* p_ = nullptr;
+    void* dev_ = nullptr;
+    size_t n_ = 0;
+    unsigned flags_ = hipHostMallocDefault;
+};
 
 // Continuous device buffer (what cv::cuda::createContinuous gives): RAII over hipMalloc + a pool.
 class DeviceBuffer {

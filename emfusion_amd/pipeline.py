@@ -7,6 +7,7 @@ pointers.  Fails loudly if the library is missing -- there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import json
 import os
 import re
 from pathlib import Path
@@ -95,6 +96,7 @@ def load() -> C.CDLL:
         "emf_fusion_destroy": [vp],
         "emf_fusion_reset": [vp],
         "emf_fusion_trim_pool": [C.POINTER(C.c_uint64)],
+        "emf_fusion_describe_switches": [C.c_char_p, C.c_size_t],
         "emf_fusion_process_rgbd": [vp, fp, C.c_int32, C.c_int32],
         "emf_fusion_use_preproc_masks": [vp, C.c_char_p],
         "emf_fusion_set_color": [vp, C.c_int],
@@ -992,6 +994,15 @@ def trim_pool() -> int:
     n = C.c_uint64(0)
     _check("emf_fusion_trim_pool", load().emf_fusion_trim_pool(C.byref(n)))
     return int(n.value)
+
+
+def describe_switches() -> dict:
+    """The run-time switches of the host classes as the loaded library parses them from the current environment:
+    {NAME: {"kind", "type", "rule", "default", "read", "value", "path", "doc", "field"}} (csrc/core/Switches.hpp).
+    Needs no GPU.  Raises FusionError (EMF_E_ARG) where a value is refused, as a Fusion constructed now would."""
+    buf = C.create_string_buffer(1 << 14)
+    _check("emf_fusion_describe_switches", load().emf_fusion_describe_switches(buf, len(buf)))
+    return {row.pop("name"): row for row in json.loads(buf.value.decode())["switches"]}
 
 
 def write_volume(filename, volume: np.ndarray, voxel_size: float):

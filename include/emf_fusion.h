@@ -85,6 +85,13 @@ int emf_fusion_reset(emf_fusion_t* h);
  * hipFree (which synchronises the device; EMF_POOL_MIB caps the pool, default 16 GiB).  This really frees them
  * -- it waits for the device -- and reports how many bytes were held (bytes_freed may be NULL). */
 int emf_fusion_trim_pool(uint64_t* bytes_freed);
+/* The run-time switches (environment variables) of the host classes -- the table of emfusion_amd/csrc/core/Switches.hpp
+ * -- as parsed from the CURRENT environment, as JSON: {"debug_switches": bool, "switches": [{"name", "field", "kind"
+ * ("product" | "demoted"), "type", "rule", "default", "read" (does this build read the variable?), "value" (what an
+ * instance constructed now would use), "path", "doc"}, ...]}.  Needs no device and no handle.  A value the table refuses
+ * (EMF_MARCH_ROWS other than 1, 2, 4) gives EMF_E_ARG and the constructor's message; a demoted variable that is set
+ * gives the product build's one line on stderr, once per process.  EMF_E_ARG if `capacity` is too small (16 KiB is enough). */
+int emf_fusion_describe_switches(char* json, size_t capacity);
 /* emf::EMFusion::processFrame(const RGBD&) -- the reference's entry (EMFusion.h:66): a HOST depth image in metres
  * (width x height floats), uploaded, bilateral-filtered and run through the schedule with the frame inputs set by the
  * emf_fusion_set_* / queue_* calls; with emf_fusion_use_preproc_masks the instance masks of every mask frame come

@@ -454,7 +454,9 @@ int emf_hip_estepBatchedFromDepth(const emf_model_t* models_dev, const emf_pose_
  * voxel size with the checked reciprocal (emf_hip_voxelReciprocal), same results.
  *   bgBandRow0, bgBandRows: multi-GPU split of the REPLICATED background (table slot 0): only the
  *   image rows [bgBandRow0, bgBandRow0 + bgBandRows) of slot 0 are marched and written, the others
- *   are left untouched for an all-gather of the ranks' bands (multiples of 16; 0, 0 = all rows). */
+ *   are left untouched for an all-gather of the ranks' bands (multiples of 16; 0, 0 = all rows).
+ * This entry point always marches one lane per background ray: it does NOT read EMF_MARCH_ROWS (emf::EMFusion's
+ * constructor does, and passes the lanes on).  A caller that wants 2 or 4 lanes uses emf_hip_raycastBatchedLanes. */
 int emf_hip_raycastBatched(const emf_model_t* models_dev, const emf_pose_t* poseCO_host,
                            const int32_t* res_host, int nmodels, int width, int height,
                            const float K[9], int useBrickFlags, int bgBandRow0, int bgBandRows,

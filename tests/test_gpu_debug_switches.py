@@ -1,5 +1,4 @@
-"""The demoted A/B switches (core/types.hpp debugEnv: EMF_FUSE_POINTS, EMF_FUSE_VISIBILITY, EMF_EARLY_FAR_BOUNDS,
-EMF_OBJ_CULL, EMF_FAR_SCAN, EMF_RAY_FOOTPRINTS, EMF_BRICK_FLAGS, the tracking driver's EMF_TRACK_WINDOW / EMF_TRACK_CHUNK)
+"""The demoted A/B switches (the rows of kind Demoted in core/Switches.hpp; pipeline.describe_switches() lists them)
 are no-ops in the product build, but the paths behind them stay compiled in (several are functional fall-backs: the
 un-fused composite serves the per-volume path, the chunked tracking loop serves hosts without device-visible memory).
 libemf_fusion_dbg.so is the same source with -DEMF_DEBUG_SWITCHES (make -C emfusion_amd/csrc dbg); here the switch-pair

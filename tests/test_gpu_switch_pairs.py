@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 # every run-time switch of the product build that selects an execution path (round 5: the switches whose A/B is on
 # record as lost -- ray footprints, brick flags, the objects' far-bound scan, un-fused points / visibility, late far
-# bounds, ... -- are read by -DEMF_DEBUG_SWITCHES builds only, core/types.hpp debugEnv)
+# bounds, ... -- are read by -DEMF_DEBUG_SWITCHES builds only: the "demoted" rows of core/Switches.hpp)
 SWITCHES = [("EMF_PER_VOLUME", "1"), ("EMF_INT_CULL", "0"), ("EMF_LAMBDA_TABLE", "0"), ("EMF_VOXEL_RCP", "0"),
             ("EMF_BG_OVERLAP", "0"), ("EMF_FAR_BOUNDS", "0"), ("EMF_UNSEEN_TILES", "0"), ("EMF_DEEP_TILES", "0"),
             ("EMF_MARCH_ROWS", "2"), ("EMF_MARCH_ROWS", "4")]
