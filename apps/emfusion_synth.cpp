@@ -4,12 +4,15 @@
 //
 //   emfusion_synth [--frames N] [--objects K] [--bg-res R] [--obj-res R] [--width W --height H]
 //                  [--materialize-gradients] [--autonomous] [--out DIR] [--export-frame-meshes] [--3d-vis]
+//                  [--weld-meshes]
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
 //                  [--bg-res R] [--bg-voxel M] [--obj-res R] [--volumes] --out DIR
 //   emfusion_synth --dir BASE/ [--colordir colour] [--depthdir depth] [--intrinsics fx fy cx cy] ... --out DIR
 // --export-frame-meshes (needs --out): the reference's per-frame mesh export (apps/EM-Fusion.cpp:240-242) -- every
 // frame ends by meshing the background and every shown object, and writeResults writes them as
 // DIR/frame_meshes/bg/%04d.ply and DIR/frame_meshes/<id>/%04d.ply.
+// --weld-meshes: every mesh written (mesh_*.ply of the live models, frame_meshes/) is welded by grid edge on the device:
+// one vertex per edge instead of one per cube that touches it, the triangles re-indexed (EMFusion::setMeshWeld).
 // --3d-vis (needs --out): the reference's 3D view (apps/EM-Fusion.cpp:118-131) -- every frame is rendered (render())
 // together with the whole map seen from a viewer 1 m behind the world origin at 1024 x 768, and writeResults writes
 // those views as DIR/mesh_vis_out/%04d.png.  --3d-vis-eye x y z --3d-vis-target x y z place the viewer instead
@@ -78,6 +81,8 @@ static void set3dView(emf::EMFusion& emf, const emf::Params& params, const View3
 
 // The reference's main loop on a dataset (apps/EM-Fusion.cpp:100-156): a TUM sequence (`--sequence`, TUMRGBDReader) or a
 // Co-Fusion style directory (`--dir`, ImageReader: ColorNNNN.png + DepthNNNN.exr), as apps/EM-Fusion.cpp:118-131 chooses
+static bool weldMeshes = false;  // --weld-meshes
+
 static int runSequence(const std::string& seq, bool cofusion, const std::string& colordir, const std::string& depthdir,
                        const float* intrinsics, const std::string& configFile, const std::string& masks,
                        const std::string& outDir, int frames, int bgRes, float bgVoxel, int objRes, int maskFrames,
@@ -133,6 +138,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     }
     emf::EMFusion emf(params);
     if (color) emf.enableColor(true);                 // --color: the sequence's colour images go into the models
+    emf.setMeshWeld(weldMeshes);
     std::vector<uint8_t> rgb;
     if (!masks.empty()) emf.usePreprocMasks(masks);   // apps/EM-Fusion.cpp:115
     emf.setupOutput(frameMeshes, volumes);            // apps/EM-Fusion.cpp:112
@@ -214,6 +220,7 @@ int main(int argc, char** argv) {
         else if (a == "--out" && i + 1 < argc) outDir = argv[++i];
         else if (a == "--3d-vis") view3d.on = true;
         else if (a == "--export-frame-meshes") frameMeshes = true;
+        else if (a == "--weld-meshes") weldMeshes = true;
         else if (a == "--color") color = true;
         else if ((a == "--3d-vis-eye" || a == "--3d-vis-target") && i + 3 < argc) {
             float* dst = a == "--3d-vis-eye" ? view3d.eye : view3d.target;
@@ -273,6 +280,7 @@ int main(int argc, char** argv) {
         std::vector<emf::DeviceImage<uint8_t>> maskDev;
         for (int k = 0; k < objects; ++k) maskDev.emplace_back(params.frameSize);
         emf.enableTimings(true);
+        emf.setMeshWeld(weldMeshes);
         if (!outDir.empty()) emf.setupOutput(frameMeshes, true);  // apps/EM-Fusion.cpp:112
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);

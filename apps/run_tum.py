@@ -44,6 +44,9 @@ def main():
                     help="the reference's per-frame mesh export: the background and every shown object meshed at the "
                          "end of every frame, written to OUT/frame_meshes/bg/%%04d.ply and OUT/frame_meshes/<id>/ "
                          "(needs --out)")
+    ap.add_argument("--weld-meshes", dest="weld_meshes", action="store_true",
+                    help="weld every mesh written (mesh_*.ply of the live models, frame_meshes/) by grid edge on the "
+                         "device: one vertex per edge instead of one per cube that touches it")
     ap.add_argument("--color", action="store_true",
                     help="fuse the sequence's colour images into per-voxel colour: mesh_*.ply (and frame meshes, volume "
                          "dumps) carry colours")
@@ -86,6 +89,7 @@ def main():
     fus = pipeline.Fusion(prm, None)
     if args.color:
         fus.enable_color()
+    fus.set_mesh_weld(args.weld_meshes)
     fus.set_ignore_person(args.ignore_person)
     fus.set_preprocess(True)
     fus.set_cleanup(True)

@@ -160,6 +160,15 @@ SIGNATURES = {
     "emf_hip_renderPhongColor": [_IMG, _IMG, _IMG, _F9, _IMG, _STREAM],
     "emf_hip_meshColors": [_FP, _FP, _FP, _FP, _I3, _FP, _FP, _STREAM],
     "emf_hip_meshColorsBatched": [_FP, _FP, _I3, C.c_int, _FP, _FP, _STREAM],
+    "emf_hip_meshEdgeKeys": [_FP, _FP, _FP, _I3, _FP, _FP, _STREAM],
+    "emf_hip_meshEdgeKeysBatched": [_FP, _I3, C.c_int, _FP, _FP, _STREAM],
+    "emf_hip_meshWeldScratchBytes": [C.c_uint64],
+    "emf_hip_meshWeldCount": [_FP, C.c_uint64, _FP, _FP, _STREAM],
+    "emf_hip_meshWeldCountBatched": [_FP, C.c_uint64, _FP, C.c_int, _FP, _FP, _FP, _STREAM],
+    "emf_hip_meshWeldStatus": [_FP, C.c_uint64, _STREAM],
+    "emf_hip_meshWeldEmit": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _STREAM],
+    "emf_hip_meshWeldEmitBatched": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, C.c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
+                                    _FP, _STREAM],
 }
 
 
@@ -257,6 +266,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.emf_hip_pointStatsScratchBytes.restype = C.c_size_t
     lib.emf_hip_meshScratchBytes.restype = C.c_size_t
     lib.emf_hip_meshScratchBytesBatched.restype = C.c_size_t
+    lib.emf_hip_meshWeldScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateCullScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateDirtyMapBytes.restype = C.c_size_t
     lib.emf_hip_signMapBytes.restype = C.c_size_t

@@ -283,7 +283,15 @@ public:
      * holds the frame.
      */
     void setDepthBroadcastRoot(int root) { depthRoot = root; }
-    /** getMesh() of the background (id 0) or of an object held by this rank. */
+    /**
+     * Welded meshes (include/emf_hip.h "Welded meshes"; new behaviour, off by default): getMesh(id), extractMeshes()
+     * and everything writeResults() and the per-frame export write become one vertex per grid edge -- the first soup
+     * copy's bits -- with the soup's triangles re-indexed, welded on the device before the copies to the host.  An
+     * output form only: TSDF::getMesh() stays the soup wherever the life cycle uses it (the extent statistics, the
+     * last mesh kept of a deleted object), so no tracking, life-cycle or clean-up decision depends on the switch.
+     */
+    void setMeshWeld(bool on) { meshWeld = on; }
+    /** getMesh() of the background (id 0) or of an object held by this rank (welded with setMeshWeld). */
     Mesh getMesh(int id);
     /**
      * getMesh() of each listed model (0 = background, else a live object id), in list order, in one pass over the
@@ -505,6 +513,10 @@ private:
     std::map<int, std::map<int, Mesh>> frame_obj_meshes;   // id -> frame -> mesh
     void storeFrameMeshes();                               // the end of a frame with exp_frame_meshes
     DeviceBuffer meshTableDev, meshCountsDev, meshScratch, meshArena;  // extractMeshes' pooled buffers
+    bool meshWeld = false;                                 // setMeshWeld
+    DeviceBuffer meshWeldScratch;                          // keys, welded counts / bases and the weld's scratch
+    void extractWelded(const std::vector<int>& ids, const std::vector<int32_t>& res, uint64_t nv, uint64_t nt,
+                       std::vector<Mesh>& out);
     bool expVols = false;                                  // setupOutput: keep / dump volumes too
     // ---- per-frame debug images of the reference's saveOutput mode, kept as encoded PNGs ----
     bool saveOutput = false;

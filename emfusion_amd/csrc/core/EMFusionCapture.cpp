@@ -289,6 +289,10 @@ std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
     emfCheck(emf_hip_meshEmitBatched(meshTableDev.as<emf_model_t>(), res.data(), n, meshScratch.data(), vDev, nDev, tDev,
                                      main.abi()),
              "meshEmitBatched");
+    if (meshWeld) {  // the welded form of the same soup: welded on the device, then only the welded arrays travel
+        extractWelded(ids, res, nv, nt, out);
+        return out;
+    }
     meshStage.grow(2 * vb + tb);
     float* vHost = meshStage.as<float>();
     float* nHost = vHost + 3 * nv;
@@ -322,6 +326,97 @@ std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
     return out;
 }
 
+// extractMeshes' tail with setMeshWeld(true) (include/emf_hip.h "Welded meshes").  The soup of the n models lies in
+// meshArena ([vertices][normals][triangles], as the emit wrote it) and the counting scratch is still valid: colours and
+// edge keys walk the surface chunks once more, the weld runs on the keys, and the welded vertex arrays land behind the
+// soup in the same arena (grown when needed; the soup is copied over, it is a quarter of what a frame's soup D2H was).
+void EMFusion::extractWelded(const std::vector<int>& ids, const std::vector<int32_t>& res, uint64_t nv, uint64_t nt,
+                             std::vector<Mesh>& out) {
+    const int n = static_cast<int>(ids.size());
+    auto* counts = reinterpret_cast<emf_mesh_counts_t*>(meshHost.as<emf_model_t>() + EMF_MAX_MODELS);
+    auto* bases = reinterpret_cast<uint64_t*>(counts + EMF_MAX_MODELS);
+    auto* basesDev = reinterpret_cast<uint64_t*>(meshCountsDev.as<emf_mesh_counts_t>() + EMF_MAX_MODELS);
+    const size_t vb = 3 * sizeof(float) * nv, tb = 4 * sizeof(int32_t) * std::max<uint64_t>(nt, 1);
+    const size_t weldBytes = emf_hip_meshWeldScratchBytes(nv);
+    if (weldBytes == 0) throw HipError("EMFusion::extractMeshes: " + std::to_string(nv) + " soup vertices", EMF_E_LIMIT);
+    // [keys u64 x nv][welded counts u32 x MAX][welded bases u64 x (MAX + 1)][weld scratch]
+    const size_t keyBytes = sizeof(uint64_t) * nv, cntBytes = sizeof(uint32_t) * EMF_MAX_MODELS,
+                 baseBytes = sizeof(uint64_t) * (EMF_MAX_MODELS + 1);
+    if (meshWeldScratch.bytes() < keyBytes + cntBytes + baseBytes + weldBytes)
+        meshWeldScratch = DeviceBuffer(keyBytes + cntBytes + baseBytes + weldBytes);
+    auto* keysDev = meshWeldScratch.as<uint64_t>();
+    auto* wBasesDev = keysDev + nv;
+    auto* wCountsDev = reinterpret_cast<uint32_t*>(wBasesDev + EMF_MAX_MODELS + 1);
+    void* weldScratch = reinterpret_cast<char*>(meshWeldScratch.data()) + keyBytes + baseBytes + cntBytes;
+    float* vDev = meshArena.as<float>();
+    float* nDev = vDev + 3 * nv;
+    int32_t* tDev = reinterpret_cast<int32_t*>(nDev + 3 * nv);
+    DeviceBuffer ptrsDev, cDev, wcDev;
+    if (colorOn) {
+        std::vector<uint16_t*> ptrs(n, nullptr);
+        for (int k = 0; k < n; ++k) ptrs[k] = ids[k] == 0 ? background.colorPtr() : getObject(ids[k])->colorPtr();
+        ptrsDev = DeviceBuffer(sizeof(uint16_t*) * n);
+        cDev = DeviceBuffer(3 * nv);
+        hipCheck(hipMemcpyAsync(ptrsDev.data(), ptrs.data(), sizeof(uint16_t*) * n, hipMemcpyHostToDevice, main.get()),
+                 "mesh colour table upload");
+        emfCheck(emf_hip_meshColorsBatched(meshTableDev.as<emf_model_t>(), ptrsDev.as<uint16_t*>(), res.data(), n,
+                                           meshScratch.data(), cDev.as<uint8_t>(), main.abi()),
+                 "meshColorsBatched");
+    }
+    emfCheck(emf_hip_meshEdgeKeysBatched(meshTableDev.as<emf_model_t>(), res.data(), n, meshScratch.data(), keysDev,
+                                         main.abi()),
+             "meshEdgeKeysBatched");
+    emfCheck(emf_hip_meshWeldCountBatched(keysDev, nv, basesDev, n, weldScratch, wCountsDev, wBasesDev, main.abi()),
+             "meshWeldCountBatched");
+    std::vector<uint32_t> wCounts(n);
+    std::vector<uint64_t> wBases(n + 1);
+    hipCheck(hipMemcpyAsync(wCounts.data(), wCountsDev, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, main.get()),
+             "welded counts D2H");
+    hipCheck(hipMemcpyAsync(wBases.data(), wBasesDev, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost, main.get()),
+             "welded bases D2H");
+    emfCheck(emf_hip_meshWeldStatus(weldScratch, nv, main.abi()), "meshWeld (table)");  // waits: the welded sizes
+    const uint64_t nw = wBases[n];
+    const size_t wvb = 3 * sizeof(float) * nw;
+    if (meshArena.bytes() < 2 * vb + tb + 2 * wvb) {  // grow, keeping the soup
+        DeviceBuffer grown(2 * vb + tb + 2 * wvb);
+        hipCheck(hipMemcpyAsync(grown.data(), meshArena.data(), 2 * vb + tb, hipMemcpyDeviceToDevice, main.get()),
+                 "mesh arena grow");
+        main.waitForCompletion();
+        meshArena = std::move(grown);
+        vDev = meshArena.as<float>();
+        nDev = vDev + 3 * nv;
+        tDev = reinterpret_cast<int32_t*>(nDev + 3 * nv);
+    }
+    float* wvDev = reinterpret_cast<float*>(reinterpret_cast<char*>(meshArena.data()) + 2 * vb + tb);
+    float* wnDev = wvDev + 3 * nw;
+    if (colorOn) wcDev = DeviceBuffer(3 * nw);
+    emfCheck(emf_hip_meshWeldEmitBatched(weldScratch, nv, nt, basesDev, wBasesDev, n, vDev, nDev,
+                                         colorOn ? cDev.as<uint8_t>() : nullptr, tDev, wvDev, wnDev,
+                                         colorOn ? wcDev.as<uint8_t>() : nullptr, tDev, main.abi()),
+             "meshWeldEmitBatched");
+    meshStage.grow(2 * wvb + tb);
+    float* vHost = meshStage.as<float>();
+    float* nHost = vHost + 3 * nw;
+    int32_t* tHost = reinterpret_cast<int32_t*>(nHost + 3 * nw);
+    hipCheck(hipMemcpyAsync(vHost, wvDev, wvb, hipMemcpyDeviceToHost, main.get()), "welded vertices D2H");
+    hipCheck(hipMemcpyAsync(nHost, wnDev, wvb, hipMemcpyDeviceToHost, main.get()), "welded normals D2H");
+    if (nt) hipCheck(hipMemcpyAsync(tHost, tDev, 4 * sizeof(int32_t) * nt, hipMemcpyDeviceToHost, main.get()), "welded triangles D2H");
+    std::vector<uint8_t> cHost;
+    if (colorOn) {
+        cHost.resize(3 * nw);
+        hipCheck(hipMemcpyAsync(cHost.data(), wcDev.data(), 3 * nw, hipMemcpyDeviceToHost, main.get()), "welded colours D2H");
+    }
+    main.waitForCompletion();
+    for (int k = 0; k < n; ++k) {  // model k's slice is its own welded mesh (local triangle indices)
+        const size_t v0 = wBases[k], t0 = bases[2 * k + 1];
+        Mesh& m = out[k];
+        m.cloud.assign(vHost + 3 * v0, vHost + 3 * (v0 + wCounts[k]));
+        m.normals.assign(nHost + 3 * v0, nHost + 3 * (v0 + wCounts[k]));
+        m.polygons.assign(tHost + 4 * t0, tHost + 4 * (t0 + counts[k].triangles));
+        if (!cHost.empty()) m.colors.assign(cHost.begin() + 3 * v0, cHost.begin() + 3 * (v0 + wCounts[k]));
+    }
+}
+
 // EMFusion.cpp:110-125 (exp_frame_meshes): the background and every live object not hidden by ignore_person, meshed
 // from the current table at the end of the frame and kept under the frame's number
 void EMFusion::storeFrameMeshes() {
@@ -335,9 +430,9 @@ void EMFusion::storeFrameMeshes() {
 
 Mesh EMFusion::getMesh(int id) {
     synchronize();
-    if (id == 0) return background.getMesh();
+    if (id == 0) return meshWeld ? background.getWeldedMesh() : background.getMesh();
     for (auto& o : objects)
-        if (o.getID() == id) return o.getMesh();
+        if (o.getID() == id) return meshWeld ? o.getWeldedMesh() : o.getMesh();
     throw HipError("EMFusion::getMesh: no object " + std::to_string(id) + " on this rank", EMF_E_ARG);
 }
 

@@ -158,6 +158,7 @@ int ObjTSDF::getClassID() const {
 }
 
 Mesh ObjTSDF::getMesh() { return extractMesh(fgVolMask.as<uint8_t>()); }
+Mesh ObjTSDF::getWeldedMesh() { return extractMesh(fgVolMask.as<uint8_t>(), true); }
 
 void ObjTSDF::describe(emf_model_t& m) const {
     TSDF::describe(m);

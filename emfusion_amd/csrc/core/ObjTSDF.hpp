@@ -67,6 +67,7 @@ public:
 
     /** Mesh of the foreground part only (reference ObjTSDF::getMesh, ObjTSDF.cpp:247-268). */
     Mesh getMesh() override;
+    Mesh getWeldedMesh() override;
 
     std::vector<float> getFgProbVol();
     std::vector<uint8_t> getFgVolMask();

@@ -336,9 +336,11 @@ void TSDF::describe(emf_model_t& m) const {
 }
 
 Mesh TSDF::getMesh() { return extractMesh(nullptr); }
+Mesh TSDF::getWeldedMesh() { return extractMesh(nullptr, true); }
 
-// count -> read back two numbers -> emit; the gradient volume is used when it is materialised
-Mesh TSDF::extractMesh(const uint8_t* fgVolMask) {
+// count -> read back two numbers -> emit; the gradient volume is used when it is materialised.  weld: keys, first
+// occurrences and ranks on the device, one more number read back, then the welded arrays are what is downloaded
+Mesh TSDF::extractMesh(const uint8_t* fgVolMask, bool weld) {
     hipCheck(hipDeviceSynchronize(), "hipDeviceSynchronize");
     Stream& s = Stream::Null();
     DeviceBuffer scratch(std::max<size_t>(emf_hip_meshScratchBytes(volumeRes.val), 8));
@@ -351,22 +353,49 @@ Mesh TSDF::extractMesh(const uint8_t* fgVolMask) {
     Mesh mesh;
     mesh.colored = !colorVol.empty();
     if (counts.vertices == 0) return mesh;
-    DeviceBuffer v(counts.vertices * 3 * sizeof(float)), n(counts.vertices * 3 * sizeof(float)),
-        t(std::max<size_t>(counts.triangles, 1) * 4 * sizeof(int32_t));
+    const size_t soup = counts.vertices;
+    DeviceBuffer v(soup * 3 * sizeof(float)), n(soup * 3 * sizeof(float)),
+        t(std::max<size_t>(counts.triangles, 1) * 4 * sizeof(int32_t)), c;
     emfCheck(emf_hip_meshEmit(tsdfVol.as<float>(), gradsPtr(), tsdfWeights.as<float>(), fgVolMask,
                               volumeRes.val, voxelSize, scratch.data(), v.as<float>(), n.as<float>(),
                               t.as<int32_t>(), s.abi()),
              "TSDF::getMesh");
-    mesh.cloud.resize(counts.vertices * 3);
-    mesh.normals.resize(counts.vertices * 3);
-    mesh.polygons.resize(static_cast<size_t>(counts.triangles) * 4);
-    v.download(mesh.cloud.data(), s);
-    n.download(mesh.normals.data(), s);
     if (!colorVol.empty()) {  // the same vertices, coloured
-        DeviceBuffer c(static_cast<size_t>(counts.vertices) * 3);
+        c = DeviceBuffer(soup * 3);
         emfCheck(emf_hip_meshColors(tsdfVol.as<float>(), tsdfWeights.as<float>(), fgVolMask, colorVol.as<uint16_t>(),
                                     volumeRes.val, scratch.data(), c.as<uint8_t>(), s.abi()),
                  "TSDF::getMesh (colours)");
+    }
+    if (weld) {
+        const size_t weldBytes = emf_hip_meshWeldScratchBytes(soup);
+        if (weldBytes == 0) throw HipError("TSDF::getWeldedMesh: " + std::to_string(soup) + " soup vertices", EMF_E_LIMIT);
+        DeviceBuffer keys(soup * sizeof(uint64_t)), weldScratch(weldBytes), weldedDev(sizeof(uint32_t));
+        emfCheck(emf_hip_meshEdgeKeys(tsdfVol.as<float>(), tsdfWeights.as<float>(), fgVolMask, volumeRes.val,
+                                      scratch.data(), keys.as<uint64_t>(), s.abi()),
+                 "TSDF::getWeldedMesh (keys)");
+        emfCheck(emf_hip_meshWeldCount(keys.as<uint64_t>(), soup, weldScratch.data(), weldedDev.as<uint32_t>(), s.abi()),
+                 "TSDF::getWeldedMesh (count)");
+        uint32_t welded = 0;
+        weldedDev.download(&welded, s);
+        emfCheck(emf_hip_meshWeldStatus(weldScratch.data(), soup, s.abi()), "TSDF::getWeldedMesh (table)");
+        DeviceBuffer wv(size_t(welded) * 3 * sizeof(float)), wn(size_t(welded) * 3 * sizeof(float)), wc;
+        if (!c.empty()) wc = DeviceBuffer(size_t(welded) * 3);
+        emfCheck(emf_hip_meshWeldEmit(weldScratch.data(), soup, counts.triangles, v.as<float>(), n.as<float>(),
+                                      c.empty() ? nullptr : c.as<uint8_t>(), t.as<int32_t>(), wv.as<float>(),
+                                      wn.as<float>(), wc.empty() ? nullptr : wc.as<uint8_t>(), t.as<int32_t>(), s.abi()),
+                 "TSDF::getWeldedMesh (emit)");
+        s.waitForCompletion();  // the scratch and the soup arrays go out of scope below
+        v = std::move(wv);
+        n = std::move(wn);
+        if (!c.empty()) c = std::move(wc);
+        counts.vertices = welded;
+    }
+    mesh.cloud.resize(size_t(counts.vertices) * 3);
+    mesh.normals.resize(size_t(counts.vertices) * 3);
+    mesh.polygons.resize(static_cast<size_t>(counts.triangles) * 4);
+    v.download(mesh.cloud.data(), s);
+    n.download(mesh.normals.data(), s);
+    if (!c.empty()) {
         mesh.colors.resize(static_cast<size_t>(counts.vertices) * 3);
         c.download(mesh.colors.data(), s);
     }

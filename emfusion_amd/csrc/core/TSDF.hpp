@@ -83,6 +83,12 @@ public:
      * (reference TSDF::getMesh, TSDF.cpp:356-373).  Synchronises.
      */
     virtual Mesh getMesh();
+    /**
+     * getMesh() welded by grid edge on the device (include/emf_hip.h "Welded meshes"): one vertex per edge -- the
+     * first copy's bits -- and the soup's triangles re-indexed.  An output form only: whatever the life cycle
+     * measures on a mesh (extent statistics count duplicates as the reference does) goes through getMesh().
+     */
+    virtual Mesh getWeldedMesh();
 
     /** Host copies in the reference layout, (Nz*Ny) rows x Nx cols (TSDF.cpp:398-408). */
     std::vector<float> getTSDF() const;
@@ -154,7 +160,7 @@ public:
     float reciprocal() const { return rcpVoxel; }
 
 protected:
-    Mesh extractMesh(const uint8_t* fgVolMask);
+    Mesh extractMesh(const uint8_t* fgVolMask, bool weld = false);
     TSDFParams params;
     Vec3i volumeRes;
     float voxelSize;

@@ -240,6 +240,11 @@ int emf_fusion_set_color(emf_fusion_t* h, int on) {
     return guarded([&] { h->impl->enableColor(on != 0); });
 }
 
+int emf_fusion_set_mesh_weld(emf_fusion_t* h, int on) {
+    REQ(h);
+    return guarded([&] { h->impl->setMeshWeld(on != 0); });
+}
+
 int emf_fusion_set_color_image(emf_fusion_t* h, const emf_image_t* rgb_dev) {
     REQ(h);
     REQ(rgb_dev);

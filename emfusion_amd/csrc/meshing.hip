@@ -21,6 +21,9 @@
 //   k_mesh_emit   a fixed grid walks list[]: classify the chunk again, scan inside the workgroup (wave
 //                 shuffles + LDS) on top of blockSums[g / 8] + the chunk totals before it, and write
 //                 vertices, normals and triangles where the reference puts them
+//   k_mesh_colors / k_mesh_keys  the emit's walk over list[] once more each (the same chunk_slot, hence the same vertex
+//                 slots): u8 x 3 vertex colours from a colour volume; the u64 grid-edge key per vertex that
+//                 mesh_weld.hip welds by (opt-in, the soup above is what it was)
 // A launch covers a TABLE of volumes (emf_hip_mesh*Batched; the level-1 entries are its one-volume case): model m
 // owns a contiguous range of counting workgroups (its own chunks-per-workgroup choice and XCD banding inside it),
 // of per-workgroup sums and of chunks; the scan restarts at every model and yields its counts and 64-bit bases in
@@ -616,6 +619,42 @@ __global__ __launch_bounds__(kMcBlock) void k_mesh_colors(const MeshArgs a, cons
     }
 }
 
+// ---- edge keys (new behaviour: include/emf_hip.h "Welded meshes"; the welding itself is mesh_weld.hip) ----------
+// The walk over the list of surface chunks a third time (chunk_slot again: the same vertex slots), writing per soup
+// vertex the u64 key of the grid edge it lies on: slot << 48 | 3 * linear(lower voxel) + axis.  The cube and the
+// edge bits are in registers here and the corner offsets are compile-time constants: no voxel is read beyond what
+// chunk_slot's classification reads.
+constexpr int kMeshKeySlotShift = 48;  // 3 * voxels of one volume stays below 2^41 (plan(): chunk ids in 31 bits)
+
+__device__ __forceinline__ void key_cube(const MeshSource& src, unsigned m, const Cube& q, unsigned edges,
+                                         unsigned vertBase, unsigned long long* keys) {
+    const I3 n = src.n;
+    const size_t sy = static_cast<size_t>(n.x), sz = sy * n.y;
+    unsigned k = 0;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) {
+        if (!((edges >> e) & 1u)) continue;
+        int ax, ay, az, bx, by, bz;
+        cube_corner(emf_mc_edge_corner[e][0], ax, ay, az);
+        cube_corner(emf_mc_edge_corner[e][1], bx, by, bz);
+        const int lx = ax < bx ? ax : bx, ly = ay < by ? ay : by, lz = az < bz ? az : bz;  // the lower voxel
+        const int axis = ax != bx ? 0 : (ay != by ? 1 : 2);
+        const unsigned long long lin = q.base + lx + ly * sy + lz * sz;
+        keys[vertBase + k] = (static_cast<unsigned long long>(m) << kMeshKeySlotShift) | (3ull * lin + axis);
+        ++k;
+    }
+}
+
+template <bool kTable>
+__global__ __launch_bounds__(kMcBlock) void k_mesh_keys(const MeshArgs a, unsigned long long* keys) {
+    __shared__ uint2 lds[8];
+    const unsigned todo = *a.listCount;
+    for (unsigned i = blockIdx.x; i < todo; i += gridDim.x) {
+        const ChunkSlot s = chunk_slot<kTable>(a, i, lds);
+        if (s.q.cls) key_cube(s.src, s.m, s.q, s.edges, s.vertBase, keys + a.bases[2 * s.m]);
+    }
+}
+
 // grid of one volume's counting pass: 8 XCDs x ceil(wpp / 8) columns x planes (see logical_block)
 unsigned launch_blocks(unsigned nblocks, unsigned wpp) {
     const unsigned band = (wpp + kXcds - 1) / kXcds, rows = (nblocks + wpp - 1) / wpp;
@@ -804,6 +843,28 @@ int emf_hip_meshColorsBatched(const emf_model_t* models_dev, uint16_t* const* co
     hipLaunchKernelGGL(k_mesh_colors<true>, dim3(nchunks < 4096u ? nchunks : 4096u), dim3(kMcBlock), 0,
                        as_stream(stream), a, ca);
     return launch_status("meshColorsBatched");
+}
+
+int emf_hip_meshEdgeKeys(const float* tsdf, const float* weights, const uint8_t* fgVolMask, const int32_t res[3],
+                         const void* scratch_dev, uint64_t* keys, emf_stream_t stream) {
+    MeshArgs a;
+    EMF_TRY(single(a, tsdf, weights, fgVolMask, nullptr, res, 1.f, const_cast<void*>(scratch_dev)));
+    EMF_REQUIRE_PTR(keys);
+    const unsigned nchunks = a.chunkBase[a.n];
+    hipLaunchKernelGGL(k_mesh_keys<false>, dim3(nchunks < 4096u ? nchunks : 4096u), dim3(kMcBlock), 0,
+                       as_stream(stream), a, reinterpret_cast<unsigned long long*>(keys));
+    return launch_status("meshEdgeKeys");
+}
+
+int emf_hip_meshEdgeKeysBatched(const emf_model_t* models_dev, const int32_t* res_host, int n, const void* scratch_dev,
+                                uint64_t* keys, emf_stream_t stream) {
+    MeshArgs a;
+    EMF_TRY(table(a, models_dev, res_host, n, const_cast<void*>(scratch_dev)));
+    EMF_REQUIRE_PTR(keys);
+    const unsigned nchunks = a.chunkBase[a.n];
+    hipLaunchKernelGGL(k_mesh_keys<true>, dim3(nchunks < 4096u ? nchunks : 4096u), dim3(kMcBlock), 0,
+                       as_stream(stream), a, reinterpret_cast<unsigned long long*>(keys));
+    return launch_status("meshEdgeKeysBatched");
 }
 
 }  // extern "C"

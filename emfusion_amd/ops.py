@@ -749,10 +749,64 @@ def render_phong_color(vertices, normals, colors, image, light=(0.0, 0.0, 0.0), 
     return image
 
 
-def extract_mesh(tsdf, weights, voxel_size, fg_mask=None, grads=None, stream=None, color=None):
+def _weld(keys, nv, nt, verts, norms, tris, cols, soup_bases=None, n=1, stream=None):
+    """emf_hip_meshWeldCount / ...Emit on device soup arrays: (welded vertices, normals, triangles, colours or None as
+    device arrays, welded counts (n,) u32, welded bases (n + 1,) u64)."""
+    scratch = DeviceArray.zeros((max(int(_L.emf_hip_meshWeldScratchBytes(nv)) // 4, 4),), np.uint32)
+    wcounts = DeviceArray.zeros((max(n, 1),), np.uint32)
+    wbases = DeviceArray.zeros((n + 1,), np.uint64)
+    if soup_bases is None:
+        check("emf_hip_meshWeldCount",
+              _L.emf_hip_meshWeldCount(_ptr(keys), nv, _ptr(scratch), _ptr(wcounts), _stream(stream)))
+    else:
+        check("emf_hip_meshWeldCountBatched",
+              _L.emf_hip_meshWeldCountBatched(_ptr(keys), nv, _ptr(soup_bases), n, _ptr(scratch), _ptr(wcounts),
+                                              _ptr(wbases), _stream(stream)))
+    check("emf_hip_meshWeldStatus", _L.emf_hip_meshWeldStatus(_ptr(scratch), nv, _stream(stream)))
+    cnt = wcounts.numpy()
+    nw = int(cnt.sum())
+    wv = DeviceArray.zeros((max(nw, 1), 3), np.float32)
+    wn = DeviceArray.zeros((max(nw, 1), 3), np.float32)
+    wc = None if cols is None else DeviceArray.zeros((max(nw, 1), 3), np.uint8)
+    if nv:
+        if soup_bases is None:
+            check("emf_hip_meshWeldEmit",
+                  _L.emf_hip_meshWeldEmit(_ptr(scratch), nv, nt, _ptr(verts), _ptr(norms), _ptr(cols), _ptr(tris),
+                                          _ptr(wv), _ptr(wn), _ptr(wc), _ptr(tris), _stream(stream)))
+        else:
+            check("emf_hip_meshWeldEmitBatched",
+                  _L.emf_hip_meshWeldEmitBatched(_ptr(scratch), nv, nt, _ptr(soup_bases), _ptr(wbases), n, _ptr(verts),
+                                                 _ptr(norms), _ptr(cols), _ptr(tris), _ptr(wv), _ptr(wn), _ptr(wc),
+                                                 _ptr(tris), _stream(stream)))
+    from .devmem import synchronize
+    synchronize()  # the scratch is released on return
+    return wv, wn, tris, wc, cnt, wbases.numpy()
+
+
+def mesh_edge_keys(tsdf, weights, fg_mask=None, stream=None):
+    """emf_hip_meshEdgeKeys: the u64 grid-edge key of every soup vertex of extract_mesh(tsdf, weights, ...), in its
+    vertex order: 3 * ((z * Ny + y) * Nx + x) + axis of the edge's lower voxel (include/emf_hip.h "Welded meshes")."""
+    res = _res(tsdf)
+    scratch = DeviceArray.zeros((max(int(_L.emf_hip_meshScratchBytes(res)) // 4, 2),), np.uint32)
+    counts = DeviceArray.zeros((2,), np.uint32)
+    check("emf_hip_meshCount",
+          _L.emf_hip_meshCount(_ptr(tsdf), _ptr(weights), _ptr(fg_mask), res, _ptr(scratch), _ptr(counts),
+                               _stream(stream)))
+    nv = int(counts.numpy()[0])
+    keys = DeviceArray.zeros((max(nv, 1),), np.uint64)
+    if nv:
+        check("emf_hip_meshEdgeKeys",
+              _L.emf_hip_meshEdgeKeys(_ptr(tsdf), _ptr(weights), _ptr(fg_mask), res, _ptr(scratch), _ptr(keys),
+                                      _stream(stream)))
+    return keys.numpy()[:nv]
+
+
+def extract_mesh(tsdf, weights, voxel_size, fg_mask=None, grads=None, stream=None, color=None, weld=False):
     """TSDF::getMesh / ObjTSDF::getMesh: (vertices (n, 3) f32, normals (n, 3) f32, triangles (m, 4) i32)
     as numpy arrays; two launches to count, one read-back, one launch to emit.  color: the volume's colour volume
-    ((Nz, Ny, Nx, 4) u16): a fourth array, the vertex colours (n, 3) u8 (emf_hip_meshColors)."""
+    ((Nz, Ny, Nx, 4) u16): a fourth array, the vertex colours (n, 3) u8 (emf_hip_meshColors).  weld: the welded mesh
+    instead of the soup (emf_hip_meshEdgeKeys / meshWeldCount / meshWeldEmit): one vertex per grid edge, the first
+    copy's bits, triangles re-indexed."""
     res = _res(tsdf)
     scratch = DeviceArray.zeros((max(int(_L.emf_hip_meshScratchBytes(res)) // 4, 2),), np.uint32)
     counts = DeviceArray.zeros((2,), np.uint32)
@@ -767,12 +821,22 @@ def extract_mesh(tsdf, weights, voxel_size, fg_mask=None, grads=None, stream=Non
         check("emf_hip_meshEmit",
               _L.emf_hip_meshEmit(_ptr(tsdf), _ptr(grads), _ptr(weights), _ptr(fg_mask), res, voxel_size,
                                   _ptr(scratch), _ptr(verts), _ptr(norms), _ptr(tris), _stream(stream)))
+    cols = None
     if color is not None:
         cols = DeviceArray.zeros((max(nv, 1), 3), np.uint8)
         if nv:
             check("emf_hip_meshColors",
                   _L.emf_hip_meshColors(_ptr(tsdf), _ptr(weights), _ptr(fg_mask), _ptr(color), res, _ptr(scratch),
                                         _ptr(cols), _stream(stream)))
+    if weld:
+        keys = DeviceArray.zeros((max(nv, 1),), np.uint64)
+        if nv:
+            check("emf_hip_meshEdgeKeys",
+                  _L.emf_hip_meshEdgeKeys(_ptr(tsdf), _ptr(weights), _ptr(fg_mask), res, _ptr(scratch), _ptr(keys),
+                                          _stream(stream)))
+        verts, norms, tris, cols, cnt, _ = _weld(keys, nv, nt, verts, norms, tris, cols, stream=stream)
+        nv = int(cnt[0])
+    if color is not None:
         return verts.numpy()[:nv], norms.numpy()[:nv], tris.numpy()[:nt], cols.numpy()[:nv]
     return verts.numpy()[:nv], norms.numpy()[:nv], tris.numpy()[:nt]
 
@@ -796,11 +860,12 @@ def mesh_table(volumes):
     return (upload_models(models) if n else None), res
 
 
-def extract_meshes(volumes, stream=None):
+def extract_meshes(volumes, stream=None, weld=False):
     """emf_hip_meshCountBatched / emf_hip_meshEmitBatched: the meshes of a table of volumes in one pass (one count
     launch, one read-back of the counts, one emit launch).  volumes: [dict(tsdf=, weights=, voxel_size=, fg_mask=None,
     grads=None), ...] of device arrays, at most EMF_MAX_MODELS.  Returns [(vertices (n, 3) f32, normals (n, 3) f32,
-    triangles (m, 4) i32), ...] in table order, each what extract_mesh gives for that volume alone."""
+    triangles (m, 4) i32), ...] in table order, each what extract_mesh gives for that volume alone -- with weld, what
+    extract_mesh(..., weld=True) gives (emf_hip_meshEdgeKeysBatched / meshWeldCountBatched / meshWeldEmitBatched)."""
     n = len(volumes)
     table, res = mesh_table(volumes)
     scratch_bytes = int(_L.emf_hip_meshScratchBytesBatched(res, n))
@@ -818,8 +883,7 @@ def extract_meshes(volumes, stream=None):
         check("emf_hip_meshEmitBatched",
               _L.emf_hip_meshEmitBatched(_ptr(table), res, n, _ptr(scratch), _ptr(verts), _ptr(norms), _ptr(tris),
                                          _stream(stream)))
-    hv, hn, ht = verts.numpy(), norms.numpy(), tris.numpy()
-    hc = None
+    cols = None
     if any(v.get("color") is not None for v in volumes):  # emf_hip_meshColorsBatched: 4-tuples, colours last
         ptrs = DeviceArray.from_numpy(np.array([0 if v.get("color") is None else v["color"].ptr for v in volumes],
                                                np.uint64))
@@ -828,10 +892,19 @@ def extract_meshes(volumes, stream=None):
             check("emf_hip_meshColorsBatched",
                   _L.emf_hip_meshColorsBatched(_ptr(table), _ptr(ptrs), res, n, _ptr(scratch), _ptr(cols),
                                                _stream(stream)))
-        hc = cols.numpy()
+    vbase, vcnt = bs[:, 0], cnt[:, 0]
+    if weld:
+        keys = DeviceArray.zeros((max(nv, 1),), np.uint64)
+        if nv:
+            check("emf_hip_meshEdgeKeysBatched",
+                  _L.emf_hip_meshEdgeKeysBatched(_ptr(table), res, n, _ptr(scratch), _ptr(keys), _stream(stream)))
+        verts, norms, tris, cols, vcnt, vbase = _weld(keys, nv, nt, verts, norms, tris, cols, soup_bases=bases, n=n,
+                                                      stream=stream)
+    hv, hn, ht = verts.numpy(), norms.numpy(), tris.numpy()
+    hc = None if cols is None else cols.numpy()
     out = []
     for k in range(n):
-        v0, t0, cv, ct = int(bs[k, 0]), int(bs[k, 1]), int(cnt[k, 0]), int(cnt[k, 1])
+        v0, t0, cv, ct = int(vbase[k]), int(bs[k, 1]), int(vcnt[k]), int(cnt[k, 1])
         out.append((hv[v0:v0 + cv], hn[v0:v0 + cv], ht[t0:t0 + ct]) + ((hc[v0:v0 + cv],) if hc is not None else ()))
     return out
 

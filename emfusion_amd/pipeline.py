@@ -100,6 +100,7 @@ def load() -> C.CDLL:
         "emf_fusion_process_rgbd": [vp, fp, C.c_int32, C.c_int32],
         "emf_fusion_use_preproc_masks": [vp, C.c_char_p],
         "emf_fusion_set_color": [vp, C.c_int],
+        "emf_fusion_set_mesh_weld": [vp, C.c_int],
         "emf_fusion_set_color_image": [vp, img],
         "emf_fusion_process_rgbd_color": [vp, fp, C.c_void_p, C.c_int32, C.c_int32],
         "emf_fusion_colored_voxels": [vp, C.POINTER(C.c_uint64)],
@@ -541,6 +542,12 @@ class Fusion:
         the colour weight in 8.8 fixed point) that frames with a colour image fuse into.  Before the first frame or
         after reset() only; refused on the sharded and per-volume paths."""
         _check("emf_fusion_set_color", load().emf_fusion_set_color(self._h, int(on)))
+
+    def set_mesh_weld(self, on=True):
+        """Welded meshes: mesh(), meshes(), write_results' PLY files and the per-frame meshes become one vertex per grid
+        edge (the first soup copy's bits) with the soup's triangles re-indexed, welded on the device.  An output form
+        only: no pose, life-cycle decision or image changes."""
+        _check("emf_fusion_set_mesh_weld", load().emf_fusion_set_mesh_weld(self._h, int(on)))
 
     def set_color_image(self, rgb_view: EmfImage):
         """The u8 x 3 device image (frame size) that goes with the next frame, and with that one only."""

@@ -111,6 +111,15 @@ int emf_fusion_process_rgbd(emf_fusion_t* h, const float* depth_host, int32_t wi
  *                      set_color_image, then the frame.
  *   colored_voxels     voxels the colour pass has updated since the last call (waits for the device) */
 int emf_fusion_set_color(emf_fusion_t* h, int on);
+/* Welded meshes (include/emf_hip.h "Welded meshes"; off by default, may be switched at any time).  on != 0:
+ * emf_fusion_extract_mesh / copy_mesh / copy_mesh_colors, emf_fusion_extract_meshes / copy_meshes / copy_meshes_colors,
+ * emf_fusion_write_results' mesh_bg.ply and mesh_<id>.ply of the live models and the per-frame frame_meshes/ of
+ * emf_fusion_setup_output deliver one vertex per grid edge (the first soup copy's position, normal and colour, bit for
+ * bit) and the soup's triangles re-indexed; the counts are the welded counts.  Welded on the device before the copies
+ * to the host.  An output form only: poses, the object life cycle and every image are the same bytes either way, and
+ * the last mesh kept of an object deleted during the run stays the soup the life cycle took.  On the sharded path:
+ * wherever emf_fusion_extract_mesh works, for this rank's models. */
+int emf_fusion_set_mesh_weld(emf_fusion_t* h, int on);
 int emf_fusion_set_color_image(emf_fusion_t* h, const emf_image_t* rgb_dev);
 int emf_fusion_process_rgbd_color(emf_fusion_t* h, const float* depth_host, const uint8_t* rgb_host, int32_t width,
                                   int32_t height);

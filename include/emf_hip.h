@@ -1052,6 +1052,68 @@ int emf_hip_meshColors(const float* tsdf, const float* weights, const uint8_t* f
 int emf_hip_meshColorsBatched(const emf_model_t* models_dev, uint16_t* const* colors_dev, const int32_t* res_host, int n,
                               const void* scratch_dev, uint8_t* colors, emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Welded meshes (new behaviour: the reference's marching cubes emits a triangle soup -- every cube its
+ * own copy of every vertex it touches).  Opt-in; the soup entries above are untouched.
+ * Soup vertex i was emitted by a cube for one of its 12 edges; it lies on the GRID EDGE joining two voxels
+ * that differ in one coordinate.  Its EDGE KEY is
+ *     (uint64_t) slot << 48  |  3 * linear(lower voxel) + axis,
+ * linear = (z * Ny + y) * Nx + x, axis 0 / 1 / 2 for x / y / z, slot = the model's index in the table
+ * (0 for a level-1 call) -- also when vertexInterp returned a corner outright: welding is by edge, never
+ * by position.  WELDED vertex j is the first soup vertex, in soup order, of the j-th distinct key in order of
+ * first occurrence: that copy's position, normal and colour, bit for bit.  WELDED triangles are the soup's,
+ * same order and (3, i0, i1, i2) layout, every index replaced by the welded index of its vertex's key,
+ * model-local in a table.  A pure function of the volume(s): no result depends on the order workgroups run in.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Edge keys of the soup of the last emf_hip_meshCount / ...Batched on the same volume(s) and scratch: one u64
+ * per soup vertex, in the vertex order of the emit (all models concatenated).  Like emf_hip_meshColors it walks
+ * the listed surface chunks once more, may run before or after the emit and does not disturb it. */
+int emf_hip_meshEdgeKeys(const float* tsdf, const float* weights, const uint8_t* fgVolMask, const int32_t res[3],
+                         const void* scratch_dev, uint64_t* keys, emf_stream_t stream);
+int emf_hip_meshEdgeKeysBatched(const emf_model_t* models_dev, const int32_t* res_host, int n, const void* scratch_dev,
+                                uint64_t* keys, emf_stream_t stream);
+
+/* Bytes of device scratch welding a soup of soupVertices needs: an open-addressing table of the smallest power
+ * of two >= 2 * soupVertices (u64 key + u32 first index per slot), two u32 per soup vertex and the scan's
+ * per-workgroup sums -- under 57 bytes per soup vertex plus 1 KiB, nothing sized by the volume.  0 if
+ * soupVertices > 2^30 (the entries below then return EMF_E_LIMIT). */
+size_t emf_hip_meshWeldScratchBytes(uint64_t soupVertices);
+
+/* First occurrence and rank of every key.  Leaves in weld_scratch_dev what emf_hip_meshWeldEmit reads (the welded
+ * index of every soup vertex) and writes, to device memory,
+ *   welded_counts : n u32, the welded vertices of each model
+ *   welded_bases  : NULL or n + 1 u64, each model's first welded vertex in the concatenated output and the total
+ *   soup_bases    : DEVICE, what emf_hip_meshCountBatched wrote to bases_dev (2 (n + 1) u64: vertex and triangle bases
+ *                   interleaved); the level-1 form is n == 1 with bases {0, 0, soupVertices, soupTriangles} implied.
+ * soupVertices == 0 is valid: nothing is launched but the clearing of the outputs.  1 <= n <= EMF_MAX_MODELS.
+ * Probing is bounded by the table's capacity; a table that cannot hold the keys (impossible with the documented
+ * size) raises a flag in the scratch instead of spinning: see emf_hip_meshWeldStatus. */
+int emf_hip_meshWeldCount(const uint64_t* keys, uint64_t soupVertices, void* weld_scratch_dev, uint32_t* welded_count,
+                          emf_stream_t stream);
+int emf_hip_meshWeldCountBatched(const uint64_t* keys, uint64_t soupVertices, const uint64_t* soup_bases_dev, int n,
+                                 void* weld_scratch_dev, uint32_t* welded_counts, uint64_t* welded_bases,
+                                 emf_stream_t stream);
+
+/* Waits for the stream and returns EMF_OK, or EMF_E_LIMIT if the last emf_hip_meshWeldCount on this scratch ran out
+ * of table (its outputs are then meaningless).  The one synchronising entry of the group: call it where the counts
+ * are read back anyway. */
+int emf_hip_meshWeldStatus(const void* weld_scratch_dev, uint64_t soupVertices, emf_stream_t stream);
+
+/* Compact and remap: soup arrays in (as the emit / colour entries wrote them: 3 f32, 3 f32, 3 u8 per vertex, 4 i32
+ * per triangle), welded arrays out.  colors / welded_colors: both NULL or both given.  triangles holds
+ * soupTriangles (3, i0, i1, i2) records with model-local soup indices; welded_triangles may be the same buffer.
+ * The vertex outputs must not alias the inputs.  The level-1 form takes no bases. */
+int emf_hip_meshWeldEmit(const void* weld_scratch_dev, uint64_t soupVertices, uint64_t soupTriangles,
+                         const float* vertices, const float* normals, const uint8_t* colors, const int32_t* triangles,
+                         float* welded_vertices, float* welded_normals, uint8_t* welded_colors,
+                         int32_t* welded_triangles, emf_stream_t stream);
+int emf_hip_meshWeldEmitBatched(const void* weld_scratch_dev, uint64_t soupVertices, uint64_t soupTriangles,
+                                const uint64_t* soup_bases_dev, const uint64_t* welded_bases_dev, int n,
+                                const float* vertices, const float* normals, const uint8_t* colors,
+                                const int32_t* triangles, float* welded_vertices, float* welded_normals,
+                                uint8_t* welded_colors, int32_t* welded_triangles, emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
