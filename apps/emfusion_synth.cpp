@@ -82,6 +82,17 @@ static void set3dView(emf::EMFusion& emf, const emf::Params& params, const View3
 // The reference's main loop on a dataset (apps/EM-Fusion.cpp:100-156): a TUM sequence (`--sequence`, TUMRGBDReader) or a
 // Co-Fusion style directory (`--dir`, ImageReader: ColorNNNN.png + DepthNNNN.exr), as apps/EM-Fusion.cpp:118-131 chooses
 static bool weldMeshes = false;  // --weld-meshes
+// --checkpoint PATH --checkpoint-every N: the session is saved to PATH after every N-th frame (EMFusion::saveCheckpoint);
+// --resume PATH: the instance is built from the file's parameters, the file is loaded and the input stream continues at
+// the stored frame index.  What the caller sets at start (output log, views, weld) is set again, as at start.
+static std::string checkpointPath, resumePath;
+static int checkpointEvery = 0;
+static void maybeCheckpoint(emf::EMFusion& emf, size_t f) {
+    if (checkpointPath.empty() || checkpointEvery <= 0 || (f + 1) % static_cast<size_t>(checkpointEvery) != 0) return;
+    const emf::CheckpointStats st = emf.saveCheckpoint(checkpointPath);
+    std::printf("checkpoint after frame %zu: %.1f MiB of volumes in a file of %.1f MiB, %.1f ms\n", f,
+                st.rawBytes / 1048576.0, st.fileBytes / 1048576.0, st.msTotal);
+}
 
 static int runSequence(const std::string& seq, bool cofusion, const std::string& colordir, const std::string& depthdir,
                        const float* intrinsics, const std::string& configFile, const std::string& masks,
@@ -136,8 +147,13 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
         params.boundary = static_cast<int>(std::lround(20 * scale));
         params.maskRCNNFrames = maskFrames;
     }
+    if (!resumePath.empty()) params = emf::EMFusion::checkpointParams(resumePath);
+    if (!resumePath.empty() && (params.frameSize.width != size.width || params.frameSize.height != size.height))
+        throw std::runtime_error("--resume: the checkpoint was saved with another frame size than the images have");
     emf::EMFusion emf(params);
-    if (color) emf.enableColor(true);                 // --color: the sequence's colour images go into the models
+    if (!resumePath.empty()) emf.loadCheckpoint(resumePath);  // (restores colour on / off itself)
+    else if (color) emf.enableColor(true);            // --color: the sequence's colour images go into the models
+    color = emf.colorEnabled();
     emf.setMeshWeld(weldMeshes);
     std::vector<uint8_t> rgb;
     if (!masks.empty()) emf.usePreprocMasks(masks);   // apps/EM-Fusion.cpp:115
@@ -145,7 +161,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     set3dView(emf, params, view3d);
     std::vector<uint8_t> rendered(3 * params.frameSize.area());
     const auto t0 = std::chrono::steady_clock::now();
-    for (size_t f = 0; f < n; ++f) {                  // while (reader->moreFrames())
+    for (size_t f = static_cast<size_t>(emf.frameIndex()); f < n; ++f) {  // while (reader->moreFrames())
         readDepth(f);                                 // frame = reader->getNextFrame()
         for (float& d : depth)
             if (!std::isfinite(d)) d = 0.f;
@@ -172,6 +188,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
             std::printf("frame %zu/%zu: %zu visible objects, %d instances in the last mask frame\n", f, n,
                         emf.visibleObjects().size(), inst);
         }
+        maybeCheckpoint(emf, f);
     }
     emf.synchronize();
     emf.writeResults(outDir, volumes);                // apps/EM-Fusion.cpp:204
@@ -222,6 +239,9 @@ int main(int argc, char** argv) {
         else if (a == "--export-frame-meshes") frameMeshes = true;
         else if (a == "--weld-meshes") weldMeshes = true;
         else if (a == "--color") color = true;
+        else if (a == "--checkpoint" && i + 1 < argc) checkpointPath = argv[++i];
+        else if (a == "--checkpoint-every") checkpointEvery = next();
+        else if (a == "--resume" && i + 1 < argc) resumePath = argv[++i];
         else if ((a == "--3d-vis-eye" || a == "--3d-vis-target") && i + 3 < argc) {
             float* dst = a == "--3d-vis-eye" ? view3d.eye : view3d.target;
             for (int k = 0; k < 3; ++k) dst[k] = static_cast<float>(std::atof(argv[++i]));
@@ -242,6 +262,10 @@ int main(int argc, char** argv) {
     }
     if (color && sequence.empty() && dataDir.empty()) {  // (before any device is touched)
         std::fprintf(stderr, "emfusion_synth: --color needs the colour images of --sequence or --dir; the synthetic stream has none\n");
+        return 2;
+    }
+    if (checkpointPath.empty() != (checkpointEvery <= 0)) {
+        std::fprintf(stderr, "emfusion_synth: --checkpoint PATH and --checkpoint-every N (> 0) go together\n");
         return 2;
     }
     if (view3d.on && outDir.empty()) {
@@ -266,13 +290,23 @@ int main(int argc, char** argv) {
         params.visibilityThresh = static_cast<int>(1600 * scale * scale);
         params.boundary = static_cast<int>(20 * scale);
 
+        if (!resumePath.empty()) params = emf::EMFusion::checkpointParams(resumePath, &materialize);
         emf::SyntheticScene scene(params.frameSize, params.intr, objects);
         emf::EMFusion emf(params, materialize ? emf::TSDF::Gradients::Materialized
                                               : emf::TSDF::Gradients::OnTheFly);
         std::vector<int> ids;
-        if (!autonomous)
+        if (!resumePath.empty()) {
+            emf.loadCheckpoint(resumePath);
+            if (!autonomous) {
+                ids = emf.objectIds();
+                if (static_cast<int>(ids.size()) != objects)
+                    throw std::runtime_error("--resume: the checkpoint holds " + std::to_string(ids.size()) +
+                                             " objects, --objects says " + std::to_string(objects));
+            }
+        } else if (!autonomous)
             for (int k = 0; k < objects; ++k)
                 ids.push_back(emf.addObject(scene.sphereCenter(k, 0), scene.objectVolumeSize(k)));
+        const int firstFrame = emf.frameIndex();
 
         const size_t P = params.frameSize.area();
         std::vector<float> depth(P);
@@ -288,7 +322,7 @@ int main(int argc, char** argv) {
         double gpuMs = 0;
         int spawned = 0;
         const auto t0 = std::chrono::steady_clock::now();
-        for (int f = 0; f < frames; ++f) {  // while (reader->moreFrames())
+        for (int f = firstFrame; f < frames; ++f) {  // while (reader->moreFrames())
             scene.render(f, depth.data(), sid.data());  // frame = reader->getNextFrame()
             emf::FrameInputs in;
             in.cam_pose = scene.cameraPose(f);
@@ -322,6 +356,7 @@ int main(int argc, char** argv) {
             if (view3d.on) emf.render(rendered.data());  // apps/EM-Fusion.cpp:156: the rendering and the 3D view
             if (autonomous)
                 for (int id : emf.lastCreatedObjects()) spawned += id >= 0;
+            maybeCheckpoint(emf, static_cast<size_t>(f));
         }
         emf.synchronize();
         if (autonomous) {

@@ -50,6 +50,11 @@ def main():
     ap.add_argument("--color", action="store_true",
                     help="fuse the sequence's colour images into per-voxel colour: mesh_*.ply (and frame meshes, volume "
                          "dumps) carry colours")
+    ap.add_argument("--checkpoint", metavar="PATH", help="save the session to PATH after every N-th frame (--checkpoint-every)")
+    ap.add_argument("--checkpoint-every", type=int, default=0, metavar="N")
+    ap.add_argument("--resume", metavar="PATH",
+                    help="build the instance from the parameters of the checkpoint PATH, load it and continue the "
+                         "sequence at its frame index (the sizing options of this command line are not applied)")
     ap.add_argument("--frames", type=int, default=0, help="0 = all")
     ap.add_argument("--bg-res", type=int, default=512)
     ap.add_argument("--bg-voxel", type=float, default=0.01)
@@ -64,6 +69,8 @@ def main():
         ap.error("--export-frame-meshes writes OUT/frame_meshes/ and needs --out")
     if args.vis3d_eye and not args.vis3d:
         ap.error("--3d-vis-eye needs --3d-vis")
+    if bool(args.checkpoint) != (args.checkpoint_every > 0):
+        ap.error("--checkpoint PATH and --checkpoint-every N (> 0) go together")
 
     import torch  # noqa: F401  (one HIP runtime, see bench.py)
     from emfusion_amd import pipeline, readers
@@ -86,9 +93,16 @@ def main():
     if args.intrinsics:
         fx, fy, cx, cy = args.intrinsics
         prm.K[:] = [fx, 0, cx, 0, fy, cy, 0, 0, 1]
-    fus = pipeline.Fusion(prm, None)
-    if args.color:
-        fus.enable_color()
+    if args.resume:  # every parameter from the file; colour on / off comes back with the session
+        fus = pipeline.Fusion.from_checkpoint(args.resume)
+        prm = fus.params
+        if (prm.width, prm.height) != (w, h):
+            raise SystemExit(f"--resume: the checkpoint was saved at {prm.width} x {prm.height}, the images are {w} x {h}")
+        args.color = bool(pipeline.checkpoint_info(args.resume)["color"])
+    else:
+        fus = pipeline.Fusion(prm, None)
+        if args.color:
+            fus.enable_color()
     fus.set_mesh_weld(args.weld_meshes)
     fus.set_ignore_person(args.ignore_person)
     fus.set_preprocess(True)
@@ -101,7 +115,7 @@ def main():
         fus.set_3d_view(R3, t3, K3, size3)
     eye, zero = np.eye(3, dtype=np.float32).reshape(-1), np.zeros(3, np.float32)
     t0 = time.time()
-    for f in range(n):
+    for f in range(fus.frame_index(), n):
         depth = np.ascontiguousarray(reader.depth(index0 + f), np.float32)
         depth[~np.isfinite(depth)] = 0
         d = DeviceArray.from_numpy(depth)
@@ -121,7 +135,7 @@ def main():
             c = DeviceArray.from_numpy(rgb)
             keep.append(c)
             fus.set_color_image(image_view(c))
-        if f == 1:
+        if f >= 1:
             fus.set_tracking(camera=True, objects=True)  # frame 0 defines the world frame
         fus.process_frame(image_view(d), eye, zero, {}, {}, False)
         fus.synchronize()
@@ -132,6 +146,10 @@ def main():
             print(f"frame {f}/{n}: objects {sorted(fus.visible_objects())}"
                   + (f", camera LM steps {r['iterations']} ({r['accepted']} accepted)" if r else ""),
                   flush=True)
+        if args.checkpoint and (f + 1) % args.checkpoint_every == 0:
+            st = fus.save_checkpoint(args.checkpoint)
+            print(f"checkpoint after frame {f}: {st['raw_bytes'] / 2**20:.1f} MiB of volumes in a file of "
+                  f"{st['file_bytes'] / 2**20:.1f} MiB, {st['ms']['total']:.1f} ms", flush=True)
     out = Path(args.out or "emfusion_out")
     out.mkdir(parents=True, exist_ok=True)
     fus.write_results(out, volumes=args.volumes)

@@ -169,6 +169,12 @@ SIGNATURES = {
     "emf_hip_meshWeldEmit": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _STREAM],
     "emf_hip_meshWeldEmitBatched": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, C.c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
                                     _FP, _STREAM],
+    "emf_hip_packScratchBytes": [C.c_uint64],
+    "emf_hip_packClassify": [_FP, C.c_uint64, _FP, _FP, _STREAM],
+    "emf_hip_packRank": [_FP, _FP, C.c_uint64, _FP, _FP, _FP, _FP, _FP, _STREAM],
+    "emf_hip_packGather": [_FP, C.c_uint64, _FP, C.c_uint32, C.c_uint32, _FP, _STREAM],
+    "emf_hip_unpackFill": [_FP, C.c_uint64, _FP, _FP, _FP, C.c_uint32, _STREAM],
+    "emf_hip_unpackLiterals": [_FP, C.c_uint64, _FP, C.c_uint32, C.c_uint32, _FP, _STREAM],
 }
 
 
@@ -267,6 +273,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.emf_hip_meshScratchBytes.restype = C.c_size_t
     lib.emf_hip_meshScratchBytesBatched.restype = C.c_size_t
     lib.emf_hip_meshWeldScratchBytes.restype = C.c_size_t
+    lib.emf_hip_packScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateCullScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateDirtyMapBytes.restype = C.c_size_t
     lib.emf_hip_signMapBytes.restype = C.c_size_t

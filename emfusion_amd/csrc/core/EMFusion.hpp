@@ -79,6 +79,16 @@ struct TrackResult {
     float error = 0.f;   // weighted squared residual sum at the final pose
 };
 
+/** What EMFusion::saveCheckpoint did (Checkpoint.cpp). */
+struct CheckpointStats {
+    uint64_t rawBytes = 0;    // bytes of the device buffers that were packed
+    uint64_t fileBytes = 0;   // size of the file
+    uint64_t chunks[3] = {0, 0, 0};  // 1 KiB chunks per class: zero, uniform, literal
+    uint32_t records = 0;     // packed buffers
+    double msClassify = 0, msGather = 0;  // device time (HIP events): classify + rank, gather
+    double msCopy = 0, msFile = 0, msTotal = 0;  // host time: device-to-host copies, file writes, the whole call
+};
+
 /** Per-stage GPU time of the last processed frame (milliseconds, from HIP events). */
 struct FrameTimings {
     float points = 0, estep = 0, raycast = 0, composite = 0, integrate = 0, masks = 0, total = 0;
@@ -309,6 +319,22 @@ public:
      */
     int addObject(const Vec3f& center, float volSize);
     int addObject(const Vec3f& center, float volSize, const Vec3i& res);
+
+    /**
+     * Checkpoint and resume (Checkpoint.cpp; new behaviour: the reference has none).  saveCheckpoint writes the
+     * session's primary state -- parameters, frame count, poses, object table and bookkeeping, pose logs, kept meshes
+     * and the volumes, packed losslessly on the device (include/emf_hip.h "Packed buffers") -- to path + ".tmp" and
+     * renames it; it changes nothing in the session.  loadCheckpoint acts as reset() followed by the restore and may
+     * be called at any time; a file that does not fit this instance (frame size, intrinsics, background geometry,
+     * TSDF parameters), is damaged or truncated is refused with EMF_E_ARG and leaves the session as it was.  A
+     * restored session continues with the bytes of one that was never interrupted.  Both throw on the sharded path.
+     */
+    CheckpointStats saveCheckpoint(const std::string& path);
+    void loadCheckpoint(const std::string& path);
+    /** The parameters, frame index, objects and per-record chunk counts of a checkpoint file as JSON; no device. */
+    static std::string checkpointInfo(const std::string& path);
+    /** The parameters a checkpoint was saved with (what --resume builds its instance from); no device. */
+    static Params checkpointParams(const std::string& path, bool* materializedGradients = nullptr);
 
     /** Poses / masks the next processFrame(RGBD) call consumes. */
     void setFrameInputs(const FrameInputs& in) { pending = in; }

@@ -142,6 +142,12 @@ Vec3f ObjTSDF::resize(const Vec3f& p10, const Vec3f& p90, float volPad, Stream& 
     return newCenter;
 }
 
+void ObjTSDF::volumesWritten(Stream& stream) {
+    TSDF::volumesWritten(stream);
+    computeFgProbs(stream);
+    stream.waitForCompletion();
+}
+
 void ObjTSDF::updateClassProbs(const std::vector<double>& scores) {
     if (scores.empty()) return;  // a mask that came without scores
     if (classProbs.empty()) {

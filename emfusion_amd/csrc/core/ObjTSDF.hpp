@@ -74,6 +74,19 @@ public:
     std::vector<float> getFgBgCounts() const;
 
     void describe(emf_model_t& m) const override;
+    /** ... and the foreground probability and mask recomputed from the counts (computeFgProbs). */
+    void volumesWritten(Stream& stream) override;
+    /** N^3 x 2 f32 (fg, bg) counts: the primary state fgProbs / fgVolMask are derived from. */
+    float* fgBgPtr() const { return fgBgProbs.as<float>(); }
+    /** Existence and class bookkeeping as stored (a checkpoint saves and restores them). */
+    int existCount() const { return exCount; }
+    int nonExistCount() const { return nonExCount; }
+    const std::vector<double>& classScores() const { return classProbs; }
+    void restoreBookkeeping(int ex, int nonEx, std::vector<double> scores) {
+        exCount = ex;
+        nonExCount = nonEx;
+        classProbs = std::move(scores);
+    }
     const float* fgProbsPtr() const { return fgProbs.as<float>(); }
     const uint8_t* fgVolMaskPtr() const { return fgVolMask.as<uint8_t>(); }
 

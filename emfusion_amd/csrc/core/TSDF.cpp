@@ -227,6 +227,14 @@ void TSDF::resyncBack() {
     Stream::Null().waitForCompletion();
 }
 
+void TSDF::volumesWritten(Stream& stream) {
+    brickFlags.setZero(stream);  // every brick "mixed": always correct; integrate() refines them
+    signMapsValid = false;
+    updateGradients(stream);
+    stream.waitForCompletion();
+    resyncBack();
+}
+
 void TSDF::flip() {
     std::swap(tsdfVol, tsdfBack);
     std::swap(tsdfWeights, weightsBack);

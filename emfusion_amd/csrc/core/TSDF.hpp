@@ -134,6 +134,13 @@ public:
      * (the owner calls it before describe()).  Volumes with Nx % 4 != 0 have none (no tile launches).
      */
     void invalidateSignMaps() { signMapsValid = false; }
+    /**
+     * The tsdf / weights (and colour) of the FRONT copy were written from outside the integration (a checkpoint being
+     * restored): what is derived from them is invalidated or rebuilt the way ObjTSDF::resize does it -- brick flags
+     * "mixed" everywhere, sign maps stale (the owner's rebuildModelTable() refreshes them and the tile lists),
+     * materialised gradients recomputed, the back copy made equal.  Waits for `stream`.
+     */
+    virtual void volumesWritten(Stream& stream);
     void refreshSignMaps(Stream& stream = Stream::Null());
 
     /**

@@ -163,6 +163,82 @@ int emf_fusion_describe_switches(char* json, size_t capacity) {
     });
 }
 
+int emf_fusion_save_checkpoint(emf_fusion_t* h, const char* path, emf_checkpoint_stats_t* stats) {
+    REQ(h);
+    REQ(path);
+    return guarded([&] {
+        const CheckpointStats st = h->impl->saveCheckpoint(path);
+        if (!stats) return;
+        *stats = emf_checkpoint_stats_t{};
+        stats->raw_bytes = st.rawBytes;
+        stats->file_bytes = st.fileBytes;
+        for (int k = 0; k < 3; ++k) stats->chunks[k] = st.chunks[k];
+        stats->ms_classify = st.msClassify;
+        stats->ms_gather = st.msGather;
+        stats->ms_copy = st.msCopy;
+        stats->ms_file = st.msFile;
+        stats->ms_total = st.msTotal;
+        stats->records = st.records;
+    });
+}
+
+int emf_fusion_load_checkpoint(emf_fusion_t* h, const char* path) {
+    REQ(h);
+    REQ(path);
+    return guarded([&] {
+        h->impl->loadCheckpoint(path);
+        h->queuedMasks.clear();
+        h->queuedInstances.clear();
+        h->queuedScores.clear();
+    });
+}
+
+int emf_fusion_checkpoint_info(const char* path, char* json, size_t capacity) {
+    REQ(path);
+    REQ(json);
+    return guarded([&] {
+        const std::string s = EMFusion::checkpointInfo(path);
+        if (s.size() + 1 > capacity) throw HipError("emf_fusion_checkpoint_info: buffer too small", EMF_E_ARG);
+        std::memcpy(json, s.c_str(), s.size() + 1);
+    });
+}
+
+int emf_fusion_create_from_checkpoint(const char* path, emf_comm_t* comm, emf_fusion_params_t* params_out,
+                                      emf_fusion_t** out) {
+    REQ(path);
+    REQ(out);
+    return guarded([&] {
+        bool materialized = false;
+        const Params q = EMFusion::checkpointParams(path, &materialized);
+        auto h = std::make_unique<emf_fusion>();
+        h->impl = std::make_unique<EMFusion>(q, materialized ? TSDF::Gradients::Materialized : TSDF::Gradients::OnTheFly,
+                                             comm ? comm->impl : nullptr);
+        h->impl->loadCheckpoint(path);
+        if (params_out) {
+            emf_fusion_params_t* p = params_out;
+            p->width = q.frameSize.width;
+            p->height = q.frameSize.height;
+            std::memcpy(p->K, q.intr.val, sizeof(p->K));
+            std::memcpy(p->bg_res, q.globalVolumeDims.val, sizeof(p->bg_res));
+            p->bg_voxel_size = q.globalVoxelSize;
+            p->bg_rel_truncdist = q.globalRelTruncDist;
+            std::memcpy(p->volume_pose_t, q.volumePose.translation().val, sizeof(p->volume_pose_t));
+            std::memcpy(p->obj_res, q.objVolumeDims.val, sizeof(p->obj_res));
+            p->obj_rel_truncdist = q.objRelTruncDist;
+            p->max_tsdf_weight = q.tsdfParams.maxTSDFWeight;
+            p->assoc_sigma = q.tsdfParams.assocSigma;
+            p->alpha = q.tsdfParams.alpha;
+            p->uni_prior = q.tsdfParams.uniPrior;
+            p->visibility_thresh = q.visibilityThresh;
+            p->boundary = q.boundary;
+            p->mask_frames = q.maskRCNNFrames;
+            p->materialize_gradients = materialized ? 1 : 0;
+            p->max_tracking_iter = q.maxTrackingIter;
+        }
+        *out = h.release();
+    });
+}
+
 int emf_fusion_reset(emf_fusion_t* h) {
     REQ(h);
     return guarded([&] { h->impl->reset(); });
@@ -969,6 +1045,12 @@ int emf_fusion_get_volume(emf_fusion_t* h, int which, int obj_id, void** dev_ptr
         case EMF_VOL_FGPROBS:
             if (obj) {
                 *dev_ptr = const_cast<float*>(obj->fgProbsPtr());
+                return EMF_OK;
+            }
+            break;
+        case EMF_VOL_FGBG:
+            if (obj) {
+                *dev_ptr = obj->fgBgPtr();
                 return EMF_OK;
             }
             break;

@@ -232,6 +232,11 @@ class DeviceArray:
         _check(_hip.hipMemset(C.c_void_p(self.ptr), 0, self.nbytes), "hipMemset")
         return self
 
+    def fill_bytes_(self, value: int):
+        """Every byte := value (hipMemset), padding included."""
+        _check(_hip.hipMemset(C.c_void_p(self.ptr), int(value) & 0xFF, self.nbytes), "hipMemset")
+        return self
+
 
 def memcpy_d2h(dst: np.ndarray, src_ptr: int):
     synchronize()

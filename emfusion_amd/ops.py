@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import EmfImage, check
-from .devmem import DeviceArray
+from .devmem import DeviceArray, DeviceView, synchronize
 
 _L = _lib.load()
 
@@ -958,3 +958,111 @@ def copy_values(src, dst, offset, stream=None):
     check("emf_hip_copyValues",
           _L.emf_hip_copyValues(_ptr(src), _ptr(dst), ch, (C.c_int32 * 3)(*[int(v) for v in offset]),
                                 _res(src), _res(dst), _stream(stream)))
+
+
+# ---- packed buffers (include/emf_hip.h "Packed buffers") --------------------------------------------------------------
+
+PACK_CHUNK = 1024
+PACK_ARENA_CHUNKS = 65536  # 64 MiB of literals per gather / upload
+
+
+def _pad8(b: bytes) -> bytes:
+    return b + bytes(-len(b) % 8)
+
+
+def pack_arrays(buf: DeviceArray, stream=None) -> dict:
+    """emf_hip_packClassify + emf_hip_packRank over a contiguous device array: dict(nbytes=, nchunks=, classes=,
+    words=, ranks=, uniform=, literal_chunks= (device arrays of nchunks entries), nuniform=, nliteral=).
+    Synchronises (the totals are read back)."""
+    assert isinstance(buf, DeviceArray) and not buf.padded
+    nbytes = buf.nbytes
+    nchunks = (nbytes + PACK_CHUNK - 1) // PACK_CHUNK
+    p = dict(nbytes=nbytes, nchunks=nchunks,
+             classes=DeviceArray((max(nchunks, 1),), np.uint8), words=DeviceArray((max(nchunks, 1),), np.uint32))
+    check("emf_hip_packClassify",
+          _L.emf_hip_packClassify(_ptr(buf), nbytes, _ptr(p["classes"]), _ptr(p["words"]), _stream(stream)))
+    _pack_rank(p, p["words"], stream)
+    return p
+
+
+def _pack_rank(p: dict, words: Optional[DeviceArray], stream=None):
+    n = max(p["nchunks"], 1)
+    scratch = DeviceArray((max(int(_L.emf_hip_packScratchBytes(p["nbytes"])) // 8, 1),), np.uint64)
+    p["ranks"], p["literal_chunks"] = DeviceArray((n,), np.uint32), DeviceArray((n,), np.uint32)
+    p["uniform"] = DeviceArray((n,), np.uint32) if words is not None else None
+    totals = DeviceArray.zeros((2,), np.uint32)
+    check("emf_hip_packRank",
+          _L.emf_hip_packRank(_ptr(p["classes"]), _ptr(words), p["nbytes"], _ptr(scratch), _ptr(p["ranks"]),
+                              _ptr(p["uniform"]), _ptr(p["literal_chunks"]), _ptr(totals), _stream(stream)))
+    p["nuniform"], p["nliteral"] = (int(v) for v in totals.numpy())
+
+
+def pack_gather(buf: DeviceArray, packed: dict, first: int, count: int, arena: Optional[DeviceArray] = None,
+                stream=None) -> np.ndarray:
+    """emf_hip_packGather: the literal chunks of ranks [first, first + count) as a (count, 1024) u8 host array."""
+    assert 0 <= first and 0 <= count and first + count <= packed["nliteral"]
+    if arena is None:
+        arena = DeviceArray((max(count, 1), PACK_CHUNK), np.uint8)
+    assert arena.nbytes >= count * PACK_CHUNK
+    check("emf_hip_packGather",
+          _L.emf_hip_packGather(_ptr(buf), packed["nbytes"], _ptr(packed["literal_chunks"]), first, count, _ptr(arena),
+                                _stream(stream)))
+    return DeviceView(arena.ptr, (count, PACK_CHUNK), np.uint8).numpy()
+
+
+def pack_buffer(buf: DeviceArray, arena_chunks: int = PACK_ARENA_CHUNKS, splits: Optional[Sequence[int]] = None,
+                stream=None) -> bytes:
+    """The packed record (include/emf_hip.h) of a contiguous device array whose size is a multiple of 4 bytes.  The
+    literals move through a device arena of at most arena_chunks chunks; ``splits`` (counts that sum to the number of
+    literals) overrides how the rank ranges are cut."""
+    p = pack_arrays(buf, stream)
+    nu, nl = p["nuniform"], p["nliteral"]
+    parts = [np.array([p["nbytes"]], "<u8").tobytes() + np.array([p["nchunks"], nu, nl, 0], "<u4").tobytes(),
+             _pad8(p["classes"].numpy().tobytes()),
+             _pad8(DeviceView(p["uniform"].ptr, (nu,), np.uint32).numpy().tobytes())]
+    if splits is None:
+        splits = [min(arena_chunks, nl - f) for f in range(0, nl, arena_chunks)]
+    assert sum(splits) == nl and all(s >= 0 for s in splits)
+    arena = DeviceArray((max(max(splits, default=0), 1), PACK_CHUNK), np.uint8)
+    first = 0
+    for count in splits:
+        parts.append(pack_gather(buf, p, first, count, arena, stream).tobytes())
+        first += count
+    return b"".join(parts)
+
+
+def unpack_buffer(record: bytes, dst: DeviceArray, arena_chunks: int = PACK_ARENA_CHUNKS, stream=None) -> DeviceArray:
+    """Writes the buffer a packed record describes into dst (same byte size; whatever dst held is overwritten, nothing
+    past it is touched).  Raises ValueError for a record that is inconsistent with itself or with dst."""
+    assert isinstance(dst, DeviceArray) and not dst.padded
+    mv = memoryview(record)
+    if len(mv) < 24:
+        raise ValueError("packed record: shorter than its header")
+    nbytes = int(np.frombuffer(mv[:8], "<u8")[0])
+    nchunks, nu, nl, zero = (int(v) for v in np.frombuffer(mv[8:24], "<u4"))
+    if nbytes != dst.nbytes or nbytes % 4 or nchunks != (nbytes + PACK_CHUNK - 1) // PACK_CHUNK or zero:
+        raise ValueError(f"packed record: header ({nbytes} bytes, {nchunks} chunks) does not describe a buffer of "
+                         f"{dst.nbytes} bytes")
+    o_cls, o_uni = 24, 24 + (nchunks + 7) // 8 * 8
+    o_lit = o_uni + (4 * nu + 7) // 8 * 8
+    if len(mv) != o_lit + nl * PACK_CHUNK:
+        raise ValueError(f"packed record: {len(mv)} bytes, its header says {o_lit + nl * PACK_CHUNK}")
+    cls = np.frombuffer(mv[o_cls:o_cls + nchunks], np.uint8)
+    if int((cls == 1).sum()) != nu or int((cls == 2).sum()) != nl or int((cls > 2).sum()):
+        raise ValueError("packed record: class array and counts disagree")
+    p = dict(nbytes=nbytes, nchunks=nchunks, classes=DeviceArray.from_numpy(cls))
+    _pack_rank(p, None, stream)
+    assert (p["nuniform"], p["nliteral"]) == (nu, nl)
+    uniform = DeviceArray.from_numpy(np.frombuffer(mv[o_uni:o_uni + 4 * nu], "<u4")) if nu else None
+    check("emf_hip_unpackFill",
+          _L.emf_hip_unpackFill(_ptr(dst), nbytes, _ptr(p["classes"]), _ptr(p["ranks"]), _ptr(uniform), nu,
+                                _stream(stream)))
+    for first in range(0, nl, arena_chunks):
+        count = min(arena_chunks, nl - first)
+        arena = DeviceArray.from_numpy(np.frombuffer(mv[o_lit + first * PACK_CHUNK:o_lit + (first + count) * PACK_CHUNK],
+                                                     np.uint8))
+        check("emf_hip_unpackLiterals",
+              _L.emf_hip_unpackLiterals(_ptr(dst), nbytes, _ptr(p["literal_chunks"]), first, count, _ptr(arena),
+                                        _stream(stream)))
+        synchronize()  # the arena is freed when the loop moves on
+    return dst

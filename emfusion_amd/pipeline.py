@@ -44,6 +44,13 @@ class FrameTimings(C.Structure):
         return {n: float(getattr(self, n)) for n, _ in self._fields_}
 
 
+class CheckpointStats(C.Structure):
+    """Mirror of emf_checkpoint_stats_t."""
+    _fields_ = [("raw_bytes", C.c_uint64), ("file_bytes", C.c_uint64), ("chunks", C.c_uint64 * 3),
+                ("ms_classify", C.c_double), ("ms_gather", C.c_double), ("ms_copy", C.c_double), ("ms_file", C.c_double),
+                ("ms_total", C.c_double), ("records", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class KernelSummary(C.Structure):
     _fields_ = [("launches", C.c_uint64), ("total_ms", C.c_double), ("units", C.c_double)]
 
@@ -57,7 +64,7 @@ _IMG_DTYPE = {0: ("float32", 3), 1: ("float32", 1), 2: ("float32", 1), 3: ("floa
               4: ("float32", 1), 5: ("float32", 3), 6: ("float32", 3), 7: ("uint8", 1),
               8: ("float32", 1), 9: ("float32", 1)}
 SHADING = dict(label=0, color=1)
-VOL = dict(tsdf=0, weights=1, fgprobs=2, fgmask=3, bricks=4, color=5)
+VOL = dict(tsdf=0, weights=1, fgprobs=2, fgmask=3, bricks=4, color=5, fgbg=6)
 
 _lib = None
 
@@ -96,6 +103,10 @@ def load() -> C.CDLL:
         "emf_fusion_destroy": [vp],
         "emf_fusion_reset": [vp],
         "emf_fusion_trim_pool": [C.POINTER(C.c_uint64)],
+        "emf_fusion_save_checkpoint": [vp, C.c_char_p, C.POINTER(CheckpointStats)],
+        "emf_fusion_load_checkpoint": [vp, C.c_char_p],
+        "emf_fusion_checkpoint_info": [C.c_char_p, C.c_char_p, C.c_size_t],
+        "emf_fusion_create_from_checkpoint": [C.c_char_p, vp, C.c_void_p, C.POINTER(vp)],
         "emf_fusion_describe_switches": [C.c_char_p, C.c_size_t],
         "emf_fusion_process_rgbd": [vp, fp, C.c_int32, C.c_int32],
         "emf_fusion_use_preproc_masks": [vp, C.c_char_p],
@@ -873,10 +884,40 @@ class Fusion:
                load().emf_fusion_get_volume(self._h, VOL[which], obj_id, C.byref(ptr), res))
         if which == "color":
             out = np.empty((res[2], res[1], res[0], 4), np.uint16)
+        elif which == "fgbg":
+            out = np.empty((res[2], res[1], res[0], 2), np.float32)
         else:
             out = np.empty((res[2], res[1], res[0]), np.uint8 if which in ("fgmask", "bricks") else np.float32)
         devmem.memcpy_d2h(out, ptr.value)
         return out
+
+    def save_checkpoint(self, path) -> dict:
+        """emf_fusion_save_checkpoint: the session's primary state, volumes packed losslessly on the device, written to
+        `path` (through path + ".tmp").  Returns raw_bytes / file_bytes, chunks per class and the milliseconds of the
+        stages (classify, gather: device; copy, file, total: host)."""
+        st = CheckpointStats()
+        _check("emf_fusion_save_checkpoint", load().emf_fusion_save_checkpoint(self._h, os.fspath(path).encode(), C.byref(st)))
+        return dict(raw_bytes=int(st.raw_bytes), file_bytes=int(st.file_bytes), records=int(st.records),
+                    chunks=dict(zero=int(st.chunks[0]), uniform=int(st.chunks[1]), literal=int(st.chunks[2])),
+                    ms=dict(classify=st.ms_classify, gather=st.ms_gather, copy=st.ms_copy, file=st.ms_file,
+                            total=st.ms_total))
+
+    def load_checkpoint(self, path):
+        """emf_fusion_load_checkpoint: reset, then restore the session saved in `path`; FusionError (EMF_E_ARG) with
+        the session untouched if the file does not fit this instance or is damaged."""
+        _check("emf_fusion_load_checkpoint", load().emf_fusion_load_checkpoint(self._h, os.fspath(path).encode()))
+
+    @classmethod
+    def from_checkpoint(cls, path, comm: Optional["Communicator"] = None):
+        """The instance built from the parameters a checkpoint was saved with, with the checkpoint loaded."""
+        self = cls.__new__(cls)
+        self.params = FusionParams()
+        self._comm = comm
+        self._h = C.c_void_p()
+        _check("emf_fusion_create_from_checkpoint",
+               load().emf_fusion_create_from_checkpoint(os.fspath(path).encode(), comm._h if comm else None,
+                                                        C.byref(self.params), C.byref(self._h)))
+        return self
 
     def background_overlap(self) -> bool:
         return load().emf_fusion_background_overlap(self._h) == 1
@@ -1001,6 +1042,15 @@ def trim_pool() -> int:
     n = C.c_uint64(0)
     _check("emf_fusion_trim_pool", load().emf_fusion_trim_pool(C.byref(n)))
     return int(n.value)
+
+
+def checkpoint_info(path) -> dict:
+    """emf_fusion_checkpoint_info: what a checkpoint file holds (no device needed); FusionError if it is not a
+    complete checkpoint."""
+    cap = 1 << 20
+    buf = C.create_string_buffer(cap)
+    _check("emf_fusion_checkpoint_info", load().emf_fusion_checkpoint_info(os.fspath(path).encode(), buf, cap))
+    return json.loads(buf.value.decode())
 
 
 def describe_switches() -> dict:

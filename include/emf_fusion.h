@@ -64,7 +64,8 @@ enum emf_fusion_volume {
     EMF_VOL_FGPROBS = 2,  /* f32, objects only */
     EMF_VOL_FGMASK = 3,   /* u8,  objects only */
     EMF_VOL_BRICKS = 4,   /* u8,  brick uniformity flags, ceil(N/4) per axis (res = brick grid) */
-    EMF_VOL_COLOR = 5     /* u16 x 4 (R, G, B, Wc in 8.8 fixed point), only after emf_fusion_set_color(on) */
+    EMF_VOL_COLOR = 5,    /* u16 x 4 (R, G, B, Wc in 8.8 fixed point), only after emf_fusion_set_color(on) */
+    EMF_VOL_FGBG = 6      /* f32 x 2 (foreground, background) counts, objects only: what fgprobs / fgmask derive from */
 };
 
 const char* emf_fusion_last_error_string(void);
@@ -344,6 +345,41 @@ int emf_fusion_batched_chunks(emf_fusion_t* h);
 int emf_fusion_upload_host_time(emf_fusion_t* h, double* seconds, uint64_t* frames);
 /* 1 if this rank holds object id's volume */
 int emf_fusion_owns_object(emf_fusion_t* h, int obj_id);
+
+/* ---- checkpoint and resume (emfusion_amd/csrc/core/Checkpoint.cpp holds the file format) ----
+ * save_checkpoint  waits for this instance's work, then writes its primary state -- parameters, frame count, camera
+ *                  pose, object table with existence and class bookkeeping, pose logs, the meshes kept of deleted
+ *                  objects and every volume (tsdf, weights, fg/bg counts, colour), packed losslessly on the device
+ *                  (include/emf_hip.h "Packed buffers") -- to <path>.tmp and renames it to path.  Changes nothing in
+ *                  the session.  stats may be NULL.
+ * load_checkpoint  acts as emf_fusion_reset followed by the restore; allowed at any time.  EMF_E_ARG, with the
+ *                  session left as it was, if the file was saved with another frame size, intrinsics, background
+ *                  resolution, voxel size or TSDF parameters, or if its magic, version, header checksum, section
+ *                  lengths or end marker are wrong (a truncated file).  The derived state (fgprobs / fgmask, sign
+ *                  maps, tile lists, brick flags, the back copy) is rebuilt; the switches of the emf_fusion_set_*
+ *                  calls and emf_fusion_enable_pose_log / setup_output are the caller's to set again, as at start.
+ *                  A restored session continues with the bytes of one that was never interrupted.
+ * Both return EMF_E_ARG on the sharded path.
+ * checkpoint_info  needs no device and no handle: the parameters, frame index, object ids and resolutions, colour
+ *                  flag and per-record chunk counts of a file as JSON ({"version", "file_bytes", "frame_index",
+ *                  "next_id", "color", "params": {...}, "objects": [{"id", "res", ...}], "kept_meshes", "logged_frames",
+ *                  "records": [{"id", "which", "offset", "bytes", "packed_bytes", "chunks": [zero, uniform, literal]}]});
+ *                  the same checks as load_checkpoint's, EMF_E_ARG if they fail or `capacity` is too small.
+ * create_from_checkpoint  the instance emf_fusion_create would build from the file's parameters (every field of
+ *                  emf::Params, also those emf_fusion_params_t does not carry), with the file loaded; params_out
+ *                  (may be NULL) receives the subset the struct carries. */
+typedef struct emf_checkpoint_stats {
+    uint64_t raw_bytes, file_bytes; /* bytes of the packed device buffers; size of the file */
+    uint64_t chunks[3];             /* 1 KiB chunks per class: zero, uniform, literal */
+    double ms_classify, ms_gather;  /* device time: classify + rank, gather */
+    double ms_copy, ms_file, ms_total; /* host time: device-to-host copies, file writes, the whole call */
+    uint32_t records, reserved;
+} emf_checkpoint_stats_t;
+int emf_fusion_save_checkpoint(emf_fusion_t* h, const char* path, emf_checkpoint_stats_t* stats);
+int emf_fusion_load_checkpoint(emf_fusion_t* h, const char* path);
+int emf_fusion_checkpoint_info(const char* path, char* json, size_t capacity);
+int emf_fusion_create_from_checkpoint(const char* path, emf_comm_t* comm, emf_fusion_params_t* params_out,
+                                      emf_fusion_t** out);
 
 /* ---- RCCL communicator for the object-sharded multi-GPU path (one process per GPU) ---- */
 #define EMF_COMM_UNIQUE_ID_BYTES 128

@@ -1114,6 +1114,60 @@ int emf_hip_meshWeldEmitBatched(const void* weld_scratch_dev, uint64_t soupVerti
                                 const int32_t* triangles, float* welded_vertices, float* welded_normals,
                                 uint8_t* welded_colors, int32_t* welded_triangles, emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Packed buffers (new behaviour: the reference has no checkpoint).  A device buffer of nbytes (a positive
+ * multiple of 4, at most 2^40, 16-byte aligned) is a sequence of 1024-byte CHUNKS of 256 32-bit words; the last
+ * chunk may be ragged and only its valid words are read, compared or written.  Classification compares bits,
+ * never floats:
+ *     class 0  every word is 0x00000000
+ *     class 1  every word equals the same non-zero word (-0.0f, a NaN pattern, the capped weight 64.0f ...)
+ *     class 2  anything else (a LITERAL chunk)
+ * The RANK of a class-1 / class-2 chunk is the number of chunks of its class before it, so the uniform words and
+ * the literals are in chunk order on every run (placement is by scan, never by atomics).  The packed record the
+ * host classes and emfusion_amd.ops.pack_buffer assemble from these arrays (little-endian):
+ *     u64 nbytes; u32 nchunks; u32 nuniform; u32 nliteral; u32 0
+ *     u8  class[nchunks]            zero-padded to a multiple of 8 bytes
+ *     u32 uniform[nuniform]         chunk order, zero-padded to a multiple of 8 bytes
+ *     u8  literal[nliteral][1024]   chunk order; a ragged last chunk is zero-padded
+ * All byte offsets are 64-bit.  No entry allocates, copies synchronously or waits.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Bytes of device scratch emf_hip_packRank needs for a buffer of nbytes (8 per 256 chunks, plus 8); 0 if nbytes is 0
+ * or above 2^40. */
+size_t emf_hip_packScratchBytes(uint64_t nbytes);
+
+/* classes[c] (u8) and words[c] (u32, the chunk's first word) for every chunk c; both hold nchunks =
+ * ceil(nbytes / 1024) entries.  One wave per chunk, every byte of src read once. */
+int emf_hip_packClassify(const void* src, uint64_t nbytes, uint8_t* classes, uint32_t* words, emf_stream_t stream);
+
+/* From a class array (device) of a buffer of nbytes:
+ *   ranks[c]           : nchunks u32, the rank of chunk c in its class (0 for class 0)
+ *   uniform[r]         : the word of the class-1 chunk of rank r (words: what emf_hip_packClassify wrote);
+ *                        words and uniform may both be NULL (restoring: the words come from the record)
+ *   literal_chunks[r]  : the chunk index of the literal of rank r
+ *   totals             : 2 u32 {nuniform, nliteral}
+ * uniform and literal_chunks hold nchunks entries (the totals are not known before the call).  A class byte
+ * above 2 counts as class 0 here and is skipped by the unpack entries. */
+int emf_hip_packRank(const uint8_t* classes, const uint32_t* words, uint64_t nbytes, void* scratch_dev, uint32_t* ranks,
+                     uint32_t* uniform, uint32_t* literal_chunks, uint32_t* totals, emf_stream_t stream);
+
+/* Copies the literal chunks of ranks [first, first + count) to arena (count * 1024 bytes, 16-byte aligned), a ragged
+ * last chunk zero-padded: a volume moves through a bounded arena, range by range.  first + count <= nchunks is
+ * checked here; that it is <= nliteral is the caller's (entries of literal_chunks past nliteral are not chunk
+ * indices; an index outside the buffer is skipped, never dereferenced).  count == 0 launches nothing. */
+int emf_hip_packGather(const void* src, uint64_t nbytes, const uint32_t* literal_chunks, uint32_t first, uint32_t count,
+                       void* arena, emf_stream_t stream);
+
+/* Unpack is emf_hip_unpackFill once plus emf_hip_unpackLiterals per rank range; together they write every valid
+ * word of dst exactly once -- no prior clear is needed and nothing past nbytes is written.
+ * unpackFill writes the class-0 chunks (zeros) and the class-1 chunks (uniform[ranks[c]], nuniform entries; a rank
+ * at or past nuniform writes nothing); unpackLiterals writes the literals of ranks [first, first + count) from
+ * arena, laid out as emf_hip_packGather leaves it. */
+int emf_hip_unpackFill(void* dst, uint64_t nbytes, const uint8_t* classes, const uint32_t* ranks, const uint32_t* uniform,
+                       uint32_t nuniform, emf_stream_t stream);
+int emf_hip_unpackLiterals(void* dst, uint64_t nbytes, const uint32_t* literal_chunks, uint32_t first, uint32_t count,
+                           const void* arena, emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
