@@ -4,7 +4,7 @@
 //
 //   emfusion_synth [--frames N] [--objects K] [--bg-res R] [--obj-res R] [--width W --height H]
 //                  [--materialize-gradients] [--autonomous] [--out DIR] [--export-frame-meshes] [--3d-vis]
-//                  [--weld-meshes]
+//                  [--weld-meshes] [--mesh-min-triangles N] [--mesh-largest-object]
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
 //                  [--bg-res R] [--bg-voxel M] [--obj-res R] [--volumes] --out DIR
 //   emfusion_synth --dir BASE/ [--colordir colour] [--depthdir depth] [--intrinsics fx fy cx cy] ... --out DIR
@@ -13,6 +13,10 @@
 // DIR/frame_meshes/bg/%04d.ply and DIR/frame_meshes/<id>/%04d.ply.
 // --weld-meshes: every mesh written (mesh_*.ply of the live models, frame_meshes/) is welded by grid edge on the device:
 // one vertex per edge instead of one per cube that touches it, the triangles re-indexed (EMFusion::setMeshWeld).
+// --mesh-min-triangles N / --mesh-largest-object: every mesh written is filtered by connected component on the device
+// (EMFusion::setMeshFilter): components of fewer than N triangles are removed from every model and, with
+// --mesh-largest-object, every component but the largest from the object meshes.  Either implies --weld-meshes; both
+// are set again after --resume (a checkpoint does not store them).
 // --3d-vis (needs --out): the reference's 3D view (apps/EM-Fusion.cpp:118-131) -- every frame is rendered (render())
 // together with the whole map seen from a viewer 1 m behind the world origin at 1024 x 768, and writeResults writes
 // those views as DIR/mesh_vis_out/%04d.png.  --3d-vis-eye x y z --3d-vis-target x y z place the viewer instead
@@ -82,6 +86,8 @@ static void set3dView(emf::EMFusion& emf, const emf::Params& params, const View3
 // The reference's main loop on a dataset (apps/EM-Fusion.cpp:100-156): a TUM sequence (`--sequence`, TUMRGBDReader) or a
 // Co-Fusion style directory (`--dir`, ImageReader: ColorNNNN.png + DepthNNNN.exr), as apps/EM-Fusion.cpp:118-131 chooses
 static bool weldMeshes = false;  // --weld-meshes
+static unsigned meshMinTriangles = 0;    // --mesh-min-triangles
+static bool meshLargestObject = false;   // --mesh-largest-object
 // --checkpoint PATH --checkpoint-every N: the session is saved to PATH after every N-th frame (EMFusion::saveCheckpoint);
 // --resume PATH: the instance is built from the file's parameters, the file is loaded and the input stream continues at
 // the stored frame index.  What the caller sets at start (output log, views, weld) is set again, as at start.
@@ -155,6 +161,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     else if (color) emf.enableColor(true);            // --color: the sequence's colour images go into the models
     color = emf.colorEnabled();
     emf.setMeshWeld(weldMeshes);
+    emf.setMeshFilter(meshMinTriangles, meshLargestObject);
     std::vector<uint8_t> rgb;
     if (!masks.empty()) emf.usePreprocMasks(masks);   // apps/EM-Fusion.cpp:115
     emf.setupOutput(frameMeshes, volumes);            // apps/EM-Fusion.cpp:112
@@ -238,6 +245,8 @@ int main(int argc, char** argv) {
         else if (a == "--3d-vis") view3d.on = true;
         else if (a == "--export-frame-meshes") frameMeshes = true;
         else if (a == "--weld-meshes") weldMeshes = true;
+        else if (a == "--mesh-min-triangles") meshMinTriangles = static_cast<unsigned>(std::max(next(), 0));
+        else if (a == "--mesh-largest-object") meshLargestObject = true;
         else if (a == "--color") color = true;
         else if (a == "--checkpoint" && i + 1 < argc) checkpointPath = argv[++i];
         else if (a == "--checkpoint-every") checkpointEvery = next();
@@ -315,6 +324,7 @@ int main(int argc, char** argv) {
         for (int k = 0; k < objects; ++k) maskDev.emplace_back(params.frameSize);
         emf.enableTimings(true);
         emf.setMeshWeld(weldMeshes);
+        emf.setMeshFilter(meshMinTriangles, meshLargestObject);
         if (!outDir.empty()) emf.setupOutput(frameMeshes, true);  // apps/EM-Fusion.cpp:112
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);

@@ -47,6 +47,12 @@ def main():
     ap.add_argument("--weld-meshes", dest="weld_meshes", action="store_true",
                     help="weld every mesh written (mesh_*.ply of the live models, frame_meshes/) by grid edge on the "
                          "device: one vertex per edge instead of one per cube that touches it")
+    ap.add_argument("--mesh-min-triangles", dest="mesh_min_triangles", type=int, default=0, metavar="N",
+                    help="remove connected components of fewer than N triangles from every mesh written, on the "
+                         "device (implies --weld-meshes)")
+    ap.add_argument("--mesh-largest-object", dest="mesh_largest_object", action="store_true",
+                    help="keep only the largest connected component of every object mesh written (the background "
+                         "keeps its pieces; implies --weld-meshes)")
     ap.add_argument("--color", action="store_true",
                     help="fuse the sequence's colour images into per-voxel colour: mesh_*.ply (and frame meshes, volume "
                          "dumps) carry colours")
@@ -104,6 +110,7 @@ def main():
         if args.color:
             fus.enable_color()
     fus.set_mesh_weld(args.weld_meshes)
+    fus.set_mesh_filter(args.mesh_min_triangles, args.mesh_largest_object)
     fus.set_ignore_person(args.ignore_person)
     fus.set_preprocess(True)
     fus.set_cleanup(True)

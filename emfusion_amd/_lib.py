@@ -169,6 +169,16 @@ SIGNATURES = {
     "emf_hip_meshWeldEmit": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _STREAM],
     "emf_hip_meshWeldEmitBatched": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, C.c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
                                     _FP, _STREAM],
+    "emf_hip_meshComponentsScratchBytes": [C.c_uint64, C.c_uint64],
+    "emf_hip_meshComponentsLabel": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, _FP, _STREAM],
+    "emf_hip_meshComponentsLabelBatched": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, C.c_int, _FP, _FP, _FP, _STREAM],
+    "emf_hip_meshComponentsFilterCount": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, _FP, _FP, _FP, _FP, _STREAM],
+    "emf_hip_meshComponentsFilterCountBatched": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, C.c_int, _FP, _FP, _FP, _FP,
+                                                 _FP, _FP, _FP, _STREAM],
+    "emf_hip_meshComponentsStatus": [_FP, C.c_uint64, C.c_uint64, _STREAM],
+    "emf_hip_meshComponentsEmit": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _STREAM],
+    "emf_hip_meshComponentsEmitBatched": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, C.c_int, _FP, _FP, _FP, _FP, _FP, _FP,
+                                          _FP, _FP, _STREAM],
     "emf_hip_packScratchBytes": [C.c_uint64],
     "emf_hip_packClassify": [_FP, C.c_uint64, _FP, _FP, _STREAM],
     "emf_hip_packRank": [_FP, _FP, C.c_uint64, _FP, _FP, _FP, _FP, _FP, _STREAM],
@@ -273,6 +283,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.emf_hip_meshScratchBytes.restype = C.c_size_t
     lib.emf_hip_meshScratchBytesBatched.restype = C.c_size_t
     lib.emf_hip_meshWeldScratchBytes.restype = C.c_size_t
+    lib.emf_hip_meshComponentsScratchBytes.restype = C.c_size_t
     lib.emf_hip_packScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateCullScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateDirtyMapBytes.restype = C.c_size_t

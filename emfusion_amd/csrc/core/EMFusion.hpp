@@ -301,7 +301,26 @@ public:
      * last mesh kept of a deleted object), so no tracking, life-cycle or clean-up decision depends on the switch.
      */
     void setMeshWeld(bool on) { meshWeld = on; }
-    /** getMesh() of the background (id 0) or of an object held by this rank (welded with setMeshWeld). */
+    /**
+     * The component filter (include/emf_hip.h "Mesh components"; new behaviour, off by default): wherever the weld
+     * switch acts -- getMesh(id), extractMeshes(), writeResults()' meshes of the live models, the per-frame export --
+     * connected components of fewer than minTriangles triangles are removed from every model's welded mesh and, with
+     * largestObjects, every component but the largest from the OBJECT meshes (a background legitimately has several
+     * pieces).  Labelled, filtered and compacted on the device behind the weld; only the filtered arrays travel to the
+     * host.  An active filter (minTriangles > 1 or largestObjects) implies the welded form whatever setMeshWeld says.
+     * An output form only, exactly as the weld: the life cycle's soup, the last mesh kept of a deleted object, poses,
+     * decisions, volumes and images do not depend on it.  Not stored in a checkpoint.
+     */
+    void setMeshFilter(uint32_t minTriangles, bool largestObjects) {
+        meshMinTriangles = minTriangles;
+        meshLargestObjects = largestObjects;
+    }
+    /** Per model id of the last getMesh() / extractMeshes() under an active filter: what the filter met and kept. */
+    const std::map<int, MeshFilterStats>& lastMeshFilter() const { return meshFilterStats; }
+    /** Labels and component sizes of model id's welded, unfiltered mesh (TSDF::getMeshComponents). */
+    MeshComponents getMeshComponents(int id);
+    /** getMesh() of the background (id 0) or of an object held by this rank (welded with setMeshWeld, filtered with
+     *  setMeshFilter). */
     Mesh getMesh(int id);
     /**
      * getMesh() of each listed model (0 = background, else a live object id), in list order, in one pass over the
@@ -541,6 +560,14 @@ private:
     DeviceBuffer meshTableDev, meshCountsDev, meshScratch, meshArena;  // extractMeshes' pooled buffers
     bool meshWeld = false;                                 // setMeshWeld
     DeviceBuffer meshWeldScratch;                          // keys, welded counts / bases and the weld's scratch
+    uint32_t meshMinTriangles = 0;                         // setMeshFilter
+    bool meshLargestObjects = false;
+    std::map<int, MeshFilterStats> meshFilterStats;        // lastMeshFilter
+    DeviceBuffer meshFilterScratch, meshFilterArena;       // the filter's counts + scratch, its kept arrays
+    MeshFilter meshFilterFor(int id) const {               // the background keeps its pieces
+        return MeshFilter{meshMinTriangles, meshLargestObjects && id != 0};
+    }
+    bool meshFilterActive() const { return meshMinTriangles > 1 || meshLargestObjects; }
     void extractWelded(const std::vector<int>& ids, const std::vector<int32_t>& res, uint64_t nv, uint64_t nt,
                        std::vector<Mesh>& out);
     bool expVols = false;                                  // setupOutput: keep / dump volumes too

@@ -238,6 +238,7 @@ std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
     const int n = static_cast<int>(ids.size());
     std::vector<Mesh> out(ids.size());
     for (Mesh& m : out) m.colored = colorOn;
+    meshFilterStats.clear();
     if (n == 0) return out;
     if (n > EMF_MAX_MODELS) throw HipError("EMFusion::extractMeshes: " + std::to_string(n) + " models", EMF_E_LIMIT);
     if (meshHost.empty())
@@ -280,7 +281,11 @@ std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
     hipCheck(hipMemcpyAsync(counts, countsDev, meshCountsDev.bytes(), hipMemcpyDeviceToHost, main.get()), "mesh counts D2H");
     main.waitForCompletion();  // the one wait before the emit: the outputs' sizes
     const uint64_t nv = bases[2 * n], nt = bases[2 * n + 1];
-    if (nv == 0) return out;
+    if (nv == 0) {  // nothing to mesh: the filter met nothing
+        if (meshFilterActive())
+            for (int id : ids) meshFilterStats[id] = MeshFilterStats{};
+        return out;
+    }
     const size_t vb = 3 * sizeof(float) * nv, tb = 4 * sizeof(int32_t) * std::max<uint64_t>(nt, 1);
     if (meshArena.bytes() < 2 * vb + tb) meshArena = DeviceBuffer(2 * vb + tb);
     float* vDev = meshArena.as<float>();
@@ -289,7 +294,7 @@ std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
     emfCheck(emf_hip_meshEmitBatched(meshTableDev.as<emf_model_t>(), res.data(), n, meshScratch.data(), vDev, nDev, tDev,
                                      main.abi()),
              "meshEmitBatched");
-    if (meshWeld) {  // the welded form of the same soup: welded on the device, then only the welded arrays travel
+    if (meshWeld || meshFilterActive()) {  // the welded form of the same soup: welded (and filtered) on the device
         extractWelded(ids, res, nv, nt, out);
         return out;
     }
@@ -330,6 +335,8 @@ std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
 // meshArena ([vertices][normals][triangles], as the emit wrote it) and the counting scratch is still valid: colours and
 // edge keys walk the surface chunks once more, the weld runs on the keys, and the welded vertex arrays land behind the
 // soup in the same arena (grown when needed; the soup is copied over, it is a quarter of what a frame's soup D2H was).
+// With setMeshFilter the components are labelled, filtered and compacted behind the weld (include/emf_hip.h "Mesh
+// components") and the kept arrays are what travels.
 void EMFusion::extractWelded(const std::vector<int>& ids, const std::vector<int32_t>& res, uint64_t nv, uint64_t nt,
                              std::vector<Mesh>& out) {
     const int n = static_cast<int>(ids.size());
@@ -394,26 +401,95 @@ void EMFusion::extractWelded(const std::vector<int>& ids, const std::vector<int3
                                          colorOn ? cDev.as<uint8_t>() : nullptr, tDev, wvDev, wnDev,
                                          colorOn ? wcDev.as<uint8_t>() : nullptr, tDev, main.abi()),
              "meshWeldEmitBatched");
-    meshStage.grow(2 * wvb + tb);
+    // what travels: the welded arrays, or the filter's kept arrays
+    struct Slice {
+        size_t v0, vc, t0, tc;
+    };
+    std::vector<Slice> slices(n);
+    for (int k = 0; k < n; ++k) slices[k] = Slice{wBases[k], wCounts[k], bases[2 * k + 1], counts[k].triangles};
+    const float* outV = wvDev;
+    const float* outN = wnDev;
+    const int32_t* outT = tDev;
+    const uint8_t* outC = colorOn ? wcDev.as<uint8_t>() : nullptr;
+    uint64_t outNv = nw, outNt = nt;
+    DeviceBuffer kcDev;
+    if (meshFilterActive()) {
+        const size_t ccBytes = emf_hip_meshComponentsScratchBytes(nw, nt);
+        if (ccBytes == 0) throw HipError("EMFusion::extractMeshes: " + std::to_string(nw) + " welded vertices", EMF_E_LIMIT);
+        // [kept bases u64 x 2 (MAX + 1)][kept counts u32 x 2 MAX][components u32 x MAX][kept components u32 x MAX][scratch]
+        const size_t kbBytes = sizeof(uint64_t) * 2 * (EMF_MAX_MODELS + 1), kcBytes = sizeof(uint32_t) * 2 * EMF_MAX_MODELS,
+                     cBytes = sizeof(uint32_t) * EMF_MAX_MODELS, head = kbBytes + kcBytes + 2 * cBytes;
+        if (meshFilterScratch.bytes() < head + ccBytes) meshFilterScratch = DeviceBuffer(head + ccBytes);
+        auto* kBasesDev = meshFilterScratch.as<uint64_t>();
+        auto* kCountsDev = reinterpret_cast<uint32_t*>(kBasesDev + 2 * (EMF_MAX_MODELS + 1));
+        uint32_t* compsDev = kCountsDev + 2 * EMF_MAX_MODELS;
+        uint32_t* kCompsDev = compsDev + EMF_MAX_MODELS;
+        void* ccScratch = reinterpret_cast<char*>(meshFilterScratch.data()) + head;
+        std::vector<uint32_t> mins(n, meshMinTriangles);
+        std::vector<uint8_t> largest(n);
+        for (int k = 0; k < n; ++k) largest[k] = meshFilterFor(ids[k]).largestOnly ? 1 : 0;
+        emfCheck(emf_hip_meshComponentsLabelBatched(tDev, nw, nt, basesDev, wBasesDev, n, ccScratch, nullptr, nullptr,
+                                                    main.abi()),
+                 "meshComponentsLabelBatched");
+        emfCheck(emf_hip_meshComponentsFilterCountBatched(tDev, nw, nt, basesDev, wBasesDev, n, ccScratch, mins.data(),
+                                                          largest.data(), kCountsDev, kBasesDev, compsDev, kCompsDev,
+                                                          main.abi()),
+                 "meshComponentsFilterCountBatched");
+        std::vector<uint64_t> kBases(2 * (n + 1));
+        std::vector<uint32_t> kCounts(2 * n), comps(n), kComps(n);
+        hipCheck(hipMemcpyAsync(kBases.data(), kBasesDev, sizeof(uint64_t) * 2 * (n + 1), hipMemcpyDeviceToHost, main.get()),
+                 "kept bases D2H");
+        hipCheck(hipMemcpyAsync(kCounts.data(), kCountsDev, sizeof(uint32_t) * 2 * n, hipMemcpyDeviceToHost, main.get()),
+                 "kept counts D2H");
+        hipCheck(hipMemcpyAsync(comps.data(), compsDev, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, main.get()),
+                 "components D2H");
+        hipCheck(hipMemcpyAsync(kComps.data(), kCompsDev, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, main.get()),
+                 "kept components D2H");
+        emfCheck(emf_hip_meshComponentsStatus(ccScratch, nw, nt, main.abi()), "meshComponents (indices)");  // waits
+        const uint64_t knv = kBases[2 * n], knt = kBases[2 * n + 1];
+        const size_t kvb = 3 * sizeof(float) * std::max<uint64_t>(knv, 1), ktb = 4 * sizeof(int32_t) * std::max<uint64_t>(knt, 1);
+        if (meshFilterArena.bytes() < 2 * kvb + ktb) meshFilterArena = DeviceBuffer(2 * kvb + ktb);
+        float* kvDev = meshFilterArena.as<float>();
+        float* knDev = kvDev + 3 * std::max<uint64_t>(knv, 1);
+        int32_t* ktDev = reinterpret_cast<int32_t*>(knDev + 3 * std::max<uint64_t>(knv, 1));
+        if (colorOn) kcDev = DeviceBuffer(3 * std::max<uint64_t>(knv, 1));
+        emfCheck(emf_hip_meshComponentsEmitBatched(ccScratch, nw, nt, basesDev, wBasesDev, n, wvDev, wnDev, outC, tDev, kvDev,
+                                                   knDev, colorOn ? kcDev.as<uint8_t>() : nullptr, ktDev, main.abi()),
+                 "meshComponentsEmitBatched");
+        for (int k = 0; k < n; ++k) {
+            meshFilterStats[ids[k]] = MeshFilterStats{comps[k], kComps[k], counts[k].triangles, kCounts[2 * k + 1]};
+            slices[k] = Slice{kBases[2 * k], kCounts[2 * k], kBases[2 * k + 1], kCounts[2 * k + 1]};
+        }
+        outV = kvDev;
+        outN = knDev;
+        outT = ktDev;
+        outC = colorOn ? kcDev.as<uint8_t>() : nullptr;
+        outNv = knv;
+        outNt = knt;
+    }
+    const size_t ovb = 3 * sizeof(float) * outNv;
+    meshStage.grow(2 * ovb + 4 * sizeof(int32_t) * std::max<uint64_t>(outNt, 1));
     float* vHost = meshStage.as<float>();
-    float* nHost = vHost + 3 * nw;
-    int32_t* tHost = reinterpret_cast<int32_t*>(nHost + 3 * nw);
-    hipCheck(hipMemcpyAsync(vHost, wvDev, wvb, hipMemcpyDeviceToHost, main.get()), "welded vertices D2H");
-    hipCheck(hipMemcpyAsync(nHost, wnDev, wvb, hipMemcpyDeviceToHost, main.get()), "welded normals D2H");
-    if (nt) hipCheck(hipMemcpyAsync(tHost, tDev, 4 * sizeof(int32_t) * nt, hipMemcpyDeviceToHost, main.get()), "welded triangles D2H");
+    float* nHost = vHost + 3 * outNv;
+    int32_t* tHost = reinterpret_cast<int32_t*>(nHost + 3 * outNv);
+    if (outNv) {
+        hipCheck(hipMemcpyAsync(vHost, outV, ovb, hipMemcpyDeviceToHost, main.get()), "welded vertices D2H");
+        hipCheck(hipMemcpyAsync(nHost, outN, ovb, hipMemcpyDeviceToHost, main.get()), "welded normals D2H");
+    }
+    if (outNt) hipCheck(hipMemcpyAsync(tHost, outT, 4 * sizeof(int32_t) * outNt, hipMemcpyDeviceToHost, main.get()), "welded triangles D2H");
     std::vector<uint8_t> cHost;
-    if (colorOn) {
-        cHost.resize(3 * nw);
-        hipCheck(hipMemcpyAsync(cHost.data(), wcDev.data(), 3 * nw, hipMemcpyDeviceToHost, main.get()), "welded colours D2H");
+    if (colorOn && outNv) {
+        cHost.resize(3 * outNv);
+        hipCheck(hipMemcpyAsync(cHost.data(), outC, 3 * outNv, hipMemcpyDeviceToHost, main.get()), "welded colours D2H");
     }
     main.waitForCompletion();
-    for (int k = 0; k < n; ++k) {  // model k's slice is its own welded mesh (local triangle indices)
-        const size_t v0 = wBases[k], t0 = bases[2 * k + 1];
+    for (int k = 0; k < n; ++k) {  // model k's slice is its own welded (filtered) mesh (local triangle indices)
+        const Slice& s = slices[k];
         Mesh& m = out[k];
-        m.cloud.assign(vHost + 3 * v0, vHost + 3 * (v0 + wCounts[k]));
-        m.normals.assign(nHost + 3 * v0, nHost + 3 * (v0 + wCounts[k]));
-        m.polygons.assign(tHost + 4 * t0, tHost + 4 * (t0 + counts[k].triangles));
-        if (!cHost.empty()) m.colors.assign(cHost.begin() + 3 * v0, cHost.begin() + 3 * (v0 + wCounts[k]));
+        m.cloud.assign(vHost + 3 * s.v0, vHost + 3 * (s.v0 + s.vc));
+        m.normals.assign(nHost + 3 * s.v0, nHost + 3 * (s.v0 + s.vc));
+        m.polygons.assign(tHost + 4 * s.t0, tHost + 4 * (s.t0 + s.tc));
+        if (!cHost.empty()) m.colors.assign(cHost.begin() + 3 * s.v0, cHost.begin() + 3 * (s.v0 + s.vc));
     }
 }
 
@@ -430,10 +506,26 @@ void EMFusion::storeFrameMeshes() {
 
 Mesh EMFusion::getMesh(int id) {
     synchronize();
-    if (id == 0) return meshWeld ? background.getWeldedMesh() : background.getMesh();
+    meshFilterStats.clear();
+    TSDF* model = id == 0 ? &background : nullptr;
     for (auto& o : objects)
-        if (o.getID() == id) return meshWeld ? o.getWeldedMesh() : o.getMesh();
-    throw HipError("EMFusion::getMesh: no object " + std::to_string(id) + " on this rank", EMF_E_ARG);
+        if (o.getID() == id) model = &o;
+    if (!model) throw HipError("EMFusion::getMesh: no object " + std::to_string(id) + " on this rank", EMF_E_ARG);
+    if (meshFilterActive()) {
+        MeshFilterStats stats;
+        Mesh m = model->getFilteredMesh(meshFilterFor(id), &stats);
+        meshFilterStats[id] = stats;
+        return m;
+    }
+    return meshWeld ? model->getWeldedMesh() : model->getMesh();
+}
+
+MeshComponents EMFusion::getMeshComponents(int id) {
+    synchronize();
+    if (id == 0) return background.getMeshComponents();
+    for (auto& o : objects)
+        if (o.getID() == id) return o.getMeshComponents();
+    throw HipError("EMFusion::getMeshComponents: no object " + std::to_string(id) + " on this rank", EMF_E_ARG);
 }
 
 }  // namespace emf

@@ -165,6 +165,14 @@ int ObjTSDF::getClassID() const {
 
 Mesh ObjTSDF::getMesh() { return extractMesh(fgVolMask.as<uint8_t>()); }
 Mesh ObjTSDF::getWeldedMesh() { return extractMesh(fgVolMask.as<uint8_t>(), true); }
+Mesh ObjTSDF::getFilteredMesh(const MeshFilter& filter, MeshFilterStats* stats) {
+    return extractMesh(fgVolMask.as<uint8_t>(), true, &filter, stats);
+}
+MeshComponents ObjTSDF::getMeshComponents() {
+    MeshComponents c;
+    extractMesh(fgVolMask.as<uint8_t>(), true, nullptr, nullptr, &c);
+    return c;
+}
 
 void ObjTSDF::describe(emf_model_t& m) const {
     TSDF::describe(m);

@@ -68,6 +68,8 @@ public:
     /** Mesh of the foreground part only (reference ObjTSDF::getMesh, ObjTSDF.cpp:247-268). */
     Mesh getMesh() override;
     Mesh getWeldedMesh() override;
+    Mesh getFilteredMesh(const MeshFilter& filter, MeshFilterStats* stats = nullptr) override;
+    MeshComponents getMeshComponents() override;
 
     std::vector<float> getFgProbVol();
     std::vector<uint8_t> getFgVolMask();

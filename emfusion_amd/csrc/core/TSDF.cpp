@@ -345,10 +345,22 @@ void TSDF::describe(emf_model_t& m) const {
 
 Mesh TSDF::getMesh() { return extractMesh(nullptr); }
 Mesh TSDF::getWeldedMesh() { return extractMesh(nullptr, true); }
+Mesh TSDF::getFilteredMesh(const MeshFilter& filter, MeshFilterStats* stats) {
+    return extractMesh(nullptr, true, &filter, stats);
+}
+MeshComponents TSDF::getMeshComponents() {
+    MeshComponents c;
+    extractMesh(nullptr, true, nullptr, nullptr, &c);
+    return c;
+}
 
 // count -> read back two numbers -> emit; the gradient volume is used when it is materialised.  weld: keys, first
-// occurrences and ranks on the device, one more number read back, then the welded arrays are what is downloaded
-Mesh TSDF::extractMesh(const uint8_t* fgVolMask, bool weld) {
+// occurrences and ranks on the device, one more number read back, then the welded arrays are what is downloaded.
+// filter (an active one, on the welded mesh): labels, keep flags and ranks on the device, the kept counts read back,
+// then the filtered arrays are what is downloaded.  components: the welded mesh's labels and sizes instead.
+Mesh TSDF::extractMesh(const uint8_t* fgVolMask, bool weld, const MeshFilter* filter, MeshFilterStats* stats,
+                       MeshComponents* components) {
+    if (stats) *stats = MeshFilterStats{};
     hipCheck(hipDeviceSynchronize(), "hipDeviceSynchronize");
     Stream& s = Stream::Null();
     DeviceBuffer scratch(std::max<size_t>(emf_hip_meshScratchBytes(volumeRes.val), 8));
@@ -397,6 +409,61 @@ Mesh TSDF::extractMesh(const uint8_t* fgVolMask, bool weld) {
         n = std::move(wn);
         if (!c.empty()) c = std::move(wc);
         counts.vertices = welded;
+        const bool filtering = filter && filter->active();
+        if (filtering || components) {
+            const uint64_t nw = welded, nt = counts.triangles;
+            const size_t ccBytes = emf_hip_meshComponentsScratchBytes(nw, nt);
+            if (ccBytes == 0) throw HipError("TSDF::getFilteredMesh: " + std::to_string(nw) + " welded vertices", EMF_E_LIMIT);
+            DeviceBuffer ccScratch(ccBytes), labelsDev, sizesDev;
+            if (components) {
+                labelsDev = DeviceBuffer(std::max<size_t>(nw, 1) * sizeof(int32_t));
+                sizesDev = DeviceBuffer(std::max<size_t>(nw, 1) * sizeof(uint32_t));
+            }
+            emfCheck(emf_hip_meshComponentsLabel(t.as<int32_t>(), nw, nt, ccScratch.data(),
+                                                 components ? labelsDev.as<int32_t>() : nullptr,
+                                                 components ? sizesDev.as<uint32_t>() : nullptr, s.abi()),
+                     "TSDF::getFilteredMesh (label)");
+            if (components) {
+                emfCheck(emf_hip_meshComponentsStatus(ccScratch.data(), nw, nt, s.abi()), "TSDF::getMeshComponents");
+                components->labels.resize(nw);
+                components->sizes.resize(nw);
+                if (nw) {
+                    hipCheck(hipMemcpy(components->labels.data(), labelsDev.data(), nw * sizeof(int32_t), hipMemcpyDeviceToHost),
+                             "labels D2H");
+                    hipCheck(hipMemcpy(components->sizes.data(), sizesDev.data(), nw * sizeof(uint32_t), hipMemcpyDeviceToHost),
+                             "sizes D2H");
+                }
+            }
+            if (filtering) {
+                const uint32_t minTriangles = filter->minTriangles;
+                const uint8_t largestOnly = filter->largestOnly ? 1 : 0;
+                DeviceBuffer outDev(4 * sizeof(uint32_t));  // kept vertices, kept triangles, components, kept components
+                uint32_t* o = outDev.as<uint32_t>();
+                emfCheck(emf_hip_meshComponentsFilterCount(t.as<int32_t>(), nw, nt, ccScratch.data(), &minTriangles,
+                                                           &largestOnly, o, o + 2, o + 3, s.abi()),
+                         "TSDF::getFilteredMesh (count)");
+                uint32_t kept[4] = {0, 0, 0, 0};
+                outDev.download(kept, s);
+                emfCheck(emf_hip_meshComponentsStatus(ccScratch.data(), nw, nt, s.abi()), "TSDF::getFilteredMesh (indices)");
+                DeviceBuffer kv(std::max<size_t>(kept[0], 1) * 3 * sizeof(float)), kn(std::max<size_t>(kept[0], 1) * 3 * sizeof(float)),
+                    kt(std::max<size_t>(kept[1], 1) * 4 * sizeof(int32_t)), kc;
+                if (!c.empty()) kc = DeviceBuffer(std::max<size_t>(kept[0], 1) * 3);
+                emfCheck(emf_hip_meshComponentsEmit(ccScratch.data(), nw, nt, v.as<float>(), n.as<float>(),
+                                                    c.empty() ? nullptr : c.as<uint8_t>(), t.as<int32_t>(), kv.as<float>(),
+                                                    kn.as<float>(), kc.empty() ? nullptr : kc.as<uint8_t>(),
+                                                    kt.as<int32_t>(), s.abi()),
+                         "TSDF::getFilteredMesh (emit)");
+                s.waitForCompletion();  // the scratch and the welded arrays go out of scope below
+                if (stats) *stats = MeshFilterStats{kept[2], kept[3], counts.triangles, kept[1]};
+                v = std::move(kv);
+                n = std::move(kn);
+                t = std::move(kt);
+                if (!c.empty()) c = std::move(kc);
+                counts.vertices = kept[0];
+                counts.triangles = kept[1];
+                if (kept[0] == 0) return mesh;  // nothing kept: an empty mesh (the buffers above hold one spare element)
+            }
+        }
     }
     mesh.cloud.resize(size_t(counts.vertices) * 3);
     mesh.normals.resize(size_t(counts.vertices) * 3);

@@ -89,6 +89,13 @@ public:
      * measures on a mesh (extent statistics count duplicates as the reference does) goes through getMesh().
      */
     virtual Mesh getWeldedMesh();
+    /**
+     * getWeldedMesh() with its small connected components removed on the device (include/emf_hip.h "Mesh
+     * components"): only the filtered arrays travel to the host.  An output form only, as getWeldedMesh().
+     */
+    virtual Mesh getFilteredMesh(const MeshFilter& filter, MeshFilterStats* stats = nullptr);
+    /** Labels and component sizes of getWeldedMesh()'s vertices, unfiltered. */
+    virtual MeshComponents getMeshComponents();
 
     /** Host copies in the reference layout, (Nz*Ny) rows x Nx cols (TSDF.cpp:398-408). */
     std::vector<float> getTSDF() const;
@@ -167,7 +174,8 @@ public:
     float reciprocal() const { return rcpVoxel; }
 
 protected:
-    Mesh extractMesh(const uint8_t* fgVolMask, bool weld = false);
+    Mesh extractMesh(const uint8_t* fgVolMask, bool weld = false, const MeshFilter* filter = nullptr,
+                     MeshFilterStats* stats = nullptr, MeshComponents* components = nullptr);
     TSDFParams params;
     Vec3i volumeRes;
     float voxelSize;

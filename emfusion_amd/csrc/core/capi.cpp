@@ -22,6 +22,7 @@ struct emf_fusion {
     std::vector<emf_image_t> queuedMasks, queuedInstances;
     std::vector<std::vector<double>> queuedScores;
     emf::Mesh mesh;  // result of the last emf_fusion_extract_mesh
+    emf::MeshComponents components;  // result of the last emf_fusion_mesh_components
     std::vector<emf::Mesh> meshList;  // result of the last emf_fusion_extract_meshes
 };
 struct emf_synth {
@@ -319,6 +320,49 @@ int emf_fusion_set_color(emf_fusion_t* h, int on) {
 int emf_fusion_set_mesh_weld(emf_fusion_t* h, int on) {
     REQ(h);
     return guarded([&] { h->impl->setMeshWeld(on != 0); });
+}
+
+int emf_fusion_set_mesh_filter(emf_fusion_t* h, uint32_t min_triangles, int largest_objects) {
+    REQ(h);
+    return guarded([&] { h->impl->setMeshFilter(min_triangles, largest_objects != 0); });
+}
+
+int emf_fusion_mesh_components(emf_fusion_t* h, int id, uint32_t* num_vertices) {
+    REQ(h);
+    REQ(num_vertices);
+    return guarded([&] {
+        h->components = h->impl->getMeshComponents(id);
+        *num_vertices = static_cast<uint32_t>(h->components.labels.size());
+    });
+}
+
+int emf_fusion_copy_mesh_components(emf_fusion_t* h, int32_t* labels, uint32_t* sizes) {
+    REQ(h);
+    return guarded([&] {
+        if (labels) std::copy(h->components.labels.begin(), h->components.labels.end(), labels);
+        if (sizes) std::copy(h->components.sizes.begin(), h->components.sizes.end(), sizes);
+    });
+}
+
+int emf_fusion_last_mesh_filter(emf_fusion_t* h, int32_t* ids, uint32_t* stats, int capacity, int32_t* count) {
+    REQ(h);
+    REQ(count);
+    return guarded([&] {
+        const auto& last = h->impl->lastMeshFilter();
+        *count = static_cast<int32_t>(last.size());
+        int k = 0;
+        for (const auto& kv : last) {
+            if (k >= capacity) break;
+            if (ids) ids[k] = kv.first;
+            if (stats) {
+                stats[4 * k] = kv.second.components;
+                stats[4 * k + 1] = kv.second.keptComponents;
+                stats[4 * k + 2] = kv.second.triangles;
+                stats[4 * k + 3] = kv.second.keptTriangles;
+            }
+            ++k;
+        }
+    });
 }
 
 int emf_fusion_set_color_image(emf_fusion_t* h, const emf_image_t* rgb_dev) {

@@ -114,6 +114,24 @@ struct Mesh {
     size_t triangles() const { return polygons.size() / 4; }
 };
 
+/** The component filter of a welded mesh (include/emf_hip.h "Mesh components"). */
+struct MeshFilter {
+    uint32_t minTriangles = 0;  // components with fewer triangles are dropped (<= 1: none)
+    bool largestOnly = false;   // only the largest component by triangles, a tie to the smaller label
+    bool active() const { return minTriangles > 1 || largestOnly; }
+};
+
+/** What the filter met and kept in one model's welded mesh. */
+struct MeshFilterStats {
+    uint32_t components = 0, keptComponents = 0, triangles = 0, keptTriangles = 0;
+};
+
+/** Per welded vertex: the smallest welded index of its component and that component's triangles. */
+struct MeshComponents {
+    std::vector<int32_t> labels;
+    std::vector<uint32_t> sizes;
+};
+
 struct Size {
     int width = 0, height = 0;
     Size() = default;

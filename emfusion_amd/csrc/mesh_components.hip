@@ -1,0 +1,597 @@
+// mesh_components.hip -- connected components of the welded mesh and the component filter (include/emf_hip.h
+// "Mesh components").
+//
+// Works on the welded index buffer and the soup / welded bases mesh_weld.hip leaves behind; it never sees a volume.
+// Two welded vertices are connected when a triangle has both -- by INDEX: vertices of different grid edges that
+// coincide at a voxel corner stay distinct, as the weld keeps them.  A vertex's label is the smallest model-local
+// welded index of its component, a component's size its number of triangles.
+//
+// The scratch is linear in welded vertices plus triangles, under 13 bytes per vertex + 5 per triangle + 6 KiB:
+//   [parent: u32 x nv][size: u32 x nv][vexcl: u32 x nv][texcl: u32 x nt][vsums: u32 x (vblocks + 1)]
+//   [tsums: u32 x (tblocks + 1)][best: u64 x MAX][components: u32 x MAX][kept components: u32 x MAX][flag]
+//   k_cc_init     parent[i] = i, size[i] = 0
+//   k_cc_hook     per triangle: unite(a, b), unite(a, c) in a lock-free union-find over GLOBAL welded indices with
+//                 parent[x] <= x always: find both roots, CAS the larger root's parent from itself to the smaller
+//                 root; on failure go on from what the CAS saw.  Every step of every loop moves to a strictly
+//                 smaller index, so each loop is bounded by construction and no lane waits for another lane's
+//                 progress (no lock, no spin-wait: a wave runs in lock-step).  find halves the path it walks with
+//                 atomicMin -- parent[x] only ever decreases, and only to an ancestor.
+//   k_cc_flatten  parent[i] := root of i.  A root is the minimum index of its tree, whatever order the hooks ran in.
+//   k_cc_count    size[root] += 1 per triangle: a wave whose triangles share one root adds its lane count once, the
+//                 workgroup's waves are merged through LDS, lanes of a mixed wave add for themselves
+//   k_cc_labels   labels[i] = root - the model's welded base, sizes[i] = size[root]   (optional outputs)
+//   k_cc_select   per root: atomicMax(best[model], size << 32 | ~label) -- the largest component, ties to the
+//                 smaller label
+//   k_cc_flags    keep flags of vertex i and triangle i, summed per workgroup; roots count the model's components
+//   k_cc_scan     two workgroups: the exclusive scans of the two sums arrays (mesh_scan.hpp)
+//   k_cc_rank     vexcl[i], texcl[i] = kept vertices / triangles before i; per-model kept counts and bases are the
+//                 ranks at the models' bases
+//   k_cc_emit     kept vertices copy position, normal and colour to their rank; kept triangles are rewritten
+// A triangle index outside its model's welded range is never dereferenced: the triangle joins nothing, counts
+// nowhere, is dropped by the filter, and raises `flag` (emf_hip_meshComponentsStatus -> EMF_E_ARG).
+// All atomics are ordinary global atomics on vector memory; every output is a pure function of the index buffer.
+#include "common.hpp"
+#include "mesh_scan.hpp"
+
+namespace emf_hip {
+namespace {
+
+constexpr int kCcBlock = kScanBlock;
+
+struct CcArgs {
+    unsigned* parent;
+    unsigned* size;
+    unsigned* vexcl;
+    unsigned* texcl;
+    unsigned* vsums;  // vblocks + 1
+    unsigned* tsums;  // tblocks + 1
+    unsigned long long* best;  // EMF_MAX_MODELS
+    unsigned* ncomp;           // EMF_MAX_MODELS
+    unsigned* nkept;           // EMF_MAX_MODELS
+    unsigned* flag;
+    unsigned nv, nt, vblocks, tblocks;
+};
+
+inline size_t align16(size_t b) { return (b + 15) & ~static_cast<size_t>(15); }
+
+inline size_t place(CcArgs& a, unsigned long long nv, unsigned long long nt, void* scratch) {
+    a.nv = static_cast<unsigned>(nv);
+    a.nt = static_cast<unsigned>(nt);
+    a.vblocks = ceil_div(nv, kCcBlock);
+    a.tblocks = ceil_div(nt, kCcBlock);
+    char* p = static_cast<char*>(scratch);
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char* q = p + off;
+        off += align16(bytes);
+        return q;
+    };
+    a.parent = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nv));
+    a.size = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nv));
+    a.vexcl = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nv));
+    a.texcl = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nt));
+    a.vsums = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * (a.vblocks + 1)));
+    a.tsums = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * (a.tblocks + 1)));
+    a.best = reinterpret_cast<unsigned long long*>(take(sizeof(unsigned long long) * EMF_MAX_MODELS));
+    a.ncomp = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * EMF_MAX_MODELS));
+    a.nkept = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * EMF_MAX_MODELS));
+    a.flag = reinterpret_cast<unsigned*>(take(16));
+    return off;
+}
+
+// the models of a table launch (device arrays as the weld leaves them) or, for one model, none
+struct CcModels {
+    const unsigned long long* soupBases;    // 2 (n + 1) interleaved: the triangle bases are the odd entries
+    const unsigned long long* weldedBases;  // n + 1
+    unsigned n;
+};
+
+// each model's criteria, by value: the host arrays need not outlive the call
+struct CcCriteria {
+    unsigned minTriangles[EMF_MAX_MODELS];
+    unsigned char largestOnly[EMF_MAX_MODELS];
+};
+
+// the last model whose base is <= x (empty models share a base with their successor: the one that holds x wins)
+__device__ __forceinline__ unsigned model_of(const unsigned long long* bases, unsigned stride, unsigned n,
+                                             unsigned long long x) {
+    unsigned lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (x >= bases[stride * mid]) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+struct Range {
+    unsigned model, lo, hi;  // the model's welded vertices are [lo, hi)
+};
+
+__device__ __forceinline__ Range range_of_vertex(const CcArgs& a, const CcModels& md, unsigned g) {
+    if (!md.weldedBases) return Range{0u, 0u, a.nv};
+    const unsigned m = model_of(md.weldedBases, 1, md.n, g);
+    return Range{m, static_cast<unsigned>(md.weldedBases[m]), static_cast<unsigned>(md.weldedBases[m + 1])};
+}
+
+__device__ __forceinline__ Range range_of_triangle(const CcArgs& a, const CcModels& md, unsigned t) {
+    if (!md.weldedBases) return Range{0u, 0u, a.nv};
+    const unsigned m = model_of(md.soupBases + 1, 2, md.n, t);
+    return Range{m, static_cast<unsigned>(md.weldedBases[m]), static_cast<unsigned>(md.weldedBases[m + 1])};
+}
+
+// the global welded indices of triangle t's corners; false (and nothing to dereference) if one lies outside its
+// model's welded range or past the scratch
+__device__ __forceinline__ bool corners(const CcArgs& a, const Range& r, const int32_t* tris, unsigned t,
+                                        unsigned g[3]) {
+    const int32_t* ti = tris + 4 * static_cast<size_t>(t);
+    const unsigned hi = r.hi < a.nv ? r.hi : a.nv;
+    bool ok = r.lo <= hi;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const unsigned long long x = static_cast<unsigned long long>(r.lo) + static_cast<unsigned>(ti[1 + j]);
+        ok = ok && ti[1 + j] >= 0 && x < hi;
+        g[j] = static_cast<unsigned>(x);
+    }
+    return ok;
+}
+
+__device__ __forceinline__ unsigned load_parent(const unsigned* parent, unsigned x) {
+    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the root above x at the time of the walk.  Every step goes to a strictly smaller index (parent[y] < y for a
+// non-root), so the loop ends after at most x steps; nodes on the way are pointed at their grandparent.
+__device__ __forceinline__ unsigned find_root(unsigned* parent, unsigned x) {
+    unsigned p = load_parent(parent, x);
+    while (p < x) {
+        const unsigned gp = load_parent(parent, p);
+        if (gp < p) atomicMin(parent + x, gp);
+        x = p;
+        p = gp;
+    }
+    return x;
+}
+
+// Joins the trees of a and b.  Each round either ends or goes on from indices of which one is strictly smaller than
+// before (a failed CAS saw a parent below the root it tried to hook), so the rounds are bounded by a + b.
+__device__ __forceinline__ void unite(unsigned* parent, unsigned a, unsigned b) {
+    for (;;) {
+        a = find_root(parent, a);
+        b = find_root(parent, b);
+        if (a == b) return;
+        const unsigned hi = a > b ? a : b, lo = a > b ? b : a;
+        const unsigned seen = atomicCAS(parent + hi, hi, lo);
+        if (seen == hi) return;
+        a = seen;  // hi was hooked meanwhile: seen < hi
+        b = lo;
+    }
+}
+
+__global__ __launch_bounds__(kCcBlock) void k_cc_init(const CcArgs a) {
+    const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
+    if (i < a.nv) {
+        a.parent[i] = i;
+        a.size[i] = 0u;
+    }
+}
+
+__global__ __launch_bounds__(kCcBlock) void k_cc_hook(const CcArgs a, const CcModels md, const int32_t* tris) {
+    const unsigned t = blockIdx.x * kCcBlock + threadIdx.x;
+    if (t >= a.nt) return;
+    unsigned g[3];
+    if (!corners(a, range_of_triangle(a, md, t), tris, t, g)) {
+        atomicOr(a.flag, 1u);
+        return;
+    }
+    unite(a.parent, g[0], g[1]);
+    unite(a.parent, g[0], g[2]);
+}
+
+__global__ __launch_bounds__(kCcBlock) void k_cc_flatten(const CcArgs a) {
+    const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
+    if (i >= a.nv) return;
+    const unsigned r = find_root(a.parent, i);
+    atomicMin(a.parent + i, r);  // (a halving step of another lane may still be under way: the minimum wins)
+}
+
+// On a real mesh nearly every triangle belongs to one giant component, and one add per triangle would serialise on
+// one address.  A wave whose live lanes share a root adds once; the workgroup's uniform waves are merged in LDS.
+__global__ __launch_bounds__(kCcBlock) void k_cc_count(const CcArgs a, const CcModels md, const int32_t* tris) {
+    __shared__ unsigned wroot[kCcBlock / 64], wcount[kCcBlock / 64];
+    const unsigned t = blockIdx.x * kCcBlock + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned root = 0u;
+    bool live = false;
+    if (t < a.nt) {
+        unsigned g[3];
+        if (corners(a, range_of_triangle(a, md, t), tris, t, g)) {
+            root = a.parent[g[0]];
+            live = true;
+        }
+    }
+    const unsigned long long mask = __ballot(live);
+    unsigned uroot = 0u, ucount = 0u;
+    if (mask) {
+        const unsigned first = __shfl(root, __ffsll(static_cast<long long>(mask)) - 1);
+        if (__all(!live || root == first)) {
+            uroot = first;
+            ucount = static_cast<unsigned>(__popcll(mask));
+        } else if (live) {
+            atomicAdd(a.size + root, 1u);
+        }
+    }
+    if (lane == 0) {
+        wroot[wave] = uroot;
+        wcount[wave] = ucount;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 0; w < kCcBlock / 64; ++w) {
+            unsigned c = wcount[w];
+            if (c == 0u) continue;
+            for (int u = w + 1; u < kCcBlock / 64; ++u)
+                if (wcount[u] && wroot[u] == wroot[w]) {
+                    c += wcount[u];
+                    wcount[u] = 0u;
+                }
+            atomicAdd(a.size + wroot[w], c);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kCcBlock) void k_cc_labels(const CcArgs a, const CcModels md, int32_t* labels,
+                                                        uint32_t* sizes) {
+    const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
+    if (i >= a.nv) return;
+    const unsigned r = a.parent[i];
+    if (labels) labels[i] = static_cast<int32_t>(r - range_of_vertex(a, md, i).lo);
+    if (sizes) sizes[i] = a.size[r];
+}
+
+__device__ __forceinline__ unsigned long long pack_best(unsigned size, unsigned label) {
+    return static_cast<unsigned long long>(size) << 32 | static_cast<unsigned>(~label);
+}
+
+__global__ __launch_bounds__(kCcBlock) void k_cc_select(const CcArgs a, const CcModels md) {
+    const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
+    if (i >= a.nv || a.parent[i] != i) return;
+    const Range r = range_of_vertex(a, md, i);
+    atomicMax(a.best + r.model, pack_best(a.size[i], i - r.lo));
+}
+
+// is the component rooted at `root` (of a model whose welded vertices start at r.lo) kept?
+__device__ __forceinline__ bool kept(const CcArgs& a, const CcCriteria& c, const Range& r, unsigned root) {
+    const unsigned size = a.size[root];
+    if (c.minTriangles[r.model] > 1u && size < c.minTriangles[r.model]) return false;
+    return !c.largestOnly[r.model] || a.best[r.model] == pack_best(size, root - r.lo);
+}
+
+__device__ __forceinline__ unsigned vertex_flag(const CcArgs& a, const CcModels& md, const CcCriteria& c, unsigned i) {
+    if (i >= a.nv) return 0u;
+    return kept(a, c, range_of_vertex(a, md, i), a.parent[i]) ? 1u : 0u;
+}
+
+__device__ __forceinline__ unsigned triangle_flag(const CcArgs& a, const CcModels& md, const CcCriteria& c,
+                                                  const int32_t* tris, unsigned t) {
+    if (t >= a.nt) return 0u;
+    const Range r = range_of_triangle(a, md, t);
+    unsigned g[3];
+    if (!corners(a, r, tris, t, g)) return 0u;
+    return kept(a, c, r, a.parent[g[0]]) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(kCcBlock) void k_cc_flags(const CcArgs a, const CcModels md, const CcCriteria c,
+                                                       const int32_t* tris) {
+    __shared__ unsigned lds[kCcBlock / 64];
+    const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
+    const unsigned vf = vertex_flag(a, md, c, i);
+    if (i < a.nv && a.parent[i] == i) {  // a root: one component of its model
+        const unsigned m = range_of_vertex(a, md, i).model;
+        atomicAdd(a.ncomp + m, 1u);
+        if (vf) atomicAdd(a.nkept + m, 1u);
+    }
+    unsigned total;
+    block_scan1(vf, total, lds);
+    if (threadIdx.x == 0 && blockIdx.x < a.vblocks) a.vsums[blockIdx.x] = total;
+    block_scan1(triangle_flag(a, md, c, tris, i), total, lds);
+    if (threadIdx.x == 0 && blockIdx.x < a.tblocks) a.tsums[blockIdx.x] = total;
+}
+
+// workgroup 0 scans the vertex sums, workgroup 1 the triangle sums
+__global__ __launch_bounds__(kSumsBlock) void k_cc_scan(const CcArgs a) {
+    __shared__ unsigned lds[kSumsBlock / 64];
+    __shared__ unsigned carry;
+    if (blockIdx.x == 0) scan_sums(a.vsums, a.vblocks, lds, &carry);
+    else scan_sums(a.tsums, a.tblocks, lds, &carry);
+}
+
+__global__ __launch_bounds__(kCcBlock) void k_cc_rank(const CcArgs a, const CcModels md, const CcCriteria c,
+                                                      const int32_t* tris) {
+    __shared__ unsigned lds[kCcBlock / 64];
+    const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
+    unsigned total;
+    const unsigned vmine = block_scan1(vertex_flag(a, md, c, i), total, lds);
+    if (i < a.nv) a.vexcl[i] = a.vsums[blockIdx.x] + vmine;
+    const unsigned tmine = block_scan1(triangle_flag(a, md, c, tris, i), total, lds);
+    if (i < a.nt) a.texcl[i] = a.tsums[blockIdx.x] + tmine;
+}
+
+// kept vertices before welded vertex b / kept triangles before triangle b (b past the end: all of them)
+__device__ __forceinline__ unsigned vrank_at(const CcArgs& a, unsigned long long b) {
+    return b < a.nv ? a.vexcl[b] : a.vsums[a.vblocks];
+}
+__device__ __forceinline__ unsigned trank_at(const CcArgs& a, unsigned long long b) {
+    return b < a.nt ? a.texcl[b] : a.tsums[a.tblocks];
+}
+
+struct CcCounts {
+    uint32_t* keptCounts;           // 2 n: vertices, triangles
+    unsigned long long* keptBases;  // 2 (n + 1) interleaved or nullptr
+    uint32_t* components;           // n or nullptr
+    uint32_t* keptComponents;       // n or nullptr
+};
+
+// per model: a model's kept vertices and triangles lie in its own ranges, so its kept ranges start at the ranks of
+// its bases
+__global__ __launch_bounds__(kCcBlock) void k_cc_bases(const CcArgs a, const CcModels md, const CcCounts out) {
+    const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
+    if (i > md.n) return;
+    const unsigned long long vlo = md.weldedBases ? md.weldedBases[i] : (i == 0 ? 0ull : a.nv);
+    const unsigned long long tlo = md.weldedBases ? md.soupBases[2 * i + 1] : (i == 0 ? 0ull : a.nt);
+    const unsigned rv = vrank_at(a, vlo), rt = trank_at(a, tlo);
+    if (out.keptBases) {
+        out.keptBases[2 * i] = rv;
+        out.keptBases[2 * i + 1] = rt;
+    }
+    if (i < md.n) {
+        const unsigned long long vhi = md.weldedBases ? md.weldedBases[i + 1] : a.nv;
+        const unsigned long long thi = md.weldedBases ? md.soupBases[2 * i + 3] : a.nt;
+        out.keptCounts[2 * i] = vrank_at(a, vhi) - rv;
+        out.keptCounts[2 * i + 1] = trank_at(a, thi) - rt;
+        if (out.components) out.components[i] = a.ncomp[i];
+        if (out.keptComponents) out.keptComponents[i] = a.nkept[i];
+    }
+}
+
+struct CcEmitArgs {
+    const float* v;
+    const float* nrm;
+    const uint8_t* c;
+    const int32_t* t;
+    float* kv;
+    float* kn;
+    uint8_t* kc;
+    int32_t* kt;
+};
+
+__global__ __launch_bounds__(kCcBlock) void k_cc_emit(const CcArgs a, const CcModels md, const CcEmitArgs e) {
+    const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
+    if (i < a.nv) {
+        const unsigned r = a.vexcl[i];
+        if (vrank_at(a, static_cast<unsigned long long>(i) + 1) != r) {  // kept: the rank steps behind it
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                e.kv[3 * static_cast<size_t>(r) + j] = e.v[3 * static_cast<size_t>(i) + j];
+                e.kn[3 * static_cast<size_t>(r) + j] = e.nrm[3 * static_cast<size_t>(i) + j];
+            }
+            if (e.c) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) e.kc[3 * static_cast<size_t>(r) + j] = e.c[3 * static_cast<size_t>(i) + j];
+            }
+        }
+    }
+    if (i < a.nt) {
+        const unsigned r = a.texcl[i];
+        if (trank_at(a, static_cast<unsigned long long>(i) + 1) != r) {  // kept, hence inside its model's range
+            const Range m = range_of_triangle(a, md, i);
+            unsigned g[3];
+            if (corners(a, m, e.t, i, g)) {
+                const unsigned base = vrank_at(a, m.lo);
+                int32_t* to = e.kt + 4 * static_cast<size_t>(r);
+                to[0] = 3;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) to[1 + j] = static_cast<int32_t>(a.vexcl[g[j]] - base);
+            }
+        }
+    }
+}
+
+int check_sizes(unsigned long long nv, unsigned long long nt, int n, const char* what) {
+    if (nv > (1ull << 30)) return fail(EMF_E_LIMIT, "%s: %llu welded vertices (at most 2^30)", what, nv);
+    if (nt >= (1ull << 31)) return fail(EMF_E_LIMIT, "%s: %llu triangles (below 2^31)", what, nt);
+    if (n < 1 || n > EMF_MAX_MODELS) return fail(EMF_E_LIMIT, "%s: %d models (1 .. %d per launch)", what, n, EMF_MAX_MODELS);
+    return EMF_OK;
+}
+
+int memset_async(void* p, int v, size_t bytes, emf_stream_t stream, const char* what) {
+    const hipError_t e = hipMemsetAsync(p, v, bytes, as_stream(stream));
+    if (e != hipSuccess) {
+        set_error("%s: memset: %s", what, hipGetErrorString(e));
+        return static_cast<int>(e);
+    }
+    return EMF_OK;
+}
+
+inline unsigned items_blocks(const CcArgs& a) { return a.vblocks > a.tblocks ? a.vblocks : a.tblocks; }
+
+int cc_label(const int32_t* tris, uint64_t nv, uint64_t nt, const uint64_t* soupBases, const uint64_t* weldedBases, int n,
+             void* scratch, int32_t* labels, uint32_t* sizes, emf_stream_t stream, const char* what) {
+    EMF_TRY(check_sizes(nv, nt, n, what));
+    EMF_REQUIRE_PTR(scratch);
+    if (nt) EMF_REQUIRE_PTR(tris);
+    if (nv == 0 && nt != 0) return fail(EMF_E_ARG, "%s: %llu triangles over no vertex", what, (unsigned long long)nt);
+    CcArgs a;
+    place(a, nv, nt, scratch);
+    EMF_TRY(memset_async(a.flag, 0, sizeof(unsigned), stream, what));
+    if (nv == 0) return EMF_OK;  // nothing to label, no launch
+    const CcModels md{reinterpret_cast<const unsigned long long*>(soupBases),
+                      reinterpret_cast<const unsigned long long*>(weldedBases), static_cast<unsigned>(n)};
+    const dim3 block(kCcBlock);
+    hipLaunchKernelGGL(k_cc_init, dim3(a.vblocks), block, 0, as_stream(stream), a);
+    if (nt) {
+        hipLaunchKernelGGL(k_cc_hook, dim3(a.tblocks), block, 0, as_stream(stream), a, md, tris);
+        hipLaunchKernelGGL(k_cc_flatten, dim3(a.vblocks), block, 0, as_stream(stream), a);
+        hipLaunchKernelGGL(k_cc_count, dim3(a.tblocks), block, 0, as_stream(stream), a, md, tris);
+    }
+    if (labels || sizes) hipLaunchKernelGGL(k_cc_labels, dim3(a.vblocks), block, 0, as_stream(stream), a, md, labels, sizes);
+    return launch_status(what);
+}
+
+int cc_filter_count(const int32_t* tris, uint64_t nv, uint64_t nt, const uint64_t* soupBases, const uint64_t* weldedBases,
+                    int n, void* scratch, const uint32_t* minTriangles, const uint8_t* largestOnly, uint32_t* keptCounts,
+                    uint64_t* keptBases, uint32_t* components, uint32_t* keptComponents, emf_stream_t stream,
+                    const char* what) {
+    EMF_TRY(check_sizes(nv, nt, n, what));
+    EMF_REQUIRE_PTR(scratch);
+    EMF_REQUIRE_PTR(keptCounts);
+    if (nt) EMF_REQUIRE_PTR(tris);
+    if (nv == 0 && nt != 0) return fail(EMF_E_ARG, "%s: %llu triangles over no vertex", what, (unsigned long long)nt);
+    if (nv == 0) {  // empty meshes: zero counts, zero bases, no launch
+        EMF_TRY(memset_async(keptCounts, 0, sizeof(uint32_t) * 2 * n, stream, what));
+        if (keptBases) EMF_TRY(memset_async(keptBases, 0, sizeof(uint64_t) * 2 * (n + 1), stream, what));
+        if (components) EMF_TRY(memset_async(components, 0, sizeof(uint32_t) * n, stream, what));
+        if (keptComponents) EMF_TRY(memset_async(keptComponents, 0, sizeof(uint32_t) * n, stream, what));
+        return EMF_OK;
+    }
+    CcArgs a;
+    place(a, nv, nt, scratch);
+    CcCriteria c;
+    for (int k = 0; k < EMF_MAX_MODELS; ++k) {
+        c.minTriangles[k] = k < n && minTriangles ? minTriangles[k] : 0u;
+        c.largestOnly[k] = k < n && largestOnly && largestOnly[k] ? 1 : 0;
+    }
+    // best, components and kept components are contiguous
+    EMF_TRY(memset_async(a.best, 0, reinterpret_cast<char*>(a.flag) - reinterpret_cast<char*>(a.best), stream, what));
+    const CcModels md{reinterpret_cast<const unsigned long long*>(soupBases),
+                      reinterpret_cast<const unsigned long long*>(weldedBases), static_cast<unsigned>(n)};
+    const CcCounts out{keptCounts, reinterpret_cast<unsigned long long*>(keptBases), components, keptComponents};
+    const dim3 block(kCcBlock), items(items_blocks(a));
+    hipLaunchKernelGGL(k_cc_select, dim3(a.vblocks), block, 0, as_stream(stream), a, md);
+    hipLaunchKernelGGL(k_cc_flags, items, block, 0, as_stream(stream), a, md, c, tris);
+    hipLaunchKernelGGL(k_cc_scan, dim3(2), dim3(kSumsBlock), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(k_cc_rank, items, block, 0, as_stream(stream), a, md, c, tris);
+    hipLaunchKernelGGL(k_cc_bases, dim3(ceil_div(n + 1, kCcBlock)), block, 0, as_stream(stream), a, md, out);
+    return launch_status(what);
+}
+
+int cc_emit(const void* scratch, uint64_t nv, uint64_t nt, const uint64_t* soupBases, const uint64_t* weldedBases, int n,
+            const float* v, const float* nrm, const uint8_t* c, const int32_t* t, float* kv, float* kn, uint8_t* kc,
+            int32_t* kt, emf_stream_t stream, const char* what) {
+    EMF_TRY(check_sizes(nv, nt, n, what));
+    if (nv == 0) {
+        if (nt != 0) return fail(EMF_E_ARG, "%s: %llu triangles over no vertex", what, (unsigned long long)nt);
+        return EMF_OK;
+    }
+    EMF_REQUIRE_PTR(scratch);
+    EMF_REQUIRE_PTR(v);
+    EMF_REQUIRE_PTR(nrm);
+    EMF_REQUIRE_PTR(kv);
+    EMF_REQUIRE_PTR(kn);
+    if (nt) {
+        EMF_REQUIRE_PTR(t);
+        EMF_REQUIRE_PTR(kt);
+    }
+    if ((c == nullptr) != (kc == nullptr)) return fail(EMF_E_NULL, "%s: colors and kept_colors go together", what);
+    if (kv == v || kn == nrm || (c && kc == c) || (nt && kt == t))
+        return fail(EMF_E_ARG, "%s: the kept arrays must not alias the welded mesh's", what);
+    CcArgs a;
+    place(a, nv, nt, const_cast<void*>(scratch));
+    const CcModels md{reinterpret_cast<const unsigned long long*>(soupBases),
+                      reinterpret_cast<const unsigned long long*>(weldedBases), static_cast<unsigned>(n)};
+    const CcEmitArgs e{v, nrm, c, t, kv, kn, kc, kt};
+    hipLaunchKernelGGL(k_cc_emit, dim3(items_blocks(a)), dim3(kCcBlock), 0, as_stream(stream), a, md, e);
+    return launch_status(what);
+}
+
+}  // namespace
+}  // namespace emf_hip
+
+using namespace emf_hip;
+
+extern "C" {
+
+// The bound include/emf_hip.h declares: under 13 bytes per welded vertex + 5 per triangle + 6 KiB.
+size_t emf_hip_meshComponentsScratchBytes(uint64_t weldedVertices, uint64_t triangles) {
+    if (weldedVertices > (1ull << 30) || triangles >= (1ull << 31)) return 0;
+    CcArgs a;
+    char origin[16];
+    (void)origin;
+    return place(a, weldedVertices, triangles, origin);  // only the offsets are used
+}
+
+int emf_hip_meshComponentsLabel(const int32_t* triangles, uint64_t weldedVertices, uint64_t nTriangles, void* cc_scratch_dev,
+                                int32_t* labels, uint32_t* sizes, emf_stream_t stream) {
+    return cc_label(triangles, weldedVertices, nTriangles, nullptr, nullptr, 1, cc_scratch_dev, labels, sizes, stream,
+                    "meshComponentsLabel");
+}
+
+int emf_hip_meshComponentsLabelBatched(const int32_t* triangles, uint64_t weldedVertices, uint64_t nTriangles,
+                                       const uint64_t* soup_bases_dev, const uint64_t* welded_bases_dev, int n,
+                                       void* cc_scratch_dev, int32_t* labels, uint32_t* sizes, emf_stream_t stream) {
+    EMF_REQUIRE_PTR(soup_bases_dev);
+    EMF_REQUIRE_PTR(welded_bases_dev);
+    return cc_label(triangles, weldedVertices, nTriangles, soup_bases_dev, welded_bases_dev, n, cc_scratch_dev, labels,
+                    sizes, stream, "meshComponentsLabelBatched");
+}
+
+int emf_hip_meshComponentsFilterCount(const int32_t* triangles, uint64_t weldedVertices, uint64_t nTriangles,
+                                      void* cc_scratch_dev, const uint32_t* min_triangles, const uint8_t* largest_only,
+                                      uint32_t* kept_counts, uint32_t* components, uint32_t* kept_components,
+                                      emf_stream_t stream) {
+    return cc_filter_count(triangles, weldedVertices, nTriangles, nullptr, nullptr, 1, cc_scratch_dev, min_triangles,
+                           largest_only, kept_counts, nullptr, components, kept_components, stream,
+                           "meshComponentsFilterCount");
+}
+
+int emf_hip_meshComponentsFilterCountBatched(const int32_t* triangles, uint64_t weldedVertices, uint64_t nTriangles,
+                                             const uint64_t* soup_bases_dev, const uint64_t* welded_bases_dev, int n,
+                                             void* cc_scratch_dev, const uint32_t* min_triangles,
+                                             const uint8_t* largest_only, uint32_t* kept_counts, uint64_t* kept_bases,
+                                             uint32_t* components, uint32_t* kept_components, emf_stream_t stream) {
+    EMF_REQUIRE_PTR(soup_bases_dev);
+    EMF_REQUIRE_PTR(welded_bases_dev);
+    return cc_filter_count(triangles, weldedVertices, nTriangles, soup_bases_dev, welded_bases_dev, n, cc_scratch_dev,
+                           min_triangles, largest_only, kept_counts, kept_bases, components, kept_components, stream,
+                           "meshComponentsFilterCountBatched");
+}
+
+int emf_hip_meshComponentsStatus(const void* cc_scratch_dev, uint64_t weldedVertices, uint64_t nTriangles,
+                                 emf_stream_t stream) {
+    EMF_REQUIRE_PTR(cc_scratch_dev);
+    EMF_TRY(check_sizes(weldedVertices, nTriangles, 1, "meshComponentsStatus"));
+    CcArgs a;
+    place(a, weldedVertices, nTriangles, const_cast<void*>(cc_scratch_dev));
+    unsigned flag = 0;
+    hipError_t e = hipMemcpyAsync(&flag, a.flag, sizeof(flag), hipMemcpyDeviceToHost, as_stream(stream));
+    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
+    if (e != hipSuccess) {
+        set_error("meshComponentsStatus: %s", hipGetErrorString(e));
+        return static_cast<int>(e);
+    }
+    if (flag) return fail(EMF_E_ARG, "meshComponents: a triangle index lies outside its model's welded vertices");
+    return EMF_OK;
+}
+
+int emf_hip_meshComponentsEmit(const void* cc_scratch_dev, uint64_t weldedVertices, uint64_t nTriangles,
+                               const float* vertices, const float* normals, const uint8_t* colors,
+                               const int32_t* triangles, float* kept_vertices, float* kept_normals, uint8_t* kept_colors,
+                               int32_t* kept_triangles, emf_stream_t stream) {
+    return cc_emit(cc_scratch_dev, weldedVertices, nTriangles, nullptr, nullptr, 1, vertices, normals, colors, triangles,
+                   kept_vertices, kept_normals, kept_colors, kept_triangles, stream, "meshComponentsEmit");
+}
+
+int emf_hip_meshComponentsEmitBatched(const void* cc_scratch_dev, uint64_t weldedVertices, uint64_t nTriangles,
+                                      const uint64_t* soup_bases_dev, const uint64_t* welded_bases_dev, int n,
+                                      const float* vertices, const float* normals, const uint8_t* colors,
+                                      const int32_t* triangles, float* kept_vertices, float* kept_normals,
+                                      uint8_t* kept_colors, int32_t* kept_triangles, emf_stream_t stream) {
+    EMF_REQUIRE_PTR(soup_bases_dev);
+    EMF_REQUIRE_PTR(welded_bases_dev);
+    return cc_emit(cc_scratch_dev, weldedVertices, nTriangles, soup_bases_dev, welded_bases_dev, n, vertices, normals,
+                   colors, triangles, kept_vertices, kept_normals, kept_colors, kept_triangles, stream,
+                   "meshComponentsEmitBatched");
+}
+
+}  // extern "C"

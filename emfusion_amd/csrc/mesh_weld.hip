@@ -25,11 +25,12 @@
 // Which slot a key lands in depends on the order the lanes arrive; the MINIMUM soup index per key, hence every
 // output, does not.  All atomics are ordinary global atomics on vector memory.
 #include "common.hpp"
+#include "mesh_scan.hpp"
 
 namespace emf_hip {
 namespace {
 
-constexpr int kWeldBlock = 256;
+constexpr int kWeldBlock = kScanBlock;
 constexpr unsigned long long kEmptyKey = ~0ull;  // no edge key has all bits set (slot < 256 sits at bit 48)
 
 struct WeldArgs {
@@ -101,29 +102,6 @@ __global__ __launch_bounds__(kWeldBlock) void k_weld_insert(const WeldArgs a, co
     atomicOr(a.flag, 1u);
 }
 
-// the workgroup's sum of v (all lanes get it) and this lane's exclusive prefix
-__device__ __forceinline__ unsigned block_scan1(unsigned v, unsigned& total, unsigned* lds /* [kWeldBlock / 64] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(inc, o);
-        if (lane >= o) inc += up;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    unsigned before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kWeldBlock / 64; ++w) {
-        const unsigned t = lds[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    __syncthreads();
-    return before + inc - v;
-}
-
 __device__ __forceinline__ unsigned is_first(const WeldArgs& a, unsigned i) {
     return i < a.nv && a.tfirst[a.remap[i]] == i ? 1u : 0u;
 }
@@ -136,35 +114,10 @@ __global__ __launch_bounds__(kWeldBlock) void k_weld_flags(const WeldArgs a) {
 }
 
 // one workgroup: sums[b] := sum of sums[0 .. b), sums[nblocks] := the total
-__global__ __launch_bounds__(1024) void k_weld_scan(const WeldArgs a) {
-    __shared__ unsigned lds[16];
+__global__ __launch_bounds__(kSumsBlock) void k_weld_scan(const WeldArgs a) {
+    __shared__ unsigned lds[kSumsBlock / 64];
     __shared__ unsigned carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry = 0u;
-    __syncthreads();
-    for (unsigned start = 0; start < a.nblocks; start += 1024) {
-        const unsigned i = start + threadIdx.x;
-        const unsigned v = i < a.nblocks ? a.sums[i] : 0u;
-        unsigned inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned up = __shfl_up(inc, o);
-            if (lane >= o) inc += up;
-        }
-        if (lane == 63) lds[wave] = inc;
-        __syncthreads();
-        unsigned before = carry, total = 0u;
-        for (int w = 0; w < 16; ++w) {
-            const unsigned t = lds[w];
-            if (w < wave) before += t;
-            total += t;
-        }
-        if (i < a.nblocks) a.sums[i] = before + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) a.sums[a.nblocks] = carry;
+    scan_sums(a.sums, a.nblocks, lds, &carry);
 }
 
 __global__ __launch_bounds__(kWeldBlock) void k_weld_rank(const WeldArgs a) {
@@ -308,7 +261,7 @@ int weld_count(const uint64_t* keys, uint64_t nv, const uint64_t* soupBases, int
     hipLaunchKernelGGL(k_weld_insert, grid, block, 0, as_stream(stream), a,
                        reinterpret_cast<const unsigned long long*>(keys));
     hipLaunchKernelGGL(k_weld_flags, grid, block, 0, as_stream(stream), a);
-    hipLaunchKernelGGL(k_weld_scan, dim3(1), dim3(1024), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(k_weld_scan, dim3(1), dim3(kSumsBlock), 0, as_stream(stream), a);
     hipLaunchKernelGGL(k_weld_rank, grid, block, 0, as_stream(stream), a);
     // the per-model part needs n + 1 <= 257 threads: two workgroups at least
     hipLaunchKernelGGL(k_weld_remap, dim3(a.nblocks < 2u ? 2u : a.nblocks), block, 0, as_stream(stream), a, md);

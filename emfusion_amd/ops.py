@@ -751,7 +751,7 @@ def render_phong_color(vertices, normals, colors, image, light=(0.0, 0.0, 0.0), 
 
 def _weld(keys, nv, nt, verts, norms, tris, cols, soup_bases=None, n=1, stream=None):
     """emf_hip_meshWeldCount / ...Emit on device soup arrays: (welded vertices, normals, triangles, colours or None as
-    device arrays, welded counts (n,) u32, welded bases (n + 1,) u64)."""
+    device arrays, welded counts (n,) u32, welded bases (n + 1,) u64 on the host and on the device)."""
     scratch = DeviceArray.zeros((max(int(_L.emf_hip_meshWeldScratchBytes(nv)) // 4, 4),), np.uint32)
     wcounts = DeviceArray.zeros((max(n, 1),), np.uint32)
     wbases = DeviceArray.zeros((n + 1,), np.uint64)
@@ -780,7 +780,149 @@ def _weld(keys, nv, nt, verts, norms, tris, cols, soup_bases=None, n=1, stream=N
                                                  _ptr(tris), _stream(stream)))
     from .devmem import synchronize
     synchronize()  # the scratch is released on return
-    return wv, wn, tris, wc, cnt, wbases.numpy()
+    return wv, wn, tris, wc, cnt, wbases.numpy(), wbases
+
+
+def _on_device(a, dtype):
+    return a if isinstance(a, DeviceArray) else DeviceArray.from_numpy(np.ascontiguousarray(a, dtype))
+
+
+def _table_bases(tri_bases, vertex_bases):
+    """Host bases of a table of meshes -> (n, device soup bases 2 (n + 1) u64 with the triangle bases in the odd
+    entries, device welded bases (n + 1) u64), or (1, None, None) for one mesh."""
+    if tri_bases is None and vertex_bases is None:
+        return 1, None, None
+    tb, vb = np.asarray(tri_bases, np.uint64), np.asarray(vertex_bases, np.uint64)
+    if tb.ndim != 1 or tb.shape != vb.shape or len(tb) < 2:
+        raise ValueError("tri_bases and vertex_bases: n + 1 entries each")
+    inter = np.zeros((len(tb), 2), np.uint64)
+    inter[:, 1] = tb
+    return len(tb) - 1, DeviceArray.from_numpy(inter), DeviceArray.from_numpy(vb)
+
+
+def _label(tris, nv, nt, soup_bases=None, wbases=None, n=1, outputs=True, stream=None):
+    """emf_hip_meshComponentsLabel / ...Batched on a device index buffer: (scratch, labels, sizes) as device arrays
+    (labels and sizes None without `outputs`)."""
+    nbytes = int(_L.emf_hip_meshComponentsScratchBytes(nv, nt))
+    if nbytes == 0:
+        raise ValueError(f"mesh components: {nv} vertices / {nt} triangles are beyond the limits")
+    scratch = DeviceArray.zeros((nbytes // 4,), np.uint32)
+    labels = DeviceArray.zeros((max(nv, 1),), np.int32) if outputs else None
+    sizes = DeviceArray.zeros((max(nv, 1),), np.uint32) if outputs else None
+    if soup_bases is None:
+        check("emf_hip_meshComponentsLabel",
+              _L.emf_hip_meshComponentsLabel(_ptr(tris), nv, nt, _ptr(scratch), _ptr(labels), _ptr(sizes),
+                                             _stream(stream)))
+    else:
+        check("emf_hip_meshComponentsLabelBatched",
+              _L.emf_hip_meshComponentsLabelBatched(_ptr(tris), nv, nt, _ptr(soup_bases), _ptr(wbases), n, _ptr(scratch),
+                                                    _ptr(labels), _ptr(sizes), _stream(stream)))
+    return scratch, labels, sizes
+
+
+def _per_model(value, n, dtype):
+    a = np.asarray(value)
+    return np.ascontiguousarray(np.broadcast_to(a, (n,)) if a.ndim == 0 else a.reshape(n), dtype)
+
+
+def _filter(nv, nt, verts, norms, tris, cols, min_triangles, largest_only, soup_bases=None, wbases=None, n=1,
+            stream=None):
+    """Label, filter-count, status and emit on device welded arrays: (kept vertices, normals, triangles, colours or
+    None as device arrays, kept counts (n, 2) u32, kept bases (n + 1, 2) u64, dict(components=, kept_components=))."""
+    scratch, _, _ = _label(tris, nv, nt, soup_bases, wbases, n, outputs=False, stream=stream)
+    mins = _per_model(min_triangles, n, np.uint32)
+    largest = _per_model(largest_only, n, np.uint8)
+    kcounts = DeviceArray.zeros((n, 2), np.uint32)
+    kbases = DeviceArray.zeros((n + 1, 2), np.uint64)
+    comps = DeviceArray.zeros((n,), np.uint32)
+    kcomps = DeviceArray.zeros((n,), np.uint32)
+    hp = lambda a: a.ctypes.data_as(C.c_void_p)
+    if soup_bases is None:
+        check("emf_hip_meshComponentsFilterCount",
+              _L.emf_hip_meshComponentsFilterCount(_ptr(tris), nv, nt, _ptr(scratch), hp(mins), hp(largest),
+                                                   _ptr(kcounts), _ptr(comps), _ptr(kcomps), _stream(stream)))
+    else:
+        check("emf_hip_meshComponentsFilterCountBatched",
+              _L.emf_hip_meshComponentsFilterCountBatched(_ptr(tris), nv, nt, _ptr(soup_bases), _ptr(wbases), n,
+                                                          _ptr(scratch), hp(mins), hp(largest), _ptr(kcounts),
+                                                          _ptr(kbases), _ptr(comps), _ptr(kcomps), _stream(stream)))
+    check("emf_hip_meshComponentsStatus", _L.emf_hip_meshComponentsStatus(_ptr(scratch), nv, nt, _stream(stream)))
+    cnt = kcounts.numpy()
+    if soup_bases is None:
+        bs = np.array([[0, 0], cnt[0]], np.uint64)
+    else:
+        bs = kbases.numpy()
+    knv, knt = int(bs[n, 0]), int(bs[n, 1])
+    kv = DeviceArray.zeros((max(knv, 1), 3), np.float32)
+    kn = DeviceArray.zeros((max(knv, 1), 3), np.float32)
+    kt = DeviceArray.zeros((max(knt, 1), 4), np.int32)
+    kc = None if cols is None else DeviceArray.zeros((max(knv, 1), 3), np.uint8)
+    if nv:
+        if soup_bases is None:
+            check("emf_hip_meshComponentsEmit",
+                  _L.emf_hip_meshComponentsEmit(_ptr(scratch), nv, nt, _ptr(verts), _ptr(norms), _ptr(cols), _ptr(tris),
+                                                _ptr(kv), _ptr(kn), _ptr(kc), _ptr(kt), _stream(stream)))
+        else:
+            check("emf_hip_meshComponentsEmitBatched",
+                  _L.emf_hip_meshComponentsEmitBatched(_ptr(scratch), nv, nt, _ptr(soup_bases), _ptr(wbases), n,
+                                                       _ptr(verts), _ptr(norms), _ptr(cols), _ptr(tris), _ptr(kv),
+                                                       _ptr(kn), _ptr(kc), _ptr(kt), _stream(stream)))
+    from .devmem import synchronize
+    synchronize()  # the scratch is released on return
+    return kv, kn, kt, kc, cnt, bs, dict(components=comps.numpy(), kept_components=kcomps.numpy())
+
+
+def mesh_components(triangles, n_vertices, tri_bases=None, vertex_bases=None, stream=None):
+    """emf_hip_meshComponentsLabel: connected components of an indexed mesh, by index (include/emf_hip.h "Mesh
+    components").  triangles: (m, 4) i32 records (3, i0, i1, i2), numpy or device; n_vertices: the vertices they index.
+    A table of meshes: tri_bases / vertex_bases, n + 1 host entries each, the triangles' indices model-local.
+    Returns (labels (n_vertices,) i32 -- the smallest model-local index of the vertex's component --, sizes
+    (n_vertices,) u32 -- that component's triangles)."""
+    nv = int(n_vertices)
+    nt = int(triangles.shape[0])
+    n, sb, wb = _table_bases(tri_bases, vertex_bases)
+    if nv == 0 and nt == 0:
+        return np.zeros((0,), np.int32), np.zeros((0,), np.uint32)
+    tris = _on_device(triangles, np.int32) if nt else None
+    scratch, labels, sizes = _label(tris, nv, nt, sb, wb, n, stream=stream)
+    check("emf_hip_meshComponentsStatus", _L.emf_hip_meshComponentsStatus(_ptr(scratch), nv, nt, _stream(stream)))
+    return labels.numpy()[:nv], sizes.numpy()[:nv]
+
+
+def filter_mesh(vertices, normals, triangles, colors=None, min_triangles=0, largest_only=False, tri_bases=None,
+                vertex_bases=None, stats=False, stream=None):
+    """emf_hip_meshComponentsFilterCount / ...Emit on an indexed mesh (numpy or device arrays): the components with
+    fewer than min_triangles triangles removed and, with largest_only, every component but the largest (a tie to the
+    smaller label).  Returns (vertices, normals, triangles[, colours]) as numpy arrays -- kept vertices in order, bits
+    unchanged, kept triangles in order, re-indexed.  A table of meshes (tri_bases / vertex_bases, n + 1 host entries
+    each; min_triangles / largest_only scalars or one per mesh): a list of such tuples.  stats: also a dict
+    (components, kept_components, one per mesh)."""
+    nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
+    n, sb, wb = _table_bases(tri_bases, vertex_bases)
+    if nv == 0:
+        empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 4), np.int32)) + \
+                (() if colors is None else (np.zeros((0, 3), np.uint8),))
+        out = empty if sb is None else [empty] * n
+        zero = dict(components=np.zeros((n,), np.uint32), kept_components=np.zeros((n,), np.uint32))
+        return (out, zero) if stats else out
+    verts, norms = _on_device(vertices, np.float32), _on_device(normals, np.float32)
+    tris = _on_device(triangles, np.int32) if nt else None
+    cols = None if colors is None else _on_device(colors, np.uint8)
+    kv, kn, kt, kc, cnt, bs, st = _filter(nv, nt, verts, norms, tris, cols, min_triangles, largest_only, sb, wb, n,
+                                          stream=stream)
+    out = _slices(kv, kn, kt, kc, bs[:, 0], cnt[:, 0], bs[:, 1], cnt[:, 1], n)
+    out = out[0] if sb is None else out
+    return (out, st) if stats else out
+
+
+def _slices(verts, norms, tris, cols, vbase, vcnt, tbase, tcnt, n):
+    hv, hn, ht = verts.numpy(), norms.numpy(), tris.numpy()
+    hc = None if cols is None else cols.numpy()
+    out = []
+    for k in range(n):
+        v0, t0, cv, ct = int(vbase[k]), int(tbase[k]), int(vcnt[k]), int(tcnt[k])
+        out.append((hv[v0:v0 + cv], hn[v0:v0 + cv], ht[t0:t0 + ct]) + ((hc[v0:v0 + cv],) if hc is not None else ()))
+    return out
 
 
 def mesh_edge_keys(tsdf, weights, fg_mask=None, stream=None):
@@ -801,12 +943,16 @@ def mesh_edge_keys(tsdf, weights, fg_mask=None, stream=None):
     return keys.numpy()[:nv]
 
 
-def extract_mesh(tsdf, weights, voxel_size, fg_mask=None, grads=None, stream=None, color=None, weld=False):
+def extract_mesh(tsdf, weights, voxel_size, fg_mask=None, grads=None, stream=None, color=None, weld=False,
+                 min_triangles=0, largest_only=False):
     """TSDF::getMesh / ObjTSDF::getMesh: (vertices (n, 3) f32, normals (n, 3) f32, triangles (m, 4) i32)
     as numpy arrays; two launches to count, one read-back, one launch to emit.  color: the volume's colour volume
     ((Nz, Ny, Nx, 4) u16): a fourth array, the vertex colours (n, 3) u8 (emf_hip_meshColors).  weld: the welded mesh
     instead of the soup (emf_hip_meshEdgeKeys / meshWeldCount / meshWeldEmit): one vertex per grid edge, the first
-    copy's bits, triangles re-indexed."""
+    copy's bits, triangles re-indexed.  min_triangles / largest_only (with weld): the welded mesh filtered by
+    connected component (filter_mesh) on the device; off (0, False) launches nothing more."""
+    if (int(min_triangles) > 1 or largest_only) and not weld:
+        raise ValueError("extract_mesh: the component filter works on the welded mesh (weld=True)")
     res = _res(tsdf)
     scratch = DeviceArray.zeros((max(int(_L.emf_hip_meshScratchBytes(res)) // 4, 2),), np.uint32)
     counts = DeviceArray.zeros((2,), np.uint32)
@@ -834,8 +980,12 @@ def extract_mesh(tsdf, weights, voxel_size, fg_mask=None, grads=None, stream=Non
             check("emf_hip_meshEdgeKeys",
                   _L.emf_hip_meshEdgeKeys(_ptr(tsdf), _ptr(weights), _ptr(fg_mask), res, _ptr(scratch), _ptr(keys),
                                           _stream(stream)))
-        verts, norms, tris, cols, cnt, _ = _weld(keys, nv, nt, verts, norms, tris, cols, stream=stream)
+        verts, norms, tris, cols, cnt, _, _ = _weld(keys, nv, nt, verts, norms, tris, cols, stream=stream)
         nv = int(cnt[0])
+        if int(min_triangles) > 1 or largest_only:
+            verts, norms, tris, cols, kcnt, _, _ = _filter(nv, nt, verts, norms, tris if nt else None, cols, min_triangles,
+                                                           largest_only, stream=stream)
+            nv, nt = int(kcnt[0, 0]), int(kcnt[0, 1])
     if color is not None:
         return verts.numpy()[:nv], norms.numpy()[:nv], tris.numpy()[:nt], cols.numpy()[:nv]
     return verts.numpy()[:nv], norms.numpy()[:nv], tris.numpy()[:nt]
@@ -860,13 +1010,18 @@ def mesh_table(volumes):
     return (upload_models(models) if n else None), res
 
 
-def extract_meshes(volumes, stream=None, weld=False):
+def extract_meshes(volumes, stream=None, weld=False, min_triangles=0, largest_only=False):
     """emf_hip_meshCountBatched / emf_hip_meshEmitBatched: the meshes of a table of volumes in one pass (one count
     launch, one read-back of the counts, one emit launch).  volumes: [dict(tsdf=, weights=, voxel_size=, fg_mask=None,
     grads=None), ...] of device arrays, at most EMF_MAX_MODELS.  Returns [(vertices (n, 3) f32, normals (n, 3) f32,
     triangles (m, 4) i32), ...] in table order, each what extract_mesh gives for that volume alone -- with weld, what
-    extract_mesh(..., weld=True) gives (emf_hip_meshEdgeKeysBatched / meshWeldCountBatched / meshWeldEmitBatched)."""
+    extract_mesh(..., weld=True) gives (emf_hip_meshEdgeKeysBatched / meshWeldCountBatched / meshWeldEmitBatched).
+    min_triangles / largest_only (with weld; scalars or one value per volume): each slice filtered by connected component
+    as extract_mesh(..., weld=True, min_triangles=, largest_only=) filters that volume alone."""
     n = len(volumes)
+    filtered = bool(np.any(np.asarray(min_triangles) > 1) or np.any(largest_only))
+    if filtered and not weld:
+        raise ValueError("extract_meshes: the component filter works on the welded meshes (weld=True)")
     table, res = mesh_table(volumes)
     scratch_bytes = int(_L.emf_hip_meshScratchBytesBatched(res, n))
     scratch = DeviceArray.zeros((max(scratch_bytes // 4, 2),), np.uint32)
@@ -898,15 +1053,14 @@ def extract_meshes(volumes, stream=None, weld=False):
         if nv:
             check("emf_hip_meshEdgeKeysBatched",
                   _L.emf_hip_meshEdgeKeysBatched(_ptr(table), res, n, _ptr(scratch), _ptr(keys), _stream(stream)))
-        verts, norms, tris, cols, vcnt, vbase = _weld(keys, nv, nt, verts, norms, tris, cols, soup_bases=bases, n=n,
-                                                      stream=stream)
-    hv, hn, ht = verts.numpy(), norms.numpy(), tris.numpy()
-    hc = None if cols is None else cols.numpy()
-    out = []
-    for k in range(n):
-        v0, t0, cv, ct = int(vbase[k]), int(bs[k, 1]), int(vcnt[k]), int(cnt[k, 1])
-        out.append((hv[v0:v0 + cv], hn[v0:v0 + cv], ht[t0:t0 + ct]) + ((hc[v0:v0 + cv],) if hc is not None else ()))
-    return out
+        verts, norms, tris, cols, vcnt, vbase, wbases = _weld(keys, nv, nt, verts, norms, tris, cols, soup_bases=bases,
+                                                              n=n, stream=stream)
+        if filtered and n:
+            nw = int(vbase[n])
+            verts, norms, tris, cols, kcnt, kbs, _ = _filter(nw, nt, verts, norms, tris if nt else None, cols,
+                                                             min_triangles, largest_only, bases, wbases, n, stream=stream)
+            return _slices(verts, norms, tris, cols, kbs[:, 0], kcnt[:, 0], kbs[:, 1], kcnt[:, 1], n)
+    return _slices(verts, norms, tris, cols, vbase, vcnt, bs[:, 1], cnt[:, 1], n)
 
 
 def mask_association_masses(hit_masks, assocs, match_masks=None, verdict=None, stream=None):

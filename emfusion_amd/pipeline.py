@@ -112,6 +112,10 @@ def load() -> C.CDLL:
         "emf_fusion_use_preproc_masks": [vp, C.c_char_p],
         "emf_fusion_set_color": [vp, C.c_int],
         "emf_fusion_set_mesh_weld": [vp, C.c_int],
+        "emf_fusion_set_mesh_filter": [vp, C.c_uint32, C.c_int],
+        "emf_fusion_mesh_components": [vp, C.c_int, C.POINTER(C.c_uint32)],
+        "emf_fusion_copy_mesh_components": [vp, C.c_void_p, C.c_void_p],
+        "emf_fusion_last_mesh_filter": [vp, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32)],
         "emf_fusion_set_color_image": [vp, img],
         "emf_fusion_process_rgbd_color": [vp, fp, C.c_void_p, C.c_int32, C.c_int32],
         "emf_fusion_colored_voxels": [vp, C.POINTER(C.c_uint64)],
@@ -559,6 +563,34 @@ class Fusion:
         edge (the first soup copy's bits) with the soup's triangles re-indexed, welded on the device.  An output form
         only: no pose, life-cycle decision or image changes."""
         _check("emf_fusion_set_mesh_weld", load().emf_fusion_set_mesh_weld(self._h, int(on)))
+
+    def set_mesh_filter(self, min_triangles=0, largest_objects=False):
+        """The component filter: wherever set_mesh_weld acts, every mesh loses its connected components of fewer than
+        min_triangles triangles and, with largest_objects, every object mesh all components but its largest (the
+        background keeps its pieces).  Done on the device behind the weld; an active filter implies the welded form.
+        An output form only; not stored in a checkpoint.  Off: set_mesh_filter()."""
+        _check("emf_fusion_set_mesh_filter",
+               load().emf_fusion_set_mesh_filter(self._h, int(min_triangles), int(bool(largest_objects))))
+
+    def mesh_components(self, obj_id: int = 0):
+        """(labels (n,) i32, sizes (n,) u32) of model obj_id's welded, unfiltered mesh: per vertex the smallest welded
+        index of its connected component and that component's triangles."""
+        nv = C.c_uint32()
+        _check("emf_fusion_mesh_components", load().emf_fusion_mesh_components(self._h, int(obj_id), C.byref(nv)))
+        labels, sizes = np.empty((nv.value,), np.int32), np.empty((nv.value,), np.uint32)
+        _check("emf_fusion_copy_mesh_components",
+               load().emf_fusion_copy_mesh_components(self._h, labels.ctypes.data, sizes.ctypes.data))
+        return labels, sizes
+
+    def last_mesh_filter(self):
+        """{id: dict(components, kept_components, triangles, kept_triangles)} of the last mesh() / meshes() (or
+        write_results / per-frame export) under an active filter; empty without one."""
+        cap = 257
+        ids, stats, count = np.zeros((cap,), np.int32), np.zeros((cap, 4), np.uint32), C.c_int32()
+        _check("emf_fusion_last_mesh_filter",
+               load().emf_fusion_last_mesh_filter(self._h, ids.ctypes.data, stats.ctypes.data, cap, C.byref(count)))
+        keys = ("components", "kept_components", "triangles", "kept_triangles")
+        return {int(ids[k]): dict(zip(keys, (int(x) for x in stats[k]))) for k in range(min(count.value, cap))}
 
     def set_color_image(self, rgb_view: EmfImage):
         """The u8 x 3 device image (frame size) that goes with the next frame, and with that one only."""

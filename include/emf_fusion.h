@@ -121,6 +121,25 @@ int emf_fusion_set_color(emf_fusion_t* h, int on);
  * the last mesh kept of an object deleted during the run stays the soup the life cycle took.  On the sharded path:
  * wherever emf_fusion_extract_mesh works, for this rank's models. */
 int emf_fusion_set_mesh_weld(emf_fusion_t* h, int on);
+/* The component filter (include/emf_hip.h "Mesh components"; off by default -- min_triangles <= 1 and
+ * largest_objects == 0 --, may be switched at any time).  Exactly where emf_fusion_set_mesh_weld acts, every mesh
+ * loses its connected components of fewer than min_triangles triangles and, with largest_objects != 0, every OBJECT
+ * mesh all components but its largest (by triangles, a tie to the smaller label; the background keeps its pieces).
+ * Labelled, filtered and compacted on the device behind the weld; only the filtered arrays travel to the host.  An
+ * active filter implies the welded form whatever set_mesh_weld says; a mesh may come out empty.  An output form only,
+ * as the weld: nothing else changes, and the last mesh kept of an object deleted during the run stays the soup.  Not
+ * stored in a checkpoint.
+ *   mesh_components       labels and component sizes of model id's welded, UNFILTERED mesh: kept in the handle,
+ *                         copy_mesh_components hands them out (num_vertices int32 labels -- the smallest welded index
+ *                         of the vertex's component --, num_vertices uint32 sizes in triangles; NULL: not wanted)
+ *   last_mesh_filter      per model of the last emf_fusion_extract_mesh / extract_meshes (write_results and the
+ *                         per-frame export run the latter) under an active filter: ids ascending and 4 uint32 per id
+ *                         (components, kept components, triangles, kept triangles); count = how many there are,
+ *                         at most `capacity` are written */
+int emf_fusion_set_mesh_filter(emf_fusion_t* h, uint32_t min_triangles, int largest_objects);
+int emf_fusion_mesh_components(emf_fusion_t* h, int id, uint32_t* num_vertices);
+int emf_fusion_copy_mesh_components(emf_fusion_t* h, int32_t* labels, uint32_t* sizes);
+int emf_fusion_last_mesh_filter(emf_fusion_t* h, int32_t* ids, uint32_t* stats, int capacity, int32_t* count);
 int emf_fusion_set_color_image(emf_fusion_t* h, const emf_image_t* rgb_dev);
 int emf_fusion_process_rgbd_color(emf_fusion_t* h, const float* depth_host, const uint8_t* rgb_host, int32_t width,
                                   int32_t height);

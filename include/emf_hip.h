@@ -1115,6 +1115,78 @@ int emf_hip_meshWeldEmitBatched(const void* weld_scratch_dev, uint64_t soupVerti
                                 uint8_t* welded_colors, int32_t* welded_triangles, emf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mesh components (new behaviour: the reference has none).  Opt-in; the entries above are untouched.
+ * The graph of one model's WELDED mesh has the model's welded vertices as nodes; two vertices are joined when a
+ * triangle has both -- by index only: vertices of different grid edges that coincide at a voxel corner stay
+ * unconnected.  A vertex's LABEL is the smallest model-local welded index in its component, a component's SIZE
+ * its number of triangles (a vertex no triangle uses is a component of size 0).  Components never cross models.
+ * FILTER: each model has (min_triangles, largest_only).  A component is kept if its size >= min_triangles
+ * (min_triangles <= 1 keeps every size) and, with largest_only, only if it is also the model's largest by
+ * triangles, a tie going to the smaller label.  The output holds the kept vertices in welded order (position,
+ * normal and colour bits unchanged) and the kept triangles in order, (3, i0, i1, i2), re-indexed to the
+ * compacted vertices, model-local; each model's slice is what the filter gives for that mesh alone, possibly
+ * empty.  A pure function of the welded mesh: no result depends on the order workgroups run in.
+ * The entries take the welded arrays as emf_hip_meshWeldEmit / ...Batched leave them: triangles hold
+ * (3, i0, i1, i2) records with model-local welded indices; the table forms take soup_bases_dev (2 (n + 1) u64,
+ * of which the TRIANGLE bases, the odd entries, are read) and welded_bases_dev (n + 1 u64), both on the device.
+ * The level-1 forms are n == 1 with bases {0, weldedVertices} and {0, nTriangles} implied.
+ * Limits: weldedVertices <= 2^30, nTriangles < 2^31, 1 <= n <= EMF_MAX_MODELS.
+ * A triangle index outside its model's welded vertices is never dereferenced: the triangle joins nothing, is
+ * dropped by the filter, and emf_hip_meshComponentsStatus reports EMF_E_ARG.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Bytes of device scratch: three u32 per welded vertex, one per triangle, the scans' per-workgroup sums and 4 KiB
+ * of per-model cells -- under 13 bytes per welded vertex + 5 per triangle + 6 KiB.  0 beyond the limits. */
+size_t emf_hip_meshComponentsScratchBytes(uint64_t weldedVertices, uint64_t nTriangles);
+
+/* Labels every welded vertex and counts every component; leaves both in cc_scratch_dev for the entries below.
+ *   labels : NULL or weldedVertices i32, model-local
+ *   sizes  : NULL or weldedVertices u32, the size of the vertex's component
+ * weldedVertices == 0 launches nothing. */
+int emf_hip_meshComponentsLabel(const int32_t* triangles, uint64_t weldedVertices, uint64_t nTriangles, void* cc_scratch_dev,
+                                int32_t* labels, uint32_t* sizes, emf_stream_t stream);
+int emf_hip_meshComponentsLabelBatched(const int32_t* triangles, uint64_t weldedVertices, uint64_t nTriangles,
+                                       const uint64_t* soup_bases_dev, const uint64_t* welded_bases_dev, int n,
+                                       void* cc_scratch_dev, int32_t* labels, uint32_t* sizes, emf_stream_t stream);
+
+/* After emf_hip_meshComponentsLabel on the same arguments and scratch: keep flags and their ranks.
+ *   min_triangles  : HOST, NULL (0 for every model) or n u32; read before the call returns
+ *   largest_only   : HOST, NULL (off) or n u8
+ * and, to device memory,
+ *   kept_counts    : 2 n u32, the kept vertices and triangles of each model, interleaved
+ *   kept_bases     : NULL or 2 (n + 1) u64, each model's first kept vertex and triangle in the concatenated output,
+ *                    interleaved, and the totals (the layout of emf_hip_meshCountBatched's bases)
+ *   components, kept_components : NULL or n u32 each
+ * weldedVertices == 0 launches nothing but the clearing of the outputs. */
+int emf_hip_meshComponentsFilterCount(const int32_t* triangles, uint64_t weldedVertices, uint64_t nTriangles,
+                                      void* cc_scratch_dev, const uint32_t* min_triangles, const uint8_t* largest_only,
+                                      uint32_t* kept_counts, uint32_t* components, uint32_t* kept_components,
+                                      emf_stream_t stream);
+int emf_hip_meshComponentsFilterCountBatched(const int32_t* triangles, uint64_t weldedVertices, uint64_t nTriangles,
+                                             const uint64_t* soup_bases_dev, const uint64_t* welded_bases_dev, int n,
+                                             void* cc_scratch_dev, const uint32_t* min_triangles,
+                                             const uint8_t* largest_only, uint32_t* kept_counts, uint64_t* kept_bases,
+                                             uint32_t* components, uint32_t* kept_components, emf_stream_t stream);
+
+/* Waits for the stream and returns EMF_OK, or EMF_E_ARG if the last emf_hip_meshComponentsLabel on this scratch met
+ * a triangle index outside its model's welded vertices.  The one synchronising entry of the group: call it where
+ * the counts are read back anyway. */
+int emf_hip_meshComponentsStatus(const void* cc_scratch_dev, uint64_t weldedVertices, uint64_t nTriangles,
+                                 emf_stream_t stream);
+
+/* Compact: welded arrays in, kept arrays out (sized by the kept counts).  colors / kept_colors: both NULL or both
+ * given.  No output may alias its input -- triangles move to lower positions, so not the triangles either. */
+int emf_hip_meshComponentsEmit(const void* cc_scratch_dev, uint64_t weldedVertices, uint64_t nTriangles,
+                               const float* vertices, const float* normals, const uint8_t* colors,
+                               const int32_t* triangles, float* kept_vertices, float* kept_normals, uint8_t* kept_colors,
+                               int32_t* kept_triangles, emf_stream_t stream);
+int emf_hip_meshComponentsEmitBatched(const void* cc_scratch_dev, uint64_t weldedVertices, uint64_t nTriangles,
+                                      const uint64_t* soup_bases_dev, const uint64_t* welded_bases_dev, int n,
+                                      const float* vertices, const float* normals, const uint8_t* colors,
+                                      const int32_t* triangles, float* kept_vertices, float* kept_normals,
+                                      uint8_t* kept_colors, int32_t* kept_triangles, emf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Packed buffers (new behaviour: the reference has no checkpoint).  A device buffer of nbytes (a positive
  * multiple of 4, at most 2^40, 16-byte aligned) is a sequence of 1024-byte CHUNKS of 256 32-bit words; the last
  * chunk may be ragged and only its valid words are read, compared or written.  Classification compares bits,
