@@ -37,6 +37,11 @@
 // are spawned from the masks of frame 0 (initNewObjVolume), camera and object poses are tracked
 // (performTracking), later masks are matched to the models (matchSegmentation); the ground-truth
 // poses of the stream are only used to report the tracking error at the end.
+// --motion-masks [--motion-band M] [--motion-min-pixels N] [--motion-max-masks N]: no instance masks go in either --
+// every mask frame (--mask-frames N) proposes its own from the depth that lies more than M metres (default: the
+// background's truncation distance) in front of the background model (EMFusion::setMotionMasks).
+// Excludes --masks.  With --autonomous it replaces the generator's masks, and the spheres enter the scene at frame 5
+// (the first frames show the empty room): what is there from the start and hardly moves belongs to the background.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -86,6 +91,10 @@ static void set3dView(emf::EMFusion& emf, const emf::Params& params, const View3
 // The reference's main loop on a dataset (apps/EM-Fusion.cpp:100-156): a TUM sequence (`--sequence`, TUMRGBDReader) or a
 // Co-Fusion style directory (`--dir`, ImageReader: ColorNNNN.png + DepthNNNN.exr), as apps/EM-Fusion.cpp:118-131 chooses
 static bool weldMeshes = false;  // --weld-meshes
+// --motion-masks [--motion-band M] [--motion-min-pixels N] [--motion-max-masks N]: mask frames propose their own
+// instance masks from the depth in front of the background model (EMFusion::setMotionMasks) instead of reading them
+static bool motionMasks = false;
+static emf::MotionMaskParams motionParams;
 static unsigned meshMinTriangles = 0;    // --mesh-min-triangles
 static bool meshLargestObject = false;   // --mesh-largest-object
 // --checkpoint PATH --checkpoint-every N: the session is saved to PATH after every N-th frame (EMFusion::saveCheckpoint);
@@ -162,6 +171,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     color = emf.colorEnabled();
     emf.setMeshWeld(weldMeshes);
     emf.setMeshFilter(meshMinTriangles, meshLargestObject);
+    if (motionMasks) emf.setMotionMasks(true, motionParams);  // (not stored in a checkpoint: set again on --resume)
     std::vector<uint8_t> rgb;
     if (!masks.empty()) emf.usePreprocMasks(masks);   // apps/EM-Fusion.cpp:115
     emf.setupOutput(frameMeshes, volumes);            // apps/EM-Fusion.cpp:112
@@ -212,6 +222,7 @@ int main(int argc, char** argv) {
     float intrinsics[4] = {0.f, 0.f, 0.f, 0.f};
     bool haveIntrinsics = false;
     int maskFrames = 30, visThresh = 0, framesGiven = 0;
+    bool maskFramesGiven = false;
     float bgVoxel = 0.f;
     bool volumes = false;
     View3d view3d;
@@ -230,7 +241,14 @@ int main(int argc, char** argv) {
             for (int k = 0; k < 4; ++k) intrinsics[k] = static_cast<float>(std::atof(argv[++i]));
             haveIntrinsics = true;
         }
-        else if (a == "--mask-frames") maskFrames = next();
+        else if (a == "--mask-frames") {
+            maskFrames = next();
+            maskFramesGiven = true;
+        }
+        else if (a == "--motion-masks") motionMasks = true;
+        else if (a == "--motion-band" && i + 1 < argc) motionParams.band = static_cast<float>(std::atof(argv[++i]));
+        else if (a == "--motion-min-pixels") motionParams.minPixels = next();
+        else if (a == "--motion-max-masks") motionParams.maxMasks = next();
         else if (a == "--visibility-thresh") visThresh = next();
         else if (a == "--bg-voxel" && i + 1 < argc) bgVoxel = static_cast<float>(std::atof(argv[++i]));
         else if (a == "--volumes") volumes = true;
@@ -260,6 +278,11 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "unknown argument %s\n", a.c_str());
             return 2;
         }
+    }
+    if (motionMasks && !maskDir.empty()) {  // (before any device is touched)
+        std::fprintf(stderr, "usage: emfusion_synth: --motion-masks and --masks DIR exclude each other: a mask frame takes its "
+                             "instance masks from the files or proposes them itself\n");
+        return 2;
     }
     if (view3d.placed && !view3d.on) {
         std::fprintf(stderr, "emfusion_synth: --3d-vis-eye / --3d-vis-target need --3d-vis\n");
@@ -299,8 +322,14 @@ int main(int argc, char** argv) {
         params.visibilityThresh = static_cast<int>(1600 * scale * scale);
         params.boundary = static_cast<int>(20 * scale);
 
+        if (motionMasks && maskFramesGiven && maskFrames > 0) params.maskRCNNFrames = maskFrames;
+
         if (!resumePath.empty()) params = emf::EMFusion::checkpointParams(resumePath, &materialize);
         emf::SyntheticScene scene(params.frameSize, params.intr, objects);
+        // --autonomous --motion-masks: an object that is there from the first frame and hardly moves is fused into the
+        // background and never proposed, so the spheres ENTER the scene: the first frames show the empty room
+        const int motionEnter = 5;
+        emf::SyntheticScene emptyRoom(params.frameSize, params.intr, 0);
         emf::EMFusion emf(params, materialize ? emf::TSDF::Gradients::Materialized
                                               : emf::TSDF::Gradients::OnTheFly);
         std::vector<int> ids;
@@ -325,6 +354,7 @@ int main(int argc, char** argv) {
         emf.enableTimings(true);
         emf.setMeshWeld(weldMeshes);
         emf.setMeshFilter(meshMinTriangles, meshLargestObject);
+        if (motionMasks) emf.setMotionMasks(true, motionParams);
         if (!outDir.empty()) emf.setupOutput(frameMeshes, true);  // apps/EM-Fusion.cpp:112
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);
@@ -333,11 +363,12 @@ int main(int argc, char** argv) {
         int spawned = 0;
         const auto t0 = std::chrono::steady_clock::now();
         for (int f = firstFrame; f < frames; ++f) {  // while (reader->moreFrames())
-            scene.render(f, depth.data(), sid.data());  // frame = reader->getNextFrame()
+            if (autonomous && motionMasks && f < motionEnter) emptyRoom.render(f, depth.data(), sid.data());
+            else scene.render(f, depth.data(), sid.data());  // frame = reader->getNextFrame()
             emf::FrameInputs in;
             in.cam_pose = scene.cameraPose(f);
             in.runMasks = f % params.maskRCNNFrames == 0;
-            if (in.runMasks)
+            if (in.runMasks && !(autonomous && motionMasks))
                 for (int k = 0; k < objects; ++k) {
                     for (size_t i = 0; i < P; ++i) mask[i] = sid[i] == k + 1 ? 1 : 0;
                     maskDev[k].upload(mask.data(), emf.mainStream());
@@ -353,9 +384,10 @@ int main(int argc, char** argv) {
                 in.cleanUp = true;
                 // a "Mask R-CNN frame": all instance masks go through initOrMatchObjs inside the
                 // frame (match / spawn / existence bookkeeping), then integrateMasks, cleanUpObjs
-                if (in.runMasks)
+                // (--motion-masks: no masks go in; a mask frame stays one and proposes its own)
+                if (in.runMasks && !motionMasks)
                     for (int k = 0; k < objects; ++k) in.instanceMasks.push_back(maskDev[k].view());
-                in.runMasks = false;
+                if (!motionMasks) in.runMasks = false;
             }
             emf.setFrameInputs(in);
             emf::RGBD frame;
@@ -371,9 +403,9 @@ int main(int argc, char** argv) {
         emf.synchronize();
         if (autonomous) {
             const emf::Vec3f d = emf.getCameraPose().translation() - scene.cameraPose(frames - 1).translation();
-            std::printf("autonomous: %d objects spawned from masks; camera position error after %d "
+            std::printf("autonomous: %d objects spawned from %s; camera position error after %d "
                         "tracked frames: %.1f mm",
-                        spawned, frames - 1,
+                        spawned, motionMasks ? "motion masks" : "masks", frames - 1,
                         1e3 * std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]));
             if (const emf::TrackResult* r = emf.getTrackResult(0))
                 std::printf(" (last frame: %d LM steps, %d accepted)", r->iterations, r->accepted);

@@ -32,6 +32,13 @@ def main():
     ap.add_argument("--ignore-person", action="store_true",
                     help="Params.ignore_person of config/tum.cfg: person objects stay out of renderings and meshes")
     ap.add_argument("--masks", help="directory with Mask%%04d.plk files of the reference's preprocessing")
+    ap.add_argument("--motion-masks", dest="motion_masks", action="store_true",
+                    help="no mask files: every mask frame proposes its own instance masks from the depth that lies in "
+                         "front of the background model (Fusion.set_motion_masks); excludes --masks")
+    ap.add_argument("--motion-band", dest="motion_band", type=float, default=None, metavar="M",
+                    help="metres in front of the background a pixel must lie (default: the background's truncation distance)")
+    ap.add_argument("--motion-min-pixels", dest="motion_min_pixels", type=int, default=200, metavar="N")
+    ap.add_argument("--motion-max-masks", dest="motion_max_masks", type=int, default=8, metavar="N")
     ap.add_argument("--out", default=None, help="results directory (default emfusion_out)")
     ap.add_argument("--3d-vis", dest="vis3d", action="store_true",
                     help="the reference's 3D view: every frame also seen from a viewer 1 m behind the origin at "
@@ -69,7 +76,9 @@ def main():
     ap.add_argument("--visibility-thresh", type=int, default=0, help="0 = 1600 scaled by the image area")
     ap.add_argument("--mask-frames", type=int, default=30, help="Mask R-CNN every n-th frame (maskRCNNFrames)")
     args = ap.parse_args()
-    if args.vis3d and args.out is None:  # (before the device is opened)
+    if args.motion_masks and args.masks:  # (before the device is opened)
+        ap.error("--motion-masks and --masks exclude each other")
+    if args.vis3d and args.out is None:
         ap.error("--3d-vis writes OUT/mesh_vis_out/ and needs --out")
     if args.frame_meshes and args.out is None:
         ap.error("--export-frame-meshes writes OUT/frame_meshes/ and needs --out")
@@ -111,6 +120,8 @@ def main():
             fus.enable_color()
     fus.set_mesh_weld(args.weld_meshes)
     fus.set_mesh_filter(args.mesh_min_triangles, args.mesh_largest_object)
+    if args.motion_masks:  # (not stored in a checkpoint: set again on --resume)
+        fus.set_motion_masks(True, band=args.motion_band, min_pixels=args.motion_min_pixels, max_masks=args.motion_max_masks)
     fus.set_ignore_person(args.ignore_person)
     fus.set_preprocess(True)
     fus.set_cleanup(True)
@@ -144,7 +155,7 @@ def main():
             fus.set_color_image(image_view(c))
         if f >= 1:
             fus.set_tracking(camera=True, objects=True)  # frame 0 defines the world frame
-        fus.process_frame(image_view(d), eye, zero, {}, {}, False)
+        fus.process_frame(image_view(d), eye, zero, {}, {}, args.motion_masks and f % prm.mask_frames == 0)
         fus.synchronize()
         if args.vis3d:
             fus.render()  # apps/EM-Fusion.cpp:156: the rendering and, logged, the 3D view

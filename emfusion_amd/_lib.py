@@ -185,6 +185,8 @@ SIGNATURES = {
     "emf_hip_packGather": [_FP, C.c_uint64, _FP, C.c_uint32, C.c_uint32, _FP, _STREAM],
     "emf_hip_unpackFill": [_FP, C.c_uint64, _FP, _FP, _FP, C.c_uint32, _STREAM],
     "emf_hip_unpackLiterals": [_FP, C.c_uint64, _FP, C.c_uint32, C.c_uint32, _FP, _STREAM],
+    "emf_hip_motionMasksScratchBytes": [C.c_int, C.c_int, C.c_int],
+    "emf_hip_motionMasks": [_FP, _FP, C.c_int, C.c_int, C.c_void_p, _FP, _FP, _FP, _FP, _FP, _STREAM],
 }
 
 
@@ -220,6 +222,27 @@ class EmfTrackParams(C.Structure):
     @classmethod
     def defaults(cls):
         return cls(0.2, 64.0, 1e3, 1e-8, 1e-8, 2.0)
+
+
+class EmfMotionParams(C.Structure):
+    """Mirror of emf_motion_params_t (include/emf_hip.h "Motion masks")."""
+
+    _fields_ = [("band", C.c_float), ("continuity", C.c_float), ("erode", C.c_int32), ("min_pixels", C.c_int32),
+                ("max_masks", C.c_int32)]
+
+    @classmethod
+    def defaults(cls):
+        return cls(0.08, 0.05, 1, 200, 8)
+
+
+class EmfMotionInfo(C.Structure):
+    """Mirror of emf_motion_info_t: one proposal."""
+
+    _fields_ = [("label", C.c_int32), ("area", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32),
+                ("y1", C.c_int32)]
+
+
+MOTION_MAX_MASKS = 16
 
 
 class EmfTrackState(C.Structure):
@@ -285,6 +308,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.emf_hip_meshWeldScratchBytes.restype = C.c_size_t
     lib.emf_hip_meshComponentsScratchBytes.restype = C.c_size_t
     lib.emf_hip_packScratchBytes.restype = C.c_size_t
+    lib.emf_hip_motionMasksScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateCullScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateDirtyMapBytes.restype = C.c_size_t
     lib.emf_hip_signMapBytes.restype = C.c_size_t

@@ -128,6 +128,9 @@ void EMFusion::reset() {
     bgPrepared = false;
     bgListPending = false;
     colorImageSet = false;
+    motionInfo.clear();
+    motionFired = false;
+    motionVisStale = false;
     trackPredicted[0] = trackPredicted[1] = 0;
     Stream& s = Stream::Null();
     bg_associationWeights.setTo(1.f, s);
@@ -437,6 +440,7 @@ void EMFusion::processFrame(const RGBD& frame) {
     FrameInputs in = pending;
     in.preprocessDepth = true;              // reference EMFusion.cpp:74
     if (!maskPath.empty() && frameCount % params.maskRCNNFrames == 0) loadPreprocMasks(in);  // EMFusion.cpp:99-101, 375-395
+    if (motionOn && frameCount % params.maskRCNNFrames == 0) in.runMasks = true;  // a mask frame of the motion masks
     // the slot's device image may be overwritten once this frame's kernels are through -- also those a frame that
     // throws half-way has already enqueued
     auto markDone = [&]() {
@@ -580,9 +584,14 @@ void EMFusion::runSchedule(const emf_image_t& depthDev, const FrameInputs& in) {
         if (id >= 0) masks[id] = m;
     }
     lastAssigned.clear();
-    const bool instances = !in.instanceMasks.empty();
+    std::vector<emf_image_t> segs = in.instanceMasks;
+    motionInfo.clear();
+    motionFired = false;
+    // motion masks: a mask frame that ran a raycast and was handed no masks of any kind proposes its own
+    if (motionOn && frameCount > 0 && in.runMasks && segs.empty() && in.newObjectMasks.empty() && in.masks.empty())
+        proposeMotionMasks(segs);
+    const bool instances = !segs.empty();
     if (instances) {  // reference EMFusion.cpp:100-101
-        std::vector<emf_image_t> segs = in.instanceMasks;
         masks = initOrMatchObjs(segs, lastAssigned, in.instanceScores);
         masks.erase(-1);
     }

@@ -89,6 +89,15 @@ struct CheckpointStats {
     double msCopy = 0, msFile = 0, msTotal = 0;  // host time: device-to-host copies, file writes, the whole call
 };
 
+/** emf_motion_params_t for EMFusion::setMotionMasks (include/emf_hip.h "Motion masks"). */
+struct MotionMaskParams {
+    float band = -1.f;        // m; negative: the background's truncation distance
+    float continuity = 0.05f; // m
+    int erode = 1;            // 0 .. 3
+    int minPixels = 200;
+    int maxMasks = 8;         // 1 .. EMF_MOTION_MAX_MASKS
+};
+
 /** Per-stage GPU time of the last processed frame (milliseconds, from HIP events). */
 struct FrameTimings {
     float points = 0, estep = 0, raycast = 0, composite = 0, integrate = 0, masks = 0, total = 0;
@@ -248,10 +257,25 @@ public:
      * (MaskRCNN.cpp:290-301) on black: rgb = W x H x 3 bytes; empty before the first mask frame.  Returns the number
      * of instances of that frame.
      */
-    int getLastMasks(std::vector<uint8_t>& rgb) const {
-        rgb = lastMaskVis;
-        return lastMaskInstances;
-    }
+    int getLastMasks(std::vector<uint8_t>& rgb);
+    /**
+     * Motion masks (include/emf_hip.h "Motion masks"; new behaviour, off by default, may be switched at any time).
+     * With it on, a frame that ran a raycast (frameCount > 0), is a mask frame (FrameInputs::runMasks; every
+     * maskRCNNFrames-th frame of processFrame(const RGBD&)) and was handed no masks of any kind (instanceMasks --
+     * queued, or loaded by usePreprocMasks --, newObjectMasks, masks: those take precedence) proposes its own
+     * instance masks: connected regions of pixels measured in front of the background's raycast by more than
+     * `band`.  The kernels run on the main stream between raycast and integration, the count is read back (the one
+     * wait) and the first `count` planes go through initOrMatchObjs exactly as queued instance masks do, without
+     * class scores; matching, carving, spawning, integrateMasks, existence probabilities and clean-up see ordinary
+     * masks.  Nothing is kept from frame to frame and nothing goes into a checkpoint (a resumed session calls this
+     * again).  With it off no launch and no output byte changes.  Throws on the sharded path (the background's ray
+     * lengths are gathered in bands there and the life cycle's exchanges assume masks every rank was handed).
+     */
+    void setMotionMasks(bool on, const MotionMaskParams& p = MotionMaskParams());
+    bool motionMasksEnabled() const { return motionOn; }
+    /** The proposals of the last processed frame (none if it did not propose) and, if wanted, the W x H rank image
+     *  (-1: no proposal); waits for the device when it has labels to fetch. */
+    const std::vector<emf_motion_info_t>& lastMotionMasks(std::vector<int32_t>* labels = nullptr);
     /** Ids returned by initNewObjVolume for FrameInputs::newObjectMasks of the last frame (-1: none). */
     const std::vector<int>& lastCreatedObjects() const { return lastCreated; }
     Affine3f getCameraPose() const { return pose; }
@@ -520,6 +544,17 @@ private:
     std::vector<DeviceImage<uint8_t>> preprocMaskDev;  // the instances of the last mask frame (device copies)
     std::vector<uint8_t> lastMaskVis;
     int lastMaskInstances = 0;
+    // ---- motion masks (setMotionMasks; EMFusionLifecycle.cpp) ----
+    bool motionOn = false;
+    emf_motion_params_t motionParams{};
+    DeviceBuffer motionScratch, motionPlanes;   // the kernels' scratch; EMF_MOTION_MAX_MASKS u8 planes
+    DeviceBuffer motionInfoDev;                 // EMF_MOTION_MAX_MASKS emf_motion_info_t, then the count
+    DeviceImage<int32_t> motionLabels;
+    std::vector<emf_motion_info_t> motionInfo;  // the last frame's proposals
+    bool motionFired = false;                   // the last frame ran the proposal (motionLabels is that frame's)
+    bool motionVisStale = false;                // lastMaskVis is to be drawn from motionLabels when somebody asks
+    void ensureMotionBuffers();
+    void proposeMotionMasks(std::vector<emf_image_t>& segs);
     DeviceImage<float> depthFiltered;  // output of preprocessDepth
     DeviceImage<float> invLambda;  // per-pixel 1 / lambda of the integration, fixed by the intrinsics (sw.useLambdaTable)
     DeviceBuffer integrateCullScratch;  // survivor list of emf_hip_integrateBatchedCulled (empty: plain launch)
@@ -702,6 +737,7 @@ private:
     PinnedBuffer trackStatesHost;  // emf_track_state_t[EMF_MAX_MODELS]: mirror of trackStates
     PinnedBuffer trackWatch;       // mapped: the words the step kernel reports to while the stream runs (empty: chunked polls)
     PinnedBuffer lifecycleHost;    // kLcHostBytes, layout above
+    PinnedBuffer motionHost;       // mirror of motionInfoDev
     PinnedBuffer viewPosesHost;    // EMF_MAX_MODELS viewer -> volume poses
     PinnedBuffer meshHost;         // EMF_MAX_MODELS emf_model_t, then the counts and bases read back
     PinnedBuffer meshStage;        // staging of the meshes' bytes (grown when needed)

@@ -6,11 +6,23 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <fstream>
+#include <string>
 
 namespace emf {
 
 using namespace detail;
+
+namespace {
+// the reference's instance colours (MaskRCNN.cpp:290-301), index 0 = no instance
+const unsigned char colors[31][3] = {
+    {0, 0, 0},       {0, 0, 255},     {255, 0, 0},    {0, 255, 0},     {255, 26, 184},  {255, 211, 0},   {0, 131, 246},
+    {0, 140, 70},    {167, 96, 61},   {79, 0, 105},   {0, 255, 246},   {61, 123, 140},  {237, 167, 255}, {211, 255, 149},
+    {184, 79, 255},  {228, 26, 87},   {131, 131, 0},  {0, 255, 149},   {96, 0, 43},     {246, 131, 17},  {202, 255, 0},
+    {43, 61, 0},     {0, 52, 193},    {255, 202, 131}, {0, 43, 96},    {158, 114, 140}, {79, 184, 17},   {158, 193, 255},
+    {149, 158, 123}, {255, 123, 175}, {158, 8, 0}};
+}  // namespace
 
 // runMaskRCNN with a mask path (reference EMFusion.cpp:383-389) + the label image getLastMasks hands out
 void EMFusion::loadPreprocMasks(FrameInputs& in) {
@@ -30,15 +42,9 @@ void EMFusion::loadPreprocMasks(FrameInputs& in) {
     preprocMaskDev.clear();
     in.instanceMasks.clear();
     in.instanceScores.clear();
-    // the reference's instance colours (MaskRCNN.cpp:290-301), index 0 = no instance
-    static const unsigned char colors[31][3] = {
-        {0, 0, 0},       {0, 0, 255},     {255, 0, 0},    {0, 255, 0},     {255, 26, 184},  {255, 211, 0},   {0, 131, 246},
-        {0, 140, 70},    {167, 96, 61},   {79, 0, 105},   {0, 255, 246},   {61, 123, 140},  {237, 167, 255}, {211, 255, 149},
-        {184, 79, 255},  {228, 26, 87},   {131, 131, 0},  {0, 255, 149},   {96, 0, 43},     {246, 131, 17},  {202, 255, 0},
-        {43, 61, 0},     {0, 52, 193},    {255, 202, 131}, {0, 43, 96},    {158, 114, 140}, {79, 184, 17},   {158, 193, 255},
-        {149, 158, 123}, {255, 123, 175}, {158, 8, 0}};
     lastMaskVis.assign(static_cast<size_t>(w) * h * 3, 0);
     lastMaskInstances = n;
+    motionVisStale = false;
     for (int k = 0; k < n; ++k) {
         preprocMaskDev.emplace_back(params.frameSize);
         preprocMaskDev.back().upload(pm.masks[k].data(), main);
@@ -53,6 +59,97 @@ void EMFusion::loadPreprocMasks(FrameInputs& in) {
     main.waitForCompletion();  // (pm's host buffers go out of scope)
     for (auto& m : preprocMaskDev) in.instanceMasks.push_back(m.view());
     in.instanceScores = pm.scores;
+}
+
+// ---- motion masks: instance proposals from the frame's points and the background's raycast -------------
+
+void EMFusion::setMotionMasks(bool on, const MotionMaskParams& p) {
+    if (!on) {
+        motionOn = false;
+        return;
+    }
+    // the background's ray lengths are band-local until the composite's exchange there, and the life cycle's
+    // exchanges assume masks that every rank was handed
+    if (sharded) throw HipError("EMFusion::setMotionMasks: motion masks are not supported on the sharded path", EMF_E_ARG);
+    if (p.erode < 0 || p.erode > 3) throw HipError("EMFusion::setMotionMasks: erode must be 0 .. 3", EMF_E_ARG);
+    if (p.maxMasks < 1 || p.maxMasks > EMF_MOTION_MAX_MASKS)
+        throw HipError("EMFusion::setMotionMasks: maxMasks must be 1 .. " + std::to_string(EMF_MOTION_MAX_MASKS), EMF_E_ARG);
+    if (p.minPixels < 0) throw HipError("EMFusion::setMotionMasks: minPixels must not be negative", EMF_E_ARG);
+    if (!(p.continuity >= 0.f)) throw HipError("EMFusion::setMotionMasks: continuity must not be negative", EMF_E_ARG);
+    if (p.band != p.band) throw HipError("EMFusion::setMotionMasks: band is not a number", EMF_E_ARG);
+    // by default the margin below which the TSDF itself does not tell "in front of the surface" from the surface
+    motionParams.band = p.band < 0.f ? params.globalRelTruncDist * params.globalVoxelSize : p.band;
+    motionParams.continuity = p.continuity;
+    motionParams.erode = p.erode;
+    motionParams.min_pixels = p.minPixels;
+    motionParams.max_masks = p.maxMasks;
+    motionOn = true;
+}
+
+void EMFusion::ensureMotionBuffers() {
+    if (!motionScratch.empty()) return;
+    const int w = params.frameSize.width, h = params.frameSize.height;
+    const size_t bytes = emf_hip_motionMasksScratchBytes(w, h, EMF_MOTION_MAX_MASKS);
+    if (bytes == 0) throw HipError("EMFusion::setMotionMasks: the frame size is beyond the motion masks' limits", EMF_E_LIMIT);
+    motionScratch = DeviceBuffer(bytes);
+    motionPlanes = DeviceBuffer(params.frameSize.area() * EMF_MOTION_MAX_MASKS);
+    motionInfoDev = DeviceBuffer(EMF_MOTION_MAX_MASKS * sizeof(emf_motion_info_t) + 16);
+    motionLabels = DeviceImage<int32_t>(params.frameSize);
+    motionHost = PinnedBuffer(motionInfoDev.bytes());
+}
+
+// The hook of runSchedule: the proposals of this frame become its instance masks.  Everything on `main`, behind the
+// raycast that wrote bg_raylengths (on the per-volume path the volume streams were joined into `main`) and the launch
+// that made the points; the count and the info records come back in one small copy, the only wait.
+void EMFusion::proposeMotionMasks(std::vector<emf_image_t>& segs) {
+    ensureMotionBuffers();
+    const int w = params.frameSize.width, h = params.frameSize.height;
+    emf_motion_info_t* infoDev = motionInfoDev.as<emf_motion_info_t>();
+    int32_t* countDev = reinterpret_cast<int32_t*>(infoDev + EMF_MOTION_MAX_MASKS);
+    emfCheck(emf_hip_motionMasks(points.ptr(), bg_raylengths.ptr(), w, h, &motionParams, motionScratch.data(),
+                                 motionLabels.ptr(), motionPlanes.as<uint8_t>(), infoDev, countDev, main.abi()),
+             "motionMasks");
+    const size_t used = motionParams.max_masks * sizeof(emf_motion_info_t);
+    hipCheck(hipMemcpyAsync(motionHost.data(), infoDev, used, hipMemcpyDeviceToHost, main.get()), "hipMemcpyAsync");
+    hipCheck(hipMemcpyAsync(motionHost.as<char>() + used, countDev, sizeof(int32_t), hipMemcpyDeviceToHost, main.get()),
+             "hipMemcpyAsync");
+    main.waitForCompletion();
+    int32_t count = 0;
+    std::memcpy(&count, motionHost.as<char>() + used, sizeof(count));
+    count = std::max(0, std::min(count, motionParams.max_masks));
+    const emf_motion_info_t* info = motionHost.as<const emf_motion_info_t>();
+    motionInfo.assign(info, info + count);
+    motionFired = true;
+    lastMaskInstances = count;  // getLastMasks draws them when somebody asks
+    motionVisStale = true;
+    const size_t plane = params.frameSize.area();
+    for (int r = 0; r < count; ++r)
+        segs.push_back(imageView(motionPlanes.as<uint8_t>() + plane * r, params.frameSize, 1));
+}
+
+const std::vector<emf_motion_info_t>& EMFusion::lastMotionMasks(std::vector<int32_t>* labels) {
+    if (labels) {
+        if (motionFired) *labels = motionLabels.download(main);
+        else labels->assign(params.frameSize.area(), -1);
+    }
+    return motionInfo;
+}
+
+int EMFusion::getLastMasks(std::vector<uint8_t>& rgb) {
+    if (motionVisStale) {  // the proposals of the last frame that looked for any, in instance colours by rank
+        const std::vector<int32_t> lab = motionLabels.download(main);
+        lastMaskVis.assign(lab.size() * 3, 0);
+        for (size_t i = 0; i < lab.size(); ++i) {
+            if (lab[i] < 0) continue;
+            const unsigned char* c = colors[1 + lab[i] % 30];
+            lastMaskVis[3 * i] = c[0];
+            lastMaskVis[3 * i + 1] = c[1];
+            lastMaskVis[3 * i + 2] = c[2];
+        }
+        motionVisStale = false;
+    }
+    rgb = lastMaskVis;
+    return lastMaskInstances;
 }
 
 // ---- object creation / matching from masks ---------------------------------------------------------

@@ -417,6 +417,34 @@ int emf_fusion_get_last_masks(emf_fusion_t* h, uint8_t* rgb, size_t capacity, in
     });
 }
 
+int emf_fusion_set_motion_masks(emf_fusion_t* h, int on, const emf_motion_params_t* params) {
+    REQ(h);
+    return guarded([&] {
+        MotionMaskParams p;
+        if (params) {
+            p.band = params->band;
+            p.continuity = params->continuity;
+            p.erode = params->erode;
+            p.minPixels = params->min_pixels;
+            p.maxMasks = params->max_masks;
+        }
+        h->impl->setMotionMasks(on != 0, p);
+    });
+}
+
+int emf_fusion_last_motion_masks(emf_fusion_t* h, int32_t* labels_out, emf_motion_info_t* info_out, int capacity,
+                                 int32_t* count) {
+    REQ(h);
+    REQ(count);
+    return guarded([&] {
+        std::vector<int32_t> labels;
+        const auto& info = h->impl->lastMotionMasks(labels_out ? &labels : nullptr);
+        *count = static_cast<int32_t>(info.size());
+        for (int i = 0; info_out && i < capacity && i < static_cast<int>(info.size()); ++i) info_out[i] = info[i];
+        if (labels_out) std::copy(labels.begin(), labels.end(), labels_out);
+    });
+}
+
 int emf_io_read_color_png(const char* path, uint8_t* out, size_t capacity, int32_t* width, int32_t* height) {
     REQ(path);
     return guarded([&] {

@@ -32,6 +32,7 @@
 // All atomics are ordinary global atomics on vector memory; every output is a pure function of the index buffer.
 #include "common.hpp"
 #include "mesh_scan.hpp"
+#include "union_find.hpp"
 
 namespace emf_hip {
 namespace {
@@ -136,37 +137,7 @@ __device__ __forceinline__ bool corners(const CcArgs& a, const Range& r, const i
     return ok;
 }
 
-__device__ __forceinline__ unsigned load_parent(const unsigned* parent, unsigned x) {
-    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the root above x at the time of the walk.  Every step goes to a strictly smaller index (parent[y] < y for a
-// non-root), so the loop ends after at most x steps; nodes on the way are pointed at their grandparent.
-__device__ __forceinline__ unsigned find_root(unsigned* parent, unsigned x) {
-    unsigned p = load_parent(parent, x);
-    while (p < x) {
-        const unsigned gp = load_parent(parent, p);
-        if (gp < p) atomicMin(parent + x, gp);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-
-// Joins the trees of a and b.  Each round either ends or goes on from indices of which one is strictly smaller than
-// before (a failed CAS saw a parent below the root it tried to hook), so the rounds are bounded by a + b.
-__device__ __forceinline__ void unite(unsigned* parent, unsigned a, unsigned b) {
-    for (;;) {
-        a = find_root(parent, a);
-        b = find_root(parent, b);
-        if (a == b) return;
-        const unsigned hi = a > b ? a : b, lo = a > b ? b : a;
-        const unsigned seen = atomicCAS(parent + hi, hi, lo);
-        if (seen == hi) return;
-        a = seen;  // hi was hooked meanwhile: seen < hi
-        b = lo;
-    }
-}
+// (find_root / unite: union_find.hpp, shared with motion_masks.hip)
 
 __global__ __launch_bounds__(kCcBlock) void k_cc_init(const CcArgs a) {
     const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;

@@ -1220,3 +1220,60 @@ def unpack_buffer(record: bytes, dst: DeviceArray, arena_chunks: int = PACK_AREN
                                         _stream(stream)))
         synchronize()  # the arena is freed when the loop moves on
     return dst
+
+
+# ---- motion masks (include/emf_hip.h "Motion masks") ---------------------------------------------------------------
+
+class MotionBuffers:
+    """The scratch and the outputs of emf_hip_motionMasks for one frame size, reusable from call to call."""
+
+    def __init__(self, width: int, height: int, max_masks: int = _lib.MOTION_MAX_MASKS):
+        nbytes = int(_L.emf_hip_motionMasksScratchBytes(int(width), int(height), int(max_masks)))
+        if nbytes == 0:
+            raise ValueError(f"motion masks: {width} x {height} with {max_masks} masks is beyond the limits")
+        self.width, self.height, self.max_masks = int(width), int(height), int(max_masks)
+        self.scratch = DeviceArray.zeros(((nbytes + 3) // 4,), np.uint32)
+        self.labels = DeviceArray.zeros((height, width), np.int32)
+        self.masks = DeviceArray.zeros((max_masks, height, width), np.uint8)
+        self.info = DeviceArray.zeros((max_masks, 6), np.int32)
+        self.count = DeviceArray.zeros((1,), np.int32)
+
+
+def motion_params(band=None, continuity=None, erode=None, min_pixels=None, max_masks=None) -> _lib.EmfMotionParams:
+    """emf_motion_params_t with the documented defaults for whatever is None."""
+    p = _lib.EmfMotionParams.defaults()
+    for name, value in (("band", band), ("continuity", continuity), ("erode", erode), ("min_pixels", min_pixels),
+                        ("max_masks", max_masks)):
+        if value is not None:
+            setattr(p, name, value)
+    return p
+
+
+def motion_info_dicts(info: np.ndarray, count: int):
+    """Rows {label, area, x0, y0, x1, y1} of an info array as a list of dicts."""
+    keys = ("label", "area", "x0", "y0", "x1", "y1")
+    return [dict(zip(keys, (int(v) for v in row))) for row in np.asarray(info).reshape(-1, 6)[:count]]
+
+
+def motion_masks(points, bg_raylengths, band=None, continuity=None, erode=None, min_pixels=None, max_masks=None,
+                 buffers: Optional[MotionBuffers] = None, stream=None):
+    """emf_hip_motionMasks: instance proposals from a points image (H, W, 3) f32 and the background's ray-length
+    image (H, W) f32, numpy or dense device arrays.  Returns dict(labels (H, W) i32, masks (max_masks, H, W) u8,
+    info (max_masks, 6) i32 rows {label, area, x0, y0, x1, y1}, count, proposals: the first `count` rows as dicts).
+    `buffers` (MotionBuffers of the same size) are reused when given."""
+    pts = _on_device(points, np.float32)
+    bg = _on_device(bg_raylengths, np.float32)
+    h, w = bg.shape
+    assert pts.shape == (h, w, 3) and not pts.padded and not bg.padded, "dense (H, W, 3) points and (H, W) ray lengths"
+    p = motion_params(band, continuity, erode, min_pixels, max_masks)
+    if buffers is None:
+        buffers = MotionBuffers(w, h, min(max(int(p.max_masks), 1), _lib.MOTION_MAX_MASKS))
+    assert (buffers.width, buffers.height) == (w, h) and buffers.max_masks >= p.max_masks
+    check("emf_hip_motionMasks",
+          _L.emf_hip_motionMasks(_ptr(pts), _ptr(bg), w, h, C.byref(p), _ptr(buffers.scratch), _ptr(buffers.labels),
+                                 _ptr(buffers.masks), _ptr(buffers.info), _ptr(buffers.count), _stream(stream)))
+    count = int(buffers.count.numpy()[0])  # waits for the device: the inputs and the scratch may go after this
+    info = buffers.info.numpy()[:p.max_masks]
+    masks = buffers.masks.numpy().reshape(-1)[:p.max_masks * h * w].reshape(p.max_masks, h, w)
+    return dict(labels=buffers.labels.numpy(), masks=masks, info=info, count=count,
+                proposals=motion_info_dicts(info, count))

@@ -120,6 +120,8 @@ def load() -> C.CDLL:
         "emf_fusion_process_rgbd_color": [vp, fp, C.c_void_p, C.c_int32, C.c_int32],
         "emf_fusion_colored_voxels": [vp, C.POINTER(C.c_uint64)],
         "emf_fusion_get_last_masks": [vp, C.c_void_p, C.c_size_t, ip],
+        "emf_fusion_set_motion_masks": [vp, C.c_int, C.c_void_p],
+        "emf_fusion_last_motion_masks": [vp, C.c_void_p, C.c_void_p, C.c_int, ip],
         "emf_io_read_depth_png": [C.c_char_p, C.c_float, fp, C.c_size_t, ip, ip],
         "emf_io_read_exr": [C.c_char_p, C.c_char_p, fp, C.c_size_t, ip, ip],
         "emf_io_read_color_png": [C.c_char_p, C.c_void_p, C.c_size_t, ip, ip],
@@ -612,6 +614,30 @@ class Fusion:
         img = np.zeros((self.params.height, self.params.width, 3), np.uint8)
         _check("emf_fusion_get_last_masks", load().emf_fusion_get_last_masks(self._h, img.ctypes.data, img.nbytes, C.byref(n)))
         return n.value, img
+
+    def set_motion_masks(self, on=True, band=None, continuity=None, erode=1, min_pixels=200, max_masks=8):
+        """Motion masks: a mask frame that ran a raycast and was handed no masks proposes its own instance masks --
+        connected regions of pixels measured in front of the background's raycast by more than `band` metres (None:
+        the background's truncation distance), neighbours joined across ray-length steps of at most `continuity`
+        metres (None: 0.05), after `erode` 3 x 3 erosion passes, at least `min_pixels` large, the `max_masks` largest
+        -- and runs them through the object life cycle as queued instance masks would.  Queued or preprocessed masks
+        take precedence on a frame that has them.  Off by default; nothing is kept between frames or in a checkpoint
+        (a resumed session switches it on again).  Refused on the sharded path."""
+        from ._lib import EmfMotionParams
+        p = EmfMotionParams(-1.0 if band is None else float(band), 0.05 if continuity is None else float(continuity),
+                            int(erode), int(min_pixels), int(max_masks))
+        _check("emf_fusion_set_motion_masks", load().emf_fusion_set_motion_masks(self._h, int(bool(on)), C.addressof(p)))
+
+    def last_motion_masks(self):
+        """The proposals of the last processed frame: ((H, W) i32 image of proposal ranks, -1 where none is, list of
+        dicts {label, area, x0, y0, x1, y1} by rank).  Empty / all -1 if the frame proposed nothing."""
+        from ._lib import MOTION_MAX_MASKS
+        labels = np.empty((self.params.height, self.params.width), np.int32)
+        info, n = np.zeros((MOTION_MAX_MASKS, 6), np.int32), C.c_int32(0)
+        _check("emf_fusion_last_motion_masks",
+               load().emf_fusion_last_motion_masks(self._h, labels.ctypes.data, info.ctypes.data, MOTION_MAX_MASKS, C.byref(n)))
+        keys = ("label", "area", "x0", "y0", "x1", "y1")
+        return labels, [dict(zip(keys, (int(v) for v in row))) for row in info[:n.value]]
 
     def set_tracking(self, camera=True, objects=True):
         """From the next frame on, track the camera / object poses instead of taking them as inputs."""

@@ -146,6 +146,24 @@ int emf_fusion_process_rgbd_color(emf_fusion_t* h, const float* depth_host, cons
 int emf_fusion_colored_voxels(emf_fusion_t* h, uint64_t* count);
 int emf_fusion_use_preproc_masks(emf_fusion_t* h, const char* path);
 int emf_fusion_get_last_masks(emf_fusion_t* h, uint8_t* rgb, size_t capacity, int32_t* instances);
+/* Motion masks (include/emf_hip.h "Motion masks"; off by default, may be switched at any time, and with it off no
+ * launch and no output byte of a frame changes).  on != 0: a frame that ran a raycast (every frame but the first), is
+ * a mask frame (run_masks of emf_fusion_process_frame; every mask_frames-th frame of emf_fusion_process_rgbd) and was
+ * handed NO masks of any kind -- queued instance or new-object masks, a Mask%04d.plk of use_preproc_masks, the masks
+ * argument of process_frame: those take precedence -- proposes its own instance masks from the frame's points and the
+ * background's ray lengths, on the frame's stream between raycast and integration, and hands them to the object life
+ * cycle exactly as queued instance masks are (no class scores).  One wait per such frame, for the count.
+ *   params             NULL: the defaults.  band < 0 (the default here): the background's truncation distance.
+ *                      EMF_E_ARG for a value outside the ranges of emf_motion_params_t.
+ *   last_motion_masks  of the last processed frame: *count proposals (0 if the frame proposed nothing or did not run
+ *                      the proposal at all), at most `capacity` records to info_out (may be NULL), and to labels_out
+ *                      (may be NULL) the W x H int32 rank image, -1 where no proposal is.  Waits for the device.
+ * emf_fusion_get_last_masks draws the proposals of the last frame that made any attempt, in instance colours by rank.
+ * Nothing is kept from frame to frame and nothing goes into a checkpoint: a resumed session switches it on again.
+ * Refused (EMF_E_ARG, "... not supported on the sharded path", the session stays usable) on the sharded path. */
+int emf_fusion_set_motion_masks(emf_fusion_t* h, int on, const emf_motion_params_t* params);
+int emf_fusion_last_motion_masks(emf_fusion_t* h, int32_t* labels_out, emf_motion_info_t* info_out, int capacity,
+                                 int32_t* count);
 
 /* Create an object volume (edge vol_size metres, obj_res voxels) centred at `center` in world
  * coordinates; every rank issues the same calls.  *id_out = object id (1-based). */

@@ -1240,6 +1240,59 @@ int emf_hip_unpackFill(void* dst, uint64_t nbytes, const uint8_t* classes, const
 int emf_hip_unpackLiterals(void* dst, uint64_t nbytes, const uint32_t* literal_chunks, uint32_t first, uint32_t count,
                            const void* arena, emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Motion masks (new behaviour: the reference takes its instance masks from Mask R-CNN).  Opt-in; nothing above
+ * is touched.  Instance proposals from geometry alone: connected regions of pixels whose measurement lies IN
+ * FRONT of the background model's own raycast by more than a margin.
+ * Inputs, both dense (no row padding), device memory:
+ *   points        : w x h x 3 f32, the frame's points in the camera frame (emf_hip_computePoints)
+ *   bg_raylengths : w x h f32, the background's raycast: the distance along the pixel's ray, 0 = the ray missed
+ * With p the pixel's point, m = sqrtf(p.x * p.x + p.y * p.y + p.z * p.z) (every operation rounded on its own) and
+ * b its background ray length:
+ *   1 candidates  a pixel is a CANDIDATE iff p.z > 0 and b > 0 and b - m > band.  A pixel whose background ray
+ *                 missed is unknown, not novel: never a candidate.  NaN fails every comparison.
+ *   2 erosion     `erode` passes of 3 x 3 binary erosion; outside the image counts as not-candidate.
+ *   3 labels      4-connected components of the eroded candidates, two neighbours joined only if
+ *                 |m_a - m_b| <= continuity.  A component's LABEL is the smallest linear index y * w + x in it.
+ *   4 selection   components of at least min_pixels pixels, by area descending, ties to the smaller label, the
+ *                 first max_masks of them: the PROPOSALS, their position in that order their RANK.
+ *   5 outputs     labels : w x h i32, the rank of the pixel's proposal, -1 for every other pixel
+ *                 masks  : max_masks planes of w x h u8, plane r = 1 inside proposal r, 0 elsewhere; planes at and
+ *                          past the count are written as zeros
+ *                 info   : max_masks emf_motion_info_t, entries at and past the count zeroed
+ *                 count  : one i32, the number of proposals
+ * Integer work and single comparisons on floats only: the outputs are a pure function of the inputs, whatever
+ * order the workgroups run in.  Nothing allocates, copies to the host or waits.
+ * Every rejected argument -- a NULL pointer included -- returns EMF_E_ARG with nothing enqueued; w * h <= 2^30.
+ * ---------------------------------------------------------------------------------------------- */
+#define EMF_MOTION_MAX_MASKS 16
+
+typedef struct emf_motion_params {
+    float band;         /* m, >= 0: the candidate margin.  0.08 by default; the host classes use the background's
+                           truncation distance, below which the TSDF itself cannot tell "in front" from noise */
+    float continuity;   /* m, >= 0: the largest ray-length step across which neighbours still join.  0.05 */
+    int32_t erode;      /* 0 .. 3 erosion passes.  1: removes the mixed pixels of a depth edge and one-pixel bridges */
+    int32_t min_pixels; /* >= 0: the smallest component area kept.  200 */
+    int32_t max_masks;  /* 1 .. EMF_MOTION_MAX_MASKS.  8 */
+} emf_motion_params_t;
+
+typedef struct emf_motion_info {
+    int32_t label;          /* the smallest linear index of the proposal's pixels */
+    int32_t area;           /* its pixels */
+    int32_t x0, y0, x1, y1; /* its bounding box, both corners inclusive */
+} emf_motion_info_t;
+
+/* Bytes of device scratch for a w x h frame: 18 bytes per pixel plus the scan's per-workgroup sums, under
+ * 19 bytes per pixel + 1 KiB.  0 for a size or a max_masks outside the limits. */
+size_t emf_hip_motionMasksScratchBytes(int w, int h, int max_masks);
+
+/* Stages 1-5 on `stream`: 9 + erode launches.  scratch_dev: emf_hip_motionMasksScratchBytes(w, h, max_masks)
+ * bytes, 16-byte aligned, contents irrelevant before and meaningless after.  params is read before the call
+ * returns. */
+int emf_hip_motionMasks(const float* points, const float* bg_raylengths, int w, int h, const emf_motion_params_t* params,
+                        void* scratch_dev, int32_t* labels, uint8_t* masks, emf_motion_info_t* info, int32_t* count,
+                        emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
