@@ -95,6 +95,11 @@ static bool weldMeshes = false;  // --weld-meshes
 // instance masks from the depth in front of the background model (EMFusion::setMotionMasks) instead of reading them
 static bool motionMasks = false;
 static emf::MotionMaskParams motionParams;
+// --follow-camera [--follow-step X,Y,Z] [--follow-lookahead M]: the background is rolled by whole voxels after the camera
+// (EMFusion::setBackgroundFollow); what leaves is meshed and written as OUT/bg_retired/.  A rolled
+// session's checkpoint carries the switch and its parameters.
+static bool followCamera = false;
+static emf::BackgroundFollowParams followParams;
 static unsigned meshMinTriangles = 0;    // --mesh-min-triangles
 static bool meshLargestObject = false;   // --mesh-largest-object
 // --checkpoint PATH --checkpoint-every N: the session is saved to PATH after every N-th frame (EMFusion::saveCheckpoint);
@@ -172,6 +177,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     emf.setMeshWeld(weldMeshes);
     emf.setMeshFilter(meshMinTriangles, meshLargestObject);
     if (motionMasks) emf.setMotionMasks(true, motionParams);  // (not stored in a checkpoint: set again on --resume)
+    if (followCamera) emf.setBackgroundFollow(true, followParams);
     std::vector<uint8_t> rgb;
     if (!masks.empty()) emf.usePreprocMasks(masks);   // apps/EM-Fusion.cpp:115
     emf.setupOutput(frameMeshes, volumes);            // apps/EM-Fusion.cpp:112
@@ -246,6 +252,16 @@ int main(int argc, char** argv) {
             maskFramesGiven = true;
         }
         else if (a == "--motion-masks") motionMasks = true;
+        else if (a == "--follow-camera") followCamera = true;
+        else if (a == "--follow-step" && i + 1 < argc) {
+            int x = 0, y = 0, z = 0;
+            if (std::sscanf(argv[++i], "%d,%d,%d", &x, &y, &z) != 3) {
+                std::fprintf(stderr, "usage: emfusion_synth: --follow-step X,Y,Z (voxels, positive multiples of 32,8,8)\n");
+                return 2;
+            }
+            followParams.step = emf::Vec3i(x, y, z);
+        }
+        else if (a == "--follow-lookahead" && i + 1 < argc) followParams.lookAhead = static_cast<float>(std::atof(argv[++i]));
         else if (a == "--motion-band" && i + 1 < argc) motionParams.band = static_cast<float>(std::atof(argv[++i]));
         else if (a == "--motion-min-pixels") motionParams.minPixels = next();
         else if (a == "--motion-max-masks") motionParams.maxMasks = next();
@@ -355,6 +371,7 @@ int main(int argc, char** argv) {
         emf.setMeshWeld(weldMeshes);
         emf.setMeshFilter(meshMinTriangles, meshLargestObject);
         if (motionMasks) emf.setMotionMasks(true, motionParams);
+        if (followCamera) emf.setBackgroundFollow(true, followParams);
         if (!outDir.empty()) emf.setupOutput(frameMeshes, true);  // apps/EM-Fusion.cpp:112
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);

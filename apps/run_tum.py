@@ -39,6 +39,13 @@ def main():
                     help="metres in front of the background a pixel must lie (default: the background's truncation distance)")
     ap.add_argument("--motion-min-pixels", dest="motion_min_pixels", type=int, default=200, metavar="N")
     ap.add_argument("--motion-max-masks", dest="motion_max_masks", type=int, default=8, metavar="N")
+    ap.add_argument("--follow-camera", dest="follow_camera", action="store_true",
+                    help="roll the background by whole voxels after the camera (Fusion.set_background_follow); what leaves "
+                         "the cube is meshed and written as OUT/bg_retired/")
+    ap.add_argument("--follow-step", dest="follow_step", default="64,64,64", metavar="X,Y,Z",
+                    help="voxels a roll moves by per axis: positive multiples of 32,8,8")
+    ap.add_argument("--follow-lookahead", dest="follow_lookahead", type=float, default=0.0, metavar="M",
+                    help="follow the point M metres in front of the camera")
     ap.add_argument("--out", default=None, help="results directory (default emfusion_out)")
     ap.add_argument("--3d-vis", dest="vis3d", action="store_true",
                     help="the reference's 3D view: every frame also seen from a viewer 1 m behind the origin at "
@@ -78,6 +85,11 @@ def main():
     args = ap.parse_args()
     if args.motion_masks and args.masks:  # (before the device is opened)
         ap.error("--motion-masks and --masks exclude each other")
+    try:
+        follow_step = tuple(int(v) for v in args.follow_step.split(","))
+        assert len(follow_step) == 3
+    except (ValueError, AssertionError):
+        ap.error("--follow-step takes three integers X,Y,Z")
     if args.vis3d and args.out is None:
         ap.error("--3d-vis writes OUT/mesh_vis_out/ and needs --out")
     if args.frame_meshes and args.out is None:
@@ -122,6 +134,8 @@ def main():
     fus.set_mesh_filter(args.mesh_min_triangles, args.mesh_largest_object)
     if args.motion_masks:  # (not stored in a checkpoint: set again on --resume)
         fus.set_motion_masks(True, band=args.motion_band, min_pixels=args.motion_min_pixels, max_masks=args.motion_max_masks)
+    if args.follow_camera:
+        fus.set_background_follow(True, step=follow_step, look_ahead=args.follow_lookahead)
     fus.set_ignore_person(args.ignore_person)
     fus.set_preprocess(True)
     fus.set_cleanup(True)

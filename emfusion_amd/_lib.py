@@ -187,6 +187,8 @@ SIGNATURES = {
     "emf_hip_unpackLiterals": [_FP, C.c_uint64, _FP, C.c_uint32, C.c_uint32, _FP, _STREAM],
     "emf_hip_motionMasksScratchBytes": [C.c_int, C.c_int, C.c_int],
     "emf_hip_motionMasks": [_FP, _FP, C.c_int, C.c_int, C.c_void_p, _FP, _FP, _FP, _FP, _FP, _STREAM],
+    "emf_hip_rollVolumeIsTiled": [_I3, _I3],
+    "emf_hip_rollVolume": [_FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _I3, _I3, _STREAM],
 }
 
 

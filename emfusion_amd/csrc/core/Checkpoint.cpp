@@ -1,7 +1,7 @@
 // Checkpoint.cpp -- EMFusion::saveCheckpoint / loadCheckpoint / checkpointInfo (see EMFusion.hpp).
 //
 // The file (little-endian, every block a multiple of 8 bytes):
-//   header   char magic[8] "EMFCKPT\0"; u32 version (1); u32 headerBytes; the Params block (putParams below: 56 words);
+//   header   char magic[8] "EMFCKPT\0"; u32 version (1; 2 once the background has been rolled); u32 headerBytes; the Params block (putParams below: 56 words);
 //            u64 FNV-1a of every header byte before it
 //   sections {u32 tag; i32 id; u32 which; u32 0; u64 payloadBytes} + payload, zero-padded to 8 bytes:
 //     "SESS"  frame count, nextId, colour on/off, camera pose, allIds, the visible set, the colour map
@@ -12,6 +12,9 @@
 //     "PACK"  one packed record (include/emf_hip.h "Packed buffers") per volume buffer: id 0 = background, `which` an
 //             emf_fusion_volume selector -- tsdf, weights, [colour] of the background, then tsdf, weights, fg/bg counts,
 //             [colour] of every object in creation order; always the FRONT copy
+//     "ROLL"  version 2 only, exactly once, behind the last packed record: the background's cumulative origin, the
+//             follow switch and parameters, the background's current pose, the retired slabs.  A session that has never
+//             rolled writes version 1, byte for byte the file it always wrote
 //     "END!"  empty; the file ends behind it
 // Saved: the PRIMARY state.  Not saved because derived, rebuilt by the load the way ObjTSDF::resize and reset() do
 // (TSDF::volumesWritten, rebuildModelTable): fgProbs / fgVolMask, materialised gradients, sign maps, tile lists, dirty
@@ -25,6 +28,7 @@
 // through a second copy of itself: classify + rank on the device, the class array and the uniform words come over in
 // slab-sized pieces, the literals rank range by rank range (emf_hip_packGather).
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -37,7 +41,7 @@ namespace emf {
 namespace {
 
 constexpr char kMagic[8] = {'E', 'M', 'F', 'C', 'K', 'P', 'T', '\0'};
-constexpr uint32_t kVersion = 1;
+constexpr uint32_t kVersion = 1, kVersionRolled = 2;
 constexpr uint32_t kParamWords = 56;
 constexpr uint32_t kHeaderBytes = 16 + 4 * kParamWords + 8;
 constexpr uint64_t kChunk = 1024;
@@ -48,7 +52,8 @@ constexpr uint32_t fourcc(char a, char b, char c, char d) {
            static_cast<uint32_t>(static_cast<uint8_t>(c)) << 16 | static_cast<uint32_t>(static_cast<uint8_t>(d)) << 24;
 }
 constexpr uint32_t kSess = fourcc('S', 'E', 'S', 'S'), kObj = fourcc('O', 'B', 'J', ' '), kLogs = fourcc('L', 'O', 'G', 'S'),
-                   kMesh = fourcc('M', 'E', 'S', 'H'), kPack = fourcc('P', 'A', 'C', 'K'), kEnd = fourcc('E', 'N', 'D', '!');
+                   kMesh = fourcc('M', 'E', 'S', 'H'), kPack = fourcc('P', 'A', 'C', 'K'), kEnd = fourcc('E', 'N', 'D', '!'),
+                   kRoll = fourcc('R', 'O', 'L', 'L');
 constexpr uint32_t kVolFgBg = 6;  // EMF_VOL_FGBG
 
 struct SectionHeader {
@@ -239,7 +244,45 @@ struct FileIndex {
     std::map<int, Mesh> meshes;
     std::vector<RecordRef> records;
     uint64_t fileBytes = 0;
+    uint32_t version = kVersion;
+    // version 2: the "ROLL" section
+    Vec3i origin;
+    bool followOn = false;
+    BackgroundFollowParams follow;
+    Affine3f bgPose;
+    std::vector<RetiredSlab> retired;
 };
+
+void putMesh(Blob& b, const Mesh& m) {
+    b.put<uint64_t>(m.vertices());
+    b.put<uint64_t>(m.triangles());
+    b.put<uint32_t>(m.colored ? 1 : 0);
+    const bool colors = m.colors.size() == 3 * m.vertices() && m.vertices() > 0;
+    b.put<uint32_t>(colors ? 1 : 0);
+    b.putBytes(m.cloud.data(), m.cloud.size() * sizeof(float));
+    b.putBytes(m.normals.data(), m.normals.size() * sizeof(float));
+    b.putBytes(m.polygons.data(), m.polygons.size() * sizeof(int32_t));
+    if (colors) b.putBytes(m.colors.data(), m.colors.size());
+}
+
+Mesh getMesh(Cursor& c, uint64_t sectionBytes, const std::string& path) {
+    Mesh m;
+    const uint64_t nv = c.get<uint64_t>(), nt = c.get<uint64_t>();
+    m.colored = c.get<uint32_t>() != 0;
+    const bool colors = c.get<uint32_t>() != 0;
+    if (nv > sectionBytes / 24 || nt > sectionBytes / 16) refuse(path, "a mesh exceeds its section");
+    m.cloud.resize(3 * nv);
+    m.normals.resize(3 * nv);
+    m.polygons.resize(4 * nt);
+    c.getBytes(m.cloud.data(), m.cloud.size() * sizeof(float));
+    c.getBytes(m.normals.data(), m.normals.size() * sizeof(float));
+    c.getBytes(m.polygons.data(), m.polygons.size() * sizeof(int32_t));
+    if (colors) {
+        m.colors.resize(3 * nv);
+        c.getBytes(m.colors.data(), m.colors.size());
+    }
+    return m;
+}
 
 struct File {
     FILE* f = nullptr;
@@ -285,7 +328,10 @@ FileIndex scanFile(const std::string& path, bool headerOnly = false) {
     uint32_t version, headerBytes;
     std::memcpy(&version, head + 8, 4);
     std::memcpy(&headerBytes, head + 12, 4);
-    if (version != kVersion) refuse(path, "format version " + std::to_string(version) + ", this build reads " + std::to_string(kVersion));
+    if (version != kVersion && version != kVersionRolled)
+        refuse(path, "format version " + std::to_string(version) + ", this build reads " + std::to_string(kVersion) + " and " +
+                         std::to_string(kVersionRolled));
+    ix.version = version;
     uint64_t sum;
     std::memcpy(&sum, head + kHeaderBytes - 8, 8);
     if (headerBytes != kHeaderBytes || sum != fnv1a(head, kHeaderBytes - 8)) refuse(path, "header checksum");
@@ -303,7 +349,7 @@ FileIndex scanFile(const std::string& path, bool headerOnly = false) {
     // the records that must come, in order, once the object table is known
     std::vector<std::pair<int, uint32_t>> expect;
     size_t nextRecord = 0;
-    bool sawSess = false, sawLogs = false, sawEnd = false;
+    bool sawSess = false, sawLogs = false, sawEnd = false, sawRoll = false;
     size_t nobjects = 0;
     uint64_t at = kHeaderBytes;
     std::vector<uint8_t> buf;
@@ -395,24 +441,32 @@ FileIndex scanFile(const std::string& path, bool headerOnly = false) {
                 }
             }
         } else if (sh.tag == kMesh) {
-            Mesh m;
-            const uint64_t nv = c.get<uint64_t>(), nt = c.get<uint64_t>();
-            m.colored = c.get<uint32_t>() != 0;
-            const bool colors = c.get<uint32_t>() != 0;
-            if (nv > sh.bytes / 24 || nt > sh.bytes / 16) refuse(path, "a mesh exceeds its section");
-            m.cloud.resize(3 * nv);
-            m.normals.resize(3 * nv);
-            m.polygons.resize(4 * nt);
-            c.getBytes(m.cloud.data(), m.cloud.size() * sizeof(float));
-            c.getBytes(m.normals.data(), m.normals.size() * sizeof(float));
-            c.getBytes(m.polygons.data(), m.polygons.size() * sizeof(int32_t));
-            if (colors) {
-                m.colors.resize(3 * nv);
-                c.getBytes(m.colors.data(), m.colors.size());
+            ix.meshes[sh.id] = getMesh(c, sh.bytes, path);
+        } else if (sh.tag == kRoll) {
+            if (version != kVersionRolled || sawRoll || !sawSess || nextRecord != expect.size())
+                refuse(path, "a roll section out of place");
+            sawRoll = true;
+            c.getBytes(ix.origin.val, sizeof(ix.origin.val));
+            ix.followOn = c.get<int32_t>() != 0;
+            c.getBytes(ix.follow.step.val, sizeof(ix.follow.step.val));
+            ix.follow.lookAhead = c.get<float>();
+            ix.follow.keepRetired = c.get<int32_t>() != 0;
+            ix.bgPose = c.getPose();
+            const size_t ns = c.count(28 + 24);
+            for (size_t k = 0; k < ns; ++k) {
+                RetiredSlab r;
+                r.frame = c.get<int32_t>();
+                c.getBytes(r.origin.val, sizeof(r.origin.val));
+                c.getBytes(r.res.val, sizeof(r.res.val));
+                r.mesh = getMesh(c, sh.bytes, path);
+                ix.retired.push_back(std::move(r));
             }
-            ix.meshes[sh.id] = std::move(m);
+            const int tile[3] = {32, 8, 8};  // as EMFusion::setBackgroundFollow: positive multiples of the tile
+            for (int i = 0; i < 3; ++i)
+                if (ix.follow.step[i] <= 0 || ix.follow.step[i] % tile[i] != 0) refuse(path, "follow parameters out of range");
+            if (!std::isfinite(ix.follow.lookAhead)) refuse(path, "follow parameters out of range");
         } else if (sh.tag == kPack) {
-            if (ix.objects.size() != nobjects || !sawSess || nextRecord >= expect.size() ||
+            if (sawRoll || ix.objects.size() != nobjects || !sawSess || nextRecord >= expect.size() ||
                 expect[nextRecord] != std::make_pair(static_cast<int>(sh.id), sh.which))
                 refuse(path, "a packed record out of place");
             RecordRef r;
@@ -452,6 +506,7 @@ FileIndex scanFile(const std::string& path, bool headerOnly = false) {
     if (at != ix.fileBytes) refuse(path, "bytes behind the end marker");
     if (!sawSess || !sawLogs || ix.objects.size() != nobjects || nextRecord != expect.size())
         refuse(path, "truncated (sections are missing)");
+    if (version == kVersionRolled && !sawRoll) refuse(path, "format version 2 without its roll section");
     return ix;
 }
 
@@ -530,7 +585,7 @@ CheckpointStats EMFusion::saveCheckpoint(const std::string& path) {
         {
             Blob h;
             h.putBytes(kMagic, 8);
-            h.put<uint32_t>(kVersion);
+            h.put<uint32_t>(bgRolled ? kVersionRolled : kVersion);
             h.put<uint32_t>(kHeaderBytes);
             putParams(h, params, gradMode == TSDF::Gradients::Materialized);
             h.put<uint64_t>(fnv1a(h.b.data(), h.b.size()));
@@ -595,15 +650,7 @@ CheckpointStats EMFusion::saveCheckpoint(const std::string& path) {
         for (const auto& im : meshes) {
             const Mesh& m = im.second;
             Blob b;
-            b.put<uint64_t>(m.vertices());
-            b.put<uint64_t>(m.triangles());
-            b.put<uint32_t>(m.colored ? 1 : 0);
-            const bool colors = m.colors.size() == 3 * m.vertices() && m.vertices() > 0;
-            b.put<uint32_t>(colors ? 1 : 0);
-            b.putBytes(m.cloud.data(), m.cloud.size() * sizeof(float));
-            b.putBytes(m.normals.data(), m.normals.size() * sizeof(float));
-            b.putBytes(m.polygons.data(), m.polygons.size() * sizeof(int32_t));
-            if (colors) b.putBytes(m.colors.data(), m.colors.size());
+            putMesh(b, m);
             w.section(kMesh, im.first, b);
         }
 
@@ -681,6 +728,24 @@ CheckpointStats EMFusion::saveCheckpoint(const std::string& path) {
             packVolume(o.getID(), o);
             pack(o.getID(), kVolFgBg, o.fgBgPtr(), o.voxels() * 2 * sizeof(float));
             packColor(o.getID(), o);
+        }
+        if (bgRolled) {  // version 2's trailing section
+            Blob b;
+            b.putBytes(bgOrigin.val, sizeof(bgOrigin.val));
+            b.put<int32_t>(followOn ? 1 : 0);
+            b.putBytes(followParams.step.val, sizeof(followParams.step.val));
+            b.put<float>(followParams.lookAhead);
+            b.put<int32_t>(followParams.keepRetired ? 1 : 0);
+            b.putPose(background.getPose());
+            b.put<int32_t>(static_cast<int32_t>(retired.size()));
+            for (const RetiredSlab& r : retired) {
+                b.put<int32_t>(r.frame);
+                b.putBytes(r.origin.val, sizeof(r.origin.val));
+                b.putBytes(r.res.val, sizeof(r.res.val));
+                putMesh(b, r.mesh);
+            }
+            b.pad();
+            w.section(kRoll, 0, b);
         }
         w.section(kEnd, 0, 0, 0);
         const auto t0 = std::chrono::steady_clock::now();
@@ -797,6 +862,14 @@ void EMFusion::loadCheckpoint(const std::string& path) {
         obj_poses = ix.objPoses;
         obj_pose_offsets = ix.objOffsets;
         meshes = ix.meshes;
+        if (ix.version == kVersionRolled) {  // the background where the rolls had taken it
+            background.setPose(ix.bgPose);
+            bgOrigin = ix.origin;
+            bgRolled = true;
+            followOn = ix.followOn;
+            followParams = ix.follow;
+            retired = ix.retired;
+        }
         forkFrame = -2;
         farBoundsReady = false;
         rebuildModelTable();  // sign maps, tile lists, the visibility gate, the table
@@ -830,8 +903,10 @@ std::string EMFusion::checkpointInfo(const std::string& path) {
         for (int k = 0; k < n; ++k) add(k ? ", %.9g" : "%.9g", static_cast<double>(v[k]));
         s += "]";
     };
-    add("{\"version\": %u, \"file_bytes\": %llu, \"frame_index\": %d, \"next_id\": %d, \"color\": %s, ", kVersion,
+    add("{\"version\": %u, \"file_bytes\": %llu, \"frame_index\": %d, \"next_id\": %d, \"color\": %s, ", ix.version,
         static_cast<unsigned long long>(ix.fileBytes), ix.frameCount, ix.nextId, ix.colorOn ? "true" : "false");
+    add("\"background_origin\": [%d, %d, %d], \"retired_slabs\": %d, ", ix.origin[0], ix.origin[1], ix.origin[2],
+        static_cast<int>(ix.retired.size()));
     add("\"params\": {\"width\": %d, \"height\": %d, \"K\": ", p.frameSize.width, p.frameSize.height);
     floats(p.intr.val, 9);
     add(", \"bg_res\": [%d, %d, %d], \"bg_voxel_size\": %.9g, \"bg_rel_truncdist\": %.9g, \"volume_pose_t\": ",

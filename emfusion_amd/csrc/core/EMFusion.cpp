@@ -131,6 +131,9 @@ void EMFusion::reset() {
     motionInfo.clear();
     motionFired = false;
     motionVisStale = false;
+    bgOrigin = Vec3i();
+    bgRolled = false;
+    retired.clear();
     trackPredicted[0] = trackPredicted[1] = 0;
     Stream& s = Stream::Null();
     bg_associationWeights.setTo(1.f, s);
@@ -630,6 +633,7 @@ void EMFusion::runSchedule(const emf_image_t& depthDev, const FrameInputs& in) {
         timings.masks = ms(kIntegrate, kMasks);
         timings.total = ms(kStart, kMasks);
     }
+    if (followOn) followCamera();  // after the integration and its join, outside the timings
     if (expFrameMeshes_) storeFrameMeshes();  // EMFusion.cpp:110-125, after cleanUpObjs and outside the timings
     ++frameCount;
 }

@@ -98,6 +98,21 @@ struct MotionMaskParams {
     int maxMasks = 8;         // 1 .. EMF_MOTION_MAX_MASKS
 };
 
+/** EMFusion::setBackgroundFollow. */
+struct BackgroundFollowParams {
+    Vec3i step = Vec3i(64, 64, 64);  // voxels per axis a roll moves by: positive multiples of the tile (32, 8, 8)
+    float lookAhead = 0.f;           // m along the optical axis: the followed point lies this far in front of the camera
+    bool keepRetired = true;         // mesh what slides out of the cube before it is dropped
+};
+
+/** The marching cubes of one sub-box of the background that a roll removed, meshed before the roll. */
+struct RetiredSlab {
+    int frame = 0;   // the frame at whose end the roll happened (an explicit roll: the last one processed, frameIndex() - 1)
+    Vec3i origin;    // lattice index of the sub-box's voxel (0, 0, 0): backgroundOrigin() then + its offset in the volume
+    Vec3i res;       // voxels of the sub-box
+    Mesh mesh;       // in the sub-box's own frame (its centre at 0), as TSDF::getMesh() of a volume of that size
+};
+
 /** Per-stage GPU time of the last processed frame (milliseconds, from HIP events). */
 struct FrameTimings {
     float points = 0, estep = 0, raycast = 0, composite = 0, integrate = 0, masks = 0, total = 0;
@@ -276,6 +291,34 @@ public:
     /** The proposals of the last processed frame (none if it did not propose) and, if wanted, the W x H rank image
      *  (-1: no proposal); waits for the device when it has labels to fetch. */
     const std::vector<emf_motion_info_t>& lastMotionMasks(std::vector<int32_t>* labels = nullptr);
+    /**
+     * Follow the camera (new behaviour, off by default, may be switched at any time; with it off no
+     * launch and no output byte changes).  At the end of a frame -- after the integration and its join, before the
+     * per-frame meshes -- the followed point q = bgPose^-1 (camT + camR (0, 0, lookAhead)) is put through followShift;
+     * a non-zero result retires the leaving slabs (keepRetired), rolls the background by it (TSDF::roll), rebuilds the
+     * model table and adds it to backgroundOrigin().  All rolls are whole voxels along the background's own axes, so
+     * the background at any time and every retired slab sit on one integer voxel lattice whose index (0, 0, 0) is
+     * voxel (0, 0, 0) of the background at its initial pose.  Objects are untouched: their poses are in the world
+     * frame.  A step that is not a positive multiple of (32, 8, 8) is refused (EMF_E_ARG); so is the sharded path.
+     * A checkpoint carries the switch and its parameters only once the background has rolled (version 2; a
+     * never-rolled session writes version 1 byte for byte): a session saved before its first roll resumes with
+     * follow off, and the caller sets it again, as with the motion masks.
+     */
+    void setBackgroundFollow(bool on, const BackgroundFollowParams& p = BackgroundFollowParams());
+    bool backgroundFollowEnabled() const { return followOn; }
+    /**
+     * The policy, a pure function of floats that touches no device: per axis shift_i =
+     * trunc(q_i / (float(step_i) * voxelSize)) * step_i, every operation in single precision.  False (nothing
+     * written) for a step that is not a positive multiple of (32, 8, 8), a voxel size that is not positive and finite,
+     * a q that is not finite or a quotient outside +-2^20 steps.
+     */
+    static bool followShift(const float q[3], const int32_t step[3], float voxelSize, int32_t shift[3]);
+    /** Roll the background now by `shift` voxels (any integers): retire, roll, rebuild the table.  keepRetired < 0:
+     *  as the session's follow parameters say (true by default, also with follow off); 0: only re-centre, nothing is
+     *  meshed or kept; > 0: retire. */
+    void rollBackground(const Vec3i& shift, int keepRetired = -1);
+    Vec3i backgroundOrigin() const { return bgOrigin; }
+    const std::vector<RetiredSlab>& retiredSlabs() const { return retired; }
     /** Ids returned by initNewObjVolume for FrameInputs::newObjectMasks of the last frame (-1: none). */
     const std::vector<int>& lastCreatedObjects() const { return lastCreated; }
     Affine3f getCameraPose() const { return pose; }
@@ -555,6 +598,15 @@ private:
     bool motionVisStale = false;                // lastMaskVis is to be drawn from motionLabels when somebody asks
     void ensureMotionBuffers();
     void proposeMotionMasks(std::vector<emf_image_t>& segs);
+    // ---- follow the camera (setBackgroundFollow; EMFusionFollow.cpp) ----
+    bool followOn = false;
+    BackgroundFollowParams followParams;
+    Vec3i bgOrigin;                     // cumulative roll, in voxels on the lattice of the initial pose
+    bool bgRolled = false;              // the background has been rolled since construction / reset()
+    std::vector<RetiredSlab> retired;
+    void followCamera();                // the end of a frame with follow on
+    void rollBackgroundAt(const Vec3i& shift, int frame, bool keepRetired);
+    void retireSlabs(const Vec3i& shift, int frame);
     DeviceImage<float> depthFiltered;  // output of preprocessDepth
     DeviceImage<float> invLambda;  // per-pixel 1 / lambda of the integration, fixed by the intrinsics (sw.useLambdaTable)
     DeviceBuffer integrateCullScratch;  // survivor list of emf_hip_integrateBatchedCulled (empty: plain launch)

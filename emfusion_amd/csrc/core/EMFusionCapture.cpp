@@ -51,6 +51,28 @@ void EMFusion::writeResults(const std::string& dir, bool volumes) {
         writeAll(dir + "/frame_meshes/bg", frame_meshes);
         for (const auto& o : frame_obj_meshes) writeAll(dir + "/frame_meshes/" + std::to_string(o.first), o.second);
     }
+    if (!retired.empty()) {  // what the rolls removed (setBackgroundFollow / rollBackground), in the frame of the INITIAL pose
+        const std::string d = dir + "/bg_retired";
+        io::createDirectories(d);
+        const Vec3i n = background.getVolumeRes();
+        const double vox = static_cast<double>(background.getVoxelSize());
+        std::FILE* f = std::fopen((d + "/origins.txt").c_str(), "w");
+        if (!f) throw std::runtime_error("EMFusion::writeResults: cannot create " + d + "/origins.txt");
+        char name[32];
+        for (size_t k = 0; k < retired.size(); ++k) {
+            const RetiredSlab& r = retired[k];
+            Mesh m = r.mesh;
+            for (int i = 0; i < 3; ++i) {  // the sub-box's centre on the lattice, from the initial volume's centre
+                const double off = (static_cast<double>(r.origin[i]) + (r.res[i] - 1) / 2.0 - (n[i] - 1) / 2.0) * vox;
+                for (size_t v = 0; v < m.vertices(); ++v)
+                    m.cloud[3 * v + i] = static_cast<float>(static_cast<double>(m.cloud[3 * v + i]) + off);
+            }
+            std::snprintf(name, sizeof(name), "/%04d.ply", static_cast<int>(k));
+            io::writeMesh(d + name, m);
+            std::fprintf(f, "%d %d %d %d %d %d %d\n", r.frame, r.origin[0], r.origin[1], r.origin[2], r.res[0], r.res[1], r.res[2]);
+        }
+        std::fclose(f);
+    }
     // writeRenderings / writeAssocs / writeHuberWeights / writeTrackWeights / writeFgProbs (EMFusion.cpp:1009-1145):
     // directories are created whether or not the log holds anything, like the reference's
     io::writeImageLog(dir + "/output", renderings);

@@ -235,6 +235,75 @@ void TSDF::volumesWritten(Stream& stream) {
     resyncBack();
 }
 
+void TSDF::roll(const Vec3i& shift, Stream& stream) {
+    const bool twice = doubleBuffered();
+    DeviceBuffer newVol, newWeights, newColor, newSign, newUnseen;
+    if (!twice) {
+        newVol = DeviceBuffer(voxels() * sizeof(float));
+        newWeights = DeviceBuffer(voxels() * sizeof(float));
+    }
+    if (!colorVol.empty()) newColor = DeviceBuffer(voxels() * 4 * sizeof(uint16_t));
+    // maps that describe the values travel with them on the tile-granular path; stale ones stay stale
+    const bool moveMaps = emf_hip_rollVolumeIsTiled(volumeRes.val, shift.val) && signMapsValid && !signMaps.empty() &&
+                          !unseenTiles.empty();
+    if (moveMaps) {
+        newSign = DeviceBuffer(signMaps.bytes());
+        newUnseen = DeviceBuffer(unseenTiles.bytes());
+    }
+    emfCheck(emf_hip_rollVolume(tsdfVol.as<float>(), tsdfWeights.as<float>(), colorVol.empty() ? nullptr : colorVol.as<uint16_t>(),
+                                moveMaps ? signMaps.as<uint8_t>() : nullptr, moveMaps ? unseenTiles.as<uint8_t>() : nullptr,
+                                twice ? tsdfBack.as<float>() : newVol.as<float>(),
+                                twice ? weightsBack.as<float>() : newWeights.as<float>(),
+                                newColor.empty() ? nullptr : newColor.as<uint16_t>(),
+                                moveMaps ? newSign.as<uint8_t>() : nullptr, moveMaps ? newUnseen.as<uint8_t>() : nullptr,
+                                volumeRes.val, shift.val, stream.abi()),
+             "TSDF::roll");
+    stream.waitForCompletion();  // the old buffers are released below
+    if (twice) {
+        flip();
+    } else {
+        tsdfVol = std::move(newVol);
+        tsdfWeights = std::move(newWeights);
+    }
+    if (!newColor.empty()) colorVol = std::move(newColor);
+    if (moveMaps) {
+        signMaps = std::move(newSign);
+        unseenTiles = std::move(newUnseen);
+    }
+    Vec3f offset;  // as ObjTSDF::resize forms its newCenter
+    for (int i = 0; i < 3; ++i) offset[i] = static_cast<float>(shift[i]) * voxelSize;
+    pose = pose.translate(pose.rotation() * offset);
+    brickFlags.setZero(stream);  // every brick "mixed": always correct; integrate() refines them
+    signMapsValid = moveMaps;
+    if (!relevantTiles.empty()) relevantTiles.setZero(stream);  // the owner rebuilds the list before it is used
+    updateGradients(stream);
+    stream.waitForCompletion();
+    resyncBack();
+}
+
+TSDF TSDF::cutBox(const Vec3i& lo, const Vec3i& res, Stream& stream) const {
+    Vec3f centre;  // of the box, in this volume's frame: voxel index i sits at (i - (N - 1) / 2) * voxelSize
+    for (int i = 0; i < 3; ++i)
+        centre[i] = (static_cast<float>(lo[i]) + static_cast<float>(res[i] - 1) / 2.f - static_cast<float>(volumeRes[i] - 1) / 2.f) *
+                    voxelSize;
+    TSDF box(res, voxelSize, truncdist, pose.translate(pose.rotation() * centre), params, frameSize, gradMode);
+    emfCheck(emf_hip_copyValues(tsdfVol.as<float>(), box.tsdfVol.as<float>(), 1, lo.val, volumeRes.val, res.val, stream.abi()),
+             "TSDF::cutBox");
+    emfCheck(emf_hip_copyValues(tsdfWeights.as<float>(), box.tsdfWeights.as<float>(), 1, lo.val, volumeRes.val, res.val,
+                                stream.abi()),
+             "TSDF::cutBox");
+    if (!colorVol.empty()) {
+        box.enableColor();
+        emfCheck(emf_hip_copyColorValues(colorVol.as<uint16_t>(), box.colorVol.as<uint16_t>(), lo.val, volumeRes.val, res.val,
+                                         stream.abi()),
+                 "TSDF::cutBox (colour)");
+    }
+    box.signMapsValid = false;
+    box.updateGradients(stream);
+    stream.waitForCompletion();
+    return box;
+}
+
 void TSDF::flip() {
     std::swap(tsdfVol, tsdfBack);
     std::swap(tsdfWeights, weightsBack);

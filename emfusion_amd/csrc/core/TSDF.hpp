@@ -148,6 +148,24 @@ public:
      * materialised gradients recomputed, the back copy made equal.  Waits for `stream`.
      */
     virtual void volumesWritten(Stream& stream);
+    /**
+     * Shift the contents by whole voxels (include/emf_hip.h "Rolling a volume"): afterwards voxel v holds what voxel
+     * v + shift held, zeros where that lay outside, and the pose is translated by the same amount exactly as
+     * ObjTSDF::resize moves an object's: pose.translate(pose.rotation() * (float(shift_i) * voxelSize)).  One launch,
+     * front copy -> back copy and flip() (a volume kept once, and the colour volume, roll into a fresh buffer that
+     * takes the old one's place); then the other copy is made equal (resyncBack).  Derived state ends as
+     * volumesWritten() leaves it -- brick flags "mixed", relevant-tile list emptied for the owner's
+     * rebuildModelTable(), materialised gradients recomputed -- except that valid sign / unseen maps stay valid on
+     * the tile-granular path: the launch moves their entries.  Waits for `stream`; the owner has joined every other
+     * stream that touches this volume.
+     */
+    void roll(const Vec3i& shift, Stream& stream);
+    /**
+     * A volume of its own holding the voxels [lo, lo + res) of this one's front copy (and colour), cut with
+     * emf_hip_copyValues / emf_hip_copyColorValues; the parts of the box outside this volume read as zeros.  Its
+     * pose is this volume's, translated to the box's centre.  Waits for `stream`.
+     */
+    TSDF cutBox(const Vec3i& lo, const Vec3i& res, Stream& stream) const;
     void refreshSignMaps(Stream& stream = Stream::Null());
 
     /**

@@ -445,6 +445,80 @@ int emf_fusion_last_motion_masks(emf_fusion_t* h, int32_t* labels_out, emf_motio
     });
 }
 
+int emf_fusion_set_background_follow(emf_fusion_t* h, int on, const emf_follow_params_t* params) {
+    REQ(h);
+    return guarded([&] {
+        BackgroundFollowParams p;
+        if (params) {
+            p.step = Vec3i(params->step[0], params->step[1], params->step[2]);
+            p.lookAhead = params->look_ahead;
+            p.keepRetired = params->keep_retired != 0;
+        }
+        h->impl->setBackgroundFollow(on != 0, p);
+    });
+}
+
+int emf_fusion_roll_background(emf_fusion_t* h, const int32_t shift[3], int keep_retired) {
+    REQ(h);
+    REQ(shift);
+    return guarded([&] { h->impl->rollBackground(Vec3i(shift[0], shift[1], shift[2]), keep_retired); });
+}
+
+int emf_fusion_background_origin(emf_fusion_t* h, int32_t origin[3], float R[9], float t[3]) {
+    REQ(h);
+    REQ(origin);
+    return guarded([&] {
+        const Vec3i o = h->impl->backgroundOrigin();
+        std::memcpy(origin, o.val, sizeof(o.val));
+        const Affine3f pose = h->impl->getBackground().getPose();
+        if (R) std::memcpy(R, pose.rotation().val, 9 * sizeof(float));
+        if (t) std::memcpy(t, pose.translation().val, 3 * sizeof(float));
+    });
+}
+
+int emf_fusion_retired_slabs(emf_fusion_t* h, int32_t* info, int capacity, int32_t* count) {
+    REQ(h);
+    REQ(count);
+    return guarded([&] {
+        const std::vector<RetiredSlab>& slabs = h->impl->retiredSlabs();
+        *count = static_cast<int32_t>(slabs.size());
+        for (int k = 0; info && k < capacity && k < static_cast<int>(slabs.size()); ++k) {
+            int32_t* row = info + 7 * k;
+            row[0] = slabs[k].frame;
+            for (int i = 0; i < 3; ++i) {
+                row[1 + i] = slabs[k].origin[i];
+                row[4 + i] = slabs[k].res[i];
+            }
+        }
+    });
+}
+
+int emf_fusion_retired_slab_mesh(emf_fusion_t* h, int index, uint32_t* num_vertices, uint32_t* num_triangles) {
+    REQ(h);
+    REQ(num_vertices);
+    REQ(num_triangles);
+    return guarded([&] {
+        const std::vector<RetiredSlab>& slabs = h->impl->retiredSlabs();
+        if (index < 0 || index >= static_cast<int>(slabs.size()))
+            throw HipError("emf_fusion_retired_slab_mesh: no slab " + std::to_string(index), EMF_E_ARG);
+        h->mesh = slabs[index].mesh;
+        *num_vertices = static_cast<uint32_t>(h->mesh.vertices());
+        *num_triangles = static_cast<uint32_t>(h->mesh.triangles());
+    });
+}
+
+int emf_fusion_follow_shift(const float q[3], const int32_t step[3], float voxel_size, int32_t shift[3]) {
+    REQ(q);
+    REQ(step);
+    REQ(shift);
+    return guarded([&] {
+        if (!EMFusion::followShift(q, step, voxel_size, shift))
+            throw HipError("emf_fusion_follow_shift: the step must be a positive multiple of the tile (32, 8, 8), the voxel "
+                           "size positive and q finite",
+                           EMF_E_ARG);
+    });
+}
+
 int emf_io_read_color_png(const char* path, uint8_t* out, size_t capacity, int32_t* width, int32_t* height) {
     REQ(path);
     return guarded([&] {

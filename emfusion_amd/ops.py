@@ -392,6 +392,32 @@ def rebuild_unseen_tiles(tsdf, weights, unseen_tiles, stream=None):
                                         _stream(stream)))
 
 
+def roll_volume(tsdf, weights, shift, color=None, sign_maps=None, unseen_tiles=None, out=None, stream=None):
+    """emf_hip_rollVolume: dst(v) = src(v + shift) inside the volume, 0 elsewhere, bit for bit, for (Nz, Ny, Nx) f32
+    tsdf / weights and an optional (Nz, Ny, Nx, 4) u16 colour volume; shift = (x, y, z) voxels.  On the tile-granular
+    path (resolution and shift multiples of 32 x 8 x 8) sign_maps / unseen_tiles -- the SOURCE's maps, both or
+    neither -- are moved along.  out: (tsdf, weights[, color]) destination arrays, allocated when None.
+    Returns (tsdf, weights, color or None, sign_maps or None, unseen_tiles or None): the maps are None where the
+    launch did not write them (the caller rebuilds them)."""
+    nz, ny, nx = tsdf.shape
+    res = (C.c_int32 * 3)(nx, ny, nz)
+    sh = (C.c_int32 * 3)(*[int(v) for v in shift])
+    if out is None:
+        out = (DeviceArray(tsdf.shape, np.float32), DeviceArray(weights.shape, np.float32)) + \
+              (() if color is None else (DeviceArray(color.shape, np.uint16),))
+    d_color = out[2] if color is not None else None
+    tiled = bool(_L.emf_hip_rollVolumeIsTiled(res, sh))
+    d_sign = d_unseen = None
+    if tiled and sign_maps is not None and unseen_tiles is not None:
+        d_sign = DeviceArray((sign_map_bytes((nx, ny, nz)),), np.uint8)
+        d_unseen = DeviceArray((unseen_tile_bytes((nx, ny, nz)),), np.uint8)
+    check("emf_hip_rollVolume",
+          _L.emf_hip_rollVolume(_ptr(tsdf), _ptr(weights), _ptr(color), _ptr(sign_maps) if d_sign is not None else None,
+                                _ptr(unseen_tiles) if d_sign is not None else None, _ptr(out[0]), _ptr(out[1]),
+                                _ptr(d_color), _ptr(d_sign), _ptr(d_unseen), res, sh, _stream(stream)))
+    return out[0], out[1], d_color, d_sign, d_unseen
+
+
 def raycast_far_bounds(models_dev, poses_co, res_list, width, height, K, bounds=None, stream=None, scan_mask=0xffffffff):
     """emf_hip_raycastFarBounds -> float32 (nmodels, cellsY, cellsX) device array."""
     n = len(poses_co)

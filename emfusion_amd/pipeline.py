@@ -117,6 +117,12 @@ def load() -> C.CDLL:
         "emf_fusion_copy_mesh_components": [vp, C.c_void_p, C.c_void_p],
         "emf_fusion_last_mesh_filter": [vp, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32)],
         "emf_fusion_set_color_image": [vp, img],
+        "emf_fusion_set_background_follow": [vp, C.c_int, C.c_void_p],
+        "emf_fusion_roll_background": [vp, ip, C.c_int],
+        "emf_fusion_background_origin": [vp, ip, fp, fp],
+        "emf_fusion_retired_slabs": [vp, C.c_void_p, C.c_int, ip],
+        "emf_fusion_retired_slab_mesh": [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+        "emf_fusion_follow_shift": [fp, ip, C.c_float, ip],
         "emf_fusion_process_rgbd_color": [vp, fp, C.c_void_p, C.c_int32, C.c_int32],
         "emf_fusion_colored_voxels": [vp, C.POINTER(C.c_uint64)],
         "emf_fusion_get_last_masks": [vp, C.c_void_p, C.c_size_t, ip],
@@ -628,6 +634,64 @@ class Fusion:
                             int(erode), int(min_pixels), int(max_masks))
         _check("emf_fusion_set_motion_masks", load().emf_fusion_set_motion_masks(self._h, int(bool(on)), C.addressof(p)))
 
+    def set_background_follow(self, on=True, step=(64, 64, 64), look_ahead=0.0, keep_retired=True):
+        """Follow the camera: at the end of every frame the background is rolled by whole voxels (multiples of `step`,
+        each a positive multiple of the tile (32, 8, 8)) so that the point `look_ahead` metres in front of the camera
+        stays within one step of its centre; with `keep_retired` what slides out is meshed first (retired_slabs()).
+        Off by default; refused on the sharded path.  save_checkpoint() carries the switch and its parameters only once
+        the background has rolled (a never-rolled session's file is the version 1 file byte for byte): a session saved
+        before its first roll resumes with follow off, and the caller sets it again, as with the motion masks."""
+        p = EmfFollowParams((C.c_int32 * 3)(*[int(v) for v in step]), float(look_ahead), int(bool(keep_retired)))
+        _check("emf_fusion_set_background_follow",
+               load().emf_fusion_set_background_follow(self._h, int(bool(on)), C.addressof(p)))
+
+    def roll_background(self, shift, keep_retired=None):
+        """Roll the background now by `shift` = (x, y, z) voxels: afterwards voxel v holds what v + shift held, zeros
+        where that lay outside, and the background's pose is translated by R (shift * voxel_size).  keep_retired None:
+        what leaves is meshed and kept (retired_slabs()) if the session's keep_retired says so, which it does by
+        default, also with follow off; False: only re-centre, nothing is meshed or kept; True: retire."""
+        keep = -1 if keep_retired is None else int(bool(keep_retired))
+        _check("emf_fusion_roll_background",
+               load().emf_fusion_roll_background(self._h, (C.c_int32 * 3)(*[int(v) for v in shift]), keep))
+
+    def background_origin(self):
+        """The cumulative roll in voxels, on the lattice whose index (0, 0, 0) is voxel (0, 0, 0) at the initial pose."""
+        o = (C.c_int32 * 3)()
+        _check("emf_fusion_background_origin", load().emf_fusion_background_origin(self._h, o, None, None))
+        return tuple(int(v) for v in o)
+
+    def background_pose(self):
+        """(R 3x3, t 3): the background's current pose, volume centre -> world."""
+        o, R, t = (C.c_int32 * 3)(), (C.c_float * 9)(), (C.c_float * 3)()
+        _check("emf_fusion_background_origin", load().emf_fusion_background_origin(self._h, o, R, t))
+        return np.array(R, np.float32).reshape(3, 3), np.array(t, np.float32)
+
+    def retired_slabs(self, colors=False):
+        """What the rolls removed, in order: dicts {frame, origin (x, y, z), res (x, y, z), vertices (n, 3), normals
+        (n, 3), triangles (m, 4)[, colors (n, 3) u8]}; vertices in the slab's own frame (its centre at 0).  frame: the one at whose
+        end the roll happened, which for roll_background() is the last one processed."""
+        n = C.c_int32(0)
+        _check("emf_fusion_retired_slabs", load().emf_fusion_retired_slabs(self._h, None, 0, C.byref(n)))
+        info = np.zeros((max(n.value, 1), 7), np.int32)
+        _check("emf_fusion_retired_slabs", load().emf_fusion_retired_slabs(self._h, info.ctypes.data, n.value, C.byref(n)))
+        out = []
+        for k in range(n.value):
+            nv, nt = C.c_uint32(), C.c_uint32()
+            _check("emf_fusion_retired_slab_mesh",
+                   load().emf_fusion_retired_slab_mesh(self._h, k, C.byref(nv), C.byref(nt)))
+            v, nr = np.empty((nv.value, 3), np.float32), np.empty((nv.value, 3), np.float32)
+            t = np.empty((nt.value, 4), np.int32)
+            _check("emf_fusion_copy_mesh", load().emf_fusion_copy_mesh(self._h, v.ctypes.data, nr.ctypes.data, t.ctypes.data))
+            slab = dict(frame=int(info[k, 0]), origin=tuple(int(x) for x in info[k, 1:4]),
+                        res=tuple(int(x) for x in info[k, 4:7]), vertices=v, normals=nr, triangles=t)
+            if colors:
+                c = np.empty((nv.value, 3), np.uint8)
+                if nv.value:
+                    _check("emf_fusion_copy_mesh_colors", load().emf_fusion_copy_mesh_colors(self._h, c.ctypes.data))
+                slab["colors"] = c
+            out.append(slab)
+        return out
+
     def last_motion_masks(self):
         """The proposals of the last processed frame: ((H, W) i32 image of proposal ranks, -1 where none is, list of
         dicts {label, area, x0, y0, x1, y1} by rank).  Empty / all -1 if the frame proposed nothing."""
@@ -952,7 +1016,8 @@ class Fusion:
     def save_checkpoint(self, path) -> dict:
         """emf_fusion_save_checkpoint: the session's primary state, volumes packed losslessly on the device, written to
         `path` (through path + ".tmp").  Returns raw_bytes / file_bytes, chunks per class and the milliseconds of the
-        stages (classify, gather: device; copy, file, total: host)."""
+        stages (classify, gather: device; copy, file, total: host).  The background-follow switch and its parameters
+        are in the file only once the background has rolled (see set_background_follow)."""
         st = CheckpointStats()
         _check("emf_fusion_save_checkpoint", load().emf_fusion_save_checkpoint(self._h, os.fspath(path).encode(), C.byref(st)))
         return dict(raw_bytes=int(st.raw_bytes), file_bytes=int(st.file_bytes), records=int(st.records),
@@ -1100,6 +1165,22 @@ def trim_pool() -> int:
     n = C.c_uint64(0)
     _check("emf_fusion_trim_pool", load().emf_fusion_trim_pool(C.byref(n)))
     return int(n.value)
+
+
+class EmfFollowParams(C.Structure):
+    """Mirror of emf_follow_params_t (include/emf_fusion.h)."""
+
+    _fields_ = [("step", C.c_int32 * 3), ("look_ahead", C.c_float), ("keep_retired", C.c_int32)]
+
+
+def follow_shift(q, step=(64, 64, 64), voxel=0.01):
+    """The follow policy (emf_fusion_follow_shift; no device): per axis trunc(q_i / (step_i * voxel)) * step_i for the
+    followed point q in the background's frame, in single precision.  FusionError (EMF_E_ARG) for a step component that
+    is not a positive multiple of the tile (32, 8, 8)."""
+    out = (C.c_int32 * 3)()
+    _check("emf_fusion_follow_shift",
+           load().emf_fusion_follow_shift(_farr(q, 3), (C.c_int32 * 3)(*[int(v) for v in step]), float(voxel), out))
+    return tuple(int(v) for v in out)
 
 
 def checkpoint_info(path) -> dict:

@@ -164,6 +164,45 @@ int emf_fusion_get_last_masks(emf_fusion_t* h, uint8_t* rgb, size_t capacity, in
 int emf_fusion_set_motion_masks(emf_fusion_t* h, int on, const emf_motion_params_t* params);
 int emf_fusion_last_motion_masks(emf_fusion_t* h, int32_t* labels_out, emf_motion_info_t* info_out, int capacity,
                                  int32_t* count);
+/* Follow the camera (new behaviour, off by default, may be switched at any time, and with it off no
+ * launch and no output byte of a frame changes).  The background is rolled by whole voxels along its own axes
+ * (include/emf_hip.h "Rolling a volume") so that the followed point q = bgPose^-1 (camT + camR (0, 0, look_ahead))
+ * stays within one step of its centre; what slides out is meshed first (keep_retired) and kept on the host.  The
+ * background at any time and every retired slab sit on one integer voxel lattice, index (0, 0, 0) = voxel (0, 0, 0) of
+ * the background at its initial pose.  Object poses are in the world frame and are untouched.
+ *   set_background_follow  params NULL: the defaults, step (64, 64, 64), look_ahead 0, keep_retired 1.  EMF_E_ARG for
+ *                      a step component that is not a positive multiple of the tile (32, 8, 8), and ("... not
+ *                      supported on the sharded path", the session stays usable) on the sharded path.  The policy
+ *                      runs at the end of every frame: after the integration, before the per-frame meshes.
+ *                      A checkpoint carries the switch and its parameters only once the background has rolled
+ *                      (version 2; a never-rolled session writes version 1 byte for byte): a session saved before its
+ *                      first roll resumes with follow off and the caller sets it again, as with the motion masks.
+ *   roll_background    rolls now by `shift` voxels (any integers; multiples of the tile take the fast path).
+ *                      keep_retired < 0: retire first if the session's keep_retired is set (it is by default, also
+ *                      with follow off); 0: only re-centre, nothing is meshed or kept; > 0: retire first.
+ *   background_origin  the cumulative shift; R, t (either may be NULL): the background's current pose, volume centre
+ *                      -> world.  After a roll by k: t' = t + R (float(k_i) * voxel_size), as an object's resize.
+ *   retired_slabs      *count slabs so far; up to `capacity` records of 7 int32 to info (may be NULL): frame, origin
+ *                      x y z (lattice index of the slab's voxel (0, 0, 0)), resolution x y z.  frame: the one at whose
+ *                      end the roll happened; for roll_background the last one processed.
+ *   retired_slab_mesh  makes slab `index`'s mesh the one emf_fusion_copy_mesh / emf_fusion_copy_mesh_colors copy.  Its
+ *                      vertices are in the slab's own frame (its centre at 0), exactly what meshing a volume of that
+ *                      size holding those voxels gives; emf_fusion_write_results writes them as bg_retired/%04d.ply
+ *                      translated into the frame of the background's INITIAL pose, with bg_retired/origins.txt
+ *                      (one line per slab: the 7 numbers above), and creates bg_retired/ only if there is a slab.
+ *   follow_shift       the policy alone, no device and no handle: shift_i = trunc(q_i / (float(step_i) * voxel_size))
+ *                      * step_i in single precision.  EMF_E_ARG for a refused step, voxel size or q. */
+typedef struct emf_follow_params {
+    int32_t step[3];
+    float look_ahead;
+    int32_t keep_retired;
+} emf_follow_params_t;
+int emf_fusion_set_background_follow(emf_fusion_t* h, int on, const emf_follow_params_t* params);
+int emf_fusion_roll_background(emf_fusion_t* h, const int32_t shift[3], int keep_retired);
+int emf_fusion_background_origin(emf_fusion_t* h, int32_t origin[3], float R[9], float t[3]);
+int emf_fusion_retired_slabs(emf_fusion_t* h, int32_t* info, int capacity, int32_t* count);
+int emf_fusion_retired_slab_mesh(emf_fusion_t* h, int index, uint32_t* num_vertices, uint32_t* num_triangles);
+int emf_fusion_follow_shift(const float q[3], const int32_t step[3], float voxel_size, int32_t shift[3]);
 
 /* Create an object volume (edge vol_size metres, obj_res voxels) centred at `center` in world
  * coordinates; every rank issues the same calls.  *id_out = object id (1-based). */

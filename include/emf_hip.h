@@ -1293,6 +1293,37 @@ int emf_hip_motionMasks(const float* points, const float* bg_raylengths, int w, 
                         void* scratch_dev, int32_t* labels, uint8_t* masks, emf_motion_info_t* info, int32_t* count,
                         emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Rolling a volume (new behaviour: the reference's background never moves).  Opt-in; nothing above is touched.
+ * One launch shifts a volume by whole voxels from one copy (src*) into a DIFFERENT copy (dst*), with the semantics
+ * of emf_hip_copyValues at equal resolutions:
+ *     dst(v) = src(v + shift) where v + shift lies inside the volume, 0 elsewhere
+ * for the tsdf, the weights and, when both colour pointers are given, the u16 x 4 colour volume (both or neither).
+ * Words are moved, never interpreted: the copy is bit for bit (-0.0f, NaN patterns).  |shift_i| >= res_i on any
+ * axis gives an all-zero volume.  Every destination array must be disjoint from every source array and from the
+ * other destination arrays: EMF_E_ARG otherwise, with nothing enqueued.
+ *   Tile-granular roll  (emf_hip_rollVolumeIsTiled: every res_i and every shift_i a multiple of the integration
+ *     tile 32 x 8 x 8)  one workgroup per destination tile, 16-byte accesses (all arrays 16-byte aligned:
+ *     EMF_E_ARG otherwise), no index division.  With the four map pointers given (all or none) the same launch
+ *     writes the destination's sign maps (emf_hip_signMapBytes) and unseen-tile map (emf_hip_unseenTileBytes) by
+ *     moving the source's per-tile entries; a tile whose source lies outside the volume gets "no sign, unseen".
+ *     PRECONDITION: the source maps describe the source values (the caller refreshes stale ones first).  When they
+ *     are what emf_hip_rebuildSignMaps / emf_hip_rebuildUnseenTiles compute from the source, the written maps equal,
+ *     byte for byte, what those entries compute from the destination.  The destination maps must not overlap the
+ *     source maps.
+ *   Any other shift or resolution  one voxel per lane, same values.  The map pointers are ignored and nothing is
+ *     written through them: the caller rebuilds the maps with the two rebuild entries.
+ * Nothing allocates, copies to the host or waits.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* 1 if (res, shift) takes the tile-granular path of emf_hip_rollVolume (and so writes the maps), else 0.  No device. */
+int emf_hip_rollVolumeIsTiled(const int32_t res[3], const int32_t shift[3]);
+
+int emf_hip_rollVolume(const float* srcTsdf, const float* srcWeights, const uint16_t* srcColor, const uint8_t* srcSignMaps,
+                       const uint8_t* srcUnseenTiles, float* dstTsdf, float* dstWeights, uint16_t* dstColor,
+                       uint8_t* dstSignMaps, uint8_t* dstUnseenTiles, const int32_t res[3], const int32_t shift[3],
+                       emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
