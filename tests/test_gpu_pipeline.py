@@ -15,10 +15,9 @@ BG_RES, BG_VOX, OBJ_RES = 64, 0.04, 32
 NOBJ, NFRAMES, MASK_EVERY = 2, 6, 3
 
 
-@pytest.fixture(scope="module", params=["batched", "batched_in_place", "per_volume", "sharded_1rank",
-                                         "sharded_1rank_per_volume", "sharded_1rank_peer", "sharded_1rank_peer_unfused"])
-def run(request, oracle, dev):
-    """Execution paths of emf::EMFusion: batched model-table launches (default), the
+def run_scenario(path, oracle, W=W, H=H):
+    """The scenario on execution path `path` at W x H: yields (fusion, oracle pipeline, object ids, history), closes
+    everything afterwards.  Execution paths of emf::EMFusion: batched model-table launches (default), the
     reference-shaped one-stream-per-volume path (EMF_PER_VOLUME=1), and the object-sharded
     multi-GPU path driven through a real RCCL communicator of ONE rank (EMF_FORCE_SHARDED=1):
     E-step partial sum -> ncclAllReduce(sum) -> normalise, hit keys -> ncclAllReduce(min) ->
@@ -32,16 +31,16 @@ def run(request, oracle, dev):
     from emfusion_amd import pipeline
     from emfusion_amd.ops import image_view
 
-    os.environ["EMF_PER_VOLUME"] = "1" if request.param.endswith("per_volume") else "0"
+    os.environ["EMF_PER_VOLUME"] = "1" if path.endswith("per_volume") else "0"
     # default: the background is kept twice and integrated out of place beside the raycast;
     # "in_place": the reference's sequence raycast -> integrate on one copy
-    os.environ["EMF_BG_OVERLAP"] = "0" if request.param.endswith("in_place") else "1"
+    os.environ["EMF_BG_OVERLAP"] = "0" if path.endswith("in_place") else "1"
     comm = None
-    if request.param.startswith("sharded"):
+    if path.startswith("sharded"):
         os.environ["EMF_FORCE_SHARDED"] = "1"
-        if "peer" in request.param:
+        if "peer" in path:
             comm = pipeline.Communicator.local_group(1, transport="peer",
-                                                     max_bytes=W * H * (8 if request.param.endswith("unfused") else 16))[0]
+                                                     max_bytes=W * H * (8 if path.endswith("unfused") else 16))[0]
         else:
             comm = pipeline.Communicator(pipeline.Communicator.unique_id(), 0, 1)
 
@@ -86,6 +85,12 @@ def run(request, oracle, dev):
     if comm is not None:
         comm.close()
     synth.close()
+
+
+@pytest.fixture(scope="module", params=["batched", "batched_in_place", "per_volume", "sharded_1rank",
+                                         "sharded_1rank_per_volume", "sharded_1rank_peer", "sharded_1rank_peer_unfused"])
+def run(request, oracle, dev):
+    yield from run_scenario(request.param, oracle)
 
 
 def test_frames_were_processed(run):
