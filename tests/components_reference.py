@@ -38,10 +38,11 @@ def kept_labels(labels, sizes, min_triangles=0, largest_only=False):
     return roots[keep]
 
 
-def filter_mesh(v, n, t, c=None, min_triangles=0, largest_only=False):
+def filter_mesh(v, n, t, c=None, min_triangles=0, largest_only=False, comps=None):
     """Filtered (vertices, normals, triangles[, colours]): kept vertices in order, bits unchanged; kept triangles in
-    order, re-indexed to the compacted vertices."""
-    labels, sizes = components(t, len(v))
+    order, re-indexed to the compacted vertices.  comps: components(t, len(v)) where the caller has it already (the
+    sequential union-find takes seconds on a mesh of millions of triangles)."""
+    labels, sizes = components(t, len(v)) if comps is None else comps
     keepv = np.isin(labels, kept_labels(labels, sizes, min_triangles, largest_only))
     rank = np.cumsum(keepv) - 1
     t = np.asarray(t).reshape(-1, 4)

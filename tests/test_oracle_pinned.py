@@ -294,6 +294,12 @@ def _mesh_volumes():
     odd = rng.uniform(-1, 1, (7, 10, 13)).astype(np.float32)
     odd[rng.random(odd.shape) < 0.1] = 0.0  # exact zeros: vertexInterp's |val| < 1e-5 branches
     yield "noise 13x10x7", odd, (rng.random(odd.shape) < 0.9).astype(np.float32), None, 0.02
+    # the dense fills of tests/mesh_volumes.py (zeros of both signs, denormals, values inside vertexInterp's 1e-5
+    # branches, denormal and negative weights), one of them under its foreground mask of bytes 0, 1, 2, 128, 255
+    from tests import mesh_volumes as MV
+    for shape, masked in (((5, 3, 70), False), ((65, 7, 40), True), ((74, 90, 66), False)):
+        t, w, fg, vox = MV.dense(shape)
+        yield "dense " + MV.name_of(shape) + (", foreground mask" if masked else ""), t, w, fg if masked else None, vox
 
 
 @pytest.mark.parametrize("case", list(_mesh_volumes()), ids=lambda c: c[0])

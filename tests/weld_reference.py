@@ -22,16 +22,17 @@ def edge_keys(tsdf, weights, fg=None, slot=0):
     valid = np.ones((nz - 1, ny - 1, nx - 1), bool)
     for c in range(8):
         valid &= at(ok, c)
-    z, y, x = np.meshgrid(np.arange(nz - 1), np.arange(ny - 1), np.arange(nx - 1), indexing="ij")
-    linear = ((z * ny + y) * nx + x).astype(np.uint64)
     active = np.zeros(valid.shape + (12,), bool)
-    keys = np.zeros(valid.shape + (12,), np.uint64)
+    offset, axes = np.zeros(12, np.uint64), np.zeros(12, np.uint64)
     for e, (a, b) in enumerate(EDGES):
         active[..., e] = valid & (at(neg, a) != at(neg, b))
         lo = np.minimum(CORNERS[a], CORNERS[b])
-        axis = int(np.flatnonzero(np.array(CORNERS[a]) != np.array(CORNERS[b]))[0])
-        keys[..., e] = np.uint64(3) * (linear + np.uint64(lo[0] + lo[1] * nx + lo[2] * nx * ny)) + np.uint64(axis)
-    return keys[active] | (np.uint64(slot) << np.uint64(48))
+        offset[e] = lo[0] + lo[1] * nx + lo[2] * nx * ny
+        axes[e] = np.flatnonzero(np.array(CORNERS[a]) != np.array(CORNERS[b]))[0]
+    # only the active (cube, edge) pairs get a key (a 256^3 volume has 2 * 10^8 pairs and a few 10^5 vertices)
+    z, y, x, e = (i.astype(np.uint64) for i in np.nonzero(active))
+    linear = (z * np.uint64(ny) + y) * np.uint64(nx) + x
+    return (np.uint64(3) * (linear + offset[e]) + axes[e]) | (np.uint64(slot) << np.uint64(48))
 
 
 def weld(v, n, t, keys, c=None):
