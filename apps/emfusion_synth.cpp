@@ -100,6 +100,12 @@ static emf::MotionMaskParams motionParams;
 // session's checkpoint carries the switch and its parameters.
 static bool followCamera = false;
 static emf::BackgroundFollowParams followParams;
+// --follow-store [--follow-store-mib N]: what rolls out is kept on the host and put back when the camera returns
+// (EMFusion::setBackgroundStore); N: the budget in MiB, 1024 by default -- a cap, not a measurement.
+// Needs --follow-camera.
+static bool followStore = false;
+static long followStoreMib = 1024;
+static bool followStoreMibGiven = false;
 static unsigned meshMinTriangles = 0;    // --mesh-min-triangles
 static bool meshLargestObject = false;   // --mesh-largest-object
 // --checkpoint PATH --checkpoint-every N: the session is saved to PATH after every N-th frame (EMFusion::saveCheckpoint);
@@ -178,6 +184,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     emf.setMeshFilter(meshMinTriangles, meshLargestObject);
     if (motionMasks) emf.setMotionMasks(true, motionParams);  // (not stored in a checkpoint: set again on --resume)
     if (followCamera) emf.setBackgroundFollow(true, followParams);
+    if (followStore) emf.setBackgroundStore(true, static_cast<uint64_t>(followStoreMib) << 20);
     std::vector<uint8_t> rgb;
     if (!masks.empty()) emf.usePreprocMasks(masks);   // apps/EM-Fusion.cpp:115
     emf.setupOutput(frameMeshes, volumes);            // apps/EM-Fusion.cpp:112
@@ -261,6 +268,11 @@ int main(int argc, char** argv) {
             }
             followParams.step = emf::Vec3i(x, y, z);
         }
+        else if (a == "--follow-store") followStore = true;
+        else if (a == "--follow-store-mib" && i + 1 < argc) {
+            followStoreMib = std::atol(argv[++i]);
+            followStoreMibGiven = true;
+        }
         else if (a == "--follow-lookahead" && i + 1 < argc) followParams.lookAhead = static_cast<float>(std::atof(argv[++i]));
         else if (a == "--motion-band" && i + 1 < argc) motionParams.band = static_cast<float>(std::atof(argv[++i]));
         else if (a == "--motion-min-pixels") motionParams.minPixels = next();
@@ -294,6 +306,11 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "unknown argument %s\n", a.c_str());
             return 2;
         }
+    }
+    if ((followStore && !followCamera) || (followStoreMibGiven && !followStore) || followStoreMib < 1) {  // (before any device is touched)
+        std::fprintf(stderr, "usage: emfusion_synth: --follow-store needs --follow-camera, and --follow-store-mib N (>= 1) needs "
+                             "--follow-store\n");
+        return 2;
     }
     if (motionMasks && !maskDir.empty()) {  // (before any device is touched)
         std::fprintf(stderr, "usage: emfusion_synth: --motion-masks and --masks DIR exclude each other: a mask frame takes its "
@@ -372,6 +389,7 @@ int main(int argc, char** argv) {
         emf.setMeshFilter(meshMinTriangles, meshLargestObject);
         if (motionMasks) emf.setMotionMasks(true, motionParams);
         if (followCamera) emf.setBackgroundFollow(true, followParams);
+        if (followStore) emf.setBackgroundStore(true, static_cast<uint64_t>(followStoreMib) << 20);
         if (!outDir.empty()) emf.setupOutput(frameMeshes, true);  // apps/EM-Fusion.cpp:112
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);

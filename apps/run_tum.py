@@ -46,6 +46,11 @@ def main():
                     help="voxels a roll moves by per axis: positive multiples of 32,8,8")
     ap.add_argument("--follow-lookahead", dest="follow_lookahead", type=float, default=0.0, metavar="M",
                     help="follow the point M metres in front of the camera")
+    ap.add_argument("--follow-store", dest="follow_store", action="store_true",
+                    help="remember what rolls out of the background and put it back when the camera returns "
+                         "(Fusion.set_background_store; needs --follow-camera)")
+    ap.add_argument("--follow-store-mib", dest="follow_store_mib", type=int, default=1024, metavar="N",
+                    help="the store's budget in MiB (default 1024: a cap, not a measurement); past it the oldest spills are dropped")
     ap.add_argument("--out", default=None, help="results directory (default emfusion_out)")
     ap.add_argument("--3d-vis", dest="vis3d", action="store_true",
                     help="the reference's 3D view: every frame also seen from a viewer 1 m behind the origin at "
@@ -90,6 +95,12 @@ def main():
         assert len(follow_step) == 3
     except (ValueError, AssertionError):
         ap.error("--follow-step takes three integers X,Y,Z")
+    if args.follow_store and not args.follow_camera:
+        ap.error("--follow-store needs --follow-camera")
+    if args.follow_store_mib != 1024 and not args.follow_store:
+        ap.error("--follow-store-mib needs --follow-store")
+    if args.follow_store_mib < 1:
+        ap.error("--follow-store-mib takes a positive number of MiB")
     if args.vis3d and args.out is None:
         ap.error("--3d-vis writes OUT/mesh_vis_out/ and needs --out")
     if args.frame_meshes and args.out is None:
@@ -136,6 +147,8 @@ def main():
         fus.set_motion_masks(True, band=args.motion_band, min_pixels=args.motion_min_pixels, max_masks=args.motion_max_masks)
     if args.follow_camera:
         fus.set_background_follow(True, step=follow_step, look_ahead=args.follow_lookahead)
+    if args.follow_store:
+        fus.set_background_store(True, max_bytes=args.follow_store_mib << 20)
     fus.set_ignore_person(args.ignore_person)
     fus.set_preprocess(True)
     fus.set_cleanup(True)

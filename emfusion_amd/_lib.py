@@ -189,6 +189,9 @@ SIGNATURES = {
     "emf_hip_motionMasks": [_FP, _FP, C.c_int, C.c_int, C.c_void_p, _FP, _FP, _FP, _FP, _FP, _STREAM],
     "emf_hip_rollVolumeIsTiled": [_I3, _I3],
     "emf_hip_rollVolume": [_FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _I3, _I3, _STREAM],
+    "emf_hip_spillScratchBytes": [C.c_uint64],
+    "emf_hip_spillTiles": [_FP, _FP, _FP, _I3, _I3, _I3, _FP, _FP, _FP, _FP, _FP, _FP, C.c_uint64, _STREAM],
+    "emf_hip_fillTiles": [_FP, _FP, _FP, _FP, _FP, _I3, _FP, _FP, _FP, _FP, _FP, _FP, C.c_uint64, C.c_uint32, _STREAM],
 }
 
 
@@ -310,6 +313,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.emf_hip_meshWeldScratchBytes.restype = C.c_size_t
     lib.emf_hip_meshComponentsScratchBytes.restype = C.c_size_t
     lib.emf_hip_packScratchBytes.restype = C.c_size_t
+    lib.emf_hip_spillScratchBytes.restype = C.c_size_t
     lib.emf_hip_motionMasksScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateCullScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateDirtyMapBytes.restype = C.c_size_t

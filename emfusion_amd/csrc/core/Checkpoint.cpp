@@ -1,7 +1,7 @@
 // Checkpoint.cpp -- EMFusion::saveCheckpoint / loadCheckpoint / checkpointInfo (see EMFusion.hpp).
 //
 // The file (little-endian, every block a multiple of 8 bytes):
-//   header   char magic[8] "EMFCKPT\0"; u32 version (1; 2 once the background has been rolled); u32 headerBytes; the Params block (putParams below: 56 words);
+//   header   char magic[8] "EMFCKPT\0"; u32 version (1; 2 once the background has been rolled; 3 with the background store on); u32 headerBytes; the Params block (putParams below: 56 words);
 //            u64 FNV-1a of every header byte before it
 //   sections {u32 tag; i32 id; u32 which; u32 0; u64 payloadBytes} + payload, zero-padded to 8 bytes:
 //     "SESS"  frame count, nextId, colour on/off, camera pose, allIds, the visible set, the colour map
@@ -15,6 +15,12 @@
 //     "ROLL"  version 2 only, exactly once, behind the last packed record: the background's cumulative origin, the
 //             follow switch and parameters, the background's current pose, the retired slabs.  A session that has never
 //             rolled writes version 1, byte for byte the file it always wrote
+//     "TILE"  version 3 only (a session with the background store on; its "ROLL" section is always
+//             present), exactly once, behind the roll section: u32 store on; u32 the background has rolled; u64 budget;
+//             u64 tiles held, bytes held, tiles spilled, restored, evicted; u64 last spill sequence; u64 tile count;
+//             then per stored tile, in store order: i32 lattice coordinate x y z; u64 spill sequence; u8 class x 3;
+//             u8 0; u32 word x 4 (40 bytes) and its literal arrays (8 KiB per unit).  A session with the store off
+//             writes version 1 or 2, byte for byte the file it always wrote
 //     "END!"  empty; the file ends behind it
 // Saved: the PRIMARY state.  Not saved because derived, rebuilt by the load the way ObjTSDF::resize and reset() do
 // (TSDF::volumesWritten, rebuildModelTable): fgProbs / fgVolMask, materialised gradients, sign maps, tile lists, dirty
@@ -31,6 +37,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <set>
 
 #include "EMFusion.hpp"
 #include "EMFusionDetail.hpp"
@@ -41,7 +48,7 @@ namespace emf {
 namespace {
 
 constexpr char kMagic[8] = {'E', 'M', 'F', 'C', 'K', 'P', 'T', '\0'};
-constexpr uint32_t kVersion = 1, kVersionRolled = 2;
+constexpr uint32_t kVersion = 1, kVersionRolled = 2, kVersionStore = 3;
 constexpr uint32_t kParamWords = 56;
 constexpr uint32_t kHeaderBytes = 16 + 4 * kParamWords + 8;
 constexpr uint64_t kChunk = 1024;
@@ -53,7 +60,7 @@ constexpr uint32_t fourcc(char a, char b, char c, char d) {
 }
 constexpr uint32_t kSess = fourcc('S', 'E', 'S', 'S'), kObj = fourcc('O', 'B', 'J', ' '), kLogs = fourcc('L', 'O', 'G', 'S'),
                    kMesh = fourcc('M', 'E', 'S', 'H'), kPack = fourcc('P', 'A', 'C', 'K'), kEnd = fourcc('E', 'N', 'D', '!'),
-                   kRoll = fourcc('R', 'O', 'L', 'L');
+                   kRoll = fourcc('R', 'O', 'L', 'L'), kTile = fourcc('T', 'I', 'L', 'E');
 constexpr uint32_t kVolFgBg = 6;  // EMF_VOL_FGBG
 
 struct SectionHeader {
@@ -251,7 +258,22 @@ struct FileIndex {
     BackgroundFollowParams follow;
     Affine3f bgPose;
     std::vector<RetiredSlab> retired;
+    // version 3: the "TILE" section
+    struct TileRef {
+        TileKey key{};
+        uint64_t seq = 0;
+        uint8_t cls[3] = {0, 0, 0};
+        uint32_t words[4] = {0, 0, 0, 0};
+        uint64_t offset = 0;  // of its literals in the file
+        uint64_t bytes = 0;
+    };
+    bool storeOn = false, storeRolled = false;
+    uint64_t storeBudget = 0, storeSeq = 0;
+    TileStore::Counters storeCounters;
+    std::vector<TileRef> tiles;
 };
+constexpr uint64_t kTileHead = 72, kTileRecord = 40;
+static_assert(kTileRecord == TileStore::kRecordBytes, "a stored tile costs its checkpoint header plus its literals");
 
 void putMesh(Blob& b, const Mesh& m) {
     b.put<uint64_t>(m.vertices());
@@ -328,9 +350,9 @@ FileIndex scanFile(const std::string& path, bool headerOnly = false) {
     uint32_t version, headerBytes;
     std::memcpy(&version, head + 8, 4);
     std::memcpy(&headerBytes, head + 12, 4);
-    if (version != kVersion && version != kVersionRolled)
-        refuse(path, "format version " + std::to_string(version) + ", this build reads " + std::to_string(kVersion) + " and " +
-                         std::to_string(kVersionRolled));
+    if (version != kVersion && version != kVersionRolled && version != kVersionStore)
+        refuse(path, "format version " + std::to_string(version) + ", this build reads " + std::to_string(kVersion) + ", " +
+                         std::to_string(kVersionRolled) + " and " + std::to_string(kVersionStore));
     ix.version = version;
     uint64_t sum;
     std::memcpy(&sum, head + kHeaderBytes - 8, 8);
@@ -349,7 +371,7 @@ FileIndex scanFile(const std::string& path, bool headerOnly = false) {
     // the records that must come, in order, once the object table is known
     std::vector<std::pair<int, uint32_t>> expect;
     size_t nextRecord = 0;
-    bool sawSess = false, sawLogs = false, sawEnd = false, sawRoll = false;
+    bool sawSess = false, sawLogs = false, sawEnd = false, sawRoll = false, sawTile = false;
     size_t nobjects = 0;
     uint64_t at = kHeaderBytes;
     std::vector<uint8_t> buf;
@@ -361,7 +383,7 @@ FileIndex scanFile(const std::string& path, bool headerOnly = false) {
         at += sizeof(sh);
         if (sh.zero != 0 || sh.bytes > ix.fileBytes - at || pad8(sh.bytes) > ix.fileBytes - at)
             refuse(path, "truncated (a section runs past the end of the file)");
-        const bool small = sh.tag != kPack;
+        const bool small = sh.tag != kPack && sh.tag != kTile;  // (those two are read piece by piece)
         if (small) {
             if (sh.bytes > (1ull << 31)) refuse(path, "a section is implausibly large");
             buf.resize(sh.bytes);
@@ -443,7 +465,8 @@ FileIndex scanFile(const std::string& path, bool headerOnly = false) {
         } else if (sh.tag == kMesh) {
             ix.meshes[sh.id] = getMesh(c, sh.bytes, path);
         } else if (sh.tag == kRoll) {
-            if (version != kVersionRolled || sawRoll || !sawSess || nextRecord != expect.size())
+            if ((version != kVersionRolled && version != kVersionStore) || sawRoll || sawTile || !sawSess ||
+                nextRecord != expect.size())
                 refuse(path, "a roll section out of place");
             sawRoll = true;
             c.getBytes(ix.origin.val, sizeof(ix.origin.val));
@@ -465,6 +488,52 @@ FileIndex scanFile(const std::string& path, bool headerOnly = false) {
             for (int i = 0; i < 3; ++i)
                 if (ix.follow.step[i] <= 0 || ix.follow.step[i] % tile[i] != 0) refuse(path, "follow parameters out of range");
             if (!std::isfinite(ix.follow.lookAhead)) refuse(path, "follow parameters out of range");
+        } else if (sh.tag == kTile) {
+            if (version != kVersionStore || sawTile || !sawRoll) refuse(path, "a tile section out of place");
+            sawTile = true;
+            if (sh.bytes < kTileHead) refuse(path, "a tile section is shorter than its header");
+            uint8_t th[kTileHead];
+            readExact(in.f, th, sizeof(th), path);
+            Cursor t{th, th + sizeof(th), path};
+            ix.storeOn = t.get<uint32_t>() != 0;
+            ix.storeRolled = t.get<uint32_t>() != 0;
+            ix.storeBudget = t.get<uint64_t>();
+            TileStore::Counters& sc = ix.storeCounters;
+            sc.tilesHeld = t.get<uint64_t>();
+            sc.bytesHeld = t.get<uint64_t>();
+            sc.tilesSpilled = t.get<uint64_t>();
+            sc.tilesRestored = t.get<uint64_t>();
+            sc.tilesEvicted = t.get<uint64_t>();
+            ix.storeSeq = t.get<uint64_t>();
+            const uint64_t ntiles = t.get<uint64_t>();
+            if (!ix.storeOn || ntiles != sc.tilesHeld || ntiles > (sh.bytes - kTileHead) / kTileRecord)
+                refuse(path, "a tile section and its counts disagree");
+            uint64_t used = kTileHead, held = 0, lastSeq = 0;
+            std::set<TileKey> seen;
+            for (uint64_t k = 0; k < ntiles; ++k) {
+                if (sh.bytes - used < kTileRecord) refuse(path, "a tile section is shorter than its contents");
+                uint8_t rec[kTileRecord];
+                seekTo(in.f, at + used, path);
+                readExact(in.f, rec, sizeof(rec), path);
+                used += kTileRecord;
+                FileIndex::TileRef r;
+                std::memcpy(r.key.data(), rec, 12);
+                std::memcpy(&r.seq, rec + 12, 8);
+                std::memcpy(r.cls, rec + 20, 3);
+                std::memcpy(r.words, rec + 24, 16);
+                if (r.cls[0] > 2 || r.cls[1] > 2 || r.cls[2] > 2 || rec[23] != 0) refuse(path, "a stored tile holds an unknown class");
+                if ((r.cls[0] | r.cls[1] | r.cls[2]) == 0 || r.seq < lastSeq || r.seq == 0 || r.seq > ix.storeSeq ||
+                    !seen.insert(r.key).second)
+                    refuse(path, "the stored tiles are not in store order");
+                lastSeq = r.seq;
+                r.bytes = TileStore::unitsOf(r.cls) * TileStore::kUnitBytes;
+                if (sh.bytes - used < r.bytes) refuse(path, "a tile section is shorter than its contents");
+                r.offset = at + used;
+                used += r.bytes;
+                held += kTileRecord + r.bytes;
+                ix.tiles.push_back(r);
+            }
+            if (used != sh.bytes || held != sc.bytesHeld) refuse(path, "a tile section and its counts disagree");
         } else if (sh.tag == kPack) {
             if (sawRoll || ix.objects.size() != nobjects || !sawSess || nextRecord >= expect.size() ||
                 expect[nextRecord] != std::make_pair(static_cast<int>(sh.id), sh.which))
@@ -507,6 +576,8 @@ FileIndex scanFile(const std::string& path, bool headerOnly = false) {
     if (!sawSess || !sawLogs || ix.objects.size() != nobjects || nextRecord != expect.size())
         refuse(path, "truncated (sections are missing)");
     if (version == kVersionRolled && !sawRoll) refuse(path, "format version 2 without its roll section");
+    if (version == kVersionStore && !sawRoll) refuse(path, "format version 3 without its roll section");
+    if (version == kVersionStore && !sawTile) refuse(path, "format version 3 without its tile section");
     return ix;
 }
 
@@ -585,7 +656,7 @@ CheckpointStats EMFusion::saveCheckpoint(const std::string& path) {
         {
             Blob h;
             h.putBytes(kMagic, 8);
-            h.put<uint32_t>(bgRolled ? kVersionRolled : kVersion);
+            h.put<uint32_t>(storeOn ? kVersionStore : (bgRolled ? kVersionRolled : kVersion));
             h.put<uint32_t>(kHeaderBytes);
             putParams(h, params, gradMode == TSDF::Gradients::Materialized);
             h.put<uint64_t>(fnv1a(h.b.data(), h.b.size()));
@@ -729,7 +800,7 @@ CheckpointStats EMFusion::saveCheckpoint(const std::string& path) {
             pack(o.getID(), kVolFgBg, o.fgBgPtr(), o.voxels() * 2 * sizeof(float));
             packColor(o.getID(), o);
         }
-        if (bgRolled) {  // version 2's trailing section
+        if (bgRolled || storeOn) {  // version 2's trailing section; version 3 always has it
             Blob b;
             b.putBytes(bgOrigin.val, sizeof(bgOrigin.val));
             b.put<int32_t>(followOn ? 1 : 0);
@@ -746,6 +817,34 @@ CheckpointStats EMFusion::saveCheckpoint(const std::string& path) {
             }
             b.pad();
             w.section(kRoll, 0, b);
+        }
+        if (storeOn) {  // version 3's trailing section: the store, tile by tile (never a second copy of it)
+            const TileStore::Counters& sc = bgStore.counters();
+            const auto tiles = bgStore.inOrder();
+            w.section(kTile, 0, 0, kTileHead + sc.bytesHeld);
+            Blob b;
+            b.put<uint32_t>(1);
+            b.put<uint32_t>(bgRolled ? 1 : 0);
+            b.put<uint64_t>(bgStore.budget());
+            b.put<uint64_t>(sc.tilesHeld);
+            b.put<uint64_t>(sc.bytesHeld);
+            b.put<uint64_t>(sc.tilesSpilled);
+            b.put<uint64_t>(sc.tilesRestored);
+            b.put<uint64_t>(sc.tilesEvicted);
+            b.put<uint64_t>(bgStore.sequence());
+            b.put<uint64_t>(tiles.size());
+            w.bytes(b.b.data(), b.b.size());
+            for (const auto& t : tiles) {
+                Blob r;
+                r.putBytes(t.first.data(), 12);
+                r.put<uint64_t>(t.second->seq);
+                r.putBytes(t.second->cls, 3);
+                r.put<uint8_t>(0);
+                r.putBytes(t.second->words, 16);
+                w.bytes(r.b.data(), r.b.size());
+                w.bytes(t.second->literals.data(), t.second->literals.size());
+            }
+            w.padTo8();
         }
         w.section(kEnd, 0, 0, 0);
         const auto t0 = std::chrono::steady_clock::now();
@@ -862,13 +961,29 @@ void EMFusion::loadCheckpoint(const std::string& path) {
         obj_poses = ix.objPoses;
         obj_pose_offsets = ix.objOffsets;
         meshes = ix.meshes;
-        if (ix.version == kVersionRolled) {  // the background where the rolls had taken it
+        if (ix.version == kVersionRolled || ix.version == kVersionStore) {  // the background where the rolls had taken it
             background.setPose(ix.bgPose);
             bgOrigin = ix.origin;
-            bgRolled = true;
+            bgRolled = ix.version == kVersionRolled || ix.storeRolled;
             followOn = ix.followOn;
             followParams = ix.follow;
             retired = ix.retired;
+        }
+        if (ix.version == kVersionStore) {  // the store as it was: switch, budget, counters, every tile in its order
+            storeOn = true;
+            bgStore.restore(ix.storeBudget, ix.storeCounters, ix.storeSeq);
+            uint32_t index = 0;
+            for (const FileIndex::TileRef& r : ix.tiles) {
+                StoredTile t;
+                t.seq = r.seq;
+                t.index = index++;  // store order is file order
+                std::memcpy(t.cls, r.cls, 3);
+                std::memcpy(t.words, r.words, 16);
+                t.literals.resize(r.bytes);
+                seekTo(in.f, r.offset, path);
+                readExact(in.f, t.literals.data(), t.literals.size(), path);
+                bgStore.restoreTile(r.key, std::move(t));
+            }
         }
         forkFrame = -2;
         farBoundsReady = false;
@@ -907,6 +1022,8 @@ std::string EMFusion::checkpointInfo(const std::string& path) {
         static_cast<unsigned long long>(ix.fileBytes), ix.frameCount, ix.nextId, ix.colorOn ? "true" : "false");
     add("\"background_origin\": [%d, %d, %d], \"retired_slabs\": %d, ", ix.origin[0], ix.origin[1], ix.origin[2],
         static_cast<int>(ix.retired.size()));
+    add("\"stored_tiles\": %llu, \"stored_bytes\": %llu, ", static_cast<unsigned long long>(ix.tiles.size()),
+        static_cast<unsigned long long>(ix.storeCounters.bytesHeld));
     add("\"params\": {\"width\": %d, \"height\": %d, \"K\": ", p.frameSize.width, p.frameSize.height);
     floats(p.intr.val, 9);
     add(", \"bg_res\": [%d, %d, %d], \"bg_voxel_size\": %.9g, \"bg_rel_truncdist\": %.9g, \"volume_pose_t\": ",

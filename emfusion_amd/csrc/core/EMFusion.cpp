@@ -134,6 +134,7 @@ void EMFusion::reset() {
     bgOrigin = Vec3i();
     bgRolled = false;
     retired.clear();
+    bgStore.restore(bgStore.budget(), TileStore::Counters(), 0);  // empty, its counters zero; the switch stays
     trackPredicted[0] = trackPredicted[1] = 0;
     Stream& s = Stream::Null();
     bg_associationWeights.setTo(1.f, s);

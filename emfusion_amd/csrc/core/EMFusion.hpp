@@ -26,6 +26,7 @@
 #include "Output.hpp"
 #include "Switches.hpp"
 #include "TSDF.hpp"
+#include "TileStore.hpp"
 
 namespace emf {
 
@@ -319,6 +320,20 @@ public:
     void rollBackground(const Vec3i& shift, int keepRetired = -1);
     Vec3i backgroundOrigin() const { return bgOrigin; }
     const std::vector<RetiredSlab>& retiredSlabs() const { return retired; }
+    /**
+     * Remember what rolls out (new behaviour, off by default; with it off no launch, no output byte
+     * and no checkpoint byte changes).  With the store on a roll must be tile-granular -- shift, background
+     * resolution and backgroundOrigin() multiples of (32, 8, 8), as every policy roll is: EMF_E_ARG otherwise, before
+     * anything is changed.  After the slabs are retired the leaving tiles go to the host as the bytes they are
+     * (emf::TileStore, at most maxBytes: the oldest spills are dropped first); the tiles that enter are looked up, taken
+     * out of the store and written into the rolled volume, with their sign and unseen-tile entries, before the two
+     * copies are made equal.  retiredSlabs() stays the chronological log it is: a region that leaves twice is logged
+     * twice.  Turning the store off drops what it holds.  Refused on the sharded path, as follow is.  A session
+     * with the store on writes a version-3 checkpoint that carries the store.
+     */
+    void setBackgroundStore(bool on, uint64_t maxBytes = TileStore::kDefaultBudget);
+    bool backgroundStoreEnabled() const { return storeOn; }
+    const TileStore& backgroundStore() const { return bgStore; }
     /** Ids returned by initNewObjVolume for FrameInputs::newObjectMasks of the last frame (-1: none). */
     const std::vector<int>& lastCreatedObjects() const { return lastCreated; }
     Affine3f getCameraPose() const { return pose; }
@@ -606,6 +621,9 @@ private:
     std::vector<RetiredSlab> retired;
     void followCamera();                // the end of a frame with follow on
     void rollBackgroundAt(const Vec3i& shift, int frame, bool keepRetired);
+    // ---- the tile store (setBackgroundStore; EMFusionFollow.cpp) ----
+    bool storeOn = false;
+    TileStore bgStore;
     void retireSlabs(const Vec3i& shift, int frame);
     DeviceImage<float> depthFiltered;  // output of preprocessDepth
     DeviceImage<float> invLambda;  // per-pixel 1 / lambda of the integration, fixed by the intrinsics (sw.useLambdaTable)

@@ -2,7 +2,9 @@
 // reference's background is built once at params.volumePose and never moves).
 #include "EMFusion.hpp"
 
+#include <algorithm>
 #include <cmath>
+#include <cstdlib>
 
 namespace emf {
 
@@ -41,6 +43,44 @@ void EMFusion::setBackgroundFollow(bool on, const BackgroundFollowParams& p) {
     followParams = p;
 }
 
+void EMFusion::setBackgroundStore(bool on, uint64_t maxBytes) {
+    if (on && (sharded || world > 1))
+        throw HipError("EMFusion::setBackgroundStore: the background store is not supported on the sharded path", EMF_E_ARG);
+    if (!on) bgStore.clear();
+    storeOn = on;
+    bgStore.setBudget(maxBytes);
+}
+
+namespace {
+// The tiles of a volume of nt tiles that a roll by k tiles (|k_i| <= nt_i) moves out of it -- or, entering = true, the
+// tiles of the rolled volume that nothing moved into -- in at most three disjoint boxes: x first over all y, z, then
+// y over the x that stays, then z over the x, y that stay (as retireSlabs cuts, without its extra voxel layer).
+// dst(t) = src(t + k): with k > 0 the low tiles [0, k) leave and the high tiles [nt - k, nt) enter.
+std::vector<TileBox> rollBoxes(const int nt[3], const int k[3], bool entering) {
+    std::vector<TileBox> boxes;
+    int lo[3] = {0, 0, 0}, hi[3] = {nt[0], nt[1], nt[2]};
+    for (int axis = 0; axis < 3; ++axis) {
+        if (k[axis] == 0) continue;
+        const int m = std::abs(k[axis]);
+        const bool low = (k[axis] > 0) != entering;  // the box sits at the low end of the axis
+        TileBox b;
+        for (int i = 0; i < 3; ++i) {
+            b.lo[i] = lo[i];
+            b.size[i] = hi[i] - lo[i];
+        }
+        b.lo[axis] = low ? 0 : nt[axis] - m;
+        b.size[axis] = m;
+        if (b.size[0] > 0 && b.size[1] > 0 && b.size[2] > 0) boxes.push_back(b);
+        if (low)
+            lo[axis] = m;
+        else
+            hi[axis] = nt[axis] - m;
+        if (hi[axis] <= lo[axis]) break;  // everything left (entered): the later boxes are empty
+    }
+    return boxes;
+}
+}  // namespace
+
 // The end of a frame with follow on: where is the followed point in the background's frame, and has it left the
 // dead zone of one step around the centre?
 void EMFusion::followCamera() {
@@ -62,13 +102,36 @@ void EMFusion::rollBackgroundAt(const Vec3i& shift, int frame, bool keepRetired)
     if (sharded || world > 1)
         throw HipError("EMFusion::rollBackground: rolling the background is not supported on the sharded path", EMF_E_ARG);
     if (shift[0] == 0 && shift[1] == 0 && shift[2] == 0) return;
+    if (storeOn) {  // before anything is changed
+        const Vec3i n = background.getVolumeRes();
+        if (!emf_hip_rollVolumeIsTiled(n.val, shift.val) || !emf_hip_rollVolumeIsTiled(n.val, bgOrigin.val))
+            throw HipError("EMFusion::rollBackground: with the background store on, the shift (" + std::to_string(shift[0]) + ", " +
+                               std::to_string(shift[1]) + ", " + std::to_string(shift[2]) +
+                               "), the background resolution and the background origin must be multiples of the tile (32, 8, 8)",
+                           EMF_E_ARG);
+    }
     // as saveCheckpoint: nothing of this instance in flight, the visible set on the host (the table is rebuilt below)
     quiesce();
     refreshVisibleFromDevice();
     if (bgInFlight) joinBackground();
     quiesce();
     if (keepRetired) retireSlabs(shift, frame);
-    background.roll(shift, main);  // leaves the two copies equal, whatever they were
+    if (storeOn) {
+        const Vec3i n = background.getVolumeRes();
+        int nt[3], k[3];
+        TileKey before, after;  // lattice coordinate of the volume's tile (0, 0, 0)
+        for (int i = 0; i < 3; ++i) {
+            nt[i] = n[i] / kTile[i];
+            k[i] = std::clamp(shift[i] / kTile[i], -nt[i], nt[i]);
+            before[i] = bgOrigin[i] / kTile[i];
+            after[i] = (bgOrigin[i] + shift[i]) / kTile[i];
+        }
+        bgStore.spill(background.tsdfPtr(), background.weightsPtr(), background.colorPtr(), n, rollBoxes(nt, k, false), before, main);
+        const TileFill fill = bgStore.takeFill(rollBoxes(nt, k, true), after, main);
+        background.roll(shift, main, &fill);
+    } else {
+        background.roll(shift, main);  // leaves the two copies equal, whatever they were
+    }
     bgBackStale = false;
     bgPrepared = false;
     bgListPending = false;

@@ -2,6 +2,7 @@
 #include "TSDF.hpp"
 
 #include "Switches.hpp"
+#include "TileStore.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -235,7 +236,7 @@ void TSDF::volumesWritten(Stream& stream) {
     resyncBack();
 }
 
-void TSDF::roll(const Vec3i& shift, Stream& stream) {
+void TSDF::roll(const Vec3i& shift, Stream& stream, const TileFill* fill) {
     const bool twice = doubleBuffered();
     DeviceBuffer newVol, newWeights, newColor, newSign, newUnseen;
     if (!twice) {
@@ -258,6 +259,14 @@ void TSDF::roll(const Vec3i& shift, Stream& stream) {
                                 moveMaps ? newSign.as<uint8_t>() : nullptr, moveMaps ? newUnseen.as<uint8_t>() : nullptr,
                                 volumeRes.val, shift.val, stream.abi()),
              "TSDF::roll");
+    if (fill && fill->n)  // what the store kept of the entering region, maps included when they travel
+        emfCheck(emf_hip_fillTiles(twice ? tsdfBack.as<float>() : newVol.as<float>(),
+                                   twice ? weightsBack.as<float>() : newWeights.as<float>(),
+                                   newColor.empty() ? nullptr : newColor.as<uint16_t>(), moveMaps ? newSign.as<uint8_t>() : nullptr,
+                                   moveMaps ? newUnseen.as<uint8_t>() : nullptr, volumeRes.val, fill->coords.as<int32_t>(),
+                                   fill->classes.as<uint8_t>(), fill->classesHost.data(), fill->words.as<uint32_t>(),
+                                   fill->lits.as<uint32_t>(), fill->arena.data(), fill->arenaUnits, fill->n, stream.abi()),
+                 "TSDF::roll (fill)");
     stream.waitForCompletion();  // the old buffers are released below
     if (twice) {
         flip();

@@ -16,6 +16,8 @@
 
 namespace emf {
 
+struct TileFill;  // TileStore.hpp
+
 class TSDF {
 public:
     /** How raycast() obtains the surface normal. */
@@ -158,8 +160,12 @@ public:
      * rebuildModelTable(), materialised gradients recomputed -- except that valid sign / unseen maps stay valid on
      * the tile-granular path: the launch moves their entries.  Waits for `stream`; the owner has joined every other
      * stream that touches this volume.
+     * fill (emf::TileStore::takeFill; needs a resolution that is a multiple of the tile): tiles to write into the
+     * rolled volume with emf_hip_fillTiles, after the roll's launch and before the copies change roles -- into the
+     * destination arrays, the new colour buffer and, only when the roll moved the maps, the new maps -- so that the
+     * gradients and the other copy are made from the restored values.
      */
-    void roll(const Vec3i& shift, Stream& stream);
+    void roll(const Vec3i& shift, Stream& stream, const TileFill* fill = nullptr);
     /**
      * A volume of its own holding the voxels [lo, lo + res) of this one's front copy (and colour), cut with
      * emf_hip_copyValues / emf_hip_copyColorValues; the parts of the box outside this volume read as zeros.  Its

@@ -464,6 +464,24 @@ int emf_fusion_roll_background(emf_fusion_t* h, const int32_t shift[3], int keep
     return guarded([&] { h->impl->rollBackground(Vec3i(shift[0], shift[1], shift[2]), keep_retired); });
 }
 
+int emf_fusion_set_background_store(emf_fusion_t* h, int on, uint64_t max_bytes) {
+    REQ(h);
+    return guarded([&] { h->impl->setBackgroundStore(on != 0, max_bytes ? max_bytes : TileStore::kDefaultBudget); });
+}
+
+int emf_fusion_background_store_info(emf_fusion_t* h, uint64_t out[5]) {
+    REQ(h);
+    REQ(out);
+    return guarded([&] {
+        const TileStore::Counters& c = h->impl->backgroundStore().counters();
+        out[0] = c.tilesHeld;
+        out[1] = c.bytesHeld;
+        out[2] = c.tilesSpilled;
+        out[3] = c.tilesRestored;
+        out[4] = c.tilesEvicted;
+    });
+}
+
 int emf_fusion_background_origin(emf_fusion_t* h, int32_t origin[3], float R[9], float t[3]) {
     REQ(h);
     REQ(origin);

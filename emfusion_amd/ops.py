@@ -418,6 +418,62 @@ def roll_volume(tsdf, weights, shift, color=None, sign_maps=None, unseen_tiles=N
     return out[0], out[1], d_color, d_sign, d_unseen
 
 
+TILE = (32, 8, 8)
+TILE_UNIT = 8192  # bytes of one arena unit: a tile's tsdf or weights; its colour is two
+
+
+def _tile_res(tsdf):
+    nz, ny, nx = tsdf.shape
+    return (C.c_int32 * 3)(nx, ny, nz), (nx // TILE[0], ny // TILE[1], nz // TILE[2])
+
+
+def spill_tiles(tsdf, weights, box_lo, box_size, color=None, count_only=False, arena_units=None, stream=None):
+    """emf_hip_spillTiles over the tile box [box_lo, box_lo + box_size) (x, y, z, in tiles) of (Nz, Ny, Nx) f32 tsdf /
+    weights and an optional (Nz, Ny, Nx, 4) u16 colour volume.  Returns dict(classes (n, 3) u8, words (n, 4) u32,
+    lits (n, 3) u32, units, arena): numpy arrays, candidates x fastest inside the box; arena is the DeviceArray
+    ((capacity, 8192) u8) whose first `units` rows hold the literals, None with count_only.  arena_units overrides the
+    capacity (the box's worst case by default).  Synchronises (the totals are read back)."""
+    res, _ = _tile_res(tsdf)
+    n = int(box_size[0]) * int(box_size[1]) * int(box_size[2]) if min(int(v) for v in box_size) >= 0 else 0
+    classes, words = DeviceArray.zeros((max(n, 1), 3), np.uint8), DeviceArray.zeros((max(n, 1), 4), np.uint32)
+    lits, totals = DeviceArray.zeros((max(n, 1), 3), np.uint32), DeviceArray.zeros((1,), np.uint32)
+    scratch = DeviceArray((max(int(_L.emf_hip_spillScratchBytes(max(n, 0))) // 4, 1),), np.uint32)
+    arena = None
+    if not count_only:
+        cap = n * (2 if color is None else 4) if arena_units is None else int(arena_units)
+        arena = DeviceArray((max(cap, 1), TILE_UNIT), np.uint8)
+    check("emf_hip_spillTiles",
+          _L.emf_hip_spillTiles(_ptr(tsdf), _ptr(weights), _ptr(color), res, (C.c_int32 * 3)(*[int(v) for v in box_lo]),
+                                (C.c_int32 * 3)(*[int(v) for v in box_size]), _ptr(scratch), _ptr(classes), _ptr(words),
+                                _ptr(lits), _ptr(totals), _ptr(arena), 0 if arena is None else cap, _stream(stream)))
+    return dict(classes=classes.numpy()[:n], words=words.numpy()[:n], lits=lits.numpy()[:n],
+                units=int(totals.numpy()[0]), arena=arena)
+
+
+def fill_tiles(tsdf, weights, coords, classes, words, lits, arena=None, arena_units=None, color=None, sign_maps=None,
+               unseen_tiles=None, stream=None):
+    """emf_hip_fillTiles: write the listed tiles -- coords (n, 3) i32 tile coordinates (x, y, z) with classes (n, 3) u8,
+    words (n, 4) u32, lits (n, 3) u32 as spill_tiles returns them (numpy) and its arena (DeviceArray) -- into the
+    device volumes tsdf / weights[/ color] in place, and their entries into sign_maps / unseen_tiles (both or
+    neither).  Tiles not listed are not touched.  Synchronises: the four lists are uploaded for the call and released
+    when it returns."""
+    res, _ = _tile_res(tsdf)
+    coords = np.ascontiguousarray(np.asarray(coords, np.int32).reshape(-1, 3))
+    n = coords.shape[0]
+    classes = np.ascontiguousarray(np.asarray(classes, np.uint8).reshape(-1, 3))
+    words = np.ascontiguousarray(np.asarray(words, np.uint32).reshape(-1, 4))
+    lits = np.ascontiguousarray(np.asarray(lits, np.uint32).reshape(-1, 3))
+    assert classes.shape[0] == n and words.shape[0] == n and lits.shape[0] == n
+    d = [DeviceArray.from_numpy(a) if n else None for a in (coords, classes, words, lits)]
+    if arena_units is None:
+        arena_units = 0 if arena is None else arena.nbytes // TILE_UNIT
+    check("emf_hip_fillTiles",
+          _L.emf_hip_fillTiles(_ptr(tsdf), _ptr(weights), _ptr(color), _ptr(sign_maps), _ptr(unseen_tiles), res, _ptr(d[0]),
+                               _ptr(d[1]), classes.ctypes.data_as(C.c_void_p) if n else None, _ptr(d[2]), _ptr(d[3]),
+                               _ptr(arena), int(arena_units), n, _stream(stream)))
+    synchronize()
+
+
 def raycast_far_bounds(models_dev, poses_co, res_list, width, height, K, bounds=None, stream=None, scan_mask=0xffffffff):
     """emf_hip_raycastFarBounds -> float32 (nmodels, cellsY, cellsX) device array."""
     n = len(poses_co)

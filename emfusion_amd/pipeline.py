@@ -64,6 +64,7 @@ _IMG_DTYPE = {0: ("float32", 3), 1: ("float32", 1), 2: ("float32", 1), 3: ("floa
               4: ("float32", 1), 5: ("float32", 3), 6: ("float32", 3), 7: ("uint8", 1),
               8: ("float32", 1), 9: ("float32", 1)}
 SHADING = dict(label=0, color=1)
+BACKGROUND_STORE_BYTES = 1 << 30  # set_background_store's default budget: a cap, not a measurement
 VOL = dict(tsdf=0, weights=1, fgprobs=2, fgmask=3, bricks=4, color=5, fgbg=6)
 
 _lib = None
@@ -119,6 +120,8 @@ def load() -> C.CDLL:
         "emf_fusion_set_color_image": [vp, img],
         "emf_fusion_set_background_follow": [vp, C.c_int, C.c_void_p],
         "emf_fusion_roll_background": [vp, ip, C.c_int],
+        "emf_fusion_set_background_store": [vp, C.c_int, C.c_uint64],
+        "emf_fusion_background_store_info": [vp, C.c_void_p],
         "emf_fusion_background_origin": [vp, ip, fp, fp],
         "emf_fusion_retired_slabs": [vp, C.c_void_p, C.c_int, ip],
         "emf_fusion_retired_slab_mesh": [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
@@ -654,6 +657,23 @@ class Fusion:
         _check("emf_fusion_roll_background",
                load().emf_fusion_roll_background(self._h, (C.c_int32 * 3)(*[int(v) for v in shift]), keep))
 
+    def set_background_store(self, on=True, max_bytes=BACKGROUND_STORE_BYTES):
+        """Remember what rolls out: the whole tiles (32 x 8 x 8) that a roll moves out of the background are kept on the
+        host as the bytes they are and written back -- tsdf, weights, colour, sign and unseen-tile entries -- when a
+        later roll moves them in again.  `max_bytes` caps the store (1 GiB by default: a cap, not a measurement); past
+        it whole spills are dropped, the oldest first.  With the store on, a roll that is not tile-granular is refused.
+        retired_slabs() stays the chronological log it is: a region that leaves twice is logged twice.  Turning the
+        store off drops what it holds.  Off by default; refused on the sharded path.  save_checkpoint() of a session
+        with the store on writes version 3, which carries the store."""
+        _check("emf_fusion_set_background_store",
+               load().emf_fusion_set_background_store(self._h, int(bool(on)), int(max_bytes)))
+
+    def background_store_info(self):
+        """dict(tiles_held, bytes_held, tiles_spilled, tiles_restored, tiles_evicted) of the background store."""
+        out = (C.c_uint64 * 5)()
+        _check("emf_fusion_background_store_info", load().emf_fusion_background_store_info(self._h, C.addressof(out)))
+        return dict(zip(("tiles_held", "bytes_held", "tiles_spilled", "tiles_restored", "tiles_evicted"), (int(v) for v in out)))
+
     def background_origin(self):
         """The cumulative roll in voxels, on the lattice whose index (0, 0, 0) is voxel (0, 0, 0) at the initial pose."""
         o = (C.c_int32 * 3)()
@@ -1017,7 +1037,8 @@ class Fusion:
         """emf_fusion_save_checkpoint: the session's primary state, volumes packed losslessly on the device, written to
         `path` (through path + ".tmp").  Returns raw_bytes / file_bytes, chunks per class and the milliseconds of the
         stages (classify, gather: device; copy, file, total: host).  The background-follow switch and its parameters
-        are in the file only once the background has rolled (see set_background_follow)."""
+        are in the file only once the background has rolled (see set_background_follow); a session with the
+        background store on writes version 3, which carries the store (see set_background_store)."""
         st = CheckpointStats()
         _check("emf_fusion_save_checkpoint", load().emf_fusion_save_checkpoint(self._h, os.fspath(path).encode(), C.byref(st)))
         return dict(raw_bytes=int(st.raw_bytes), file_bytes=int(st.file_bytes), records=int(st.records),

@@ -203,6 +203,21 @@ int emf_fusion_background_origin(emf_fusion_t* h, int32_t origin[3], float R[9],
 int emf_fusion_retired_slabs(emf_fusion_t* h, int32_t* info, int capacity, int32_t* count);
 int emf_fusion_retired_slab_mesh(emf_fusion_t* h, int index, uint32_t* num_vertices, uint32_t* num_triangles);
 int emf_fusion_follow_shift(const float q[3], const int32_t step[3], float voxel_size, int32_t shift[3]);
+/* Remember what rolls out (new behaviour, off by default; with it off no launch, no output byte and no
+ * checkpoint byte changes).  With the store on, the whole integration tiles (32 x 8 x 8) that a roll moves out of the
+ * background go to host memory as the bytes they are, after the slabs are retired; the tiles that a later roll moves
+ * back in are taken out of the store and written into the rolled volume (tsdf, weights, colour, sign and unseen-tile
+ * entries) before its two copies are made equal, so a camera that returns finds what it left.
+ *   set_background_store   max_bytes: the budget (0: the default, 1 GiB -- a cap, not a measurement).  A tile costs 40
+ *                      bytes plus its literal arrays; a spill that pushes the store past the budget drops whole
+ *                      spills, the oldest first.  Turning the store off drops what it holds.  Refused on the sharded
+ *                      path, as follow is.  With the store on, a roll whose shift, background resolution or
+ *                      background origin is not a multiple of the tile is refused (EMF_E_ARG, nothing changed); every
+ *                      roll of the policy passes.  retired_slabs stays the chronological log it is: a region that
+ *                      leaves twice is logged (and written to bg_retired/) twice.
+ *   background_store_info  out[5]: tiles held, bytes held, tiles spilled, tiles restored, tiles evicted. */
+int emf_fusion_set_background_store(emf_fusion_t* h, int on, uint64_t max_bytes);
+int emf_fusion_background_store_info(emf_fusion_t* h, uint64_t out[5]);
 
 /* Create an object volume (edge vol_size metres, obj_res voxels) centred at `center` in world
  * coordinates; every rank issues the same calls.  *id_out = object id (1-based). */
@@ -427,7 +442,9 @@ int emf_fusion_owns_object(emf_fusion_t* h, int obj_id);
  *                  pose, object table with existence and class bookkeeping, pose logs, the meshes kept of deleted
  *                  objects and every volume (tsdf, weights, fg/bg counts, colour), packed losslessly on the device
  *                  (include/emf_hip.h "Packed buffers") -- to <path>.tmp and renames it to path.  Changes nothing in
- *                  the session.  stats may be NULL.
+ *                  the session.  stats may be NULL.  Format version 1; 2 once the background has rolled; 3 with the
+ *                  background store on (the store travels with the file; checkpoint_info: "stored_tiles",
+ *                  "stored_bytes").
  * load_checkpoint  acts as emf_fusion_reset followed by the restore; allowed at any time.  EMF_E_ARG, with the
  *                  session left as it was, if the file was saved with another frame size, intrinsics, background
  *                  resolution, voxel size or TSDF parameters, or if its magic, version, header checksum, section

@@ -1324,6 +1324,57 @@ int emf_hip_rollVolume(const float* srcTsdf, const float* srcWeights, const uint
                        uint8_t* dstSignMaps, uint8_t* dstUnseenTiles, const int32_t res[3], const int32_t shift[3],
                        emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Storing and restoring tiles (new behaviour: the reference's background never moves).  Opt-in; nothing above is
+ * touched.  Whole integration tiles (32 x 8 x 8 voxels) of a volume whose resolution is a multiple of the tile on
+ * every axis and whose arrays are 16-byte aligned (EMF_E_ARG otherwise) are taken out of a volume, and written back
+ * into one, as the bytes they are.  Words are moved and compared as bits, never interpreted.  Each ARRAY of a tile
+ * (0 tsdf, 1 weights, 2 colour) gets a packed-buffer class of its own:
+ *     class 0  every word is 0x00000000
+ *     class 1  every element equals the same non-zero element; an element is a u32 for tsdf and weights and the
+ *              8-byte voxel for colour (-0.0f, -1.0f under weight 0, the capped weight 64.0f ...)
+ *     class 2  anything else: a LITERAL, 8 KiB for tsdf or weights, 16 KiB for colour, in TILE ORDER: voxel
+ *              (z * 8 + y) * 32 + x of the tile, x fastest
+ * Per tile c:  classes[c][3] u8;  words[c][4] u32 = the first tsdf word, the first weight word, the first colour
+ * voxel's two words (whatever the class; zeros without a colour volume);  lits[c][3] u32 = where array k's literal
+ * starts in the ARENA, in units of 8 KiB (0 for an array that is not a literal).
+ * Nothing allocates, copies to the host or waits.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Bytes of device scratch emf_hip_spillTiles needs for a box of ntiles tiles (4 per 256 tiles, plus 4); 0 above 2^30. */
+size_t emf_hip_spillScratchBytes(uint64_t ntiles);
+
+/* Classify and gather the box of tiles [box_lo, box_lo + box_size) (in TILES, inside the volume: EMF_E_ARG otherwise).
+ * Candidates are numbered x fastest inside the box; classes / words / lits hold one entry per candidate and totals[0]
+ * (one u32) the arena units used.  Literals are placed in candidate order, within a candidate tsdf, weights, colour,
+ * by a scan and never by atomics: two spills of one box give the same bytes.  color may be NULL (classes[c][2] = 0).
+ *   arena == NULL   count only: everything but the arena is written.
+ *   arena != NULL   arena_units (8 KiB each) must cover the box's worst case, box tiles x (colour ? 4 : 2):
+ *                   EMF_E_LIMIT otherwise, with nothing enqueued -- the host moves a big box in several calls.
+ * words must be 16-byte aligned.  A box of zero tiles writes totals[0] = 0 and nothing else.  The source is only
+ * read: once by the classify pass, its literals once more by the gather. */
+int emf_hip_spillTiles(const float* tsdf, const float* weights, const uint16_t* color, const int32_t res[3],
+                       const int32_t box_lo[3], const int32_t box_size[3], void* scratch_dev, uint8_t* classes,
+                       uint32_t* words, uint32_t* lits, uint32_t* totals, void* arena, uint64_t arena_units,
+                       emf_stream_t stream);
+
+/* The inverse, for a list of n destination tiles: coords[i][3] i32 (tile coordinates in the destination volume, on
+ * the device) with classes / words / lits as above (device) and an arena of arena_units units.  One workgroup per
+ * listed tile writes every word of its tsdf and weights, and of its colour when color is given, from zero, the
+ * repeated element or the literal; a tile stored without colour (class 0) gets zero colour, colour data for a
+ * destination without a colour volume is ignored.  Tiles not listed are not touched; a tile must not be listed twice.
+ * With signMaps and unseenTiles given (both or neither: EMF_E_ARG) the tile's three map entries are written from the
+ * values just written -- positive: any tsdf > 0; negative: any tsdf < 0; unseen: every weight == 0.f and every
+ * |tsdf| <= 3.0e38f -- byte for byte what emf_hip_rebuildSignMaps / emf_hip_rebuildUnseenTiles compute.
+ * classes_host: the same n x 3 class bytes in host memory (the caller assembled the list there), read before the
+ * call returns: a class above 2 is EMF_E_ARG with nothing enqueued.  What only the device can see is skipped, never
+ * dereferenced: a tile whose coordinate lies outside the volume, whose device class byte is above 2 or whose literal
+ * does not lie inside the arena is left untouched.  n == 0 launches nothing. */
+int emf_hip_fillTiles(float* tsdf, float* weights, uint16_t* color, uint8_t* signMaps, uint8_t* unseenTiles,
+                      const int32_t res[3], const int32_t* coords, const uint8_t* classes, const uint8_t* classes_host,
+                      const uint32_t* words, const uint32_t* lits, const void* arena, uint64_t arena_units, uint32_t n,
+                      emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
