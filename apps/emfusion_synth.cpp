@@ -4,7 +4,7 @@
 //
 //   emfusion_synth [--frames N] [--objects K] [--bg-res R] [--obj-res R] [--width W --height H]
 //                  [--materialize-gradients] [--autonomous] [--out DIR] [--export-frame-meshes] [--3d-vis]
-//                  [--weld-meshes] [--mesh-min-triangles N] [--mesh-largest-object]
+//                  [--weld-meshes] [--mesh-min-triangles N] [--mesh-largest-object] [--world-mesh]
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
 //                  [--bg-res R] [--bg-voxel M] [--obj-res R] [--volumes] --out DIR
 //   emfusion_synth --dir BASE/ [--colordir colour] [--depthdir depth] [--intrinsics fx fy cx cy] ... --out DIR
@@ -91,6 +91,7 @@ static void set3dView(emf::EMFusion& emf, const emf::Params& params, const View3
 // The reference's main loop on a dataset (apps/EM-Fusion.cpp:100-156): a TUM sequence (`--sequence`, TUMRGBDReader) or a
 // Co-Fusion style directory (`--dir`, ImageReader: ColorNNNN.png + DepthNNNN.exr), as apps/EM-Fusion.cpp:118-131 chooses
 static bool weldMeshes = false;  // --weld-meshes
+static bool worldMeshOut = false;  // --world-mesh: OUT/world.ply, one mesh of the background and its stored tiles
 // --motion-masks [--motion-band M] [--motion-min-pixels N] [--motion-max-masks N]: mask frames propose their own
 // instance masks from the depth in front of the background model (EMFusion::setMotionMasks) instead of reading them
 static bool motionMasks = false;
@@ -100,6 +101,8 @@ static emf::MotionMaskParams motionParams;
 // session's checkpoint carries the switch and its parameters.
 static bool followCamera = false;
 static emf::BackgroundFollowParams followParams;
+// --world-mesh (needs --out): writeResults also writes OUT/world.ply, ONE mesh of the current background and of the tiles
+// the background store holds, without duplicates or seams; without it no output byte changes
 // --follow-store [--follow-store-mib N]: what rolls out is kept on the host and put back when the camera returns
 // (EMFusion::setBackgroundStore); N: the budget in MiB, 1024 by default -- a cap, not a measurement.
 // Needs --follow-camera.
@@ -188,6 +191,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     std::vector<uint8_t> rgb;
     if (!masks.empty()) emf.usePreprocMasks(masks);   // apps/EM-Fusion.cpp:115
     emf.setupOutput(frameMeshes, volumes);            // apps/EM-Fusion.cpp:112
+    emf.setWorldMeshOutput(worldMeshOut);
     set3dView(emf, params, view3d);
     std::vector<uint8_t> rendered(3 * params.frameSize.area());
     const auto t0 = std::chrono::steady_clock::now();
@@ -291,6 +295,7 @@ int main(int argc, char** argv) {
         else if (a == "--3d-vis") view3d.on = true;
         else if (a == "--export-frame-meshes") frameMeshes = true;
         else if (a == "--weld-meshes") weldMeshes = true;
+        else if (a == "--world-mesh") worldMeshOut = true;
         else if (a == "--mesh-min-triangles") meshMinTriangles = static_cast<unsigned>(std::max(next(), 0));
         else if (a == "--mesh-largest-object") meshLargestObject = true;
         else if (a == "--color") color = true;
@@ -391,6 +396,7 @@ int main(int argc, char** argv) {
         if (followCamera) emf.setBackgroundFollow(true, followParams);
         if (followStore) emf.setBackgroundStore(true, static_cast<uint64_t>(followStoreMib) << 20);
         if (!outDir.empty()) emf.setupOutput(frameMeshes, true);  // apps/EM-Fusion.cpp:112
+        emf.setWorldMeshOutput(worldMeshOut);
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);
 

@@ -63,6 +63,9 @@ def main():
                     help="the reference's per-frame mesh export: the background and every shown object meshed at the "
                          "end of every frame, written to OUT/frame_meshes/bg/%%04d.ply and OUT/frame_meshes/<id>/ "
                          "(needs --out)")
+    ap.add_argument("--world-mesh", dest="world_mesh", action="store_true",
+                    help="also write OUT/world.ply: one mesh of the current background and of the tiles the background "
+                         "store holds, without duplicates or seams (needs --out)")
     ap.add_argument("--weld-meshes", dest="weld_meshes", action="store_true",
                     help="weld every mesh written (mesh_*.ply of the live models, frame_meshes/) by grid edge on the "
                          "device: one vertex per edge instead of one per cube that touches it")
@@ -152,7 +155,7 @@ def main():
     fus.set_ignore_person(args.ignore_person)
     fus.set_preprocess(True)
     fus.set_cleanup(True)
-    fus.setup_output(args.frame_meshes, args.volumes)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
+    fus.setup_output(args.frame_meshes, args.volumes, args.world_mesh)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
     if args.vis3d:  # the reference's window (apps/EM-Fusion.cpp:118-131), or a viewer placed with look_at
         R3, t3, K3, size3 = pipeline.default_3d_view(prm)
         if args.vis3d_eye:

@@ -192,6 +192,11 @@ SIGNATURES = {
     "emf_hip_spillScratchBytes": [C.c_uint64],
     "emf_hip_spillTiles": [_FP, _FP, _FP, _I3, _I3, _I3, _FP, _FP, _FP, _FP, _FP, _FP, C.c_uint64, _STREAM],
     "emf_hip_fillTiles": [_FP, _FP, _FP, _FP, _FP, _I3, _FP, _FP, _FP, _FP, _FP, _FP, C.c_uint64, C.c_uint32, _STREAM],
+    "emf_hip_meshTilesScratchBytes": [C.c_uint32],
+    "emf_hip_meshTilesCount": [_FP, C.c_void_p, C.c_uint32, C.c_void_p, _FP, _FP, _STREAM],
+    "emf_hip_meshTilesEmit": [_FP, C.c_uint32, C.c_void_p, _F9, C.c_float, _FP, _FP, _FP, _FP, _STREAM],
+    "emf_hip_meshTilesColors": [_FP, C.c_uint32, C.c_void_p, _FP, _FP, _STREAM],
+    "emf_hip_meshTilesEdgeKeys": [_FP, C.c_uint32, C.c_void_p, _FP, _FP, _STREAM],
 }
 
 
@@ -212,6 +217,21 @@ class EmfModel(C.Structure):
                 ("maxWeight", C.c_float), ("assocC1", C.c_float), ("assocC2", C.c_float),
                 ("alpha", C.c_float), ("assocC3", C.c_float), ("reserved", C.c_int32),
                 ("rcpVoxel", C.c_float), ("pad_", C.c_int32)]
+
+
+class EmfMeshTile(C.Structure):
+    """Mirror of emf_mesh_tile_t (include/emf_hip.h "Meshing a set of tiles"): 88 bytes."""
+
+    _fields_ = [("coord", C.c_int32 * 3), ("cls", C.c_uint8 * 3), ("reserved0", C.c_uint8), ("words", C.c_uint32 * 4),
+                ("nbr", C.c_int32 * 7), ("reserved1", C.c_int32), ("at", C.c_uint64 * 3)]
+
+
+class EmfMeshTilesSource(C.Structure):
+    """Mirror of emf_mesh_tiles_source_t: the arena of the literals and the dense volume of the in-place tiles."""
+
+    _fields_ = [("arena", C.c_void_p), ("arena_units", C.c_uint64), ("tsdf", C.c_void_p), ("weights", C.c_void_p),
+                ("color", C.c_void_p), ("volume_elements", C.c_uint64), ("row_stride", C.c_uint64),
+                ("plane_stride", C.c_uint64)]
 
 
 class EmfPose(C.Structure):
@@ -314,6 +334,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.emf_hip_meshComponentsScratchBytes.restype = C.c_size_t
     lib.emf_hip_packScratchBytes.restype = C.c_size_t
     lib.emf_hip_spillScratchBytes.restype = C.c_size_t
+    lib.emf_hip_meshTilesScratchBytes.restype = C.c_size_t
     lib.emf_hip_motionMasksScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateCullScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateDirtyMapBytes.restype = C.c_size_t

@@ -334,6 +334,23 @@ public:
     void setBackgroundStore(bool on, uint64_t maxBytes = TileStore::kDefaultBudget);
     bool backgroundStoreEnabled() const { return storeOn; }
     const TileStore& backgroundStore() const { return bgStore; }
+    /** What the last worldMesh() was made of. */
+    struct WorldMeshInfo {
+        uint64_t volumeTiles = 0, storedTiles = 0, duplicateTiles = 0, storedSurfaceCubes = 0;
+    };
+    /**
+     * One mesh of what the session has mapped: the tiles of the current background that hold an
+     * observation, in place, plus every tile the background store holds, meshed as ONE lattice by emf_hip_meshTiles*
+     * -- no duplicates, no seams; the current volume wins where both claim a coordinate.  Positions are in the frame
+     * the retired slabs are written in (a never-rolled background gets its own mesh's positions).  weld < 0: the
+     * session's switch; an active component filter implies the weld; colours when the session has colour.  Drains as a
+     * roll does and changes nothing of the session: no volume, map, store, retired slab or checkpoint byte.  Refused
+     * (EMF_E_ARG) on the sharded path and when the background's resolution or origin is not a multiple of the tile.
+     */
+    Mesh worldMesh(int weld = -1);
+    /** writeResults also writes world.ply = writeMesh(worldMesh()); without it no output byte changes. */
+    void setWorldMeshOutput(bool on) { expWorldMesh_ = on; }
+    const WorldMeshInfo& worldMeshInfo() const { return worldInfo; }
     /** Ids returned by initNewObjVolume for FrameInputs::newObjectMasks of the last frame (-1: none). */
     const std::vector<int>& lastCreatedObjects() const { return lastCreated; }
     Affine3f getCameraPose() const { return pose; }
@@ -623,6 +640,7 @@ private:
     void rollBackgroundAt(const Vec3i& shift, int frame, bool keepRetired);
     // ---- the tile store (setBackgroundStore; EMFusionFollow.cpp) ----
     bool storeOn = false;
+    WorldMeshInfo worldInfo;  // of the last worldMesh()
     TileStore bgStore;
     void retireSlabs(const Vec3i& shift, int frame);
     DeviceImage<float> depthFiltered;  // output of preprocessDepth
@@ -659,6 +677,7 @@ private:
     std::map<int, Mesh> meshes;                            // id -> last mesh (deleted objects keep theirs)
     // ---- per-frame meshes (setupOutput's exp_frame_meshes, EMFusionCapture.cpp) ----
     bool expFrameMeshes_ = false;
+    bool expWorldMesh_ = false;  // setWorldMeshOutput: writeResults also writes world.ply
     std::map<int, Mesh> frame_meshes;                      // frame -> background mesh
     std::map<int, std::map<int, Mesh>> frame_obj_meshes;   // id -> frame -> mesh
     void storeFrameMeshes();                               // the end of a frame with exp_frame_meshes

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <map>
 
 namespace emf {
 
@@ -140,6 +141,140 @@ void EMFusion::rollBackgroundAt(const Vec3i& shift, int frame, bool keepRetired)
     rebuildModelTable();  // the copies changed roles; the relevant-tile list; sign maps of the general path
     for (int i = 0; i < 3; ++i) bgOrigin[i] += shift[i];
     bgRolled = true;
+}
+
+Mesh EMFusion::worldMesh(int weld) {
+    if (sharded || world > 1)
+        throw HipError("EMFusion::worldMesh: the world mesh is not supported on the sharded path", EMF_E_ARG);
+    const Vec3i n = background.getVolumeRes();
+    const int32_t none[3] = {0, 0, 0};
+    if (!emf_hip_rollVolumeIsTiled(n.val, none) || !emf_hip_rollVolumeIsTiled(n.val, bgOrigin.val))
+        throw HipError("EMFusion::worldMesh: the background resolution and the background origin must be multiples of the "
+                       "tile (32, 8, 8)",
+                       EMF_E_ARG);
+    // as rollBackgroundAt: nothing of this instance in flight, the front copy current
+    quiesce();
+    refreshVisibleFromDevice();
+    if (bgInFlight) joinBackground();
+    quiesce();
+    const bool filtering = meshFilterActive();
+    const bool welded = filtering || (weld < 0 ? meshWeld : weld > 0);
+    const int nt[3] = {n[0] / kTile[0], n[1] / kTile[1], n[2] / kTile[2]};
+    const size_t volTiles = static_cast<size_t>(nt[0]) * nt[1] * nt[2];
+    // an unseen-tile map of its own, from the front copy: the session's maps, valid or stale, are not touched
+    DeviceBuffer unseenDev((emf_hip_unseenTileBytes(n.val) + 3) / 4 * 4);
+    emfCheck(emf_hip_rebuildUnseenTiles(background.tsdfPtr(), background.weightsPtr(), n.val, unseenDev.as<uint8_t>(), main.abi()),
+             "EMFusion::worldMesh (unseen tiles)");
+    std::vector<uint8_t> unseen(unseenDev.bytes());
+    unseenDev.download(unseen.data(), main);
+    TileGather stored;
+    if (storeOn && !bgStore.empty()) stored = bgStore.gather(main);
+
+    // the table, sorted by (z, y, x) of the lattice tile coordinate
+    const uint16_t* color = background.colorPtr();
+    std::map<std::array<int32_t, 3>, emf_mesh_tile_t> table;  // key (z, y, x)
+    worldInfo = WorldMeshInfo{};
+    const int32_t first[3] = {bgOrigin[0] / kTile[0], bgOrigin[1] / kTile[1], bgOrigin[2] / kTile[2]};
+    for (int z = 0; z < nt[2]; ++z)
+        for (int y = 0; y < nt[1]; ++y)
+            for (int x = 0; x < nt[0]; ++x) {
+                if (unseen[(static_cast<size_t>(z) * nt[1] + y) * nt[0] + x]) continue;
+                emf_mesh_tile_t e{};
+                e.coord[0] = first[0] + x;
+                e.coord[1] = first[1] + y;
+                e.coord[2] = first[2] + z;
+                const uint64_t at = (static_cast<uint64_t>(z) * kTile[2] * n[1] + static_cast<uint64_t>(y) * kTile[1]) * n[0] +
+                                    static_cast<uint64_t>(x) * kTile[0];
+                e.cls[0] = e.cls[1] = 3;
+                e.cls[2] = color ? 3 : 0;
+                e.at[0] = e.at[1] = at;
+                e.at[2] = color ? at : 0;
+                table[{e.coord[2], e.coord[1], e.coord[0]}] = e;
+                ++worldInfo.volumeTiles;
+            }
+    std::vector<std::array<int32_t, 3>> storedKeys;
+    for (size_t i = 0; i < stored.keys.size(); ++i) {
+        const TileKey& k = stored.keys[i];
+        const std::array<int32_t, 3> key{k[2], k[1], k[0]};
+        if (table.count(key)) {  // should not happen: a returned tile is taken out of the store
+            ++worldInfo.duplicateTiles;
+            continue;
+        }
+        emf_mesh_tile_t e{};
+        for (int a = 0; a < 3; ++a) {
+            e.coord[a] = k[a];
+            e.cls[a] = stored.cls[3 * i + a];
+            e.at[a] = stored.at[3 * i + a];
+        }
+        for (int a = 0; a < 4; ++a) e.words[a] = stored.words[4 * i + a];
+        table[key] = e;
+        storedKeys.push_back(key);
+        ++worldInfo.storedTiles;
+    }
+    (void)volTiles;
+    std::vector<emf_mesh_tile_t> tiles;
+    std::map<std::array<int32_t, 3>, int32_t> index;
+    tiles.reserve(table.size());
+    for (const auto& [key, e] : table) {
+        index[key] = static_cast<int32_t>(tiles.size());
+        tiles.push_back(e);
+    }
+    for (emf_mesh_tile_t& e : tiles)
+        for (int k = 1; k < 8; ++k) {
+            const auto it = index.find({e.coord[2] + ((k >> 2) & 1), e.coord[1] + ((k >> 1) & 1), e.coord[0] + (k & 1)});
+            e.nbr[k - 1] = it == index.end() ? -1 : it->second;
+        }
+
+    Mesh mesh;
+    mesh.colored = color != nullptr;
+    const uint32_t count = static_cast<uint32_t>(tiles.size());
+    if (count == 0) return mesh;
+    emf_mesh_tiles_source_t src{};
+    src.arena = stored.arena.empty() ? nullptr : stored.arena.data();
+    src.arena_units = stored.arenaUnits;
+    src.tsdf = background.tsdfPtr();
+    src.weights = background.weightsPtr();
+    src.color = color;
+    src.volume_elements = static_cast<uint64_t>(n[0]) * n[1] * n[2];
+    src.row_stride = n[0];
+    src.plane_stride = static_cast<uint64_t>(n[0]) * n[1];
+    const size_t scratchBytes = emf_hip_meshTilesScratchBytes(count);
+    if (scratchBytes == 0) throw HipError("EMFusion::worldMesh: " + std::to_string(count) + " tiles", EMF_E_LIMIT);
+    DeviceBuffer tilesDev(tiles.size() * sizeof(emf_mesh_tile_t)), scratch(scratchBytes), countsDev(sizeof(emf_mesh_counts_t));
+    tilesDev.upload(tiles.data(), main);
+    emfCheck(emf_hip_meshTilesCount(tilesDev.as<emf_mesh_tile_t>(), tiles.data(), count, &src, scratch.data(),
+                                    countsDev.as<emf_mesh_counts_t>(), main.abi()),
+             "EMFusion::worldMesh (count)");
+    emf_mesh_counts_t counts{};
+    countsDev.download(&counts, main);
+    {  // surface cubes owned by stored tiles: the third array of the scratch
+        std::vector<uint32_t> all(scratchBytes / sizeof(uint32_t));
+        scratch.download(all.data(), main);
+        const uint32_t* cubes = all.data() + 2 * (static_cast<size_t>(count) + 1);
+        for (const auto& key : storedKeys) worldInfo.storedSurfaceCubes += cubes[index[key]];
+    }
+    if (counts.vertices == 0) return mesh;
+    const size_t soup = counts.vertices;
+    const float half[3] = {static_cast<float>(n[0] - 1) / 2.f, static_cast<float>(n[1] - 1) / 2.f, static_cast<float>(n[2] - 1) / 2.f};
+    DeviceBuffer v(soup * 3 * sizeof(float)), nn(soup * 3 * sizeof(float)),
+        t(std::max<size_t>(counts.triangles, 1) * 4 * sizeof(int32_t)), c, keys;
+    emfCheck(emf_hip_meshTilesEmit(tilesDev.as<emf_mesh_tile_t>(), count, &src, half, background.getVoxelSize(), scratch.data(),
+                                   v.as<float>(), nn.as<float>(), t.as<int32_t>(), main.abi()),
+             "EMFusion::worldMesh (emit)");
+    if (color) {
+        c = DeviceBuffer(soup * 3);
+        emfCheck(emf_hip_meshTilesColors(tilesDev.as<emf_mesh_tile_t>(), count, &src, scratch.data(), c.as<uint8_t>(), main.abi()),
+                 "EMFusion::worldMesh (colours)");
+    }
+    if (welded) {
+        keys = DeviceBuffer(soup * sizeof(uint64_t));
+        emfCheck(emf_hip_meshTilesEdgeKeys(tilesDev.as<emf_mesh_tile_t>(), count, &src, scratch.data(), keys.as<uint64_t>(), main.abi()),
+                 "EMFusion::worldMesh (keys)");
+    }
+    main.waitForCompletion();  // the weld and the filter run on the null stream
+    const MeshFilter filter = meshFilterFor(0);
+    return TSDF::finishMesh(std::move(mesh), counts, std::move(v), std::move(nn), std::move(t), std::move(c), std::move(keys),
+                            welded, filtering ? &filter : nullptr);
 }
 
 // The cubes of the old volume with at least one leaving voxel, in at most three disjoint sub-boxes: x first over all

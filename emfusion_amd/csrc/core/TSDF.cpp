@@ -464,13 +464,29 @@ Mesh TSDF::extractMesh(const uint8_t* fgVolMask, bool weld, const MeshFilter* fi
                                     volumeRes.val, scratch.data(), c.as<uint8_t>(), s.abi()),
                  "TSDF::getMesh (colours)");
     }
+    DeviceBuffer keys;
     if (weld) {
-        const size_t weldBytes = emf_hip_meshWeldScratchBytes(soup);
-        if (weldBytes == 0) throw HipError("TSDF::getWeldedMesh: " + std::to_string(soup) + " soup vertices", EMF_E_LIMIT);
-        DeviceBuffer keys(soup * sizeof(uint64_t)), weldScratch(weldBytes), weldedDev(sizeof(uint32_t));
+        keys = DeviceBuffer(soup * sizeof(uint64_t));
         emfCheck(emf_hip_meshEdgeKeys(tsdfVol.as<float>(), tsdfWeights.as<float>(), fgVolMask, volumeRes.val,
                                       scratch.data(), keys.as<uint64_t>(), s.abi()),
                  "TSDF::getWeldedMesh (keys)");
+    }
+    return finishMesh(std::move(mesh), counts, std::move(v), std::move(n), std::move(t), std::move(c), std::move(keys), weld,
+                      filter, stats, components);
+}
+
+// What every mesher here does with its soup on the device (vertices, normals, triangles, colours or an empty buffer,
+// and with `weld` one u64 grid-edge key per vertex): weld, label / filter by component, and bring to the host only
+// what is left.  mesh: the empty result with its `colored` flag set.
+Mesh TSDF::finishMesh(Mesh mesh, emf_mesh_counts_t counts, DeviceBuffer v, DeviceBuffer n, DeviceBuffer t, DeviceBuffer c,
+                      DeviceBuffer keys, bool weld, const MeshFilter* filter, MeshFilterStats* stats,
+                      MeshComponents* components) {
+    Stream& s = Stream::Null();
+    const size_t soup = counts.vertices;
+    if (weld) {
+        const size_t weldBytes = emf_hip_meshWeldScratchBytes(soup);
+        if (weldBytes == 0) throw HipError("TSDF::getWeldedMesh: " + std::to_string(soup) + " soup vertices", EMF_E_LIMIT);
+        DeviceBuffer weldScratch(weldBytes), weldedDev(sizeof(uint32_t));
         emfCheck(emf_hip_meshWeldCount(keys.as<uint64_t>(), soup, weldScratch.data(), weldedDev.as<uint32_t>(), s.abi()),
                  "TSDF::getWeldedMesh (count)");
         uint32_t welded = 0;

@@ -81,6 +81,13 @@ public:
                             Stream& stream = Stream::Null());
 
     /**
+     * The second half of every mesh extraction, on a soup that lies on the device: weld by `keys` (one u64 per vertex,
+     * needed with `weld`), label / filter by connected component, download.  `mesh`: the empty result, `colored` set.
+     */
+    static Mesh finishMesh(Mesh mesh, emf_mesh_counts_t counts, DeviceBuffer v, DeviceBuffer n, DeviceBuffer t, DeviceBuffer c,
+                           DeviceBuffer keys, bool weld, const MeshFilter* filter = nullptr, MeshFilterStats* stats = nullptr,
+                           MeshComponents* components = nullptr);
+    /**
      * Iso-surface of the observed part of the volume (weights > 0), marching cubes on the device
      * (reference TSDF::getMesh, TSDF.cpp:356-373).  Synchronises.
      */

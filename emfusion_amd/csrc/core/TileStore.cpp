@@ -255,4 +255,41 @@ TileFill TileStore::takeFill(const std::vector<TileBox>& boxes, const TileKey& l
     return f;
 }
 
+TileGather TileStore::gather(Stream& stream) {
+    TileGather g;
+    uint64_t units = 0;
+    for (const auto& [key, t] : tiles) {
+        g.keys.push_back(key);
+        g.cls.insert(g.cls.end(), t.cls, t.cls + 3);
+        g.words.insert(g.words.end(), t.words, t.words + 4);
+        uint64_t at = units;
+        for (int a = 0; a < 3; ++a) {
+            g.at.push_back(t.cls[a] == 2 ? at : 0ull);
+            if (t.cls[a] == 2) at += a == 2 ? 2 : 1;
+        }
+        units += unitsOf(t.cls);
+    }
+    g.arenaUnits = units;
+    if (units == 0) return g;
+    g.arena = DeviceBuffer(units * kUnitBytes);
+    // the literals: consecutive tiles share a slab piece (a tile is at most 32 KiB), as takeFill moves them
+    size_t at = 0, held = 0;
+    needSlab(std::min<size_t>(kSlabBytes, std::max<size_t>(units * kUnitBytes, 4096)));
+    auto flush = [&]() {
+        if (!held) return;
+        hipCheck(hipMemcpyAsync(static_cast<char*>(g.arena.data()) + at, slab.data(), held, hipMemcpyHostToDevice, stream.get()), "hipMemcpyAsync H2D");
+        stream.waitForCompletion();
+        at += held;
+        held = 0;
+    };
+    for (const auto& [key, t] : tiles) {
+        if (t.literals.empty()) continue;
+        if (held + t.literals.size() > slab.bytes()) flush();
+        std::memcpy(slab.as<char>() + held, t.literals.data(), t.literals.size());
+        held += t.literals.size();
+    }
+    flush();
+    return g;
+}
+
 }  // namespace emf

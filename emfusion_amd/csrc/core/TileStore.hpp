@@ -44,6 +44,16 @@ struct TileFill {
     uint64_t arenaUnits = 0;
 };
 
+/** Every held tile, read-only, with its literals in one device arena (TileStore::gather). */
+struct TileGather {
+    std::vector<TileKey> keys;    // map order
+    std::vector<uint8_t> cls;     // 3 per tile
+    std::vector<uint32_t> words;  // 4 per tile
+    std::vector<uint64_t> at;     // 3 per tile: the arena unit of a class-2 array, else 0
+    DeviceBuffer arena;
+    uint64_t arenaUnits = 0;
+};
+
 class TileStore {
 public:
     static constexpr uint64_t kRecordBytes = 40;  // what a tile costs besides its literals (its checkpoint header)
@@ -97,6 +107,11 @@ public:
      * next leave -- and upload them as a fill list.  n == 0 if none was found.  Waits for `stream`.
      */
     TileFill takeFill(const std::vector<TileBox>& boxes, const TileKey& lattice, Stream& stream);
+    /**
+     * Every held tile's record, and the literals uploaded into one device arena through the pinned slab.  Read-only:
+     * the tiles, their order and the counters stay exactly as they were.  Waits for `stream`.
+     */
+    TileGather gather(Stream& stream);
 
 private:
     std::map<TileKey, StoredTile> tiles;

@@ -525,6 +525,34 @@ int emf_fusion_retired_slab_mesh(emf_fusion_t* h, int index, uint32_t* num_verti
     });
 }
 
+int emf_fusion_world_mesh(emf_fusion_t* h, int weld, uint32_t* num_vertices, uint32_t* num_triangles) {
+    REQ(h);
+    REQ(num_vertices);
+    REQ(num_triangles);
+    return guarded([&] {
+        h->mesh = h->impl->worldMesh(weld);
+        *num_vertices = static_cast<uint32_t>(h->mesh.vertices());
+        *num_triangles = static_cast<uint32_t>(h->mesh.triangles());
+    });
+}
+
+int emf_fusion_set_world_mesh_output(emf_fusion_t* h, int on) {
+    REQ(h);
+    return guarded([&] { h->impl->setWorldMeshOutput(on != 0); });
+}
+
+int emf_fusion_world_mesh_info(emf_fusion_t* h, uint64_t out[4]) {
+    REQ(h);
+    REQ(out);
+    return guarded([&] {
+        const EMFusion::WorldMeshInfo& i = h->impl->worldMeshInfo();
+        out[0] = i.volumeTiles;
+        out[1] = i.storedTiles;
+        out[2] = i.duplicateTiles;
+        out[3] = i.storedSurfaceCubes;
+    });
+}
+
 int emf_fusion_follow_shift(const float q[3], const int32_t step[3], float voxel_size, int32_t shift[3]) {
     REQ(q);
     REQ(step);

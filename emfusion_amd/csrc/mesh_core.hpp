@@ -36,6 +36,25 @@ __device__ __forceinline__ V3 vertex_interp(const V3& p1, const V3& p2, float v1
     return p1 + d * mu;
 }
 
+// The colour of the vertex on an edge whose endpoints hold the voxels c[0], c[1] (R, G, B in 1/256 levels, Wc) and the
+// values v1, v2: an uncoloured endpoint (Wc == 0) contributes the other endpoint's colour; both: black.  Interpolated
+// like the position, with contraction off whatever the build says, then rounded to u8.
+__device__ __forceinline__ void edge_colour(ushort4 c0, ushort4 c1, float v1, float v2, uint8_t* o) {
+#pragma clang fp contract(off)
+    if (c0.w == 0) c0 = c1;
+    if (c1.w == 0) c1 = c0;
+    const bool none = c0.w == 0;
+    float mu;
+    const int take = vertex_interp_mu(v1, v2, mu);
+    const unsigned short a[3] = {c0.x, c0.y, c0.z}, b[3] = {c1.x, c1.y, c1.z};
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float c1f = static_cast<float>(a[j]) / 256.f, c2f = static_cast<float>(b[j]) / 256.f;
+        const float v = take == 1 ? c1f : (take == 2 ? c2f : c1f + mu * (c2f - c1f));
+        o[j] = none ? 0 : static_cast<uint8_t>(fminf(fmaxf(rintf(v), 0.f), 255.f));
+    }
+}
+
 // corner i of cube (x, y, z) in the reference's numbering (TSDF.cu:896-903): x + (i ^ (i >> 1)) & 1,
 // z + (i >> 1) & 1, y + (i >> 2) & 1
 __device__ __forceinline__ void cube_corner(int i, int& dx, int& dy, int& dz) {

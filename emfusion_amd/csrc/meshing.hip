@@ -573,7 +573,6 @@ struct MeshColorArgs {
 
 __device__ __forceinline__ void color_cube(const MeshSource& src, const ushort4* vol, const Cube& q, unsigned edges,
                                            unsigned vertBase, uint8_t* colors) {
-#pragma clang fp contract(off)
     const I3 n = src.n;
     const size_t sy = static_cast<size_t>(n.x), sz = sy * n.y;
     unsigned k = 0;
@@ -590,20 +589,7 @@ __device__ __forceinline__ void color_cube(const MeshSource& src, const ushort4*
             val[s] = src.tsdf[idx];
             c[s] = vol ? vol[idx] : make_ushort4(0, 0, 0, 0);
         }
-        // an uncoloured endpoint (Wc == 0) contributes the other endpoint's colour; both: black
-        if (c[0].w == 0) c[0] = c[1];
-        if (c[1].w == 0) c[1] = c[0];
-        const bool none = c[0].w == 0;
-        float mu;
-        const int take = vertex_interp_mu(val[0], val[1], mu);
-        const unsigned short a[3] = {c[0].x, c[0].y, c[0].z}, b[3] = {c[1].x, c[1].y, c[1].z};
-        uint8_t* o = colors + 3 * static_cast<size_t>(vertBase + k);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const float c1 = static_cast<float>(a[j]) / 256.f, c2 = static_cast<float>(b[j]) / 256.f;
-            const float v = take == 1 ? c1 : (take == 2 ? c2 : c1 + mu * (c2 - c1));
-            o[j] = none ? 0 : static_cast<uint8_t>(fminf(fmaxf(rintf(v), 0.f), 255.f));
-        }
+        edge_colour(c[0], c[1], val[0], val[1], colors + 3 * static_cast<size_t>(vertBase + k));
         ++k;
     }
 }

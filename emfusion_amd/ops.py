@@ -1073,6 +1073,107 @@ def extract_mesh(tsdf, weights, voxel_size, fg_mask=None, grads=None, stream=Non
     return verts.numpy()[:nv], norms.numpy()[:nv], tris.numpy()[:nt]
 
 
+def mesh_tile_table(coords, classes, words, at, neighbours=None):
+    """The emf_mesh_tile_t table of n tiles as a ctypes array: coords (n, 3) i32 lattice tile coordinates (x, y, z),
+    classes (n, 3) u8, words (n, 4) u32, at (n, 3) u64 (class 2: arena unit, class 3: element offset).  neighbours:
+    (n, 7) i32, or None to look them up by coordinate."""
+    coords = np.asarray(coords, np.int64).reshape(-1, 3)
+    n = coords.shape[0]
+    classes = np.asarray(classes, np.uint8).reshape(n, 3)
+    words = np.asarray(words, np.uint32).reshape(n, 4)
+    at = np.asarray(at, np.uint64).reshape(n, 3)
+    if neighbours is None:
+        index = {tuple(int(v) for v in c): i for i, c in enumerate(coords)}
+        neighbours = np.full((n, 7), -1, np.int32)
+        for i, c in enumerate(coords):
+            for k in range(1, 8):
+                key = (int(c[0]) + (k & 1), int(c[1]) + ((k >> 1) & 1), int(c[2]) + (k >> 2))
+                neighbours[i, k - 1] = index.get(key, -1)
+    neighbours = np.asarray(neighbours, np.int32).reshape(n, 7)
+    table = (_lib.EmfMeshTile * max(n, 1))()
+    for i in range(n):
+        e = table[i]
+        e.coord[:] = [int(v) for v in coords[i]]
+        e.cls[:] = [int(v) for v in classes[i]]
+        e.words[:] = [int(v) for v in words[i]]
+        e.nbr[:] = [int(v) for v in neighbours[i]]
+        e.at[:] = [int(v) for v in at[i]]
+    return table
+
+
+def mesh_tiles(tiles, voxel_size, half, weld=False, colors=False, min_triangles=0, keys=False, stream=None):
+    """emf_hip_meshTilesCount / ...Emit[/ ...Colors / ...EdgeKeys] (include/emf_hip.h "Meshing a set of tiles"): the
+    mesh of the dense volume that holds exactly the listed tiles.  tiles: dict(coords (n, 3) lattice tile coordinates
+    (x, y, z), sorted ascending in (z, y, x); classes (n, 3) u8; words (n, 4) u32; at (n, 3): the arena unit of a
+    class-2 array, the element offset of a class-3 one; arena: (units, 8192) u8 numpy or None; volume: None or
+    dict(tsdf, weights[, color]) -- numpy (Nz, Ny, Nx) volumes that class 3 reads in place; neighbours: optional
+    (n, 7) i32 instead of the lookup by coordinate).  half: the three floats a lattice voxel is shifted by.  Returns
+    (vertices (n, 3) f32, normals (n, 3) f32, triangles (m, 4) i32[, colours (n, 3) u8][, keys (n,) u64]) as numpy
+    arrays with global indices; weld / min_triangles as in extract_mesh (the keys are then not returned)."""
+    if int(min_triangles) > 1 and not weld:
+        raise ValueError("mesh_tiles: the component filter works on the welded mesh (weld=True)")
+    table = mesh_tile_table(tiles["coords"], tiles["classes"], tiles["words"], tiles["at"], tiles.get("neighbours"))
+    n = int(np.asarray(tiles["coords"]).reshape(-1, 3).shape[0])
+    src = _lib.EmfMeshTilesSource()
+    arena = tiles.get("arena")
+    d_arena = None
+    if arena is not None and np.asarray(arena).size:
+        d_arena = DeviceArray.from_numpy(np.ascontiguousarray(arena, np.uint8).reshape(-1, TILE_UNIT))
+        src.arena, src.arena_units = d_arena.ptr, d_arena.nbytes // TILE_UNIT
+    vol = tiles.get("volume")
+    d_vol = []
+    if vol is not None:
+        nz, ny, nx = vol["tsdf"].shape
+        d_vol = [DeviceArray.from_numpy(np.ascontiguousarray(vol["tsdf"], np.float32)),
+                 DeviceArray.from_numpy(np.ascontiguousarray(vol["weights"], np.float32))]
+        src.tsdf, src.weights = d_vol[0].ptr, d_vol[1].ptr
+        if vol.get("color") is not None:
+            d_vol.append(DeviceArray.from_numpy(np.ascontiguousarray(vol["color"], np.uint16)))
+            src.color = d_vol[2].ptr
+        src.volume_elements, src.row_stride, src.plane_stride = nz * ny * nx, nx, nx * ny
+    d_table = DeviceArray.from_numpy(np.frombuffer(table, np.uint8).copy()) if n else None
+    scratch = DeviceArray.zeros((max(int(_L.emf_hip_meshTilesScratchBytes(n)) // 4, 2),), np.uint32)
+    counts = DeviceArray.zeros((2,), np.uint32)
+    check("emf_hip_meshTilesCount",
+          _L.emf_hip_meshTilesCount(_ptr(d_table), C.cast(table, C.c_void_p), n, C.byref(src), _ptr(scratch),
+                                    _ptr(counts), _stream(stream)))
+    nv, nt = (int(v) for v in counts.numpy())
+    verts = DeviceArray.zeros((max(nv, 1), 3), np.float32)
+    norms = DeviceArray.zeros((max(nv, 1), 3), np.float32)
+    tris = DeviceArray.zeros((max(nt, 1), 4), np.int32)
+    if nv:
+        check("emf_hip_meshTilesEmit",
+              _L.emf_hip_meshTilesEmit(_ptr(d_table), n, C.byref(src), _f(half, 3), voxel_size, _ptr(scratch), _ptr(verts),
+                                       _ptr(norms), _ptr(tris), _stream(stream)))
+    cols = None
+    if colors:
+        cols = DeviceArray.zeros((max(nv, 1), 3), np.uint8)
+        if nv:
+            check("emf_hip_meshTilesColors",
+                  _L.emf_hip_meshTilesColors(_ptr(d_table), n, C.byref(src), _ptr(scratch), _ptr(cols), _stream(stream)))
+    d_keys = None
+    if weld or keys:
+        d_keys = DeviceArray.zeros((max(nv, 1),), np.uint64)
+        if nv:
+            check("emf_hip_meshTilesEdgeKeys",
+                  _L.emf_hip_meshTilesEdgeKeys(_ptr(d_table), n, C.byref(src), _ptr(scratch), _ptr(d_keys),
+                                               _stream(stream)))
+    if weld:
+        verts, norms, tris, cols, cnt, _, _ = _weld(d_keys, nv, nt, verts, norms, tris, cols, stream=stream)
+        nv = int(cnt[0])
+        if int(min_triangles) > 1:
+            verts, norms, tris, cols, kcnt, _, _ = _filter(nv, nt, verts, norms, tris if nt else None, cols, min_triangles,
+                                                           False, stream=stream)
+            nv, nt = int(kcnt[0, 0]), int(kcnt[0, 1])
+    synchronize()  # the uploads are released on return
+    out = (verts.numpy()[:nv], norms.numpy()[:nv], tris.numpy()[:nt])
+    if colors:
+        out += (cols.numpy()[:nv],)
+    if keys and not weld:
+        out += (d_keys.numpy()[:nv],)
+    return out
+
+
 def mesh_table(volumes):
     """The device model table (only what meshing reads) and the host resolutions of extract_meshes' volumes."""
     n = len(volumes)

@@ -125,6 +125,9 @@ def load() -> C.CDLL:
         "emf_fusion_background_origin": [vp, ip, fp, fp],
         "emf_fusion_retired_slabs": [vp, C.c_void_p, C.c_int, ip],
         "emf_fusion_retired_slab_mesh": [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+        "emf_fusion_world_mesh": [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+        "emf_fusion_world_mesh_info": [vp, C.c_void_p],
+        "emf_fusion_set_world_mesh_output": [vp, C.c_int],
         "emf_fusion_follow_shift": [fp, ip, C.c_float, ip],
         "emf_fusion_process_rgbd_color": [vp, fp, C.c_void_p, C.c_int32, C.c_int32],
         "emf_fusion_colored_voxels": [vp, C.POINTER(C.c_uint64)],
@@ -712,6 +715,31 @@ class Fusion:
             out.append(slab)
         return out
 
+    def world_mesh(self, weld=None, colors=False):
+        """ONE mesh of what the session has mapped: the current background's observed tiles plus the
+        tiles the background store holds, meshed as one lattice -- no duplicates, no seams.  (vertices (n, 3), normals
+        (n, 3), triangles (m, 4)[, colours (n, 3) u8]) in the frame retired_slabs() are written in.  weld None: the
+        session's switch; an active set_mesh_filter implies the weld.  Changes nothing of the session."""
+        nv, nt = C.c_uint32(), C.c_uint32()
+        _check("emf_fusion_world_mesh",
+               load().emf_fusion_world_mesh(self._h, -1 if weld is None else int(bool(weld)), C.byref(nv), C.byref(nt)))
+        v, nr = np.empty((nv.value, 3), np.float32), np.empty((nv.value, 3), np.float32)
+        t = np.empty((nt.value, 4), np.int32)
+        _check("emf_fusion_copy_mesh", load().emf_fusion_copy_mesh(self._h, v.ctypes.data, nr.ctypes.data, t.ctypes.data))
+        if not colors:
+            return v, nr, t
+        c = np.empty((nv.value, 3), np.uint8)
+        if nv.value:
+            _check("emf_fusion_copy_mesh_colors", load().emf_fusion_copy_mesh_colors(self._h, c.ctypes.data))
+        return v, nr, t, c
+
+    def world_mesh_info(self):
+        """Of the last world_mesh(): dict(volume_tiles, stored_tiles, duplicate_tiles, stored_surface_cubes)."""
+        out = np.zeros(4, np.uint64)
+        _check("emf_fusion_world_mesh_info", load().emf_fusion_world_mesh_info(self._h, out.ctypes.data))
+        return dict(volume_tiles=int(out[0]), stored_tiles=int(out[1]), duplicate_tiles=int(out[2]),
+                    stored_surface_cubes=int(out[3]))
+
     def last_motion_masks(self):
         """The proposals of the last processed frame: ((H, W) i32 image of proposal ranks, -1 where none is, list of
         dicts {label, area, x0, y0, x1, y1} by rank).  Empty / all -1 if the frame proposed nothing."""
@@ -906,12 +934,14 @@ class Fusion:
     def enable_pose_log(self, on=True):
         _check("emf_fusion_enable_pose_log", load().emf_fusion_enable_pose_log(self._h, int(on)))
 
-    def setup_output(self, exp_frame_meshes=False, exp_vols=False):
+    def setup_output(self, exp_frame_meshes=False, exp_vols=False, exp_world_mesh=False):
         """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
         the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
-        the sharded path)."""
+        the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh()."""
         _check("emf_fusion_setup_output",
                load().emf_fusion_setup_output(self._h, int(exp_frame_meshes), int(exp_vols)))
+        _check("emf_fusion_set_world_mesh_output",
+               load().emf_fusion_set_world_mesh_output(self._h, int(bool(exp_world_mesh))))
 
     def write_results(self, directory: str, volumes: bool = True):
         """poses-*.txt, mesh_bg.ply, mesh_<id>.ply always; tsdfs/*.bin with `volumes` (reference formats)."""

@@ -202,6 +202,20 @@ int emf_fusion_roll_background(emf_fusion_t* h, const int32_t shift[3], int keep
 int emf_fusion_background_origin(emf_fusion_t* h, int32_t origin[3], float R[9], float t[3]);
 int emf_fusion_retired_slabs(emf_fusion_t* h, int32_t* info, int capacity, int32_t* count);
 int emf_fusion_retired_slab_mesh(emf_fusion_t* h, int index, uint32_t* num_vertices, uint32_t* num_triangles);
+/* The world mesh: ONE mesh of the current background's observed tiles and of every tile the
+ * background store holds, meshed as one lattice -- no duplicates, no seams, the current volume winning where both
+ * claim a tile.  It becomes the mesh that emf_fusion_copy_mesh / emf_fusion_copy_mesh_colors copy, as
+ * retired_slab_mesh's does.  weld < 0: the session's switch (emf_fusion_set_mesh_weld); an active component filter
+ * implies the weld.  Nothing of the session changes.  EMF_E_ARG on a sharded session and when the background's
+ * resolution or origin is not a multiple of the tile (32, 8, 8). */
+int emf_fusion_world_mesh(emf_fusion_t* h, int weld, uint32_t* num_vertices, uint32_t* num_triangles);
+/* Of the last world mesh: tiles taken from the volume, tiles taken from the store, stored tiles skipped because the
+ * volume holds their coordinate, surface cubes owned by stored tiles. */
+int emf_fusion_world_mesh_info(emf_fusion_t* h, uint64_t out[4]);
+/* setup_output's exp_world_mesh, as an entry of its own so that emf_fusion_setup_output keeps its signature:
+ * emf_fusion_write_results also writes world.ply, the PLY of the world mesh at that moment, byte for byte
+ * emf_io_write_mesh of it, and nothing else new.  Off (the default): no output byte changes. */
+int emf_fusion_set_world_mesh_output(emf_fusion_t* h, int on);
 int emf_fusion_follow_shift(const float q[3], const int32_t step[3], float voxel_size, int32_t shift[3]);
 /* Remember what rolls out (new behaviour, off by default; with it off no launch, no output byte and no
  * checkpoint byte changes).  With the store on, the whole integration tiles (32 x 8 x 8) that a roll moves out of the

@@ -1375,6 +1375,87 @@ int emf_hip_fillTiles(float* tsdf, float* weights, uint16_t* color, uint8_t* sig
                       const uint32_t* words, const uint32_t* lits, const void* arena, uint64_t arena_units, uint32_t n,
                       emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Meshing a set of tiles (new behaviour: DESIGN.md 5.16).  Opt-in; nothing above is touched.  Marching cubes over a
+ * SPARSE set of integration tiles (32 x 8 x 8 voxels) on one integer lattice instead of a dense volume: the result is
+ * the mesh of the dense volume that holds exactly these tiles and is unobserved (tsdf 0, weight 0) everywhere else.
+ *   ownership   the cube anchored at voxel v belongs to the tile that contains v
+ *   validity    all 8 corners have weights > 0 (no foreground mask)
+ *   geometry    class, edge order, vertexInterp, triangle table and the (3, i0, i1, i2) records of emf_hip_meshEmit
+ *   normals     the interpolated raw forward differences of the corner voxels; the difference reads the next voxel in
+ *               whatever tile it lies and 0 where there is none -- a tile set has no "last plane"
+ *   positions   a corner is (float(lattice voxel) - half) * voxelSize per axis; the caller passes half
+ *   colours     the rule of emf_hip_meshColors; an array absent from a tile (class 0) counts as uncoloured
+ *   order       tiles in table order; within a tile its 2048 cubes in (z, y, x) order of their anchor; within a cube
+ *               vertices in edge-bit order and triangles in table order.  Triangle indices are GLOBAL u32.
+ * The table: n emf_mesh_tile_t sorted by lattice tile coordinate, strictly ascending in (z, y, x).  Per array (0 tsdf,
+ * 1 weights, 2 colour) a class: 0, 1, 2 as in "Storing and restoring tiles" (1: words[]; 2: at[k] = the literal's
+ * arena unit of 8 KiB), and
+ *     class 3  in place in a dense volume: at[k] = the element offset of the tile's first voxel in
+ *              emf_mesh_tiles_source_t's arrays (a multiple of 4), rows and planes row_stride / plane_stride apart
+ * nbr[k - 1], k = 1 .. 7: the table index of the tile at +(k & 1, k >> 1 & 1, k >> 2) tiles, or -1.  The host fills
+ * them; a tile that is not listed is unobserved.
+ * What the host can see is refused before any launch (emf_hip_meshTilesCount reads tiles_host, the same n entries in
+ * host memory): a class above 3, a coordinate that is not strictly ascending, a neighbour index outside [-1, n) or
+ * one that names a tile at another coordinate (EMF_E_ARG); an arena or a volume array that is not 16-byte aligned, a
+ * stride that is not a multiple of 4 (EMF_E_ARG); literals without an arena or class 3 without a volume (EMF_E_NULL);
+ * a tile with a lattice VOXEL coordinate outside [-2^19, 2^19) or n > 2^17 (EMF_E_LIMIT).  What only the device sees
+ * skips the tile -- it counts as not listed, as an owner and as a neighbour -- and is never dereferenced: a literal
+ * outside the arena, an in-place offset (not a multiple of 4, or) whose tile does not lie inside volume_elements, a
+ * class above 3, a neighbour whose coordinate is not the one the index stands for.  A tile is skipped as a whole
+ * when ANY of its three arrays fails: a colour literal outside the arena removes the tile's geometry too, also from
+ * a mesh made without colours -- the same tiles count in every pass, so the passes always agree on the vertex slots.
+ * ---------------------------------------------------------------------------------------------- */
+
+typedef struct emf_mesh_tile {
+    int32_t coord[3];  /* lattice tile coordinate (x, y, z) */
+    uint8_t cls[3];    /* class of tsdf, weights, colour */
+    uint8_t reserved0;
+    uint32_t words[4]; /* class 1: the tsdf word, the weight word, the colour voxel's two words */
+    int32_t nbr[7];
+    int32_t reserved1;
+    uint64_t at[3];    /* class 2: arena unit; class 3: element offset */
+} emf_mesh_tile_t;     /* 88 bytes */
+
+typedef struct emf_mesh_tiles_source {
+    const void* arena;        /* literals (device), or NULL */
+    uint64_t arena_units;     /* its size in units of 8 KiB */
+    const float* tsdf;        /* the dense volume of class 3 (device), or NULL */
+    const float* weights;
+    const uint16_t* color;    /* u16 x 4 per voxel, or NULL */
+    uint64_t volume_elements; /* voxels each of the three arrays holds */
+    uint64_t row_stride;      /* voxels from (x, y, z) to (x, y + 1, z) */
+    uint64_t plane_stride;    /* voxels from (x, y, z) to (x, y, z + 1) */
+} emf_mesh_tiles_source_t;
+
+/* Bytes of device scratch the four calls below share for a table of n tiles (12 per tile, plus 8); 0 above 2^17.
+ * After emf_hip_meshTilesCount it holds three u32 arrays: [n + 1] the first vertex of every tile and the total,
+ * [n + 1] the same for triangles, [n] the surface cubes each tile owns. */
+size_t emf_hip_meshTilesScratchBytes(uint32_t n);
+
+/* Pass 1: one workgroup per listed tile counts its vertices and triangles; one workgroup scans the per-tile totals
+ * (mesh_scan.hpp: no atomics) and writes the totals to counts_dev (device).  n == 0 writes zero counts. */
+int emf_hip_meshTilesCount(const emf_mesh_tile_t* tiles_dev, const emf_mesh_tile_t* tiles_host, uint32_t n,
+                           const emf_mesh_tiles_source_t* source, void* scratch_dev, emf_mesh_counts_t* counts_dev,
+                           emf_stream_t stream);
+
+/* Pass 2, after the count on the same table, source and scratch: 3 floats per vertex twice and 4 int32 per triangle,
+ * sized by the counts.  half: HOST float[3]. */
+int emf_hip_meshTilesEmit(const emf_mesh_tile_t* tiles_dev, uint32_t n, const emf_mesh_tiles_source_t* source,
+                          const float half[3], float voxelSize, const void* scratch_dev, float* vertices, float* normals,
+                          int32_t* triangles, emf_stream_t stream);
+
+/* u8 x 3 per vertex, in the emit's vertex order (the same scratch). */
+int emf_hip_meshTilesColors(const emf_mesh_tile_t* tiles_dev, uint32_t n, const emf_mesh_tiles_source_t* source,
+                            const void* scratch_dev, uint8_t* colors, emf_stream_t stream);
+
+/* One u64 per vertex, in the emit's vertex order: the key of the grid edge the vertex lies on,
+ *     3 * (((z + 2^19) << 40) | ((y + 2^19) << 20) | (x + 2^19)) + axis
+ * of the edge's lower LATTICE voxel (x, y, z).  It is below 2^62, hence never the weld table's empty key; the keys and
+ * the soup go unchanged into emf_hip_meshWeldCount / ...Emit and emf_hip_meshComponents* as one model. */
+int emf_hip_meshTilesEdgeKeys(const emf_mesh_tile_t* tiles_dev, uint32_t n, const emf_mesh_tiles_source_t* source,
+                              const void* scratch_dev, uint64_t* keys, emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
