@@ -687,10 +687,18 @@ def preprocess_depth(raw, out, ksz=7, sigma_depth=0.04, sigma_spatial=4.5, strea
 
 # ---- object creation / matching from masks (SURVEY f-3) ------------------------------------------
 
-def masked_point_stats(points, mask, R, t, stream=None):
-    """(count, p10[3], p90[3]) of the valid masked points after x' = R x + t (synchronises)."""
-    scratch = DeviceArray.zeros((int(_L.emf_hip_pointStatsScratchBytes()) // 4,), np.uint32)
-    out = DeviceArray.zeros((7,), np.float32)
+def _stats_buffers(buffers):
+    """(scratch, out) of the point statistics: fresh and zeroed, or the caller's pair (any contents)."""
+    if buffers is not None:
+        return buffers
+    return (DeviceArray.zeros((int(_L.emf_hip_pointStatsScratchBytes()) // 4,), np.uint32),
+            DeviceArray.zeros((7,), np.float32))
+
+
+def masked_point_stats(points, mask, R, t, stream=None, buffers=None):
+    """(count, p10[3], p90[3]) of the valid masked points after x' = R x + t (synchronises).  buffers: None, or
+    the (scratch uint32[emf_hip_pointStatsScratchBytes / 4], out float32[7]) device arrays to use."""
+    scratch, out = _stats_buffers(buffers)
     check("emf_hip_maskedPointStats",
           _L.emf_hip_maskedPointStats(C.byref(image_view(points)), C.byref(image_view(mask)), _f(R, 9),
                                       _f(t, 3), _ptr(scratch), _ptr(out), _stream(stream)))
@@ -708,9 +716,11 @@ def mask_overlap(seg, model_seg, stream=None):
     return int(c[0]), c[1:257].copy(), c[257:513].copy()
 
 
-def mask_association_mass(obj_seg, match_mask, assoc, stream=None):
-    """(count, sum) of cleanUpObjs' association test; match_mask may be None (synchronises)."""
-    out = DeviceArray.zeros((int(_L.emf_hip_maskAssociationMassBytes()) // 8,), np.float64)
+def mask_association_mass(obj_seg, match_mask, assoc, stream=None, out=None):
+    """(count, sum) of cleanUpObjs' association test; match_mask may be None (synchronises).  out: None, or the
+    float64[emf_hip_maskAssociationMassBytes / 8] device array to use (any contents)."""
+    if out is None:
+        out = DeviceArray.zeros((int(_L.emf_hip_maskAssociationMassBytes()) // 8,), np.float64)
     check("emf_hip_maskAssociationMass",
           _L.emf_hip_maskAssociationMass(C.byref(image_view(obj_seg)), _opt_view(match_mask),
                                          C.byref(image_view(assoc)), _ptr(out), _stream(stream)))
@@ -728,10 +738,10 @@ def carve_mask(seg, model_seg, obj_id, match_mask=None, stream=None):
     return int(c[0]), int(c[1])
 
 
-def object_extent_stats(points, mask, R, t, tsdf, weights, fg_mask, voxel_size, stream=None):
-    """updateObj's statistics: masked points (R x + t) plus the object's iso-surface vertex cloud."""
-    scratch = DeviceArray.zeros((int(_L.emf_hip_pointStatsScratchBytes()) // 4,), np.uint32)
-    out = DeviceArray.zeros((7,), np.float32)
+def object_extent_stats(points, mask, R, t, tsdf, weights, fg_mask, voxel_size, stream=None, buffers=None):
+    """updateObj's statistics: masked points (R x + t) plus the object's iso-surface vertex cloud.  buffers: as in
+    masked_point_stats."""
+    scratch, out = _stats_buffers(buffers)
     check("emf_hip_objectExtentStats",
           _L.emf_hip_objectExtentStats(C.byref(image_view(points)), C.byref(image_view(mask)), _f(R, 9),
                                        _f(t, 3), _ptr(tsdf), _ptr(weights), _ptr(fg_mask), _res(tsdf),
@@ -1246,11 +1256,12 @@ def extract_meshes(volumes, stream=None, weld=False, min_triangles=0, largest_on
     return _slices(verts, norms, tris, cols, vbase, vcnt, bs[:, 1], cnt[:, 1], n)
 
 
-def mask_association_masses(hit_masks, assocs, match_masks=None, verdict=None, stream=None):
+def mask_association_masses(hit_masks, assocs, match_masks=None, verdict=None, stream=None, seed_byte=0):
     """emf_hip_maskAssociationMassBatched: cleanUpObjs' (count, sum) for n objects in one pass over a model table.
     hit_masks / assocs: n unpadded device images (u8 / f32 W x H), the objects' raycast masks and association weights,
     placed at table slots 1 .. n behind an empty slot 0 (as in the product's table); match_masks: None or n entries,
-    each a device image or None.  verdict: None, or dict(nall=, list_pos=[n ints], visible=[n 0/1], ex_low=[n 0/1],
+    each a device image or None.  seed_byte: what every byte of the scratch and the answers holds before the call.
+    verdict: None, or dict(nall=, list_pos=[n ints], visible=[n 0/1], ex_low=[n 0/1],
     assoc_thresh=) for the delete verdicts by list position.  Returns (counts (n,) uint32, sums (n,) float64,
     verdicts (round_up(nall, 4),) float32 or None); synchronises."""
     n = len(hit_masks)
@@ -1270,6 +1281,9 @@ def mask_association_masses(hit_masks, assocs, match_masks=None, verdict=None, s
             imgs[k] = image_view(mm)
     scratch = DeviceArray.zeros((max(int(_L.emf_hip_maskAssociationMassScratchBytes(n)) // 8, 2),), np.float64)
     out = DeviceArray.zeros((max(n, 1), 2), np.float64)
+    if seed_byte:
+        scratch.fill_bytes_(seed_byte)
+        out.fill_bytes_(seed_byte)
     vd, nall, lp, vis, ex, thr = None, 0, None, None, None, 0.0
     if verdict is not None:
         nall = int(verdict["nall"])

@@ -5,6 +5,7 @@ EMFusion::matchSegmentation (EMFusion.cpp:797-825)."""
 import numpy as np
 import pytest
 
+from tests.lifecycle_cases import f32_transform, mesh_cloud, sorted_stats
 from tests.parity_util import dev_full, to_dev
 from tests.scenes import Pose, camera_path, intrinsics, render_depth, rot
 
@@ -18,22 +19,6 @@ SPHERES = [((0.25, 0.05, 1.3), 0.22), ((-0.3, -0.1, 1.6), 0.18)]
 def ops(dev):
     from emfusion_amd import ops as _ops
     return _ops
-
-
-def sorted_stats(points, mask, R, t):
-    """The reference's way: compact, transform, sort each channel, take two columns."""
-    f32 = np.float32
-    valid = (mask != 0) & np.any(points != 0, axis=2)
-    p = points[valid].astype(f32)
-    n = len(p)
-    if n == 0:
-        return 0, np.zeros(3, f32), np.zeros(3, f32)
-    R = np.asarray(R, f32).reshape(3, 3)
-    q = np.empty_like(p)
-    for i in range(3):  # (r0 x + r1 y) + r2 z, then + t: the product's operation order
-        q[:, i] = f32(f32(f32(R[i, 0] * p[:, 0]) + f32(R[i, 1] * p[:, 1])) + f32(R[i, 2] * p[:, 2])) + f32(t[i])
-    s = np.sort(q, axis=0)
-    return n, s[int(f32(n) * f32(.1))], s[int(f32(n) * f32(.9))]
 
 
 @pytest.mark.parametrize("case", ["sphere", "rotated", "empty", "single", "negative", "padded"])
@@ -327,38 +312,6 @@ def test_instance_masks_run_the_reference_control_flow(oracle, dev):
 
 # ---- updateObj / resize: iso-surface vertex cloud + points, copyValues ------------------------------
 
-def mesh_cloud(tsdf, weights, fg, voxel):
-    """Vertex cloud of the reference's marching cubes (TSDF.cu:855-1152, ObjTSDF.cpp:247-268) in numpy:
-    one vertex per sign-changing edge of every cube whose 8 voxels pass the mask, vertexInterp."""
-    f32 = np.float32
-    nz, ny, nx = tsdf.shape
-    ok = weights > 0 if fg is None else (weights > 0) & (fg != 0)
-    corner = [(0, 0, 0), (1, 0, 0), (1, 0, 1), (0, 0, 1), (0, 1, 0), (1, 1, 0), (1, 1, 1), (0, 1, 1)]  # dx, dy, dz
-    sub = lambda a, c: a[c[2]:nz - 1 + c[2], c[1]:ny - 1 + c[1], c[0]:nx - 1 + c[0]]
-    valid = np.ones((nz - 1, ny - 1, nx - 1), bool)
-    for c in corner:
-        valid &= sub(ok, c)
-    zz, yy, xx = np.meshgrid(np.arange(nz - 1), np.arange(ny - 1), np.arange(nx - 1), indexing="ij")
-    half = [f32(n - 1) / f32(2) for n in (nx, ny, nz)]
-    pos = lambda c: np.stack([(f32(1) * (xx + c[0]).astype(f32) - half[0]) * f32(voxel),
-                              ((yy + c[1]).astype(f32) - half[1]) * f32(voxel),
-                              ((zz + c[2]).astype(f32) - half[2]) * f32(voxel)], -1).astype(f32)
-    out = []
-    for a, b in [(0, 1), (1, 2), (2, 3), (3, 0), (4, 5), (5, 6), (6, 7), (7, 4), (0, 4), (1, 5), (2, 6), (3, 7)]:
-        v1, v2 = sub(tsdf, corner[a]), sub(tsdf, corner[b])
-        sel = valid & ((v1 < 0) != (v2 < 0))
-        p1, p2, v1, v2 = pos(corner[a])[sel], pos(corner[b])[sel], v1[sel], v2[sel]
-        mu = (-v1 / (v2 - v1)).astype(f32)
-        p = (p1 + (mu[:, None] * (p2 - p1)).astype(f32)).astype(f32)
-        use1 = (np.abs(v1).astype(np.float64) < 1e-5)
-        use2 = ~use1 & (np.abs(v2).astype(np.float64) < 1e-5)
-        use3 = ~use1 & ~use2 & (np.abs(v1 - v2).astype(np.float64) < 1e-5)
-        p[use1 | use3] = p1[use1 | use3]
-        p[use2] = p2[use2]
-        out.append(p)
-    return np.concatenate(out) if out else np.zeros((0, 3), f32)
-
-
 def test_object_extent_stats_equal_mesh_cloud_plus_points(oracle, ops, dev):
     from tests.scenes import rel_CO, rel_OC
     f32 = np.float32
@@ -410,12 +363,6 @@ def test_copy_values(ops, dev, channels):
                     if 0 <= xn < dres[0] and 0 <= yn < dres[1] and 0 <= zn < dres[2]:
                         want[zn, yn, xn] = src[z, y, x]
         assert np.array_equal(dst.numpy(), want), (off, dres)
-
-
-def f32_transform(R, t, p):
-    f32 = np.float32
-    return np.stack([f32(f32(f32(R[i, 0] * p[:, 0]) + f32(R[i, 1] * p[:, 1])) + f32(R[i, 2] * p[:, 2])) + t[i]
-                     for i in range(3)], -1).astype(f32)
 
 
 def expected_resize(res, vox, p10, p90, vol_pad=2.0):
