@@ -4,7 +4,7 @@
 //
 //   emfusion_synth [--frames N] [--objects K] [--bg-res R] [--obj-res R] [--width W --height H]
 //                  [--materialize-gradients] [--autonomous] [--out DIR] [--export-frame-meshes] [--3d-vis]
-//                  [--weld-meshes] [--mesh-min-triangles N] [--mesh-largest-object] [--world-mesh]
+//                  [--weld-meshes] [--mesh-min-triangles N] [--mesh-largest-object] [--mesh-simplify CELL] [--world-mesh]
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
 //                  [--bg-res R] [--bg-voxel M] [--obj-res R] [--volumes] --out DIR
 //   emfusion_synth --dir BASE/ [--colordir colour] [--depthdir depth] [--intrinsics fx fy cx cy] ... --out DIR
@@ -17,6 +17,9 @@
 // (EMFusion::setMeshFilter): components of fewer than N triangles are removed from every model and, with
 // --mesh-largest-object, every component but the largest from the object meshes.  Either implies --weld-meshes; both
 // are set again after --resume (a checkpoint does not store them).
+// --mesh-simplify CELL: every mesh written, world.ply and the slabs retired from then on included, is simplified on the
+// device behind the weld and the filter (EMFusion::setMeshSimplify): the vertices of a model that share a cubic cell of
+// CELL metres become one vertex, collapsed triangles are dropped.  Implies --weld-meshes; set again after --resume.
 // --3d-vis (needs --out): the reference's 3D view (apps/EM-Fusion.cpp:118-131) -- every frame is rendered (render())
 // together with the whole map seen from a viewer 1 m behind the world origin at 1024 x 768, and writeResults writes
 // those views as DIR/mesh_vis_out/%04d.png.  --3d-vis-eye x y z --3d-vis-target x y z place the viewer instead
@@ -111,6 +114,7 @@ static long followStoreMib = 1024;
 static bool followStoreMibGiven = false;
 static unsigned meshMinTriangles = 0;    // --mesh-min-triangles
 static bool meshLargestObject = false;   // --mesh-largest-object
+static float meshSimplifyCell = 0.f;     // --mesh-simplify
 // --checkpoint PATH --checkpoint-every N: the session is saved to PATH after every N-th frame (EMFusion::saveCheckpoint);
 // --resume PATH: the instance is built from the file's parameters, the file is loaded and the input stream continues at
 // the stored frame index.  What the caller sets at start (output log, views, weld) is set again, as at start.
@@ -185,6 +189,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     color = emf.colorEnabled();
     emf.setMeshWeld(weldMeshes);
     emf.setMeshFilter(meshMinTriangles, meshLargestObject);
+    emf.setMeshSimplify(meshSimplifyCell);
     if (motionMasks) emf.setMotionMasks(true, motionParams);  // (not stored in a checkpoint: set again on --resume)
     if (followCamera) emf.setBackgroundFollow(true, followParams);
     if (followStore) emf.setBackgroundStore(true, static_cast<uint64_t>(followStoreMib) << 20);
@@ -298,6 +303,7 @@ int main(int argc, char** argv) {
         else if (a == "--world-mesh") worldMeshOut = true;
         else if (a == "--mesh-min-triangles") meshMinTriangles = static_cast<unsigned>(std::max(next(), 0));
         else if (a == "--mesh-largest-object") meshLargestObject = true;
+        else if (a == "--mesh-simplify" && i + 1 < argc) meshSimplifyCell = static_cast<float>(std::atof(argv[++i]));
         else if (a == "--color") color = true;
         else if (a == "--checkpoint" && i + 1 < argc) checkpointPath = argv[++i];
         else if (a == "--checkpoint-every") checkpointEvery = next();
@@ -392,6 +398,7 @@ int main(int argc, char** argv) {
         emf.enableTimings(true);
         emf.setMeshWeld(weldMeshes);
         emf.setMeshFilter(meshMinTriangles, meshLargestObject);
+        emf.setMeshSimplify(meshSimplifyCell);
         if (motionMasks) emf.setMotionMasks(true, motionParams);
         if (followCamera) emf.setBackgroundFollow(true, followParams);
         if (followStore) emf.setBackgroundStore(true, static_cast<uint64_t>(followStoreMib) << 20);

@@ -75,6 +75,10 @@ def main():
     ap.add_argument("--mesh-largest-object", dest="mesh_largest_object", action="store_true",
                     help="keep only the largest connected component of every object mesh written (the background "
                          "keeps its pieces; implies --weld-meshes)")
+    ap.add_argument("--mesh-simplify", dest="mesh_simplify", type=float, default=0.0, metavar="CELL",
+                    help="simplify every mesh written (world.ply and the slabs retired from then on included) on the "
+                         "device, behind the weld and the filter: the vertices of a model that share a cubic cell of CELL "
+                         "metres become one vertex, collapsed triangles are dropped (implies --weld-meshes)")
     ap.add_argument("--color", action="store_true",
                     help="fuse the sequence's colour images into per-voxel colour: mesh_*.ply (and frame meshes, volume "
                          "dumps) carry colours")
@@ -146,6 +150,7 @@ def main():
             fus.enable_color()
     fus.set_mesh_weld(args.weld_meshes)
     fus.set_mesh_filter(args.mesh_min_triangles, args.mesh_largest_object)
+    fus.set_mesh_simplify(args.mesh_simplify)
     if args.motion_masks:  # (not stored in a checkpoint: set again on --resume)
         fus.set_motion_masks(True, band=args.motion_band, min_pixels=args.motion_min_pixels, max_masks=args.motion_max_masks)
     if args.follow_camera:

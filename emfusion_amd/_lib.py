@@ -179,6 +179,12 @@ SIGNATURES = {
     "emf_hip_meshComponentsEmit": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _STREAM],
     "emf_hip_meshComponentsEmitBatched": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, C.c_int, _FP, _FP, _FP, _FP, _FP, _FP,
                                           _FP, _FP, _STREAM],
+    "emf_hip_meshSimplifyScratchBytes": [C.c_uint64, C.c_uint64],
+    "emf_hip_meshSimplifyCount": [_FP, _FP, _FP, _FP, C.c_uint64, C.c_uint64, _FP, _FP, C.c_int, _FP, _FP, _FP, _FP,
+                                  _FP, _FP, _STREAM],
+    "emf_hip_meshSimplifyStatus": [_FP, C.c_uint64, C.c_uint64, _STREAM],
+    "emf_hip_meshSimplifyEmit": [_FP, C.c_uint64, C.c_uint64, _FP, _FP, C.c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
+                                 _FP, _STREAM],
     "emf_hip_packScratchBytes": [C.c_uint64],
     "emf_hip_packClassify": [_FP, C.c_uint64, _FP, _FP, _STREAM],
     "emf_hip_packRank": [_FP, _FP, C.c_uint64, _FP, _FP, _FP, _FP, _FP, _STREAM],
@@ -332,6 +338,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.emf_hip_meshScratchBytesBatched.restype = C.c_size_t
     lib.emf_hip_meshWeldScratchBytes.restype = C.c_size_t
     lib.emf_hip_meshComponentsScratchBytes.restype = C.c_size_t
+    lib.emf_hip_meshSimplifyScratchBytes.restype = C.c_size_t
     lib.emf_hip_packScratchBytes.restype = C.c_size_t
     lib.emf_hip_spillScratchBytes.restype = C.c_size_t
     lib.emf_hip_meshTilesScratchBytes.restype = C.c_size_t

@@ -416,6 +416,23 @@ public:
     }
     /** Per model id of the last getMesh() / extractMeshes() under an active filter: what the filter met and kept. */
     const std::map<int, MeshFilterStats>& lastMeshFilter() const { return meshFilterStats; }
+    /**
+     * Simplified meshes (include/emf_hip.h "Simplified meshes"; new behaviour, off by default): wherever the weld switch
+     * and the filter act -- getMesh(id), extractMeshes(), writeResults()' meshes of the live models, the per-frame
+     * export -- and in worldMesh() and the retired slabs meshed after the call, the welded and filtered mesh is
+     * clustered by cubic cells of cellMetres (counted from 0 in the mesh's own frame) on the device; only the simplified
+     * arrays travel to the host.  It runs behind the filter, so fragment sizes are counted in original triangles.  A
+     * cell > 0 implies the welded form whatever setMeshWeld says; 0 (or less) is off.  An output form only, exactly as
+     * the weld: the life cycle's soup, the last mesh kept of a deleted object, poses, decisions, volumes and images
+     * do not depend on it.  Not stored in a checkpoint.
+     */
+    void setMeshSimplify(float cellMetres) {
+        if (!(cellMetres < 3.0e38f)) throw HipError("EMFusion::setMeshSimplify: the cell must be finite", EMF_E_ARG);
+        meshSimplifyCell = cellMetres > 0.f ? cellMetres : 0.f;
+    }
+    /** Per model id of the last getMesh() / extractMeshes() with setMeshSimplify on: vertices and triangles in and out,
+     *  and the clusters met. */
+    const std::map<int, MeshSimplifyStats>& lastMeshSimplify() const { return meshSimplifyStats; }
     /** Labels and component sizes of model id's welded, unfiltered mesh (TSDF::getMeshComponents). */
     MeshComponents getMeshComponents(int id);
     /** getMesh() of the background (id 0) or of an object held by this rank (welded with setMeshWeld, filtered with
@@ -688,8 +705,12 @@ private:
     bool meshLargestObjects = false;
     std::map<int, MeshFilterStats> meshFilterStats;        // lastMeshFilter
     DeviceBuffer meshFilterScratch, meshFilterArena;       // the filter's counts + scratch, its kept arrays
+    float meshSimplifyCell = 0.f;                          // setMeshSimplify
+    std::map<int, MeshSimplifyStats> meshSimplifyStats;    // lastMeshSimplify
+    DeviceBuffer meshSimplifyScratch, meshSimplifyArena;   // the simplification's counts + scratch, its arrays
+    bool meshSimplifyActive() const { return meshSimplifyCell > 0.f; }
     MeshFilter meshFilterFor(int id) const {               // the background keeps its pieces
-        return MeshFilter{meshMinTriangles, meshLargestObjects && id != 0};
+        return MeshFilter{meshMinTriangles, meshLargestObjects && id != 0, meshSimplifyCell};
     }
     bool meshFilterActive() const { return meshMinTriangles > 1 || meshLargestObjects; }
     void extractWelded(const std::vector<int>& ids, const std::vector<int32_t>& res, uint64_t nv, uint64_t nt,

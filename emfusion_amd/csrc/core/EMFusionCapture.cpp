@@ -262,6 +262,7 @@ std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
     std::vector<Mesh> out(ids.size());
     for (Mesh& m : out) m.colored = colorOn;
     meshFilterStats.clear();
+    meshSimplifyStats.clear();
     if (n == 0) return out;
     if (n > EMF_MAX_MODELS) throw HipError("EMFusion::extractMeshes: " + std::to_string(n) + " models", EMF_E_LIMIT);
     if (meshHost.empty())
@@ -307,6 +308,8 @@ std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
     if (nv == 0) {  // nothing to mesh: the filter met nothing
         if (meshFilterActive())
             for (int id : ids) meshFilterStats[id] = MeshFilterStats{};
+        if (meshSimplifyActive())
+            for (int id : ids) meshSimplifyStats[id] = MeshSimplifyStats{};
         return out;
     }
     const size_t vb = 3 * sizeof(float) * nv, tb = 4 * sizeof(int32_t) * std::max<uint64_t>(nt, 1);
@@ -317,7 +320,8 @@ std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
     emfCheck(emf_hip_meshEmitBatched(meshTableDev.as<emf_model_t>(), res.data(), n, meshScratch.data(), vDev, nDev, tDev,
                                      main.abi()),
              "meshEmitBatched");
-    if (meshWeld || meshFilterActive()) {  // the welded form of the same soup: welded (and filtered) on the device
+    if (meshWeld || meshFilterActive() || meshSimplifyActive()) {  // the welded form of the same soup: welded (filtered,
+                                                                   // simplified) on the device
         extractWelded(ids, res, nv, nt, out);
         return out;
     }
@@ -359,7 +363,8 @@ std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
 // edge keys walk the surface chunks once more, the weld runs on the keys, and the welded vertex arrays land behind the
 // soup in the same arena (grown when needed; the soup is copied over, it is a quarter of what a frame's soup D2H was).
 // With setMeshFilter the components are labelled, filtered and compacted behind the weld (include/emf_hip.h "Mesh
-// components") and the kept arrays are what travels.
+// components") and the kept arrays are what travels; with setMeshSimplify those are clustered by cell behind the filter
+// (include/emf_hip.h "Simplified meshes") and the simplified arrays travel instead.
 void EMFusion::extractWelded(const std::vector<int>& ids, const std::vector<int32_t>& res, uint64_t nv, uint64_t nt,
                              std::vector<Mesh>& out) {
     const int n = static_cast<int>(ids.size());
@@ -480,7 +485,7 @@ void EMFusion::extractWelded(const std::vector<int>& ids, const std::vector<int3
                                                    knDev, colorOn ? kcDev.as<uint8_t>() : nullptr, ktDev, main.abi()),
                  "meshComponentsEmitBatched");
         for (int k = 0; k < n; ++k) {
-            meshFilterStats[ids[k]] = MeshFilterStats{comps[k], kComps[k], counts[k].triangles, kCounts[2 * k + 1]};
+            meshFilterStats[ids[k]] = MeshFilterStats{comps[k], kComps[k], counts[k].triangles, kCounts[2 * k + 1], {}};
             slices[k] = Slice{kBases[2 * k], kCounts[2 * k], kBases[2 * k + 1], kCounts[2 * k + 1]};
         }
         outV = kvDev;
@@ -489,6 +494,72 @@ void EMFusion::extractWelded(const std::vector<int>& ids, const std::vector<int3
         outC = colorOn ? kcDev.as<uint8_t>() : nullptr;
         outNv = knv;
         outNt = knt;
+    }
+    DeviceBuffer scDev;
+    if (meshSimplifyActive() && outNv == 0) {
+        for (int k = 0; k < n; ++k) meshSimplifyStats[ids[k]] = MeshSimplifyStats{};
+    } else if (meshSimplifyActive()) {
+        const size_t spBytes = emf_hip_meshSimplifyScratchBytes(outNv, outNt);
+        if (spBytes == 0) throw HipError("EMFusion::extractMeshes: " + std::to_string(outNv) + " vertices to simplify", EMF_E_LIMIT);
+        // [triangle bases u64 x 2 (MAX + 1)][vertex bases u64 x (MAX + 1)][kept bases u64 x 2 (MAX + 1)]
+        // [kept counts u32 x 2 MAX][clusters u32 x MAX][scratch]
+        const size_t tbBytes = sizeof(uint64_t) * 2 * (EMF_MAX_MODELS + 1), vbBytes = sizeof(uint64_t) * (EMF_MAX_MODELS + 1),
+                     kcBytes = sizeof(uint32_t) * 2 * EMF_MAX_MODELS, clBytes = sizeof(uint32_t) * EMF_MAX_MODELS,
+                     head = 2 * tbBytes + vbBytes + kcBytes + clBytes;
+        if (meshSimplifyScratch.bytes() < head + spBytes) meshSimplifyScratch = DeviceBuffer(head + spBytes);
+        auto* tBasesDev = meshSimplifyScratch.as<uint64_t>();
+        auto* vBasesDev = tBasesDev + 2 * (EMF_MAX_MODELS + 1);
+        auto* sBasesDev = vBasesDev + (EMF_MAX_MODELS + 1);
+        auto* sCountsDev = reinterpret_cast<uint32_t*>(sBasesDev + 2 * (EMF_MAX_MODELS + 1));
+        uint32_t* clustersDev = sCountsDev + 2 * EMF_MAX_MODELS;
+        void* spScratch = reinterpret_cast<char*>(meshSimplifyScratch.data()) + head;
+        // the bases of what the weld (or the filter) left, in the layout the entries take
+        std::vector<uint64_t> tBases(2 * (n + 1), 0), vBases(n + 1, 0);
+        for (int k = 0; k < n; ++k) {
+            vBases[k] = slices[k].v0;
+            tBases[2 * k] = slices[k].v0;
+            tBases[2 * k + 1] = slices[k].t0;
+        }
+        vBases[n] = tBases[2 * n] = outNv;
+        tBases[2 * n + 1] = outNt;
+        hipCheck(hipMemcpyAsync(tBasesDev, tBases.data(), sizeof(uint64_t) * 2 * (n + 1), hipMemcpyHostToDevice, main.get()),
+                 "simplify triangle bases upload");
+        hipCheck(hipMemcpyAsync(vBasesDev, vBases.data(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, main.get()),
+                 "simplify vertex bases upload");
+        const std::vector<float> cells(n, meshSimplifyCell);
+        emfCheck(emf_hip_meshSimplifyCount(outV, outN, outC, outT, outNv, outNt, tBasesDev, vBasesDev, n, cells.data(), nullptr,
+                                           spScratch, sCountsDev, sBasesDev, clustersDev, main.abi()),
+                 "meshSimplifyCount");
+        std::vector<uint64_t> sBases(2 * (n + 1));
+        std::vector<uint32_t> sCounts(2 * n), clusters(n);
+        hipCheck(hipMemcpyAsync(sBases.data(), sBasesDev, sizeof(uint64_t) * 2 * (n + 1), hipMemcpyDeviceToHost, main.get()),
+                 "simplified bases D2H");
+        hipCheck(hipMemcpyAsync(sCounts.data(), sCountsDev, sizeof(uint32_t) * 2 * n, hipMemcpyDeviceToHost, main.get()),
+                 "simplified counts D2H");
+        hipCheck(hipMemcpyAsync(clusters.data(), clustersDev, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, main.get()),
+                 "clusters D2H");
+        emfCheck(emf_hip_meshSimplifyStatus(spScratch, outNv, outNt, main.abi()), "meshSimplify");  // waits; the uploads too
+        const uint64_t snv = sBases[2 * n], snt = sBases[2 * n + 1];
+        const size_t svb = 3 * sizeof(float) * std::max<uint64_t>(snv, 1), stb = 4 * sizeof(int32_t) * std::max<uint64_t>(snt, 1);
+        if (meshSimplifyArena.bytes() < 2 * svb + stb) meshSimplifyArena = DeviceBuffer(2 * svb + stb);
+        float* svDev = meshSimplifyArena.as<float>();
+        float* snDev = svDev + 3 * std::max<uint64_t>(snv, 1);
+        int32_t* stDev = reinterpret_cast<int32_t*>(snDev + 3 * std::max<uint64_t>(snv, 1));
+        if (colorOn) scDev = DeviceBuffer(3 * std::max<uint64_t>(snv, 1));
+        emfCheck(emf_hip_meshSimplifyEmit(spScratch, outNv, outNt, tBasesDev, vBasesDev, n, outV, outN, outC, outT, svDev, snDev,
+                                          colorOn ? scDev.as<uint8_t>() : nullptr, stDev, main.abi()),
+                 "meshSimplifyEmit");
+        for (int k = 0; k < n; ++k) {
+            meshSimplifyStats[ids[k]] = MeshSimplifyStats{static_cast<uint32_t>(slices[k].vc), static_cast<uint32_t>(slices[k].tc),
+                                                          sCounts[2 * k], sCounts[2 * k + 1], clusters[k]};
+            slices[k] = Slice{sBases[2 * k], sCounts[2 * k], sBases[2 * k + 1], sCounts[2 * k + 1]};
+        }
+        outV = svDev;
+        outN = snDev;
+        outT = stDev;
+        outC = colorOn ? scDev.as<uint8_t>() : nullptr;
+        outNv = snv;
+        outNt = snt;
     }
     const size_t ovb = 3 * sizeof(float) * outNv;
     meshStage.grow(2 * ovb + 4 * sizeof(int32_t) * std::max<uint64_t>(outNt, 1));
@@ -530,14 +601,16 @@ void EMFusion::storeFrameMeshes() {
 Mesh EMFusion::getMesh(int id) {
     synchronize();
     meshFilterStats.clear();
+    meshSimplifyStats.clear();
     TSDF* model = id == 0 ? &background : nullptr;
     for (auto& o : objects)
         if (o.getID() == id) model = &o;
     if (!model) throw HipError("EMFusion::getMesh: no object " + std::to_string(id) + " on this rank", EMF_E_ARG);
-    if (meshFilterActive()) {
+    if (meshFilterActive() || meshSimplifyActive()) {
         MeshFilterStats stats;
         Mesh m = model->getFilteredMesh(meshFilterFor(id), &stats);
-        meshFilterStats[id] = stats;
+        if (meshFilterActive()) meshFilterStats[id] = stats;
+        if (meshSimplifyActive()) meshSimplifyStats[id] = stats.simplify;
         return m;
     }
     return meshWeld ? model->getWeldedMesh() : model->getMesh();

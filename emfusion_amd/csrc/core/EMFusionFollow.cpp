@@ -157,7 +157,7 @@ Mesh EMFusion::worldMesh(int weld) {
     refreshVisibleFromDevice();
     if (bgInFlight) joinBackground();
     quiesce();
-    const bool filtering = meshFilterActive();
+    const bool filtering = meshFilterActive() || meshSimplifyActive();  // (finishMesh does what the filter it gets asks)
     const bool welded = filtering || (weld < 0 ? meshWeld : weld > 0);
     const int nt[3] = {n[0] / kTile[0], n[1] / kTile[1], n[2] / kTile[2]};
     const size_t volTiles = static_cast<size_t>(nt[0]) * nt[1] * nt[2];
@@ -307,7 +307,7 @@ void EMFusion::retireSlabs(const Vec3i& shift, int frame) {
             slab.frame = frame;
             slab.origin = Vec3i(bgOrigin[0] + boxLo[0], bgOrigin[1] + boxLo[1], bgOrigin[2] + boxLo[2]);
             slab.res = boxRes;
-            if (meshFilterActive())
+            if (meshFilterActive() || meshSimplifyActive())
                 slab.mesh = box.getFilteredMesh(meshFilterFor(0));
             else
                 slab.mesh = meshWeld ? box.getWeldedMesh() : box.getMesh();

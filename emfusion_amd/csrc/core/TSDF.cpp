@@ -435,7 +435,9 @@ MeshComponents TSDF::getMeshComponents() {
 // count -> read back two numbers -> emit; the gradient volume is used when it is materialised.  weld: keys, first
 // occurrences and ranks on the device, one more number read back, then the welded arrays are what is downloaded.
 // filter (an active one, on the welded mesh): labels, keep flags and ranks on the device, the kept counts read back,
-// then the filtered arrays are what is downloaded.  components: the welded mesh's labels and sizes instead.
+// then the filtered arrays are what is downloaded; a filter with a simplifyCell: the welded (and filtered) mesh
+// clustered by cell on the device, the simplified arrays downloaded.  components: the welded mesh's labels and sizes
+// instead.
 Mesh TSDF::extractMesh(const uint8_t* fgVolMask, bool weld, const MeshFilter* filter, MeshFilterStats* stats,
                        MeshComponents* components) {
     if (stats) *stats = MeshFilterStats{};
@@ -548,7 +550,7 @@ Mesh TSDF::finishMesh(Mesh mesh, emf_mesh_counts_t counts, DeviceBuffer v, Devic
                                                     kt.as<int32_t>(), s.abi()),
                          "TSDF::getFilteredMesh (emit)");
                 s.waitForCompletion();  // the scratch and the welded arrays go out of scope below
-                if (stats) *stats = MeshFilterStats{kept[2], kept[3], counts.triangles, kept[1]};
+                if (stats) *stats = MeshFilterStats{kept[2], kept[3], counts.triangles, kept[1], {}};
                 v = std::move(kv);
                 n = std::move(kn);
                 t = std::move(kt);
@@ -557,6 +559,38 @@ Mesh TSDF::finishMesh(Mesh mesh, emf_mesh_counts_t counts, DeviceBuffer v, Devic
                 counts.triangles = kept[1];
                 if (kept[0] == 0) return mesh;  // nothing kept: an empty mesh (the buffers above hold one spare element)
             }
+        }
+        if (filter && filter->simplifying()) {  // clustered by cell behind the filter: only the simplified arrays travel
+            const uint64_t nv = counts.vertices, nt = counts.triangles;
+            const size_t spBytes = emf_hip_meshSimplifyScratchBytes(nv, nt);
+            if (spBytes == 0) throw HipError("TSDF::getFilteredMesh: " + std::to_string(nv) + " vertices to simplify", EMF_E_LIMIT);
+            DeviceBuffer spScratch(spBytes), outDev(4 * sizeof(uint32_t));  // kept vertices, kept triangles, clusters
+            uint32_t* o = outDev.as<uint32_t>();
+            const float cell = filter->simplifyCell;
+            const uint8_t* cIn = c.empty() ? nullptr : c.as<uint8_t>();
+            emfCheck(emf_hip_meshSimplifyCount(v.as<float>(), n.as<float>(), cIn, t.as<int32_t>(), nv, nt, nullptr, nullptr, 1,
+                                               &cell, nullptr, spScratch.data(), o, nullptr, o + 2, s.abi()),
+                     "TSDF::getFilteredMesh (simplify count)");
+            uint32_t kept[4] = {0, 0, 0, 0};
+            outDev.download(kept, s);
+            emfCheck(emf_hip_meshSimplifyStatus(spScratch.data(), nv, nt, s.abi()), "TSDF::getFilteredMesh (simplify)");
+            DeviceBuffer sv(std::max<size_t>(kept[0], 1) * 3 * sizeof(float)), sn(std::max<size_t>(kept[0], 1) * 3 * sizeof(float)),
+                st(std::max<size_t>(kept[1], 1) * 4 * sizeof(int32_t)), sc;
+            if (cIn) sc = DeviceBuffer(std::max<size_t>(kept[0], 1) * 3);
+            emfCheck(emf_hip_meshSimplifyEmit(spScratch.data(), nv, nt, nullptr, nullptr, 1, v.as<float>(), n.as<float>(), cIn,
+                                              t.as<int32_t>(), sv.as<float>(), sn.as<float>(),
+                                              cIn ? sc.as<uint8_t>() : nullptr, st.as<int32_t>(), s.abi()),
+                     "TSDF::getFilteredMesh (simplify emit)");
+            s.waitForCompletion();  // the scratch and the input arrays go out of scope below
+            if (stats)
+                stats->simplify = MeshSimplifyStats{static_cast<uint32_t>(nv), static_cast<uint32_t>(nt), kept[0], kept[1], kept[2]};
+            v = std::move(sv);
+            n = std::move(sn);
+            t = std::move(st);
+            if (cIn) c = std::move(sc);
+            counts.vertices = kept[0];
+            counts.triangles = kept[1];
+            if (kept[0] == 0) return mesh;
         }
     }
     mesh.cloud.resize(size_t(counts.vertices) * 3);

@@ -327,6 +327,33 @@ int emf_fusion_set_mesh_filter(emf_fusion_t* h, uint32_t min_triangles, int larg
     return guarded([&] { h->impl->setMeshFilter(min_triangles, largest_objects != 0); });
 }
 
+int emf_fusion_set_mesh_simplify(emf_fusion_t* h, float cell_metres) {
+    REQ(h);
+    return guarded([&] { h->impl->setMeshSimplify(cell_metres); });
+}
+
+int emf_fusion_last_mesh_simplify(emf_fusion_t* h, int32_t* ids, uint32_t* stats, int capacity, int32_t* count) {
+    REQ(h);
+    REQ(count);
+    return guarded([&] {
+        const auto& last = h->impl->lastMeshSimplify();
+        *count = static_cast<int32_t>(last.size());
+        int k = 0;
+        for (const auto& kv : last) {
+            if (k >= capacity) break;
+            if (ids) ids[k] = kv.first;
+            if (stats) {
+                stats[5 * k] = kv.second.verticesIn;
+                stats[5 * k + 1] = kv.second.trianglesIn;
+                stats[5 * k + 2] = kv.second.verticesOut;
+                stats[5 * k + 3] = kv.second.trianglesOut;
+                stats[5 * k + 4] = kv.second.clusters;
+            }
+            ++k;
+        }
+    });
+}
+
 int emf_fusion_mesh_components(emf_fusion_t* h, int id, uint32_t* num_vertices) {
     REQ(h);
     REQ(num_vertices);

@@ -114,16 +114,25 @@ struct Mesh {
     size_t triangles() const { return polygons.size() / 4; }
 };
 
-/** The component filter of a welded mesh (include/emf_hip.h "Mesh components"). */
+/** The component filter of a welded mesh (include/emf_hip.h "Mesh components") and, behind it, the cell its
+ *  vertices are clustered by (include/emf_hip.h "Simplified meshes"). */
 struct MeshFilter {
     uint32_t minTriangles = 0;  // components with fewer triangles are dropped (<= 1: none)
     bool largestOnly = false;   // only the largest component by triangles, a tie to the smaller label
+    float simplifyCell = 0.f;   // metres; <= 0: not simplified
     bool active() const { return minTriangles > 1 || largestOnly; }
+    bool simplifying() const { return simplifyCell > 0.f; }
 };
 
-/** What the filter met and kept in one model's welded mesh. */
+/** What the simplification of one model's welded (and filtered) mesh took and gave. */
+struct MeshSimplifyStats {
+    uint32_t verticesIn = 0, trianglesIn = 0, verticesOut = 0, trianglesOut = 0, clusters = 0;
+};
+
+/** What the filter met and kept in one model's welded mesh; what the simplification behind it did. */
 struct MeshFilterStats {
     uint32_t components = 0, keptComponents = 0, triangles = 0, keptTriangles = 0;
+    MeshSimplifyStats simplify;
 };
 
 /** Per welded vertex: the smallest welded index of its component and that component's triangles. */

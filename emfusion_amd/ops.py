@@ -1007,6 +1007,96 @@ def filter_mesh(vertices, normals, triangles, colors=None, min_triangles=0, larg
     return (out, st) if stats else out
 
 
+def _simplify(nv, nt, verts, norms, tris, cols, cells, origin=(0.0, 0.0, 0.0), soup_bases=None, wbases=None, n=1,
+              stream=None):
+    """emf_hip_meshSimplifyCount / ...Status / ...Emit on device arrays: (vertices, normals, triangles, colours or None
+    as device arrays, kept counts (n, 2) u32, kept bases (n + 1, 2) u64, clusters (n,) u32).  An EMF_E_ARG refusal (a
+    triangle index out of range) is raised after the emit, with the arrays in the error's `partial`."""
+    nbytes = int(_L.emf_hip_meshSimplifyScratchBytes(nv, nt))
+    if nbytes == 0:
+        raise ValueError(f"mesh simplify: {nv} vertices / {nt} triangles are beyond the limits")
+    scratch = DeviceArray.zeros((nbytes // 4,), np.uint32)
+    cell = _per_model(cells, n, np.float32)
+    org = np.ascontiguousarray(origin, np.float32).reshape(3)
+    kcounts = DeviceArray.zeros((n, 2), np.uint32)
+    kbases = DeviceArray.zeros((n + 1, 2), np.uint64)
+    clusters = DeviceArray.zeros((n,), np.uint32)
+    hp = lambda a: a.ctypes.data_as(C.c_void_p)
+    check("emf_hip_meshSimplifyCount",
+          _L.emf_hip_meshSimplifyCount(_ptr(verts), _ptr(norms), _ptr(cols), _ptr(tris), nv, nt, _ptr(soup_bases),
+                                       _ptr(wbases), n, hp(cell), hp(org), _ptr(scratch), _ptr(kcounts), _ptr(kbases),
+                                       _ptr(clusters), _stream(stream)))
+    refused = None
+    try:
+        check("emf_hip_meshSimplifyStatus", _L.emf_hip_meshSimplifyStatus(_ptr(scratch), nv, nt, _stream(stream)))
+    except _lib.EmfHipError as e:
+        if e.code != -4:  # EMF_E_LIMIT: the outputs are meaningless
+            raise
+        refused = e      # EMF_E_ARG: the offending triangles are dropped, the rest stands
+    cnt, bs = kcounts.numpy(), kbases.numpy()
+    knv, knt = int(bs[n, 0]), int(bs[n, 1])
+    kv = DeviceArray.zeros((max(knv, 1), 3), np.float32)
+    kn = DeviceArray.zeros((max(knv, 1), 3), np.float32)
+    kt = DeviceArray.zeros((max(knt, 1), 4), np.int32)
+    kc = None if cols is None else DeviceArray.zeros((max(knv, 1), 3), np.uint8)
+    if nv:
+        check("emf_hip_meshSimplifyEmit",
+              _L.emf_hip_meshSimplifyEmit(_ptr(scratch), nv, nt, _ptr(soup_bases), _ptr(wbases), n, _ptr(verts),
+                                          _ptr(norms), _ptr(cols), _ptr(tris), _ptr(kv), _ptr(kn), _ptr(kc), _ptr(kt),
+                                          _stream(stream)))
+    from .devmem import synchronize
+    synchronize()  # the scratch is released on return
+    out = (kv, kn, kt, kc, cnt, bs, clusters.numpy())
+    if refused is not None:
+        refused.partial = out
+        raise refused
+    return out
+
+
+def simplify_mesh(vertices, normals, triangles, colors=None, cell=0.0, origin=(0.0, 0.0, 0.0), tri_bases=None,
+                  vertex_bases=None, stats=False, stream=None):
+    """emf_hip_meshSimplifyCount / ...Emit on an indexed mesh (numpy or device arrays): vertex clustering by cubic cells
+    of `cell` metres counted from `origin` (include/emf_hip.h "Simplified meshes").  Returns (vertices, normals,
+    triangles[, colours]) as numpy arrays: one vertex per cluster that a kept triangle references, in order of first
+    occurrence, the triangles with three distinct clusters in input order, re-indexed.  cell <= 0 passes the mesh
+    through.  A table of meshes (tri_bases / vertex_bases, n + 1 host entries each; cell a scalar or one per mesh): a
+    list of such tuples.  stats: also a dict (vertices_in, triangles_in, vertices_out, triangles_out, clusters, one
+    entry per mesh).  A refusal raises EmfHipError; for a triangle index out of range (EMF_E_ARG) its `partial` holds
+    what would have been returned, without the offending triangles."""
+    nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
+    n, sb, wb = _table_bases(tri_bases, vertex_bases)
+    if sb is None:
+        vin, tin = np.array([nv], np.uint32), np.array([nt], np.uint32)
+    else:
+        vin = np.diff(np.asarray(vertex_bases, np.int64)).astype(np.uint32)
+        tin = np.diff(np.asarray(tri_bases, np.int64)).astype(np.uint32)
+    if nv == 0 and nt == 0:
+        empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 4), np.int32)) + \
+                (() if colors is None else (np.zeros((0, 3), np.uint8),))
+        out = empty if sb is None else [empty] * n
+        zero = np.zeros((n,), np.uint32)
+        st = dict(vertices_in=vin, triangles_in=tin, vertices_out=zero, triangles_out=zero, clusters=zero)
+        return (out, st) if stats else out
+    verts, norms = _on_device(vertices, np.float32), _on_device(normals, np.float32)
+    tris = _on_device(triangles, np.int32) if nt else None
+    cols = None if colors is None else _on_device(colors, np.uint8)
+
+    def result(dev):
+        kv, kn, kt, kc, cnt, bs, clusters = dev
+        out = _slices(kv, kn, kt, kc, bs[:, 0], cnt[:, 0], bs[:, 1], cnt[:, 1], n)
+        out = out[0] if sb is None else out
+        st = dict(vertices_in=vin, triangles_in=tin, vertices_out=cnt[:, 0].copy(), triangles_out=cnt[:, 1].copy(),
+                  clusters=clusters)
+        return (out, st) if stats else out
+
+    try:
+        return result(_simplify(nv, nt, verts, norms, tris, cols, cell, origin, sb, wb, n, stream=stream))
+    except _lib.EmfHipError as e:
+        if getattr(e, "partial", None) is not None:
+            e.partial = result(e.partial)
+        raise
+
+
 def _slices(verts, norms, tris, cols, vbase, vcnt, tbase, tcnt, n):
     hv, hn, ht = verts.numpy(), norms.numpy(), tris.numpy()
     hc = None if cols is None else cols.numpy()
@@ -1036,15 +1126,18 @@ def mesh_edge_keys(tsdf, weights, fg_mask=None, stream=None):
 
 
 def extract_mesh(tsdf, weights, voxel_size, fg_mask=None, grads=None, stream=None, color=None, weld=False,
-                 min_triangles=0, largest_only=False):
+                 min_triangles=0, largest_only=False, simplify=0.0):
     """TSDF::getMesh / ObjTSDF::getMesh: (vertices (n, 3) f32, normals (n, 3) f32, triangles (m, 4) i32)
     as numpy arrays; two launches to count, one read-back, one launch to emit.  color: the volume's colour volume
     ((Nz, Ny, Nx, 4) u16): a fourth array, the vertex colours (n, 3) u8 (emf_hip_meshColors).  weld: the welded mesh
     instead of the soup (emf_hip_meshEdgeKeys / meshWeldCount / meshWeldEmit): one vertex per grid edge, the first
     copy's bits, triangles re-indexed.  min_triangles / largest_only (with weld): the welded mesh filtered by
-    connected component (filter_mesh) on the device; off (0, False) launches nothing more."""
+    connected component (filter_mesh) on the device; off (0, False) launches nothing more.  simplify (with weld): the
+    welded, filtered mesh clustered by cells of that many metres (simplify_mesh, origin 0); 0 launches nothing more."""
     if (int(min_triangles) > 1 or largest_only) and not weld:
         raise ValueError("extract_mesh: the component filter works on the welded mesh (weld=True)")
+    if float(simplify) > 0 and not weld:
+        raise ValueError("extract_mesh: simplification works on the welded mesh (weld=True)")
     res = _res(tsdf)
     scratch = DeviceArray.zeros((max(int(_L.emf_hip_meshScratchBytes(res)) // 4, 2),), np.uint32)
     counts = DeviceArray.zeros((2,), np.uint32)
@@ -1077,6 +1170,10 @@ def extract_mesh(tsdf, weights, voxel_size, fg_mask=None, grads=None, stream=Non
         if int(min_triangles) > 1 or largest_only:
             verts, norms, tris, cols, kcnt, _, _ = _filter(nv, nt, verts, norms, tris if nt else None, cols, min_triangles,
                                                            largest_only, stream=stream)
+            nv, nt = int(kcnt[0, 0]), int(kcnt[0, 1])
+        if float(simplify) > 0 and nv:
+            verts, norms, tris, cols, kcnt, _, _ = _simplify(nv, nt, verts, norms, tris if nt else None, cols, simplify,
+                                                             stream=stream)
             nv, nt = int(kcnt[0, 0]), int(kcnt[0, 1])
     if color is not None:
         return verts.numpy()[:nv], norms.numpy()[:nv], tris.numpy()[:nt], cols.numpy()[:nv]
@@ -1111,7 +1208,8 @@ def mesh_tile_table(coords, classes, words, at, neighbours=None):
     return table
 
 
-def mesh_tiles(tiles, voxel_size, half, weld=False, colors=False, min_triangles=0, keys=False, stream=None):
+def mesh_tiles(tiles, voxel_size, half, weld=False, colors=False, min_triangles=0, keys=False, stream=None,
+               simplify=0.0):
     """emf_hip_meshTilesCount / ...Emit[/ ...Colors / ...EdgeKeys] (include/emf_hip.h "Meshing a set of tiles"): the
     mesh of the dense volume that holds exactly the listed tiles.  tiles: dict(coords (n, 3) lattice tile coordinates
     (x, y, z), sorted ascending in (z, y, x); classes (n, 3) u8; words (n, 4) u32; at (n, 3): the arena unit of a
@@ -1119,9 +1217,11 @@ def mesh_tiles(tiles, voxel_size, half, weld=False, colors=False, min_triangles=
     dict(tsdf, weights[, color]) -- numpy (Nz, Ny, Nx) volumes that class 3 reads in place; neighbours: optional
     (n, 7) i32 instead of the lookup by coordinate).  half: the three floats a lattice voxel is shifted by.  Returns
     (vertices (n, 3) f32, normals (n, 3) f32, triangles (m, 4) i32[, colours (n, 3) u8][, keys (n,) u64]) as numpy
-    arrays with global indices; weld / min_triangles as in extract_mesh (the keys are then not returned)."""
+    arrays with global indices; weld / min_triangles / simplify as in extract_mesh (the keys are then not returned)."""
     if int(min_triangles) > 1 and not weld:
         raise ValueError("mesh_tiles: the component filter works on the welded mesh (weld=True)")
+    if float(simplify) > 0 and not weld:
+        raise ValueError("mesh_tiles: simplification works on the welded mesh (weld=True)")
     table = mesh_tile_table(tiles["coords"], tiles["classes"], tiles["words"], tiles["at"], tiles.get("neighbours"))
     n = int(np.asarray(tiles["coords"]).reshape(-1, 3).shape[0])
     src = _lib.EmfMeshTilesSource()
@@ -1175,6 +1275,10 @@ def mesh_tiles(tiles, voxel_size, half, weld=False, colors=False, min_triangles=
             verts, norms, tris, cols, kcnt, _, _ = _filter(nv, nt, verts, norms, tris if nt else None, cols, min_triangles,
                                                            False, stream=stream)
             nv, nt = int(kcnt[0, 0]), int(kcnt[0, 1])
+        if float(simplify) > 0 and nv:
+            verts, norms, tris, cols, kcnt, _, _ = _simplify(nv, nt, verts, norms, tris if nt else None, cols, simplify,
+                                                             stream=stream)
+            nv, nt = int(kcnt[0, 0]), int(kcnt[0, 1])
     synchronize()  # the uploads are released on return
     out = (verts.numpy()[:nv], norms.numpy()[:nv], tris.numpy()[:nt])
     if colors:
@@ -1203,18 +1307,23 @@ def mesh_table(volumes):
     return (upload_models(models) if n else None), res
 
 
-def extract_meshes(volumes, stream=None, weld=False, min_triangles=0, largest_only=False):
+def extract_meshes(volumes, stream=None, weld=False, min_triangles=0, largest_only=False, simplify=0.0):
     """emf_hip_meshCountBatched / emf_hip_meshEmitBatched: the meshes of a table of volumes in one pass (one count
     launch, one read-back of the counts, one emit launch).  volumes: [dict(tsdf=, weights=, voxel_size=, fg_mask=None,
     grads=None), ...] of device arrays, at most EMF_MAX_MODELS.  Returns [(vertices (n, 3) f32, normals (n, 3) f32,
     triangles (m, 4) i32), ...] in table order, each what extract_mesh gives for that volume alone -- with weld, what
     extract_mesh(..., weld=True) gives (emf_hip_meshEdgeKeysBatched / meshWeldCountBatched / meshWeldEmitBatched).
     min_triangles / largest_only (with weld; scalars or one value per volume): each slice filtered by connected component
-    as extract_mesh(..., weld=True, min_triangles=, largest_only=) filters that volume alone."""
+    as extract_mesh(..., weld=True, min_triangles=, largest_only=) filters that volume alone.  simplify (with weld; a
+    scalar or one cell per volume, 0 = that volume as it is): each slice clustered as extract_mesh(..., simplify=)
+    clusters that volume alone."""
     n = len(volumes)
     filtered = bool(np.any(np.asarray(min_triangles) > 1) or np.any(largest_only))
     if filtered and not weld:
         raise ValueError("extract_meshes: the component filter works on the welded meshes (weld=True)")
+    simplified = bool(np.any(np.asarray(simplify, np.float32) > 0))
+    if simplified and not weld:
+        raise ValueError("extract_meshes: simplification works on the welded meshes (weld=True)")
     table, res = mesh_table(volumes)
     scratch_bytes = int(_L.emf_hip_meshScratchBytesBatched(res, n))
     scratch = DeviceArray.zeros((max(scratch_bytes // 4, 2),), np.uint32)
@@ -1240,7 +1349,7 @@ def extract_meshes(volumes, stream=None, weld=False, min_triangles=0, largest_on
             check("emf_hip_meshColorsBatched",
                   _L.emf_hip_meshColorsBatched(_ptr(table), _ptr(ptrs), res, n, _ptr(scratch), _ptr(cols),
                                                _stream(stream)))
-    vbase, vcnt = bs[:, 0], cnt[:, 0]
+    vbase, vcnt, tbase, tcnt = bs[:, 0], cnt[:, 0], bs[:, 1], cnt[:, 1]
     if weld:
         keys = DeviceArray.zeros((max(nv, 1),), np.uint64)
         if nv:
@@ -1252,8 +1361,17 @@ def extract_meshes(volumes, stream=None, weld=False, min_triangles=0, largest_on
             nw = int(vbase[n])
             verts, norms, tris, cols, kcnt, kbs, _ = _filter(nw, nt, verts, norms, tris if nt else None, cols,
                                                              min_triangles, largest_only, bases, wbases, n, stream=stream)
-            return _slices(verts, norms, tris, cols, kbs[:, 0], kcnt[:, 0], kbs[:, 1], kcnt[:, 1], n)
-    return _slices(verts, norms, tris, cols, vbase, vcnt, bs[:, 1], cnt[:, 1], n)
+            vbase, vcnt, tbase, tcnt = kbs[:, 0], kcnt[:, 0], kbs[:, 1], kcnt[:, 1]
+            if simplified:  # the filtered table's bases, in the layout the entries take
+                bases = DeviceArray.from_numpy(np.ascontiguousarray(kbs))
+                wbases = DeviceArray.from_numpy(np.ascontiguousarray(vbase))
+        if simplified and n and int(vbase[n]):
+            nt = int(tbase[n])
+            verts, norms, tris, cols, kcnt, kbs, _ = _simplify(int(vbase[n]), nt, verts, norms, tris if nt else None, cols,
+                                                               simplify, soup_bases=bases, wbases=wbases, n=n,
+                                                               stream=stream)
+            vbase, vcnt, tbase, tcnt = kbs[:, 0], kcnt[:, 0], kbs[:, 1], kcnt[:, 1]
+    return _slices(verts, norms, tris, cols, vbase, vcnt, tbase, tcnt, n)
 
 
 def mask_association_masses(hit_masks, assocs, match_masks=None, verdict=None, stream=None, seed_byte=0):

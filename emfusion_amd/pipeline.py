@@ -114,6 +114,8 @@ def load() -> C.CDLL:
         "emf_fusion_set_color": [vp, C.c_int],
         "emf_fusion_set_mesh_weld": [vp, C.c_int],
         "emf_fusion_set_mesh_filter": [vp, C.c_uint32, C.c_int],
+        "emf_fusion_set_mesh_simplify": [vp, C.c_float],
+        "emf_fusion_last_mesh_simplify": [vp, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32)],
         "emf_fusion_mesh_components": [vp, C.c_int, C.POINTER(C.c_uint32)],
         "emf_fusion_copy_mesh_components": [vp, C.c_void_p, C.c_void_p],
         "emf_fusion_last_mesh_filter": [vp, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32)],
@@ -606,6 +608,24 @@ class Fusion:
         keys = ("components", "kept_components", "triangles", "kept_triangles")
         return {int(ids[k]): dict(zip(keys, (int(x) for x in stats[k]))) for k in range(min(count.value, cap))}
 
+    def set_mesh_simplify(self, cell=0.0):
+        """Simplified meshes: wherever set_mesh_weld and the filter act, and in world_mesh() and the slabs retired from
+        then on, the vertices of a model's welded, filtered mesh that share a cubic cell of `cell` metres become one
+        vertex (ops.simplify_mesh of that mesh, origin 0); collapsed triangles and unreferenced vertices are dropped.
+        Done on the device behind the filter; a cell > 0 implies the welded form.  An output form only; not stored in a
+        checkpoint.  Off: set_mesh_simplify()."""
+        _check("emf_fusion_set_mesh_simplify", load().emf_fusion_set_mesh_simplify(self._h, float(cell)))
+
+    def last_mesh_simplify(self):
+        """{id: dict(vertices_in, triangles_in, vertices_out, triangles_out, clusters)} of the last mesh() / meshes() (or
+        write_results / per-frame export) with set_mesh_simplify on; empty without it."""
+        cap = 257
+        ids, stats, count = np.zeros((cap,), np.int32), np.zeros((cap, 5), np.uint32), C.c_int32()
+        _check("emf_fusion_last_mesh_simplify",
+               load().emf_fusion_last_mesh_simplify(self._h, ids.ctypes.data, stats.ctypes.data, cap, C.byref(count)))
+        keys = ("vertices_in", "triangles_in", "vertices_out", "triangles_out", "clusters")
+        return {int(ids[k]): dict(zip(keys, (int(x) for x in stats[k]))) for k in range(min(count.value, cap))}
+
     def set_color_image(self, rgb_view: EmfImage):
         """The u8 x 3 device image (frame size) that goes with the next frame, and with that one only."""
         _check("emf_fusion_set_color_image", load().emf_fusion_set_color_image(self._h, C.byref(rgb_view)))
@@ -719,7 +739,8 @@ class Fusion:
         """ONE mesh of what the session has mapped: the current background's observed tiles plus the
         tiles the background store holds, meshed as one lattice -- no duplicates, no seams.  (vertices (n, 3), normals
         (n, 3), triangles (m, 4)[, colours (n, 3) u8]) in the frame retired_slabs() are written in.  weld None: the
-        session's switch; an active set_mesh_filter implies the weld.  Changes nothing of the session."""
+        session's switch; an active set_mesh_filter or set_mesh_simplify implies the weld, and the latter simplifies the
+        mesh.  Changes nothing of the session."""
         nv, nt = C.c_uint32(), C.c_uint32()
         _check("emf_fusion_world_mesh",
                load().emf_fusion_world_mesh(self._h, -1 if weld is None else int(bool(weld)), C.byref(nv), C.byref(nt)))

@@ -140,6 +140,22 @@ int emf_fusion_set_mesh_filter(emf_fusion_t* h, uint32_t min_triangles, int larg
 int emf_fusion_mesh_components(emf_fusion_t* h, int id, uint32_t* num_vertices);
 int emf_fusion_copy_mesh_components(emf_fusion_t* h, int32_t* labels, uint32_t* sizes);
 int emf_fusion_last_mesh_filter(emf_fusion_t* h, int32_t* ids, uint32_t* stats, int capacity, int32_t* count);
+/* Simplified meshes (include/emf_hip.h "Simplified meshes"; off by default -- cell_metres <= 0 --, may be switched at
+ * any time).  Exactly where emf_fusion_set_mesh_weld and the filter act, and in emf_fusion_world_mesh and the slabs
+ * retired after the call, the vertices of a model's welded and filtered mesh that share a cubic cell of cell_metres
+ * (counted from 0 in the mesh's own frame) become one vertex: the member itself if it is alone, else the mean of
+ * positions, normals and colours in integers; triangles are re-indexed, the collapsed ones dropped, and so are the
+ * vertices nothing references.  Done on the device behind the filter, so fragment sizes are counted in original
+ * triangles; only the simplified arrays travel to the host.  A cell > 0 implies the welded form whatever set_mesh_weld
+ * says; a mesh may come out empty.  A cell so small that a vertex lies 2^15 cells or more from 0 is refused by the call
+ * that meshes (EMF_E_LIMIT).  An output form only, as the weld: nothing else changes, and the last mesh kept of an
+ * object deleted during the run stays the soup.  Not stored in a checkpoint.
+ *   last_mesh_simplify    per model of the last emf_fusion_extract_mesh / extract_meshes (write_results and the
+ *                         per-frame export run the latter) with a cell set: ids ascending and 5 uint32 per id (vertices
+ *                         in, triangles in, vertices out, triangles out, clusters); count = how many there are, at most
+ *                         `capacity` are written */
+int emf_fusion_set_mesh_simplify(emf_fusion_t* h, float cell_metres);
+int emf_fusion_last_mesh_simplify(emf_fusion_t* h, int32_t* ids, uint32_t* stats, int capacity, int32_t* count);
 int emf_fusion_set_color_image(emf_fusion_t* h, const emf_image_t* rgb_dev);
 int emf_fusion_process_rgbd_color(emf_fusion_t* h, const float* depth_host, const uint8_t* rgb_host, int32_t width,
                                   int32_t height);

@@ -1187,6 +1187,74 @@ int emf_hip_meshComponentsEmitBatched(const void* cc_scratch_dev, uint64_t welde
                                       uint8_t* kept_colors, int32_t* kept_triangles, emf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Simplified meshes (new behaviour: the reference has none).  Opt-in; the entries above are untouched.
+ * Vertex clustering (Rossignac-Borrel) of an indexed mesh, or of a table of n meshes, in the form the filter takes:
+ * vertices and normals 3 f32 each, optional colours 3 u8, triangles (3, i0, i1, i2) i32 with model-local indices,
+ * tri_bases_dev (2 (n + 1) u64, of which the TRIANGLE bases, the odd entries, are read) and vertex_bases_dev
+ * (n + 1 u64), both on the device and both NULL for one mesh (n == 1, bases {0, nVertices} and {0, nTriangles}).
+ *   CELL of a vertex, per axis:  c = floor(((double)p - (double)origin) / (double)cell), in double, no reciprocal,
+ *       no contraction; negative coordinates floor.  cell is the model's, in metres; a model with cell <= 0 is
+ *       PASSED THROUGH: every vertex its own cluster, every vertex kept, every triangle with in-range indices kept
+ *       (also one with two equal indices), so its arrays come out as they went in.
+ *   KEY  (uint64_t) slot << 48 | (cz + 2^15) << 32 | (cy + 2^15) << 16 | (cx + 2^15), slot = the model's index in
+ *       the table (0 for one mesh): clusters never cross models.
+ *   CLUSTER j of a model is the j-th distinct key in order of first occurrence, i.e. by its smallest member index.
+ *   CLUSTER VERTEX  one member: that member's position, normal and colour, bit for bit.  Several members:
+ *       position per axis  q = llrint(ldexp((double)p, 20)) summed in int64, (float)(((double)sum / (double)count)
+ *                          * 2^-20)
+ *       normal             the same, a component that is not finite or has |n| >= 2^10 counting as 0 (the mean of
+ *                          the raw gradients: it is not normalised)
+ *       colour per channel (2 * sum + count) / (2 * count) in integers
+ *       -- sums of integers, so no result depends on the order workgroups run in.
+ *   TRIANGLES  every index is replaced by its cluster's; a triangle with two equal cluster indices is dropped; the
+ *       kept ones stay in input order.  Two kept triangles over the same three clusters are both kept.
+ *   VERTICES OUT  the clusters some kept triangle references, in cluster order; the triangles are re-indexed to them,
+ *       model-local.  A model may come out empty.  Every output is a pure function of the input arrays.
+ *   REFUSALS, reported by emf_hip_meshSimplifyStatus; nothing spins, nothing is dereferenced out of range:
+ *       EMF_E_LIMIT  a coordinate of a clustered vertex that is NaN or infinite or has |p| >= 2^10 m, a cell coordinate
+ *                    outside [-2^15, 2^15), a table that cannot hold the keys; the outputs are then meaningless
+ *       EMF_E_ARG    a triangle index outside its model's vertices: the triangle is dropped (in a passed-through
+ *                    model too) and the rest of the output is what the mesh without it gives
+ *       with both, EMF_E_LIMIT is reported.
+ * Limits: nVertices <= 2^30, nTriangles < 2^31, 1 <= n <= EMF_MAX_MODELS.
+ * Not done: merging kept triangles that span the same three clusters (a 96-bit triple does not fit the table's
+ * 64-bit key), quadric error placement, normalising the merged normal.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Bytes of device scratch: an open-addressing table of the smallest power of two >= 2 * vertices (u64 key + u32
+ * first index per slot), 22 words of cluster cells per vertex, one word per triangle and the scans' per-workgroup
+ * sums -- under 137 bytes per vertex + 5 per triangle + 8 KiB.  0 beyond the limits. */
+size_t emf_hip_meshSimplifyScratchBytes(uint64_t vertices, uint64_t triangles);
+
+/* Clusters, sums, kept flags and their ranks; leaves in simplify_scratch_dev what emf_hip_meshSimplifyEmit reads.
+ *   colors        : NULL or the colours; the same choice goes to the emit
+ *   cells         : HOST, n f32 (finite; <= 0 passes the model through); read before the call returns
+ *   origin        : HOST, NULL (0, 0, 0) or 3 finite f32
+ * and, to device memory,
+ *   kept_counts   : 2 n u32, the vertices and triangles of each simplified model, interleaved
+ *   kept_bases    : NULL or 2 (n + 1) u64, each model's first vertex and triangle in the concatenated output,
+ *                   interleaved, and the totals (the layout of emf_hip_meshCountBatched's bases)
+ *   clusters      : NULL or n u32, the clusters met in each model (referenced or not)
+ * nVertices == 0 launches nothing but the clearing of the outputs. */
+int emf_hip_meshSimplifyCount(const float* vertices, const float* normals, const uint8_t* colors,
+                              const int32_t* triangles, uint64_t nVertices, uint64_t nTriangles,
+                              const uint64_t* tri_bases_dev, const uint64_t* vertex_bases_dev, int n, const float* cells,
+                              const float origin[3], void* simplify_scratch_dev, uint32_t* kept_counts,
+                              uint64_t* kept_bases, uint32_t* clusters, emf_stream_t stream);
+
+/* Waits for the stream and returns EMF_OK or the refusal of the last emf_hip_meshSimplifyCount on this scratch.  The
+ * one synchronising entry of the group: call it where the counts are read back anyway. */
+int emf_hip_meshSimplifyStatus(const void* simplify_scratch_dev, uint64_t nVertices, uint64_t nTriangles,
+                               emf_stream_t stream);
+
+/* Input arrays in (the ones the count saw), simplified arrays out (sized by the kept counts).  colors / kept_colors:
+ * both NULL or both given.  No output may alias its input: EMF_E_ARG with nothing enqueued. */
+int emf_hip_meshSimplifyEmit(const void* simplify_scratch_dev, uint64_t nVertices, uint64_t nTriangles,
+                             const uint64_t* tri_bases_dev, const uint64_t* vertex_bases_dev, int n, const float* vertices,
+                             const float* normals, const uint8_t* colors, const int32_t* triangles, float* kept_vertices,
+                             float* kept_normals, uint8_t* kept_colors, int32_t* kept_triangles, emf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Packed buffers (new behaviour: the reference has no checkpoint).  A device buffer of nbytes (a positive
  * multiple of 4, at most 2^40, 16-byte aligned) is a sequence of 1024-byte CHUNKS of 256 32-bit words; the last
  * chunk may be ragged and only its valid words are read, compared or written.  Classification compares bits,
