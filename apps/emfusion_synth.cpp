@@ -5,6 +5,7 @@
 //   emfusion_synth [--frames N] [--objects K] [--bg-res R] [--obj-res R] [--width W --height H]
 //                  [--materialize-gradients] [--autonomous] [--out DIR] [--export-frame-meshes] [--3d-vis]
 //                  [--weld-meshes] [--mesh-min-triangles N] [--mesh-largest-object] [--mesh-simplify CELL] [--world-mesh]
+//                  [--distance-field] [--distance-cap M] [--distance-unknown-obstacle]
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
 //                  [--bg-res R] [--bg-voxel M] [--obj-res R] [--volumes] --out DIR
 //   emfusion_synth --dir BASE/ [--colordir colour] [--depthdir depth] [--intrinsics fx fy cx cy] ... --out DIR
@@ -95,6 +96,11 @@ static void set3dView(emf::EMFusion& emf, const emf::Params& params, const View3
 // Co-Fusion style directory (`--dir`, ImageReader: ColorNNNN.png + DepthNNNN.exr), as apps/EM-Fusion.cpp:118-131 chooses
 static bool weldMeshes = false;  // --weld-meshes
 static bool worldMeshOut = false;  // --world-mesh: OUT/world.ply, one mesh of the background and its stored tiles
+// --distance-field [--distance-cap M] [--distance-unknown-obstacle] (needs --out): writeResults also writes
+// OUT/distance.bin (f32 metres to the nearest occupied -- or occupied or unknown -- voxel of the background, objects
+// stamped in, +inf beyond M metres) and OUT/occupancy.bin (u8 classes); without it no output byte changes
+static bool distanceOut = false, distanceUnknownObstacle = false;
+static float distanceCap = 0.f;
 // --motion-masks [--motion-band M] [--motion-min-pixels N] [--motion-max-masks N]: mask frames propose their own
 // instance masks from the depth in front of the background model (EMFusion::setMotionMasks) instead of reading them
 static bool motionMasks = false;
@@ -197,6 +203,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     if (!masks.empty()) emf.usePreprocMasks(masks);   // apps/EM-Fusion.cpp:115
     emf.setupOutput(frameMeshes, volumes);            // apps/EM-Fusion.cpp:112
     emf.setWorldMeshOutput(worldMeshOut);
+    emf.setDistanceOutput(distanceOut, distanceCap, distanceUnknownObstacle);
     set3dView(emf, params, view3d);
     std::vector<uint8_t> rendered(3 * params.frameSize.area());
     const auto t0 = std::chrono::steady_clock::now();
@@ -301,6 +308,9 @@ int main(int argc, char** argv) {
         else if (a == "--export-frame-meshes") frameMeshes = true;
         else if (a == "--weld-meshes") weldMeshes = true;
         else if (a == "--world-mesh") worldMeshOut = true;
+        else if (a == "--distance-field") distanceOut = true;
+        else if (a == "--distance-cap" && i + 1 < argc) distanceCap = std::max(static_cast<float>(std::atof(argv[++i])), 0.f);
+        else if (a == "--distance-unknown-obstacle") distanceUnknownObstacle = true;
         else if (a == "--mesh-min-triangles") meshMinTriangles = static_cast<unsigned>(std::max(next(), 0));
         else if (a == "--mesh-largest-object") meshLargestObject = true;
         else if (a == "--mesh-simplify" && i + 1 < argc) meshSimplifyCell = static_cast<float>(std::atof(argv[++i]));
@@ -404,6 +414,7 @@ int main(int argc, char** argv) {
         if (followStore) emf.setBackgroundStore(true, static_cast<uint64_t>(followStoreMib) << 20);
         if (!outDir.empty()) emf.setupOutput(frameMeshes, true);  // apps/EM-Fusion.cpp:112
         emf.setWorldMeshOutput(worldMeshOut);
+        emf.setDistanceOutput(distanceOut, distanceCap, distanceUnknownObstacle);
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);
 

@@ -66,6 +66,13 @@ def main():
     ap.add_argument("--world-mesh", dest="world_mesh", action="store_true",
                     help="also write OUT/world.ply: one mesh of the current background and of the tiles the background "
                          "store holds, without duplicates or seams (needs --out)")
+    ap.add_argument("--distance-field", dest="distance_field", action="store_true",
+                    help="also write OUT/distance.bin (f32 metres to the nearest obstacle of the background, objects "
+                         "stamped in at their poses) and OUT/occupancy.bin (u8: 0 free, 1 occupied, 2 unknown) (needs --out)")
+    ap.add_argument("--distance-cap", dest="distance_cap", type=float, default=0.0, metavar="M",
+                    help="with --distance-field: voxels farther than M metres from an obstacle get +inf (0: no cap)")
+    ap.add_argument("--distance-unknown-obstacle", dest="distance_unknown", action="store_true",
+                    help="with --distance-field: unobserved voxels count as obstacles too")
     ap.add_argument("--weld-meshes", dest="weld_meshes", action="store_true",
                     help="weld every mesh written (mesh_*.ply of the live models, frame_meshes/) by grid edge on the "
                          "device: one vertex per edge instead of one per cube that touches it")
@@ -160,7 +167,8 @@ def main():
     fus.set_ignore_person(args.ignore_person)
     fus.set_preprocess(True)
     fus.set_cleanup(True)
-    fus.setup_output(args.frame_meshes, args.volumes, args.world_mesh)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
+    fus.setup_output(args.frame_meshes, args.volumes, args.world_mesh, exp_distance_field=args.distance_field,
+                     distance_cap=max(args.distance_cap, 0.0), distance_unknown_is_obstacle=args.distance_unknown)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
     if args.vis3d:  # the reference's window (apps/EM-Fusion.cpp:118-131), or a viewer placed with look_at
         R3, t3, K3, size3 = pipeline.default_3d_view(prm)
         if args.vis3d_eye:

@@ -203,6 +203,10 @@ SIGNATURES = {
     "emf_hip_meshTilesEmit": [_FP, C.c_uint32, C.c_void_p, _F9, C.c_float, _FP, _FP, _FP, _FP, _STREAM],
     "emf_hip_meshTilesColors": [_FP, C.c_uint32, C.c_void_p, _FP, _FP, _STREAM],
     "emf_hip_meshTilesEdgeKeys": [_FP, C.c_uint32, C.c_void_p, _FP, _FP, _STREAM],
+    "emf_hip_occupancyClasses": [_FP, _FP, _I3, _I3, _I3, _FP, _STREAM],
+    "emf_hip_occupancyObjectBox": [C.c_void_p, _I3, C.c_float],
+    "emf_hip_occupancyStampObjects": [_FP, _I3, C.c_float, _I3, _I3, C.c_void_p, C.c_int32, _STREAM],
+    "emf_hip_distanceTransform": [_FP, _I3, C.c_uint32, C.c_int32, _FP, _FP, C.c_float, _STREAM],
 }
 
 
@@ -238,6 +242,19 @@ class EmfMeshTilesSource(C.Structure):
     _fields_ = [("arena", C.c_void_p), ("arena_units", C.c_uint64), ("tsdf", C.c_void_p), ("weights", C.c_void_p),
                 ("color", C.c_void_p), ("volume_elements", C.c_uint64), ("row_stride", C.c_uint64),
                 ("plane_stride", C.c_uint64)]
+
+
+class EmfOccObject(C.Structure):
+    """Mirror of emf_occ_object_t (include/emf_hip.h "Distance field"): 112 bytes."""
+
+    _fields_ = [("tsdf", C.c_void_p), ("weights", C.c_void_p), ("fgVolMask", C.c_void_p), ("res", C.c_int32 * 3),
+                ("voxelSize", C.c_float), ("R", C.c_float * 9), ("t", C.c_float * 3), ("lo", C.c_int32 * 3),
+                ("size", C.c_int32 * 3)]
+
+
+OCC_FREE, OCC_OCCUPIED, OCC_UNKNOWN = 0, 1, 2
+DF_FAR = 0x7fffffff
+DF_MAX_AXIS = 2048
 
 
 class EmfPose(C.Structure):

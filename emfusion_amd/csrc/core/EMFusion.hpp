@@ -351,6 +351,36 @@ public:
     /** writeResults also writes world.ply = writeMesh(worldMesh()); without it no output byte changes. */
     void setWorldMeshOutput(bool on) { expWorldMesh_ = on; }
     const WorldMeshInfo& worldMeshInfo() const { return worldInfo; }
+    /** What the last distanceField() computed; the device arrays stay valid until the next one. */
+    struct DistanceField {
+        Vec3i boxLo, boxSize;           // voxels of the background, (x, y, z)
+        Affine3f boxPose;               // voxel (0, 0, 0) of the box -> world: the background's pose and the box origin
+        float voxelSize = 0.f;
+        const uint8_t* classes = nullptr;  // device, box (z, y, x) order: EMF_OCC_*
+        const int32_t* d2 = nullptr;       // device: squared distance in voxels, EMF_DF_FAR
+        const float* metres = nullptr;     // device, or NULL when not asked for
+        std::vector<int> objectIds;        // the objects that were stamped, creation order
+        std::vector<Affine3f> objectPoses; // object volume <- background volume, as passed to the kernel
+    };
+    /**
+     * Distance field of the scene (include/emf_hip.h "Distance field"): the occupancy classes of the box
+     * [boxLo, boxLo + boxSize) of the background, every live object that is not in excludeIds stamped at its current
+     * pose (object <- background composed in float as the frame path composes poses), then the exact squared distance
+     * to the nearest voxel whose class is in siteMask, capped at capVoxels (0: no cap).  Enqueued on the main stream
+     * after the frame; buffers are allocated at first use and reused.  Changes nothing of the session and nothing goes
+     * into a checkpoint.  Refused (EMF_E_ARG) on the sharded path.
+     */
+    const DistanceField& distanceField(const Vec3i& boxLo, const Vec3i& boxSize, uint32_t siteMask, int capVoxels,
+                                       const std::vector<int>& excludeIds, bool metres);
+    const DistanceField& lastDistanceField() const { return dfLast; }
+    /** writeResults also writes distance.bin (f32 metres, +inf beyond the cap or without an obstacle) and occupancy.bin
+     *  (u8 classes) of the whole background, both io::writeVolume; without it no output byte changes. */
+    void setDistanceOutput(bool on, float capMetres = 0.f, bool unknownIsObstacle = false) {
+        expDistance_ = on;
+        distanceCapMetres_ = capMetres;
+        distanceUnknownObstacle_ = unknownIsObstacle;
+    }
+    void writeDistanceField(const std::string& dir);
     /** Ids returned by initNewObjVolume for FrameInputs::newObjectMasks of the last frame (-1: none). */
     const std::vector<int>& lastCreatedObjects() const { return lastCreated; }
     Affine3f getCameraPose() const { return pose; }
@@ -658,6 +688,11 @@ private:
     // ---- the tile store (setBackgroundStore; EMFusionFollow.cpp) ----
     bool storeOn = false;
     WorldMeshInfo worldInfo;  // of the last worldMesh()
+    // ---- the distance field (distanceField; EMFusionDistance.cpp): allocated at first use, never in a checkpoint ----
+    DistanceField dfLast;
+    DeviceBuffer dfClasses, dfD2, dfMetres;
+    bool expDistance_ = false, distanceUnknownObstacle_ = false;  // setDistanceOutput
+    float distanceCapMetres_ = 0.f;
     TileStore bgStore;
     void retireSlabs(const Vec3i& shift, int frame);
     DeviceImage<float> depthFiltered;  // output of preprocessDepth

@@ -1,0 +1,105 @@
+// EMFusionDistance.cpp -- emf::EMFusion: the distance field of the scene (new behaviour, the reference
+// exports meshes only).  Occupancy classes of a box of the background, the live objects stamped at their current
+// poses, and the exact Euclidean distance transform over them: three entries of include/emf_hip.h "Distance field"
+// on the main stream.
+#include "EMFusion.hpp"
+#include "Output.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+
+namespace emf {
+
+const EMFusion::DistanceField& EMFusion::distanceField(const Vec3i& boxLo, const Vec3i& boxSize, uint32_t siteMask, int capVoxels,
+                                                       const std::vector<int>& excludeIds, bool metres) {
+    if (sharded || world > 1)
+        throw HipError("EMFusion::distanceField: the distance field is not supported on the sharded path", EMF_E_ARG);
+    const Vec3i n = background.getVolumeRes();
+    unsigned long long voxels = 1;
+    for (int i = 0; i < 3; ++i) {
+        if (boxSize[i] < 1 || boxLo[i] < 0 || boxLo[i] > n[i] - boxSize[i])
+            throw HipError("EMFusion::distanceField: the box leaves the background on axis " + std::to_string(i), EMF_E_ARG);
+        if (boxSize[i] > EMF_DF_MAX_AXIS)
+            throw HipError("EMFusion::distanceField: a box axis of " + std::to_string(boxSize[i]) + " voxels", EMF_E_LIMIT);
+        voxels *= static_cast<unsigned long long>(boxSize[i]);
+    }
+    if (voxels > 0x7fffffffull) throw HipError("EMFusion::distanceField: a box of more than 2^31 - 1 voxels", EMF_E_LIMIT);
+    if (siteMask < 1u || siteMask > 7u) throw HipError("EMFusion::distanceField: siteMask outside 1 .. 7", EMF_E_ARG);
+    if (capVoxels < 0) throw HipError("EMFusion::distanceField: a negative cap", EMF_E_ARG);
+    // as worldMesh: nothing of this instance in flight, the front copies current
+    quiesce();
+    refreshVisibleFromDevice();
+    if (bgInFlight) joinBackground();
+    quiesce();
+    // buffers of the types.hpp owner, at first use and whenever a larger box comes
+    if (dfClasses.bytes() < voxels) dfClasses = DeviceBuffer((voxels + 3) / 4 * 4);
+    if (dfD2.bytes() < voxels * sizeof(int32_t)) dfD2 = DeviceBuffer(voxels * sizeof(int32_t));
+    if (metres && dfMetres.bytes() < voxels * sizeof(float)) dfMetres = DeviceBuffer(voxels * sizeof(float));
+
+    const float voxel = background.getVoxelSize();
+    const Affine3f bgPose = background.getPose();
+    DistanceField out;
+    out.boxLo = boxLo;
+    out.boxSize = boxSize;
+    out.voxelSize = voxel;
+    const Vec3f corner((static_cast<float>(boxLo[0]) - static_cast<float>(n[0] - 1) / 2.f) * voxel,
+                       (static_cast<float>(boxLo[1]) - static_cast<float>(n[1] - 1) / 2.f) * voxel,
+                       (static_cast<float>(boxLo[2]) - static_cast<float>(n[2] - 1) / 2.f) * voxel);
+    out.boxPose = Affine3f(bgPose.rotation(), bgPose.rotation() * corner + bgPose.translation());
+
+    emfCheck(emf_hip_occupancyClasses(background.tsdfPtr(), background.weightsPtr(), n.val, boxLo.val, boxSize.val,
+                                      dfClasses.as<uint8_t>(), main.abi()),
+             "EMFusion::distanceField (classes)");
+    std::vector<emf_occ_object_t> table;
+    for (const ObjTSDF& obj : objects) {
+        if (std::find(excludeIds.begin(), excludeIds.end(), obj.getID()) != excludeIds.end()) continue;
+        const Affine3f ob = obj.getPose().inv() * bgPose;  // object volume <- background volume
+        emf_occ_object_t o{};
+        o.tsdf = obj.tsdfPtr();
+        o.weights = obj.weightsPtr();
+        o.fgVolMask = obj.fgVolMaskPtr();
+        const Vec3i r = obj.getVolumeRes();
+        for (int i = 0; i < 3; ++i) o.res[i] = r[i];
+        o.voxelSize = obj.getVoxelSize();
+        std::copy(ob.rotation().val, ob.rotation().val + 9, o.R);
+        std::copy(ob.translation().val, ob.translation().val + 3, o.t);
+        emfCheck(emf_hip_occupancyObjectBox(&o, n.val, voxel), "EMFusion::distanceField (object box)");
+        table.push_back(o);
+        out.objectIds.push_back(obj.getID());
+        out.objectPoses.push_back(ob);
+    }
+    if (!table.empty())
+        emfCheck(emf_hip_occupancyStampObjects(dfClasses.as<uint8_t>(), n.val, voxel, boxLo.val, boxSize.val, table.data(),
+                                               static_cast<int32_t>(table.size()), main.abi()),
+                 "EMFusion::distanceField (objects)");
+    emfCheck(emf_hip_distanceTransform(dfClasses.as<uint8_t>(), boxSize.val, siteMask, capVoxels, dfD2.as<int32_t>(),
+                                       metres ? dfMetres.as<float>() : nullptr, voxel, main.abi()),
+             "EMFusion::distanceField (transform)");
+    out.classes = dfClasses.as<uint8_t>();
+    out.d2 = dfD2.as<int32_t>();
+    out.metres = metres ? dfMetres.as<float>() : nullptr;
+    dfLast = std::move(out);
+    return dfLast;
+}
+
+// distance.bin and occupancy.bin of the whole background (setDistanceOutput), in the container of the tsdfs/ dumps
+void EMFusion::writeDistanceField(const std::string& dir) {
+    const Vec3i n = background.getVolumeRes();
+    const float voxel = background.getVoxelSize();
+    const int cap = distanceCapMetres_ > 0.f ? static_cast<int>(std::min(std::ceil(distanceCapMetres_ / voxel), 4096.f)) : 0;
+    const uint32_t sites = (1u << EMF_OCC_OCCUPIED) | (distanceUnknownObstacle_ ? 1u << EMF_OCC_UNKNOWN : 0u);
+    const DistanceField& df = distanceField(Vec3i(0, 0, 0), n, sites, cap, {}, true);
+    const size_t voxels = static_cast<size_t>(n[0]) * n[1] * n[2];
+    std::vector<float> metres(voxels);
+    std::vector<uint8_t> classes(voxels);
+    hipCheck(hipMemcpyAsync(metres.data(), df.metres, voxels * sizeof(float), hipMemcpyDeviceToHost, main.get()),
+             "EMFusion::writeDistanceField (metres)");
+    hipCheck(hipMemcpyAsync(classes.data(), df.classes, voxels, hipMemcpyDeviceToHost, main.get()),
+             "EMFusion::writeDistanceField (classes)");
+    main.waitForCompletion();
+    io::writeVolume(dir + "/distance.bin", metres.data(), sizeof(float), n, voxel);
+    io::writeVolume(dir + "/occupancy.bin", classes.data(), sizeof(uint8_t), n, voxel);
+}
+
+}  // namespace emf

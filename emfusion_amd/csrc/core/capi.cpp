@@ -580,6 +580,69 @@ int emf_fusion_world_mesh_info(emf_fusion_t* h, uint64_t out[4]) {
     });
 }
 
+int emf_fusion_distance_field(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], uint32_t site_mask,
+                              int32_t cap_voxels, const int32_t* exclude_ids, int32_t num_exclude, int metres,
+                              int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3]) {
+    REQ(h);
+    if (num_exclude < 0 || (num_exclude > 0 && !exclude_ids)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_distance_field: %d excluded ids without a list", num_exclude);
+        return EMF_E_ARG;
+    }
+    if ((box_lo == nullptr) != (box_size == nullptr)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_distance_field: box_lo and box_size go together");
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const Vec3i n = h->impl->getBackground().getVolumeRes();
+        const Vec3i lo = box_lo ? Vec3i(box_lo[0], box_lo[1], box_lo[2]) : Vec3i(0, 0, 0);
+        const Vec3i size = box_size ? Vec3i(box_size[0], box_size[1], box_size[2]) : n;
+        const std::vector<int> exclude(exclude_ids, exclude_ids + num_exclude);
+        const EMFusion::DistanceField& df = h->impl->distanceField(lo, size, site_mask, cap_voxels, exclude, metres != 0);
+        if (lo_out) std::memcpy(lo_out, df.boxLo.val, sizeof(df.boxLo.val));
+        if (size_out) std::memcpy(size_out, df.boxSize.val, sizeof(df.boxSize.val));
+        if (R) std::memcpy(R, df.boxPose.rotation().val, 9 * sizeof(float));
+        if (t) std::memcpy(t, df.boxPose.translation().val, 3 * sizeof(float));
+    });
+}
+
+int emf_fusion_copy_distance_field(emf_fusion_t* h, uint8_t* classes, int32_t* d2, float* metres) {
+    REQ(h);
+    return guarded([&] {
+        const EMFusion::DistanceField& df = h->impl->lastDistanceField();
+        if (!df.classes) throw HipError("emf_fusion_copy_distance_field: no distance field has been computed", EMF_E_ARG);
+        if (metres && !df.metres) throw HipError("emf_fusion_copy_distance_field: the last distance field has no metres", EMF_E_ARG);
+        const size_t voxels = static_cast<size_t>(df.boxSize[0]) * df.boxSize[1] * df.boxSize[2];
+        Stream& s = h->impl->mainStream();
+        if (classes) hipCheck(hipMemcpyAsync(classes, df.classes, voxels, hipMemcpyDeviceToHost, s.get()), "copy_distance_field");
+        if (d2) hipCheck(hipMemcpyAsync(d2, df.d2, voxels * sizeof(int32_t), hipMemcpyDeviceToHost, s.get()), "copy_distance_field");
+        if (metres) hipCheck(hipMemcpyAsync(metres, df.metres, voxels * sizeof(float), hipMemcpyDeviceToHost, s.get()), "copy_distance_field");
+        s.waitForCompletion();
+    });
+}
+
+int emf_fusion_distance_field_objects(emf_fusion_t* h, int32_t* ids, float* R, float* t, int capacity, int32_t* count) {
+    REQ(h);
+    REQ(count);
+    return guarded([&] {
+        const EMFusion::DistanceField& df = h->impl->lastDistanceField();
+        *count = static_cast<int32_t>(df.objectIds.size());
+        for (int k = 0; k < std::min<int>(capacity, *count); ++k) {
+            if (ids) ids[k] = df.objectIds[k];
+            if (R) std::memcpy(R + 9 * k, df.objectPoses[k].rotation().val, 9 * sizeof(float));
+            if (t) std::memcpy(t + 3 * k, df.objectPoses[k].translation().val, 3 * sizeof(float));
+        }
+    });
+}
+
+int emf_fusion_set_distance_output(emf_fusion_t* h, int on, float cap_metres, int unknown_is_obstacle) {
+    REQ(h);
+    if (!(cap_metres >= 0.f)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_set_distance_output: cap %g", static_cast<double>(cap_metres));
+        return EMF_E_ARG;
+    }
+    return guarded([&] { h->impl->setDistanceOutput(on != 0, cap_metres, unknown_is_obstacle != 0); });
+}
+
 int emf_fusion_follow_shift(const float q[3], const int32_t step[3], float voxel_size, int32_t shift[3]) {
     REQ(q);
     REQ(step);

@@ -1592,3 +1592,96 @@ def motion_masks(points, bg_raylengths, band=None, continuity=None, erode=None, 
     masks = buffers.masks.numpy().reshape(-1)[:p.max_masks * h * w].reshape(p.max_masks, h, w)
     return dict(labels=buffers.labels.numpy(), masks=masks, info=info, count=count,
                 proposals=motion_info_dicts(info, count))
+
+
+# ---- distance field (include/emf_hip.h "Distance field") -----------------------------------------
+
+OCC_FREE, OCC_OCCUPIED, OCC_UNKNOWN = _lib.OCC_FREE, _lib.OCC_OCCUPIED, _lib.OCC_UNKNOWN
+DF_FAR = _lib.DF_FAR
+
+
+def _i3(values):
+    return (C.c_int32 * 3)(*[int(v) for v in values])
+
+
+def _box(res, box):
+    """box None: the whole volume; else (lo, size), both (x, y, z) in voxels."""
+    if box is None:
+        return (0, 0, 0), tuple(int(v) for v in res)
+    lo, size = box
+    return tuple(int(v) for v in lo), tuple(int(v) for v in size)
+
+
+def occupancy_objects(objects, res, voxel_size):
+    """The emf_occ_object_t table of `objects` -- a sequence of (tsdf, weights, fg_mask or None, voxel_size, R, t)
+    with (Nz, Ny, Nx) device volumes and (R, t) = object frame <- background volume frame -- each with the covering
+    sub-box of a background of resolution res (x, y, z) and voxel size voxel_size (emf_hip_occupancyObjectBox)."""
+    table = (_lib.EmfOccObject * max(len(objects), 1))()
+    bres = _i3(res)
+    for k, (tsdf, weights, fg_mask, vs, R, t) in enumerate(objects):
+        o = table[k]
+        _vol(tsdf, np.float32)
+        assert weights.shape == tsdf.shape and (fg_mask is None or fg_mask.shape == tsdf.shape)
+        o.tsdf, o.weights, o.fgVolMask = tsdf.ptr, weights.ptr, None if fg_mask is None else fg_mask.ptr
+        o.res = _i3((tsdf.shape[2], tsdf.shape[1], tsdf.shape[0]))
+        o.voxelSize = float(vs)
+        o.R, o.t = _f(R, 9), _f(t, 3)
+        check("emf_hip_occupancyObjectBox", _L.emf_hip_occupancyObjectBox(C.byref(o), bres, float(voxel_size)))
+    return table
+
+
+def stamp_objects(classes, res, voxel_size, objects, box=None, stream=None):
+    """emf_hip_occupancyStampObjects on a (bz, by, bx) u8 class volume of the box `box` of a background of resolution
+    res (x, y, z): OCCUPIED wherever an object is solid, nothing else written.  objects: see occupancy_objects, or a
+    ready table of it (then with its length as (table, n))."""
+    lo, size = _box(res, box)
+    assert classes.dtype == np.uint8 and classes.shape == (size[2], size[1], size[0]) and not classes.padded
+    table, n = objects if isinstance(objects, tuple) else (occupancy_objects(objects, res, voxel_size), len(objects))
+    check("emf_hip_occupancyStampObjects",
+          _L.emf_hip_occupancyStampObjects(_ptr(classes), _i3(res), float(voxel_size), _i3(lo), _i3(size),
+                                           C.cast(table, C.c_void_p), int(n), _stream(stream)))
+    return classes
+
+
+def occupancy_classes(tsdf, weights, box=None, objects=None, voxel_size=None, out=None, stream=None):
+    """emf_hip_occupancyClasses (+ emf_hip_occupancyStampObjects with `objects`): the (bz, by, bx) u8 classes --
+    OCC_FREE / OCC_OCCUPIED / OCC_UNKNOWN -- of the box (lo, size), both (x, y, z), of (Nz, Ny, Nx) f32 tsdf / weights;
+    box None: the whole volume.  objects: see occupancy_objects; they need the background's voxel_size."""
+    _vol(tsdf, np.float32)
+    assert weights.shape == tsdf.shape and weights.dtype == np.float32
+    res = (tsdf.shape[2], tsdf.shape[1], tsdf.shape[0])
+    lo, size = _box(res, box)
+    shape = tuple(max(int(v), 0) for v in (size[2], size[1], size[0]))
+    if out is None:
+        out = DeviceArray(shape, np.uint8)
+    assert out.dtype == np.uint8 and out.shape == shape and not out.padded
+    check("emf_hip_occupancyClasses",
+          _L.emf_hip_occupancyClasses(_ptr(tsdf), _ptr(weights), _i3(res), _i3(lo), _i3(size), _ptr(out), _stream(stream)))
+    if objects:
+        assert voxel_size is not None, "stamping objects needs the background's voxel_size"
+        stamp_objects(out, res, voxel_size, objects, box=(lo, size), stream=stream)
+    return out
+
+
+def distance_transform(classes, site_mask=2, cap=0, voxel_size=None, out=None, stream=None):
+    """emf_hip_distanceTransform of a (nz, ny, nx) u8 class volume: d2 (nz, ny, nx) i32, the exact squared distance in
+    voxels to the nearest voxel whose class bit is set in site_mask (1 FREE, 2 OCCUPIED, 4 UNKNOWN), DF_FAR where there
+    is none or, with cap > 0 (voxels), beyond cap.  With voxel_size also metres (nz, ny, nx) f32, +inf where DF_FAR:
+    returns d2, or (d2, metres).  out: (d2[, metres]) to reuse."""
+    assert classes.dtype == np.uint8 and len(classes.shape) == 3 and not classes.padded
+    d2 = out[0] if out is not None else DeviceArray(classes.shape, np.int32)
+    metres = None
+    if voxel_size is not None:
+        metres = out[1] if out is not None else DeviceArray(classes.shape, np.float32)
+    assert d2.shape == classes.shape and d2.dtype == np.int32 and (metres is None or metres.shape == classes.shape)
+    check("emf_hip_distanceTransform",
+          _L.emf_hip_distanceTransform(_ptr(classes), _i3(classes.shape[::-1]), int(site_mask), int(cap), _ptr(d2),
+                                       _ptr(metres), 0.0 if voxel_size is None else float(voxel_size), _stream(stream)))
+    return d2 if metres is None else (d2, metres)
+
+
+def distance_field(tsdf, weights, voxel_size, box=None, objects=None, site_mask=2, cap=0, metres=True, stream=None):
+    """occupancy_classes then distance_transform: (classes, d2, metres or None) of the box."""
+    classes = occupancy_classes(tsdf, weights, box=box, objects=objects, voxel_size=voxel_size, stream=stream)
+    r = distance_transform(classes, site_mask=site_mask, cap=cap, voxel_size=voxel_size if metres else None, stream=stream)
+    return (classes, r[0], r[1]) if metres else (classes, r, None)

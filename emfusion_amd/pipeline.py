@@ -131,6 +131,10 @@ def load() -> C.CDLL:
         "emf_fusion_world_mesh_info": [vp, C.c_void_p],
         "emf_fusion_set_world_mesh_output": [vp, C.c_int],
         "emf_fusion_follow_shift": [fp, ip, C.c_float, ip],
+        "emf_fusion_distance_field": [vp, ip, ip, C.c_uint32, C.c_int32, ip, C.c_int32, C.c_int, ip, ip, fp, fp],
+        "emf_fusion_copy_distance_field": [vp, C.c_void_p, C.c_void_p, C.c_void_p],
+        "emf_fusion_distance_field_objects": [vp, ip, fp, fp, C.c_int, ip],
+        "emf_fusion_set_distance_output": [vp, C.c_int, C.c_float, C.c_int],
         "emf_fusion_process_rgbd_color": [vp, fp, C.c_void_p, C.c_int32, C.c_int32],
         "emf_fusion_colored_voxels": [vp, C.POINTER(C.c_uint64)],
         "emf_fusion_get_last_masks": [vp, C.c_void_p, C.c_size_t, ip],
@@ -761,6 +765,76 @@ class Fusion:
         return dict(volume_tiles=int(out[0]), stored_tiles=int(out[1]), duplicate_tiles=int(out[2]),
                     stored_surface_cubes=int(out[3]))
 
+    def camera_box(self, size):
+        """The box (lo, size), both (x, y, z) voxels, of `size` voxels (an int or three) centred on the background voxel
+        under the camera and clipped to the volume; None if nothing of it lies inside."""
+        size = (int(size),) * 3 if np.isscalar(size) else tuple(int(v) for v in size)
+        R, t = self.background_pose()
+        res = np.array(list(self.params.bg_res), np.int64)
+        q = R.astype(np.float64).T @ (self.pose(0)[1].astype(np.float64) - t.astype(np.float64))
+        centre = np.rint(q / float(self.params.bg_voxel_size) + (res - 1) / 2.0).astype(np.int64)
+        lo = np.maximum(centre - np.array(size) // 2, 0)
+        hi = np.minimum(centre - np.array(size) // 2 + np.array(size), res)
+        if (hi <= lo).any():
+            return None
+        return tuple(int(v) for v in lo), tuple(int(v) for v in hi - lo)
+
+    def distance_field(self, box=None, unknown_is_obstacle=False, cap=0.0, exclude=(), signed=False, metres=True,
+                       size=None):
+        """The distance field of the scene: how far is the nearest obstacle.  Over a box of the
+        background -- None: all of it; ((x, y, z) lo, (x, y, z) size) in voxels; "camera" with `size`: centred on the
+        voxel under the camera, clipped to the volume -- the occupancy classes (0 free, 1 occupied, 2 unknown) with
+        every live object not in `exclude` stamped as occupied at its current pose, and the exact Euclidean distance to
+        the nearest occupied voxel (or occupied or unknown, with unknown_is_obstacle).  cap (metres, rounded up to whole
+        voxels; 0: none): farther voxels count as having no obstacle.  Returns a dict:
+          classes (bz, by, bx) u8; d2 (bz, by, bx) i32, squared voxels, DF_FAR = 0x7fffffff for "none"; metres f32 with
+          +inf for "none" (when asked); box (lo, size); pose (R 3x3, t 3) of voxel (0, 0, 0) of the box -> world, the
+          background's pose composed with the box origin, so right after rolls too; voxel_size; objects [(id, R, t)]
+          stamped, (R, t) = object volume <- background volume.
+        signed=True: a second transform from the complement gives d2_inside / metres_inside, the distance from an
+        obstacle voxel to the nearest voxel that is none, and `signed` (metres) = +outside, -inside."""
+        if isinstance(box, str):
+            if box != "camera" or size is None:
+                raise ValueError('distance_field: box="camera" needs a size')
+            box = self.camera_box(size)
+            if box is None:
+                raise ValueError("distance_field: the camera box lies outside the background")
+        vs = float(self.params.bg_voxel_size)
+        cap_voxels = min(int(np.ceil(np.float32(cap) / np.float32(vs))), 4096) if cap > 0 else 0  # float32, as write_results does
+        sites = 2 | (4 if unknown_is_obstacle else 0)
+        ex = (C.c_int32 * max(len(exclude), 1))(*[int(i) for i in exclude])
+        lo_arg = size_arg = None
+        if box is not None:
+            lo_arg, size_arg = (C.c_int32 * 3)(*[int(v) for v in box[0]]), (C.c_int32 * 3)(*[int(v) for v in box[1]])
+
+        def run(mask, want_metres):
+            lo, sz, R, t = (C.c_int32 * 3)(), (C.c_int32 * 3)(), (C.c_float * 9)(), (C.c_float * 3)()
+            _check("emf_fusion_distance_field",
+                   load().emf_fusion_distance_field(self._h, lo_arg, size_arg, mask, cap_voxels, ex, len(exclude),
+                                                    int(want_metres), lo, sz, R, t))
+            shape = (sz[2], sz[1], sz[0])
+            classes, d2 = np.empty(shape, np.uint8), np.empty(shape, np.int32)
+            m = np.empty(shape, np.float32) if want_metres else None
+            _check("emf_fusion_copy_distance_field",
+                   load().emf_fusion_copy_distance_field(self._h, classes.ctypes.data, d2.ctypes.data,
+                                                         m.ctypes.data if want_metres else None))
+            return classes, d2, m, (tuple(lo), tuple(sz)), (np.array(R, np.float32).reshape(3, 3), np.array(t, np.float32))
+
+        classes, d2, m, out_box, pose = run(sites, metres or signed)
+        n = C.c_int32(0)
+        _check("emf_fusion_distance_field_objects", load().emf_fusion_distance_field_objects(self._h, None, None, None, 0, C.byref(n)))
+        ids, Rs, ts = (C.c_int32 * max(n.value, 1))(), (C.c_float * (9 * max(n.value, 1)))(), (C.c_float * (3 * max(n.value, 1)))()
+        _check("emf_fusion_distance_field_objects", load().emf_fusion_distance_field_objects(self._h, ids, Rs, ts, n.value, C.byref(n)))
+        objects = [(int(ids[k]), np.array(Rs[9 * k:9 * k + 9], np.float32).reshape(3, 3), np.array(ts[3 * k:3 * k + 3], np.float32))
+                   for k in range(n.value)]
+        out = dict(classes=classes, d2=d2, box=out_box, pose=pose, voxel_size=vs, objects=objects)
+        if metres or signed:
+            out["metres"] = m
+        if signed:
+            _, d2_in, m_in, _, _ = run(7 ^ sites, True)
+            out.update(d2_inside=d2_in, metres_inside=m_in, signed=np.where(m > 0, m, -m_in).astype(np.float32))
+        return out
+
     def last_motion_masks(self):
         """The proposals of the last processed frame: ((H, W) i32 image of proposal ranks, -1 where none is, list of
         dicts {label, area, x0, y0, x1, y1} by rank).  Empty / all -1 if the frame proposed nothing."""
@@ -955,14 +1029,20 @@ class Fusion:
     def enable_pose_log(self, on=True):
         _check("emf_fusion_enable_pose_log", load().emf_fusion_enable_pose_log(self._h, int(on)))
 
-    def setup_output(self, exp_frame_meshes=False, exp_vols=False, exp_world_mesh=False):
+    def setup_output(self, exp_frame_meshes=False, exp_vols=False, exp_world_mesh=False, exp_distance_field=False,
+                     distance_cap=0.0, distance_unknown_is_obstacle=False):
         """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
         the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
-        the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh()."""
+        the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh();
+        exp_distance_field: write_results also writes distance.bin (f32 metres to the nearest obstacle of the whole
+        background, +inf beyond distance_cap metres or without an obstacle) and occupancy.bin (u8 classes)."""
         _check("emf_fusion_setup_output",
                load().emf_fusion_setup_output(self._h, int(exp_frame_meshes), int(exp_vols)))
         _check("emf_fusion_set_world_mesh_output",
                load().emf_fusion_set_world_mesh_output(self._h, int(bool(exp_world_mesh))))
+        _check("emf_fusion_set_distance_output",
+               load().emf_fusion_set_distance_output(self._h, int(bool(exp_distance_field)), float(distance_cap),
+                                                     int(bool(distance_unknown_is_obstacle))))
 
     def write_results(self, directory: str, volumes: bool = True):
         """poses-*.txt, mesh_bg.ply, mesh_<id>.ply always; tsdfs/*.bin with `volumes` (reference formats)."""

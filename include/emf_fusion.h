@@ -233,6 +233,30 @@ int emf_fusion_world_mesh_info(emf_fusion_t* h, uint64_t out[4]);
  * emf_io_write_mesh of it, and nothing else new.  Off (the default): no output byte changes. */
 int emf_fusion_set_world_mesh_output(emf_fusion_t* h, int on);
 int emf_fusion_follow_shift(const float q[3], const int32_t step[3], float voxel_size, int32_t shift[3]);
+/* The distance field of the scene (include/emf_hip.h "Distance field"; new behaviour, nothing of the
+ * session changes and nothing goes into a checkpoint).  Over the box [box_lo, box_lo + box_size) of the background, in
+ * voxels (x, y, z), inside the volume -- both NULL: the whole background -- the occupancy classes of the background
+ * (0 free, 1 occupied, 2 unknown), every live object whose id is not in exclude_ids stamped as occupied at its current
+ * pose, and d2, the exact squared distance in voxels to the nearest voxel whose class bit is set in site_mask (1 free,
+ * 2 occupied, 4 unknown), EMF_DF_FAR where there is none or, with cap_voxels > 0, beyond the cap; with metres != 0
+ * also sqrtf(d2) * voxel size as f32, +inf for EMF_DF_FAR.  Enqueued on the main stream after the frame; the results
+ * stay on the device until the next call.  lo_out / size_out (may be NULL): the box; R / t (may be NULL): the pose of
+ * voxel (0, 0, 0) of the box -> world, i.e. the background's current pose composed with the box origin, so it stays
+ * right after rolls.  EMF_E_ARG on a sharded session ("not supported on the sharded path"). */
+int emf_fusion_distance_field(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], uint32_t site_mask,
+                              int32_t cap_voxels, const int32_t* exclude_ids, int32_t num_exclude, int metres,
+                              int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3]);
+/* Copies the last distance field to the host (waits for the main stream): one u8, one i32 and one f32 per voxel of
+ * the box in (z, y, x) order; any of the three may be NULL. */
+int emf_fusion_copy_distance_field(emf_fusion_t* h, uint8_t* classes, int32_t* d2, float* metres);
+/* The objects the last distance field stamped, in creation order: ids[k], and R[9 k ..] / t[3 k ..], object volume <-
+ * background volume exactly as passed to the kernel.  count is always the full number; at most capacity are written. */
+int emf_fusion_distance_field_objects(emf_fusion_t* h, int32_t* ids, float* R, float* t, int capacity, int32_t* count);
+/* setup_output's exp_distance_field, as an entry of its own so that emf_fusion_setup_output keeps its signature:
+ * emf_fusion_write_results also writes distance.bin (f32 metres to the nearest occupied voxel -- or occupied or unknown
+ * with unknown_is_obstacle -- of the whole background, +inf beyond cap_metres, which is rounded up to whole voxels; 0:
+ * no cap) and occupancy.bin (u8 classes), both in the container of the tsdfs/ dumps.  Off: no output byte changes. */
+int emf_fusion_set_distance_output(emf_fusion_t* h, int on, float cap_metres, int unknown_is_obstacle);
 /* Remember what rolls out (new behaviour, off by default; with it off no launch, no output byte and no
  * checkpoint byte changes).  With the store on, the whole integration tiles (32 x 8 x 8) that a roll moves out of the
  * background go to host memory as the bytes they are, after the slabs are retired; the tiles that a later roll moves

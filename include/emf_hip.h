@@ -1524,6 +1524,78 @@ int emf_hip_meshTilesColors(const emf_mesh_tile_t* tiles_dev, uint32_t n, const 
 int emf_hip_meshTilesEdgeKeys(const emf_mesh_tile_t* tiles_dev, uint32_t n, const emf_mesh_tiles_source_t* source,
                               const void* scratch_dev, uint64_t* keys, emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Distance field (new behaviour: DESIGN.md 5.18).  Opt-in; nothing above is touched.  Three steps from the volumes of
+ * a scene to "how far is the nearest obstacle", all over a BOX of voxels [box_lo, box_lo + box_size) of a volume of
+ * resolution res (res, box_lo, box_size: x, y, z).  The result is that of the cropped arrays: what lies outside the
+ * box does not exist.  Box arrays are dense, one element per voxel of the box in (z, y, x) order, x fastest.
+ *   1 classes   one u8 per voxel from the volume's (tsdf, weights), single float comparisons only:
+ *                   EMF_OCC_FREE      0   weights > 0 && tsdf > 0
+ *                   EMF_OCC_OCCUPIED  1   weights > 0 && !(tsdf > 0)      (-0.0 and NaN count as occupied)
+ *                   EMF_OCC_UNKNOWN   2   !(weights > 0)                  (0, negative and NaN weights)
+ *   2 stamping  objects mark EMF_OCC_OCCUPIED where they are solid.  For the voxel v (volume coordinates) of the
+ *               background and one object, every operation a single float32 operation in this order:
+ *                   p_b = (float(v) - half_b) * voxel_b            half = (res - 1) / 2.f per axis
+ *                   p_o = R p_b + t                                rows of R summed left to right; R, t: the object's
+ *                                                                  frame <- the background volume's frame
+ *                   q   = p_o / voxel_o + half_o
+ *                   i   = rint(q) per axis, ties to even           a NaN coordinate is outside
+ *               the voxel becomes OCCUPIED iff i lies inside the object's resolution, the object's weights[i] > 0,
+ *               fgVolMask[i] != 0 (unless fgVolMask is NULL) and !(tsdf[i] > 0).  Nothing else is written: an object
+ *               never turns a voxel free.  Each object is evaluated over its own sub-box [lo, lo + size) of the
+ *               background lattice (emf_hip_occupancyObjectBox computes a covering one), clipped to the box.  Plain
+ *               stores of one value, no atomics: the result does not depend on the order of objects or workgroups.
+ *   3 distance  d2, one i32 per voxel: the exact squared Euclidean distance, in voxels, to the nearest SITE of the
+ *               box -- a voxel whose class bit is set in site_mask (bit 0 FREE, bit 1 OCCUPIED, bit 2 UNKNOWN; a
+ *               class byte above 2 is never a site) -- 0 at a site, EMF_DF_FAR where the box holds no site.  With
+ *               cap > 0 every d2 > cap * cap becomes EMF_DF_FAR.  Integer arithmetic only: a pure function of the
+ *               inputs, bit for bit.
+ * Limits: every box axis in 1 .. EMF_DF_MAX_AXIS and at most 2^31 - 1 voxels in a box (EMF_E_LIMIT above; a zero or
+ * negative axis and a box that leaves the volume are EMF_E_ARG).  Every rejected argument -- a NULL pointer
+ * included -- returns EMF_E_ARG or EMF_E_LIMIT with nothing enqueued.  Nothing allocates, copies to the host or waits.
+ * ---------------------------------------------------------------------------------------------- */
+#define EMF_OCC_FREE 0
+#define EMF_OCC_OCCUPIED 1
+#define EMF_OCC_UNKNOWN 2
+#define EMF_DF_FAR 0x7fffffff
+#define EMF_DF_MAX_AXIS 2048
+
+typedef struct emf_occ_object {
+    const float* tsdf;        /* the object's volume (device) */
+    const float* weights;
+    const uint8_t* fgVolMask; /* or NULL: no foreground gate */
+    int32_t res[3];           /* its resolution (x, y, z), every axis >= 1 */
+    float voxelSize;          /* > 0 */
+    float R[9], t[3];         /* object frame <- background volume frame, row-major */
+    int32_t lo[3], size[3];   /* the sub-box of the BACKGROUND lattice the object is evaluated over (volume coordinates);
+                                 a size <= 0 on any axis: nowhere */
+} emf_occ_object_t;           /* 112 bytes */
+
+/* Step 1.  tsdf, weights: the whole volume (device); classes: box_size[0] * [1] * [2] bytes.  Rows whose first voxel
+ * is 16-byte aligned in both arrays are read with 16-byte loads, four voxels per lane; other rows voxel by voxel. */
+int emf_hip_occupancyClasses(const float* tsdf, const float* weights, const int32_t res[3], const int32_t box_lo[3],
+                             const int32_t box_size[3], uint8_t* classes, emf_stream_t stream);
+
+/* Host only, no device: sets object->lo / size to a sub-box of a background of resolution res and voxel size
+ * voxel_size that covers every voxel step 2 can map into the object (the object's corners taken through the inverse of
+ * (R, t) in double precision, one voxel of margin, clipped to the volume; the whole volume when R is singular or a
+ * value is not finite). */
+int emf_hip_occupancyObjectBox(emf_occ_object_t* object, const int32_t res[3], float voxel_size);
+
+/* Step 2 on the classes of the box.  objects: n entries in HOST memory, read before the call returns (passed to the
+ * kernels by value); n >= 0, EMF_MAX_BATCH per launch, longer lists in several launches.  A launch covers only the
+ * objects' sub-boxes. */
+int emf_hip_occupancyStampObjects(uint8_t* classes, const int32_t res[3], float voxel_size, const int32_t box_lo[3],
+                                  const int32_t box_size[3], const emf_occ_object_t* objects, int32_t n,
+                                  emf_stream_t stream);
+
+/* Step 3.  classes: size[0] * [1] * [2] bytes, only read; d2: as many i32.  site_mask in 1 .. 7; cap >= 0 in voxels,
+ * 0 = none.  metres: NULL, or as many f32, written by the last pass as sqrtf(float(d2)) * voxel_size (two roundings;
+ * voxel_size > 0 then) and +inf where d2 is EMF_DF_FAR.  Three separable passes, x (wave ballots and bit scans, no
+ * LDS), then y and z in place in d2 (bundles of whole lines staged in LDS); no atomics, no scratch buffer. */
+int emf_hip_distanceTransform(const uint8_t* classes, const int32_t size[3], uint32_t site_mask, int32_t cap, int32_t* d2,
+                              float* metres, float voxel_size, emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
