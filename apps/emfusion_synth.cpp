@@ -6,6 +6,7 @@
 //                  [--materialize-gradients] [--autonomous] [--out DIR] [--export-frame-meshes] [--3d-vis]
 //                  [--weld-meshes] [--mesh-min-triangles N] [--mesh-largest-object] [--mesh-simplify CELL] [--world-mesh]
 //                  [--distance-field] [--distance-cap M] [--distance-unknown-obstacle]
+//                  [--frontiers] [--frontier-min-voxels N] [--frontier-clearance M]
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
 //                  [--bg-res R] [--bg-voxel M] [--obj-res R] [--volumes] --out DIR
 //   emfusion_synth --dir BASE/ [--colordir colour] [--depthdir depth] [--intrinsics fx fy cx cy] ... --out DIR
@@ -101,6 +102,12 @@ static bool worldMeshOut = false;  // --world-mesh: OUT/world.ply, one mesh of t
 // stamped in, +inf beyond M metres) and OUT/occupancy.bin (u8 classes); without it no output byte changes
 static bool distanceOut = false, distanceUnknownObstacle = false;
 static float distanceCap = 0.f;
+// --frontiers [--frontier-min-voxels N] [--frontier-clearance M] (needs --out): writeResults also writes
+// OUT/frontiers.txt, one line per cluster of frontier voxels (free next to unknown) of the background of at least N
+// (default 8) voxels, largest first; M metres of clearance from the nearest occupied voxel.
+static bool frontiersOut = false;
+static int frontierMinVoxels = 8;
+static float frontierClearance = 0.f;
 // --motion-masks [--motion-band M] [--motion-min-pixels N] [--motion-max-masks N]: mask frames propose their own
 // instance masks from the depth in front of the background model (EMFusion::setMotionMasks) instead of reading them
 static bool motionMasks = false;
@@ -204,6 +211,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     emf.setupOutput(frameMeshes, volumes);            // apps/EM-Fusion.cpp:112
     emf.setWorldMeshOutput(worldMeshOut);
     emf.setDistanceOutput(distanceOut, distanceCap, distanceUnknownObstacle);
+    emf.setFrontierOutput(frontiersOut, frontierMinVoxels, frontierClearance);
     set3dView(emf, params, view3d);
     std::vector<uint8_t> rendered(3 * params.frameSize.area());
     const auto t0 = std::chrono::steady_clock::now();
@@ -311,6 +319,9 @@ int main(int argc, char** argv) {
         else if (a == "--distance-field") distanceOut = true;
         else if (a == "--distance-cap" && i + 1 < argc) distanceCap = std::max(static_cast<float>(std::atof(argv[++i])), 0.f);
         else if (a == "--distance-unknown-obstacle") distanceUnknownObstacle = true;
+        else if (a == "--frontiers") frontiersOut = true;
+        else if (a == "--frontier-min-voxels" && i + 1 < argc) frontierMinVoxels = std::max(std::atoi(argv[++i]), 1);
+        else if (a == "--frontier-clearance" && i + 1 < argc) frontierClearance = std::max(static_cast<float>(std::atof(argv[++i])), 0.f);
         else if (a == "--mesh-min-triangles") meshMinTriangles = static_cast<unsigned>(std::max(next(), 0));
         else if (a == "--mesh-largest-object") meshLargestObject = true;
         else if (a == "--mesh-simplify" && i + 1 < argc) meshSimplifyCell = static_cast<float>(std::atof(argv[++i]));
@@ -415,6 +426,7 @@ int main(int argc, char** argv) {
         if (!outDir.empty()) emf.setupOutput(frameMeshes, true);  // apps/EM-Fusion.cpp:112
         emf.setWorldMeshOutput(worldMeshOut);
         emf.setDistanceOutput(distanceOut, distanceCap, distanceUnknownObstacle);
+        emf.setFrontierOutput(frontiersOut, frontierMinVoxels, frontierClearance);
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);
 

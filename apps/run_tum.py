@@ -73,6 +73,13 @@ def main():
                     help="with --distance-field: voxels farther than M metres from an obstacle get +inf (0: no cap)")
     ap.add_argument("--distance-unknown-obstacle", dest="distance_unknown", action="store_true",
                     help="with --distance-field: unobserved voxels count as obstacles too")
+    ap.add_argument("--frontiers", dest="frontiers", action="store_true",
+                    help="also write OUT/frontiers.txt: one line per cluster of frontier voxels (free next to unknown) of "
+                         "the background, largest first")
+    ap.add_argument("--frontier-min-voxels", dest="frontier_min_voxels", type=int, default=8, metavar="N",
+                    help="with --frontiers: drop clusters of fewer than N voxels (default 8)")
+    ap.add_argument("--frontier-clearance", dest="frontier_clearance", type=float, default=0.0, metavar="M",
+                    help="with --frontiers: only frontier voxels at least M metres from the nearest occupied voxel")
     ap.add_argument("--weld-meshes", dest="weld_meshes", action="store_true",
                     help="weld every mesh written (mesh_*.ply of the live models, frame_meshes/) by grid edge on the "
                          "device: one vertex per edge instead of one per cube that touches it")
@@ -168,7 +175,9 @@ def main():
     fus.set_preprocess(True)
     fus.set_cleanup(True)
     fus.setup_output(args.frame_meshes, args.volumes, args.world_mesh, exp_distance_field=args.distance_field,
-                     distance_cap=max(args.distance_cap, 0.0), distance_unknown_is_obstacle=args.distance_unknown)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
+                     distance_cap=max(args.distance_cap, 0.0), distance_unknown_is_obstacle=args.distance_unknown,
+                     exp_frontiers=args.frontiers, frontier_min_voxels=max(args.frontier_min_voxels, 1),
+                     frontier_clearance=max(args.frontier_clearance, 0.0))  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
     if args.vis3d:  # the reference's window (apps/EM-Fusion.cpp:118-131), or a viewer placed with look_at
         R3, t3, K3, size3 = pipeline.default_3d_view(prm)
         if args.vis3d_eye:

@@ -207,6 +207,9 @@ SIGNATURES = {
     "emf_hip_occupancyObjectBox": [C.c_void_p, _I3, C.c_float],
     "emf_hip_occupancyStampObjects": [_FP, _I3, C.c_float, _I3, _I3, C.c_void_p, C.c_int32, _STREAM],
     "emf_hip_distanceTransform": [_FP, _I3, C.c_uint32, C.c_int32, _FP, _FP, C.c_float, _STREAM],
+    "emf_hip_frontierLabel": [_FP, _I3, _FP, C.c_int32, _FP, _FP, _STREAM],
+    "emf_hip_frontierScratchBytes": [_I3, C.c_uint32],
+    "emf_hip_frontierClusters": [_FP, _I3, C.c_int32, C.c_uint32, _FP, _FP, C.c_int32, _FP, _STREAM],
 }
 
 
@@ -255,6 +258,19 @@ class EmfOccObject(C.Structure):
 OCC_FREE, OCC_OCCUPIED, OCC_UNKNOWN = 0, 1, 2
 DF_FAR = 0x7fffffff
 DF_MAX_AXIS = 2048
+
+
+class EmfFrontierCluster(C.Structure):
+    """Mirror of emf_frontier_cluster_t (include/emf_hip.h "Frontiers"): 72 bytes."""
+
+    _fields_ = [("label", C.c_int32), ("count", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
+                ("sum", C.c_uint64 * 3), ("rep", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+
+# the same record as a numpy structured dtype (what ops.frontier_clusters returns)
+FRONTIER_CLUSTER_DTYPE = [("label", "<i4"), ("count", "<i4"), ("lo", "<i4", 3), ("hi", "<i4", 3), ("sum", "<u8", 3),
+                          ("rep", "<i4", 3), ("reserved", "<i4")]
+FRONTIER_KEPT, FRONTIER_CLUSTERS, FRONTIER_VOXELS = 0, 1, 2
 
 
 class EmfPose(C.Structure):
@@ -360,6 +376,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.emf_hip_spillScratchBytes.restype = C.c_size_t
     lib.emf_hip_meshTilesScratchBytes.restype = C.c_size_t
     lib.emf_hip_motionMasksScratchBytes.restype = C.c_size_t
+    lib.emf_hip_frontierScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateCullScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateDirtyMapBytes.restype = C.c_size_t
     lib.emf_hip_signMapBytes.restype = C.c_size_t

@@ -381,6 +381,43 @@ public:
         distanceUnknownObstacle_ = unknownIsObstacle;
     }
     void writeDistanceField(const std::string& dir);
+    /** What the last frontiers() computed; the device arrays stay valid until the next one. */
+    struct Frontiers {
+        Vec3i boxLo, boxSize;              // voxels of the background, (x, y, z)
+        Affine3f boxPose;                  // voxel (0, 0, 0) of the box -> world, as DistanceField::boxPose
+        Affine3f bgPose;                   // the background's pose the world points go through
+        Vec3i bgRes;
+        float voxelSize = 0.f;
+        int minVoxels = 1, clearanceVoxels = 0;
+        std::vector<emf_frontier_cluster_t> clusters;  // the kept ones: count descending, ties by label ascending
+        uint32_t kept = 0, all = 0, voxels = 0;        // the three counters: kept clusters, all clusters, frontier voxels
+        const uint8_t* classes = nullptr;  // device, box (z, y, x) order: EMF_OCC_*
+        const int32_t* labels = nullptr;   // device: the label volume, -1 off the frontier
+    };
+    /**
+     * Exploration frontiers of the scene (include/emf_hip.h "Frontiers"): over the box
+     * [boxLo, boxLo + boxSize) of the background the occupancy classes exactly as distanceField() forms them (every live
+     * object not in excludeIds stamped as occupied), the free voxels that touch unknown space, their 26-connected
+     * clusters and one record per cluster of at least minVoxels voxels.  clearanceVoxels > 0: only frontier voxels at
+     * least that many voxels from the nearest occupied voxel of the box (the distance transform with sites = occupied).
+     * Enqueued on the main stream after the frame, in buffers of its own allocated at first use and reused; waits once
+     * for the number of clusters, which sizes the per-cluster tables, and once for the records, which are sorted on the
+     * host.  Changes nothing of the session -- the last distance field included -- and nothing goes into a checkpoint.
+     * Refused (EMF_E_ARG) on the sharded path.
+     */
+    const Frontiers& frontiers(const Vec3i& boxLo, const Vec3i& boxSize, int minVoxels, int clearanceVoxels,
+                               const std::vector<int>& excludeIds);
+    const Frontiers& lastFrontiers() const { return frLast; }
+    /** The centroid (sum / count) or the representative of a record in the world frame: the voxel plus
+     *  boxLo - (res - 1) / 2, times the voxel size, through the background's pose -- in double. */
+    static void frontierWorldPoint(const Frontiers& f, const emf_frontier_cluster_t& c, bool representative, double out[3]);
+    /** writeResults also writes frontiers.txt of the whole background (writeFrontiers); without it no output byte changes. */
+    void setFrontierOutput(bool on, int minVoxels = 8, float clearanceMetres = 0.f) {
+        expFrontiers_ = on;
+        frontierMinVoxels_ = minVoxels;
+        frontierClearanceMetres_ = clearanceMetres;
+    }
+    void writeFrontiers(const std::string& dir);
     /** Ids returned by initNewObjVolume for FrameInputs::newObjectMasks of the last frame (-1: none). */
     const std::vector<int>& lastCreatedObjects() const { return lastCreated; }
     Affine3f getCameraPose() const { return pose; }
@@ -693,6 +730,18 @@ private:
     DeviceBuffer dfClasses, dfD2, dfMetres;
     bool expDistance_ = false, distanceUnknownObstacle_ = false;  // setDistanceOutput
     float distanceCapMetres_ = 0.f;
+    // the steps distanceField() and frontiers() share: the box check, the drain, and classes + stamped objects into `classes`
+    void checkQueryBox(const char* who, const Vec3i& boxLo, const Vec3i& boxSize, unsigned long long& voxels) const;
+    void drainForQuery();
+    void enqueueOccupancy(const char* who, const Vec3i& boxLo, const Vec3i& boxSize, const std::vector<int>& excludeIds,
+                          uint8_t* classes, std::vector<int>* ids, std::vector<Affine3f>* poses);
+    Affine3f queryBoxPose(const Vec3i& boxLo) const;
+    // ---- frontiers (frontiers; EMFusionFrontier.cpp): allocated at first use, never in a checkpoint ----
+    Frontiers frLast;
+    DeviceBuffer frClasses, frD2, frLabels, frCounters, frScratch, frRecords;
+    bool expFrontiers_ = false;  // setFrontierOutput
+    int frontierMinVoxels_ = 8;
+    float frontierClearanceMetres_ = 0.f;
     TileStore bgStore;
     void retireSlabs(const Vec3i& shift, int frame);
     DeviceImage<float> depthFiltered;  // output of preprocessDepth

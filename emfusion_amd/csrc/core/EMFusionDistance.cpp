@@ -7,50 +7,57 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <limits>
 
 namespace emf {
 
-const EMFusion::DistanceField& EMFusion::distanceField(const Vec3i& boxLo, const Vec3i& boxSize, uint32_t siteMask, int capVoxels,
-                                                       const std::vector<int>& excludeIds, bool metres) {
+void EMFusion::checkQueryBox(const char* who, const Vec3i& boxLo, const Vec3i& boxSize, unsigned long long& voxels) const {
+    const std::string name = std::string("EMFusion::") + who;
     if (sharded || world > 1)
-        throw HipError("EMFusion::distanceField: the distance field is not supported on the sharded path", EMF_E_ARG);
+        throw HipError(name + ": " + (std::strcmp(who, "distanceField") == 0 ? "the distance field is" : "frontiers are") +
+                           " not supported on the sharded path",
+                       EMF_E_ARG);
     const Vec3i n = background.getVolumeRes();
-    unsigned long long voxels = 1;
+    voxels = 1;
     for (int i = 0; i < 3; ++i) {
         if (boxSize[i] < 1 || boxLo[i] < 0 || boxLo[i] > n[i] - boxSize[i])
-            throw HipError("EMFusion::distanceField: the box leaves the background on axis " + std::to_string(i), EMF_E_ARG);
+            throw HipError(name + ": the box leaves the background on axis " + std::to_string(i), EMF_E_ARG);
         if (boxSize[i] > EMF_DF_MAX_AXIS)
-            throw HipError("EMFusion::distanceField: a box axis of " + std::to_string(boxSize[i]) + " voxels", EMF_E_LIMIT);
+            throw HipError(name + ": a box axis of " + std::to_string(boxSize[i]) + " voxels", EMF_E_LIMIT);
         voxels *= static_cast<unsigned long long>(boxSize[i]);
     }
-    if (voxels > 0x7fffffffull) throw HipError("EMFusion::distanceField: a box of more than 2^31 - 1 voxels", EMF_E_LIMIT);
-    if (siteMask < 1u || siteMask > 7u) throw HipError("EMFusion::distanceField: siteMask outside 1 .. 7", EMF_E_ARG);
-    if (capVoxels < 0) throw HipError("EMFusion::distanceField: a negative cap", EMF_E_ARG);
-    // as worldMesh: nothing of this instance in flight, the front copies current
+    if (voxels > 0x7fffffffull) throw HipError(name + ": a box of more than 2^31 - 1 voxels", EMF_E_LIMIT);
+}
+
+// as worldMesh: nothing of this instance in flight, the front copies current
+void EMFusion::drainForQuery() {
     quiesce();
     refreshVisibleFromDevice();
     if (bgInFlight) joinBackground();
     quiesce();
-    // buffers of the types.hpp owner, at first use and whenever a larger box comes
-    if (dfClasses.bytes() < voxels) dfClasses = DeviceBuffer((voxels + 3) / 4 * 4);
-    if (dfD2.bytes() < voxels * sizeof(int32_t)) dfD2 = DeviceBuffer(voxels * sizeof(int32_t));
-    if (metres && dfMetres.bytes() < voxels * sizeof(float)) dfMetres = DeviceBuffer(voxels * sizeof(float));
+}
 
+Affine3f EMFusion::queryBoxPose(const Vec3i& boxLo) const {
+    const Vec3i n = background.getVolumeRes();
     const float voxel = background.getVoxelSize();
     const Affine3f bgPose = background.getPose();
-    DistanceField out;
-    out.boxLo = boxLo;
-    out.boxSize = boxSize;
-    out.voxelSize = voxel;
     const Vec3f corner((static_cast<float>(boxLo[0]) - static_cast<float>(n[0] - 1) / 2.f) * voxel,
                        (static_cast<float>(boxLo[1]) - static_cast<float>(n[1] - 1) / 2.f) * voxel,
                        (static_cast<float>(boxLo[2]) - static_cast<float>(n[2] - 1) / 2.f) * voxel);
-    out.boxPose = Affine3f(bgPose.rotation(), bgPose.rotation() * corner + bgPose.translation());
+    return Affine3f(bgPose.rotation(), bgPose.rotation() * corner + bgPose.translation());
+}
 
-    emfCheck(emf_hip_occupancyClasses(background.tsdfPtr(), background.weightsPtr(), n.val, boxLo.val, boxSize.val,
-                                      dfClasses.as<uint8_t>(), main.abi()),
-             "EMFusion::distanceField (classes)");
+// the classes of the box and the live objects stamped into them, on the main stream
+void EMFusion::enqueueOccupancy(const char* who, const Vec3i& boxLo, const Vec3i& boxSize, const std::vector<int>& excludeIds,
+                                uint8_t* classes, std::vector<int>* ids, std::vector<Affine3f>* poses) {
+    const std::string name = std::string("EMFusion::") + who;
+    const Vec3i n = background.getVolumeRes();
+    const float voxel = background.getVoxelSize();
+    const Affine3f bgPose = background.getPose();
+    emfCheck(emf_hip_occupancyClasses(background.tsdfPtr(), background.weightsPtr(), n.val, boxLo.val, boxSize.val, classes,
+                                      main.abi()),
+             (name + " (classes)").c_str());
     std::vector<emf_occ_object_t> table;
     for (const ObjTSDF& obj : objects) {
         if (std::find(excludeIds.begin(), excludeIds.end(), obj.getID()) != excludeIds.end()) continue;
@@ -64,15 +71,36 @@ const EMFusion::DistanceField& EMFusion::distanceField(const Vec3i& boxLo, const
         o.voxelSize = obj.getVoxelSize();
         std::copy(ob.rotation().val, ob.rotation().val + 9, o.R);
         std::copy(ob.translation().val, ob.translation().val + 3, o.t);
-        emfCheck(emf_hip_occupancyObjectBox(&o, n.val, voxel), "EMFusion::distanceField (object box)");
+        emfCheck(emf_hip_occupancyObjectBox(&o, n.val, voxel), (name + " (object box)").c_str());
         table.push_back(o);
-        out.objectIds.push_back(obj.getID());
-        out.objectPoses.push_back(ob);
+        if (ids) ids->push_back(obj.getID());
+        if (poses) poses->push_back(ob);
     }
     if (!table.empty())
-        emfCheck(emf_hip_occupancyStampObjects(dfClasses.as<uint8_t>(), n.val, voxel, boxLo.val, boxSize.val, table.data(),
+        emfCheck(emf_hip_occupancyStampObjects(classes, n.val, voxel, boxLo.val, boxSize.val, table.data(),
                                                static_cast<int32_t>(table.size()), main.abi()),
-                 "EMFusion::distanceField (objects)");
+                 (name + " (objects)").c_str());
+}
+
+const EMFusion::DistanceField& EMFusion::distanceField(const Vec3i& boxLo, const Vec3i& boxSize, uint32_t siteMask, int capVoxels,
+                                                       const std::vector<int>& excludeIds, bool metres) {
+    unsigned long long voxels = 1;
+    checkQueryBox("distanceField", boxLo, boxSize, voxels);
+    if (siteMask < 1u || siteMask > 7u) throw HipError("EMFusion::distanceField: siteMask outside 1 .. 7", EMF_E_ARG);
+    if (capVoxels < 0) throw HipError("EMFusion::distanceField: a negative cap", EMF_E_ARG);
+    drainForQuery();
+    // buffers of the types.hpp owner, at first use and whenever a larger box comes
+    if (dfClasses.bytes() < voxels) dfClasses = DeviceBuffer((voxels + 3) / 4 * 4);
+    if (dfD2.bytes() < voxels * sizeof(int32_t)) dfD2 = DeviceBuffer(voxels * sizeof(int32_t));
+    if (metres && dfMetres.bytes() < voxels * sizeof(float)) dfMetres = DeviceBuffer(voxels * sizeof(float));
+
+    const float voxel = background.getVoxelSize();
+    DistanceField out;
+    out.boxLo = boxLo;
+    out.boxSize = boxSize;
+    out.voxelSize = voxel;
+    out.boxPose = queryBoxPose(boxLo);
+    enqueueOccupancy("distanceField", boxLo, boxSize, excludeIds, dfClasses.as<uint8_t>(), &out.objectIds, &out.objectPoses);
     emfCheck(emf_hip_distanceTransform(dfClasses.as<uint8_t>(), boxSize.val, siteMask, capVoxels, dfD2.as<int32_t>(),
                                        metres ? dfMetres.as<float>() : nullptr, voxel, main.abi()),
              "EMFusion::distanceField (transform)");

@@ -643,6 +643,71 @@ int emf_fusion_set_distance_output(emf_fusion_t* h, int on, float cap_metres, in
     return guarded([&] { h->impl->setDistanceOutput(on != 0, cap_metres, unknown_is_obstacle != 0); });
 }
 
+int emf_fusion_frontiers(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], int32_t min_voxels,
+                         int32_t clearance_voxels, const int32_t* exclude_ids, int32_t num_exclude, int32_t lo_out[3],
+                         int32_t size_out[3], float R[9], float t[3], uint32_t counters[3]) {
+    REQ(h);
+    if (num_exclude < 0 || (num_exclude > 0 && !exclude_ids)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_frontiers: %d excluded ids without a list", num_exclude);
+        return EMF_E_ARG;
+    }
+    if ((box_lo == nullptr) != (box_size == nullptr)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_frontiers: box_lo and box_size go together");
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const Vec3i n = h->impl->getBackground().getVolumeRes();
+        const Vec3i lo = box_lo ? Vec3i(box_lo[0], box_lo[1], box_lo[2]) : Vec3i(0, 0, 0);
+        const Vec3i size = box_size ? Vec3i(box_size[0], box_size[1], box_size[2]) : n;
+        const std::vector<int> exclude(exclude_ids, exclude_ids + num_exclude);
+        const EMFusion::Frontiers& f = h->impl->frontiers(lo, size, min_voxels, clearance_voxels, exclude);
+        if (lo_out) std::memcpy(lo_out, f.boxLo.val, sizeof(f.boxLo.val));
+        if (size_out) std::memcpy(size_out, f.boxSize.val, sizeof(f.boxSize.val));
+        if (R) std::memcpy(R, f.boxPose.rotation().val, 9 * sizeof(float));
+        if (t) std::memcpy(t, f.boxPose.translation().val, 3 * sizeof(float));
+        if (counters) {
+            counters[EMF_FRONTIER_KEPT] = f.kept;
+            counters[EMF_FRONTIER_CLUSTERS] = f.all;
+            counters[EMF_FRONTIER_VOXELS] = f.voxels;
+        }
+    });
+}
+
+int emf_fusion_copy_frontiers(emf_fusion_t* h, emf_frontier_cluster_t* records, int32_t capacity, double* rep_world,
+                              double* centroid_world, int32_t* labels) {
+    REQ(h);
+    if (capacity < 0) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_copy_frontiers: capacity %d", capacity);
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const EMFusion::Frontiers& f = h->impl->lastFrontiers();
+        if (!f.labels) throw HipError("emf_fusion_copy_frontiers: no frontiers have been computed", EMF_E_ARG);
+        const size_t n = std::min<size_t>(f.clusters.size(), static_cast<size_t>(capacity));
+        for (size_t k = 0; k < n; ++k) {
+            if (records) records[k] = f.clusters[k];
+            if (rep_world) EMFusion::frontierWorldPoint(f, f.clusters[k], true, rep_world + 3 * k);
+            if (centroid_world) EMFusion::frontierWorldPoint(f, f.clusters[k], false, centroid_world + 3 * k);
+        }
+        if (labels) {
+            const size_t voxels = static_cast<size_t>(f.boxSize[0]) * f.boxSize[1] * f.boxSize[2];
+            Stream& s = h->impl->mainStream();
+            hipCheck(hipMemcpyAsync(labels, f.labels, voxels * sizeof(int32_t), hipMemcpyDeviceToHost, s.get()), "copy_frontiers");
+            s.waitForCompletion();
+        }
+    });
+}
+
+int emf_fusion_set_frontier_output(emf_fusion_t* h, int on, int32_t min_voxels, float clearance_metres) {
+    REQ(h);
+    if (min_voxels < 1 || !(clearance_metres >= 0.f)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_set_frontier_output: min_voxels %d, clearance %g", min_voxels,
+                      static_cast<double>(clearance_metres));
+        return EMF_E_ARG;
+    }
+    return guarded([&] { h->impl->setFrontierOutput(on != 0, min_voxels, clearance_metres); });
+}
+
 int emf_fusion_follow_shift(const float q[3], const int32_t step[3], float voxel_size, int32_t shift[3]) {
     REQ(q);
     REQ(step);

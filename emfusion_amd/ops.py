@@ -1685,3 +1685,60 @@ def distance_field(tsdf, weights, voxel_size, box=None, objects=None, site_mask=
     classes = occupancy_classes(tsdf, weights, box=box, objects=objects, voxel_size=voxel_size, stream=stream)
     r = distance_transform(classes, site_mask=site_mask, cap=cap, voxel_size=voxel_size if metres else None, stream=stream)
     return (classes, r[0], r[1]) if metres else (classes, r, None)
+
+
+# ---- frontiers (include/emf_hip.h "Frontiers") ---------------------------------------------------
+
+FRONTIER_KEPT, FRONTIER_CLUSTERS, FRONTIER_VOXELS = _lib.FRONTIER_KEPT, _lib.FRONTIER_CLUSTERS, _lib.FRONTIER_VOXELS
+FRONTIER_CLUSTER_DTYPE = np.dtype(_lib.FRONTIER_CLUSTER_DTYPE)
+assert FRONTIER_CLUSTER_DTYPE.itemsize == C.sizeof(_lib.EmfFrontierCluster) == 72
+
+
+def frontier_labels(classes, d2=None, min_d2=0, out=None, stream=None):
+    """emf_hip_frontierLabel of a (nz, ny, nx) u8 class volume: labels (nz, ny, nx) i32, the smallest linear index of
+    the voxel's 26-connected cluster of frontier voxels (FREE with an UNKNOWN face neighbour inside the volume and,
+    with d2 (nz, ny, nx) i32 and min_d2 > 0, d2 >= min_d2), -1 elsewhere.  labels.counters: u32 x 3 on the device,
+    [FRONTIER_CLUSTERS] and [FRONTIER_VOXELS] written, [FRONTIER_KEPT] zero.  out: a labels array to reuse."""
+    assert classes.dtype == np.uint8 and len(classes.shape) == 3 and not classes.padded
+    assert d2 is None or (d2.dtype == np.int32 and d2.shape == classes.shape and not d2.padded)
+    labels = out if out is not None else DeviceArray(classes.shape, np.int32)
+    assert labels.shape == classes.shape and labels.dtype == np.int32 and not labels.padded
+    if getattr(labels, "counters", None) is None:
+        labels.counters = DeviceArray((3,), np.uint32)
+    check("emf_hip_frontierLabel",
+          _L.emf_hip_frontierLabel(_ptr(classes), _i3(classes.shape[::-1]), _ptr(d2), int(min_d2), _ptr(labels),
+                                   _ptr(labels.counters), _stream(stream)))
+    return labels
+
+
+def frontier_clusters(labels, min_voxels=1, capacity=None, records=None, stream=None):
+    """emf_hip_frontierClusters of what frontier_labels returned: (records, counts) -- records a numpy array of
+    FRONTIER_CLUSTER_DTYPE, the clusters of at least min_voxels voxels in ascending label order, at most capacity of
+    them (None: all); counts the three counters as a tuple (kept, clusters, voxels), always the full numbers.  Waits
+    once for the number of clusters, which sizes the scratch, and once for the result.  records: a device array of
+    capacity FRONTIER_CLUSTER_DTYPE entries to write into (then returned as it is instead of a numpy array)."""
+    assert labels.dtype == np.int32 and len(labels.shape) == 3 and not labels.padded
+    counters = labels.counters
+    size = _i3(labels.shape[::-1])
+    n_clusters = int(counters.numpy()[FRONTIER_CLUSTERS])
+    cap = n_clusters if capacity is None else int(capacity)
+    own = records is None
+    if own:
+        records = DeviceArray((max(cap, 0),), FRONTIER_CLUSTER_DTYPE)
+    else:
+        assert records.dtype == FRONTIER_CLUSTER_DTYPE and records.shape == (cap,)
+    scratch = DeviceArray((max(int(_L.emf_hip_frontierScratchBytes(size, n_clusters)), 16),), np.uint8)
+    check("emf_hip_frontierClusters",
+          _L.emf_hip_frontierClusters(_ptr(labels), size, int(min_voxels), n_clusters, _ptr(scratch),
+                                      _ptr(records) if cap > 0 else None, cap, _ptr(counters), _stream(stream)))
+    counts = tuple(int(v) for v in counters.numpy())
+    if not own:
+        return records, counts
+    return records.numpy()[:min(counts[FRONTIER_KEPT], max(cap, 0))], counts
+
+
+def frontiers(classes, d2=None, min_d2=0, min_voxels=1, capacity=None, stream=None):
+    """frontier_labels then frontier_clusters: (labels, records, (kept, clusters, voxels))."""
+    labels = frontier_labels(classes, d2=d2, min_d2=min_d2, stream=stream)
+    records, counts = frontier_clusters(labels, min_voxels=min_voxels, capacity=capacity, stream=stream)
+    return labels, records, counts

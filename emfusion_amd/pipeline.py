@@ -135,6 +135,9 @@ def load() -> C.CDLL:
         "emf_fusion_copy_distance_field": [vp, C.c_void_p, C.c_void_p, C.c_void_p],
         "emf_fusion_distance_field_objects": [vp, ip, fp, fp, C.c_int, ip],
         "emf_fusion_set_distance_output": [vp, C.c_int, C.c_float, C.c_int],
+        "emf_fusion_frontiers": [vp, ip, ip, C.c_int32, C.c_int32, ip, C.c_int32, ip, ip, fp, fp, C.c_void_p],
+        "emf_fusion_copy_frontiers": [vp, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+        "emf_fusion_set_frontier_output": [vp, C.c_int, C.c_int32, C.c_float],
         "emf_fusion_process_rgbd_color": [vp, fp, C.c_void_p, C.c_int32, C.c_int32],
         "emf_fusion_colored_voxels": [vp, C.POINTER(C.c_uint64)],
         "emf_fusion_get_last_masks": [vp, C.c_void_p, C.c_size_t, ip],
@@ -835,6 +838,65 @@ class Fusion:
             out.update(d2_inside=d2_in, metres_inside=m_in, signed=np.where(m > 0, m, -m_in).astype(np.float32))
         return out
 
+    def frontiers(self, box=None, min_voxels=8, clearance=0.0, exclude=(), labels=False, size=None):
+        """Exploration frontiers of the scene: where the known map ends.  Over a box of the background
+        as for distance_field -- None, ((x, y, z) lo, (x, y, z) size) or "camera" with `size` -- and on the same
+        occupancy classes (every live object not in `exclude` stamped as occupied): the free voxels with an unknown face
+        neighbour inside the box, grouped into 26-connected clusters; clusters of fewer than min_voxels voxels are
+        dropped.  clearance (metres, rounded up to whole voxels; 0: none): only frontier voxels at least that far from
+        the nearest occupied voxel of the box, i.e. where a robot of that radius can stand.  Returns a dict:
+          clusters: a list of dicts, largest first (ties: smallest label), each with label, count, lo and hi (the
+          inclusive bounding box), sum (of the members' coordinates) and rep (the representative voxel, a member of the
+          cluster nearest its centroid) -- integers, (x, y, z) in box coordinates -- and centroid_world, rep_world:
+          float32 points in the world frame, computed from those integers in float64 and rounded once;
+          box (lo, size); box_pose (R 3x3, t 3) of voxel (0, 0, 0) of the box -> world; voxel_size;
+          kept, n_clusters, n_voxels: clusters kept, all clusters, frontier voxels;
+          labels (bz, by, bx) i32 with labels=True: the label of the voxel's cluster, -1 off the frontier."""
+        from ._lib import FRONTIER_CLUSTER_DTYPE
+        if isinstance(box, str):
+            if box != "camera" or size is None:
+                raise ValueError('frontiers: box="camera" needs a size')
+            box = self.camera_box(size)
+            if box is None:
+                raise ValueError("frontiers: the camera box lies outside the background")
+        vs = float(self.params.bg_voxel_size)
+        clearance_voxels = min(int(np.ceil(np.float32(clearance) / np.float32(vs))), 4096) if clearance > 0 else 0
+        ex = (C.c_int32 * max(len(exclude), 1))(*[int(i) for i in exclude])
+        lo_arg = size_arg = None
+        if box is not None:
+            lo_arg, size_arg = (C.c_int32 * 3)(*[int(v) for v in box[0]]), (C.c_int32 * 3)(*[int(v) for v in box[1]])
+        lo, sz, R, t = (C.c_int32 * 3)(), (C.c_int32 * 3)(), (C.c_float * 9)(), (C.c_float * 3)()
+        counters = np.zeros(3, np.uint32)
+        _check("emf_fusion_frontiers",
+               load().emf_fusion_frontiers(self._h, lo_arg, size_arg, int(min_voxels), clearance_voxels, ex, len(exclude), lo,
+                                           sz, R, t, counters.ctypes.data))
+        kept = int(counters[0])
+        records = np.zeros(kept, np.dtype(FRONTIER_CLUSTER_DTYPE))
+        volume = np.empty((sz[2], sz[1], sz[0]), np.int32) if labels else None
+        _check("emf_fusion_copy_frontiers",
+               load().emf_fusion_copy_frontiers(self._h, records.ctypes.data if kept else None, kept, None, None,
+                                                volume.ctypes.data if labels else None))
+        # the world points: from the integers, in float64, rounded once
+        bg_R, bg_t = self.background_pose()
+        off = np.array(list(lo), np.float64) - (np.array(list(self.params.bg_res), np.float64) - 1) / 2
+
+        def world(v):
+            p = (v + off) * np.float64(vs)
+            return (p @ bg_R.astype(np.float64).T + bg_t.astype(np.float64)).astype(np.float32)
+
+        centroid = world(records["sum"].astype(np.float64) / np.maximum(records["count"], 1).astype(np.float64)[:, None])
+        rep = world(records["rep"].astype(np.float64))
+        clusters = [dict(label=int(r["label"]), count=int(r["count"]), lo=tuple(int(v) for v in r["lo"]),
+                         hi=tuple(int(v) for v in r["hi"]), sum=tuple(int(v) for v in r["sum"]),
+                         rep=tuple(int(v) for v in r["rep"]), centroid_world=centroid[k], rep_world=rep[k])
+                    for k, r in enumerate(records)]
+        out = dict(clusters=clusters, centroid_world=centroid, rep_world=rep, box=(tuple(lo), tuple(sz)),
+                   box_pose=(np.array(R, np.float32).reshape(3, 3), np.array(t, np.float32)), voxel_size=vs, kept=kept,
+                   n_clusters=int(counters[1]), n_voxels=int(counters[2]), records=records)
+        if labels:
+            out["labels"] = volume
+        return out
+
     def last_motion_masks(self):
         """The proposals of the last processed frame: ((H, W) i32 image of proposal ranks, -1 where none is, list of
         dicts {label, area, x0, y0, x1, y1} by rank).  Empty / all -1 if the frame proposed nothing."""
@@ -1030,12 +1092,15 @@ class Fusion:
         _check("emf_fusion_enable_pose_log", load().emf_fusion_enable_pose_log(self._h, int(on)))
 
     def setup_output(self, exp_frame_meshes=False, exp_vols=False, exp_world_mesh=False, exp_distance_field=False,
-                     distance_cap=0.0, distance_unknown_is_obstacle=False):
+                     distance_cap=0.0, distance_unknown_is_obstacle=False, exp_frontiers=False, frontier_min_voxels=8,
+                     frontier_clearance=0.0):
         """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
         the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
         the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh();
         exp_distance_field: write_results also writes distance.bin (f32 metres to the nearest obstacle of the whole
-        background, +inf beyond distance_cap metres or without an obstacle) and occupancy.bin (u8 classes)."""
+        background, +inf beyond distance_cap metres or without an obstacle) and occupancy.bin (u8 classes);
+        exp_frontiers: write_results also writes frontiers.txt, one line per frontier cluster of the whole background
+        of at least frontier_min_voxels voxels, largest first (include/emf_fusion.h emf_fusion_set_frontier_output)."""
         _check("emf_fusion_setup_output",
                load().emf_fusion_setup_output(self._h, int(exp_frame_meshes), int(exp_vols)))
         _check("emf_fusion_set_world_mesh_output",
@@ -1043,6 +1108,9 @@ class Fusion:
         _check("emf_fusion_set_distance_output",
                load().emf_fusion_set_distance_output(self._h, int(bool(exp_distance_field)), float(distance_cap),
                                                      int(bool(distance_unknown_is_obstacle))))
+        _check("emf_fusion_set_frontier_output",
+               load().emf_fusion_set_frontier_output(self._h, int(bool(exp_frontiers)), int(frontier_min_voxels),
+                                                     float(frontier_clearance)))
 
     def write_results(self, directory: str, volumes: bool = True):
         """poses-*.txt, mesh_bg.ply, mesh_<id>.ply always; tsdfs/*.bin with `volumes` (reference formats)."""

@@ -257,6 +257,32 @@ int emf_fusion_distance_field_objects(emf_fusion_t* h, int32_t* ids, float* R, f
  * with unknown_is_obstacle -- of the whole background, +inf beyond cap_metres, which is rounded up to whole voxels; 0:
  * no cap) and occupancy.bin (u8 classes), both in the container of the tsdfs/ dumps.  Off: no output byte changes. */
 int emf_fusion_set_distance_output(emf_fusion_t* h, int on, float cap_metres, int unknown_is_obstacle);
+/* Exploration frontiers of the scene (include/emf_hip.h "Frontiers"; new behaviour, nothing of the
+ * session changes -- the last distance field included -- and nothing goes into a checkpoint).  Over the box of the
+ * background as for emf_fusion_distance_field, on the same occupancy classes (every live object whose id is not in
+ * exclude_ids stamped as occupied): the free voxels with an unknown face neighbour inside the box -- with
+ * clearance_voxels > 0 only those at least that many voxels from the nearest occupied voxel of the box -- their
+ * 26-connected clusters, and one record per cluster of at least min_voxels (>= 1) voxels.  Enqueued on the main stream
+ * after the frame; waits for the number of clusters and for the records, which are kept sorted by count descending,
+ * ties by label ascending, until the next call.  lo_out / size_out / R / t (may be NULL): the box and the pose of its
+ * voxel (0, 0, 0) -> world, as emf_fusion_distance_field returns them.  counters (may be NULL): kept clusters, all
+ * clusters, frontier voxels (EMF_FRONTIER_*).  EMF_E_ARG on a sharded session ("not supported on the sharded path"). */
+int emf_fusion_frontiers(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], int32_t min_voxels,
+                         int32_t clearance_voxels, const int32_t* exclude_ids, int32_t num_exclude, int32_t lo_out[3],
+                         int32_t size_out[3], float R[9], float t[3], uint32_t counters[3]);
+/* The last frontiers: the first min(kept, capacity) records in the sorted order; per record (x, y, z) of the
+ * representative and of the centroid in the world frame, in double -- the voxel (rep, or sum / count) plus
+ * box_lo - (res - 1) / 2, times the voxel size, through the background's pose; and the label volume, one i32 per voxel
+ * of the box in (z, y, x) order (waits for the main stream).  Any of the four may be NULL. */
+int emf_fusion_copy_frontiers(emf_fusion_t* h, emf_frontier_cluster_t* records, int32_t capacity, double* rep_world,
+                              double* centroid_world, int32_t* labels);
+/* setup_output's exp_frontiers, as an entry of its own so that emf_fusion_setup_output keeps its signature:
+ * emf_fusion_write_results also writes frontiers.txt of the whole background -- after one comment line, one line per
+ * cluster of at least min_voxels voxels, largest first:  count (%d), x y z of the representative voxel and x y z of the
+ * centroid in the world frame (metres, the double value rounded once to float, %.9g each), and the inclusive bounding
+ * box lo_x lo_y lo_z hi_x hi_y hi_z in voxels of the background (%d).  clearance_metres is rounded up to whole voxels.
+ * Off: no output byte changes. */
+int emf_fusion_set_frontier_output(emf_fusion_t* h, int on, int32_t min_voxels, float clearance_metres);
 /* Remember what rolls out (new behaviour, off by default; with it off no launch, no output byte and no
  * checkpoint byte changes).  With the store on, the whole integration tiles (32 x 8 x 8) that a roll moves out of the
  * background go to host memory as the bytes they are, after the slabs are retired; the tiles that a later roll moves

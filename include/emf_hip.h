@@ -1596,6 +1596,67 @@ int emf_hip_occupancyStampObjects(uint8_t* classes, const int32_t res[3], float 
 int emf_hip_distanceTransform(const uint8_t* classes, const int32_t size[3], uint32_t site_mask, int32_t cap, int32_t* d2,
                               float* metres, float voxel_size, emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Frontiers (new behaviour: DESIGN.md 5.19).  Opt-in; nothing above is touched.  "Where does the known map end": the
+ * free voxels that touch unknown space, grouped into clusters, over a box of class bytes of shape size (x, y, z) as
+ * the steps above produce them.  Arrays are dense, (z, y, x) order, x fastest; what lies outside the box does not exist.
+ *   frontier voxel  a voxel v with class EMF_OCC_FREE of which at least one of the six face neighbours INSIDE the box
+ *                   is EMF_OCC_UNKNOWN (a class byte above 2 is neither free nor unknown) and, where a d2 array of the
+ *                   same shape (emf_hip_distanceTransform's output) is passed with min_d2 > 0, d2[v] >= min_d2
+ *                   (EMF_DF_FAR passes): the clearance gate.  d2 == NULL or min_d2 <= 0: no gate.
+ *   cluster         a 26-connected component of frontier voxels (3 x 3 x 3 neighbourhoods).  Its label is the smallest
+ *                   linear index (z * ny + y) * nx + x among its members.
+ *   label volume    one i32 per voxel: the label of the voxel's cluster, -1 where the voxel is no frontier voxel.
+ *   record          emf_frontier_cluster_t: label, count, the inclusive bounding box lo / hi, the sums of the members'
+ *                   x, y, z (box coordinates) and a representative voxel rep -- a MEMBER of the cluster (the centroid
+ *                   of a curved frontier can lie in unknown or occupied space): with the rounded centroid
+ *                   c = (2 * sum + count) / (2 * count) per axis (integer division), the member that minimises the
+ *                   integer |v - c|^2, ties to the smallest linear index -- the minimum of the 64-bit key
+ *                   (dist^2 << 31) | linear (dist^2 <= 3 * 2047^2 < 2^24, linear < 2^31).
+ *   filter, order   clusters with count < min_voxels (>= 1) are dropped; the kept records are written in ascending
+ *                   label order, placed by scan, at most capacity of them.  counters (3 x u32):
+ *                   [EMF_FRONTIER_KEPT] kept clusters, [EMF_FRONTIER_CLUSTERS] all clusters, [EMF_FRONTIER_VOXELS]
+ *                   frontier voxels -- always the full numbers, whatever capacity is.
+ * Integer arithmetic and integer atomics only: every output is a pure function of the inputs, bit for bit.
+ * Limits as for the distance field: every axis in 1 .. EMF_DF_MAX_AXIS, at most 2^31 - 1 voxels (EMF_E_LIMIT above).
+ * Every rejected argument -- a NULL pointer, a non-positive axis, min_voxels < 1, a negative capacity -- returns
+ * EMF_E_ARG or EMF_E_LIMIT with nothing enqueued.  Nothing allocates, copies to the host or waits.
+ * ---------------------------------------------------------------------------------------------- */
+#define EMF_FRONTIER_KEPT 0
+#define EMF_FRONTIER_CLUSTERS 1
+#define EMF_FRONTIER_VOXELS 2
+
+typedef struct emf_frontier_cluster {
+    int32_t label;         /* the smallest linear index of the cluster */
+    int32_t count;         /* voxels */
+    int32_t lo[3], hi[3];  /* inclusive bounding box (x, y, z), box coordinates */
+    uint64_t sum[3];       /* sums of the members' x, y, z */
+    int32_t rep[3];        /* the representative voxel (x, y, z) */
+    int32_t reserved;      /* 0 */
+} emf_frontier_cluster_t;  /* 72 bytes */
+
+/* Labels.  classes: size[0] * [1] * [2] bytes, only read; d2: NULL or as many i32, only read; labels: as many i32.
+ * Writes counters[EMF_FRONTIER_CLUSTERS] and [EMF_FRONTIER_VOXELS] and zeroes [EMF_FRONTIER_KEPT].  Flags (one wave per
+ * row, wave ballots), hooks (lock-free union-find over the label volume itself, 13 neighbours of smaller index per
+ * frontier voxel), flatten, count. */
+int emf_hip_frontierLabel(const uint8_t* classes, const int32_t size[3], const int32_t* d2, int32_t min_d2,
+                          int32_t* labels, uint32_t* counters, emf_stream_t stream);
+
+/* Host only, no device: the bytes of scratch emf_hip_frontierClusters needs for a box of this size that holds
+ * n_clusters clusters -- 4 bytes per 256 voxels + under 65 bytes per cluster + under 1 KiB.  0 for a size beyond the limits. */
+size_t emf_hip_frontierScratchBytes(const int32_t size[3], uint32_t n_clusters);
+
+/* Records of a label volume as emf_hip_frontierLabel leaves it.  n_clusters: counters[EMF_FRONTIER_CLUSTERS] as the
+ * host read it after the labelling -- the one number the host needs to size the per-cluster tables; a smaller value
+ * drops the clusters of the largest labels, a larger one only wastes scratch (no index ever leaves the tables).
+ * scratch_dev: emf_hip_frontierScratchBytes(size, n_clusters) bytes, 16-byte aligned; records: capacity entries (NULL
+ * with capacity 0).  Writes the first min(kept, capacity) records and counters[EMF_FRONTIER_KEPT]; with n_clusters == 0
+ * only the counter is cleared.  Roots by scan in index order, a voxel finds its cluster's slot by binary search of its
+ * label; per-slot statistics by integer atomics, merged per row and per workgroup before they touch global memory. */
+int emf_hip_frontierClusters(const int32_t* labels, const int32_t size[3], int32_t min_voxels, uint32_t n_clusters,
+                             void* scratch_dev, emf_frontier_cluster_t* records, int32_t capacity, uint32_t* counters,
+                             emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
