@@ -7,6 +7,7 @@
 //                  [--weld-meshes] [--mesh-min-triangles N] [--mesh-largest-object] [--mesh-simplify CELL] [--world-mesh]
 //                  [--distance-field] [--distance-cap M] [--distance-unknown-obstacle]
 //                  [--frontiers] [--frontier-min-voxels N] [--frontier-clearance M]
+//                  [--plan] [--plan-clearance M] [--plan-through-unknown]
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
 //                  [--bg-res R] [--bg-voxel M] [--obj-res R] [--volumes] --out DIR
 //   emfusion_synth --dir BASE/ [--colordir colour] [--depthdir depth] [--intrinsics fx fy cx cy] ... --out DIR
@@ -108,6 +109,11 @@ static float distanceCap = 0.f;
 static bool frontiersOut = false;
 static int frontierMinVoxels = 8;
 static float frontierClearance = 0.f;
+// --plan [--plan-clearance M] [--plan-through-unknown] (needs --out): writeResults also writes OUT/plan.txt, the plan
+// from the voxel under the last camera position to the representative of every kept frontier cluster of the
+// background (--frontier-min-voxels), M metres clear of the nearest occupied voxel.
+static bool planOut = false, planThroughUnknown = false;
+static float planClearance = 0.f;
 // --motion-masks [--motion-band M] [--motion-min-pixels N] [--motion-max-masks N]: mask frames propose their own
 // instance masks from the depth in front of the background model (EMFusion::setMotionMasks) instead of reading them
 static bool motionMasks = false;
@@ -212,6 +218,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     emf.setWorldMeshOutput(worldMeshOut);
     emf.setDistanceOutput(distanceOut, distanceCap, distanceUnknownObstacle);
     emf.setFrontierOutput(frontiersOut, frontierMinVoxels, frontierClearance);
+    emf.setPlanOutput(planOut, planClearance, planThroughUnknown);
     set3dView(emf, params, view3d);
     std::vector<uint8_t> rendered(3 * params.frameSize.area());
     const auto t0 = std::chrono::steady_clock::now();
@@ -322,6 +329,9 @@ int main(int argc, char** argv) {
         else if (a == "--frontiers") frontiersOut = true;
         else if (a == "--frontier-min-voxels" && i + 1 < argc) frontierMinVoxels = std::max(std::atoi(argv[++i]), 1);
         else if (a == "--frontier-clearance" && i + 1 < argc) frontierClearance = std::max(static_cast<float>(std::atof(argv[++i])), 0.f);
+        else if (a == "--plan") planOut = true;
+        else if (a == "--plan-clearance" && i + 1 < argc) planClearance = std::max(static_cast<float>(std::atof(argv[++i])), 0.f);
+        else if (a == "--plan-through-unknown") planThroughUnknown = true;
         else if (a == "--mesh-min-triangles") meshMinTriangles = static_cast<unsigned>(std::max(next(), 0));
         else if (a == "--mesh-largest-object") meshLargestObject = true;
         else if (a == "--mesh-simplify" && i + 1 < argc) meshSimplifyCell = static_cast<float>(std::atof(argv[++i]));
@@ -427,6 +437,7 @@ int main(int argc, char** argv) {
         emf.setWorldMeshOutput(worldMeshOut);
         emf.setDistanceOutput(distanceOut, distanceCap, distanceUnknownObstacle);
         emf.setFrontierOutput(frontiersOut, frontierMinVoxels, frontierClearance);
+        emf.setPlanOutput(planOut, planClearance, planThroughUnknown);
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);
 

@@ -80,6 +80,13 @@ def main():
                     help="with --frontiers: drop clusters of fewer than N voxels (default 8)")
     ap.add_argument("--frontier-clearance", dest="frontier_clearance", type=float, default=0.0, metavar="M",
                     help="with --frontiers: only frontier voxels at least M metres from the nearest occupied voxel")
+    ap.add_argument("--plan", dest="plan", action="store_true",
+                    help="also write OUT/plan.txt: the plan from the voxel under the last camera position to every kept "
+                         "frontier cluster of the background (reachable, cost, length, path)")
+    ap.add_argument("--plan-clearance", dest="plan_clearance", type=float, default=0.0, metavar="M",
+                    help="with --plan: keep paths and goals at least M metres from the nearest occupied voxel")
+    ap.add_argument("--plan-through-unknown", dest="plan_through_unknown", action="store_true",
+                    help="with --plan: unobserved voxels are traversable too")
     ap.add_argument("--weld-meshes", dest="weld_meshes", action="store_true",
                     help="weld every mesh written (mesh_*.ply of the live models, frame_meshes/) by grid edge on the "
                          "device: one vertex per edge instead of one per cube that touches it")
@@ -177,7 +184,8 @@ def main():
     fus.setup_output(args.frame_meshes, args.volumes, args.world_mesh, exp_distance_field=args.distance_field,
                      distance_cap=max(args.distance_cap, 0.0), distance_unknown_is_obstacle=args.distance_unknown,
                      exp_frontiers=args.frontiers, frontier_min_voxels=max(args.frontier_min_voxels, 1),
-                     frontier_clearance=max(args.frontier_clearance, 0.0))  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
+                     frontier_clearance=max(args.frontier_clearance, 0.0), exp_plan=args.plan,
+                     plan_clearance=max(args.plan_clearance, 0.0), plan_through_unknown=args.plan_through_unknown)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
     if args.vis3d:  # the reference's window (apps/EM-Fusion.cpp:118-131), or a viewer placed with look_at
         R3, t3, K3, size3 = pipeline.default_3d_view(prm)
         if args.vis3d_eye:

@@ -210,6 +210,10 @@ SIGNATURES = {
     "emf_hip_frontierLabel": [_FP, _I3, _FP, C.c_int32, _FP, _FP, _STREAM],
     "emf_hip_frontierScratchBytes": [_I3, C.c_uint32],
     "emf_hip_frontierClusters": [_FP, _I3, C.c_int32, C.c_uint32, _FP, _FP, C.c_int32, _FP, _STREAM],
+    "emf_hip_planScratchBytes": [_I3],
+    "emf_hip_planCost": [_FP, _I3, _FP, C.c_int32, C.c_uint32, _FP, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, _FP, _FP,
+                         _FP, _STREAM],
+    "emf_hip_planPaths": [_FP, _I3, _FP, C.c_int32, C.c_int32, _FP, _FP, _FP, _STREAM],
 }
 
 
@@ -271,6 +275,9 @@ class EmfFrontierCluster(C.Structure):
 FRONTIER_CLUSTER_DTYPE = [("label", "<i4"), ("count", "<i4"), ("lo", "<i4", 3), ("hi", "<i4", 3), ("sum", "<u8", 3),
                           ("rep", "<i4", 3), ("reserved", "<i4")]
 FRONTIER_KEPT, FRONTIER_CLUSTERS, FRONTIER_VOXELS = 0, 1, 2
+# include/emf_hip.h "Planning"
+PLAN_UNREACHED, PLAN_BLOCKED = 0xffffffff, 0xfffffffe
+PLAN_CONVERGED, PLAN_ROUNDS, PLAN_FINITE, PLAN_SEEDS = 0, 1, 2, 3
 
 
 class EmfPose(C.Structure):
@@ -377,6 +384,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.emf_hip_meshTilesScratchBytes.restype = C.c_size_t
     lib.emf_hip_motionMasksScratchBytes.restype = C.c_size_t
     lib.emf_hip_frontierScratchBytes.restype = C.c_size_t
+    lib.emf_hip_planScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateCullScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateDirtyMapBytes.restype = C.c_size_t
     lib.emf_hip_signMapBytes.restype = C.c_size_t

@@ -418,6 +418,56 @@ public:
         frontierClearanceMetres_ = clearanceMetres;
     }
     void writeFrontiers(const std::string& dir);
+    /** What the last plan() computed; the device arrays stay valid until the next one. */
+    struct Plan {
+        Vec3i boxLo, boxSize;  // voxels of the background, (x, y, z)
+        Affine3f boxPose;      // voxel (0, 0, 0) of the box -> world, as DistanceField::boxPose
+        Affine3f bgPose;       // the background's pose the world points go through
+        Vec3i bgRes;
+        float voxelSize = 0.f;
+        int seedRadiusVoxels = 0, clearanceVoxels = 0;
+        bool throughUnknown = false;
+        uint32_t maxCost = 0;
+        uint32_t counters[4] = {0u, 0u, 0u, 0u};  // EMF_PLAN_*: converged, rounds, voxels with a finite cost, seeds used
+        struct Goal {
+            Vec3i voxel;                         // box coordinates
+            uint32_t cost = EMF_PLAN_BLOCKED;    // EMF_PLAN_UNREACHED / EMF_PLAN_BLOCKED: no path
+            int32_t length = 0;                  // voxels of the whole path, the goal first (0: none)
+            int32_t faces = 0, edges = 0, corners = 0;  // its steps by kind (of the whole path where it was kept whole)
+            std::vector<int32_t> path;           // linear indices of the box, at most pathCapacity of them
+        };
+        std::vector<Goal> goals;
+        const uint8_t* classes = nullptr;  // device, box (z, y, x) order: EMF_OCC_*
+        const uint32_t* cost = nullptr;    // device: the cost field
+    };
+    /**
+     * Path planning over the scene (include/emf_hip.h "Planning"): over the box [boxLo, boxLo + boxSize)
+     * of the background, on the occupancy classes exactly as frontiers() forms them (every live object not in excludeIds
+     * stamped as occupied), the cost-to-go field from startVoxels (box coordinates) through the free voxels -- and the
+     * unknown ones with throughUnknown -- that are at least clearanceVoxels from the nearest occupied voxel of the box
+     * (the capped transform, as frontiers()), plus the start bubble of seedRadiusVoxels; maxCost 0: no cap.  Then the
+     * paths from goalVoxels (box coordinates) back to a start: pathCapacity < 0 keeps every path whole (one more wait,
+     * for the lengths), otherwise at most that many voxels of each.  Enqueued on the main stream after the frame, in
+     * buffers of its own allocated at first use and reused; waits for the rounds' activity counters and the results.
+     * Changes nothing of the session -- the last distance field and the last frontiers included -- and nothing goes into
+     * a checkpoint.  Refused (EMF_E_ARG) on the sharded path; a box of more than 2^29 voxels is EMF_E_LIMIT.
+     */
+    const Plan& plan(const Vec3i& boxLo, const Vec3i& boxSize, const std::vector<Vec3i>& startVoxels, int seedRadiusVoxels,
+                     bool throughUnknown, int clearanceVoxels, uint32_t maxCost, const std::vector<Vec3i>& goalVoxels,
+                     int pathCapacity, const std::vector<int>& excludeIds);
+    const Plan& lastPlan() const { return plLast; }
+    /** A voxel of the plan's box in the world frame, as frontierWorldPoint: in double. */
+    static void planWorldPoint(const Plan& p, int32_t linear, double out[3]);
+    /** The background voxel under the camera: rint(R^T (camera - t) / voxel + (res - 1) / 2), in double, clamped to
+     *  the volume -- the nearest voxel of the background where the camera stands outside it. */
+    Vec3i cameraVoxel() const;
+    /** writeResults also writes plan.txt of the whole background from the camera (writePlan); without it no output byte changes. */
+    void setPlanOutput(bool on, float clearanceMetres = 0.f, bool throughUnknown = false) {
+        expPlan_ = on;
+        planClearanceMetres_ = clearanceMetres;
+        planThroughUnknown_ = throughUnknown;
+    }
+    void writePlan(const std::string& dir);
     /** Ids returned by initNewObjVolume for FrameInputs::newObjectMasks of the last frame (-1: none). */
     const std::vector<int>& lastCreatedObjects() const { return lastCreated; }
     Affine3f getCameraPose() const { return pose; }
@@ -742,6 +792,11 @@ private:
     bool expFrontiers_ = false;  // setFrontierOutput
     int frontierMinVoxels_ = 8;
     float frontierClearanceMetres_ = 0.f;
+    // ---- planning (plan; EMFusionPlan.cpp): allocated at first use, never in a checkpoint ----
+    Plan plLast;
+    DeviceBuffer plClasses, plD2, plCost, plScratch, plCounters, plSeeds, plGoals, plPaths, plLengths, plGoalCost;
+    bool expPlan_ = false, planThroughUnknown_ = false;  // setPlanOutput
+    float planClearanceMetres_ = 0.f;
     TileStore bgStore;
     void retireSlabs(const Vec3i& shift, int frame);
     DeviceImage<float> depthFiltered;  // output of preprocessDepth

@@ -15,7 +15,10 @@ namespace emf {
 void EMFusion::checkQueryBox(const char* who, const Vec3i& boxLo, const Vec3i& boxSize, unsigned long long& voxels) const {
     const std::string name = std::string("EMFusion::") + who;
     if (sharded || world > 1)
-        throw HipError(name + ": " + (std::strcmp(who, "distanceField") == 0 ? "the distance field is" : "frontiers are") +
+        throw HipError(name + ": " +
+                           (std::strcmp(who, "distanceField") == 0 ? "the distance field is"
+                            : std::strcmp(who, "plan") == 0        ? "planning is"
+                                                                   : "frontiers are") +
                            " not supported on the sharded path",
                        EMF_E_ARG);
     const Vec3i n = background.getVolumeRes();

@@ -708,6 +708,97 @@ int emf_fusion_set_frontier_output(emf_fusion_t* h, int on, int32_t min_voxels, 
     return guarded([&] { h->impl->setFrontierOutput(on != 0, min_voxels, clearance_metres); });
 }
 
+int emf_fusion_plan(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], const int32_t* start_voxels,
+                    int32_t num_start, int32_t seed_radius_voxels, int through_unknown, int32_t clearance_voxels,
+                    uint32_t max_cost, const int32_t* goal_voxels, int32_t num_goals, int32_t path_capacity,
+                    const int32_t* exclude_ids, int32_t num_exclude, int32_t lo_out[3], int32_t size_out[3], float R[9],
+                    float t[3], uint32_t counters[4], int32_t* longest_path) {
+    REQ(h);
+    if (num_exclude < 0 || (num_exclude > 0 && !exclude_ids) || num_goals < 0 || (num_goals > 0 && !goal_voxels) ||
+        num_start < 0 || (num_start > 0 && !start_voxels)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_plan: %d start voxels, %d goals or %d excluded ids without a list",
+                      num_start, num_goals, num_exclude);
+        return EMF_E_ARG;
+    }
+    if ((box_lo == nullptr) != (box_size == nullptr)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_plan: box_lo and box_size go together");
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const Vec3i n = h->impl->getBackground().getVolumeRes();
+        const Vec3i lo = box_lo ? Vec3i(box_lo[0], box_lo[1], box_lo[2]) : Vec3i(0, 0, 0);
+        const Vec3i size = box_size ? Vec3i(box_size[0], box_size[1], box_size[2]) : n;
+        std::vector<Vec3i> start, goals;
+        if (num_start == 0) {  // the voxel under the camera
+            const Vec3i c = h->impl->cameraVoxel();
+            start.push_back(Vec3i(c[0] - lo[0], c[1] - lo[1], c[2] - lo[2]));
+        }
+        for (int32_t k = 0; k < num_start; ++k) start.push_back(Vec3i(start_voxels[3 * k], start_voxels[3 * k + 1], start_voxels[3 * k + 2]));
+        for (int32_t k = 0; k < num_goals; ++k) goals.push_back(Vec3i(goal_voxels[3 * k], goal_voxels[3 * k + 1], goal_voxels[3 * k + 2]));
+        const std::vector<int> exclude(exclude_ids, exclude_ids + num_exclude);
+        const EMFusion::Plan& p = h->impl->plan(lo, size, start, seed_radius_voxels, through_unknown != 0, clearance_voxels,
+                                                max_cost, goals, path_capacity, exclude);
+        if (lo_out) std::memcpy(lo_out, p.boxLo.val, sizeof(p.boxLo.val));
+        if (size_out) std::memcpy(size_out, p.boxSize.val, sizeof(p.boxSize.val));
+        if (R) std::memcpy(R, p.boxPose.rotation().val, 9 * sizeof(float));
+        if (t) std::memcpy(t, p.boxPose.translation().val, 3 * sizeof(float));
+        if (counters) std::memcpy(counters, p.counters, sizeof(p.counters));
+        if (longest_path) {
+            *longest_path = 0;
+            for (const EMFusion::Plan::Goal& g : p.goals) *longest_path = std::max<int32_t>(*longest_path, static_cast<int32_t>(g.path.size()));
+        }
+    });
+}
+
+int emf_fusion_copy_plan(emf_fusion_t* h, uint32_t* goal_cost, int32_t* lengths, int32_t* steps, int32_t* paths,
+                         int32_t capacity, double* path_world, uint32_t* cost) {
+    REQ(h);
+    if (capacity < 0) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_copy_plan: capacity %d", capacity);
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const EMFusion::Plan& p = h->impl->lastPlan();
+        if (!p.cost) throw HipError("emf_fusion_copy_plan: no plan has been computed", EMF_E_ARG);
+        for (size_t g = 0; g < p.goals.size(); ++g) {
+            const EMFusion::Plan::Goal& r = p.goals[g];
+            if (goal_cost) goal_cost[g] = r.cost;
+            if (lengths) lengths[g] = r.length;
+            if (steps) {
+                steps[3 * g] = r.faces;
+                steps[3 * g + 1] = r.edges;
+                steps[3 * g + 2] = r.corners;
+            }
+            const size_t kept = std::min<size_t>(r.path.size(), static_cast<size_t>(capacity));
+            for (size_t k = 0; k < kept; ++k) {
+                if (paths) paths[g * capacity + k] = r.path[k];
+                if (path_world) EMFusion::planWorldPoint(p, r.path[k], path_world + 3 * (g * capacity + k));
+            }
+        }
+        if (cost) {
+            const size_t voxels = static_cast<size_t>(p.boxSize[0]) * p.boxSize[1] * p.boxSize[2];
+            Stream& s = h->impl->mainStream();
+            hipCheck(hipMemcpyAsync(cost, p.cost, voxels * sizeof(uint32_t), hipMemcpyDeviceToHost, s.get()), "copy_plan");
+            s.waitForCompletion();
+        }
+    });
+}
+
+int emf_fusion_plan_cost_ptr(emf_fusion_t* h, const uint32_t** cost_dev) {
+    REQ(h);
+    REQ(cost_dev);
+    return guarded([&] { *cost_dev = h->impl->lastPlan().cost; });
+}
+
+int emf_fusion_set_plan_output(emf_fusion_t* h, int on, float clearance_metres, int through_unknown) {
+    REQ(h);
+    if (!(clearance_metres >= 0.f)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_set_plan_output: clearance %g", static_cast<double>(clearance_metres));
+        return EMF_E_ARG;
+    }
+    return guarded([&] { h->impl->setPlanOutput(on != 0, clearance_metres, through_unknown != 0); });
+}
+
 int emf_fusion_follow_shift(const float q[3], const int32_t step[3], float voxel_size, int32_t shift[3]) {
     REQ(q);
     REQ(step);

@@ -1742,3 +1742,83 @@ def frontiers(classes, d2=None, min_d2=0, min_voxels=1, capacity=None, stream=No
     labels = frontier_labels(classes, d2=d2, min_d2=min_d2, stream=stream)
     records, counts = frontier_clusters(labels, min_voxels=min_voxels, capacity=capacity, stream=stream)
     return labels, records, counts
+
+
+# ---- planning (include/emf_hip.h "Planning") -----------------------------------------------------
+
+PLAN_UNREACHED, PLAN_BLOCKED = _lib.PLAN_UNREACHED, _lib.PLAN_BLOCKED
+PLAN_CONVERGED, PLAN_ROUNDS, PLAN_FINITE, PLAN_SEEDS = _lib.PLAN_CONVERGED, _lib.PLAN_ROUNDS, _lib.PLAN_FINITE, _lib.PLAN_SEEDS
+
+
+def _voxel_list(points, what):
+    """An (n, 3) list of (x, y, z) voxels as a device array of i32."""
+    v = np.ascontiguousarray(np.asarray(points, np.int32).reshape(-1, 3))
+    assert len(v) >= 1, f"{what}: an empty list"
+    return DeviceArray.from_numpy(v.reshape(-1)), len(v)
+
+
+def plan_cost(classes, seeds, d2=None, min_d2=0, traverse_mask=1, seed_radius=0, max_cost=0, max_rounds=0, out=None,
+              stream=None):
+    """emf_hip_planCost of a (nz, ny, nx) u8 class volume: the cost-to-go field (nz, ny, nx) u32 from the seeds -- an
+    (n, 3) list of (x, y, z) voxels -- through the traversable voxels: those whose class is in traverse_mask (bit
+    1 << class) and, with d2 (nz, ny, nx) i32 and min_d2 > 0, d2 >= min_d2, plus whatever is not occupied within
+    seed_radius voxels of a used seed.  26-connected moves of weight 3 / 4 / 5; 0 at a used seed, PLAN_UNREACHED where
+    no seed reaches or the cost exceeds max_cost (> 0), PLAN_BLOCKED off the traversable set.  cost.counters: u32 x 4 on
+    the device, [converged, rounds enqueued, voxels with a finite cost, seeds used].  Waits on the stream, once per
+    batch of rounds.  out: a cost array to reuse."""
+    assert classes.dtype == np.uint8 and len(classes.shape) == 3 and not classes.padded
+    assert d2 is None or (d2.dtype == np.int32 and d2.shape == classes.shape and not d2.padded)
+    cost = out if out is not None else DeviceArray(classes.shape, np.uint32)
+    assert cost.shape == classes.shape and cost.dtype == np.uint32 and not cost.padded
+    if getattr(cost, "counters", None) is None:
+        cost.counters = DeviceArray((4,), np.uint32)
+    size = _i3(classes.shape[::-1])
+    d_seeds, n_seeds = _voxel_list(seeds, "plan_cost")
+    scratch = DeviceArray((max(int(_L.emf_hip_planScratchBytes(size)), 16),), np.uint8)
+    check("emf_hip_planCost",
+          _L.emf_hip_planCost(_ptr(classes), size, _ptr(d2), int(min_d2), int(traverse_mask), _ptr(d_seeds),
+                              n_seeds, int(seed_radius), int(max_cost), int(max_rounds), _ptr(cost),
+                              _ptr(scratch), _ptr(cost.counters), _stream(stream)))
+    return cost
+
+
+def plan_paths(cost, goals, capacity=None, paths=None, lengths=None, goal_cost=None, stream=None):
+    """emf_hip_planPaths over what plan_cost returned: (paths, lengths, goal_cost) as numpy arrays -- paths (n, capacity)
+    i32 linear indices (z * ny + y) * nx + x, the goal first, each step to the neighbour the cost came from (ties: the
+    smallest index), valid up to min(length, capacity); lengths (n,) i32, 0 for a goal that is unreached, blocked or
+    out of the box; goal_cost (n,) u32.  capacity None: the longest path (one more call after the lengths are known).
+    paths / lengths / goal_cost: device arrays to write into, returned as they are."""
+    assert cost.dtype == np.uint32 and len(cost.shape) == 3 and not cost.padded
+    size = _i3(cost.shape[::-1])
+    d_goals, n = _voxel_list(goals, "plan_paths")
+    own = paths is None and lengths is None and goal_cost is None
+    lengths = lengths if lengths is not None else DeviceArray((n,), np.int32)
+    goal_cost = goal_cost if goal_cost is not None else DeviceArray((n,), np.uint32)
+
+    def run(cap, sink):
+        check("emf_hip_planPaths",
+              _L.emf_hip_planPaths(_ptr(cost), size, _ptr(d_goals), n, cap, _ptr(sink) if cap > 0 else None, _ptr(lengths),
+                                   _ptr(goal_cost), _stream(stream)))
+
+    if capacity is None:
+        assert paths is None
+        run(0, None)
+        capacity = int(np.abs(lengths.numpy()).max(initial=0))
+    capacity = int(capacity)
+    if paths is None:
+        paths = DeviceArray((n, max(capacity, 1)), np.int32)
+        if capacity == 0:
+            paths = None
+    run(capacity, paths)
+    if not own:
+        return paths, lengths, goal_cost
+    host = paths.numpy()[:, :capacity] if paths is not None else np.zeros((n, 0), np.int32)
+    return host, lengths.numpy(), goal_cost.numpy()
+
+
+def plan(classes, seeds, goals, capacity=None, **kwargs):
+    """plan_cost then plan_paths: (cost, paths, lengths, goal_cost)."""
+    stream = kwargs.get("stream")
+    cost = plan_cost(classes, seeds, **kwargs)
+    paths, lengths, goal_cost = plan_paths(cost, goals, capacity=capacity, stream=stream)
+    return cost, paths, lengths, goal_cost

@@ -138,6 +138,11 @@ def load() -> C.CDLL:
         "emf_fusion_frontiers": [vp, ip, ip, C.c_int32, C.c_int32, ip, C.c_int32, ip, ip, fp, fp, C.c_void_p],
         "emf_fusion_copy_frontiers": [vp, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
         "emf_fusion_set_frontier_output": [vp, C.c_int, C.c_int32, C.c_float],
+        "emf_fusion_plan": [vp, ip, ip, ip, C.c_int32, C.c_int32, C.c_int, C.c_int32, C.c_uint32, ip, C.c_int32, C.c_int32, ip,
+                            C.c_int32, ip, ip, fp, fp, C.c_void_p, ip],
+        "emf_fusion_copy_plan": [vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
+        "emf_fusion_plan_cost_ptr": [vp, C.POINTER(C.c_void_p)],
+        "emf_fusion_set_plan_output": [vp, C.c_int, C.c_float, C.c_int],
         "emf_fusion_process_rgbd_color": [vp, fp, C.c_void_p, C.c_int32, C.c_int32],
         "emf_fusion_colored_voxels": [vp, C.POINTER(C.c_uint64)],
         "emf_fusion_get_last_masks": [vp, C.c_void_p, C.c_size_t, ip],
@@ -897,6 +902,115 @@ class Fusion:
             out["labels"] = volume
         return out
 
+    def plan(self, goals="frontiers", start=None, box=None, size=None, clearance=0.0, start_radius=None,
+             through_unknown=False, max_cost=0.0, exclude=(), min_voxels=8, field=False):
+        """Path planning over the scene: can the robot get there, by which way, at what cost.  Over a
+        box of the background as for frontiers -- None, ((x, y, z) lo, (x, y, z) size) or "camera" with `size` -- and on
+        the same occupancy classes (every live object not in `exclude` stamped as occupied): the cost-to-go field from
+        `start` (None: the voxel under the camera, or the nearest voxel of the background where the camera is outside; else (n, 3) world points, each rounded to its voxel) through the free
+        voxels -- and the unknown ones with through_unknown -- at least `clearance` metres (rounded up to whole voxels)
+        from the nearest occupied voxel of the box, plus whatever is not occupied within start_radius metres of a start
+        (None: max(clearance, one voxel); rounded up to whole voxels): the robot stands there, and the sensor does not
+        see its own near field.  Moves are 26-connected with the integer weights 3 / 4 / 5 for face / edge / corner
+        steps; max_cost (metres of face steps, 0: none) stops the search at max(floor(3 * max_cost / voxel), 1).
+        goals="frontiers": self.frontiers(box, min_voxels, clearance, exclude) and a plan to every kept cluster's
+        representative; else (n, 3) world points, each rounded to its voxel and never moved to another one.
+        Returns a dict:
+          goals: one dict per goal -- with "frontiers" the cluster's record of frontiers() -- that gains voxel (box
+          coordinates), reachable, cost (the chamfer cost; PLAN_UNREACHED / PLAN_BLOCKED without a path), length_m =
+          (faces + sqrt 2 edges + sqrt 3 corners) * voxel in float64, steps (faces, edges, corners), path_vox (k, 3) i32
+          box voxels from the goal to the start, path_world (k, 3) f32 (float64, rounded once).  With "frontiers" the
+          reachable clusters come first, cheapest first, then the rest in the frontier order; `clusters` is the same list;
+          start_voxels (box coordinates), start_radius_voxels, clearance_voxels; box (lo, size); box_pose; voxel_size;
+          converged, rounds, n_finite, n_starts: the counters; frontiers: what frontiers() returned (with "frontiers");
+          cost (bz, by, bx) u32 with field=True."""
+        from ._lib import PLAN_BLOCKED
+        if isinstance(box, str):
+            if box != "camera" or size is None:
+                raise ValueError('plan: box="camera" needs a size')
+            box = self.camera_box(size)
+            if box is None:
+                raise ValueError("plan: the camera box lies outside the background")
+        vs = float(self.params.bg_voxel_size)
+
+        def voxels_of(metres):
+            return min(int(np.ceil(np.float32(metres) / np.float32(vs))), 4096) if metres > 0 else 0
+
+        clearance_voxels = voxels_of(clearance)
+        radius_voxels = max(clearance_voxels, 1) if start_radius is None else voxels_of(start_radius)
+        # at least 1: a positive cap below a third of a voxel must not turn into 0, which means "no cap"
+        cost_cap = min(max(int(np.floor(3.0 * float(max_cost) / vs)), 1), PLAN_BLOCKED - 1) if max_cost > 0 else 0
+        res = np.array(list(self.params.bg_res), np.float64)
+        lo_box = np.array(box[0] if box is not None else (0, 0, 0), np.int64)
+        bg_R, bg_t = self.background_pose()
+        bg_R, bg_t = bg_R.astype(np.float64), bg_t.astype(np.float64)
+
+        def to_voxels(points):  # world points -> box voxels, each rounded to its voxel
+            q = (np.asarray(points, np.float64).reshape(-1, 3) - bg_t) @ bg_R
+            return (np.rint(q / vs + (res - 1) / 2.0).astype(np.int64) - lo_box).astype(np.int32)
+
+        def world(v):  # box voxels -> world, as frontiers() does: float64, rounded once
+            p = (np.asarray(v, np.float64) + (lo_box - (res - 1) / 2.0)) * np.float64(vs)
+            return (p @ bg_R.T + bg_t).astype(np.float32)
+
+        found = None
+        if isinstance(goals, str):
+            if goals != "frontiers":
+                raise ValueError('plan: goals is "frontiers" or an (n, 3) array of world points')
+            found = self.frontiers(box=box, min_voxels=min_voxels, clearance=clearance, exclude=exclude)
+            goal_voxels = np.array([c["rep"] for c in found["clusters"]], np.int32).reshape(-1, 3)
+        else:
+            goal_voxels = to_voxels(goals)
+        if start is None:  # the voxel under the camera; the nearest voxel of the background where it stands outside
+            cam = to_voxels(self.pose(0)[1]).astype(np.int64) + lo_box
+            start_voxels = (np.clip(cam, 0, res.astype(np.int64) - 1) - lo_box).astype(np.int32)
+        else:
+            start_voxels = to_voxels(start)
+        n_goals = len(goal_voxels)
+        ex = (C.c_int32 * max(len(exclude), 1))(*[int(i) for i in exclude])
+        lo_arg = size_arg = None
+        if box is not None:
+            lo_arg, size_arg = (C.c_int32 * 3)(*[int(v) for v in box[0]]), (C.c_int32 * 3)(*[int(v) for v in box[1]])
+        lo, sz, R, t = (C.c_int32 * 3)(), (C.c_int32 * 3)(), (C.c_float * 9)(), (C.c_float * 3)()
+        counters, longest = np.zeros(4, np.uint32), C.c_int32(0)
+        starts = np.ascontiguousarray(start_voxels.reshape(-1))
+        flat_goals = np.ascontiguousarray(goal_voxels.reshape(-1)) if n_goals else np.zeros(3, np.int32)
+        _check("emf_fusion_plan",
+               load().emf_fusion_plan(self._h, lo_arg, size_arg, starts.ctypes.data_as(C.POINTER(C.c_int32)), len(start_voxels),
+                                      radius_voxels, int(bool(through_unknown)), clearance_voxels, cost_cap,
+                                      flat_goals.ctypes.data_as(C.POINTER(C.c_int32)), n_goals, -1, ex, len(exclude), lo, sz, R, t,
+                                      counters.ctypes.data, C.byref(longest)))
+        cap = int(longest.value)
+        goal_cost, lengths = np.zeros(n_goals, np.uint32), np.zeros(n_goals, np.int32)
+        steps, paths = np.zeros((n_goals, 3), np.int32), np.full((n_goals, max(cap, 1)), -1, np.int32)
+        volume = np.empty((sz[2], sz[1], sz[0]), np.uint32) if field else None
+        _check("emf_fusion_copy_plan",
+               load().emf_fusion_copy_plan(self._h, goal_cost.ctypes.data, lengths.ctypes.data, steps.ctypes.data,
+                                           paths.ctypes.data, cap, None, volume.ctypes.data if field else None))
+        nx, ny = int(sz[0]), int(sz[1])
+        records = []
+        for g in range(n_goals):
+            k = max(int(lengths[g]), 0)
+            lin = paths[g, :k].astype(np.int64)
+            vox = np.stack([lin % nx, lin // nx % ny, lin // (nx * ny)], axis=1).astype(np.int32)
+            r = dict(found["clusters"][g]) if found is not None else {}
+            f, e, c = (int(v) for v in steps[g])
+            r.update(voxel=tuple(int(v) for v in goal_voxels[g]), reachable=k > 0, cost=int(goal_cost[g]),
+                     length_m=(f + np.sqrt(2.0) * e + np.sqrt(3.0) * c) * np.float64(vs), steps=(f, e, c), path_vox=vox,
+                     path_world=world(vox))
+            records.append(r)
+        if found is not None:  # reachable first, cheapest first (stable: ties and the rest keep the frontier order)
+            records = sorted(records, key=lambda r: (not r["reachable"], r["cost"] if r["reachable"] else 0))
+        out = dict(goals=records, start_voxels=start_voxels, start_radius_voxels=radius_voxels, clearance_voxels=clearance_voxels,
+                   max_cost=cost_cap, box=(tuple(lo), tuple(sz)),
+                   box_pose=(np.array(R, np.float32).reshape(3, 3), np.array(t, np.float32)), voxel_size=vs,
+                   converged=bool(counters[0]), rounds=int(counters[1]), n_finite=int(counters[2]), n_starts=int(counters[3]))
+        if found is not None:
+            out.update(clusters=records, frontiers=found)
+        if field:
+            out["cost"] = volume
+        return out
+
     def last_motion_masks(self):
         """The proposals of the last processed frame: ((H, W) i32 image of proposal ranks, -1 where none is, list of
         dicts {label, area, x0, y0, x1, y1} by rank).  Empty / all -1 if the frame proposed nothing."""
@@ -1093,14 +1207,17 @@ class Fusion:
 
     def setup_output(self, exp_frame_meshes=False, exp_vols=False, exp_world_mesh=False, exp_distance_field=False,
                      distance_cap=0.0, distance_unknown_is_obstacle=False, exp_frontiers=False, frontier_min_voxels=8,
-                     frontier_clearance=0.0):
+                     frontier_clearance=0.0, exp_plan=False, plan_clearance=0.0, plan_through_unknown=False):
         """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
         the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
         the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh();
         exp_distance_field: write_results also writes distance.bin (f32 metres to the nearest obstacle of the whole
         background, +inf beyond distance_cap metres or without an obstacle) and occupancy.bin (u8 classes);
         exp_frontiers: write_results also writes frontiers.txt, one line per frontier cluster of the whole background
-        of at least frontier_min_voxels voxels, largest first (include/emf_fusion.h emf_fusion_set_frontier_output)."""
+        of at least frontier_min_voxels voxels, largest first (include/emf_fusion.h emf_fusion_set_frontier_output);
+        exp_plan: write_results also writes plan.txt, the plan from the voxel under the last camera position to every
+        frontier cluster of at least frontier_min_voxels voxels at plan_clearance metres
+        (include/emf_fusion.h emf_fusion_set_plan_output)."""
         _check("emf_fusion_setup_output",
                load().emf_fusion_setup_output(self._h, int(exp_frame_meshes), int(exp_vols)))
         _check("emf_fusion_set_world_mesh_output",
@@ -1111,6 +1228,9 @@ class Fusion:
         _check("emf_fusion_set_frontier_output",
                load().emf_fusion_set_frontier_output(self._h, int(bool(exp_frontiers)), int(frontier_min_voxels),
                                                      float(frontier_clearance)))
+        _check("emf_fusion_set_plan_output",
+               load().emf_fusion_set_plan_output(self._h, int(bool(exp_plan)), float(plan_clearance),
+                                                 int(bool(plan_through_unknown))))
 
     def write_results(self, directory: str, volumes: bool = True):
         """poses-*.txt, mesh_bg.ply, mesh_<id>.ply always; tsdfs/*.bin with `volumes` (reference formats)."""

@@ -283,6 +283,42 @@ int emf_fusion_copy_frontiers(emf_fusion_t* h, emf_frontier_cluster_t* records, 
  * box lo_x lo_y lo_z hi_x hi_y hi_z in voxels of the background (%d).  clearance_metres is rounded up to whole voxels.
  * Off: no output byte changes. */
 int emf_fusion_set_frontier_output(emf_fusion_t* h, int on, int32_t min_voxels, float clearance_metres);
+/* Path planning over the scene (include/emf_hip.h "Planning"; new behaviour, nothing of the session
+ * changes -- the last distance field and the last frontiers included -- and nothing goes into a checkpoint).  Over the box
+ * of the background as for emf_fusion_frontiers, on the same occupancy classes (every live object whose id is not in
+ * exclude_ids stamped as occupied): the cost-to-go field from the start voxels -- num_start x (x, y, z) in BOX
+ * coordinates; num_start == 0: the background voxel under the camera, or the nearest one where the camera is outside -- through the free voxels (and the unknown ones,
+ * with through_unknown) at least clearance_voxels from the nearest occupied voxel of the box, plus whatever is not
+ * occupied within seed_radius_voxels of a start; 26-connected moves of weight 3 / 4 / 5; max_cost 0: no cap.  Then the
+ * paths from the goal voxels (num_goals x (x, y, z), box coordinates; a goal is never moved to another voxel) back to a
+ * start, at most path_capacity voxels of each, or all of each with path_capacity < 0.  Enqueued on the main stream after
+ * the frame; waits for the rounds of the relaxation and for the results, which are kept until the next call.
+ * lo_out / size_out / R / t (may be NULL): as emf_fusion_frontiers.  counters (may be NULL): EMF_PLAN_* -- converged,
+ * rounds, voxels with a finite cost, start voxels used.  longest_path (may be NULL): the voxels of the longest kept path.
+ * EMF_E_ARG on a sharded session ("not supported on the sharded path"); EMF_E_LIMIT for a box above 2^29 voxels. */
+int emf_fusion_plan(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], const int32_t* start_voxels,
+                    int32_t num_start, int32_t seed_radius_voxels, int through_unknown, int32_t clearance_voxels,
+                    uint32_t max_cost, const int32_t* goal_voxels, int32_t num_goals, int32_t path_capacity,
+                    const int32_t* exclude_ids, int32_t num_exclude, int32_t lo_out[3], int32_t size_out[3], float R[9],
+                    float t[3], uint32_t counters[4], int32_t* longest_path);
+/* The last plan, per goal in the order given: goal_cost (EMF_PLAN_UNREACHED / EMF_PLAN_BLOCKED: no path), lengths (the
+ * voxels of the whole path, 0: none), steps (3 per goal: the face, edge and corner moves of the kept path), paths
+ * (capacity i32 per goal: linear indices (z * ny + y) * nx + x of the box, the goal first; untouched beyond the kept
+ * length), path_world (3 doubles per path entry, the voxel in the world frame as emf_fusion_copy_frontiers computes
+ * it), and cost: the field, one u32 per voxel of the box in (z, y, x) order (waits for the main stream).  Any may be NULL. */
+int emf_fusion_copy_plan(emf_fusion_t* h, uint32_t* goal_cost, int32_t* lengths, int32_t* steps, int32_t* paths,
+                         int32_t capacity, double* path_world, uint32_t* cost);
+/* The device pointer of the last plan's cost field (NULL before the first plan); valid until the next plan. */
+int emf_fusion_plan_cost_ptr(emf_fusion_t* h, const uint32_t** cost_dev);
+/* setup_output's exp_plan, as an entry of its own so that emf_fusion_setup_output keeps its signature:
+ * emf_fusion_write_results also writes plan.txt of the whole background, planned from the voxel under the last camera
+ * position (start radius max(clearance, one voxel)) to the representative of every frontier cluster that
+ * emf_fusion_set_frontier_output's min_voxels keeps at this clearance.  After one comment line, per cluster in the order
+ * of frontiers.txt:  count (%d) reachable (0 / 1) cost (%u) length_m (%.9g: (faces + sqrt 2 edges + sqrt 3 corners) *
+ * voxel, in double) x y z of the representative in the world frame (%.9g, the double rounded once to float) n_path (%d),
+ * followed by n_path lines x y z: the path's voxels in the world frame, from the goal to the start (%.9g each).
+ * clearance_metres is rounded up to whole voxels.  Off: no output byte changes. */
+int emf_fusion_set_plan_output(emf_fusion_t* h, int on, float clearance_metres, int through_unknown);
 /* Remember what rolls out (new behaviour, off by default; with it off no launch, no output byte and no
  * checkpoint byte changes).  With the store on, the whole integration tiles (32 x 8 x 8) that a roll moves out of the
  * background go to host memory as the bytes they are, after the slabs are retired; the tiles that a later roll moves

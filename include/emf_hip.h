@@ -1657,6 +1657,72 @@ int emf_hip_frontierClusters(const int32_t* labels, const int32_t size[3], int32
                              void* scratch_dev, emf_frontier_cluster_t* records, int32_t capacity, uint32_t* counters,
                              emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Planning (new behaviour: DESIGN.md 5.20).  Opt-in; nothing above is touched.  "Can the robot get there, by which way,
+ * at what cost": a multi-source shortest-path (cost-to-go) field over the traversable voxels of a box of class bytes,
+ * and the paths from any number of goals back to the start.  Arrays are dense, (z, y, x) order, x fastest; size[3] =
+ * (nx, ny, nz) as in the frontier entries; what lies outside the box does not exist.
+ *   traversable set T   a voxel v is in T if either holds:
+ *                       gate    (1u << class[v]) & traverse_mask is non-zero (the bit convention of site_mask; a class
+ *                               byte above 2 is in no mask) and, where a d2 array is passed with min_d2 > 0,
+ *                               d2[v] >= min_d2 (EMF_DF_FAR passes): the frontier gate;
+ *                       bubble  class[v] != EMF_OCC_OCCUPIED and v lies within seed_radius voxels of a used seed s
+ *                               (integer |v - s|^2 <= seed_radius^2, seed_radius >= 0).  The bubble ignores class and
+ *                               clearance: the robot is standing there, and a sensor cannot see its own near field.
+ *                               With radius 0 the bubble is the seed voxel itself.
+ *   seeds               n_seeds >= 1 voxels (x, y, z), a device array of 3 * n_seeds i32.  A seed outside the box, or
+ *                       one whose class is EMF_OCC_OCCUPIED, is ignored; counters[EMF_PLAN_SEEDS] is the number of
+ *                       seeds of the list that were used.
+ *   moves               26-connected, between two voxels that are both in T.  Integer chamfer weights: 3 for a face
+ *                       move, 4 for an edge move, 5 for a corner move.  No extra corner-cutting rule: the clearance is
+ *                       what keeps paths off walls.
+ *   cost field (u32)    0 at a used seed; at any other voxel of T the least total weight of a move sequence from any
+ *                       used seed; EMF_PLAN_UNREACHED for a voxel of T that no seed reaches or whose cost exceeds
+ *                       max_cost (when max_cost > 0); EMF_PLAN_BLOCKED for a voxel outside T.  A truncated field equals
+ *                       the untruncated one wherever it is finite (costs are non-negative: every prefix of a path
+ *                       within the cap is within it).
+ *   paths               for each goal voxel g with a finite cost the path g = p0, p1, ..., pk with cost[pk] == 0, where
+ *                       p(i+1) is the neighbour n of pi with cost[n] + w(n, pi) == cost[pi], ties to the smallest
+ *                       linear index (z * ny + y) * nx + x.  At the fixed point such a neighbour always exists.
+ *                       paths[n_goals][capacity] i32: linear indices, the goal first, truncated to capacity, untouched
+ *                       beyond; lengths[n_goals] i32: the full k + 1, 0 for a goal that is unreached, blocked or out of
+ *                       the box, minus the steps taken where the walk found no such neighbour (only on a field that
+ *                       did not converge; where that happens at the goal itself this is 0 too, and a goal_cost that is
+ *                       finite tells it from a goal without a path); goal_cost[n_goals] u32 (EMF_PLAN_BLOCKED for a goal out of the box).
+ * Limits: every axis in 1 .. EMF_DF_MAX_AXIS and at most 2^29 voxels, so that 5 * voxels < EMF_PLAN_BLOCKED and no cost
+ * can overflow (EMF_E_LIMIT above, checked first, from the sizes alone).  Every rejected argument -- a NULL pointer,
+ * n_seeds < 1, a negative radius or capacity -- returns EMF_E_ARG or EMF_E_LIMIT with nothing enqueued.
+ * Integer arithmetic only: every output but counters[0..1] of a run that was cut off is a pure function of the inputs.
+ * ---------------------------------------------------------------------------------------------- */
+#define EMF_PLAN_UNREACHED 0xffffffffu
+#define EMF_PLAN_BLOCKED 0xfffffffeu
+#define EMF_PLAN_CONVERGED 0 /* counters (4 x u32): 1 if a round found no active tile, else 0 */
+#define EMF_PLAN_ROUNDS 1    /* rounds enqueued */
+#define EMF_PLAN_FINITE 2    /* voxels with a finite cost */
+#define EMF_PLAN_SEEDS 3     /* seeds used */
+
+/* Host only, no device: the bytes of scratch emf_hip_planCost needs for a box of this size -- two bytes per tile of
+ * 32 x 8 x 8 voxels + under 128 bytes.  0 for a size beyond the limits. */
+size_t emf_hip_planScratchBytes(const int32_t size[3]);
+
+/* The cost field.  classes: size[0] * [1] * [2] bytes, only read; d2: NULL or as many i32, only read; seeds: device,
+ * 3 * n_seeds i32, only read; cost: as many u32 as voxels; scratch_dev: emf_hip_planScratchBytes(size) bytes, 16-byte
+ * aligned; counters: device, 4 x u32 (EMF_PLAN_*).  max_cost: 0 for none.  max_rounds <= 0: voxels + 1, which a
+ * converging run never reaches.  A tiled label-correcting iteration: k_pl_init, then rounds of k_pl_relax -- one
+ * workgroup per active tile, the tile and a one-voxel halo relaxed in LDS, the tiles whose halo changed flagged for
+ * the next launch -- enqueued on the stream in batches; like emf_hip_frontierLabel's caller this entry WAITS on the
+ * stream, once per batch, to read the rounds' activity counters, and stops at the first round with no active tile or
+ * at max_rounds.  A run that was cut off (counters[EMF_PLAN_CONVERGED] == 0) leaves costs that are >= the true ones. */
+int emf_hip_planCost(const uint8_t* classes, const int32_t size[3], const int32_t* d2, int32_t min_d2, uint32_t traverse_mask,
+                     const int32_t* seeds, int32_t n_seeds, int32_t seed_radius, uint32_t max_cost, int32_t max_rounds,
+                     uint32_t* cost, void* scratch_dev, uint32_t* counters, emf_stream_t stream);
+
+/* Paths over a cost field as emf_hip_planCost leaves it.  goals: device, 3 * n_goals i32 (x, y, z); paths: n_goals *
+ * capacity i32 (NULL with capacity 0); lengths, goal_cost: n_goals each.  One wave per goal, at most
+ * max(capacity, cost / 3 + 1) steps.  Nothing allocates, copies to the host or waits. */
+int emf_hip_planPaths(const uint32_t* cost, const int32_t size[3], const int32_t* goals, int32_t n_goals, int32_t capacity,
+                      int32_t* paths, int32_t* lengths, uint32_t* goal_cost, emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
