@@ -5,7 +5,7 @@
 //   emfusion_synth [--frames N] [--objects K] [--bg-res R] [--obj-res R] [--width W --height H]
 //                  [--materialize-gradients] [--autonomous] [--out DIR] [--export-frame-meshes] [--3d-vis]
 //                  [--weld-meshes] [--mesh-min-triangles N] [--mesh-largest-object] [--mesh-simplify CELL] [--world-mesh]
-//                  [--distance-field] [--distance-cap M] [--distance-unknown-obstacle]
+//                  [--distance-field] [--distance-cap M] [--distance-unknown-obstacle] [--distance-nearest]
 //                  [--frontiers] [--frontier-min-voxels N] [--frontier-clearance M]
 //                  [--plan] [--plan-clearance M] [--plan-through-unknown]
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
@@ -102,6 +102,9 @@ static bool worldMeshOut = false;  // --world-mesh: OUT/world.ply, one mesh of t
 // OUT/distance.bin (f32 metres to the nearest occupied -- or occupied or unknown -- voxel of the background, objects
 // stamped in, +inf beyond M metres) and OUT/occupancy.bin (u8 classes); without it no output byte changes
 static bool distanceOut = false, distanceUnknownObstacle = false;
+// --distance-nearest (needs --distance-field): also OUT/nearest.bin, i32 in the container of distance.bin: the linear
+// index of the nearest obstacle voxel of the background, -1 where distance.bin holds +inf.
+static bool distanceNearest = false;
 static float distanceCap = 0.f;
 // --frontiers [--frontier-min-voxels N] [--frontier-clearance M] (needs --out): writeResults also writes
 // OUT/frontiers.txt, one line per cluster of frontier voxels (free next to unknown) of the background of at least N
@@ -217,6 +220,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     emf.setupOutput(frameMeshes, volumes);            // apps/EM-Fusion.cpp:112
     emf.setWorldMeshOutput(worldMeshOut);
     emf.setDistanceOutput(distanceOut, distanceCap, distanceUnknownObstacle);
+    emf.setDistanceNearestOutput(distanceNearest);
     emf.setFrontierOutput(frontiersOut, frontierMinVoxels, frontierClearance);
     emf.setPlanOutput(planOut, planClearance, planThroughUnknown);
     set3dView(emf, params, view3d);
@@ -326,6 +330,7 @@ int main(int argc, char** argv) {
         else if (a == "--distance-field") distanceOut = true;
         else if (a == "--distance-cap" && i + 1 < argc) distanceCap = std::max(static_cast<float>(std::atof(argv[++i])), 0.f);
         else if (a == "--distance-unknown-obstacle") distanceUnknownObstacle = true;
+        else if (a == "--distance-nearest") distanceNearest = true;
         else if (a == "--frontiers") frontiersOut = true;
         else if (a == "--frontier-min-voxels" && i + 1 < argc) frontierMinVoxels = std::max(std::atoi(argv[++i]), 1);
         else if (a == "--frontier-clearance" && i + 1 < argc) frontierClearance = std::max(static_cast<float>(std::atof(argv[++i])), 0.f);
@@ -352,6 +357,10 @@ int main(int argc, char** argv) {
     if ((followStore && !followCamera) || (followStoreMibGiven && !followStore) || followStoreMib < 1) {  // (before any device is touched)
         std::fprintf(stderr, "usage: emfusion_synth: --follow-store needs --follow-camera, and --follow-store-mib N (>= 1) needs "
                              "--follow-store\n");
+        return 2;
+    }
+    if (distanceNearest && !distanceOut) {  // (before any device is touched)
+        std::fprintf(stderr, "usage: emfusion_synth: --distance-nearest writes nearest.bin beside distance.bin and needs --distance-field\n");
         return 2;
     }
     if (motionMasks && !maskDir.empty()) {  // (before any device is touched)
@@ -436,6 +445,7 @@ int main(int argc, char** argv) {
         if (!outDir.empty()) emf.setupOutput(frameMeshes, true);  // apps/EM-Fusion.cpp:112
         emf.setWorldMeshOutput(worldMeshOut);
         emf.setDistanceOutput(distanceOut, distanceCap, distanceUnknownObstacle);
+        emf.setDistanceNearestOutput(distanceNearest);
         emf.setFrontierOutput(frontiersOut, frontierMinVoxels, frontierClearance);
         emf.setPlanOutput(planOut, planClearance, planThroughUnknown);
         set3dView(emf, params, view3d);

@@ -73,6 +73,9 @@ def main():
                     help="with --distance-field: voxels farther than M metres from an obstacle get +inf (0: no cap)")
     ap.add_argument("--distance-unknown-obstacle", dest="distance_unknown", action="store_true",
                     help="with --distance-field: unobserved voxels count as obstacles too")
+    ap.add_argument("--distance-nearest", dest="distance_nearest", action="store_true",
+                    help="with --distance-field: also write OUT/nearest.bin (i32: the linear index of the nearest obstacle "
+                         "voxel of the background, -1 where there is none)")
     ap.add_argument("--frontiers", dest="frontiers", action="store_true",
                     help="also write OUT/frontiers.txt: one line per cluster of frontier voxels (free next to unknown) of "
                          "the background, largest first")
@@ -118,6 +121,8 @@ def main():
     args = ap.parse_args()
     if args.motion_masks and args.masks:  # (before the device is opened)
         ap.error("--motion-masks and --masks exclude each other")
+    if args.distance_nearest and not args.distance_field:
+        ap.error("--distance-nearest writes nearest.bin beside distance.bin and needs --distance-field")
     try:
         follow_step = tuple(int(v) for v in args.follow_step.split(","))
         assert len(follow_step) == 3
@@ -185,7 +190,8 @@ def main():
                      distance_cap=max(args.distance_cap, 0.0), distance_unknown_is_obstacle=args.distance_unknown,
                      exp_frontiers=args.frontiers, frontier_min_voxels=max(args.frontier_min_voxels, 1),
                      frontier_clearance=max(args.frontier_clearance, 0.0), exp_plan=args.plan,
-                     plan_clearance=max(args.plan_clearance, 0.0), plan_through_unknown=args.plan_through_unknown)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
+                     plan_clearance=max(args.plan_clearance, 0.0), plan_through_unknown=args.plan_through_unknown,
+                     exp_distance_nearest=args.distance_nearest)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
     if args.vis3d:  # the reference's window (apps/EM-Fusion.cpp:118-131), or a viewer placed with look_at
         R3, t3, K3, size3 = pipeline.default_3d_view(prm)
         if args.vis3d_eye:

@@ -207,6 +207,9 @@ SIGNATURES = {
     "emf_hip_occupancyObjectBox": [C.c_void_p, _I3, C.c_float],
     "emf_hip_occupancyStampObjects": [_FP, _I3, C.c_float, _I3, _I3, C.c_void_p, C.c_int32, _STREAM],
     "emf_hip_distanceTransform": [_FP, _I3, C.c_uint32, C.c_int32, _FP, _FP, C.c_float, _STREAM],
+    "emf_hip_nearestSiteScratchBytes": [_I3],
+    "emf_hip_distanceTransformNearest": [_FP, _I3, C.c_uint32, C.c_int32, _FP, _FP, _FP, _FP, C.c_float, _STREAM],
+    "emf_hip_distanceQuery": [_FP, _FP, _FP, _I3, _FP, C.c_int32, _FP, _FP, _FP, _STREAM],
     "emf_hip_frontierLabel": [_FP, _I3, _FP, C.c_int32, _FP, _FP, _STREAM],
     "emf_hip_frontierScratchBytes": [_I3, C.c_uint32],
     "emf_hip_frontierClusters": [_FP, _I3, C.c_int32, C.c_uint32, _FP, _FP, C.c_int32, _FP, _STREAM],
@@ -261,6 +264,7 @@ class EmfOccObject(C.Structure):
 
 OCC_FREE, OCC_OCCUPIED, OCC_UNKNOWN = 0, 1, 2
 DF_FAR = 0x7fffffff
+DF_NONE = -1  # nearest site: none (exactly where d2 is DF_FAR)
 DF_MAX_AXIS = 2048
 
 
@@ -384,6 +388,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.emf_hip_meshTilesScratchBytes.restype = C.c_size_t
     lib.emf_hip_motionMasksScratchBytes.restype = C.c_size_t
     lib.emf_hip_frontierScratchBytes.restype = C.c_size_t
+    lib.emf_hip_nearestSiteScratchBytes.restype = C.c_size_t
     lib.emf_hip_planScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateCullScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateDirtyMapBytes.restype = C.c_size_t

@@ -359,6 +359,8 @@ public:
         const uint8_t* classes = nullptr;  // device, box (z, y, x) order: EMF_OCC_*
         const int32_t* d2 = nullptr;       // device: squared distance in voxels, EMF_DF_FAR
         const float* metres = nullptr;     // device, or NULL when not asked for
+        const int32_t* nearest = nullptr;  // device, or NULL when not asked for: linear index of the nearest site, EMF_DF_NONE
+        uint32_t siteMask = 0;
         std::vector<int> objectIds;        // the objects that were stamped, creation order
         std::vector<Affine3f> objectPoses; // object volume <- background volume, as passed to the kernel
     };
@@ -371,8 +373,19 @@ public:
      * into a checkpoint.  Refused (EMF_E_ARG) on the sharded path.
      */
     const DistanceField& distanceField(const Vec3i& boxLo, const Vec3i& boxSize, uint32_t siteMask, int capVoxels,
-                                       const std::vector<int>& excludeIds, bool metres);
+                                       const std::vector<int>& excludeIds, bool metres, bool nearest = false);
     const DistanceField& lastDistanceField() const { return dfLast; }
+    /**
+     * Point queries on the last distance field (emf_hip_distanceQuery): for n voxels (x, y, z) in BOX
+     * coordinates the class byte, d2 and the linear index of the nearest site, any of the three outputs NULL.  A voxel
+     * outside the box reads as 255, EMF_DF_FAR and EMF_DF_NONE.  Answers from the device arrays of the last
+     * distanceField(): only the n voxels go up and n records come down (waits for the main stream).  EMF_E_ARG when no
+     * field has been computed, and for outNearest when the last one was computed without the index.
+     */
+    void queryDistance(const int32_t* voxels, int n, uint8_t* outClass, int32_t* outD2, int32_t* outNearest);
+    /** writeResults of setDistanceOutput also writes nearest.bin (i32, the container of distance.bin): the linear index
+     *  of the nearest obstacle voxel of the whole background, -1 without one.  Needs setDistanceOutput on. */
+    void setDistanceNearestOutput(bool on) { expDistanceNearest_ = on; }
     /** writeResults also writes distance.bin (f32 metres, +inf beyond the cap or without an obstacle) and occupancy.bin
      *  (u8 classes) of the whole background, both io::writeVolume; without it no output byte changes. */
     void setDistanceOutput(bool on, float capMetres = 0.f, bool unknownIsObstacle = false) {
@@ -777,8 +790,9 @@ private:
     WorldMeshInfo worldInfo;  // of the last worldMesh()
     // ---- the distance field (distanceField; EMFusionDistance.cpp): allocated at first use, never in a checkpoint ----
     DistanceField dfLast;
-    DeviceBuffer dfClasses, dfD2, dfMetres;
+    DeviceBuffer dfClasses, dfD2, dfMetres, dfNearest, dfNearestScratch, dfQuery;
     bool expDistance_ = false, distanceUnknownObstacle_ = false;  // setDistanceOutput
+    bool expDistanceNearest_ = false;                             // setDistanceNearestOutput
     float distanceCapMetres_ = 0.f;
     // the steps distanceField() and frontiers() share: the box check, the drain, and classes + stamped objects into `classes`
     void checkQueryBox(const char* who, const Vec3i& boxLo, const Vec3i& boxSize, unsigned long long& voxels) const;

@@ -86,7 +86,7 @@ void EMFusion::enqueueOccupancy(const char* who, const Vec3i& boxLo, const Vec3i
 }
 
 const EMFusion::DistanceField& EMFusion::distanceField(const Vec3i& boxLo, const Vec3i& boxSize, uint32_t siteMask, int capVoxels,
-                                                       const std::vector<int>& excludeIds, bool metres) {
+                                                       const std::vector<int>& excludeIds, bool metres, bool nearest) {
     unsigned long long voxels = 1;
     checkQueryBox("distanceField", boxLo, boxSize, voxels);
     if (siteMask < 1u || siteMask > 7u) throw HipError("EMFusion::distanceField: siteMask outside 1 .. 7", EMF_E_ARG);
@@ -96,6 +96,8 @@ const EMFusion::DistanceField& EMFusion::distanceField(const Vec3i& boxLo, const
     if (dfClasses.bytes() < voxels) dfClasses = DeviceBuffer((voxels + 3) / 4 * 4);
     if (dfD2.bytes() < voxels * sizeof(int32_t)) dfD2 = DeviceBuffer(voxels * sizeof(int32_t));
     if (metres && dfMetres.bytes() < voxels * sizeof(float)) dfMetres = DeviceBuffer(voxels * sizeof(float));
+    if (nearest && dfNearest.bytes() < voxels * sizeof(int32_t)) dfNearest = DeviceBuffer(voxels * sizeof(int32_t));
+    if (nearest && dfNearestScratch.bytes() < voxels * sizeof(int32_t)) dfNearestScratch = DeviceBuffer(voxels * sizeof(int32_t));
 
     const float voxel = background.getVoxelSize();
     DistanceField out;
@@ -104,23 +106,59 @@ const EMFusion::DistanceField& EMFusion::distanceField(const Vec3i& boxLo, const
     out.voxelSize = voxel;
     out.boxPose = queryBoxPose(boxLo);
     enqueueOccupancy("distanceField", boxLo, boxSize, excludeIds, dfClasses.as<uint8_t>(), &out.objectIds, &out.objectPoses);
-    emfCheck(emf_hip_distanceTransform(dfClasses.as<uint8_t>(), boxSize.val, siteMask, capVoxels, dfD2.as<int32_t>(),
-                                       metres ? dfMetres.as<float>() : nullptr, voxel, main.abi()),
-             "EMFusion::distanceField (transform)");
+    if (nearest)
+        emfCheck(emf_hip_distanceTransformNearest(dfClasses.as<uint8_t>(), boxSize.val, siteMask, capVoxels, dfD2.as<int32_t>(),
+                                                  metres ? dfMetres.as<float>() : nullptr, dfNearest.as<int32_t>(),
+                                                  dfNearestScratch.as<int32_t>(), voxel, main.abi()),
+                 "EMFusion::distanceField (transform, nearest)");
+    else
+        emfCheck(emf_hip_distanceTransform(dfClasses.as<uint8_t>(), boxSize.val, siteMask, capVoxels, dfD2.as<int32_t>(),
+                                           metres ? dfMetres.as<float>() : nullptr, voxel, main.abi()),
+                 "EMFusion::distanceField (transform)");
     out.classes = dfClasses.as<uint8_t>();
     out.d2 = dfD2.as<int32_t>();
     out.metres = metres ? dfMetres.as<float>() : nullptr;
+    out.nearest = nearest ? dfNearest.as<int32_t>() : nullptr;
+    out.siteMask = siteMask;
     dfLast = std::move(out);
     return dfLast;
 }
 
-// distance.bin and occupancy.bin of the whole background (setDistanceOutput), in the container of the tsdfs/ dumps
+void EMFusion::queryDistance(const int32_t* voxels, int n, uint8_t* outClass, int32_t* outD2, int32_t* outNearest) {
+    if (sharded || world > 1)
+        throw HipError("EMFusion::queryDistance: the distance field is not supported on the sharded path", EMF_E_ARG);
+    if (n < 0 || (n > 0 && !voxels)) throw HipError("EMFusion::queryDistance: " + std::to_string(n) + " points without a list", EMF_E_ARG);
+    if (!dfLast.classes) throw HipError("EMFusion::queryDistance: no distance field has been computed", EMF_E_ARG);
+    if (outNearest && !dfLast.nearest)
+        throw HipError("EMFusion::queryDistance: the last distance field was computed without the nearest-site index", EMF_E_ARG);
+    if (n == 0 || (!outClass && !outD2 && !outNearest)) return;
+    // one device block: the voxels, then the three outputs (i32, i32, u8)
+    const size_t un = static_cast<size_t>(n), need = un * (3 + 1 + 1) * sizeof(int32_t) + (un + 3) / 4 * 4;
+    if (dfQuery.bytes() < need) dfQuery = DeviceBuffer(need);
+    int32_t* dVox = dfQuery.as<int32_t>();
+    int32_t* dD2 = dVox + 3 * un;
+    int32_t* dNear = dD2 + un;
+    uint8_t* dClass = reinterpret_cast<uint8_t*>(dNear + un);
+    hipCheck(hipMemcpyAsync(dVox, voxels, 3 * un * sizeof(int32_t), hipMemcpyHostToDevice, main.get()), "EMFusion::queryDistance (voxels)");
+    emfCheck(emf_hip_distanceQuery(outClass ? dfLast.classes : nullptr, outD2 ? dfLast.d2 : nullptr,
+                                   outNearest ? dfLast.nearest : nullptr, dfLast.boxSize.val, dVox, n, outClass ? dClass : nullptr,
+                                   outD2 ? dD2 : nullptr, outNearest ? dNear : nullptr, main.abi()),
+             "EMFusion::queryDistance");
+    if (outClass) hipCheck(hipMemcpyAsync(outClass, dClass, un, hipMemcpyDeviceToHost, main.get()), "EMFusion::queryDistance (class)");
+    if (outD2) hipCheck(hipMemcpyAsync(outD2, dD2, un * sizeof(int32_t), hipMemcpyDeviceToHost, main.get()), "EMFusion::queryDistance (d2)");
+    if (outNearest)
+        hipCheck(hipMemcpyAsync(outNearest, dNear, un * sizeof(int32_t), hipMemcpyDeviceToHost, main.get()), "EMFusion::queryDistance (nearest)");
+    main.waitForCompletion();
+}
+
+// distance.bin and occupancy.bin of the whole background (setDistanceOutput), in the container of the tsdfs/ dumps;
+// with setDistanceNearestOutput also nearest.bin
 void EMFusion::writeDistanceField(const std::string& dir) {
     const Vec3i n = background.getVolumeRes();
     const float voxel = background.getVoxelSize();
     const int cap = distanceCapMetres_ > 0.f ? static_cast<int>(std::min(std::ceil(distanceCapMetres_ / voxel), 4096.f)) : 0;
     const uint32_t sites = (1u << EMF_OCC_OCCUPIED) | (distanceUnknownObstacle_ ? 1u << EMF_OCC_UNKNOWN : 0u);
-    const DistanceField& df = distanceField(Vec3i(0, 0, 0), n, sites, cap, {}, true);
+    const DistanceField& df = distanceField(Vec3i(0, 0, 0), n, sites, cap, {}, true, expDistanceNearest_);
     const size_t voxels = static_cast<size_t>(n[0]) * n[1] * n[2];
     std::vector<float> metres(voxels);
     std::vector<uint8_t> classes(voxels);
@@ -131,6 +169,13 @@ void EMFusion::writeDistanceField(const std::string& dir) {
     main.waitForCompletion();
     io::writeVolume(dir + "/distance.bin", metres.data(), sizeof(float), n, voxel);
     io::writeVolume(dir + "/occupancy.bin", classes.data(), sizeof(uint8_t), n, voxel);
+    if (expDistanceNearest_) {
+        std::vector<int32_t> nearest(voxels);
+        hipCheck(hipMemcpyAsync(nearest.data(), df.nearest, voxels * sizeof(int32_t), hipMemcpyDeviceToHost, main.get()),
+                 "EMFusion::writeDistanceField (nearest)");
+        main.waitForCompletion();
+        io::writeVolume(dir + "/nearest.bin", nearest.data(), sizeof(int32_t), n, voxel);
+    }
 }
 
 }  // namespace emf

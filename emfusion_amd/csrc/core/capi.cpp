@@ -580,16 +580,16 @@ int emf_fusion_world_mesh_info(emf_fusion_t* h, uint64_t out[4]) {
     });
 }
 
-int emf_fusion_distance_field(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], uint32_t site_mask,
-                              int32_t cap_voxels, const int32_t* exclude_ids, int32_t num_exclude, int metres,
-                              int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3]) {
+static int distance_field_entry(const char* who, emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3],
+                                uint32_t site_mask, int32_t cap_voxels, const int32_t* exclude_ids, int32_t num_exclude,
+                                int metres, bool nearest, int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3]) {
     REQ(h);
     if (num_exclude < 0 || (num_exclude > 0 && !exclude_ids)) {
-        std::snprintf(g_err, sizeof(g_err), "emf_fusion_distance_field: %d excluded ids without a list", num_exclude);
+        std::snprintf(g_err, sizeof(g_err), "%s: %d excluded ids without a list", who, num_exclude);
         return EMF_E_ARG;
     }
     if ((box_lo == nullptr) != (box_size == nullptr)) {
-        std::snprintf(g_err, sizeof(g_err), "emf_fusion_distance_field: box_lo and box_size go together");
+        std::snprintf(g_err, sizeof(g_err), "%s: box_lo and box_size go together", who);
         return EMF_E_ARG;
     }
     return guarded([&] {
@@ -597,12 +597,57 @@ int emf_fusion_distance_field(emf_fusion_t* h, const int32_t box_lo[3], const in
         const Vec3i lo = box_lo ? Vec3i(box_lo[0], box_lo[1], box_lo[2]) : Vec3i(0, 0, 0);
         const Vec3i size = box_size ? Vec3i(box_size[0], box_size[1], box_size[2]) : n;
         const std::vector<int> exclude(exclude_ids, exclude_ids + num_exclude);
-        const EMFusion::DistanceField& df = h->impl->distanceField(lo, size, site_mask, cap_voxels, exclude, metres != 0);
+        const EMFusion::DistanceField& df = h->impl->distanceField(lo, size, site_mask, cap_voxels, exclude, metres != 0, nearest);
         if (lo_out) std::memcpy(lo_out, df.boxLo.val, sizeof(df.boxLo.val));
         if (size_out) std::memcpy(size_out, df.boxSize.val, sizeof(df.boxSize.val));
         if (R) std::memcpy(R, df.boxPose.rotation().val, 9 * sizeof(float));
         if (t) std::memcpy(t, df.boxPose.translation().val, 3 * sizeof(float));
     });
+}
+
+int emf_fusion_distance_field(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], uint32_t site_mask,
+                              int32_t cap_voxels, const int32_t* exclude_ids, int32_t num_exclude, int metres,
+                              int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3]) {
+    return distance_field_entry("emf_fusion_distance_field", h, box_lo, box_size, site_mask, cap_voxels, exclude_ids, num_exclude,
+                                metres, false, lo_out, size_out, R, t);
+}
+
+int emf_fusion_distance_field_nearest(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], uint32_t site_mask,
+                                      int32_t cap_voxels, const int32_t* exclude_ids, int32_t num_exclude, int metres,
+                                      int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3]) {
+    return distance_field_entry("emf_fusion_distance_field_nearest", h, box_lo, box_size, site_mask, cap_voxels, exclude_ids,
+                                num_exclude, metres, true, lo_out, size_out, R, t);
+}
+
+int emf_fusion_copy_distance_nearest(emf_fusion_t* h, int32_t* nearest) {
+    REQ(h);
+    REQ(nearest);
+    return guarded([&] {
+        const EMFusion::DistanceField& df = h->impl->lastDistanceField();
+        if (!df.classes) throw HipError("emf_fusion_copy_distance_nearest: no distance field has been computed", EMF_E_ARG);
+        if (!df.nearest)
+            throw HipError("emf_fusion_copy_distance_nearest: the last distance field was computed without the nearest-site index", EMF_E_ARG);
+        const size_t voxels = static_cast<size_t>(df.boxSize[0]) * df.boxSize[1] * df.boxSize[2];
+        Stream& s = h->impl->mainStream();
+        hipCheck(hipMemcpyAsync(nearest, df.nearest, voxels * sizeof(int32_t), hipMemcpyDeviceToHost, s.get()), "copy_distance_nearest");
+        s.waitForCompletion();
+    });
+}
+
+int emf_fusion_query_distance(emf_fusion_t* h, const int32_t* voxels, int32_t n, uint8_t* classes, int32_t* d2, int32_t* nearest,
+                              int32_t lo_out[3], int32_t size_out[3]) {
+    REQ(h);
+    return guarded([&] {
+        h->impl->queryDistance(voxels, n, classes, d2, nearest);
+        const EMFusion::DistanceField& df = h->impl->lastDistanceField();
+        if (lo_out) std::memcpy(lo_out, df.boxLo.val, sizeof(df.boxLo.val));
+        if (size_out) std::memcpy(size_out, df.boxSize.val, sizeof(df.boxSize.val));
+    });
+}
+
+int emf_fusion_set_distance_nearest_output(emf_fusion_t* h, int on) {
+    REQ(h);
+    return guarded([&] { h->impl->setDistanceNearestOutput(on != 0); });
 }
 
 int emf_fusion_copy_distance_field(emf_fusion_t* h, uint8_t* classes, int32_t* d2, float* metres) {

@@ -19,6 +19,13 @@
 //                  starts at cap^2 + 1 at the latest: what lies beyond ends as "far" anyway).  A lane reads
 //                  line[i +- d] at its own column: with C = 64 or 32 the 32 lanes that share an LDS cycle sit in 32
 //                  different banks however they diverge in d.
+//   nearest site    the NEAREST instantiations of the two kernels also carry the linear index of the
+//                  winning site: pass x writes it next to dx^2 (on dl == dr the left site), passes y and z find the
+//                  winning line element j -- the scan runs while d * d <= best and takes the lower side on equality, so
+//                  every pass breaks ties toward the smaller coordinate, which is the smallest linear index overall --
+//                  and copy index_in[column, j] from global memory into a second index buffer: the indices ping-pong
+//                  between `nearest` and a scratch array, no pass reads an index array it writes, and LDS holds d2 only.
+//   k_df_query     one lane per point: a gather of class, d2 and nearest site at box voxels.
 // Integer arithmetic throughout (the metres output is one correctly rounded square root and one product per voxel).
 #include "common.hpp"
 
@@ -119,8 +126,10 @@ __device__ __forceinline__ unsigned long long shfl64(unsigned long long v, int s
 }
 
 // Pass x: d2 = (distance along the row to the nearest site of the row)^2, kFar for a row without a site.
-__global__ __launch_bounds__(256) void k_df_rows(const uint8_t* __restrict__ classes, int* __restrict__ d2, int nx,
-                                                 size_t rows, unsigned siteMask) {
+// NEAREST: also idx = the linear index of that site (the left one where both sides are equally far), -1 without one.
+template <bool NEAREST>
+__global__ __launch_bounds__(256) void k_df_rows(const uint8_t* __restrict__ classes, int* __restrict__ d2,
+                                                 int* __restrict__ idx, int nx, size_t rows, unsigned siteMask) {
     const int lane = threadIdx.x & 63;
     const size_t row = static_cast<size_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;  // whole waves leave
@@ -155,13 +164,19 @@ __global__ __launch_bounds__(256) void k_df_rows(const uint8_t* __restrict__ cla
         else if (above) dr = nextFirst - x;
         const int d = dl < 0 ? dr : (dr < 0 ? dl : min(dl, dr));
         if (x < nx) o[x] = d < 0 ? kFar : d * d;
+        if (NEAREST) {
+            const int site = dl >= 0 && (dr < 0 || dl <= dr) ? x - dl : (dr >= 0 ? x + dr : -1);
+            if (x < nx) idx[row * nx + x] = site < 0 ? EMF_DF_NONE : static_cast<int>(row * nx) + site;
+        }
     }
 }
 
 // Passes y and z, in place.  Line element i of column x of bundle row blockIdx.y lives at
 // d2[blockIdx.y * outerStride + i * lineStride + x]; C (a power of two) columns per workgroup.
-template <bool FINAL>
-__global__ __launch_bounds__(1024) void k_df_lines(int* __restrict__ d2, float* __restrict__ metres, int n, int nx,
+// NEAREST: idxOut[v] = idxIn at the winning line element of v's column, -1 where d2 ends as kFar; idxIn != idxOut.
+template <bool FINAL, bool NEAREST>
+__global__ __launch_bounds__(1024) void k_df_lines(int* __restrict__ d2, float* __restrict__ metres,
+                                                   const int* __restrict__ idxIn, int* __restrict__ idxOut, int n, int nx,
                                                    size_t lineStride, size_t outerStride, int logC, int cap2,
                                                    float voxel) {
     extern __shared__ int line[];
@@ -181,14 +196,39 @@ __global__ __launch_bounds__(1024) void k_df_lines(int* __restrict__ d2, float* 
     const int bound = cap2 > 0 ? cap2 + 1 : kBig;
     for (int i = slot; i < n; i += slots) {
         int best = min(line[(i << logC) + col], bound);
-        for (int d = 1; d * d < best; ++d) {
-            const int lo = i - d, hi = i + d;
-            if (lo < 0 && hi >= n) break;
-            if (lo >= 0) best = min(best, line[(lo << logC) + col] + d * d);
-            if (hi < n) best = min(best, line[(hi << logC) + col] + d * d);
+        int j = i;  // the winning line element (NEAREST)
+        if (NEAREST) {
+            // an element at distance exactly d with d * d == best ties the best so far: the scan goes on while
+            // d * d <= best.  Every lo is below, every hi above all elements seen before it: lo wins on equality.
+            for (int d = 1; d * d <= best; ++d) {
+                const int lo = i - d, hi = i + d;
+                if (lo < 0 && hi >= n) break;
+                if (lo >= 0) {
+                    const int v = line[(lo << logC) + col] + d * d;
+                    if (v <= best) {
+                        best = v;
+                        j = lo;
+                    }
+                }
+                if (hi < n) {
+                    const int v = line[(hi << logC) + col] + d * d;
+                    if (v < best) {
+                        best = v;
+                        j = hi;
+                    }
+                }
+            }
+        } else {
+            for (int d = 1; d * d < best; ++d) {
+                const int lo = i - d, hi = i + d;
+                if (lo < 0 && hi >= n) break;
+                if (lo >= 0) best = min(best, line[(lo << logC) + col] + d * d);
+                if (hi < n) best = min(best, line[(hi << logC) + col] + d * d);
+            }
         }
         const int out = best >= bound ? kFar : best;
         const size_t at = base + i * lineStride;
+        if (NEAREST) idxOut[at] = out == kFar ? EMF_DF_NONE : idxIn[base + j * lineStride];
         if (FINAL) {
             if (metres) metres[at] = out == kFar ? __builtin_inff() : sqrtf(static_cast<float>(out)) * voxel;
         }
@@ -219,9 +259,9 @@ int check_box(const int32_t res[3], const int32_t lo[3], const int32_t size[3], 
     return EMF_OK;
 }
 
-template <bool FINAL>
-int launch_lines(int32_t* d2, float* metres, int n, int nx, size_t lineStride, size_t outerStride, int outer, int cap2,
-                 float voxel, hipStream_t stream) {
+template <bool FINAL, bool NEAREST>
+int launch_lines(int32_t* d2, float* metres, const int32_t* idxIn, int32_t* idxOut, int n, int nx, size_t lineStride,
+                 size_t outerStride, int outer, int cap2, float voxel, hipStream_t stream) {
     // C = 64 up to 512 voxels per line, narrower so that a bundle stays within kMaxBundleBytes: 16 at 2048
     const int logC = n <= 512 ? 6 : (n <= 1024 ? 5 : 4);
     const int C = 1 << logC, perWave = 64 >> logC;  // lines of the bundle a wave covers at once
@@ -230,16 +270,70 @@ int launch_lines(int32_t* d2, float* metres, int n, int nx, size_t lineStride, s
     const size_t lds = static_cast<size_t>(n) * C * sizeof(int);
     if (lds > kMaxBundleBytes) return fail(EMF_E_LIMIT, "distanceTransform: a line of %d voxels does not fit a bundle", n);
     if (lds > (48u << 10)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_df_lines<FINAL>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_df_lines<FINAL, NEAREST>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
         if (e != hipSuccess) {
             (void)hipGetLastError();
             return fail(static_cast<int>(e), "distanceTransform: %zu bytes of LDS refused: %s", lds, hipGetErrorString(e));
         }
     }
-    hipLaunchKernelGGL(k_df_lines<FINAL>, dim3(ceil_div(nx, C), outer), dim3(C * slots), lds, stream, d2, metres, n, nx,
-                       lineStride, outerStride, logC, cap2, voxel);
+    hipLaunchKernelGGL((k_df_lines<FINAL, NEAREST>), dim3(ceil_div(nx, C), outer), dim3(C * slots), lds, stream, d2, metres,
+                       idxIn, idxOut, n, nx, lineStride, outerStride, logC, cap2, voxel);
     return launch_status("distanceTransform");
+}
+
+int check_transform(const char* what, const uint8_t* classes, const int32_t size[3], uint32_t site_mask, int32_t cap,
+                    const int32_t* d2, const float* metres, float voxel_size) {
+    if (!classes || !d2 || !size) return fail(EMF_E_ARG, "%s: classes, d2 or size is NULL", what);
+    EMF_TRY(check_box_size(size, what));
+    if (site_mask < 1u || site_mask > 7u) return fail(EMF_E_ARG, "%s: site_mask %u outside 1 .. 7", what, site_mask);
+    if (cap < 0) return fail(EMF_E_ARG, "%s: cap %d", what, cap);
+    if (metres && !(voxel_size > 0.f)) return fail(EMF_E_ARG, "%s: voxel_size %g", what, static_cast<double>(voxel_size));
+    if ((reinterpret_cast<uintptr_t>(d2) | reinterpret_cast<uintptr_t>(metres)) & 3u)
+        return fail(EMF_E_ARG, "%s: misaligned arrays", what);
+    return EMF_OK;
+}
+
+// the three passes; NEAREST: the indices go x -> nearest, y -> scratch, z -> nearest
+template <bool NEAREST>
+int run_transform(const uint8_t* classes, const int32_t size[3], uint32_t site_mask, int32_t cap, int32_t* d2, float* metres,
+                  int32_t* nearest, int32_t* scratch, float voxel_size, hipStream_t stream) {
+    const int nx = size[0], ny = size[1], nz = size[2];
+    // the largest distance of a box is below 3 * 2047^2: a cap at or above 4096 voxels caps nothing
+    const int cap2 = cap > 0 && cap < 4096 ? cap * cap : 0;
+    const size_t rows = static_cast<size_t>(ny) * nz, plane = static_cast<size_t>(nx) * ny;
+    hipLaunchKernelGGL(k_df_rows<NEAREST>, dim3(ceil_div(rows, 4)), dim3(256), 0, stream, classes, d2, nearest, nx, rows,
+                       site_mask);
+    EMF_TRY(launch_status("distanceTransform"));
+    EMF_TRY((launch_lines<false, NEAREST>(d2, nullptr, nearest, scratch, ny, nx, static_cast<size_t>(nx), plane, nz, cap2, 0.f,
+                                          stream)));
+    return launch_lines<true, NEAREST>(d2, metres, scratch, nearest, nz, nx, plane, static_cast<size_t>(nx), ny, cap2,
+                                       voxel_size, stream);
+}
+
+struct QueryArgs {
+    const uint8_t* classes;
+    const int* d2;
+    const int* nearest;
+    const int* voxels;
+    uint8_t* outClass;
+    int* outD2;
+    int* outNearest;
+    I3 size;
+    int n;
+};
+
+// one lane per point: plain loads and stores; a voxel outside the box reads as class 255, kFar, no site
+__global__ __launch_bounds__(256) void k_df_query(const QueryArgs a) {
+    const int i = static_cast<int>(blockIdx.x * 256u + threadIdx.x);
+    if (i >= a.n) return;
+    const int x = a.voxels[3 * static_cast<size_t>(i)], y = a.voxels[3 * static_cast<size_t>(i) + 1],
+              z = a.voxels[3 * static_cast<size_t>(i) + 2];
+    const bool inside = x >= 0 && x < a.size.x && y >= 0 && y < a.size.y && z >= 0 && z < a.size.z;
+    const size_t at = inside ? (static_cast<size_t>(z) * a.size.y + y) * a.size.x + x : 0;
+    if (a.outClass) a.outClass[i] = inside ? a.classes[at] : static_cast<uint8_t>(255);
+    if (a.outD2) a.outD2[i] = inside ? a.d2[at] : kFar;
+    if (a.outNearest) a.outNearest[i] = inside ? a.nearest[at] : EMF_DF_NONE;
 }
 
 }  // namespace
@@ -354,21 +448,49 @@ int emf_hip_occupancyStampObjects(uint8_t* classes, const int32_t res[3], float 
 
 int emf_hip_distanceTransform(const uint8_t* classes, const int32_t size[3], uint32_t site_mask, int32_t cap, int32_t* d2,
                               float* metres, float voxel_size, emf_stream_t stream) {
-    if (!classes || !d2 || !size) return fail(EMF_E_ARG, "distanceTransform: classes, d2 or size is NULL");
-    EMF_TRY(check_box_size(size, "distanceTransform"));
-    if (site_mask < 1u || site_mask > 7u) return fail(EMF_E_ARG, "distanceTransform: site_mask %u outside 1 .. 7", site_mask);
-    if (cap < 0) return fail(EMF_E_ARG, "distanceTransform: cap %d", cap);
-    if (metres && !(voxel_size > 0.f)) return fail(EMF_E_ARG, "distanceTransform: voxel_size %g", static_cast<double>(voxel_size));
-    if ((reinterpret_cast<uintptr_t>(d2) | reinterpret_cast<uintptr_t>(metres)) & 3u)
-        return fail(EMF_E_ARG, "distanceTransform: misaligned arrays");
-    const int nx = size[0], ny = size[1], nz = size[2];
-    // the largest distance of a box is below 3 * 2047^2: a cap at or above 4096 voxels caps nothing
-    const int cap2 = cap > 0 && cap < 4096 ? cap * cap : 0;
-    const size_t rows = static_cast<size_t>(ny) * nz, plane = static_cast<size_t>(nx) * ny;
-    hipLaunchKernelGGL(k_df_rows, dim3(ceil_div(rows, 4)), dim3(256), 0, as_stream(stream), classes, d2, nx, rows, site_mask);
-    EMF_TRY(launch_status("distanceTransform"));
-    EMF_TRY(launch_lines<false>(d2, nullptr, ny, nx, static_cast<size_t>(nx), plane, nz, cap2, 0.f, as_stream(stream)));
-    return launch_lines<true>(d2, metres, nz, nx, plane, static_cast<size_t>(nx), ny, cap2, voxel_size, as_stream(stream));
+    EMF_TRY(check_transform("distanceTransform", classes, size, site_mask, cap, d2, metres, voxel_size));
+    return run_transform<false>(classes, size, site_mask, cap, d2, metres, nullptr, nullptr, voxel_size, as_stream(stream));
+}
+
+size_t emf_hip_nearestSiteScratchBytes(const int32_t size[3]) {
+    if (!size) return 0;
+    unsigned long long voxels = 1;
+    for (int i = 0; i < 3; ++i) {
+        if (size[i] < 1 || size[i] > EMF_DF_MAX_AXIS) return 0;
+        voxels *= static_cast<unsigned long long>(size[i]);
+    }
+    return voxels > 0x7fffffffull ? 0 : static_cast<size_t>(voxels) * sizeof(int32_t);
+}
+
+int emf_hip_distanceTransformNearest(const uint8_t* classes, const int32_t size[3], uint32_t site_mask, int32_t cap,
+                                     int32_t* d2, float* metres, int32_t* nearest, void* scratch, float voxel_size,
+                                     emf_stream_t stream) {
+    EMF_TRY(check_transform("distanceTransformNearest", classes, size, site_mask, cap, d2, metres, voxel_size));
+    if (!nearest || !scratch) return fail(EMF_E_ARG, "distanceTransformNearest: nearest or scratch is NULL");
+    if ((reinterpret_cast<uintptr_t>(nearest) | reinterpret_cast<uintptr_t>(scratch)) & 3u)
+        return fail(EMF_E_ARG, "distanceTransformNearest: misaligned arrays");
+    if (nearest == scratch || nearest == d2 || scratch == d2)
+        return fail(EMF_E_ARG, "distanceTransformNearest: d2, nearest and scratch must be three arrays");
+    return run_transform<true>(classes, size, site_mask, cap, d2, metres, nearest, static_cast<int32_t*>(scratch), voxel_size,
+                               as_stream(stream));
+}
+
+int emf_hip_distanceQuery(const uint8_t* classes, const int32_t* d2, const int32_t* nearest, const int32_t size[3],
+                          const int32_t* voxels, int32_t n, uint8_t* out_class, int32_t* out_d2, int32_t* out_nearest,
+                          emf_stream_t stream) {
+    if (!size) return fail(EMF_E_ARG, "distanceQuery: size is NULL");
+    EMF_TRY(check_box_size(size, "distanceQuery"));
+    if (n < 0 || (n > 0 && !voxels)) return fail(EMF_E_ARG, "distanceQuery: %d points, list %p", n, static_cast<const void*>(voxels));
+    if ((classes == nullptr) != (out_class == nullptr) || (d2 == nullptr) != (out_d2 == nullptr) ||
+        (nearest == nullptr) != (out_nearest == nullptr))
+        return fail(EMF_E_ARG, "distanceQuery: an input array and its output go together");
+    if ((reinterpret_cast<uintptr_t>(d2) | reinterpret_cast<uintptr_t>(nearest) | reinterpret_cast<uintptr_t>(voxels) |
+         reinterpret_cast<uintptr_t>(out_d2) | reinterpret_cast<uintptr_t>(out_nearest)) & 3u)
+        return fail(EMF_E_ARG, "distanceQuery: misaligned arrays");
+    if (n == 0 || (!classes && !d2 && !nearest)) return EMF_OK;
+    const QueryArgs a{classes, d2, nearest, voxels, out_class, out_d2, out_nearest, i3_from(size), n};
+    hipLaunchKernelGGL(k_df_query, dim3(ceil_div(n, 256)), dim3(256), 0, as_stream(stream), a);
+    return launch_status("distanceQuery");
 }
 
 }  // extern "C"

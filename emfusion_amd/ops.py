@@ -1597,7 +1597,7 @@ def motion_masks(points, bg_raylengths, band=None, continuity=None, erode=None, 
 # ---- distance field (include/emf_hip.h "Distance field") -----------------------------------------
 
 OCC_FREE, OCC_OCCUPIED, OCC_UNKNOWN = _lib.OCC_FREE, _lib.OCC_OCCUPIED, _lib.OCC_UNKNOWN
-DF_FAR = _lib.DF_FAR
+DF_FAR, DF_NONE = _lib.DF_FAR, _lib.DF_NONE
 
 
 def _i3(values):
@@ -1663,21 +1663,52 @@ def occupancy_classes(tsdf, weights, box=None, objects=None, voxel_size=None, ou
     return out
 
 
-def distance_transform(classes, site_mask=2, cap=0, voxel_size=None, out=None, stream=None):
+def distance_transform(classes, site_mask=2, cap=0, voxel_size=None, out=None, stream=None, nearest=False):
     """emf_hip_distanceTransform of a (nz, ny, nx) u8 class volume: d2 (nz, ny, nx) i32, the exact squared distance in
     voxels to the nearest voxel whose class bit is set in site_mask (1 FREE, 2 OCCUPIED, 4 UNKNOWN), DF_FAR where there
     is none or, with cap > 0 (voxels), beyond cap.  With voxel_size also metres (nz, ny, nx) f32, +inf where DF_FAR:
-    returns d2, or (d2, metres).  out: (d2[, metres]) to reuse."""
+    returns d2, or (d2, metres).  out: (d2[, metres]) to reuse.
+    nearest=True (emf_hip_distanceTransformNearest): also nearest (nz, ny, nx) i32, the linear index
+    (z * ny + y) * nx + x of the nearest site -- the smallest one among equally near sites -- and DF_NONE exactly where
+    d2 is DF_FAR: returns (d2, nearest) or (d2, metres, nearest); out then is (d2[, metres], nearest)."""
     assert classes.dtype == np.uint8 and len(classes.shape) == 3 and not classes.padded
     d2 = out[0] if out is not None else DeviceArray(classes.shape, np.int32)
     metres = None
     if voxel_size is not None:
         metres = out[1] if out is not None else DeviceArray(classes.shape, np.float32)
     assert d2.shape == classes.shape and d2.dtype == np.int32 and (metres is None or metres.shape == classes.shape)
-    check("emf_hip_distanceTransform",
-          _L.emf_hip_distanceTransform(_ptr(classes), _i3(classes.shape[::-1]), int(site_mask), int(cap), _ptr(d2),
-                                       _ptr(metres), 0.0 if voxel_size is None else float(voxel_size), _stream(stream)))
-    return d2 if metres is None else (d2, metres)
+    size, vs = _i3(classes.shape[::-1]), 0.0 if voxel_size is None else float(voxel_size)
+    if not nearest:
+        check("emf_hip_distanceTransform",
+              _L.emf_hip_distanceTransform(_ptr(classes), size, int(site_mask), int(cap), _ptr(d2), _ptr(metres), vs,
+                                           _stream(stream)))
+        return d2 if metres is None else (d2, metres)
+    index = out[-1] if out is not None else DeviceArray(classes.shape, np.int32)
+    assert index.shape == classes.shape and index.dtype == np.int32 and not index.padded and index is not d2
+    scratch = DeviceArray((max(int(_L.emf_hip_nearestSiteScratchBytes(size)), 16),), np.uint8)
+    check("emf_hip_distanceTransformNearest",
+          _L.emf_hip_distanceTransformNearest(_ptr(classes), size, int(site_mask), int(cap), _ptr(d2), _ptr(metres),
+                                              _ptr(index), _ptr(scratch), vs, _stream(stream)))
+    return (d2, index) if metres is None else (d2, metres, index)
+
+
+def distance_query(voxels, classes=None, d2=None, nearest=None, stream=None):
+    """emf_hip_distanceQuery: a gather of n voxels -- an (n, 3) list of (x, y, z) -- from the (nz, ny, nx) device arrays
+    of a box, any of classes u8, d2 i32 and nearest i32 (at least one).  Returns a dict of numpy arrays with the keys of
+    the arrays passed: "classes" (n,) u8, "d2" (n,) i32, "nearest" (n,) i32.  A voxel outside the box reads as 255,
+    DF_FAR and DF_NONE."""
+    given = {k: a for k, a in (("classes", classes), ("d2", d2), ("nearest", nearest)) if a is not None}
+    assert given, "distance_query: no array to read"
+    shape = next(iter(given.values())).shape
+    for k, a in given.items():
+        assert a.dtype == (np.uint8 if k == "classes" else np.int32) and a.shape == shape and len(shape) == 3 and not a.padded
+    d_vox, n = _voxel_list(voxels, "distance_query")
+    outs = {k: DeviceArray((n,), a.dtype) for k, a in given.items()}
+    check("emf_hip_distanceQuery",
+          _L.emf_hip_distanceQuery(_ptr(classes), _ptr(d2), _ptr(nearest), _i3(shape[::-1]), _ptr(d_vox), n,
+                                   _ptr(outs.get("classes")), _ptr(outs.get("d2")), _ptr(outs.get("nearest")),
+                                   _stream(stream)))
+    return {k: o.numpy() for k, o in outs.items()}
 
 
 def distance_field(tsdf, weights, voxel_size, box=None, objects=None, site_mask=2, cap=0, metres=True, stream=None):

@@ -23,6 +23,23 @@ LIB_PATH = PKG_DIR / ("libemf_fusion%s.so" % os.environ.get("EMF_FUSION_VARIANT"
 HEADER_PATH = REPO_ROOT / "include" / "emf_fusion.h"
 
 
+def obstacle_offsets(nearest, box_size=None):
+    """The vectors from every voxel to its nearest obstacle voxel: (offsets (bz, by, bx, 3) i32 -- (dx, dy, dz) in
+    voxels, zero where there is none -- and valid (bz, by, bx) bool) from the `nearest` array of
+    Fusion.distance_field(nearest=True), linear indices (z * by + y) * bx + x with -1 for "none".  box_size (x, y, z):
+    checked against the array's shape when given.  For an exact Euclidean transform the offset is the exact gradient
+    direction of the distance field."""
+    nearest = np.asarray(nearest)
+    bz, by, bx = nearest.shape
+    if box_size is not None and tuple(int(v) for v in box_size) != (bx, by, bz):
+        raise ValueError(f"obstacle_offsets: box_size {tuple(box_size)} against an array of shape {nearest.shape}")
+    valid = nearest >= 0
+    lin = np.where(valid, nearest, 0).astype(np.int64)
+    z, y, x = np.indices(nearest.shape)
+    off = np.stack([lin % bx - x, lin // bx % by - y, lin // (bx * by) - z], axis=-1)
+    return np.where(valid[..., None], off, 0).astype(np.int32), valid
+
+
 class FusionParams(C.Structure):
     """Mirror of emf_fusion_params_t."""
 
@@ -135,6 +152,10 @@ def load() -> C.CDLL:
         "emf_fusion_copy_distance_field": [vp, C.c_void_p, C.c_void_p, C.c_void_p],
         "emf_fusion_distance_field_objects": [vp, ip, fp, fp, C.c_int, ip],
         "emf_fusion_set_distance_output": [vp, C.c_int, C.c_float, C.c_int],
+        "emf_fusion_distance_field_nearest": [vp, ip, ip, C.c_uint32, C.c_int32, ip, C.c_int32, C.c_int, ip, ip, fp, fp],
+        "emf_fusion_copy_distance_nearest": [vp, C.c_void_p],
+        "emf_fusion_query_distance": [vp, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, ip, ip],
+        "emf_fusion_set_distance_nearest_output": [vp, C.c_int],
         "emf_fusion_frontiers": [vp, ip, ip, C.c_int32, C.c_int32, ip, C.c_int32, ip, ip, fp, fp, C.c_void_p],
         "emf_fusion_copy_frontiers": [vp, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
         "emf_fusion_set_frontier_output": [vp, C.c_int, C.c_int32, C.c_float],
@@ -788,7 +809,7 @@ class Fusion:
         return tuple(int(v) for v in lo), tuple(int(v) for v in hi - lo)
 
     def distance_field(self, box=None, unknown_is_obstacle=False, cap=0.0, exclude=(), signed=False, metres=True,
-                       size=None):
+                       size=None, nearest=False):
         """The distance field of the scene: how far is the nearest obstacle.  Over a box of the
         background -- None: all of it; ((x, y, z) lo, (x, y, z) size) in voxels; "camera" with `size`: centred on the
         voxel under the camera, clipped to the volume -- the occupancy classes (0 free, 1 occupied, 2 unknown) with
@@ -800,7 +821,11 @@ class Fusion:
           background's pose composed with the box origin, so right after rolls too; voxel_size; objects [(id, R, t)]
           stamped, (R, t) = object volume <- background volume.
         signed=True: a second transform from the complement gives d2_inside / metres_inside, the distance from an
-        obstacle voxel to the nearest voxel that is none, and `signed` (metres) = +outside, -inside."""
+        obstacle voxel to the nearest voxel that is none, and `signed` (metres) = +outside, -inside.
+        nearest=True: also nearest (bz, by, bx) i32, the linear index (z * by + y) * bx + x in the box of
+        the nearest obstacle voxel -- the smallest index among equally near ones -- and -1 exactly where d2 is DF_FAR
+        (obstacle_offsets turns it into vectors); with signed=True also nearest_inside, the same for the second
+        transform.  The index stays on the device for query_distance."""
         if isinstance(box, str):
             if box != "camera" or size is None:
                 raise ValueError('distance_field: box="camera" needs a size')
@@ -817,18 +842,24 @@ class Fusion:
 
         def run(mask, want_metres):
             lo, sz, R, t = (C.c_int32 * 3)(), (C.c_int32 * 3)(), (C.c_float * 9)(), (C.c_float * 3)()
-            _check("emf_fusion_distance_field",
-                   load().emf_fusion_distance_field(self._h, lo_arg, size_arg, mask, cap_voxels, ex, len(exclude),
-                                                    int(want_metres), lo, sz, R, t))
+            entry = "emf_fusion_distance_field_nearest" if nearest else "emf_fusion_distance_field"
+            _check(entry, getattr(load(), entry)(self._h, lo_arg, size_arg, mask, cap_voxels, ex, len(exclude),
+                                                 int(want_metres), lo, sz, R, t))
             shape = (sz[2], sz[1], sz[0])
             classes, d2 = np.empty(shape, np.uint8), np.empty(shape, np.int32)
             m = np.empty(shape, np.float32) if want_metres else None
             _check("emf_fusion_copy_distance_field",
                    load().emf_fusion_copy_distance_field(self._h, classes.ctypes.data, d2.ctypes.data,
                                                          m.ctypes.data if want_metres else None))
-            return classes, d2, m, (tuple(lo), tuple(sz)), (np.array(R, np.float32).reshape(3, 3), np.array(t, np.float32))
+            index = np.empty(shape, np.int32) if nearest else None
+            if nearest:
+                _check("emf_fusion_copy_distance_nearest", load().emf_fusion_copy_distance_nearest(self._h, index.ctypes.data))
+            return (classes, d2, m, (tuple(lo), tuple(sz)), (np.array(R, np.float32).reshape(3, 3), np.array(t, np.float32)),
+                    index)
 
-        classes, d2, m, out_box, pose = run(sites, metres or signed)
+        if signed:  # the complement first: the field that stays on the device for query_distance is the outside one
+            _, d2_in, m_in, _, _, index_in = run(7 ^ sites, True)
+        classes, d2, m, out_box, pose, index = run(sites, metres or signed)
         n = C.c_int32(0)
         _check("emf_fusion_distance_field_objects", load().emf_fusion_distance_field_objects(self._h, None, None, None, 0, C.byref(n)))
         ids, Rs, ts = (C.c_int32 * max(n.value, 1))(), (C.c_float * (9 * max(n.value, 1)))(), (C.c_float * (3 * max(n.value, 1)))()
@@ -838,9 +869,64 @@ class Fusion:
         out = dict(classes=classes, d2=d2, box=out_box, pose=pose, voxel_size=vs, objects=objects)
         if metres or signed:
             out["metres"] = m
+        if nearest:
+            out["nearest"] = index
         if signed:
-            _, d2_in, m_in, _, _ = run(7 ^ sites, True)
             out.update(d2_inside=d2_in, metres_inside=m_in, signed=np.where(m > 0, m, -m_in).astype(np.float32))
+            if nearest:
+                out["nearest_inside"] = index_in
+        return out
+
+    def query_distance(self, points):
+        """Point queries on the last distance_field(), answered from its arrays on the device: only the
+        n points' records cross the bus.  points: (n, 3) world points, each rounded to its voxel exactly as plan()
+        rounds world goals and never moved to another one.  Returns a dict of arrays, one entry per point:
+          voxel (n, 3) i32, box coordinates (x, y, z); inside (n,) bool: the voxel lies in the field's box;
+          class (n,) u8 (255 outside the box); d2 (n,) i32 (DF_FAR outside, beyond the cap or without an obstacle);
+          metres (n,) f32 = sqrt(f32(d2)) * voxel size by the field's own formula, +inf for DF_FAR;
+          nearest_voxel (n, 3) i32, the nearest obstacle voxel in box coordinates, (-1, -1, -1) where there is none;
+          nearest_world (n, 3) f32, its centre in the world frame (float64 through the background's pose, rounded
+          once), NaN where there is none; direction (n, 3) f32, the unit vector from the point's voxel toward it in the
+          world frame, NaN where there is none or the voxel is the obstacle itself.
+        Needs a last distance_field(nearest=True); box, pose and voxel size are the session's current ones."""
+        pts = np.asarray(points, np.float64).reshape(-1, 3)
+        vs = float(self.params.bg_voxel_size)
+        res = np.array(list(self.params.bg_res), np.float64)
+        c_lo, c_size = (C.c_int32 * 3)(), (C.c_int32 * 3)()  # the box of the last field
+        _check("emf_fusion_query_distance", load().emf_fusion_query_distance(self._h, None, 0, None, None, None, c_lo, c_size))
+        lo_box, size = np.array(list(c_lo), np.int64), np.array(list(c_size), np.int64)
+        bg_R, bg_t = self.background_pose()
+        bg_R, bg_t = bg_R.astype(np.float64), bg_t.astype(np.float64)
+        q = (pts - bg_t) @ bg_R
+        with np.errstate(invalid="ignore"):
+            v = np.rint(q / vs + (res - 1) / 2.0) - lo_box
+        v = np.where(np.isfinite(v), np.clip(v, -2.0 ** 31, 2.0 ** 31 - 1), -1).astype(np.int64).astype(np.int32)
+        n = len(v)
+        cls, d2, near = np.full(n, 255, np.uint8), np.full(n, 0x7fffffff, np.int32), np.full(n, -1, np.int32)
+        flat = np.ascontiguousarray(v.reshape(-1))
+        _check("emf_fusion_query_distance",
+               load().emf_fusion_query_distance(self._h, flat.ctypes.data, n, cls.ctypes.data, d2.ctypes.data,
+                                                near.ctypes.data, None, None))
+        inside = ((v >= 0) & (v < size)).all(axis=1)
+        with np.errstate(invalid="ignore"):
+            metres = np.sqrt(d2.astype(np.float32)) * np.float32(vs)
+        metres = np.where(d2 == 0x7fffffff, np.float32(np.inf), metres).astype(np.float32)
+        has = near >= 0
+        lin = np.where(has, near, 0).astype(np.int64)
+        site = np.stack([lin % size[0], lin // size[0] % size[1], lin // (size[0] * size[1])], axis=1)
+        nearest_voxel = np.where(has[:, None], site, -1).astype(np.int32)
+
+        def world(vox):  # box voxels -> world, as frontiers() and plan() do: float64, rounded once
+            p = (np.asarray(vox, np.float64) + (lo_box - (res - 1) / 2.0)) * np.float64(vs)
+            return p @ bg_R.T + bg_t
+
+        nearest_world = np.where(has[:, None], world(site), np.nan).astype(np.float32)
+        step = (site - v.astype(np.int64)).astype(np.float64) @ bg_R.T  # the rotation of the voxel offset
+        norm = np.sqrt((step * step).sum(axis=1))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            direction = np.where((has & (norm > 0))[:, None], step / norm[:, None], np.nan).astype(np.float32)
+        out = {"voxel": v, "inside": inside, "class": cls, "d2": d2, "metres": metres, "nearest_voxel": nearest_voxel,
+               "nearest_world": nearest_world, "direction": direction}
         return out
 
     def frontiers(self, box=None, min_voxels=8, clearance=0.0, exclude=(), labels=False, size=None):
@@ -1207,7 +1293,8 @@ class Fusion:
 
     def setup_output(self, exp_frame_meshes=False, exp_vols=False, exp_world_mesh=False, exp_distance_field=False,
                      distance_cap=0.0, distance_unknown_is_obstacle=False, exp_frontiers=False, frontier_min_voxels=8,
-                     frontier_clearance=0.0, exp_plan=False, plan_clearance=0.0, plan_through_unknown=False):
+                     frontier_clearance=0.0, exp_plan=False, plan_clearance=0.0, plan_through_unknown=False,
+                     exp_distance_nearest=False):
         """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
         the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
         the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh();
@@ -1217,7 +1304,11 @@ class Fusion:
         of at least frontier_min_voxels voxels, largest first (include/emf_fusion.h emf_fusion_set_frontier_output);
         exp_plan: write_results also writes plan.txt, the plan from the voxel under the last camera position to every
         frontier cluster of at least frontier_min_voxels voxels at plan_clearance metres
-        (include/emf_fusion.h emf_fusion_set_plan_output)."""
+        (include/emf_fusion.h emf_fusion_set_plan_output);
+        exp_distance_nearest (needs exp_distance_field): write_results also writes nearest.bin, i32 in the container of
+        distance.bin: the linear index of the nearest obstacle voxel of the background, -1 where there is none."""
+        if exp_distance_nearest and not exp_distance_field:
+            raise ValueError("setup_output: exp_distance_nearest writes nearest.bin beside distance.bin and needs exp_distance_field")
         _check("emf_fusion_setup_output",
                load().emf_fusion_setup_output(self._h, int(exp_frame_meshes), int(exp_vols)))
         _check("emf_fusion_set_world_mesh_output",
@@ -1225,6 +1316,8 @@ class Fusion:
         _check("emf_fusion_set_distance_output",
                load().emf_fusion_set_distance_output(self._h, int(bool(exp_distance_field)), float(distance_cap),
                                                      int(bool(distance_unknown_is_obstacle))))
+        _check("emf_fusion_set_distance_nearest_output",
+               load().emf_fusion_set_distance_nearest_output(self._h, int(bool(exp_distance_nearest))))
         _check("emf_fusion_set_frontier_output",
                load().emf_fusion_set_frontier_output(self._h, int(bool(exp_frontiers)), int(frontier_min_voxels),
                                                      float(frontier_clearance)))

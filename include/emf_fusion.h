@@ -257,6 +257,30 @@ int emf_fusion_distance_field_objects(emf_fusion_t* h, int32_t* ids, float* R, f
  * with unknown_is_obstacle -- of the whole background, +inf beyond cap_metres, which is rounded up to whole voxels; 0:
  * no cap) and occupancy.bin (u8 classes), both in the container of the tsdfs/ dumps.  Off: no output byte changes. */
 int emf_fusion_set_distance_output(emf_fusion_t* h, int on, float cap_metres, int unknown_is_obstacle);
+/* The distance field with the nearest site (include/emf_hip.h emf_hip_distanceTransformNearest): the
+ * arguments and results of emf_fusion_distance_field, and also, per voxel of the box, the linear index
+ * (z * size_y + y) * size_x + x -- box coordinates -- of the nearest voxel whose class bit is set in site_mask, the
+ * smallest index among equally near ones, -1 exactly where d2 is EMF_DF_FAR.  Two more i32 per voxel on the device,
+ * allocated at first use.  EMF_E_ARG on a sharded session ("not supported on the sharded path"). */
+int emf_fusion_distance_field_nearest(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], uint32_t site_mask,
+                                      int32_t cap_voxels, const int32_t* exclude_ids, int32_t num_exclude, int metres,
+                                      int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3]);
+/* Copies the index of the last distance field to the host (waits for the main stream): one i32 per voxel of the box in
+ * (z, y, x) order.  EMF_E_ARG when the last field was computed by emf_fusion_distance_field, i.e. without the index. */
+int emf_fusion_copy_distance_nearest(emf_fusion_t* h, int32_t* nearest);
+/* Point queries on the last distance field, answered from its device arrays: for n voxels (x, y, z) in BOX coordinates
+ * (host memory) the class byte, d2 and the nearest-site index, n of each; any of the three outputs may be NULL.  A
+ * voxel outside the box yields 255, EMF_DF_FAR and -1.  Only the n voxels and the n records cross the bus (waits for the
+ * main stream).  lo_out / size_out (may be NULL): the box of the last field, in voxels of the background.  EMF_E_ARG
+ * when no field has been computed, for a non-NULL nearest when the last field has no index, and on a sharded session
+ * ("not supported on the sharded path"). */
+int emf_fusion_query_distance(emf_fusion_t* h, const int32_t* voxels, int32_t n, uint8_t* classes, int32_t* d2, int32_t* nearest,
+                              int32_t lo_out[3], int32_t size_out[3]);
+/* setup_output's exp_distance_nearest, as an entry of its own: with emf_fusion_set_distance_output on,
+ * emf_fusion_write_results also writes nearest.bin, i32 in the container of distance.bin (the element size in its header
+ * is 4): the linear index (z * res_y + y) * res_x + x of the nearest obstacle voxel of the whole background, -1 where
+ * distance.bin holds +inf.  Off, or without the distance output: no output byte changes. */
+int emf_fusion_set_distance_nearest_output(emf_fusion_t* h, int on);
 /* Exploration frontiers of the scene (include/emf_hip.h "Frontiers"; new behaviour, nothing of the
  * session changes -- the last distance field included -- and nothing goes into a checkpoint).  Over the box of the
  * background as for emf_fusion_distance_field, on the same occupancy classes (every live object whose id is not in

@@ -1596,6 +1596,32 @@ int emf_hip_occupancyStampObjects(uint8_t* classes, const int32_t res[3], float 
 int emf_hip_distanceTransform(const uint8_t* classes, const int32_t size[3], uint32_t site_mask, int32_t cap, int32_t* d2,
                               float* metres, float voxel_size, emf_stream_t stream);
 
+/* Step 3 with the nearest site.  For a box of class bytes, a site_mask and a cap exactly as above,
+ * nearest, one i32 per voxel v: the linear index (z' * ny + y') * nx + x' of the site nearest to v.
+ *   ties     where several sites share the minimal squared distance, the one with the smallest linear index
+ *   no site  EMF_DF_NONE exactly where d2[v] == EMF_DF_FAR: no site in the box, or cap > 0 and the nearest one beyond it
+ *   a site   nearest[v] == v
+ * (at most 2^31 - 1 voxels: the index fits.)  d2 and metres are those of emf_hip_distanceTransform byte for byte, from
+ * the same three passes in one run: pass x writes the index of the row's winner (the left site where both sides are
+ * equally far), passes y and z break ties toward the smaller y' and z' and gather the winner's index from the previous
+ * pass's index array into the other one of (nearest, scratch); no pass reads an index array it writes.
+ * scratch: emf_hip_nearestSiteScratchBytes(size) bytes (one i32 per voxel; 0 for a size beyond the limits), contents
+ * undefined afterwards.  d2, nearest and scratch are three different arrays, 4-byte aligned; a NULL nearest or scratch
+ * is EMF_E_ARG. */
+#define EMF_DF_NONE (-1)
+size_t emf_hip_nearestSiteScratchBytes(const int32_t size[3]);
+int emf_hip_distanceTransformNearest(const uint8_t* classes, const int32_t size[3], uint32_t site_mask, int32_t cap,
+                                     int32_t* d2, float* metres, int32_t* nearest, void* scratch, float voxel_size,
+                                     emf_stream_t stream);
+
+/* A gather of n box voxels (voxels: n x (x, y, z) i32 on the device) from the arrays of a box of shape size: per point
+ * the class byte, d2 and the nearest site.  Any of the three inputs may be NULL together with its output (an input
+ * without its output or the reverse is EMF_E_ARG).  A voxel outside the box yields class 255, EMF_DF_FAR and
+ * EMF_DF_NONE.  One lane per point, plain loads and stores; n == 0 enqueues nothing. */
+int emf_hip_distanceQuery(const uint8_t* classes, const int32_t* d2, const int32_t* nearest, const int32_t size[3],
+                          const int32_t* voxels, int32_t n, uint8_t* out_class, int32_t* out_d2, int32_t* out_nearest,
+                          emf_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Frontiers (new behaviour: DESIGN.md 5.19).  Opt-in; nothing above is touched.  "Where does the known map end": the
  * free voxels that touch unknown space, grouped into clusters, over a box of class bytes of shape size (x, y, z) as
