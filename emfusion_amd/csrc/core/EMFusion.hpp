@@ -24,6 +24,7 @@
 #include "KernelTimers.hpp"
 #include "ObjTSDF.hpp"
 #include "Output.hpp"
+#include "QueryBox.hpp"
 #include "Switches.hpp"
 #include "TSDF.hpp"
 #include "TileStore.hpp"
@@ -353,9 +354,7 @@ public:
     const WorldMeshInfo& worldMeshInfo() const { return worldInfo; }
     /** What the last distanceField() computed; the device arrays stay valid until the next one. */
     struct DistanceField {
-        Vec3i boxLo, boxSize;           // voxels of the background, (x, y, z)
-        Affine3f boxPose;               // voxel (0, 0, 0) of the box -> world: the background's pose and the box origin
-        float voxelSize = 0.f;
+        QueryBox box;
         const uint8_t* classes = nullptr;  // device, box (z, y, x) order: EMF_OCC_*
         const int32_t* d2 = nullptr;       // device: squared distance in voxels, EMF_DF_FAR
         const float* metres = nullptr;     // device, or NULL when not asked for
@@ -396,11 +395,7 @@ public:
     void writeDistanceField(const std::string& dir);
     /** What the last frontiers() computed; the device arrays stay valid until the next one. */
     struct Frontiers {
-        Vec3i boxLo, boxSize;              // voxels of the background, (x, y, z)
-        Affine3f boxPose;                  // voxel (0, 0, 0) of the box -> world, as DistanceField::boxPose
-        Affine3f bgPose;                   // the background's pose the world points go through
-        Vec3i bgRes;
-        float voxelSize = 0.f;
+        QueryBox box;
         int minVoxels = 1, clearanceVoxels = 0;
         std::vector<emf_frontier_cluster_t> clusters;  // the kept ones: count descending, ties by label ascending
         uint32_t kept = 0, all = 0, voxels = 0;        // the three counters: kept clusters, all clusters, frontier voxels
@@ -421,8 +416,7 @@ public:
     const Frontiers& frontiers(const Vec3i& boxLo, const Vec3i& boxSize, int minVoxels, int clearanceVoxels,
                                const std::vector<int>& excludeIds);
     const Frontiers& lastFrontiers() const { return frLast; }
-    /** The centroid (sum / count) or the representative of a record in the world frame: the voxel plus
-     *  boxLo - (res - 1) / 2, times the voxel size, through the background's pose -- in double. */
+    /** The centroid (sum / count) or the representative of a record in the world frame (QueryBox::worldPoint). */
     static void frontierWorldPoint(const Frontiers& f, const emf_frontier_cluster_t& c, bool representative, double out[3]);
     /** writeResults also writes frontiers.txt of the whole background (writeFrontiers); without it no output byte changes. */
     void setFrontierOutput(bool on, int minVoxels = 8, float clearanceMetres = 0.f) {
@@ -433,11 +427,7 @@ public:
     void writeFrontiers(const std::string& dir);
     /** What the last plan() computed; the device arrays stay valid until the next one. */
     struct Plan {
-        Vec3i boxLo, boxSize;  // voxels of the background, (x, y, z)
-        Affine3f boxPose;      // voxel (0, 0, 0) of the box -> world, as DistanceField::boxPose
-        Affine3f bgPose;       // the background's pose the world points go through
-        Vec3i bgRes;
-        float voxelSize = 0.f;
+        QueryBox box;
         int seedRadiusVoxels = 0, clearanceVoxels = 0;
         bool throughUnknown = false;
         uint32_t maxCost = 0;
@@ -469,8 +459,6 @@ public:
                      bool throughUnknown, int clearanceVoxels, uint32_t maxCost, const std::vector<Vec3i>& goalVoxels,
                      int pathCapacity, const std::vector<int>& excludeIds);
     const Plan& lastPlan() const { return plLast; }
-    /** A voxel of the plan's box in the world frame, as frontierWorldPoint: in double. */
-    static void planWorldPoint(const Plan& p, int32_t linear, double out[3]);
     /** The background voxel under the camera: rint(R^T (camera - t) / voxel + (res - 1) / 2), in double, clamped to
      *  the volume -- the nearest voxel of the background where the camera stands outside it. */
     Vec3i cameraVoxel() const;
@@ -794,21 +782,30 @@ private:
     bool expDistance_ = false, distanceUnknownObstacle_ = false;  // setDistanceOutput
     bool expDistanceNearest_ = false;                             // setDistanceNearestOutput
     float distanceCapMetres_ = 0.f;
-    // the steps distanceField() and frontiers() share: the box check, the drain, and classes + stamped objects into `classes`
-    void checkQueryBox(const char* who, const Vec3i& boxLo, const Vec3i& boxSize, unsigned long long& voxels) const;
+    // the steps the scene queries share: the box -- unchecked, and checked for EMFusion::`who`, whose
+    // refusal on the sharded path reads "`noun` not supported ..." --, the drain, classes + stamped objects into
+    // `classes`, and the clearance of frontiers() and plan()
+    QueryBox queryBoxAt(const Vec3i& lo, const Vec3i& size) const;
+    QueryBox makeQueryBox(const char* who, const char* noun, const Vec3i& lo, const Vec3i& size) const;
     void drainForQuery();
-    void enqueueOccupancy(const char* who, const Vec3i& boxLo, const Vec3i& boxSize, const std::vector<int>& excludeIds,
-                          uint8_t* classes, std::vector<int>* ids, std::vector<Affine3f>* poses);
-    Affine3f queryBoxPose(const Vec3i& boxLo) const;
+    void enqueueOccupancy(const char* who, const QueryBox& box, const std::vector<int>& excludeIds, uint8_t* classes,
+                          std::vector<int>* ids, std::vector<Affine3f>* poses);
+    struct Clearance {
+        const int32_t* d2;  // device: the capped transform with sites = occupied, or NULL without a clearance
+        int32_t minD2;
+    };
+    // into clearanceD2, which both callers consume on the main stream before they return: no result points into it
+    Clearance enqueueClearance(const char* who, const QueryBox& box, const uint8_t* classes, int clearanceVoxels);
+    DeviceBuffer clearanceD2;
     // ---- frontiers (frontiers; EMFusionFrontier.cpp): allocated at first use, never in a checkpoint ----
     Frontiers frLast;
-    DeviceBuffer frClasses, frD2, frLabels, frCounters, frScratch, frRecords;
+    DeviceBuffer frClasses, frLabels, frCounters, frScratch, frRecords;
     bool expFrontiers_ = false;  // setFrontierOutput
     int frontierMinVoxels_ = 8;
     float frontierClearanceMetres_ = 0.f;
     // ---- planning (plan; EMFusionPlan.cpp): allocated at first use, never in a checkpoint ----
     Plan plLast;
-    DeviceBuffer plClasses, plD2, plCost, plScratch, plCounters, plSeeds, plGoals, plPaths, plLengths, plGoalCost;
+    DeviceBuffer plClasses, plCost, plScratch, plCounters, plSeeds, plGoals, plPaths, plLengths, plGoalCost;
     bool expPlan_ = false, planThroughUnknown_ = false;  // setPlanOutput
     float planClearanceMetres_ = 0.f;
     TileStore bgStore;

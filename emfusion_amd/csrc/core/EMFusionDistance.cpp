@@ -12,25 +12,36 @@
 
 namespace emf {
 
-void EMFusion::checkQueryBox(const char* who, const Vec3i& boxLo, const Vec3i& boxSize, unsigned long long& voxels) const {
+QueryBox EMFusion::queryBoxAt(const Vec3i& lo, const Vec3i& size) const {
+    QueryBox box;
+    box.lo = lo;
+    box.size = size;
+    box.bgRes = background.getVolumeRes();
+    box.bgPose = background.getPose();
+    box.voxelSize = background.getVoxelSize();
+    const Vec3i n = box.bgRes;
+    const float voxel = box.voxelSize;
+    const Vec3f corner((static_cast<float>(lo[0]) - static_cast<float>(n[0] - 1) / 2.f) * voxel,
+                       (static_cast<float>(lo[1]) - static_cast<float>(n[1] - 1) / 2.f) * voxel,
+                       (static_cast<float>(lo[2]) - static_cast<float>(n[2] - 1) / 2.f) * voxel);
+    box.boxPose = Affine3f(box.bgPose.rotation(), box.bgPose.rotation() * corner + box.bgPose.translation());
+    return box;
+}
+
+QueryBox EMFusion::makeQueryBox(const char* who, const char* noun, const Vec3i& lo, const Vec3i& size) const {
     const std::string name = std::string("EMFusion::") + who;
-    if (sharded || world > 1)
-        throw HipError(name + ": " +
-                           (std::strcmp(who, "distanceField") == 0 ? "the distance field is"
-                            : std::strcmp(who, "plan") == 0        ? "planning is"
-                                                                   : "frontiers are") +
-                           " not supported on the sharded path",
-                       EMF_E_ARG);
+    if (sharded || world > 1) throw HipError(name + ": " + noun + " not supported on the sharded path", EMF_E_ARG);
     const Vec3i n = background.getVolumeRes();
-    voxels = 1;
+    unsigned long long voxels = 1;
     for (int i = 0; i < 3; ++i) {
-        if (boxSize[i] < 1 || boxLo[i] < 0 || boxLo[i] > n[i] - boxSize[i])
+        if (size[i] < 1 || lo[i] < 0 || lo[i] > n[i] - size[i])
             throw HipError(name + ": the box leaves the background on axis " + std::to_string(i), EMF_E_ARG);
-        if (boxSize[i] > EMF_DF_MAX_AXIS)
-            throw HipError(name + ": a box axis of " + std::to_string(boxSize[i]) + " voxels", EMF_E_LIMIT);
-        voxels *= static_cast<unsigned long long>(boxSize[i]);
+        if (size[i] > EMF_DF_MAX_AXIS)
+            throw HipError(name + ": a box axis of " + std::to_string(size[i]) + " voxels", EMF_E_LIMIT);
+        voxels *= static_cast<unsigned long long>(size[i]);
     }
     if (voxels > 0x7fffffffull) throw HipError(name + ": a box of more than 2^31 - 1 voxels", EMF_E_LIMIT);
+    return queryBoxAt(lo, size);
 }
 
 // as worldMesh: nothing of this instance in flight, the front copies current
@@ -41,23 +52,13 @@ void EMFusion::drainForQuery() {
     quiesce();
 }
 
-Affine3f EMFusion::queryBoxPose(const Vec3i& boxLo) const {
-    const Vec3i n = background.getVolumeRes();
-    const float voxel = background.getVoxelSize();
-    const Affine3f bgPose = background.getPose();
-    const Vec3f corner((static_cast<float>(boxLo[0]) - static_cast<float>(n[0] - 1) / 2.f) * voxel,
-                       (static_cast<float>(boxLo[1]) - static_cast<float>(n[1] - 1) / 2.f) * voxel,
-                       (static_cast<float>(boxLo[2]) - static_cast<float>(n[2] - 1) / 2.f) * voxel);
-    return Affine3f(bgPose.rotation(), bgPose.rotation() * corner + bgPose.translation());
-}
-
 // the classes of the box and the live objects stamped into them, on the main stream
-void EMFusion::enqueueOccupancy(const char* who, const Vec3i& boxLo, const Vec3i& boxSize, const std::vector<int>& excludeIds,
-                                uint8_t* classes, std::vector<int>* ids, std::vector<Affine3f>* poses) {
+void EMFusion::enqueueOccupancy(const char* who, const QueryBox& box, const std::vector<int>& excludeIds, uint8_t* classes,
+                                std::vector<int>* ids, std::vector<Affine3f>* poses) {
     const std::string name = std::string("EMFusion::") + who;
-    const Vec3i n = background.getVolumeRes();
-    const float voxel = background.getVoxelSize();
-    const Affine3f bgPose = background.getPose();
+    const Vec3i n = box.bgRes, boxLo = box.lo, boxSize = box.size;
+    const float voxel = box.voxelSize;
+    const Affine3f bgPose = box.bgPose;
     emfCheck(emf_hip_occupancyClasses(background.tsdfPtr(), background.weightsPtr(), n.val, boxLo.val, boxSize.val, classes,
                                       main.abi()),
              (name + " (classes)").c_str());
@@ -85,27 +86,37 @@ void EMFusion::enqueueOccupancy(const char* who, const Vec3i& boxLo, const Vec3i
                  (name + " (objects)").c_str());
 }
 
+// the clearance of frontiers() and plan(): at least clearanceVoxels from the nearest occupied voxel of the box.  The cap
+// keeps the scans of the transform short; what lies beyond it comes back as "far", which passes the gate as every d2
+// above it would
+EMFusion::Clearance EMFusion::enqueueClearance(const char* who, const QueryBox& box, const uint8_t* classes, int clearanceVoxels) {
+    const int cap = std::min(clearanceVoxels, 4095);
+    const Clearance out{nullptr, cap * cap};  // 4095^2 is above every distance of a box: only "far" passes then
+    if (clearanceVoxels <= 0) return out;
+    clearanceD2.reserve(box.voxels() * sizeof(int32_t));
+    emfCheck(emf_hip_distanceTransform(classes, box.size.val, 1u << EMF_OCC_OCCUPIED, cap, clearanceD2.as<int32_t>(), nullptr, 0.f,
+                                       main.abi()),
+             (std::string("EMFusion::") + who + " (clearance)").c_str());
+    return Clearance{clearanceD2.as<int32_t>(), out.minD2};
+}
+
 const EMFusion::DistanceField& EMFusion::distanceField(const Vec3i& boxLo, const Vec3i& boxSize, uint32_t siteMask, int capVoxels,
                                                        const std::vector<int>& excludeIds, bool metres, bool nearest) {
-    unsigned long long voxels = 1;
-    checkQueryBox("distanceField", boxLo, boxSize, voxels);
+    DistanceField out;
+    out.box = makeQueryBox("distanceField", "the distance field is", boxLo, boxSize);
     if (siteMask < 1u || siteMask > 7u) throw HipError("EMFusion::distanceField: siteMask outside 1 .. 7", EMF_E_ARG);
     if (capVoxels < 0) throw HipError("EMFusion::distanceField: a negative cap", EMF_E_ARG);
     drainForQuery();
     // buffers of the types.hpp owner, at first use and whenever a larger box comes
-    if (dfClasses.bytes() < voxels) dfClasses = DeviceBuffer((voxels + 3) / 4 * 4);
-    if (dfD2.bytes() < voxels * sizeof(int32_t)) dfD2 = DeviceBuffer(voxels * sizeof(int32_t));
-    if (metres && dfMetres.bytes() < voxels * sizeof(float)) dfMetres = DeviceBuffer(voxels * sizeof(float));
-    if (nearest && dfNearest.bytes() < voxels * sizeof(int32_t)) dfNearest = DeviceBuffer(voxels * sizeof(int32_t));
-    if (nearest && dfNearestScratch.bytes() < voxels * sizeof(int32_t)) dfNearestScratch = DeviceBuffer(voxels * sizeof(int32_t));
+    const size_t voxels = out.box.voxels();
+    dfClasses.reserve(voxels);
+    dfD2.reserve(voxels * sizeof(int32_t));
+    if (metres) dfMetres.reserve(voxels * sizeof(float));
+    if (nearest) dfNearest.reserve(voxels * sizeof(int32_t));
+    if (nearest) dfNearestScratch.reserve(voxels * sizeof(int32_t));
 
-    const float voxel = background.getVoxelSize();
-    DistanceField out;
-    out.boxLo = boxLo;
-    out.boxSize = boxSize;
-    out.voxelSize = voxel;
-    out.boxPose = queryBoxPose(boxLo);
-    enqueueOccupancy("distanceField", boxLo, boxSize, excludeIds, dfClasses.as<uint8_t>(), &out.objectIds, &out.objectPoses);
+    const float voxel = out.box.voxelSize;
+    enqueueOccupancy("distanceField", out.box, excludeIds, dfClasses.as<uint8_t>(), &out.objectIds, &out.objectPoses);
     if (nearest)
         emfCheck(emf_hip_distanceTransformNearest(dfClasses.as<uint8_t>(), boxSize.val, siteMask, capVoxels, dfD2.as<int32_t>(),
                                                   metres ? dfMetres.as<float>() : nullptr, dfNearest.as<int32_t>(),
@@ -134,14 +145,14 @@ void EMFusion::queryDistance(const int32_t* voxels, int n, uint8_t* outClass, in
     if (n == 0 || (!outClass && !outD2 && !outNearest)) return;
     // one device block: the voxels, then the three outputs (i32, i32, u8)
     const size_t un = static_cast<size_t>(n), need = un * (3 + 1 + 1) * sizeof(int32_t) + (un + 3) / 4 * 4;
-    if (dfQuery.bytes() < need) dfQuery = DeviceBuffer(need);
+    dfQuery.reserve(need);
     int32_t* dVox = dfQuery.as<int32_t>();
     int32_t* dD2 = dVox + 3 * un;
     int32_t* dNear = dD2 + un;
     uint8_t* dClass = reinterpret_cast<uint8_t*>(dNear + un);
     hipCheck(hipMemcpyAsync(dVox, voxels, 3 * un * sizeof(int32_t), hipMemcpyHostToDevice, main.get()), "EMFusion::queryDistance (voxels)");
     emfCheck(emf_hip_distanceQuery(outClass ? dfLast.classes : nullptr, outD2 ? dfLast.d2 : nullptr,
-                                   outNearest ? dfLast.nearest : nullptr, dfLast.boxSize.val, dVox, n, outClass ? dClass : nullptr,
+                                   outNearest ? dfLast.nearest : nullptr, dfLast.box.size.val, dVox, n, outClass ? dClass : nullptr,
                                    outD2 ? dD2 : nullptr, outNearest ? dNear : nullptr, main.abi()),
              "EMFusion::queryDistance");
     if (outClass) hipCheck(hipMemcpyAsync(outClass, dClass, un, hipMemcpyDeviceToHost, main.get()), "EMFusion::queryDistance (class)");
@@ -156,7 +167,7 @@ void EMFusion::queryDistance(const int32_t* voxels, int n, uint8_t* outClass, in
 void EMFusion::writeDistanceField(const std::string& dir) {
     const Vec3i n = background.getVolumeRes();
     const float voxel = background.getVoxelSize();
-    const int cap = distanceCapMetres_ > 0.f ? static_cast<int>(std::min(std::ceil(distanceCapMetres_ / voxel), 4096.f)) : 0;
+    const int cap = metresToVoxels(distanceCapMetres_, voxel);
     const uint32_t sites = (1u << EMF_OCC_OCCUPIED) | (distanceUnknownObstacle_ ? 1u << EMF_OCC_UNKNOWN : 0u);
     const DistanceField& df = distanceField(Vec3i(0, 0, 0), n, sites, cap, {}, true, expDistanceNearest_);
     const size_t voxels = static_cast<size_t>(n[0]) * n[1] * n[2];

@@ -14,47 +14,31 @@ namespace emf {
 
 const EMFusion::Frontiers& EMFusion::frontiers(const Vec3i& boxLo, const Vec3i& boxSize, int minVoxels, int clearanceVoxels,
                                                const std::vector<int>& excludeIds) {
-    unsigned long long voxels = 1;
-    checkQueryBox("frontiers", boxLo, boxSize, voxels);
+    Frontiers out;
+    out.box = makeQueryBox("frontiers", "frontiers are", boxLo, boxSize);
     if (minVoxels < 1) throw HipError("EMFusion::frontiers: minVoxels below 1", EMF_E_ARG);
     if (clearanceVoxels < 0) throw HipError("EMFusion::frontiers: a negative clearance", EMF_E_ARG);
     drainForQuery();
-    if (frClasses.bytes() < voxels) frClasses = DeviceBuffer((voxels + 3) / 4 * 4);
-    if (frLabels.bytes() < voxels * sizeof(int32_t)) frLabels = DeviceBuffer(voxels * sizeof(int32_t));
-    if (clearanceVoxels > 0 && frD2.bytes() < voxels * sizeof(int32_t)) frD2 = DeviceBuffer(voxels * sizeof(int32_t));
-    if (frCounters.empty()) frCounters = DeviceBuffer(4 * sizeof(uint32_t));
+    frClasses.reserve(out.box.voxels());
+    frLabels.reserve(out.box.voxels() * sizeof(int32_t));
+    frCounters.reserve(4 * sizeof(uint32_t));
 
-    Frontiers out;
-    out.boxLo = boxLo;
-    out.boxSize = boxSize;
-    out.voxelSize = background.getVoxelSize();
-    out.bgPose = background.getPose();
-    out.bgRes = background.getVolumeRes();
-    out.boxPose = queryBoxPose(boxLo);
     out.minVoxels = minVoxels;
     out.clearanceVoxels = clearanceVoxels;
     uint8_t* classes = frClasses.as<uint8_t>();
     int32_t* labels = frLabels.as<int32_t>();
     uint32_t* counters = frCounters.as<uint32_t>();
-    enqueueOccupancy("frontiers", boxLo, boxSize, excludeIds, classes, nullptr, nullptr);
-    // the clearance: at least clearanceVoxels from the nearest occupied voxel of the box.  The cap keeps the scans of
-    // the transform short; what lies beyond it comes back as "far", which passes the gate as every d2 above it would
-    const int cap = std::min(clearanceVoxels, 4095);
-    const int32_t minD2 = cap * cap;  // 4095^2 is above every distance of a box: only "far" passes then
-    if (clearanceVoxels > 0)
-        emfCheck(emf_hip_distanceTransform(classes, boxSize.val, 1u << EMF_OCC_OCCUPIED, cap, frD2.as<int32_t>(), nullptr, 0.f,
-                                           main.abi()),
-                 "EMFusion::frontiers (clearance)");
-    emfCheck(emf_hip_frontierLabel(classes, boxSize.val, clearanceVoxels > 0 ? frD2.as<int32_t>() : nullptr, minD2, labels,
-                                   counters, main.abi()),
+    enqueueOccupancy("frontiers", out.box, excludeIds, classes, nullptr, nullptr);
+    const Clearance clear = enqueueClearance("frontiers", out.box, classes, clearanceVoxels);
+    emfCheck(emf_hip_frontierLabel(classes, boxSize.val, clear.d2, clear.minD2, labels, counters, main.abi()),
              "EMFusion::frontiers (labels)");
     uint32_t host[3] = {0u, 0u, 0u};
     hipCheck(hipMemcpyAsync(host, counters, sizeof(host), hipMemcpyDeviceToHost, main.get()), "EMFusion::frontiers (counters)");
     main.waitForCompletion();  // the one number the per-cluster tables are sized by
     const uint32_t all = host[EMF_FRONTIER_CLUSTERS];
     const size_t scratch = emf_hip_frontierScratchBytes(boxSize.val, all);
-    if (frScratch.bytes() < scratch) frScratch = DeviceBuffer(scratch);
-    if (frRecords.bytes() < all * sizeof(emf_frontier_cluster_t)) frRecords = DeviceBuffer(all * sizeof(emf_frontier_cluster_t));
+    frScratch.reserve(scratch);
+    frRecords.reserve(all * sizeof(emf_frontier_cluster_t));
     emfCheck(emf_hip_frontierClusters(labels, boxSize.val, minVoxels, all, frScratch.data(),
                                       all ? frRecords.as<emf_frontier_cluster_t>() : nullptr, static_cast<int32_t>(all), counters,
                                       main.abi()),
@@ -80,16 +64,10 @@ const EMFusion::Frontiers& EMFusion::frontiers(const Vec3i& boxLo, const Vec3i& 
 }
 
 void EMFusion::frontierWorldPoint(const Frontiers& f, const emf_frontier_cluster_t& c, bool representative, double out[3]) {
-    double p[3];
-    for (int i = 0; i < 3; ++i) {
-        const double v = representative ? static_cast<double>(c.rep[i]) : static_cast<double>(c.sum[i]) / static_cast<double>(c.count);
-        p[i] = (v + (static_cast<double>(f.boxLo[i]) - (static_cast<double>(f.bgRes[i]) - 1.0) / 2.0)) * static_cast<double>(f.voxelSize);
-    }
-    const float* R = f.bgPose.rotation().val;
-    const float* t = f.bgPose.translation().val;
+    double v[3];
     for (int i = 0; i < 3; ++i)
-        out[i] = static_cast<double>(R[3 * i]) * p[0] + static_cast<double>(R[3 * i + 1]) * p[1] +
-                 static_cast<double>(R[3 * i + 2]) * p[2] + static_cast<double>(t[i]);
+        v[i] = representative ? static_cast<double>(c.rep[i]) : static_cast<double>(c.sum[i]) / static_cast<double>(c.count);
+    f.box.worldPoint(v, out);
 }
 
 // frontiers.txt of the whole background (setFrontierOutput).  After a comment line, one line per kept cluster, largest
@@ -100,8 +78,7 @@ void EMFusion::frontierWorldPoint(const Frontiers& f, const emf_frontier_cluster
 void EMFusion::writeFrontiers(const std::string& dir) {
     const Vec3i n = background.getVolumeRes();
     const float voxel = background.getVoxelSize();
-    const int clearance =
-        frontierClearanceMetres_ > 0.f ? static_cast<int>(std::min(std::ceil(frontierClearanceMetres_ / voxel), 4096.f)) : 0;
+    const int clearance = metresToVoxels(frontierClearanceMetres_, voxel);
     const Frontiers& f = frontiers(Vec3i(0, 0, 0), n, std::max(frontierMinVoxels_, 1), clearance, {});
     const std::string path = dir + "/frontiers.txt";
     std::FILE* file = std::fopen(path.c_str(), "w");
@@ -115,8 +92,8 @@ void EMFusion::writeFrontiers(const std::string& dir) {
                      static_cast<double>(static_cast<float>(r[0])), static_cast<double>(static_cast<float>(r[1])),
                      static_cast<double>(static_cast<float>(r[2])), static_cast<double>(static_cast<float>(m[0])),
                      static_cast<double>(static_cast<float>(m[1])), static_cast<double>(static_cast<float>(m[2])),
-                     f.boxLo[0] + c.lo[0], f.boxLo[1] + c.lo[1], f.boxLo[2] + c.lo[2], f.boxLo[0] + c.hi[0],
-                     f.boxLo[1] + c.hi[1], f.boxLo[2] + c.hi[2]);
+                     f.box.lo[0] + c.lo[0], f.box.lo[1] + c.lo[1], f.box.lo[2] + c.lo[2], f.box.lo[0] + c.hi[0],
+                     f.box.lo[1] + c.hi[1], f.box.lo[2] + c.hi[2]);
     }
     std::fclose(file);
 }

@@ -14,10 +14,6 @@ namespace emf {
 
 namespace {
 
-void grow(DeviceBuffer& b, size_t bytes) {
-    if (b.bytes() < bytes) b = DeviceBuffer(std::max<size_t>((bytes + 15) / 16 * 16, 16));
-}
-
 std::vector<int32_t> flat(const std::vector<Vec3i>& voxels) {
     std::vector<int32_t> out;
     out.reserve(3 * voxels.size());
@@ -30,8 +26,8 @@ std::vector<int32_t> flat(const std::vector<Vec3i>& voxels) {
 const EMFusion::Plan& EMFusion::plan(const Vec3i& boxLo, const Vec3i& boxSize, const std::vector<Vec3i>& startVoxels,
                                      int seedRadiusVoxels, bool throughUnknown, int clearanceVoxels, uint32_t maxCost,
                                      const std::vector<Vec3i>& goalVoxels, int pathCapacity, const std::vector<int>& excludeIds) {
-    unsigned long long voxels = 1;
-    checkQueryBox("plan", boxLo, boxSize, voxels);
+    const QueryBox box = makeQueryBox("plan", "planning is", boxLo, boxSize);
+    const size_t voxels = box.voxels();
     if (voxels > (1ull << 29)) throw HipError("EMFusion::plan: a box of more than 2^29 voxels", EMF_E_LIMIT);
     if (startVoxels.empty()) throw HipError("EMFusion::plan: no start voxel", EMF_E_ARG);
     if (seedRadiusVoxels < 0 || seedRadiusVoxels > 4096) throw HipError("EMFusion::plan: a start radius outside 0 .. 4096", EMF_E_ARG);
@@ -41,23 +37,17 @@ const EMFusion::Plan& EMFusion::plan(const Vec3i& boxLo, const Vec3i& boxSize, c
     drainForQuery();
     plLast = Plan();  // its device arrays are about to be reused or freed: no last plan until this one is complete
     const size_t nGoals = goalVoxels.size();
-    grow(plClasses, voxels);
-    grow(plCost, voxels * sizeof(uint32_t));
-    if (clearanceVoxels > 0) grow(plD2, voxels * sizeof(int32_t));
-    grow(plScratch, emf_hip_planScratchBytes(boxSize.val));
-    grow(plCounters, 4 * sizeof(uint32_t));
-    grow(plSeeds, 3 * sizeof(int32_t) * startVoxels.size());
-    grow(plGoals, 3 * sizeof(int32_t) * nGoals);
-    grow(plLengths, sizeof(int32_t) * nGoals);
-    grow(plGoalCost, sizeof(uint32_t) * nGoals);
+    plClasses.reserve(voxels);
+    plCost.reserve(voxels * sizeof(uint32_t));
+    plScratch.reserve(emf_hip_planScratchBytes(boxSize.val));
+    plCounters.reserve(4 * sizeof(uint32_t));
+    plSeeds.reserve(3 * sizeof(int32_t) * startVoxels.size());
+    plGoals.reserve(3 * sizeof(int32_t) * nGoals);
+    plLengths.reserve(sizeof(int32_t) * nGoals);
+    plGoalCost.reserve(sizeof(uint32_t) * nGoals);
 
     Plan out;
-    out.boxLo = boxLo;
-    out.boxSize = boxSize;
-    out.voxelSize = background.getVoxelSize();
-    out.bgPose = background.getPose();
-    out.bgRes = background.getVolumeRes();
-    out.boxPose = queryBoxPose(boxLo);
+    out.box = box;
     out.seedRadiusVoxels = seedRadiusVoxels;
     out.clearanceVoxels = clearanceVoxels;
     out.throughUnknown = throughUnknown;
@@ -65,20 +55,14 @@ const EMFusion::Plan& EMFusion::plan(const Vec3i& boxLo, const Vec3i& boxSize, c
     uint8_t* classes = plClasses.as<uint8_t>();
     uint32_t* cost = plCost.as<uint32_t>();
     uint32_t* counters = plCounters.as<uint32_t>();
-    enqueueOccupancy("plan", boxLo, boxSize, excludeIds, classes, nullptr, nullptr);
-    // the clearance, as frontiers(): the capped transform with sites = occupied; what lies beyond the cap is "far"
-    const int cap = std::min(clearanceVoxels, 4095);
-    const int32_t minD2 = cap * cap;
-    if (clearanceVoxels > 0)
-        emfCheck(emf_hip_distanceTransform(classes, boxSize.val, 1u << EMF_OCC_OCCUPIED, cap, plD2.as<int32_t>(), nullptr, 0.f,
-                                           main.abi()),
-                 "EMFusion::plan (clearance)");
+    enqueueOccupancy("plan", box, excludeIds, classes, nullptr, nullptr);
+    const Clearance clear = enqueueClearance("plan", box, classes, clearanceVoxels);
     const std::vector<int32_t> seeds = flat(startVoxels), goals = flat(goalVoxels);
     hipCheck(hipMemcpyAsync(plSeeds.data(), seeds.data(), seeds.size() * sizeof(int32_t), hipMemcpyHostToDevice, main.get()),
              "EMFusion::plan (seeds)");
     const uint32_t mask = (1u << EMF_OCC_FREE) | (throughUnknown ? 1u << EMF_OCC_UNKNOWN : 0u);
     // waits on the main stream, once per batch of rounds
-    emfCheck(emf_hip_planCost(classes, boxSize.val, clearanceVoxels > 0 ? plD2.as<int32_t>() : nullptr, minD2, mask,
+    emfCheck(emf_hip_planCost(classes, boxSize.val, clear.d2, clear.minD2, mask,
                               plSeeds.as<int32_t>(), static_cast<int32_t>(startVoxels.size()), seedRadiusVoxels, maxCost, 0, cost,
                               plScratch.data(), counters, main.abi()),
              "EMFusion::plan (cost)");
@@ -105,7 +89,7 @@ const EMFusion::Plan& EMFusion::plan(const Vec3i& boxLo, const Vec3i& boxSize, c
         if (static_cast<unsigned long long>(capacity) * nGoals > 0x7fffffffull)
             throw HipError("EMFusion::plan: the paths of all goals exceed 2^31 - 1 voxels", EMF_E_LIMIT);
         paths.assign(static_cast<size_t>(capacity) * nGoals, -1);
-        if (capacity > 0) grow(plPaths, paths.size() * sizeof(int32_t));
+        if (capacity > 0) plPaths.reserve(paths.size() * sizeof(int32_t));
         walk(capacity);
         hipCheck(hipMemcpyAsync(goalCost.data(), plGoalCost.data(), nGoals * sizeof(uint32_t), hipMemcpyDeviceToHost, main.get()),
                  "EMFusion::plan (goal costs)");
@@ -114,7 +98,6 @@ const EMFusion::Plan& EMFusion::plan(const Vec3i& boxLo, const Vec3i& boxSize, c
                      "EMFusion::plan (paths)");
     }
     main.waitForCompletion();
-    const int nx = boxSize[0], ny = boxSize[1];
     out.goals.resize(nGoals);
     for (size_t g = 0; g < nGoals; ++g) {
         Plan::Goal& r = out.goals[g];
@@ -124,8 +107,8 @@ const EMFusion::Plan& EMFusion::plan(const Vec3i& boxLo, const Vec3i& boxSize, c
         const int kept = std::min(std::max(r.length, 0), capacity);
         r.path.assign(paths.begin() + static_cast<size_t>(g) * capacity, paths.begin() + static_cast<size_t>(g) * capacity + kept);
         for (int k = 0; k + 1 < kept; ++k) {
-            const int a = r.path[k], b = r.path[k + 1];
-            const int moved = std::abs(a % nx - b % nx) + std::abs(a / nx % ny - b / nx % ny) + std::abs(a / (nx * ny) - b / (nx * ny));
+            const Vec3i a = box.unravel(r.path[k]), b = box.unravel(r.path[k + 1]);
+            const int moved = std::abs(a[0] - b[0]) + std::abs(a[1] - b[1]) + std::abs(a[2] - b[2]);
             (moved == 1 ? r.faces : moved == 2 ? r.edges : r.corners) += 1;
         }
     }
@@ -135,36 +118,14 @@ const EMFusion::Plan& EMFusion::plan(const Vec3i& boxLo, const Vec3i& boxSize, c
     return plLast;
 }
 
-void EMFusion::planWorldPoint(const Plan& p, int32_t linear, double out[3]) {
-    const int nx = p.boxSize[0], ny = p.boxSize[1];
-    const int v[3] = {linear % nx, linear / nx % ny, linear / (nx * ny)};
-    double q[3];
-    for (int i = 0; i < 3; ++i)
-        q[i] = (static_cast<double>(v[i]) + (static_cast<double>(p.boxLo[i]) - (static_cast<double>(p.bgRes[i]) - 1.0) / 2.0)) *
-               static_cast<double>(p.voxelSize);
-    const float* R = p.bgPose.rotation().val;
-    const float* t = p.bgPose.translation().val;
-    for (int i = 0; i < 3; ++i)
-        out[i] = static_cast<double>(R[3 * i]) * q[0] + static_cast<double>(R[3 * i + 1]) * q[1] +
-                 static_cast<double>(R[3 * i + 2]) * q[2] + static_cast<double>(t[i]);
-}
-
 Vec3i EMFusion::cameraVoxel() const {
-    const Affine3f bg = background.getPose();
-    const float* R = bg.rotation().val;
-    const float* t = bg.translation().val;
-    const float* c = pose.translation().val;
     const Vec3i n = background.getVolumeRes();
-    const double voxel = static_cast<double>(background.getVoxelSize());
+    double v[3];
+    queryBoxAt(Vec3i(0, 0, 0), n).voxelAt(pose.translation().val, v);
+    // a camera outside the background (both apps place the volume's near face half a voxel behind the first
+    // camera, so tracking leaves it a hair outside as often as inside): the nearest voxel of the background
     Vec3i out;
-    for (int i = 0; i < 3; ++i) {  // R^T (c - t)
-        double q = 0.0;
-        for (int j = 0; j < 3; ++j) q += static_cast<double>(R[3 * j + i]) * (static_cast<double>(c[j]) - static_cast<double>(t[j]));
-        const double v = std::nearbyint(q / voxel + (static_cast<double>(n[i]) - 1.0) / 2.0);
-        // a camera outside the background (both apps place the volume's near face half a voxel behind the first
-        // camera, so tracking leaves it a hair outside as often as inside): the nearest voxel of the background
-        out.val[i] = static_cast<int>(std::min(std::max(v, 0.0), static_cast<double>(n[i] - 1)));
-    }
+    for (int i = 0; i < 3; ++i) out.val[i] = static_cast<int>(std::min(std::max(v[i], 0.0), static_cast<double>(n[i] - 1)));
     return out;
 }
 
@@ -179,7 +140,7 @@ Vec3i EMFusion::cameraVoxel() const {
 void EMFusion::writePlan(const std::string& dir) {
     const Vec3i n = background.getVolumeRes();
     const float voxel = background.getVoxelSize();
-    const int clearance = planClearanceMetres_ > 0.f ? static_cast<int>(std::min(std::ceil(planClearanceMetres_ / voxel), 4096.f)) : 0;
+    const int clearance = metresToVoxels(planClearanceMetres_, voxel);
     const Frontiers& f = frontiers(Vec3i(0, 0, 0), n, std::max(frontierMinVoxels_, 1), clearance, {});  // as writeFrontiers
     std::vector<Vec3i> goals;
     for (const emf_frontier_cluster_t& c : f.clusters) goals.push_back(Vec3i(c.rep[0], c.rep[1], c.rep[2]));
@@ -199,7 +160,7 @@ void EMFusion::writePlan(const std::string& dir) {
                      static_cast<double>(static_cast<float>(r[2])), static_cast<int>(g.path.size()));
         for (int32_t v : g.path) {
             double w[3];
-            planWorldPoint(p, v, w);
+            p.box.worldPoint(p.box.unravel(v), w);
             std::fprintf(file, "%.9g %.9g %.9g\n", static_cast<double>(static_cast<float>(w[0])),
                          static_cast<double>(static_cast<float>(w[1])), static_cast<double>(static_cast<float>(w[2])));
         }

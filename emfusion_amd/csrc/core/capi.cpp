@@ -580,10 +580,15 @@ int emf_fusion_world_mesh_info(emf_fusion_t* h, uint64_t out[4]) {
     });
 }
 
-static int distance_field_entry(const char* who, emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3],
-                                uint32_t site_mask, int32_t cap_voxels, const int32_t* exclude_ids, int32_t num_exclude,
-                                int metres, bool nearest, int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3]) {
-    REQ(h);
+// ---- what the scene queries (distance field, frontiers, plan) share ----
+struct QueryArgs {
+    Vec3i lo, size;  // no box: the whole background
+    std::vector<int> exclude;
+};
+
+// the (box_lo, box_size, exclude_ids, num_exclude) arguments of the entry `who`; EMF_E_ARG with the message set
+static int queryArgs(const char* who, emf_fusion_t* h, const int32_t* box_lo, const int32_t* box_size, const int32_t* exclude_ids,
+                     int32_t num_exclude, QueryArgs& out) {
     if (num_exclude < 0 || (num_exclude > 0 && !exclude_ids)) {
         std::snprintf(g_err, sizeof(g_err), "%s: %d excluded ids without a list", who, num_exclude);
         return EMF_E_ARG;
@@ -592,16 +597,36 @@ static int distance_field_entry(const char* who, emf_fusion_t* h, const int32_t 
         std::snprintf(g_err, sizeof(g_err), "%s: box_lo and box_size go together", who);
         return EMF_E_ARG;
     }
+    out.lo = box_lo ? Vec3i(box_lo[0], box_lo[1], box_lo[2]) : Vec3i(0, 0, 0);
+    out.size = box_size ? Vec3i(box_size[0], box_size[1], box_size[2]) : h->impl->getBackground().getVolumeRes();
+    out.exclude.assign(exclude_ids, exclude_ids + num_exclude);
+    return EMF_OK;
+}
+
+// a result's box into the entry's outputs, each of which may be NULL
+static void putBox(const QueryBox& b, int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3]) {
+    if (lo_out) std::memcpy(lo_out, b.lo.val, sizeof(b.lo.val));
+    if (size_out) std::memcpy(size_out, b.size.val, sizeof(b.size.val));
+    if (R) std::memcpy(R, b.boxPose.rotation().val, 9 * sizeof(float));
+    if (t) std::memcpy(t, b.boxPose.translation().val, 3 * sizeof(float));
+}
+
+// one device array of the box, `elem` bytes per voxel, to the host on the main stream; NULL: not asked for
+static void copyBoxArray(emf_fusion_t* h, const QueryBox& b, void* host, const void* dev, size_t elem, const char* what) {
+    if (!host) return;
+    Stream& s = h->impl->mainStream();
+    hipCheck(hipMemcpyAsync(host, dev, b.voxels() * elem, hipMemcpyDeviceToHost, s.get()), what);
+    s.waitForCompletion();
+}
+
+static int distance_field_entry(const char* who, emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3],
+                                uint32_t site_mask, int32_t cap_voxels, const int32_t* exclude_ids, int32_t num_exclude,
+                                int metres, bool nearest, int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3]) {
+    REQ(h);
+    QueryArgs a;
+    if (const int rc = queryArgs(who, h, box_lo, box_size, exclude_ids, num_exclude, a)) return rc;
     return guarded([&] {
-        const Vec3i n = h->impl->getBackground().getVolumeRes();
-        const Vec3i lo = box_lo ? Vec3i(box_lo[0], box_lo[1], box_lo[2]) : Vec3i(0, 0, 0);
-        const Vec3i size = box_size ? Vec3i(box_size[0], box_size[1], box_size[2]) : n;
-        const std::vector<int> exclude(exclude_ids, exclude_ids + num_exclude);
-        const EMFusion::DistanceField& df = h->impl->distanceField(lo, size, site_mask, cap_voxels, exclude, metres != 0, nearest);
-        if (lo_out) std::memcpy(lo_out, df.boxLo.val, sizeof(df.boxLo.val));
-        if (size_out) std::memcpy(size_out, df.boxSize.val, sizeof(df.boxSize.val));
-        if (R) std::memcpy(R, df.boxPose.rotation().val, 9 * sizeof(float));
-        if (t) std::memcpy(t, df.boxPose.translation().val, 3 * sizeof(float));
+        putBox(h->impl->distanceField(a.lo, a.size, site_mask, cap_voxels, a.exclude, metres != 0, nearest).box, lo_out, size_out, R, t);
     });
 }
 
@@ -627,10 +652,7 @@ int emf_fusion_copy_distance_nearest(emf_fusion_t* h, int32_t* nearest) {
         if (!df.classes) throw HipError("emf_fusion_copy_distance_nearest: no distance field has been computed", EMF_E_ARG);
         if (!df.nearest)
             throw HipError("emf_fusion_copy_distance_nearest: the last distance field was computed without the nearest-site index", EMF_E_ARG);
-        const size_t voxels = static_cast<size_t>(df.boxSize[0]) * df.boxSize[1] * df.boxSize[2];
-        Stream& s = h->impl->mainStream();
-        hipCheck(hipMemcpyAsync(nearest, df.nearest, voxels * sizeof(int32_t), hipMemcpyDeviceToHost, s.get()), "copy_distance_nearest");
-        s.waitForCompletion();
+        copyBoxArray(h, df.box, nearest, df.nearest, sizeof(int32_t), "copy_distance_nearest");
     });
 }
 
@@ -639,9 +661,7 @@ int emf_fusion_query_distance(emf_fusion_t* h, const int32_t* voxels, int32_t n,
     REQ(h);
     return guarded([&] {
         h->impl->queryDistance(voxels, n, classes, d2, nearest);
-        const EMFusion::DistanceField& df = h->impl->lastDistanceField();
-        if (lo_out) std::memcpy(lo_out, df.boxLo.val, sizeof(df.boxLo.val));
-        if (size_out) std::memcpy(size_out, df.boxSize.val, sizeof(df.boxSize.val));
+        putBox(h->impl->lastDistanceField().box, lo_out, size_out, nullptr, nullptr);
     });
 }
 
@@ -656,12 +676,9 @@ int emf_fusion_copy_distance_field(emf_fusion_t* h, uint8_t* classes, int32_t* d
         const EMFusion::DistanceField& df = h->impl->lastDistanceField();
         if (!df.classes) throw HipError("emf_fusion_copy_distance_field: no distance field has been computed", EMF_E_ARG);
         if (metres && !df.metres) throw HipError("emf_fusion_copy_distance_field: the last distance field has no metres", EMF_E_ARG);
-        const size_t voxels = static_cast<size_t>(df.boxSize[0]) * df.boxSize[1] * df.boxSize[2];
-        Stream& s = h->impl->mainStream();
-        if (classes) hipCheck(hipMemcpyAsync(classes, df.classes, voxels, hipMemcpyDeviceToHost, s.get()), "copy_distance_field");
-        if (d2) hipCheck(hipMemcpyAsync(d2, df.d2, voxels * sizeof(int32_t), hipMemcpyDeviceToHost, s.get()), "copy_distance_field");
-        if (metres) hipCheck(hipMemcpyAsync(metres, df.metres, voxels * sizeof(float), hipMemcpyDeviceToHost, s.get()), "copy_distance_field");
-        s.waitForCompletion();
+        copyBoxArray(h, df.box, classes, df.classes, sizeof(uint8_t), "copy_distance_field");
+        copyBoxArray(h, df.box, d2, df.d2, sizeof(int32_t), "copy_distance_field");
+        copyBoxArray(h, df.box, metres, df.metres, sizeof(float), "copy_distance_field");
     });
 }
 
@@ -692,24 +709,11 @@ int emf_fusion_frontiers(emf_fusion_t* h, const int32_t box_lo[3], const int32_t
                          int32_t clearance_voxels, const int32_t* exclude_ids, int32_t num_exclude, int32_t lo_out[3],
                          int32_t size_out[3], float R[9], float t[3], uint32_t counters[3]) {
     REQ(h);
-    if (num_exclude < 0 || (num_exclude > 0 && !exclude_ids)) {
-        std::snprintf(g_err, sizeof(g_err), "emf_fusion_frontiers: %d excluded ids without a list", num_exclude);
-        return EMF_E_ARG;
-    }
-    if ((box_lo == nullptr) != (box_size == nullptr)) {
-        std::snprintf(g_err, sizeof(g_err), "emf_fusion_frontiers: box_lo and box_size go together");
-        return EMF_E_ARG;
-    }
+    QueryArgs a;
+    if (const int rc = queryArgs("emf_fusion_frontiers", h, box_lo, box_size, exclude_ids, num_exclude, a)) return rc;
     return guarded([&] {
-        const Vec3i n = h->impl->getBackground().getVolumeRes();
-        const Vec3i lo = box_lo ? Vec3i(box_lo[0], box_lo[1], box_lo[2]) : Vec3i(0, 0, 0);
-        const Vec3i size = box_size ? Vec3i(box_size[0], box_size[1], box_size[2]) : n;
-        const std::vector<int> exclude(exclude_ids, exclude_ids + num_exclude);
-        const EMFusion::Frontiers& f = h->impl->frontiers(lo, size, min_voxels, clearance_voxels, exclude);
-        if (lo_out) std::memcpy(lo_out, f.boxLo.val, sizeof(f.boxLo.val));
-        if (size_out) std::memcpy(size_out, f.boxSize.val, sizeof(f.boxSize.val));
-        if (R) std::memcpy(R, f.boxPose.rotation().val, 9 * sizeof(float));
-        if (t) std::memcpy(t, f.boxPose.translation().val, 3 * sizeof(float));
+        const EMFusion::Frontiers& f = h->impl->frontiers(a.lo, a.size, min_voxels, clearance_voxels, a.exclude);
+        putBox(f.box, lo_out, size_out, R, t);
         if (counters) {
             counters[EMF_FRONTIER_KEPT] = f.kept;
             counters[EMF_FRONTIER_CLUSTERS] = f.all;
@@ -734,12 +738,7 @@ int emf_fusion_copy_frontiers(emf_fusion_t* h, emf_frontier_cluster_t* records, 
             if (rep_world) EMFusion::frontierWorldPoint(f, f.clusters[k], true, rep_world + 3 * k);
             if (centroid_world) EMFusion::frontierWorldPoint(f, f.clusters[k], false, centroid_world + 3 * k);
         }
-        if (labels) {
-            const size_t voxels = static_cast<size_t>(f.boxSize[0]) * f.boxSize[1] * f.boxSize[2];
-            Stream& s = h->impl->mainStream();
-            hipCheck(hipMemcpyAsync(labels, f.labels, voxels * sizeof(int32_t), hipMemcpyDeviceToHost, s.get()), "copy_frontiers");
-            s.waitForCompletion();
-        }
+        copyBoxArray(h, f.box, labels, f.labels, sizeof(int32_t), "copy_frontiers");
     });
 }
 
@@ -765,28 +764,19 @@ int emf_fusion_plan(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_
                       num_start, num_goals, num_exclude);
         return EMF_E_ARG;
     }
-    if ((box_lo == nullptr) != (box_size == nullptr)) {
-        std::snprintf(g_err, sizeof(g_err), "emf_fusion_plan: box_lo and box_size go together");
-        return EMF_E_ARG;
-    }
+    QueryArgs a;
+    if (const int rc = queryArgs("emf_fusion_plan", h, box_lo, box_size, exclude_ids, num_exclude, a)) return rc;
     return guarded([&] {
-        const Vec3i n = h->impl->getBackground().getVolumeRes();
-        const Vec3i lo = box_lo ? Vec3i(box_lo[0], box_lo[1], box_lo[2]) : Vec3i(0, 0, 0);
-        const Vec3i size = box_size ? Vec3i(box_size[0], box_size[1], box_size[2]) : n;
         std::vector<Vec3i> start, goals;
         if (num_start == 0) {  // the voxel under the camera
             const Vec3i c = h->impl->cameraVoxel();
-            start.push_back(Vec3i(c[0] - lo[0], c[1] - lo[1], c[2] - lo[2]));
+            start.push_back(Vec3i(c[0] - a.lo[0], c[1] - a.lo[1], c[2] - a.lo[2]));
         }
         for (int32_t k = 0; k < num_start; ++k) start.push_back(Vec3i(start_voxels[3 * k], start_voxels[3 * k + 1], start_voxels[3 * k + 2]));
         for (int32_t k = 0; k < num_goals; ++k) goals.push_back(Vec3i(goal_voxels[3 * k], goal_voxels[3 * k + 1], goal_voxels[3 * k + 2]));
-        const std::vector<int> exclude(exclude_ids, exclude_ids + num_exclude);
-        const EMFusion::Plan& p = h->impl->plan(lo, size, start, seed_radius_voxels, through_unknown != 0, clearance_voxels,
-                                                max_cost, goals, path_capacity, exclude);
-        if (lo_out) std::memcpy(lo_out, p.boxLo.val, sizeof(p.boxLo.val));
-        if (size_out) std::memcpy(size_out, p.boxSize.val, sizeof(p.boxSize.val));
-        if (R) std::memcpy(R, p.boxPose.rotation().val, 9 * sizeof(float));
-        if (t) std::memcpy(t, p.boxPose.translation().val, 3 * sizeof(float));
+        const EMFusion::Plan& p = h->impl->plan(a.lo, a.size, start, seed_radius_voxels, through_unknown != 0, clearance_voxels,
+                                                max_cost, goals, path_capacity, a.exclude);
+        putBox(p.box, lo_out, size_out, R, t);
         if (counters) std::memcpy(counters, p.counters, sizeof(p.counters));
         if (longest_path) {
             *longest_path = 0;
@@ -817,15 +807,10 @@ int emf_fusion_copy_plan(emf_fusion_t* h, uint32_t* goal_cost, int32_t* lengths,
             const size_t kept = std::min<size_t>(r.path.size(), static_cast<size_t>(capacity));
             for (size_t k = 0; k < kept; ++k) {
                 if (paths) paths[g * capacity + k] = r.path[k];
-                if (path_world) EMFusion::planWorldPoint(p, r.path[k], path_world + 3 * (g * capacity + k));
+                if (path_world) p.box.worldPoint(p.box.unravel(r.path[k]), path_world + 3 * (g * capacity + k));
             }
         }
-        if (cost) {
-            const size_t voxels = static_cast<size_t>(p.boxSize[0]) * p.boxSize[1] * p.boxSize[2];
-            Stream& s = h->impl->mainStream();
-            hipCheck(hipMemcpyAsync(cost, p.cost, voxels * sizeof(uint32_t), hipMemcpyDeviceToHost, s.get()), "copy_plan");
-            s.waitForCompletion();
-        }
+        copyBoxArray(h, p.box, cost, p.cost, sizeof(uint32_t), "copy_plan");
     });
 }
 

@@ -263,6 +263,10 @@ public:
     }
     size_t bytes() const { return n_; }
     bool empty() const { return p_ == nullptr; }
+    // at least `bytes`, contents not kept: a new block (a multiple of 16 bytes) only when this one is smaller
+    void reserve(size_t bytes) {
+        if (n_ < bytes) *this = DeviceBuffer((bytes + 15) / 16 * 16);
+    }
     // Released buffers wait in a process-wide pool (types.cpp, capped by EMF_POOL_MIB) instead of going
     // through hipFree, which synchronises the device.  trimPool() really frees them (and does wait);
     // emf_fusion_trim_pool() is its C entry, and a failing hipMalloc trims and retries once.

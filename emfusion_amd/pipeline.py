@@ -280,6 +280,58 @@ def _farr(v, n):
     return (C.c_float * n)(*a.tolist())
 
 
+def _metres_to_voxels(metres, voxel):
+    """Metres rounded up to whole voxels, at most 4096 and 0 for "none" -- in float32, as write_results does."""
+    return int(min(np.ceil(np.float32(metres) / np.float32(voxel)), np.float32(4096))) if metres > 0 else 0
+
+
+class _BoxFrame:
+    """The frame of a box of the background that the scene queries share: bg_R (3x3), bg_t (3) the
+    background's pose, res its resolution and lo the box origin, both (x, y, z) voxels, voxel its voxel size."""
+
+    def __init__(self, bg_R, bg_t, res, voxel, lo=(0, 0, 0)):
+        self.R, self.t = np.ascontiguousarray(bg_R, np.float64), np.asarray(bg_t, np.float64)
+        self.res, self.lo = np.array(list(res), np.float64), np.array(list(lo), np.int64)
+        self.voxel = float(voxel)
+
+    def world(self, vox):
+        """Box voxels (n, 3), fractional ones too -> world points (n, 3) f32: in float64, rounded once."""
+        p = (np.asarray(vox, np.float64) + (self.lo - (self.res - 1) / 2.0)) * np.float64(self.voxel)
+        return (p @ self.R.T + self.t).astype(np.float32)
+
+    def to_voxels(self, points):
+        """World points -> box voxels (n, 3) i32, each rounded to its voxel: clipped to the int32 range, -1 in a
+        coordinate that is not finite -- so a point that is no point lies outside every box."""
+        with np.errstate(invalid="ignore"):
+            q = (np.asarray(points, np.float64).reshape(-1, 3) - self.t) @ self.R
+            v = np.rint(q / self.voxel + (self.res - 1) / 2.0) - self.lo
+        return np.where(np.isfinite(v), np.clip(v, -2.0 ** 31, 2.0 ** 31 - 1), -1).astype(np.int64).astype(np.int32)
+
+    @staticmethod
+    def unravel(lin, size):
+        """Linear indices (z * ny + y) * nx + x of a box of `size` (x, y, z) -> its voxels (n, 3) i64."""
+        lin, nx, ny = np.asarray(lin, np.int64), int(size[0]), int(size[1])
+        return np.stack([lin % nx, lin // nx % ny, lin // (nx * ny)], axis=1)
+
+
+def _box_args(box, exclude):
+    """(box_lo, box_size, exclude_ids, num_exclude) of the query entries; a box of None is the whole background."""
+    lo = size = None
+    if box is not None:
+        lo, size = (C.c_int32 * 3)(*[int(v) for v in box[0]]), (C.c_int32 * 3)(*[int(v) for v in box[1]])
+    return lo, size, (C.c_int32 * max(len(exclude), 1))(*[int(i) for i in exclude]), len(exclude)
+
+
+def _box_outs():
+    """The (lo_out, size_out, R, t) arrays the query entries describe their box in."""
+    return (C.c_int32 * 3)(), (C.c_int32 * 3)(), (C.c_float * 9)(), (C.c_float * 3)()
+
+
+def _read_box_outs(lo, sz, R, t):
+    """((lo, size), (R 3x3, t 3)): the box and the pose of its voxel (0, 0, 0) -> world."""
+    return (tuple(lo), tuple(sz)), (np.array(R, np.float32).reshape(3, 3), np.array(t, np.float32))
+
+
 def look_at(eye, target, up=(0.0, -1.0, 0.0)):
     """Viewer -> world (R, t) of a camera at `eye` looking at `target`, in the OpenCV camera convention (+z forward,
     +y down, +x right): R's columns are the camera axes in world coordinates, t = eye.  `up` is the world direction
@@ -798,15 +850,28 @@ class Fusion:
         """The box (lo, size), both (x, y, z) voxels, of `size` voxels (an int or three) centred on the background voxel
         under the camera and clipped to the volume; None if nothing of it lies inside."""
         size = (int(size),) * 3 if np.isscalar(size) else tuple(int(v) for v in size)
-        R, t = self.background_pose()
         res = np.array(list(self.params.bg_res), np.int64)
-        q = R.astype(np.float64).T @ (self.pose(0)[1].astype(np.float64) - t.astype(np.float64))
-        centre = np.rint(q / float(self.params.bg_voxel_size) + (res - 1) / 2.0).astype(np.int64)
+        centre = self._box_frame().to_voxels(self.pose(0)[1])[0].astype(np.int64)
         lo = np.maximum(centre - np.array(size) // 2, 0)
         hi = np.minimum(centre - np.array(size) // 2 + np.array(size), res)
         if (hi <= lo).any():
             return None
         return tuple(int(v) for v in lo), tuple(int(v) for v in hi - lo)
+
+    def _box_frame(self, lo=(0, 0, 0)):
+        """The frame of the box of the background at `lo`, at the background's current pose."""
+        return _BoxFrame(*self.background_pose(), self.params.bg_res, self.params.bg_voxel_size, lo)
+
+    def _resolve_box(self, who, box, size):
+        """The `box` argument of the query `who`: None, (lo, size), or "camera" with `size` for camera_box(size)."""
+        if not isinstance(box, str):
+            return box
+        if box != "camera" or size is None:
+            raise ValueError(f'{who}: box="camera" needs a size')
+        box = self.camera_box(size)
+        if box is None:
+            raise ValueError(f"{who}: the camera box lies outside the background")
+        return box
 
     def distance_field(self, box=None, unknown_is_obstacle=False, cap=0.0, exclude=(), signed=False, metres=True,
                        size=None, nearest=False):
@@ -826,26 +891,17 @@ class Fusion:
         the nearest obstacle voxel -- the smallest index among equally near ones -- and -1 exactly where d2 is DF_FAR
         (obstacle_offsets turns it into vectors); with signed=True also nearest_inside, the same for the second
         transform.  The index stays on the device for query_distance."""
-        if isinstance(box, str):
-            if box != "camera" or size is None:
-                raise ValueError('distance_field: box="camera" needs a size')
-            box = self.camera_box(size)
-            if box is None:
-                raise ValueError("distance_field: the camera box lies outside the background")
+        box = self._resolve_box("distance_field", box, size)
         vs = float(self.params.bg_voxel_size)
-        cap_voxels = min(int(np.ceil(np.float32(cap) / np.float32(vs))), 4096) if cap > 0 else 0  # float32, as write_results does
+        cap_voxels = _metres_to_voxels(cap, vs)
         sites = 2 | (4 if unknown_is_obstacle else 0)
-        ex = (C.c_int32 * max(len(exclude), 1))(*[int(i) for i in exclude])
-        lo_arg = size_arg = None
-        if box is not None:
-            lo_arg, size_arg = (C.c_int32 * 3)(*[int(v) for v in box[0]]), (C.c_int32 * 3)(*[int(v) for v in box[1]])
+        lo_arg, size_arg, ex, n_ex = _box_args(box, exclude)
 
         def run(mask, want_metres):
-            lo, sz, R, t = (C.c_int32 * 3)(), (C.c_int32 * 3)(), (C.c_float * 9)(), (C.c_float * 3)()
+            outs = _box_outs()
             entry = "emf_fusion_distance_field_nearest" if nearest else "emf_fusion_distance_field"
-            _check(entry, getattr(load(), entry)(self._h, lo_arg, size_arg, mask, cap_voxels, ex, len(exclude),
-                                                 int(want_metres), lo, sz, R, t))
-            shape = (sz[2], sz[1], sz[0])
+            _check(entry, getattr(load(), entry)(self._h, lo_arg, size_arg, mask, cap_voxels, ex, n_ex, int(want_metres), *outs))
+            shape = tuple(outs[1])[::-1]
             classes, d2 = np.empty(shape, np.uint8), np.empty(shape, np.int32)
             m = np.empty(shape, np.float32) if want_metres else None
             _check("emf_fusion_copy_distance_field",
@@ -854,8 +910,7 @@ class Fusion:
             index = np.empty(shape, np.int32) if nearest else None
             if nearest:
                 _check("emf_fusion_copy_distance_nearest", load().emf_fusion_copy_distance_nearest(self._h, index.ctypes.data))
-            return (classes, d2, m, (tuple(lo), tuple(sz)), (np.array(R, np.float32).reshape(3, 3), np.array(t, np.float32)),
-                    index)
+            return classes, d2, m, *_read_box_outs(*outs), index
 
         if signed:  # the complement first: the field that stays on the device for query_distance is the outside one
             _, d2_in, m_in, _, _, index_in = run(7 ^ sites, True)
@@ -889,18 +944,12 @@ class Fusion:
           once), NaN where there is none; direction (n, 3) f32, the unit vector from the point's voxel toward it in the
           world frame, NaN where there is none or the voxel is the obstacle itself.
         Needs a last distance_field(nearest=True); box, pose and voxel size are the session's current ones."""
-        pts = np.asarray(points, np.float64).reshape(-1, 3)
         vs = float(self.params.bg_voxel_size)
-        res = np.array(list(self.params.bg_res), np.float64)
         c_lo, c_size = (C.c_int32 * 3)(), (C.c_int32 * 3)()  # the box of the last field
         _check("emf_fusion_query_distance", load().emf_fusion_query_distance(self._h, None, 0, None, None, None, c_lo, c_size))
-        lo_box, size = np.array(list(c_lo), np.int64), np.array(list(c_size), np.int64)
-        bg_R, bg_t = self.background_pose()
-        bg_R, bg_t = bg_R.astype(np.float64), bg_t.astype(np.float64)
-        q = (pts - bg_t) @ bg_R
-        with np.errstate(invalid="ignore"):
-            v = np.rint(q / vs + (res - 1) / 2.0) - lo_box
-        v = np.where(np.isfinite(v), np.clip(v, -2.0 ** 31, 2.0 ** 31 - 1), -1).astype(np.int64).astype(np.int32)
+        size = np.array(list(c_size), np.int64)
+        frame = self._box_frame(c_lo)
+        v = frame.to_voxels(points)
         n = len(v)
         cls, d2, near = np.full(n, 255, np.uint8), np.full(n, 0x7fffffff, np.int32), np.full(n, -1, np.int32)
         flat = np.ascontiguousarray(v.reshape(-1))
@@ -913,15 +962,10 @@ class Fusion:
         metres = np.where(d2 == 0x7fffffff, np.float32(np.inf), metres).astype(np.float32)
         has = near >= 0
         lin = np.where(has, near, 0).astype(np.int64)
-        site = np.stack([lin % size[0], lin // size[0] % size[1], lin // (size[0] * size[1])], axis=1)
+        site = frame.unravel(lin, size)
         nearest_voxel = np.where(has[:, None], site, -1).astype(np.int32)
-
-        def world(vox):  # box voxels -> world, as frontiers() and plan() do: float64, rounded once
-            p = (np.asarray(vox, np.float64) + (lo_box - (res - 1) / 2.0)) * np.float64(vs)
-            return p @ bg_R.T + bg_t
-
-        nearest_world = np.where(has[:, None], world(site), np.nan).astype(np.float32)
-        step = (site - v.astype(np.int64)).astype(np.float64) @ bg_R.T  # the rotation of the voxel offset
+        nearest_world = np.where(has[:, None], frame.world(site), np.nan).astype(np.float32)
+        step = (site - v.astype(np.int64)).astype(np.float64) @ frame.R.T  # the rotation of the voxel offset
         norm = np.sqrt((step * step).sum(axis=1))
         with np.errstate(invalid="ignore", divide="ignore"):
             direction = np.where((has & (norm > 0))[:, None], step / norm[:, None], np.nan).astype(np.float32)
@@ -944,45 +988,29 @@ class Fusion:
           kept, n_clusters, n_voxels: clusters kept, all clusters, frontier voxels;
           labels (bz, by, bx) i32 with labels=True: the label of the voxel's cluster, -1 off the frontier."""
         from ._lib import FRONTIER_CLUSTER_DTYPE
-        if isinstance(box, str):
-            if box != "camera" or size is None:
-                raise ValueError('frontiers: box="camera" needs a size')
-            box = self.camera_box(size)
-            if box is None:
-                raise ValueError("frontiers: the camera box lies outside the background")
+        box = self._resolve_box("frontiers", box, size)
         vs = float(self.params.bg_voxel_size)
-        clearance_voxels = min(int(np.ceil(np.float32(clearance) / np.float32(vs))), 4096) if clearance > 0 else 0
-        ex = (C.c_int32 * max(len(exclude), 1))(*[int(i) for i in exclude])
-        lo_arg = size_arg = None
-        if box is not None:
-            lo_arg, size_arg = (C.c_int32 * 3)(*[int(v) for v in box[0]]), (C.c_int32 * 3)(*[int(v) for v in box[1]])
-        lo, sz, R, t = (C.c_int32 * 3)(), (C.c_int32 * 3)(), (C.c_float * 9)(), (C.c_float * 3)()
+        lo_arg, size_arg, ex, n_ex = _box_args(box, exclude)
+        lo, sz, _, _ = outs = _box_outs()
         counters = np.zeros(3, np.uint32)
         _check("emf_fusion_frontiers",
-               load().emf_fusion_frontiers(self._h, lo_arg, size_arg, int(min_voxels), clearance_voxels, ex, len(exclude), lo,
-                                           sz, R, t, counters.ctypes.data))
+               load().emf_fusion_frontiers(self._h, lo_arg, size_arg, int(min_voxels), _metres_to_voxels(clearance, vs), ex, n_ex,
+                                           *outs, counters.ctypes.data))
         kept = int(counters[0])
         records = np.zeros(kept, np.dtype(FRONTIER_CLUSTER_DTYPE))
         volume = np.empty((sz[2], sz[1], sz[0]), np.int32) if labels else None
         _check("emf_fusion_copy_frontiers",
                load().emf_fusion_copy_frontiers(self._h, records.ctypes.data if kept else None, kept, None, None,
                                                 volume.ctypes.data if labels else None))
-        # the world points: from the integers, in float64, rounded once
-        bg_R, bg_t = self.background_pose()
-        off = np.array(list(lo), np.float64) - (np.array(list(self.params.bg_res), np.float64) - 1) / 2
-
-        def world(v):
-            p = (v + off) * np.float64(vs)
-            return (p @ bg_R.astype(np.float64).T + bg_t.astype(np.float64)).astype(np.float32)
-
+        world = self._box_frame(lo).world  # the world points: from the integers, in float64, rounded once
         centroid = world(records["sum"].astype(np.float64) / np.maximum(records["count"], 1).astype(np.float64)[:, None])
         rep = world(records["rep"].astype(np.float64))
         clusters = [dict(label=int(r["label"]), count=int(r["count"]), lo=tuple(int(v) for v in r["lo"]),
                          hi=tuple(int(v) for v in r["hi"]), sum=tuple(int(v) for v in r["sum"]),
                          rep=tuple(int(v) for v in r["rep"]), centroid_world=centroid[k], rep_world=rep[k])
                     for k, r in enumerate(records)]
-        out = dict(clusters=clusters, centroid_world=centroid, rep_world=rep, box=(tuple(lo), tuple(sz)),
-                   box_pose=(np.array(R, np.float32).reshape(3, 3), np.array(t, np.float32)), voxel_size=vs, kept=kept,
+        out_box, box_pose = _read_box_outs(*outs)
+        out = dict(clusters=clusters, centroid_world=centroid, rep_world=rep, box=out_box, box_pose=box_pose, voxel_size=vs, kept=kept,
                    n_clusters=int(counters[1]), n_voxels=int(counters[2]), records=records)
         if labels:
             out["labels"] = volume
@@ -1000,7 +1028,8 @@ class Fusion:
         see its own near field.  Moves are 26-connected with the integer weights 3 / 4 / 5 for face / edge / corner
         steps; max_cost (metres of face steps, 0: none) stops the search at max(floor(3 * max_cost / voxel), 1).
         goals="frontiers": self.frontiers(box, min_voxels, clearance, exclude) and a plan to every kept cluster's
-        representative; else (n, 3) world points, each rounded to its voxel and never moved to another one.
+        representative; else (n, 3) world points, each rounded to its voxel and never moved to another one.  A start or
+        goal with a coordinate that is not finite becomes a voxel outside the box: a goal without a path, a start that is ignored.
         Returns a dict:
           goals: one dict per goal -- with "frontiers" the cluster's record of frontiers() -- that gains voxel (box
           coordinates), reachable, cost (the chamfer cost; PLAN_UNREACHED / PLAN_BLOCKED without a path), length_m =
@@ -1011,34 +1040,13 @@ class Fusion:
           converged, rounds, n_finite, n_starts: the counters; frontiers: what frontiers() returned (with "frontiers");
           cost (bz, by, bx) u32 with field=True."""
         from ._lib import PLAN_BLOCKED
-        if isinstance(box, str):
-            if box != "camera" or size is None:
-                raise ValueError('plan: box="camera" needs a size')
-            box = self.camera_box(size)
-            if box is None:
-                raise ValueError("plan: the camera box lies outside the background")
+        box = self._resolve_box("plan", box, size)
         vs = float(self.params.bg_voxel_size)
-
-        def voxels_of(metres):
-            return min(int(np.ceil(np.float32(metres) / np.float32(vs))), 4096) if metres > 0 else 0
-
-        clearance_voxels = voxels_of(clearance)
-        radius_voxels = max(clearance_voxels, 1) if start_radius is None else voxels_of(start_radius)
+        clearance_voxels = _metres_to_voxels(clearance, vs)
+        radius_voxels = max(clearance_voxels, 1) if start_radius is None else _metres_to_voxels(start_radius, vs)
         # at least 1: a positive cap below a third of a voxel must not turn into 0, which means "no cap"
         cost_cap = min(max(int(np.floor(3.0 * float(max_cost) / vs)), 1), PLAN_BLOCKED - 1) if max_cost > 0 else 0
-        res = np.array(list(self.params.bg_res), np.float64)
-        lo_box = np.array(box[0] if box is not None else (0, 0, 0), np.int64)
-        bg_R, bg_t = self.background_pose()
-        bg_R, bg_t = bg_R.astype(np.float64), bg_t.astype(np.float64)
-
-        def to_voxels(points):  # world points -> box voxels, each rounded to its voxel
-            q = (np.asarray(points, np.float64).reshape(-1, 3) - bg_t) @ bg_R
-            return (np.rint(q / vs + (res - 1) / 2.0).astype(np.int64) - lo_box).astype(np.int32)
-
-        def world(v):  # box voxels -> world, as frontiers() does: float64, rounded once
-            p = (np.asarray(v, np.float64) + (lo_box - (res - 1) / 2.0)) * np.float64(vs)
-            return (p @ bg_R.T + bg_t).astype(np.float32)
-
+        frame = self._box_frame(box[0] if box is not None else (0, 0, 0))
         found = None
         if isinstance(goals, str):
             if goals != "frontiers":
@@ -1046,25 +1054,23 @@ class Fusion:
             found = self.frontiers(box=box, min_voxels=min_voxels, clearance=clearance, exclude=exclude)
             goal_voxels = np.array([c["rep"] for c in found["clusters"]], np.int32).reshape(-1, 3)
         else:
-            goal_voxels = to_voxels(goals)
+            goal_voxels = frame.to_voxels(goals)
         if start is None:  # the voxel under the camera; the nearest voxel of the background where it stands outside
-            cam = to_voxels(self.pose(0)[1]).astype(np.int64) + lo_box
-            start_voxels = (np.clip(cam, 0, res.astype(np.int64) - 1) - lo_box).astype(np.int32)
+            cam = frame.to_voxels(self.pose(0)[1]).astype(np.int64) + frame.lo
+            start_voxels = (np.clip(cam, 0, frame.res.astype(np.int64) - 1) - frame.lo).astype(np.int32)
         else:
-            start_voxels = to_voxels(start)
+            start_voxels = frame.to_voxels(start)
         n_goals = len(goal_voxels)
-        ex = (C.c_int32 * max(len(exclude), 1))(*[int(i) for i in exclude])
-        lo_arg = size_arg = None
-        if box is not None:
-            lo_arg, size_arg = (C.c_int32 * 3)(*[int(v) for v in box[0]]), (C.c_int32 * 3)(*[int(v) for v in box[1]])
-        lo, sz, R, t = (C.c_int32 * 3)(), (C.c_int32 * 3)(), (C.c_float * 9)(), (C.c_float * 3)()
+        lo_arg, size_arg, ex, n_ex = _box_args(box, exclude)
+        outs = _box_outs()
+        sz = outs[1]
         counters, longest = np.zeros(4, np.uint32), C.c_int32(0)
         starts = np.ascontiguousarray(start_voxels.reshape(-1))
         flat_goals = np.ascontiguousarray(goal_voxels.reshape(-1)) if n_goals else np.zeros(3, np.int32)
         _check("emf_fusion_plan",
                load().emf_fusion_plan(self._h, lo_arg, size_arg, starts.ctypes.data_as(C.POINTER(C.c_int32)), len(start_voxels),
                                       radius_voxels, int(bool(through_unknown)), clearance_voxels, cost_cap,
-                                      flat_goals.ctypes.data_as(C.POINTER(C.c_int32)), n_goals, -1, ex, len(exclude), lo, sz, R, t,
+                                      flat_goals.ctypes.data_as(C.POINTER(C.c_int32)), n_goals, -1, ex, n_ex, *outs,
                                       counters.ctypes.data, C.byref(longest)))
         cap = int(longest.value)
         goal_cost, lengths = np.zeros(n_goals, np.uint32), np.zeros(n_goals, np.int32)
@@ -1073,23 +1079,21 @@ class Fusion:
         _check("emf_fusion_copy_plan",
                load().emf_fusion_copy_plan(self._h, goal_cost.ctypes.data, lengths.ctypes.data, steps.ctypes.data,
                                            paths.ctypes.data, cap, None, volume.ctypes.data if field else None))
-        nx, ny = int(sz[0]), int(sz[1])
         records = []
         for g in range(n_goals):
             k = max(int(lengths[g]), 0)
-            lin = paths[g, :k].astype(np.int64)
-            vox = np.stack([lin % nx, lin // nx % ny, lin // (nx * ny)], axis=1).astype(np.int32)
+            vox = frame.unravel(paths[g, :k], sz).astype(np.int32)
             r = dict(found["clusters"][g]) if found is not None else {}
             f, e, c = (int(v) for v in steps[g])
             r.update(voxel=tuple(int(v) for v in goal_voxels[g]), reachable=k > 0, cost=int(goal_cost[g]),
                      length_m=(f + np.sqrt(2.0) * e + np.sqrt(3.0) * c) * np.float64(vs), steps=(f, e, c), path_vox=vox,
-                     path_world=world(vox))
+                     path_world=frame.world(vox))
             records.append(r)
         if found is not None:  # reachable first, cheapest first (stable: ties and the rest keep the frontier order)
             records = sorted(records, key=lambda r: (not r["reachable"], r["cost"] if r["reachable"] else 0))
+        out_box, box_pose = _read_box_outs(*outs)
         out = dict(goals=records, start_voxels=start_voxels, start_radius_voxels=radius_voxels, clearance_voxels=clearance_voxels,
-                   max_cost=cost_cap, box=(tuple(lo), tuple(sz)),
-                   box_pose=(np.array(R, np.float32).reshape(3, 3), np.array(t, np.float32)), voxel_size=vs,
+                   max_cost=cost_cap, box=out_box, box_pose=box_pose, voxel_size=vs,
                    converged=bool(counters[0]), rounds=int(counters[1]), n_finite=int(counters[2]), n_starts=int(counters[3]))
         if found is not None:
             out.update(clusters=records, frontiers=found)

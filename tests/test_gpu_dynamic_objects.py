@@ -22,10 +22,26 @@ def _spin(lib, stream, word, ms=4000):
     assert rc == 0, rc
 
 
-def test_reciprocal_verdicts_are_cached_and_can_be_had_without_waiting(dev):
+def _own_process(args):
+    """python `args` in a fresh process in which every stream has a hardware queue to itself (dynamic_probe.py
+    says why): with the default four, a stream created during the scenario can land on the probe's queue and wait
+    behind the spinning wave; whether one does depends on how many streams the process has made before."""
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    env = dict(os.environ, GPU_MAX_HW_QUEUES="16")
+    run = subprocess.run([sys.executable, *args], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
+    return run.stdout
+
+
+def reciprocal_scenario():
     import ctypes as C
     from emfusion_amd import _lib, devmem
     lib = _lib.load()
+    devmem.set_device(0)
     size = C.c_float(0.0123456)  # a size nothing else in the suite uses
     r = C.c_float(-1)
     assert lib.emf_hip_voxelReciprocalCached(size, C.byref(r)) == -7 and r.value == 0  # EMF_E_NOTREADY
@@ -54,6 +70,10 @@ def test_reciprocal_verdicts_are_cached_and_can_be_had_without_waiting(dev):
     probe.synchronize()
 
 
+def test_reciprocal_verdicts_are_cached_and_can_be_had_without_waiting(dev):
+    _own_process(["-c", "from tests.test_gpu_dynamic_objects import reciprocal_scenario as run; run()"])
+
+
 def test_spawning_and_resizing_objects_never_synchronises_the_device(dev):
     """30 frames (tests/dynamic_probe.py, in a process of its own so that every stream has a hardware queue
     to itself): object 1 is spawned from its mask; from frame 3 on its instance mask is reported too
@@ -62,16 +82,8 @@ def test_spawning_and_resizing_objects_never_synchronises_the_device(dev):
     8.  Every process_frame() returns within milliseconds while the probe's wave -- resident for three
     seconds unless released -- is still spinning: nothing in the frame waited for the device."""
     import json
-    import os
-    import subprocess
-    import sys
-    from pathlib import Path
-    root = Path(__file__).resolve().parent.parent
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="16")
-    run = subprocess.run([sys.executable, str(root / "tests" / "dynamic_probe.py")], cwd=root, env=env,
-                         capture_output=True, text=True, timeout=600)
-    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
-    line = [ln for ln in run.stdout.splitlines() if ln.startswith("PROBE_RESULT ")][-1]
+    stdout = _own_process(["tests/dynamic_probe.py"])
+    line = [ln for ln in stdout.splitlines() if ln.startswith("PROBE_RESULT ")][-1]
     out = json.loads(line[len("PROBE_RESULT "):])
     frames = out["frames"]
     assert len(frames) == 30

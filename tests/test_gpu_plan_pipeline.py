@@ -193,6 +193,19 @@ def test_earlier_queries_are_unchanged_after_a_plan(session):
     assert records.tobytes() == fr["records"].tobytes() and labels.tobytes() == fr["labels"].tobytes()
 
 
+def test_the_shared_clearance_scratch_is_never_reused_stale(session):
+    """frontiers() and plan() put their clearance transform into one scratch volume: each call fills it for its own
+    clearance, so a plan with another clearance in between leaves the frontiers what they were."""
+    fus, _ = session
+    a = fus.frontiers(labels=True, min_voxels=1, clearance=0.03)
+    got = fus.plan(goals=world_of(fus, (0, 0, 0), np.array([[31, 32, 5]])), clearance=0.07, through_unknown=True)
+    b = fus.frontiers(labels=True, min_voxels=1, clearance=0.03)
+    c = fus.frontiers(labels=True, min_voxels=1, clearance=0.07)
+    assert a["records"].tobytes() == b["records"].tobytes() and a["labels"].tobytes() == b["labels"].tobytes()
+    assert c["n_voxels"] <= a["n_voxels"]
+    check(fus, got, clearance=0.07, through_unknown=True)
+
+
 def test_the_next_frame_is_that_of_a_session_that_never_asked(dev):
     from tests.test_gpu_frontier_pipeline import feed, open_session
     out = []
