@@ -7,7 +7,7 @@
 //                  [--weld-meshes] [--mesh-min-triangles N] [--mesh-largest-object] [--mesh-simplify CELL] [--world-mesh]
 //                  [--distance-field] [--distance-cap M] [--distance-unknown-obstacle] [--distance-nearest]
 //                  [--frontiers] [--frontier-min-voxels N] [--frontier-clearance M]
-//                  [--plan] [--plan-clearance M] [--plan-through-unknown]
+//                  [--plan] [--plan-clearance M] [--plan-through-unknown] [--plan-shortcut W]
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
 //                  [--bg-res R] [--bg-voxel M] [--obj-res R] [--volumes] --out DIR
 //   emfusion_synth --dir BASE/ [--colordir colour] [--depthdir depth] [--intrinsics fx fy cx cy] ... --out DIR
@@ -117,6 +117,9 @@ static float frontierClearance = 0.f;
 // background (--frontier-min-voxels), M metres clear of the nearest occupied voxel.
 static bool planOut = false, planThroughUnknown = false;
 static float planClearance = 0.f;
+// --plan-shortcut W (needs --plan): plan.txt also carries one "waypoints" line per reachable goal (EMFusion::shortcutPlan)
+static int planShortcut = 0;
+static bool planShortcutGiven = false;
 // --motion-masks [--motion-band M] [--motion-min-pixels N] [--motion-max-masks N]: mask frames propose their own
 // instance masks from the depth in front of the background model (EMFusion::setMotionMasks) instead of reading them
 static bool motionMasks = false;
@@ -223,6 +226,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     emf.setDistanceNearestOutput(distanceNearest);
     emf.setFrontierOutput(frontiersOut, frontierMinVoxels, frontierClearance);
     emf.setPlanOutput(planOut, planClearance, planThroughUnknown);
+    if (planShortcut > 0) emf.setPlanShortcutOutput(planShortcut);
     set3dView(emf, params, view3d);
     std::vector<uint8_t> rendered(3 * params.frameSize.area());
     const auto t0 = std::chrono::steady_clock::now();
@@ -337,6 +341,10 @@ int main(int argc, char** argv) {
         else if (a == "--plan") planOut = true;
         else if (a == "--plan-clearance" && i + 1 < argc) planClearance = std::max(static_cast<float>(std::atof(argv[++i])), 0.f);
         else if (a == "--plan-through-unknown") planThroughUnknown = true;
+        else if (a == "--plan-shortcut" && i + 1 < argc) {
+            planShortcut = std::atoi(argv[++i]);
+            planShortcutGiven = true;
+        }
         else if (a == "--mesh-min-triangles") meshMinTriangles = static_cast<unsigned>(std::max(next(), 0));
         else if (a == "--mesh-largest-object") meshLargestObject = true;
         else if (a == "--mesh-simplify" && i + 1 < argc) meshSimplifyCell = static_cast<float>(std::atof(argv[++i]));
@@ -361,6 +369,10 @@ int main(int argc, char** argv) {
     }
     if (distanceNearest && !distanceOut) {  // (before any device is touched)
         std::fprintf(stderr, "usage: emfusion_synth: --distance-nearest writes nearest.bin beside distance.bin and needs --distance-field\n");
+        return 2;
+    }
+    if (planShortcutGiven && (!planOut || planShortcut < 1)) {  // (before any device is touched)
+        std::fprintf(stderr, "usage: emfusion_synth: --plan-shortcut W (>= 1) adds the waypoints lines to plan.txt and needs --plan\n");
         return 2;
     }
     if (motionMasks && !maskDir.empty()) {  // (before any device is touched)
@@ -448,6 +460,7 @@ int main(int argc, char** argv) {
         emf.setDistanceNearestOutput(distanceNearest);
         emf.setFrontierOutput(frontiersOut, frontierMinVoxels, frontierClearance);
         emf.setPlanOutput(planOut, planClearance, planThroughUnknown);
+        if (planShortcut > 0) emf.setPlanShortcutOutput(planShortcut);
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);
 

@@ -90,6 +90,9 @@ def main():
                     help="with --plan: keep paths and goals at least M metres from the nearest occupied voxel")
     ap.add_argument("--plan-through-unknown", dest="plan_through_unknown", action="store_true",
                     help="with --plan: unobserved voxels are traversable too")
+    ap.add_argument("--plan-shortcut", dest="plan_shortcut", type=int, default=0, metavar="W",
+                    help="with --plan: plan.txt also carries one waypoints line per reachable goal, the path shortened by "
+                         "lines of sight over at most W path voxels")
     ap.add_argument("--weld-meshes", dest="weld_meshes", action="store_true",
                     help="weld every mesh written (mesh_*.ply of the live models, frame_meshes/) by grid edge on the "
                          "device: one vertex per edge instead of one per cube that touches it")
@@ -123,6 +126,10 @@ def main():
         ap.error("--motion-masks and --masks exclude each other")
     if args.distance_nearest and not args.distance_field:
         ap.error("--distance-nearest writes nearest.bin beside distance.bin and needs --distance-field")
+    if args.plan_shortcut and not args.plan:
+        ap.error("--plan-shortcut W adds the waypoints lines to plan.txt and needs --plan")
+    if args.plan_shortcut < 0:
+        ap.error("--plan-shortcut takes a positive window W")
     try:
         follow_step = tuple(int(v) for v in args.follow_step.split(","))
         assert len(follow_step) == 3
@@ -191,7 +198,7 @@ def main():
                      exp_frontiers=args.frontiers, frontier_min_voxels=max(args.frontier_min_voxels, 1),
                      frontier_clearance=max(args.frontier_clearance, 0.0), exp_plan=args.plan,
                      plan_clearance=max(args.plan_clearance, 0.0), plan_through_unknown=args.plan_through_unknown,
-                     exp_distance_nearest=args.distance_nearest)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
+                     exp_distance_nearest=args.distance_nearest, exp_plan_shortcut=args.plan_shortcut)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
     if args.vis3d:  # the reference's window (apps/EM-Fusion.cpp:118-131), or a viewer placed with look_at
         R3, t3, K3, size3 = pipeline.default_3d_view(prm)
         if args.vis3d_eye:

@@ -217,6 +217,8 @@ SIGNATURES = {
     "emf_hip_planCost": [_FP, _I3, _FP, C.c_int32, C.c_uint32, _FP, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, _FP, _FP,
                          _FP, _STREAM],
     "emf_hip_planPaths": [_FP, _I3, _FP, C.c_int32, C.c_int32, _FP, _FP, _FP, _STREAM],
+    "emf_hip_castVoxelRays": [_FP, _I3, _FP, C.c_int32, C.c_uint32, C.c_uint32, _FP, _FP, C.c_int32, _FP, C.c_int32, _FP,
+                              _STREAM],
 }
 
 
@@ -278,6 +280,12 @@ class EmfFrontierCluster(C.Structure):
 # the same record as a numpy structured dtype (what ops.frontier_clusters returns)
 FRONTIER_CLUSTER_DTYPE = [("label", "<i4"), ("count", "<i4"), ("lo", "<i4", 3), ("hi", "<i4", 3), ("sum", "<u8", 3),
                           ("rep", "<i4", 3), ("reserved", "<i4")]
+# include/emf_hip.h "Voxel rays": emf_ray_result_t (24 bytes) and emf_ray_group_t (32 bytes)
+RAY_RESULT_DTYPE = [("stop", "<i4"), ("steps", "<i4"), ("counted", "<u4"), ("status", "<u4"), ("weighted", "<u8")]
+RAY_GROUP_DTYPE = [("counted", "<u8"), ("weighted", "<u8"), ("reached", "<u4"), ("blocked", "<u4"), ("left", "<u4"),
+                   ("invalid", "<u4")]
+RAY_MAX_DELTA = 4095
+RAY_REACHED, RAY_BLOCKED, RAY_LEFT, RAY_OUTSIDE, RAY_INVALID = 0, 1, 2, 3, 4
 FRONTIER_KEPT, FRONTIER_CLUSTERS, FRONTIER_VOXELS = 0, 1, 2
 # include/emf_hip.h "Planning"
 PLAN_UNREACHED, PLAN_BLOCKED = 0xffffffff, 0xfffffffe

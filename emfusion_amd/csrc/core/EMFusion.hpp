@@ -438,6 +438,7 @@ public:
             int32_t length = 0;                  // voxels of the whole path, the goal first (0: none)
             int32_t faces = 0, edges = 0, corners = 0;  // its steps by kind (of the whole path where it was kept whole)
             std::vector<int32_t> path;           // linear indices of the box, at most pathCapacity of them
+            std::vector<int32_t> waypoints;      // shortcutPlan: ascending indices into path, from 0 to its last one
         };
         std::vector<Goal> goals;
         const uint8_t* classes = nullptr;  // device, box (z, y, x) order: EMF_OCC_*
@@ -469,6 +470,60 @@ public:
         planThroughUnknown_ = throughUnknown;
     }
     void writePlan(const std::string& dir);
+    /** writePlan also runs shortcutPlan(window) and adds one "waypoints" line per reachable goal; 0: plan.txt as before. */
+    void setPlanShortcutOutput(int window) { planShortcutWindow_ = window; }
+    /** What the last castRays() / viewGain() computed, on the host. */
+    struct Rays {
+        QueryBox box;
+        int clearanceVoxels = 0, group = 0;
+        uint32_t passMask = 0, countMask = 0;
+        std::vector<int32_t> from, to;            // 3 per ray, box coordinates
+        std::vector<emf_ray_result_t> results;    // one per ray, empty when not asked for
+        std::vector<emf_ray_group_t> groups;      // ceil(n / group) with group > 0
+        std::vector<int32_t> origins;             // viewGain: 3 per view, the voxel under each camera
+        int gridW = 0, gridH = 0;                 // viewGain: the grid
+    };
+    /**
+     * Voxel rays over the scene (include/emf_hip.h "Voxel rays"): n rays from[k] -> to[k] (3 * n i32 each,
+     * box coordinates, used as they are) over the box [boxLo, boxLo + boxSize) of the background, on the occupancy
+     * classes exactly as frontiers() forms them (every live object not in excludeIds stamped as occupied).  Each ray is
+     * the integer walk of the header -- NOT symmetric in its ends -- and ends at the first voxel whose class is not in
+     * passMask or, with clearanceVoxels > 0, that is nearer than that to an occupied voxel of the box (the capped
+     * transform, as frontiers()).  countMask: the classes counted along the way.  group > 0: one record of sums per run
+     * of `group` consecutive rays; wantResults false (with group > 0): the per-ray records are neither written nor
+     * copied.  Uploads the rays, launches once, copies the records back and waits once.  Changes nothing of the session
+     * -- the last distance field, frontiers and plan included -- and nothing goes into a checkpoint.  Refused (EMF_E_ARG)
+     * on the sharded path.
+     */
+    const Rays& castRays(const Vec3i& boxLo, const Vec3i& boxSize, const int32_t* from, const int32_t* to, int n, uint32_t passMask,
+                         uint32_t countMask, int clearanceVoxels, const std::vector<int>& excludeIds, int group,
+                         bool wantResults = true);
+    const Rays& lastRays() const { return ryLast; }
+    /** A candidate view: viewer -> world, OpenCV camera (as renderView), in double. */
+    struct ViewPose {
+        double R[9];
+        double t[3];
+    };
+    /**
+     * The unknown space each candidate view would see: per view the rays of a gw x gh grid image with intrinsics K =
+     * (fx, fy, cx, cy), range metres long (viewRayTargets), cast in ONE castRays with passMask = FREE | UNKNOWN and
+     * countMask = UNKNOWN -- a ray sees through unknown space and stops at the first occupied voxel -- and group =
+     * gw * gh: one group record per view.  A count over rays is a score, not a volume.  The per-ray records only with
+     * wantResults.  A camera outside the box yields OUTSIDE rays: groups[v].invalid == gw * gh and zero counts.
+     */
+    const Rays& viewGain(const std::vector<ViewPose>& views, int gw, int gh, const double K[4], double range, const Vec3i& boxLo,
+                         const Vec3i& boxSize, const std::vector<int>& excludeIds, bool wantResults = false);
+    /**
+     * Shortcuts of the last plan()'s paths: for every goal with a kept path p_0 .. p_k (goal first) the rays p_i -> p_j
+     * for all i and 2 <= j - i <= window, clipped at k, over the plan's own classes with its traverse mask and clearance
+     * gate (no bubble), in one launch for all goals; then greedily on the host from i the largest such j whose ray is
+     * REACHED, else i + 1 -- a step of the planner's own path is accepted untested (a face walk may clip a corner a
+     * diagonal move may cut, and inside the start bubble the gate does not hold).  Fills Goal::waypoints, the ascending
+     * path indices from 0 to k, of the last plan and returns it.  EMF_E_ARG without a plan or with window < 1.
+     */
+    const Plan& shortcutPlan(int window);
+    /** The window of the last shortcutPlan() on the last plan; 0: none since that plan. */
+    int lastShortcutWindow() const { return plShortcutWindow; }
     /** Ids returned by initNewObjVolume for FrameInputs::newObjectMasks of the last frame (-1: none). */
     const std::vector<int>& lastCreatedObjects() const { return lastCreated; }
     Affine3f getCameraPose() const { return pose; }
@@ -797,6 +852,9 @@ private:
     // into clearanceD2, which both callers consume on the main stream before they return: no result points into it
     Clearance enqueueClearance(const char* who, const QueryBox& box, const uint8_t* classes, int clearanceVoxels);
     DeviceBuffer clearanceD2;
+    void castOnDevice(const char* who, const QueryBox& box, const uint8_t* classes, const Clearance& clear, uint32_t passMask,
+                      uint32_t countMask, const std::vector<int32_t>& from, const std::vector<int32_t>& to, int group, bool wantResults,
+                      std::vector<emf_ray_result_t>& results, std::vector<emf_ray_group_t>& groups);
     // ---- frontiers (frontiers; EMFusionFrontier.cpp): allocated at first use, never in a checkpoint ----
     Frontiers frLast;
     DeviceBuffer frClasses, frLabels, frCounters, frScratch, frRecords;
@@ -1002,6 +1060,41 @@ private:
     PinnedBuffer meshHost;         // EMF_MAX_MODELS emf_model_t, then the counts and bases read back
     PinnedBuffer meshStage;        // staging of the meshes' bytes (grown when needed)
     std::vector<Event> stamps;     // the frame timings' marks on `main`
+
+    // ---- voxel rays (castRays, viewGain, shortcutPlan; EMFusionRays.cpp): allocated at first use, never in a checkpoint.
+    // Behind everything else so that the members the frame path touches stay where they were; ~EMFusion has waited for
+    // the device before any member goes ----
+    Rays ryLast;
+    DeviceBuffer ryClasses, ryEnds, ryResults, ryGroups;
+    uint64_t clearanceSerial = 0;    // counts the transforms written into clearanceD2 (5.18a)
+    uint64_t plClearanceSerial = 0;  // ... and which of them is the gate of the last plan
+    int plShortcutWindow = 0;        // of the last shortcutPlan on the last plan, 0: none
+    int planShortcutWindow_ = 0;     // setPlanShortcutOutput
 };
+
+/**
+ * The integer ray targets of one candidate view, on the host, without a device.  (R, t): viewer ->
+ * world, OpenCV camera; fx, fy, cx, cy: the intrinsics of a gw x gh grid image; range in metres; then the background's
+ * pose, resolution and voxel size and the box origin.  origin: the box voxel under the camera, by the rounding of
+ * QueryBox::voxelAt; targets: 3 * gw * gh i32, cell (i, j) at j * gw + i.  Everything in float64, every line a single
+ * operation in this order:
+ *     x = (i - cx) / fx;  y = (j - cy) / fy
+ *     m = sqrt(x * x + y * y + 1.0)                  summed left to right
+ *     c = (x / m, y / m, 1.0 / m)
+ *     M = bgR^T * R                                  each element a three-term sum left to right, once per view
+ *     dir = M c                                      rows summed left to right
+ *     target = origin + rint(dir * (range / voxel))  ties to even
+ * A value outside the i32 range is clipped to it, one that is not finite becomes -1.  range / voxel above
+ * EMF_RAY_MAX_DELTA is EMF_E_ARG.
+ */
+void viewRayTargets(const double R[9], const double t[3], double fx, double fy, double cx, double cy, int gw, int gh, double range,
+                    const float bgR[9], const float bgT[3], const Vec3i& bgRes, float voxelSize, const Vec3i& boxLo,
+                    int32_t origin[3], int32_t* targets);
+
+/**
+ * The greedy choice of EMFusion::shortcutPlan over a path p_0 .. p_k: from i the largest j in i + 2 .. min(i + window, k)
+ * with reached[rowStart[i] + (j - i - 2)] set, else i + 1, until k.  The ascending indices from 0 to k; empty for k < 0.
+ */
+std::vector<int32_t> shortcutGreedy(int k, int window, const std::vector<uint8_t>& reached, const std::vector<size_t>& rowStart);
 
 }  // namespace emf

@@ -94,6 +94,7 @@ EMFusion::Clearance EMFusion::enqueueClearance(const char* who, const QueryBox& 
     const Clearance out{nullptr, cap * cap};  // 4095^2 is above every distance of a box: only "far" passes then
     if (clearanceVoxels <= 0) return out;
     clearanceD2.reserve(box.voxels() * sizeof(int32_t));
+    ++clearanceSerial;
     emfCheck(emf_hip_distanceTransform(classes, box.size.val, 1u << EMF_OCC_OCCUPIED, cap, clearanceD2.as<int32_t>(), nullptr, 0.f,
                                        main.abi()),
              (std::string("EMFusion::") + who + " (clearance)").c_str());

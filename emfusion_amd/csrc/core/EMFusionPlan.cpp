@@ -36,6 +36,7 @@ const EMFusion::Plan& EMFusion::plan(const Vec3i& boxLo, const Vec3i& boxSize, c
     if (goalVoxels.size() > 0x7fffffffull / 3) throw HipError("EMFusion::plan: too many goals", EMF_E_LIMIT);
     drainForQuery();
     plLast = Plan();  // its device arrays are about to be reused or freed: no last plan until this one is complete
+    plShortcutWindow = 0;
     const size_t nGoals = goalVoxels.size();
     plClasses.reserve(voxels);
     plCost.reserve(voxels * sizeof(uint32_t));
@@ -57,6 +58,7 @@ const EMFusion::Plan& EMFusion::plan(const Vec3i& boxLo, const Vec3i& boxSize, c
     uint32_t* counters = plCounters.as<uint32_t>();
     enqueueOccupancy("plan", box, excludeIds, classes, nullptr, nullptr);
     const Clearance clear = enqueueClearance("plan", box, classes, clearanceVoxels);
+    plClearanceSerial = clearanceSerial;
     const std::vector<int32_t> seeds = flat(startVoxels), goals = flat(goalVoxels);
     hipCheck(hipMemcpyAsync(plSeeds.data(), seeds.data(), seeds.size() * sizeof(int32_t), hipMemcpyHostToDevice, main.get()),
              "EMFusion::plan (seeds)");
@@ -136,7 +138,8 @@ Vec3i EMFusion::cameraVoxel() const {
 // count: voxels of the cluster, %d; reachable 0 / 1; cost %u (the chamfer cost; 4294967295 / 4294967294 where there is
 // no path); length_m = (faces + sqrt(2) edges + sqrt(3) corners) * voxel in double, %.9g; r: the representative in the
 // world frame as in frontiers.txt; then n_path lines "x y z", the path's voxels in the world frame from the goal to the
-// start, each the double value rounded once to float, %.9g.
+// start, each the double value rounded once to float, %.9g.  With setPlanShortcutOutput(W > 0) the path lines of a
+// reachable cluster are followed by one line "waypoints n i_0 .. i_(n-1)", shortcutPlan(W) of that path.
 void EMFusion::writePlan(const std::string& dir) {
     const Vec3i n = background.getVolumeRes();
     const float voxel = background.getVoxelSize();
@@ -144,7 +147,8 @@ void EMFusion::writePlan(const std::string& dir) {
     const Frontiers& f = frontiers(Vec3i(0, 0, 0), n, std::max(frontierMinVoxels_, 1), clearance, {});  // as writeFrontiers
     std::vector<Vec3i> goals;
     for (const emf_frontier_cluster_t& c : f.clusters) goals.push_back(Vec3i(c.rep[0], c.rep[1], c.rep[2]));
-    const Plan& p = plan(Vec3i(0, 0, 0), n, {cameraVoxel()}, std::max(clearance, 1), planThroughUnknown_, clearance, 0u, goals, -1, {});
+    plan(Vec3i(0, 0, 0), n, {cameraVoxel()}, std::max(clearance, 1), planThroughUnknown_, clearance, 0u, goals, -1, {});
+    const Plan& p = planShortcutWindow_ > 0 ? shortcutPlan(planShortcutWindow_) : lastPlan();
     const std::string path = dir + "/plan.txt";
     std::FILE* file = std::fopen(path.c_str(), "w");
     if (!file) throw std::runtime_error("EMFusion::writePlan: cannot create " + path);
@@ -163,6 +167,11 @@ void EMFusion::writePlan(const std::string& dir) {
             p.box.worldPoint(p.box.unravel(v), w);
             std::fprintf(file, "%.9g %.9g %.9g\n", static_cast<double>(static_cast<float>(w[0])),
                          static_cast<double>(static_cast<float>(w[1])), static_cast<double>(static_cast<float>(w[2])));
+        }
+        if (planShortcutWindow_ > 0 && g.length > 0) {  // "waypoints n i_0 .. i_(n-1)": indices into the path lines above
+            std::fprintf(file, "waypoints %d", static_cast<int>(g.waypoints.size()));
+            for (int32_t i : g.waypoints) std::fprintf(file, " %d", i);
+            std::fprintf(file, "\n");
         }
     }
     std::fclose(file);

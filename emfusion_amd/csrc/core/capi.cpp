@@ -829,6 +829,110 @@ int emf_fusion_set_plan_output(emf_fusion_t* h, int on, float clearance_metres, 
     return guarded([&] { h->impl->setPlanOutput(on != 0, clearance_metres, through_unknown != 0); });
 }
 
+int emf_fusion_cast_rays(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], const int32_t* from,
+                         const int32_t* to, int32_t n, uint32_t pass_mask, uint32_t count_mask, int32_t clearance_voxels,
+                         const int32_t* exclude_ids, int32_t num_exclude, int32_t group, emf_ray_result_t* results,
+                         emf_ray_group_t* groups, int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3]) {
+    REQ(h);
+    if (n < 0 || (n > 0 && (!from || !to)) || group < 0 || (group > 0) != (groups != nullptr) || (!results && !groups)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_cast_rays: %d rays in groups of %d without their lists or outputs", n, group);
+        return EMF_E_ARG;
+    }
+    QueryArgs a;
+    if (const int rc = queryArgs("emf_fusion_cast_rays", h, box_lo, box_size, exclude_ids, num_exclude, a)) return rc;
+    return guarded([&] {
+        const EMFusion::Rays& r = h->impl->castRays(a.lo, a.size, from, to, n, pass_mask, count_mask, clearance_voxels, a.exclude,
+                                                    group, results != nullptr);
+        putBox(r.box, lo_out, size_out, R, t);
+        if (results) std::copy(r.results.begin(), r.results.end(), results);
+        if (groups) std::copy(r.groups.begin(), r.groups.end(), groups);
+    });
+}
+
+int emf_fusion_view_ray_targets(const double R[9], const double t[3], const double K[4], int32_t gw, int32_t gh, double range,
+                                const float bg_R[9], const float bg_t[3], const int32_t res[3], float voxel_size,
+                                const int32_t box_lo[3], int32_t origin[3], int32_t* targets) {
+    REQ(R);
+    REQ(t);
+    REQ(K);
+    REQ(bg_R);
+    REQ(bg_t);
+    REQ(res);
+    REQ(box_lo);
+    REQ(origin);
+    return guarded([&] {
+        viewRayTargets(R, t, K[0], K[1], K[2], K[3], gw, gh, range, bg_R, bg_t, Vec3i(res[0], res[1], res[2]), voxel_size,
+                       Vec3i(box_lo[0], box_lo[1], box_lo[2]), origin, targets);
+    });
+}
+
+int emf_fusion_view_gain(emf_fusion_t* h, const double* views_R, const double* views_t, int32_t num_views, int32_t gw, int32_t gh,
+                         const double K[4], double range, const int32_t box_lo[3], const int32_t box_size[3],
+                         const int32_t* exclude_ids, int32_t num_exclude, emf_ray_group_t* groups, int32_t* origins,
+                         int32_t* targets, emf_ray_result_t* results, int32_t lo_out[3], int32_t size_out[3], float R[9],
+                         float t[3]) {
+    REQ(h);
+    REQ(K);
+    if (num_views < 0 || (num_views > 0 && (!views_R || !views_t || !groups))) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_view_gain: %d views without their poses or group records", num_views);
+        return EMF_E_ARG;
+    }
+    QueryArgs a;
+    if (const int rc = queryArgs("emf_fusion_view_gain", h, box_lo, box_size, exclude_ids, num_exclude, a)) return rc;
+    return guarded([&] {
+        std::vector<EMFusion::ViewPose> views(static_cast<size_t>(num_views));
+        for (int32_t v = 0; v < num_views; ++v) {
+            std::copy(views_R + 9 * v, views_R + 9 * v + 9, views[v].R);
+            std::copy(views_t + 3 * v, views_t + 3 * v + 3, views[v].t);
+        }
+        const EMFusion::Rays& r = h->impl->viewGain(views, gw, gh, K, range, a.lo, a.size, a.exclude, results != nullptr);
+        putBox(r.box, lo_out, size_out, R, t);
+        std::copy(r.groups.begin(), r.groups.end(), groups);
+        if (origins) std::copy(r.origins.begin(), r.origins.end(), origins);
+        if (targets) std::copy(r.to.begin(), r.to.end(), targets);
+        if (results) std::copy(r.results.begin(), r.results.end(), results);
+    });
+}
+
+int emf_fusion_plan_shortcut(emf_fusion_t* h, int32_t window, int32_t* counts, int32_t* longest) {
+    REQ(h);
+    return guarded([&] {
+        const EMFusion::Plan& p = h->impl->shortcutPlan(window);
+        if (longest) *longest = 0;
+        for (size_t g = 0; g < p.goals.size(); ++g) {
+            const int32_t n = p.goals[g].length > 0 ? static_cast<int32_t>(p.goals[g].waypoints.size()) : 0;
+            if (counts) counts[g] = n;
+            if (longest) *longest = std::max(*longest, n);
+        }
+    });
+}
+
+int emf_fusion_copy_plan_shortcut(emf_fusion_t* h, int32_t* waypoints, int32_t capacity) {
+    REQ(h);
+    if (capacity < 0 || (capacity > 0 && !waypoints)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_copy_plan_shortcut: capacity %d", capacity);
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const EMFusion::Plan& p = h->impl->lastPlan();
+        if (!p.cost || h->impl->lastShortcutWindow() < 1) throw HipError("emf_fusion_copy_plan_shortcut: no shortcuts have been computed", EMF_E_ARG);
+        for (size_t g = 0; g < p.goals.size(); ++g) {
+            if (p.goals[g].length <= 0) continue;
+            const std::vector<int32_t>& w = p.goals[g].waypoints;
+            std::copy(w.begin(), w.begin() + std::min<size_t>(w.size(), static_cast<size_t>(capacity)), waypoints + g * static_cast<size_t>(capacity));
+        }
+    });
+}
+
+int emf_fusion_set_plan_shortcut_output(emf_fusion_t* h, int32_t window) {
+    REQ(h);
+    if (window < 0) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_set_plan_shortcut_output: window %d", window);
+        return EMF_E_ARG;
+    }
+    return guarded([&] { h->impl->setPlanShortcutOutput(window); });
+}
+
 int emf_fusion_follow_shift(const float q[3], const int32_t step[3], float voxel_size, int32_t shift[3]) {
     REQ(q);
     REQ(step);

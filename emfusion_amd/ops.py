@@ -1853,3 +1853,57 @@ def plan(classes, seeds, goals, capacity=None, **kwargs):
     cost = plan_cost(classes, seeds, **kwargs)
     paths, lengths, goal_cost = plan_paths(cost, goals, capacity=capacity, stream=stream)
     return cost, paths, lengths, goal_cost
+
+
+# ---- voxel rays (include/emf_hip.h "Voxel rays") -------------------------------------------------
+
+RAY_MAX_DELTA = _lib.RAY_MAX_DELTA
+RAY_REACHED, RAY_BLOCKED, RAY_LEFT, RAY_OUTSIDE, RAY_INVALID = (_lib.RAY_REACHED, _lib.RAY_BLOCKED, _lib.RAY_LEFT,
+                                                                _lib.RAY_OUTSIDE, _lib.RAY_INVALID)
+RAY_RESULT_DTYPE = np.dtype(_lib.RAY_RESULT_DTYPE)
+RAY_GROUP_DTYPE = np.dtype(_lib.RAY_GROUP_DTYPE)
+assert RAY_RESULT_DTYPE.itemsize == 24 and RAY_GROUP_DTYPE.itemsize == 32
+
+
+def _ray_ends(points, what):
+    """(n, 3) voxels (x, y, z) as a device array of 3 * n i32: a device array goes through as it is."""
+    if isinstance(points, DeviceArray):
+        assert points.dtype == np.int32 and not points.padded and int(np.prod(points.shape)) % 3 == 0, what
+        return points, int(np.prod(points.shape)) // 3
+    v = np.ascontiguousarray(np.asarray(points, np.int32).reshape(-1, 3))
+    return DeviceArray.from_numpy(v.reshape(-1)), len(v)
+
+
+def cast_voxel_rays(classes, rays_from, rays_to, d2=None, min_d2=0, pass_mask=1, count_mask=0, group=0, out=None,
+                    stream=None):
+    """emf_hip_castVoxelRays over a (nz, ny, nx) u8 class volume: n rays from rays_from to rays_to -- (n, 3) lists of
+    (x, y, z) voxels, numpy or device i32 -- each an integer walk of |dx| + |dy| + |dz| face steps (the next step along
+    the axis with the smallest crossing parameter (2 i + 1) / (2 d), ties x before y before z; NOT symmetric in its
+    ends) that ends at the first voxel that is outside the volume, whose class bit is not in pass_mask or, with d2
+    (nz, ny, nx) i32 and min_d2 > 0, whose d2 < min_d2.  The origin is never tested.  Returns the records, a numpy
+    array of RAY_RESULT_DTYPE (stop: linear index of the blocking voxel or DF_NONE; steps; counted: passed voxels whose
+    class bit is in count_mask; status RAY_*; weighted: the sum of |v - origin|^2 over the counted voxels), and with
+    group > 0 the pair (records, groups): one RAY_GROUP_DTYPE record per run of `group` consecutive rays, the last one
+    may be short.  out: (results, groups) device arrays of at least n and ceil(n / group) records to write into, either
+    may be None (results None with groups: only the groups are computed); they are returned as they are."""
+    assert classes.dtype == np.uint8 and len(classes.shape) == 3 and not classes.padded
+    assert d2 is None or (d2.dtype == np.int32 and d2.shape == classes.shape and not d2.padded)
+    d_from, n = _ray_ends(rays_from, "cast_voxel_rays: rays_from")
+    d_to, n_to = _ray_ends(rays_to, "cast_voxel_rays: rays_to")
+    assert n == n_to, "cast_voxel_rays: as many origins as targets"
+    group = int(group)
+    n_groups = -(-n // group) if group > 0 else 0
+    if out is None:
+        results = DeviceArray((n,), RAY_RESULT_DTYPE)
+        groups = DeviceArray((n_groups,), RAY_GROUP_DTYPE) if group > 0 else None
+    else:
+        results, groups = out
+        assert results is None or (results.dtype == RAY_RESULT_DTYPE and results.shape[0] >= n)
+        assert groups is None or (groups.dtype == RAY_GROUP_DTYPE and groups.shape[0] >= n_groups)
+    check("emf_hip_castVoxelRays",
+          _L.emf_hip_castVoxelRays(_ptr(classes), _i3(classes.shape[::-1]), _ptr(d2), int(min_d2), int(pass_mask),
+                                   int(count_mask), _ptr(d_from), _ptr(d_to), n, _ptr(results), group, _ptr(groups),
+                                   _stream(stream)))
+    if out is not None:
+        return results, groups
+    return (results.numpy(), groups.numpy()) if group > 0 else results.numpy()

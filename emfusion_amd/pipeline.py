@@ -164,6 +164,15 @@ def load() -> C.CDLL:
         "emf_fusion_copy_plan": [vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
         "emf_fusion_plan_cost_ptr": [vp, C.POINTER(C.c_void_p)],
         "emf_fusion_set_plan_output": [vp, C.c_int, C.c_float, C.c_int],
+        "emf_fusion_cast_rays": [vp, ip, ip, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, ip, C.c_int32,
+                                 C.c_int32, C.c_void_p, C.c_void_p, ip, ip, fp, fp],
+        "emf_fusion_view_ray_targets": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, fp, fp, ip,
+                                        C.c_float, ip, ip, C.c_void_p],
+        "emf_fusion_view_gain": [vp, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_double, ip, ip, ip,
+                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, ip, ip, fp, fp],
+        "emf_fusion_plan_shortcut": [vp, C.c_int32, C.c_void_p, ip],
+        "emf_fusion_copy_plan_shortcut": [vp, C.c_void_p, C.c_int32],
+        "emf_fusion_set_plan_shortcut_output": [vp, C.c_int32],
         "emf_fusion_process_rgbd_color": [vp, fp, C.c_void_p, C.c_int32, C.c_int32],
         "emf_fusion_colored_voxels": [vp, C.POINTER(C.c_uint64)],
         "emf_fusion_get_last_masks": [vp, C.c_void_p, C.c_size_t, ip],
@@ -350,6 +359,22 @@ def look_at(eye, target, up=(0.0, -1.0, 0.0)):
 
 
 DEFAULT_3D_VIEW_SIZE = (1024, 768)
+
+
+def view_ray_targets(R, t, K, grid, range_m, bg_R, bg_t, res, voxel, lo=(0, 0, 0)):
+    """emf_fusion_view_ray_targets, on the host without a device: (origin (3,) i32, targets (gh, gw, 3)
+    i32) of the view (R, t) viewer -> world with the intrinsics K = (fx, fy, cx, cy) of a grid = (gw, gh) image and rays
+    of range_m metres, in the box at `lo` of a background of pose (bg_R, bg_t), resolution res and voxel size voxel."""
+    gw, gh = int(grid[0]), int(grid[1])
+    Rd, td = np.ascontiguousarray(R, np.float64).reshape(9), np.ascontiguousarray(t, np.float64).reshape(3)
+    Kd = np.ascontiguousarray(K, np.float64).reshape(4)
+    origin, targets = np.zeros(3, np.int32), np.zeros((gh, gw, 3), np.int32)
+    _check("emf_fusion_view_ray_targets",
+           load().emf_fusion_view_ray_targets(Rd.ctypes.data, td.ctypes.data, Kd.ctypes.data, gw, gh, float(range_m), _farr(bg_R, 9),
+                                              _farr(bg_t, 3), (C.c_int32 * 3)(*[int(v) for v in res]), float(voxel),
+                                              (C.c_int32 * 3)(*[int(v) for v in lo]),
+                                              origin.ctypes.data_as(C.POINTER(C.c_int32)), targets.ctypes.data))
+    return origin, targets
 
 
 def default_3d_view(params: FusionParams):
@@ -1016,8 +1041,119 @@ class Fusion:
             out["labels"] = volume
         return out
 
+    def cast_rays(self, origins, targets, box=None, size=None, clearance=0.0, through_unknown=False, count=("unknown",),
+                  exclude=(), group=0):
+        """Voxel rays over the scene: can I go, or look, straight from A to B.  Over a box of the
+        background as for frontiers -- None, ((x, y, z) lo, (x, y, z) size) or "camera" with `size` -- and on the same
+        occupancy classes (every live object not in `exclude` stamped as occupied): one ray per pair of origins[k],
+        targets[k], (n, 3) world points each rounded to its voxel and never moved to another one.  A ray is an integer
+        walk of |dx| + |dy| + |dz| face steps on the voxel lattice (include/emf_hip.h "Voxel rays") that ends at the
+        first voxel that is not free -- or neither free nor unknown, with through_unknown --, that leaves the box or,
+        with clearance (metres, rounded up to whole voxels), that is nearer than that to an occupied voxel of the box.
+        The origin voxel is never tested.  The walk is NOT symmetric: A -> B and B -> A may visit different voxels.
+        count: the classes counted along the way, of "free", "occupied", "unknown".  Returns a dict of arrays, one entry
+        per ray: from_voxel, to_voxel (n, 3) i32 box coordinates; status (RAY_*); visible = status == RAY_REACHED; steps,
+        the voxels entered and passed; stop_voxel (n, 3) i32, the blocking voxel, -1s where none; stop_world (n, 3) f32
+        (float64, rounded once), NaN where none; counted, the passed voxels of a counted class; weighted u64, the sum of
+        their squared voxel distances from the origin (a far voxel stands for more solid angle) -- scores, not volumes;
+        and box, box_pose, voxel_size, clearance_voxels.  group > 0: also groups, one RAY_GROUP_DTYPE record of sums per
+        run of `group` consecutive rays."""
+        from ._lib import RAY_GROUP_DTYPE, RAY_RESULT_DTYPE
+        box = self._resolve_box("cast_rays", box, size)
+        vs = float(self.params.bg_voxel_size)
+        names = {"free": 1, "occupied": 2, "unknown": 4}
+        count_mask = 0
+        for c in count:
+            if c not in names:
+                raise ValueError('cast_rays: count holds "free", "occupied" or "unknown"')
+            count_mask |= names[c]
+        clearance_voxels = _metres_to_voxels(clearance, vs)
+        frame = self._box_frame(box[0] if box is not None else (0, 0, 0))
+        a, b = frame.to_voxels(origins), frame.to_voxels(targets)
+        if len(a) != len(b):
+            raise ValueError("cast_rays: as many origins as targets")
+        n, group = len(a), int(group)
+        n_groups = -(-n // group) if group > 0 else 0
+        results = np.zeros(n, np.dtype(RAY_RESULT_DTYPE))
+        groups = np.zeros(n_groups, np.dtype(RAY_GROUP_DTYPE)) if group > 0 else None
+        lo_arg, size_arg, ex, n_ex = _box_args(box, exclude)
+        outs = _box_outs()
+        flat_a, flat_b = np.ascontiguousarray(a.reshape(-1)), np.ascontiguousarray(b.reshape(-1))
+        _check("emf_fusion_cast_rays",
+               load().emf_fusion_cast_rays(self._h, lo_arg, size_arg, flat_a.ctypes.data, flat_b.ctypes.data, n,
+                                           1 | (4 if through_unknown else 0), count_mask, clearance_voxels, ex, n_ex, group,
+                                           results.ctypes.data, groups.ctypes.data if group > 0 else None, *outs))
+        out_box, box_pose = _read_box_outs(*outs)
+        out = self._ray_records(frame, out_box[1], results)
+        out.update(from_voxel=a, to_voxel=b, box=out_box, box_pose=box_pose, voxel_size=vs, clearance_voxels=clearance_voxels)
+        if group > 0:
+            out["groups"] = groups
+        return out
+
+    @staticmethod
+    def _ray_records(frame, size, results):
+        """The per-ray entries of cast_rays / view_gain from the RAY_RESULT_DTYPE records of a box of `size`."""
+        from ._lib import RAY_REACHED
+        has = results["stop"] >= 0
+        site = frame.unravel(np.where(has, results["stop"], 0), size)
+        return dict(status=results["status"].copy(), visible=results["status"] == RAY_REACHED, steps=results["steps"].copy(),
+                    stop_voxel=np.where(has[:, None], site, -1).astype(np.int32),
+                    stop_world=np.where(has[:, None], frame.world(site), np.nan).astype(np.float32),
+                    counted=results["counted"].copy(), weighted=results["weighted"].copy())
+
+    def view_gain(self, views, grid=(32, 24), K=None, range_m=3.0, box=None, size=None, exclude=(), rays=False):
+        """View scoring: which candidate pose would see the most unknown space.  views: a list of (R, t),
+        viewer -> world in the OpenCV camera convention (as render_view / look_at).  Per view the rays of a grid = (gw, gh)
+        image with the intrinsics K (3 x 3; None: the frame's, scaled to the grid as default_3d_view scales them), range_m
+        metres long, from the voxel under the camera to integer targets computed on the host in float64
+        (view_ray_targets); all views in one launch over a box of the background as for cast_rays.  A ray sees through
+        free and unknown space and stops at the first occupied voxel; the unknown voxels it passes are counted.  The
+        counts are SCORES, not volumes: rays share voxels near the origin, and a diagonal ray enters up to sqrt(3) times
+        more voxels per metre than an axis-parallel one.  Returns a dict of arrays, one entry per view: origin_voxel
+        (n, 3) i32; inside: the camera stands in the box (else zero counts); unknown, the unknown voxels passed; weighted
+        u64, each weighted by its squared voxel distance from the camera; reached, blocked, left: rays by how they ended;
+        and order: the views' indices by weighted, descending, ties to the lower index; box, box_pose, voxel_size.
+        rays=True: also targets (n, gh, gw, 3) i32 and rays, the per-ray entries of cast_rays as (n * gh * gw,) arrays."""
+        from ._lib import RAY_GROUP_DTYPE, RAY_RESULT_DTYPE
+        box = self._resolve_box("view_gain", box, size)
+        vs = float(self.params.bg_voxel_size)
+        gw, gh = int(grid[0]), int(grid[1])
+        if K is None:
+            K = np.array(self.params.K, np.float32).reshape(3, 3)
+            sx, sy = np.float32(gw / self.params.width), np.float32(gh / self.params.height)
+            K[0, 0] *= sx
+            K[0, 2] *= sx
+            K[1, 1] *= sy
+            K[1, 2] *= sy
+        K = np.asarray(K, np.float64).reshape(3, 3)
+        k4 = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]], np.float64)
+        n = len(views)
+        Rs = np.ascontiguousarray(np.array([np.asarray(v[0], np.float64).reshape(9) for v in views], np.float64).reshape(n, 9))
+        ts = np.ascontiguousarray(np.array([np.asarray(v[1], np.float64).reshape(3) for v in views], np.float64).reshape(n, 3))
+        groups = np.zeros(n, np.dtype(RAY_GROUP_DTYPE))
+        origins = np.zeros((n, 3), np.int32)
+        targets = np.zeros((n, gh, gw, 3), np.int32) if rays else None
+        results = np.zeros(n * gh * gw, np.dtype(RAY_RESULT_DTYPE)) if rays else None
+        lo_arg, size_arg, ex, n_ex = _box_args(box, exclude)
+        outs = _box_outs()
+        _check("emf_fusion_view_gain",
+               load().emf_fusion_view_gain(self._h, Rs.ctypes.data, ts.ctypes.data, n, gw, gh, k4.ctypes.data, float(range_m),
+                                           lo_arg, size_arg, ex, n_ex, groups.ctypes.data, origins.ctypes.data,
+                                           targets.ctypes.data if rays else None, results.ctypes.data if rays else None, *outs))
+        out_box, box_pose = _read_box_outs(*outs)
+        inside = ((origins >= 0) & (origins < np.array(out_box[1], np.int64))).all(axis=1)
+        weighted = groups["weighted"].copy()
+        order = np.array(sorted(range(n), key=lambda v: (-int(weighted[v]), v)), np.int64)
+        out = dict(origin_voxel=origins, inside=inside, unknown=groups["counted"].copy(), weighted=weighted,
+                   reached=groups["reached"].copy(), blocked=groups["blocked"].copy(), left=groups["left"].copy(), order=order,
+                   groups=groups, box=out_box, box_pose=box_pose, voxel_size=vs, K=k4)
+        if rays:
+            frame = self._box_frame(out_box[0])
+            out.update(targets=targets, rays=self._ray_records(frame, out_box[1], results), records=results)
+        return out
+
     def plan(self, goals="frontiers", start=None, box=None, size=None, clearance=0.0, start_radius=None,
-             through_unknown=False, max_cost=0.0, exclude=(), min_voxels=8, field=False):
+             through_unknown=False, max_cost=0.0, exclude=(), min_voxels=8, field=False, shortcut=0):
         """Path planning over the scene: can the robot get there, by which way, at what cost.  Over a
         box of the background as for frontiers -- None, ((x, y, z) lo, (x, y, z) size) or "camera" with `size` -- and on
         the same occupancy classes (every live object not in `exclude` stamped as occupied): the cost-to-go field from
@@ -1038,7 +1174,12 @@ class Fusion:
           reachable clusters come first, cheapest first, then the rest in the frontier order; `clusters` is the same list;
           start_voxels (box coordinates), start_radius_voxels, clearance_voxels; box (lo, size); box_pose; voxel_size;
           converged, rounds, n_finite, n_starts: the counters; frontiers: what frontiers() returned (with "frontiers");
-          cost (bz, by, bx) u32 with field=True."""
+          cost (bz, by, bx) u32 with field=True.
+        shortcut=W > 0: every goal also gains waypoints -- ascending indices into its path, from 0 to the
+        last one: from index i the farthest of the next W path voxels that a voxel ray from path[i] reaches through the
+        plan's own traversable voxels (its classes and clearance, without the start bubble), else i + 1 --,
+        waypoints_vox, waypoints_world and waypoints_length_m, the sum of the Euclidean voxel distances between
+        consecutive waypoints times the voxel size, in float64.  The default 0 changes nothing and makes no new call."""
         from ._lib import PLAN_BLOCKED
         box = self._resolve_box("plan", box, size)
         vs = float(self.params.bg_voxel_size)
@@ -1089,6 +1230,17 @@ class Fusion:
                      length_m=(f + np.sqrt(2.0) * e + np.sqrt(3.0) * c) * np.float64(vs), steps=(f, e, c), path_vox=vox,
                      path_world=frame.world(vox))
             records.append(r)
+        if shortcut > 0:
+            counts, most = np.zeros(max(n_goals, 1), np.int32), C.c_int32(0)
+            _check("emf_fusion_plan_shortcut", load().emf_fusion_plan_shortcut(self._h, int(shortcut), counts.ctypes.data, C.byref(most)))
+            ways = np.full((max(n_goals, 1), max(int(most.value), 1)), -1, np.int32)
+            _check("emf_fusion_copy_plan_shortcut", load().emf_fusion_copy_plan_shortcut(self._h, ways.ctypes.data, ways.shape[1]))
+            for g, r in enumerate(records):
+                w = ways[g, :int(counts[g])].copy()
+                vox = r["path_vox"][w]
+                hops = np.diff(vox.astype(np.float64), axis=0)
+                r.update(waypoints=w, waypoints_vox=vox, waypoints_world=r["path_world"][w],
+                         waypoints_length_m=np.sqrt((hops * hops).sum(axis=1)).sum() * np.float64(vs))
         if found is not None:  # reachable first, cheapest first (stable: ties and the rest keep the frontier order)
             records = sorted(records, key=lambda r: (not r["reachable"], r["cost"] if r["reachable"] else 0))
         out_box, box_pose = _read_box_outs(*outs)
@@ -1298,7 +1450,7 @@ class Fusion:
     def setup_output(self, exp_frame_meshes=False, exp_vols=False, exp_world_mesh=False, exp_distance_field=False,
                      distance_cap=0.0, distance_unknown_is_obstacle=False, exp_frontiers=False, frontier_min_voxels=8,
                      frontier_clearance=0.0, exp_plan=False, plan_clearance=0.0, plan_through_unknown=False,
-                     exp_distance_nearest=False):
+                     exp_distance_nearest=False, exp_plan_shortcut=0):
         """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
         the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
         the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh();
@@ -1310,7 +1462,11 @@ class Fusion:
         frontier cluster of at least frontier_min_voxels voxels at plan_clearance metres
         (include/emf_fusion.h emf_fusion_set_plan_output);
         exp_distance_nearest (needs exp_distance_field): write_results also writes nearest.bin, i32 in the container of
-        distance.bin: the linear index of the nearest obstacle voxel of the background, -1 where there is none."""
+        distance.bin: the linear index of the nearest obstacle voxel of the background, -1 where there is none;
+        exp_plan_shortcut=W > 0 (needs exp_plan): plan.txt carries one extra "waypoints n i_0 .. i_(n-1)" line per
+        reachable goal, plan(shortcut=W) of its path (include/emf_fusion.h emf_fusion_set_plan_shortcut_output)."""
+        if exp_plan_shortcut and not exp_plan:
+            raise ValueError("setup_output: exp_plan_shortcut adds lines to plan.txt and needs exp_plan")
         if exp_distance_nearest and not exp_distance_field:
             raise ValueError("setup_output: exp_distance_nearest writes nearest.bin beside distance.bin and needs exp_distance_field")
         _check("emf_fusion_setup_output",
@@ -1328,6 +1484,9 @@ class Fusion:
         _check("emf_fusion_set_plan_output",
                load().emf_fusion_set_plan_output(self._h, int(bool(exp_plan)), float(plan_clearance),
                                                  int(bool(plan_through_unknown))))
+        if exp_plan_shortcut:  # off: no new call
+            _check("emf_fusion_set_plan_shortcut_output",
+                   load().emf_fusion_set_plan_shortcut_output(self._h, int(exp_plan_shortcut)))
 
     def write_results(self, directory: str, volumes: bool = True):
         """poses-*.txt, mesh_bg.ply, mesh_<id>.ply always; tsdfs/*.bin with `volumes` (reference formats)."""

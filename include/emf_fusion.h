@@ -343,6 +343,60 @@ int emf_fusion_plan_cost_ptr(emf_fusion_t* h, const uint32_t** cost_dev);
  * followed by n_path lines x y z: the path's voxels in the world frame, from the goal to the start (%.9g each).
  * clearance_metres is rounded up to whole voxels.  Off: no output byte changes. */
 int emf_fusion_set_plan_output(emf_fusion_t* h, int on, float clearance_metres, int through_unknown);
+/* Voxel rays over the scene (include/emf_hip.h "Voxel rays"; new behaviour, nothing of the session
+ * changes -- the last distance field, frontiers and plan included -- and nothing goes into a checkpoint).  Over the box of
+ * the background as for emf_fusion_frontiers, on the same occupancy classes (every live object whose id is not in
+ * exclude_ids stamped as occupied): n rays from[k] -> to[k], 3 * n i32 each in BOX coordinates, used as they are.  A ray
+ * is the integer walk of the header -- it is NOT symmetric in its two ends -- and ends at the first voxel that is
+ * outside the box, whose class bit is not in pass_mask or, with clearance_voxels > 0, that is nearer than that to an
+ * occupied voxel of the box; count_mask: the classes counted on the way.  results (n records, or NULL) and groups
+ * (ceil(n / group) records with group > 0, else NULL): at least one of the two.  Uploads the rays, launches once, copies
+ * the records back and waits once.  lo_out / size_out / R / t (may be NULL): as emf_fusion_frontiers.  EMF_E_ARG on a
+ * sharded session ("not supported on the sharded path"). */
+int emf_fusion_cast_rays(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], const int32_t* from,
+                         const int32_t* to, int32_t n, uint32_t pass_mask, uint32_t count_mask, int32_t clearance_voxels,
+                         const int32_t* exclude_ids, int32_t num_exclude, int32_t group, emf_ray_result_t* results,
+                         emf_ray_group_t* groups, int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3]);
+/* The integer ray targets of one candidate view; needs no handle and no device.  (R, t): viewer -> world, OpenCV camera
+ * (as emf_fusion_render_view), row-major, in double; K = (fx, fy, cx, cy) of a gw x gh grid image; range in metres; the
+ * background's pose (bg_R, bg_t), resolution and voxel size, and the box origin.  origin: the box voxel under the
+ * camera, rint(bg_R^T (t - bg_t) / voxel + (res - 1) / 2) - box_lo; targets: 3 * gw * gh i32, cell (i, j) at j * gw + i.
+ * Everything in float64, every line a single operation in this order:
+ *     x = (i - cx) / fx;  y = (j - cy) / fy
+ *     m = sqrt(x * x + y * y + 1.0)                  summed left to right
+ *     c = (x / m, y / m, 1.0 / m)
+ *     M = bg_R^T * R                                 each element a three-term sum left to right, once per view
+ *     dir = M c                                      rows summed left to right
+ *     target = origin + rint(dir * (range / voxel))  ties to even
+ * range / voxel above EMF_RAY_MAX_DELTA is EMF_E_ARG. */
+int emf_fusion_view_ray_targets(const double R[9], const double t[3], const double K[4], int32_t gw, int32_t gh, double range,
+                                const float bg_R[9], const float bg_t[3], const int32_t res[3], float voxel_size,
+                                const int32_t box_lo[3], int32_t origin[3], int32_t* targets);
+/* The unknown space each of num_views candidate views would see (views_R: 9 doubles per view, views_t: 3): the targets
+ * of all views by emf_fusion_view_ray_targets, then ONE emf_fusion_cast_rays from each view's origin voxel with pass_mask
+ * = FREE | UNKNOWN and count_mask = UNKNOWN -- a ray sees through unknown space and stops at the first occupied voxel --
+ * and group = gw * gh.  groups: num_views records, one per view (a camera outside the box: invalid == gw * gh, zero
+ * counts).  Optional copy-outs, each may be NULL: origins (3 i32 per view), targets (3 * gw * gh i32 per view), results
+ * (gw * gh records per view; only then are the per-ray records written and copied).  A count over rays is a score, not a
+ * volume.  EMF_E_ARG on a sharded session. */
+int emf_fusion_view_gain(emf_fusion_t* h, const double* views_R, const double* views_t, int32_t num_views, int32_t gw, int32_t gh,
+                         const double K[4], double range, const int32_t box_lo[3], const int32_t box_size[3],
+                         const int32_t* exclude_ids, int32_t num_exclude, emf_ray_group_t* groups, int32_t* origins,
+                         int32_t* targets, emf_ray_result_t* results, int32_t lo_out[3], int32_t size_out[3], float R[9],
+                         float t[3]);
+/* Shortcuts of the last plan's paths: for every goal with a kept path p_0 .. p_k (goal first) the rays p_i -> p_j, 2 <=
+ * j - i <= window clipped at k, over the plan's own classes, traverse mask and clearance gate (no bubble) in one launch;
+ * then greedily from i the largest such j whose ray is REACHED, else i + 1 (a step of the planner's own path is accepted
+ * untested).  counts (may be NULL): per goal the number of waypoints, 0 for a goal without a path; longest (may be
+ * NULL): their maximum.  EMF_E_ARG without a plan, with window < 1 and on a sharded session. */
+int emf_fusion_plan_shortcut(emf_fusion_t* h, int32_t window, int32_t* counts, int32_t* longest);
+/* The waypoints of the last emf_fusion_plan_shortcut: capacity i32 per goal, the ascending indices into the goal's path
+ * from 0 to k, untouched beyond the goal's count. */
+int emf_fusion_copy_plan_shortcut(emf_fusion_t* h, int32_t* waypoints, int32_t capacity);
+/* setup_output's exp_plan_shortcut, as an entry of its own: with window > 0 plan.txt (emf_fusion_set_plan_output) gains,
+ * after the path lines of every reachable goal, one line "waypoints n i_0 .. i_(n-1)": emf_fusion_plan_shortcut(window)
+ * of that goal's path.  0: plan.txt as before, byte for byte. */
+int emf_fusion_set_plan_shortcut_output(emf_fusion_t* h, int32_t window);
 /* Remember what rolls out (new behaviour, off by default; with it off no launch, no output byte and no
  * checkpoint byte changes).  With the store on, the whole integration tiles (32 x 8 x 8) that a roll moves out of the
  * background go to host memory as the bytes they are, after the slabs are retired; the tiles that a later roll moves

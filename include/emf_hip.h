@@ -1749,6 +1749,69 @@ int emf_hip_planCost(const uint8_t* classes, const int32_t size[3], const int32_
 int emf_hip_planPaths(const uint32_t* cost, const int32_t size[3], const int32_t* goals, int32_t n_goals, int32_t capacity,
                       int32_t* paths, int32_t* lengths, uint32_t* goal_cost, emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Voxel rays (new behaviour: DESIGN.md 5.22).  Opt-in; nothing above is touched.  "Can I go, or look, straight from a
+ * to b, and what would I pass on the way": a straight walk through a box of class bytes of shape size = (nx, ny, nz)
+ * that stops at the first voxel that blocks.  Arrays are dense, (z, y, x) order, x fastest; what lies outside the box
+ * does not exist.  The ray is an INTEGER walk on the voxel lattice, not a floating-point march.
+ *   the walk     a ray goes from voxel a to voxel b (x, y, z, i32).  d_k = |b_k - a_k|, s_k = sign(b_k - a_k) per axis.
+ *                It makes exactly n = d_x + d_y + d_z face steps v_1 .. v_n, v_n = b.  With i_k the steps already made
+ *                along axis k, the next step goes along the axis that still has steps left (i_k < d_k) and has the
+ *                smallest crossing parameter (2 i_k + 1) / (2 d_k), compared by cross-multiplication in integers,
+ *                (2 i_p + 1) * d_q < (2 i_q + 1) * d_p; TIES GO TO THE LOWER AXIS INDEX, x before y before z.  These
+ *                are the voxels the centre-to-centre segment passes through, with a fixed rule where it passes
+ *                exactly through an edge or a corner; sorting all crossings by (parameter as a fraction, axis) gives
+ *                the same sequence.  The walk is NOT symmetric: a -> b and b -> a visit different voxel sets for most
+ *                rays (integer segments hit edges often, and the tie rule is stated per axis, not per direction).
+ *   limits       d_k <= EMF_RAY_MAX_DELTA on every axis: the products stay below 2^26 and no ray takes more than
+ *                3 * EMF_RAY_MAX_DELTA steps.
+ *   what stops   a itself is never tested and never counted: the robot or sensor stands there.  A voxel v PASSES if it
+ *                lies in the box, (1u << class[v]) & pass_mask is non-zero (the bit convention of site_mask and
+ *                traverse_mask; a class byte above 2 is in no mask and blocks) and, where a d2 array is passed with
+ *                min_d2 > 0, d2[v] >= min_d2 (EMF_DF_FAR passes): the clearance gate of the frontiers and the plan.
+ *                The first voxel that does not pass ends the ray.
+ *   per ray      emf_ray_result_t.  status: EMF_RAY_REACHED (steps == n; a == b is REACHED with 0 steps),
+ *                EMF_RAY_BLOCKED (stop is the blocking voxel), EMF_RAY_LEFT (stepped out of the box), EMF_RAY_OUTSIDE
+ *                (a is not in the box, nothing walked; tested first), EMF_RAY_INVALID (a d_k above the limit, nothing
+ *                walked).  weighted gives a far voxel the weight of the solid angle it stands for, so that rays that
+ *                share their first voxels do not dominate a sum.
+ *   per group    with group > 0 every run of group consecutive rays is one group, the last one may be short:
+ *                ceil(n / group) records emf_ray_group_t, the integer sums over the group's rays; invalid counts the
+ *                OUTSIDE and the INVALID rays.  Integer sums: no dependence on the order of waves or workgroups.
+ * Limits of the box as for the distance field: every axis in 1 .. EMF_DF_MAX_AXIS, at most 2^31 - 1 voxels
+ * (EMF_E_LIMIT above).  Every rejected argument -- a NULL pointer, a mask above 7, a negative n or group, group > 0
+ * without groups or the reverse, neither results nor groups -- returns EMF_E_ARG or EMF_E_LIMIT with nothing enqueued.
+ * Integer arithmetic only: every output is a pure function of the inputs, bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+#define EMF_RAY_MAX_DELTA 4095
+#define EMF_RAY_REACHED 0
+#define EMF_RAY_BLOCKED 1
+#define EMF_RAY_LEFT 2
+#define EMF_RAY_OUTSIDE 3
+#define EMF_RAY_INVALID 4
+
+typedef struct emf_ray_result {
+    int32_t stop;      /* linear index of the blocking voxel, EMF_DF_NONE if none */
+    int32_t steps;     /* voxels entered and passed */
+    uint32_t counted;  /* passed voxels whose class bit is in count_mask */
+    uint32_t status;   /* EMF_RAY_* */
+    uint64_t weighted; /* sum over the counted voxels of the integer |v - a|^2 */
+} emf_ray_result_t;    /* 24 bytes */
+
+typedef struct emf_ray_group {
+    uint64_t counted, weighted;               /* sums of the rays' fields */
+    uint32_t reached, blocked, left, invalid; /* rays by status; invalid: OUTSIDE + INVALID */
+} emf_ray_group_t;                            /* 32 bytes */
+
+/* classes: size[0] * [1] * [2] bytes, only read; d2: NULL or as many i32, only read; from, to: device, 3 * n i32
+ * each, only read; results: n records, or NULL when only the groups are wanted; groups: ceil(n / group) records with
+ * group > 0, NULL with group == 0 (zeroed by a memset on the stream, then one integer atomic per non-zero quantity and
+ * run of lanes).  pass_mask, count_mask in 0 .. 7.  n == 0 enqueues nothing.  One lane per ray, one loop bounded by
+ * 3 * EMF_RAY_MAX_DELTA; a voxel outside the box is never dereferenced.  Nothing allocates, copies to the host or waits. */
+int emf_hip_castVoxelRays(const uint8_t* classes, const int32_t size[3], const int32_t* d2, int32_t min_d2, uint32_t pass_mask,
+                          uint32_t count_mask, const int32_t* from, const int32_t* to, int32_t n, emf_ray_result_t* results,
+                          int32_t group, emf_ray_group_t* groups, emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
