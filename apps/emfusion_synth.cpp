@@ -7,7 +7,7 @@
 //                  [--weld-meshes] [--mesh-min-triangles N] [--mesh-largest-object] [--mesh-simplify CELL] [--world-mesh]
 //                  [--distance-field] [--distance-cap M] [--distance-unknown-obstacle] [--distance-nearest]
 //                  [--frontiers] [--frontier-min-voxels N] [--frontier-clearance M]
-//                  [--plan] [--plan-clearance M] [--plan-through-unknown] [--plan-shortcut W]
+//                  [--plan] [--plan-clearance M] [--plan-through-unknown] [--plan-shortcut W] [--object-shapes]
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
 //                  [--bg-res R] [--bg-voxel M] [--obj-res R] [--volumes] --out DIR
 //   emfusion_synth --dir BASE/ [--colordir colour] [--depthdir depth] [--intrinsics fx fy cx cy] ... --out DIR
@@ -119,6 +119,10 @@ static bool planOut = false, planThroughUnknown = false;
 static float planClearance = 0.f;
 // --plan-shortcut W (needs --plan): plan.txt also carries one "waypoints" line per reachable goal (EMFusion::shortcutPlan)
 static int planShortcut = 0;
+// --object-shapes (needs --out): writeResults also writes OUT/shapes.txt, one line per live object in id order: the
+// integer moments of its observed solid band (not its body), then its box in the world frame;
+// without it no output byte changes
+static bool objectShapesOut = false;
 static bool planShortcutGiven = false;
 // --motion-masks [--motion-band M] [--motion-min-pixels N] [--motion-max-masks N]: mask frames propose their own
 // instance masks from the depth in front of the background model (EMFusion::setMotionMasks) instead of reading them
@@ -227,6 +231,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     emf.setFrontierOutput(frontiersOut, frontierMinVoxels, frontierClearance);
     emf.setPlanOutput(planOut, planClearance, planThroughUnknown);
     if (planShortcut > 0) emf.setPlanShortcutOutput(planShortcut);
+    if (objectShapesOut) emf.setShapeOutput(true);
     set3dView(emf, params, view3d);
     std::vector<uint8_t> rendered(3 * params.frameSize.area());
     const auto t0 = std::chrono::steady_clock::now();
@@ -335,6 +340,7 @@ int main(int argc, char** argv) {
         else if (a == "--distance-cap" && i + 1 < argc) distanceCap = std::max(static_cast<float>(std::atof(argv[++i])), 0.f);
         else if (a == "--distance-unknown-obstacle") distanceUnknownObstacle = true;
         else if (a == "--distance-nearest") distanceNearest = true;
+        else if (a == "--object-shapes") objectShapesOut = true;
         else if (a == "--frontiers") frontiersOut = true;
         else if (a == "--frontier-min-voxels" && i + 1 < argc) frontierMinVoxels = std::max(std::atoi(argv[++i]), 1);
         else if (a == "--frontier-clearance" && i + 1 < argc) frontierClearance = std::max(static_cast<float>(std::atof(argv[++i])), 0.f);
@@ -461,6 +467,7 @@ int main(int argc, char** argv) {
         emf.setFrontierOutput(frontiersOut, frontierMinVoxels, frontierClearance);
         emf.setPlanOutput(planOut, planClearance, planThroughUnknown);
         if (planShortcut > 0) emf.setPlanShortcutOutput(planShortcut);
+        if (objectShapesOut) emf.setShapeOutput(true);
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);
 

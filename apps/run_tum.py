@@ -93,6 +93,9 @@ def main():
     ap.add_argument("--plan-shortcut", dest="plan_shortcut", type=int, default=0, metavar="W",
                     help="with --plan: plan.txt also carries one waypoints line per reachable goal, the path shortened by "
                          "lines of sight over at most W path voxels")
+    ap.add_argument("--object-shapes", dest="object_shapes", action="store_true",
+                    help="also write OUT/shapes.txt: one line per live object in id order, the integer moments of its "
+                         "observed solid band (not its body), then its box in the world frame")
     ap.add_argument("--weld-meshes", dest="weld_meshes", action="store_true",
                     help="weld every mesh written (mesh_*.ply of the live models, frame_meshes/) by grid edge on the "
                          "device: one vertex per edge instead of one per cube that touches it")
@@ -198,7 +201,8 @@ def main():
                      exp_frontiers=args.frontiers, frontier_min_voxels=max(args.frontier_min_voxels, 1),
                      frontier_clearance=max(args.frontier_clearance, 0.0), exp_plan=args.plan,
                      plan_clearance=max(args.plan_clearance, 0.0), plan_through_unknown=args.plan_through_unknown,
-                     exp_distance_nearest=args.distance_nearest, exp_plan_shortcut=args.plan_shortcut)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
+                     exp_distance_nearest=args.distance_nearest, exp_plan_shortcut=args.plan_shortcut,
+                     exp_object_shapes=args.object_shapes)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
     if args.vis3d:  # the reference's window (apps/EM-Fusion.cpp:118-131), or a viewer placed with look_at
         R3, t3, K3, size3 = pipeline.default_3d_view(prm)
         if args.vis3d_eye:

@@ -219,6 +219,8 @@ SIGNATURES = {
     "emf_hip_planPaths": [_FP, _I3, _FP, C.c_int32, C.c_int32, _FP, _FP, _FP, _STREAM],
     "emf_hip_castVoxelRays": [_FP, _I3, _FP, C.c_int32, C.c_uint32, C.c_uint32, _FP, _FP, C.c_int32, _FP, C.c_int32, _FP,
                               _STREAM],
+    "emf_hip_shapeMoments": [_FP, _I3, C.c_int32, C.c_int32, _FP, _STREAM],
+    "emf_hip_shapeExtents": [_FP, _I3, C.c_int32, C.c_int32, _FP, _FP, _STREAM],
 }
 
 
@@ -256,6 +258,25 @@ class EmfMeshTilesSource(C.Structure):
                 ("plane_stride", C.c_uint64)]
 
 
+class EmfShapeMoments(C.Structure):
+    """Mirror of emf_shape_moments_t (include/emf_hip.h "Object shapes"): 128 bytes, integers only."""
+
+    _fields_ = [("solid", C.c_uint64), ("observed", C.c_uint64), ("sum", C.c_uint64 * 3), ("sum2", C.c_uint64 * 6),
+                ("faces_free", C.c_uint64), ("faces_unknown", C.c_uint64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
+
+
+class EmfShapeAxes(C.Structure):
+    """Mirror of emf_shape_axes_t: three row vectors and a centre, f32, voxel coordinates (48 bytes)."""
+
+    _fields_ = [("A", C.c_float * 9), ("c", C.c_float * 3)]
+
+
+class EmfShapeExtents(C.Structure):
+    """Mirror of emf_shape_extents_t: minimum and maximum along the three axes (24 bytes)."""
+
+    _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+
 class EmfOccObject(C.Structure):
     """Mirror of emf_occ_object_t (include/emf_hip.h "Distance field"): 112 bytes."""
 
@@ -285,6 +306,18 @@ RAY_RESULT_DTYPE = [("stop", "<i4"), ("steps", "<i4"), ("counted", "<u4"), ("sta
 RAY_GROUP_DTYPE = [("counted", "<u8"), ("weighted", "<u8"), ("reached", "<u4"), ("blocked", "<u4"), ("left", "<u4"),
                    ("invalid", "<u4")]
 RAY_MAX_DELTA = 4095
+# include/emf_hip.h "Object shapes": emf_shape_moments_t (128 bytes), emf_shape_axes_t (48), emf_shape_extents_t (24),
+# emf_shape_frame_t (224) and emf_shape_box_t (584)
+SHAPE_MOMENTS_DTYPE = [("solid", "<u8"), ("observed", "<u8"), ("sum", "<u8", 3), ("sum2", "<u8", 6), ("faces_free", "<u8"),
+                       ("faces_unknown", "<u8"), ("lo", "<i4", 3), ("hi", "<i4", 3)]
+SHAPE_AXES_DTYPE = [("A", "<f4", 9), ("c", "<f4", 3)]
+SHAPE_EXTENTS_DTYPE = [("lo", "<f4", 3), ("hi", "<f4", 3)]
+SHAPE_FRAME_DTYPE = [("valid", "<i4"), ("reserved", "<i4"), ("centroid", "<f8", 3), ("covariance", "<f8", 6),
+                     ("eigenvalues", "<f8", 3), ("axes", "<f8", 9), ("f32", SHAPE_AXES_DTYPE)]
+SHAPE_BOX_DTYPE = [("center_vox", "<f8", 3), ("half_vox", "<f8", 3), ("completeness", "<f8"), ("center_obj", "<f8", 3),
+                   ("half_m", "<f8", 3), ("corners_obj", "<f8", 24), ("center_world", "<f8", 3), ("axes_world", "<f8", 9),
+                   ("corners_world", "<f8", 24)]
+SHAPE_JACOBI_SWEEPS = 8
 RAY_REACHED, RAY_BLOCKED, RAY_LEFT, RAY_OUTSIDE, RAY_INVALID = 0, 1, 2, 3, 4
 FRONTIER_KEPT, FRONTIER_CLUSTERS, FRONTIER_VOXELS = 0, 1, 2
 # include/emf_hip.h "Planning"

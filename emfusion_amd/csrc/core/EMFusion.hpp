@@ -524,6 +524,32 @@ public:
     const Plan& shortcutPlan(int window);
     /** The window of the last shortcutPlan() on the last plan; 0: none since that plan. */
     int lastShortcutWindow() const { return plShortcutWindow; }
+    /** One model of objectShapes(): the integer record, the frame from it, the extents along the frame and the box. */
+    struct ObjectShape {
+        int id = 0;
+        Vec3i res;
+        float voxelSize = 0.f;
+        Affine3f pose;                // volume -> world, as the call found it
+        emf_shape_moments_t moments;  // integers only
+        emf_shape_frame_t frame;      // valid == 0: no solid voxel; frame and box are zeros then
+        emf_shape_extents_t extents;
+        emf_shape_box_t box;
+    };
+    /**
+     * Object shapes (include/emf_hip.h "Object shapes"): where in its volume each asked model is, how
+     * large it is, how it is oriented and how much of its surface has been seen.  WHAT IS MEASURED IS THE OBSERVED SOLID
+     * BAND, NOT THE BODY: a TSDF observes a band around the surface, the interior has weight 0; no result of this call is
+     * a volume in cubic metres.  ids: live objects, in the order of the result; includeBackground puts slot 0 in front.
+     * Drains the frame as the other queries do, then one moments launch for all models and one wait, the frames on the
+     * host (shapeFrame), one extents launch and one more wait, the boxes on the host (shapeBox).  An id that does not
+     * exist is EMF_E_ARG; an object without a solid voxel is a record with frame.valid == 0.  Changes nothing of the
+     * session and nothing goes into a checkpoint.  Refused (EMF_E_ARG) on the sharded path.
+     */
+    const std::vector<ObjectShape>& objectShapes(const std::vector<int>& ids, bool includeBackground = false);
+    const std::vector<ObjectShape>& lastShapes() const { return shLast; }
+    /** writeResults also writes shapes.txt, one line per live object in id order (writeShapes); without it no output byte changes. */
+    void setShapeOutput(bool on) { expShapes_ = on; }
+    void writeShapes(const std::string& dir);
     /** Ids returned by initNewObjVolume for FrameInputs::newObjectMasks of the last frame (-1: none). */
     const std::vector<int>& lastCreatedObjects() const { return lastCreated; }
     Affine3f getCameraPose() const { return pose; }
@@ -1070,6 +1096,12 @@ private:
     uint64_t plClearanceSerial = 0;  // ... and which of them is the gate of the last plan
     int plShortcutWindow = 0;        // of the last shortcutPlan on the last plan, 0: none
     int planShortcutWindow_ = 0;     // setPlanShortcutOutput
+
+    // ---- object shapes (objectShapes; EMFusionShape.cpp): allocated at first use, never in a checkpoint; behind all
+    // existing members ----
+    std::vector<ObjectShape> shLast;
+    DeviceBuffer shScratch;          // the compact model table, the moments, the frames and the extents of one call
+    bool expShapes_ = false;         // setShapeOutput
 };
 
 /**
@@ -1096,5 +1128,20 @@ void viewRayTargets(const double R[9], const double t[3], double fx, double fy, 
  * with reached[rowStart[i] + (j - i - 2)] set, else i + 1, until k.  The ascending indices from 0 to k; empty for k < 0.
  */
 std::vector<int32_t> shortcutGreedy(int k, int window, const std::vector<uint8_t>& reached, const std::vector<size_t>& rowStart);
+
+/**
+ * The frame of a model from its integer moments, on the host, without a device: centroid, covariance,
+ * cyclic Jacobi with EMF_SHAPE_JACOBI_SWEEPS sweeps, axes sorted by eigenvalue and signed, rounded to f32 once for the
+ * extents pass.  Float64 in the operation order written out in include/emf_hip.h "Object shapes".  mom.solid == 0 sets
+ * valid = 0 and writes nothing else.
+ */
+void shapeFrame(const emf_shape_moments_t& mom, emf_shape_frame_t& out);
+/**
+ * The box of a model from its frame and its extents along that frame: centre and half extents in voxels, completeness,
+ * then metres in the model's own frame and the world frame through its pose (R, t: volume -> world).  Float64 in the
+ * order of the header.  For a frame with valid != 0.
+ */
+void shapeBox(const emf_shape_moments_t& mom, const emf_shape_frame_t& frame, const emf_shape_extents_t& ext, const int32_t res[3],
+              float voxelSize, const float R[9], const float t[3], emf_shape_box_t& out);
 
 }  // namespace emf

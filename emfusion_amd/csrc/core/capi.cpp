@@ -933,6 +933,61 @@ int emf_fusion_set_plan_shortcut_output(emf_fusion_t* h, int32_t window) {
     return guarded([&] { h->impl->setPlanShortcutOutput(window); });
 }
 
+int emf_fusion_object_shapes(emf_fusion_t* h, const int32_t* ids, int32_t n, int32_t include_background, int32_t* ids_out,
+                             int32_t* res_out, float* voxel_size_out, float* poses_out, emf_shape_moments_t* moments,
+                             emf_shape_frame_t* frames, emf_shape_extents_t* extents, emf_shape_box_t* boxes) {
+    REQ(h);
+    if (n < 0 || (n > 0 && !ids)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_object_shapes: %d ids without a list", n);
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const std::vector<EMFusion::ObjectShape>& shapes =
+            h->impl->objectShapes(std::vector<int>(ids, ids + n), include_background != 0);
+        for (size_t k = 0; k < shapes.size(); ++k) {
+            const EMFusion::ObjectShape& s = shapes[k];
+            if (ids_out) ids_out[k] = s.id;
+            if (res_out) std::copy(s.res.val, s.res.val + 3, res_out + 3 * k);
+            if (voxel_size_out) voxel_size_out[k] = s.voxelSize;
+            if (poses_out) {
+                std::copy(s.pose.rotation().val, s.pose.rotation().val + 9, poses_out + 12 * k);
+                std::copy(s.pose.translation().val, s.pose.translation().val + 3, poses_out + 12 * k + 9);
+            }
+            if (moments) moments[k] = s.moments;
+            if (frames) frames[k] = s.frame;
+            if (extents) extents[k] = s.extents;
+            if (boxes) boxes[k] = s.box;
+        }
+    });
+}
+
+int emf_fusion_shape_frame(const emf_shape_moments_t* moments, emf_shape_frame_t* frame) {
+    REQ(moments);
+    REQ(frame);
+    return guarded([&] { shapeFrame(*moments, *frame); });
+}
+
+int emf_fusion_shape_box(const emf_shape_moments_t* moments, const emf_shape_frame_t* frame, const emf_shape_extents_t* extents,
+                         const int32_t res[3], float voxel_size, const float R[9], const float t[3], emf_shape_box_t* box) {
+    REQ(moments);
+    REQ(frame);
+    REQ(extents);
+    REQ(res);
+    REQ(R);
+    REQ(t);
+    REQ(box);
+    if (!frame->valid) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_shape_box: a frame with valid == 0 has no box");
+        return EMF_E_ARG;
+    }
+    return guarded([&] { shapeBox(*moments, *frame, *extents, res, voxel_size, R, t, *box); });
+}
+
+int emf_fusion_set_shape_output(emf_fusion_t* h, int on) {
+    REQ(h);
+    return guarded([&] { h->impl->setShapeOutput(on != 0); });
+}
+
 int emf_fusion_follow_shift(const float q[3], const int32_t step[3], float voxel_size, int32_t shift[3]) {
     REQ(q);
     REQ(step);

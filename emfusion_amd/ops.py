@@ -1907,3 +1907,71 @@ def cast_voxel_rays(classes, rays_from, rays_to, d2=None, min_d2=0, pass_mask=1,
     if out is not None:
         return results, groups
     return (results.numpy(), groups.numpy()) if group > 0 else results.numpy()
+
+
+# ---- object shapes (include/emf_hip.h "Object shapes") -------------------------------------------
+
+SHAPE_MOMENTS_DTYPE = np.dtype(_lib.SHAPE_MOMENTS_DTYPE)
+SHAPE_AXES_DTYPE = np.dtype(_lib.SHAPE_AXES_DTYPE)
+SHAPE_EXTENTS_DTYPE = np.dtype(_lib.SHAPE_EXTENTS_DTYPE)
+assert SHAPE_MOMENTS_DTYPE.itemsize == C.sizeof(_lib.EmfShapeMoments) == 128
+assert SHAPE_AXES_DTYPE.itemsize == C.sizeof(_lib.EmfShapeAxes) == 48
+assert SHAPE_EXTENTS_DTYPE.itemsize == C.sizeof(_lib.EmfShapeExtents) == 24
+
+
+def shape_table(volumes, first=0):
+    """The device model table of shape_moments / shape_extents -- only what they read: tsdf, weights, fg_mask,
+    unseen_tiles (optional, as rebuild_unseen_tiles leaves it) and the resolution -- with `first` empty slots in front,
+    and the host resolutions of the volumes."""
+    n = len(volumes)
+    models = [_lib.EmfModel() for _ in range(first)]
+    res = (C.c_int32 * (3 * max(n, 1)))()
+    for k, v in enumerate(volumes):
+        tsdf = _vol(v["tsdf"], np.float32)
+        m = _lib.EmfModel()
+        m.tsdf, m.weights = tsdf.ptr, _vol(v["weights"], np.float32).ptr
+        assert v["weights"].shape == tsdf.shape
+        if v.get("fg_mask") is not None:
+            assert v["fg_mask"].shape == tsdf.shape
+            m.fgVolMask = _vol(v["fg_mask"], np.uint8).ptr
+        if v.get("unseen_tiles") is not None:
+            m.unseenTiles = v["unseen_tiles"].ptr
+        nz, ny, nx = tsdf.shape
+        m.res[:] = [nx, ny, nz]
+        res[3 * k:3 * k + 3] = [nx, ny, nz]
+        models.append(m)
+    return (upload_models(models) if models else None), res
+
+
+def shape_moments(volumes, first=0, out=None, stream=None):
+    """emf_hip_shapeMoments: the integer moments of the OBSERVED SOLID BAND of every volume of a table in one launch --
+    a TSDF observes a band around the surface, so this is not the body and no volume in cubic metres.  volumes:
+    [dict(tsdf=, weights=, fg_mask=None, unseen_tiles=None), ...] of device arrays, as extract_meshes takes them; they
+    occupy the table slots [first, first + n), first + n <= EMF_MAX_MODELS.  A voxel is solid where weights > 0, the
+    mask (if any) is non-zero and not tsdf > 0.  Returns a numpy array of n SHAPE_MOMENTS_DTYPE records (solid,
+    observed, sum, sum2 = xx yy zz xy xz yz, faces_free, faces_unknown, lo, hi), or with out= (a device array of at
+    least n such records) that array."""
+    n = len(volumes)
+    table, res = shape_table(volumes, first)
+    records = DeviceArray((max(n, 1),), SHAPE_MOMENTS_DTYPE) if out is None else out
+    assert records.dtype == SHAPE_MOMENTS_DTYPE and records.shape[0] >= n
+    check("emf_hip_shapeMoments", _L.emf_hip_shapeMoments(_ptr(table), res, int(first), n, _ptr(records), _stream(stream)))
+    return records.numpy()[:n] if out is None else out
+
+
+def shape_extents(volumes, frames, first=0, out=None, stream=None):
+    """emf_hip_shapeExtents: minimum and maximum, over the solid voxels v of every volume of a table, of
+    e_k = A_k0 p_0 + A_k1 p_1 + A_k2 p_2 with p = float(v) - c, each a single float32 operation, in one launch.
+    frames: n SHAPE_AXES_DTYPE records (A: three row vectors, c: the centre, voxel coordinates), numpy or device.
+    Returns a numpy array of n SHAPE_EXTENTS_DTYPE records (+inf / -inf for a volume without a solid voxel), or with
+    out= (a device array of at least n such records) that array."""
+    n = len(volumes)
+    table, res = shape_table(volumes, first)
+    if not isinstance(frames, DeviceArray):
+        frames = DeviceArray.from_numpy(np.ascontiguousarray(np.asarray(frames, SHAPE_AXES_DTYPE).reshape(-1)))
+    assert frames.dtype == SHAPE_AXES_DTYPE and frames.shape[0] >= n
+    records = DeviceArray((max(n, 1),), SHAPE_EXTENTS_DTYPE) if out is None else out
+    assert records.dtype == SHAPE_EXTENTS_DTYPE and records.shape[0] >= n
+    check("emf_hip_shapeExtents",
+          _L.emf_hip_shapeExtents(_ptr(table), res, int(first), n, _ptr(frames), _ptr(records), _stream(stream)))
+    return records.numpy()[:n] if out is None else out

@@ -173,6 +173,11 @@ def load() -> C.CDLL:
         "emf_fusion_plan_shortcut": [vp, C.c_int32, C.c_void_p, ip],
         "emf_fusion_copy_plan_shortcut": [vp, C.c_void_p, C.c_int32],
         "emf_fusion_set_plan_shortcut_output": [vp, C.c_int32],
+        "emf_fusion_object_shapes": [vp, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+        "emf_fusion_shape_frame": [C.c_void_p, C.c_void_p],
+        "emf_fusion_shape_box": [C.c_void_p, C.c_void_p, C.c_void_p, ip, C.c_float, fp, fp, C.c_void_p],
+        "emf_fusion_set_shape_output": [vp, C.c_int],
         "emf_fusion_process_rgbd_color": [vp, fp, C.c_void_p, C.c_int32, C.c_int32],
         "emf_fusion_colored_voxels": [vp, C.POINTER(C.c_uint64)],
         "emf_fusion_get_last_masks": [vp, C.c_void_p, C.c_size_t, ip],
@@ -375,6 +380,42 @@ def view_ray_targets(R, t, K, grid, range_m, bg_R, bg_t, res, voxel, lo=(0, 0, 0
                                               (C.c_int32 * 3)(*[int(v) for v in lo]),
                                               origin.ctypes.data_as(C.POINTER(C.c_int32)), targets.ctypes.data))
     return origin, targets
+
+
+def _shape_dtypes():
+    from . import _lib as hip
+    return (np.dtype(hip.SHAPE_MOMENTS_DTYPE), np.dtype(hip.SHAPE_FRAME_DTYPE), np.dtype(hip.SHAPE_EXTENTS_DTYPE),
+            np.dtype(hip.SHAPE_BOX_DTYPE))
+
+
+def shape_frame(moments):
+    """emf_fusion_shape_frame, on the host without a device: the frame of one record of
+    SHAPE_MOMENTS_DTYPE (ops.shape_moments) as a 0-d array of SHAPE_FRAME_DTYPE -- valid, centroid (voxels), covariance
+    (xx yy zz xy xz yz, voxels^2), eigenvalues (descending), axes (three row vectors, right-handed) and f32, the frame
+    rounded once for ops.shape_extents.  Float64 in the fixed operation order of include/emf_hip.h "Object shapes".  The
+    moments describe the OBSERVED SOLID BAND of a model, not its body.  Without a solid voxel valid is 0 and the rest
+    zeros."""
+    md, fd, _, _ = _shape_dtypes()
+    m = np.ascontiguousarray(np.asarray(moments, md).reshape(()))
+    out = np.zeros((), fd)
+    _check("emf_fusion_shape_frame", load().emf_fusion_shape_frame(m.ctypes.data, out.ctypes.data))
+    return out
+
+
+def shape_box(moments, frame, extents, res, voxel_size, R, t):
+    """emf_fusion_shape_box, on the host without a device: the box of a model (a 0-d array of SHAPE_BOX_DTYPE) from its
+    moments, a frame with valid != 0, the extents along it, the model's resolution (nx, ny, nz), voxel size and pose
+    (R, t: volume -> world).  Voxels, metres in the model's own frame (p = (v - (res - 1) / 2) * voxel_size) and the
+    world frame; float64 in the order of the header."""
+    md, fd, ed, bd = _shape_dtypes()
+    m = np.ascontiguousarray(np.asarray(moments, md).reshape(()))
+    f = np.ascontiguousarray(np.asarray(frame, fd).reshape(()))
+    e = np.ascontiguousarray(np.asarray(extents, ed).reshape(()))
+    out = np.zeros((), bd)
+    _check("emf_fusion_shape_box",
+           load().emf_fusion_shape_box(m.ctypes.data, f.ctypes.data, e.ctypes.data, (C.c_int32 * 3)(*[int(v) for v in res]),
+                                       float(voxel_size), _farr(R, 9), _farr(t, 3), out.ctypes.data))
+    return out
 
 
 def default_3d_view(params: FusionParams):
@@ -1253,6 +1294,59 @@ class Fusion:
             out["cost"] = volume
         return out
 
+    def object_shapes(self, ids=None, background=False):
+        """Where in its volume each object is, how large it is, how it is oriented and how much of its surface has been
+        seen, computed on the device from the volumes as they are: one launch for the integer moments of
+        all asked models, the frames on the host, one launch for the extents along them.
+
+        WHAT IS MEASURED IS THE OBSERVED SOLID BAND, NOT THE BODY.  A TSDF observes a band around the surface; the
+        interior of an object has weight 0.  solid counts the voxels with weight > 0, a set foreground bit and tsdf <= 0
+        (the rule by which the distance field calls an object solid), so neither a count nor a box here is a volume in
+        cubic metres, and the box bounds what has been seen so far.
+
+        ids: live object ids (default: all of them, in creation order); background=True puts the background (id 0) in
+        front.  An id that does not exist raises.  Returns a list of dicts, per model: id, valid (False: no solid voxel;
+        everything from centroid_vox on is None then), solid, observed, faces_free, faces_unknown (voxel faces of the
+        band towards seen free space / towards space nobody has seen), completeness = faces_free / (faces_free +
+        faces_unknown) (NaN without either), bounds_vox = (lo, hi) of the solid voxels, res, voxel_size, pose = (R, t)
+        volume -> world as the call found it (Fusion.pose(id) for an object), centroid_vox, axes (3 x 3 rows, sorted by
+        eigenvalue, right-handed), eigenvalues (voxels^2), extents_vox = (lo, hi) along the axes about the centroid
+        (f32), box_center_vox, box_half_vox; box_center, box_half, box_corners (8 x 3) in the model's own frame in
+        metres, p = (v - (res - 1) / 2) * voxel_size; box_center_world, box_axes_world, box_corners_world through the
+        pose.  Float64, rounded once.  The raw records are under moments, frame, extents and box.  Changes nothing of
+        the session; refused on the sharded path."""
+        md, fd, ed, bd = _shape_dtypes()
+        ids = self.object_ids() if ids is None else [int(i) for i in ids]
+        n = len(ids) + (1 if background else 0)
+        arr = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1)) if ids else np.zeros(1, np.int32)
+        ids_out, res, vs, poses = (np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), 3), np.int32),
+                                   np.zeros(max(n, 1), np.float32), np.zeros((max(n, 1), 12), np.float32))
+        mom, fr, ex, bx = np.zeros(max(n, 1), md), np.zeros(max(n, 1), fd), np.zeros(max(n, 1), ed), np.zeros(max(n, 1), bd)
+        _check("emf_fusion_object_shapes",
+               load().emf_fusion_object_shapes(self._h, arr.ctypes.data, len(ids), int(bool(background)), ids_out.ctypes.data,
+                                               res.ctypes.data, vs.ctypes.data, poses.ctypes.data, mom.ctypes.data,
+                                               fr.ctypes.data, ex.ctypes.data, bx.ctypes.data))
+        out = []
+        for k in range(n):
+            m, f, e, b = mom[k], fr[k], ex[k], bx[k]
+            valid = bool(f["valid"])
+            r = dict(id=int(ids_out[k]), valid=valid, solid=int(m["solid"]), observed=int(m["observed"]),
+                     faces_free=int(m["faces_free"]), faces_unknown=int(m["faces_unknown"]),
+                     bounds_vox=(m["lo"].copy(), m["hi"].copy()), res=tuple(int(v) for v in res[k]), voxel_size=float(vs[k]),
+                     pose=(poses[k, :9].reshape(3, 3).copy(), poses[k, 9:].copy()), moments=m.copy(), frame=f.copy(),
+                     extents=e.copy(), box=b.copy())
+            faces = r["faces_free"] + r["faces_unknown"]
+            r["completeness"] = float(b["completeness"]) if valid else (r["faces_free"] / faces if faces else float("nan"))
+            for key, value in (("centroid_vox", f["centroid"]), ("axes", f["axes"].reshape(3, 3)), ("eigenvalues", f["eigenvalues"]),
+                               ("extents_vox", (e["lo"], e["hi"])), ("box_center_vox", b["center_vox"]),
+                               ("box_half_vox", b["half_vox"]), ("box_center", b["center_obj"]), ("box_half", b["half_m"]),
+                               ("box_corners", b["corners_obj"].reshape(8, 3)), ("box_center_world", b["center_world"]),
+                               ("box_axes_world", b["axes_world"].reshape(3, 3)),
+                               ("box_corners_world", b["corners_world"].reshape(8, 3))):
+                r[key] = (tuple(v.copy() for v in value) if isinstance(value, tuple) else value.copy()) if valid else None
+            out.append(r)
+        return out
+
     def last_motion_masks(self):
         """The proposals of the last processed frame: ((H, W) i32 image of proposal ranks, -1 where none is, list of
         dicts {label, area, x0, y0, x1, y1} by rank).  Empty / all -1 if the frame proposed nothing."""
@@ -1450,7 +1544,7 @@ class Fusion:
     def setup_output(self, exp_frame_meshes=False, exp_vols=False, exp_world_mesh=False, exp_distance_field=False,
                      distance_cap=0.0, distance_unknown_is_obstacle=False, exp_frontiers=False, frontier_min_voxels=8,
                      frontier_clearance=0.0, exp_plan=False, plan_clearance=0.0, plan_through_unknown=False,
-                     exp_distance_nearest=False, exp_plan_shortcut=0):
+                     exp_distance_nearest=False, exp_plan_shortcut=0, exp_object_shapes=False):
         """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
         the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
         the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh();
@@ -1464,7 +1558,9 @@ class Fusion:
         exp_distance_nearest (needs exp_distance_field): write_results also writes nearest.bin, i32 in the container of
         distance.bin: the linear index of the nearest obstacle voxel of the background, -1 where there is none;
         exp_plan_shortcut=W > 0 (needs exp_plan): plan.txt carries one extra "waypoints n i_0 .. i_(n-1)" line per
-        reachable goal, plan(shortcut=W) of its path (include/emf_fusion.h emf_fusion_set_plan_shortcut_output)."""
+        reachable goal, plan(shortcut=W) of its path (include/emf_fusion.h emf_fusion_set_plan_shortcut_output);
+        exp_object_shapes: write_results also writes shapes.txt, one line per live object in id order: the integers of
+        object_shapes(), then the world-frame box in %.9g (include/emf_fusion.h emf_fusion_set_shape_output)."""
         if exp_plan_shortcut and not exp_plan:
             raise ValueError("setup_output: exp_plan_shortcut adds lines to plan.txt and needs exp_plan")
         if exp_distance_nearest and not exp_distance_field:
@@ -1487,6 +1583,8 @@ class Fusion:
         if exp_plan_shortcut:  # off: no new call
             _check("emf_fusion_set_plan_shortcut_output",
                    load().emf_fusion_set_plan_shortcut_output(self._h, int(exp_plan_shortcut)))
+        if exp_object_shapes:  # off: no new call
+            _check("emf_fusion_set_shape_output", load().emf_fusion_set_shape_output(self._h, 1))
 
     def write_results(self, directory: str, volumes: bool = True):
         """poses-*.txt, mesh_bg.ply, mesh_<id>.ply always; tsdfs/*.bin with `volumes` (reference formats)."""

@@ -397,6 +397,34 @@ int emf_fusion_copy_plan_shortcut(emf_fusion_t* h, int32_t* waypoints, int32_t c
  * after the path lines of every reachable goal, one line "waypoints n i_0 .. i_(n-1)": emf_fusion_plan_shortcut(window)
  * of that goal's path.  0: plan.txt as before, byte for byte. */
 int emf_fusion_set_plan_shortcut_output(emf_fusion_t* h, int32_t window);
+/* Object shapes (include/emf_hip.h "Object shapes"; new behaviour, opt-in): where in its volume each
+ * asked model is, how large it is, how it is oriented and how much of its surface has been seen.  WHAT IS MEASURED IS THE
+ * OBSERVED SOLID BAND, NOT THE BODY -- a TSDF observes a band around the surface, the interior of an object has weight
+ * 0 -- so nothing here is a volume in cubic metres.
+ *   object_shapes   ids: n live objects (emf_fusion_object_ids lists them), in the order of the result;
+ *                   include_background != 0 puts the background (id 0) in front.  The outputs hold n (+ 1) records each,
+ *                   NULL = not wanted: ids_out, res_out (3 per model), voxel_size_out, poses_out (12 per model: R row-major,
+ *                   then t; volume -> world as the call found it), the integer moments, the frame from them, the extents along the frame, and the box (voxels, metres in the model's frame, world frame
+ *                   through the model's pose as emf_fusion_get_pose gives it).  One moments launch for all models and
+ *                   one wait, the frames on the host, one extents launch and one more wait.  An id that does not exist
+ *                   is EMF_E_ARG; an object without a solid voxel has frames[k].valid == 0 and zeros for frame and box.
+ *                   Changes nothing of the session.  EMF_E_ARG on the sharded path.
+ *   shape_frame     needs no device and no handle: the frame of one moments record, float64 in the fixed operation order
+ *                   of include/emf_hip.h (moments->solid == 0: valid = 0 and nothing else is written).
+ *   shape_box       needs no device and no handle: the box of a model from its moments, a frame with valid != 0, the
+ *                   extents along it, the model's resolution, voxel size and pose (R, t: volume -> world).
+ *   set_shape_output  setup_output's exp_object_shapes, as an entry of its own so that the existing entries keep their
+ *                   signatures: emf_fusion_write_results also writes shapes.txt, after a comment line one line per live
+ *                   object in id order: id valid solid observed faces_free faces_unknown lo(3) hi(3), the integers, then
+ *                   the world-frame box in %.9g: centre (3), half extents in metres (3), axes (9).  Off: the set of
+ *                   result files and every byte of them as before. */
+int emf_fusion_object_shapes(emf_fusion_t* h, const int32_t* ids, int32_t n, int32_t include_background, int32_t* ids_out,
+                             int32_t* res_out, float* voxel_size_out, float* poses_out, emf_shape_moments_t* moments,
+                             emf_shape_frame_t* frames, emf_shape_extents_t* extents, emf_shape_box_t* boxes);
+int emf_fusion_shape_frame(const emf_shape_moments_t* moments, emf_shape_frame_t* frame);
+int emf_fusion_shape_box(const emf_shape_moments_t* moments, const emf_shape_frame_t* frame, const emf_shape_extents_t* extents,
+                         const int32_t res[3], float voxel_size, const float R[9], const float t[3], emf_shape_box_t* box);
+int emf_fusion_set_shape_output(emf_fusion_t* h, int on);
 /* Remember what rolls out (new behaviour, off by default; with it off no launch, no output byte and no
  * checkpoint byte changes).  With the store on, the whole integration tiles (32 x 8 x 8) that a roll moves out of the
  * background go to host memory as the bytes they are, after the slabs are retired; the tiles that a later roll moves

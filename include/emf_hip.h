@@ -1812,6 +1812,123 @@ int emf_hip_castVoxelRays(const uint8_t* classes, const int32_t size[3], const i
                           uint32_t count_mask, const int32_t* from, const int32_t* to, int32_t n, emf_ray_result_t* results,
                           int32_t group, emf_ray_group_t* groups, emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Object shapes (new behaviour: DESIGN.md 5.23).  Opt-in; nothing above is touched.  Where in its volume a model is,
+ * how large it is, how it is oriented and how much of its surface has been seen: a per-voxel pass over a model table
+ * that reduces to a few dozen integers per model, and a second pass that measures the model along given axes.
+ * WHAT IS MEASURED IS THE OBSERVED SOLID BAND, NOT THE BODY: a TSDF observes a band around the surface, the interior
+ * of an object has weight 0.  Nothing here is a volume in cubic metres and nothing must be presented as one.
+ * Volumes are dense, (z, y, x) order, x fastest, resolution res = (nx, ny, nz); a voxel is v = (x, y, z).  Single float
+ * comparisons only:
+ *   solid(v)     weights[v] > 0 && (fgVolMask == NULL || fgVolMask[v] != 0) && !(tsdf[v] > 0): exactly the rule by which
+ *                emf_hip_occupancyStampObjects calls an object solid.  A tsdf of -0.0 or NaN is solid; a NaN, zero or
+ *                negative weight is not.
+ *   observed(v)  weights[v] > 0.
+ *   faces        for each of the up to six face neighbours n of a solid voxel that lie INSIDE the volume: n is FREE if
+ *                weights[n] > 0 && tsdf[n] > 0, UNKNOWN if !(weights[n] > 0), and neither otherwise.  A neighbour
+ *                outside the volume does not exist.  The mask plays no part in a neighbour's kind.
+ * emf_shape_moments_t, per model, integers only: the counts, the sums of the solid voxels' coordinates and of their
+ * products, the ordered pairs (solid voxel, face neighbour) by the neighbour's kind -- faces_free is the seen surface in
+ * voxel faces, faces_unknown is where the solid band ends against space nobody has seen -- and the axis-aligned bounds
+ * of the solid voxels (lo = res and hi = -1 without one).
+ * Limits: every axis in 1 .. EMF_DF_MAX_AXIS and at most 2^31 - 1 voxels per model (EMF_E_LIMIT above; a zero or
+ * negative axis is EMF_E_ARG), so that every sum stays below 2^53; the models of one call together at most 2^24 - 1
+ * tiles of 32 x 8 x 8 voxels, partial ones included (EMF_E_LIMIT above).
+ *
+ * Extents along given axes: per model a frame emf_shape_axes_t -- three row vectors A and a centre c, f32, in voxel
+ * coordinates -- and for every solid voxel, each line a single float32 operation without contraction, rows summed left
+ * to right (the discipline of the stamping arithmetic):
+ *     p_j = float(v_j) - c_j
+ *     e_k = A_k0 * p_0 + A_k1 * p_1 + A_k2 * p_2
+ * emf_shape_extents_t holds the minimum and the maximum of e_k over the solid voxels (lo = +inf, hi = -inf without
+ * one).  They are taken on the order-preserving map of the f32 bits to u32 (key = bits ^ 0x80000000 for a clear sign
+ * bit, ~bits for a set one): for numbers that is the float order with -0 below +0, a NaN with a clear sign bit lies
+ * above +inf and one with a set sign bit below -inf.  Minimum and maximum do not depend on the order of the voxels:
+ * both records are pure functions of the inputs, bit for bit.
+ *
+ * The frame of a model from its moments (emf_fusion_shape_frame of include/emf_fusion.h; on the host, without a
+ * device).  Everything in float64, every line a single operation in this order, no contraction:
+ *     m_j  = double(sum_j) / double(solid)
+ *     C_jk = double(solid * sum2_jk - sum_j * sum_k) / (double(solid) * double(solid))
+ *            the integer numerator exact in 128 bits and rounded to double once (ties to even)
+ *     cyclic Jacobi on S = C with V = I: EMF_SHAPE_JACOBI_SWEEPS sweeps over the pairs (p, q) = (0,1), (0,2), (1,2);
+ *     a pair with S_pq == 0 exactly is skipped, else
+ *         theta = (S_qq - S_pp) / (2 * S_pq)
+ *         t = 1 / (|theta| + sqrt(theta * theta + 1)), negated where theta < 0
+ *         c = 1 / sqrt(t * t + 1);  s = t * c;  h = t * S_pq
+ *         S_pp = S_pp - h;  S_qq = S_qq + h;  S_pq = S_qp = 0
+ *         with r the third index: (S_rp, S_rq) = (c * S_rp - s * S_rq, s * S_rp + c * S_rq), mirrored
+ *         for every row i of V:    (V_ip, V_iq) = (c * V_ip - s * V_iq, s * V_ip + c * V_iq)
+ *     eigenvalue j = S_jj, its vector column j of V; sorted by eigenvalue, descending, ties to the lower index
+ *     axes 0 and 1 are negated where their component of largest magnitude (ties to the lowest index) is negative;
+ *     axis 2 = axis 0 x axis 1, each component one difference of two products: the frame is right-handed
+ *     A = float(axes), c = float(m): rounded to f32 once, for the extents pass
+ * solid == 0 gives valid = 0 and nothing else is written.
+ * The box of a model from its frame and extents (emf_fusion_shape_box), float64 in this order, sums left to right:
+ *     mid_k    = (double(lo_k) + double(hi_k)) / 2
+ *     centre_j = m_j + (A_0j * mid_0 + A_1j * mid_1 + A_2j * mid_2)         A: the float64 axes
+ *     half_k   = (double(hi_k) - double(lo_k)) / 2 + (|A_k0| + |A_k1| + |A_k2|) / 2
+ *                the second term is the half-width of a voxel cube along the axis
+ *     completeness = double(faces_free) / (double(faces_free) + double(faces_unknown)), NaN when both are 0
+ *     metres, in the model's own frame:  centre_obj_j = (centre_j - (double(res_j) - 1) / 2) * double(voxel_size),
+ *                half_m_k = half_k * double(voxel_size)
+ *     corner i (bit k of i set: +half_m_k, clear: -half_m_k):  p_j = ((centre_obj_j + h_0 * A_0j) + h_1 * A_1j) + h_2 * A_2j
+ *     world, with the model's pose (R, t; f32 taken to double):  x_i = (R_i0 * p_0 + R_i1 * p_1 + R_i2 * p_2) + t_i;
+ *                world axis k, component i = R_i0 * A_k0 + R_i1 * A_k1 + R_i2 * A_k2
+ * ---------------------------------------------------------------------------------------------- */
+#define EMF_SHAPE_JACOBI_SWEEPS 8 /* the smallest count after which another sweep changes no bit on the fixtures, + 2 */
+
+typedef struct emf_shape_moments {
+    uint64_t solid, observed;           /* counts */
+    uint64_t sum[3];                    /* sum of x, y, z over the solid voxels */
+    uint64_t sum2[6];                   /* sums of xx, yy, zz, xy, xz, yz */
+    uint64_t faces_free, faces_unknown; /* ordered pairs (solid voxel, face neighbour inside the volume) */
+    int32_t lo[3], hi[3];               /* bounds of the solid voxels; res and -1 without one */
+} emf_shape_moments_t;                  /* 128 bytes */
+
+typedef struct emf_shape_axes {
+    float A[9]; /* three row vectors */
+    float c[3]; /* the centre, voxel coordinates */
+} emf_shape_axes_t; /* 48 bytes */
+
+typedef struct emf_shape_extents {
+    float lo[3], hi[3]; /* minimum and maximum of e_k; +inf and -inf without a solid voxel */
+} emf_shape_extents_t;  /* 24 bytes */
+
+typedef struct emf_shape_frame {
+    int32_t valid, reserved; /* valid == 0 (solid == 0): nothing else is written */
+    double centroid[3];      /* m, voxel coordinates */
+    double covariance[6];    /* C: xx, yy, zz, xy, xz, yz (voxels^2) */
+    double eigenvalues[3];   /* descending (voxels^2) */
+    double axes[9];          /* three row vectors, right-handed */
+    emf_shape_axes_t f32;    /* the same frame rounded once: what the extents pass takes */
+} emf_shape_frame_t;         /* 224 bytes */
+
+typedef struct emf_shape_box {
+    double center_vox[3], half_vox[3]; /* voxel coordinates, along the frame's axes */
+    double completeness;               /* faces_free / (faces_free + faces_unknown), NaN without either */
+    double center_obj[3], half_m[3];   /* metres, the model's own frame */
+    double corners_obj[24];            /* 8 x 3 */
+    double center_world[3], axes_world[9], corners_world[24];
+} emf_shape_box_t;                     /* 584 bytes */
+
+/* Both run over the slots [first, first + n) of a device model table, 1 <= n, first >= 0, first + n <= EMF_MAX_MODELS,
+ * in ONE launch for the whole range (plus the small launches that initialise and finish the records).  res_host: HOST
+ * int32[3 n], the resolutions of those slots as the table stores them.  Of a model tsdf, weights, fgVolMask (NULL: no
+ * gate), res and unseenTiles are read; nothing of a model is written.  A workgroup whose 32 x 8 x 8 tile the model's
+ * unseenTiles map (NULL: none) marks "every weight is 0" adds nothing of its own and is skipped; its voxels are still
+ * read as the neighbours of other tiles' solid voxels.
+ *   moments_dev  n records (record k: slot first + k), initialised by the call on the stream, then one integer atomic
+ *                per non-zero quantity and workgroup
+ *   frames_dev   n emf_shape_axes_t, only read;  extents_dev: n records, initialised by the call on the stream
+ * A second call into the same buffers gives the same bytes.  Every rejected argument -- a NULL pointer, n <= 0,
+ * first < 0, first + n > EMF_MAX_MODELS, an axis outside the limits -- returns EMF_E_ARG or EMF_E_LIMIT with nothing
+ * enqueued.  Nothing allocates, copies to the host or waits. */
+int emf_hip_shapeMoments(const emf_model_t* models_dev, const int32_t* res_host, int32_t first, int32_t n,
+                         emf_shape_moments_t* moments_dev, emf_stream_t stream);
+int emf_hip_shapeExtents(const emf_model_t* models_dev, const int32_t* res_host, int32_t first, int32_t n,
+                         const emf_shape_axes_t* frames_dev, emf_shape_extents_t* extents_dev, emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
