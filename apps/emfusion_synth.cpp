@@ -8,6 +8,8 @@
 //                  [--distance-field] [--distance-cap M] [--distance-unknown-obstacle] [--distance-nearest]
 //                  [--frontiers] [--frontier-min-voxels N] [--frontier-clearance M]
 //                  [--plan] [--plan-clearance M] [--plan-through-unknown] [--plan-shortcut W] [--object-shapes]
+//                  [--ground-map] [--ground-up X,Y,Z] [--ground-cell M] [--ground-bin M] [--ground-band LO,HI]
+//                  [--ground-robot-height M] [--ground-max-step M]
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
 //                  [--bg-res R] [--bg-voxel M] [--obj-res R] [--volumes] --out DIR
 //   emfusion_synth --dir BASE/ [--colordir colour] [--depthdir depth] [--intrinsics fx fy cx cy] ... --out DIR
@@ -123,6 +125,22 @@ static int planShortcut = 0;
 // integer moments of its observed solid band (not its body), then its box in the world frame;
 // without it no output byte changes
 static bool objectShapesOut = false;
+// --ground-map (needs --out): writeResults also writes OUT/ground.bin and OUT/ground.txt, the 2-D traversability map of
+// the whole background with a floor height per cell; --ground-up X,Y,Z (world frame; default: minus the
+// background's y axis), --ground-cell / --ground-bin M (default: two voxels), --ground-band LO,HI (metres relative to
+// the camera along up), --ground-robot-height M, --ground-max-step M; without --ground-map no output byte changes
+static emf::EMFusion::GroundOutput groundOut;
+static bool groundGiven = false, groundBad = false;
+// "a,b[,c]" into n doubles; false if it does not hold n numbers
+static bool parseList(const char* text, double* out, int n) {
+    char* end = nullptr;
+    for (int i = 0; i < n; ++i) {
+        out[i] = std::strtod(text, &end);
+        if (end == text || (i + 1 < n && *end != ',')) return false;
+        text = end + 1;
+    }
+    return *end == 0;
+}
 static bool planShortcutGiven = false;
 // --motion-masks [--motion-band M] [--motion-min-pixels N] [--motion-max-masks N]: mask frames propose their own
 // instance masks from the depth in front of the background model (EMFusion::setMotionMasks) instead of reading them
@@ -232,6 +250,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     emf.setPlanOutput(planOut, planClearance, planThroughUnknown);
     if (planShortcut > 0) emf.setPlanShortcutOutput(planShortcut);
     if (objectShapesOut) emf.setShapeOutput(true);
+    if (groundOut.on) emf.setGroundOutput(groundOut);
     set3dView(emf, params, view3d);
     std::vector<uint8_t> rendered(3 * params.frameSize.area());
     const auto t0 = std::chrono::steady_clock::now();
@@ -341,6 +360,17 @@ int main(int argc, char** argv) {
         else if (a == "--distance-unknown-obstacle") distanceUnknownObstacle = true;
         else if (a == "--distance-nearest") distanceNearest = true;
         else if (a == "--object-shapes") objectShapesOut = true;
+        else if (a == "--ground-map") groundOut.on = true;
+        else if (a == "--ground-up" && i + 1 < argc) groundGiven = true, groundBad |= !parseList(argv[++i], groundOut.up, 3);
+        else if (a == "--ground-band" && i + 1 < argc) {
+            double band[2] = {0.0, 0.0};
+            groundGiven = true, groundBad |= !parseList(argv[++i], band, 2);
+            groundOut.bandLo = band[0], groundOut.bandHi = band[1];
+        }
+        else if (a == "--ground-cell" && i + 1 < argc) groundGiven = true, groundOut.cell = std::atof(argv[++i]);
+        else if (a == "--ground-bin" && i + 1 < argc) groundGiven = true, groundOut.bin = std::atof(argv[++i]);
+        else if (a == "--ground-robot-height" && i + 1 < argc) groundGiven = true, groundOut.robotHeight = std::atof(argv[++i]);
+        else if (a == "--ground-max-step" && i + 1 < argc) groundGiven = true, groundOut.maxStep = std::atof(argv[++i]);
         else if (a == "--frontiers") frontiersOut = true;
         else if (a == "--frontier-min-voxels" && i + 1 < argc) frontierMinVoxels = std::max(std::atoi(argv[++i]), 1);
         else if (a == "--frontier-clearance" && i + 1 < argc) frontierClearance = std::max(static_cast<float>(std::atof(argv[++i])), 0.f);
@@ -379,6 +409,12 @@ int main(int argc, char** argv) {
     }
     if (planShortcutGiven && (!planOut || planShortcut < 1)) {  // (before any device is touched)
         std::fprintf(stderr, "usage: emfusion_synth: --plan-shortcut W (>= 1) adds the waypoints lines to plan.txt and needs --plan\n");
+        return 2;
+    }
+    if ((groundGiven && !groundOut.on) || groundBad || (groundOut.on && outDir.empty())) {  // (before any device is touched)
+        std::fprintf(stderr, "usage: emfusion_synth: --ground-up X,Y,Z, --ground-band LO,HI, --ground-cell, --ground-bin, "
+                             "--ground-robot-height and --ground-max-step need --ground-map, which writes ground.bin and "
+                             "ground.txt and needs --out DIR\n");
         return 2;
     }
     if (motionMasks && !maskDir.empty()) {  // (before any device is touched)
@@ -468,6 +504,7 @@ int main(int argc, char** argv) {
         emf.setPlanOutput(planOut, planClearance, planThroughUnknown);
         if (planShortcut > 0) emf.setPlanShortcutOutput(planShortcut);
         if (objectShapesOut) emf.setShapeOutput(true);
+        if (groundOut.on) emf.setGroundOutput(groundOut);
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);
 

@@ -96,6 +96,21 @@ def main():
     ap.add_argument("--object-shapes", dest="object_shapes", action="store_true",
                     help="also write OUT/shapes.txt: one line per live object in id order, the integer moments of its "
                          "observed solid band (not its body), then its box in the world frame")
+    ap.add_argument("--ground-map", dest="ground_map", action="store_true",
+                    help="also write OUT/ground.bin and OUT/ground.txt: the 2-D traversability map of the whole background "
+                         "with a floor height per cell (classes, then records of floor, top, clear, levels)")
+    ap.add_argument("--ground-up", dest="ground_up", default=None, metavar="X,Y,Z",
+                    help="with --ground-map: the world direction that is up (default: minus the background's y axis)")
+    ap.add_argument("--ground-cell", dest="ground_cell", type=float, default=None, metavar="M",
+                    help="with --ground-map: the side of a ground cell in metres (default: two voxels)")
+    ap.add_argument("--ground-bin", dest="ground_bin", type=float, default=None, metavar="M",
+                    help="with --ground-map: the height of a bin in metres (default: two voxels)")
+    ap.add_argument("--ground-band", dest="ground_band", default="-1.5,0.5", metavar="LO,HI",
+                    help="with --ground-map: the heights looked at, metres relative to the camera along up")
+    ap.add_argument("--ground-robot-height", dest="ground_robot_height", type=float, default=0.3, metavar="M",
+                    help="with --ground-map: the free height a floor needs above it")
+    ap.add_argument("--ground-max-step", dest="ground_max_step", type=float, default=0.05, metavar="M",
+                    help="with --ground-map: a larger difference between neighbouring floors is an obstacle")
     ap.add_argument("--weld-meshes", dest="weld_meshes", action="store_true",
                     help="weld every mesh written (mesh_*.ply of the live models, frame_meshes/) by grid edge on the "
                          "device: one vertex per edge instead of one per cube that touches it")
@@ -202,7 +217,11 @@ def main():
                      frontier_clearance=max(args.frontier_clearance, 0.0), exp_plan=args.plan,
                      plan_clearance=max(args.plan_clearance, 0.0), plan_through_unknown=args.plan_through_unknown,
                      exp_distance_nearest=args.distance_nearest, exp_plan_shortcut=args.plan_shortcut,
-                     exp_object_shapes=args.object_shapes)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
+                     exp_object_shapes=args.object_shapes, exp_ground_map=args.ground_map,
+                     ground_up=None if args.ground_up is None else [float(v) for v in args.ground_up.split(",")],
+                     ground_cell=args.ground_cell, ground_bin=args.ground_bin,
+                     ground_band=[float(v) for v in args.ground_band.split(",")],
+                     ground_robot_height=args.ground_robot_height, ground_max_step=args.ground_max_step)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)
     if args.vis3d:  # the reference's window (apps/EM-Fusion.cpp:118-131), or a viewer placed with look_at
         R3, t3, K3, size3 = pipeline.default_3d_view(prm)
         if args.vis3d_eye:

@@ -221,6 +221,9 @@ SIGNATURES = {
                               _STREAM],
     "emf_hip_shapeMoments": [_FP, _I3, C.c_int32, C.c_int32, _FP, _STREAM],
     "emf_hip_shapeExtents": [_FP, _I3, C.c_int32, C.c_int32, _FP, _FP, _STREAM],
+    "emf_hip_groundColumns": [_FP, _I3, None, _FP, _FP, _STREAM],  # [2]: EmfGroundFrame by value, set below its class
+    "emf_hip_groundCells": [_FP, _FP, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _FP, _STREAM],
+    "emf_hip_groundClasses": [_FP, C.POINTER(C.c_int32), C.c_int32, _FP, _STREAM],
 }
 
 
@@ -277,6 +280,15 @@ class EmfShapeExtents(C.Structure):
     _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3)]
 
 
+class EmfGroundFrame(C.Structure):
+    """Mirror of emf_ground_frame_t (include/emf_hip.h "Ground map"): 60 bytes, passed by value."""
+
+    _fields_ = [("G", C.c_float * 12), ("map", C.c_int32 * 2), ("bins", C.c_int32)]
+
+
+SIGNATURES["emf_hip_groundColumns"][2] = EmfGroundFrame
+
+
 class EmfOccObject(C.Structure):
     """Mirror of emf_occ_object_t (include/emf_hip.h "Distance field"): 112 bytes."""
 
@@ -318,6 +330,9 @@ SHAPE_BOX_DTYPE = [("center_vox", "<f8", 3), ("half_vox", "<f8", 3), ("completen
                    ("half_m", "<f8", 3), ("corners_obj", "<f8", 24), ("center_world", "<f8", 3), ("axes_world", "<f8", 9),
                    ("corners_world", "<f8", 24)]
 SHAPE_JACOBI_SWEEPS = 8
+# include/emf_hip.h "Ground map": emf_ground_cell_t (8 bytes)
+GROUND_CELL_DTYPE = [("floor", "<i2"), ("top", "<i2"), ("clear", "<i2"), ("levels", "<i2")]
+GROUND_MAX_BINS = 256
 RAY_REACHED, RAY_BLOCKED, RAY_LEFT, RAY_OUTSIDE, RAY_INVALID = 0, 1, 2, 3, 4
 FRONTIER_KEPT, FRONTIER_CLUSTERS, FRONTIER_VOXELS = 0, 1, 2
 # include/emf_hip.h "Planning"

@@ -550,6 +550,38 @@ public:
     /** writeResults also writes shapes.txt, one line per live object in id order (writeShapes); without it no output byte changes. */
     void setShapeOutput(bool on) { expShapes_ = on; }
     void writeShapes(const std::string& dir);
+    /** The result of groundMap(): the frame, the pose "ground metres -> world" and the arrays left on the device. */
+    struct GroundMap {
+        QueryBox box;
+        emf_ground_frame_t frame{};
+        double pose[12] = {};  // R row-major with (u, v, h) as columns, then t
+        int robotBins = 0, maxStepBins = 0;
+        const emf_ground_cell_t* cells = nullptr;  // device, map[0] * map[1] records
+        const uint8_t* classes = nullptr;          // device, (1, H, W): an input of the 2-D distance, frontier and plan entries
+    };
+    /**
+     * Ground map (include/emf_hip.h "Ground map"): where a robot that drives on a floor can stand.  The
+     * occupancy classes of the box, every live object not in excludeIds stamped, are projected along `up` (world frame)
+     * onto cells of `cell` metres with height bins of `bin` metres over the band [bandLo, bandHi) metres relative to the
+     * world point `ref` along up; every column gives a floor level with robotBins FREE bins above it, and the cells a 2-D
+     * class volume in which steps of more than maxStepBins bins are obstacles.  Drains the frame as the other queries do,
+     * then the classes and the three ground entries on the main stream and one wait.  Changes nothing of the session and
+     * nothing goes into a checkpoint.  Refused (EMF_E_ARG) on the sharded path.
+     */
+    const GroundMap& groundMap(const Vec3i& boxLo, const Vec3i& boxSize, const double up[3], double cell, double bin,
+                               const double ref[3], double bandLo, double bandHi, int robotBins, int maxStepBins,
+                               const std::vector<int>& excludeIds);
+    const GroundMap& lastGroundMap() const { return gmLast; }
+    /** The parameters of setGroundOutput: metres; cell or bin <= 0: two voxels of the background. */
+    struct GroundOutput {
+        bool on = false;
+        double up[3] = {0.0, 0.0, 0.0};  // all zero: minus the background's y axis in the world frame
+        double cell = 0.0, bin = 0.0, bandLo = -1.5, bandHi = 0.5, robotHeight = 0.3, maxStep = 0.05;
+    };
+    /** writeResults also writes ground.bin and ground.txt of the whole background (writeGround); without it no output
+     *  byte changes. */
+    void setGroundOutput(const GroundOutput& g) { expGround_ = g; }
+    void writeGround(const std::string& dir);
     /** Ids returned by initNewObjVolume for FrameInputs::newObjectMasks of the last frame (-1: none). */
     const std::vector<int>& lastCreatedObjects() const { return lastCreated; }
     Affine3f getCameraPose() const { return pose; }
@@ -1102,6 +1134,12 @@ private:
     std::vector<ObjectShape> shLast;
     DeviceBuffer shScratch;          // the compact model table, the moments, the frames and the extents of one call
     bool expShapes_ = false;         // setShapeOutput
+
+    // ---- ground map (groundMap; EMFusionGround.cpp): allocated at first use, never in a checkpoint; behind all
+    // existing members ----
+    GroundMap gmLast;
+    DeviceBuffer gmBoxClasses, gmPlanes, gmCells, gmClasses;  // the box's classes, occ + fre, the records, the 2-D classes
+    GroundOutput expGround_;         // setGroundOutput
 };
 
 /**
@@ -1143,5 +1181,24 @@ void shapeFrame(const emf_shape_moments_t& mom, emf_shape_frame_t& out);
  */
 void shapeBox(const emf_shape_moments_t& mom, const emf_shape_frame_t& frame, const emf_shape_extents_t& ext, const int32_t res[3],
               float voxelSize, const float R[9], const float t[3], emf_shape_box_t& out);
+
+/**
+ * The frame of a ground map, on the host, without a device: float64 in the operation order written out
+ * in include/emf_hip.h "Ground map", G rounded to f32 once.  pose: "ground metres -> world", R row-major with (u, v, h)
+ * as columns, then t.  Returns EMF_OK, or EMF_E_ARG / EMF_E_LIMIT with the reason in `why`.
+ */
+int groundFrame(const QueryBox& box, const double up[3], double cell, double bin, const double ref[3], double bandLo,
+                double bandHi, emf_ground_frame_t& frame, double pose[12], std::string& why);
+/** Is up along a box axis to within float rounding of the frame: in every row of G all entries but the largest are at
+ *  most 2^-20 of it.  Only then slots narrower than two voxels leave no holes. */
+bool groundFrameAligned(const emf_ground_frame_t& frame);
+/** Metres to height bins, in float as metresToVoxels: the robot's height rounded up and at least 1, the step rounded down
+ *  -- both err on the careful side. */
+inline int groundRobotBins(float height, float bin) {
+    return std::max(static_cast<int>(std::min(std::ceil(height / bin), 4096.f)), 1);
+}
+inline int groundStepBins(float step, float bin) {
+    return step > 0.f ? static_cast<int>(std::min(std::floor(step / bin), 4096.f)) : 0;
+}
 
 }  // namespace emf

@@ -988,6 +988,97 @@ int emf_fusion_set_shape_output(emf_fusion_t* h, int on) {
     return guarded([&] { h->impl->setShapeOutput(on != 0); });
 }
 
+static void copyGround(emf_fusion_t* h, const EMFusion::GroundMap& g, emf_ground_cell_t* cells, uint8_t* classes) {
+    if (!g.cells) throw HipError("emf_fusion_copy_ground_map: no ground map has been computed", EMF_E_ARG);
+    const size_t n = static_cast<size_t>(g.frame.map[0]) * g.frame.map[1];
+    Stream& s = h->impl->mainStream();
+    if (cells) hipCheck(hipMemcpyAsync(cells, g.cells, n * sizeof(emf_ground_cell_t), hipMemcpyDeviceToHost, s.get()), "copy_ground_map (cells)");
+    if (classes) hipCheck(hipMemcpyAsync(classes, g.classes, n, hipMemcpyDeviceToHost, s.get()), "copy_ground_map (classes)");
+    if (cells || classes) s.waitForCompletion();
+}
+
+int emf_fusion_ground_map(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], const int32_t* exclude_ids,
+                          int32_t num_exclude, const double up[3], double cell, double bin, const double reference[3],
+                          double band_lo, double band_hi, int32_t robot_bins, int32_t max_step_bins, int32_t lo_out[3],
+                          int32_t size_out[3], emf_ground_frame_t* frame, double ground_pose[12], emf_ground_cell_t* cells,
+                          uint8_t* classes, int64_t capacity) {
+    REQ(h);
+    REQ(up);
+    REQ(reference);
+    QueryArgs a;
+    if (const int rc = queryArgs("emf_fusion_ground_map", h, box_lo, box_size, exclude_ids, num_exclude, a)) return rc;
+    return guarded([&] {
+        const EMFusion::GroundMap& g =
+            h->impl->groundMap(a.lo, a.size, up, cell, bin, reference, band_lo, band_hi, robot_bins, max_step_bins, a.exclude);
+        putBox(g.box, lo_out, size_out, nullptr, nullptr);
+        if (frame) *frame = g.frame;
+        if (ground_pose) std::copy(g.pose, g.pose + 12, ground_pose);
+        if ((cells || classes) && capacity < static_cast<int64_t>(g.frame.map[0]) * g.frame.map[1])
+            throw HipError("emf_fusion_ground_map: the outputs hold fewer cells than the map has", EMF_E_ARG);
+        copyGround(h, g, cells, classes);
+    });
+}
+
+int emf_fusion_copy_ground_map(emf_fusion_t* h, emf_ground_cell_t* cells, uint8_t* classes) {
+    REQ(h);
+    return guarded([&] { copyGround(h, h->impl->lastGroundMap(), cells, classes); });
+}
+
+int emf_fusion_ground_classes_ptr(emf_fusion_t* h, void** classes_dev, void** cells_dev) {
+    REQ(h);
+    return guarded([&] {
+        const EMFusion::GroundMap& g = h->impl->lastGroundMap();
+        if (!g.cells) throw HipError("emf_fusion_ground_classes_ptr: no ground map has been computed", EMF_E_ARG);
+        if (classes_dev) *classes_dev = const_cast<uint8_t*>(g.classes);
+        if (cells_dev) *cells_dev = const_cast<emf_ground_cell_t*>(g.cells);
+    });
+}
+
+int emf_fusion_set_ground_output(emf_fusion_t* h, int on, const double up[3], double cell, double bin, double band_lo,
+                                 double band_hi, double robot_height, double max_step) {
+    REQ(h);
+    return guarded([&] {
+        EMFusion::GroundOutput g;
+        g.on = on != 0;
+        if (up) std::copy(up, up + 3, g.up);
+        g.cell = cell, g.bin = bin, g.bandLo = band_lo, g.bandHi = band_hi, g.robotHeight = robot_height, g.maxStep = max_step;
+        h->impl->setGroundOutput(g);
+    });
+}
+
+int emf_fusion_ground_frame(const int32_t box_lo[3], const int32_t box_size[3], const int32_t bg_res[3], float voxel_size,
+                            const float R[9], const float t[3], const double up[3], double cell, double bin,
+                            const double reference[3], double band_lo, double band_hi, emf_ground_frame_t* frame,
+                            double ground_pose[12]) {
+    REQ(box_lo);
+    REQ(box_size);
+    REQ(bg_res);
+    REQ(R);
+    REQ(t);
+    REQ(up);
+    REQ(reference);
+    REQ(frame);
+    REQ(ground_pose);
+    return guarded([&] {
+        QueryBox box;
+        box.lo = Vec3i(box_lo[0], box_lo[1], box_lo[2]);
+        box.size = Vec3i(box_size[0], box_size[1], box_size[2]);
+        box.bgRes = Vec3i(bg_res[0], bg_res[1], bg_res[2]);
+        box.voxelSize = voxel_size;
+        box.bgPose = Affine3f(Matx33f(R), Vec3f(t[0], t[1], t[2]));
+        for (int i = 0; i < 3; ++i)
+            if (box.size[i] < 1) throw HipError("emf_fusion_ground_frame: an empty box", EMF_E_ARG);
+        if (!(voxel_size > 0.f)) throw HipError("emf_fusion_ground_frame: a voxel size that is not positive", EMF_E_ARG);
+        std::string why;
+        emf_ground_frame_t f{};
+        double pose[12];
+        if (const int rc = groundFrame(box, up, cell, bin, reference, band_lo, band_hi, f, pose, why))
+            throw HipError("emf_fusion_ground_frame: " + why, rc);
+        *frame = f;
+        std::copy(pose, pose + 12, ground_pose);
+    });
+}
+
 int emf_fusion_follow_shift(const float q[3], const int32_t step[3], float voxel_size, int32_t shift[3]) {
     REQ(q);
     REQ(step);

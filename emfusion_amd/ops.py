@@ -1975,3 +1975,76 @@ def shape_extents(volumes, frames, first=0, out=None, stream=None):
     check("emf_hip_shapeExtents",
           _L.emf_hip_shapeExtents(_ptr(table), res, int(first), n, _ptr(frames), _ptr(records), _stream(stream)))
     return records.numpy()[:n] if out is None else out
+
+
+# ---- ground map (include/emf_hip.h "Ground map") -------------------------------------------------
+
+GROUND_CELL_DTYPE = np.dtype(_lib.GROUND_CELL_DTYPE)
+GROUND_MAX_BINS = _lib.GROUND_MAX_BINS
+GroundFrame = _lib.EmfGroundFrame
+assert GROUND_CELL_DTYPE.itemsize == 8 and C.sizeof(GroundFrame) == 60
+
+
+def ground_frame(G, map_size, bins):
+    """The emf_ground_frame_t of a 3 x 4 map G (box voxel -> u in cells, v in cells, h in bins; rounded to f32 here
+    unless it is f32 already), map_size = (W, H) and `bins` height bins.  A GroundFrame passes through."""
+    if isinstance(G, GroundFrame):
+        return G
+    f = GroundFrame()
+    f.G = _f(G, 12)
+    f.map[:] = [int(map_size[0]), int(map_size[1])]
+    f.bins = int(bins)
+    return f
+
+
+def _ground_words(bins):
+    return (int(bins) + 63) // 64
+
+
+def ground_columns(classes, frame, out=None, stream=None):
+    """emf_hip_groundColumns: the two bit planes (occ, fre), each (H, W, words) u64 with words = (bins + 63) // 64, of a
+    (nz, ny, nx) u8 class volume under `frame` (a GroundFrame, see ground_frame).  Bit h & 63 of word h >> 6 of cell
+    (v, u) is set in occ where an OCCUPIED voxel falls into slot (u, v, h), in fre where a FREE one does; every voxel
+    counts.  The planes are zeroed by the call.  out: (occ, fre) to reuse."""
+    assert classes.dtype == np.uint8 and len(classes.shape) == 3 and not classes.padded
+    assert isinstance(frame, GroundFrame)
+    shape = (max(frame.map[1], 1), max(frame.map[0], 1), max(_ground_words(frame.bins), 1))
+    occ, fre = out if out is not None else (DeviceArray(shape, np.uint64), DeviceArray(shape, np.uint64))
+    for p in (occ, fre):
+        assert p.dtype == np.uint64 and not p.padded and p.shape == shape
+    check("emf_hip_groundColumns",
+          _L.emf_hip_groundColumns(_ptr(classes), _i3(classes.shape[::-1]), frame, _ptr(occ), _ptr(fre), _stream(stream)))
+    return occ, fre
+
+
+def ground_cells(occ, fre, bins, robot_bins, out=None, stream=None):
+    """emf_hip_groundCells: the (H, W) GROUND_CELL_DTYPE records (floor, top, clear, levels) of the (H, W, words) planes
+    of ground_columns for a robot of robot_bins >= 1 bins.  out: a records array to reuse."""
+    assert occ.dtype == np.uint64 and fre.dtype == np.uint64 and occ.shape == fre.shape and len(occ.shape) == 3
+    H, W = occ.shape[0], occ.shape[1]
+    cells = DeviceArray((H, W), GROUND_CELL_DTYPE) if out is None else out
+    assert cells.dtype == GROUND_CELL_DTYPE and cells.shape == (H, W) and not cells.padded
+    check("emf_hip_groundCells",
+          _L.emf_hip_groundCells(_ptr(occ), _ptr(fre), (C.c_int32 * 2)(W, H), int(bins), int(robot_bins), _ptr(cells),
+                                 _stream(stream)))
+    return cells
+
+
+def ground_classes(cells, max_step, out=None, stream=None):
+    """emf_hip_groundClasses: the (1, H, W) u8 classes of (H, W) ground cells for a largest step of max_step >= 0 bins:
+    FREE where a robot can stand, OCCUPIED at steps and where there is matter but no floor, UNKNOWN elsewhere.  A valid
+    input of distance_transform, frontier_labels, plan_cost and cast_voxel_rays."""
+    assert cells.dtype == GROUND_CELL_DTYPE and len(cells.shape) == 2 and not cells.padded
+    H, W = cells.shape
+    classes2d = DeviceArray((1, H, W), np.uint8) if out is None else out
+    assert classes2d.dtype == np.uint8 and classes2d.shape == (1, H, W) and not classes2d.padded
+    check("emf_hip_groundClasses",
+          _L.emf_hip_groundClasses(_ptr(cells), (C.c_int32 * 2)(W, H), int(max_step), _ptr(classes2d), _stream(stream)))
+    return classes2d
+
+
+def ground_map(classes, frame, robot_bins, max_step, stream=None):
+    """ground_columns, ground_cells and ground_classes of a class volume: (cells, classes2d), both on the device."""
+    occ, fre = ground_columns(classes, frame, stream=stream)
+    cells = ground_cells(occ, fre, frame.bins, robot_bins, stream=stream)
+    return cells, ground_classes(cells, max_step, stream=stream)

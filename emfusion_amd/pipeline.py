@@ -178,6 +178,15 @@ def load() -> C.CDLL:
         "emf_fusion_shape_frame": [C.c_void_p, C.c_void_p],
         "emf_fusion_shape_box": [C.c_void_p, C.c_void_p, C.c_void_p, ip, C.c_float, fp, fp, C.c_void_p],
         "emf_fusion_set_shape_output": [vp, C.c_int],
+        "emf_fusion_ground_map": [vp, ip, ip, ip, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_double,
+                                  C.c_double, C.c_int32, C.c_int32, ip, ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_int64],
+        "emf_fusion_copy_ground_map": [vp, C.c_void_p, C.c_void_p],
+        "emf_fusion_ground_classes_ptr": [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)],
+        "emf_fusion_ground_frame": [ip, ip, ip, C.c_float, fp, fp, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_double,
+                                    C.c_double, C.c_void_p, C.c_void_p],
+        "emf_fusion_set_ground_output": [vp, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                         C.c_double],
         "emf_fusion_process_rgbd_color": [vp, fp, C.c_void_p, C.c_int32, C.c_int32],
         "emf_fusion_colored_voxels": [vp, C.POINTER(C.c_uint64)],
         "emf_fusion_get_last_masks": [vp, C.c_void_p, C.c_size_t, ip],
@@ -344,6 +353,151 @@ def _box_outs():
 def _read_box_outs(lo, sz, R, t):
     """((lo, size), (R 3x3, t 3)): the box and the pose of its voxel (0, 0, 0) -> world."""
     return (tuple(lo), tuple(sz)), (np.array(R, np.float32).reshape(3, 3), np.array(t, np.float32))
+
+
+def ground_bins(robot_height, max_step, bin):
+    """(R, S): the robot's height rounded up to whole bins and at least 1, the largest step rounded down -- in float32,
+    as _metres_to_voxels; both roundings err on the careful side."""
+    b = np.float32(bin)
+    robot = max(int(min(np.ceil(np.float32(robot_height) / b), np.float32(4096))), 1)
+    step = int(min(np.floor(np.float32(max_step) / b), np.float32(4096))) if max_step > 0 else 0
+    return robot, step
+
+
+def ground_frame(lo, size, res, voxel, bg_R, bg_t, up, cell, bin, reference, band):
+    """The frame of a ground map (include/emf_hip.h "Ground map"), restated in numpy float64 with the
+    operand order of emf_fusion_ground_frame, so that both give the same bits.  lo, size: the box, res: the background's
+    resolution, all (x, y, z) voxels; voxel: its voxel size; bg_R, bg_t: its pose (f32); up: the world direction that is
+    up; cell, bin: metres; reference: a world point; band = (lo, hi) metres relative to it along up.  Returns
+    (G (3, 4) f32: box voxel -> (u cells, v cells, h bins), W, H, B, pose (12,) f64: R row-major with (u, v, h) as
+    columns, then t; ground metres -> world).  Raises ValueError where the entry returns an error."""
+    f8 = np.float64
+    lo, size, res = (np.array([int(v) for v in a], f8) for a in (lo, size, res))
+    vs = f8(np.float32(voxel))
+    R = np.asarray(bg_R, np.float32).reshape(9).astype(f8)
+    t = np.asarray(bg_t, np.float32).reshape(3).astype(f8)
+    up, ref = np.asarray(up, f8).reshape(3), np.asarray(reference, f8).reshape(3)
+    cell, bin, band_lo, band_hi = f8(cell), f8(bin), f8(band[0]), f8(band[1])
+    if not (np.isfinite(up).all() and np.isfinite(ref).all()):
+        raise ValueError("ground_frame: a non-finite up or reference")
+    if not (cell > 0 and bin > 0 and np.isfinite(cell) and np.isfinite(bin)):
+        raise ValueError("ground_frame: cell and bin must be positive metres")
+    if not (np.isfinite(band_lo) and np.isfinite(band_hi) and band_hi > band_lo):
+        raise ValueError("ground_frame: the height band is empty")
+    s = up[0] * up[0]
+    s = s + up[1] * up[1]
+    s = s + up[2] * up[2]
+    length = np.sqrt(s)
+    if not (length > 0 and np.isfinite(length)):
+        raise ValueError("ground_frame: up has no direction")
+    h = up / length
+    for column in (0, 2):
+        a = R[column::3]
+        d = a[0] * h[0]
+        d = d + a[1] * h[1]
+        d = d + a[2] * h[2]
+        along = d * h
+        w = a - along
+        n2 = w[0] * w[0]
+        n2 = n2 + w[1] * w[1]
+        n2 = n2 + w[2] * w[2]
+        if not n2 < 1e-6:
+            break
+    u = w / np.sqrt(n2)
+    v = np.array([h[1] * u[2] - h[2] * u[1], h[2] * u[0] - h[0] * u[2], h[0] * u[1] - h[1] * u[0]], f8)
+    E = np.stack([u, v, h])
+    c = (f8(0.0) + (lo - (res - 1.0) / 2.0)) * vs  # QueryBox::worldPoint of box voxel (0, 0, 0)
+    p0 = np.empty(3, f8)
+    for i in range(3):
+        q = R[3 * i] * c[0]
+        q = q + R[3 * i + 1] * c[1]
+        q = q + R[3 * i + 2] * c[2]
+        p0[i] = q + t[i]
+    M, g = np.empty((3, 3), f8), np.empty(3, f8)
+    for j in range(3):
+        for k in range(3):
+            m = E[j, 0] * R[k]
+            m = m + E[j, 1] * R[3 + k]
+            m = m + E[j, 2] * R[6 + k]
+            M[j, k] = m * vs
+        q = E[j, 0] * p0[0]
+        q = q + E[j, 1] * p0[1]
+        q = q + E[j, 2] * p0[2]
+        g[j] = q
+    A, mn, dims = np.empty((3, 4), f8), np.empty(2, f8), []
+    corners = np.array([[size[k] - 0.5 if (n >> k) & 1 else -0.5 for k in range(3)] for n in range(8)], f8)
+    for j in range(2):
+        A[j, :3] = M[j] / cell
+        a = g[j] / cell
+        q = A[j, 0] * corners[:, 0]
+        q = q + A[j, 1] * corners[:, 1]
+        q = q + A[j, 2] * corners[:, 2]
+        q = q + a
+        mn[j] = q.min()
+        A[j, 3] = a - mn[j]
+        n = np.floor(q.max() - mn[j]) + 1.0
+        if not n <= _GROUND_MAX_AXIS:
+            raise ValueError(f"ground_frame: the map has more than {_GROUND_MAX_AXIS} cells on an axis")
+        dims.append(int(n))
+    A[2, :3] = M[2] / bin
+    z0 = h[0] * ref[0]
+    z0 = z0 + h[1] * ref[1]
+    z0 = z0 + h[2] * ref[2]
+    z0 = z0 + band_lo
+    above = g[2] - z0
+    A[2, 3] = above / bin
+    span = band_hi - band_lo
+    bins = np.ceil(span / bin)
+    if not bins >= 1:
+        raise ValueError("ground_frame: the height band holds no bin")
+    if not bins <= _GROUND_MAX_BINS:
+        raise ValueError(f"ground_frame: more than {_GROUND_MAX_BINS} height bins")
+    ou, ov = mn[0] * cell, mn[1] * cell
+    pose = np.empty(12, f8)
+    pose[0:9:3], pose[1:9:3], pose[2:9:3] = u, v, h
+    o = u * ou
+    o = o + v * ov
+    o = o + h * z0
+    pose[9:] = o
+    return A.astype(np.float32), dims[0], dims[1], int(bins), pose
+
+
+_GROUND_MAX_AXIS, _GROUND_MAX_BINS = 2048, 256
+
+
+def ground_frame_aligned(G):
+    """Is up along a box axis to within float rounding of the frame: in every row of G[:, :3] all entries but the
+    largest are at most 2^-20 of it.  Only then cells and bins below two voxels leave no holes in the columns."""
+    G = np.abs(np.asarray(G, np.float32).reshape(3, 4)[:, :3])
+    return all(int((row > row.max() * np.float32(2.0 ** -20)).sum()) == 1 for row in G)
+
+
+class _GroundFrame:
+    """Ground coordinates of a ground map: pose (12,) f64 "ground metres -> world", cell and bin in metres."""
+
+    def __init__(self, pose, cell, bin):
+        pose = np.asarray(pose, np.float64)
+        self.R, self.o = pose[:9].reshape(3, 3), pose[9:]
+        self.cell, self.bin = np.float64(cell), np.float64(bin)
+
+    def world(self, cu, cv, ch):
+        """Ground metres -> world (n, 3) f64: ((o + u cu) + v cv) + h ch per component."""
+        cu, cv, ch = (np.asarray(a, np.float64) for a in (cu, cv, ch))
+        out = []
+        for i in range(3):
+            q = self.o[i] + self.R[i, 0] * cu
+            q = q + self.R[i, 1] * cv
+            q = q + self.R[i, 2] * ch
+            out.append(q)
+        return np.stack(np.broadcast_arrays(*out), axis=-1)
+
+    def to_cells(self, points):
+        """World points -> the (u, v) cells they lie over, (n, 2) i32; -1 in a coordinate that is not finite."""
+        d = np.asarray(points, np.float64).reshape(-1, 3) - self.o
+        with np.errstate(invalid="ignore"):
+            c = np.stack([np.floor(((d[:, 0] * self.R[0, k] + d[:, 1] * self.R[1, k]) + d[:, 2] * self.R[2, k]) / self.cell)
+                          for k in range(2)], axis=1)
+        return np.where(np.isfinite(c), np.clip(c, -2.0 ** 31, 2.0 ** 31 - 1), -1).astype(np.int64).astype(np.int32)
 
 
 def look_at(eye, target, up=(0.0, -1.0, 0.0)):
@@ -1347,6 +1501,149 @@ class Fusion:
             out.append(r)
         return out
 
+    def ground_map(self, box=None, size=None, up=None, cell=None, bin=None, band=(-1.5, 0.5), reference=None,
+                   robot_height=0.3, max_step=0.05, exclude=()):
+        """Where can a robot drive: a 2-D traversability map with a floor height per cell, projected on
+        the device from the occupancy classes of a box of the background -- None, ((x, y, z) lo, (x, y, z) size) or
+        "camera" with `size`, as for distance_field -- with every live object not in `exclude` stamped as occupied.
+        up: the world direction that is up (None: minus the background's y axis in the world frame, the OpenCV camera
+        convention at the first pose).  cell, bin (metres; None: two voxels): the side of a ground cell and the height
+        of a bin; below two voxels a slot can miss every voxel centre of a tilted lattice, so smaller values are refused
+        unless up is along a box axis.  band = (lo, hi) metres relative to `reference` (a world point; None: the camera
+        position) along up: the heights that are looked at.  Per cell the column of height bins is OCCUPIED where any
+        occupied voxel falls into the bin, FREE where a free one and no occupied one does; the floor is the lowest
+        occupied bin with ceil(robot_height / bin) free bins above it, and a cell whose floor differs from a
+        neighbour's by more than floor(max_step / bin) bins is an obstacle.  THE NUMERIC DEFAULTS ARE POLICY, NOT
+        MEASUREMENTS: a band from 1.5 m below to 0.5 m above the camera, a robot 0.3 m high that climbs 5 cm.
+        Returns a dict: classes (H, W) u8 (0 free: a floor the robot can stand on; 1 occupied: a step, or matter
+        without a floor; 2 unknown); floor, top, clear, levels (H, W) i16 (-1 / -1 / 0 / 0 without); height_m (H, W)
+        f32, the top face of the floor bin relative to the reference along up, NaN without a floor; frame = (G (3, 4)
+        f32, W, H, B); ground_pose (12,) f64 (R row-major with the ground axes as columns, then t; ground metres ->
+        world); cell, bin, band, up, reference, robot_bins, max_step_bins, box; cells, the raw records; cell_world(u, v): the world
+        points (n, 3) f32 of the cells' centres at their floor height, float64 rounded once, NaN without a floor.  The
+        classes stay on the device for ground_plan().  Changes nothing of the session; refused on the sharded path."""
+        from ._lib import GROUND_CELL_DTYPE
+        box = self._resolve_box("ground_map", box, size)
+        vs = float(np.float32(self.params.bg_voxel_size))
+        bg_R, bg_t = self.background_pose()
+        up = -bg_R[:, 1].astype(np.float64) if up is None else np.asarray(up, np.float64).reshape(3)
+        cell = 2.0 * vs if cell is None else float(cell)
+        bin = 2.0 * vs if bin is None else float(bin)
+        ref = np.ascontiguousarray(self.pose(0)[1] if reference is None else reference, np.float64).reshape(3)
+        up = np.ascontiguousarray(up)
+        robot_bins, step_bins = ground_bins(robot_height, max_step, bin)
+        lo, sz = box if box is not None else ((0, 0, 0), tuple(self.params.bg_res))
+        G, W, H, B, _ = ground_frame(lo, sz, self.params.bg_res, vs, bg_R, bg_t, up, cell, bin, ref, band)
+        if (cell < 2.0 * vs or bin < 2.0 * vs) and not ground_frame_aligned(G):
+            raise ValueError("ground_map: cells and bins below two voxels need an up along a box axis")
+        lo_arg, size_arg, ex, n_ex = _box_args(box, exclude)
+        lo_out, size_out = (C.c_int32 * 3)(), (C.c_int32 * 3)()
+        frame, pose = np.zeros(15, np.int32), np.zeros(12, np.float64)
+        cells, classes = np.zeros((H, W), np.dtype(GROUND_CELL_DTYPE)), np.zeros((H, W), np.uint8)
+        _check("emf_fusion_ground_map",
+               load().emf_fusion_ground_map(self._h, lo_arg, size_arg, ex, n_ex, up.ctypes.data, cell, bin, ref.ctypes.data,
+                                            float(band[0]), float(band[1]), robot_bins, step_bins, lo_out, size_out,
+                                            frame.ctypes.data, pose.ctypes.data, cells.ctypes.data, classes.ctypes.data, H * W))
+        G_out = frame[:12].view(np.float32).reshape(3, 4).copy()
+        assert (int(frame[12]), int(frame[13])) == (W, H), "the frame on the host and the session's disagree"
+        gf = _GroundFrame(pose, cell, bin)
+        floor = cells["floor"].copy()
+        has = floor >= 0
+        top_face = (floor.astype(np.float64) + 1.0) * np.float64(bin)
+        height = np.where(has, np.float64(band[0]) + top_face, np.nan).astype(np.float32)
+
+        def cell_world(u, v):
+            u, v = np.asarray(u, np.int64).reshape(-1), np.asarray(v, np.int64).reshape(-1)
+            inside = (u >= 0) & (u < W) & (v >= 0) & (v < H)
+            f = np.where(inside, floor[np.clip(v, 0, H - 1), np.clip(u, 0, W - 1)], -1)
+            ch = np.where(f >= 0, (f.astype(np.float64) + 1.0) * np.float64(bin), np.nan)
+            return gf.world((u.astype(np.float64) + 0.5) * np.float64(cell), (v.astype(np.float64) + 0.5) * np.float64(cell),
+                            ch).astype(np.float32)
+
+        return dict(classes=classes, floor=floor, top=cells["top"].copy(), clear=cells["clear"].copy(),
+                    levels=cells["levels"].copy(), height_m=height, frame=(G_out, W, H, int(frame[14])), ground_pose=pose,
+                    cell=cell, bin=bin, band=(float(band[0]), float(band[1])), robot_bins=robot_bins, max_step_bins=step_bins,
+                    box=(tuple(lo_out), tuple(size_out)), cells=cells, cell_world=cell_world, up=up, reference=ref)
+
+    def ground_plan(self, goals="frontiers", start=None, robot_radius=0.0, through_unknown=False, min_cells=8,
+                    **ground_map_args):
+        """Path planning on the ground: ground_map(**ground_map_args), then the existing 2-D entries
+        on its (1, H, W) classes where they lie on the device -- the capped distance transform from the occupied cells
+        for robot_radius (metres, rounded up to whole cells), the frontiers (clusters of at least min_cells cells) for
+        goals="frontiers", the cost-to-go from `start` (None: the cell under the camera, clipped to the map; else (n, 3)
+        world points) with a start bubble of max(radius, 1) cells, and the paths.  goals: "frontiers" or (n, 3) world
+        points, each taken to the cell it lies over.  Returns what plan() returns with cells (u, v, 0) for voxels --
+        goals (voxel, reachable, cost, length_m = (faces + sqrt 2 edges) * cell, steps, path_vox, path_world: the
+        cells' centres at their floor height, NaN where a path crosses a cell without a floor), start_voxels,
+        start_radius_voxels, clearance_voxels, converged, rounds, n_finite, n_starts, and with "frontiers" clusters and
+        frontiers -- plus ground, the dict of ground_map()."""
+        from . import ops
+        from ._lib import FRONTIER_KEPT
+        from .devmem import DeviceView
+        if isinstance(goals, str) and goals != "frontiers":
+            raise ValueError('ground_plan: goals is "frontiers" or an (n, 3) array of world points')
+        gm = self.ground_map(**ground_map_args)
+        H, W = gm["classes"].shape
+        gf = _GroundFrame(gm["ground_pose"], gm["cell"], gm["bin"])
+        ptr = C.c_void_p()
+        _check("emf_fusion_ground_classes_ptr", load().emf_fusion_ground_classes_ptr(self._h, C.byref(ptr), None))
+        classes = DeviceView(ptr.value, (1, H, W), np.uint8)
+        radius = _metres_to_voxels(robot_radius, gm["cell"])
+        cap = min(radius, 4095)
+        d2 = ops.distance_transform(classes, site_mask=2, cap=cap) if radius > 0 else None
+        min_d2 = cap * cap
+        found = None
+        if isinstance(goals, str):
+            _, records, counts = ops.frontiers(classes, d2=d2, min_d2=min_d2, min_voxels=int(min_cells))
+            order = sorted(range(len(records)), key=lambda k: (-int(records[k]["count"]), int(records[k]["label"])))
+            records = records[order] if len(records) else records
+            goal_cells = records["rep"].astype(np.int32).reshape(-1, 3)
+            clusters = []
+            for r in records:
+                rep, mean = r["rep"], r["sum"].astype(np.float64) / max(int(r["count"]), 1)
+                clusters.append(dict(label=int(r["label"]), count=int(r["count"]), lo=tuple(int(v) for v in r["lo"]),
+                                     hi=tuple(int(v) for v in r["hi"]), sum=tuple(int(v) for v in r["sum"]),
+                                     rep=tuple(int(v) for v in rep), rep_world=gm["cell_world"](rep[0], rep[1])[0],
+                                     centroid_cells=mean[:2]))
+            found = dict(clusters=clusters, kept=counts[FRONTIER_KEPT], n_clusters=counts[1], n_voxels=counts[2], records=records)
+        else:
+            uv = gf.to_cells(goals)
+            goal_cells = np.concatenate([uv, np.zeros((len(uv), 1), np.int32)], axis=1)
+        if start is None:
+            uv = np.clip(gf.to_cells(self.pose(0)[1]).astype(np.int64), 0, np.array([W - 1, H - 1])).astype(np.int32)
+        else:
+            uv = gf.to_cells(start)
+        start_cells = np.concatenate([uv, np.zeros((len(uv), 1), np.int32)], axis=1)
+        seed_radius = max(radius, 1)
+        cost = ops.plan_cost(classes, start_cells, d2=d2, min_d2=min_d2, traverse_mask=1 | (4 if through_unknown else 0),
+                             seed_radius=seed_radius)
+        n_goals = len(goal_cells)
+        if n_goals:
+            paths, lengths, goal_cost = ops.plan_paths(cost, goal_cells)
+        else:
+            paths, lengths, goal_cost = np.zeros((0, 0), np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint32)
+        counters = cost.counters.numpy()
+        records = []
+        for g in range(n_goals):
+            k = max(int(lengths[g]), 0)
+            lin = paths[g, :k].astype(np.int64)
+            vox = np.stack([lin % W, lin // W, np.zeros_like(lin)], axis=1).astype(np.int32)
+            hops = np.abs(np.diff(vox[:, :2].astype(np.int64), axis=0)).sum(axis=1)
+            faces, edges = int((hops == 1).sum()), int((hops == 2).sum())
+            r = dict(found["clusters"][g]) if found is not None else {}
+            r.update(voxel=tuple(int(v) for v in goal_cells[g]), reachable=k > 0, cost=int(goal_cost[g]),
+                     length_m=(faces + np.sqrt(2.0) * edges) * np.float64(gm["cell"]), steps=(faces, edges, 0), path_vox=vox,
+                     path_world=gm["cell_world"](vox[:, 0], vox[:, 1]))
+            records.append(r)
+        if found is not None:  # reachable first, cheapest first, as plan() orders them
+            records = sorted(records, key=lambda r: (not r["reachable"], r["cost"] if r["reachable"] else 0))
+        out = dict(goals=records, start_voxels=start_cells, start_radius_voxels=seed_radius, clearance_voxels=radius,
+                   converged=bool(counters[0]), rounds=int(counters[1]), n_finite=int(counters[2]), n_starts=int(counters[3]),
+                   ground=gm)
+        if found is not None:
+            out.update(clusters=records, frontiers=found)
+        return out
+
     def last_motion_masks(self):
         """The proposals of the last processed frame: ((H, W) i32 image of proposal ranks, -1 where none is, list of
         dicts {label, area, x0, y0, x1, y1} by rank).  Empty / all -1 if the frame proposed nothing."""
@@ -1544,7 +1841,9 @@ class Fusion:
     def setup_output(self, exp_frame_meshes=False, exp_vols=False, exp_world_mesh=False, exp_distance_field=False,
                      distance_cap=0.0, distance_unknown_is_obstacle=False, exp_frontiers=False, frontier_min_voxels=8,
                      frontier_clearance=0.0, exp_plan=False, plan_clearance=0.0, plan_through_unknown=False,
-                     exp_distance_nearest=False, exp_plan_shortcut=0, exp_object_shapes=False):
+                     exp_distance_nearest=False, exp_plan_shortcut=0, exp_object_shapes=False, exp_ground_map=False,
+                     ground_up=None, ground_cell=None, ground_bin=None, ground_band=(-1.5, 0.5), ground_robot_height=0.3,
+                     ground_max_step=0.05):
         """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
         the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
         the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh();
@@ -1560,7 +1859,12 @@ class Fusion:
         exp_plan_shortcut=W > 0 (needs exp_plan): plan.txt carries one extra "waypoints n i_0 .. i_(n-1)" line per
         reachable goal, plan(shortcut=W) of its path (include/emf_fusion.h emf_fusion_set_plan_shortcut_output);
         exp_object_shapes: write_results also writes shapes.txt, one line per live object in id order: the integers of
-        object_shapes(), then the world-frame box in %.9g (include/emf_fusion.h emf_fusion_set_shape_output)."""
+        object_shapes(), then the world-frame box in %.9g (include/emf_fusion.h emf_fusion_set_shape_output);
+        exp_ground_map: write_results also writes ground.bin (the W * H class bytes, then the W * H records of four
+        i16) and ground.txt (map size, bins, G and the ground pose) of ground_map() over the whole background with
+        ground_up (None: minus the background's y axis), ground_cell, ground_bin (None: two voxels), ground_band,
+        ground_robot_height and ground_max_step; the reference is the camera position
+        (include/emf_fusion.h emf_fusion_set_ground_output)."""
         if exp_plan_shortcut and not exp_plan:
             raise ValueError("setup_output: exp_plan_shortcut adds lines to plan.txt and needs exp_plan")
         if exp_distance_nearest and not exp_distance_field:
@@ -1585,6 +1889,13 @@ class Fusion:
                    load().emf_fusion_set_plan_shortcut_output(self._h, int(exp_plan_shortcut)))
         if exp_object_shapes:  # off: no new call
             _check("emf_fusion_set_shape_output", load().emf_fusion_set_shape_output(self._h, 1))
+        if exp_ground_map:  # off: no new call
+            up = None if ground_up is None else np.ascontiguousarray(ground_up, np.float64).reshape(3)
+            _check("emf_fusion_set_ground_output",
+                   load().emf_fusion_set_ground_output(self._h, 1, None if up is None else up.ctypes.data,
+                                                       0.0 if ground_cell is None else float(ground_cell),
+                                                       0.0 if ground_bin is None else float(ground_bin), float(ground_band[0]),
+                                                       float(ground_band[1]), float(ground_robot_height), float(ground_max_step)))
 
     def write_results(self, directory: str, volumes: bool = True):
         """poses-*.txt, mesh_bg.ply, mesh_<id>.ply always; tsdfs/*.bin with `volumes` (reference formats)."""

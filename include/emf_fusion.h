@@ -425,6 +425,47 @@ int emf_fusion_shape_frame(const emf_shape_moments_t* moments, emf_shape_frame_t
 int emf_fusion_shape_box(const emf_shape_moments_t* moments, const emf_shape_frame_t* frame, const emf_shape_extents_t* extents,
                          const int32_t res[3], float voxel_size, const float R[9], const float t[3], emf_shape_box_t* box);
 int emf_fusion_set_shape_output(emf_fusion_t* h, int on);
+/* Ground map (include/emf_hip.h "Ground map"; new behaviour, opt-in): where a robot that drives on a
+ * floor can stand -- a 2-D traversability map with a floor height per cell, projected on the device from the occupancy
+ * classes of a box of the background (box_lo / box_size NULL: all of it) with every live object not in exclude_ids
+ * stamped.
+ *   ground_map      up: the world direction that is up; cell, bin: the side of a ground cell and the height of a bin in
+ *                   metres; reference: a world point; (band_lo, band_hi): the height band in metres relative to the
+ *                   reference along up; robot_bins >= 1: the FREE bins a floor needs above it; max_step_bins >= 0: a
+ *                   larger difference between the floors of neighbouring cells is an obstacle.  Outputs, NULL = not
+ *                   wanted: the box, the frame (G, W, H, B), ground_pose (12 doubles: R row-major with the ground axes
+ *                   u, v, h as columns, then t; ground metres -> world), and cells / classes for `capacity` cells each
+ *                   (fewer than W * H with a non-NULL output: EMF_E_ARG; emf_fusion_ground_frame gives W and H before
+ *                   the call, emf_fusion_copy_ground_map copies after it).  The arrays stay on the device as the input
+ *                   of 2-D distance, frontier and plan entries with size (W, H, 1).  One wait.  Changes nothing of the
+ *                   session; EMF_E_ARG on the sharded path.
+ *   copy_ground_map the cells (W * H emf_ground_cell_t) and the classes (W * H bytes, v-major) of the last ground_map.
+ *   ground_classes_ptr  the device pointers of those classes and cells (NULL = not wanted), valid until the next
+ *                   ground_map: what Fusion.ground_plan hands to the 2-D entries of include/emf_hip.h.
+ *   ground_frame    needs no device and no handle: the frame and the ground pose of a box (box_lo, box_size) of a
+ *                   background of resolution bg_res, voxel size and pose (R, t: volume -> world), float64 in the fixed
+ *                   operation order of include/emf_hip.h.  A zero or non-finite up, a cell or bin that is not positive,
+ *                   an empty band: EMF_E_ARG; W or H above EMF_DF_MAX_AXIS or more than EMF_GROUND_MAX_BINS bins:
+ *                   EMF_E_LIMIT.
+ *   set_ground_output  setup_output's exp_ground_map, as an entry of its own: emf_fusion_write_results also writes
+ *                   ground.bin -- the W * H class bytes, then the W * H cell records -- and ground.txt -- a comment
+ *                   line, then "map W H", "bins B robot R step S", "cell c bin b", three lines "G ..." of four values
+ *                   and four lines "pose ..." of three (the rows of R, then t), floats in %.9g -- of the whole
+ *                   background with the given parameters; the reference is the camera position.  on == 0: the set of
+ *                   result files and every byte of them as before. */
+int emf_fusion_ground_map(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], const int32_t* exclude_ids,
+                          int32_t num_exclude, const double up[3], double cell, double bin, const double reference[3],
+                          double band_lo, double band_hi, int32_t robot_bins, int32_t max_step_bins, int32_t lo_out[3],
+                          int32_t size_out[3], emf_ground_frame_t* frame, double ground_pose[12], emf_ground_cell_t* cells,
+                          uint8_t* classes, int64_t capacity);
+int emf_fusion_copy_ground_map(emf_fusion_t* h, emf_ground_cell_t* cells, uint8_t* classes);
+int emf_fusion_ground_classes_ptr(emf_fusion_t* h, void** classes_dev, void** cells_dev);
+int emf_fusion_ground_frame(const int32_t box_lo[3], const int32_t box_size[3], const int32_t bg_res[3], float voxel_size,
+                            const float R[9], const float t[3], const double up[3], double cell, double bin,
+                            const double reference[3], double band_lo, double band_hi, emf_ground_frame_t* frame,
+                            double ground_pose[12]);
+int emf_fusion_set_ground_output(emf_fusion_t* h, int on, const double up[3], double cell, double bin, double band_lo,
+                                 double band_hi, double robot_height, double max_step);
 /* Remember what rolls out (new behaviour, off by default; with it off no launch, no output byte and no
  * checkpoint byte changes).  With the store on, the whole integration tiles (32 x 8 x 8) that a roll moves out of the
  * background go to host memory as the bytes they are, after the slabs are retired; the tiles that a later roll moves

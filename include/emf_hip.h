@@ -1929,6 +1929,99 @@ int emf_hip_shapeMoments(const emf_model_t* models_dev, const int32_t* res_host,
 int emf_hip_shapeExtents(const emf_model_t* models_dev, const int32_t* res_host, int32_t first, int32_t n,
                          const emf_shape_axes_t* frames_dev, emf_shape_extents_t* extents_dev, emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Ground map (new behaviour: DESIGN.md 5.24).  Opt-in; nothing above is touched.  A box of class bytes, as
+ * emf_hip_occupancyClasses + emf_hip_occupancyStampObjects leave it, is projected along a given "up" onto a 2-D lattice
+ * of ground cells with a column of height bins per cell; every column reduces to a floor level, its headroom and a
+ * 2-D class, so that a robot that drives on a floor can use the 2-D paths of the entries above (size = (W, H, 1)).
+ * After one float mapping per voxel everything is integer: the results are pure functions of the inputs, bit for bit.
+ *
+ * Input: classes, dense, (z, y, x) order, x fastest, size = (nx, ny, nz), and an emf_ground_frame_t BY VALUE from host
+ * memory: G, a 3 x 4 row-major map from box voxel to ground coordinates (row 0: u in cells, row 1: v in cells, row 2:
+ * h in height bins), map = (W, H), each in 1 .. EMF_DF_MAX_AXIS, and bins = B in 1 .. EMF_GROUND_MAX_BINS.
+ *
+ * Slot of the voxel (x, y, z), every line a single float32 operation in this order, never contracted:
+ *     q_j = ((G_j0 * float(x) + G_j1 * float(y)) + G_j2 * float(z)) + G_j3        j = u, v, h
+ *     i_j = floorf(q_j)
+ * The voxel is dropped unless 0 <= i_u < W, 0 <= i_v < H and 0 <= i_h < B, compared in float before any cast: a NaN or
+ * an infinity drops the voxel (-0.0 is cell 0).
+ *
+ * Bit columns: per cell c = i_v * W + i_u two bit planes occ and fre of words = (B + 63) / 64 u64 words each, word w
+ * of cell c at index c * words + w, bit i_h & 63 of word i_h >> 6.  An EMF_OCC_OCCUPIED voxel sets its bit of occ, an
+ * EMF_OCC_FREE voxel its bit of fre; EMF_OCC_UNKNOWN and class bytes above 2 set nothing.  EVERY voxel counts, nothing
+ * is sampled: a thin obstacle inside a coarse cell is never missed.  OR does not depend on the order of the voxels.
+ * Slot state: OCC if the occ bit is set; FREE if it is clear and the fre bit is set; UNK otherwise.
+ *
+ * Cell records emf_ground_cell_t for a robot height of R >= 1 bins:
+ *     level k is standable iff slot k is OCC, k + R <= B - 1 and the slots k + 1 .. k + R are all FREE
+ *     floor   the lowest standable level, or -1          top     the highest OCC slot, or -1
+ *     clear   the number of consecutive FREE slots directly above floor, or 0 without one
+ *     levels  the number of standable levels
+ *
+ * 2-D classes, one byte per cell, (1, H, W) order, u fastest, for a largest step of S >= 0 bins:
+ *     floor >= 0   EMF_OCC_FREE, unless one of the eight neighbours INSIDE the map has floor_n >= 0 and
+ *                  |floor - floor_n| > S: then EMF_OCC_OCCUPIED.  A neighbour without a floor constrains nothing.
+ *     floor < 0    EMF_OCC_OCCUPIED if top >= 0, else EMF_OCC_UNKNOWN
+ * The array is a valid input of every class-volume entry above with size = (W, H, 1).
+ *
+ * Holes: the ground lattice is rotated against the voxel lattice; a closed ball of radius sqrt(3) / 2 always holds a
+ * lattice point, so with cells and bins of at least 2 voxels every slot that lies wholly inside the box receives a voxel
+ * centre.  Narrower slots can stay empty and break a FREE run by a spurious UNK unless up is along a box axis.  The
+ * entries take any frame; the layers above refuse narrower slots on a tilted frame.
+ *
+ * The frame on the host (emf_fusion_ground_frame of include/emf_fusion.h; no device): float64, every line a single
+ * operation in this order, sums left to right, no contraction.  Inputs: the query box (lo, the background's resolution
+ * res, voxel size vs and pose R, t: volume -> world, f32 taken to double), up, cell and bin in metres, a reference world
+ * point ref and a band (lo_m, hi_m) in metres relative to ref along up.  The world point of the box voxel b (any real
+ * b) is that of QueryBox::worldPoint:  p_i = (R_i0 * o_0 + R_i1 * o_1 + R_i2 * o_2) + t_i  with
+ * o_j = ((double(lo_j) + b_j) - (double(res_j) - 1) / 2) * vs.
+ *     1  h = up / sqrt(up_0 * up_0 + up_1 * up_1 + up_2 * up_2)            (a zero or non-finite up: EMF_E_ARG)
+ *     2  a = column 0 of R;  d = a_0 * h_0 + a_1 * h_1 + a_2 * h_2;  w_i = a_i - d * h_i;
+ *        n2 = w_0 * w_0 + w_1 * w_1 + w_2 * w_2;  if n2 < 1e-6 the same with a = column 2 of R;  u = w / sqrt(n2)
+ *     3  v = h x u, each component one difference of two products
+ *     4  with E = (u, v, h) as rows:  M_jk = (E_j0 * R_0k + E_j1 * R_1k + E_j2 * R_2k) * vs      per voxel step
+ *        c_j = ((double(lo_j)) - (double(res_j) - 1) / 2) * vs;   p0_i = (R_i0 * c_0 + R_i1 * c_1 + R_i2 * c_2) + t_i
+ *        g_j = E_j0 * p0_0 + E_j1 * p0_1 + E_j2 * p0_2                   ground metres of box voxel (0, 0, 0)
+ *     5  rows j = 0, 1:  A_jk = M_jk / cell,  a_j = g_j / cell;  over the eight corners b_k in {-0.5, size_k - 0.5}, the
+ *        corner index counting x fastest:  s = ((A_j0 * b_0 + A_j1 * b_1) + A_j2 * b_2) + a_j,  mn_j and mx_j their
+ *        minimum and maximum;  G_j3 = a_j - mn_j;  W (j = 0) or H (j = 1) = floor(mx_j - mn_j) + 1, above
+ *        EMF_DF_MAX_AXIS: EMF_E_LIMIT
+ *     6  row 2:  A_2k = M_2k / bin;  z0 = (h_0 * ref_0 + h_1 * ref_1 + h_2 * ref_2) + lo_m;  G_23 = (g_2 - z0) / bin
+ *     7  B = ceil((hi_m - lo_m) / bin); below 1 EMF_E_ARG, above EMF_GROUND_MAX_BINS EMF_E_LIMIT
+ *     8  G = float(A | G_j3): rounded to f32 once
+ * The ground pose "ground coordinates in metres -> world" has the rotation (u, v, h) as COLUMNS and the translation
+ * o_i = u_i * (mn_0 * cell) + v_i * (mn_1 * cell) + h_i * z0 (left to right): the ground point (cu, cv, ch) metres --
+ * cu = (i_u + 0.5) * cell for the centre of cell i_u, ch = (i_h + 1) * bin for the top face of bin i_h -- is the world
+ * point  ((o_i + u_i * cu) + v_i * cv) + h_i * ch.
+ * ---------------------------------------------------------------------------------------------- */
+#define EMF_GROUND_MAX_BINS 256
+
+typedef struct emf_ground_frame {
+    float G[12];    /* 3 x 4 row-major: box voxel -> (u in cells, v in cells, h in bins) */
+    int32_t map[2]; /* W, H */
+    int32_t bins;   /* B */
+} emf_ground_frame_t; /* 60 bytes */
+
+typedef struct emf_ground_cell {
+    int16_t floor, top, clear, levels;
+} emf_ground_cell_t; /* 8 bytes */
+
+/*   groundColumns  classes_dev: the box, only read.  occ_dev, fre_dev: W * H * words u64 each, 8-byte aligned, distinct;
+ *                  zeroed by the call on the stream, then 64-bit integer atomicOr, issued only for known voxels, the
+ *                  lanes of a wave that share a destination word combined first.
+ *   groundCells    one lane per cell; robot_bins = R >= 1.  cells_dev: W * H records.
+ *   groundClasses  one lane per cell; max_step = S >= 0.  classes2d_dev: W * H bytes, distinct from nothing it reads.
+ * A second call into the same buffers gives the same bytes.  Every rejected argument -- a NULL pointer, a misaligned
+ * plane, an axis, a map side or a bin count outside its limits (below 1: EMF_E_ARG, above: EMF_E_LIMIT), more than
+ * 2^31 - 1 voxels (EMF_E_LIMIT), R < 1, S < 0 -- returns its code with nothing enqueued.  Nothing allocates, copies to
+ * the host or waits. */
+int emf_hip_groundColumns(const uint8_t* classes_dev, const int32_t size[3], emf_ground_frame_t frame, uint64_t* occ_dev,
+                          uint64_t* fre_dev, emf_stream_t stream);
+int emf_hip_groundCells(const uint64_t* occ_dev, const uint64_t* fre_dev, const int32_t map[2], int32_t bins,
+                        int32_t robot_bins, emf_ground_cell_t* cells_dev, emf_stream_t stream);
+int emf_hip_groundClasses(const emf_ground_cell_t* cells_dev, const int32_t map[2], int32_t max_step,
+                          uint8_t* classes2d_dev, emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
