@@ -9,7 +9,7 @@
 //                  [--frontiers] [--frontier-min-voxels N] [--frontier-clearance M]
 //                  [--plan] [--plan-clearance M] [--plan-through-unknown] [--plan-shortcut W] [--object-shapes]
 //                  [--ground-map] [--ground-up X,Y,Z] [--ground-cell M] [--ground-bin M] [--ground-band LO,HI]
-//                  [--ground-robot-height M] [--ground-max-step M]
+//                  [--ground-robot-height M] [--ground-max-step M] [--planes] [--planes-angle DEG] [--planes-min-votes N]
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
 //                  [--bg-res R] [--bg-voxel M] [--obj-res R] [--volumes] --out DIR
 //   emfusion_synth --dir BASE/ [--colordir colour] [--depthdir depth] [--intrinsics fx fy cx cy] ... --out DIR
@@ -129,8 +129,16 @@ static bool objectShapesOut = false;
 // the whole background with a floor height per cell; --ground-up X,Y,Z (world frame; default: minus the
 // background's y axis), --ground-cell / --ground-bin M (default: two voxels), --ground-band LO,HI (metres relative to
 // the camera along up), --ground-robot-height M, --ground-max-step M; without --ground-map no output byte changes
+// --ground-up floor: up is the normal of the floor the plane search of DESIGN.md 5.25 finds in the whole background; the
+// run ends with a message where it finds none
 static emf::EMFusion::GroundOutput groundOut;
-static bool groundGiven = false, groundBad = false;
+static bool groundGiven = false, groundBad = false, groundUpFloor = false;
+// --planes (needs --out): writeResults also writes OUT/planes.txt, one line per dominant plane of the whole background
+// ordered by count: kind count, the world normal, d, a point, the thickness in metres and the bounds in voxels
+// (DESIGN.md 5.25); --planes-angle DEG (the alignment gate, default 20), --planes-min-votes N (default: max(50, records /
+// 200)); without --planes no output byte changes
+static emf::EMFusion::PlanesOutput planesOut;
+static bool planesGiven = false;
 // "a,b[,c]" into n doubles; false if it does not hold n numbers
 static bool parseList(const char* text, double* out, int n) {
     char* end = nullptr;
@@ -251,6 +259,8 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     if (planShortcut > 0) emf.setPlanShortcutOutput(planShortcut);
     if (objectShapesOut) emf.setShapeOutput(true);
     if (groundOut.on) emf.setGroundOutput(groundOut);
+    if (groundUpFloor) emf.setGroundUpFloor(true);
+    if (planesOut.on) emf.setPlanesOutput(planesOut);
     set3dView(emf, params, view3d);
     std::vector<uint8_t> rendered(3 * params.frameSize.area());
     const auto t0 = std::chrono::steady_clock::now();
@@ -361,7 +371,11 @@ int main(int argc, char** argv) {
         else if (a == "--distance-nearest") distanceNearest = true;
         else if (a == "--object-shapes") objectShapesOut = true;
         else if (a == "--ground-map") groundOut.on = true;
+        else if (a == "--ground-up" && i + 1 < argc && std::string(argv[i + 1]) == "floor") groundGiven = true, groundUpFloor = true, ++i;
         else if (a == "--ground-up" && i + 1 < argc) groundGiven = true, groundBad |= !parseList(argv[++i], groundOut.up, 3);
+        else if (a == "--planes") planesOut.on = true;
+        else if (a == "--planes-angle" && i + 1 < argc) planesGiven = true, planesOut.angle = std::atof(argv[++i]);
+        else if (a == "--planes-min-votes" && i + 1 < argc) planesGiven = true, planesOut.minVotes = std::atoll(argv[++i]);
         else if (a == "--ground-band" && i + 1 < argc) {
             double band[2] = {0.0, 0.0};
             groundGiven = true, groundBad |= !parseList(argv[++i], band, 2);
@@ -412,9 +426,14 @@ int main(int argc, char** argv) {
         return 2;
     }
     if ((groundGiven && !groundOut.on) || groundBad || (groundOut.on && outDir.empty())) {  // (before any device is touched)
-        std::fprintf(stderr, "usage: emfusion_synth: --ground-up X,Y,Z, --ground-band LO,HI, --ground-cell, --ground-bin, "
+        std::fprintf(stderr, "usage: emfusion_synth: --ground-up X,Y,Z or floor, --ground-band LO,HI, --ground-cell, --ground-bin, "
                              "--ground-robot-height and --ground-max-step need --ground-map, which writes ground.bin and "
                              "ground.txt and needs --out DIR\n");
+        return 2;
+    }
+    if ((planesGiven && !planesOut.on) || (planesOut.on && (outDir.empty() || !(planesOut.angle > 0.0 && planesOut.angle <= 90.0)))) {
+        std::fprintf(stderr, "usage: emfusion_synth: --planes-angle DEG (in (0, 90]) and --planes-min-votes N need --planes, which "
+                             "writes planes.txt and needs --out DIR\n");
         return 2;
     }
     if (motionMasks && !maskDir.empty()) {  // (before any device is touched)
@@ -505,6 +524,8 @@ int main(int argc, char** argv) {
         if (planShortcut > 0) emf.setPlanShortcutOutput(planShortcut);
         if (objectShapesOut) emf.setShapeOutput(true);
         if (groundOut.on) emf.setGroundOutput(groundOut);
+        if (groundUpFloor) emf.setGroundUpFloor(true);
+        if (planesOut.on) emf.setPlanesOutput(planesOut);
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);
 

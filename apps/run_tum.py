@@ -100,7 +100,15 @@ def main():
                     help="also write OUT/ground.bin and OUT/ground.txt: the 2-D traversability map of the whole background "
                          "with a floor height per cell (classes, then records of floor, top, clear, levels)")
     ap.add_argument("--ground-up", dest="ground_up", default=None, metavar="X,Y,Z",
-                    help="with --ground-map: the world direction that is up (default: minus the background's y axis)")
+                    help="with --ground-map: the world direction that is up (default: minus the background's y axis), or "
+                         "'floor': the normal of the floor the plane search finds (the run ends with a message without one)")
+    ap.add_argument("--planes", dest="planes", action="store_true",
+                    help="also write OUT/planes.txt: one line per dominant plane of the whole background ordered by count: kind "
+                         "count, the world normal, d, a point, the thickness in metres and the bounds in voxels")
+    ap.add_argument("--planes-angle", dest="planes_angle", type=float, default=20.0, metavar="DEG",
+                    help="with --planes: the alignment gate in degrees")
+    ap.add_argument("--planes-min-votes", dest="planes_min_votes", type=int, default=None, metavar="N",
+                    help="with --planes: the votes a direction and an offset need (default: max(50, records / 200))")
     ap.add_argument("--ground-cell", dest="ground_cell", type=float, default=None, metavar="M",
                     help="with --ground-map: the side of a ground cell in metres (default: two voxels)")
     ap.add_argument("--ground-bin", dest="ground_bin", type=float, default=None, metavar="M",
@@ -218,7 +226,9 @@ def main():
                      plan_clearance=max(args.plan_clearance, 0.0), plan_through_unknown=args.plan_through_unknown,
                      exp_distance_nearest=args.distance_nearest, exp_plan_shortcut=args.plan_shortcut,
                      exp_object_shapes=args.object_shapes, exp_ground_map=args.ground_map,
-                     ground_up=None if args.ground_up is None else [float(v) for v in args.ground_up.split(",")],
+                     ground_up=None if args.ground_up is None else "floor" if args.ground_up == "floor"
+                     else [float(v) for v in args.ground_up.split(",")],
+                     exp_planes=args.planes, planes_angle=args.planes_angle, planes_min_votes=args.planes_min_votes,
                      ground_cell=args.ground_cell, ground_bin=args.ground_bin,
                      ground_band=[float(v) for v in args.ground_band.split(",")],
                      ground_robot_height=args.ground_robot_height, ground_max_step=args.ground_max_step)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)

@@ -224,6 +224,13 @@ SIGNATURES = {
     "emf_hip_groundColumns": [_FP, _I3, None, _FP, _FP, _STREAM],  # [2]: EmfGroundFrame by value, set below its class
     "emf_hip_groundCells": [_FP, _FP, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _FP, _STREAM],
     "emf_hip_groundClasses": [_FP, C.POINTER(C.c_int32), C.c_int32, _FP, _STREAM],
+    "emf_hip_planeSurfaceScratchBytes": [_I3],
+    "emf_hip_planeSurface": [_FP, _FP, _I3, _I3, _I3, _FP, _FP, C.c_uint32, _FP, _FP, _STREAM],
+    "emf_hip_planeDirections": [_FP, _FP, C.c_uint32, C.c_int32, _FP, _STREAM],
+    "emf_hip_planeOffsets": [_FP, _FP, C.c_uint32, _I3, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_float,
+                             C.c_float, C.c_int32, _FP, _STREAM],
+    "emf_hip_planeAssign": [_FP, _FP, C.c_uint32, _I3, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_float, _FP, _FP,
+                            _STREAM],
 }
 
 
@@ -333,6 +340,11 @@ SHAPE_JACOBI_SWEEPS = 8
 # include/emf_hip.h "Ground map": emf_ground_cell_t (8 bytes)
 GROUND_CELL_DTYPE = [("floor", "<i2"), ("top", "<i2"), ("clear", "<i2"), ("levels", "<i2")]
 GROUND_MAX_BINS = 256
+# include/emf_hip.h "Planes": emf_plane_voxel_t (16 bytes) and emf_plane_moments_t (104)
+PLANE_VOXEL_DTYPE = [("index", "<i4"), ("g", "<f4", 3)]
+PLANE_MOMENTS_DTYPE = [("count", "<u8"), ("sum", "<u8", 3), ("sum2", "<u8", 6), ("lo", "<i4", 3), ("hi", "<i4", 3)]
+PLANE_MAX_K, PLANE_MAX_DIRS, PLANE_MAX_SLOTS, PLANE_MAX_PLANES = 31, 16, 4096, 64
+PLANE_SURFACE, PLANE_NORMALS, PLANE_WRITTEN = 0, 1, 2  # the counters of emf_hip_planeSurface
 RAY_REACHED, RAY_BLOCKED, RAY_LEFT, RAY_OUTSIDE, RAY_INVALID = 0, 1, 2, 3, 4
 FRONTIER_KEPT, FRONTIER_CLUSTERS, FRONTIER_VOXELS = 0, 1, 2
 # include/emf_hip.h "Planning"
@@ -446,6 +458,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.emf_hip_frontierScratchBytes.restype = C.c_size_t
     lib.emf_hip_nearestSiteScratchBytes.restype = C.c_size_t
     lib.emf_hip_planScratchBytes.restype = C.c_size_t
+    lib.emf_hip_planeSurfaceScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateCullScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateDirtyMapBytes.restype = C.c_size_t
     lib.emf_hip_signMapBytes.restype = C.c_size_t

@@ -572,6 +572,54 @@ public:
                                const double ref[3], double bandLo, double bandHi, int robotBins, int maxStepBins,
                                const std::vector<int>& excludeIds);
     const GroundMap& lastGroundMap() const { return gmLast; }
+    /** The result of planes(): the planes ordered by count, the counters of the surface pass and what stays on the device. */
+    struct Planes {
+        QueryBox box;
+        uint32_t counters[4] = {0, 0, 0, 0};  // surface voxels, those with a normal, records written, 0
+        uint32_t minVotes = 0;                // the threshold that was applied
+        std::vector<emf_plane_t> planes;
+        const emf_plane_voxel_t* records = nullptr;  // device, counters[2] records
+        const int16_t* labels = nullptr;             // device, one per record; NULL where no plane was found
+        bool keptLabels = false;
+    };
+    /**
+     * Planes (include/emf_hip.h "Planes"): the dominant planes of a box of the background -- floor, walls,
+     * table tops -- from a vote of the surface voxels' TSDF gradients: direction, offset, then assignment with an integer
+     * least-squares refit.  A plane is the plane of the shell's voxel centres: up to one voxel behind the surface.
+     * Drains the frame as the other queries do; the surface pass skips tiles the background's unseen-tile map marks.
+     * Waits 3 + refine times: the host decisions between the stages are inherent.  Changes nothing of the session and
+     * nothing goes into a checkpoint.  Refused (EMF_E_ARG) on the sharded path.
+     */
+    const Planes& planes(const Vec3i& boxLo, const Vec3i& boxSize, const emf_plane_params_t& params, bool keepLabels = false);
+    const Planes& lastPlanes() const { return pnLast; }
+    /** A plane of planes() in the world frame, with its kind (describePlanes). */
+    struct PlaneWorld {
+        double normal[3] = {0, 0, 0}, point[3] = {0, 0, 0}, d = 0.0;  // normal . x = d; the point is the members' centroid
+        double thicknessM = 0.0;
+        const char* kind = "slope";  // floor, level, ceiling, wall or slope
+    };
+    /**
+     * The planes of a result in the world frame and their kinds; returns the index of the floor or -1.  The normal goes
+     * through the background's rotation, the centroid through QueryBox::worldPoint, d = n . point, all float64, sums left
+     * to right.  The floor is, among planes whose normal is within floorAngle degrees of up (all zero: minus the
+     * background's y axis), the one whose point is lowest along up, ties to the lowest index; the others are level
+     * (within kindAngle of the floor's normal, or of up without a floor), ceiling (of its opposite), wall
+     * (perpendicular within kindAngle) or slope.  pipeline.plane_kinds states the same in Python.
+     */
+    static int describePlanes(const Planes& planes, const double up[3], double floorAngle, double kindAngle,
+                              std::vector<PlaneWorld>& out);
+    /** The parameters of setPlanesOutput. */
+    struct PlanesOutput {
+        bool on = false;
+        double angle = 20.0;    // degrees
+        int64_t minVotes = 0;   // <= 0: the policy of emf_plane_params_t
+    };
+    /** writeResults also writes planes.txt of the whole background (writePlanes); without it no output byte changes. */
+    void setPlanesOutput(const PlanesOutput& p) { expPlanes_ = p; }
+    void writePlanes(const std::string& dir);
+    /** setGroundOutput's up becomes the normal of the floor planes() finds in the whole background (an error where it
+     *  finds none): --ground-up floor. */
+    void setGroundUpFloor(bool on) { expGroundUpFloor_ = on; }
     /** The parameters of setGroundOutput: metres; cell or bin <= 0: two voxels of the background. */
     struct GroundOutput {
         bool on = false;
@@ -1140,6 +1188,13 @@ private:
     GroundMap gmLast;
     DeviceBuffer gmBoxClasses, gmPlanes, gmCells, gmClasses;  // the box's classes, occ + fre, the records, the 2-D classes
     GroundOutput expGround_;         // setGroundOutput
+
+    // ---- planes (planes; EMFusionPlanes.cpp): allocated at first use, never in a checkpoint; behind all existing
+    // members ----
+    Planes pnLast;
+    DeviceBuffer pnRecords, pnLabels, pnScratch, pnSmall;  // the records, their labels, the tiles' counts; counters, moments and votes
+    PlanesOutput expPlanes_;         // setPlanesOutput
+    bool expGroundUpFloor_ = false;  // setGroundUpFloor
 };
 
 /**
@@ -1174,6 +1229,21 @@ std::vector<int32_t> shortcutGreedy(int k, int window, const std::vector<uint8_t
  * valid = 0 and writes nothing else.
  */
 void shapeFrame(const emf_shape_moments_t& mom, emf_shape_frame_t& out);
+/** The host steps of the plane finder (include/emf_hip.h "Planes"): float64 in a fixed operation order, no device. */
+struct PlaneDirection {
+    int bin = 0;
+    uint32_t votes = 0;
+    double n[3] = {0.0, 0.0, 0.0};
+};
+struct PlaneOffsetFrame {
+    double lo = 0.0, invBin = 0.0, shift = 0.0;
+    int64_t slots = 0;
+};
+void planeCellCentre(int bin, int K, double n[3]);
+std::vector<PlaneDirection> planeDirections(const uint32_t* bins, int K, uint32_t minVotes, double separationDeg);
+PlaneOffsetFrame planeOffsetFrame(const double n[3], const int32_t size[3], double binVox);
+std::vector<std::pair<int, uint32_t>> planePeaks(const uint32_t* row, int slots, uint32_t minVotes, int peakGap);
+void planeFit(const emf_plane_moments_t& mom, const double seedN[3], double seedD, emf_plane_t& out);
 /**
  * The box of a model from its frame and its extents along that frame: centre and half extents in voxels, completeness,
  * then metres in the model's own frame and the world frame through its pose (R, t: volume -> world).  Float64 in the

@@ -200,7 +200,15 @@ void EMFusion::writeGround(const std::string& dir) {
     const double voxel = static_cast<double>(background.getVoxelSize());
     const double cell = o.cell > 0.0 ? o.cell : 2.0 * voxel, bin = o.bin > 0.0 ? o.bin : 2.0 * voxel;
     double up[3] = {o.up[0], o.up[1], o.up[2]};
-    if (up[0] == 0.0 && up[1] == 0.0 && up[2] == 0.0) {
+    if (expGroundUpFloor_) {  // --ground-up floor: the normal of the floor the plane search finds
+        const emf_plane_params_t pp{15, 1, EMF_PLANE_MAX_PLANES, 2, 20.0, 0.0, 1.0, 2.0, 0};
+        const Planes& found = planes(Vec3i(0, 0, 0), n, pp, false);
+        std::vector<PlaneWorld> world;
+        const double hint[3] = {0.0, 0.0, 0.0};
+        const int floor = describePlanes(found, hint, 30.0, 10.0, world);
+        if (floor < 0) throw HipError("EMFusion::writeGround: up is the floor's normal and the plane search finds no floor", EMF_E_ARG);
+        for (int i = 0; i < 3; ++i) up[i] = world[static_cast<size_t>(floor)].normal[i];
+    } else if (up[0] == 0.0 && up[1] == 0.0 && up[2] == 0.0) {
         const float* R = background.getPose().rotation().val;
         for (int i = 0; i < 3; ++i) up[i] = -static_cast<double>(R[3 * i + 1]);
     }

@@ -988,6 +988,115 @@ int emf_fusion_set_shape_output(emf_fusion_t* h, int on) {
     return guarded([&] { h->impl->setShapeOutput(on != 0); });
 }
 
+int emf_fusion_planes(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], const emf_plane_params_t* params,
+                      int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3], uint32_t counters[4], uint32_t* min_votes,
+                      emf_plane_t* planes, int32_t capacity, int32_t* count) {
+    REQ(h);
+    if (capacity < 0 || (capacity > 0 && !planes)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_planes: capacity %d", capacity);
+        return EMF_E_ARG;
+    }
+    QueryArgs a;
+    if (const int rc = queryArgs("emf_fusion_planes", h, box_lo, box_size, nullptr, 0, a)) return rc;
+    return guarded([&] {
+        emf_plane_params_t p{15, 1, EMF_PLANE_MAX_PLANES, 2, 20.0, 0.0, 1.0, 2.0, 0};
+        if (params) p = *params;
+        const EMFusion::Planes& r = h->impl->planes(a.lo, a.size, p, true);
+        putBox(r.box, lo_out, size_out, R, t);
+        if (counters) std::copy(r.counters, r.counters + 4, counters);
+        if (min_votes) *min_votes = r.minVotes;
+        if (count) *count = static_cast<int32_t>(r.planes.size());
+        std::copy(r.planes.begin(), r.planes.begin() + std::min<size_t>(r.planes.size(), static_cast<size_t>(capacity)), planes);
+    });
+}
+
+int emf_fusion_set_planes_output(emf_fusion_t* h, int on, double angle_deg, int64_t min_votes, int ground_up_floor) {
+    REQ(h);
+    if (on && !(angle_deg > 0.0 && angle_deg <= 90.0)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_set_planes_output: an angle of %g degrees", angle_deg);
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        EMFusion::PlanesOutput p;
+        p.on = on != 0, p.angle = on ? angle_deg : 20.0, p.minVotes = min_votes;
+        h->impl->setPlanesOutput(p);
+        h->impl->setGroundUpFloor(ground_up_floor != 0);
+    });
+}
+
+int emf_fusion_copy_plane_labels(emf_fusion_t* h, emf_plane_voxel_t* records, int16_t* labels, int64_t capacity) {
+    REQ(h);
+    if (capacity < 0) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_copy_plane_labels: capacity %lld", static_cast<long long>(capacity));
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const EMFusion::Planes& r = h->impl->lastPlanes();
+        if (!r.records) throw HipError("emf_fusion_copy_plane_labels: no planes have been computed", EMF_E_ARG);
+        const size_t n = std::min<size_t>(static_cast<size_t>(capacity), r.counters[2]);
+        Stream& s = h->impl->mainStream();
+        if (records && n) hipCheck(hipMemcpyAsync(records, r.records, n * sizeof(emf_plane_voxel_t), hipMemcpyDeviceToHost, s.get()), "copy_plane_labels (records)");
+        if (labels && n) {
+            if (r.labels) hipCheck(hipMemcpyAsync(labels, r.labels, n * sizeof(int16_t), hipMemcpyDeviceToHost, s.get()), "copy_plane_labels (labels)");
+            else std::fill(labels, labels + n, static_cast<int16_t>(-1));
+        }
+        s.waitForCompletion();
+    });
+}
+
+int emf_fusion_plane_directions(const uint32_t* bins, int32_t K, uint32_t min_votes, double separation_deg, double* dirs,
+                                int32_t* bins_out, uint32_t* votes_out, int32_t* count) {
+    REQ(bins);
+    REQ(dirs);
+    REQ(count);
+    if (K < 1 || K > EMF_PLANE_MAX_K) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_plane_directions: K = %d", K);
+        return K < 1 ? EMF_E_ARG : EMF_E_LIMIT;
+    }
+    return guarded([&] {
+        const std::vector<PlaneDirection> d = planeDirections(bins, K, min_votes, separation_deg);
+        *count = static_cast<int32_t>(d.size());
+        for (size_t k = 0; k < d.size(); ++k) {
+            std::copy(d[k].n, d[k].n + 3, dirs + 3 * k);
+            if (bins_out) bins_out[k] = d[k].bin;
+            if (votes_out) votes_out[k] = d[k].votes;
+        }
+    });
+}
+
+int emf_fusion_plane_offsets(const double n[3], const int32_t box_size[3], double bin_vox, double* lo, int64_t* slots,
+                             double* inv_bin, double* shift, const uint32_t* row, uint32_t min_votes, int32_t peak_gap,
+                             int32_t* peak_slots, uint32_t* peak_votes, int32_t capacity, int32_t* count) {
+    REQ(n);
+    REQ(box_size);
+    if (!(bin_vox > 0.0) || box_size[0] < 1 || box_size[1] < 1 || box_size[2] < 1 || peak_gap < 0 || capacity < 0) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_plane_offsets: a bin that is not positive, an empty box or a negative gap");
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const PlaneOffsetFrame f = planeOffsetFrame(n, box_size, bin_vox);
+        if (lo) *lo = f.lo;
+        if (slots) *slots = f.slots;
+        if (inv_bin) *inv_bin = f.invBin;
+        if (shift) *shift = f.shift;
+        if (!row) return;
+        if (f.slots > EMF_PLANE_MAX_SLOTS) throw HipError("emf_fusion_plane_offsets: more than 4096 slots", EMF_E_LIMIT);
+        const auto peaks = planePeaks(row, static_cast<int>(f.slots), min_votes, peak_gap);
+        if (count) *count = static_cast<int32_t>(peaks.size());
+        for (size_t k = 0; k < peaks.size() && k < static_cast<size_t>(capacity); ++k) {
+            if (peak_slots) peak_slots[k] = peaks[k].first;
+            if (peak_votes) peak_votes[k] = peaks[k].second;
+        }
+    });
+}
+
+int emf_fusion_plane_fit(const emf_plane_moments_t* moments, const double seed_n[3], double seed_d, emf_plane_t* plane) {
+    REQ(moments);
+    REQ(seed_n);
+    REQ(plane);
+    return guarded([&] { planeFit(*moments, seed_n, seed_d, *plane); });
+}
+
 static void copyGround(emf_fusion_t* h, const EMFusion::GroundMap& g, emf_ground_cell_t* cells, uint8_t* classes) {
     if (!g.cells) throw HipError("emf_fusion_copy_ground_map: no ground map has been computed", EMF_E_ARG);
     const size_t n = static_cast<size_t>(g.frame.map[0]) * g.frame.map[1];

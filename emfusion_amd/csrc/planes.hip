@@ -1,0 +1,587 @@
+// planes.hip -- planes: the surface voxels of a box of a volume with their TSDF gradients, the votes of those gradients
+// for a direction and for an offset along given directions, and the assignment of every surface voxel to one of a list
+// of planes with the integer moments of each plane's members (include/emf_hip.h "Planes").
+//
+//   k_pl_surface<false>  one workgroup of 256 lanes per 32 x 8 x 8 tile anchored at the box origin.  tsdf and weights of
+//                        the tile with a one-voxel halo (34 x 10 x 10, taken from the VOLUME, weight 0 outside it) are
+//                        staged in LDS: the 32 voxels of a row as eight 16-byte loads where the row's first voxel is
+//                        16-byte aligned in both arrays, voxel by voxel elsewhere, the two halo columns voxel by voxel.
+//                        A lane owns 8 consecutive voxels of a row, so lane order is the tile's (z, y, x) order.  The
+//                        workgroup's count of records goes to the tile's u32, the two totals to the counters with one
+//                        integer atomic each.  A workgroup whose voxels all lie in tiles the volume's unseen-tile map
+//                        marks "every weight is 0" writes a count of 0 and leaves before it stages anything.
+//   k_pl_scan            one workgroup: the tiles' counts -> exclusive offsets in place, records written -> counters[2].
+//   k_pl_surface<true>   the same walk; a tile without a record or wholly past the capacity leaves at once; the rank of a
+//                        record is the tile's offset plus the workgroup scan of the lanes' counts.  One 16-byte store per
+//                        record.  No atomic decides a position.
+//   k_pl_directions      a workgroup takes 8192 consecutive records into a cube-map histogram in LDS (6 K^2 u32, at most
+//                        23064 bytes) and adds the non-zero bins to the global one.
+//   k_pl_offsets         one lane per record; per direction the destination slot, then a segmented scan over the wave's
+//                        runs of equal destinations and one atomic per run (records are spatially ordered: runs are long).  The
+//                        scan is that of voxel_rays.hip over run numbers, since a destination can come back in a wave.
+//   k_pl_assign          one lane per record; the label, then the ten sums and six bounds per run of equal labels.
+// Every float step is a single float32 operation through the _rn intrinsics, never contracted whatever the build; integer
+// atomics only: every output is a pure function of the inputs.  No scratch memory, no float atomics, no inline assembly.
+#include <cfloat>
+
+#include "common.hpp"
+
+namespace emf_hip {
+namespace {
+
+constexpr int kPlBlock = 256;
+constexpr int kPlTX = 32, kPlTY = 8, kPlTZ = 8;       // the tile, and the tile of the unseen-tile map
+constexpr int kPlHX = kPlTX + 2, kPlHY = kPlTY + 2, kPlHZ = kPlTZ + 2;
+constexpr int kPlRowTasks = 10;                       // eight quads and the two halo voxels of a staged row
+constexpr int kPlScanBlock = 1024;
+constexpr unsigned kPlChunk = 8192;                   // records per workgroup of k_pl_directions
+constexpr unsigned long long kPlMaxTiles = 0xffffffull;
+
+static_assert(sizeof(emf_plane_voxel_t) == 16 && sizeof(emf_plane_moments_t) == 104, "mirrored by emfusion_amd/_lib.py");
+static_assert(6 * EMF_PLANE_MAX_K * EMF_PLANE_MAX_K * sizeof(unsigned) <= 24 * 1024, "the direction histogram lives in LDS");
+
+struct SurfArgs {
+    const float* tsdf;
+    const float* weights;
+    const uint8_t* unseen;  // or NULL
+    emf_plane_voxel_t* records;
+    unsigned* tiles;  // count: the tiles' counts; emit: their exclusive offsets
+    unsigned* counters;
+    I3 res, lo, size;
+    unsigned ntx, nty, ntiles;
+    unsigned capacity;
+};
+
+__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= FLT_MAX; }
+
+// the workgroup's sum of v (all lanes get it) and this lane's exclusive prefix
+__device__ __forceinline__ unsigned block_scan(unsigned v, unsigned& total, unsigned* lds /* [kPlBlock / 64] */) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned up = __shfl_up(inc, o);
+        if (lane >= o) inc += up;
+    }
+    if (lane == 63) lds[wave] = inc;
+    __syncthreads();
+    unsigned before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < kPlBlock / 64; ++w) {
+        const unsigned t = lds[w];
+        if (w < wave) before += t;
+        total += t;
+    }
+    return before + inc - v;
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__(kPlBlock) void k_pl_surface(const SurfArgs a) {
+    __shared__ float st[kPlHZ][kPlHY][kPlHX];
+    __shared__ float sw[kPlHZ][kPlHY][kPlHX];
+    __shared__ unsigned scanLds[kPlBlock / 64];
+    const unsigned b = blockIdx.x;
+    const unsigned tz = b / (a.ntx * a.nty), r = b - tz * a.ntx * a.nty, ty = r / a.ntx, tx = r - ty * a.ntx;
+    const int bx0 = static_cast<int>(tx) * kPlTX, by0 = static_cast<int>(ty) * kPlTY, bz0 = static_cast<int>(tz) * kPlTZ;
+    const int ex = min(kPlTX, a.size.x - bx0), ey = min(kPlTY, a.size.y - by0), ez = min(kPlTZ, a.size.z - bz0);
+    const int vx0 = a.lo.x + bx0, vy0 = a.lo.y + by0, vz0 = a.lo.z + bz0;  // volume coordinates of the tile's origin
+    unsigned base = 0u;
+    if (EMIT) {  // block-uniform
+        base = a.tiles[b];
+        const unsigned next = b + 1u < a.ntiles ? a.tiles[b + 1u] : a.counters[1];
+        if (next == base || base >= a.capacity) return;
+    } else if (a.unseen != nullptr) {  // block-uniform: the map's tiles are anchored at the volume's origin
+        const unsigned mtx = (a.res.x + kPlTX - 1) / kPlTX, mty = (a.res.y + kPlTY - 1) / kPlTY;
+        bool seen = false;
+        for (int mz = vz0 / kPlTZ; mz <= (vz0 + ez - 1) / kPlTZ; ++mz)
+            for (int my = vy0 / kPlTY; my <= (vy0 + ey - 1) / kPlTY; ++my)
+                for (int mx = vx0 / kPlTX; mx <= (vx0 + ex - 1) / kPlTX; ++mx)
+                    seen = seen || a.unseen[(static_cast<size_t>(mz) * mty + my) * mtx + mx] == 0;
+        if (!seen) {
+            if (threadIdx.x == 0) a.tiles[b] = 0u;
+            return;
+        }
+    }
+    // stage: row (ly, lz) of the halo box is the volume row (vy0 + ly - 1, vz0 + lz - 1); what lies outside the volume
+    // has weight 0, which makes it neither free nor observed
+    const long long sy = a.res.x, sz = sy * a.res.y;
+    for (int t = threadIdx.x; t < kPlHZ * kPlHY * kPlRowTasks; t += kPlBlock) {
+        const int row = t / kPlRowTasks, q = t - row * kPlRowTasks;
+        const int lz = row / kPlHY, ly = row - lz * kPlHY;
+        const int vy = vy0 + ly - 1, vz = vz0 + lz - 1;
+        const bool rowIn = vy >= 0 && vy < a.res.y && vz >= 0 && vz < a.res.z;
+        const int lx = q < 8 ? 1 + 4 * q : (q == 8 ? 0 : kPlHX - 1);
+        const int vx = vx0 + lx - 1, count = q < 8 ? 4 : 1;
+        float tv[4] = {0.f, 0.f, 0.f, 0.f}, wv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (rowIn) {
+            const long long i = static_cast<long long>(vz) * sz + static_cast<long long>(vy) * sy + vx;  // used only where inside
+            const float* tp = a.tsdf + i;
+            const float* wp = a.weights + i;
+            if (count == 4 && vx + 3 < a.res.x &&
+                ((reinterpret_cast<uintptr_t>(tp) | reinterpret_cast<uintptr_t>(wp)) & 15u) == 0) {
+                const float4 p = *reinterpret_cast<const float4*>(tp), w = *reinterpret_cast<const float4*>(wp);
+                tv[0] = p.x, tv[1] = p.y, tv[2] = p.z, tv[3] = p.w;
+                wv[0] = w.x, wv[1] = w.y, wv[2] = w.z, wv[3] = w.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (e < count && vx + e >= 0 && vx + e < a.res.x) {
+                        tv[e] = tp[e];
+                        wv[e] = wp[e];
+                    }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (e < count) {
+                st[lz][ly][lx + e] = tv[e];
+                sw[lz][ly][lx + e] = wv[e];
+            }
+    }
+    __syncthreads();
+    // a lane's 8 voxels: x0 .. x0 + 7 of row (y, z); bit e of the masks is voxel x0 + e
+    const int x0 = 8 * static_cast<int>(threadIdx.x & 3u), y = static_cast<int>((threadIdx.x >> 2) & 7u),
+              z = static_cast<int>(threadIdx.x >> 5);
+    unsigned surf = 0u, norm = 0u;
+    if (y < ey && z < ez) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int x = x0 + e;
+            if (x >= ex) continue;
+            const int cx = x + 1, cy = y + 1, cz = z + 1;
+            if (!(sw[cz][cy][cx] > 0.f) || st[cz][cy][cx] > 0.f) continue;  // not solid
+            const float wxm = sw[cz][cy][cx - 1], wxp = sw[cz][cy][cx + 1], wym = sw[cz][cy - 1][cx], wyp = sw[cz][cy + 1][cx],
+                        wzm = sw[cz - 1][cy][cx], wzp = sw[cz + 1][cy][cx];
+            const float txm = st[cz][cy][cx - 1], txp = st[cz][cy][cx + 1], tym = st[cz][cy - 1][cx], typ = st[cz][cy + 1][cx],
+                        tzm = st[cz - 1][cy][cx], tzp = st[cz + 1][cy][cx];
+            const bool anyFree = (wxm > 0.f && txm > 0.f) || (wxp > 0.f && txp > 0.f) || (wym > 0.f && tym > 0.f) ||
+                                 (wyp > 0.f && typ > 0.f) || (wzm > 0.f && tzm > 0.f) || (wzp > 0.f && tzp > 0.f);
+            if (!anyFree) continue;
+            surf |= 1u << e;
+            if (!(wxm > 0.f && wxp > 0.f && wym > 0.f && wyp > 0.f && wzm > 0.f && wzp > 0.f)) continue;
+            const float g0 = __fsub_rn(txp, txm), g1 = __fsub_rn(typ, tym), g2 = __fsub_rn(tzp, tzm);
+            if (!(finite_f(g0) && finite_f(g1) && finite_f(g2))) continue;
+            if (g0 == 0.f && g1 == 0.f && g2 == 0.f) continue;
+            norm |= 1u << e;
+        }
+    }
+    unsigned total;
+    const unsigned before = block_scan(__popc(norm) | (__popc(surf) << 16), total, scanLds);  // both at most 2048
+    if (!EMIT) {
+        if (threadIdx.x == 0) {
+            a.tiles[b] = total & 0xffffu;
+            if (total >> 16) atomicAdd(&a.counters[0], total >> 16);
+            if (total & 0xffffu) atomicAdd(&a.counters[1], total & 0xffffu);
+        }
+        return;
+    }
+    unsigned pos = base + (before & 0xffffu);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        if (!((norm >> e) & 1u)) continue;
+        if (pos < a.capacity) {
+            const int cx = x0 + e + 1, cy = y + 1, cz = z + 1;
+            const float g0 = __fsub_rn(st[cz][cy][cx + 1], st[cz][cy][cx - 1]);
+            const float g1 = __fsub_rn(st[cz][cy + 1][cx], st[cz][cy - 1][cx]);
+            const float g2 = __fsub_rn(st[cz + 1][cy][cx], st[cz - 1][cy][cx]);
+            const int index = ((bz0 + z) * a.size.y + (by0 + y)) * a.size.x + (bx0 + x0 + e);
+            *reinterpret_cast<float4*>(a.records + pos) = make_float4(__int_as_float(index), g0, g1, g2);
+        }
+        ++pos;
+    }
+}
+
+// one workgroup: tiles[b] := sum of tiles[0 .. b); counters[2] := min(total, capacity), counters[3] := 0
+__global__ __launch_bounds__(kPlScanBlock) void k_pl_scan(unsigned* tiles, unsigned ntiles, unsigned* counters, unsigned capacity) {
+    __shared__ unsigned lds[kPlScanBlock / 64];
+    __shared__ unsigned carry;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) carry = 0u;
+    __syncthreads();
+    for (unsigned start = 0; start < ntiles; start += kPlScanBlock) {
+        const unsigned i = start + threadIdx.x;
+        const unsigned v = i < ntiles ? tiles[i] : 0u;
+        unsigned inc = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned up = __shfl_up(inc, o);
+            if (lane >= o) inc += up;
+        }
+        if (lane == 63) lds[wave] = inc;
+        __syncthreads();
+        unsigned before = carry, total = 0u;
+        for (int w = 0; w < kPlScanBlock / 64; ++w) {
+            const unsigned t = lds[w];
+            if (w < wave) before += t;
+            total += t;
+        }
+        if (i < ntiles) tiles[i] = before + inc - v;
+        __syncthreads();
+        if (threadIdx.x == 0) carry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        counters[2] = min(carry, capacity);
+        counters[3] = 0u;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pl_zero(unsigned* words, unsigned n) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) words[i] = 0u;
+}
+
+// ---- votes ------------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ emf_plane_voxel_t load_record(const emf_plane_voxel_t* records, unsigned i) {
+    const float4 v = *reinterpret_cast<const float4*>(records + i);
+    emf_plane_voxel_t r;
+    r.index = __float_as_int(v.x);
+    r.g[0] = v.y, r.g[1] = v.z, r.g[2] = v.w;
+    return r;
+}
+
+struct DirArgs {
+    const emf_plane_voxel_t* records;
+    const unsigned* counters;
+    unsigned capacity;
+    int K;
+    float halfK;
+    unsigned* bins;
+};
+
+__device__ __forceinline__ int cube_cell(float u, int K, float halfK) {
+    const int c = static_cast<int>(floorf(__fmul_rn(__fadd_rn(u, 1.f), halfK)));  // u in [-1, 1]: 0 .. K
+    return min(c, K - 1);
+}
+
+__global__ __launch_bounds__(kPlBlock) void k_pl_directions(const DirArgs a) {
+    __shared__ unsigned h[6 * EMF_PLANE_MAX_K * EMF_PLANE_MAX_K];
+    const unsigned n = min(a.counters[2], a.capacity);
+    const unsigned first = blockIdx.x * kPlChunk;
+    if (first >= n) return;  // block-uniform
+    const unsigned nb = 6u * a.K * a.K;
+    for (unsigned i = threadIdx.x; i < nb; i += kPlBlock) h[i] = 0u;
+    __syncthreads();
+    const unsigned end = min(n - first, kPlChunk) + first;
+    for (unsigned i = first + threadIdx.x; i < end; i += kPlBlock) {
+        const emf_plane_voxel_t r = load_record(a.records, i);
+        const float a0 = fabsf(r.g[0]), a1 = fabsf(r.g[1]), a2 = fabsf(r.g[2]);
+        if (!(finite_f(a0) && finite_f(a1) && finite_f(a2))) continue;
+        int m = 0;
+        float am = a0;
+        if (a1 > am) m = 1, am = a1;
+        if (a2 > am) m = 2, am = a2;
+        if (!(am > 0.f)) continue;
+        const float gm = m == 0 ? r.g[0] : (m == 1 ? r.g[1] : r.g[2]);
+        const float gu = m == 0 ? r.g[1] : (m == 1 ? r.g[2] : r.g[0]);
+        const float gv = m == 0 ? r.g[2] : (m == 1 ? r.g[0] : r.g[1]);
+        const int face = 2 * m + (gm < 0.f ? 1 : 0);
+        const int iu = cube_cell(__fdiv_rn(gu, am), a.K, a.halfK), iv = cube_cell(__fdiv_rn(gv, am), a.K, a.halfK);
+        atomicAdd(&h[(face * a.K + iv) * a.K + iu], 1u);
+    }
+    __syncthreads();
+    for (unsigned i = threadIdx.x; i < nb; i += kPlBlock) {
+        const unsigned v = h[i];
+        if (v) atomicAdd(&a.bins[i], v);
+    }
+}
+
+struct OffArgs {
+    const emf_plane_voxel_t* records;
+    const unsigned* counters;
+    unsigned capacity;
+    int bx, by;
+    int D, S;
+    float cos2, invBin;
+    float n[3 * EMF_PLANE_MAX_DIRS];
+    float shift[EMF_PLANE_MAX_DIRS];
+    unsigned* hist;
+};
+
+// The number of the run of neighbouring lanes with the same key that this lane lies in, counted from lane 0 of the wave.
+// Every lane of the wave must be here.  The same key can come back after another one: run numbers, unlike keys, ascend.
+__device__ __forceinline__ int run_id(int key, int lane) {
+    const int below = __shfl_up(key, 1);
+    const unsigned long long heads = __ballot(lane == 0 || below != key);
+    return __popcll(heads & (~0ull >> (63 - lane)));
+}
+
+__device__ __forceinline__ float dot3(float n0, float n1, float n2, float x, float y, float z) {
+    return __fadd_rn(__fadd_rn(__fmul_rn(n0, x), __fmul_rn(n1, y)), __fmul_rn(n2, z));
+}
+
+// a > 0 && a * a >= cos2 * gg, as computed; a NaN aligns with nothing
+__device__ __forceinline__ bool is_aligned(float a, float gg, float cos2) {
+    return a > 0.f && __fmul_rn(a, a) >= __fmul_rn(cos2, gg);
+}
+
+__global__ __launch_bounds__(kPlBlock) void k_pl_offsets(const OffArgs a) {
+    const unsigned n = min(a.counters[2], a.capacity);
+    if (blockIdx.x * static_cast<unsigned>(kPlBlock) >= n) return;  // block-uniform
+    const unsigned i = blockIdx.x * kPlBlock + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool live = i < n;
+    float g0 = 0.f, g1 = 0.f, g2 = 0.f, x = 0.f, y = 0.f, z = 0.f;
+    if (live) {
+        const emf_plane_voxel_t r = load_record(a.records, i);
+        g0 = r.g[0], g1 = r.g[1], g2 = r.g[2];
+        const int row = r.index / a.bx;
+        x = static_cast<float>(r.index - row * a.bx);
+        z = static_cast<float>(row / a.by);
+        y = static_cast<float>(row - (row / a.by) * a.by);
+    }
+    const float gg = dot3(g0, g1, g2, g0, g1, g2);
+    // every lane of the wave is here: a lane without a vote has destination -1 and adds nothing
+    for (int k = 0; k < a.D; ++k) {
+        const float n0 = a.n[3 * k], n1 = a.n[3 * k + 1], n2 = a.n[3 * k + 2];
+        int dest = -1;
+        if (live && is_aligned(dot3(n0, n1, n2, g0, g1, g2), gg, a.cos2)) {
+            const float s = floorf(__fadd_rn(__fmul_rn(dot3(n0, n1, n2, x, y, z), a.invBin), a.shift[k]));
+            if (s >= 0.f && s < static_cast<float>(a.S)) dest = k * a.S + static_cast<int>(s);
+        }
+        const int run = run_id(dest, lane);
+        unsigned votes = dest >= 0 ? 1u : 0u;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned below = __shfl_up(votes, o);
+            const int belowRun = __shfl_up(run, o);
+            if (lane >= o && belowRun == run) votes += below;  // run numbers ascend: every lane between shares it too
+        }
+        const int above = __shfl_down(run, 1);
+        if (dest >= 0 && (lane == 63 || above != run)) atomicAdd(&a.hist[dest], votes);
+    }
+}
+
+struct AssignArgs {
+    const emf_plane_voxel_t* records;
+    const unsigned* counters;
+    unsigned capacity;
+    int bx, by, bz;
+    int P;
+    float cos2, band;
+    float planes[4 * EMF_PLANE_MAX_PLANES];  // n0, n1, n2, d
+    int16_t* labels;
+    emf_plane_moments_t* moments;
+};
+static_assert(sizeof(AssignArgs) <= 4096, "AssignArgs travels in the kernel arguments");
+
+__global__ __launch_bounds__(256) void k_pl_assign_init(emf_plane_moments_t* moments, int P, int bx, int by, int bz) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= P) return;
+    emf_plane_moments_t m{};
+    m.lo[0] = bx, m.lo[1] = by, m.lo[2] = bz;
+    m.hi[0] = m.hi[1] = m.hi[2] = -1;
+    moments[k] = m;
+}
+
+__global__ __launch_bounds__(kPlBlock) void k_pl_assign(const AssignArgs a) {
+    const unsigned n = min(a.counters[2], a.capacity);
+    if (blockIdx.x * static_cast<unsigned>(kPlBlock) >= n) return;  // block-uniform
+    const unsigned i = blockIdx.x * kPlBlock + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool live = i < n;
+    int label = -1, ix = 0, iy = 0, iz = 0;
+    if (live) {
+        const emf_plane_voxel_t r = load_record(a.records, i);
+        const int row = r.index / a.bx;
+        ix = r.index - row * a.bx;
+        iz = row / a.by;
+        iy = row - iz * a.by;
+        const float x = static_cast<float>(ix), y = static_cast<float>(iy), z = static_cast<float>(iz);
+        const float gg = dot3(r.g[0], r.g[1], r.g[2], r.g[0], r.g[1], r.g[2]);
+        float best = 0.f;
+        for (int k = 0; k < a.P; ++k) {
+            const float n0 = a.planes[4 * k], n1 = a.planes[4 * k + 1], n2 = a.planes[4 * k + 2];
+            if (!is_aligned(dot3(n0, n1, n2, r.g[0], r.g[1], r.g[2]), gg, a.cos2)) continue;
+            const float e = fabsf(__fsub_rn(dot3(n0, n1, n2, x, y, z), a.planes[4 * k + 3]));
+            if (e <= a.band && (label < 0 || e < best)) label = k, best = e;
+        }
+        a.labels[i] = static_cast<int16_t>(label);
+    }
+    if (__ballot(label >= 0) == 0ull) return;  // wave-uniform
+    // count, x, y, z, xx, yy, zz, xy, xz, yz of the run's lanes that are not above this one: at most 64 * 2047^2 < 2^32
+    const unsigned ux = ix, uy = iy, uz = iz, in = label >= 0 ? 1u : 0u;
+    unsigned s[10] = {in, ux, uy, uz, ux * ux, uy * uy, uz * uz, ux * uy, ux * uz, uy * uz};
+    int lo[3] = {ix, iy, iz}, hi[3] = {ix, iy, iz};
+    const int run = run_id(label, lane);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int belowRun = __shfl_up(run, o);       // by every lane, before the test: lane o reads lane 0
+        const bool take = lane >= o && belowRun == run;  // run numbers ascend: every lane between shares it too
+#pragma unroll
+        for (int q = 0; q < 10; ++q) {
+            const unsigned below = __shfl_up(s[q], o);
+            if (take) s[q] += below;
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int bl = __shfl_up(lo[j], o), bh = __shfl_up(hi[j], o);
+            if (take) lo[j] = min(lo[j], bl), hi[j] = max(hi[j], bh);
+        }
+    }
+    const int above = __shfl_down(run, 1);
+    if (label < 0 || (lane != 63 && above == run)) return;  // not the last lane of a run of members
+    emf_plane_moments_t* m = a.moments + label;
+    unsigned long long* w = reinterpret_cast<unsigned long long*>(m);  // count, sum[3], sum2[6]: the record's first ten words
+#pragma unroll
+    for (int q = 0; q < 10; ++q)
+        if (s[q]) atomicAdd(w + q, static_cast<unsigned long long>(s[q]));
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        atomicMin(&m->lo[j], lo[j]);
+        atomicMax(&m->hi[j], hi[j]);
+    }
+}
+
+// ---- host: the checks; nothing is enqueued by them --------------------------------------------------------------
+
+int check_size(const int32_t size[3], const char* who) {
+    if (!size) return fail(EMF_E_ARG, "%s: box_size is NULL", who);
+    for (int i = 0; i < 3; ++i) {
+        if (size[i] < 1) return fail(EMF_E_ARG, "%s: box axis %d has %d voxels", who, i, size[i]);
+        if (size[i] > EMF_DF_MAX_AXIS)
+            return fail(EMF_E_LIMIT, "%s: box axis %d has %d voxels, above %d", who, i, size[i], EMF_DF_MAX_AXIS);
+    }
+    const unsigned long long voxels = static_cast<unsigned long long>(size[0]) * size[1] * static_cast<unsigned long long>(size[2]);
+    if (voxels > 0x7fffffffull) return fail(EMF_E_LIMIT, "%s: a box of %llu voxels, above 2^31 - 1", who, voxels);
+    return EMF_OK;
+}
+
+unsigned long long tiles_of(const int32_t size[3]) {
+    return static_cast<unsigned long long>((size[0] + kPlTX - 1) / kPlTX) * ((size[1] + kPlTY - 1) / kPlTY) *
+           ((size[2] + kPlTZ - 1) / kPlTZ);
+}
+
+// the record list of the three entries that read one
+int check_records(const char* who, const emf_plane_voxel_t* records, const uint32_t* counters, uint32_t capacity) {
+    if (!records || !counters) return fail(EMF_E_ARG, "%s: the records or the counters are NULL", who);
+    if ((reinterpret_cast<uintptr_t>(records) & 15u) || (reinterpret_cast<uintptr_t>(counters) & 3u))
+        return fail(EMF_E_ARG, "%s: misaligned records or counters", who);
+    if (capacity < 1u) return fail(EMF_E_ARG, "%s: a capacity of 0 records", who);
+    if (capacity > 0x7fffffffu) return fail(EMF_E_LIMIT, "%s: a capacity of %u records, above 2^31 - 1", who, capacity);
+    return EMF_OK;
+}
+
+int check_gate(const char* who, float cos2) {
+    if (!(cos2 >= 0.f && cos2 <= 1.f)) return fail(EMF_E_ARG, "%s: cos2 %g outside 0 .. 1", who, static_cast<double>(cos2));
+    return EMF_OK;
+}
+
+void zero(unsigned* words, size_t n, hipStream_t s) {
+    hipLaunchKernelGGL(k_pl_zero, dim3(ceil_div(n, 256)), dim3(256), 0, s, words, static_cast<unsigned>(n));
+}
+
+}  // namespace
+}  // namespace emf_hip
+
+using namespace emf_hip;
+
+extern "C" {
+
+size_t emf_hip_planeSurfaceScratchBytes(const int32_t box_size[3]) {
+    if (!box_size) return 0;
+    for (int i = 0; i < 3; ++i)
+        if (box_size[i] < 1 || box_size[i] > EMF_DF_MAX_AXIS) return 0;
+    const unsigned long long tiles = tiles_of(box_size);
+    return tiles > kPlMaxTiles ? 0 : static_cast<size_t>(tiles) * sizeof(uint32_t);
+}
+
+int emf_hip_planeSurface(const float* tsdf, const float* weights, const int32_t res[3], const int32_t box_lo[3],
+                         const int32_t box_size[3], const uint8_t* unseenTiles, emf_plane_voxel_t* records, uint32_t capacity,
+                         uint32_t* counters, void* scratch, emf_stream_t stream) {
+    if (!tsdf || !weights || !counters || !scratch) return fail(EMF_E_ARG, "planeSurface: tsdf, weights, counters or scratch is NULL");
+    if (!res || !box_lo) return fail(EMF_E_ARG, "planeSurface: res or box_lo is NULL");
+    EMF_TRY(check_size(box_size, "planeSurface"));
+    for (int i = 0; i < 3; ++i)
+        if (res[i] < 1 || box_lo[i] < 0 || box_lo[i] > res[i] - box_size[i])
+            return fail(EMF_E_ARG, "planeSurface: the box [%d, %d + %d) leaves the volume's axis %d of %d voxels", box_lo[i],
+                        box_lo[i], box_size[i], i, res[i]);
+    const unsigned long long voxels = static_cast<unsigned long long>(res[0]) * res[1] * static_cast<unsigned long long>(res[2]);
+    if (voxels > (1ull << 36)) return fail(EMF_E_LIMIT, "planeSurface: volume of %llu voxels exceeds 2^36", voxels);
+    const unsigned long long tiles = tiles_of(box_size);
+    if (tiles > kPlMaxTiles) return fail(EMF_E_LIMIT, "planeSurface: more than 2^24 - 1 tiles");
+    if (capacity > 0u && !records) return fail(EMF_E_ARG, "planeSurface: a capacity of %u records and no records", capacity);
+    if (capacity > 0x7fffffffu) return fail(EMF_E_LIMIT, "planeSurface: a capacity of %u records, above 2^31 - 1", capacity);
+    if (((reinterpret_cast<uintptr_t>(tsdf) | reinterpret_cast<uintptr_t>(weights) | reinterpret_cast<uintptr_t>(counters) |
+          reinterpret_cast<uintptr_t>(scratch)) & 3u) || (reinterpret_cast<uintptr_t>(records) & 15u))
+        return fail(EMF_E_ARG, "planeSurface: misaligned arrays");
+    SurfArgs a{};
+    a.tsdf = tsdf, a.weights = weights, a.unseen = unseenTiles, a.records = records;
+    a.tiles = static_cast<unsigned*>(scratch), a.counters = counters;
+    a.res = i3_from(res), a.lo = i3_from(box_lo), a.size = i3_from(box_size);
+    a.ntx = (box_size[0] + kPlTX - 1) / kPlTX, a.nty = (box_size[1] + kPlTY - 1) / kPlTY;
+    a.ntiles = static_cast<unsigned>(tiles);
+    a.capacity = capacity;
+    const hipStream_t s = as_stream(stream);
+    zero(counters, 4, s);
+    hipLaunchKernelGGL(k_pl_surface<false>, dim3(a.ntiles), dim3(kPlBlock), 0, s, a);
+    hipLaunchKernelGGL(k_pl_scan, dim3(1), dim3(kPlScanBlock), 0, s, a.tiles, a.ntiles, counters, capacity);
+    if (capacity > 0u) hipLaunchKernelGGL(k_pl_surface<true>, dim3(a.ntiles), dim3(kPlBlock), 0, s, a);
+    return launch_status("planeSurface");
+}
+
+int emf_hip_planeDirections(const emf_plane_voxel_t* records, const uint32_t* counters, uint32_t capacity, int32_t K,
+                            uint32_t* bins, emf_stream_t stream) {
+    EMF_TRY(check_records("planeDirections", records, counters, capacity));
+    if (K < 1) return fail(EMF_E_ARG, "planeDirections: %d cells per face side", K);
+    if (K > EMF_PLANE_MAX_K) return fail(EMF_E_LIMIT, "planeDirections: %d cells per face side, above %d", K, EMF_PLANE_MAX_K);
+    if (!bins || (reinterpret_cast<uintptr_t>(bins) & 3u)) return fail(EMF_E_ARG, "planeDirections: the bins are NULL or misaligned");
+    const DirArgs a{records, counters, capacity, K, static_cast<float>(K) / 2.f, bins};
+    const hipStream_t s = as_stream(stream);
+    zero(bins, 6u * K * K, s);
+    hipLaunchKernelGGL(k_pl_directions, dim3(ceil_div(capacity, kPlChunk)), dim3(kPlBlock), 0, s, a);
+    return launch_status("planeDirections");
+}
+
+int emf_hip_planeOffsets(const emf_plane_voxel_t* records, const uint32_t* counters, uint32_t capacity,
+                         const int32_t box_size[3], const float* dirs_host, const float* shift_host, int32_t D, float cos2,
+                         float inv_bin, int32_t S, uint32_t* hist, emf_stream_t stream) {
+    EMF_TRY(check_records("planeOffsets", records, counters, capacity));
+    EMF_TRY(check_size(box_size, "planeOffsets"));
+    if (!dirs_host || !shift_host) return fail(EMF_E_ARG, "planeOffsets: the directions or the shifts are NULL");
+    if (D < 1 || S < 1) return fail(EMF_E_ARG, "planeOffsets: %d directions of %d slots", D, S);
+    if (D > EMF_PLANE_MAX_DIRS) return fail(EMF_E_LIMIT, "planeOffsets: %d directions, above %d", D, EMF_PLANE_MAX_DIRS);
+    if (S > EMF_PLANE_MAX_SLOTS) return fail(EMF_E_LIMIT, "planeOffsets: %d slots, above %d", S, EMF_PLANE_MAX_SLOTS);
+    EMF_TRY(check_gate("planeOffsets", cos2));
+    if (!hist || (reinterpret_cast<uintptr_t>(hist) & 3u)) return fail(EMF_E_ARG, "planeOffsets: the histogram is NULL or misaligned");
+    OffArgs a{};
+    a.records = records, a.counters = counters, a.capacity = capacity;
+    a.bx = box_size[0], a.by = box_size[1];
+    a.D = D, a.S = S, a.cos2 = cos2, a.invBin = inv_bin;
+    std::memcpy(a.n, dirs_host, sizeof(float) * 3 * D);
+    std::memcpy(a.shift, shift_host, sizeof(float) * D);
+    a.hist = hist;
+    const hipStream_t s = as_stream(stream);
+    zero(hist, static_cast<size_t>(D) * S, s);
+    hipLaunchKernelGGL(k_pl_offsets, dim3(ceil_div(capacity, kPlBlock)), dim3(kPlBlock), 0, s, a);
+    return launch_status("planeOffsets");
+}
+
+int emf_hip_planeAssign(const emf_plane_voxel_t* records, const uint32_t* counters, uint32_t capacity,
+                        const int32_t box_size[3], const float* planes_host, int32_t P, float cos2, float band,
+                        int16_t* labels, emf_plane_moments_t* moments, emf_stream_t stream) {
+    EMF_TRY(check_records("planeAssign", records, counters, capacity));
+    EMF_TRY(check_size(box_size, "planeAssign"));
+    if (!planes_host) return fail(EMF_E_ARG, "planeAssign: the planes are NULL");
+    if (P < 1) return fail(EMF_E_ARG, "planeAssign: %d planes", P);
+    if (P > EMF_PLANE_MAX_PLANES) return fail(EMF_E_LIMIT, "planeAssign: %d planes, above %d", P, EMF_PLANE_MAX_PLANES);
+    EMF_TRY(check_gate("planeAssign", cos2));
+    if (!(band >= 0.f)) return fail(EMF_E_ARG, "planeAssign: a band of %g voxels", static_cast<double>(band));
+    if (!labels || !moments) return fail(EMF_E_ARG, "planeAssign: the labels or the moments are NULL");
+    if ((reinterpret_cast<uintptr_t>(labels) & 1u) || (reinterpret_cast<uintptr_t>(moments) & 7u))
+        return fail(EMF_E_ARG, "planeAssign: misaligned labels or moments");
+    AssignArgs a{};
+    a.records = records, a.counters = counters, a.capacity = capacity;
+    a.bx = box_size[0], a.by = box_size[1], a.bz = box_size[2];
+    a.P = P, a.cos2 = cos2, a.band = band;
+    std::memcpy(a.planes, planes_host, sizeof(float) * 4 * P);
+    a.labels = labels, a.moments = moments;
+    const hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(k_pl_assign_init, dim3(1), dim3(256), 0, s, moments, P, a.bx, a.by, a.bz);
+    hipLaunchKernelGGL(k_pl_assign, dim3(ceil_div(capacity, kPlBlock)), dim3(kPlBlock), 0, s, a);
+    return launch_status("planeAssign");
+}
+
+}  // extern "C"

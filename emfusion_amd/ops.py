@@ -2048,3 +2048,95 @@ def ground_map(classes, frame, robot_bins, max_step, stream=None):
     occ, fre = ground_columns(classes, frame, stream=stream)
     cells = ground_cells(occ, fre, frame.bins, robot_bins, stream=stream)
     return cells, ground_classes(cells, max_step, stream=stream)
+
+
+# ---- planes (include/emf_hip.h "Planes") ----------------------------------------------------------
+
+PLANE_VOXEL_DTYPE = np.dtype(_lib.PLANE_VOXEL_DTYPE)
+PLANE_MOMENTS_DTYPE = np.dtype(_lib.PLANE_MOMENTS_DTYPE)
+PLANE_MAX_K, PLANE_MAX_DIRS, PLANE_MAX_SLOTS, PLANE_MAX_PLANES = (_lib.PLANE_MAX_K, _lib.PLANE_MAX_DIRS,
+                                                                  _lib.PLANE_MAX_SLOTS, _lib.PLANE_MAX_PLANES)
+assert PLANE_VOXEL_DTYPE.itemsize == 16 and PLANE_MOMENTS_DTYPE.itemsize == 104
+
+
+def plane_surface_scratch_bytes(size) -> int:
+    return int(_L.emf_hip_planeSurfaceScratchBytes(_i3(size)))
+
+
+def plane_surface(tsdf, weights, box=None, capacity=None, unseen_tiles=None, records=None, counters=None, stream=None):
+    """emf_hip_planeSurface: the surface voxels with a normal of the box (lo, size), both (x, y, z), of (Nz, Ny, Nx) f32
+    tsdf / weights (box None: the whole volume) as PLANE_VOXEL_DTYPE records (index: linear index in the box, g: the
+    central tsdf differences), in the fixed tile order of the header.  capacity None: one record per voxel of the box.
+    unseen_tiles: the volume's map as rebuild_unseen_tiles leaves it, or None; the bytes are the same either way.
+    Returns (records, counters), both on the device: counters = 4 x u32 (surface voxels, those with a normal, records
+    written, 0).  The host does not wait: the entries below read the count from counters (the scratch stays alive as
+    counters.scratch)."""
+    _vol(tsdf, np.float32)
+    assert weights.shape == tsdf.shape and weights.dtype == np.float32
+    res = (tsdf.shape[2], tsdf.shape[1], tsdf.shape[0])
+    lo, size = _box(res, box)
+    if capacity is None:
+        capacity = max(size[0], 0) * max(size[1], 0) * max(size[2], 0)
+    capacity = int(capacity)
+    if records is None and capacity > 0:
+        records = DeviceArray((capacity,), PLANE_VOXEL_DTYPE)
+    assert records is None or (records.dtype == PLANE_VOXEL_DTYPE and records.shape[0] >= capacity)
+    if counters is None:
+        counters = DeviceArray((4,), np.uint32)
+    assert counters.dtype == np.uint32 and counters.shape == (4,)
+    scratch = DeviceArray((max(plane_surface_scratch_bytes(size), 4),), np.uint8)
+    check("emf_hip_planeSurface",
+          _L.emf_hip_planeSurface(_ptr(tsdf), _ptr(weights), _i3(res), _i3(lo), _i3(size), _ptr(unseen_tiles), _ptr(records),
+                                  capacity, _ptr(counters), _ptr(scratch), _stream(stream)))
+    counters.scratch = scratch
+    return records, counters
+
+
+def plane_directions(records, counters, k=15, capacity=None, out=None, stream=None):
+    """emf_hip_planeDirections: the (6, k, k) u32 cube-map histogram (face, v cell, u cell) of the records' gradients."""
+    capacity = records.shape[0] if capacity is None else int(capacity)
+    shape = (6, max(int(k), 1), max(int(k), 1))
+    bins = DeviceArray(shape, np.uint32) if out is None else out
+    assert bins.dtype == np.uint32 and bins.shape == shape and not bins.padded
+    check("emf_hip_planeDirections",
+          _L.emf_hip_planeDirections(_ptr(records), _ptr(counters), capacity, int(k), _ptr(bins), _stream(stream)))
+    return bins
+
+
+def plane_offsets(records, counters, size, dirs, shift, cos2, inv_bin, slots, capacity=None, out=None, stream=None):
+    """emf_hip_planeOffsets: the (D, slots) u32 histogram of the offsets along the D unit directions dirs (D x 3 f32, box
+    voxel coordinates) of the records of a box of shape size (x, y, z) that are aligned with them (cos2: the squared
+    cosine of the gate); slot = floor(n . b * inv_bin + shift[k])."""
+    capacity = records.shape[0] if capacity is None else int(capacity)
+    dirs = np.ascontiguousarray(np.asarray(dirs, np.float32).reshape(-1, 3))
+    shift = np.ascontiguousarray(np.asarray(shift, np.float32).reshape(-1))
+    D = dirs.shape[0]
+    assert shift.shape[0] == D
+    shape = (max(D, 1), max(int(slots), 1))
+    hist = DeviceArray(shape, np.uint32) if out is None else out
+    assert hist.dtype == np.uint32 and hist.shape == shape and not hist.padded
+    fp = C.POINTER(C.c_float)
+    check("emf_hip_planeOffsets",
+          _L.emf_hip_planeOffsets(_ptr(records), _ptr(counters), capacity, _i3(size), dirs.ctypes.data_as(fp),
+                                  shift.ctypes.data_as(fp), D, float(np.float32(cos2)), float(np.float32(inv_bin)), int(slots),
+                                  _ptr(hist), _stream(stream)))
+    return hist
+
+
+def plane_assign(records, counters, size, planes, cos2, band, capacity=None, out=None, stream=None):
+    """emf_hip_planeAssign: per record the index of the plane (planes: P x 4 f32 = n0, n1, n2, d in box voxels) of
+    smallest |n . b - d| among those it is aligned with and within `band` voxels of, -1 for none, and per plane the
+    integer moments of its members.  Returns (labels, moments) on the device: `capacity` i16 of which the first
+    counters[2] are written, and P PLANE_MOMENTS_DTYPE records.  out: (labels, moments) to reuse."""
+    capacity = records.shape[0] if capacity is None else int(capacity)
+    planes = np.ascontiguousarray(np.asarray(planes, np.float32).reshape(-1, 4))
+    P = planes.shape[0]
+    labels, moments = out if out is not None else (DeviceArray((max(capacity, 1),), np.int16),
+                                                   DeviceArray((max(P, 1),), PLANE_MOMENTS_DTYPE))
+    assert labels.dtype == np.int16 and labels.shape[0] >= capacity
+    assert moments.dtype == PLANE_MOMENTS_DTYPE and moments.shape[0] >= P
+    check("emf_hip_planeAssign",
+          _L.emf_hip_planeAssign(_ptr(records), _ptr(counters), capacity, _i3(size), planes.ctypes.data_as(C.POINTER(C.c_float)),
+                                 P, float(np.float32(cos2)), float(np.float32(band)), _ptr(labels), _ptr(moments),
+                                 _stream(stream)))
+    return labels, moments

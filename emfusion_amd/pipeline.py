@@ -178,6 +178,16 @@ def load() -> C.CDLL:
         "emf_fusion_shape_frame": [C.c_void_p, C.c_void_p],
         "emf_fusion_shape_box": [C.c_void_p, C.c_void_p, C.c_void_p, ip, C.c_float, fp, fp, C.c_void_p],
         "emf_fusion_set_shape_output": [vp, C.c_int],
+        "emf_fusion_planes": [vp, ip, ip, C.c_void_p, ip, ip, fp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                              C.POINTER(C.c_int32)],
+        "emf_fusion_copy_plane_labels": [vp, C.c_void_p, C.c_void_p, C.c_int64],
+        "emf_fusion_set_planes_output": [vp, C.c_int, C.c_double, C.c_int64, C.c_int],
+        "emf_fusion_plane_directions": [C.c_void_p, C.c_int32, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_int32)],
+        "emf_fusion_plane_offsets": [C.c_void_p, ip, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_uint32, C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
+        "emf_fusion_plane_fit": [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p],
         "emf_fusion_ground_map": [vp, ip, ip, ip, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_double,
                                   C.c_double, C.c_int32, C.c_int32, ip, ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int64],
@@ -316,6 +326,12 @@ class _BoxFrame:
         self.R, self.t = np.ascontiguousarray(bg_R, np.float64), np.asarray(bg_t, np.float64)
         self.res, self.lo = np.array(list(res), np.float64), np.array(list(lo), np.int64)
         self.voxel = float(voxel)
+
+    def world64(self, vox):
+        """One box voxel (3,), fractional too -> its world point (3,) f64 with the operand order of QueryBox::worldPoint:
+        p_j = (v_j + (lo_j - (res_j - 1) / 2)) * voxel, then ((R_i0 p_0 + R_i1 p_1) + R_i2 p_2) + t_i."""
+        p = (np.asarray(vox, np.float64) + (self.lo - (self.res - 1) / 2.0)) * np.float64(self.voxel)
+        return np.array([((self.R[i, 0] * p[0] + self.R[i, 1] * p[1]) + self.R[i, 2] * p[2]) + self.t[i] for i in range(3)])
 
     def world(self, vox):
         """Box voxels (n, 3), fractional ones too -> world points (n, 3) f32: in float64, rounded once."""
@@ -570,6 +586,136 @@ def shape_box(moments, frame, extents, res, voxel_size, R, t):
            load().emf_fusion_shape_box(m.ctypes.data, f.ctypes.data, e.ctypes.data, (C.c_int32 * 3)(*[int(v) for v in res]),
                                        float(voxel_size), _farr(R, 9), _farr(t, 3), out.ctypes.data))
     return out
+
+
+# include/emf_hip.h "Planes": emf_plane_params_t (56 bytes) and emf_plane_t (176)
+PLANE_PARAMS_DTYPE = np.dtype([("K", "<i4"), ("refine", "<i4"), ("max_planes", "<i4"), ("peak_gap", "<i4"), ("angle_deg", "<f8"),
+                               ("separation_deg", "<f8"), ("bin_vox", "<f8"), ("band_vox", "<f8"), ("min_votes", "<i8")])
+PLANE_DTYPE = np.dtype([("n", "<f8", 3), ("d", "<f8"), ("centroid", "<f8", 3), ("thickness", "<f8"), ("axes", "<f8", 6),
+                        ("eigenvalues", "<f8", 3), ("count", "<u8"), ("lo", "<i4", 3), ("hi", "<i4", 3), ("fitted", "<i4"),
+                        ("label", "<i4")])
+assert PLANE_PARAMS_DTYPE.itemsize == 56 and PLANE_DTYPE.itemsize == 176
+
+
+def _dot3(a, b):
+    """(a0 * b0 + a1 * b1) + a2 * b2 in float64, one operation after the other."""
+    s = np.float64(a[0]) * np.float64(b[0])
+    s = s + np.float64(a[1]) * np.float64(b[1])
+    return s + np.float64(a[2]) * np.float64(b[2])
+
+
+def plane_cell_centre(b, k):
+    """The unit vector (3,) f64 through the centre of bin b of a cube map of k cells per face side."""
+    face, iv, iu = b // (k * k), b // k % k, b % k
+    m = face // 2
+    half = np.float64(k) / np.float64(2.0)
+    c = np.zeros(3, np.float64)
+    c[m] = -1.0 if face % 2 else 1.0
+    c[(m + 1) % 3] = (np.float64(iu) + np.float64(0.5)) / half - np.float64(1.0)
+    c[(m + 2) % 3] = (np.float64(iv) + np.float64(0.5)) / half - np.float64(1.0)
+    return c / np.sqrt(_dot3(c, c))
+
+
+def plane_directions(bins, k, min_votes, separation):
+    """emf_fusion_plane_directions restated in numpy float64 with its operand order (include/emf_hip.h "Planes"), so that
+    both give the same bits; on the host without a device.  The directions of a (6, k, k) u32 cube-map histogram
+    (ops.plane_directions): bins by count descending, ties to the lower bin; a bin of at least min_votes becomes a
+    direction, the normalised centre of its cell, unless its dot with a chosen one exceeds cos(separation degrees); at
+    most 16.  Returns (dirs (n, 3) f64, bins (n,) i32, votes (n,) u32)."""
+    from ._lib import PLANE_MAX_DIRS
+    b = np.asarray(bins, np.uint32).reshape(-1)
+    assert b.size == 6 * int(k) * int(k)
+    order = np.argsort(-b.astype(np.int64), kind="stable")
+    limit = np.cos(np.float64(separation) * np.float64(np.pi) / np.float64(180.0))
+    dirs, which = [], []
+    for i in order:
+        if b[i] < min_votes or len(dirs) == PLANE_MAX_DIRS:
+            break
+        n = plane_cell_centre(int(i), int(k))
+        if any(_dot3(n, c) > limit for c in dirs):
+            continue
+        dirs.append(n)
+        which.append(int(i))
+    return (np.array(dirs, np.float64).reshape(-1, 3), np.array(which, np.int32),
+            b[np.array(which, np.int64)].astype(np.uint32) if which else np.zeros(0, np.uint32))
+
+
+def plane_offsets(n, size, bin=1.0, row=None, min_votes=1, peak_gap=2):
+    """emf_fusion_plane_offsets restated in numpy float64 with its operand order; on the host without a device.  The
+    offset frame of the unit direction n over a box of `size` (x, y, z) voxels -- lo, the minimum of n . corner over the
+    corners of the voxel cubes, the number of slots of `bin` voxels, inv_bin and shift with slot = floor(n . b * inv_bin +
+    shift) -- and, with a row of votes, its peaks [(slot, votes)]: slots by votes descending, ties to the lower slot, at
+    least min_votes, no two within peak_gap slots.  Returns (lo, slots, inv_bin, shift, peaks)."""
+    n = np.asarray(n, np.float64).reshape(3)
+    lo, hi = np.float64(np.inf), np.float64(-np.inf)
+    for c in range(8):
+        b = [np.float64(size[j]) - np.float64(0.5) if (c >> j) & 1 else np.float64(-0.5) for j in range(3)]
+        s = _dot3(n, b)
+        lo, hi = min(lo, s), max(hi, s)
+    slots = int(np.floor((hi - lo) / np.float64(bin))) + 1
+    inv_bin = np.float64(1.0) / np.float64(bin)
+    shift = -lo * inv_bin
+    peaks = []
+    if row is not None:
+        r = np.asarray(row, np.uint32).reshape(-1)[:slots]
+        for i in np.argsort(-r.astype(np.int64), kind="stable"):
+            if r[i] < min_votes:
+                break
+            if all(abs(int(i) - p[0]) > peak_gap for p in peaks):
+                peaks.append((int(i), int(r[i])))
+    return float(lo), slots, float(inv_bin), float(shift), peaks
+
+
+def plane_fit(moments, seed_n, seed_d):
+    """emf_fusion_plane_fit restated in numpy float64; on the host without a device.  One plane (a 0-d array of
+    PLANE_DTYPE, box voxel coordinates) from a record of PLANE_MOMENTS_DTYPE (ops.plane_assign) and its seed: centroid,
+    covariance and Jacobi frame are shape_frame's, called, not restated; the normal is the axis of the smallest
+    eigenvalue turned towards the seed, d = n . centroid, thickness the root of that eigenvalue.  Fewer than 3 members
+    keep the seed (fitted == 0)."""
+    from ._lib import PLANE_MOMENTS_DTYPE, SHAPE_MOMENTS_DTYPE
+    m = np.asarray(moments, np.dtype(PLANE_MOMENTS_DTYPE)).reshape(())
+    seed = np.asarray(seed_n, np.float64).reshape(3)
+    out = np.zeros((), PLANE_DTYPE)
+    out["count"], out["lo"], out["hi"] = m["count"], m["lo"], m["hi"]
+    if int(m["count"]) < 3:
+        out["n"], out["d"] = seed, np.float64(seed_d)
+        return out
+    sm = np.zeros((), np.dtype(SHAPE_MOMENTS_DTYPE))
+    sm["solid"], sm["sum"], sm["sum2"] = m["count"], m["sum"], m["sum2"]
+    fr = shape_frame(sm)
+    a = fr["axes"][6:9]
+    n = -a if _dot3(a, seed) < 0.0 else a.copy()
+    out["n"], out["centroid"], out["eigenvalues"], out["axes"] = n, fr["centroid"], fr["eigenvalues"], fr["axes"][:6]
+    out["d"] = _dot3(n, fr["centroid"])
+    out["thickness"] = np.sqrt(max(np.float64(fr["eigenvalues"][2]), np.float64(0.0)))
+    out["fitted"] = 1
+    return out
+
+
+def plane_kinds(normals, heights, up, floor_angle=30.0, kind_angle=10.0):
+    """(floor, kinds) of planes with world unit normals and centroid heights along `up`.  The floor is, among the planes
+    whose normal is within floor_angle degrees of up, the one whose centroid is lowest along up, ties to the lowest
+    index, or None.  Relative to the floor's normal (to up without a floor): "floor", "level" (within kind_angle),
+    "ceiling" (within kind_angle of the opposite), "wall" (perpendicular within kind_angle), "slope"."""
+    def dot(a, b):
+        return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+    up = [float(v) for v in up]
+    norm = float(np.sqrt(dot(up, up)))
+    up = [up[0] / norm, up[1] / norm, up[2] / norm]
+    cos_floor = float(np.cos(floor_angle * np.pi / 180.0))
+    cos_kind, sin_kind = float(np.cos(kind_angle * np.pi / 180.0)), float(np.sin(kind_angle * np.pi / 180.0))
+    normals = [[float(v) for v in n] for n in normals]
+    floor = None
+    for k, n in enumerate(normals):
+        if dot(n, up) >= cos_floor and (floor is None or heights[k] < heights[floor]):
+            floor = k
+    ref = up if floor is None else normals[floor]
+    kinds = []
+    for k, n in enumerate(normals):
+        c = dot(n, ref)
+        kinds.append("floor" if k == floor else "level" if c >= cos_kind else "ceiling" if c <= -cos_kind
+                     else "wall" if abs(c) <= sin_kind else "slope")
+    return floor, kinds
 
 
 def default_3d_view(params: FusionParams):
@@ -1501,13 +1647,88 @@ class Fusion:
             out.append(r)
         return out
 
+    def planes(self, box=None, size=None, k=15, angle=20.0, separation=None, bin=None, band=None, min_votes=None, refine=1,
+               up_hint=None, floor_angle=30.0, kind_angle=10.0, max_planes=64, labels=False):
+        """What the scene is made of: the dominant planes -- floor, walls, table tops -- of a box of the
+        background: None, ((x, y, z) lo, (x, y, z) size) or "camera" with `size`, as for distance_field.  On the device
+        the surface voxels (solid with a free face neighbour) with their TSDF gradients vote for a direction on a cube
+        map of k cells per face side, then for an offset along each chosen direction in slots of `bin` voxels; every
+        surface voxel whose gradient is within `angle` degrees of a plane's normal and that lies within `band` voxels
+        of it joins the nearest such plane, and the plane is refitted to its members by least squares from integer
+        moments, `refine` + 1 times.  A PLANE IS THE PLANE OF THE SHELL'S VOXEL CENTRES: a solid voxel with a free
+        neighbour lies less than one voxel behind the zero crossing, so the plane sits up to one voxel behind the
+        surface, and nothing corrects that.  ALL NUMERIC DEFAULTS ARE POLICY, NOT MEASUREMENTS: k 15, angle 20 degrees,
+        separation = angle, bin 1 voxel, band 2 voxels, min_votes max(50, records / 200), suppression of 2 slots.
+        Returns a dict: planes, a list of dicts ordered by count -- normal (3,), point (3,) and d in the world frame
+        (normal . x = d, the normal pointing into free space; float64, d rounded once), normal_voxel and d_voxel in box
+        voxels, count, bounds (lo, hi) in box voxels, thickness_m, axes (2, 3) world and extents_m (the roots of the
+        in-plane eigenvalues times the voxel size), area_m2 = count * voxel^2 / max |normal_voxel_j| (AN ESTIMATE from a
+        shell one voxel thick), kind and label; box; counters (surface voxels, with a normal, records kept, 0);
+        min_votes; floor (an index into planes or None) and, with labels=True, records (the surface voxels, PLANE_VOXEL_DTYPE)
+        and labels (bz, by, bx) i16, the `label` of the plane a voxel belongs to, -1 for none.
+        The floor is, among planes whose normal is within floor_angle of up_hint (None: minus the background's y axis,
+        ground_map's own default), the one whose centroid is lowest along up_hint; the others are named relative to its
+        normal: level, ceiling, wall (within kind_angle) or slope.  Waits 3 + refine times.  Changes nothing of the
+        session; refused on the sharded path."""
+        from ._lib import PLANE_VOXEL_DTYPE
+        box = self._resolve_box("planes", box, size)
+        prm = np.zeros((), PLANE_PARAMS_DTYPE)
+        prm["K"], prm["refine"], prm["max_planes"], prm["peak_gap"] = int(k), int(refine), int(max_planes), 2
+        prm["angle_deg"], prm["separation_deg"] = float(angle), 0.0 if separation is None else float(separation)
+        prm["bin_vox"], prm["band_vox"] = 1.0 if bin is None else float(bin), 2.0 if band is None else float(band)
+        prm["min_votes"] = 0 if min_votes is None else int(min_votes)
+        lo_arg, size_arg, _, _ = _box_args(box, ())
+        lo_out, size_out, R, t = _box_outs()
+        counters, votes, count = np.zeros(4, np.uint32), C.c_uint32(0), C.c_int32(0)
+        recs = np.zeros(64, PLANE_DTYPE)
+        _check("emf_fusion_planes",
+               load().emf_fusion_planes(self._h, lo_arg, size_arg, prm.ctypes.data, lo_out, size_out, R, t, counters.ctypes.data,
+                                        C.byref(votes), recs.ctypes.data, 64, C.byref(count)))
+        (blo, bsize), _ = _read_box_outs(lo_out, size_out, R, t)
+        vs = float(np.float32(self.params.bg_voxel_size))
+        bg_R, bg_t = self.background_pose()
+        frame = _BoxFrame(bg_R, bg_t, self.params.bg_res, vs, blo)
+        Rd = bg_R.astype(np.float64)
+        up = -Rd[:, 1] if up_hint is None else np.asarray(up_hint, np.float64).reshape(3)
+
+        def rotate(v):
+            return np.array([(Rd[i, 0] * v[0] + Rd[i, 1] * v[1]) + Rd[i, 2] * v[2] for i in range(3)])
+
+        out = []
+        for r in recs[:count.value]:
+            n_vox = r["n"].copy()
+            n = rotate(n_vox)
+            m = r["centroid"] if r["fitted"] else n_vox * r["d"]  # a point of the plane
+            point = frame.world64(m)
+            out.append(dict(normal=n, point=point, d=float((n[0] * point[0] + n[1] * point[1]) + n[2] * point[2]),
+                            normal_voxel=n_vox, d_voxel=float(r["d"]), count=int(r["count"]),
+                            bounds=(tuple(int(v) for v in r["lo"]), tuple(int(v) for v in r["hi"])),
+                            thickness_m=float(r["thickness"] * vs), axes=np.stack([rotate(r["axes"][:3]), rotate(r["axes"][3:])]),
+                            extents_m=tuple(float(np.sqrt(max(e, 0.0)) * vs) for e in r["eigenvalues"][:2]),
+                            area_m2=float(r["count"] * (vs * vs) / np.abs(n_vox).max()), label=int(r["label"])))
+        heights = [float((p["point"][0] * up[0] + p["point"][1] * up[1]) + p["point"][2] * up[2]) for p in out]
+        floor, kinds = plane_kinds([p["normal"] for p in out], heights, up, floor_angle, kind_angle)
+        for p, kind in zip(out, kinds):
+            p["kind"] = kind
+        res = dict(planes=out, box=(blo, bsize), counters=tuple(int(v) for v in counters), min_votes=int(votes.value), floor=floor)
+        if labels:
+            n = int(counters[2])
+            rec, lab = np.zeros(max(n, 1), np.dtype(PLANE_VOXEL_DTYPE)), np.full(max(n, 1), -1, np.int16)
+            _check("emf_fusion_copy_plane_labels", load().emf_fusion_copy_plane_labels(self._h, rec.ctypes.data, lab.ctypes.data, n))
+            volume = np.full(bsize[0] * bsize[1] * bsize[2], -1, np.int16)
+            volume[rec["index"][:n]] = lab[:n]
+            res["labels"] = volume.reshape(bsize[2], bsize[1], bsize[0])
+            res["records"] = rec[:n]
+        return res
+
     def ground_map(self, box=None, size=None, up=None, cell=None, bin=None, band=(-1.5, 0.5), reference=None,
-                   robot_height=0.3, max_step=0.05, exclude=()):
+                   robot_height=0.3, max_step=0.05, exclude=(), up_hint=None):
         """Where can a robot drive: a 2-D traversability map with a floor height per cell, projected on
         the device from the occupancy classes of a box of the background -- None, ((x, y, z) lo, (x, y, z) size) or
         "camera" with `size`, as for distance_field -- with every live object not in `exclude` stamped as occupied.
         up: the world direction that is up (None: minus the background's y axis in the world frame, the OpenCV camera
-        convention at the first pose).  cell, bin (metres; None: two voxels): the side of a ground cell and the height
+        convention at the first pose; "floor": the normal of the floor that planes(box, size, up_hint=up_hint) finds,
+        ValueError where it finds none).  cell, bin (metres; None: two voxels): the side of a ground cell and the height
         of a bin; below two voxels a slot can miss every voxel centre of a tilted lattice, so smaller values are refused
         unless up is along a box axis.  band = (lo, hi) metres relative to `reference` (a world point; None: the camera
         position) along up: the heights that are looked at.  Per cell the column of height bins is OCCUPIED where any
@@ -1524,6 +1745,13 @@ class Fusion:
         classes stay on the device for ground_plan().  Changes nothing of the session; refused on the sharded path."""
         from ._lib import GROUND_CELL_DTYPE
         box = self._resolve_box("ground_map", box, size)
+        if isinstance(up, str):
+            if up != "floor":
+                raise ValueError('ground_map: up is a world direction, None or "floor"')
+            found = self.planes(box=box, up_hint=up_hint)
+            if found["floor"] is None:
+                raise ValueError('ground_map: up="floor" and planes() finds no floor')
+            up = found["planes"][found["floor"]]["normal"]
         vs = float(np.float32(self.params.bg_voxel_size))
         bg_R, bg_t = self.background_pose()
         up = -bg_R[:, 1].astype(np.float64) if up is None else np.asarray(up, np.float64).reshape(3)
@@ -1843,7 +2071,7 @@ class Fusion:
                      frontier_clearance=0.0, exp_plan=False, plan_clearance=0.0, plan_through_unknown=False,
                      exp_distance_nearest=False, exp_plan_shortcut=0, exp_object_shapes=False, exp_ground_map=False,
                      ground_up=None, ground_cell=None, ground_bin=None, ground_band=(-1.5, 0.5), ground_robot_height=0.3,
-                     ground_max_step=0.05):
+                     ground_max_step=0.05, exp_planes=False, planes_angle=20.0, planes_min_votes=None):
         """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
         the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
         the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh();
@@ -1864,7 +2092,12 @@ class Fusion:
         i16) and ground.txt (map size, bins, G and the ground pose) of ground_map() over the whole background with
         ground_up (None: minus the background's y axis), ground_cell, ground_bin (None: two voxels), ground_band,
         ground_robot_height and ground_max_step; the reference is the camera position
-        (include/emf_fusion.h emf_fusion_set_ground_output)."""
+        (include/emf_fusion.h emf_fusion_set_ground_output); ground_up="floor": up is the normal of the floor that
+        planes() finds in the whole background, and write_results fails where it finds none;
+        exp_planes: write_results also writes planes.txt, one line per plane of planes(angle=planes_angle,
+        min_votes=planes_min_votes) over the whole background ordered by count: kind count, then in %.9g the world
+        normal, d, the point, the thickness in metres, then the bounds in voxels (include/emf_fusion.h
+        emf_fusion_set_planes_output)."""
         if exp_plan_shortcut and not exp_plan:
             raise ValueError("setup_output: exp_plan_shortcut adds lines to plan.txt and needs exp_plan")
         if exp_distance_nearest and not exp_distance_field:
@@ -1889,8 +2122,15 @@ class Fusion:
                    load().emf_fusion_set_plan_shortcut_output(self._h, int(exp_plan_shortcut)))
         if exp_object_shapes:  # off: no new call
             _check("emf_fusion_set_shape_output", load().emf_fusion_set_shape_output(self._h, 1))
+        up_floor = isinstance(ground_up, str)
+        if up_floor and ground_up != "floor":
+            raise ValueError('setup_output: ground_up is a world direction, None or "floor"')
+        if exp_planes or up_floor:  # off: no new call
+            _check("emf_fusion_set_planes_output",
+                   load().emf_fusion_set_planes_output(self._h, int(bool(exp_planes)), float(planes_angle),
+                                                       0 if planes_min_votes is None else int(planes_min_votes), int(up_floor)))
         if exp_ground_map:  # off: no new call
-            up = None if ground_up is None else np.ascontiguousarray(ground_up, np.float64).reshape(3)
+            up = None if ground_up is None or up_floor else np.ascontiguousarray(ground_up, np.float64).reshape(3)
             _check("emf_fusion_set_ground_output",
                    load().emf_fusion_set_ground_output(self._h, 1, None if up is None else up.ctypes.data,
                                                        0.0 if ground_cell is None else float(ground_cell),

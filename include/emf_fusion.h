@@ -425,6 +425,42 @@ int emf_fusion_shape_frame(const emf_shape_moments_t* moments, emf_shape_frame_t
 int emf_fusion_shape_box(const emf_shape_moments_t* moments, const emf_shape_frame_t* frame, const emf_shape_extents_t* extents,
                          const int32_t res[3], float voxel_size, const float R[9], const float t[3], emf_shape_box_t* box);
 int emf_fusion_set_shape_output(emf_fusion_t* h, int on);
+/* Planes (include/emf_hip.h "Planes"; new behaviour, opt-in): the dominant planes of a box of the
+ * background (box_lo / box_size NULL: all of it) -- floor, walls, table tops.  A plane is the plane of the SHELL's voxel
+ * centres: up to one voxel behind the surface, and nothing corrects that.
+ *   planes          params NULL: K 15, refine 1, max_planes 64, peak_gap 2, angle 20 degrees, separation = angle, bins of
+ *                   1 voxel, a band of 2 voxels, min_votes max(50, records / 200) -- policy, not measurements.  Outputs,
+ *                   NULL = not wanted: the box and its pose (box voxel -> world), the four counters of the surface pass,
+ *                   the threshold applied, and up to `capacity` planes ordered by count (ties to the lower label), in BOX
+ *                   VOXEL coordinates; *count is the number found.  Waits 3 + refine times.  At most max(2^16, voxels / 8)
+ *                   records are kept: counters[1] > counters[2] says that the surface held more.
+ *   copy_plane_labels  the records of the last call and their labels (i16, the `label` of a plane, -1: none), the first
+ *                   min(capacity, counters[2]) of them; labels are all -1 where no plane was found.
+ *   plane_directions / plane_offsets / plane_fit   need no device and no handle: the host steps between the stages,
+ *                   float64 in the fixed operation order of include/emf_hip.h.  directions: dirs = 3 doubles, bins_out
+ *                   and votes_out one entry per direction, capacity EMF_PLANE_MAX_DIRS; returns the count in *count.
+ *                   offsets: the frame (lo, S, inv_bin, shift) of one direction and, with a row of S votes, its peaks
+ *                   (slot, votes), at most `capacity`.  fit: one plane from its moments and its seed.
+ * Refused (EMF_E_ARG) on the sharded path; changes nothing of the session and nothing goes into a checkpoint. */
+int emf_fusion_planes(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], const emf_plane_params_t* params,
+                      int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3], uint32_t counters[4], uint32_t* min_votes,
+                      emf_plane_t* planes, int32_t capacity, int32_t* count);
+int emf_fusion_copy_plane_labels(emf_fusion_t* h, emf_plane_voxel_t* records, int16_t* labels, int64_t capacity);
+/*   set_planes_output  setup_output's exp_planes and ground_up="floor", as an entry of its own so that the existing entries
+ *                   keep their signatures.  on: emf_fusion_write_results also writes planes.txt of the whole background
+ *                   (angle_deg in (0, 90], min_votes <= 0: the policy above; the other parameters at their defaults; kinds
+ *                   relative to minus the background's y axis): a comment line, then one line per plane ordered by count:
+ *                   kind count, then in %.9g the world normal (3), d, the point (3), the thickness in metres, then the
+ *                   bounds lo (3) hi (3) in voxels.  ground_up_floor: the ground output (emf_fusion_set_ground_output)
+ *                   takes the normal of the floor the plane search finds as up; write_results fails where there is none.
+ *                   Both off: the set of result files and every byte of them as before. */
+int emf_fusion_set_planes_output(emf_fusion_t* h, int on, double angle_deg, int64_t min_votes, int ground_up_floor);
+int emf_fusion_plane_directions(const uint32_t* bins, int32_t K, uint32_t min_votes, double separation_deg, double* dirs,
+                                int32_t* bins_out, uint32_t* votes_out, int32_t* count);
+int emf_fusion_plane_offsets(const double n[3], const int32_t box_size[3], double bin_vox, double* lo, int64_t* slots,
+                             double* inv_bin, double* shift, const uint32_t* row, uint32_t min_votes, int32_t peak_gap,
+                             int32_t* peak_slots, uint32_t* peak_votes, int32_t capacity, int32_t* count);
+int emf_fusion_plane_fit(const emf_plane_moments_t* moments, const double seed_n[3], double seed_d, emf_plane_t* plane);
 /* Ground map (include/emf_hip.h "Ground map"; new behaviour, opt-in): where a robot that drives on a
  * floor can stand -- a 2-D traversability map with a floor height per cell, projected on the device from the occupancy
  * classes of a box of the background (box_lo / box_size NULL: all of it) with every live object not in exclude_ids

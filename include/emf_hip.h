@@ -2022,6 +2022,147 @@ int emf_hip_groundCells(const uint64_t* occ_dev, const uint64_t* fre_dev, const 
 int emf_hip_groundClasses(const emf_ground_cell_t* cells_dev, const int32_t map[2], int32_t max_step,
                           uint8_t* classes2d_dev, emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Planes (new behaviour: DESIGN.md 5.25).  Opt-in; nothing above is touched.  What the scene is made of: the dominant
+ * planes -- floor, walls, table tops -- of a box [box_lo, box_lo + box_size) of a volume, by a three-stage vote on the
+ * TSDF gradients of its surface voxels: direction, then offset, then assignment with integer moments for a least-squares
+ * refit.  Every float step below is a single float32 operation in the stated order, never contracted whatever the build;
+ * everything after it is integer.  Every output is a pure function of the inputs, bit for bit.
+ * Volumes and boxes are dense, (z, y, x) order, x fastest; a box voxel is b = (x, y, z), its linear index
+ * (z * by + y) * bx + x with box_size = (bx, by, bz).  Box limits are those of emf_hip_occupancyClasses.
+ * WHAT A PLANE IS: the plane of the SHELL's voxel centres.  A solid voxel with a free face neighbour lies less than one
+ * voxel behind the zero crossing, so a plane fitted to these records sits up to one voxel behind the surface.  Nothing
+ * here corrects that.
+ *
+ * Stage 1, surface records.  The rules of emf_hip_shapeMoments without a mask:
+ *     solid(v)    weights[v] > 0 && !(tsdf[v] > 0)                 free(n)   weights[n] > 0 && tsdf[n] > 0
+ *     surface(v)  solid(v) and at least one of the six face neighbours INSIDE THE VOLUME is free
+ *     normal(v)   surface(v), all six face neighbours lie inside the volume and have weights > 0, the three differences
+ *                 g_j = tsdf[v + e_j] - tsdf[v - e_j] (one float32 subtraction each) are finite and not all zero
+ * Neighbours come from the volume, not from the box: the records of a box are exactly those of the whole volume that
+ * fall into it, re-indexed.  g points from solid to free space.
+ * Output: the voxels with a normal as emf_plane_voxel_t, in this fixed order: tiles of 32 x 8 x 8 voxels anchored at the
+ * box origin, partial ones included, in (z, y, x) order of the tiles, then the voxels inside a tile in (z, y, x) order.
+ * Positions come from a count per tile, an exclusive scan and a second pass; no atomic decides a position.  At most
+ * `capacity` records are written: the first `capacity` of that order.
+ *     counters (device, 4 x u32): [0] surface voxels, [1] those with a normal, [2] records written = min([1], capacity),
+ *     [3] 0.  Zeroed and written by the call on the stream.
+ *     scratch: emf_hip_planeSurfaceScratchBytes(box_size) bytes, one u32 per tile (0 for a size beyond the limits);
+ *     contents undefined afterwards.  At most 2^24 - 1 tiles (EMF_E_LIMIT above).
+ *     unseenTiles: NULL or the VOLUME's unseen-tile map (emf_hip_unseenTileBytes(res)).  A workgroup whose voxels all lie
+ *     in tiles marked "every weight is 0" leaves at once; a surface voxel is observed, so that is exact: the bytes are
+ *     the same with the map and without it.
+ *     capacity == 0: records may be NULL, only the counters are written.  capacity <= 2^31 - 1.
+ *
+ * Stage 2a, direction votes.  A cube map with K cells per face side, K in 1 .. EMF_PLANE_MAX_K: 6 K^2 bins of u32.  For
+ * a record with gradient g (a record whose g has a component that is not finite, or is all zero, votes for nothing;
+ * stage 1 writes none):
+ *     m    = the index of the largest |g_j|, ties to the lowest index
+ *     face = 2 m + (g_m < 0)
+ *     u    = g_((m + 1) % 3) / |g_m|,  v = g_((m + 2) % 3) / |g_m|          one IEEE division each
+ *     cell(u) = min(int(floorf((u + 1.f) * h)), K - 1)   with h = float(K) / 2.f formed once on the host
+ *     bin  = (face * K + cell(v)) * K + cell(u)
+ * The bins are zeroed by the call; the histogram is kept in LDS per workgroup and flushed with integer atomics.
+ *
+ * Stage 2b, offset votes.  D unit directions n_k (f32, box voxel coordinates), D in 1 .. EMF_PLANE_MAX_DIRS, with cos2 in
+ * [0, 1], inv_bin, one shift_k per direction and S slots, S in 1 .. EMF_PLANE_MAX_SLOTS.  With (x, y, z) the record's box
+ * voxel as floats:
+ *     a  = (n0 * g0 + n1 * g1) + n2 * g2        gg = (g0 * g0 + g1 * g1) + g2 * g2
+ *     ALIGNED with k iff  a > 0 && a * a >= cos2 * gg   as computed; a NaN aligns with nothing
+ *     slot = floorf(((n0 * x + n1 * y) + n2 * z) * inv_bin + shift_k)
+ * An aligned record votes for hist[k * S + slot] iff 0 <= slot < S, compared in float before any cast, in every
+ * direction it is aligned with.  hist: D * S u32 in device memory, zeroed by the call.  One atomic per run of
+ * neighbouring lanes of a wave with the same destination.
+ *
+ * Stage 3, assignment.  P planes (n_k, d_k) in f32, P in 1 .. EMF_PLANE_MAX_PLANES, with cos2 and a band >= 0 in voxels.
+ *     e_k = ((n0 * x + n1 * y) + n2 * z) - d_k
+ * A record belongs to the plane of smallest |e_k| among those it is ALIGNED with (as above) and for which
+ * |e_k| <= band; ties go to the lowest k.  labels: one i16 per record written by stage 1 (-1: none); labels past
+ * counters[2] are not written.  moments: P records emf_plane_moments_t of integers only, initialised by the call
+ * (count 0, lo = box_size, hi = -1), then per run of equal labels in a wave one integer atomic per quantity.
+ * A second call of any entry into the same buffers gives the same bytes.
+ *
+ * The three entries of stages 2 and 3 read the record count counters[2] on the device, bounded by `capacity` (the
+ * capacity given to stage 1, 1 .. 2^31 - 1): the host does not wait in between.  dirs_host (3 D f32), shift_host (D f32)
+ * and planes_host (4 P f32: n0, n1, n2, d) are HOST arrays, read before the call returns.
+ * Every rejected argument -- a NULL pointer, a misaligned array (records: 16 bytes, moments: 8), a count below 1
+ * (EMF_E_ARG) or above its limit (EMF_E_LIMIT), cos2 outside [0, 1] or NaN, a negative or NaN band -- returns its code
+ * with nothing enqueued.  Nothing allocates, copies to the host or waits.
+ * ---------------------------------------------------------------------------------------------- */
+#define EMF_PLANE_MAX_K 31
+#define EMF_PLANE_MAX_DIRS 16
+#define EMF_PLANE_MAX_SLOTS 4096
+#define EMF_PLANE_MAX_PLANES 64
+
+typedef struct emf_plane_voxel {
+    int32_t index; /* linear index in the box */
+    float g[3];    /* tsdf[v + e_j] - tsdf[v - e_j] */
+} emf_plane_voxel_t; /* 16 bytes */
+
+typedef struct emf_plane_moments {
+    uint64_t count;
+    uint64_t sum[3];     /* sum of x, y, z over the members, BOX voxel coordinates */
+    uint64_t sum2[6];    /* sums of xx, yy, zz, xy, xz, yz: the layout of emf_shape_moments_t */
+    int32_t lo[3], hi[3]; /* bounds of the members; box_size and -1 without one */
+} emf_plane_moments_t;   /* 104 bytes */
+
+/* The host steps between the stages (emf_fusion_plane_directions / _offsets / _fit of include/emf_fusion.h; no device).
+ * Float64, every line a single operation in this order, sums left to right, no contraction:
+ *   directions  bins sorted by count descending, ties to the lower bin.  Greedy: a bin of at least min_votes becomes a
+ *               direction unless its dot with an already chosen one exceeds cos(separation * pi / 180); at most
+ *               EMF_PLANE_MAX_DIRS.  The direction of bin b (face, iv, iu as above, m = face / 2) is the normalised centre
+ *               of its cell: c_m = +1 or -1, c_((m+1)%3) = (iu + 0.5) / (K / 2) - 1, c_((m+2)%3) = (iv + 0.5) / (K / 2) - 1,
+ *               n = c / sqrt((c0 * c0 + c1 * c1) + c2 * c2).
+ *   offsets     per direction, over the eight corners b_j in {-0.5, size_j - 0.5} of the box's voxel cubes (x fastest):
+ *               s = (n0 * b0 + n1 * b1) + n2 * b2, lo and hi their minimum and maximum; S = floor((hi - lo) / bin) + 1
+ *               (above EMF_PLANE_MAX_SLOTS: EMF_E_LIMIT), inv_bin = 1 / bin, shift = -lo * inv_bin; inv_bin and shift are
+ *               rounded to f32 once for stage 2b.  Peaks of a direction's S slots: slots by votes descending, ties to the
+ *               lower slot; a slot of at least min_votes is a peak unless a chosen one lies within peak_gap slots.  The
+ *               offset of a peak is the centre of its slot, d = lo + (slot + 0.5) * bin.  Seed planes ordered by votes,
+ *               ties by (direction, slot), at most max_planes <= EMF_PLANE_MAX_PLANES.
+ *   fit         from a plane's emf_plane_moments_t: centroid m, covariance and Jacobi frame are those of
+ *               emf_fusion_shape_frame (count -> solid, sum, sum2), called, not restated.  n = the axis of the smallest
+ *               eigenvalue, negated where its dot with the seed normal is negative, so that it points into free space;
+ *               d = (n0 * m0 + n1 * m1) + n2 * m2; thickness = sqrt(max(eigenvalue, 0)) in voxels; the two in-plane axes
+ *               and all three eigenvalues are kept.  A plane of fewer than 3 members keeps its seed (fitted = 0).
+ *   rounds      (refine + 1) times: stage 3 with the current planes rounded to f32 once, then the fit of every plane.
+ *   gate        cos2 = float(c * c) with c = cos(angle * pi / 180). */
+typedef struct emf_plane_params {
+    int32_t K;          /* cells per cube-map face side, 1 .. EMF_PLANE_MAX_K */
+    int32_t refine;     /* >= 0 */
+    int32_t max_planes; /* 1 .. EMF_PLANE_MAX_PLANES */
+    int32_t peak_gap;   /* slots, >= 0 */
+    double angle_deg;      /* the alignment gate, (0, 90] */
+    double separation_deg; /* between directions; <= 0: angle_deg */
+    double bin_vox;        /* the width of an offset slot in voxels, > 0 */
+    double band_vox;       /* the assignment band in voxels, >= 0 */
+    int64_t min_votes;     /* <= 0: max(50, records / 200) */
+} emf_plane_params_t; /* 56 bytes */
+
+typedef struct emf_plane {
+    double n[3], d;        /* box voxel coordinates: n . b = d; n points into free space */
+    double centroid[3];    /* of the members (fitted != 0) */
+    double thickness;      /* sqrt of the smallest eigenvalue, voxels */
+    double axes[6];        /* the two in-plane axes, larger eigenvalue first */
+    double eigenvalues[3]; /* descending, voxels^2 */
+    uint64_t count;        /* members */
+    int32_t lo[3], hi[3];  /* their bounds, box voxels */
+    int32_t fitted, label; /* label: the plane's value in the label array */
+} emf_plane_t; /* 176 bytes */
+
+size_t emf_hip_planeSurfaceScratchBytes(const int32_t box_size[3]);
+int emf_hip_planeSurface(const float* tsdf, const float* weights, const int32_t res[3], const int32_t box_lo[3],
+                         const int32_t box_size[3], const uint8_t* unseenTiles, emf_plane_voxel_t* records, uint32_t capacity,
+                         uint32_t* counters, void* scratch, emf_stream_t stream);
+int emf_hip_planeDirections(const emf_plane_voxel_t* records, const uint32_t* counters, uint32_t capacity, int32_t K,
+                            uint32_t* bins, emf_stream_t stream);
+int emf_hip_planeOffsets(const emf_plane_voxel_t* records, const uint32_t* counters, uint32_t capacity,
+                         const int32_t box_size[3], const float* dirs_host, const float* shift_host, int32_t D, float cos2,
+                         float inv_bin, int32_t S, uint32_t* hist, emf_stream_t stream);
+int emf_hip_planeAssign(const emf_plane_voxel_t* records, const uint32_t* counters, uint32_t capacity,
+                        const int32_t box_size[3], const float* planes_host, int32_t P, float cos2, float band,
+                        int16_t* labels, emf_plane_moments_t* moments, emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
