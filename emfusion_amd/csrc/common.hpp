@@ -150,4 +150,19 @@ inline hipStream_t as_stream(emf_stream_t s) { return reinterpret_cast<hipStream
 
 inline unsigned ceil_div(size_t a, size_t b) { return static_cast<unsigned>((a + b - 1) / b); }
 
+inline size_t align16(size_t b) { return (b + 15) & ~static_cast<size_t>(15); }
+
+// The arrays of an entry's scratch allocation, one behind the other and each 16-byte aligned.  A `place` function lays
+// them out once for the entry's ...ScratchBytes (any origin: only `off` is used) and once for its launches.
+struct ScratchArena {
+    char* p;
+    size_t off;
+    template <typename T>
+    T* take(size_t count) {
+        T* q = reinterpret_cast<T*>(p + off);
+        off += align16(sizeof(T) * count);
+        return q;
+    }
+};
+
 }  // namespace emf_hip

@@ -12,7 +12,7 @@
 //                 union_find.hpp as it is: lock-free, every step to a strictly smaller index.
 //   k_fr_flatten  labels[i] := root of i, the minimum index of the cluster whatever order the hooks ran in
 //   k_fr_count    roots (labels[i] == i), summed per workgroup, one atomicAdd per workgroup that has any
-//   k_fr_rootsums roots per workgroup of 256 voxels -> bsums;  k_fr_scan: their exclusive scan (mesh_scan.hpp)
+//   k_fr_rootsums roots per workgroup of 256 voxels -> bsums;  k_fr_scan: their exclusive scan (wave_ops.hpp)
 //   k_fr_roots    roots[rank] = i in index order, placed by scan; clears the slot's statistics
 //   k_fr_stats    one wave per row, 16 rows per workgroup.  A RUN is a maximal stretch of consecutive lanes with the
 //                 same label: same y and z, consecutive x, so its count, sums and box follow from its first x and
@@ -32,7 +32,7 @@
 // neighbour is tested against the box before it is read, a slot is used only where roots[slot] == label with
 // slot < min(n_clusters, roots found), a record's rank is below capacity.
 #include "common.hpp"
-#include "mesh_scan.hpp"
+#include "wave_ops.hpp"
 #include "union_find.hpp"
 
 #include <climits>
@@ -57,8 +57,6 @@ struct FrArgs {
     int nx, ny, nz;
 };
 
-inline size_t align16(size_t b) { return (b + 15) & ~static_cast<size_t>(15); }
-
 inline size_t place(FrArgs& a, const int32_t size[3], unsigned nc, void* scratch) {
     const size_t n = static_cast<size_t>(size[0]) * size[1] * static_cast<size_t>(size[2]);
     a.nx = size[0];
@@ -68,21 +66,15 @@ inline size_t place(FrArgs& a, const int32_t size[3], unsigned nc, void* scratch
     a.nc = nc;
     a.blocks = ceil_div(n, kFrBlock);
     a.cblocks = ceil_div(nc, kFrBlock);
-    char* p = static_cast<char*>(scratch);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* q = p + off;
-        off += align16(bytes);
-        return q;
-    };
-    a.sums = reinterpret_cast<unsigned long long*>(take(sizeof(unsigned long long) * 3 * nc));
-    a.key = reinterpret_cast<unsigned long long*>(take(sizeof(unsigned long long) * nc));
-    a.roots = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nc));
-    a.count = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nc));
-    a.box = reinterpret_cast<int*>(take(sizeof(int) * 6 * nc));
-    a.bsums = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * (a.blocks + 1)));
-    a.csums = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * (a.cblocks + 1)));
-    return off;
+    ScratchArena s{static_cast<char*>(scratch), 0};
+    a.sums = s.take<unsigned long long>(3 * static_cast<size_t>(nc));
+    a.key = s.take<unsigned long long>(nc);
+    a.roots = s.take<unsigned>(nc);
+    a.count = s.take<unsigned>(nc);
+    a.box = s.take<int>(6 * static_cast<size_t>(nc));
+    a.bsums = s.take<unsigned>(a.blocks + 1);
+    a.csums = s.take<unsigned>(a.cblocks + 1);
+    return s.off;
 }
 
 // the free and the unknown bits of chunk k of a row (bit l: voxel 64 k + l; nothing past the row's end)
@@ -165,21 +157,21 @@ __global__ __launch_bounds__(kFrBlock) void k_fr_count(const unsigned* __restric
                                                        unsigned* clusters) {
     __shared__ unsigned lds[kFrBlock / 64];
     unsigned total;
-    block_scan1(root_flag(labels, n, blockIdx.x * kFrBlock + threadIdx.x), total, lds);
+    block_exclusive_scan<kScanBlock / 64>(root_flag(labels, n, blockIdx.x * kFrBlock + threadIdx.x), total, lds);
     if (threadIdx.x == 0 && total) atomicAdd(clusters, total);
 }
 
 __global__ __launch_bounds__(kFrBlock) void k_fr_rootsums(const FrArgs a, const unsigned* __restrict__ labels) {
     __shared__ unsigned lds[kFrBlock / 64];
     unsigned total;
-    block_scan1(root_flag(labels, a.n, blockIdx.x * kFrBlock + threadIdx.x), total, lds);
+    block_exclusive_scan<kScanBlock / 64>(root_flag(labels, a.n, blockIdx.x * kFrBlock + threadIdx.x), total, lds);
     if (threadIdx.x == 0) a.bsums[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(kSumsBlock) void k_fr_scan(unsigned* sums, unsigned nblocks) {
     __shared__ unsigned lds[kSumsBlock / 64];
-    __shared__ unsigned carry;
-    scan_sums(sums, nblocks, lds, &carry);
+    const unsigned total = scan_sums(sums, 0u, nblocks, lds);
+    if (threadIdx.x == 0) sums[nblocks] = total;
 }
 
 __global__ __launch_bounds__(kFrBlock) void k_fr_roots(const FrArgs a, const unsigned* __restrict__ labels) {
@@ -187,7 +179,7 @@ __global__ __launch_bounds__(kFrBlock) void k_fr_roots(const FrArgs a, const uns
     const unsigned i = blockIdx.x * kFrBlock + threadIdx.x;
     const unsigned flag = root_flag(labels, a.n, i);
     unsigned total;
-    const unsigned rank = a.bsums[blockIdx.x] + block_scan1(flag, total, lds);
+    const unsigned rank = a.bsums[blockIdx.x] + block_exclusive_scan<kScanBlock / 64>(flag, total, lds);
     if (!flag || rank >= a.nc) return;
     a.roots[rank] = i;
     a.count[rank] = 0u;
@@ -388,7 +380,7 @@ __global__ __launch_bounds__(kFrBlock) void k_fr_keepsums(const FrArgs a, unsign
     __shared__ unsigned lds[kFrBlock / 64];
     const unsigned nc = min(a.nc, a.bsums[a.blocks]);
     unsigned total;
-    block_scan1(keep_flag(a, nc, blockIdx.x * kFrBlock + threadIdx.x, minVoxels), total, lds);
+    block_exclusive_scan<kScanBlock / 64>(keep_flag(a, nc, blockIdx.x * kFrBlock + threadIdx.x, minVoxels), total, lds);
     if (threadIdx.x == 0) a.csums[blockIdx.x] = total;
 }
 
@@ -400,7 +392,7 @@ __global__ __launch_bounds__(kFrBlock) void k_fr_emit(const FrArgs a, unsigned m
     const unsigned s = blockIdx.x * kFrBlock + threadIdx.x;
     const unsigned flag = keep_flag(a, nc, s, minVoxels);
     unsigned total;
-    const unsigned rank = a.csums[blockIdx.x] + block_scan1(flag, total, lds);
+    const unsigned rank = a.csums[blockIdx.x] + block_exclusive_scan<kScanBlock / 64>(flag, total, lds);
     if (s == 0u) *kept = a.csums[a.cblocks];
     if (!flag || rank >= capacity) return;
     emf_frontier_cluster_t r;

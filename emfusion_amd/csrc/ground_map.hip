@@ -6,7 +6,7 @@
 //                     ragged rows.  A wave none of whose bytes is FREE or OCCUPIED leaves at once.  A lane walks its
 //                     sixteen voxels in x order and keeps the bits of the destination word it is in (occ and fre); when
 //                     the word changes, the finished one is flushed.  A flush is a wave matter: consecutive lanes with
-//                     the same destination word OR their bits in a segmented scan and the last lane of the run issues
+//                     the same destination word OR their bits (run_scan of wave_ops.hpp) and the last lane of the run issues
 //                     the atomics, so with up along x a whole row is one atomic and with up along z a pair of rows
 //                     shares theirs.  The flush steps are skipped while no lane of the wave has a word to flush.
 //   k_ground_cells    one lane per cell: both columns in registers (at most four words each), walked from the top bin
@@ -14,6 +14,7 @@
 //   k_ground_classes  one lane per cell, plain loads of the eight neighbours' floors.
 // Integer atomics only (64-bit OR): the planes do not depend on the order of lanes, waves or workgroups.
 #include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace emf_hip {
 namespace {
@@ -40,24 +41,14 @@ __device__ __forceinline__ bool any_known(unsigned w) {
     return ((v - 0x01010101u) & ~v & 0x80808080u) != 0u;
 }
 
-// OR over the lanes of this lane's run that are not above it (a run: consecutive lanes with the same `run`)
-__device__ __forceinline__ unsigned long long run_or(unsigned long long v, int lane, int run) {
-#pragma unroll
-    for (int offset = 1; offset < 64; offset <<= 1) {
-        const unsigned long long below = __shfl_up(v, offset);
-        const int belowRun = __shfl_up(run, offset);
-        if (lane >= offset && belowRun == run) v |= below;  // runs are contiguous: every lane between shares it too
-    }
-    return v;
-}
-
 // Every lane of the wave is here.  dest < 0: nothing to flush (such lanes form runs that issue nothing).
+// The destination itself is the run number: it can come back within a wave, but OR is idempotent and the bits go to the
+// word that is the key (wave_ops.hpp), so no run_id and no ballot for it in the seventeen flushes of a lane.
 __device__ __forceinline__ void flush(const ColumnArgs& a, int lane, int dest, unsigned long long o, unsigned long long f) {
     if (__ballot(dest >= 0) == 0ull) return;  // wave-uniform
-    o = run_or(o, lane, dest);
-    f = run_or(f, lane, dest);
-    const int above = __shfl_down(dest, 1);
-    if (dest < 0 || (lane != 63 && above == dest)) return;  // not the last lane of its run
+    o = run_scan<OpOr>(o, lane, dest);
+    f = run_scan<OpOr>(f, lane, dest);
+    if (!run_is_last(dest, lane) || dest < 0) return;
     if (o) atomicOr(a.occ + dest, o);
     if (f) atomicOr(a.fre + dest, f);
 }

@@ -23,7 +23,7 @@
 //   k_cc_select   per root: atomicMax(best[model], size << 32 | ~label) -- the largest component, ties to the
 //                 smaller label
 //   k_cc_flags    keep flags of vertex i and triangle i, summed per workgroup; roots count the model's components
-//   k_cc_scan     two workgroups: the exclusive scans of the two sums arrays (mesh_scan.hpp)
+//   k_cc_scan     two workgroups: the exclusive scans of the two sums arrays (wave_ops.hpp)
 //   k_cc_rank     vexcl[i], texcl[i] = kept vertices / triangles before i; per-model kept counts and bases are the
 //                 ranks at the models' bases
 //   k_cc_emit     kept vertices copy position, normal and colour to their rank; kept triangles are rewritten
@@ -31,7 +31,7 @@
 // nowhere, is dropped by the filter, and raises `flag` (emf_hip_meshComponentsStatus -> EMF_E_ARG).
 // All atomics are ordinary global atomics on vector memory; every output is a pure function of the index buffer.
 #include "common.hpp"
-#include "mesh_scan.hpp"
+#include "wave_ops.hpp"
 #include "union_find.hpp"
 
 namespace emf_hip {
@@ -53,31 +53,23 @@ struct CcArgs {
     unsigned nv, nt, vblocks, tblocks;
 };
 
-inline size_t align16(size_t b) { return (b + 15) & ~static_cast<size_t>(15); }
-
 inline size_t place(CcArgs& a, unsigned long long nv, unsigned long long nt, void* scratch) {
     a.nv = static_cast<unsigned>(nv);
     a.nt = static_cast<unsigned>(nt);
     a.vblocks = ceil_div(nv, kCcBlock);
     a.tblocks = ceil_div(nt, kCcBlock);
-    char* p = static_cast<char*>(scratch);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* q = p + off;
-        off += align16(bytes);
-        return q;
-    };
-    a.parent = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nv));
-    a.size = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nv));
-    a.vexcl = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nv));
-    a.texcl = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nt));
-    a.vsums = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * (a.vblocks + 1)));
-    a.tsums = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * (a.tblocks + 1)));
-    a.best = reinterpret_cast<unsigned long long*>(take(sizeof(unsigned long long) * EMF_MAX_MODELS));
-    a.ncomp = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * EMF_MAX_MODELS));
-    a.nkept = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * EMF_MAX_MODELS));
-    a.flag = reinterpret_cast<unsigned*>(take(16));
-    return off;
+    ScratchArena s{static_cast<char*>(scratch), 0};
+    a.parent = s.take<unsigned>(nv);
+    a.size = s.take<unsigned>(nv);
+    a.vexcl = s.take<unsigned>(nv);
+    a.texcl = s.take<unsigned>(nt);
+    a.vsums = s.take<unsigned>(a.vblocks + 1);
+    a.tsums = s.take<unsigned>(a.tblocks + 1);
+    a.best = s.take<unsigned long long>(EMF_MAX_MODELS);
+    a.ncomp = s.take<unsigned>(EMF_MAX_MODELS);
+    a.nkept = s.take<unsigned>(EMF_MAX_MODELS);
+    a.flag = s.take<unsigned>(4);
+    return s.off;
 }
 
 // the models of a table launch (device arrays as the weld leaves them) or, for one model, none
@@ -264,18 +256,19 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_flags(const CcArgs a, const CcM
         if (vf) atomicAdd(a.nkept + m, 1u);
     }
     unsigned total;
-    block_scan1(vf, total, lds);
+    block_exclusive_scan<kScanBlock / 64>(vf, total, lds);
     if (threadIdx.x == 0 && blockIdx.x < a.vblocks) a.vsums[blockIdx.x] = total;
-    block_scan1(triangle_flag(a, md, c, tris, i), total, lds);
+    block_exclusive_scan<kScanBlock / 64>(triangle_flag(a, md, c, tris, i), total, lds);
     if (threadIdx.x == 0 && blockIdx.x < a.tblocks) a.tsums[blockIdx.x] = total;
 }
 
 // workgroup 0 scans the vertex sums, workgroup 1 the triangle sums
 __global__ __launch_bounds__(kSumsBlock) void k_cc_scan(const CcArgs a) {
     __shared__ unsigned lds[kSumsBlock / 64];
-    __shared__ unsigned carry;
-    if (blockIdx.x == 0) scan_sums(a.vsums, a.vblocks, lds, &carry);
-    else scan_sums(a.tsums, a.tblocks, lds, &carry);
+    unsigned* sums = blockIdx.x == 0 ? a.vsums : a.tsums;
+    const unsigned n = blockIdx.x == 0 ? a.vblocks : a.tblocks;
+    const unsigned total = scan_sums(sums, 0u, n, lds);
+    if (threadIdx.x == 0) sums[n] = total;
 }
 
 __global__ __launch_bounds__(kCcBlock) void k_cc_rank(const CcArgs a, const CcModels md, const CcCriteria c,
@@ -283,9 +276,9 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_rank(const CcArgs a, const CcMo
     __shared__ unsigned lds[kCcBlock / 64];
     const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
     unsigned total;
-    const unsigned vmine = block_scan1(vertex_flag(a, md, c, i), total, lds);
+    const unsigned vmine = block_exclusive_scan<kScanBlock / 64>(vertex_flag(a, md, c, i), total, lds);
     if (i < a.nv) a.vexcl[i] = a.vsums[blockIdx.x] + vmine;
-    const unsigned tmine = block_scan1(triangle_flag(a, md, c, tris, i), total, lds);
+    const unsigned tmine = block_exclusive_scan<kScanBlock / 64>(triangle_flag(a, md, c, tris, i), total, lds);
     if (i < a.nt) a.texcl[i] = a.tsums[blockIdx.x] + tmine;
 }
 

@@ -25,7 +25,7 @@
 //                    1).  Per vertex of a pass-through model: ref[i] := 1
 //   k_sp_flags       three flags summed per workgroup: "is a first" (the clusters met), "is a referenced first" (the
 //                    kept vertices), "kept triangle"
-//   k_sp_scan        three workgroups: the exclusive scans of the three sums arrays (mesh_scan.hpp)
+//   k_sp_scan        three workgroups: the exclusive scans of the three sums arrays (wave_ops.hpp)
 //   k_sp_rank        vexcl[i], texcl[i] = kept vertices / triangles before i
 //   k_sp_bases       per model: kept counts, kept bases and the clusters met, all ranks at the models' bases
 //   k_sp_emit        a kept first writes its cluster's vertex at its rank (its own bits if it is alone, the integer
@@ -38,7 +38,7 @@
 // Which slot a key lands in depends on the order the lanes arrive; the MINIMUM index per key does not.  All atomics
 // are ordinary global atomics on vector memory; every loop is bounded by construction; nothing waits on another lane.
 #include "common.hpp"
-#include "mesh_scan.hpp"
+#include "wave_ops.hpp"
 
 namespace emf_hip {
 namespace {
@@ -70,34 +70,26 @@ inline unsigned capacity_for(unsigned long long nv) {
     return static_cast<unsigned>(cap);
 }
 
-inline size_t align16(size_t b) { return (b + 15) & ~static_cast<size_t>(15); }
-
 inline size_t place(SpArgs& a, unsigned long long nv, unsigned long long nt, void* scratch) {
     a.nv = static_cast<unsigned>(nv);
     a.nt = static_cast<unsigned>(nt);
     a.cap = capacity_for(nv);
     a.vblocks = ceil_div(nv, kSpBlock);
     a.tblocks = ceil_div(nt, kSpBlock);
-    char* p = static_cast<char*>(scratch);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* q = p + off;
-        off += align16(bytes);
-        return q;
-    };
-    a.tkeys = reinterpret_cast<unsigned long long*>(take(sizeof(unsigned long long) * a.cap));
-    a.tfirst = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * a.cap));
-    a.rep = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nv));
-    a.count = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nv));
-    a.ref = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nv));
-    a.sums = reinterpret_cast<long long*>(take(sizeof(long long) * 9 * nv));
-    a.vexcl = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nv));
-    a.texcl = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * nt));
-    a.csums = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * (a.vblocks + 1)));
-    a.vsums = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * (a.vblocks + 1)));
-    a.tsums = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * (a.tblocks + 1)));
-    a.flag = reinterpret_cast<unsigned*>(take(16));
-    return off;
+    ScratchArena s{static_cast<char*>(scratch), 0};
+    a.tkeys = s.take<unsigned long long>(a.cap);
+    a.tfirst = s.take<unsigned>(a.cap);
+    a.rep = s.take<unsigned>(nv);
+    a.count = s.take<unsigned>(nv);
+    a.ref = s.take<unsigned>(nv);
+    a.sums = s.take<long long>(9 * nv);
+    a.vexcl = s.take<unsigned>(nv);
+    a.texcl = s.take<unsigned>(nt);
+    a.csums = s.take<unsigned>(a.vblocks + 1);
+    a.vsums = s.take<unsigned>(a.vblocks + 1);
+    a.tsums = s.take<unsigned>(a.tblocks + 1);
+    a.flag = s.take<unsigned>(4);
+    return s.off;
 }
 
 // the models of a table launch (device arrays in the layout the weld and the filter leave) or, for one mesh, none
@@ -303,21 +295,21 @@ __global__ __launch_bounds__(kSpBlock) void k_sp_flags(const SpArgs a) {
     __shared__ unsigned lds[kSpBlock / 64];
     const unsigned i = blockIdx.x * kSpBlock + threadIdx.x;
     unsigned total;
-    block_scan1(is_first(a, i) ? 1u : 0u, total, lds);
+    block_exclusive_scan<kScanBlock / 64>(is_first(a, i) ? 1u : 0u, total, lds);
     if (threadIdx.x == 0 && blockIdx.x < a.vblocks) a.csums[blockIdx.x] = total;
-    block_scan1(vertex_flag(a, i), total, lds);
+    block_exclusive_scan<kScanBlock / 64>(vertex_flag(a, i), total, lds);
     if (threadIdx.x == 0 && blockIdx.x < a.vblocks) a.vsums[blockIdx.x] = total;
-    block_scan1(i < a.nt ? a.texcl[i] : 0u, total, lds);
+    block_exclusive_scan<kScanBlock / 64>(i < a.nt ? a.texcl[i] : 0u, total, lds);
     if (threadIdx.x == 0 && blockIdx.x < a.tblocks) a.tsums[blockIdx.x] = total;
 }
 
 // workgroup 0 scans the cluster sums, workgroup 1 the kept-vertex sums, workgroup 2 the kept-triangle sums
 __global__ __launch_bounds__(kSumsBlock) void k_sp_scan(const SpArgs a) {
     __shared__ unsigned lds[kSumsBlock / 64];
-    __shared__ unsigned carry;
-    if (blockIdx.x == 0) scan_sums(a.csums, a.vblocks, lds, &carry);
-    else if (blockIdx.x == 1) scan_sums(a.vsums, a.vblocks, lds, &carry);
-    else scan_sums(a.tsums, a.tblocks, lds, &carry);
+    unsigned* sums = blockIdx.x == 0 ? a.csums : (blockIdx.x == 1 ? a.vsums : a.tsums);
+    const unsigned n = blockIdx.x == 2 ? a.tblocks : a.vblocks;
+    const unsigned total = scan_sums(sums, 0u, n, lds);
+    if (threadIdx.x == 0) sums[n] = total;
 }
 
 // texcl[i] holds triangle i's kept flag on entry and its rank on exit: each lane reads and writes its own element
@@ -325,9 +317,9 @@ __global__ __launch_bounds__(kSpBlock) void k_sp_rank(const SpArgs a) {
     __shared__ unsigned lds[kSpBlock / 64];
     const unsigned i = blockIdx.x * kSpBlock + threadIdx.x;
     unsigned total;
-    const unsigned vmine = block_scan1(vertex_flag(a, i), total, lds);
+    const unsigned vmine = block_exclusive_scan<kScanBlock / 64>(vertex_flag(a, i), total, lds);
     if (i < a.nv) a.vexcl[i] = a.vsums[blockIdx.x] + vmine;
-    const unsigned tmine = block_scan1(i < a.nt ? a.texcl[i] : 0u, total, lds);
+    const unsigned tmine = block_exclusive_scan<kScanBlock / 64>(i < a.nt ? a.texcl[i] : 0u, total, lds);
     if (i < a.nt) a.texcl[i] = a.tsums[blockIdx.x] + tmine;
 }
 

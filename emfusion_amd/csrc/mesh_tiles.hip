@@ -13,7 +13,7 @@
 //             (z, y, x) order; rows of 34 floats keep the 32 lanes of a half-wave on 32 different banks.
 //   k_tiles<kCount>  per (j, wave) the packed (vertices | triangles << 16) sum, per tile their total -> vertBase[t],
 //             triBase[t].  A tile owns at most 24576 vertices and 10240 triangles: 16 + 16 bits.
-//   k_tiles_scan     one workgroup: both arrays become their exclusive scans, entry n the totals (mesh_scan.hpp)
+//   k_tiles_scan     one workgroup: both arrays become their exclusive scans, entry n the totals (wave_ops.hpp)
 //   k_tiles<kEmit / kColors / kKeys>  a tile without surface returns before it stages anything; the others classify
 //             again, scan inside the workgroup (wave shuffles + 32 LDS words) and write where the canonical order
 //             puts them: tiles in table order, cubes in (z, y, x) order, vertices in edge-bit order.
@@ -21,7 +21,7 @@
 // checked: an entry whose literal leaves the arena or whose in-place tile leaves the volume, and a neighbour index
 // that does not name the tile at the neighbouring coordinate, count as "not listed" and are never dereferenced.
 #include "mesh_core.hpp"
-#include "mesh_scan.hpp"
+#include "wave_ops.hpp"
 
 #include "mc_tables.h"
 
@@ -225,22 +225,14 @@ __device__ __forceinline__ void tile_totals(const float* sT, const uint8_t* sV, 
         unsigned p = packed_counts(cube_class<kH>(sT, sV, x, y, j));
         const unsigned long long surface = __ballot(p != 0u);
         cubes += static_cast<unsigned>(__popcll(surface));
-        if (surface != 0ull) {  // wave-uniform: most waves hold no surface
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o);
-        }
+        if (surface != 0ull) p = wave_reduce<OpAdd>(p);  // wave-uniform: most waves hold no surface
         if (lane == 0) sTot[j * 4 + wave] = p;
     }
     if (lane == 0) sTot[33 + wave] = cubes;
     __syncthreads();
     if (threadIdx.x < 64) {
         const unsigned v = threadIdx.x < 32 ? sTot[threadIdx.x] : 0u;
-        unsigned inc = v;
-#pragma unroll
-        for (int o = 1; o < 32; o <<= 1) {
-            const unsigned up = __shfl_up(inc, o);
-            if (lane >= o) inc += up;
-        }
+        const unsigned inc = wave_inclusive_scan(v);
         if (threadIdx.x < 32) sTot[threadIdx.x] = inc - v;
         if (threadIdx.x == 31) sTot[32] = inc;
     }
@@ -379,7 +371,7 @@ __global__ __launch_bounds__(kTilesBlock) void k_tiles(const TilesArgs a) {
         }
         return;
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wave = threadIdx.x >> 6;
     const emf_mesh_tile_t& self = a.tiles[t];
     const int lat[3] = {static_cast<int>(static_cast<unsigned>(self.coord[0]) * kTX),
                         static_cast<int>(static_cast<unsigned>(self.coord[1]) * kTY),
@@ -394,12 +386,7 @@ __global__ __launch_bounds__(kTilesBlock) void k_tiles(const TilesArgs a) {
         q.cls = cube_class<kH>(sT, sV, q.x, q.y, j);
         const unsigned p = packed_counts(q.cls);
         if (__ballot(p != 0u) == 0ull) continue;  // wave-uniform
-        unsigned inc = p;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned up = __shfl_up(inc, o);
-            if (lane >= o) inc += up;
-        }
+        const unsigned inc = wave_inclusive_scan(p);
         if (!q.cls) continue;
         const unsigned before = sTot[j * 4 + wave] + inc - p;
         q.edges = active_edges(q.cls);
@@ -416,14 +403,11 @@ __global__ __launch_bounds__(kTilesBlock) void k_tiles(const TilesArgs a) {
 __global__ __launch_bounds__(kSumsBlock) void k_tiles_scan(unsigned* vertBase, unsigned* triBase, unsigned n,
                                                            emf_mesh_counts_t* counts) {
     __shared__ unsigned lds[kSumsBlock / 64];
-    __shared__ unsigned carry;
-    scan_sums(vertBase, n, lds, &carry);
-    __syncthreads();
-    scan_sums(triBase, n, lds, &carry);
-    __syncthreads();
+    const unsigned vertices = scan_sums(vertBase, 0u, n, lds);
+    const unsigned triangles = scan_sums(triBase, 0u, n, lds);
     if (threadIdx.x == 0) {
-        counts->vertices = vertBase[n];
-        counts->triangles = triBase[n];
+        counts->vertices = vertBase[n] = vertices;
+        counts->triangles = triBase[n] = triangles;
     }
 }
 

@@ -17,7 +17,7 @@
 //                  probing bounded by cap -- a table that is too small raises `flag` instead of spinning), then
 //                  atomicMin the soup index into it; remap[i] := the slot
 //   k_weld_flags   first[i] = (table first[remap[i]] == i), summed per workgroup -> sums[b]
-//   k_weld_scan    one workgroup: exclusive scan of sums in place, the total behind them (as k_mesh_scan)
+//   k_weld_scan    one workgroup: exclusive scan of sums in place, the total behind them (wave_ops.hpp)
 //   k_weld_rank    excl[i] = firsts before i = the welded index of i if i is a first
 //   k_weld_remap   remap[i] := excl[first of i's key]; the models' welded bases are excl at their soup bases
 //   k_weld_emit    firsts (remap[i] == excl[i]) copy position, normal and colour to their rank; triangles are
@@ -25,7 +25,7 @@
 // Which slot a key lands in depends on the order the lanes arrive; the MINIMUM soup index per key, hence every
 // output, does not.  All atomics are ordinary global atomics on vector memory.
 #include "common.hpp"
-#include "mesh_scan.hpp"
+#include "wave_ops.hpp"
 
 namespace emf_hip {
 namespace {
@@ -50,27 +50,18 @@ inline unsigned capacity_for(unsigned long long nv) {
     return static_cast<unsigned>(cap);
 }
 
-inline size_t align16(size_t b) { return (b + 15) & ~static_cast<size_t>(15); }
-
 inline size_t place(WeldArgs& a, unsigned long long nv, void* scratch) {
     a.nv = static_cast<unsigned>(nv);
     a.cap = capacity_for(nv);
     a.nblocks = ceil_div(nv, kWeldBlock);
-    char* p = static_cast<char*>(scratch);
-    size_t off = 0;
-    a.tkeys = reinterpret_cast<unsigned long long*>(p + off);
-    off += align16(sizeof(unsigned long long) * a.cap);
-    a.tfirst = reinterpret_cast<unsigned*>(p + off);
-    off += align16(sizeof(unsigned) * a.cap);
-    a.remap = reinterpret_cast<unsigned*>(p + off);
-    off += align16(sizeof(unsigned) * nv);
-    a.excl = reinterpret_cast<unsigned*>(p + off);
-    off += align16(sizeof(unsigned) * nv);
-    a.sums = reinterpret_cast<unsigned*>(p + off);
-    off += align16(sizeof(unsigned) * (a.nblocks + 1));
-    a.flag = reinterpret_cast<unsigned*>(p + off);
-    off += 16;
-    return off;
+    ScratchArena s{static_cast<char*>(scratch), 0};
+    a.tkeys = s.take<unsigned long long>(a.cap);
+    a.tfirst = s.take<unsigned>(a.cap);
+    a.remap = s.take<unsigned>(nv);
+    a.excl = s.take<unsigned>(nv);
+    a.sums = s.take<unsigned>(a.nblocks + 1);
+    a.flag = s.take<unsigned>(4);
+    return s.off;
 }
 
 // splitmix64's finaliser: neighbouring edges (keys 3 apart) must not land in neighbouring slots
@@ -109,22 +100,22 @@ __device__ __forceinline__ unsigned is_first(const WeldArgs& a, unsigned i) {
 __global__ __launch_bounds__(kWeldBlock) void k_weld_flags(const WeldArgs a) {
     __shared__ unsigned lds[kWeldBlock / 64];
     unsigned total;
-    block_scan1(is_first(a, blockIdx.x * kWeldBlock + threadIdx.x), total, lds);
+    block_exclusive_scan<kScanBlock / 64>(is_first(a, blockIdx.x * kWeldBlock + threadIdx.x), total, lds);
     if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
 }
 
 // one workgroup: sums[b] := sum of sums[0 .. b), sums[nblocks] := the total
 __global__ __launch_bounds__(kSumsBlock) void k_weld_scan(const WeldArgs a) {
     __shared__ unsigned lds[kSumsBlock / 64];
-    __shared__ unsigned carry;
-    scan_sums(a.sums, a.nblocks, lds, &carry);
+    const unsigned total = scan_sums(a.sums, 0u, a.nblocks, lds);
+    if (threadIdx.x == 0) a.sums[a.nblocks] = total;
 }
 
 __global__ __launch_bounds__(kWeldBlock) void k_weld_rank(const WeldArgs a) {
     __shared__ unsigned lds[kWeldBlock / 64];
     const unsigned i = blockIdx.x * kWeldBlock + threadIdx.x;
     unsigned total;
-    const unsigned mine = block_scan1(is_first(a, i), total, lds);
+    const unsigned mine = block_exclusive_scan<kScanBlock / 64>(is_first(a, i), total, lds);
     if (i < a.nv) a.excl[i] = a.sums[blockIdx.x] + mine;
 }
 

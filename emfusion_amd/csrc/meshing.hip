@@ -17,7 +17,7 @@
 //                 instructions per wave.  Only lanes with surface (rare) build their class.  Per
 //                 chunk the packed (vertices, triangles) total -> chunkTot[g], per workgroup their
 //                 sum -> blockSums[b], and the ids of the chunks that hold surface -> list[]
-//   k_mesh_scan   one workgroup: exclusive scan of blockSums in place (17 k pairs at 512^3), totals
+//   k_mesh_scan   one workgroup: exclusive scan of blockSums in place (wave_ops.hpp; 17 k pairs at 512^3), totals
 //   k_mesh_emit   a fixed grid walks list[]: classify the chunk again, scan inside the workgroup (wave
 //                 shuffles + LDS) on top of blockSums[g / 8] + the chunk totals before it, and write
 //                 vertices, normals and triangles where the reference puts them
@@ -39,6 +39,7 @@
 // operator/= that takes its left side by const reference and returns the quotient (common.cuh:170-173),
 // so nothing is normalised (quirk Q19).
 #include "mesh_core.hpp"
+#include "wave_ops.hpp"
 
 #include "mc_tables.h"
 
@@ -267,36 +268,6 @@ __device__ __forceinline__ unsigned triangles_of(unsigned cls) {
     return n;
 }
 
-// sums over the workgroup (all lanes get the totals) and the exclusive prefix of this lane
-__device__ __forceinline__ uint2 block_scan(uint2 v, uint2& total, uint2* lds /* [8] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint2 inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned ax = __shfl_up(inc.x, o), ay = __shfl_up(inc.y, o);
-        if (lane >= o) {
-            inc.x += ax;
-            inc.y += ay;
-        }
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    uint2 before = make_uint2(0u, 0u);
-    total = make_uint2(0u, 0u);
-#pragma unroll
-    for (int w = 0; w < kMcBlock / 64; ++w) {
-        const uint2 t = lds[w];
-        if (w < wave) {
-            before.x += t.x;
-            before.y += t.y;
-        }
-        total.x += t.x;
-        total.y += t.y;
-    }
-    __syncthreads();
-    return make_uint2(before.x + inc.x - v.x, before.y + inc.y - v.y);
-}
-
 // the counting work of one workgroup: logical workgroup b of a volume with kMcChunks chunks per workgroup
 template <int kMcChunks>
 __device__ __forceinline__ void count_chunks(const MeshArgs& a, const MeshSource& src, unsigned b,
@@ -362,59 +333,23 @@ __global__ __launch_bounds__(kMcBlock) void k_mesh_count(const MeshArgs a) {
 }
 
 // one workgroup walks each model's per-workgroup sums in chunks of 1024 (a 512^3 volume has 17 k of them), the
-// carry restarting at every model; the models' totals become their counts and, summed in 64 bits, their bases
-__global__ __launch_bounds__(1024) void k_mesh_scan(const MeshArgs a) {
-    __shared__ uint2 lds[16];
-    __shared__ uint2 carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long vbase = 0, tbase = 0;  // (thread 0's)
+// total restarting at every model; the models' totals become their counts and, summed in 64 bits, their bases
+__global__ __launch_bounds__(kSumsBlock) void k_mesh_scan(const MeshArgs a) {
+    __shared__ uint2 lds[kSumsBlock / 64];
+    unsigned long long vbase = 0, tbase = 0;
     for (unsigned m = 0; m < a.n; ++m) {
-        if (threadIdx.x == 0) carry = make_uint2(0u, 0u);
-        __syncthreads();
-        const unsigned hi = a.blockBase[m + 1];
-        for (unsigned start = a.blockBase[m]; start < hi; start += 1024) {
-            const unsigned i = start + threadIdx.x;
-            const uint2 v = i < hi ? a.blockSums[i] : make_uint2(0u, 0u);
-            uint2 inc = v;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned ax = __shfl_up(inc.x, o), ay = __shfl_up(inc.y, o);
-                if (lane >= o) {
-                    inc.x += ax;
-                    inc.y += ay;
-                }
-            }
-            if (lane == 63) lds[wave] = inc;
-            __syncthreads();
-            uint2 before = carry, total = make_uint2(0u, 0u);
-            for (int w = 0; w < 16; ++w) {
-                const uint2 t = lds[w];
-                if (w < wave) {
-                    before.x += t.x;
-                    before.y += t.y;
-                }
-                total.x += t.x;
-                total.y += t.y;
-            }
-            if (i < hi) a.blockSums[i] = make_uint2(before.x + inc.x - v.x, before.y + inc.y - v.y);
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                carry.x += total.x;
-                carry.y += total.y;
-            }
-            __syncthreads();
-        }
+        const uint2 total = scan_sums(a.blockSums, a.blockBase[m], a.blockBase[m + 1], lds);
         if (threadIdx.x == 0) {
-            a.counts[m].vertices = carry.x;
-            a.counts[m].triangles = carry.y;
+            a.counts[m].vertices = total.x;
+            a.counts[m].triangles = total.y;
             a.bases[2 * m] = vbase;
             a.bases[2 * m + 1] = tbase;
             if (a.basesOut) {
                 a.basesOut[2 * m] = vbase;
                 a.basesOut[2 * m + 1] = tbase;
             }
-            vbase += carry.x;
-            tbase += carry.y;
+            vbase += total.x;
+            tbase += total.y;
         }
     }
     if (threadIdx.x == 0 && a.basesOut) {
@@ -483,7 +418,7 @@ __device__ __forceinline__ ChunkSlot chunk_slot(const MeshArgs& a, unsigned i, u
     uint2 v = make_uint2(0u, 0u);
     if (s.q.cls) v = make_uint2(__popc(s.edges), triangles_of(s.q.cls));
     uint2 total;
-    const uint2 mine = block_scan(v, total, lds);
+    const uint2 mine = block_exclusive_scan<kMcBlock / 64>(v, total, lds);
     s.ntris = v.y;
     s.vertBase = base.x + mine.x;
     s.triBase = base.y + mine.y;
@@ -494,7 +429,7 @@ __device__ __forceinline__ ChunkSlot chunk_slot(const MeshArgs& a, unsigned i, u
 // argument form to 81 = 5 waves
 template <bool kTable>
 __global__ __launch_bounds__(kMcBlock) __attribute__((amdgpu_waves_per_eu(6))) void k_mesh_emit(const MeshArgs a) {
-    __shared__ uint2 lds[8];
+    __shared__ uint2 lds[kMcBlock / 64];
     const unsigned todo = *a.listCount;
     for (unsigned i = blockIdx.x; i < todo; i += gridDim.x) {
         const ChunkSlot s = chunk_slot<kTable>(a, i, lds);
@@ -596,7 +531,7 @@ __device__ __forceinline__ void color_cube(const MeshSource& src, const ushort4*
 
 template <bool kTable>
 __global__ __launch_bounds__(kMcBlock) void k_mesh_colors(const MeshArgs a, const MeshColorArgs ca) {
-    __shared__ uint2 lds[8];
+    __shared__ uint2 lds[kMcBlock / 64];
     const unsigned todo = *a.listCount;
     for (unsigned i = blockIdx.x; i < todo; i += gridDim.x) {
         const ChunkSlot s = chunk_slot<kTable>(a, i, lds);
@@ -633,7 +568,7 @@ __device__ __forceinline__ void key_cube(const MeshSource& src, unsigned m, cons
 
 template <bool kTable>
 __global__ __launch_bounds__(kMcBlock) void k_mesh_keys(const MeshArgs a, unsigned long long* keys) {
-    __shared__ uint2 lds[8];
+    __shared__ uint2 lds[kMcBlock / 64];
     const unsigned todo = *a.listCount;
     for (unsigned i = blockIdx.x; i < todo; i += gridDim.x) {
         const ChunkSlot s = chunk_slot<kTable>(a, i, lds);
@@ -698,7 +633,7 @@ int launch_count(MeshArgs& a, emf_stream_t stream, const char* what) {
         hipLaunchKernelGGL(k_mesh_count<true>, dim3(a.launchStart[a.n]), dim3(kMcBlock), 0, as_stream(stream), a);
     else
         hipLaunchKernelGGL(k_mesh_count<false>, dim3(a.launchStart[a.n]), dim3(kMcBlock), 0, as_stream(stream), a);
-    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(1024), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kSumsBlock), 0, as_stream(stream), a);
     return launch_status(what);
 }
 

@@ -13,7 +13,7 @@
 //   k_mm_count       area[root] += 1 per candidate: a wave whose live lanes share one root adds its lane count
 //                    once, the workgroup's uniform waves are merged through LDS (as k_cc_count)        (stage 4)
 //   k_mm_flags       roots with area >= min_pixels, summed per workgroup
-//   k_mm_scan        one workgroup: the exclusive scan of the sums (mesh_scan.hpp)
+//   k_mm_scan        one workgroup: the exclusive scan of the sums (wave_ops.hpp)
 //   k_mm_compact     roots[rank] = i for every such root: index order, placed by scan, never by atomics
 //   k_mm_select      one workgroup: max_masks rounds of "the largest key (area << 32 | ~label) below the last one"
 //                    over the compacted roots; writes count and info (boxes empty)
@@ -22,7 +22,7 @@
 // No index leaves [0, n): the neighbours of the hook are tested against w and h, the tile's halo against the image,
 // ranks are below the scanned total <= n, and a proposal's rank is below max_masks <= EMF_MOTION_MAX_MASKS.
 #include "common.hpp"
-#include "mesh_scan.hpp"
+#include "wave_ops.hpp"
 #include "union_find.hpp"
 
 #include <climits>
@@ -46,29 +46,21 @@ struct MmArgs {
     int w, h;
 };
 
-inline size_t align16(size_t b) { return (b + 15) & ~static_cast<size_t>(15); }
-
 inline size_t place(MmArgs& a, int w, int h, void* scratch) {
     const size_t n = static_cast<size_t>(w) * static_cast<size_t>(h);
     a.w = w;
     a.h = h;
     a.n = static_cast<unsigned>(n);
     a.blocks = ceil_div(n, kMmBlock);
-    char* p = static_cast<char*>(scratch);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* q = p + off;
-        off += align16(bytes);
-        return q;
-    };
-    a.m = reinterpret_cast<float*>(take(sizeof(float) * n));
-    a.parent = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * n));
-    a.area = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * n));
-    a.roots = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * n));
-    a.candA = reinterpret_cast<uint8_t*>(take(n));
-    a.candB = reinterpret_cast<uint8_t*>(take(n));
-    a.sums = reinterpret_cast<unsigned*>(take(sizeof(unsigned) * (a.blocks + 1)));
-    return off;
+    ScratchArena s{static_cast<char*>(scratch), 0};
+    a.m = s.take<float>(n);
+    a.parent = s.take<unsigned>(n);
+    a.area = s.take<unsigned>(n);
+    a.roots = s.take<unsigned>(n);
+    a.candA = s.take<uint8_t>(n);
+    a.candB = s.take<uint8_t>(n);
+    a.sums = s.take<unsigned>(a.blocks + 1);
+    return s.off;
 }
 
 __global__ __launch_bounds__(kMmBlock) void k_mm_candidates(const MmArgs a, const float* __restrict__ points,
@@ -175,14 +167,14 @@ __global__ __launch_bounds__(kMmBlock) void k_mm_flags(const MmArgs a, const uin
     __shared__ unsigned lds[kMmBlock / 64];
     const unsigned i = blockIdx.x * kMmBlock + threadIdx.x;
     unsigned total;
-    block_scan1(root_flag(a, cand, i, minPixels), total, lds);
+    block_exclusive_scan<kScanBlock / 64>(root_flag(a, cand, i, minPixels), total, lds);
     if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(kSumsBlock) void k_mm_scan(const MmArgs a) {
     __shared__ unsigned lds[kSumsBlock / 64];
-    __shared__ unsigned carry;
-    scan_sums(a.sums, a.blocks, lds, &carry);
+    const unsigned total = scan_sums(a.sums, 0u, a.blocks, lds);
+    if (threadIdx.x == 0) a.sums[a.blocks] = total;
 }
 
 __global__ __launch_bounds__(kMmBlock) void k_mm_compact(const MmArgs a, const uint8_t* __restrict__ cand,
@@ -191,7 +183,7 @@ __global__ __launch_bounds__(kMmBlock) void k_mm_compact(const MmArgs a, const u
     const unsigned i = blockIdx.x * kMmBlock + threadIdx.x;
     const unsigned f = root_flag(a, cand, i, minPixels);
     unsigned total;
-    const unsigned mine = block_scan1(f, total, lds);
+    const unsigned mine = block_exclusive_scan<kScanBlock / 64>(f, total, lds);
     if (f) a.roots[a.sums[blockIdx.x] + mine] = i;  // < sums[blocks] <= n
 }
 

@@ -19,6 +19,7 @@
 // A workgroup whose tile the model's unseen-tile map marks "every weight is 0" leaves at once: it holds no solid and no
 // observed voxel.  Integer atomics only: the records do not depend on the order of waves or workgroups.
 #include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace emf_hip {
 namespace {
@@ -56,32 +57,6 @@ __device__ __forceinline__ unsigned float_key(float v) {
     return (b & 0x80000000u) ? ~b : (b ^ 0x80000000u);
 }
 __device__ __forceinline__ unsigned key_bits(unsigned k) { return (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k; }
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ unsigned wave_min(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, static_cast<unsigned>(__shfl_xor(v, o)));
-    return v;
-}
-__device__ __forceinline__ unsigned wave_max(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, static_cast<unsigned>(__shfl_xor(v, o)));
-    return v;
-}
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-    return v;
-}
 
 // The tile of a workgroup and the model it belongs to; false: nothing to do (block-uniform).
 struct Tile {
@@ -209,9 +184,9 @@ __global__ __launch_bounds__(kShBlock) void k_shape_moments(const ShapeArgs a) {
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     if (__ballot(acc[1] != 0u) != 0ull) {  // wave-uniform
 #pragma unroll
-        for (int k = 0; k < kShSums; ++k) acc[k] = wave_sum(acc[k]);
-        lox = wave_min(lox), loy = wave_min(loy), loz = wave_min(loz);
-        hix = wave_max(hix), hiy = wave_max(hiy), hiz = wave_max(hiz);
+        for (int k = 0; k < kShSums; ++k) acc[k] = wave_reduce<OpAdd>(acc[k]);
+        lox = wave_reduce<OpMin>(lox), loy = wave_reduce<OpMin>(loy), loz = wave_reduce<OpMin>(loz);
+        hix = wave_reduce<OpMax>(hix), hiy = wave_reduce<OpMax>(hiy), hiz = wave_reduce<OpMax>(hiz);
     }
     if (lane == 0) {
 #pragma unroll
@@ -280,8 +255,8 @@ __global__ __launch_bounds__(kShBlock) void k_shape_extents(const ShapeArgs a) {
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const bool waveSolid = __ballot(solid != 0u) != 0ull;  // wave-uniform
     if (waveSolid) {
-        lo0 = wave_min(lo0), lo1 = wave_min(lo1), lo2 = wave_min(lo2);
-        hi0 = wave_max(hi0), hi1 = wave_max(hi1), hi2 = wave_max(hi2);
+        lo0 = wave_reduce<OpMin>(lo0), lo1 = wave_reduce<OpMin>(lo1), lo2 = wave_reduce<OpMin>(lo2);
+        hi0 = wave_reduce<OpMax>(hi0), hi1 = wave_reduce<OpMax>(hi1), hi2 = wave_reduce<OpMax>(hi2);
     }
     if (lane == 0) {
         keys[wave][0] = lo0, keys[wave][1] = lo1, keys[wave][2] = lo2;

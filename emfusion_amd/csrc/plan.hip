@@ -31,7 +31,7 @@
 // workgroups; every device loop is bounded by a constant or an argument.  No index leaves its array: a neighbour is
 // tested against the box before it is read, a tile against the tile grid before it is flagged.
 #include "common.hpp"
-#include "mesh_scan.hpp"
+#include "wave_ops.hpp"
 
 namespace emf_hip {
 namespace {
@@ -56,8 +56,6 @@ struct PlArgs {
     int nx, ny, nz;
 };
 
-inline size_t align16(size_t b) { return (b + 15) & ~static_cast<size_t>(15); }
-
 inline size_t place(PlArgs& a, const int32_t size[3], void* scratch) {
     a.nx = size[0];
     a.ny = size[1];
@@ -66,10 +64,10 @@ inline size_t place(PlArgs& a, const int32_t size[3], void* scratch) {
     a.tilesY = (a.ny + kTy - 1) / kTy;
     a.tilesZ = (a.nz + kTz - 1) / kTz;
     a.tiles = static_cast<unsigned>(a.tilesX) * a.tilesY * a.tilesZ;
-    char* p = static_cast<char*>(scratch);
-    a.active = reinterpret_cast<unsigned*>(p);  // first: the memset of a batch starts at the allocation's start
-    a.flags = reinterpret_cast<uint8_t*>(p + align16(sizeof(unsigned) * kBatch));
-    return align16(sizeof(unsigned) * kBatch) + align16(2 * static_cast<size_t>(a.tiles));
+    ScratchArena s{static_cast<char*>(scratch), 0};
+    a.active = s.take<unsigned>(kBatch);  // first: the memset of a batch starts at the allocation's start
+    a.flags = s.take<uint8_t>(2 * static_cast<size_t>(a.tiles));
+    return s.off;
 }
 
 __global__ __launch_bounds__(256) void k_pl_init(const PlArgs a, const uint8_t* __restrict__ classes,
@@ -201,7 +199,7 @@ __global__ __launch_bounds__(kScanBlock) void k_pl_finish(const unsigned* __rest
     __shared__ unsigned lds[kScanBlock / 64];
     const unsigned i = blockIdx.x * kScanBlock + threadIdx.x;
     unsigned total;
-    block_scan1(i < n && cost[i] < kBlocked ? 1u : 0u, total, lds);
+    block_exclusive_scan<kScanBlock / 64>(i < n && cost[i] < kBlocked ? 1u : 0u, total, lds);
     if (threadIdx.x == 0 && total) atomicAdd(counters + EMF_PLAN_FINITE, total);
     if (i == 0u) {
         counters[EMF_PLAN_CONVERGED] = converged;

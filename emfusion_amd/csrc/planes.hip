@@ -10,21 +10,23 @@
 //                        workgroup's count of records goes to the tile's u32, the two totals to the counters with one
 //                        integer atomic each.  A workgroup whose voxels all lie in tiles the volume's unseen-tile map
 //                        marks "every weight is 0" writes a count of 0 and leaves before it stages anything.
-//   k_pl_scan            one workgroup: the tiles' counts -> exclusive offsets in place, records written -> counters[2].
+//   k_pl_scan            one workgroup: the tiles' counts -> exclusive offsets in place (scan_sums of wave_ops.hpp), records
+//                        written -> counters[2].
 //   k_pl_surface<true>   the same walk; a tile without a record or wholly past the capacity leaves at once; the rank of a
 //                        record is the tile's offset plus the workgroup scan of the lanes' counts.  One 16-byte store per
 //                        record.  No atomic decides a position.
 //   k_pl_directions      a workgroup takes 8192 consecutive records into a cube-map histogram in LDS (6 K^2 u32, at most
 //                        23064 bytes) and adds the non-zero bins to the global one.
-//   k_pl_offsets         one lane per record; per direction the destination slot, then a segmented scan over the wave's
-//                        runs of equal destinations and one atomic per run (records are spatially ordered: runs are long).  The
-//                        scan is that of voxel_rays.hip over run numbers, since a destination can come back in a wave.
+//   k_pl_offsets         one lane per record; per direction the destination slot, then run_scan (wave_ops.hpp) over the
+//                        wave's runs of equal destinations and one atomic per run (records are spatially ordered: runs are
+//                        long).  Over run numbers (run_id), since a destination can come back in a wave.
 //   k_pl_assign          one lane per record; the label, then the ten sums and six bounds per run of equal labels.
 // Every float step is a single float32 operation through the _rn intrinsics, never contracted whatever the build; integer
 // atomics only: every output is a pure function of the inputs.  No scratch memory, no float atomics, no inline assembly.
 #include <cfloat>
 
 #include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace emf_hip {
 namespace {
@@ -33,7 +35,6 @@ constexpr int kPlBlock = 256;
 constexpr int kPlTX = 32, kPlTY = 8, kPlTZ = 8;       // the tile, and the tile of the unseen-tile map
 constexpr int kPlHX = kPlTX + 2, kPlHY = kPlTY + 2, kPlHZ = kPlTZ + 2;
 constexpr int kPlRowTasks = 10;                       // eight quads and the two halo voxels of a staged row
-constexpr int kPlScanBlock = 1024;
 constexpr unsigned kPlChunk = 8192;                   // records per workgroup of k_pl_directions
 constexpr unsigned long long kPlMaxTiles = 0xffffffull;
 
@@ -53,28 +54,6 @@ struct SurfArgs {
 };
 
 __device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= FLT_MAX; }
-
-// the workgroup's sum of v (all lanes get it) and this lane's exclusive prefix
-__device__ __forceinline__ unsigned block_scan(unsigned v, unsigned& total, unsigned* lds /* [kPlBlock / 64] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(inc, o);
-        if (lane >= o) inc += up;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    unsigned before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kPlBlock / 64; ++w) {
-        const unsigned t = lds[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    return before + inc - v;
-}
 
 template <bool EMIT>
 __global__ __launch_bounds__(kPlBlock) void k_pl_surface(const SurfArgs a) {
@@ -166,8 +145,9 @@ __global__ __launch_bounds__(kPlBlock) void k_pl_surface(const SurfArgs a) {
             norm |= 1u << e;
         }
     }
+    const unsigned counts = __popc(norm) | (__popc(surf) << 16);  // both at most 2048 over the workgroup
     unsigned total;
-    const unsigned before = block_scan(__popc(norm) | (__popc(surf) << 16), total, scanLds);  // both at most 2048
+    const unsigned before = block_exclusive_scan<kPlBlock / 64>(counts, total, scanLds);
     if (!EMIT) {
         if (threadIdx.x == 0) {
             a.tiles[b] = total & 0xffffu;
@@ -193,36 +173,11 @@ __global__ __launch_bounds__(kPlBlock) void k_pl_surface(const SurfArgs a) {
 }
 
 // one workgroup: tiles[b] := sum of tiles[0 .. b); counters[2] := min(total, capacity), counters[3] := 0
-__global__ __launch_bounds__(kPlScanBlock) void k_pl_scan(unsigned* tiles, unsigned ntiles, unsigned* counters, unsigned capacity) {
-    __shared__ unsigned lds[kPlScanBlock / 64];
-    __shared__ unsigned carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry = 0u;
-    __syncthreads();
-    for (unsigned start = 0; start < ntiles; start += kPlScanBlock) {
-        const unsigned i = start + threadIdx.x;
-        const unsigned v = i < ntiles ? tiles[i] : 0u;
-        unsigned inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned up = __shfl_up(inc, o);
-            if (lane >= o) inc += up;
-        }
-        if (lane == 63) lds[wave] = inc;
-        __syncthreads();
-        unsigned before = carry, total = 0u;
-        for (int w = 0; w < kPlScanBlock / 64; ++w) {
-            const unsigned t = lds[w];
-            if (w < wave) before += t;
-            total += t;
-        }
-        if (i < ntiles) tiles[i] = before + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += total;
-        __syncthreads();
-    }
+__global__ __launch_bounds__(kSumsBlock) void k_pl_scan(unsigned* tiles, unsigned ntiles, unsigned* counters, unsigned capacity) {
+    __shared__ unsigned lds[kSumsBlock / 64];
+    const unsigned total = scan_sums(tiles, 0u, ntiles, lds);
     if (threadIdx.x == 0) {
-        counters[2] = min(carry, capacity);
+        counters[2] = min(total, capacity);
         counters[3] = 0u;
     }
 }
@@ -300,14 +255,6 @@ struct OffArgs {
     unsigned* hist;
 };
 
-// The number of the run of neighbouring lanes with the same key that this lane lies in, counted from lane 0 of the wave.
-// Every lane of the wave must be here.  The same key can come back after another one: run numbers, unlike keys, ascend.
-__device__ __forceinline__ int run_id(int key, int lane) {
-    const int below = __shfl_up(key, 1);
-    const unsigned long long heads = __ballot(lane == 0 || below != key);
-    return __popcll(heads & (~0ull >> (63 - lane)));
-}
-
 __device__ __forceinline__ float dot3(float n0, float n1, float n2, float x, float y, float z) {
     return __fadd_rn(__fadd_rn(__fmul_rn(n0, x), __fmul_rn(n1, y)), __fmul_rn(n2, z));
 }
@@ -342,15 +289,8 @@ __global__ __launch_bounds__(kPlBlock) void k_pl_offsets(const OffArgs a) {
             if (s >= 0.f && s < static_cast<float>(a.S)) dest = k * a.S + static_cast<int>(s);
         }
         const int run = run_id(dest, lane);
-        unsigned votes = dest >= 0 ? 1u : 0u;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned below = __shfl_up(votes, o);
-            const int belowRun = __shfl_up(run, o);
-            if (lane >= o && belowRun == run) votes += below;  // run numbers ascend: every lane between shares it too
-        }
-        const int above = __shfl_down(run, 1);
-        if (dest >= 0 && (lane == 63 || above != run)) atomicAdd(&a.hist[dest], votes);
+        const unsigned votes = run_scan<OpAdd>(dest >= 0 ? 1u : 0u, lane, run);
+        if (run_is_last(run, lane) && dest >= 0) atomicAdd(&a.hist[dest], votes);
     }
 }
 
@@ -407,22 +347,10 @@ __global__ __launch_bounds__(kPlBlock) void k_pl_assign(const AssignArgs a) {
     int lo[3] = {ix, iy, iz}, hi[3] = {ix, iy, iz};
     const int run = run_id(label, lane);
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int belowRun = __shfl_up(run, o);       // by every lane, before the test: lane o reads lane 0
-        const bool take = lane >= o && belowRun == run;  // run numbers ascend: every lane between shares it too
+    for (int q = 0; q < 10; ++q) s[q] = run_scan<OpAdd>(s[q], lane, run);
 #pragma unroll
-        for (int q = 0; q < 10; ++q) {
-            const unsigned below = __shfl_up(s[q], o);
-            if (take) s[q] += below;
-        }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int bl = __shfl_up(lo[j], o), bh = __shfl_up(hi[j], o);
-            if (take) lo[j] = min(lo[j], bl), hi[j] = max(hi[j], bh);
-        }
-    }
-    const int above = __shfl_down(run, 1);
-    if (label < 0 || (lane != 63 && above == run)) return;  // not the last lane of a run of members
+    for (int j = 0; j < 3; ++j) lo[j] = run_scan<OpMin>(lo[j], lane, run), hi[j] = run_scan<OpMax>(hi[j], lane, run);
+    if (!run_is_last(run, lane) || label < 0) return;  // not the last lane of a run of members
     emf_plane_moments_t* m = a.moments + label;
     unsigned long long* w = reinterpret_cast<unsigned long long*>(m);  // count, sum[3], sum2[6]: the record's first ten words
 #pragma unroll
@@ -517,7 +445,7 @@ int emf_hip_planeSurface(const float* tsdf, const float* weights, const int32_t 
     const hipStream_t s = as_stream(stream);
     zero(counters, 4, s);
     hipLaunchKernelGGL(k_pl_surface<false>, dim3(a.ntiles), dim3(kPlBlock), 0, s, a);
-    hipLaunchKernelGGL(k_pl_scan, dim3(1), dim3(kPlScanBlock), 0, s, a.tiles, a.ntiles, counters, capacity);
+    hipLaunchKernelGGL(k_pl_scan, dim3(1), dim3(kSumsBlock), 0, s, a.tiles, a.ntiles, counters, capacity);
     if (capacity > 0u) hipLaunchKernelGGL(k_pl_surface<true>, dim3(a.ntiles), dim3(kPlBlock), 0, s, a);
     return launch_status("planeSurface");
 }

@@ -13,7 +13,7 @@
 //   k_pack_classify  one wave per chunk, one 16-byte load per lane; the decision is a ballot against the chunk's
 //                    first word; lane 0 writes the class byte and the word
 //   k_pack_sums      (uniform, literal) counts per workgroup of 256 chunks, both in one u64 (low / high half)
-//   k_pack_scan      one workgroup: exclusive scan of the sums in place, the totals behind them (as k_weld_scan)
+//   k_pack_scan      one workgroup: exclusive scan of the sums in place, the totals behind them (wave_ops.hpp)
 //   k_pack_place     rank[i] = chunks of i's class before i; uniform[rank] = the word, literalChunks[rank] = i.
 //                    Placement is by scan, not by atomics: the order is chunk order on every run
 //   k_pack_gather    one wave per literal of a rank range: chunk literalChunks[first + w] -> arena + 1024 w
@@ -22,6 +22,7 @@
 // Every byte offset is 64-bit (the 1024^3 tsdf is exactly 4 GiB); chunk indices and ranks fit 32 bits by the
 // entry's limit of 2^40 bytes.  A pure HBM stream: classify reads each byte once, gather re-reads the literals.
 #include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace emf_hip {
 namespace {
@@ -97,54 +98,17 @@ __device__ __forceinline__ unsigned long long class_count(const uint8_t* cls, un
     return c == 1u ? 1ull : (c == 2u ? (1ull << 32) : 0ull);
 }
 
-// the workgroup's sum of v (all lanes get it) and this lane's exclusive prefix; NW waves
-template <int NW>
-__device__ __forceinline__ unsigned long long block_scan(unsigned long long v, unsigned long long& total,
-                                                         unsigned long long* lds /* [NW] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long up = __shfl_up(inc, o);
-        if (lane >= o) inc += up;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    unsigned long long before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        const unsigned long long t = lds[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    __syncthreads();
-    return before + inc - v;
-}
-
 __global__ __launch_bounds__(kPackBlock) void k_pack_sums(const uint8_t* cls, unsigned nchunks, unsigned long long* sums) {
     __shared__ unsigned long long lds[kWavesPerBlock];
     unsigned long long total;
-    block_scan<kWavesPerBlock>(class_count(cls, blockIdx.x * kPackBlock + threadIdx.x, nchunks), total, lds);
+    block_exclusive_scan<kWavesPerBlock>(class_count(cls, blockIdx.x * kPackBlock + threadIdx.x, nchunks), total, lds);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
 // one workgroup: sums[b] := sum of sums[0 .. b), sums[nblocks] := the total, totals = {uniform, literal}
-__global__ __launch_bounds__(1024) void k_pack_scan(unsigned long long* sums, unsigned nblocks, unsigned* totals) {
-    __shared__ unsigned long long lds[16];
-    __shared__ unsigned long long carry;
-    if (threadIdx.x == 0) carry = 0ull;
-    __syncthreads();
-    for (unsigned start = 0; start < nblocks; start += 1024) {
-        const unsigned i = start + threadIdx.x;
-        const unsigned long long v = i < nblocks ? sums[i] : 0ull;
-        unsigned long long total;
-        const unsigned long long mine = block_scan<16>(v, total, lds);
-        if (i < nblocks) sums[i] = carry + mine;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += total;
-        __syncthreads();
-    }
+__global__ __launch_bounds__(kSumsBlock) void k_pack_scan(unsigned long long* sums, unsigned nblocks, unsigned* totals) {
+    __shared__ unsigned long long lds[kSumsBlock / 64];
+    const unsigned long long carry = scan_sums(sums, 0u, nblocks, lds);
     if (threadIdx.x == 0) {
         sums[nblocks] = carry;
         totals[0] = static_cast<unsigned>(carry);
@@ -158,7 +122,7 @@ __global__ __launch_bounds__(kPackBlock) void k_pack_place(const uint8_t* cls, c
     __shared__ unsigned long long lds[kWavesPerBlock];
     const unsigned i = blockIdx.x * kPackBlock + threadIdx.x;
     unsigned long long total;
-    const unsigned long long at = sums[blockIdx.x] + block_scan<kWavesPerBlock>(class_count(cls, i, nchunks), total, lds);
+    const unsigned long long at = sums[blockIdx.x] + block_exclusive_scan<kWavesPerBlock>(class_count(cls, i, nchunks), total, lds);
     if (i >= nchunks) return;
     const unsigned c = cls[i];
     // ranks stay below the class's total, which is at most nchunks: every array here has nchunks entries
@@ -266,7 +230,7 @@ int emf_hip_packRank(const uint8_t* classes, const uint32_t* words, uint64_t nby
     const unsigned nchunks = chunks_of(nbytes), nblocks = ceil_div(nchunks, kPackBlock);
     unsigned long long* sums = static_cast<unsigned long long*>(scratch_dev);
     hipLaunchKernelGGL(k_pack_sums, dim3(nblocks), dim3(kPackBlock), 0, as_stream(stream), classes, nchunks, sums);
-    hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(1024), 0, as_stream(stream), sums, nblocks, totals);
+    hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(kSumsBlock), 0, as_stream(stream), sums, nblocks, totals);
     hipLaunchKernelGGL(k_pack_place, dim3(nblocks), dim3(kPackBlock), 0, as_stream(stream), classes, words, nchunks,
                        static_cast<const unsigned long long*>(sums), ranks, uniform, literal_chunks);
     return launch_status("packRank");

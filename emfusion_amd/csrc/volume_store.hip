@@ -10,7 +10,7 @@
 //                     four consecutive voxels of a row in two z planes, 16-byte loads, every load issued before the
 //                     first compare; the verdict is __syncthreads_and against lane 0's first element
 //   k_spill_sums      arena units (8 KiB) per workgroup of 256 candidates
-//   k_spill_scan      one workgroup: exclusive scan of the sums in place, the total behind them (mesh_scan.hpp)
+//   k_spill_scan      one workgroup: exclusive scan of the sums in place, the total behind them (wave_ops.hpp)
 //   k_spill_place     lits[c][k] = the arena unit of candidate c's array k.  Placement is by scan, not by atomics:
 //                     candidate order, tsdf / weights / colour within a candidate, on every run
 //   k_spill_gather    one workgroup per tile again: the literal arrays -> arena, tile order (z, y, x; x fastest)
@@ -18,7 +18,7 @@
 //                     arena; thread 0 writes the tile's sign / unseen entries from the values just written
 // Every byte offset is 64-bit.  A pure HBM stream: classify reads each byte once, gather re-reads the literals.
 #include "device_core.hpp"
-#include "mesh_scan.hpp"
+#include "wave_ops.hpp"
 
 namespace emf_hip {
 namespace {
@@ -99,16 +99,14 @@ __device__ __forceinline__ unsigned units_of(const uint8_t* cls, unsigned i, uns
 __global__ __launch_bounds__(kScanBlock) void k_spill_sums(const uint8_t* cls, unsigned ncand, unsigned* sums) {
     __shared__ unsigned lds[kScanBlock / 64];
     unsigned total;
-    block_scan1(units_of(cls, blockIdx.x * kScanBlock + threadIdx.x, ncand), total, lds);
+    block_exclusive_scan<kScanBlock / 64>(units_of(cls, blockIdx.x * kScanBlock + threadIdx.x, ncand), total, lds);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(kSumsBlock) void k_spill_scan(unsigned* sums, unsigned nblocks, unsigned* totals) {
     __shared__ unsigned lds[kSumsBlock / 64];
-    __shared__ unsigned carry;
-    scan_sums(sums, nblocks, lds, &carry);
-    __syncthreads();
-    if (threadIdx.x == 0) totals[0] = sums[nblocks];
+    const unsigned total = scan_sums(sums, 0u, nblocks, lds);
+    if (threadIdx.x == 0) sums[nblocks] = totals[0] = total;
 }
 
 __global__ __launch_bounds__(kScanBlock) void k_spill_place(const uint8_t* cls, unsigned ncand, const unsigned* sums,
@@ -116,7 +114,7 @@ __global__ __launch_bounds__(kScanBlock) void k_spill_place(const uint8_t* cls, 
     __shared__ unsigned lds[kScanBlock / 64];
     const unsigned i = blockIdx.x * kScanBlock + threadIdx.x;
     unsigned total;
-    unsigned at = sums[blockIdx.x] + block_scan1(units_of(cls, i, ncand), total, lds);
+    unsigned at = sums[blockIdx.x] + block_exclusive_scan<kScanBlock / 64>(units_of(cls, i, ncand), total, lds);
     if (i >= ncand) return;
     const uint8_t* c = cls + 3 * static_cast<size_t>(i);
     unsigned* l = lits + 3 * static_cast<size_t>(i);

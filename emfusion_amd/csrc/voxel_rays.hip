@@ -8,12 +8,13 @@
 //               times at most, so a wave runs as long as its longest ray, whatever the memory holds.  The axis is
 //               chosen by selects, not branches: the lanes of a wave diverge only where their rays end.  A voxel is
 //               tested against the box before its class byte is read, and d2 only where the class passed.  After
-//               the loop the whole wave meets again: the six group quantities go through a segmented inclusive scan
-//               by lane shuffles (rays of a group are consecutive, so a group is one run of lanes), and the last lane
+//               the loop the whole wave meets again: the six group quantities go through run_scan of wave_ops.hpp
+//               (rays of a group are consecutive, so a group is one run of lanes), and the last lane
 //               of each run adds the run's sums to the group's record with one integer atomic per non-zero quantity.
 //               Integer sums: the records do not depend on the order of waves or workgroups.
 // The group records are zeroed by a memset on the stream before the launch.  No float, no LDS, no scratch memory.
 #include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace emf_hip {
 namespace {
@@ -32,18 +33,6 @@ struct RayArgs {
     unsigned passMask, countMask;
     int n, group;
 };
-
-// the sum over the lanes of this lane's run that are not above it (a run: consecutive lanes with the same `run`)
-template <typename T>
-__device__ __forceinline__ T run_scan(T v, int lane, int run) {
-#pragma unroll
-    for (int offset = 1; offset < 64; offset <<= 1) {
-        const T below = __shfl_up(v, offset);
-        const int belowRun = __shfl_up(run, offset);
-        if (lane >= offset && belowRun == run) v += below;  // runs are contiguous: every lane between shares it too
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(kVrBlock) void k_vr_cast(const RayArgs a) {
     const int lane = threadIdx.x & 63;
@@ -114,16 +103,16 @@ __global__ __launch_bounds__(kVrBlock) void k_vr_cast(const RayArgs a) {
         }
     }
     if (a.groups == nullptr) return;  // wave-uniform
-    // every lane of the wave is here: the lanes past the list form a run of their own that adds nothing
+    // every lane of the wave is here: the lanes past the list form a run of their own that adds nothing.  The group
+    // number ascends with the lane, so it is the run number (wave_ops.hpp)
     const int run = live ? static_cast<int>(i / a.group) : -1;
-    const unsigned long long sumCounted = run_scan<unsigned long long>(counted, lane, run);
-    const unsigned long long sumWeighted = run_scan<unsigned long long>(weighted, lane, run);
-    const unsigned sumReached = run_scan<unsigned>(live && status == EMF_RAY_REACHED ? 1u : 0u, lane, run);
-    const unsigned sumBlocked = run_scan<unsigned>(live && status == EMF_RAY_BLOCKED ? 1u : 0u, lane, run);
-    const unsigned sumLeft = run_scan<unsigned>(live && status == EMF_RAY_LEFT ? 1u : 0u, lane, run);
-    const unsigned sumInvalid = run_scan<unsigned>(live && status >= EMF_RAY_OUTSIDE ? 1u : 0u, lane, run);
-    const int above = __shfl_down(run, 1);
-    if (!live || (lane != 63 && above == run)) return;  // not the last lane of its run
+    const unsigned long long sumCounted = run_scan<OpAdd, unsigned long long>(counted, lane, run);
+    const unsigned long long sumWeighted = run_scan<OpAdd>(weighted, lane, run);
+    const unsigned sumReached = run_scan<OpAdd>(live && status == EMF_RAY_REACHED ? 1u : 0u, lane, run);
+    const unsigned sumBlocked = run_scan<OpAdd>(live && status == EMF_RAY_BLOCKED ? 1u : 0u, lane, run);
+    const unsigned sumLeft = run_scan<OpAdd>(live && status == EMF_RAY_LEFT ? 1u : 0u, lane, run);
+    const unsigned sumInvalid = run_scan<OpAdd>(live && status >= EMF_RAY_OUTSIDE ? 1u : 0u, lane, run);
+    if (!run_is_last(run, lane) || !live) return;
     emf_ray_group_t* g = a.groups + run;
     if (sumCounted) atomicAdd(reinterpret_cast<unsigned long long*>(&g->counted), sumCounted);
     if (sumWeighted) atomicAdd(reinterpret_cast<unsigned long long*>(&g->weighted), sumWeighted);

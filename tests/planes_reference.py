@@ -272,6 +272,20 @@ def assign_loop(rec, size, planes, cos2, band):
     return labels, mom
 
 
+RECURRING = [0, 1, 0, 0, 1, 1, 0, -1]
+
+
+def recurring_labels():
+    """(records, size, planes, cos2, band): 64 records, one wave of the assign kernel, whose labels are RECURRING eight
+    times over.  A label that comes back after another one is a run of its own: its sums must not cross the gap."""
+    size = (16, 16, 16)
+    rec = np.zeros(64, VOXEL)
+    for i in range(64):
+        z = {0: 3, 1: 11, -1: 7}[RECURRING[i % 8]]
+        rec[i] = ((z * size[1] + (7 * i) % 16) * size[0] + i % 16, (0.0, 0.0, 1.0))
+    return rec, size, np.array([(0, 0, 1, 3), (0, 0, 1, 11)], f32), f32(0.25), 0.5
+
+
 # ---- the host steps between the stages, Python floats ---------------------------------------------------------------
 
 def cell_centre(b, K):

@@ -31,7 +31,7 @@ GROUP = np.dtype([("counted", "<u8"), ("weighted", "<u8"), ("reached", "<u4"), (
 
 SHAPES = [(1, 1, 1), (1, 1, 65), (3, 5, 2), (8, 8, 32), (9, 17, 65), (19, 21, 70), (1, 2, 2048)]  # (nz, ny, nx)
 CONTENTS = pl.CONTENTS + ["sparse"]
-COUNTS = [0, 1, 63, 64, 65, 257]
+COUNTS = [0, 1, 63, 64, 65, 129, 257]  # 129: a third wave with one ray (tests/test_rays_reference_cpu.py has the run edges)
 GROUPS = [1, 3, 64, 100]
 
 

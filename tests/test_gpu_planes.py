@@ -39,6 +39,7 @@ CASES = [
     ((12, 10, 9), None, "infinite"),
     ((13, 5, 5), None, "zero_gradient"),
     ((40, 24, 20), None, "unseen"),
+    ((4, 328, 200), None, "random"),                          # 1 x 41 x 25 = 1025 tiles: the tile scan crosses its carry
 ]
 _expected = {}
 
@@ -225,6 +226,23 @@ def test_what_the_vote_cases_hold(dev):
     mid = size[2] // 2
     assert (z == mid).sum() > 20 and (labels[z == mid] == 0).all() and mom[1]["count"] == (z == mid + 1).sum() > 20
     assert mom[0]["count"] == (z == mid).sum() + (z == mid - 1).sum()
+
+
+def test_a_label_that_comes_back_is_a_run_of_its_own(dev):
+    """Labels A, B, A, A, B, B, A, none within one wave (tests/test_planes_reference_cpu.py checks that they are): the sums
+    and bounds of a run must not reach across another label to an earlier run of the same one."""
+    lib = lib_()
+    rec, size, planes, cos2, band = pr.recurring_labels()
+    want_labels, want_mom = pr.assign(rec, size, planes, cos2, band)
+    d_rec, d_cnt = to_dev(rec), to_dev(np.array([0, len(rec), len(rec), 0], np.uint32))
+    d_labels, d_mom = poisoned(len(rec) + EXTRA, np.int16), poisoned(len(planes) + EXTRA, pr.MOMENTS)
+    for again in (False, True):
+        assert lib.emf_hip_planeAssign(ptr(d_rec), ptr(d_cnt), len(rec), i3(size), fp(planes), len(planes), float(cos2), band,
+                                       ptr(d_labels), ptr(d_mom), None) == 0
+        got_labels, got_mom = d_labels.numpy(), d_mom.numpy()
+        assert got_labels[:len(rec)].tobytes() == want_labels.tobytes(), again
+        assert got_mom[:len(planes)].tobytes() == want_mom.tobytes(), (again, got_mom[:len(planes)], want_mom)
+        assert (got_labels[len(rec):].view(np.uint8) == POISON).all() and (got_mom[len(planes):].view(np.uint8) == POISON).all()
 
 
 @pytest.mark.parametrize("case", [CASES[8], CASES[9], CASES[17], CASES[7]], ids=case_id)

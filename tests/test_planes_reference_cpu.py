@@ -46,6 +46,30 @@ def test_the_fixtures_hold_what_their_names_say():
     assert pr.records(tsdf, weights)[1][1] > 50
 
 
+def test_the_carry_case_has_records_on_both_sides_of_the_carry():
+    """The case of tests/test_gpu_planes.py with more than 1024 tiles: the one workgroup that scans the tiles' counts
+    takes them 1024 at a time, and a tile behind the first 1024 holds a record whose rank needs what came before."""
+    from tests.test_gpu_planes import CASES
+    shape, box, content = CASES[-1]
+    assert box is None and content == "random"
+    ntx, nty, ntz = (-(-shape[k] // pr.TILE[k]) for k in range(3))
+    assert ntx * nty * ntz > 1024
+    rec, counts = pr.records(*pr.volume(shape, content))
+    x, y, z = pr.voxel_of(rec["index"], shape)
+    tile = ((z // pr.TILE[2]) * nty + y // pr.TILE[1]) * ntx + x // pr.TILE[0]
+    assert (np.diff(tile) >= 0).all()  # records are in tile order
+    assert (tile >= 1024).sum() >= 1 and (tile < 1024).sum() >= 1
+
+
+def test_the_recurring_labels_recur():
+    rec, size, planes, cos2, band = pr.recurring_labels()
+    labels, mom = pr.assign(rec, size, planes, cos2, band)
+    assert labels.tolist() == pr.RECURRING * 8  # A, B, A within one wave of 64 records, and lanes without a label
+    assert mom[0]["count"] == 32 and mom[1]["count"] == 24
+    a, b = pr.assign_loop(rec, size, planes, cos2, band)
+    assert a.tobytes() == labels.tobytes() and b.tobytes() == mom.tobytes()
+
+
 def truth(k):
     n, d = pr.ROOM_PLANES[k]
     return np.asarray(n) / np.linalg.norm(n), d

@@ -129,6 +129,32 @@ def test_a_group_of_full_rows_exceeds_32_bits():
     assert rr.group_records(rec, 3)["weighted"][0] > 2 ** 32
 
 
+def test_the_counts_and_groups_hold_every_run_edge():
+    """What steers the run scan of the group sums (csrc/wave_ops.hpp): ray i sits in lane i % 64 of wave i // 64 and its
+    run is group i // group.  Over COUNTS x GROUPS: a run that ends at lane 63 with the next wave going on in another
+    group, a run that is a whole wave, a group split across two waves, every lane a run of its own, and a last wave
+    with a single live lane."""
+    seen = set()
+    for n in rr.COUNTS:
+        for group in rr.GROUPS:
+            i = np.arange(n)
+            g, wave = i // group, i // 64
+            for w in range(-(-n // 64)):
+                runs = g[wave == w]
+                if len(runs) == 64 and runs[0] == runs[-1] and (g == runs[0]).sum() == 64:
+                    seen.add("whole wave")
+                if len(runs) == 64 and 64 * (w + 1) < n and g[64 * (w + 1)] != runs[-1]:
+                    seen.add("ends at lane 63")
+                if 64 * (w + 1) < n and g[64 * (w + 1)] == runs[-1]:
+                    seen.add("split across two waves")
+                if len(runs) == 64 and len(set(runs)) == 64:
+                    seen.add("every lane a run")
+                if len(runs) == 1 and w == 2:
+                    seen.add("one live lane")
+    assert seen == {"whole wave", "ends at lane 63", "split across two waves", "every lane a run", "one live lane"}
+    assert 129 in rr.COUNTS and {1, 64} <= set(rr.GROUPS)
+
+
 def rot(axis, angle):
     c, s = np.cos(angle), np.sin(angle)
     m = {"x": [[1, 0, 0], [0, c, -s], [0, s, c]], "y": [[c, 0, s], [0, 1, 0], [-s, 0, c]], "z": [[c, -s, 0], [s, c, 0], [0, 0, 1]]}
