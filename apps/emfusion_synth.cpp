@@ -10,6 +10,7 @@
 //                  [--plan] [--plan-clearance M] [--plan-through-unknown] [--plan-shortcut W] [--object-shapes]
 //                  [--ground-map] [--ground-up X,Y,Z] [--ground-cell M] [--ground-bin M] [--ground-band LO,HI]
 //                  [--ground-robot-height M] [--ground-max-step M] [--planes] [--planes-angle DEG] [--planes-min-votes N]
+//                  [--plane-patches] [--plane-patch-reach R] [--plane-patch-min N]
 //   emfusion_synth --sequence DIR/ [--masks DIR] [--mask-frames N] [--visibility-thresh N] [--frames N]
 //                  [--bg-res R] [--bg-voxel M] [--obj-res R] [--volumes] --out DIR
 //   emfusion_synth --dir BASE/ [--colordir colour] [--depthdir depth] [--intrinsics fx fy cx cy] ... --out DIR
@@ -139,6 +140,11 @@ static bool groundGiven = false, groundBad = false, groundUpFloor = false;
 // 200)); without --planes no output byte changes
 static emf::EMFusion::PlanesOutput planesOut;
 static bool planesGiven = false;
+// --plane-patches (needs --planes): planes.txt also lists every plane's connected patches and, with --object-shapes, which
+// patch each object rests on; --plane-patch-reach R (1 or 2, default 1), --plane-patch-min N (default:
+// max(25, min votes / 4)); without --plane-patches no output byte changes
+static emf::EMFusion::PlanePatchesOutput patchesOut;
+static bool patchesGiven = false;
 // "a,b[,c]" into n doubles; false if it does not hold n numbers
 static bool parseList(const char* text, double* out, int n) {
     char* end = nullptr;
@@ -261,6 +267,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     if (groundOut.on) emf.setGroundOutput(groundOut);
     if (groundUpFloor) emf.setGroundUpFloor(true);
     if (planesOut.on) emf.setPlanesOutput(planesOut);
+    if (patchesOut.on) emf.setPlanePatchesOutput(patchesOut);
     set3dView(emf, params, view3d);
     std::vector<uint8_t> rendered(3 * params.frameSize.area());
     const auto t0 = std::chrono::steady_clock::now();
@@ -376,6 +383,9 @@ int main(int argc, char** argv) {
         else if (a == "--planes") planesOut.on = true;
         else if (a == "--planes-angle" && i + 1 < argc) planesGiven = true, planesOut.angle = std::atof(argv[++i]);
         else if (a == "--planes-min-votes" && i + 1 < argc) planesGiven = true, planesOut.minVotes = std::atoll(argv[++i]);
+        else if (a == "--plane-patches") patchesOut.on = true;
+        else if (a == "--plane-patch-reach" && i + 1 < argc) patchesGiven = true, patchesOut.reach = std::atoi(argv[++i]);
+        else if (a == "--plane-patch-min" && i + 1 < argc) patchesGiven = true, patchesOut.minCount = std::atoll(argv[++i]);
         else if (a == "--ground-band" && i + 1 < argc) {
             double band[2] = {0.0, 0.0};
             groundGiven = true, groundBad |= !parseList(argv[++i], band, 2);
@@ -434,6 +444,11 @@ int main(int argc, char** argv) {
     if ((planesGiven && !planesOut.on) || (planesOut.on && (outDir.empty() || !(planesOut.angle > 0.0 && planesOut.angle <= 90.0)))) {
         std::fprintf(stderr, "usage: emfusion_synth: --planes-angle DEG (in (0, 90]) and --planes-min-votes N need --planes, which "
                              "writes planes.txt and needs --out DIR\n");
+        return 2;
+    }
+    if ((patchesGiven && !patchesOut.on) || (patchesOut.on && (!planesOut.on || patchesOut.reach < 1 || patchesOut.reach > EMF_PLANE_MAX_REACH))) {
+        std::fprintf(stderr, "usage: emfusion_synth: --plane-patch-reach R (1 or 2) and --plane-patch-min N need --plane-patches, which "
+                             "adds the patch lines to planes.txt and needs --planes\n");
         return 2;
     }
     if (motionMasks && !maskDir.empty()) {  // (before any device is touched)
@@ -526,6 +541,7 @@ int main(int argc, char** argv) {
         if (groundOut.on) emf.setGroundOutput(groundOut);
         if (groundUpFloor) emf.setGroundUpFloor(true);
         if (planesOut.on) emf.setPlanesOutput(planesOut);
+    if (patchesOut.on) emf.setPlanePatchesOutput(patchesOut);
         set3dView(emf, params, view3d);
         std::vector<uint8_t> rendered(3 * P);
 

@@ -109,6 +109,13 @@ def main():
                     help="with --planes: the alignment gate in degrees")
     ap.add_argument("--planes-min-votes", dest="planes_min_votes", type=int, default=None, metavar="N",
                     help="with --planes: the votes a direction and an offset need (default: max(50, records / 200))")
+    ap.add_argument("--plane-patches", dest="plane_patches", action="store_true",
+                    help="with --planes: planes.txt also lists every plane's connected patches (id, count, world point, the four "
+                         "corners of its rectangle, fill) and, with --object-shapes, which patch each object rests on")
+    ap.add_argument("--plane-patch-reach", dest="plane_patch_reach", type=int, default=None, metavar="R",
+                    help="with --plane-patches: members within R voxels of each other (1 or 2) are one patch (default 1)")
+    ap.add_argument("--plane-patch-min", dest="plane_patch_min", type=int, default=None, metavar="N",
+                    help="with --plane-patches: the members a patch needs (default: max(25, min votes / 4))")
     ap.add_argument("--ground-cell", dest="ground_cell", type=float, default=None, metavar="M",
                     help="with --ground-map: the side of a ground cell in metres (default: two voxels)")
     ap.add_argument("--ground-bin", dest="ground_bin", type=float, default=None, metavar="M",
@@ -156,6 +163,12 @@ def main():
         ap.error("--plan-shortcut W adds the waypoints lines to plan.txt and needs --plan")
     if args.plan_shortcut < 0:
         ap.error("--plan-shortcut takes a positive window W")
+    if args.plane_patches and not args.planes:
+        ap.error("--plane-patches adds the patch lines to planes.txt and needs --planes")
+    if (args.plane_patch_reach is not None or args.plane_patch_min is not None) and not args.plane_patches:
+        ap.error("--plane-patch-reach and --plane-patch-min need --plane-patches")
+    if args.plane_patch_reach is not None and args.plane_patch_reach not in (1, 2):
+        ap.error("--plane-patch-reach takes 1 or 2")
     try:
         follow_step = tuple(int(v) for v in args.follow_step.split(","))
         assert len(follow_step) == 3
@@ -229,6 +242,8 @@ def main():
                      ground_up=None if args.ground_up is None else "floor" if args.ground_up == "floor"
                      else [float(v) for v in args.ground_up.split(",")],
                      exp_planes=args.planes, planes_angle=args.planes_angle, planes_min_votes=args.planes_min_votes,
+                     exp_plane_patches=args.plane_patches, plane_patch_reach=args.plane_patch_reach or 1,
+                     plane_patch_min=args.plane_patch_min,
                      ground_cell=args.ground_cell, ground_bin=args.ground_bin,
                      ground_band=[float(v) for v in args.ground_band.split(",")],
                      ground_robot_height=args.ground_robot_height, ground_max_step=args.ground_max_step)  # EMFusion::setupOutput of the reference app (apps/EM-Fusion.cpp:112)

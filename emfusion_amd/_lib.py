@@ -231,6 +231,10 @@ SIGNATURES = {
                              C.c_float, C.c_int32, _FP, _STREAM],
     "emf_hip_planeAssign": [_FP, _FP, C.c_uint32, _I3, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_float, _FP, _FP,
                             _STREAM],
+    "emf_hip_planePatchLabel": [_FP, _FP, _FP, C.c_uint32, _I3, C.c_int32, _FP, _FP, _STREAM],
+    "emf_hip_planePatchScratchBytes": [C.c_uint32, C.c_uint32],
+    "emf_hip_planePatches": [_FP, _FP, _FP, _FP, C.c_uint32, _I3, C.POINTER(C.c_float), C.c_int32, C.c_int64, C.c_uint32, _FP,
+                             _FP, C.c_int32, _FP, _STREAM],
 }
 
 
@@ -345,6 +349,11 @@ PLANE_VOXEL_DTYPE = [("index", "<i4"), ("g", "<f4", 3)]
 PLANE_MOMENTS_DTYPE = [("count", "<u8"), ("sum", "<u8", 3), ("sum2", "<u8", 6), ("lo", "<i4", 3), ("hi", "<i4", 3)]
 PLANE_MAX_K, PLANE_MAX_DIRS, PLANE_MAX_SLOTS, PLANE_MAX_PLANES = 31, 16, 4096, 64
 PLANE_SURFACE, PLANE_NORMALS, PLANE_WRITTEN = 0, 1, 2  # the counters of emf_hip_planeSurface
+# emf_plane_patch_t (128 bytes), the counters of emf_hip_planePatchLabel / emf_hip_planePatches
+PLANE_PATCH_DTYPE = [("id", "<i4"), ("plane", "<i4"), ("count", "<u8"), ("sum", "<u8", 3), ("sum2", "<u8", 6), ("lo", "<i4", 3),
+                     ("hi", "<i4", 3), ("ulo", "<f4"), ("uhi", "<f4"), ("vlo", "<f4"), ("vhi", "<f4")]
+PLANE_MAX_REACH = 2
+PATCH_KEPT, PATCH_PATCHES, PATCH_MEMBERS = 0, 1, 2
 RAY_REACHED, RAY_BLOCKED, RAY_LEFT, RAY_OUTSIDE, RAY_INVALID = 0, 1, 2, 3, 4
 FRONTIER_KEPT, FRONTIER_CLUSTERS, FRONTIER_VOXELS = 0, 1, 2
 # include/emf_hip.h "Planning"
@@ -459,6 +468,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.emf_hip_nearestSiteScratchBytes.restype = C.c_size_t
     lib.emf_hip_planScratchBytes.restype = C.c_size_t
     lib.emf_hip_planeSurfaceScratchBytes.restype = C.c_size_t
+    lib.emf_hip_planePatchScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateCullScratchBytes.restype = C.c_size_t
     lib.emf_hip_integrateDirtyMapBytes.restype = C.c_size_t
     lib.emf_hip_signMapBytes.restype = C.c_size_t

@@ -592,6 +592,37 @@ public:
      */
     const Planes& planes(const Vec3i& boxLo, const Vec3i& boxSize, const emf_plane_params_t& params, bool keepLabels = false);
     const Planes& lastPlanes() const { return pnLast; }
+    /** The result of planePatches(): the kept patches in ascending id order and what stays on the device. */
+    struct PlanePatches {
+        uint32_t counters[3] = {0, 0, 0};  // EMF_PATCH_KEPT, _PATCHES, _MEMBERS
+        int reach = 0;
+        int64_t minCount = 0;
+        std::vector<emf_plane_patch_t> patches;
+        const int32_t* ids = nullptr;  // device, one per record of the planes it was computed from; NULL without a plane
+    };
+    /**
+     * Plane patches (include/emf_hip.h "Planes", stage 4): the planes of the last planes() split into
+     * connected surfaces -- two tables of one height are two patches of one plane.  Works on the records and labels that
+     * planes() left on the device and refuses (EMF_E_ARG) where there are none; the extents are taken along each plane's
+     * own in-plane axes, rounded to f32 once.  Waits twice: for the number of patches, then for the records.  Changes
+     * nothing of the session and nothing goes into a checkpoint.  Refused (EMF_E_ARG) on the sharded path.
+     */
+    const PlanePatches& planePatches(int reach, int64_t minCount);
+    const PlanePatches& lastPlanePatches() const { return ppLast; }
+    /** A patch in the world frame (describePlanePatches). */
+    struct PatchWorld {
+        int plane = -1;  // index into Planes::planes
+        int32_t id = 0;
+        emf_plane_patch_rect_t rect;  // box voxel coordinates
+        double point[3] = {0, 0, 0}, normal[3] = {0, 0, 0}, d = 0.0;  // the patch's own fit
+        double center[3] = {0, 0, 0}, axes[6] = {0, 0, 0, 0, 0, 0}, halfM[2] = {0, 0}, corners[12] = {};  // the rectangle
+    };
+    /**
+     * The patches of a result in the world frame, plane by plane in the planes' order, inside a plane by count descending,
+     * ties to the lower id.  Points go through QueryBox::worldPoint, directions through the background's rotation,
+     * lengths times the voxel size; float64, sums left to right.  pipeline.plane_patch_world states the same in Python.
+     */
+    static void describePlanePatches(const Planes& planes, const PlanePatches& patches, std::vector<PatchWorld>& out);
     /** A plane of planes() in the world frame, with its kind (describePlanes). */
     struct PlaneWorld {
         double normal[3] = {0, 0, 0}, point[3] = {0, 0, 0}, d = 0.0;  // normal . x = d; the point is the members' centroid
@@ -617,6 +648,15 @@ public:
     /** writeResults also writes planes.txt of the whole background (writePlanes); without it no output byte changes. */
     void setPlanesOutput(const PlanesOutput& p) { expPlanes_ = p; }
     void writePlanes(const std::string& dir);
+    /** The parameters of setPlanePatchesOutput. */
+    struct PlanePatchesOutput {
+        bool on = false;
+        int reach = 1;
+        int64_t minCount = 0;  // <= 0: max(25, min_votes / 4) of the planes
+    };
+    /** With setPlanesOutput on, planes.txt also lists every plane's patches and, with setShapeOutput on as well, which
+     *  patch each object rests on (writePlanes); without it no output byte changes. */
+    void setPlanePatchesOutput(const PlanePatchesOutput& p) { expPatches_ = p; }
     /** setGroundOutput's up becomes the normal of the floor planes() finds in the whole background (an error where it
      *  finds none): --ground-up floor. */
     void setGroundUpFloor(bool on) { expGroundUpFloor_ = on; }
@@ -1194,6 +1234,11 @@ private:
     Planes pnLast;
     DeviceBuffer pnRecords, pnLabels, pnScratch, pnSmall;  // the records, their labels, the tiles' counts; counters, moments and votes
     PlanesOutput expPlanes_;         // setPlanesOutput
+    // ---- plane patches (planePatches; EMFusionPlanes.cpp): as the planes' buffers
+    PlanePatches ppLast;
+    PlanePatchesOutput expPatches_;  // setPlanePatchesOutput
+    uint32_t pnCapacity = 0;         // the capacity planes() gave stage 1: what the later stages bound the count by
+    DeviceBuffer ppIds, ppScratch, ppOut, ppSmall;  // the ids, the slots' scratch, the records, the three counters
     bool expGroundUpFloor_ = false;  // setGroundUpFloor
 };
 
@@ -1244,6 +1289,15 @@ std::vector<PlaneDirection> planeDirections(const uint32_t* bins, int K, uint32_
 PlaneOffsetFrame planeOffsetFrame(const double n[3], const int32_t size[3], double binVox);
 std::vector<std::pair<int, uint32_t>> planePeaks(const uint32_t* row, int slots, uint32_t minVotes, int peakGap);
 void planeFit(const emf_plane_moments_t& mom, const double seedN[3], double seedD, emf_plane_t& out);
+/** The fit, the rectangle and the fill of a patch from its plane (include/emf_hip.h, the host steps behind stage 4). */
+void planePatchRect(const emf_plane_t& plane, const emf_plane_patch_t& patch, emf_plane_patch_rect_t& out);
+/**
+ * One oriented box against one patch, world metres: s = (n . c - d) - sum_k |n . A_k| * h_k, the height
+ * of the box's lowest point above the patch's plane, and whether the box centre, in the rectangle's axes about its
+ * centre, lies within half + margin.  Float64, every line a single operation, sums left to right.
+ */
+bool planeSupport(const double n[3], double d, const double center[3], const double axes[6], const double half[2],
+                  const double boxCenter[3], const double boxAxes[9], const double boxHalf[3], double margin, double& s);
 /**
  * The box of a model from its frame and its extents along that frame: centre and half extents in voxels, completeness,
  * then metres in the model's own frame and the world frame through its pose (R, t: volume -> world).  Float64 in the

@@ -16,6 +16,7 @@ namespace emf {
 namespace {
 
 constexpr double kPi = 3.141592653589793;
+constexpr double kSupportGap = 0.05;  // metres: the policy of the support lines of planes.txt
 
 double dot3(const double a[3], const double b[3]) {
     double s = a[0] * b[0];
@@ -119,10 +120,163 @@ void planeFit(const emf_plane_moments_t& mom, const double seedN[3], double seed
     out.fitted = 1;
 }
 
+void planePatchRect(const emf_plane_t& plane, const emf_plane_patch_t& patch, emf_plane_patch_rect_t& out) {
+    std::memset(&out, 0, sizeof(out));
+    emf_plane_moments_t mom{};
+    mom.count = patch.count;
+    for (int j = 0; j < 3; ++j) mom.sum[j] = patch.sum[j], mom.lo[j] = patch.lo[j], mom.hi[j] = patch.hi[j];
+    for (int j = 0; j < 6; ++j) mom.sum2[j] = patch.sum2[j];
+    planeFit(mom, plane.n, plane.d, out.fit);  // called, not restated
+    out.fit.label = plane.label;
+    const double* u = plane.axes;
+    const double* v = plane.axes + 3;
+    const double a0 = static_cast<double>(patch.ulo) - 0.5;
+    const double a1 = static_cast<double>(patch.uhi) + 0.5;
+    const double b0 = static_cast<double>(patch.vlo) - 0.5;
+    const double b1 = static_cast<double>(patch.vhi) + 0.5;
+    const double su = a0 + a1, cu = su * 0.5;
+    const double du = a1 - a0, hu = du * 0.5;
+    const double sv = b0 + b1, cv = sv * 0.5;
+    const double dv = b1 - b0, hv = dv * 0.5;
+    auto point = [&](double eu, double ev, double* p) {
+        for (int j = 0; j < 3; ++j) {
+            double s = plane.d * plane.n[j];
+            double t = u[j] * eu;
+            s = s + t;
+            t = v[j] * ev;
+            s = s + t;
+            p[j] = s;
+        }
+    };
+    point(cu, cv, out.center);
+    out.half[0] = hu, out.half[1] = hv;
+    const double sign[4][2] = {{-1.0, -1.0}, {1.0, -1.0}, {1.0, 1.0}, {-1.0, 1.0}};
+    for (int k = 0; k < 4; ++k) {
+        const double ou = sign[k][0] * hu, ov = sign[k][1] * hv;
+        const double eu = cu + ou, ev = cv + ov;
+        point(eu, ev, out.corners + 3 * k);
+    }
+    double wu = static_cast<double>(patch.uhi) - static_cast<double>(patch.ulo);
+    wu = wu + 1.0;
+    double wv = static_cast<double>(patch.vhi) - static_cast<double>(patch.vlo);
+    wv = wv + 1.0;
+    const double nmax = std::max(std::fabs(plane.n[0]), std::max(std::fabs(plane.n[1]), std::fabs(plane.n[2])));
+    double area = wu * wv;
+    area = area * nmax;
+    out.fill = static_cast<double>(patch.count) / area;
+}
+
+bool planeSupport(const double n[3], double d, const double center[3], const double axes[6], const double half[2],
+                  const double boxCenter[3], const double boxAxes[9], const double boxHalf[3], double margin, double& s) {
+    s = dot3(n, boxCenter);
+    s = s - d;
+    for (int k = 0; k < 3; ++k) {
+        const double a = dot3(n, boxAxes + 3 * k);
+        const double r = std::fabs(a) * boxHalf[k];
+        s = s - r;
+    }
+    const double q[3] = {boxCenter[0] - center[0], boxCenter[1] - center[1], boxCenter[2] - center[2]};
+    bool over = true;
+    for (int j = 0; j < 2; ++j) {
+        const double a = dot3(q, axes + 3 * j);
+        const double reach = half[j] + margin;
+        over = over && std::fabs(a) <= reach;
+    }
+    return over;
+}
+
+const EMFusion::PlanePatches& EMFusion::planePatches(int reach, int64_t minCount) {
+    if (sharded || world > 1) throw HipError("EMFusion::planePatches: the plane search is not supported on the sharded path", EMF_E_ARG);
+    if (!pnLast.records) throw HipError("EMFusion::planePatches: no planes have been computed", EMF_E_ARG);
+    if (reach < 1 || reach > EMF_PLANE_MAX_REACH)
+        throw HipError("EMFusion::planePatches: a reach outside 1 .. 2", reach < 1 ? EMF_E_ARG : EMF_E_LIMIT);
+    if (minCount < 1) throw HipError("EMFusion::planePatches: min_count below 1", EMF_E_ARG);
+    PlanePatches out;
+    out.reach = reach, out.minCount = minCount;
+    ppLast = PlanePatches();  // a call that throws leaves no result
+    if (!pnLast.labels) {     // no plane: no member, no patch
+        ppLast = out;
+        return ppLast;
+    }
+    int P = 0;
+    for (const emf_plane_t& p : pnLast.planes) P = std::max(P, p.label + 1);
+    std::vector<float> axes(6 * static_cast<size_t>(P), 0.f);
+    for (const emf_plane_t& p : pnLast.planes)
+        for (int j = 0; j < 6; ++j) axes[6 * static_cast<size_t>(p.label) + j] = static_cast<float>(p.axes[j]);
+    const uint32_t capacity = pnCapacity;
+    auto* dCounters = pnSmall.as<uint32_t>();
+    ppIds.reserve(static_cast<size_t>(capacity) * sizeof(int32_t));
+    ppSmall.reserve(16);
+    auto* dPc = ppSmall.as<uint32_t>();
+    emfCheck(emf_hip_planePatchLabel(pnLast.records, pnLast.labels, dCounters, capacity, pnLast.box.size.val, reach, ppIds.as<int32_t>(),
+                                     dPc, main.abi()), "EMFusion::planePatches (label)");
+    hipCheck(hipMemcpyAsync(out.counters, dPc, 12, hipMemcpyDeviceToHost, main.get()), "EMFusion::planePatches (counters)");
+    main.waitForCompletion();  // wait 1: the scratch and the records are sized by the number of patches
+    const uint32_t nPatches = out.counters[EMF_PATCH_PATCHES];
+    out.ids = ppIds.as<int32_t>();
+    if (nPatches == 0u) {
+        ppLast = out;
+        return ppLast;
+    }
+    ppScratch.reserve(std::max<size_t>(emf_hip_planePatchScratchBytes(capacity, nPatches), 16));
+    ppOut.reserve(static_cast<size_t>(nPatches) * sizeof(emf_plane_patch_t));
+    emfCheck(emf_hip_planePatches(pnLast.records, pnLast.labels, ppIds.as<int32_t>(), dCounters, capacity, pnLast.box.size.val,
+                                  axes.data(), P, minCount, nPatches, ppScratch.data(), ppOut.as<emf_plane_patch_t>(),
+                                  static_cast<int32_t>(std::min<uint32_t>(nPatches, 0x7fffffffu)), dPc, main.abi()),
+             "EMFusion::planePatches (records)");
+    out.patches.resize(nPatches);
+    hipCheck(hipMemcpyAsync(out.counters, dPc, 12, hipMemcpyDeviceToHost, main.get()), "EMFusion::planePatches (kept)");
+    hipCheck(hipMemcpyAsync(out.patches.data(), ppOut.data(), static_cast<size_t>(nPatches) * sizeof(emf_plane_patch_t),
+                            hipMemcpyDeviceToHost, main.get()), "EMFusion::planePatches (patches)");
+    main.waitForCompletion();  // wait 2: the records
+    out.patches.resize(out.counters[EMF_PATCH_KEPT]);  // behind the kept ones nothing was written
+    ppLast = out;
+    return ppLast;
+}
+
+void EMFusion::describePlanePatches(const Planes& r, const PlanePatches& pp, std::vector<PatchWorld>& out) {
+    out.clear();
+    const float* R = r.box.bgPose.rotation().val;
+    const double vs = static_cast<double>(r.box.voxelSize);
+    auto rotate = [&](const double* a, double* w) {
+        for (int i = 0; i < 3; ++i) {
+            double s = static_cast<double>(R[3 * i]) * a[0];
+            s = s + static_cast<double>(R[3 * i + 1]) * a[1];
+            s = s + static_cast<double>(R[3 * i + 2]) * a[2];
+            w[i] = s;
+        }
+    };
+    for (size_t k = 0; k < r.planes.size(); ++k) {
+        const emf_plane_t& plane = r.planes[k];
+        std::vector<const emf_plane_patch_t*> mine;
+        for (const emf_plane_patch_t& p : pp.patches)
+            if (p.plane == plane.label) mine.push_back(&p);
+        std::stable_sort(mine.begin(), mine.end(), [](const emf_plane_patch_t* a, const emf_plane_patch_t* b) { return a->count > b->count; });
+        for (const emf_plane_patch_t* p : mine) {
+            PatchWorld w;
+            w.plane = static_cast<int>(k), w.id = p->id;
+            planePatchRect(plane, *p, w.rect);
+            const emf_plane_t& f = w.rect.fit;
+            rotate(f.n, w.normal);
+            double m[3];
+            for (int i = 0; i < 3; ++i) m[i] = f.fitted ? f.centroid[i] : f.n[i] * f.d;  // a point of the patch's plane
+            r.box.worldPoint(m, w.point);
+            w.d = dot3(w.normal, w.point);
+            r.box.worldPoint(w.rect.center, w.center);
+            rotate(plane.axes, w.axes);
+            rotate(plane.axes + 3, w.axes + 3);
+            w.halfM[0] = w.rect.half[0] * vs, w.halfM[1] = w.rect.half[1] * vs;
+            for (int c = 0; c < 4; ++c) r.box.worldPoint(w.rect.corners + 3 * c, w.corners + 3 * c);
+            out.push_back(w);
+        }
+    }
+}
+
 const EMFusion::Planes& EMFusion::planes(const Vec3i& boxLo, const Vec3i& boxSize, const emf_plane_params_t& p, bool keepLabels) {
     Planes out;
     out.box = makeQueryBox("planes", "the plane search is", boxLo, boxSize);
     pnLast = Planes();  // a call that throws leaves no result: the buffers of the last one are about to be rewritten
+    ppLast = PlanePatches();  // ... and the patches of the last one are those of records that are about to go
     if (p.K < 1 || p.K > EMF_PLANE_MAX_K) throw HipError("EMFusion::planes: K outside 1 .. 31", p.K < 1 ? EMF_E_ARG : EMF_E_LIMIT);
     if (p.refine < 0 || p.max_planes < 1 || p.max_planes > EMF_PLANE_MAX_PLANES || p.peak_gap < 0)
         throw HipError("EMFusion::planes: refine, max_planes or peak_gap outside its range", EMF_E_ARG);
@@ -137,6 +291,7 @@ const EMFusion::Planes& EMFusion::planes(const Vec3i& boxLo, const Vec3i& boxSiz
     const size_t voxels = out.box.voxels();
     // a surface is about one voxel in a hundred; an eighth of the box (at least 2^16 records) holds any scene worth asking
     const uint32_t capacity = static_cast<uint32_t>(std::min(voxels, std::max<size_t>(size_t(1) << 16, voxels / 8)));
+    pnCapacity = capacity;
     const size_t nb = 6 * static_cast<size_t>(p.K) * p.K;
     const size_t histWords = static_cast<size_t>(EMF_PLANE_MAX_DIRS) * EMF_PLANE_MAX_SLOTS;
     pnRecords.reserve(static_cast<size_t>(capacity) * sizeof(emf_plane_voxel_t));
@@ -284,6 +439,18 @@ void EMFusion::writePlanes(const std::string& dir) {
     std::vector<PlaneWorld> world;
     const double up[3] = {0.0, 0.0, 0.0};
     describePlanes(r, up, 30.0, 10.0, world);
+    std::vector<PatchWorld> patchWorld;  // stays empty without setPlanePatchesOutput: the file is as before
+    std::vector<ObjectShape> shapes;
+    if (expPatches_.on) {
+        const int64_t minCount = expPatches_.minCount > 0 ? expPatches_.minCount : std::max<int64_t>(25, r.minVotes / 4);
+        describePlanePatches(r, planePatches(expPatches_.reach, minCount), patchWorld);
+        if (expShapes_) {
+            std::vector<int> ids;
+            for (const ObjTSDF& obj : objects) ids.push_back(obj.getID());
+            std::sort(ids.begin(), ids.end());
+            if (!ids.empty()) shapes = objectShapes(ids, false);
+        }
+    }
     const std::string path = dir + "/planes.txt";
     std::FILE* file = std::fopen(path.c_str(), "w");
     if (!file) throw std::runtime_error("EMFusion::writePlanes: cannot create " + path);
@@ -297,6 +464,32 @@ void EMFusion::writePlanes(const std::string& dir) {
         std::fprintf(file, " %.9g", w.d);
         for (int i = 0; i < 3; ++i) std::fprintf(file, " %.9g", w.point[i]);
         std::fprintf(file, " %.9g %d %d %d %d %d %d\n", w.thicknessM, q.lo[0], q.lo[1], q.lo[2], q.hi[0], q.hi[1], q.hi[2]);
+        // setPlanePatchesOutput: "patch" id count, then in %.9g the world point (3), the four corners (12) and fill
+        for (const PatchWorld& pw : patchWorld) {
+            if (pw.plane != static_cast<int>(k)) continue;
+            std::fprintf(file, "patch %d %llu", pw.id, static_cast<unsigned long long>(pw.rect.fit.count));
+            for (int i = 0; i < 3; ++i) std::fprintf(file, " %.9g", pw.point[i]);
+            for (int i = 0; i < 12; ++i) std::fprintf(file, " %.9g", pw.corners[i]);
+            std::fprintf(file, " %.9g\n", pw.rect.fill);
+        }
+    }
+    // ... and with the shapes output on as well: "support" object plane patch s, per object that rests on a patch
+    for (const ObjectShape& s : shapes) {
+        if (!s.frame.valid) continue;
+        int best = -1;
+        double bestS = 0.0;
+        for (size_t j = 0; j < patchWorld.size(); ++j) {
+            const PatchWorld& pw = patchWorld[j];
+            const char* kind = world[static_cast<size_t>(pw.plane)].kind;
+            if (std::strcmp(kind, "floor") != 0 && std::strcmp(kind, "level") != 0) continue;
+            double h = 0.0;
+            const bool over = planeSupport(pw.normal, pw.d, pw.center, pw.axes, pw.halfM, s.box.center_world, s.box.axes_world,
+                                           s.box.half_m, 0.0, h);
+            if (over && std::fabs(h) <= kSupportGap && (best < 0 || std::fabs(h) < std::fabs(bestS))) best = static_cast<int>(j), bestS = h;
+        }
+        if (best >= 0)
+            std::fprintf(file, "support %d %d %d %.9g\n", s.id, patchWorld[static_cast<size_t>(best)].plane,
+                         patchWorld[static_cast<size_t>(best)].id, bestS);
     }
     std::fclose(file);
 }

@@ -1097,6 +1097,78 @@ int emf_fusion_plane_fit(const emf_plane_moments_t* moments, const double seed_n
     return guarded([&] { planeFit(*moments, seed_n, seed_d, *plane); });
 }
 
+int emf_fusion_plane_patches(emf_fusion_t* h, int32_t reach, int64_t min_count, uint32_t counters[3], emf_plane_patch_t* patches,
+                             int32_t capacity, int32_t* count) {
+    REQ(h);
+    if (capacity < 0 || (capacity > 0 && !patches)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_plane_patches: capacity %d", capacity);
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const EMFusion::PlanePatches& r = h->impl->planePatches(reach, min_count);
+        if (counters) std::copy(r.counters, r.counters + 3, counters);
+        if (count) *count = static_cast<int32_t>(r.patches.size());
+        std::copy(r.patches.begin(), r.patches.begin() + std::min<size_t>(r.patches.size(), static_cast<size_t>(capacity)), patches);
+    });
+}
+
+int emf_fusion_copy_plane_patch_ids(emf_fusion_t* h, int32_t* ids, int64_t capacity) {
+    REQ(h);
+    if (capacity < 0) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_copy_plane_patch_ids: capacity %lld", static_cast<long long>(capacity));
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const EMFusion::Planes& r = h->impl->lastPlanes();
+        const EMFusion::PlanePatches& p = h->impl->lastPlanePatches();
+        if (!r.records || p.reach == 0) throw HipError("emf_fusion_copy_plane_patch_ids: no plane patches have been computed", EMF_E_ARG);
+        const size_t n = std::min<size_t>(static_cast<size_t>(capacity), r.counters[2]);
+        if (!ids || !n) return;
+        if (!p.ids) {  // no plane was found: no record has a patch
+            std::fill(ids, ids + n, -1);
+            return;
+        }
+        Stream& s = h->impl->mainStream();
+        hipCheck(hipMemcpyAsync(ids, p.ids, n * sizeof(int32_t), hipMemcpyDeviceToHost, s.get()), "copy_plane_patch_ids");
+        s.waitForCompletion();
+    });
+}
+
+int emf_fusion_plane_patch_rect(const emf_plane_t* plane, const emf_plane_patch_t* patch, emf_plane_patch_rect_t* rect) {
+    REQ(plane);
+    REQ(patch);
+    REQ(rect);
+    return guarded([&] { planePatchRect(*plane, *patch, *rect); });
+}
+
+int emf_fusion_plane_support(const double n[3], double d, const double center[3], const double axes[6], const double half[2],
+                             const double box_center[3], const double box_axes[9], const double box_half[3], double margin,
+                             double* s, int32_t* over) {
+    REQ(n);
+    REQ(center);
+    REQ(axes);
+    REQ(half);
+    REQ(box_center);
+    REQ(box_axes);
+    REQ(box_half);
+    REQ(s);
+    REQ(over);
+    return guarded([&] { *over = planeSupport(n, d, center, axes, half, box_center, box_axes, box_half, margin, *s) ? 1 : 0; });
+}
+
+int emf_fusion_set_plane_patches_output(emf_fusion_t* h, int on, int32_t reach, int64_t min_count) {
+    REQ(h);
+    if (on && (reach < 1 || reach > EMF_PLANE_MAX_REACH)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_set_plane_patches_output: a reach of %d voxels", reach);
+        return reach < 1 ? EMF_E_ARG : EMF_E_LIMIT;
+    }
+    return guarded([&] {
+        EMFusion::PlanePatchesOutput p;
+        p.on = on != 0, p.reach = on ? reach : 1, p.minCount = min_count;
+        h->impl->setPlanePatchesOutput(p);
+    });
+}
+
 static void copyGround(emf_fusion_t* h, const EMFusion::GroundMap& g, emf_ground_cell_t* cells, uint8_t* classes) {
     if (!g.cells) throw HipError("emf_fusion_copy_ground_map: no ground map has been computed", EMF_E_ARG);
     const size_t n = static_cast<size_t>(g.frame.map[0]) * g.frame.map[1];

@@ -21,12 +21,23 @@
 //                        wave's runs of equal destinations and one atomic per run (records are spatially ordered: runs are
 //                        long).  Over run numbers (run_id), since a destination can come back in a wave.
 //   k_pl_assign          one lane per record; the label, then the ten sums and six bounds per run of equal labels.
+// Stage 4, patches: the connected surfaces of every plane, without a dense volume.
+//   k_pp_init            parent[i] = i for a record with a label, -1 for one without (the patch array is the union-find)
+//   k_pp_hook            one lane per member: the 13 (reach 1) or 62 (reach 2) voxels that precede its own in (z, y, x)
+//                        order; each one inside the box is looked up by a binary search of its tile-order key among the
+//                        records' own keys, and a record found there with the same label is united (union_find.hpp)
+//   k_pp_flatten         patch[i] := root of i, the smallest record index of the patch; members and roots counted
+//   k_pp_rootsums / k_pp_scan / k_pp_roots   roots ranked by scan in record order; roots[rank] = i, the slot initialised
+//   k_pp_stats           one lane per record; ten sums, six bounds and four extent keys per run of equal PATCH in a wave
+//                        (run_id: a patch can come back), the slot by binary search of the root, then one atomic each
+//   k_pp_keepsums / k_pp_scan / k_pp_emit    slots of at least min_count members written in id order, placed by scan
 // Every float step is a single float32 operation through the _rn intrinsics, never contracted whatever the build; integer
 // atomics only: every output is a pure function of the inputs.  No scratch memory, no float atomics, no inline assembly.
 #include <cfloat>
 
 #include "common.hpp"
 #include "wave_ops.hpp"
+#include "union_find.hpp"
 
 namespace emf_hip {
 namespace {
@@ -363,6 +374,310 @@ __global__ __launch_bounds__(kPlBlock) void k_pl_assign(const AssignArgs a) {
     }
 }
 
+// ---- stage 4: patches -----------------------------------------------------------------------------------------------
+// The patch array is the union-find's parent array over RECORD indices (union_find.hpp): a member holds an index <= its
+// own, every other record the sentinel -1, which is never followed and never changes.  There is no dense volume: the
+// record of a neighbouring voxel is found by binary search of that voxel's tile-order key among the records' own keys.
+
+constexpr unsigned kPpNone = 0xffffffffu;
+
+static_assert(sizeof(emf_plane_patch_t) == 128, "mirrored by emfusion_amd/_lib.py");
+
+struct PatchBox {
+    int bx, by, bz;
+    unsigned ntx, nty, voxels;
+};
+
+// tile(v) * 2048 + within(v): strictly increasing along stage 1's order; at most 2^22 tiles, so below 2^33
+__device__ __forceinline__ unsigned long long voxel_key(const PatchBox& b, int x, int y, int z) {
+    const unsigned tile = (static_cast<unsigned>(z >> 3) * b.nty + static_cast<unsigned>(y >> 3)) * b.ntx + static_cast<unsigned>(x >> 5);
+    const unsigned within = (static_cast<unsigned>(z & 7) << 8) | (static_cast<unsigned>(y & 7) << 5) | static_cast<unsigned>(x & 31);
+    return (static_cast<unsigned long long>(tile) << 11) | within;
+}
+
+// the box voxel of a linear index; false for an index outside the box, which then has no voxel
+__device__ __forceinline__ bool index_voxel(const PatchBox& b, int index, int& x, int& y, int& z) {
+    if (index < 0 || static_cast<unsigned>(index) >= b.voxels) return false;
+    const int row = index / b.bx;
+    x = index - row * b.bx;
+    z = row / b.by;
+    y = row - z * b.by;
+    return true;
+}
+
+// the key of record i; ~0 (the key of no voxel) where its index lies outside the box
+__device__ __forceinline__ unsigned long long record_key(const emf_plane_voxel_t* __restrict__ records, const PatchBox& b, unsigned i) {
+    int x, y, z;
+    return index_voxel(b, records[i].index, x, y, z) ? voxel_key(b, x, y, z) : ~0ull;
+}
+
+// the record whose key is `key` among the first n (> 0), or kPpNone.  Bounded by n whatever the records hold.
+__device__ __forceinline__ unsigned record_of(const emf_plane_voxel_t* __restrict__ records, const PatchBox& b, unsigned n,
+                                              unsigned long long key) {
+    unsigned lo = 0u, hi = n;  // key(lo) <= key < key(hi) once lo's holds
+    while (hi - lo > 1u) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (record_key(records, b, mid) <= key) lo = mid;
+        else hi = mid;
+    }
+    return record_key(records, b, lo) == key ? lo : kPpNone;
+}
+
+struct PatchLabelArgs {
+    const emf_plane_voxel_t* records;
+    const int16_t* labels;
+    const unsigned* counters;
+    unsigned capacity;
+    PatchBox box;
+    int reach;
+    unsigned* parent;         // the patch array
+    unsigned* patchCounters;  // EMF_PATCH_*
+};
+
+__global__ __launch_bounds__(kPlBlock) void k_pp_init(const PatchLabelArgs a) {
+    const unsigned n = min(a.counters[2], a.capacity);
+    const unsigned i = blockIdx.x * kPlBlock + threadIdx.x;
+    if (i < n) a.parent[i] = a.labels[i] >= 0 ? i : kPpNone;
+}
+
+// per member: unite with the members of the same label among the voxels that precede its own in (z, y, x) order and lie
+// within `reach` of it -- every pair of the (2 reach + 1)^3 neighbourhood once: 13 offsets at reach 1, 62 at reach 2
+__global__ __launch_bounds__(kPlBlock) void k_pp_hook(const PatchLabelArgs a) {
+    const unsigned n = min(a.counters[2], a.capacity);
+    const unsigned i = blockIdx.x * kPlBlock + threadIdx.x;
+    if (i >= n) return;
+    const int label = a.labels[i];
+    int x, y, z;
+    if (label < 0 || !index_voxel(a.box, a.records[i].index, x, y, z)) return;
+    const int R = a.reach;
+    for (int dz = -R; dz <= 0; ++dz) {
+        const int qz = z + dz;
+        if (qz < 0) continue;
+        for (int dy = -R; dy <= (dz < 0 ? R : 0); ++dy) {
+            const int qy = y + dy;
+            if (qy < 0 || qy >= a.box.by) continue;
+            for (int dx = -R; dx <= (dz < 0 || dy < 0 ? R : -1); ++dx) {
+                const int qx = x + dx;
+                if (qx < 0 || qx >= a.box.bx) continue;
+                const unsigned j = record_of(a.records, a.box, n, voxel_key(a.box, qx, qy, qz));
+                if (j != kPpNone && a.labels[j] == label) unite(a.parent, i, j);
+            }
+        }
+    }
+}
+
+// patch[i] := root of i, the smallest record index of the patch whatever order the hooks ran in; members and roots counted
+__global__ __launch_bounds__(kPlBlock) void k_pp_flatten(const PatchLabelArgs a) {
+    __shared__ unsigned lds[kPlBlock / 64];
+    const unsigned n = min(a.counters[2], a.capacity);
+    if (blockIdx.x * static_cast<unsigned>(kPlBlock) >= n) return;  // block-uniform
+    const unsigned i = blockIdx.x * kPlBlock + threadIdx.x;
+    unsigned flags = 0u;  // member | root << 16: both at most 256 over the workgroup
+    if (i < n && load_parent(a.parent, i) != kPpNone) {
+        const unsigned r = find_root(a.parent, i);
+        atomicMin(a.parent + i, r);  // (a halving step of another lane may still be under way: the minimum wins)
+        flags = 1u | (r == i ? 1u << 16 : 0u);
+    }
+    unsigned total;
+    block_exclusive_scan<kPlBlock / 64>(flags, total, lds);
+    if (threadIdx.x == 0) {
+        if (total & 0xffffu) atomicAdd(&a.patchCounters[EMF_PATCH_MEMBERS], total & 0xffffu);
+        if (total >> 16) atomicAdd(&a.patchCounters[EMF_PATCH_PATCHES], total >> 16);
+    }
+}
+
+struct PatchArgs {
+    const emf_plane_voxel_t* records;
+    const int16_t* labels;
+    const unsigned* patch;
+    const unsigned* counters;
+    unsigned capacity;
+    PatchBox box;
+    int P;
+    unsigned long long minCount;
+    emf_plane_patch_t* slots;  // per slot; the four floats hold their u32 keys until k_pp_emit
+    unsigned* roots;           // per slot, ascending
+    unsigned* bsums;           // blocks + 1
+    unsigned* csums;           // cblocks + 1
+    unsigned nc, blocks, cblocks;
+    emf_plane_patch_t* out;
+    unsigned capacityOut;
+    unsigned* kept;
+    float axes[6 * EMF_PLANE_MAX_PLANES];  // u0, u1, u2, v0, v1, v2 per plane
+};
+static_assert(sizeof(PatchArgs) <= 4096, "PatchArgs travels in the kernel arguments");
+
+inline size_t place(PatchArgs& a, unsigned capacity, unsigned nPatches, void* scratch) {
+    a.nc = min(nPatches, capacity);
+    a.blocks = ceil_div(capacity, kPlBlock);
+    a.cblocks = ceil_div(a.nc, kPlBlock);
+    ScratchArena s{static_cast<char*>(scratch), 0};
+    a.slots = s.take<emf_plane_patch_t>(a.nc);
+    a.roots = s.take<unsigned>(a.nc);
+    a.bsums = s.take<unsigned>(static_cast<size_t>(a.blocks) + 1);
+    a.csums = s.take<unsigned>(static_cast<size_t>(a.cblocks) + 1);
+    return s.off;
+}
+
+__device__ __forceinline__ unsigned pp_root_flag(const PatchArgs& a, unsigned n, unsigned i) {
+    return i < n && a.patch[i] == i ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(kPlBlock) void k_pp_rootsums(const PatchArgs a) {
+    __shared__ unsigned lds[kPlBlock / 64];
+    const unsigned n = min(a.counters[2], a.capacity);
+    if (blockIdx.x * static_cast<unsigned>(kPlBlock) >= n) return;  // block-uniform; k_pp_scan stops at n as well
+    unsigned total;
+    block_exclusive_scan<kPlBlock / 64>(pp_root_flag(a, n, blockIdx.x * kPlBlock + threadIdx.x), total, lds);
+    if (threadIdx.x == 0) a.bsums[blockIdx.x] = total;
+}
+
+// one workgroup: the exclusive scan of the sums of the workgroups that hold records (of all `count` sums where counters
+// is NULL); the total goes behind the last sum
+__global__ __launch_bounds__(kSumsBlock) void k_pp_scan(unsigned* sums, unsigned count, const unsigned* counters, unsigned capacity) {
+    __shared__ unsigned lds[kSumsBlock / 64];
+    const unsigned used = counters ? (min(counters[2], capacity) + kPlBlock - 1u) / kPlBlock : count;
+    const unsigned total = scan_sums(sums, 0u, used, lds);
+    if (threadIdx.x == 0) sums[count] = total;
+}
+
+__global__ __launch_bounds__(kPlBlock) void k_pp_roots(const PatchArgs a) {
+    __shared__ unsigned lds[kPlBlock / 64];
+    const unsigned n = min(a.counters[2], a.capacity);
+    if (blockIdx.x * static_cast<unsigned>(kPlBlock) >= n) return;  // block-uniform
+    const unsigned i = blockIdx.x * kPlBlock + threadIdx.x;
+    const unsigned flag = pp_root_flag(a, n, i);
+    unsigned total;
+    const unsigned rank = a.bsums[blockIdx.x] + block_exclusive_scan<kPlBlock / 64>(flag, total, lds);
+    if (!flag || rank >= a.nc) return;
+    a.roots[rank] = i;
+    emf_plane_patch_t s{};
+    s.id = static_cast<int32_t>(i);
+    s.plane = a.labels[i];
+    s.lo[0] = a.box.bx, s.lo[1] = a.box.by, s.lo[2] = a.box.bz;
+    s.hi[0] = s.hi[1] = s.hi[2] = -1;
+    s.ulo = s.vlo = __uint_as_float(0xff800000u);  // the key of +inf
+    s.uhi = s.vhi = __uint_as_float(0x007fffffu);  // the key of -inf
+    a.slots[rank] = s;
+}
+
+// v, through a DPP move with the identity lane pattern: a value the compiler cannot look through.  A build with
+// -ffp-contract=fast fuses a product into a neighbouring sum whatever a pragma or an _rn intrinsic says; a product
+// that went through here is no product to it any more.
+__device__ __forceinline__ float pp_rounded(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xE4 /* quad_perm 0, 1, 2, 3 */, 0xf, 0xf, false));
+}
+
+// (a0 * x + a1 * y) + a2 * z as five single float32 operations, whatever the build
+__device__ __forceinline__ float pp_extent(float a0, float a1, float a2, float x, float y, float z) {
+    const float p0 = pp_rounded(__fmul_rn(a0, x)), p1 = pp_rounded(__fmul_rn(a1, y)), p2 = pp_rounded(__fmul_rn(a2, z));
+    return __fadd_rn(__fadd_rn(p0, p1), p2);
+}
+
+// the order-preserving map of the f32 bits to u32 that emf_hip_shapeExtents documents, and back
+__device__ __forceinline__ unsigned pp_float_key(float v) {
+    const unsigned b = __float_as_uint(v);
+    return (b & 0x80000000u) ? ~b : (b ^ 0x80000000u);
+}
+__device__ __forceinline__ unsigned pp_key_bits(unsigned k) { return (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k; }
+
+// the slot of the patch `id` among the first nc sorted roots, or kPpNone
+__device__ __forceinline__ unsigned pp_slot_of(const unsigned* __restrict__ roots, unsigned nc, unsigned id) {
+    unsigned lo = 0u, hi = nc;
+    while (hi - lo > 1u) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (roots[mid] <= id) lo = mid;
+        else hi = mid;
+    }
+    return nc != 0u && roots[lo] == id ? lo : kPpNone;
+}
+
+// one lane per record; the ten sums, six bounds and four extent keys per run of equal patches in a wave, then one
+// integer atomic per quantity and run.  Over run numbers (run_id): a patch can come back within a wave.
+__global__ __launch_bounds__(kPlBlock) void k_pp_stats(const PatchArgs a) {
+    const unsigned n = min(a.counters[2], a.capacity);
+    if (blockIdx.x * static_cast<unsigned>(kPlBlock) >= n) return;  // block-uniform
+    const unsigned i = blockIdx.x * kPlBlock + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int id = -1, ix = 0, iy = 0, iz = 0;
+    unsigned k[4] = {0xffffffffu, 0u, 0xffffffffu, 0u};  // ulo, uhi, vlo, vhi: neutral
+    if (i < n) {
+        id = static_cast<int>(a.patch[i]);  // below 2^31 - 1: the capacity is
+        if (id >= 0) {
+            if (!index_voxel(a.box, a.records[i].index, ix, iy, iz)) ix = iy = iz = 0;
+            const int plane = a.labels[i];
+            if (plane >= 0 && plane < a.P) {
+                const float x = static_cast<float>(ix), y = static_cast<float>(iy), z = static_cast<float>(iz);
+                const float* ax = a.axes + 6 * plane;
+                k[0] = k[1] = pp_float_key(pp_extent(ax[0], ax[1], ax[2], x, y, z));
+                k[2] = k[3] = pp_float_key(pp_extent(ax[3], ax[4], ax[5], x, y, z));
+            }
+        }
+    }
+    if (__ballot(id >= 0) == 0ull) return;  // wave-uniform
+    // count, x, y, z, xx, yy, zz, xy, xz, yz of the run's lanes that are not above this one: at most 64 * 2047^2 < 2^32;
+    // a patch's totals stay below 2^31 * 2047^2 < 2^53
+    const unsigned ux = ix, uy = iy, uz = iz, in = id >= 0 ? 1u : 0u;
+    unsigned s[10] = {in, ux, uy, uz, ux * ux, uy * uy, uz * uz, ux * uy, ux * uz, uy * uz};
+    int lo[3] = {ix, iy, iz}, hi[3] = {ix, iy, iz};
+    const int run = run_id(id, lane);
+#pragma unroll
+    for (int q = 0; q < 10; ++q) s[q] = run_scan<OpAdd>(s[q], lane, run);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) lo[j] = run_scan<OpMin>(lo[j], lane, run), hi[j] = run_scan<OpMax>(hi[j], lane, run);
+    k[0] = run_scan<OpMin>(k[0], lane, run), k[1] = run_scan<OpMax>(k[1], lane, run);
+    k[2] = run_scan<OpMin>(k[2], lane, run), k[3] = run_scan<OpMax>(k[3], lane, run);
+    if (!run_is_last(run, lane) || id < 0) return;  // not the last lane of a run of members
+    const unsigned slot = pp_slot_of(a.roots, min(a.nc, a.bsums[a.blocks]), static_cast<unsigned>(id));
+    if (slot == kPpNone) return;  // a patch beyond n_patches
+    emf_plane_patch_t* m = a.slots + slot;
+    unsigned long long* w = reinterpret_cast<unsigned long long*>(m) + 1;  // count, sum[3], sum2[6] behind id and plane
+#pragma unroll
+    for (int q = 0; q < 10; ++q)
+        if (s[q]) atomicAdd(w + q, static_cast<unsigned long long>(s[q]));
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        atomicMin(&m->lo[j], lo[j]);
+        atomicMax(&m->hi[j], hi[j]);
+    }
+    unsigned* e = reinterpret_cast<unsigned*>(&m->ulo);
+    atomicMin(e, k[0]);
+    atomicMax(e + 1, k[1]);
+    atomicMin(e + 2, k[2]);
+    atomicMax(e + 3, k[3]);
+}
+
+__device__ __forceinline__ unsigned pp_keep_flag(const PatchArgs& a, unsigned nc, unsigned s) {
+    return s < nc && a.slots[s].count >= a.minCount ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(kPlBlock) void k_pp_keepsums(const PatchArgs a) {
+    __shared__ unsigned lds[kPlBlock / 64];
+    const unsigned nc = min(a.nc, a.bsums[a.blocks]);  // the slots k_pp_roots did fill
+    unsigned total;
+    block_exclusive_scan<kPlBlock / 64>(pp_keep_flag(a, nc, blockIdx.x * kPlBlock + threadIdx.x), total, lds);
+    if (threadIdx.x == 0) a.csums[blockIdx.x] = total;
+}
+
+// kept slots write their record at their rank (id order: the slots are sorted by id) while the rank is below the
+// capacity; the keys become the bits of the floats; thread 0 writes the kept total
+__global__ __launch_bounds__(kPlBlock) void k_pp_emit(const PatchArgs a) {
+    __shared__ unsigned lds[kPlBlock / 64];
+    const unsigned nc = min(a.nc, a.bsums[a.blocks]);
+    const unsigned s = blockIdx.x * kPlBlock + threadIdx.x;
+    const unsigned flag = pp_keep_flag(a, nc, s);
+    unsigned total;
+    const unsigned rank = a.csums[blockIdx.x] + block_exclusive_scan<kPlBlock / 64>(flag, total, lds);
+    if (s == 0u) *a.kept = a.csums[a.cblocks];
+    if (!flag || rank >= a.capacityOut) return;
+    emf_plane_patch_t r = a.slots[s];
+    r.ulo = __uint_as_float(pp_key_bits(__float_as_uint(r.ulo)));
+    r.uhi = __uint_as_float(pp_key_bits(__float_as_uint(r.uhi)));
+    r.vlo = __uint_as_float(pp_key_bits(__float_as_uint(r.vlo)));
+    r.vhi = __uint_as_float(pp_key_bits(__float_as_uint(r.vhi)));
+    a.out[rank] = r;
+}
+
 // ---- host: the checks; nothing is enqueued by them --------------------------------------------------------------
 
 int check_size(const int32_t size[3], const char* who) {
@@ -382,7 +697,15 @@ unsigned long long tiles_of(const int32_t size[3]) {
            ((size[2] + kPlTZ - 1) / kPlTZ);
 }
 
-// the record list of the three entries that read one
+PatchBox patch_box(const int32_t size[3]) {  // of a size check_size has passed
+    PatchBox b;
+    b.bx = size[0], b.by = size[1], b.bz = size[2];
+    b.ntx = (size[0] + kPlTX - 1) / kPlTX, b.nty = (size[1] + kPlTY - 1) / kPlTY;
+    b.voxels = static_cast<unsigned>(size[0]) * size[1] * static_cast<unsigned>(size[2]);
+    return b;
+}
+
+// the record list of the entries that read one
 int check_records(const char* who, const emf_plane_voxel_t* records, const uint32_t* counters, uint32_t capacity) {
     if (!records || !counters) return fail(EMF_E_ARG, "%s: the records or the counters are NULL", who);
     if ((reinterpret_cast<uintptr_t>(records) & 15u) || (reinterpret_cast<uintptr_t>(counters) & 3u))
@@ -510,6 +833,79 @@ int emf_hip_planeAssign(const emf_plane_voxel_t* records, const uint32_t* counte
     hipLaunchKernelGGL(k_pl_assign_init, dim3(1), dim3(256), 0, s, moments, P, a.bx, a.by, a.bz);
     hipLaunchKernelGGL(k_pl_assign, dim3(ceil_div(capacity, kPlBlock)), dim3(kPlBlock), 0, s, a);
     return launch_status("planeAssign");
+}
+
+int emf_hip_planePatchLabel(const emf_plane_voxel_t* records, const int16_t* labels, const uint32_t* counters, uint32_t capacity,
+                            const int32_t box_size[3], int32_t reach, int32_t* patch, uint32_t* patch_counters,
+                            emf_stream_t stream) {
+    EMF_TRY(check_records("planePatchLabel", records, counters, capacity));
+    EMF_TRY(check_size(box_size, "planePatchLabel"));
+    if (reach < 1) return fail(EMF_E_ARG, "planePatchLabel: a reach of %d voxels", reach);
+    if (reach > EMF_PLANE_MAX_REACH) return fail(EMF_E_LIMIT, "planePatchLabel: a reach of %d voxels, above %d", reach, EMF_PLANE_MAX_REACH);
+    if (!labels || !patch || !patch_counters) return fail(EMF_E_ARG, "planePatchLabel: the labels, the patches or their counters are NULL");
+    if ((reinterpret_cast<uintptr_t>(labels) & 1u) || ((reinterpret_cast<uintptr_t>(patch) | reinterpret_cast<uintptr_t>(patch_counters)) & 3u))
+        return fail(EMF_E_ARG, "planePatchLabel: misaligned labels, patches or counters");
+    PatchLabelArgs a{};
+    a.records = records, a.labels = labels, a.counters = counters, a.capacity = capacity;
+    a.box = patch_box(box_size);
+    a.reach = reach;
+    a.parent = reinterpret_cast<unsigned*>(patch), a.patchCounters = patch_counters;
+    const hipStream_t s = as_stream(stream);
+    const dim3 grid(ceil_div(capacity, kPlBlock)), block(kPlBlock);
+    zero(patch_counters, 3, s);
+    hipLaunchKernelGGL(k_pp_init, grid, block, 0, s, a);
+    hipLaunchKernelGGL(k_pp_hook, grid, block, 0, s, a);
+    hipLaunchKernelGGL(k_pp_flatten, grid, block, 0, s, a);
+    return launch_status("planePatchLabel");
+}
+
+size_t emf_hip_planePatchScratchBytes(uint32_t capacity, uint32_t n_patches) {
+    if (capacity < 1u || capacity > 0x7fffffffu) return 0;
+    PatchArgs a;
+    char origin[16];
+    return place(a, capacity, n_patches, origin);  // only the offsets are used
+}
+
+int emf_hip_planePatches(const emf_plane_voxel_t* records, const int16_t* labels, const int32_t* patch, const uint32_t* counters,
+                         uint32_t capacity, const int32_t box_size[3], const float* axes_host, int32_t P, int64_t min_count,
+                         uint32_t n_patches, void* scratch, emf_plane_patch_t* out, int32_t capacity_patches,
+                         uint32_t* patch_counters, emf_stream_t stream) {
+    EMF_TRY(check_records("planePatches", records, counters, capacity));
+    EMF_TRY(check_size(box_size, "planePatches"));
+    if (!labels || !patch || !patch_counters) return fail(EMF_E_ARG, "planePatches: the labels, the patches or their counters are NULL");
+    if (!axes_host) return fail(EMF_E_ARG, "planePatches: the axes are NULL");
+    if (P < 1) return fail(EMF_E_ARG, "planePatches: %d planes", P);
+    if (P > EMF_PLANE_MAX_PLANES) return fail(EMF_E_LIMIT, "planePatches: %d planes, above %d", P, EMF_PLANE_MAX_PLANES);
+    if (min_count < 1) return fail(EMF_E_ARG, "planePatches: a min_count of %lld members", static_cast<long long>(min_count));
+    if (capacity_patches < 0) return fail(EMF_E_ARG, "planePatches: a capacity of %d patches", capacity_patches);
+    if (capacity_patches > 0 && !out) return fail(EMF_E_ARG, "planePatches: a capacity of %d patches and no patches", capacity_patches);
+    if (n_patches && !scratch) return fail(EMF_E_ARG, "planePatches: scratch is NULL");
+    if ((reinterpret_cast<uintptr_t>(labels) & 1u) || ((reinterpret_cast<uintptr_t>(patch) | reinterpret_cast<uintptr_t>(patch_counters)) & 3u) ||
+        (reinterpret_cast<uintptr_t>(scratch) & 15u) || (reinterpret_cast<uintptr_t>(out) & 7u))
+        return fail(EMF_E_ARG, "planePatches: misaligned arrays");
+    const hipStream_t s = as_stream(stream);
+    if (n_patches == 0u) {
+        zero(patch_counters + EMF_PATCH_KEPT, 1, s);
+        return launch_status("planePatches");
+    }
+    PatchArgs a{};
+    place(a, capacity, n_patches, scratch);
+    a.records = records, a.labels = labels, a.patch = reinterpret_cast<const unsigned*>(patch), a.counters = counters;
+    a.capacity = capacity;
+    a.box = patch_box(box_size);
+    a.P = P;
+    a.minCount = static_cast<unsigned long long>(min_count);
+    a.out = out, a.capacityOut = static_cast<unsigned>(capacity_patches), a.kept = patch_counters + EMF_PATCH_KEPT;
+    std::memcpy(a.axes, axes_host, sizeof(float) * 6 * P);
+    const dim3 grid(a.blocks), cgrid(a.cblocks), block(kPlBlock);
+    hipLaunchKernelGGL(k_pp_rootsums, grid, block, 0, s, a);
+    hipLaunchKernelGGL(k_pp_scan, dim3(1), dim3(kSumsBlock), 0, s, a.bsums, a.blocks, counters, capacity);
+    hipLaunchKernelGGL(k_pp_roots, grid, block, 0, s, a);
+    hipLaunchKernelGGL(k_pp_stats, grid, block, 0, s, a);
+    hipLaunchKernelGGL(k_pp_keepsums, cgrid, block, 0, s, a);
+    hipLaunchKernelGGL(k_pp_scan, dim3(1), dim3(kSumsBlock), 0, s, a.csums, a.cblocks, static_cast<const unsigned*>(nullptr), 0u);
+    hipLaunchKernelGGL(k_pp_emit, cgrid, block, 0, s, a);
+    return launch_status("planePatches");
 }
 
 }  // extern "C"

@@ -2140,3 +2140,59 @@ def plane_assign(records, counters, size, planes, cos2, band, capacity=None, out
                                  P, float(np.float32(cos2)), float(np.float32(band)), _ptr(labels), _ptr(moments),
                                  _stream(stream)))
     return labels, moments
+
+
+# ---- plane patches (include/emf_hip.h "Planes", stage 4) ------------------------------------------
+
+PLANE_PATCH_DTYPE = np.dtype(_lib.PLANE_PATCH_DTYPE)
+PLANE_MAX_REACH = _lib.PLANE_MAX_REACH
+PATCH_KEPT, PATCH_PATCHES, PATCH_MEMBERS = _lib.PATCH_KEPT, _lib.PATCH_PATCHES, _lib.PATCH_MEMBERS
+assert PLANE_PATCH_DTYPE.itemsize == 128
+
+
+def plane_patch_label(records, labels, counters, size, reach=1, capacity=None, out=None, stream=None):
+    """emf_hip_planePatchLabel: per record of plane_surface (labels: plane_assign's) the id of its PATCH -- the connected
+    component of the records with its label whose box voxels lie within `reach` (1 or 2, Chebyshev) of each other, named
+    by the smallest record index among its members -- or -1 where the label is < 0.  Returns (patch, patch_counters) on
+    the device: `capacity` i32 of which the first counters[2] are written, and 3 x u32 (kept patches: 0 until
+    plane_patches, all patches, records with a label >= 0).  out: (patch, patch_counters) to reuse.  The host does not
+    wait."""
+    capacity = records.shape[0] if capacity is None else int(capacity)
+    patch, pc = out if out is not None else (DeviceArray((max(capacity, 1),), np.int32), DeviceArray((3,), np.uint32))
+    assert patch.dtype == np.int32 and patch.shape[0] >= capacity
+    assert pc.dtype == np.uint32 and pc.shape == (3,)
+    check("emf_hip_planePatchLabel",
+          _L.emf_hip_planePatchLabel(_ptr(records), _ptr(labels), _ptr(counters), capacity, _i3(size), int(reach), _ptr(patch),
+                                     _ptr(pc), _stream(stream)))
+    return patch, pc
+
+
+def plane_patch_scratch_bytes(capacity, n_patches) -> int:
+    return int(_L.emf_hip_planePatchScratchBytes(int(capacity), int(n_patches)))
+
+
+def plane_patches(records, labels, patch, counters, size, axes, patch_counters, min_count=1, n_patches=None, capacity=None,
+                  capacity_patches=None, out=None, stream=None):
+    """emf_hip_planePatches: one PLANE_PATCH_DTYPE record per patch of at least min_count members, in ascending id order:
+    id, plane, the integer moments and bounds of the members and the extents (ulo, uhi, vlo, vhi) of the members along
+    the two in-plane axes of their plane (axes: P x 6 f32 = u0, u1, u2, v0, v1, v2, box voxels).  n_patches None: read
+    from patch_counters here -- the one wait.  Returns the records on the device (capacity_patches of them, None:
+    n_patches); patch_counters[PATCH_KEPT] says how many are kept."""
+    capacity = records.shape[0] if capacity is None else int(capacity)
+    axes = np.ascontiguousarray(np.asarray(axes, np.float32).reshape(-1, 6))
+    if n_patches is None:
+        n_patches = int(patch_counters.numpy()[PATCH_PATCHES])
+    n_patches = int(n_patches)
+    if capacity_patches is None:
+        capacity_patches = n_patches
+    capacity_patches = int(capacity_patches)
+    if out is None:
+        out = DeviceArray((max(capacity_patches, 1),), PLANE_PATCH_DTYPE)
+    assert out.dtype == PLANE_PATCH_DTYPE and out.shape[0] >= capacity_patches
+    scratch = DeviceArray((max(plane_patch_scratch_bytes(capacity, n_patches), 16),), np.uint8)
+    check("emf_hip_planePatches",
+          _L.emf_hip_planePatches(_ptr(records), _ptr(labels), _ptr(patch), _ptr(counters), capacity, _i3(size),
+                                  axes.ctypes.data_as(C.POINTER(C.c_float)), axes.shape[0], int(min_count), n_patches,
+                                  _ptr(scratch), _ptr(out), capacity_patches, _ptr(patch_counters), _stream(stream)))
+    out.scratch = scratch
+    return out

@@ -188,6 +188,12 @@ def load() -> C.CDLL:
                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_uint32, C.c_int32,
                                      C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
         "emf_fusion_plane_fit": [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p],
+        "emf_fusion_plane_patches": [vp, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
+        "emf_fusion_copy_plane_patch_ids": [vp, C.c_void_p, C.c_int64],
+        "emf_fusion_plane_patch_rect": [C.c_void_p, C.c_void_p, C.c_void_p],
+        "emf_fusion_plane_support": [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int32)],
+        "emf_fusion_set_plane_patches_output": [vp, C.c_int, C.c_int32, C.c_int64],
         "emf_fusion_ground_map": [vp, ip, ip, ip, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_double,
                                   C.c_double, C.c_int32, C.c_int32, ip, ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int64],
@@ -689,6 +695,99 @@ def plane_fit(moments, seed_n, seed_d):
     out["d"] = _dot3(n, fr["centroid"])
     out["thickness"] = np.sqrt(max(np.float64(fr["eigenvalues"][2]), np.float64(0.0)))
     out["fitted"] = 1
+    return out
+
+
+# include/emf_hip.h "Planes", stage 4: emf_plane_patch_rect_t (320 bytes)
+PLANE_PATCH_RECT_DTYPE = np.dtype([("fit", PLANE_DTYPE), ("center", "<f8", 3), ("half", "<f8", 2), ("corners", "<f8", 12),
+                                   ("fill", "<f8")])
+assert PLANE_PATCH_RECT_DTYPE.itemsize == 320
+
+
+def plane_patch_rect(plane, patch):
+    """emf_fusion_plane_patch_rect restated in numpy float64 with its operand order (include/emf_hip.h, the host steps
+    behind stage 4), so that both give the same bits; on the host without a device.  From a plane (PLANE_DTYPE, box voxel
+    coordinates) and one of its patches (ops.PLANE_PATCH_DTYPE): fit, the patch's own plane by plane_fit CALLED on its
+    moments with the plane as the seed; the rectangle that holds the patch's members along the plane's two in-plane
+    axes, widened by half a voxel on each side -- center, half (2), corners (4 x 3, flat), all IN the plane; and
+    fill = count / (the rectangle's voxel columns), near 1 for a full rectangle and lower for an L shape or one with
+    holes: A RATIO OF TWO ESTIMATES.  Returns a 0-d array of PLANE_PATCH_RECT_DTYPE."""
+    from ._lib import PLANE_MOMENTS_DTYPE
+    f8 = np.float64
+    mom = np.zeros((), np.dtype(PLANE_MOMENTS_DTYPE))
+    for key in ("count", "sum", "sum2", "lo", "hi"):
+        mom[key] = patch[key]
+    n, d = np.asarray(plane["n"], f8).reshape(3), f8(plane["d"])
+    u, v = np.asarray(plane["axes"], f8).reshape(6)[:3], np.asarray(plane["axes"], f8).reshape(6)[3:]
+    out = np.zeros((), PLANE_PATCH_RECT_DTYPE)
+    out["fit"] = plane_fit(mom, n, d)
+    out["fit"]["label"] = plane["label"]
+    a0, a1 = f8(patch["ulo"]) - f8(0.5), f8(patch["uhi"]) + f8(0.5)
+    b0, b1 = f8(patch["vlo"]) - f8(0.5), f8(patch["vhi"]) + f8(0.5)
+    with np.errstate(all="ignore"):
+        cu, hu = (a0 + a1) * f8(0.5), (a1 - a0) * f8(0.5)
+        cv, hv = (b0 + b1) * f8(0.5), (b1 - b0) * f8(0.5)
+
+        def point(eu, ev):
+            p = np.zeros(3, f8)
+            for j in range(3):
+                s = d * n[j]
+                t = u[j] * eu
+                s = s + t
+                t = v[j] * ev
+                p[j] = s + t
+            return p
+
+        out["center"], out["half"] = point(cu, cv), (hu, hv)
+        out["corners"] = np.concatenate([point(cu + su * hu, cv + sv * hv)
+                                         for su, sv in ((f8(-1), f8(-1)), (f8(1), f8(-1)), (f8(1), f8(1)), (f8(-1), f8(1)))])
+        wu = (f8(patch["uhi"]) - f8(patch["ulo"])) + f8(1.0)
+        wv = (f8(patch["vhi"]) - f8(patch["vlo"])) + f8(1.0)
+        area = (wu * wv) * np.abs(n).max()
+        out["fill"] = f8(int(patch["count"])) / area
+    return out
+
+
+def plane_support_of(n, d, center, axes, half, box_center, box_axes, box_half, margin=0.0):
+    """emf_fusion_plane_support restated in numpy float64 with its operand order; on the host without a device.  One
+    oriented box (centre, three unit row axes, half sizes) against one patch (plane n . x = d, rectangle centre, two row
+    axes, half sizes), world metres: (s, over) with s = (n . c - d) - sum_k |n . A_k| * h_k, the height of the box's lowest
+    point above the plane, and over = the box centre lies, along the rectangle's axes about its centre, within
+    half + margin."""
+    f8 = np.float64
+    n, c = np.asarray(n, f8).reshape(3), np.asarray(box_center, f8).reshape(3)
+    A, h = np.asarray(box_axes, f8).reshape(3, 3), np.asarray(box_half, f8).reshape(3)
+    axes, half, center = np.asarray(axes, f8).reshape(2, 3), np.asarray(half, f8).reshape(2), np.asarray(center, f8).reshape(3)
+    s = _dot3(n, c) - f8(d)
+    for k in range(3):
+        s = s - np.abs(_dot3(n, A[k])) * h[k]
+    q = [c[0] - center[0], c[1] - center[1], c[2] - center[2]]
+    over = True
+    for j in range(2):
+        over = over and bool(np.abs(_dot3(q, axes[j])) <= half[j] + f8(margin))
+    return float(s), over
+
+
+def plane_support(patches, boxes, gap=0.05, margin=0.0):
+    """Which patch each oriented box rests on; on the host without a device.  patches: the patch dicts of
+    Fusion.planes(patches=True) in any order (normal, d, rect and kind are read); boxes: dicts with center (3,), axes
+    (3 x 3 unit rows) and half (3,) in world metres, or None.  A box is OVER a patch iff its centre, along the
+    rectangle's axes about the rectangle's centre, lies within half_m + margin: the rectangle, not the members, because
+    the surface under a standing object is occluded and missing from the patch, and the rectangle spans the hole.  It
+    RESTS ON the patch of smallest |s| (plane_support_of) among those it is over with |s| <= gap and whose kind is floor
+    or level; ties go to the earlier patch.  gap 0.05 m IS POLICY, NOT A MEASUREMENT.  Returns per box (index into
+    patches, s) or None."""
+    out = []
+    for box in boxes:
+        best = None
+        for k, p in enumerate(patches if box is not None else ()):
+            if p["kind"] not in ("floor", "level"):
+                continue
+            s, over = plane_support_of(p["normal"], p["d"], p["rect"]["center"], p["rect"]["axes"], p["rect"]["half_m"],
+                                       box["center"], box["axes"], box["half"], margin)
+            if over and abs(s) <= gap and (best is None or abs(s) < abs(best[1])):
+                best = (k, s)
+        out.append(best)
     return out
 
 
@@ -1648,7 +1747,8 @@ class Fusion:
         return out
 
     def planes(self, box=None, size=None, k=15, angle=20.0, separation=None, bin=None, band=None, min_votes=None, refine=1,
-               up_hint=None, floor_angle=30.0, kind_angle=10.0, max_planes=64, labels=False):
+               up_hint=None, floor_angle=30.0, kind_angle=10.0, max_planes=64, labels=False, patches=False, patch_reach=1,
+               patch_min_voxels=None):
         """What the scene is made of: the dominant planes -- floor, walls, table tops -- of a box of the
         background: None, ((x, y, z) lo, (x, y, z) size) or "camera" with `size`, as for distance_field.  On the device
         the surface voxels (solid with a free face neighbour) with their TSDF gradients vote for a direction on a cube
@@ -1669,7 +1769,21 @@ class Fusion:
         The floor is, among planes whose normal is within floor_angle of up_hint (None: minus the background's y axis,
         ground_map's own default), the one whose centroid is lowest along up_hint; the others are named relative to its
         normal: level, ceiling, wall (within kind_angle) or slope.  Waits 3 + refine times.  Changes nothing of the
-        session; refused on the sharded path."""
+        session; refused on the sharded path.
+
+        patches=True (off: nothing new runs and the dict is as above): a plane is infinite -- two tables
+        of one height are one plane -- so every plane is split on the device into its connected surfaces, the components
+        of its members under a Chebyshev reach of patch_reach voxels (1 or 2), and patches of fewer than patch_min_voxels
+        members are dropped.  THE REACH OF 1 AND patch_min_voxels = max(25, min_votes // 4) ARE POLICY, NOT MEASUREMENTS.
+        Every plane gains patches, a list ordered by count descending, ties to the lower id, of dicts: id (the smallest
+        record index of the members), count, bounds (lo, hi) in box voxels, point, normal and d in the world frame from
+        the patch's OWN least-squares fit, thickness_m, rect -- center (3,), axes (2, 3: the plane's), half_m (2,) and
+        corners (4, 3) in the world frame, the rectangle IN THE PLANE that holds the members along the plane's axes --,
+        area_m2 (the plane's formula on the patch's count), fill = count / the rectangle's voxel columns (near 1 for a
+        full rectangle, lower for an L shape or one with holes: A RATIO OF TWO ESTIMATES), kind (the plane's) and the raw
+        records under record and rect_voxel.  The result gains patch_counters (kept patches, all patches, members) and,
+        with labels=True, patch_ids (bz, by, bx) i32, the id of the patch a voxel belongs to, -1 for none (a dropped
+        patch keeps its id here).  Two more waits."""
         from ._lib import PLANE_VOXEL_DTYPE
         box = self._resolve_box("planes", box, size)
         prm = np.zeros((), PLANE_PARAMS_DTYPE)
@@ -1719,7 +1833,72 @@ class Fusion:
             volume[rec["index"][:n]] = lab[:n]
             res["labels"] = volume.reshape(bsize[2], bsize[1], bsize[0])
             res["records"] = rec[:n]
+        if patches:
+            self._plane_patches(res, recs[:count.value], frame, rotate, vs, int(patch_reach),
+                                max(25, res["min_votes"] // 4) if patch_min_voxels is None else int(patch_min_voxels), labels)
         return res
+
+    def _plane_patches(self, res, recs, frame, rotate, vs, reach, min_count, labels):
+        """planes(patches=True): the patches of the planes just found, into their dicts."""
+        from ._lib import PLANE_PATCH_DTYPE
+        dtype = np.dtype(PLANE_PATCH_DTYPE)
+        counters, count = np.zeros(3, np.uint32), C.c_int32(0)
+        found = np.zeros(1024, dtype)
+        _check("emf_fusion_plane_patches",
+               load().emf_fusion_plane_patches(self._h, reach, min_count, counters.ctypes.data, found.ctypes.data, len(found),
+                                               C.byref(count)))
+        if count.value > len(found):  # rare: once more with room for all (every buffer is initialised by the call)
+            found = np.zeros(count.value, dtype)
+            _check("emf_fusion_plane_patches",
+                   load().emf_fusion_plane_patches(self._h, reach, min_count, counters.ctypes.data, found.ctypes.data,
+                                                   count.value, C.byref(count)))
+        found = found[:count.value]
+        res["patch_counters"] = tuple(int(v) for v in counters)
+        for p, r in zip(res["planes"], recs):
+            mine = found[found["plane"] == r["label"]]
+            p["patches"] = []
+            for q in mine[np.argsort(-mine["count"].astype(np.int64), kind="stable")]:
+                rect = np.zeros((), PLANE_PATCH_RECT_DTYPE)  # the C entry: plane_patch_rect gives the same bits, more slowly
+                plane, one = np.ascontiguousarray(r).reshape(1), np.ascontiguousarray(q).reshape(1)  # alive across the call
+                _check("emf_fusion_plane_patch_rect",
+                       load().emf_fusion_plane_patch_rect(plane.ctypes.data, one.ctypes.data, rect.ctypes.data))
+                f = rect["fit"]
+                n = rotate(f["n"])
+                point = frame.world64(f["centroid"] if f["fitted"] else f["n"] * f["d"])
+                p["patches"].append(dict(
+                    id=int(q["id"]), count=int(q["count"]), bounds=(tuple(int(v) for v in q["lo"]), tuple(int(v) for v in q["hi"])),
+                    point=point, normal=n, d=float((n[0] * point[0] + n[1] * point[1]) + n[2] * point[2]),
+                    thickness_m=float(f["thickness"] * vs),
+                    rect=dict(center=frame.world64(rect["center"]), axes=p["axes"].copy(), half_m=rect["half"] * vs,
+                              corners=np.stack([frame.world64(rect["corners"][3 * c:3 * c + 3]) for c in range(4)])),
+                    area_m2=float(q["count"] * (vs * vs) / np.abs(r["n"]).max()), fill=float(rect["fill"]), kind=p["kind"],
+                    record=q.copy(), rect_voxel=rect))
+        if labels:
+            n = int(res["counters"][2])
+            ids = np.full(max(n, 1), -1, np.int32)
+            _check("emf_fusion_copy_plane_patch_ids", load().emf_fusion_copy_plane_patch_ids(self._h, ids.ctypes.data, n))
+            bsize = res["box"][1]
+            volume = np.full(bsize[0] * bsize[1] * bsize[2], -1, np.int32)
+            volume[res["records"]["index"]] = ids[:n]
+            res["patch_ids"] = volume.reshape(bsize[2], bsize[1], bsize[0])
+
+    def object_support(self, ids=None, gap=0.05, margin=0.0, **plane_args):
+        """Which surface each object stands on: planes(patches=True, **plane_args) and object_shapes(ids),
+        then plane_support of every object's oriented box against every patch.  THE BOX BOUNDS THE OBSERVED SOLID BAND,
+        NOT THE BODY (object_shapes): an object seen only from above has a box that ends where the observation does,
+        and the test is about that box.  gap 0.05 m IS POLICY, NOT A MEASUREMENT.  Returns a dict: per object id
+        dict(plane (an index into planes), patch (its id), s (the height of the box's lowest point above the patch's
+        plane, metres)) or None -- also for an object without a valid box --, under "objects"; and the planes() result
+        under "planes"."""
+        found = self.planes(patches=True, **plane_args)
+        shapes = self.object_shapes(ids)
+        flat = [(k, q) for k, p in enumerate(found["planes"]) for q in p["patches"]]
+        boxes = [dict(center=s["box_center_world"], axes=s["box_axes_world"], half=s["box_half"]) if s["valid"] else None
+                 for s in shapes]
+        objects = {}
+        for s, hit in zip(shapes, plane_support([q for _, q in flat], boxes, gap, margin)):
+            objects[s["id"]] = None if hit is None else dict(plane=flat[hit[0]][0], patch=flat[hit[0]][1]["id"], s=hit[1])
+        return dict(objects=objects, planes=found)
 
     def ground_map(self, box=None, size=None, up=None, cell=None, bin=None, band=(-1.5, 0.5), reference=None,
                    robot_height=0.3, max_step=0.05, exclude=(), up_hint=None):
@@ -2071,7 +2250,8 @@ class Fusion:
                      frontier_clearance=0.0, exp_plan=False, plan_clearance=0.0, plan_through_unknown=False,
                      exp_distance_nearest=False, exp_plan_shortcut=0, exp_object_shapes=False, exp_ground_map=False,
                      ground_up=None, ground_cell=None, ground_bin=None, ground_band=(-1.5, 0.5), ground_robot_height=0.3,
-                     ground_max_step=0.05, exp_planes=False, planes_angle=20.0, planes_min_votes=None):
+                     ground_max_step=0.05, exp_planes=False, planes_angle=20.0, planes_min_votes=None,
+                     exp_plane_patches=False, plane_patch_reach=1, plane_patch_min=None):
         """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
         the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
         the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh();
@@ -2097,7 +2277,12 @@ class Fusion:
         exp_planes: write_results also writes planes.txt, one line per plane of planes(angle=planes_angle,
         min_votes=planes_min_votes) over the whole background ordered by count: kind count, then in %.9g the world
         normal, d, the point, the thickness in metres, then the bounds in voxels (include/emf_fusion.h
-        emf_fusion_set_planes_output)."""
+        emf_fusion_set_planes_output);
+        exp_plane_patches (needs exp_planes): planes.txt gains, after each plane's line, one line per patch of
+        planes(patches=True, patch_reach=plane_patch_reach, patch_min_voxels=plane_patch_min) of that plane: "patch" id
+        count, then in %.9g the world point, the four corners and fill; and, with exp_object_shapes as well, after all
+        planes one "support <object id> <plane> <patch id> <s>" line per object that rests on a patch
+        (include/emf_fusion.h emf_fusion_set_plane_patches_output)."""
         if exp_plan_shortcut and not exp_plan:
             raise ValueError("setup_output: exp_plan_shortcut adds lines to plan.txt and needs exp_plan")
         if exp_distance_nearest and not exp_distance_field:
@@ -2129,6 +2314,12 @@ class Fusion:
             _check("emf_fusion_set_planes_output",
                    load().emf_fusion_set_planes_output(self._h, int(bool(exp_planes)), float(planes_angle),
                                                        0 if planes_min_votes is None else int(planes_min_votes), int(up_floor)))
+        if exp_plane_patches:  # off: no new call
+            if not exp_planes:
+                raise ValueError("setup_output: exp_plane_patches adds lines to planes.txt and needs exp_planes")
+            _check("emf_fusion_set_plane_patches_output",
+                   load().emf_fusion_set_plane_patches_output(self._h, 1, int(plane_patch_reach),
+                                                              0 if plane_patch_min is None else int(plane_patch_min)))
         if exp_ground_map:  # off: no new call
             up = None if ground_up is None or up_floor else np.ascontiguousarray(ground_up, np.float64).reshape(3)
             _check("emf_fusion_set_ground_output",

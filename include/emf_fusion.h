@@ -461,6 +461,35 @@ int emf_fusion_plane_offsets(const double n[3], const int32_t box_size[3], doubl
                              double* inv_bin, double* shift, const uint32_t* row, uint32_t min_votes, int32_t peak_gap,
                              int32_t* peak_slots, uint32_t* peak_votes, int32_t capacity, int32_t* count);
 int emf_fusion_plane_fit(const emf_plane_moments_t* moments, const double seed_n[3], double seed_d, emf_plane_t* plane);
+/* Plane patches (include/emf_hip.h "Planes", stage 4; new behaviour, opt-in): the planes of the last
+ * emf_fusion_planes split into connected surfaces, so that two tables of one height are two patches of one plane.
+ *   plane_patches   works on what the last emf_fusion_planes left on the device; EMF_E_ARG where there is none.  reach in
+ *                   1 .. EMF_PLANE_MAX_REACH (above: EMF_E_LIMIT), min_count >= 1.  counters[3]: kept patches, all
+ *                   patches, records with a label.  patches: the kept ones in ascending id order, the first
+ *                   min(capacity, kept) of them; *count = kept.  patch.plane is the `label` of its plane.  Waits twice.
+ *   copy_plane_patch_ids  one i32 per record of the last emf_fusion_planes (the order of copy_plane_labels): the id of the
+ *                   record's patch under the last plane_patches, -1 for none; the first min(capacity, counters[2]).
+ *   plane_patch_rect / plane_support   need no device and no handle: float64 in the fixed operation order of
+ *                   include/emf_hip.h.  rect: the fit, the rectangle and the fill of one patch from its plane, box voxel
+ *                   coordinates.  support: one oriented box (centre, three unit row axes, half sizes) against one patch
+ *                   (plane n, d; rectangle centre, two row axes, half sizes), all in world metres:
+ *                   *s = (n . c - d) - sum_k |n . A_k| * h_k, the height of the box's lowest point above the plane, every
+ *                   dot product left to right; *over = 1 iff |(c - centre) . axis_j| <= half_j + margin for j = 0, 1.
+ *   set_plane_patches_output  with emf_fusion_set_planes_output on, planes.txt gains after each plane's line one line per
+ *                   patch of that plane, by count descending, ties to the lower id: "patch" id count, then in %.9g the
+ *                   world point of its own fit (3), the four corners (12) and fill; and, with the shapes output on as
+ *                   well, after all planes one line "support <object id> <plane> <patch id> <s>" per object that rests on
+ *                   a patch (gap 0.05 m, margin 0): plane is the index of the plane's line.  min_count <= 0:
+ *                   max(25, min_votes / 4) of the planes.  Off: every byte of every result file as before.
+ * Refused (EMF_E_ARG) on the sharded path; changes nothing of the session and nothing goes into a checkpoint. */
+int emf_fusion_plane_patches(emf_fusion_t* h, int32_t reach, int64_t min_count, uint32_t counters[3], emf_plane_patch_t* patches,
+                             int32_t capacity, int32_t* count);
+int emf_fusion_copy_plane_patch_ids(emf_fusion_t* h, int32_t* ids, int64_t capacity);
+int emf_fusion_plane_patch_rect(const emf_plane_t* plane, const emf_plane_patch_t* patch, emf_plane_patch_rect_t* rect);
+int emf_fusion_plane_support(const double n[3], double d, const double center[3], const double axes[6], const double half[2],
+                             const double box_center[3], const double box_axes[9], const double box_half[3], double margin,
+                             double* s, int32_t* over);
+int emf_fusion_set_plane_patches_output(emf_fusion_t* h, int on, int32_t reach, int64_t min_count);
 /* Ground map (include/emf_hip.h "Ground map"; new behaviour, opt-in): where a robot that drives on a
  * floor can stand -- a 2-D traversability map with a floor height per cell, projected on the device from the occupancy
  * classes of a box of the background (box_lo / box_size NULL: all of it) with every live object not in exclude_ids

@@ -2088,8 +2088,59 @@ int emf_hip_groundClasses(const emf_ground_cell_t* cells_dev, const int32_t map[
  * Every rejected argument -- a NULL pointer, a misaligned array (records: 16 bytes, moments: 8), a count below 1
  * (EMF_E_ARG) or above its limit (EMF_E_LIMIT), cos2 outside [0, 1] or NaN, a negative or NaN band -- returns its code
  * with nothing enqueued.  Nothing allocates, copies to the host or waits.
+ *
+ * Stage 4, patches.  A plane of stage 3 is infinite: two tables of one height are one plane.  This stage
+ * splits every plane into its connected surfaces.  Inputs: records (stage 1's output in stage 1's order), labels (stage
+ * 3's output), counters (n = min(counters[2], capacity) is read on the device, as stages 2 and 3 do), box_size and a
+ * reach in 1 .. EMF_PLANE_MAX_REACH.
+ *     Two records are LINKED iff their labels are equal and >= 0 and the Chebyshev distance of their box voxels (from
+ *     `index`) is <= reach.  Only the record list matters: a voxel without a record links nothing.
+ *     A PATCH is a connected component of the link graph; its id is the smallest RECORD INDEX among its members.  Record
+ *     order is the fixed tile order of stage 1, so the id is a pure function of the inputs.
+ *     patch: one i32 per record, the id, or -1 where labels[i] < 0.  Entries past n are not written.
+ *     patch_counters (device, 3 x u32): [EMF_PATCH_KEPT] patches of at least min_count members (written by
+ *     emf_hip_planePatches, zeroed by emf_hip_planePatchLabel), [EMF_PATCH_PATCHES] all patches, [EMF_PATCH_MEMBERS]
+ *     records with a label >= 0.  Always the full numbers, whatever the capacities.
+ * How a neighbour is found: there is NO dense volume; scratch is O(records + patches).  Stage 1's order is strictly
+ * increasing in the key  tile(v) * 2048 + within(v)  with, for the 32 x 8 x 8 tiles anchored at the box origin,
+ *     tile(v)   = ((z / 8) * ceil(by / 8) + y / 8) * ceil(bx / 32) + x / 32
+ *     within(v) = ((z % 8) * 8 + y % 8) * 32 + x % 32
+ * so the record of a voxel is found by a binary search of the voxel's key among the n records' own keys, recomputed
+ * from `index`.  One lane per member visits the HALF neighbourhood of the offsets (dx, dy, dz) that precede (0, 0, 0) in
+ * (z, y, x) order -- dz < 0, or dz == 0 and dy < 0, or dz == dy == 0 and dx < 0 -- with |dx|, |dy|, |dz| <= reach: 13
+ * offsets at reach 1, 62 at reach 2; a neighbour outside the box is skipped, the others are searched, their label compared
+ * and the two records united in a lock-free union-find over record indices whose roots are minimal indices.
+ * Records that are NOT in stage 1's order give unspecified patches, but no access leaves the arrays: the search is
+ * bounded by n, a record whose index lies outside [0, bx * by * bz) has no voxel (it links nothing), no array is indexed
+ * by a voxel, and a slot is used only where it holds the record's patch.
+ *
+ * Patch records emf_plane_patch_t: id, plane (the members' label), count, sum and sum2 in the layout of
+ * emf_plane_moments_t, the bounds lo, hi of the members, and ulo, uhi, vlo, vhi: the minimum and maximum over the members of
+ *     e_u = (u0 * x + u1 * y) + u2 * z        e_v = (v0 * x + v1 * y) + v2 * z
+ * each line a single float32 operation, never contracted, with (u, v) the two in-plane axes of the member's PLANE from
+ * axes_host (HOST, 6 P f32: u0, u1, u2, v0, v1, v2 per plane, read before the call returns).  They are reduced on the
+ * order-preserving u32 key of emf_hip_shapeExtents, so they do not depend on the order of lanes or workgroups.  A member
+ * whose label is >= P contributes to everything but the four floats (+inf, -inf without a contribution).
+ * Roots are ranked by a scan in record order; a record finds its patch's slot by binary search; the integer sums are
+ * aggregated per run of equal patch within a wave, then one integer atomic per quantity and run.  Patches of fewer than
+ * min_count (>= 1) members are dropped; the kept ones are written in ascending id order, placed by scan, at most
+ * capacity_patches (>= 0; 0: out may be NULL) of them.
+ *     n_patches: patch_counters[EMF_PATCH_PATCHES] as the host read it after emf_hip_planePatchLabel -- the one wait, with
+ *     the contract of emf_hip_frontierClusters: a smaller value drops the patches of the largest ids (from the records
+ *     and from EMF_PATCH_KEPT), a larger one only wastes scratch; 0 writes EMF_PATCH_KEPT = 0 and nothing else.
+ *     scratch: emf_hip_planePatchScratchBytes(capacity, n_patches) bytes, 16-byte aligned (0 for a capacity outside
+ *     1 .. 2^31 - 1); contents undefined afterwards.
+ * Every buffer is initialised by a launch of the entry's own: a second call into dirty buffers gives the same bytes.
+ * Every rejected argument -- a NULL pointer, a reach below 1 (EMF_E_ARG) or above EMF_PLANE_MAX_REACH (EMF_E_LIMIT),
+ * min_count < 1, P outside 1 .. EMF_PLANE_MAX_PLANES, a negative capacity_patches, a misaligned array (records and
+ * scratch: 16 bytes, out: 8, patch and counters: 4, labels: 2) -- returns its code with nothing enqueued.  Nothing
+ * allocates, copies to the host or waits.
  * ---------------------------------------------------------------------------------------------- */
 #define EMF_PLANE_MAX_K 31
+#define EMF_PLANE_MAX_REACH 2
+#define EMF_PATCH_KEPT 0
+#define EMF_PATCH_PATCHES 1
+#define EMF_PATCH_MEMBERS 2
 #define EMF_PLANE_MAX_DIRS 16
 #define EMF_PLANE_MAX_SLOTS 4096
 #define EMF_PLANE_MAX_PLANES 64
@@ -2105,6 +2156,15 @@ typedef struct emf_plane_moments {
     uint64_t sum2[6];    /* sums of xx, yy, zz, xy, xz, yz: the layout of emf_shape_moments_t */
     int32_t lo[3], hi[3]; /* bounds of the members; box_size and -1 without one */
 } emf_plane_moments_t;   /* 104 bytes */
+
+typedef struct emf_plane_patch {
+    int32_t id, plane;        /* the smallest record index of the members; their label */
+    uint64_t count;
+    uint64_t sum[3];          /* as emf_plane_moments_t */
+    uint64_t sum2[6];
+    int32_t lo[3], hi[3];     /* bounds of the members, box voxels */
+    float ulo, uhi, vlo, vhi; /* extents along the plane's two in-plane axes, voxels */
+} emf_plane_patch_t;          /* 128 bytes */
 
 /* The host steps between the stages (emf_fusion_plane_directions / _offsets / _fit of include/emf_fusion.h; no device).
  * Float64, every line a single operation in this order, sums left to right, no contraction:
@@ -2150,6 +2210,28 @@ typedef struct emf_plane {
     int32_t fitted, label; /* label: the plane's value in the label array */
 } emf_plane_t; /* 176 bytes */
 
+/* The host steps behind stage 4 (emf_fusion_plane_patch_rect of include/emf_fusion.h; no device).  Float64, every line a
+ * single operation in this order, sums left to right, no contraction.  Inputs: the patch and its PLANE (n, d, axes
+ * u = axes[0..2], v = axes[3..5], box voxel coordinates).
+ *   fit         emf_fusion_plane_fit CALLED on the patch's count, sum, sum2, lo, hi with the plane's (n, d) as the seed:
+ *               the patch's own centroid, normal, d and thickness; below 3 members it keeps the seed (fitted = 0).
+ *   rectangle   the extents widened by half a voxel on each side:
+ *                   a0 = double(ulo) - 0.5   a1 = double(uhi) + 0.5   b0 = double(vlo) - 0.5   b1 = double(vhi) + 0.5
+ *                   cu = (a0 + a1) * 0.5     hu = (a1 - a0) * 0.5     cv = (b0 + b1) * 0.5     hv = (b1 - b0) * 0.5
+ *               center_j = (d * n_j + u_j * cu) + v_j * cv, and the corners k = 0 .. 3 with (su, sv) = (-1, -1), (+1, -1),
+ *               (+1, +1), (-1, +1):  eu = cu + su * hu,  ev = cv + sv * hv,  corner_kj = (d * n_j + u_j * eu) + v_j * ev
+ *               (each product formed first, then added), with the PLANE's n and d: the rectangle lies in the plane.
+ *   fill        count / (((double(uhi) - double(ulo)) + 1) * ((double(vhi) - double(vlo)) + 1) * max |n_j|), the
+ *               products left to right: near 1 for a full rectangle, lower for an L shape or one with holes.  A ratio
+ *               of two estimates. */
+typedef struct emf_plane_patch_rect {
+    emf_plane_t fit;    /* the patch's own fit */
+    double center[3];   /* box voxel coordinates */
+    double half[2];     /* hu, hv in voxels */
+    double corners[12]; /* 4 x 3 */
+    double fill;
+} emf_plane_patch_rect_t; /* 320 bytes */
+
 size_t emf_hip_planeSurfaceScratchBytes(const int32_t box_size[3]);
 int emf_hip_planeSurface(const float* tsdf, const float* weights, const int32_t res[3], const int32_t box_lo[3],
                          const int32_t box_size[3], const uint8_t* unseenTiles, emf_plane_voxel_t* records, uint32_t capacity,
@@ -2162,6 +2244,14 @@ int emf_hip_planeOffsets(const emf_plane_voxel_t* records, const uint32_t* count
 int emf_hip_planeAssign(const emf_plane_voxel_t* records, const uint32_t* counters, uint32_t capacity,
                         const int32_t box_size[3], const float* planes_host, int32_t P, float cos2, float band,
                         int16_t* labels, emf_plane_moments_t* moments, emf_stream_t stream);
+int emf_hip_planePatchLabel(const emf_plane_voxel_t* records, const int16_t* labels, const uint32_t* counters, uint32_t capacity,
+                            const int32_t box_size[3], int32_t reach, int32_t* patch, uint32_t* patch_counters,
+                            emf_stream_t stream);
+size_t emf_hip_planePatchScratchBytes(uint32_t capacity, uint32_t n_patches);
+int emf_hip_planePatches(const emf_plane_voxel_t* records, const int16_t* labels, const int32_t* patch, const uint32_t* counters,
+                         uint32_t capacity, const int32_t box_size[3], const float* axes_host, int32_t P, int64_t min_count,
+                         uint32_t n_patches, void* scratch, emf_plane_patch_t* out, int32_t capacity_patches,
+                         uint32_t* patch_counters, emf_stream_t stream);
 
 #ifdef __cplusplus
 }
