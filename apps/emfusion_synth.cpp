@@ -8,6 +8,7 @@
 //                  [--distance-field] [--distance-cap M] [--distance-unknown-obstacle] [--distance-nearest]
 //                  [--frontiers] [--frontier-min-voxels N] [--frontier-clearance M]
 //                  [--plan] [--plan-clearance M] [--plan-through-unknown] [--plan-shortcut W] [--object-shapes]
+//                  [--object-contacts] [--contact-touch M]
 //                  [--ground-map] [--ground-up X,Y,Z] [--ground-cell M] [--ground-bin M] [--ground-band LO,HI]
 //                  [--ground-robot-height M] [--ground-max-step M] [--planes] [--planes-angle DEG] [--planes-min-votes N]
 //                  [--plane-patches] [--plane-patch-reach R] [--plane-patch-min N]
@@ -126,6 +127,12 @@ static int planShortcut = 0;
 // integer moments of its observed solid band (not its body), then its box in the world frame;
 // without it no output byte changes
 static bool objectShapesOut = false;
+// --object-contacts (needs --out): writeResults also writes OUT/contacts.txt, one line per ordered pair (probe object,
+// field object or background) with a sampled surface voxel: the ids, the eight counts, min_s and the world contact point
+// and normal; --contact-touch M: the touching threshold in metres (default: one voxel of the probe);
+// without --object-contacts no output byte changes
+static bool objectContactsOut = false, contactTouchGiven = false;
+static double contactTouch = -1.0;
 // --ground-map (needs --out): writeResults also writes OUT/ground.bin and OUT/ground.txt, the 2-D traversability map of
 // the whole background with a floor height per cell; --ground-up X,Y,Z (world frame; default: minus the
 // background's y axis), --ground-cell / --ground-bin M (default: two voxels), --ground-band LO,HI (metres relative to
@@ -264,6 +271,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     emf.setPlanOutput(planOut, planClearance, planThroughUnknown);
     if (planShortcut > 0) emf.setPlanShortcutOutput(planShortcut);
     if (objectShapesOut) emf.setShapeOutput(true);
+    if (objectContactsOut) emf.setContactsOutput(true, contactTouch);
     if (groundOut.on) emf.setGroundOutput(groundOut);
     if (groundUpFloor) emf.setGroundUpFloor(true);
     if (planesOut.on) emf.setPlanesOutput(planesOut);
@@ -377,6 +385,8 @@ int main(int argc, char** argv) {
         else if (a == "--distance-unknown-obstacle") distanceUnknownObstacle = true;
         else if (a == "--distance-nearest") distanceNearest = true;
         else if (a == "--object-shapes") objectShapesOut = true;
+        else if (a == "--object-contacts") objectContactsOut = true;
+        else if (a == "--contact-touch" && i + 1 < argc) contactTouchGiven = true, contactTouch = std::atof(argv[++i]);
         else if (a == "--ground-map") groundOut.on = true;
         else if (a == "--ground-up" && i + 1 < argc && std::string(argv[i + 1]) == "floor") groundGiven = true, groundUpFloor = true, ++i;
         else if (a == "--ground-up" && i + 1 < argc) groundGiven = true, groundBad |= !parseList(argv[++i], groundOut.up, 3);
@@ -449,6 +459,11 @@ int main(int argc, char** argv) {
     if ((patchesGiven && !patchesOut.on) || (patchesOut.on && (!planesOut.on || patchesOut.reach < 1 || patchesOut.reach > EMF_PLANE_MAX_REACH))) {
         std::fprintf(stderr, "usage: emfusion_synth: --plane-patch-reach R (1 or 2) and --plane-patch-min N need --plane-patches, which "
                              "adds the patch lines to planes.txt and needs --planes\n");
+        return 2;
+    }
+    if ((contactTouchGiven && (!objectContactsOut || !(contactTouch >= 0.0))) || (objectContactsOut && outDir.empty())) {
+        std::fprintf(stderr, "usage: emfusion_synth: --contact-touch M (>= 0, metres) needs --object-contacts, which writes "
+                             "contacts.txt and needs --out DIR\n");
         return 2;
     }
     if (motionMasks && !maskDir.empty()) {  // (before any device is touched)
@@ -538,6 +553,7 @@ int main(int argc, char** argv) {
         emf.setPlanOutput(planOut, planClearance, planThroughUnknown);
         if (planShortcut > 0) emf.setPlanShortcutOutput(planShortcut);
         if (objectShapesOut) emf.setShapeOutput(true);
+        if (objectContactsOut) emf.setContactsOutput(true, contactTouch);
         if (groundOut.on) emf.setGroundOutput(groundOut);
         if (groundUpFloor) emf.setGroundUpFloor(true);
         if (planesOut.on) emf.setPlanesOutput(planesOut);

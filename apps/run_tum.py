@@ -96,6 +96,12 @@ def main():
     ap.add_argument("--object-shapes", dest="object_shapes", action="store_true",
                     help="also write OUT/shapes.txt: one line per live object in id order, the integer moments of its "
                          "observed solid band (not its body), then its box in the world frame")
+    ap.add_argument("--object-contacts", dest="object_contacts", action="store_true",
+                    help="also write OUT/contacts.txt: one line per ordered pair (probe object, field object or background) "
+                         "with a sampled surface voxel: the ids, the eight counts, min_s (1: at least one truncation distance "
+                         "apart, not a distance) and the world contact point and normal")
+    ap.add_argument("--contact-touch", dest="contact_touch", type=float, default=None, metavar="M",
+                    help="with --object-contacts: the touching threshold in metres (default: one voxel of the probe)")
     ap.add_argument("--ground-map", dest="ground_map", action="store_true",
                     help="also write OUT/ground.bin and OUT/ground.txt: the 2-D traversability map of the whole background "
                          "with a floor height per cell (classes, then records of floor, top, clear, levels)")
@@ -163,6 +169,8 @@ def main():
         ap.error("--plan-shortcut W adds the waypoints lines to plan.txt and needs --plan")
     if args.plan_shortcut < 0:
         ap.error("--plan-shortcut takes a positive window W")
+    if args.contact_touch is not None and (not args.object_contacts or not args.contact_touch >= 0):
+        ap.error("--contact-touch M (>= 0, metres) needs --object-contacts")
     if args.plane_patches and not args.planes:
         ap.error("--plane-patches adds the patch lines to planes.txt and needs --planes")
     if (args.plane_patch_reach is not None or args.plane_patch_min is not None) and not args.plane_patches:
@@ -238,7 +246,8 @@ def main():
                      frontier_clearance=max(args.frontier_clearance, 0.0), exp_plan=args.plan,
                      plan_clearance=max(args.plan_clearance, 0.0), plan_through_unknown=args.plan_through_unknown,
                      exp_distance_nearest=args.distance_nearest, exp_plan_shortcut=args.plan_shortcut,
-                     exp_object_shapes=args.object_shapes, exp_ground_map=args.ground_map,
+                     exp_object_shapes=args.object_shapes, exp_object_contacts=args.object_contacts,
+                     contact_touch=args.contact_touch, exp_ground_map=args.ground_map,
                      ground_up=None if args.ground_up is None else "floor" if args.ground_up == "floor"
                      else [float(v) for v in args.ground_up.split(",")],
                      exp_planes=args.planes, planes_angle=args.planes_angle, planes_min_votes=args.planes_min_votes,

@@ -235,6 +235,7 @@ SIGNATURES = {
     "emf_hip_planePatchScratchBytes": [C.c_uint32, C.c_uint32],
     "emf_hip_planePatches": [_FP, _FP, _FP, _FP, C.c_uint32, _I3, C.POINTER(C.c_float), C.c_int32, C.c_int64, C.c_uint32, _FP,
                              _FP, C.c_int32, _FP, _STREAM],
+    "emf_hip_contactProbe": [_FP, C.POINTER(C.c_int32), C.c_int32, _FP, C.c_void_p, C.c_int32, _FP, _STREAM],
 }
 
 
@@ -354,6 +355,18 @@ PLANE_PATCH_DTYPE = [("id", "<i4"), ("plane", "<i4"), ("count", "<u8"), ("sum", 
                      ("hi", "<i4", 3), ("ulo", "<f4"), ("uhi", "<f4"), ("vlo", "<f4"), ("vhi", "<f4")]
 PLANE_MAX_REACH = 2
 PATCH_KEPT, PATCH_PATCHES, PATCH_MEMBERS = 0, 1, 2
+# include/emf_hip.h "Object contacts": emf_contact_pair_t (64 bytes), emf_contact_t (144), emf_contact_side_t (68) and
+# emf_contact_summary_t (264)
+CONTACT_PAIR_DTYPE = [("a", "<i4"), ("b", "<i4"), ("R", "<f4", 9), ("t", "<f4", 3), ("touch", "<f4"), ("reserved", "<i4")]
+CONTACT_DTYPE = [("surface", "<u8"), ("outside", "<u8"), ("unknown", "<u8"), ("masked", "<u8"), ("sampled", "<u8"),
+                 ("inside", "<u8"), ("touching", "<u8"), ("normals", "<u8"), ("sum", "<u8", 3), ("gsum", "<i8", 3),
+                 ("lo", "<i4", 3), ("hi", "<i4", 3), ("min_s", "<f4"), ("reserved", "<i4")]
+CONTACT_SIDE_DTYPE = [("res", "<i4", 3), ("voxel_size", "<f4"), ("truncdist", "<f4"), ("R", "<f4", 9), ("t", "<f4", 3)]
+CONTACT_SUMMARY_DTYPE = [("state", "<i4"), ("saturated", "<i4"), ("direction", "<i4"), ("has_normal", "<i4"),
+                         ("distance_m", "<f8"), ("point", "<f8", 3), ("normal", "<f8", 3), ("corners", "<f8", 24)]
+CONTACT_MAX_PAIRS = 65535
+CONTACT_UNSEEN, CONTACT_APART, CONTACT_TOUCHING, CONTACT_PENETRATING = 0, 1, 2, 3
+CONTACT_STATES = ("unseen", "apart", "touching", "penetrating")
 RAY_REACHED, RAY_BLOCKED, RAY_LEFT, RAY_OUTSIDE, RAY_INVALID = 0, 1, 2, 3, 4
 FRONTIER_KEPT, FRONTIER_CLUSTERS, FRONTIER_VOXELS = 0, 1, 2
 # include/emf_hip.h "Planning"

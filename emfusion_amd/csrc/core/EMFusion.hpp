@@ -550,6 +550,40 @@ public:
     /** writeResults also writes shapes.txt, one line per live object in id order (writeShapes); without it no output byte changes. */
     void setShapeOutput(bool on) { expShapes_ = on; }
     void writeShapes(const std::string& dir);
+    /** One ordered pair of objectContacts(): probe a, field b (ids; 0 = the background), what it carried and its record. */
+    struct ObjectContact {
+        int a = 0, b = 0;
+        emf_contact_pair_t pair;  // a, b: the slots of the call's compact table; R, t: b's frame <- a's; touch
+        emf_contact_t record;     // integers and min_s
+    };
+    /** What objectContacts() leaves: the models asked (fields; the probes are those with id != 0), the ordered pairs
+     *  grouped by probe, and one summary per unordered pair {a, b}: recAB its record a -> b, recBA b -> a or -1. */
+    struct ObjectContacts {
+        std::vector<int> ids;
+        std::vector<emf_contact_side_t> sides;  // per id: res, voxel size, truncation distance, pose
+        std::vector<ObjectContact> pairs;
+        struct Summary {
+            int a = 0, b = 0, recAB = -1, recBA = -1;
+            emf_contact_summary_t summary;
+        };
+        std::vector<Summary> summaries;
+    };
+    /**
+     * Object contacts (include/emf_hip.h "Object contacts"): whether the asked objects touch each other
+     * or the background, how far apart their surfaces are and whether they interpenetrate, read from the signed-distance
+     * volumes.  IT MEASURES WHAT THE VOLUMES SAY: min_s == 1 is "at least one truncation distance apart", a penetration
+     * deeper than the fused band reads UNKNOWN, a clearance reads up to one probe voxel large.  Probes are the asked
+     * objects; fields are the asked objects and, with includeBackground, slot 0 (the background as a probe is not
+     * built).  touchMetres < 0: one voxel of the probe -- a policy, not a measurement.  Drains the frame as the other
+     * queries do, then one table, one device block, one launch and one wait; the summaries on the host.  An id that
+     * does not exist or is named twice is EMF_E_ARG.  Changes nothing of the session and nothing goes into a
+     * checkpoint.  Refused (EMF_E_ARG) on the sharded path.
+     */
+    const ObjectContacts& objectContacts(const std::vector<int>& ids, bool includeBackground = true, double touchMetres = -1.0);
+    const ObjectContacts& lastContacts() const { return ctLast; }
+    /** writeResults also writes contacts.txt (writeContacts); without it no output byte changes. */
+    void setContactsOutput(bool on, double touchMetres = -1.0) { expContacts_ = on, expContactTouch_ = touchMetres; }
+    void writeContacts(const std::string& dir);
     /** The result of groundMap(): the frame, the pose "ground metres -> world" and the arrays left on the device. */
     struct GroundMap {
         QueryBox box;
@@ -1240,6 +1274,13 @@ private:
     uint32_t pnCapacity = 0;         // the capacity planes() gave stage 1: what the later stages bound the count by
     DeviceBuffer ppIds, ppScratch, ppOut, ppSmall;  // the ids, the slots' scratch, the records, the three counters
     bool expGroundUpFloor_ = false;  // setGroundUpFloor
+
+    // ---- object contacts (objectContacts; EMFusionContacts.cpp): allocated at first use, never in a checkpoint;
+    // behind all existing members ----
+    ObjectContacts ctLast;
+    DeviceBuffer ctScratch;          // the compact model table, the pairs and the records of one call
+    bool expContacts_ = false;       // setContactsOutput
+    double expContactTouch_ = -1.0;
 };
 
 /**
@@ -1305,6 +1346,17 @@ bool planeSupport(const double n[3], double d, const double center[3], const dou
  */
 void shapeBox(const emf_shape_moments_t& mom, const emf_shape_frame_t& frame, const emf_shape_extents_t& ext, const int32_t res[3],
               float voxelSize, const float R[9], const float t[3], emf_shape_box_t& out);
+
+/**
+ * The host stage of the object contacts, without a device: float64, every line a single operation in the
+ * order written out in include/emf_hip.h "Object contacts".  contactPose: what a pair carries (b's frame <- a's frame)
+ * from the two poses (world <- model), rounded to f32 once.  contactTouch: metres -> units of b's stored tsdf.
+ * contactSummary: the unordered pair from the record a -> b and, where there is one, b -> a (else nullptr).
+ */
+void contactPose(const float Ra[9], const float ta[3], const float Rb[9], const float tb[3], float R[9], float t[3]);
+float contactTouch(double touchMetres, float truncdistB);
+void contactSummary(const emf_contact_t& ab, const emf_contact_t* ba, const emf_contact_side_t& a, const emf_contact_side_t& b,
+                    emf_contact_summary_t& out);
 
 /**
  * The frame of a ground map, on the host, without a device: float64 in the operation order written out

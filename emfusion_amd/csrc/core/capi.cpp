@@ -988,6 +988,72 @@ int emf_fusion_set_shape_output(emf_fusion_t* h, int on) {
     return guarded([&] { h->impl->setShapeOutput(on != 0); });
 }
 
+int emf_fusion_object_contacts(emf_fusion_t* h, const int32_t* ids, int32_t n, int32_t include_background, double touch_m,
+                               int32_t* ids_out, emf_contact_side_t* sides_out, int32_t* pair_ids_out, emf_contact_pair_t* pairs_out,
+                               emf_contact_t* records_out, int32_t* summary_ids_out, emf_contact_summary_t* summaries_out,
+                               int32_t* n_pairs_out, int32_t* n_summaries_out) {
+    REQ(h);
+    if (n < 0 || (n > 0 && !ids)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_object_contacts: %d ids without a list", n);
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const EMFusion::ObjectContacts& c = h->impl->objectContacts(std::vector<int>(ids, ids + n), include_background != 0, touch_m);
+        for (size_t k = 0; k < c.ids.size(); ++k) {
+            if (ids_out) ids_out[k] = c.ids[k];
+            if (sides_out && k < c.sides.size()) sides_out[k] = c.sides[k];
+        }
+        for (size_t k = 0; k < c.pairs.size(); ++k) {
+            if (pair_ids_out) pair_ids_out[2 * k] = c.pairs[k].a, pair_ids_out[2 * k + 1] = c.pairs[k].b;
+            if (pairs_out) pairs_out[k] = c.pairs[k].pair;
+            if (records_out) records_out[k] = c.pairs[k].record;
+        }
+        for (size_t k = 0; k < c.summaries.size(); ++k) {
+            const EMFusion::ObjectContacts::Summary& s = c.summaries[k];
+            if (summary_ids_out) {
+                int32_t* o = summary_ids_out + 4 * k;
+                o[0] = s.a, o[1] = s.b, o[2] = s.recAB, o[3] = s.recBA;
+            }
+            if (summaries_out) summaries_out[k] = s.summary;
+        }
+        if (n_pairs_out) *n_pairs_out = static_cast<int32_t>(c.pairs.size());
+        if (n_summaries_out) *n_summaries_out = static_cast<int32_t>(c.summaries.size());
+    });
+}
+
+int emf_fusion_contact_pose(const float Ra[9], const float ta[3], const float Rb[9], const float tb[3], float R[9], float t[3]) {
+    REQ(Ra);
+    REQ(ta);
+    REQ(Rb);
+    REQ(tb);
+    REQ(R);
+    REQ(t);
+    return guarded([&] { contactPose(Ra, ta, Rb, tb, R, t); });
+}
+
+int emf_fusion_contact_touch(double touch_m, float truncdist_b, float* touch) {
+    REQ(touch);
+    return guarded([&] { *touch = contactTouch(touch_m, truncdist_b); });
+}
+
+int emf_fusion_contact_summary(const emf_contact_t* ab, const emf_contact_t* ba, const emf_contact_side_t* a,
+                               const emf_contact_side_t* b, emf_contact_summary_t* summary) {
+    REQ(ab);
+    REQ(a);
+    REQ(b);
+    REQ(summary);
+    return guarded([&] { contactSummary(*ab, ba, *a, *b, *summary); });
+}
+
+int emf_fusion_set_contacts_output(emf_fusion_t* h, int on, double touch_m) {
+    REQ(h);
+    if (touch_m != touch_m) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_set_contacts_output: the touch distance is NaN");
+        return EMF_E_ARG;
+    }
+    return guarded([&] { h->impl->setContactsOutput(on != 0, touch_m); });
+}
+
 int emf_fusion_planes(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], const emf_plane_params_t* params,
                       int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3], uint32_t counters[4], uint32_t* min_votes,
                       emf_plane_t* planes, int32_t capacity, int32_t* count) {

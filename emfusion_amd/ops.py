@@ -1977,6 +1977,72 @@ def shape_extents(volumes, frames, first=0, out=None, stream=None):
     return records.numpy()[:n] if out is None else out
 
 
+# ---- object contacts (include/emf_hip.h "Object contacts") ---------------------------------------
+
+CONTACT_PAIR_DTYPE = np.dtype(_lib.CONTACT_PAIR_DTYPE)
+CONTACT_DTYPE = np.dtype(_lib.CONTACT_DTYPE)
+assert CONTACT_PAIR_DTYPE.itemsize == 64 and CONTACT_DTYPE.itemsize == 144
+
+
+def contact_table(volumes):
+    """The device model table of contact_probe -- shape_table's plus the voxel size of every volume
+    (dict(tsdf=, weights=, voxel_size=, fg_mask=None, unseen_tiles=None)) -- and the host resolutions."""
+    models, n = [], len(volumes)
+    res = (C.c_int32 * (3 * max(n, 1)))()
+    for k, v in enumerate(volumes):
+        tsdf = _vol(v["tsdf"], np.float32)
+        m = _lib.EmfModel()
+        m.tsdf, m.weights = tsdf.ptr, _vol(v["weights"], np.float32).ptr
+        assert v["weights"].shape == tsdf.shape
+        if v.get("fg_mask") is not None:
+            assert v["fg_mask"].shape == tsdf.shape
+            m.fgVolMask = _vol(v["fg_mask"], np.uint8).ptr
+        if v.get("unseen_tiles") is not None:
+            m.unseenTiles = v["unseen_tiles"].ptr
+        nz, ny, nx = tsdf.shape
+        m.res[:] = [nx, ny, nz]
+        m.voxelSize = float(np.float32(v["voxel_size"]))
+        res[3 * k:3 * k + 3] = [nx, ny, nz]
+        models.append(m)
+    return (upload_models(models) if models else None), res
+
+
+def contact_pairs(pairs):
+    """A list of (a, b, R, t, touch) -- or an array of CONTACT_PAIR_DTYPE -- as a contiguous array of CONTACT_PAIR_DTYPE."""
+    if isinstance(pairs, np.ndarray) and pairs.dtype == CONTACT_PAIR_DTYPE:
+        return np.ascontiguousarray(pairs.reshape(-1))
+    out = np.zeros(len(pairs), CONTACT_PAIR_DTYPE)
+    for k, (a, b, R, t, touch) in enumerate(pairs):
+        out[k]["a"], out[k]["b"] = int(a), int(b)
+        out[k]["R"] = np.asarray(R, np.float32).reshape(9)
+        out[k]["t"] = np.asarray(t, np.float32).reshape(3)
+        out[k]["touch"] = np.float32(touch)
+    return out
+
+
+def contact_probe(volumes, pairs, out=None, stream=None, lib=None):
+    """emf_hip_contactProbe: for every ordered pair (probe a, field b) of `pairs` -- (a, b, R, t, touch) with a, b indices
+    into `volumes`, R, t taking a's frame into b's and touch in units of b's stored tsdf -- the surface voxels of a are
+    taken into b's volume and b's tsdf is sampled there trilinearly, in one launch for the whole list.  Returns a numpy
+    array of CONTACT_DTYPE records, one per pair in the list's order (surface = outside + unknown + masked + sampled;
+    inside, touching, normals; sum, gsum, lo, hi of the touching voxels; min_s), or with out= (a device array of at
+    least that many records) that array.  IT MEASURES WHAT THE VOLUMES SAY: min_s == 1 means "at least one truncation
+    distance apart", a penetration deeper than the fused band reads unknown, and a clearance reads up to one probe voxel
+    large.  A list grouped by probe is the fast one; any order gives the same bytes.  lib: another build of the kernel
+    library (_lib.load_variant)."""
+    L = _L if lib is None else lib
+    table, res = contact_table(volumes)
+    host = contact_pairs(pairs)
+    n = len(host)
+    d_pairs = DeviceArray.from_numpy(host if n else np.zeros(1, CONTACT_PAIR_DTYPE))
+    records = DeviceArray((max(n, 1),), CONTACT_DTYPE) if out is None else out
+    assert records.dtype == CONTACT_DTYPE and records.shape[0] >= n
+    check("emf_hip_contactProbe",
+          L.emf_hip_contactProbe(_ptr(table), res, len(volumes), _ptr(d_pairs), C.c_void_p(host.ctypes.data), n, _ptr(records),
+                                 _stream(stream)))
+    return records.numpy()[:n] if out is None else out
+
+
 # ---- ground map (include/emf_hip.h "Ground map", DESIGN.md 5.24) -------------------------------------------------
 
 GROUND_CELL_DTYPE = np.dtype(_lib.GROUND_CELL_DTYPE)

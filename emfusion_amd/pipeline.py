@@ -178,6 +178,12 @@ def load() -> C.CDLL:
         "emf_fusion_shape_frame": [C.c_void_p, C.c_void_p],
         "emf_fusion_shape_box": [C.c_void_p, C.c_void_p, C.c_void_p, ip, C.c_float, fp, fp, C.c_void_p],
         "emf_fusion_set_shape_output": [vp, C.c_int],
+        "emf_fusion_object_contacts": [vp, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, ip, ip],
+        "emf_fusion_contact_pose": [fp, fp, fp, fp, fp, fp],
+        "emf_fusion_contact_touch": [C.c_double, C.c_float, fp],
+        "emf_fusion_contact_summary": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+        "emf_fusion_set_contacts_output": [vp, C.c_int, C.c_double],
         "emf_fusion_planes": [vp, ip, ip, C.c_void_p, ip, ip, fp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                               C.POINTER(C.c_int32)],
         "emf_fusion_copy_plane_labels": [vp, C.c_void_p, C.c_void_p, C.c_int64],
@@ -592,6 +598,59 @@ def shape_box(moments, frame, extents, res, voxel_size, R, t):
            load().emf_fusion_shape_box(m.ctypes.data, f.ctypes.data, e.ctypes.data, (C.c_int32 * 3)(*[int(v) for v in res]),
                                        float(voxel_size), _farr(R, 9), _farr(t, 3), out.ctypes.data))
     return out
+
+
+def _contact_dtypes():
+    from . import _lib as hip
+    return (np.dtype(hip.CONTACT_PAIR_DTYPE), np.dtype(hip.CONTACT_DTYPE), np.dtype(hip.CONTACT_SIDE_DTYPE),
+            np.dtype(hip.CONTACT_SUMMARY_DTYPE))
+
+
+def contact_pose(pose_a, pose_b):
+    """emf_fusion_contact_pose, on the host without a device: what a contact pair (probe a, field b)
+    carries -- (R, t) taking a's frame into b's, R = Rb^T Ra, t = Rb^T (ta - tb) -- from the two poses (R, t: model ->
+    world, f32).  Float64 in the fixed operation order of include/emf_hip.h "Object contacts", rounded to f32 once."""
+    (Ra, ta), (Rb, tb) = pose_a, pose_b
+    R, t = np.zeros(9, np.float32), np.zeros(3, np.float32)
+    _check("emf_fusion_contact_pose",
+           load().emf_fusion_contact_pose(_farr(Ra, 9), _farr(ta, 3), _farr(Rb, 9), _farr(tb, 3),
+                                          R.ctypes.data_as(C.POINTER(C.c_float)), t.ctypes.data_as(C.POINTER(C.c_float))))
+    return R.reshape(3, 3), t
+
+
+def contact_touch(touch_m, truncdist_b):
+    """emf_fusion_contact_touch: a distance in metres in units of the field's stored tsdf, float(touch_m / truncdist_b)."""
+    out = (C.c_float * 1)()
+    _check("emf_fusion_contact_touch", load().emf_fusion_contact_touch(float(touch_m), float(np.float32(truncdist_b)), out))
+    return np.float32(out[0])
+
+
+def contact_summary(record_ab, record_ba, side_a, side_b):
+    """emf_fusion_contact_summary, on the host without a device: the unordered pair {a, b} from the record a -> b of
+    ops.contact_probe and, where b was a probe as well, b -> a (else None).  side_a, side_b: records of
+    _lib.CONTACT_SIDE_DTYPE (res, voxel_size, truncdist, R, t: model -> world).  Returns a 0-d array of
+    _lib.CONTACT_SUMMARY_DTYPE: state (0 unseen, 1 apart, 2 touching, 3 penetrating), saturated (the deciding min_s is 1:
+    AT LEAST one truncation distance apart, not a distance), direction (0: a -> b, 1: b -> a, -1: no touching voxel),
+    has_normal, distance_m, and the world point, normal (out of the probe of `direction`) and the eight corners of the
+    contact region.  Float64 in the fixed operation order of include/emf_hip.h "Object contacts"."""
+    _, cd, sd, ud = _contact_dtypes()
+    ab = np.ascontiguousarray(np.asarray(record_ab, cd).reshape(()))
+    ba = None if record_ba is None else np.ascontiguousarray(np.asarray(record_ba, cd).reshape(()))
+    a, b = (np.ascontiguousarray(np.asarray(v, sd).reshape(())) for v in (side_a, side_b))
+    out = np.zeros((), ud)
+    _check("emf_fusion_contact_summary",
+           load().emf_fusion_contact_summary(ab.ctypes.data, None if ba is None else ba.ctypes.data, a.ctypes.data, b.ctypes.data,
+                                             out.ctypes.data))
+    return out
+
+
+def contact_line(a, b, record, side_a, side_b):
+    """One line of contacts.txt (without the newline): the ids, the eight counts, then in %.9g min_s and the world
+    contact point and normal of this record alone."""
+    s = contact_summary(record, None, side_a, side_b)
+    ints = [int(record[k]) for k in ("surface", "outside", "unknown", "masked", "sampled", "inside", "touching", "normals")]
+    floats = [float(record["min_s"])] + [float(v) for v in s["point"]] + [float(v) for v in s["normal"]]
+    return " ".join([str(int(a)), str(int(b))] + [str(v) for v in ints] + ["%.9g" % v for v in floats])
 
 
 # include/emf_hip.h "Planes": emf_plane_params_t (56 bytes) and emf_plane_t (176)
@@ -1746,6 +1805,68 @@ class Fusion:
             out.append(r)
         return out
 
+    def object_contacts(self, ids=None, background=True, touch=None):
+        """Whether objects touch each other or the scene, how far apart their surfaces are and whether they interpenetrate
+        (DESIGN.md 5.27), read on the device from the signed-distance volumes as they are: every surface voxel of a
+        PROBE a is taken through the relative pose into a FIELD b's volume and b's tsdf is sampled there trilinearly --
+        one launch for all ordered pairs, one wait.
+
+        IT MEASURES WHAT THE VOLUMES SAY.  A tsdf is clamped to +-1, so a summary with saturated=True means "at least
+        one truncation distance apart" and its distance_m is no distance.  Nothing is fused deeper than one truncation
+        distance behind a surface, so a deeper penetration reads `unknown`, not a larger depth.  A surface voxel lies up
+        to one voxel behind the probe's zero crossing, so clearances read up to one probe voxel large.
+
+        ids: live object ids, each once (default: all of them, in creation order): the probes.  The fields are those
+        objects and, with background=True, the background (id 0), so a-versus-background says whether an object rests
+        on the scene; the background is never a probe.  touch: the `touching` threshold in metres; None means one voxel
+        of the probe -- A POLICY, NOT A MEASUREMENT.  An id that does not exist raises.
+
+        Returns dict(pairs=, summaries=, ids=, sides=).  pairs: one dict per ordered pair, grouped by probe: a, b (ids),
+        R, t (b's frame <- a's), touch (in units of b's stored tsdf), the counts surface = outside + unknown + masked +
+        sampled, inside, touching, normals, then min_s, sum, gsum, lo, hi and the raw `record` and `pair`.  summaries:
+        one dict per unordered pair: a, b, state ("unseen", "apart", "touching", "penetrating"), distance_m, saturated,
+        direction (0: a -> b, 1: b -> a, None), point, normal (world, out of the probe of `direction`; None without),
+        corners (8 x 3, world) and the raw `summary`, with record_ab / record_ba the indices into pairs (None: b was no
+        probe).  Changes nothing of the session; refused on the sharded path."""
+        from ._lib import CONTACT_STATES
+        pd, cd, sd, ud = _contact_dtypes()
+        ids = self.object_ids() if ids is None else [int(i) for i in ids]
+        n, bg = len(ids), 1 if background else 0
+        m = n + bg
+        n_pairs, n_sum = n * max(m - 1, 0), n * (n - 1) // 2 + (n if bg else 0)
+        arr = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1)) if ids else np.zeros(1, np.int32)
+        ids_out, sides = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), sd)
+        pair_ids, pairs, recs = np.zeros((max(n_pairs, 1), 2), np.int32), np.zeros(max(n_pairs, 1), pd), np.zeros(max(n_pairs, 1), cd)
+        sum_ids, sums = np.zeros((max(n_sum, 1), 4), np.int32), np.zeros(max(n_sum, 1), ud)
+        got_pairs, got_sums = C.c_int32(0), C.c_int32(0)
+        _check("emf_fusion_object_contacts",
+               load().emf_fusion_object_contacts(self._h, arr.ctypes.data, n, bg, -1.0 if touch is None else float(touch),
+                                                 ids_out.ctypes.data, sides.ctypes.data, pair_ids.ctypes.data, pairs.ctypes.data,
+                                                 recs.ctypes.data, sum_ids.ctypes.data, sums.ctypes.data, C.byref(got_pairs),
+                                                 C.byref(got_sums)))
+        assert got_pairs.value == n_pairs and got_sums.value == n_sum, (got_pairs.value, n_pairs, got_sums.value, n_sum)
+        out_pairs = []
+        for k in range(n_pairs):
+            r, p = recs[k], pairs[k]
+            d = dict(a=int(pair_ids[k, 0]), b=int(pair_ids[k, 1]), R=p["R"].reshape(3, 3).copy(), t=p["t"].copy(),
+                     touch=float(p["touch"]), min_s=float(r["min_s"]), sum=r["sum"].copy(), gsum=r["gsum"].copy(),
+                     lo=r["lo"].copy(), hi=r["hi"].copy(), record=r.copy(), pair=p.copy())
+            for key in ("surface", "outside", "unknown", "masked", "sampled", "inside", "touching", "normals"):
+                d[key] = int(r[key])
+            out_pairs.append(d)
+        out_sums = []
+        for k in range(n_sum):
+            u = sums[k]
+            direction = int(u["direction"])
+            out_sums.append(dict(a=int(sum_ids[k, 0]), b=int(sum_ids[k, 1]), record_ab=int(sum_ids[k, 2]),
+                                 record_ba=None if sum_ids[k, 3] < 0 else int(sum_ids[k, 3]),
+                                 state=CONTACT_STATES[int(u["state"])], distance_m=float(u["distance_m"]),
+                                 saturated=bool(u["saturated"]), direction=None if direction < 0 else direction,
+                                 point=None if direction < 0 else u["point"].copy(),
+                                 normal=u["normal"].copy() if u["has_normal"] else None,
+                                 corners=None if direction < 0 else u["corners"].reshape(8, 3).copy(), summary=u.copy()))
+        return dict(pairs=out_pairs, summaries=out_sums, ids=[int(v) for v in ids_out[:m]], sides=sides[:m].copy())
+
     def planes(self, box=None, size=None, k=15, angle=20.0, separation=None, bin=None, band=None, min_votes=None, refine=1,
                up_hint=None, floor_angle=30.0, kind_angle=10.0, max_planes=64, labels=False, patches=False, patch_reach=1,
                patch_min_voxels=None):
@@ -2251,7 +2372,8 @@ class Fusion:
                      exp_distance_nearest=False, exp_plan_shortcut=0, exp_object_shapes=False, exp_ground_map=False,
                      ground_up=None, ground_cell=None, ground_bin=None, ground_band=(-1.5, 0.5), ground_robot_height=0.3,
                      ground_max_step=0.05, exp_planes=False, planes_angle=20.0, planes_min_votes=None,
-                     exp_plane_patches=False, plane_patch_reach=1, plane_patch_min=None):
+                     exp_plane_patches=False, plane_patch_reach=1, plane_patch_min=None, exp_object_contacts=False,
+                     contact_touch=None):
         """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
         the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
         the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh();
@@ -2282,7 +2404,13 @@ class Fusion:
         planes(patches=True, patch_reach=plane_patch_reach, patch_min_voxels=plane_patch_min) of that plane: "patch" id
         count, then in %.9g the world point, the four corners and fill; and, with exp_object_shapes as well, after all
         planes one "support <object id> <plane> <patch id> <s>" line per object that rests on a patch
-        (include/emf_fusion.h emf_fusion_set_plane_patches_output)."""
+        (include/emf_fusion.h emf_fusion_set_plane_patches_output);
+        exp_object_contacts: write_results also writes contacts.txt, after a comment line one line per ordered pair of
+        object_contacts(touch=contact_touch) over the live objects in id order and the background with sampled > 0: the
+        ids, the eight counts, then in %.9g min_s and the world contact point and normal of that record
+        (include/emf_fusion.h emf_fusion_set_contacts_output)."""
+        if contact_touch is not None and not exp_object_contacts:
+            raise ValueError("setup_output: contact_touch is the threshold of contacts.txt and needs exp_object_contacts")
         if exp_plan_shortcut and not exp_plan:
             raise ValueError("setup_output: exp_plan_shortcut adds lines to plan.txt and needs exp_plan")
         if exp_distance_nearest and not exp_distance_field:
@@ -2320,6 +2448,9 @@ class Fusion:
             _check("emf_fusion_set_plane_patches_output",
                    load().emf_fusion_set_plane_patches_output(self._h, 1, int(plane_patch_reach),
                                                               0 if plane_patch_min is None else int(plane_patch_min)))
+        if exp_object_contacts:  # off: no new call
+            _check("emf_fusion_set_contacts_output",
+                   load().emf_fusion_set_contacts_output(self._h, 1, -1.0 if contact_touch is None else float(contact_touch)))
         if exp_ground_map:  # off: no new call
             up = None if ground_up is None or up_floor else np.ascontiguousarray(ground_up, np.float64).reshape(3)
             _check("emf_fusion_set_ground_output",

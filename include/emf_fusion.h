@@ -425,6 +425,38 @@ int emf_fusion_shape_frame(const emf_shape_moments_t* moments, emf_shape_frame_t
 int emf_fusion_shape_box(const emf_shape_moments_t* moments, const emf_shape_frame_t* frame, const emf_shape_extents_t* extents,
                          const int32_t res[3], float voxel_size, const float R[9], const float t[3], emf_shape_box_t* box);
 int emf_fusion_set_shape_output(emf_fusion_t* h, int on);
+/* Object contacts (include/emf_hip.h "Object contacts"; new behaviour, opt-in): whether the asked objects
+ * touch each other or the background, how far apart their surfaces are and whether they interpenetrate, read from the
+ * signed-distance volumes.  IT MEASURES WHAT THE VOLUMES SAY: min_s == 1 (summary.saturated) means "at least one
+ * truncation distance apart" and is no distance; a penetration deeper than the fused band reads UNKNOWN; a clearance
+ * reads up to one probe voxel large.
+ *   object_contacts ids: n live objects, each once: the probes.  The fields are those objects and, with
+ *                   include_background != 0, the background (id 0, in front); the background as a probe is not built.
+ *                   touch_m: the TOUCHING threshold in metres; < 0: one voxel of the probe (a policy, not a
+ *                   measurement).  With m = n + (include_background != 0) models the call makes n * (m - 1) ordered
+ *                   pairs, grouped by probe, and one summary per unordered pair: n * (n - 1) / 2 + n with the background,
+ *                   else n * (n - 1) / 2.  Outputs, NULL = not wanted: ids_out and sides_out (m: res, voxel size,
+ *                   truncation distance, pose world <- model as the call found it), pair_ids_out (2 per pair: the ids of
+ *                   probe and field), pairs_out (what each pair carried; a, b: slots of the call's table), records_out,
+ *                   summary_ids_out (4 per summary: the ids a, b, the index of the record a -> b, and of b -> a or -1),
+ *                   summaries_out, and the two counts.  One launch and one wait.  An id that does not exist or is named
+ *                   twice is EMF_E_ARG.  Changes nothing of the session.  EMF_E_ARG on the sharded path.
+ *   contact_pose / contact_touch / contact_summary   need no device and no handle: the host stage, float64 in the fixed
+ *                   operation order of include/emf_hip.h.  ba NULL: the field was no probe.
+ *   set_contacts_output  setup_output's exp_object_contacts, as an entry of its own: emf_fusion_write_results also writes
+ *                   contacts.txt, after a comment line one line per ordered pair with sampled > 0 (the live objects in
+ *                   id order against each other and the background): a b surface outside unknown masked sampled inside
+ *                   touching normals, the integers, then in %.9g min_s and the world contact point (3) and normal (3) of
+ *                   that record alone, zeros without.  Off: the set of result files and every byte of them as before. */
+int emf_fusion_object_contacts(emf_fusion_t* h, const int32_t* ids, int32_t n, int32_t include_background, double touch_m,
+                               int32_t* ids_out, emf_contact_side_t* sides_out, int32_t* pair_ids_out, emf_contact_pair_t* pairs_out,
+                               emf_contact_t* records_out, int32_t* summary_ids_out, emf_contact_summary_t* summaries_out,
+                               int32_t* n_pairs_out, int32_t* n_summaries_out);
+int emf_fusion_contact_pose(const float Ra[9], const float ta[3], const float Rb[9], const float tb[3], float R[9], float t[3]);
+int emf_fusion_contact_touch(double touch_m, float truncdist_b, float* touch);
+int emf_fusion_contact_summary(const emf_contact_t* ab, const emf_contact_t* ba, const emf_contact_side_t* a,
+                               const emf_contact_side_t* b, emf_contact_summary_t* summary);
+int emf_fusion_set_contacts_output(emf_fusion_t* h, int on, double touch_m);
 /* Planes (include/emf_hip.h "Planes"; new behaviour, opt-in): the dominant planes of a box of the
  * background (box_lo / box_size NULL: all of it) -- floor, walls, table tops.  A plane is the plane of the SHELL's voxel
  * centres: up to one voxel behind the surface, and nothing corrects that.

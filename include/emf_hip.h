@@ -2253,6 +2253,128 @@ int emf_hip_planePatches(const emf_plane_voxel_t* records, const int16_t* labels
                          uint32_t n_patches, void* scratch, emf_plane_patch_t* out, int32_t capacity_patches,
                          uint32_t* patch_counters, emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Object contacts (new behaviour: DESIGN.md 5.27).  Opt-in; nothing above is touched.  Whether two models touch, how
+ * far apart their surfaces are and whether they interpenetrate, read from their signed-distance volumes: a surface
+ * voxel of model a, taken through the relative pose into model b's volume and sampled there trilinearly, reads b's
+ * signed distance at a point of a's surface.
+ * IT MEASURES WHAT THE VOLUMES SAY:
+ *   - a tsdf is clamped to +-1, so min_s == 1 means "at least one truncation distance apart" and is not a distance;
+ *   - nothing is fused deeper than one truncation distance behind a surface, so a deeper penetration reads UNKNOWN,
+ *     not a larger depth;
+ *   - a surface voxel lies up to one voxel behind a's zero crossing, so clearances read up to one probe voxel large.
+ * An ordered PAIR is (probe a, field b): two different slots of a device model table, R[9], t[3] (f32, b's frame <-
+ * a's frame, row-major) and touch (f32, in units of b's stored tsdf, i.e. fractions of b's truncation distance).
+ * Volumes are dense, (z, y, x) order, x fastest, res = (nx, ny, nz); a voxel is v = (x, y, z).  Every float step below
+ * is a single float32 operation without contraction, in this order; everything else is integer.
+ *   solid(v), free(n)  exactly the rules of emf_hip_shapeMoments: solid(v) = weights[v] > 0 && (fgVolMask == NULL ||
+ *                fgVolMask[v] != 0) && !(tsdf[v] > 0) with a's mask; free(n) = weights[n] > 0 && tsdf[n] > 0, the mask
+ *                plays no part.  A neighbour outside the volume does not exist.
+ *   surface(v)   solid(v) and at least one of the face neighbours inside a's volume is free.
+ *   sample point of a surface voxel (the stamping arithmetic of emf_hip_occupancyStampObjects with the roles named;
+ *                half_j = float(N_j - 1) / 2.f; rows of R summed left to right):
+ *                    p_a_j = (float(v_j) - half_a_j) * voxelSize_a
+ *                    p_b_i = ((R_i0 * p_a_0 + R_i1 * p_a_1) + R_i2 * p_a_2) + t_i
+ *                    q_i   = p_b_i / voxelSize_b + half_b_i
+ *                    l_i = int(q_i),  f_i = q_i - float(l_i)
+ *   classes, first match wins:
+ *     OUTSIDE    some q_j is NaN, q_j < 0 or q_j + 1 >= float(N_j) of b: the pad-1 rule of the raycast's lookups.  All
+ *                eight corners l + {0, 1}^3 of every other cell lie inside b's volume.
+ *     UNKNOWN    one of the eight corners has !(weights_b > 0), or the blended value s is NaN
+ *     MASKED     b has an fgVolMask and it is 0 at the voxel (rint(q_0), rint(q_1), rint(q_2)), ties to even (inside
+ *                the volume by the rule above)
+ *     SAMPLED    everything else
+ *   s            b's tsdf blended over the cell in the reference's order: x pairs, then y, then z, each
+ *                (1 - f) * c0 + f * c1 as one difference, two products and one sum
+ *   INSIDE       SAMPLED and s < 0.   TOUCHING: SAMPLED and s <= touch (it contains INSIDE when touch >= 0; never with a
+ *                NaN touch).
+ *   normal of a touching voxel: all six face neighbours of v lie inside a's volume with weights > 0 and the three
+ *                g_j = tsdf[v + e_j] - tsdf[v - e_j] are finite; then gq_j = int(rintf(min(max(g_j * 4096.f, -8192.f),
+ *                8192.f))).  The clamp changes nothing for a tsdf within +-1 and bounds every sum for any other:
+ *                2^31 voxels of +-8192 stay below 2^53.
+ * emf_contact_t, per pair, integers except min_s:
+ *     surface = outside + unknown + masked + sampled;  inside, touching <= sampled;  normals <= touching
+ *     sum       the sums of x, y, z of the TOUCHING voxels in a's lattice;  gsum: of gq over those with a normal
+ *     lo, hi    bounds of the touching voxels; res_a and -1 without one
+ *     min_s     the minimum of s over SAMPLED, taken on the order-preserving u32 key of emf_hip_shapeExtents (-0 below
+ *               +0); +inf when sampled == 0
+ * Every field is a pure function of the inputs, bit for bit, whatever order lanes and workgroups run in.
+ * Limits: 1 <= n_models <= EMF_MAX_MODELS, 1 <= n_pairs <= EMF_CONTACT_MAX_PAIRS; of every slot a pair names, each
+ * axis in 1 .. EMF_DF_MAX_AXIS and at most 2^31 - 1 voxels; the probes of a call (each distinct probe once) together at
+ * most 2^24 - 1 tiles of 32 x 8 x 8 voxels.
+ *
+ * The host stage (include/emf_fusion.h emf_fusion_contact_pose / _touch / _summary; no device, no handle).  Float64,
+ * every line a single operation in this order, sums left to right, no contraction; f32 inputs are taken to double.
+ *   pose (what a pair carries), from the poses (world <- model) of a and b:
+ *       R_ij = float((Rb_0i * Ra_0j + Rb_1i * Ra_1j) + Rb_2i * Ra_2j)
+ *       d_k  = ta_k - tb_k;   t_i = float((Rb_0i * d_0 + Rb_1i * d_1) + Rb_2i * d_2)
+ *   touch:  float(touch_m / double(truncdist_b)), touch_m a double in metres
+ *   summary of the unordered pair {a, b} from the record a -> b and, where b was a probe as well, b -> a:
+ *       state, first match wins: PENETRATING some inside > 0, TOUCHING some touching > 0, APART some sampled > 0, else
+ *             UNSEEN
+ *       d_ab = double(min_s_ab) * double(truncdist_b),  d_ba = double(min_s_ba) * double(truncdist_a)
+ *       distance_m = d_ba < d_ab ? d_ba : d_ab (d_ab alone without a second record); saturated: the deciding min_s == 1
+ *       direction: the record with more touching voxels, ties to a -> b; -1 when neither has one (point, normal and
+ *             corners are zeros then).  With p its probe (res, voxelSize, pose R, t):
+ *           m_j = double(sum_j) / double(touching);  h_j = (double(res_j) - 1) / 2;  o_j = (m_j - h_j) * double(voxelSize)
+ *           point_i = ((R_i0 * o_0 + R_i1 * o_1) + R_i2 * o_2) + t_i
+ *           normal: len = sqrt((g_0 * g_0 + g_1 * g_1) + g_2 * g_2) with g = double(gsum); has_normal = normals > 0 &&
+ *                 len > 0; u_j = g_j / len; normal_i = (R_i0 * u_0 + R_i1 * u_1) + R_i2 * u_2: out of the probe
+ *           corner c (bit j of c set: hi_j, clear: lo_j) goes the way of m_j: the box of the contact region in the world
+ * ---------------------------------------------------------------------------------------------- */
+#define EMF_CONTACT_MAX_PAIRS 65535
+#define EMF_CONTACT_UNSEEN 0
+#define EMF_CONTACT_APART 1
+#define EMF_CONTACT_TOUCHING 2
+#define EMF_CONTACT_PENETRATING 3
+
+typedef struct emf_contact_pair {
+    int32_t a, b;     /* probe and field: slots of the model table */
+    float R[9], t[3]; /* b's frame <- a's frame, row-major */
+    float touch;      /* in units of b's stored tsdf */
+    int32_t reserved;
+} emf_contact_pair_t; /* 64 bytes */
+
+typedef struct emf_contact {
+    uint64_t surface, outside, unknown, masked, sampled, inside, touching, normals; /* counts */
+    uint64_t sum[3];        /* sums of x, y, z of the touching voxels */
+    int64_t gsum[3];        /* sums of gq over the touching voxels with a normal */
+    int32_t lo[3], hi[3];   /* bounds of the touching voxels; res_a and -1 without one */
+    float min_s;            /* minimum of s over SAMPLED; +inf without one */
+    int32_t reserved;       /* 0 */
+} emf_contact_t;            /* 144 bytes */
+
+typedef struct emf_contact_side {
+    int32_t res[3];
+    float voxelSize, truncdist;
+    float R[9], t[3]; /* world <- model */
+} emf_contact_side_t; /* 68 bytes */
+
+typedef struct emf_contact_summary {
+    int32_t state;      /* EMF_CONTACT_* */
+    int32_t saturated;  /* the deciding min_s == 1: at least one truncation distance apart, not a distance */
+    int32_t direction;  /* 0: a -> b, 1: b -> a, -1: no touching voxel */
+    int32_t has_normal;
+    double distance_m;  /* +inf when nothing was sampled */
+    double point[3], normal[3], corners[24]; /* world; zeros without a touching voxel (the normal: without has_normal) */
+} emf_contact_summary_t; /* 264 bytes */
+
+/* models_dev: the device table, n_models slots; res_host: HOST int32[3 n_models], the resolutions as the table stores
+ * them (only the slots a pair names are looked at).  Of a model tsdf, weights, fgVolMask (NULL: no gate), res,
+ * voxelSize and, of a probe, unseenTiles are read; nothing of a model is written.  pairs_dev / pairs_host: the same
+ * n_pairs pairs in device and in host memory; the host copy serves the argument checks and the launch geometry only
+ * and is read before the call returns.  The kernel walks, per probe, the pairs between the first and the last that
+ * name it: a list grouped by probe is the fast one, any order gives the same bytes.
+ * records_dev: n_pairs records (record k: pair k), initialised by a launch of the call's own on the stream; a second
+ * call into the same buffers gives the same bytes.  One workgroup per 32 x 8 x 8 tile of a probe; a tile the probe's
+ * unseenTiles map marks holds no surface voxel and is skipped.  One integer atomic per non-zero quantity and wave.
+ * Every rejected argument -- a NULL pointer, n_pairs <= 0, a slot outside the table, a == b, an axis outside
+ * 1 .. EMF_DF_MAX_AXIS, more than 2^24 - 1 probe tiles -- returns EMF_E_ARG or EMF_E_LIMIT with nothing enqueued.
+ * Nothing allocates, copies to the host or waits. */
+int emf_hip_contactProbe(const emf_model_t* models_dev, const int32_t* res_host, int32_t n_models,
+                         const emf_contact_pair_t* pairs_dev, const emf_contact_pair_t* pairs_host, int32_t n_pairs,
+                         emf_contact_t* records_dev, emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
