@@ -180,6 +180,9 @@ static emf::BackgroundFollowParams followParams;
 static bool followStore = false;
 static long followStoreMib = 1024;
 static bool followStoreMibGiven = false;
+// --world-queries: the scene queries of writeResults cover the background AND the stored tiles
+// (EMFusion::setQueryExtent).  Needs --follow-camera --follow-store.
+static bool worldQueries = false;
 static unsigned meshMinTriangles = 0;    // --mesh-min-triangles
 static bool meshLargestObject = false;   // --mesh-largest-object
 static float meshSimplifyCell = 0.f;     // --mesh-simplify
@@ -261,6 +264,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     if (motionMasks) emf.setMotionMasks(true, motionParams);  // (not stored in a checkpoint: set again on --resume)
     if (followCamera) emf.setBackgroundFollow(true, followParams);
     if (followStore) emf.setBackgroundStore(true, static_cast<uint64_t>(followStoreMib) << 20);
+    if (worldQueries) emf.setQueryExtent(true);
     std::vector<uint8_t> rgb;
     if (!masks.empty()) emf.usePreprocMasks(masks);   // apps/EM-Fusion.cpp:115
     emf.setupOutput(frameMeshes, volumes);            // apps/EM-Fusion.cpp:112
@@ -357,6 +361,7 @@ int main(int argc, char** argv) {
             followParams.step = emf::Vec3i(x, y, z);
         }
         else if (a == "--follow-store") followStore = true;
+        else if (a == "--world-queries") worldQueries = true;
         else if (a == "--follow-store-mib" && i + 1 < argc) {
             followStoreMib = std::atol(argv[++i]);
             followStoreMibGiven = true;
@@ -435,6 +440,10 @@ int main(int argc, char** argv) {
     if ((followStore && !followCamera) || (followStoreMibGiven && !followStore) || followStoreMib < 1) {  // (before any device is touched)
         std::fprintf(stderr, "usage: emfusion_synth: --follow-store needs --follow-camera, and --follow-store-mib N (>= 1) needs "
                              "--follow-store\n");
+        return 2;
+    }
+    if (worldQueries && !(followCamera && followStore)) {  // (before any device is touched)
+        std::fprintf(stderr, "usage: emfusion_synth: --world-queries needs --follow-camera --follow-store\n");
         return 2;
     }
     if (distanceNearest && !distanceOut) {  // (before any device is touched)
@@ -545,6 +554,7 @@ int main(int argc, char** argv) {
         if (motionMasks) emf.setMotionMasks(true, motionParams);
         if (followCamera) emf.setBackgroundFollow(true, followParams);
         if (followStore) emf.setBackgroundStore(true, static_cast<uint64_t>(followStoreMib) << 20);
+        if (worldQueries) emf.setQueryExtent(true);
         if (!outDir.empty()) emf.setupOutput(frameMeshes, true);  // apps/EM-Fusion.cpp:112
         emf.setWorldMeshOutput(worldMeshOut);
         emf.setDistanceOutput(distanceOut, distanceCap, distanceUnknownObstacle);

@@ -49,6 +49,9 @@ def main():
     ap.add_argument("--follow-store", dest="follow_store", action="store_true",
                     help="remember what rolls out of the background and put it back when the camera returns "
                          "(Fusion.set_background_store; needs --follow-camera)")
+    ap.add_argument("--world-queries", dest="world_queries", action="store_true",
+                    help="the scene queries and their result files cover the background and the stored tiles "
+                         "(Fusion.set_query_extent(\"world\"); needs --follow-camera --follow-store)")
     ap.add_argument("--follow-store-mib", dest="follow_store_mib", type=int, default=1024, metavar="N",
                     help="the store's budget in MiB (default 1024: a cap, not a measurement); past it the oldest spills are dropped")
     ap.add_argument("--out", default=None, help="results directory (default emfusion_out)")
@@ -184,6 +187,8 @@ def main():
         ap.error("--follow-step takes three integers X,Y,Z")
     if args.follow_store and not args.follow_camera:
         ap.error("--follow-store needs --follow-camera")
+    if args.world_queries and not (args.follow_camera and args.follow_store):
+        ap.error("--world-queries needs --follow-camera --follow-store")
     if args.follow_store_mib != 1024 and not args.follow_store:
         ap.error("--follow-store-mib needs --follow-store")
     if args.follow_store_mib < 1:
@@ -237,6 +242,8 @@ def main():
         fus.set_background_follow(True, step=follow_step, look_ahead=args.follow_lookahead)
     if args.follow_store:
         fus.set_background_store(True, max_bytes=args.follow_store_mib << 20)
+    if args.world_queries:
+        fus.set_query_extent("world")
     fus.set_ignore_person(args.ignore_person)
     fus.set_preprocess(True)
     fus.set_cleanup(True)

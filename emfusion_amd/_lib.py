@@ -205,6 +205,7 @@ SIGNATURES = {
     "emf_hip_meshTilesEdgeKeys": [_FP, C.c_uint32, C.c_void_p, _FP, _FP, _STREAM],
     "emf_hip_occupancyClasses": [_FP, _FP, _I3, _I3, _I3, _FP, _STREAM],
     "emf_hip_occupancyObjectBox": [C.c_void_p, _I3, C.c_float],
+    "emf_hip_occupancyTiles": [_FP, C.c_void_p, C.c_uint32, C.c_void_p, _I3, _I3, _FP, _STREAM],
     "emf_hip_occupancyStampObjects": [_FP, _I3, C.c_float, _I3, _I3, C.c_void_p, C.c_int32, _STREAM],
     "emf_hip_distanceTransform": [_FP, _I3, C.c_uint32, C.c_int32, _FP, _FP, C.c_float, _STREAM],
     "emf_hip_nearestSiteScratchBytes": [_I3],

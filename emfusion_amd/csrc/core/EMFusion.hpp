@@ -352,6 +352,22 @@ public:
     /** writeResults also writes world.ply = writeMesh(worldMesh()); without it no output byte changes. */
     void setWorldMeshOutput(bool on) { expWorldMesh_ = on; }
     const WorldMeshInfo& worldMeshInfo() const { return worldInfo; }
+    /**
+     * The extent of the scene queries (new behaviour, off by default; with it off no launch, no output
+     * byte and no refusal changes).  World: the box of distanceField(), frontiers(), plan(), castRays(), viewGain()
+     * and groundMap() may leave the background -- it stays in voxels of the CURRENT background volume, so lo may be
+     * negative and lo + size may exceed the resolution -- and its classes come from the tiles worldMesh() reads: the
+     * observed tiles of the volume in place and every tile the background store holds (emf_hip_occupancyTiles);
+     * what lies in no tile is unknown.  The limits of a box stay; refused (EMF_E_ARG) on the sharded path and when the
+     * background's resolution or origin is not a multiple of the tile, with the session untouched.  planes() reads
+     * tsdf values and keeps refusing a box that leaves the background.  Sticky; never in a checkpoint.
+     */
+    void setQueryExtent(bool world) { queryWorld_ = world; }
+    bool queryExtentWorld() const { return queryWorld_; }
+    /** The bounding box, in voxels of the current background volume, of the background and every tile the store
+     *  holds: the whole background when nothing is stored.  With the extent on, writeResults uses it wherever
+     *  distance.bin, nearest.bin, frontiers.txt, plan.txt and ground.bin / ground.txt take the whole background. */
+    void worldExtent(Vec3i& lo, Vec3i& size) const;
     /** What the last distanceField() computed; the device arrays stay valid until the next one. */
     struct DistanceField {
         QueryBox box;
@@ -1011,6 +1027,26 @@ private:
     // ---- the tile store (setBackgroundStore; EMFusionFollow.cpp) ----
     bool storeOn = false;
     WorldMeshInfo worldInfo;  // of the last worldMesh()
+    // the tiles a session's map consists of: the table worldMesh() and the world queries read
+    struct WorldTiles {
+        std::vector<emf_mesh_tile_t> tiles;                      // sorted by (z, y, x), neighbours filled in
+        std::map<std::array<int32_t, 3>, int32_t> index;         // key (z, y, x) -> table index
+        std::vector<std::array<int32_t, 3>> storedKeys;          // the keys that came from the store
+        TileGather stored;                                       // owns the arena
+        emf_mesh_tiles_source_t src{};
+        WorldMeshInfo info;
+        DeviceBuffer tilesDev;
+    };
+    // refuses for EMFusion::`who` what worldMesh() refuses: the sharded path, a resolution or origin off the tile
+    void requireTiledWorld(const char* who, const char* noun) const;
+    // after a drain: an unseen-tile map of its own from the front copy, the observed tiles of the volume in place, the
+    // stored tiles under their lattice coordinate -- the volume wins --, uploaded.  Waits for the main stream.
+    WorldTiles listWorldTiles(const char* who);
+    // ---- the world extent of the scene queries (setQueryExtent; EMFusionDistance.cpp) ----
+    bool queryWorld_ = false;
+    WorldTiles queryTiles;  // of the last world query: alive while its kernels may run
+    // the box of writeResults' whole-scene outputs: the background, or worldExtent() with the switch on
+    void resultsBox(const char* who, Vec3i& lo, Vec3i& size) const;
     // ---- the distance field (distanceField; EMFusionDistance.cpp): allocated at first use, never in a checkpoint ----
     DistanceField dfLast;
     DeviceBuffer dfClasses, dfD2, dfMetres, dfNearest, dfNearestScratch, dfQuery;
@@ -1021,7 +1057,8 @@ private:
     // refusal on the sharded path reads "`noun` not supported ..." --, the drain, classes + stamped objects into
     // `classes`, and the clearance of frontiers() and plan()
     QueryBox queryBoxAt(const Vec3i& lo, const Vec3i& size) const;
-    QueryBox makeQueryBox(const char* who, const char* noun, const Vec3i& lo, const Vec3i& size) const;
+    // volumeOnly: a query that reads the volume itself (planes) keeps to the background whatever the extent
+    QueryBox makeQueryBox(const char* who, const char* noun, const Vec3i& lo, const Vec3i& size, bool volumeOnly = false) const;
     void drainForQuery();
     void enqueueOccupancy(const char* who, const QueryBox& box, const std::vector<int>& excludeIds, uint8_t* classes,
                           std::vector<int>* ids, std::vector<Affine3f>* poses);

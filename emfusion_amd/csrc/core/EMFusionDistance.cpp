@@ -14,34 +14,65 @@ namespace emf {
 
 QueryBox EMFusion::queryBoxAt(const Vec3i& lo, const Vec3i& size) const {
     QueryBox box;
-    box.lo = lo;
     box.size = size;
-    box.bgRes = background.getVolumeRes();
     box.bgPose = background.getPose();
     box.voxelSize = background.getVoxelSize();
+    // a box that leaves the background (the world extent) is one of a virtual background, padded by as
+    // many voxels on both sides of an axis as the box leaves it on either: every expression below gives the same bits
+    const Vec3i res = background.getVolumeRes();
+    box.pad = queryBoxPad(lo, size, res);
+    for (int i = 0; i < 3; ++i) {
+        box.lo[i] = lo[i] + box.pad[i];
+        box.bgRes[i] = res[i] + 2 * box.pad[i];
+    }
     const Vec3i n = box.bgRes;
     const float voxel = box.voxelSize;
-    const Vec3f corner((static_cast<float>(lo[0]) - static_cast<float>(n[0] - 1) / 2.f) * voxel,
-                       (static_cast<float>(lo[1]) - static_cast<float>(n[1] - 1) / 2.f) * voxel,
-                       (static_cast<float>(lo[2]) - static_cast<float>(n[2] - 1) / 2.f) * voxel);
+    const Vec3i at = box.lo;
+    const Vec3f corner((static_cast<float>(at[0]) - static_cast<float>(n[0] - 1) / 2.f) * voxel,
+                       (static_cast<float>(at[1]) - static_cast<float>(n[1] - 1) / 2.f) * voxel,
+                       (static_cast<float>(at[2]) - static_cast<float>(n[2] - 1) / 2.f) * voxel);
     box.boxPose = Affine3f(box.bgPose.rotation(), box.bgPose.rotation() * corner + box.bgPose.translation());
     return box;
 }
 
-QueryBox EMFusion::makeQueryBox(const char* who, const char* noun, const Vec3i& lo, const Vec3i& size) const {
+QueryBox EMFusion::makeQueryBox(const char* who, const char* noun, const Vec3i& lo, const Vec3i& size, bool volumeOnly) const {
     const std::string name = std::string("EMFusion::") + who;
-    if (sharded || world > 1) throw HipError(name + ": " + noun + " not supported on the sharded path", EMF_E_ARG);
+    const bool worldBox = queryWorld_ && !volumeOnly;
+    if (worldBox)
+        requireTiledWorld(who, noun);
+    else if (sharded || world > 1)
+        throw HipError(name + ": " + noun + " not supported on the sharded path", EMF_E_ARG);
     const Vec3i n = background.getVolumeRes();
+    constexpr long long kLattice = 1ll << 19;  // lattice voxels in [-2^19, 2^19), as the tiles of emf_hip_meshTiles*
     unsigned long long voxels = 1;
     for (int i = 0; i < 3; ++i) {
-        if (size[i] < 1 || lo[i] < 0 || lo[i] > n[i] - size[i])
+        if (size[i] < 1 || (!worldBox && (lo[i] < 0 || lo[i] > n[i] - size[i])))
             throw HipError(name + ": the box leaves the background on axis " + std::to_string(i), EMF_E_ARG);
         if (size[i] > EMF_DF_MAX_AXIS)
             throw HipError(name + ": a box axis of " + std::to_string(size[i]) + " voxels", EMF_E_LIMIT);
+        const long long first = static_cast<long long>(lo[i]) + bgOrigin[i];
+        if (worldBox && (first < -kLattice || first + size[i] > kLattice))
+            throw HipError(name + ": the box leaves the lattice on axis " + std::to_string(i), EMF_E_LIMIT);
         voxels *= static_cast<unsigned long long>(size[i]);
     }
     if (voxels > 0x7fffffffull) throw HipError(name + ": a box of more than 2^31 - 1 voxels", EMF_E_LIMIT);
     return queryBoxAt(lo, size);
+}
+
+void EMFusion::resultsBox(const char* who, Vec3i& lo, Vec3i& size) const {
+    lo = Vec3i(0, 0, 0);
+    size = background.getVolumeRes();
+    if (!queryWorld_) return;
+    worldExtent(lo, size);
+    for (int i = 0; i < 3; ++i)
+        if (size[i] > EMF_DF_MAX_AXIS)
+            throw HipError(std::string("EMFusion::") + who + ": the world extent has " + std::to_string(size[i]) + " voxels on axis " +
+                               std::to_string(i) + ", above " + std::to_string(EMF_DF_MAX_AXIS),
+                           EMF_E_LIMIT);
+    if (static_cast<unsigned long long>(size[0]) * size[1] * static_cast<unsigned long long>(size[2]) > 0x7fffffffull)
+        throw HipError(std::string("EMFusion::") + who + ": the world extent has more than 2^31 - 1 voxels (axes " +
+                           std::to_string(size[0]) + ", " + std::to_string(size[1]) + ", " + std::to_string(size[2]) + ")",
+                       EMF_E_LIMIT);
 }
 
 // as worldMesh: nothing of this instance in flight, the front copies current
@@ -59,9 +90,19 @@ void EMFusion::enqueueOccupancy(const char* who, const QueryBox& box, const std:
     const Vec3i n = box.bgRes, boxLo = box.lo, boxSize = box.size;
     const float voxel = box.voxelSize;
     const Affine3f bgPose = box.bgPose;
-    emfCheck(emf_hip_occupancyClasses(background.tsdfPtr(), background.weightsPtr(), n.val, boxLo.val, boxSize.val, classes,
-                                      main.abi()),
-             (name + " (classes)").c_str());
+    if (queryWorld_) {  // the tiles of the session's map instead of the dense volume, on the lattice
+        queryTiles = listWorldTiles(who);
+        const Vec3i at = box.volumeLo();
+        const int32_t latticeLo[3] = {at[0] + bgOrigin[0], at[1] + bgOrigin[1], at[2] + bgOrigin[2]};
+        const uint32_t count = static_cast<uint32_t>(queryTiles.tiles.size());
+        emfCheck(emf_hip_occupancyTiles(count ? queryTiles.tilesDev.as<emf_mesh_tile_t>() : nullptr, queryTiles.tiles.data(), count,
+                                        &queryTiles.src, latticeLo, boxSize.val, classes, main.abi()),
+                 (name + " (tile classes)").c_str());
+    } else {
+        emfCheck(emf_hip_occupancyClasses(background.tsdfPtr(), background.weightsPtr(), n.val, boxLo.val, boxSize.val, classes,
+                                          main.abi()),
+                 (name + " (classes)").c_str());
+    }
     std::vector<emf_occ_object_t> table;
     for (const ObjTSDF& obj : objects) {
         if (std::find(excludeIds.begin(), excludeIds.end(), obj.getID()) != excludeIds.end()) continue;
@@ -166,11 +207,12 @@ void EMFusion::queryDistance(const int32_t* voxels, int n, uint8_t* outClass, in
 // distance.bin and occupancy.bin of the whole background (setDistanceOutput), in the container of the tsdfs/ dumps;
 // with setDistanceNearestOutput also nearest.bin
 void EMFusion::writeDistanceField(const std::string& dir) {
-    const Vec3i n = background.getVolumeRes();
+    Vec3i lo, n;  // the whole background; the world extent with setQueryExtent(true)
+    resultsBox("writeDistanceField", lo, n);
     const float voxel = background.getVoxelSize();
     const int cap = metresToVoxels(distanceCapMetres_, voxel);
     const uint32_t sites = (1u << EMF_OCC_OCCUPIED) | (distanceUnknownObstacle_ ? 1u << EMF_OCC_UNKNOWN : 0u);
-    const DistanceField& df = distanceField(Vec3i(0, 0, 0), n, sites, cap, {}, true, expDistanceNearest_);
+    const DistanceField& df = distanceField(lo, n, sites, cap, {}, true, expDistanceNearest_);
     const size_t voxels = static_cast<size_t>(n[0]) * n[1] * n[2];
     std::vector<float> metres(voxels);
     std::vector<uint8_t> classes(voxels);

@@ -143,37 +143,41 @@ void EMFusion::rollBackgroundAt(const Vec3i& shift, int frame, bool keepRetired)
     bgRolled = true;
 }
 
-Mesh EMFusion::worldMesh(int weld) {
-    if (sharded || world > 1)
-        throw HipError("EMFusion::worldMesh: the world mesh is not supported on the sharded path", EMF_E_ARG);
+void EMFusion::requireTiledWorld(const char* who, const char* noun) const {
+    const std::string name = std::string("EMFusion::") + who;
+    if (sharded || world > 1) throw HipError(name + ": " + noun + " not supported on the sharded path", EMF_E_ARG);
     const Vec3i n = background.getVolumeRes();
     const int32_t none[3] = {0, 0, 0};
     if (!emf_hip_rollVolumeIsTiled(n.val, none) || !emf_hip_rollVolumeIsTiled(n.val, bgOrigin.val))
-        throw HipError("EMFusion::worldMesh: the background resolution and the background origin must be multiples of the "
-                       "tile (32, 8, 8)",
+        throw HipError(name + ": the background resolution and the background origin must be multiples of the "
+                              "tile (32, 8, 8)",
                        EMF_E_ARG);
-    // as rollBackgroundAt: nothing of this instance in flight, the front copy current
-    quiesce();
-    refreshVisibleFromDevice();
-    if (bgInFlight) joinBackground();
-    quiesce();
-    const bool filtering = meshFilterActive() || meshSimplifyActive();  // (finishMesh does what the filter it gets asks)
-    const bool welded = filtering || (weld < 0 ? meshWeld : weld > 0);
+}
+
+void EMFusion::worldExtent(Vec3i& lo, Vec3i& size) const {
+    std::vector<TileKey> keys;
+    if (storeOn)
+        for (const auto& held : bgStore.inOrder()) keys.push_back(held.first);
+    tilesExtent(keys, kTile, bgOrigin, background.getVolumeRes(), lo, size);
+}
+
+EMFusion::WorldTiles EMFusion::listWorldTiles(const char* who) {
+    const std::string name = std::string("EMFusion::") + who;
+    WorldTiles out;
+    const Vec3i n = background.getVolumeRes();
     const int nt[3] = {n[0] / kTile[0], n[1] / kTile[1], n[2] / kTile[2]};
-    const size_t volTiles = static_cast<size_t>(nt[0]) * nt[1] * nt[2];
     // an unseen-tile map of its own, from the front copy: the session's maps, valid or stale, are not touched
     DeviceBuffer unseenDev((emf_hip_unseenTileBytes(n.val) + 3) / 4 * 4);
     emfCheck(emf_hip_rebuildUnseenTiles(background.tsdfPtr(), background.weightsPtr(), n.val, unseenDev.as<uint8_t>(), main.abi()),
-             "EMFusion::worldMesh (unseen tiles)");
+             (name + " (unseen tiles)").c_str());
     std::vector<uint8_t> unseen(unseenDev.bytes());
     unseenDev.download(unseen.data(), main);
-    TileGather stored;
+    TileGather& stored = out.stored;
     if (storeOn && !bgStore.empty()) stored = bgStore.gather(main);
 
     // the table, sorted by (z, y, x) of the lattice tile coordinate
     const uint16_t* color = background.colorPtr();
     std::map<std::array<int32_t, 3>, emf_mesh_tile_t> table;  // key (z, y, x)
-    worldInfo = WorldMeshInfo{};
     const int32_t first[3] = {bgOrigin[0] / kTile[0], bgOrigin[1] / kTile[1], bgOrigin[2] / kTile[2]};
     for (int z = 0; z < nt[2]; ++z)
         for (int y = 0; y < nt[1]; ++y)
@@ -190,14 +194,13 @@ Mesh EMFusion::worldMesh(int weld) {
                 e.at[0] = e.at[1] = at;
                 e.at[2] = color ? at : 0;
                 table[{e.coord[2], e.coord[1], e.coord[0]}] = e;
-                ++worldInfo.volumeTiles;
+                ++out.info.volumeTiles;
             }
-    std::vector<std::array<int32_t, 3>> storedKeys;
     for (size_t i = 0; i < stored.keys.size(); ++i) {
         const TileKey& k = stored.keys[i];
         const std::array<int32_t, 3> key{k[2], k[1], k[0]};
         if (table.count(key)) {  // should not happen: a returned tile is taken out of the store
-            ++worldInfo.duplicateTiles;
+            ++out.info.duplicateTiles;
             continue;
         }
         emf_mesh_tile_t e{};
@@ -208,28 +211,21 @@ Mesh EMFusion::worldMesh(int weld) {
         }
         for (int a = 0; a < 4; ++a) e.words[a] = stored.words[4 * i + a];
         table[key] = e;
-        storedKeys.push_back(key);
-        ++worldInfo.storedTiles;
+        out.storedKeys.push_back(key);
+        ++out.info.storedTiles;
     }
-    (void)volTiles;
-    std::vector<emf_mesh_tile_t> tiles;
-    std::map<std::array<int32_t, 3>, int32_t> index;
+    std::vector<emf_mesh_tile_t>& tiles = out.tiles;
     tiles.reserve(table.size());
     for (const auto& [key, e] : table) {
-        index[key] = static_cast<int32_t>(tiles.size());
+        out.index[key] = static_cast<int32_t>(tiles.size());
         tiles.push_back(e);
     }
     for (emf_mesh_tile_t& e : tiles)
         for (int k = 1; k < 8; ++k) {
-            const auto it = index.find({e.coord[2] + ((k >> 2) & 1), e.coord[1] + ((k >> 1) & 1), e.coord[0] + (k & 1)});
-            e.nbr[k - 1] = it == index.end() ? -1 : it->second;
+            const auto it = out.index.find({e.coord[2] + ((k >> 2) & 1), e.coord[1] + ((k >> 1) & 1), e.coord[0] + (k & 1)});
+            e.nbr[k - 1] = it == out.index.end() ? -1 : it->second;
         }
-
-    Mesh mesh;
-    mesh.colored = color != nullptr;
-    const uint32_t count = static_cast<uint32_t>(tiles.size());
-    if (count == 0) return mesh;
-    emf_mesh_tiles_source_t src{};
+    emf_mesh_tiles_source_t& src = out.src;
     src.arena = stored.arena.empty() ? nullptr : stored.arena.data();
     src.arena_units = stored.arenaUnits;
     src.tsdf = background.tsdfPtr();
@@ -238,10 +234,39 @@ Mesh EMFusion::worldMesh(int weld) {
     src.volume_elements = static_cast<uint64_t>(n[0]) * n[1] * n[2];
     src.row_stride = n[0];
     src.plane_stride = static_cast<uint64_t>(n[0]) * n[1];
+    if (!tiles.empty()) {
+        out.tilesDev = DeviceBuffer(tiles.size() * sizeof(emf_mesh_tile_t));
+        out.tilesDev.upload(tiles.data(), main);
+    }
+    return out;
+}
+
+Mesh EMFusion::worldMesh(int weld) {
+    requireTiledWorld("worldMesh", "the world mesh is");
+    const Vec3i n = background.getVolumeRes();
+    // as rollBackgroundAt: nothing of this instance in flight, the front copy current
+    quiesce();
+    refreshVisibleFromDevice();
+    if (bgInFlight) joinBackground();
+    quiesce();
+    const bool filtering = meshFilterActive() || meshSimplifyActive();  // (finishMesh does what the filter it gets asks)
+    const bool welded = filtering || (weld < 0 ? meshWeld : weld > 0);
+    WorldTiles listing = listWorldTiles("worldMesh");
+    worldInfo = listing.info;
+    const std::vector<emf_mesh_tile_t>& tiles = listing.tiles;
+    std::map<std::array<int32_t, 3>, int32_t>& index = listing.index;
+    const std::vector<std::array<int32_t, 3>>& storedKeys = listing.storedKeys;
+    const emf_mesh_tiles_source_t& src = listing.src;
+    const DeviceBuffer& tilesDev = listing.tilesDev;
+    const uint16_t* color = background.colorPtr();
+
+    Mesh mesh;
+    mesh.colored = color != nullptr;
+    const uint32_t count = static_cast<uint32_t>(tiles.size());
+    if (count == 0) return mesh;
     const size_t scratchBytes = emf_hip_meshTilesScratchBytes(count);
     if (scratchBytes == 0) throw HipError("EMFusion::worldMesh: " + std::to_string(count) + " tiles", EMF_E_LIMIT);
-    DeviceBuffer tilesDev(tiles.size() * sizeof(emf_mesh_tile_t)), scratch(scratchBytes), countsDev(sizeof(emf_mesh_counts_t));
-    tilesDev.upload(tiles.data(), main);
+    DeviceBuffer scratch(scratchBytes), countsDev(sizeof(emf_mesh_counts_t));
     emfCheck(emf_hip_meshTilesCount(tilesDev.as<emf_mesh_tile_t>(), tiles.data(), count, &src, scratch.data(),
                                     countsDev.as<emf_mesh_counts_t>(), main.abi()),
              "EMFusion::worldMesh (count)");

@@ -70,20 +70,25 @@ void EMFusion::frontierWorldPoint(const Frontiers& f, const emf_frontier_cluster
     f.box.worldPoint(v, out);
 }
 
-// frontiers.txt of the whole background (setFrontierOutput).  After a comment line, one line per kept cluster, largest
+// frontiers.txt of the whole background, or of the world extent after a second comment line that states it
+// (setFrontierOutput).  After a comment line, one line per kept cluster, largest
 // first (ties: smallest label):
 //     count  rx ry rz  cx cy cz  x0 y0 z0 x1 y1 z1
 // count: voxels, %d; r: the representative voxel and c: the centroid in the world frame, metres, each the double value
 // rounded once to float and printed %.9g; the inclusive bounding box in voxels of the background, %d.
 void EMFusion::writeFrontiers(const std::string& dir) {
-    const Vec3i n = background.getVolumeRes();
+    Vec3i lo, n;  // the whole background; the world extent with setQueryExtent(true)
+    resultsBox("writeFrontiers", lo, n);
     const float voxel = background.getVoxelSize();
     const int clearance = metresToVoxels(frontierClearanceMetres_, voxel);
-    const Frontiers& f = frontiers(Vec3i(0, 0, 0), n, std::max(frontierMinVoxels_, 1), clearance, {});
+    const Frontiers& f = frontiers(lo, n, std::max(frontierMinVoxels_, 1), clearance, {});
     const std::string path = dir + "/frontiers.txt";
     std::FILE* file = std::fopen(path.c_str(), "w");
     if (!file) throw std::runtime_error("EMFusion::writeFrontiers: cannot create " + path);
     std::fprintf(file, "# count rep_x rep_y rep_z centroid_x centroid_y centroid_z lo_x lo_y lo_z hi_x hi_y hi_z\n");
+    if (queryWorld_)  // a second comment line: the box, in voxels of the current background
+        std::fprintf(file, "# world extent: lo %d %d %d size %d %d %d\n", lo[0], lo[1], lo[2], n[0], n[1], n[2]);
+    const Vec3i at = f.box.volumeLo();
     for (const emf_frontier_cluster_t& c : f.clusters) {
         double r[3], m[3];
         frontierWorldPoint(f, c, true, r);
@@ -92,8 +97,7 @@ void EMFusion::writeFrontiers(const std::string& dir) {
                      static_cast<double>(static_cast<float>(r[0])), static_cast<double>(static_cast<float>(r[1])),
                      static_cast<double>(static_cast<float>(r[2])), static_cast<double>(static_cast<float>(m[0])),
                      static_cast<double>(static_cast<float>(m[1])), static_cast<double>(static_cast<float>(m[2])),
-                     f.box.lo[0] + c.lo[0], f.box.lo[1] + c.lo[1], f.box.lo[2] + c.lo[2], f.box.lo[0] + c.hi[0],
-                     f.box.lo[1] + c.hi[1], f.box.lo[2] + c.hi[2]);
+                     at[0] + c.lo[0], at[1] + c.lo[1], at[2] + c.lo[2], at[0] + c.hi[0], at[1] + c.hi[1], at[2] + c.hi[2]);
     }
     std::fclose(file);
 }

@@ -197,6 +197,8 @@ const EMFusion::GroundMap& EMFusion::groundMap(const Vec3i& boxLo, const Vec3i& 
 void EMFusion::writeGround(const std::string& dir) {
     const GroundOutput& o = expGround_;
     const Vec3i n = background.getVolumeRes();
+    Vec3i boxLo, boxSize;  // the whole background; the world extent with setQueryExtent(true)
+    resultsBox("writeGround", boxLo, boxSize);
     const double voxel = static_cast<double>(background.getVoxelSize());
     const double cell = o.cell > 0.0 ? o.cell : 2.0 * voxel, bin = o.bin > 0.0 ? o.bin : 2.0 * voxel;
     double up[3] = {o.up[0], o.up[1], o.up[2]};
@@ -220,12 +222,12 @@ void EMFusion::writeGround(const std::string& dir) {
         emf_ground_frame_t f{};
         double p[12];
         std::string why;
-        const int rc = groundFrame(queryBoxAt(Vec3i(0, 0, 0), n), up, cell, bin, ref, o.bandLo, o.bandHi, f, p, why);
+        const int rc = groundFrame(queryBoxAt(boxLo, boxSize), up, cell, bin, ref, o.bandLo, o.bandHi, f, p, why);
         if (rc) throw HipError("EMFusion::writeGround: " + why, rc);
         if (!groundFrameAligned(f))
             throw HipError("EMFusion::writeGround: cells and bins below two voxels need an up along a box axis", EMF_E_ARG);
     }
-    const GroundMap& g = groundMap(Vec3i(0, 0, 0), n, up, cell, bin, ref, o.bandLo, o.bandHi, robot, step, {});
+    const GroundMap& g = groundMap(boxLo, boxSize, up, cell, bin, ref, o.bandLo, o.bandHi, robot, step, {});
     const size_t cells = static_cast<size_t>(g.frame.map[0]) * g.frame.map[1];
     std::vector<uint8_t> classes(cells);
     std::vector<emf_ground_cell_t> records(cells);

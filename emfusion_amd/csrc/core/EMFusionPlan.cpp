@@ -141,18 +141,22 @@ Vec3i EMFusion::cameraVoxel() const {
 // start, each the double value rounded once to float, %.9g.  With setPlanShortcutOutput(W > 0) the path lines of a
 // reachable cluster are followed by one line "waypoints n i_0 .. i_(n-1)", shortcutPlan(W) of that path.
 void EMFusion::writePlan(const std::string& dir) {
-    const Vec3i n = background.getVolumeRes();
+    Vec3i lo, n;  // the whole background; the world extent with setQueryExtent(true)
+    resultsBox("writePlan", lo, n);
     const float voxel = background.getVoxelSize();
     const int clearance = metresToVoxels(planClearanceMetres_, voxel);
-    const Frontiers& f = frontiers(Vec3i(0, 0, 0), n, std::max(frontierMinVoxels_, 1), clearance, {});  // as writeFrontiers
+    const Frontiers& f = frontiers(lo, n, std::max(frontierMinVoxels_, 1), clearance, {});  // as writeFrontiers
     std::vector<Vec3i> goals;
     for (const emf_frontier_cluster_t& c : f.clusters) goals.push_back(Vec3i(c.rep[0], c.rep[1], c.rep[2]));
-    plan(Vec3i(0, 0, 0), n, {cameraVoxel()}, std::max(clearance, 1), planThroughUnknown_, clearance, 0u, goals, -1, {});
+    const Vec3i cam = cameraVoxel();  // of the background; the start is a voxel of the box
+    plan(lo, n, {Vec3i(cam[0] - lo[0], cam[1] - lo[1], cam[2] - lo[2])}, std::max(clearance, 1), planThroughUnknown_, clearance, 0u, goals, -1, {});
     const Plan& p = planShortcutWindow_ > 0 ? shortcutPlan(planShortcutWindow_) : lastPlan();
     const std::string path = dir + "/plan.txt";
     std::FILE* file = std::fopen(path.c_str(), "w");
     if (!file) throw std::runtime_error("EMFusion::writePlan: cannot create " + path);
     std::fprintf(file, "# count reachable cost length_m rep_x rep_y rep_z n_path, then n_path lines x y z from the goal to the start\n");
+    if (queryWorld_)  // as frontiers.txt
+        std::fprintf(file, "# world extent: lo %d %d %d size %d %d %d\n", lo[0], lo[1], lo[2], n[0], n[1], n[2]);
     for (size_t k = 0; k < f.clusters.size(); ++k) {
         const Plan::Goal& g = p.goals[k];
         double r[3];

@@ -274,7 +274,7 @@ void EMFusion::describePlanePatches(const Planes& r, const PlanePatches& pp, std
 
 const EMFusion::Planes& EMFusion::planes(const Vec3i& boxLo, const Vec3i& boxSize, const emf_plane_params_t& p, bool keepLabels) {
     Planes out;
-    out.box = makeQueryBox("planes", "the plane search is", boxLo, boxSize);
+    out.box = makeQueryBox("planes", "the plane search is", boxLo, boxSize, true);  // tsdf values: the volume only
     pnLast = Planes();  // a call that throws leaves no result: the buffers of the last one are about to be rewritten
     ppLast = PlanePatches();  // ... and the patches of the last one are those of records that are about to go
     if (p.K < 1 || p.K > EMF_PLANE_MAX_K) throw HipError("EMFusion::planes: K outside 1 .. 31", p.K < 1 ? EMF_E_ARG : EMF_E_LIMIT);

@@ -13,6 +13,13 @@ namespace emf {
 struct QueryBox {
     Vec3i lo, size;        // voxels of the background, (x, y, z)
     Vec3i bgRes;
+    // A box of the world extent may leave the background.  It is described as a box of a VIRTUAL
+    // background of bgRes = res + 2 pad voxels at lo = the volume voxel + pad: float(v + pad) - (res + 2 pad - 1) / 2.f
+    // equals float(v) - (res - 1) / 2.f exactly -- half-integers far below 2^23 --, in double too, so everything below
+    // and every kernel that takes (res, box_lo) gives the same bits as for the real background.  pad is 0 otherwise.
+    Vec3i pad = Vec3i(0, 0, 0);
+    /** The box's first voxel in voxels of the real background volume: what callers passed and get back. */
+    Vec3i volumeLo() const { return Vec3i(lo[0] - pad[0], lo[1] - pad[1], lo[2] - pad[2]); }
     Affine3f bgPose;       // the background's pose the world points go through
     Affine3f boxPose;      // voxel (0, 0, 0) of the box -> world: the background's pose and the box origin, in float
     float voxelSize = 0.f;
@@ -52,6 +59,34 @@ struct QueryBox {
         }
     }
 };
+
+/** The padding of the virtual background of a box [lo, lo + size) of a background of `res` voxels: per axis the voxels
+ *  by which the box leaves it on either side, 0 for a box inside. */
+inline Vec3i queryBoxPad(const Vec3i& lo, const Vec3i& size, const Vec3i& res) {
+    Vec3i pad;
+    for (int i = 0; i < 3; ++i) {
+        const long long over = static_cast<long long>(lo[i]) + size[i] - res[i];
+        pad[i] = static_cast<int>(std::max<long long>({0ll, -static_cast<long long>(lo[i]), over}));
+    }
+    return pad;
+}
+
+/** The bounding box [lo, lo + size), in voxels of a background of `res` voxels whose voxel 0 is lattice voxel `origin`,
+ *  of that background and the tiles of `tile` voxels at the lattice TILE coordinates `keys` (x, y, z). */
+template <class Keys>
+inline void tilesExtent(const Keys& keys, const int tile[3], const Vec3i& origin, const Vec3i& res, Vec3i& lo, Vec3i& size) {
+    long long a[3] = {0, 0, 0}, b[3] = {res[0], res[1], res[2]};
+    for (const auto& key : keys)
+        for (int i = 0; i < 3; ++i) {
+            const long long first = static_cast<long long>(key[i]) * tile[i] - origin[i];
+            a[i] = std::min(a[i], first);
+            b[i] = std::max(b[i], first + tile[i]);
+        }
+    for (int i = 0; i < 3; ++i) {
+        lo[i] = static_cast<int>(a[i]);
+        size[i] = static_cast<int>(b[i] - a[i]);
+    }
+}
 
 /** Metres rounded up to whole voxels, at most 4096 and 0 for "none" -- in float, as both apps and the Python layer do. */
 inline int metresToVoxels(float metres, float voxel) {

@@ -580,6 +580,23 @@ int emf_fusion_world_mesh_info(emf_fusion_t* h, uint64_t out[4]) {
     });
 }
 
+int emf_fusion_set_query_extent(emf_fusion_t* h, int world) {
+    REQ(h);
+    return guarded([&] { h->impl->setQueryExtent(world != 0); });
+}
+
+int emf_fusion_world_extent(emf_fusion_t* h, int32_t lo[3], int32_t size[3]) {
+    REQ(h);
+    REQ(lo);
+    REQ(size);
+    return guarded([&] {
+        Vec3i a, n;
+        h->impl->worldExtent(a, n);
+        std::memcpy(lo, a.val, sizeof(a.val));
+        std::memcpy(size, n.val, sizeof(n.val));
+    });
+}
+
 // ---- what the scene queries (distance field, frontiers, plan) share ----
 struct QueryArgs {
     Vec3i lo, size;  // no box: the whole background
@@ -605,7 +622,8 @@ static int queryArgs(const char* who, emf_fusion_t* h, const int32_t* box_lo, co
 
 // a result's box into the entry's outputs, each of which may be NULL
 static void putBox(const QueryBox& b, int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3]) {
-    if (lo_out) std::memcpy(lo_out, b.lo.val, sizeof(b.lo.val));
+    const Vec3i lo = b.volumeLo();  // (a world box is kept with the padding of its virtual background)
+    if (lo_out) std::memcpy(lo_out, lo.val, sizeof(lo.val));
     if (size_out) std::memcpy(size_out, b.size.val, sizeof(b.size.val));
     if (R) std::memcpy(R, b.boxPose.rotation().val, 9 * sizeof(float));
     if (t) std::memcpy(t, b.boxPose.translation().val, 3 * sizeof(float));

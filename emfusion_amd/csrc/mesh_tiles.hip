@@ -21,6 +21,7 @@
 // checked: an entry whose literal leaves the arena or whose in-place tile leaves the volume, and a neighbour index
 // that does not name the tile at the neighbouring coordinate, count as "not listed" and are never dereferenced.
 #include "mesh_core.hpp"
+#include "tile_table.hpp"
 #include "wave_ops.hpp"
 
 #include "mc_tables.h"
@@ -31,10 +32,6 @@ namespace {
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kTilesBlock = 256;
-constexpr int kTX = 32, kTY = 8, kTZ = 8;  // the integration tile (device_core.hpp kTileX / Y / Z)
-constexpr unsigned kUnitWords = 2048;      // one arena unit: 8 KiB
-constexpr unsigned kMaxTiles = 1u << 17;   // 2^17 x 24576 vertices stays below 2^32
-constexpr int kLatticeBits = 19;           // lattice voxel coordinates in [-2^19, 2^19)
 constexpr int kVX = kTX + 1, kVY = kTY + 1, kVZ = kTZ + 1;  // the "weight > 0" image: +1 halo
 
 static_assert(sizeof(emf_mesh_tile_t) == 88, "emf_mesh_tile_t layout is mirrored in _lib.py");
@@ -411,8 +408,6 @@ __global__ __launch_bounds__(kSumsBlock) void k_tiles_scan(unsigned* vertBase, u
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // what every entry checks of its arguments, and the kernels' view of them
 int prepare(TilesArgs& a, const emf_mesh_tile_t* tiles_dev, uint32_t n, const emf_mesh_tiles_source_t* source,
             const void* scratch_dev, const char* what) {
@@ -422,18 +417,7 @@ int prepare(TilesArgs& a, const emf_mesh_tile_t* tiles_dev, uint32_t n, const em
     if (n) EMF_REQUIRE_PTR(tiles_dev);
     if ((reinterpret_cast<uintptr_t>(tiles_dev) & 7u) != 0 || (reinterpret_cast<uintptr_t>(scratch_dev) & 3u) != 0)
         return fail(EMF_E_ARG, "%s: tiles_dev or scratch_dev is misaligned", what);
-    if (!aligned16(source->arena)) return fail(EMF_E_ARG, "%s: the arena must be 16-byte aligned", what);
-    if (!aligned16(source->tsdf) || !aligned16(source->weights) || !aligned16(source->color))
-        return fail(EMF_E_ARG, "%s: the volume arrays must be 16-byte aligned", what);
-    if ((source->weights != nullptr || source->color != nullptr) && source->tsdf == nullptr)
-        return fail(EMF_E_NULL, "%s: a weight or colour volume without its tsdf", what);
-    if (source->tsdf != nullptr) {
-        EMF_REQUIRE_PTR(source->weights);
-        if ((source->row_stride & 3u) != 0 || (source->plane_stride & 3u) != 0)
-            return fail(EMF_E_ARG, "%s: the volume's strides must be multiples of 4 voxels", what);
-        if (source->row_stride > (1ull << 40) || source->plane_stride > (1ull << 40) || source->volume_elements > (1ull << 48))
-            return fail(EMF_E_LIMIT, "%s: volume too large", what);
-    }
+    EMF_TRY(check_tiles_source(source, what));
     a = TilesArgs{};
     a.tiles = tiles_dev;
     a.n = n;
@@ -453,28 +437,9 @@ int prepare(TilesArgs& a, const emf_mesh_tile_t* tiles_dev, uint32_t n, const em
 
 // the table as the host sees it
 int check_table(const emf_mesh_tile_t* th, uint32_t n, const emf_mesh_tiles_source_t* source) {
-    const long long lim = 1ll << kLatticeBits;
-    const int ext[3] = {kTX, kTY, kTZ};
     for (uint32_t i = 0; i < n; ++i) {
+        EMF_TRY(check_tile_entry(th, i, source, "meshTilesCount"));
         const emf_mesh_tile_t& e = th[i];
-        for (int k = 0; k < 3; ++k) {
-            if (e.cls[k] > 3) return fail(EMF_E_ARG, "meshTilesCount: class %u of tile %u (0 .. 3)", e.cls[k], i);
-            if (e.cls[k] == 2 && (source->arena == nullptr || source->arena_units == 0))
-                return fail(EMF_E_NULL, "meshTilesCount: literal tiles without an arena");
-            if (e.cls[k] == 3 && (k == 2 ? source->color == nullptr : source->tsdf == nullptr))
-                return fail(EMF_E_NULL, "meshTilesCount: in-place tiles without a volume");
-            const long long lo = static_cast<long long>(e.coord[k]) * ext[k];
-            if (lo < -lim || lo + ext[k] > lim)
-                return fail(EMF_E_LIMIT, "meshTilesCount: tile %u at lattice voxel %lld on axis %d (within +-2^%d)", i, lo, k,
-                            kLatticeBits);
-        }
-        if (i > 0) {
-            const emf_mesh_tile_t& p = th[i - 1];
-            const bool after = e.coord[2] != p.coord[2] ? e.coord[2] > p.coord[2]
-                               : (e.coord[1] != p.coord[1] ? e.coord[1] > p.coord[1] : e.coord[0] > p.coord[0]);
-            if (!after)
-                return fail(EMF_E_ARG, "meshTilesCount: tile %u is not after tile %u in (z, y, x) order", i, i - 1);
-        }
         for (int k = 1; k < 8; ++k) {
             const int32_t j = e.nbr[k - 1];
             if (j < -1 || (j >= 0 && static_cast<uint32_t>(j) >= n))

@@ -1663,6 +1663,41 @@ def occupancy_classes(tsdf, weights, box=None, objects=None, voxel_size=None, ou
     return out
 
 
+def occupancy_tiles(tiles, box, stream=None):
+    """emf_hip_occupancyTiles (include/emf_hip.h "Occupancy of a set of tiles"): the (bz, by, bx) u8
+    classes of the box (lo, size), both (x, y, z) in LATTICE voxels -- lo may be negative, nothing needs to be aligned
+    -- of the dense volume that holds exactly the listed tiles: OCC_UNKNOWN wherever no tile is listed.  tiles: the dict
+    of mesh_tiles (its neighbours, if any, are not looked at).  Returns a numpy array."""
+    coords = np.asarray(tiles["coords"]).reshape(-1, 3)
+    n = int(coords.shape[0])
+    table = mesh_tile_table(coords, tiles["classes"], tiles["words"], tiles["at"], np.full((n, 7), -1, np.int32))
+    src = _lib.EmfMeshTilesSource()
+    keep = []  # the uploads live until the synchronize below
+    arena = tiles.get("arena")
+    if arena is not None and np.asarray(arena).size:
+        keep.append(DeviceArray.from_numpy(np.ascontiguousarray(arena, np.uint8).reshape(-1, TILE_UNIT)))
+        src.arena, src.arena_units = keep[-1].ptr, keep[-1].nbytes // TILE_UNIT
+    vol = tiles.get("volume")
+    if vol is not None:
+        nz, ny, nx = vol["tsdf"].shape
+        keep.append(DeviceArray.from_numpy(np.ascontiguousarray(vol["tsdf"], np.float32)))
+        keep.append(DeviceArray.from_numpy(np.ascontiguousarray(vol["weights"], np.float32)))
+        src.tsdf, src.weights = keep[-2].ptr, keep[-1].ptr
+        if vol.get("color") is not None:
+            keep.append(DeviceArray.from_numpy(np.ascontiguousarray(vol["color"], np.uint16)))
+            src.color = keep[-1].ptr
+        src.volume_elements, src.row_stride, src.plane_stride = nz * ny * nx, nx, nx * ny
+    d_table = DeviceArray.from_numpy(np.frombuffer(table, np.uint8).copy()) if n else None
+    lo, size = box
+    shape = tuple(max(int(v), 0) for v in (size[2], size[1], size[0]))
+    out = DeviceArray(shape, np.uint8)
+    check("emf_hip_occupancyTiles",
+          _L.emf_hip_occupancyTiles(_ptr(d_table), C.cast(table, C.c_void_p), n, C.byref(src), _i3(lo), _i3(size), _ptr(out),
+                                    _stream(stream)))
+    synchronize()  # the uploads are released on return
+    return out.numpy()
+
+
 def distance_transform(classes, site_mask=2, cap=0, voxel_size=None, out=None, stream=None, nearest=False):
     """emf_hip_distanceTransform of a (nz, ny, nx) u8 class volume: d2 (nz, ny, nx) i32, the exact squared distance in
     voxels to the nearest voxel whose class bit is set in site_mask (1 FREE, 2 OCCUPIED, 4 UNKNOWN), DF_FAR where there

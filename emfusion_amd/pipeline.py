@@ -147,6 +147,8 @@ def load() -> C.CDLL:
         "emf_fusion_world_mesh": [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
         "emf_fusion_world_mesh_info": [vp, C.c_void_p],
         "emf_fusion_set_world_mesh_output": [vp, C.c_int],
+        "emf_fusion_set_query_extent": [vp, C.c_int],
+        "emf_fusion_world_extent": [vp, ip, ip],
         "emf_fusion_follow_shift": [fp, ip, C.c_float, ip],
         "emf_fusion_distance_field": [vp, ip, ip, C.c_uint32, C.c_int32, ip, C.c_int32, C.c_int, ip, ip, fp, fp],
         "emf_fusion_copy_distance_field": [vp, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -1386,10 +1388,38 @@ class Fusion:
         """The frame of the box of the background at `lo`, at the background's current pose."""
         return _BoxFrame(*self.background_pose(), self.params.bg_res, self.params.bg_voxel_size, lo)
 
+    def set_query_extent(self, extent):
+        """The extent of the scene queries: "background" (the default) or "world".  With "world" the
+        box of distance_field, frontiers, plan, cast_rays, view_gain and ground_map may leave the background -- it stays
+        in voxels of the current background volume, so lo may be negative and lo + size may exceed the resolution --
+        and is classified from the tiles world_mesh() reads: the observed tiles of the volume and every tile the
+        background store holds; what lies in no tile is unknown.  Sticky, never in a checkpoint.  A world query is
+        refused on the sharded path and when the background's resolution or origin is off the tile (32, 8, 8);
+        planes() keeps to the background."""
+        if extent not in ("world", "background"):
+            raise ValueError(f'set_query_extent: "world" or "background", not {extent!r}')
+        _check("emf_fusion_set_query_extent", load().emf_fusion_set_query_extent(self._h, int(extent == "world")))
+        self._query_extent = extent
+
+    def query_extent(self):
+        return getattr(self, "_query_extent", "background")
+
+    def world_extent(self):
+        """(lo, size), both (x, y, z) in voxels of the current background volume: the bounding box of the background
+        and every tile the background store holds -- ((0, 0, 0), the resolution) when nothing is stored."""
+        lo, size = (C.c_int32 * 3)(), (C.c_int32 * 3)()
+        _check("emf_fusion_world_extent", load().emf_fusion_world_extent(self._h, lo, size))
+        return tuple(lo), tuple(size)
+
     def _resolve_box(self, who, box, size):
-        """The `box` argument of the query `who`: None, (lo, size), or "camera" with `size` for camera_box(size)."""
+        """The `box` argument of the query `who`: None, (lo, size), "camera" with `size` for camera_box(size), or
+        "world" for world_extent() while the query extent is "world"."""
         if not isinstance(box, str):
             return box
+        if box == "world":
+            if self.query_extent() != "world":
+                raise ValueError(f'{who}: box="world" needs set_query_extent("world")')
+            return self.world_extent()
         if box != "camera" or size is None:
             raise ValueError(f'{who}: box="camera" needs a size')
         box = self.camera_box(size)

@@ -232,6 +232,22 @@ int emf_fusion_world_mesh_info(emf_fusion_t* h, uint64_t out[4]);
  * emf_fusion_write_results also writes world.ply, the PLY of the world mesh at that moment, byte for byte
  * emf_io_write_mesh of it, and nothing else new.  Off (the default): no output byte changes. */
 int emf_fusion_set_world_mesh_output(emf_fusion_t* h, int on);
+/* The extent of the scene queries (new behaviour, sticky, off by default, never in a checkpoint; with it
+ * off no launch, no output byte and no refusal changes).  world != 0: the box of emf_fusion_distance_field[_nearest],
+ * emf_fusion_frontiers, emf_fusion_plan, emf_fusion_cast_rays, emf_fusion_view_gain and emf_fusion_ground_map may leave
+ * the background.  It stays in voxels of the CURRENT background volume -- box_lo may be negative, box_lo + box_size may
+ * exceed the resolution -- and the classes come from the tiles the world mesh reads (the observed tiles of the volume
+ * and every tile the background store holds; emf_hip_occupancyTiles); what lies in no tile is unknown.  The limits
+ * of a box stay.  Such a query is refused (EMF_E_ARG) on the sharded path and when the background's resolution or
+ * origin is not a multiple of the tile (32, 8, 8), with the session untouched.  emf_fusion_planes reads tsdf values and
+ * keeps refusing a box that leaves the background.  emf_fusion_write_results then takes emf_fusion_world_extent
+ * wherever distance.bin, nearest.bin, frontiers.txt, plan.txt and ground.bin / ground.txt take the whole background
+ * (the two text files say so in a second comment line), and refuses an extent above the limits naming the axis.
+ * These are entries of their own so that every existing entry keeps its signature. */
+int emf_fusion_set_query_extent(emf_fusion_t* h, int world);
+/* The bounding box, in voxels of the current background volume, of the background and every tile the background
+ * store holds: lo = (0, 0, 0) and size = the resolution when nothing is stored.  Host state only: nothing is launched. */
+int emf_fusion_world_extent(emf_fusion_t* h, int32_t lo[3], int32_t size[3]);
 int emf_fusion_follow_shift(const float q[3], const int32_t step[3], float voxel_size, int32_t shift[3]);
 /* The distance field of the scene (include/emf_hip.h "Distance field"; new behaviour, nothing of the
  * session changes and nothing goes into a checkpoint).  Over the box [box_lo, box_lo + box_size) of the background, in

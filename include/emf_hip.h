@@ -1589,6 +1589,25 @@ int emf_hip_occupancyStampObjects(uint8_t* classes, const int32_t res[3], float 
                                   const int32_t box_size[3], const emf_occ_object_t* objects, int32_t n,
                                   emf_stream_t stream);
 
+/* Occupancy of a set of tiles (new behaviour: DESIGN.md 5.28).  Step 1 over a SPARSE set of integration tiles on one
+ * integer lattice instead of a dense volume: the result is emf_hip_occupancyClasses of the dense volume that holds
+ * exactly the listed tiles and is unobserved (tsdf 0, weight 0) everywhere else, cropped to the box.  box_lo and
+ * box_size are in LATTICE voxels (x, y, z); box_lo may be negative and nothing needs to be aligned to a tile.  A voxel
+ * in no listed tile is EMF_OCC_UNKNOWN; the three single float comparisons are those above, NaN and -0.0 included.
+ * Only the tsdf and the weights of a tile are read; its colour class counts for the skip rule alone.
+ * The table, tiles_dev / tiles_host and source are those of "Meshing a set of tiles": sorted strictly ascending in
+ * (z, y, x), classes 0 / 1 / 2 / 3 per array; what the host can see is refused from tiles_host before any launch with
+ * the codes of emf_hip_meshTilesCount, and what only the device sees skips the tile as a whole -- it then counts as
+ * not listed and is never dereferenced.  nbr[] is neither used nor checked.
+ * Limits: every box axis in 1 .. EMF_DF_MAX_AXIS and at most 2^31 - 1 voxels (EMF_E_LIMIT above; a zero or negative
+ * axis and a NULL box or classes are EMF_E_ARG); every lattice voxel of the box in [-2^19, 2^19) (EMF_E_LIMIT); n at
+ * most 2^17 (EMF_E_LIMIT).  n == 0 writes an all-unknown box.  One launch: a workgroup per tile-aligned cell the box
+ * overlaps finds its tile by a search of the sorted table; every byte of the box is written exactly once by a plain
+ * store.  Nothing allocates, copies to the host or waits. */
+int emf_hip_occupancyTiles(const emf_mesh_tile_t* tiles_dev, const emf_mesh_tile_t* tiles_host, uint32_t n,
+                           const emf_mesh_tiles_source_t* source, const int32_t box_lo[3], const int32_t box_size[3],
+                           uint8_t* classes, emf_stream_t stream);
+
 /* Step 3.  classes: size[0] * [1] * [2] bytes, only read; d2: as many i32.  site_mask in 1 .. 7; cap >= 0 in voxels,
  * 0 = none.  metres: NULL, or as many f32, written by the last pass as sqrtf(float(d2)) * voxel_size (two roundings;
  * voxel_size > 0 then) and +inf where d2 is EMF_DF_FAR.  Three separable passes, x (wave ballots and bit scans, no
