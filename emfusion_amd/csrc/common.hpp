@@ -148,6 +148,17 @@ int launch_status(const char* what);
 
 inline hipStream_t as_stream(emf_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// hipMemsetAsync as an entry's step: a failure is the entry's return code, and no later launch_status meets it again
+inline int memset_async(void* p, int v, size_t bytes, emf_stream_t stream, const char* what) {
+    const hipError_t e = hipMemsetAsync(p, v, bytes, as_stream(stream));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: memset: %s", what, hipGetErrorString(e));
+        return static_cast<int>(e);
+    }
+    return EMF_OK;
+}
+
 inline unsigned ceil_div(size_t a, size_t b) { return static_cast<unsigned>((a + b - 1) / b); }
 
 inline size_t align16(size_t b) { return (b + 15) & ~static_cast<size_t>(15); }

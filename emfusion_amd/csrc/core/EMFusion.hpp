@@ -22,6 +22,7 @@
 
 #include "Communicator.hpp"
 #include "KernelTimers.hpp"
+#include "MeshPost.hpp"
 #include "ObjTSDF.hpp"
 #include "Output.hpp"
 #include "QueryBox.hpp"
@@ -1125,19 +1126,19 @@ private:
     void storeFrameMeshes();                               // the end of a frame with exp_frame_meshes
     DeviceBuffer meshTableDev, meshCountsDev, meshScratch, meshArena;  // extractMeshes' pooled buffers
     bool meshWeld = false;                                 // setMeshWeld
-    DeviceBuffer meshWeldScratch;                          // keys, welded counts / bases and the weld's scratch
+    DeviceBuffer meshKeysDev, meshColorPtrsDev;            // the soup's grid-edge keys; the models' colour volumes
+    MeshPost meshPost;                                     // weld -> filter -> simplify and the download (MeshPost.hpp)
     uint32_t meshMinTriangles = 0;                         // setMeshFilter
     bool meshLargestObjects = false;
     std::map<int, MeshFilterStats> meshFilterStats;        // lastMeshFilter
-    DeviceBuffer meshFilterScratch, meshFilterArena;       // the filter's counts + scratch, its kept arrays
     float meshSimplifyCell = 0.f;                          // setMeshSimplify
     std::map<int, MeshSimplifyStats> meshSimplifyStats;    // lastMeshSimplify
-    DeviceBuffer meshSimplifyScratch, meshSimplifyArena;   // the simplification's counts + scratch, its arrays
     bool meshSimplifyActive() const { return meshSimplifyCell > 0.f; }
     MeshFilter meshFilterFor(int id) const {               // the background keeps its pieces
         return MeshFilter{meshMinTriangles, meshLargestObjects && id != 0, meshSimplifyCell};
     }
     bool meshFilterActive() const { return meshMinTriangles > 1 || meshLargestObjects; }
+    void meshColors(const std::vector<int>& ids, const std::vector<int32_t>& res, uint64_t nv, DeviceBuffer& cDev);
     void extractWelded(const std::vector<int>& ids, const std::vector<int32_t>& res, uint64_t nv, uint64_t nt,
                        std::vector<Mesh>& out);
     bool expVols = false;                                  // setupOutput: keep / dump volumes too
@@ -1275,7 +1276,6 @@ private:
     PinnedBuffer motionHost;       // mirror of motionInfoDev
     PinnedBuffer viewPosesHost;    // EMF_MAX_MODELS viewer -> volume poses
     PinnedBuffer meshHost;         // EMF_MAX_MODELS emf_model_t, then the counts and bases read back
-    PinnedBuffer meshStage;        // staging of the meshes' bytes (grown when needed)
     std::vector<Event> stamps;     // the frame timings' marks on `main`
 
     // ---- voxel rays (castRays, viewGain, shortcutPlan; EMFusionRays.cpp): allocated at first use, never in a checkpoint.

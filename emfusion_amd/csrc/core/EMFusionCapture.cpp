@@ -332,266 +332,61 @@ std::vector<Mesh> EMFusion::extractMeshes(const std::vector<int>& ids) {
         extractWelded(ids, res, nv, nt, out);
         return out;
     }
-    meshStage.grow(2 * vb + tb);
-    float* vHost = meshStage.as<float>();
-    float* nHost = vHost + 3 * nv;
-    int32_t* tHost = reinterpret_cast<int32_t*>(nHost + 3 * nv);
-    hipCheck(hipMemcpyAsync(vHost, vDev, vb, hipMemcpyDeviceToHost, main.get()), "mesh vertices D2H");
-    hipCheck(hipMemcpyAsync(nHost, nDev, vb, hipMemcpyDeviceToHost, main.get()), "mesh normals D2H");
-    if (nt) hipCheck(hipMemcpyAsync(tHost, tDev, 4 * sizeof(int32_t) * nt, hipMemcpyDeviceToHost, main.get()), "mesh triangles D2H");
-    main.waitForCompletion();
-    std::vector<uint8_t> cHost;
-    if (colorOn) {  // the same vertices, coloured: one more walk over the surface chunks the count listed
-        std::vector<uint16_t*> ptrs(n, nullptr);
-        for (int k = 0; k < n; ++k) ptrs[k] = ids[k] == 0 ? background.colorPtr() : getObject(ids[k])->colorPtr();
-        DeviceBuffer ptrsDev(sizeof(uint16_t*) * n), cDev(3 * nv);
-        hipCheck(hipMemcpyAsync(ptrsDev.data(), ptrs.data(), sizeof(uint16_t*) * n, hipMemcpyHostToDevice, main.get()),
-                 "mesh colour table upload");
-        emfCheck(emf_hip_meshColorsBatched(meshTableDev.as<emf_model_t>(), ptrsDev.as<uint16_t*>(), res.data(), n,
-                                           meshScratch.data(), cDev.as<uint8_t>(), main.abi()),
-                 "meshColorsBatched");
-        cHost.resize(3 * nv);
-        hipCheck(hipMemcpyAsync(cHost.data(), cDev.data(), 3 * nv, hipMemcpyDeviceToHost, main.get()), "mesh colours D2H");
-        main.waitForCompletion();
-    }
-    for (int k = 0; k < n; ++k) {  // model k's slice is its own mesh (local triangle indices)
-        const size_t v0 = bases[2 * k], t0 = bases[2 * k + 1];
-        Mesh& m = out[k];
-        m.cloud.assign(vHost + 3 * v0, vHost + 3 * (v0 + counts[k].vertices));
-        m.normals.assign(nHost + 3 * v0, nHost + 3 * (v0 + counts[k].vertices));
-        m.polygons.assign(tHost + 4 * t0, tHost + 4 * (t0 + counts[k].triangles));
-        if (!cHost.empty()) m.colors.assign(cHost.begin() + 3 * v0, cHost.begin() + 3 * (v0 + counts[k].vertices));
-    }
+    DeviceBuffer cDev;
+    if (colorOn) meshColors(ids, res, nv, cDev);
+    std::vector<MeshSlice> slices(n);
+    for (int k = 0; k < n; ++k) slices[k] = MeshSlice{bases[2 * k], counts[k].vertices, bases[2 * k + 1], counts[k].triangles};
+    meshPost.download(main, DeviceMesh{vDev, nDev, tDev, colorOn ? cDev.as<uint8_t>() : nullptr, nv, nt}, slices, out.data());
     return out;
+}
+
+// the soup's vertices coloured: one more walk over the surface chunks the count listed, enqueued on main
+void EMFusion::meshColors(const std::vector<int>& ids, const std::vector<int32_t>& res, uint64_t nv, DeviceBuffer& cDev) {
+    const int n = static_cast<int>(ids.size());
+    std::vector<uint16_t*> ptrs(n, nullptr);
+    for (int k = 0; k < n; ++k) ptrs[k] = ids[k] == 0 ? background.colorPtr() : getObject(ids[k])->colorPtr();
+    meshColorPtrsDev.reserve(sizeof(uint16_t*) * EMF_MAX_MODELS);  // (a member: the kernel reads it after this returns)
+    cDev = DeviceBuffer(3 * nv);
+    hipCheck(hipMemcpyAsync(meshColorPtrsDev.data(), ptrs.data(), sizeof(uint16_t*) * n, hipMemcpyHostToDevice, main.get()),
+             "mesh colour table upload");
+    emfCheck(emf_hip_meshColorsBatched(meshTableDev.as<emf_model_t>(), meshColorPtrsDev.as<uint16_t*>(), res.data(), n,
+                                       meshScratch.data(), cDev.as<uint8_t>(), main.abi()),
+             "meshColorsBatched");
 }
 
 // extractMeshes' tail with setMeshWeld(true) (include/emf_hip.h "Welded meshes").  The soup of the n models lies in
 // meshArena ([vertices][normals][triangles], as the emit wrote it) and the counting scratch is still valid: colours and
-// edge keys walk the surface chunks once more, the weld runs on the keys, and the welded vertex arrays land behind the
-// soup in the same arena (grown when needed; the soup is copied over, it is a quarter of what a frame's soup D2H was).
-// With setMeshFilter the components are labelled, filtered and compacted behind the weld (include/emf_hip.h "Mesh
-// components") and the kept arrays are what travels; with setMeshSimplify those are clustered by cell behind the filter
-// (include/emf_hip.h "Simplified meshes") and the simplified arrays travel instead.
+// edge keys walk the surface chunks once more, and the chain of MeshPost.hpp welds on the keys, filters by component
+// with setMeshFilter and clusters by cell with setMeshSimplify; what is left is what travels.
 void EMFusion::extractWelded(const std::vector<int>& ids, const std::vector<int32_t>& res, uint64_t nv, uint64_t nt,
                              std::vector<Mesh>& out) {
     const int n = static_cast<int>(ids.size());
     auto* counts = reinterpret_cast<emf_mesh_counts_t*>(meshHost.as<emf_model_t>() + EMF_MAX_MODELS);
     auto* bases = reinterpret_cast<uint64_t*>(counts + EMF_MAX_MODELS);
     auto* basesDev = reinterpret_cast<uint64_t*>(meshCountsDev.as<emf_mesh_counts_t>() + EMF_MAX_MODELS);
-    const size_t vb = 3 * sizeof(float) * nv, tb = 4 * sizeof(int32_t) * std::max<uint64_t>(nt, 1);
-    const size_t weldBytes = emf_hip_meshWeldScratchBytes(nv);
-    if (weldBytes == 0) throw HipError("EMFusion::extractMeshes: " + std::to_string(nv) + " soup vertices", EMF_E_LIMIT);
-    // [keys u64 x nv][welded counts u32 x MAX][welded bases u64 x (MAX + 1)][weld scratch]
-    const size_t keyBytes = sizeof(uint64_t) * nv, cntBytes = sizeof(uint32_t) * EMF_MAX_MODELS,
-                 baseBytes = sizeof(uint64_t) * (EMF_MAX_MODELS + 1);
-    if (meshWeldScratch.bytes() < keyBytes + cntBytes + baseBytes + weldBytes)
-        meshWeldScratch = DeviceBuffer(keyBytes + cntBytes + baseBytes + weldBytes);
-    auto* keysDev = meshWeldScratch.as<uint64_t>();
-    auto* wBasesDev = keysDev + nv;
-    auto* wCountsDev = reinterpret_cast<uint32_t*>(wBasesDev + EMF_MAX_MODELS + 1);
-    void* weldScratch = reinterpret_cast<char*>(meshWeldScratch.data()) + keyBytes + baseBytes + cntBytes;
     float* vDev = meshArena.as<float>();
     float* nDev = vDev + 3 * nv;
     int32_t* tDev = reinterpret_cast<int32_t*>(nDev + 3 * nv);
-    DeviceBuffer ptrsDev, cDev, wcDev;
-    if (colorOn) {
-        std::vector<uint16_t*> ptrs(n, nullptr);
-        for (int k = 0; k < n; ++k) ptrs[k] = ids[k] == 0 ? background.colorPtr() : getObject(ids[k])->colorPtr();
-        ptrsDev = DeviceBuffer(sizeof(uint16_t*) * n);
-        cDev = DeviceBuffer(3 * nv);
-        hipCheck(hipMemcpyAsync(ptrsDev.data(), ptrs.data(), sizeof(uint16_t*) * n, hipMemcpyHostToDevice, main.get()),
-                 "mesh colour table upload");
-        emfCheck(emf_hip_meshColorsBatched(meshTableDev.as<emf_model_t>(), ptrsDev.as<uint16_t*>(), res.data(), n,
-                                           meshScratch.data(), cDev.as<uint8_t>(), main.abi()),
-                 "meshColorsBatched");
-    }
-    emfCheck(emf_hip_meshEdgeKeysBatched(meshTableDev.as<emf_model_t>(), res.data(), n, meshScratch.data(), keysDev,
-                                         main.abi()),
+    DeviceBuffer cDev;
+    if (colorOn) meshColors(ids, res, nv, cDev);
+    meshKeysDev.reserve(sizeof(uint64_t) * nv);
+    emfCheck(emf_hip_meshEdgeKeysBatched(meshTableDev.as<emf_model_t>(), res.data(), n, meshScratch.data(),
+                                         meshKeysDev.as<uint64_t>(), main.abi()),
              "meshEdgeKeysBatched");
-    emfCheck(emf_hip_meshWeldCountBatched(keysDev, nv, basesDev, n, weldScratch, wCountsDev, wBasesDev, main.abi()),
-             "meshWeldCountBatched");
-    std::vector<uint32_t> wCounts(n);
-    std::vector<uint64_t> wBases(n + 1);
-    hipCheck(hipMemcpyAsync(wCounts.data(), wCountsDev, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, main.get()),
-             "welded counts D2H");
-    hipCheck(hipMemcpyAsync(wBases.data(), wBasesDev, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost, main.get()),
-             "welded bases D2H");
-    emfCheck(emf_hip_meshWeldStatus(weldScratch, nv, main.abi()), "meshWeld (table)");  // waits: the welded sizes
-    const uint64_t nw = wBases[n];
-    const size_t wvb = 3 * sizeof(float) * nw;
-    if (meshArena.bytes() < 2 * vb + tb + 2 * wvb) {  // grow, keeping the soup
-        DeviceBuffer grown(2 * vb + tb + 2 * wvb);
-        hipCheck(hipMemcpyAsync(grown.data(), meshArena.data(), 2 * vb + tb, hipMemcpyDeviceToDevice, main.get()),
-                 "mesh arena grow");
-        main.waitForCompletion();
-        meshArena = std::move(grown);
-        vDev = meshArena.as<float>();
-        nDev = vDev + 3 * nv;
-        tDev = reinterpret_cast<int32_t*>(nDev + 3 * nv);
+    std::vector<MeshFilter> filters(n);
+    for (int k = 0; k < n; ++k) filters[k] = meshFilterFor(ids[k]);
+    MeshPost::Request req;
+    req.filter = meshFilterActive();
+    req.simplify = meshSimplifyActive();
+    req.perModel = filters.data();
+    const MeshPost::Result r = meshPost.run(
+        main, MeshPost::Soup{vDev, nDev, tDev, colorOn ? cDev.as<uint8_t>() : nullptr, meshKeysDev.as<uint64_t>(), nv, nt},
+        MeshPost::Table{n, basesDev, bases}, req, "EMFusion::extractMeshes");
+    for (int k = 0; k < n; ++k) {
+        if (req.filter) meshFilterStats[ids[k]] = r.filterStats[k];
+        if (req.simplify) meshSimplifyStats[ids[k]] = r.simplifyStats[k];
     }
-    float* wvDev = reinterpret_cast<float*>(reinterpret_cast<char*>(meshArena.data()) + 2 * vb + tb);
-    float* wnDev = wvDev + 3 * nw;
-    if (colorOn) wcDev = DeviceBuffer(3 * nw);
-    emfCheck(emf_hip_meshWeldEmitBatched(weldScratch, nv, nt, basesDev, wBasesDev, n, vDev, nDev,
-                                         colorOn ? cDev.as<uint8_t>() : nullptr, tDev, wvDev, wnDev,
-                                         colorOn ? wcDev.as<uint8_t>() : nullptr, tDev, main.abi()),
-             "meshWeldEmitBatched");
-    // what travels: the welded arrays, or the filter's kept arrays
-    struct Slice {
-        size_t v0, vc, t0, tc;
-    };
-    std::vector<Slice> slices(n);
-    for (int k = 0; k < n; ++k) slices[k] = Slice{wBases[k], wCounts[k], bases[2 * k + 1], counts[k].triangles};
-    const float* outV = wvDev;
-    const float* outN = wnDev;
-    const int32_t* outT = tDev;
-    const uint8_t* outC = colorOn ? wcDev.as<uint8_t>() : nullptr;
-    uint64_t outNv = nw, outNt = nt;
-    DeviceBuffer kcDev;
-    if (meshFilterActive()) {
-        const size_t ccBytes = emf_hip_meshComponentsScratchBytes(nw, nt);
-        if (ccBytes == 0) throw HipError("EMFusion::extractMeshes: " + std::to_string(nw) + " welded vertices", EMF_E_LIMIT);
-        // [kept bases u64 x 2 (MAX + 1)][kept counts u32 x 2 MAX][components u32 x MAX][kept components u32 x MAX][scratch]
-        const size_t kbBytes = sizeof(uint64_t) * 2 * (EMF_MAX_MODELS + 1), kcBytes = sizeof(uint32_t) * 2 * EMF_MAX_MODELS,
-                     cBytes = sizeof(uint32_t) * EMF_MAX_MODELS, head = kbBytes + kcBytes + 2 * cBytes;
-        if (meshFilterScratch.bytes() < head + ccBytes) meshFilterScratch = DeviceBuffer(head + ccBytes);
-        auto* kBasesDev = meshFilterScratch.as<uint64_t>();
-        auto* kCountsDev = reinterpret_cast<uint32_t*>(kBasesDev + 2 * (EMF_MAX_MODELS + 1));
-        uint32_t* compsDev = kCountsDev + 2 * EMF_MAX_MODELS;
-        uint32_t* kCompsDev = compsDev + EMF_MAX_MODELS;
-        void* ccScratch = reinterpret_cast<char*>(meshFilterScratch.data()) + head;
-        std::vector<uint32_t> mins(n, meshMinTriangles);
-        std::vector<uint8_t> largest(n);
-        for (int k = 0; k < n; ++k) largest[k] = meshFilterFor(ids[k]).largestOnly ? 1 : 0;
-        emfCheck(emf_hip_meshComponentsLabelBatched(tDev, nw, nt, basesDev, wBasesDev, n, ccScratch, nullptr, nullptr,
-                                                    main.abi()),
-                 "meshComponentsLabelBatched");
-        emfCheck(emf_hip_meshComponentsFilterCountBatched(tDev, nw, nt, basesDev, wBasesDev, n, ccScratch, mins.data(),
-                                                          largest.data(), kCountsDev, kBasesDev, compsDev, kCompsDev,
-                                                          main.abi()),
-                 "meshComponentsFilterCountBatched");
-        std::vector<uint64_t> kBases(2 * (n + 1));
-        std::vector<uint32_t> kCounts(2 * n), comps(n), kComps(n);
-        hipCheck(hipMemcpyAsync(kBases.data(), kBasesDev, sizeof(uint64_t) * 2 * (n + 1), hipMemcpyDeviceToHost, main.get()),
-                 "kept bases D2H");
-        hipCheck(hipMemcpyAsync(kCounts.data(), kCountsDev, sizeof(uint32_t) * 2 * n, hipMemcpyDeviceToHost, main.get()),
-                 "kept counts D2H");
-        hipCheck(hipMemcpyAsync(comps.data(), compsDev, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, main.get()),
-                 "components D2H");
-        hipCheck(hipMemcpyAsync(kComps.data(), kCompsDev, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, main.get()),
-                 "kept components D2H");
-        emfCheck(emf_hip_meshComponentsStatus(ccScratch, nw, nt, main.abi()), "meshComponents (indices)");  // waits
-        const uint64_t knv = kBases[2 * n], knt = kBases[2 * n + 1];
-        const size_t kvb = 3 * sizeof(float) * std::max<uint64_t>(knv, 1), ktb = 4 * sizeof(int32_t) * std::max<uint64_t>(knt, 1);
-        if (meshFilterArena.bytes() < 2 * kvb + ktb) meshFilterArena = DeviceBuffer(2 * kvb + ktb);
-        float* kvDev = meshFilterArena.as<float>();
-        float* knDev = kvDev + 3 * std::max<uint64_t>(knv, 1);
-        int32_t* ktDev = reinterpret_cast<int32_t*>(knDev + 3 * std::max<uint64_t>(knv, 1));
-        if (colorOn) kcDev = DeviceBuffer(3 * std::max<uint64_t>(knv, 1));
-        emfCheck(emf_hip_meshComponentsEmitBatched(ccScratch, nw, nt, basesDev, wBasesDev, n, wvDev, wnDev, outC, tDev, kvDev,
-                                                   knDev, colorOn ? kcDev.as<uint8_t>() : nullptr, ktDev, main.abi()),
-                 "meshComponentsEmitBatched");
-        for (int k = 0; k < n; ++k) {
-            meshFilterStats[ids[k]] = MeshFilterStats{comps[k], kComps[k], counts[k].triangles, kCounts[2 * k + 1], {}};
-            slices[k] = Slice{kBases[2 * k], kCounts[2 * k], kBases[2 * k + 1], kCounts[2 * k + 1]};
-        }
-        outV = kvDev;
-        outN = knDev;
-        outT = ktDev;
-        outC = colorOn ? kcDev.as<uint8_t>() : nullptr;
-        outNv = knv;
-        outNt = knt;
-    }
-    DeviceBuffer scDev;
-    if (meshSimplifyActive() && outNv == 0) {
-        for (int k = 0; k < n; ++k) meshSimplifyStats[ids[k]] = MeshSimplifyStats{};
-    } else if (meshSimplifyActive()) {
-        const size_t spBytes = emf_hip_meshSimplifyScratchBytes(outNv, outNt);
-        if (spBytes == 0) throw HipError("EMFusion::extractMeshes: " + std::to_string(outNv) + " vertices to simplify", EMF_E_LIMIT);
-        // [triangle bases u64 x 2 (MAX + 1)][vertex bases u64 x (MAX + 1)][kept bases u64 x 2 (MAX + 1)]
-        // [kept counts u32 x 2 MAX][clusters u32 x MAX][scratch]
-        const size_t tbBytes = sizeof(uint64_t) * 2 * (EMF_MAX_MODELS + 1), vbBytes = sizeof(uint64_t) * (EMF_MAX_MODELS + 1),
-                     kcBytes = sizeof(uint32_t) * 2 * EMF_MAX_MODELS, clBytes = sizeof(uint32_t) * EMF_MAX_MODELS,
-                     head = 2 * tbBytes + vbBytes + kcBytes + clBytes;
-        if (meshSimplifyScratch.bytes() < head + spBytes) meshSimplifyScratch = DeviceBuffer(head + spBytes);
-        auto* tBasesDev = meshSimplifyScratch.as<uint64_t>();
-        auto* vBasesDev = tBasesDev + 2 * (EMF_MAX_MODELS + 1);
-        auto* sBasesDev = vBasesDev + (EMF_MAX_MODELS + 1);
-        auto* sCountsDev = reinterpret_cast<uint32_t*>(sBasesDev + 2 * (EMF_MAX_MODELS + 1));
-        uint32_t* clustersDev = sCountsDev + 2 * EMF_MAX_MODELS;
-        void* spScratch = reinterpret_cast<char*>(meshSimplifyScratch.data()) + head;
-        // the bases of what the weld (or the filter) left, in the layout the entries take
-        std::vector<uint64_t> tBases(2 * (n + 1), 0), vBases(n + 1, 0);
-        for (int k = 0; k < n; ++k) {
-            vBases[k] = slices[k].v0;
-            tBases[2 * k] = slices[k].v0;
-            tBases[2 * k + 1] = slices[k].t0;
-        }
-        vBases[n] = tBases[2 * n] = outNv;
-        tBases[2 * n + 1] = outNt;
-        hipCheck(hipMemcpyAsync(tBasesDev, tBases.data(), sizeof(uint64_t) * 2 * (n + 1), hipMemcpyHostToDevice, main.get()),
-                 "simplify triangle bases upload");
-        hipCheck(hipMemcpyAsync(vBasesDev, vBases.data(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, main.get()),
-                 "simplify vertex bases upload");
-        const std::vector<float> cells(n, meshSimplifyCell);
-        emfCheck(emf_hip_meshSimplifyCount(outV, outN, outC, outT, outNv, outNt, tBasesDev, vBasesDev, n, cells.data(), nullptr,
-                                           spScratch, sCountsDev, sBasesDev, clustersDev, main.abi()),
-                 "meshSimplifyCount");
-        std::vector<uint64_t> sBases(2 * (n + 1));
-        std::vector<uint32_t> sCounts(2 * n), clusters(n);
-        hipCheck(hipMemcpyAsync(sBases.data(), sBasesDev, sizeof(uint64_t) * 2 * (n + 1), hipMemcpyDeviceToHost, main.get()),
-                 "simplified bases D2H");
-        hipCheck(hipMemcpyAsync(sCounts.data(), sCountsDev, sizeof(uint32_t) * 2 * n, hipMemcpyDeviceToHost, main.get()),
-                 "simplified counts D2H");
-        hipCheck(hipMemcpyAsync(clusters.data(), clustersDev, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, main.get()),
-                 "clusters D2H");
-        emfCheck(emf_hip_meshSimplifyStatus(spScratch, outNv, outNt, main.abi()), "meshSimplify");  // waits; the uploads too
-        const uint64_t snv = sBases[2 * n], snt = sBases[2 * n + 1];
-        const size_t svb = 3 * sizeof(float) * std::max<uint64_t>(snv, 1), stb = 4 * sizeof(int32_t) * std::max<uint64_t>(snt, 1);
-        if (meshSimplifyArena.bytes() < 2 * svb + stb) meshSimplifyArena = DeviceBuffer(2 * svb + stb);
-        float* svDev = meshSimplifyArena.as<float>();
-        float* snDev = svDev + 3 * std::max<uint64_t>(snv, 1);
-        int32_t* stDev = reinterpret_cast<int32_t*>(snDev + 3 * std::max<uint64_t>(snv, 1));
-        if (colorOn) scDev = DeviceBuffer(3 * std::max<uint64_t>(snv, 1));
-        emfCheck(emf_hip_meshSimplifyEmit(spScratch, outNv, outNt, tBasesDev, vBasesDev, n, outV, outN, outC, outT, svDev, snDev,
-                                          colorOn ? scDev.as<uint8_t>() : nullptr, stDev, main.abi()),
-                 "meshSimplifyEmit");
-        for (int k = 0; k < n; ++k) {
-            meshSimplifyStats[ids[k]] = MeshSimplifyStats{static_cast<uint32_t>(slices[k].vc), static_cast<uint32_t>(slices[k].tc),
-                                                          sCounts[2 * k], sCounts[2 * k + 1], clusters[k]};
-            slices[k] = Slice{sBases[2 * k], sCounts[2 * k], sBases[2 * k + 1], sCounts[2 * k + 1]};
-        }
-        outV = svDev;
-        outN = snDev;
-        outT = stDev;
-        outC = colorOn ? scDev.as<uint8_t>() : nullptr;
-        outNv = snv;
-        outNt = snt;
-    }
-    const size_t ovb = 3 * sizeof(float) * outNv;
-    meshStage.grow(2 * ovb + 4 * sizeof(int32_t) * std::max<uint64_t>(outNt, 1));
-    float* vHost = meshStage.as<float>();
-    float* nHost = vHost + 3 * outNv;
-    int32_t* tHost = reinterpret_cast<int32_t*>(nHost + 3 * outNv);
-    if (outNv) {
-        hipCheck(hipMemcpyAsync(vHost, outV, ovb, hipMemcpyDeviceToHost, main.get()), "welded vertices D2H");
-        hipCheck(hipMemcpyAsync(nHost, outN, ovb, hipMemcpyDeviceToHost, main.get()), "welded normals D2H");
-    }
-    if (outNt) hipCheck(hipMemcpyAsync(tHost, outT, 4 * sizeof(int32_t) * outNt, hipMemcpyDeviceToHost, main.get()), "welded triangles D2H");
-    std::vector<uint8_t> cHost;
-    if (colorOn && outNv) {
-        cHost.resize(3 * outNv);
-        hipCheck(hipMemcpyAsync(cHost.data(), outC, 3 * outNv, hipMemcpyDeviceToHost, main.get()), "welded colours D2H");
-    }
-    main.waitForCompletion();
-    for (int k = 0; k < n; ++k) {  // model k's slice is its own welded (filtered) mesh (local triangle indices)
-        const Slice& s = slices[k];
-        Mesh& m = out[k];
-        m.cloud.assign(vHost + 3 * s.v0, vHost + 3 * (s.v0 + s.vc));
-        m.normals.assign(nHost + 3 * s.v0, nHost + 3 * (s.v0 + s.vc));
-        m.polygons.assign(tHost + 4 * s.t0, tHost + 4 * (s.t0 + s.tc));
-        if (!cHost.empty()) m.colors.assign(cHost.begin() + 3 * s.v0, cHost.begin() + 3 * (s.v0 + s.vc));
-    }
+    meshPost.download(main, r.mesh, r.slices, out.data());
 }
 
 // EMFusion.cpp:110-125 (exp_frame_meshes): the background and every live object not hidden by ignore_person, meshed

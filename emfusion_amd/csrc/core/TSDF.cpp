@@ -1,6 +1,7 @@
 // TSDF.cpp -- emf::TSDF over the emf_hip_* C ABI (see TSDF.hpp).
 #include "TSDF.hpp"
 
+#include "MeshPost.hpp"
 #include "Switches.hpp"
 #include "TileStore.hpp"
 
@@ -478,135 +479,32 @@ Mesh TSDF::extractMesh(const uint8_t* fgVolMask, bool weld, const MeshFilter* fi
 }
 
 // What every mesher here does with its soup on the device (vertices, normals, triangles, colours or an empty buffer,
-// and with `weld` one u64 grid-edge key per vertex): weld, label / filter by component, and bring to the host only
-// what is left.  mesh: the empty result with its `colored` flag set.
+// and with `weld` one u64 grid-edge key per vertex): the chain of MeshPost.hpp for one model on the null stream, and
+// only what is left comes to the host.  mesh: the empty result with its `colored` flag set.  The chain's buffers and
+// the soup's live until this function returns, behind the download's wait: nothing in between waits for the stream
+// but the Status calls that read the sizes.
 Mesh TSDF::finishMesh(Mesh mesh, emf_mesh_counts_t counts, DeviceBuffer v, DeviceBuffer n, DeviceBuffer t, DeviceBuffer c,
                       DeviceBuffer keys, bool weld, const MeshFilter* filter, MeshFilterStats* stats,
                       MeshComponents* components) {
     Stream& s = Stream::Null();
-    const size_t soup = counts.vertices;
+    MeshPost post;
+    DeviceMesh left{v.as<float>(), n.as<float>(), t.as<int32_t>(), c.empty() ? nullptr : c.as<uint8_t>(), counts.vertices,
+                    counts.triangles};
+    std::vector<MeshSlice> slices{MeshSlice{0, counts.vertices, 0, counts.triangles}};
     if (weld) {
-        const size_t weldBytes = emf_hip_meshWeldScratchBytes(soup);
-        if (weldBytes == 0) throw HipError("TSDF::getWeldedMesh: " + std::to_string(soup) + " soup vertices", EMF_E_LIMIT);
-        DeviceBuffer weldScratch(weldBytes), weldedDev(sizeof(uint32_t));
-        emfCheck(emf_hip_meshWeldCount(keys.as<uint64_t>(), soup, weldScratch.data(), weldedDev.as<uint32_t>(), s.abi()),
-                 "TSDF::getWeldedMesh (count)");
-        uint32_t welded = 0;
-        weldedDev.download(&welded, s);
-        emfCheck(emf_hip_meshWeldStatus(weldScratch.data(), soup, s.abi()), "TSDF::getWeldedMesh (table)");
-        DeviceBuffer wv(size_t(welded) * 3 * sizeof(float)), wn(size_t(welded) * 3 * sizeof(float)), wc;
-        if (!c.empty()) wc = DeviceBuffer(size_t(welded) * 3);
-        emfCheck(emf_hip_meshWeldEmit(weldScratch.data(), soup, counts.triangles, v.as<float>(), n.as<float>(),
-                                      c.empty() ? nullptr : c.as<uint8_t>(), t.as<int32_t>(), wv.as<float>(),
-                                      wn.as<float>(), wc.empty() ? nullptr : wc.as<uint8_t>(), t.as<int32_t>(), s.abi()),
-                 "TSDF::getWeldedMesh (emit)");
-        s.waitForCompletion();  // the scratch and the soup arrays go out of scope below
-        v = std::move(wv);
-        n = std::move(wn);
-        if (!c.empty()) c = std::move(wc);
-        counts.vertices = welded;
-        const bool filtering = filter && filter->active();
-        if (filtering || components) {
-            const uint64_t nw = welded, nt = counts.triangles;
-            const size_t ccBytes = emf_hip_meshComponentsScratchBytes(nw, nt);
-            if (ccBytes == 0) throw HipError("TSDF::getFilteredMesh: " + std::to_string(nw) + " welded vertices", EMF_E_LIMIT);
-            DeviceBuffer ccScratch(ccBytes), labelsDev, sizesDev;
-            if (components) {
-                labelsDev = DeviceBuffer(std::max<size_t>(nw, 1) * sizeof(int32_t));
-                sizesDev = DeviceBuffer(std::max<size_t>(nw, 1) * sizeof(uint32_t));
-            }
-            emfCheck(emf_hip_meshComponentsLabel(t.as<int32_t>(), nw, nt, ccScratch.data(),
-                                                 components ? labelsDev.as<int32_t>() : nullptr,
-                                                 components ? sizesDev.as<uint32_t>() : nullptr, s.abi()),
-                     "TSDF::getFilteredMesh (label)");
-            if (components) {
-                emfCheck(emf_hip_meshComponentsStatus(ccScratch.data(), nw, nt, s.abi()), "TSDF::getMeshComponents");
-                components->labels.resize(nw);
-                components->sizes.resize(nw);
-                if (nw) {
-                    hipCheck(hipMemcpy(components->labels.data(), labelsDev.data(), nw * sizeof(int32_t), hipMemcpyDeviceToHost),
-                             "labels D2H");
-                    hipCheck(hipMemcpy(components->sizes.data(), sizesDev.data(), nw * sizeof(uint32_t), hipMemcpyDeviceToHost),
-                             "sizes D2H");
-                }
-            }
-            if (filtering) {
-                const uint32_t minTriangles = filter->minTriangles;
-                const uint8_t largestOnly = filter->largestOnly ? 1 : 0;
-                DeviceBuffer outDev(4 * sizeof(uint32_t));  // kept vertices, kept triangles, components, kept components
-                uint32_t* o = outDev.as<uint32_t>();
-                emfCheck(emf_hip_meshComponentsFilterCount(t.as<int32_t>(), nw, nt, ccScratch.data(), &minTriangles,
-                                                           &largestOnly, o, o + 2, o + 3, s.abi()),
-                         "TSDF::getFilteredMesh (count)");
-                uint32_t kept[4] = {0, 0, 0, 0};
-                outDev.download(kept, s);
-                emfCheck(emf_hip_meshComponentsStatus(ccScratch.data(), nw, nt, s.abi()), "TSDF::getFilteredMesh (indices)");
-                DeviceBuffer kv(std::max<size_t>(kept[0], 1) * 3 * sizeof(float)), kn(std::max<size_t>(kept[0], 1) * 3 * sizeof(float)),
-                    kt(std::max<size_t>(kept[1], 1) * 4 * sizeof(int32_t)), kc;
-                if (!c.empty()) kc = DeviceBuffer(std::max<size_t>(kept[0], 1) * 3);
-                emfCheck(emf_hip_meshComponentsEmit(ccScratch.data(), nw, nt, v.as<float>(), n.as<float>(),
-                                                    c.empty() ? nullptr : c.as<uint8_t>(), t.as<int32_t>(), kv.as<float>(),
-                                                    kn.as<float>(), kc.empty() ? nullptr : kc.as<uint8_t>(),
-                                                    kt.as<int32_t>(), s.abi()),
-                         "TSDF::getFilteredMesh (emit)");
-                s.waitForCompletion();  // the scratch and the welded arrays go out of scope below
-                if (stats) *stats = MeshFilterStats{kept[2], kept[3], counts.triangles, kept[1], {}};
-                v = std::move(kv);
-                n = std::move(kn);
-                t = std::move(kt);
-                if (!c.empty()) c = std::move(kc);
-                counts.vertices = kept[0];
-                counts.triangles = kept[1];
-                if (kept[0] == 0) return mesh;  // nothing kept: an empty mesh (the buffers above hold one spare element)
-            }
-        }
-        if (filter && filter->simplifying()) {  // clustered by cell behind the filter: only the simplified arrays travel
-            const uint64_t nv = counts.vertices, nt = counts.triangles;
-            const size_t spBytes = emf_hip_meshSimplifyScratchBytes(nv, nt);
-            if (spBytes == 0) throw HipError("TSDF::getFilteredMesh: " + std::to_string(nv) + " vertices to simplify", EMF_E_LIMIT);
-            DeviceBuffer spScratch(spBytes), outDev(4 * sizeof(uint32_t));  // kept vertices, kept triangles, clusters
-            uint32_t* o = outDev.as<uint32_t>();
-            const float cell = filter->simplifyCell;
-            const uint8_t* cIn = c.empty() ? nullptr : c.as<uint8_t>();
-            emfCheck(emf_hip_meshSimplifyCount(v.as<float>(), n.as<float>(), cIn, t.as<int32_t>(), nv, nt, nullptr, nullptr, 1,
-                                               &cell, nullptr, spScratch.data(), o, nullptr, o + 2, s.abi()),
-                     "TSDF::getFilteredMesh (simplify count)");
-            uint32_t kept[4] = {0, 0, 0, 0};
-            outDev.download(kept, s);
-            emfCheck(emf_hip_meshSimplifyStatus(spScratch.data(), nv, nt, s.abi()), "TSDF::getFilteredMesh (simplify)");
-            DeviceBuffer sv(std::max<size_t>(kept[0], 1) * 3 * sizeof(float)), sn(std::max<size_t>(kept[0], 1) * 3 * sizeof(float)),
-                st(std::max<size_t>(kept[1], 1) * 4 * sizeof(int32_t)), sc;
-            if (cIn) sc = DeviceBuffer(std::max<size_t>(kept[0], 1) * 3);
-            emfCheck(emf_hip_meshSimplifyEmit(spScratch.data(), nv, nt, nullptr, nullptr, 1, v.as<float>(), n.as<float>(), cIn,
-                                              t.as<int32_t>(), sv.as<float>(), sn.as<float>(),
-                                              cIn ? sc.as<uint8_t>() : nullptr, st.as<int32_t>(), s.abi()),
-                     "TSDF::getFilteredMesh (simplify emit)");
-            s.waitForCompletion();  // the scratch and the input arrays go out of scope below
-            if (stats)
-                stats->simplify = MeshSimplifyStats{static_cast<uint32_t>(nv), static_cast<uint32_t>(nt), kept[0], kept[1], kept[2]};
-            v = std::move(sv);
-            n = std::move(sn);
-            t = std::move(st);
-            if (cIn) c = std::move(sc);
-            counts.vertices = kept[0];
-            counts.triangles = kept[1];
-            if (kept[0] == 0) return mesh;
-        }
+        MeshPost::Request req;
+        req.filter = filter && filter->active();
+        req.simplify = filter && filter->simplifying();  // clustered by cell behind the filter
+        req.perModel = filter;
+        req.components = components;
+        MeshPost::Result r = post.run(s, MeshPost::Soup{left.v, left.n, t.as<int32_t>(), left.c, keys.as<uint64_t>(), left.nv, left.nt},
+                                      MeshPost::Table{1, nullptr, nullptr}, req, "TSDF::getWeldedMesh");
+        if (stats && req.filter) *stats = r.filterStats[0];
+        if (stats && req.simplify) stats->simplify = r.simplifyStats[0];
+        left = r.mesh;
+        slices = r.slices;
     }
-    mesh.cloud.resize(size_t(counts.vertices) * 3);
-    mesh.normals.resize(size_t(counts.vertices) * 3);
-    mesh.polygons.resize(static_cast<size_t>(counts.triangles) * 4);
-    v.download(mesh.cloud.data(), s);
-    n.download(mesh.normals.data(), s);
-    if (!c.empty()) {
-        mesh.colors.resize(static_cast<size_t>(counts.vertices) * 3);
-        c.download(mesh.colors.data(), s);
-    }
-    if (counts.triangles) {
-        std::vector<int32_t> all(std::max<size_t>(counts.triangles, 1) * 4);
-        t.download(all.data(), s);
-        mesh.polygons.assign(all.begin(), all.begin() + static_cast<size_t>(counts.triangles) * 4);
-    }
+    post.download(s, left, slices, &mesh);
     return mesh;
 }
 

@@ -425,16 +425,6 @@ int check_size(const int32_t size[3], const char* what) {
     return EMF_OK;
 }
 
-int memset_async(void* p, size_t bytes, hipStream_t stream, const char* what) {
-    const hipError_t e = hipMemsetAsync(p, 0, bytes, stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("%s: memset: %s", what, hipGetErrorString(e));
-        return static_cast<int>(e);
-    }
-    return EMF_OK;
-}
-
 }  // namespace
 }  // namespace emf_hip
 
@@ -453,7 +443,7 @@ int emf_hip_frontierLabel(const uint8_t* classes, const int32_t size[3], const i
     const unsigned n = static_cast<unsigned>(rows * nx), blocks = ceil_div(n, kFrBlock);
     const hipStream_t s = as_stream(stream);
     unsigned* parent = reinterpret_cast<unsigned*>(labels);
-    EMF_TRY(memset_async(counters, 3 * sizeof(uint32_t), s, "frontierLabel"));
+    EMF_TRY(memset_async(counters, 0, 3 * sizeof(uint32_t), stream, "frontierLabel"));
     hipLaunchKernelGGL(k_fr_flags, dim3(ceil_div(rows, 4)), dim3(256), 0, s, classes, d2, min_d2, parent,
                        counters + EMF_FRONTIER_VOXELS, nx, ny, nz);
     hipLaunchKernelGGL(k_fr_hook, dim3(blocks), dim3(kFrBlock), 0, s, parent, nx, ny, nz);
@@ -488,7 +478,7 @@ int emf_hip_frontierClusters(const int32_t* labels, const int32_t size[3], int32
         (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) || (reinterpret_cast<uintptr_t>(records) & 7u))
         return fail(EMF_E_ARG, "frontierClusters: misaligned arrays");
     const hipStream_t s = as_stream(stream);
-    if (n_clusters == 0) return memset_async(counters + EMF_FRONTIER_KEPT, sizeof(uint32_t), s, "frontierClusters");
+    if (n_clusters == 0) return memset_async(counters + EMF_FRONTIER_KEPT, 0, sizeof(uint32_t), stream, "frontierClusters");
     FrArgs a;
     place(a, size, n_clusters, scratch_dev);
     const unsigned* parent = reinterpret_cast<const unsigned*>(labels);

@@ -23,15 +23,14 @@
 //   k_cc_select   per root: atomicMax(best[model], size << 32 | ~label) -- the largest component, ties to the
 //                 smaller label
 //   k_cc_flags    keep flags of vertex i and triangle i, summed per workgroup; roots count the model's components
-//   k_cc_scan     two workgroups: the exclusive scans of the two sums arrays (wave_ops.hpp)
+//   k_sums_scan   two workgroups: the exclusive scans of the two sums arrays (mesh_table.hpp)
 //   k_cc_rank     vexcl[i], texcl[i] = kept vertices / triangles before i; per-model kept counts and bases are the
 //                 ranks at the models' bases
 //   k_cc_emit     kept vertices copy position, normal and colour to their rank; kept triangles are rewritten
 // A triangle index outside its model's welded range is never dereferenced: the triangle joins nothing, counts
 // nowhere, is dropped by the filter, and raises `flag` (emf_hip_meshComponentsStatus -> EMF_E_ARG).
 // All atomics are ordinary global atomics on vector memory; every output is a pure function of the index buffer.
-#include "common.hpp"
-#include "wave_ops.hpp"
+#include "mesh_table.hpp"
 #include "union_find.hpp"
 
 namespace emf_hip {
@@ -39,18 +38,13 @@ namespace {
 
 constexpr int kCcBlock = kScanBlock;
 
-struct CcArgs {
+struct CcArgs : Compaction {
     unsigned* parent;
     unsigned* size;
-    unsigned* vexcl;
-    unsigned* texcl;
-    unsigned* vsums;  // vblocks + 1
-    unsigned* tsums;  // tblocks + 1
     unsigned long long* best;  // EMF_MAX_MODELS
     unsigned* ncomp;           // EMF_MAX_MODELS
     unsigned* nkept;           // EMF_MAX_MODELS
     unsigned* flag;
-    unsigned nv, nt, vblocks, tblocks;
 };
 
 inline size_t place(CcArgs& a, unsigned long long nv, unsigned long long nt, void* scratch) {
@@ -72,62 +66,11 @@ inline size_t place(CcArgs& a, unsigned long long nv, unsigned long long nt, voi
     return s.off;
 }
 
-// the models of a table launch (device arrays as the weld leaves them) or, for one model, none
-struct CcModels {
-    const unsigned long long* soupBases;    // 2 (n + 1) interleaved: the triangle bases are the odd entries
-    const unsigned long long* weldedBases;  // n + 1
-    unsigned n;
-};
-
 // each model's criteria, by value: the host arrays need not outlive the call
 struct CcCriteria {
     unsigned minTriangles[EMF_MAX_MODELS];
     unsigned char largestOnly[EMF_MAX_MODELS];
 };
-
-// the last model whose base is <= x (empty models share a base with their successor: the one that holds x wins)
-__device__ __forceinline__ unsigned model_of(const unsigned long long* bases, unsigned stride, unsigned n,
-                                             unsigned long long x) {
-    unsigned lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (x >= bases[stride * mid]) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-struct Range {
-    unsigned model, lo, hi;  // the model's welded vertices are [lo, hi)
-};
-
-__device__ __forceinline__ Range range_of_vertex(const CcArgs& a, const CcModels& md, unsigned g) {
-    if (!md.weldedBases) return Range{0u, 0u, a.nv};
-    const unsigned m = model_of(md.weldedBases, 1, md.n, g);
-    return Range{m, static_cast<unsigned>(md.weldedBases[m]), static_cast<unsigned>(md.weldedBases[m + 1])};
-}
-
-__device__ __forceinline__ Range range_of_triangle(const CcArgs& a, const CcModels& md, unsigned t) {
-    if (!md.weldedBases) return Range{0u, 0u, a.nv};
-    const unsigned m = model_of(md.soupBases + 1, 2, md.n, t);
-    return Range{m, static_cast<unsigned>(md.weldedBases[m]), static_cast<unsigned>(md.weldedBases[m + 1])};
-}
-
-// the global welded indices of triangle t's corners; false (and nothing to dereference) if one lies outside its
-// model's welded range or past the scratch
-__device__ __forceinline__ bool corners(const CcArgs& a, const Range& r, const int32_t* tris, unsigned t,
-                                        unsigned g[3]) {
-    const int32_t* ti = tris + 4 * static_cast<size_t>(t);
-    const unsigned hi = r.hi < a.nv ? r.hi : a.nv;
-    bool ok = r.lo <= hi;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const unsigned long long x = static_cast<unsigned long long>(r.lo) + static_cast<unsigned>(ti[1 + j]);
-        ok = ok && ti[1 + j] >= 0 && x < hi;
-        g[j] = static_cast<unsigned>(x);
-    }
-    return ok;
-}
 
 // (find_root / unite: union_find.hpp, shared with motion_masks.hip)
 
@@ -139,11 +82,11 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_init(const CcArgs a) {
     }
 }
 
-__global__ __launch_bounds__(kCcBlock) void k_cc_hook(const CcArgs a, const CcModels md, const int32_t* tris) {
+__global__ __launch_bounds__(kCcBlock) void k_cc_hook(const CcArgs a, const MeshTable md, const int32_t* tris) {
     const unsigned t = blockIdx.x * kCcBlock + threadIdx.x;
     if (t >= a.nt) return;
     unsigned g[3];
-    if (!corners(a, range_of_triangle(a, md, t), tris, t, g)) {
+    if (!corners(a.nv, range_of_triangle(a.nv, md, t), tris, t, g)) {
         atomicOr(a.flag, 1u);
         return;
     }
@@ -160,7 +103,7 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_flatten(const CcArgs a) {
 
 // On a real mesh nearly every triangle belongs to one giant component, and one add per triangle would serialise on
 // one address.  A wave whose live lanes share a root adds once; the workgroup's uniform waves are merged in LDS.
-__global__ __launch_bounds__(kCcBlock) void k_cc_count(const CcArgs a, const CcModels md, const int32_t* tris) {
+__global__ __launch_bounds__(kCcBlock) void k_cc_count(const CcArgs a, const MeshTable md, const int32_t* tris) {
     __shared__ unsigned wroot[kCcBlock / 64], wcount[kCcBlock / 64];
     const unsigned t = blockIdx.x * kCcBlock + threadIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -168,7 +111,7 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_count(const CcArgs a, const CcM
     bool live = false;
     if (t < a.nt) {
         unsigned g[3];
-        if (corners(a, range_of_triangle(a, md, t), tris, t, g)) {
+        if (corners(a.nv, range_of_triangle(a.nv, md, t), tris, t, g)) {
             root = a.parent[g[0]];
             live = true;
         }
@@ -204,12 +147,12 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_count(const CcArgs a, const CcM
     }
 }
 
-__global__ __launch_bounds__(kCcBlock) void k_cc_labels(const CcArgs a, const CcModels md, int32_t* labels,
+__global__ __launch_bounds__(kCcBlock) void k_cc_labels(const CcArgs a, const MeshTable md, int32_t* labels,
                                                         uint32_t* sizes) {
     const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
     if (i >= a.nv) return;
     const unsigned r = a.parent[i];
-    if (labels) labels[i] = static_cast<int32_t>(r - range_of_vertex(a, md, i).lo);
+    if (labels) labels[i] = static_cast<int32_t>(r - range_of_vertex(a.nv, md, i).lo);
     if (sizes) sizes[i] = a.size[r];
 }
 
@@ -217,10 +160,10 @@ __device__ __forceinline__ unsigned long long pack_best(unsigned size, unsigned 
     return static_cast<unsigned long long>(size) << 32 | static_cast<unsigned>(~label);
 }
 
-__global__ __launch_bounds__(kCcBlock) void k_cc_select(const CcArgs a, const CcModels md) {
+__global__ __launch_bounds__(kCcBlock) void k_cc_select(const CcArgs a, const MeshTable md) {
     const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
     if (i >= a.nv || a.parent[i] != i) return;
-    const Range r = range_of_vertex(a, md, i);
+    const Range r = range_of_vertex(a.nv, md, i);
     atomicMax(a.best + r.model, pack_best(a.size[i], i - r.lo));
 }
 
@@ -231,27 +174,27 @@ __device__ __forceinline__ bool kept(const CcArgs& a, const CcCriteria& c, const
     return !c.largestOnly[r.model] || a.best[r.model] == pack_best(size, root - r.lo);
 }
 
-__device__ __forceinline__ unsigned vertex_flag(const CcArgs& a, const CcModels& md, const CcCriteria& c, unsigned i) {
+__device__ __forceinline__ unsigned vertex_flag(const CcArgs& a, const MeshTable& md, const CcCriteria& c, unsigned i) {
     if (i >= a.nv) return 0u;
-    return kept(a, c, range_of_vertex(a, md, i), a.parent[i]) ? 1u : 0u;
+    return kept(a, c, range_of_vertex(a.nv, md, i), a.parent[i]) ? 1u : 0u;
 }
 
-__device__ __forceinline__ unsigned triangle_flag(const CcArgs& a, const CcModels& md, const CcCriteria& c,
+__device__ __forceinline__ unsigned triangle_flag(const CcArgs& a, const MeshTable& md, const CcCriteria& c,
                                                   const int32_t* tris, unsigned t) {
     if (t >= a.nt) return 0u;
-    const Range r = range_of_triangle(a, md, t);
+    const Range r = range_of_triangle(a.nv, md, t);
     unsigned g[3];
-    if (!corners(a, r, tris, t, g)) return 0u;
+    if (!corners(a.nv, r, tris, t, g)) return 0u;
     return kept(a, c, r, a.parent[g[0]]) ? 1u : 0u;
 }
 
-__global__ __launch_bounds__(kCcBlock) void k_cc_flags(const CcArgs a, const CcModels md, const CcCriteria c,
+__global__ __launch_bounds__(kCcBlock) void k_cc_flags(const CcArgs a, const MeshTable md, const CcCriteria c,
                                                        const int32_t* tris) {
     __shared__ unsigned lds[kCcBlock / 64];
     const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
     const unsigned vf = vertex_flag(a, md, c, i);
     if (i < a.nv && a.parent[i] == i) {  // a root: one component of its model
-        const unsigned m = range_of_vertex(a, md, i).model;
+        const unsigned m = range_of_vertex(a.nv, md, i).model;
         atomicAdd(a.ncomp + m, 1u);
         if (vf) atomicAdd(a.nkept + m, 1u);
     }
@@ -262,16 +205,7 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_flags(const CcArgs a, const CcM
     if (threadIdx.x == 0 && blockIdx.x < a.tblocks) a.tsums[blockIdx.x] = total;
 }
 
-// workgroup 0 scans the vertex sums, workgroup 1 the triangle sums
-__global__ __launch_bounds__(kSumsBlock) void k_cc_scan(const CcArgs a) {
-    __shared__ unsigned lds[kSumsBlock / 64];
-    unsigned* sums = blockIdx.x == 0 ? a.vsums : a.tsums;
-    const unsigned n = blockIdx.x == 0 ? a.vblocks : a.tblocks;
-    const unsigned total = scan_sums(sums, 0u, n, lds);
-    if (threadIdx.x == 0) sums[n] = total;
-}
-
-__global__ __launch_bounds__(kCcBlock) void k_cc_rank(const CcArgs a, const CcModels md, const CcCriteria c,
+__global__ __launch_bounds__(kCcBlock) void k_cc_rank(const CcArgs a, const MeshTable md, const CcCriteria c,
                                                       const int32_t* tris) {
     __shared__ unsigned lds[kCcBlock / 64];
     const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
@@ -280,14 +214,6 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_rank(const CcArgs a, const CcMo
     if (i < a.nv) a.vexcl[i] = a.vsums[blockIdx.x] + vmine;
     const unsigned tmine = block_exclusive_scan<kScanBlock / 64>(triangle_flag(a, md, c, tris, i), total, lds);
     if (i < a.nt) a.texcl[i] = a.tsums[blockIdx.x] + tmine;
-}
-
-// kept vertices before welded vertex b / kept triangles before triangle b (b past the end: all of them)
-__device__ __forceinline__ unsigned vrank_at(const CcArgs& a, unsigned long long b) {
-    return b < a.nv ? a.vexcl[b] : a.vsums[a.vblocks];
-}
-__device__ __forceinline__ unsigned trank_at(const CcArgs& a, unsigned long long b) {
-    return b < a.nt ? a.texcl[b] : a.tsums[a.tblocks];
 }
 
 struct CcCounts {
@@ -299,99 +225,36 @@ struct CcCounts {
 
 // per model: a model's kept vertices and triangles lie in its own ranges, so its kept ranges start at the ranks of
 // its bases
-__global__ __launch_bounds__(kCcBlock) void k_cc_bases(const CcArgs a, const CcModels md, const CcCounts out) {
+__global__ __launch_bounds__(kCcBlock) void k_cc_bases(const CcArgs a, const MeshTable md, const CcCounts out) {
     const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
     if (i > md.n) return;
-    const unsigned long long vlo = md.weldedBases ? md.weldedBases[i] : (i == 0 ? 0ull : a.nv);
-    const unsigned long long tlo = md.weldedBases ? md.soupBases[2 * i + 1] : (i == 0 ? 0ull : a.nt);
-    const unsigned rv = vrank_at(a, vlo), rt = trank_at(a, tlo);
-    if (out.keptBases) {
-        out.keptBases[2 * i] = rv;
-        out.keptBases[2 * i + 1] = rt;
-    }
+    kept_ranges(a, md, i, out.keptCounts, out.keptBases);
     if (i < md.n) {
-        const unsigned long long vhi = md.weldedBases ? md.weldedBases[i + 1] : a.nv;
-        const unsigned long long thi = md.weldedBases ? md.soupBases[2 * i + 3] : a.nt;
-        out.keptCounts[2 * i] = vrank_at(a, vhi) - rv;
-        out.keptCounts[2 * i + 1] = trank_at(a, thi) - rt;
         if (out.components) out.components[i] = a.ncomp[i];
         if (out.keptComponents) out.keptComponents[i] = a.nkept[i];
     }
 }
 
-struct CcEmitArgs {
-    const float* v;
-    const float* nrm;
-    const uint8_t* c;
-    const int32_t* t;
-    float* kv;
-    float* kn;
-    uint8_t* kc;
-    int32_t* kt;
-};
-
-__global__ __launch_bounds__(kCcBlock) void k_cc_emit(const CcArgs a, const CcModels md, const CcEmitArgs e) {
+__global__ __launch_bounds__(kCcBlock) void k_cc_emit(const CcArgs a, const MeshTable md, const MeshArrays e) {
     const unsigned i = blockIdx.x * kCcBlock + threadIdx.x;
     if (i < a.nv) {
         const unsigned r = a.vexcl[i];
-        if (vrank_at(a, static_cast<unsigned long long>(i) + 1) != r) {  // kept: the rank steps behind it
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                e.kv[3 * static_cast<size_t>(r) + j] = e.v[3 * static_cast<size_t>(i) + j];
-                e.kn[3 * static_cast<size_t>(r) + j] = e.nrm[3 * static_cast<size_t>(i) + j];
-            }
-            if (e.c) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) e.kc[3 * static_cast<size_t>(r) + j] = e.c[3 * static_cast<size_t>(i) + j];
-            }
-        }
+        if (a.vrank_at(static_cast<unsigned long long>(i) + 1) != r) copy_vertex(e, i, r);  // kept: the rank steps behind it
     }
-    if (i < a.nt) {
-        const unsigned r = a.texcl[i];
-        if (trank_at(a, static_cast<unsigned long long>(i) + 1) != r) {  // kept, hence inside its model's range
-            const Range m = range_of_triangle(a, md, i);
-            unsigned g[3];
-            if (corners(a, m, e.t, i, g)) {
-                const unsigned base = vrank_at(a, m.lo);
-                int32_t* to = e.kt + 4 * static_cast<size_t>(r);
-                to[0] = 3;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) to[1 + j] = static_cast<int32_t>(a.vexcl[g[j]] - base);
-            }
-        }
-    }
+    rewrite_triangle(a, md, e, i, [&](unsigned g) { return a.vexcl[g]; });
 }
-
-int check_sizes(unsigned long long nv, unsigned long long nt, int n, const char* what) {
-    if (nv > (1ull << 30)) return fail(EMF_E_LIMIT, "%s: %llu welded vertices (at most 2^30)", what, nv);
-    if (nt >= (1ull << 31)) return fail(EMF_E_LIMIT, "%s: %llu triangles (below 2^31)", what, nt);
-    if (n < 1 || n > EMF_MAX_MODELS) return fail(EMF_E_LIMIT, "%s: %d models (1 .. %d per launch)", what, n, EMF_MAX_MODELS);
-    return EMF_OK;
-}
-
-int memset_async(void* p, int v, size_t bytes, emf_stream_t stream, const char* what) {
-    const hipError_t e = hipMemsetAsync(p, v, bytes, as_stream(stream));
-    if (e != hipSuccess) {
-        set_error("%s: memset: %s", what, hipGetErrorString(e));
-        return static_cast<int>(e);
-    }
-    return EMF_OK;
-}
-
-inline unsigned items_blocks(const CcArgs& a) { return a.vblocks > a.tblocks ? a.vblocks : a.tblocks; }
 
 int cc_label(const int32_t* tris, uint64_t nv, uint64_t nt, const uint64_t* soupBases, const uint64_t* weldedBases, int n,
              void* scratch, int32_t* labels, uint32_t* sizes, emf_stream_t stream, const char* what) {
-    EMF_TRY(check_sizes(nv, nt, n, what));
+    EMF_TRY(check_sizes(nv, nt, n, "welded ", what));
     EMF_REQUIRE_PTR(scratch);
     if (nt) EMF_REQUIRE_PTR(tris);
-    if (nv == 0 && nt != 0) return fail(EMF_E_ARG, "%s: %llu triangles over no vertex", what, (unsigned long long)nt);
+    EMF_TRY(check_no_orphans(nv, nt, what));
     CcArgs a;
     place(a, nv, nt, scratch);
     EMF_TRY(memset_async(a.flag, 0, sizeof(unsigned), stream, what));
     if (nv == 0) return EMF_OK;  // nothing to label, no launch
-    const CcModels md{reinterpret_cast<const unsigned long long*>(soupBases),
-                      reinterpret_cast<const unsigned long long*>(weldedBases), static_cast<unsigned>(n)};
+    const MeshTable md = mesh_table(soupBases, weldedBases, n);
     const dim3 block(kCcBlock);
     hipLaunchKernelGGL(k_cc_init, dim3(a.vblocks), block, 0, as_stream(stream), a);
     if (nt) {
@@ -407,11 +270,11 @@ int cc_filter_count(const int32_t* tris, uint64_t nv, uint64_t nt, const uint64_
                     int n, void* scratch, const uint32_t* minTriangles, const uint8_t* largestOnly, uint32_t* keptCounts,
                     uint64_t* keptBases, uint32_t* components, uint32_t* keptComponents, emf_stream_t stream,
                     const char* what) {
-    EMF_TRY(check_sizes(nv, nt, n, what));
+    EMF_TRY(check_sizes(nv, nt, n, "welded ", what));
     EMF_REQUIRE_PTR(scratch);
     EMF_REQUIRE_PTR(keptCounts);
     if (nt) EMF_REQUIRE_PTR(tris);
-    if (nv == 0 && nt != 0) return fail(EMF_E_ARG, "%s: %llu triangles over no vertex", what, (unsigned long long)nt);
+    EMF_TRY(check_no_orphans(nv, nt, what));
     if (nv == 0) {  // empty meshes: zero counts, zero bases, no launch
         EMF_TRY(memset_async(keptCounts, 0, sizeof(uint32_t) * 2 * n, stream, what));
         if (keptBases) EMF_TRY(memset_async(keptBases, 0, sizeof(uint64_t) * 2 * (n + 1), stream, what));
@@ -428,44 +291,29 @@ int cc_filter_count(const int32_t* tris, uint64_t nv, uint64_t nt, const uint64_
     }
     // best, components and kept components are contiguous
     EMF_TRY(memset_async(a.best, 0, reinterpret_cast<char*>(a.flag) - reinterpret_cast<char*>(a.best), stream, what));
-    const CcModels md{reinterpret_cast<const unsigned long long*>(soupBases),
-                      reinterpret_cast<const unsigned long long*>(weldedBases), static_cast<unsigned>(n)};
+    const MeshTable md = mesh_table(soupBases, weldedBases, n);
     const CcCounts out{keptCounts, reinterpret_cast<unsigned long long*>(keptBases), components, keptComponents};
     const dim3 block(kCcBlock), items(items_blocks(a));
     hipLaunchKernelGGL(k_cc_select, dim3(a.vblocks), block, 0, as_stream(stream), a, md);
     hipLaunchKernelGGL(k_cc_flags, items, block, 0, as_stream(stream), a, md, c, tris);
-    hipLaunchKernelGGL(k_cc_scan, dim3(2), dim3(kSumsBlock), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(k_sums_scan, dim3(2), dim3(kSumsBlock), 0, as_stream(stream),
+                       SumsArrays{a.vsums, a.tsums, nullptr, a.vblocks, a.tblocks, 0u});
     hipLaunchKernelGGL(k_cc_rank, items, block, 0, as_stream(stream), a, md, c, tris);
     hipLaunchKernelGGL(k_cc_bases, dim3(ceil_div(n + 1, kCcBlock)), block, 0, as_stream(stream), a, md, out);
     return launch_status(what);
 }
 
 int cc_emit(const void* scratch, uint64_t nv, uint64_t nt, const uint64_t* soupBases, const uint64_t* weldedBases, int n,
-            const float* v, const float* nrm, const uint8_t* c, const int32_t* t, float* kv, float* kn, uint8_t* kc,
-            int32_t* kt, emf_stream_t stream, const char* what) {
-    EMF_TRY(check_sizes(nv, nt, n, what));
-    if (nv == 0) {
-        if (nt != 0) return fail(EMF_E_ARG, "%s: %llu triangles over no vertex", what, (unsigned long long)nt);
-        return EMF_OK;
-    }
-    EMF_REQUIRE_PTR(scratch);
-    EMF_REQUIRE_PTR(v);
-    EMF_REQUIRE_PTR(nrm);
-    EMF_REQUIRE_PTR(kv);
-    EMF_REQUIRE_PTR(kn);
-    if (nt) {
-        EMF_REQUIRE_PTR(t);
-        EMF_REQUIRE_PTR(kt);
-    }
-    if ((c == nullptr) != (kc == nullptr)) return fail(EMF_E_NULL, "%s: colors and kept_colors go together", what);
-    if (kv == v || kn == nrm || (c && kc == c) || (nt && kt == t))
-        return fail(EMF_E_ARG, "%s: the kept arrays must not alias the welded mesh's", what);
+            const MeshArrays& e, emf_stream_t stream, const char* what) {
+    EMF_TRY(check_sizes(nv, nt, n, "welded ", what));
+    EMF_TRY(check_no_orphans(nv, nt, what));
+    if (nv == 0) return EMF_OK;
+    EMF_TRY(check_emit_arrays(scratch, e, nt, what));
+    EMF_TRY(check_emit_pairs(e, false, nt, "kept", "welded mesh's", what));
     CcArgs a;
     place(a, nv, nt, const_cast<void*>(scratch));
-    const CcModels md{reinterpret_cast<const unsigned long long*>(soupBases),
-                      reinterpret_cast<const unsigned long long*>(weldedBases), static_cast<unsigned>(n)};
-    const CcEmitArgs e{v, nrm, c, t, kv, kn, kc, kt};
-    hipLaunchKernelGGL(k_cc_emit, dim3(items_blocks(a)), dim3(kCcBlock), 0, as_stream(stream), a, md, e);
+    hipLaunchKernelGGL(k_cc_emit, dim3(items_blocks(a)), dim3(kCcBlock), 0, as_stream(stream), a,
+                       mesh_table(soupBases, weldedBases, n), e);
     return launch_status(what);
 }
 
@@ -524,16 +372,11 @@ int emf_hip_meshComponentsFilterCountBatched(const int32_t* triangles, uint64_t 
 int emf_hip_meshComponentsStatus(const void* cc_scratch_dev, uint64_t weldedVertices, uint64_t nTriangles,
                                  emf_stream_t stream) {
     EMF_REQUIRE_PTR(cc_scratch_dev);
-    EMF_TRY(check_sizes(weldedVertices, nTriangles, 1, "meshComponentsStatus"));
+    EMF_TRY(check_sizes(weldedVertices, nTriangles, 1, "welded ", "meshComponentsStatus"));
     CcArgs a;
     place(a, weldedVertices, nTriangles, const_cast<void*>(cc_scratch_dev));
-    unsigned flag = 0;
-    hipError_t e = hipMemcpyAsync(&flag, a.flag, sizeof(flag), hipMemcpyDeviceToHost, as_stream(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
-    if (e != hipSuccess) {
-        set_error("meshComponentsStatus: %s", hipGetErrorString(e));
-        return static_cast<int>(e);
-    }
+    unsigned flag;
+    EMF_TRY(read_flag(a.flag, flag, stream, "meshComponentsStatus"));
     if (flag) return fail(EMF_E_ARG, "meshComponents: a triangle index lies outside its model's welded vertices");
     return EMF_OK;
 }
@@ -542,8 +385,9 @@ int emf_hip_meshComponentsEmit(const void* cc_scratch_dev, uint64_t weldedVertic
                                const float* vertices, const float* normals, const uint8_t* colors,
                                const int32_t* triangles, float* kept_vertices, float* kept_normals, uint8_t* kept_colors,
                                int32_t* kept_triangles, emf_stream_t stream) {
-    return cc_emit(cc_scratch_dev, weldedVertices, nTriangles, nullptr, nullptr, 1, vertices, normals, colors, triangles,
-                   kept_vertices, kept_normals, kept_colors, kept_triangles, stream, "meshComponentsEmit");
+    return cc_emit(cc_scratch_dev, weldedVertices, nTriangles, nullptr, nullptr, 1,
+                   MeshArrays{vertices, normals, colors, triangles, kept_vertices, kept_normals, kept_colors, kept_triangles},
+                   stream, "meshComponentsEmit");
 }
 
 int emf_hip_meshComponentsEmitBatched(const void* cc_scratch_dev, uint64_t weldedVertices, uint64_t nTriangles,
@@ -553,9 +397,9 @@ int emf_hip_meshComponentsEmitBatched(const void* cc_scratch_dev, uint64_t welde
                                       uint8_t* kept_colors, int32_t* kept_triangles, emf_stream_t stream) {
     EMF_REQUIRE_PTR(soup_bases_dev);
     EMF_REQUIRE_PTR(welded_bases_dev);
-    return cc_emit(cc_scratch_dev, weldedVertices, nTriangles, soup_bases_dev, welded_bases_dev, n, vertices, normals,
-                   colors, triangles, kept_vertices, kept_normals, kept_colors, kept_triangles, stream,
-                   "meshComponentsEmitBatched");
+    return cc_emit(cc_scratch_dev, weldedVertices, nTriangles, soup_bases_dev, welded_bases_dev, n,
+                   MeshArrays{vertices, normals, colors, triangles, kept_vertices, kept_normals, kept_colors, kept_triangles},
+                   stream, "meshComponentsEmitBatched");
 }
 
 }  // extern "C"

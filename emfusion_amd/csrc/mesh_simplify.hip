@@ -25,7 +25,7 @@
 //                    1).  Per vertex of a pass-through model: ref[i] := 1
 //   k_sp_flags       three flags summed per workgroup: "is a first" (the clusters met), "is a referenced first" (the
 //                    kept vertices), "kept triangle"
-//   k_sp_scan        three workgroups: the exclusive scans of the three sums arrays (wave_ops.hpp)
+//   k_sums_scan      three workgroups: the exclusive scans of the three sums arrays (mesh_table.hpp)
 //   k_sp_rank        vexcl[i], texcl[i] = kept vertices / triangles before i
 //   k_sp_bases       per model: kept counts, kept bases and the clusters met, all ranks at the models' bases
 //   k_sp_emit        a kept first writes its cluster's vertex at its rank (its own bits if it is alone, the integer
@@ -37,38 +37,26 @@
 // the sums, hence every output, are the same whatever order they arrive in.  No float atomics.
 // Which slot a key lands in depends on the order the lanes arrive; the MINIMUM index per key does not.  All atomics
 // are ordinary global atomics on vector memory; every loop is bounded by construction; nothing waits on another lane.
-#include "common.hpp"
-#include "wave_ops.hpp"
+#include "mesh_table.hpp"
 
 namespace emf_hip {
 namespace {
 
 constexpr int kSpBlock = kScanBlock;
-constexpr unsigned long long kEmptyKey = ~0ull;  // no cluster key has all bits set (slot < 256 sits at bit 48)
-constexpr unsigned kNone = ~0u;                  // rep[i] after the insert: no slot, the vertex is its own cluster
+constexpr unsigned kNone = kNoSlot;  // rep[i] after the insert: no slot, the vertex is its own cluster
 constexpr unsigned kFlagLimit = 1u, kFlagArg = 2u;
 
-struct SpArgs {
+struct SpArgs : Compaction {
     unsigned long long* tkeys;
     unsigned* tfirst;
     unsigned* rep;
     unsigned* count;
     unsigned* ref;
     long long* sums;  // 9 per vertex: position x y z, normal x y z, colour r g b
-    unsigned* vexcl;
-    unsigned* texcl;
-    unsigned* csums;  // vblocks + 1: firsts
-    unsigned* vsums;  // vblocks + 1: referenced firsts
-    unsigned* tsums;  // tblocks + 1: kept triangles
+    unsigned* csums;  // vblocks + 1: firsts (Compaction's vsums: referenced firsts, tsums: kept triangles)
     unsigned* flag;
-    unsigned nv, nt, cap, vblocks, tblocks;
+    unsigned cap;
 };
-
-inline unsigned capacity_for(unsigned long long nv) {
-    unsigned long long cap = 64;
-    while (cap < 2 * nv) cap <<= 1;
-    return static_cast<unsigned>(cap);
-}
 
 inline size_t place(SpArgs& a, unsigned long long nv, unsigned long long nt, void* scratch) {
     a.nv = static_cast<unsigned>(nv);
@@ -92,72 +80,11 @@ inline size_t place(SpArgs& a, unsigned long long nv, unsigned long long nt, voi
     return s.off;
 }
 
-// the models of a table launch (device arrays in the layout the weld and the filter leave) or, for one mesh, none
-struct SpModels {
-    const unsigned long long* triBases;     // 2 (n + 1) interleaved: the triangle bases are the odd entries
-    const unsigned long long* vertexBases;  // n + 1
-    unsigned n;
-};
-
 // each model's cell and the origin, by value: the host arrays need not outlive the call
 struct SpCells {
     float cell[EMF_MAX_MODELS];
     float origin[3];
 };
-
-// the last model whose base is <= x (empty models share a base with their successor: the one that holds x wins)
-__device__ __forceinline__ unsigned model_of(const unsigned long long* bases, unsigned stride, unsigned n,
-                                             unsigned long long x) {
-    unsigned lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (x >= bases[stride * mid]) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-struct Range {
-    unsigned model, lo, hi;  // the model's vertices are [lo, hi)
-};
-
-__device__ __forceinline__ Range range_of_vertex(const SpArgs& a, const SpModels& md, unsigned g) {
-    if (!md.vertexBases) return Range{0u, 0u, a.nv};
-    const unsigned m = model_of(md.vertexBases, 1, md.n, g);
-    return Range{m, static_cast<unsigned>(md.vertexBases[m]), static_cast<unsigned>(md.vertexBases[m + 1])};
-}
-
-__device__ __forceinline__ Range range_of_triangle(const SpArgs& a, const SpModels& md, unsigned t) {
-    if (!md.vertexBases) return Range{0u, 0u, a.nv};
-    const unsigned m = model_of(md.triBases + 1, 2, md.n, t);
-    return Range{m, static_cast<unsigned>(md.vertexBases[m]), static_cast<unsigned>(md.vertexBases[m + 1])};
-}
-
-// the global indices of triangle t's corners; false (and nothing to dereference) if one lies outside its model's
-// vertex range or past the scratch
-__device__ __forceinline__ bool corners(const SpArgs& a, const Range& r, const int32_t* tris, unsigned t,
-                                        unsigned g[3]) {
-    const int32_t* ti = tris + 4 * static_cast<size_t>(t);
-    const unsigned hi = r.hi < a.nv ? r.hi : a.nv;
-    bool ok = r.lo <= hi;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const unsigned long long x = static_cast<unsigned long long>(r.lo) + static_cast<unsigned>(ti[1 + j]);
-        ok = ok && ti[1 + j] >= 0 && x < hi;
-        g[j] = static_cast<unsigned>(x);
-    }
-    return ok;
-}
-
-// splitmix64's finaliser: neighbouring cells must not land in neighbouring slots
-__device__ __forceinline__ unsigned hash_slot(unsigned long long k, unsigned mask) {
-    k ^= k >> 30;
-    k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27;
-    k *= 0x94d049bb133111ebull;
-    k ^= k >> 31;
-    return static_cast<unsigned>(k) & mask;
-}
 
 // the cluster key of position p in model `slot`, or false where the definition refuses the vertex
 __device__ __forceinline__ bool cluster_key(const float* p, const SpCells& c, unsigned slot, unsigned long long& key) {
@@ -176,11 +103,11 @@ __device__ __forceinline__ bool cluster_key(const float* p, const SpCells& c, un
     return ok;
 }
 
-__global__ __launch_bounds__(kSpBlock) void k_sp_insert(const SpArgs a, const SpModels md, const SpCells c,
+__global__ __launch_bounds__(kSpBlock) void k_sp_insert(const SpArgs a, const MeshTable md, const SpCells c,
                                                         const float* verts) {
     const unsigned i = blockIdx.x * kSpBlock + threadIdx.x;
     if (i >= a.nv) return;
-    const unsigned slot = range_of_vertex(a, md, i).model;
+    const unsigned slot = range_of_vertex(a.nv, md, i).model;
     a.rep[i] = kNone;
     if (!(c.cell[slot] > 0.0f)) return;  // a pass-through model: every vertex its own cluster
     unsigned long long key;
@@ -188,18 +115,9 @@ __global__ __launch_bounds__(kSpBlock) void k_sp_insert(const SpArgs a, const Sp
         atomicOr(a.flag, kFlagLimit);
         return;
     }
-    const unsigned mask = a.cap - 1u;
-    unsigned h = hash_slot(key, mask);
-    for (unsigned probe = 0; probe < a.cap; ++probe) {
-        const unsigned long long seen = atomicCAS(a.tkeys + h, kEmptyKey, key);
-        if (seen == kEmptyKey || seen == key) {
-            atomicMin(a.tfirst + h, i);
-            a.rep[i] = h;
-            return;
-        }
-        h = (h + 1u) & mask;
-    }
-    atomicOr(a.flag, kFlagLimit);  // the table cannot hold the keys
+    const unsigned h = claim_slot(a.tkeys, a.tfirst, a.cap, key, i);
+    if (h == kNoSlot) atomicOr(a.flag, kFlagLimit);  // the table cannot hold the keys
+    else a.rep[i] = h;
 }
 
 // Q20 of a coordinate with |p| < 2^10: exact in double, |q| <= 2^30
@@ -265,15 +183,15 @@ __global__ __launch_bounds__(kSpBlock) void k_sp_accumulate(const SpArgs a, cons
 
 __device__ __forceinline__ bool is_first(const SpArgs& a, unsigned i) { return i < a.nv && a.rep[i] == i; }
 
-__global__ __launch_bounds__(kSpBlock) void k_sp_mark(const SpArgs a, const SpModels md, const SpCells c,
+__global__ __launch_bounds__(kSpBlock) void k_sp_mark(const SpArgs a, const MeshTable md, const SpCells c,
                                                       const int32_t* tris) {
     const unsigned i = blockIdx.x * kSpBlock + threadIdx.x;
-    if (i < a.nv && !(c.cell[range_of_vertex(a, md, i).model] > 0.0f)) a.ref[i] = 1u;  // pass-through: all kept
+    if (i < a.nv && !(c.cell[range_of_vertex(a.nv, md, i).model] > 0.0f)) a.ref[i] = 1u;  // pass-through: all kept
     if (i >= a.nt) return;
-    const Range r = range_of_triangle(a, md, i);
+    const Range r = range_of_triangle(a.nv, md, i);
     unsigned g[3];
     unsigned keep = 0u;
-    if (!corners(a, r, tris, i, g)) {
+    if (!corners(a.nv, r, tris, i, g)) {
         atomicOr(a.flag, kFlagArg);
     } else {
         const unsigned f0 = a.rep[g[0]], f1 = a.rep[g[1]], f2 = a.rep[g[2]];
@@ -303,15 +221,6 @@ __global__ __launch_bounds__(kSpBlock) void k_sp_flags(const SpArgs a) {
     if (threadIdx.x == 0 && blockIdx.x < a.tblocks) a.tsums[blockIdx.x] = total;
 }
 
-// workgroup 0 scans the cluster sums, workgroup 1 the kept-vertex sums, workgroup 2 the kept-triangle sums
-__global__ __launch_bounds__(kSumsBlock) void k_sp_scan(const SpArgs a) {
-    __shared__ unsigned lds[kSumsBlock / 64];
-    unsigned* sums = blockIdx.x == 0 ? a.csums : (blockIdx.x == 1 ? a.vsums : a.tsums);
-    const unsigned n = blockIdx.x == 2 ? a.tblocks : a.vblocks;
-    const unsigned total = scan_sums(sums, 0u, n, lds);
-    if (threadIdx.x == 0) sums[n] = total;
-}
-
 // texcl[i] holds triangle i's kept flag on entry and its rank on exit: each lane reads and writes its own element
 __global__ __launch_bounds__(kSpBlock) void k_sp_rank(const SpArgs a) {
     __shared__ unsigned lds[kSpBlock / 64];
@@ -323,13 +232,6 @@ __global__ __launch_bounds__(kSpBlock) void k_sp_rank(const SpArgs a) {
     if (i < a.nt) a.texcl[i] = a.tsums[blockIdx.x] + tmine;
 }
 
-// kept vertices before vertex b / kept triangles before triangle b (b past the end: all of them)
-__device__ __forceinline__ unsigned vrank_at(const SpArgs& a, unsigned long long b) {
-    return b < a.nv ? a.vexcl[b] : a.vsums[a.vblocks];
-}
-__device__ __forceinline__ unsigned trank_at(const SpArgs& a, unsigned long long b) {
-    return b < a.nt ? a.texcl[b] : a.tsums[a.tblocks];
-}
 // clusters before vertex b: the scanned sum of b's workgroup and at most kSpBlock - 1 flags behind it
 __device__ __forceinline__ unsigned crank_at(const SpArgs& a, unsigned long long b) {
     if (b >= a.nv) return a.csums[a.vblocks];
@@ -347,58 +249,28 @@ struct SpCounts {
 
 // per model: a model's clusters, kept vertices and kept triangles lie in its own ranges, so its kept ranges start
 // at the ranks of its bases
-__global__ __launch_bounds__(kSpBlock) void k_sp_bases(const SpArgs a, const SpModels md, const SpCounts out) {
+__global__ __launch_bounds__(kSpBlock) void k_sp_bases(const SpArgs a, const MeshTable md, const SpCounts out) {
     const unsigned i = blockIdx.x * kSpBlock + threadIdx.x;
     if (i > md.n) return;
-    const unsigned long long vlo = md.vertexBases ? md.vertexBases[i] : (i == 0 ? 0ull : a.nv);
-    const unsigned long long tlo = md.vertexBases ? md.triBases[2 * i + 1] : (i == 0 ? 0ull : a.nt);
-    const unsigned rv = vrank_at(a, vlo), rt = trank_at(a, tlo);
-    if (out.keptBases) {
-        out.keptBases[2 * i] = rv;
-        out.keptBases[2 * i + 1] = rt;
-    }
-    if (i < md.n) {
-        const unsigned long long vhi = md.vertexBases ? md.vertexBases[i + 1] : a.nv;
-        const unsigned long long thi = md.vertexBases ? md.triBases[2 * i + 3] : a.nt;
-        out.keptCounts[2 * i] = vrank_at(a, vhi) - rv;
-        out.keptCounts[2 * i + 1] = trank_at(a, thi) - rt;
-        if (out.clusters) out.clusters[i] = crank_at(a, vhi) - crank_at(a, vlo);
-    }
+    kept_ranges(a, md, i, out.keptCounts, out.keptBases);
+    if (i < md.n && out.clusters)
+        out.clusters[i] = crank_at(a, vertex_base(a.nv, md, i + 1)) - crank_at(a, vertex_base(a.nv, md, i));
 }
-
-struct SpEmitArgs {
-    const float* v;
-    const float* nrm;
-    const uint8_t* c;
-    const int32_t* t;
-    float* kv;
-    float* kn;
-    uint8_t* kc;
-    int32_t* kt;
-};
 
 // the mean of `count` Q20 values whose sum is `sum`
 __device__ __forceinline__ float mean_q20(long long sum, unsigned count) {
     return static_cast<float>((static_cast<double>(sum) / static_cast<double>(count)) * 0x1p-20);
 }
 
-__global__ __launch_bounds__(kSpBlock) void k_sp_emit(const SpArgs a, const SpModels md, const SpEmitArgs e) {
+__global__ __launch_bounds__(kSpBlock) void k_sp_emit(const SpArgs a, const MeshTable md, const MeshArrays e) {
     const unsigned i = blockIdx.x * kSpBlock + threadIdx.x;
     if (i < a.nv) {
         const unsigned r = a.vexcl[i];
-        if (vrank_at(a, static_cast<unsigned long long>(i) + 1) != r) {  // a kept first: the rank steps behind it
+        if (a.vrank_at(static_cast<unsigned long long>(i) + 1) != r) {  // a kept first: the rank steps behind it
             const unsigned count = a.count[i];
             const long long* s = a.sums + 9 * static_cast<size_t>(i);
             if (count <= 1u) {  // alone: its own bits
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    e.kv[3 * static_cast<size_t>(r) + j] = e.v[3 * static_cast<size_t>(i) + j];
-                    e.kn[3 * static_cast<size_t>(r) + j] = e.nrm[3 * static_cast<size_t>(i) + j];
-                }
-                if (e.c) {
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) e.kc[3 * static_cast<size_t>(r) + j] = e.c[3 * static_cast<size_t>(i) + j];
-                }
+                copy_vertex(e, i, r);
             } else {
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
@@ -414,40 +286,8 @@ __global__ __launch_bounds__(kSpBlock) void k_sp_emit(const SpArgs a, const SpMo
             }
         }
     }
-    if (i < a.nt) {
-        const unsigned r = a.texcl[i];
-        if (trank_at(a, static_cast<unsigned long long>(i) + 1) != r) {  // kept, hence inside its model's range
-            const Range m = range_of_triangle(a, md, i);
-            unsigned g[3];
-            if (corners(a, m, e.t, i, g)) {
-                const unsigned base = vrank_at(a, m.lo);
-                int32_t* to = e.kt + 4 * static_cast<size_t>(r);
-                to[0] = 3;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) to[1 + j] = static_cast<int32_t>(a.vexcl[a.rep[g[j]]] - base);
-            }
-        }
-    }
+    rewrite_triangle(a, md, e, i, [&](unsigned g) { return a.vexcl[a.rep[g]]; });
 }
-
-int check_sizes(unsigned long long nv, unsigned long long nt, int n, const char* what) {
-    if (nv > (1ull << 30)) return fail(EMF_E_LIMIT, "%s: %llu vertices (at most 2^30)", what, nv);
-    if (nt >= (1ull << 31)) return fail(EMF_E_LIMIT, "%s: %llu triangles (below 2^31)", what, nt);
-    if (n < 1 || n > EMF_MAX_MODELS) return fail(EMF_E_LIMIT, "%s: %d models (1 .. %d per launch)", what, n, EMF_MAX_MODELS);
-    if (nv == 0 && nt != 0) return fail(EMF_E_ARG, "%s: %llu triangles over no vertex", what, nt);
-    return EMF_OK;
-}
-
-int memset_async(void* p, int v, size_t bytes, emf_stream_t stream, const char* what) {
-    const hipError_t e = hipMemsetAsync(p, v, bytes, as_stream(stream));
-    if (e != hipSuccess) {
-        set_error("%s: memset: %s", what, hipGetErrorString(e));
-        return static_cast<int>(e);
-    }
-    return EMF_OK;
-}
-
-inline unsigned items_blocks(const SpArgs& a) { return a.vblocks > a.tblocks ? a.vblocks : a.tblocks; }
 
 }  // namespace
 }  // namespace emf_hip
@@ -471,7 +311,8 @@ int emf_hip_meshSimplifyCount(const float* vertices, const float* normals, const
                               const float origin[3], void* simplify_scratch_dev, uint32_t* kept_counts,
                               uint64_t* kept_bases, uint32_t* clusters, emf_stream_t stream) {
     const char* what = "meshSimplifyCount";
-    EMF_TRY(check_sizes(nVertices, nTriangles, n, what));
+    EMF_TRY(check_sizes(nVertices, nTriangles, n, "", what));
+    EMF_TRY(check_no_orphans(nVertices, nTriangles, what));
     EMF_REQUIRE_PTR(simplify_scratch_dev);
     EMF_REQUIRE_PTR(kept_counts);
     EMF_REQUIRE_PTR(cells);
@@ -503,15 +344,15 @@ int emf_hip_meshSimplifyCount(const float* vertices, const float* normals, const
     // and the sums: zero
     EMF_TRY(memset_async(a.tkeys, 0xff, reinterpret_cast<char*>(a.rep) - reinterpret_cast<char*>(a.tkeys), stream, what));
     EMF_TRY(memset_async(a.count, 0, reinterpret_cast<char*>(a.vexcl) - reinterpret_cast<char*>(a.count), stream, what));
-    const SpModels md{reinterpret_cast<const unsigned long long*>(tri_bases_dev),
-                      reinterpret_cast<const unsigned long long*>(vertex_bases_dev), static_cast<unsigned>(n)};
+    const MeshTable md = mesh_table(tri_bases_dev, vertex_bases_dev, n);
     const SpCounts out{kept_counts, reinterpret_cast<unsigned long long*>(kept_bases), clusters};
     const dim3 block(kSpBlock), vgrid(a.vblocks), items(items_blocks(a));
     hipLaunchKernelGGL(k_sp_insert, vgrid, block, 0, as_stream(stream), a, md, c, vertices);
     hipLaunchKernelGGL(k_sp_accumulate, vgrid, block, 0, as_stream(stream), a, vertices, normals, colors);
     hipLaunchKernelGGL(k_sp_mark, items, block, 0, as_stream(stream), a, md, c, triangles);
     hipLaunchKernelGGL(k_sp_flags, items, block, 0, as_stream(stream), a);
-    hipLaunchKernelGGL(k_sp_scan, dim3(3), dim3(kSumsBlock), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(k_sums_scan, dim3(3), dim3(kSumsBlock), 0, as_stream(stream),
+                       SumsArrays{a.csums, a.vsums, a.tsums, a.vblocks, a.vblocks, a.tblocks});
     hipLaunchKernelGGL(k_sp_rank, items, block, 0, as_stream(stream), a);
     hipLaunchKernelGGL(k_sp_bases, dim3(ceil_div(n + 1, kSpBlock)), block, 0, as_stream(stream), a, md, out);
     return launch_status(what);
@@ -520,16 +361,12 @@ int emf_hip_meshSimplifyCount(const float* vertices, const float* normals, const
 int emf_hip_meshSimplifyStatus(const void* simplify_scratch_dev, uint64_t nVertices, uint64_t nTriangles,
                                emf_stream_t stream) {
     EMF_REQUIRE_PTR(simplify_scratch_dev);
-    EMF_TRY(check_sizes(nVertices, nTriangles, 1, "meshSimplifyStatus"));
+    EMF_TRY(check_sizes(nVertices, nTriangles, 1, "", "meshSimplifyStatus"));
+    EMF_TRY(check_no_orphans(nVertices, nTriangles, "meshSimplifyStatus"));
     SpArgs a;
     place(a, nVertices, nTriangles, const_cast<void*>(simplify_scratch_dev));
-    unsigned flag = 0;
-    hipError_t e = hipMemcpyAsync(&flag, a.flag, sizeof(flag), hipMemcpyDeviceToHost, as_stream(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
-    if (e != hipSuccess) {
-        set_error("meshSimplifyStatus: %s", hipGetErrorString(e));
-        return static_cast<int>(e);
-    }
+    unsigned flag;
+    EMF_TRY(read_flag(a.flag, flag, stream, "meshSimplifyStatus"));
     if (flag & kFlagLimit)
         return fail(EMF_E_LIMIT, "meshSimplify: a vertex is not finite, lies 2^10 m or more from zero or in a cell outside "
                                  "[-2^15, 2^15), or the table overflowed (scratch of another size?)");
@@ -542,31 +379,19 @@ int emf_hip_meshSimplifyEmit(const void* simplify_scratch_dev, uint64_t nVertice
                              const float* normals, const uint8_t* colors, const int32_t* triangles, float* kept_vertices,
                              float* kept_normals, uint8_t* kept_colors, int32_t* kept_triangles, emf_stream_t stream) {
     const char* what = "meshSimplifyEmit";
-    EMF_TRY(check_sizes(nVertices, nTriangles, n, what));
+    EMF_TRY(check_sizes(nVertices, nTriangles, n, "", what));
+    EMF_TRY(check_no_orphans(nVertices, nTriangles, what));
     if (nVertices == 0) return EMF_OK;
-    EMF_REQUIRE_PTR(simplify_scratch_dev);
-    EMF_REQUIRE_PTR(vertices);
-    EMF_REQUIRE_PTR(normals);
-    EMF_REQUIRE_PTR(kept_vertices);
-    EMF_REQUIRE_PTR(kept_normals);
-    if (nTriangles) {
-        EMF_REQUIRE_PTR(triangles);
-        EMF_REQUIRE_PTR(kept_triangles);
-    }
+    const MeshArrays e{vertices, normals, colors, triangles, kept_vertices, kept_normals, kept_colors, kept_triangles};
+    EMF_TRY(check_emit_arrays(simplify_scratch_dev, e, nTriangles, what));
     if ((tri_bases_dev == nullptr) != (vertex_bases_dev == nullptr))
         return fail(EMF_E_NULL, "%s: tri_bases_dev and vertex_bases_dev go together", what);
     if (!tri_bases_dev && n != 1) return fail(EMF_E_ARG, "%s: %d models need their bases", what, n);
-    if ((colors == nullptr) != (kept_colors == nullptr))
-        return fail(EMF_E_NULL, "%s: colors and kept_colors go together", what);
-    if (kept_vertices == vertices || kept_normals == normals || (colors && kept_colors == colors) ||
-        (nTriangles && kept_triangles == triangles))
-        return fail(EMF_E_ARG, "%s: the kept arrays must not alias the input mesh's", what);
+    EMF_TRY(check_emit_pairs(e, false, nTriangles, "kept", "input mesh's", what));
     SpArgs a;
     place(a, nVertices, nTriangles, const_cast<void*>(simplify_scratch_dev));
-    const SpModels md{reinterpret_cast<const unsigned long long*>(tri_bases_dev),
-                      reinterpret_cast<const unsigned long long*>(vertex_bases_dev), static_cast<unsigned>(n)};
-    const SpEmitArgs e{vertices, normals, colors, triangles, kept_vertices, kept_normals, kept_colors, kept_triangles};
-    hipLaunchKernelGGL(k_sp_emit, dim3(items_blocks(a)), dim3(kSpBlock), 0, as_stream(stream), a, md, e);
+    hipLaunchKernelGGL(k_sp_emit, dim3(items_blocks(a)), dim3(kSpBlock), 0, as_stream(stream), a,
+                       mesh_table(tri_bases_dev, vertex_bases_dev, n), e);
     return launch_status(what);
 }
 

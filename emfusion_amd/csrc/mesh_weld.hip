@@ -17,21 +17,19 @@
 //                  probing bounded by cap -- a table that is too small raises `flag` instead of spinning), then
 //                  atomicMin the soup index into it; remap[i] := the slot
 //   k_weld_flags   first[i] = (table first[remap[i]] == i), summed per workgroup -> sums[b]
-//   k_weld_scan    one workgroup: exclusive scan of sums in place, the total behind them (wave_ops.hpp)
+//   k_sums_scan    one workgroup: exclusive scan of sums in place, the total behind them (mesh_table.hpp)
 //   k_weld_rank    excl[i] = firsts before i = the welded index of i if i is a first
 //   k_weld_remap   remap[i] := excl[first of i's key]; the models' welded bases are excl at their soup bases
 //   k_weld_emit    firsts (remap[i] == excl[i]) copy position, normal and colour to their rank; triangles are
 //                  rewritten through remap, minus the model's welded base
 // Which slot a key lands in depends on the order the lanes arrive; the MINIMUM soup index per key, hence every
 // output, does not.  All atomics are ordinary global atomics on vector memory.
-#include "common.hpp"
-#include "wave_ops.hpp"
+#include "mesh_table.hpp"
 
 namespace emf_hip {
 namespace {
 
 constexpr int kWeldBlock = kScanBlock;
-constexpr unsigned long long kEmptyKey = ~0ull;  // no edge key has all bits set (slot < 256 sits at bit 48)
 
 struct WeldArgs {
     unsigned long long* tkeys;
@@ -42,13 +40,6 @@ struct WeldArgs {
     unsigned* flag;
     unsigned nv, cap, nblocks;
 };
-
-// the table's capacity for nv soup vertices: a power of two >= 2 nv (load factor <= 1/2)
-inline unsigned capacity_for(unsigned long long nv) {
-    unsigned long long cap = 64;
-    while (cap < 2 * nv) cap <<= 1;
-    return static_cast<unsigned>(cap);
-}
 
 inline size_t place(WeldArgs& a, unsigned long long nv, void* scratch) {
     a.nv = static_cast<unsigned>(nv);
@@ -64,33 +55,13 @@ inline size_t place(WeldArgs& a, unsigned long long nv, void* scratch) {
     return s.off;
 }
 
-// splitmix64's finaliser: neighbouring edges (keys 3 apart) must not land in neighbouring slots
-__device__ __forceinline__ unsigned hash_slot(unsigned long long k, unsigned mask) {
-    k ^= k >> 30;
-    k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27;
-    k *= 0x94d049bb133111ebull;
-    k ^= k >> 31;
-    return static_cast<unsigned>(k) & mask;
-}
-
 __global__ __launch_bounds__(kWeldBlock) void k_weld_insert(const WeldArgs a, const unsigned long long* keys) {
     const unsigned i = blockIdx.x * kWeldBlock + threadIdx.x;
     if (i >= a.nv) return;
-    const unsigned long long key = keys[i];
-    const unsigned mask = a.cap - 1u;
-    unsigned h = hash_slot(key, mask);
-    for (unsigned probe = 0; probe < a.cap; ++probe) {
-        const unsigned long long seen = atomicCAS(a.tkeys + h, kEmptyKey, key);
-        if (seen == kEmptyKey || seen == key) {
-            atomicMin(a.tfirst + h, i);
-            a.remap[i] = h;
-            return;
-        }
-        h = (h + 1u) & mask;
-    }
-    a.remap[i] = 0u;  // (a valid slot: the later passes stay inside the table whatever they compute)
-    atomicOr(a.flag, 1u);
+    const unsigned h = claim_slot(a.tkeys, a.tfirst, a.cap, keys[i], i);
+    // (no slot: 0 is a valid one, the later passes stay inside the table whatever they compute)
+    a.remap[i] = h != kNoSlot ? h : 0u;
+    if (h == kNoSlot) atomicOr(a.flag, 1u);
 }
 
 __device__ __forceinline__ unsigned is_first(const WeldArgs& a, unsigned i) {
@@ -102,13 +73,6 @@ __global__ __launch_bounds__(kWeldBlock) void k_weld_flags(const WeldArgs a) {
     unsigned total;
     block_exclusive_scan<kScanBlock / 64>(is_first(a, blockIdx.x * kWeldBlock + threadIdx.x), total, lds);
     if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
-}
-
-// one workgroup: sums[b] := sum of sums[0 .. b), sums[nblocks] := the total
-__global__ __launch_bounds__(kSumsBlock) void k_weld_scan(const WeldArgs a) {
-    __shared__ unsigned lds[kSumsBlock / 64];
-    const unsigned total = scan_sums(a.sums, 0u, a.nblocks, lds);
-    if (threadIdx.x == 0) a.sums[a.nblocks] = total;
 }
 
 __global__ __launch_bounds__(kWeldBlock) void k_weld_rank(const WeldArgs a) {
@@ -128,8 +92,8 @@ struct WeldModels {
 };
 
 // firsts before soup vertex b (b == nv: all of them)
-__device__ __forceinline__ unsigned rank_at(const WeldArgs& a, unsigned long long b) {
-    return b < a.nv ? a.excl[b] : a.sums[a.nblocks];
+__device__ __forceinline__ unsigned first_rank(const WeldArgs& a, unsigned long long b) {
+    return rank_at(a.excl, a.sums, a.nv, a.nblocks, b);
 }
 
 __global__ __launch_bounds__(kWeldBlock) void k_weld_remap(const WeldArgs a, const WeldModels md) {
@@ -142,67 +106,34 @@ __global__ __launch_bounds__(kWeldBlock) void k_weld_remap(const WeldArgs a, con
         // a model's keys carry its slot, so its firsts lie in its own soup range: its welded range starts at the
         // rank of its soup base
         const unsigned long long lo = md.soupBases ? md.soupBases[2 * i] : (i == 0 ? 0ull : a.nv);
-        const unsigned rlo = rank_at(a, lo);
+        const unsigned rlo = first_rank(a, lo);
         if (md.weldedBases) md.weldedBases[i] = rlo;
         if (i < md.n) {
             const unsigned long long hi = md.soupBases ? md.soupBases[2 * (i + 1)] : a.nv;
-            md.weldedCounts[i] = rank_at(a, hi) - rlo;
+            md.weldedCounts[i] = first_rank(a, hi) - rlo;
         }
     }
 }
 
-struct WeldEmitArgs {
-    const unsigned long long* soupBases;    // 2 (n + 1) interleaved, or nullptr (one model)
-    const unsigned long long* weldedBases;  // n + 1, or nullptr
-    unsigned n;
-    unsigned long long ntris;
-    const float* v;
-    const float* nrm;
-    const uint8_t* c;
-    const int32_t* t;
-    float* wv;
-    float* wn;
-    uint8_t* wc;
-    int32_t* wt;
-};
-
-// the model whose triangle range holds triangle t (bases interleaved: the triangle bases are the odd entries)
-__device__ __forceinline__ unsigned tri_model(const unsigned long long* bases, unsigned n, unsigned long long t) {
-    unsigned lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (t >= bases[2 * mid + 1]) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(kWeldBlock) void k_weld_emit(const WeldArgs a, const WeldEmitArgs e) {
+// soup vertex -> welded vertex, soup triangle -> welded triangle.  md: the soup bases and the welded bases; e: the
+// soup and the welded arrays (kt may be t)
+__global__ __launch_bounds__(kWeldBlock) void k_weld_emit(const WeldArgs a, const MeshTable md, unsigned long long ntris,
+                                                          const MeshArrays e) {
     const unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * kWeldBlock + threadIdx.x;
     if (i < a.nv) {
         const unsigned r = a.remap[i];
-        if (r == a.excl[i]) {  // a later copy's excl is at least its first's + 1
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                e.wv[3 * static_cast<size_t>(r) + j] = e.v[3 * i + j];
-                e.wn[3 * static_cast<size_t>(r) + j] = e.nrm[3 * i + j];
-            }
-            if (e.c) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) e.wc[3 * static_cast<size_t>(r) + j] = e.c[3 * i + j];
-            }
-        }
+        if (r == a.excl[i]) copy_vertex(e, i, r);  // a first: a later copy's excl is at least its first's + 1
     }
-    if (i < e.ntris) {
+    if (i < ntris) {
         unsigned long long sb = 0, wb = 0;
-        if (e.soupBases) {
-            const unsigned m = tri_model(e.soupBases, e.n, i);
-            sb = e.soupBases[2 * m];
-            wb = e.weldedBases[m];
+        if (md.triBases) {
+            const unsigned m = model_of(md.triBases + 1, 2, md.n, i);
+            sb = md.triBases[2 * m];
+            wb = md.vertexBases[m];
         }
         const int32_t* ti = e.t + 4 * i;
-        const int32_t i0 = ti[1], i1 = ti[2], i2 = ti[3];  // read before written: wt may be t
-        int32_t* to = e.wt + 4 * i;
+        const int32_t i0 = ti[1], i1 = ti[2], i2 = ti[3];  // read before written: kt may be t
+        int32_t* to = e.kt + 4 * i;
         to[0] = 3;
         // (an index outside the soup -- not something the emit kernels write -- becomes -1 instead of a wild read)
         auto welded = [&](int32_t s) {
@@ -215,24 +146,9 @@ __global__ __launch_bounds__(kWeldBlock) void k_weld_emit(const WeldArgs a, cons
     }
 }
 
-int check_soup(unsigned long long nv, const char* what) {
-    if (nv > (1ull << 30)) return fail(EMF_E_LIMIT, "%s: %llu soup vertices (at most 2^30)", what, nv);
-    return EMF_OK;
-}
-
-int memset_async(void* p, int v, size_t bytes, emf_stream_t stream, const char* what) {
-    const hipError_t e = hipMemsetAsync(p, v, bytes, as_stream(stream));
-    if (e != hipSuccess) {
-        set_error("%s: memset: %s", what, hipGetErrorString(e));
-        return static_cast<int>(e);
-    }
-    return EMF_OK;
-}
-
 int weld_count(const uint64_t* keys, uint64_t nv, const uint64_t* soupBases, int n, void* scratch,
                uint32_t* counts, uint64_t* bases, emf_stream_t stream, const char* what) {
-    EMF_TRY(check_soup(nv, what));
-    if (n < 1 || n > EMF_MAX_MODELS) return fail(EMF_E_LIMIT, "%s: %d models (1 .. %d per launch)", what, n, EMF_MAX_MODELS);
+    EMF_TRY(check_sizes(nv, 0, n, "soup ", what));
     EMF_REQUIRE_PTR(counts);
     EMF_REQUIRE_PTR(scratch);
     if (nv) EMF_REQUIRE_PTR(keys);  // (nothing is enqueued for rejected arguments)
@@ -252,7 +168,8 @@ int weld_count(const uint64_t* keys, uint64_t nv, const uint64_t* soupBases, int
     hipLaunchKernelGGL(k_weld_insert, grid, block, 0, as_stream(stream), a,
                        reinterpret_cast<const unsigned long long*>(keys));
     hipLaunchKernelGGL(k_weld_flags, grid, block, 0, as_stream(stream), a);
-    hipLaunchKernelGGL(k_weld_scan, dim3(1), dim3(kSumsBlock), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(k_sums_scan, dim3(1), dim3(kSumsBlock), 0, as_stream(stream),
+                       SumsArrays{a.sums, nullptr, nullptr, a.nblocks, 0u, 0u});
     hipLaunchKernelGGL(k_weld_rank, grid, block, 0, as_stream(stream), a);
     // the per-model part needs n + 1 <= 257 threads: two workgroups at least
     hipLaunchKernelGGL(k_weld_remap, dim3(a.nblocks < 2u ? 2u : a.nblocks), block, 0, as_stream(stream), a, md);
@@ -260,34 +177,17 @@ int weld_count(const uint64_t* keys, uint64_t nv, const uint64_t* soupBases, int
 }
 
 int weld_emit(const void* scratch, uint64_t nv, uint64_t nt, const uint64_t* soupBases, const uint64_t* weldedBases,
-              int n, const float* v, const float* nrm, const uint8_t* c, const int32_t* t, float* wv, float* wn,
-              uint8_t* wc, int32_t* wt, emf_stream_t stream, const char* what) {
-    EMF_TRY(check_soup(nv, what));
-    if (nt >= (1ull << 31)) return fail(EMF_E_LIMIT, "%s: %llu triangles (below 2^31)", what, (unsigned long long)nt);
-    if (n < 1 || n > EMF_MAX_MODELS) return fail(EMF_E_LIMIT, "%s: %d models (1 .. %d per launch)", what, n, EMF_MAX_MODELS);
-    if (nv == 0) {
-        if (nt != 0) return fail(EMF_E_ARG, "%s: %llu triangles over no vertex", what, (unsigned long long)nt);
-        return EMF_OK;
-    }
-    EMF_REQUIRE_PTR(scratch);
-    EMF_REQUIRE_PTR(v);
-    EMF_REQUIRE_PTR(nrm);
-    EMF_REQUIRE_PTR(wv);
-    EMF_REQUIRE_PTR(wn);
-    if (nt) {
-        EMF_REQUIRE_PTR(t);
-        EMF_REQUIRE_PTR(wt);
-    }
-    if ((c == nullptr) != (wc == nullptr)) return fail(EMF_E_NULL, "%s: colors and welded_colors go together", what);
-    if (wv == v || wn == nrm || (c && wc == c))
-        return fail(EMF_E_ARG, "%s: the welded vertex arrays must not alias the soup's", what);
+              int n, const MeshArrays& e, emf_stream_t stream, const char* what) {
+    EMF_TRY(check_sizes(nv, nt, n, "soup ", what));
+    EMF_TRY(check_no_orphans(nv, nt, what));
+    if (nv == 0) return EMF_OK;
+    EMF_TRY(check_emit_arrays(scratch, e, nt, what));
+    EMF_TRY(check_emit_pairs(e, true, nt, "welded", "soup's", what));
     WeldArgs a;
     place(a, nv, const_cast<void*>(scratch));
-    const WeldEmitArgs e{reinterpret_cast<const unsigned long long*>(soupBases),
-                         reinterpret_cast<const unsigned long long*>(weldedBases),
-                         static_cast<unsigned>(n), nt, v, nrm, c, t, wv, wn, wc, wt};
     const uint64_t items = nv > nt ? nv : nt;
-    hipLaunchKernelGGL(k_weld_emit, dim3(ceil_div(items, kWeldBlock)), dim3(kWeldBlock), 0, as_stream(stream), a, e);
+    hipLaunchKernelGGL(k_weld_emit, dim3(ceil_div(items, kWeldBlock)), dim3(kWeldBlock), 0, as_stream(stream), a,
+                       mesh_table(soupBases, weldedBases, n), nt, e);
     return launch_status(what);
 }
 
@@ -321,16 +221,11 @@ int emf_hip_meshWeldCountBatched(const uint64_t* keys, uint64_t soupVertices, co
 
 int emf_hip_meshWeldStatus(const void* weld_scratch_dev, uint64_t soupVertices, emf_stream_t stream) {
     EMF_REQUIRE_PTR(weld_scratch_dev);
-    EMF_TRY(check_soup(soupVertices, "meshWeldStatus"));
+    EMF_TRY(check_sizes(soupVertices, 0, 1, "soup ", "meshWeldStatus"));
     WeldArgs a;
     place(a, soupVertices, const_cast<void*>(weld_scratch_dev));
-    unsigned flag = 0;
-    hipError_t e = hipMemcpyAsync(&flag, a.flag, sizeof(flag), hipMemcpyDeviceToHost, as_stream(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
-    if (e != hipSuccess) {
-        set_error("meshWeldStatus: %s", hipGetErrorString(e));
-        return static_cast<int>(e);
-    }
+    unsigned flag;
+    EMF_TRY(read_flag(a.flag, flag, stream, "meshWeldStatus"));
     if (flag)
         return fail(EMF_E_LIMIT, "meshWeld: the table for %llu soup vertices overflowed (scratch of another size?)",
                     (unsigned long long)soupVertices);
@@ -341,8 +236,10 @@ int emf_hip_meshWeldEmit(const void* weld_scratch_dev, uint64_t soupVertices, ui
                          const float* vertices, const float* normals, const uint8_t* colors, const int32_t* triangles,
                          float* welded_vertices, float* welded_normals, uint8_t* welded_colors,
                          int32_t* welded_triangles, emf_stream_t stream) {
-    return weld_emit(weld_scratch_dev, soupVertices, soupTriangles, nullptr, nullptr, 1, vertices, normals, colors,
-                     triangles, welded_vertices, welded_normals, welded_colors, welded_triangles, stream, "meshWeldEmit");
+    return weld_emit(weld_scratch_dev, soupVertices, soupTriangles, nullptr, nullptr, 1,
+                     MeshArrays{vertices, normals, colors, triangles, welded_vertices, welded_normals, welded_colors,
+                                welded_triangles},
+                     stream, "meshWeldEmit");
 }
 
 int emf_hip_meshWeldEmitBatched(const void* weld_scratch_dev, uint64_t soupVertices, uint64_t soupTriangles,
@@ -352,8 +249,9 @@ int emf_hip_meshWeldEmitBatched(const void* weld_scratch_dev, uint64_t soupVerti
                                 uint8_t* welded_colors, int32_t* welded_triangles, emf_stream_t stream) {
     EMF_REQUIRE_PTR(soup_bases_dev);
     EMF_REQUIRE_PTR(welded_bases_dev);
-    return weld_emit(weld_scratch_dev, soupVertices, soupTriangles, soup_bases_dev, welded_bases_dev, n, vertices,
-                     normals, colors, triangles, welded_vertices, welded_normals, welded_colors, welded_triangles,
+    return weld_emit(weld_scratch_dev, soupVertices, soupTriangles, soup_bases_dev, welded_bases_dev, n,
+                     MeshArrays{vertices, normals, colors, triangles, welded_vertices, welded_normals, welded_colors,
+                                welded_triangles},
                      stream, "meshWeldEmitBatched");
 }
 

@@ -841,35 +841,53 @@ def render_phong_color(vertices, normals, colors, image, light=(0.0, 0.0, 0.0), 
     return image
 
 
+class _T(tuple):
+    """The arguments only the ...Batched form of a mesh entry takes, at their place among the others."""
+
+    def __new__(cls, *args):
+        return super().__new__(cls, args)
+
+
+def _mesh_entry(name, batched, *args):
+    """check() of the mesh entry `name` for one mesh or, `batched`, of `name`Batched for a table of meshes."""
+    if batched:
+        name += "Batched"
+    flat = []
+    for a in args:
+        if isinstance(a, _T):
+            flat.extend(a if batched else ())
+        else:
+            flat.append(a)
+    check(name, getattr(_L, name)(*flat))
+
+
+def _kept_arrays(knv, knt, cols):
+    """Device arrays for knv vertices and knt triangles coming out of a pass, one spare element each: (vertices,
+    normals, triangles -- None where knt is, the pass rewrites them in place --, colours or None as `cols` is)."""
+    kv = DeviceArray.zeros((max(knv, 1), 3), np.float32)
+    kn = DeviceArray.zeros((max(knv, 1), 3), np.float32)
+    kt = None if knt is None else DeviceArray.zeros((max(knt, 1), 4), np.int32)
+    kc = None if cols is None else DeviceArray.zeros((max(knv, 1), 3), np.uint8)
+    return kv, kn, kt, kc
+
+
 def _weld(keys, nv, nt, verts, norms, tris, cols, soup_bases=None, n=1, stream=None):
     """emf_hip_meshWeldCount / ...Emit on device soup arrays: (welded vertices, normals, triangles, colours or None as
     device arrays, welded counts (n,) u32, welded bases (n + 1,) u64 on the host and on the device)."""
     scratch = DeviceArray.zeros((max(int(_L.emf_hip_meshWeldScratchBytes(nv)) // 4, 4),), np.uint32)
     wcounts = DeviceArray.zeros((max(n, 1),), np.uint32)
     wbases = DeviceArray.zeros((n + 1,), np.uint64)
-    if soup_bases is None:
-        check("emf_hip_meshWeldCount",
-              _L.emf_hip_meshWeldCount(_ptr(keys), nv, _ptr(scratch), _ptr(wcounts), _stream(stream)))
-    else:
-        check("emf_hip_meshWeldCountBatched",
-              _L.emf_hip_meshWeldCountBatched(_ptr(keys), nv, _ptr(soup_bases), n, _ptr(scratch), _ptr(wcounts),
-                                              _ptr(wbases), _stream(stream)))
+    batched = soup_bases is not None
+    _mesh_entry("emf_hip_meshWeldCount", batched, _ptr(keys), nv, _T(_ptr(soup_bases), n), _ptr(scratch), _ptr(wcounts),
+                _T(_ptr(wbases)), _stream(stream))
     check("emf_hip_meshWeldStatus", _L.emf_hip_meshWeldStatus(_ptr(scratch), nv, _stream(stream)))
     cnt = wcounts.numpy()
     nw = int(cnt.sum())
-    wv = DeviceArray.zeros((max(nw, 1), 3), np.float32)
-    wn = DeviceArray.zeros((max(nw, 1), 3), np.float32)
-    wc = None if cols is None else DeviceArray.zeros((max(nw, 1), 3), np.uint8)
+    wv, wn, _, wc = _kept_arrays(nw, None, cols)
     if nv:
-        if soup_bases is None:
-            check("emf_hip_meshWeldEmit",
-                  _L.emf_hip_meshWeldEmit(_ptr(scratch), nv, nt, _ptr(verts), _ptr(norms), _ptr(cols), _ptr(tris),
-                                          _ptr(wv), _ptr(wn), _ptr(wc), _ptr(tris), _stream(stream)))
-        else:
-            check("emf_hip_meshWeldEmitBatched",
-                  _L.emf_hip_meshWeldEmitBatched(_ptr(scratch), nv, nt, _ptr(soup_bases), _ptr(wbases), n, _ptr(verts),
-                                                 _ptr(norms), _ptr(cols), _ptr(tris), _ptr(wv), _ptr(wn), _ptr(wc),
-                                                 _ptr(tris), _stream(stream)))
+        _mesh_entry("emf_hip_meshWeldEmit", batched, _ptr(scratch), nv, nt, _T(_ptr(soup_bases), _ptr(wbases), n),
+                    _ptr(verts), _ptr(norms), _ptr(cols), _ptr(tris), _ptr(wv), _ptr(wn), _ptr(wc), _ptr(tris),
+                    _stream(stream))
     from .devmem import synchronize
     synchronize()  # the scratch is released on return
     return wv, wn, tris, wc, cnt, wbases.numpy(), wbases
@@ -901,14 +919,8 @@ def _label(tris, nv, nt, soup_bases=None, wbases=None, n=1, outputs=True, stream
     scratch = DeviceArray.zeros((nbytes // 4,), np.uint32)
     labels = DeviceArray.zeros((max(nv, 1),), np.int32) if outputs else None
     sizes = DeviceArray.zeros((max(nv, 1),), np.uint32) if outputs else None
-    if soup_bases is None:
-        check("emf_hip_meshComponentsLabel",
-              _L.emf_hip_meshComponentsLabel(_ptr(tris), nv, nt, _ptr(scratch), _ptr(labels), _ptr(sizes),
-                                             _stream(stream)))
-    else:
-        check("emf_hip_meshComponentsLabelBatched",
-              _L.emf_hip_meshComponentsLabelBatched(_ptr(tris), nv, nt, _ptr(soup_bases), _ptr(wbases), n, _ptr(scratch),
-                                                    _ptr(labels), _ptr(sizes), _stream(stream)))
+    _mesh_entry("emf_hip_meshComponentsLabel", soup_bases is not None, _ptr(tris), nv, nt,
+                _T(_ptr(soup_bases), _ptr(wbases), n), _ptr(scratch), _ptr(labels), _ptr(sizes), _stream(stream))
     return scratch, labels, sizes
 
 
@@ -929,15 +941,10 @@ def _filter(nv, nt, verts, norms, tris, cols, min_triangles, largest_only, soup_
     comps = DeviceArray.zeros((n,), np.uint32)
     kcomps = DeviceArray.zeros((n,), np.uint32)
     hp = lambda a: a.ctypes.data_as(C.c_void_p)
-    if soup_bases is None:
-        check("emf_hip_meshComponentsFilterCount",
-              _L.emf_hip_meshComponentsFilterCount(_ptr(tris), nv, nt, _ptr(scratch), hp(mins), hp(largest),
-                                                   _ptr(kcounts), _ptr(comps), _ptr(kcomps), _stream(stream)))
-    else:
-        check("emf_hip_meshComponentsFilterCountBatched",
-              _L.emf_hip_meshComponentsFilterCountBatched(_ptr(tris), nv, nt, _ptr(soup_bases), _ptr(wbases), n,
-                                                          _ptr(scratch), hp(mins), hp(largest), _ptr(kcounts),
-                                                          _ptr(kbases), _ptr(comps), _ptr(kcomps), _stream(stream)))
+    batched = soup_bases is not None
+    table = _T(_ptr(soup_bases), _ptr(wbases), n)
+    _mesh_entry("emf_hip_meshComponentsFilterCount", batched, _ptr(tris), nv, nt, table, _ptr(scratch), hp(mins),
+                hp(largest), _ptr(kcounts), _T(_ptr(kbases)), _ptr(comps), _ptr(kcomps), _stream(stream))
     check("emf_hip_meshComponentsStatus", _L.emf_hip_meshComponentsStatus(_ptr(scratch), nv, nt, _stream(stream)))
     cnt = kcounts.numpy()
     if soup_bases is None:
@@ -945,20 +952,10 @@ def _filter(nv, nt, verts, norms, tris, cols, min_triangles, largest_only, soup_
     else:
         bs = kbases.numpy()
     knv, knt = int(bs[n, 0]), int(bs[n, 1])
-    kv = DeviceArray.zeros((max(knv, 1), 3), np.float32)
-    kn = DeviceArray.zeros((max(knv, 1), 3), np.float32)
-    kt = DeviceArray.zeros((max(knt, 1), 4), np.int32)
-    kc = None if cols is None else DeviceArray.zeros((max(knv, 1), 3), np.uint8)
+    kv, kn, kt, kc = _kept_arrays(knv, knt, cols)
     if nv:
-        if soup_bases is None:
-            check("emf_hip_meshComponentsEmit",
-                  _L.emf_hip_meshComponentsEmit(_ptr(scratch), nv, nt, _ptr(verts), _ptr(norms), _ptr(cols), _ptr(tris),
-                                                _ptr(kv), _ptr(kn), _ptr(kc), _ptr(kt), _stream(stream)))
-        else:
-            check("emf_hip_meshComponentsEmitBatched",
-                  _L.emf_hip_meshComponentsEmitBatched(_ptr(scratch), nv, nt, _ptr(soup_bases), _ptr(wbases), n,
-                                                       _ptr(verts), _ptr(norms), _ptr(cols), _ptr(tris), _ptr(kv),
-                                                       _ptr(kn), _ptr(kc), _ptr(kt), _stream(stream)))
+        _mesh_entry("emf_hip_meshComponentsEmit", batched, _ptr(scratch), nv, nt, table, _ptr(verts), _ptr(norms),
+                    _ptr(cols), _ptr(tris), _ptr(kv), _ptr(kn), _ptr(kc), _ptr(kt), _stream(stream))
     from .devmem import synchronize
     synchronize()  # the scratch is released on return
     return kv, kn, kt, kc, cnt, bs, dict(components=comps.numpy(), kept_components=kcomps.numpy())
@@ -1035,10 +1032,7 @@ def _simplify(nv, nt, verts, norms, tris, cols, cells, origin=(0.0, 0.0, 0.0), s
         refused = e      # EMF_E_ARG: the offending triangles are dropped, the rest stands
     cnt, bs = kcounts.numpy(), kbases.numpy()
     knv, knt = int(bs[n, 0]), int(bs[n, 1])
-    kv = DeviceArray.zeros((max(knv, 1), 3), np.float32)
-    kn = DeviceArray.zeros((max(knv, 1), 3), np.float32)
-    kt = DeviceArray.zeros((max(knt, 1), 4), np.int32)
-    kc = None if cols is None else DeviceArray.zeros((max(knv, 1), 3), np.uint8)
+    kv, kn, kt, kc = _kept_arrays(knv, knt, cols)
     if nv:
         check("emf_hip_meshSimplifyEmit",
               _L.emf_hip_meshSimplifyEmit(_ptr(scratch), nv, nt, _ptr(soup_bases), _ptr(wbases), n, _ptr(verts),
