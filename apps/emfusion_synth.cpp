@@ -8,7 +8,7 @@
 //                  [--distance-field] [--distance-cap M] [--distance-unknown-obstacle] [--distance-nearest]
 //                  [--frontiers] [--frontier-min-voxels N] [--frontier-clearance M]
 //                  [--plan] [--plan-clearance M] [--plan-through-unknown] [--plan-shortcut W] [--object-shapes]
-//                  [--object-contacts] [--contact-touch M]
+//                  [--object-contacts] [--contact-touch M] [--absorb-objects] [--turn-away F]
 //                  [--ground-map] [--ground-up X,Y,Z] [--ground-cell M] [--ground-bin M] [--ground-band LO,HI]
 //                  [--ground-robot-height M] [--ground-max-step M] [--planes] [--planes-angle DEG] [--planes-min-votes N]
 //                  [--plane-patches] [--plane-patch-reach R] [--plane-patch-min N]
@@ -132,6 +132,15 @@ static bool objectShapesOut = false;
 // and normal; --contact-touch M: the touching threshold in metres (default: one voxel of the probe);
 // without --object-contacts no output byte changes
 static bool objectContactsOut = false, contactTouchGiven = false;
+// --absorb-objects (needs --out): an object that the clean-up deletes because it left view is first absorbed into the
+// background volume (the band of its signed-distance volume, not the free space around it), and
+// writeResults also writes OUT/absorbed.txt, one line per absorbed object; without it no output byte changes.  Objects
+// are deleted only where the clean-up runs: on a dataset, with --autonomous, or from the frame of --turn-away on; on the
+// plain synthetic stream the switch would do nothing and is refused.
+static bool absorbObjects = false;
+// --turn-away F (synthetic stream with given poses, not --autonomous): from frame F on the camera pose handed in looks
+// the other way (half a turn about its y axis) and the clean-up runs, so every object leaves view and is deleted at F
+static int turnAway = -1;
 static double contactTouch = -1.0;
 // --ground-map (needs --out): writeResults also writes OUT/ground.bin and OUT/ground.txt, the 2-D traversability map of
 // the whole background with a floor height per cell; --ground-up X,Y,Z (world frame; default: minus the
@@ -276,6 +285,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     if (planShortcut > 0) emf.setPlanShortcutOutput(planShortcut);
     if (objectShapesOut) emf.setShapeOutput(true);
     if (objectContactsOut) emf.setContactsOutput(true, contactTouch);
+    if (absorbObjects) emf.setAbsorbObjects(true), emf.setAbsorbedOutput(true);  // (not stored in a checkpoint: set again on --resume)
     if (groundOut.on) emf.setGroundOutput(groundOut);
     if (groundUpFloor) emf.setGroundUpFloor(true);
     if (planesOut.on) emf.setPlanesOutput(planesOut);
@@ -391,6 +401,8 @@ int main(int argc, char** argv) {
         else if (a == "--distance-nearest") distanceNearest = true;
         else if (a == "--object-shapes") objectShapesOut = true;
         else if (a == "--object-contacts") objectContactsOut = true;
+        else if (a == "--absorb-objects") absorbObjects = true;
+        else if (a == "--turn-away" && i + 1 < argc) turnAway = std::atoi(argv[++i]);
         else if (a == "--contact-touch" && i + 1 < argc) contactTouchGiven = true, contactTouch = std::atof(argv[++i]);
         else if (a == "--ground-map") groundOut.on = true;
         else if (a == "--ground-up" && i + 1 < argc && std::string(argv[i + 1]) == "floor") groundGiven = true, groundUpFloor = true, ++i;
@@ -468,6 +480,20 @@ int main(int argc, char** argv) {
     if ((patchesGiven && !patchesOut.on) || (patchesOut.on && (!planesOut.on || patchesOut.reach < 1 || patchesOut.reach > EMF_PLANE_MAX_REACH))) {
         std::fprintf(stderr, "usage: emfusion_synth: --plane-patch-reach R (1 or 2) and --plane-patch-min N need --plane-patches, which "
                              "adds the patch lines to planes.txt and needs --planes\n");
+        return 2;
+    }
+    if (absorbObjects && outDir.empty()) {
+        std::fprintf(stderr, "usage: emfusion_synth: --absorb-objects writes absorbed.txt and needs --out DIR\n");
+        return 2;
+    }
+    if (turnAway != -1 && (turnAway < 1 || autonomous || !sequence.empty() || !dataDir.empty())) {
+        std::fprintf(stderr, "usage: emfusion_synth: --turn-away F (>= 1) turns the camera pose handed to the synthetic stream; "
+                             "it excludes --autonomous, --sequence and --dir, where the pose is tracked\n");
+        return 2;
+    }
+    if (absorbObjects && sequence.empty() && dataDir.empty() && !autonomous && turnAway < 0) {
+        std::fprintf(stderr, "usage: emfusion_synth: --absorb-objects acts where the clean-up deletes objects: with --sequence / "
+                             "--dir, --autonomous or --turn-away F; on the plain synthetic stream it would do nothing\n");
         return 2;
     }
     if ((contactTouchGiven && (!objectContactsOut || !(contactTouch >= 0.0))) || (objectContactsOut && outDir.empty())) {
@@ -564,6 +590,7 @@ int main(int argc, char** argv) {
         if (planShortcut > 0) emf.setPlanShortcutOutput(planShortcut);
         if (objectShapesOut) emf.setShapeOutput(true);
         if (objectContactsOut) emf.setContactsOutput(true, contactTouch);
+        if (absorbObjects) emf.setAbsorbObjects(true), emf.setAbsorbedOutput(true);
         if (groundOut.on) emf.setGroundOutput(groundOut);
         if (groundUpFloor) emf.setGroundUpFloor(true);
         if (planesOut.on) emf.setPlanesOutput(planesOut);
@@ -587,10 +614,18 @@ int main(int argc, char** argv) {
                     emf.mainStream().waitForCompletion();  // host buffer is reused
                 }
             if (!autonomous) {
+                const bool turned = turnAway >= 0 && f >= turnAway;
+                if (turned) {  // x and z of the camera's frame flip: it looks the other way; no masks of what it cannot see
+                    in.cam_pose = emf::Affine3f(in.cam_pose.rotation() * emf::Matx33f(-1, 0, 0, 0, 1, 0, 0, 0, -1),
+                                                in.cam_pose.translation());
+                    in.runMasks = false;
+                    in.cleanUp = true;
+                }
                 for (int k = 0; k < objects; ++k)
-                    in.obj_poses[ids[k]] = emf::Affine3f(emf::Matx33f::eye(), scene.sphereCenter(k, f));
+                    if (emf.getObject(ids[k])) in.obj_poses[ids[k]] = emf::Affine3f(emf::Matx33f::eye(), scene.sphereCenter(k, f));
                 if (in.runMasks)
-                    for (int k = 0; k < objects; ++k) in.masks[ids[k]] = maskDev[k].view();
+                    for (int k = 0; k < objects; ++k)
+                        if (emf.getObject(ids[k])) in.masks[ids[k]] = maskDev[k].view();
             } else {
                 in.trackCamera = in.trackObjects = f > 0;
                 in.cleanUp = true;
@@ -634,6 +669,7 @@ int main(int argc, char** argv) {
                     "integrate %.3f  masks %.3f | visible objects %zu | batched launches: %s\n",
                     t.points, t.estep, t.raycast, t.composite, t.integrate, t.masks,
                     emf.visibleObjects().size(), emf.usesBatchedLaunches() ? "yes" : "no");
+        if (absorbObjects) std::printf("absorbed into the background: %zu objects\n", emf.absorbed().size());
         if (!outDir.empty()) {
             emf.writeResults(outDir, false);  // volumes follow setupOutput, as in the reference
             const emf::Mesh bg = emf.getMesh(0);

@@ -103,6 +103,10 @@ def main():
                     help="also write OUT/contacts.txt: one line per ordered pair (probe object, field object or background) "
                          "with a sampled surface voxel: the ids, the eight counts, min_s (1: at least one truncation distance "
                          "apart, not a distance) and the world contact point and normal")
+    ap.add_argument("--absorb-objects", dest="absorb_objects", action="store_true",
+                    help="absorb an object that the clean-up deletes because it left view into the background volume first "
+                         "(the band of its signed-distance volume, not the free space around it) and also write "
+                         "OUT/absorbed.txt: one line per absorbed object")
     ap.add_argument("--contact-touch", dest="contact_touch", type=float, default=None, metavar="M",
                     help="with --object-contacts: the touching threshold in metres (default: one voxel of the probe)")
     ap.add_argument("--ground-map", dest="ground_map", action="store_true",
@@ -245,6 +249,8 @@ def main():
     if args.world_queries:
         fus.set_query_extent("world")
     fus.set_ignore_person(args.ignore_person)
+    if args.absorb_objects:
+        fus.set_absorb_objects(True)
     fus.set_preprocess(True)
     fus.set_cleanup(True)
     fus.setup_output(args.frame_meshes, args.volumes, args.world_mesh, exp_distance_field=args.distance_field,
@@ -254,7 +260,7 @@ def main():
                      plan_clearance=max(args.plan_clearance, 0.0), plan_through_unknown=args.plan_through_unknown,
                      exp_distance_nearest=args.distance_nearest, exp_plan_shortcut=args.plan_shortcut,
                      exp_object_shapes=args.object_shapes, exp_object_contacts=args.object_contacts,
-                     contact_touch=args.contact_touch, exp_ground_map=args.ground_map,
+                     contact_touch=args.contact_touch, exp_absorbed=args.absorb_objects, exp_ground_map=args.ground_map,
                      ground_up=None if args.ground_up is None else "floor" if args.ground_up == "floor"
                      else [float(v) for v in args.ground_up.split(",")],
                      exp_planes=args.planes, planes_angle=args.planes_angle, planes_min_votes=args.planes_min_votes,

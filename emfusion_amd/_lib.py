@@ -237,6 +237,8 @@ SIGNATURES = {
     "emf_hip_planePatches": [_FP, _FP, _FP, _FP, C.c_uint32, _I3, C.POINTER(C.c_float), C.c_int32, C.c_int64, C.c_uint32, _FP,
                              _FP, C.c_int32, _FP, _STREAM],
     "emf_hip_contactProbe": [_FP, C.POINTER(C.c_int32), C.c_int32, _FP, C.c_void_p, C.c_int32, _FP, _STREAM],
+    "emf_hip_absorbVolume": [_FP, _FP, _I3, C.c_float, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_float),
+                             C.POINTER(C.c_float), _I3, _I3, _FP, _STREAM],
 }
 
 
@@ -310,6 +312,13 @@ class EmfOccObject(C.Structure):
                 ("size", C.c_int32 * 3)]
 
 
+class EmfAbsorbSource(C.Structure):
+    """Mirror of emf_absorb_source_t (include/emf_hip.h "Absorbing a volume"): 56 bytes."""
+
+    _fields_ = [("tsdf", C.c_void_p), ("weights", C.c_void_p), ("fgVolMask", C.c_void_p), ("unseenTiles", C.c_void_p),
+                ("res", C.c_int32 * 3), ("voxelSize", C.c_float), ("truncdist", C.c_float), ("reserved", C.c_int32)]
+
+
 OCC_FREE, OCC_OCCUPIED, OCC_UNKNOWN = 0, 1, 2
 DF_FAR = 0x7fffffff
 DF_NONE = -1  # nearest site: none (exactly where d2 is DF_FAR)
@@ -366,6 +375,9 @@ CONTACT_SIDE_DTYPE = [("res", "<i4", 3), ("voxel_size", "<f4"), ("truncdist", "<
 CONTACT_SUMMARY_DTYPE = [("state", "<i4"), ("saturated", "<i4"), ("direction", "<i4"), ("has_normal", "<i4"),
                          ("distance_m", "<f8"), ("point", "<f8", 3), ("normal", "<f8", 3), ("corners", "<f8", 24)]
 CONTACT_MAX_PAIRS = 65535
+# include/emf_hip.h "Absorbing a volume": emf_absorb_t (88 bytes); emf_absorb_source_t is EmfAbsorbSource below
+ABSORB_DTYPE = [("visited", "<u8"), ("outside", "<u8"), ("unknown", "<u8"), ("masked", "<u8"), ("saturated", "<u8"),
+                ("fused", "<u8"), ("fresh", "<u8"), ("solid", "<u8"), ("lo", "<i4", 3), ("hi", "<i4", 3)]
 CONTACT_UNSEEN, CONTACT_APART, CONTACT_TOUCHING, CONTACT_PENETRATING = 0, 1, 2, 3
 CONTACT_STATES = ("unseen", "apart", "touching", "penetrating")
 RAY_REACHED, RAY_BLOCKED, RAY_LEFT, RAY_OUTSIDE, RAY_INVALID = 0, 1, 2, 3, 4

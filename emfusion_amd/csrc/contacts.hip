@@ -18,7 +18,7 @@
 //   k_ct_init / k_ct_finish  one lane per record: the neutral records before the pass, the key of min_s -> f32 bits
 //                after it.
 // Every float step is one float32 operation: the _rn intrinsics, and every product that feeds a sum goes through an
-// identity DPP move (ct_rounded), so that a build with -ffp-contract=fast has no product left to fuse (DESIGN.md 5.26
+// identity DPP move (mul_rounded of wave_ops.hpp), so that a build with -ffp-contract=fast has no product left to fuse (DESIGN.md 5.26
 // "CONTRACTION").  Integer atomics only: the records do not depend on the order of lanes, waves or workgroups.
 #include "common.hpp"
 #include "wave_ops.hpp"
@@ -61,14 +61,6 @@ __device__ __forceinline__ unsigned ct_float_key(float v) {
 }
 __device__ __forceinline__ unsigned ct_key_bits(unsigned k) { return (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k; }
 
-// v, through a DPP move with the identity lane pattern: a value the compiler cannot look through, so a product that
-// went through here is no product to -ffp-contract=fast any more (planes.hip pp_rounded)
-__device__ __forceinline__ float ct_rounded(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xE4 /* quad_perm 0, 1, 2, 3 */, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float ct_mul(float a, float b) { return ct_rounded(__fmul_rn(a, b)); }
-// (1 - f) * c0 + f * c1 with g = 1 - f: two products, one sum
-__device__ __forceinline__ float ct_lerp(float g, float f, float c0, float c1) { return __fadd_rn(ct_mul(g, c0), ct_mul(f, c1)); }
 __device__ __forceinline__ bool ct_finite(float v) { return fabsf(v) < __uint_as_float(0x7f800000u); }  // false for NaN
 
 __global__ __launch_bounds__(kCtBlock) void k_ct_probe(const ContactArgs a) {
@@ -130,9 +122,9 @@ __global__ __launch_bounds__(kCtBlock) void k_ct_probe(const ContactArgs a) {
         const V3 halfB = half_extent(nb);
         const float fnx = static_cast<float>(nb.x), fny = static_cast<float>(nb.y), fnz = static_cast<float>(nb.z);
         // the first two products of every row, summed left to right
-        const float r0 = __fadd_rn(ct_mul(pr.R[0], pax), ct_mul(pr.R[1], pay));
-        const float r1 = __fadd_rn(ct_mul(pr.R[3], pax), ct_mul(pr.R[4], pay));
-        const float r2 = __fadd_rn(ct_mul(pr.R[6], pax), ct_mul(pr.R[7], pay));
+        const float r0 = __fadd_rn(mul_rounded(pr.R[0], pax), mul_rounded(pr.R[1], pay));
+        const float r1 = __fadd_rn(mul_rounded(pr.R[3], pax), mul_rounded(pr.R[4], pay));
+        const float r2 = __fadd_rn(mul_rounded(pr.R[6], pax), mul_rounded(pr.R[7], pay));
 
         unsigned cOut = 0u, cUnk = 0u, cMask = 0u, cSam = 0u, cIn = 0u, cTouch = 0u, cNorm = 0u;
         unsigned sx = 0u, sy1 = 0u, sz1 = 0u, key = 0xffffffffu;
@@ -142,9 +134,9 @@ __global__ __launch_bounds__(kCtBlock) void k_ct_probe(const ContactArgs a) {
         for (unsigned bits = surf; bits != 0u; bits &= bits - 1u) {
             const int z = z0 + (__ffs(bits) - 1);
             const float paz = __fmul_rn(__fsub_rn(static_cast<float>(z), halfAz), voxA);
-            const float pbx = __fadd_rn(__fadd_rn(r0, ct_mul(pr.R[2], paz)), pr.t[0]);
-            const float pby = __fadd_rn(__fadd_rn(r1, ct_mul(pr.R[5], paz)), pr.t[1]);
-            const float pbz = __fadd_rn(__fadd_rn(r2, ct_mul(pr.R[8], paz)), pr.t[2]);
+            const float pbx = __fadd_rn(__fadd_rn(r0, mul_rounded(pr.R[2], paz)), pr.t[0]);
+            const float pby = __fadd_rn(__fadd_rn(r1, mul_rounded(pr.R[5], paz)), pr.t[1]);
+            const float pbz = __fadd_rn(__fadd_rn(r2, mul_rounded(pr.R[8], paz)), pr.t[2]);
             const float qx = __fadd_rn(__fdiv_rn(pbx, voxB), halfB.x);
             const float qy = __fadd_rn(__fdiv_rn(pby, voxB), halfB.y);
             const float qz = __fadd_rn(__fdiv_rn(pbz, voxB), halfB.z);
@@ -165,10 +157,10 @@ __global__ __launch_bounds__(kCtBlock) void k_ct_probe(const ContactArgs a) {
             const bool seen = w0 > 0.f && w1 > 0.f && w2 > 0.f && w3 > 0.f && w4 > 0.f && w5 > 0.f && w6 > 0.f && w7 > 0.f;
             // blend8 of common.hpp, its products made opaque: x pairs, then y, then z
             const float gx = __fsub_rn(1.f, fx), gy = __fsub_rn(1.f, fy), gz = __fsub_rn(1.f, fz);
-            const float a0 = ct_lerp(gx, fx, t0, t1), a1 = ct_lerp(gx, fx, t2, t3), a2 = ct_lerp(gx, fx, t4, t5),
-                        a3 = ct_lerp(gx, fx, t6, t7);
-            const float b0 = ct_lerp(gy, fy, a0, a1), b1 = ct_lerp(gy, fy, a2, a3);
-            const float s = ct_lerp(gz, fz, b0, b1);
+            const float a0 = lerp_rounded(gx, fx, t0, t1), a1 = lerp_rounded(gx, fx, t2, t3), a2 = lerp_rounded(gx, fx, t4, t5),
+                        a3 = lerp_rounded(gx, fx, t6, t7);
+            const float b0 = lerp_rounded(gy, fy, a0, a1), b1 = lerp_rounded(gy, fy, a2, a3);
+            const float s = lerp_rounded(gz, fz, b0, b1);
             if (!seen || !(s == s)) {
                 cUnk += 1u;
                 continue;

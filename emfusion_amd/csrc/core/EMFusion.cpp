@@ -127,6 +127,8 @@ void EMFusion::reset() {
     bgBackStale = false;
     bgPrepared = false;
     bgListPending = false;
+    absorbLog_.clear();  // session state; the switch stays
+    absorbDirty_ = false;
     colorImageSet = false;
     motionInfo.clear();
     motionFired = false;

@@ -601,6 +601,38 @@ public:
     /** writeResults also writes contacts.txt (writeContacts); without it no output byte changes. */
     void setContactsOutput(bool on, double touchMetres = -1.0) { expContacts_ = on, expContactTouch_ = touchMetres; }
     void writeContacts(const std::string& dir);
+    /** One absorption: what went where, and what became of the voxels of the box. */
+    struct AbsorbEvent {
+        int id = 0;             // the object that was absorbed
+        int frame = 0;          // the frame index (frames()) at which it happened
+        float R[9], t[3];       // the pose used: the object's volume frame <- the background's volume frame
+        int32_t lo[3], size[3]; // the box of background voxels the launch covered
+        bool clipped = false;   // the object's cube (background voxels, rounded outwards) leaves the background's: lost
+        emf_absorb_t record;    // include/emf_hip.h "Absorbing a volume"
+    };
+    /**
+     * Absorbing objects into the background (include/emf_hip.h "Absorbing a volume").  Off by default and
+     * sticky.  When on, an object that cleanUpObjs deletes BECAUSE IT IS NOT VISIBLE any more has the band of its signed-
+     * distance volume resampled through the relative pose into the background's front copy and fused there by the
+     * background's running average, before it is erased -- so that the distance field, the planner, the ground map,
+     * the world mesh, the tile store and a checkpoint keep what the robot mapped a second ago.  Objects deleted as
+     * spurious (low existence, association mass below assocThresh) and a person under ignore_person are not absorbed.
+     * IT CARRIES THE BAND ONLY, not the free space around it; colour is not touched; an absorbed object that later moves
+     * leaves a ghost until free space carves it; what lies outside the background's cube is clipped and lost.
+     * The log (absorbed()) is session state: neither it nor the switch is written to a checkpoint, reset() clears the
+     * log.  With the switch off no launch, no output byte and no checkpoint byte changes.  Refused (EMF_E_ARG) on the
+     * sharded path.
+     */
+    void setAbsorbObjects(bool on);
+    bool absorbObjects() const { return absorbOn_; }
+    /** Absorbs the live object `id` now and removes it from the session as a deletion would (kept mesh, exp_vols copy).
+     *  An explicit call absorbs what it names, a person under ignore_person too.
+     *  Refuses (EMF_E_ARG) an unknown id, the background and an object this rank does not own. */
+    AbsorbEvent absorbObject(int id);
+    const std::vector<AbsorbEvent>& absorbed() const { return absorbLog_; }
+    /** writeResults also writes absorbed.txt (writeAbsorbed); without it no output byte changes. */
+    void setAbsorbedOutput(bool on) { expAbsorbed_ = on; }
+    void writeAbsorbed(const std::string& dir);
     /** The result of groundMap(): the frame, the pose "ground metres -> world" and the arrays left on the device. */
     struct GroundMap {
         QueryBox box;
@@ -1167,7 +1199,8 @@ private:
     DeviceBuffer verdictDev;    // ... sharded: EMF_MAX_MODELS float verdicts by list position (all-reduced)
     DeviceBuffer lifecycleMsg;  // sharded: the 16-byte messages of initNewObjVolume / updateObject
     void deleteObj(int id);
-    void deleteOwned(std::list<ObjTSDF>::iterator it);  // cleanUpObjs' removal of an object of this rank
+    // cleanUpObjs' removal of an object of this rank; absorb: into the background first (setAbsorbObjects)
+    void deleteOwned(std::list<ObjTSDF>::iterator it, bool absorb = false);
     void ensureLifecycleBuffers();
     // layout of lifecycleHost: emf_point_stats_t / 513 x u32 / EMF_MAX_MODELS x emf_mask_mass_t, then EMF_MAX_MODELS
     // floats (verdicts, messages), then EMF_MAX_MODELS int32 (gate)
@@ -1318,6 +1351,16 @@ private:
     DeviceBuffer ctScratch;          // the compact model table, the pairs and the records of one call
     bool expContacts_ = false;       // setContactsOutput
     double expContactTouch_ = -1.0;
+
+    // ---- absorbing objects (setAbsorbObjects, absorbObject; EMFusionAbsorb.cpp): never in a checkpoint; behind all
+    // existing members ----
+    bool absorbOn_ = false;          // setAbsorbObjects
+    bool absorbDirty_ = false;       // the background's front copy was written and volumesWritten() is still owed
+    std::vector<AbsorbEvent> absorbLog_;
+    DeviceBuffer absorbRecord_;      // one emf_absorb_t
+    bool expAbsorbed_ = false;       // setAbsorbedOutput
+    void absorbInto(ObjTSDF& obj);   // the launch and the log entry, on main; the caller has quiesced
+    void absorbFinish();             // volumesWritten once after the last absorption, before rebuildModelTable()
 };
 
 /**
@@ -1391,6 +1434,12 @@ void shapeBox(const emf_shape_moments_t& mom, const emf_shape_frame_t& frame, co
  * contactSummary: the unordered pair from the record a -> b and, where there is one, b -> a (else nullptr).
  */
 void contactPose(const float Ra[9], const float ta[3], const float Rb[9], const float tb[3], float R[9], float t[3]);
+/**
+ * What an absorption carries: (R, t) taking the DESTINATION's volume frame into the SOURCE's, from the
+ * poses (world <- volume) of the destination d and the source s, float64 in the fixed order of contactPose with a = d and
+ * b = s, rounded to f32 once: R_ij = float((Rs_0i * Rd_0j + Rs_1i * Rd_1j) + Rs_2i * Rd_2j), t likewise from td - ts.
+ */
+void absorbPose(const float Rd[9], const float td[3], const float Rs[9], const float ts[3], float R[9], float t[3]);
 float contactTouch(double touchMetres, float truncdistB);
 void contactSummary(const emf_contact_t& ab, const emf_contact_t* ba, const emf_contact_side_t& a, const emf_contact_side_t& b,
                     emf_contact_summary_t& out);

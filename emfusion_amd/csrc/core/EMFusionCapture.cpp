@@ -47,6 +47,7 @@ void EMFusion::writeResults(const std::string& dir, bool volumes) {
     if (expGround_.on) writeGround(dir);        // ground.bin + ground.txt of the whole background (5.24)
     if (expPlanes_.on) writePlanes(dir);        // planes.txt of the whole background (5.25)
     if (expContacts_) writeContacts(dir);       // contacts.txt of the live objects and the background (5.27)
+    if (expAbsorbed_) writeAbsorbed(dir);       // absorbed.txt, the session's log of absorbed objects (5.29)
     if (expFrameMeshes_) {  // writeFrameMeshes (EMFusion.cpp:1158-1185); the reference creates frame_meshes/ always
         auto writeAll = [](const std::string& d, const std::map<int, Mesh>& log) {
             io::createDirectories(d);

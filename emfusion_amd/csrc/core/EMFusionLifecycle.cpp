@@ -436,9 +436,11 @@ void EMFusion::deleteObj(int id) {  // reference EMFusion.cpp:982-989
 }
 
 // The deletion of an object of this rank (EMFusion.cpp:951-976); the caller rebuilds the table afterwards.
-void EMFusion::deleteOwned(std::list<ObjTSDF>::iterator it) {
+void EMFusion::deleteOwned(std::list<ObjTSDF>::iterator it, bool absorb) {
     const int id = it->getID();
     quiesce();  // nothing in flight may still use the volume
+    // gone from view with setAbsorbObjects on: its band goes into the background first
+    if (absorb && !(ignorePerson && isPerson(*it))) absorbInto(*it);
     deleteObj(id);
     if (poseLog && !(ignorePerson && isPerson(*it))) {
         meshes[id] = it->getMesh();  // saveOutput: EMFusion.cpp:962-966
@@ -495,11 +497,12 @@ std::vector<int> EMFusion::cleanUpObjs(bool maskFrame, const std::map<int, emf_i
             const int id = it->getID();
             if (spurious.count(id) || !vis_objs.count(id)) {
                 deleted.push_back(id);
-                deleteOwned(it++);
+                deleteOwned(it++, absorbOn_ && !spurious.count(id));  // absorbed: deleted because it is not visible, only
             } else {
                 ++it;
             }
         }
+        absorbFinish();  // once, after the last deletion and before the table is rebuilt
         if (!deleted.empty()) rebuildModelTable();
         return deleted;
     }

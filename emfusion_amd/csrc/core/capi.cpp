@@ -1072,6 +1072,61 @@ int emf_fusion_set_contacts_output(emf_fusion_t* h, int on, double touch_m) {
     return guarded([&] { h->impl->setContactsOutput(on != 0, touch_m); });
 }
 
+static_assert(sizeof(emf_absorb_event_t) == 176, "mirrored by emfusion_amd/pipeline.py");
+
+static emf_absorb_event_t absorbEvent(const EMFusion::AbsorbEvent& e) {
+    emf_absorb_event_t o{};
+    o.id = e.id, o.frame = e.frame, o.clipped = e.clipped ? 1 : 0;
+    std::copy(e.R, e.R + 9, o.R);
+    std::copy(e.t, e.t + 3, o.t);
+    std::copy(e.lo, e.lo + 3, o.lo);
+    std::copy(e.size, e.size + 3, o.size);
+    o.record = e.record;
+    return o;
+}
+
+int emf_fusion_absorb_pose(const float Rd[9], const float td[3], const float Rs[9], const float ts[3], float R[9], float t[3]) {
+    REQ(Rd);
+    REQ(td);
+    REQ(Rs);
+    REQ(ts);
+    REQ(R);
+    REQ(t);
+    return guarded([&] { absorbPose(Rd, td, Rs, ts, R, t); });
+}
+
+int emf_fusion_set_absorb_objects(emf_fusion_t* h, int on) {
+    REQ(h);
+    return guarded([&] { h->impl->setAbsorbObjects(on != 0); });
+}
+
+int emf_fusion_absorb_object(emf_fusion_t* h, int32_t id, emf_absorb_event_t* event) {
+    REQ(h);
+    return guarded([&] {
+        const EMFusion::AbsorbEvent e = h->impl->absorbObject(id);
+        if (event) *event = absorbEvent(e);
+    });
+}
+
+int emf_fusion_absorbed(emf_fusion_t* h, emf_absorb_event_t* events, int32_t capacity, int32_t* count) {
+    REQ(h);
+    REQ(count);
+    if (capacity < 0 || (capacity > 0 && !events)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_absorbed: capacity %d without a list", capacity);
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const std::vector<EMFusion::AbsorbEvent>& log = h->impl->absorbed();
+        *count = static_cast<int32_t>(log.size());
+        for (size_t k = 0; k < log.size() && k < static_cast<size_t>(capacity); ++k) events[k] = absorbEvent(log[k]);
+    });
+}
+
+int emf_fusion_set_absorbed_output(emf_fusion_t* h, int on) {
+    REQ(h);
+    return guarded([&] { h->impl->setAbsorbedOutput(on != 0); });
+}
+
 int emf_fusion_planes(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], const emf_plane_params_t* params,
                       int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3], uint32_t counters[4], uint32_t* min_votes,
                       emf_plane_t* planes, int32_t capacity, int32_t* count) {

@@ -50,6 +50,18 @@ __device__ __forceinline__ T wave_inclusive_scan(T v) {
     return v;
 }
 
+// v, through a DPP move with the identity lane pattern: a value the compiler cannot look through, so a product that
+// went through here is no product to -ffp-contract=fast any more (DESIGN.md 5.26 "CONTRACTION").  For the kernels whose
+// bytes must not depend on contraction: every product that feeds a sum goes through mul_rounded.
+__device__ __forceinline__ float rounded(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xE4 /* quad_perm 0, 1, 2, 3 */, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float mul_rounded(float a, float b) { return rounded(__fmul_rn(a, b)); }
+// (1 - f) * c0 + f * c1 with g = 1 - f: two products, one sum
+__device__ __forceinline__ float lerp_rounded(float g, float f, float c0, float c1) {
+    return __fadd_rn(mul_rounded(g, c0), mul_rounded(f, c1));
+}
+
 // Op over the 64 lanes of the wave, in every lane
 template <typename Op, typename T>
 __device__ __forceinline__ T wave_reduce(T v) {

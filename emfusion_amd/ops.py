@@ -2072,6 +2072,60 @@ def contact_probe(volumes, pairs, out=None, stream=None, lib=None):
     return records.numpy()[:n] if out is None else out
 
 
+# ---- absorbing a volume (include/emf_hip.h "Absorbing a volume") -----------------------------------
+
+ABSORB_DTYPE = np.dtype(_lib.ABSORB_DTYPE)
+assert ABSORB_DTYPE.itemsize == 88 and C.sizeof(_lib.EmfAbsorbSource) == 56
+
+
+def absorb_box(dst_res, dst_voxel_size, src_res, src_voxel_size, pose):
+    """The covering box (lo, size), both (x, y, z), of a whole source in a destination of resolution dst_res (x, y, z):
+    emf_hip_occupancyObjectBox of the source's corners through the inverse of pose = (R, t), source frame <-
+    destination frame.  A source that misses the destination gives a size of 0."""
+    o = _lib.EmfOccObject()
+    o.res = _i3(src_res)
+    o.voxelSize = float(src_voxel_size)
+    o.R, o.t = _f(pose[0], 9), _f(pose[1], 3)
+    check("emf_hip_occupancyObjectBox", _L.emf_hip_occupancyObjectBox(C.byref(o), _i3(dst_res), float(dst_voxel_size)))
+    return tuple(o.lo), tuple(o.size)
+
+
+def absorb_volume(dst, src, pose, box=None, out=None, lib=None, stream=None):
+    """emf_hip_absorbVolume: the signed-distance band of `src` resampled through pose = (R, t) (f32, source frame <-
+    destination frame) into `dst` and fused there, in place, by dst's running average.
+    dst: dict(tsdf=, weights=, voxel_size=, truncdist=, max_weight=), (Nz, Ny, Nx) f32 device arrays of any shape from
+    (1, 1, 1); src: dict(tsdf=, weights=, voxel_size=, truncdist=, fg_mask=None, unseen_tiles=None), only read.
+    box: (lo, size) in destination voxels, (x, y, z); None: the covering box of the whole source (absorb_box).
+    Returns the record (a 0-d numpy array of ABSORB_DTYPE: visited = outside + unknown + masked + saturated + fused;
+    fresh, solid; lo, hi of the fused voxels), or with out= (a device array of at least one record) that array.
+    IT CARRIES THE BAND, NOT THE FREE SPACE AROUND IT: saturated source samples are left alone.  lib: another build of
+    the kernel library (_lib.load_variant)."""
+    L = _L if lib is None else lib
+    tsdf, weights = _vol(dst["tsdf"], np.float32), _vol(dst["weights"], np.float32)
+    stsdf, sweights = _vol(src["tsdf"], np.float32), _vol(src["weights"], np.float32)
+    assert weights.shape == tsdf.shape and sweights.shape == stsdf.shape
+    res = (tsdf.shape[2], tsdf.shape[1], tsdf.shape[0])
+    s = _lib.EmfAbsorbSource()
+    s.tsdf, s.weights = stsdf.ptr, sweights.ptr
+    if src.get("fg_mask") is not None:
+        assert src["fg_mask"].shape == stsdf.shape
+        s.fgVolMask = _vol(src["fg_mask"], np.uint8).ptr
+    if src.get("unseen_tiles") is not None:
+        s.unseenTiles = src["unseen_tiles"].ptr
+    s.res = _i3((stsdf.shape[2], stsdf.shape[1], stsdf.shape[0]))
+    s.voxelSize, s.truncdist = float(np.float32(src["voxel_size"])), float(np.float32(src["truncdist"]))
+    if box is None:
+        box = absorb_box(res, dst["voxel_size"], tuple(s.res), src["voxel_size"], pose)
+    lo, size = _box(res, box)
+    record = DeviceArray((1,), ABSORB_DTYPE) if out is None else out
+    assert record.dtype == ABSORB_DTYPE and record.shape[0] >= 1
+    check("emf_hip_absorbVolume",
+          L.emf_hip_absorbVolume(_ptr(tsdf), _ptr(weights), _i3(res), float(np.float32(dst["voxel_size"])),
+                                 float(np.float32(dst["truncdist"])), float(np.float32(dst["max_weight"])), C.byref(s),
+                                 _f(pose[0], 9), _f(pose[1], 3), _i3(lo), _i3(size), _ptr(record), _stream(stream)))
+    return record.numpy()[0] if out is None else out
+
+
 # ---- ground map (include/emf_hip.h "Ground map", DESIGN.md 5.24) -------------------------------------------------
 
 GROUND_CELL_DTYPE = np.dtype(_lib.GROUND_CELL_DTYPE)

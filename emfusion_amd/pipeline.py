@@ -186,6 +186,11 @@ def load() -> C.CDLL:
         "emf_fusion_contact_touch": [C.c_double, C.c_float, fp],
         "emf_fusion_contact_summary": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
         "emf_fusion_set_contacts_output": [vp, C.c_int, C.c_double],
+        "emf_fusion_absorb_pose": [fp, fp, fp, fp, fp, fp],
+        "emf_fusion_set_absorb_objects": [vp, C.c_int],
+        "emf_fusion_absorb_object": [vp, C.c_int32, C.c_void_p],
+        "emf_fusion_absorbed": [vp, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
+        "emf_fusion_set_absorbed_output": [vp, C.c_int],
         "emf_fusion_planes": [vp, ip, ip, C.c_void_p, ip, ip, fp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                               C.POINTER(C.c_int32)],
         "emf_fusion_copy_plane_labels": [vp, C.c_void_p, C.c_void_p, C.c_int64],
@@ -653,6 +658,38 @@ def contact_line(a, b, record, side_a, side_b):
     ints = [int(record[k]) for k in ("surface", "outside", "unknown", "masked", "sampled", "inside", "touching", "normals")]
     floats = [float(record["min_s"])] + [float(v) for v in s["point"]] + [float(v) for v in s["normal"]]
     return " ".join([str(int(a)), str(int(b))] + [str(v) for v in ints] + ["%.9g" % v for v in floats])
+
+
+def _absorb_event_dtype():
+    """emf_absorb_event_t (include/emf_fusion.h): 176 bytes."""
+    from . import _lib as hip
+    d = np.dtype([("id", "<i4"), ("frame", "<i4"), ("clipped", "<i4"), ("reserved", "<i4"), ("R", "<f4", 9), ("t", "<f4", 3),
+                  ("lo", "<i4", 3), ("size", "<i4", 3), ("record", np.dtype(hip.ABSORB_DTYPE))])
+    assert d.itemsize == 176
+    return d
+
+
+def absorb_pose(pose_bg, pose_obj):
+    """emf_fusion_absorb_pose, on the host without a device: what an absorption carries -- (R, t) taking
+    the DESTINATION's volume frame into the SOURCE's, R = Ro^T Rb, t = Ro^T (tb - to) -- from the poses (R, t: volume ->
+    world, f32) of the background and the object.  Float64 in the fixed operation order of contact_pose(pose_bg,
+    pose_obj), rounded to f32 once."""
+    (Rb, tb), (Ro, to) = pose_bg, pose_obj
+    R, t = np.zeros(9, np.float32), np.zeros(3, np.float32)
+    _check("emf_fusion_absorb_pose",
+           load().emf_fusion_absorb_pose(_farr(Rb, 9), _farr(tb, 3), _farr(Ro, 9), _farr(to, 3),
+                                         R.ctypes.data_as(C.POINTER(C.c_float)), t.ctypes.data_as(C.POINTER(C.c_float))))
+    return R.reshape(3, 3), t
+
+
+def absorbed_line(event):
+    """One line of absorbed.txt (without the newline) from an event of Fusion.absorbed()."""
+    r = event["record"]
+    ints = [event["id"], event["frame"], int(event["clipped"]), *event["lo"], *event["size"]] + \
+        [int(r[k]) for k in ("visited", "outside", "unknown", "masked", "saturated", "fused", "fresh", "solid")] + \
+        [int(v) for v in r["lo"]] + [int(v) for v in r["hi"]]
+    floats = [float(v) for v in np.asarray(event["R"], np.float32).reshape(9)] + [float(v) for v in event["t"]]
+    return " ".join([str(int(v)) for v in ints] + ["%.9g" % v for v in floats])
 
 
 # include/emf_hip.h "Planes": emf_plane_params_t (56 bytes) and emf_plane_t (176)
@@ -1897,6 +1934,47 @@ class Fusion:
                                  corners=None if direction < 0 else u["corners"].reshape(8, 3).copy(), summary=u.copy()))
         return dict(pairs=out_pairs, summaries=out_sums, ids=[int(v) for v in ids_out[:m]], sides=sides[:m].copy())
 
+    @staticmethod
+    def _absorb_event(e):
+        return dict(id=int(e["id"]), frame=int(e["frame"]), clipped=bool(e["clipped"]), R=e["R"].reshape(3, 3).copy(),
+                    t=e["t"].copy(), lo=tuple(int(v) for v in e["lo"]), size=tuple(int(v) for v in e["size"]),
+                    record=e["record"].copy())
+
+    def set_absorb_objects(self, on=True):
+        """Absorb objects that leave view into the background.  Sticky, off by default.  On: an object
+        that the frame's clean-up (set_cleanup) deletes BECAUSE IT IS NOT VISIBLE any more has the band of its signed-
+        distance volume resampled through the relative pose into the background volume and fused there by the
+        background's running average before it is erased, so that distance_field(), plan(), ground_map(), world_mesh(),
+        the tile store and a checkpoint keep what was mapped.  Objects deleted as spurious (low existence, association
+        mass below assocThresh) and a person under set_ignore_person are not absorbed.
+
+        WHAT IT DOES NOT DO: it carries the band, not the free space around it (saturated samples are left alone);
+        colour is not touched; an absorbed object that later moves leaves a ghost until free space carves it; what lies
+        outside the background's cube is clipped and lost; objects are not merged with each other and none is seeded
+        from the background.  Neither the switch nor the log (absorbed()) is written to a checkpoint: no checkpoint byte
+        changes.  Off: no launch and no output byte changes.  Refused on the sharded path."""
+        _check("emf_fusion_set_absorb_objects", load().emf_fusion_set_absorb_objects(self._h, int(bool(on))))
+
+    def absorb_object(self, obj_id):
+        """Absorb the LIVE object obj_id into the background now (see set_absorb_objects; the switch need not be on) and
+        remove it from the session as a deletion would -- leaving it live would let two models explain one surface; with
+        the pose log on its mesh is kept.  An explicit call absorbs what it names, a person under set_ignore_person too.
+        Returns the event: dict(id, frame, clipped, R, t (object volume frame <-
+        background volume frame), lo, size (the box of background voxels), record (ops.ABSORB_DTYPE)).  An unknown id, the
+        background (0) and an object this rank does not own raise; refused on the sharded path."""
+        e = np.zeros((), _absorb_event_dtype())
+        _check("emf_fusion_absorb_object", load().emf_fusion_absorb_object(self._h, int(obj_id), e.ctypes.data))
+        return self._absorb_event(e)
+
+    def absorbed(self):
+        """The session's log of absorbed objects, oldest first: a list of the events of absorb_object().  Session state
+        only: reset() and a loaded checkpoint start it empty, and it is never written to a checkpoint."""
+        n = C.c_int32(0)
+        _check("emf_fusion_absorbed", load().emf_fusion_absorbed(self._h, None, 0, C.byref(n)))
+        events = np.zeros(max(n.value, 1), _absorb_event_dtype())
+        _check("emf_fusion_absorbed", load().emf_fusion_absorbed(self._h, events.ctypes.data, n.value, C.byref(n)))
+        return [self._absorb_event(events[k]) for k in range(n.value)]
+
     def planes(self, box=None, size=None, k=15, angle=20.0, separation=None, bin=None, band=None, min_votes=None, refine=1,
                up_hint=None, floor_angle=30.0, kind_angle=10.0, max_planes=64, labels=False, patches=False, patch_reach=1,
                patch_min_voxels=None):
@@ -2403,7 +2481,7 @@ class Fusion:
                      ground_up=None, ground_cell=None, ground_bin=None, ground_band=(-1.5, 0.5), ground_robot_height=0.3,
                      ground_max_step=0.05, exp_planes=False, planes_angle=20.0, planes_min_votes=None,
                      exp_plane_patches=False, plane_patch_reach=1, plane_patch_min=None, exp_object_contacts=False,
-                     contact_touch=None):
+                     contact_touch=None, exp_absorbed=False):
         """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
         the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
         the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh();
@@ -2438,7 +2516,9 @@ class Fusion:
         exp_object_contacts: write_results also writes contacts.txt, after a comment line one line per ordered pair of
         object_contacts(touch=contact_touch) over the live objects in id order and the background with sampled > 0: the
         ids, the eight counts, then in %.9g min_s and the world contact point and normal of that record
-        (include/emf_fusion.h emf_fusion_set_contacts_output)."""
+        (include/emf_fusion.h emf_fusion_set_contacts_output);
+        exp_absorbed: write_results also writes absorbed.txt, after a comment line one line per event of absorbed():
+        absorbed_line() of it (include/emf_fusion.h emf_fusion_set_absorbed_output)."""
         if contact_touch is not None and not exp_object_contacts:
             raise ValueError("setup_output: contact_touch is the threshold of contacts.txt and needs exp_object_contacts")
         if exp_plan_shortcut and not exp_plan:
@@ -2481,6 +2561,8 @@ class Fusion:
         if exp_object_contacts:  # off: no new call
             _check("emf_fusion_set_contacts_output",
                    load().emf_fusion_set_contacts_output(self._h, 1, -1.0 if contact_touch is None else float(contact_touch)))
+        if exp_absorbed:  # off: no new call
+            _check("emf_fusion_set_absorbed_output", load().emf_fusion_set_absorbed_output(self._h, 1))
         if exp_ground_map:  # off: no new call
             up = None if ground_up is None or up_floor else np.ascontiguousarray(ground_up, np.float64).reshape(3)
             _check("emf_fusion_set_ground_output",

@@ -473,6 +473,48 @@ int emf_fusion_contact_touch(double touch_m, float truncdist_b, float* touch);
 int emf_fusion_contact_summary(const emf_contact_t* ab, const emf_contact_t* ba, const emf_contact_side_t* a,
                                const emf_contact_side_t* b, emf_contact_summary_t* summary);
 int emf_fusion_set_contacts_output(emf_fusion_t* h, int on, double touch_m);
+/* Absorbing objects into the background (include/emf_hip.h "Absorbing a volume"; new behaviour, opt-in).
+ * An object that leaves view is deleted, as in the reference, and every scene query forgets it.  With the switch on its
+ * signed-distance band is first resampled through the relative pose into the background volume and fused there by the
+ * background's own running average, so that the distance field, plans, the ground map, the world mesh, the tile store and
+ * a checkpoint keep it.  IT CARRIES THE BAND ONLY, not the free space around it; colour is not touched (absorbed voxels
+ * keep the background's colour entries); an absorbed object that later moves leaves a ghost until free space carves it;
+ * what lies outside the background's cube is clipped and lost.
+ *   absorb_pose     needs no device and no handle: (R, t) taking the DESTINATION's volume frame into the SOURCE's from the
+ *                   poses (world <- volume) of the destination d and the source s; float64 in the fixed order of
+ *                   contact_pose with a = d, b = s, rounded to f32 once.
+ *   set_absorb_objects  sticky, off by default.  On: an object the frame's clean-up deletes BECAUSE IT IS NOT VISIBLE is
+ *                   absorbed before it is erased -- not one deleted as spurious (low existence on a mask frame, association
+ *                   mass below assocThresh), not a person under ignore_person.  The pose is the object's current pose
+ *                   against the background's current pose (correct after rolls); one launch per object on the main stream,
+ *                   in list order; the background's derived state is renewed once after the last.  The kept mesh and the
+ *                   exp_vols copies of the deleted object stay as they are.  Off: no launch, no output byte and no
+ *                   checkpoint byte changes.  Neither the switch nor the log is written to a checkpoint.
+ *   absorb_object   absorbs the LIVE object `id` now and removes it from the session as a deletion would (leaving it
+ *                   live would let two models explain one surface).  An explicit call absorbs what it names, a person
+ *                   under ignore_person too.  event NULL: not wanted.  EMF_E_ARG: an unknown id, the background (0), an
+ *                   object this rank does not own.
+ *   absorbed        the session's log, oldest first: the first min(capacity, *count) events; *count is the number logged.
+ *                   emf_fusion_reset and a loaded checkpoint start it empty.
+ *   set_absorbed_output  setup_output's exp_absorbed: emf_fusion_write_results also writes absorbed.txt, after a comment
+ *                   line one line per event: id frame clipped, box_lo (3), box_size (3), the eight counts, lo (3), hi (3),
+ *                   then R (9) and t (3) in %.9g.  Off: the set of result files and every byte of them as before.
+ * set_absorb_objects (on) and absorb_object are EMF_E_ARG on the sharded path. */
+typedef struct emf_absorb_event {
+    int32_t id;             /* the absorbed object */
+    int32_t frame;          /* the frame index at which it happened */
+    int32_t clipped;        /* the object's cube, in background voxels rounded outwards, leaves the background's: that part
+                               is lost.  Conservative by less than a voxel; 0 for a pose without a finite inverse */
+    int32_t reserved;       /* 0 */
+    float R[9], t[3];       /* the pose used: the object's volume frame <- the background's volume frame */
+    int32_t lo[3], size[3]; /* the box of background voxels the launch covered */
+    emf_absorb_t record;    /* include/emf_hip.h "Absorbing a volume" */
+} emf_absorb_event_t;       /* 176 bytes */
+int emf_fusion_absorb_pose(const float Rd[9], const float td[3], const float Rs[9], const float ts[3], float R[9], float t[3]);
+int emf_fusion_set_absorb_objects(emf_fusion_t* h, int on);
+int emf_fusion_absorb_object(emf_fusion_t* h, int32_t id, emf_absorb_event_t* event);
+int emf_fusion_absorbed(emf_fusion_t* h, emf_absorb_event_t* events, int32_t capacity, int32_t* count);
+int emf_fusion_set_absorbed_output(emf_fusion_t* h, int on);
 /* Planes (include/emf_hip.h "Planes"; new behaviour, opt-in): the dominant planes of a box of the
  * background (box_lo / box_size NULL: all of it) -- floor, walls, table tops.  A plane is the plane of the SHELL's voxel
  * centres: up to one voxel behind the surface, and nothing corrects that.

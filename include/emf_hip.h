@@ -2394,6 +2394,75 @@ int emf_hip_contactProbe(const emf_model_t* models_dev, const int32_t* res_host,
                          const emf_contact_pair_t* pairs_dev, const emf_contact_pair_t* pairs_host, int32_t n_pairs,
                          emf_contact_t* records_dev, emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Absorbing a volume (new behaviour: DESIGN.md 5.29).  Opt-in; nothing above is touched.  The signed-distance band of
+ * a SOURCE volume is resampled through a rigid pose into a DESTINATION volume and fused there by the destination's own
+ * running average: the one operation that moves geometry from one lattice onto another (roll, spill, fill and
+ * copyValues move whole voxels on one lattice).
+ * IT CARRIES THE BAND, NOT THE FREE SPACE AROUND IT: a saturated source sample (|s| == 1) only says "at least one
+ * source truncation distance away", which with another truncation distance is no value the destination can fuse; such
+ * a voxel is left alone.  Colour is not touched.
+ * Volumes are dense, (z, y, x) order, x fastest, res = (nx, ny, nz); a voxel is v = (x, y, z).  R[9], t[3] (f32,
+ * row-major): the source's volume frame <- the destination's volume frame.  Per destination voxel v of the box
+ * [box_lo, box_lo + box_size), every float step a single float32 operation without contraction, in this order;
+ * everything else is integer.  half_j = float(N_j - 1) / 2.f; rows of R summed left to right; the classes in this
+ * order, the first match wins, and only a FUSED voxel is written:
+ *   sample point (the stamping arithmetic of emf_hip_occupancyStampObjects, the sample point of "Object contacts"):
+ *                    p_d_j = (float(v_j) - half_d_j) * voxelSize_d
+ *                    p_s_i = ((R_i0 * p_d_0 + R_i1 * p_d_1) + R_i2 * p_d_2) + t_i
+ *                    q_i   = p_s_i / voxelSize_s + half_s_i
+ *                    l_i = int(q_i),  f_i = q_i - float(l_i)
+ *     OUTSIDE    some q_j is NaN, q_j < 0 or q_j + 1 >= float(N_j) of the source: the pad-1 rule of "Object contacts".
+ *     UNKNOWN    one of the eight corners l + {0, 1}^3 has !(weights_s > 0), or the blended value s is NaN; s is the
+ *                source's tsdf blended over the cell in x pairs, then y, then z, each (1 - f) * c0 + f * c1 as one
+ *                difference, two products and one sum
+ *     MASKED     the source has an fgVolMask and it is 0 at (rint(q_0), rint(q_1), rint(q_2)), ties to even
+ *     SATURATED  !(fabsf(s) < 1)
+ *     FUSED      everything else.  With ratio = truncdist_s / truncdist_d (one float32 division, made once on the host),
+ *                w_o the minimum of the eight corner weights (exact, whatever the order) and pw, pt the destination's
+ *                weight and tsdf at v:
+ *                    u = min(max(s * ratio, -1), 1)                       equal truncation distances: u == s, bit for bit
+ *                    !(pw > 0):  nt = u,  nw = min(w_o, maxWeight)        FRESH; a select, pt takes no part
+ *                    else:       nt = (pw * pt + w_o * u) / (pw + w_o),  nw = min(pw + w_o, maxWeight)
+ *                SOLID: FUSED and !(nt > 0).  Of tsdf[v] and weights[v] only the words whose bits change are stored.
+ * emf_absorb_t: visited = outside + unknown + masked + saturated + fused (the voxels of the box); fresh, solid <= fused;
+ * lo, hi: the inclusive bounds of the FUSED voxels in the destination, res_d and -1 without one.  Every destination
+ * voxel reads and writes only itself: the pass is in place, and the bytes are a pure function of the inputs whatever
+ * order lanes and workgroups run in.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct emf_absorb_source {
+    const float* tsdf;          /* the source volume (device), only read */
+    const float* weights;
+    const uint8_t* fgVolMask;   /* or NULL: no gate */
+    const uint8_t* unseenTiles; /* or NULL: the source's unseen-tile map (emf_hip_unseenTileBytes(res)); a sample whose
+                                   first corner lies in a tile marked "every weight is 0" is UNKNOWN unread: the bytes are
+                                   the same with the map and without it */
+    int32_t res[3];
+    float voxelSize;
+    float truncdist;
+    int32_t reserved;           /* 0 */
+} emf_absorb_source_t;          /* 56 bytes */
+
+typedef struct emf_absorb {
+    uint64_t visited, outside, unknown, masked, saturated, fused, fresh, solid; /* counts */
+    int32_t lo[3], hi[3];       /* bounds of the fused voxels; res_d and -1 without one */
+} emf_absorb_t;                 /* 88 bytes */
+
+/* dst_tsdf, dst_weights: the whole destination volume (device), written in place; any resolution from 1 x 1 x 1, no slot
+ * of a model table.  record_dev: one record (device, 8-byte aligned), set to the neutral record by a launch of the
+ * call's own on the stream and then counted into with one integer atomic per non-zero quantity and wave.  One workgroup
+ * of 256 lanes per 32 x 8 x 8 destination tile that meets the box; a box with a size of 0 on some axis is empty:
+ * EMF_OK, the neutral record, nothing else written.  The covering box of a whole source is what
+ * emf_hip_occupancyObjectBox computes from (res_s, voxelSize_s, R, t).
+ * Refused with EMF_E_ARG or EMF_E_LIMIT and nothing enqueued: a NULL or misaligned pointer; a destination array that
+ * shares a byte with the other, with an array of the source or with the record (dst == src included); an axis below 1
+ * or above EMF_DF_MAX_AXIS or more than 2^31 - 1 voxels, of either volume (EMF_E_LIMIT above, EMF_E_ARG below); a voxel
+ * size, a truncation distance, maxWeight or the ratio of the truncation distances that is not finite and > 0; a
+ * negative box size or a box that leaves the destination.  Nothing allocates, copies to the host or waits. */
+int emf_hip_absorbVolume(float* dst_tsdf, float* dst_weights, const int32_t dst_res[3], float dst_voxel_size, float dst_truncdist,
+                         float max_weight, const emf_absorb_source_t* source, const float R[9], const float t[3],
+                         const int32_t box_lo[3], const int32_t box_size[3], emf_absorb_t* record_dev, emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
