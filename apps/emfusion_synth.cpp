@@ -8,7 +8,7 @@
 //                  [--distance-field] [--distance-cap M] [--distance-unknown-obstacle] [--distance-nearest]
 //                  [--frontiers] [--frontier-min-voxels N] [--frontier-clearance M]
 //                  [--plan] [--plan-clearance M] [--plan-through-unknown] [--plan-shortcut W] [--object-shapes]
-//                  [--object-contacts] [--contact-touch M] [--absorb-objects] [--turn-away F]
+//                  [--object-contacts] [--contact-touch M] [--absorb-objects] [--turn-away F] [--lift-objects]
 //                  [--ground-map] [--ground-up X,Y,Z] [--ground-cell M] [--ground-bin M] [--ground-band LO,HI]
 //                  [--ground-robot-height M] [--ground-max-step M] [--planes] [--planes-angle DEG] [--planes-min-votes N]
 //                  [--plane-patches] [--plane-patch-reach R] [--plane-patch-min N]
@@ -138,6 +138,11 @@ static bool objectContactsOut = false, contactTouchGiven = false;
 // are deleted only where the clean-up runs: on a dataset, with --autonomous, or from the frame of --turn-away on; on the
 // plain synthetic stream the switch would do nothing and is refused.
 static bool absorbObjects = false;
+// --lift-objects (needs --out): an object created from a mask is seeded with the band the background already holds inside
+// its cube, and the background releases what the object then holds as foreground; writeResults also
+// writes OUT/lifted.txt, one line per lifted object; without it no output byte changes.  Objects are created from masks
+// on a dataset and with --autonomous; on the synthetic stream with given poses the switch would do nothing and is refused.
+static bool liftObjects = false;
 // --turn-away F (synthetic stream with given poses, not --autonomous): from frame F on the camera pose handed in looks
 // the other way (half a turn about its y axis) and the clean-up runs, so every object leaves view and is deleted at F
 static int turnAway = -1;
@@ -286,6 +291,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     if (objectShapesOut) emf.setShapeOutput(true);
     if (objectContactsOut) emf.setContactsOutput(true, contactTouch);
     if (absorbObjects) emf.setAbsorbObjects(true), emf.setAbsorbedOutput(true);  // (not stored in a checkpoint: set again on --resume)
+    if (liftObjects) emf.setLiftObjects(true), emf.setLiftedOutput(true);          // (nor is this)
     if (groundOut.on) emf.setGroundOutput(groundOut);
     if (groundUpFloor) emf.setGroundUpFloor(true);
     if (planesOut.on) emf.setPlanesOutput(planesOut);
@@ -402,6 +408,7 @@ int main(int argc, char** argv) {
         else if (a == "--object-shapes") objectShapesOut = true;
         else if (a == "--object-contacts") objectContactsOut = true;
         else if (a == "--absorb-objects") absorbObjects = true;
+        else if (a == "--lift-objects") liftObjects = true;
         else if (a == "--turn-away" && i + 1 < argc) turnAway = std::atoi(argv[++i]);
         else if (a == "--contact-touch" && i + 1 < argc) contactTouchGiven = true, contactTouch = std::atof(argv[++i]);
         else if (a == "--ground-map") groundOut.on = true;
@@ -484,6 +491,15 @@ int main(int argc, char** argv) {
     }
     if (absorbObjects && outDir.empty()) {
         std::fprintf(stderr, "usage: emfusion_synth: --absorb-objects writes absorbed.txt and needs --out DIR\n");
+        return 2;
+    }
+    if (liftObjects && outDir.empty()) {
+        std::fprintf(stderr, "usage: emfusion_synth: --lift-objects writes lifted.txt and needs --out DIR\n");
+        return 2;
+    }
+    if (liftObjects && sequence.empty() && dataDir.empty() && !autonomous) {
+        std::fprintf(stderr, "usage: emfusion_synth: --lift-objects acts where objects are created from masks: with --sequence / "
+                             "--dir or --autonomous; on the synthetic stream with given poses it would do nothing\n");
         return 2;
     }
     if (turnAway != -1 && (turnAway < 1 || autonomous || !sequence.empty() || !dataDir.empty())) {
@@ -591,6 +607,7 @@ int main(int argc, char** argv) {
         if (objectShapesOut) emf.setShapeOutput(true);
         if (objectContactsOut) emf.setContactsOutput(true, contactTouch);
         if (absorbObjects) emf.setAbsorbObjects(true), emf.setAbsorbedOutput(true);
+        if (liftObjects) emf.setLiftObjects(true), emf.setLiftedOutput(true);
         if (groundOut.on) emf.setGroundOutput(groundOut);
         if (groundUpFloor) emf.setGroundUpFloor(true);
         if (planesOut.on) emf.setPlanesOutput(planesOut);
@@ -670,6 +687,7 @@ int main(int argc, char** argv) {
                     t.points, t.estep, t.raycast, t.composite, t.integrate, t.masks,
                     emf.visibleObjects().size(), emf.usesBatchedLaunches() ? "yes" : "no");
         if (absorbObjects) std::printf("absorbed into the background: %zu objects\n", emf.absorbed().size());
+        if (liftObjects) std::printf("lifted out of the background: %zu objects\n", emf.lifted().size());
         if (!outDir.empty()) {
             emf.writeResults(outDir, false);  // volumes follow setupOutput, as in the reference
             const emf::Mesh bg = emf.getMesh(0);

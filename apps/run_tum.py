@@ -107,6 +107,10 @@ def main():
                     help="absorb an object that the clean-up deletes because it left view into the background volume first "
                          "(the band of its signed-distance volume, not the free space around it) and also write "
                          "OUT/absorbed.txt: one line per absorbed object")
+    ap.add_argument("--lift-objects", dest="lift_objects", action="store_true",
+                    help="seed an object created from a mask with the band the background already holds inside its cube, "
+                         "let the background release what the object then holds as foreground, and also write "
+                         "OUT/lifted.txt: one line per lifted object")
     ap.add_argument("--contact-touch", dest="contact_touch", type=float, default=None, metavar="M",
                     help="with --object-contacts: the touching threshold in metres (default: one voxel of the probe)")
     ap.add_argument("--ground-map", dest="ground_map", action="store_true",
@@ -251,6 +255,8 @@ def main():
     fus.set_ignore_person(args.ignore_person)
     if args.absorb_objects:
         fus.set_absorb_objects(True)
+    if args.lift_objects:
+        fus.set_lift_objects(True)
     fus.set_preprocess(True)
     fus.set_cleanup(True)
     fus.setup_output(args.frame_meshes, args.volumes, args.world_mesh, exp_distance_field=args.distance_field,
@@ -260,7 +266,7 @@ def main():
                      plan_clearance=max(args.plan_clearance, 0.0), plan_through_unknown=args.plan_through_unknown,
                      exp_distance_nearest=args.distance_nearest, exp_plan_shortcut=args.plan_shortcut,
                      exp_object_shapes=args.object_shapes, exp_object_contacts=args.object_contacts,
-                     contact_touch=args.contact_touch, exp_absorbed=args.absorb_objects, exp_ground_map=args.ground_map,
+                     contact_touch=args.contact_touch, exp_absorbed=args.absorb_objects, exp_lifted=args.lift_objects, exp_ground_map=args.ground_map,
                      ground_up=None if args.ground_up is None else "floor" if args.ground_up == "floor"
                      else [float(v) for v in args.ground_up.split(",")],
                      exp_planes=args.planes, planes_angle=args.planes_angle, planes_min_votes=args.planes_min_votes,

@@ -239,6 +239,10 @@ SIGNATURES = {
     "emf_hip_contactProbe": [_FP, C.POINTER(C.c_int32), C.c_int32, _FP, C.c_void_p, C.c_int32, _FP, _STREAM],
     "emf_hip_absorbVolume": [_FP, _FP, _I3, C.c_float, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_float),
                              C.POINTER(C.c_float), _I3, _I3, _FP, _STREAM],
+    "emf_hip_seedVolume": [_FP, _FP, _I3, C.c_float, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_float),
+                           C.POINTER(C.c_float), _I3, _I3, _FP, _STREAM],
+    "emf_hip_releaseVolume": [_FP, _FP, _I3, C.c_float, _FP, _I3, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), _I3,
+                              _I3, _FP, _STREAM],
 }
 
 
@@ -378,6 +382,11 @@ CONTACT_MAX_PAIRS = 65535
 # include/emf_hip.h "Absorbing a volume": emf_absorb_t (88 bytes); emf_absorb_source_t is EmfAbsorbSource below
 ABSORB_DTYPE = [("visited", "<u8"), ("outside", "<u8"), ("unknown", "<u8"), ("masked", "<u8"), ("saturated", "<u8"),
                 ("fused", "<u8"), ("fresh", "<u8"), ("solid", "<u8"), ("lo", "<i4", 3), ("hi", "<i4", 3)]
+# include/emf_hip.h "Lifting a volume": emf_seed_t (88 bytes) and emf_release_t (80)
+SEED_DTYPE = [("visited", "<u8"), ("kept", "<u8"), ("outside", "<u8"), ("unknown", "<u8"), ("masked", "<u8"), ("saturated", "<u8"),
+              ("seeded", "<u8"), ("solid", "<u8"), ("lo", "<i4", 3), ("hi", "<i4", 3)]
+RELEASE_DTYPE = [("visited", "<u8"), ("empty", "<u8"), ("free_space", "<u8"), ("outside", "<u8"), ("unclaimed", "<u8"),
+                 ("released", "<u8"), ("solid", "<u8"), ("lo", "<i4", 3), ("hi", "<i4", 3)]
 CONTACT_UNSEEN, CONTACT_APART, CONTACT_TOUCHING, CONTACT_PENETRATING = 0, 1, 2, 3
 CONTACT_STATES = ("unseen", "apart", "touching", "penetrating")
 RAY_REACHED, RAY_BLOCKED, RAY_LEFT, RAY_OUTSIDE, RAY_INVALID = 0, 1, 2, 3, 4

@@ -129,6 +129,8 @@ void EMFusion::reset() {
     bgListPending = false;
     absorbLog_.clear();  // session state; the switch stays
     absorbDirty_ = false;
+    liftLog_.clear();  // session state; the switch stays
+    liftPending_.clear();
     colorImageSet = false;
     motionInfo.clear();
     motionFired = false;
@@ -611,8 +613,13 @@ void EMFusion::runSchedule(const emf_image_t& depthDev, const FrameInputs& in) {
     integrateDepth();
     stamp(kIntegrate);
 
+    // lifting: a new object is seeded from the background before the frame's masks classify its voxels,
+    // and the background releases what the object then holds as foreground
+    const bool lift = liftOn_ && !lastCreated.empty();
+    if (lift) liftSeedCreated();
     if ((in.runMasks || instances || !in.newObjectMasks.empty()) && !masks.empty())
         integrateMasks(masks);
+    if (lift) liftReleaseCreated();
     lastDeleted.clear();
     if (in.cleanUp) {
         if (in.runMasks && !instances)  // initOrMatchObjs' bookkeeping (EMFusion.cpp:358-369)

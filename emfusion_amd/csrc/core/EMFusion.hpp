@@ -633,6 +633,45 @@ public:
     /** writeResults also writes absorbed.txt (writeAbsorbed); without it no output byte changes. */
     void setAbsorbedOutput(bool on) { expAbsorbed_ = on; }
     void writeAbsorbed(const std::string& dir);
+    /** One lift: what the new object took from the background and what the background gave up. */
+    struct LiftEvent {
+        int id = 0;                    // the object that was lifted
+        int frame = 0;                 // the frame index (frames()) at which it happened
+        float seedR[9], seedT[3];      // the seed's pose: the background's volume frame <- the object's volume frame
+        float releaseR[9], releaseT[3];  // the release's pose: the object's volume frame <- the background's
+        int32_t lo[3], size[3];        // the box of background voxels the release covered
+        bool clipped = false;          // the object's cube leaves the background's (as AbsorbEvent::clipped)
+        emf_seed_t seed;               // include/emf_hip.h "Lifting a volume"
+        emf_release_t release;
+    };
+    /**
+     * Lifting objects out of the background (include/emf_hip.h "Lifting a volume"): the other half of
+     * setAbsorbObjects.  Off by default and sticky.  When on, every object that initNewObjVolume creates in a frame
+     * (through newObjectMasks or initOrMatchObjs) is SEEDED, after the frame's integration and before its masks are
+     * integrated, with the band the background's front copy holds inside its cube -- only where the object has no
+     * observation of its own -- and, after the masks are integrated, the background RELEASES the band voxels the object
+     * holds as foreground (its fgVolMask), so that one surface has one explanation.  The frame's own integrateMask
+     * classifies the seeded voxels: under the instance mask they are foreground at once; seeded table or floor inside the
+     * cube becomes background and is never raycast.  Several creations of a frame run in list order; the background's
+     * derived state is renewed once after the last (absorbFinish), then the model table is rebuilt.
+     * COLOUR IS NOT TOUCHED: seeded voxels have none, released voxels keep their entry.  A voxel behind the object along
+     * a mask ray inside the cube is claimed and released too (a hole in the table under a cup).  An object discovered by
+     * motion masks sits where the background holds free space: the seed finds nothing, and the ghost at the OLD place
+     * is not addressed.  The log (lifted()) is session state: neither it nor the switch is written to a checkpoint,
+     * reset() and a loaded checkpoint clear the log.  With the switch off no launch, no output byte and no checkpoint
+     * byte changes.  Refused (EMF_E_ARG) on the sharded path.
+     */
+    void setLiftObjects(bool on);
+    bool liftObjects() const { return liftOn_; }
+    /** Seed, then release, for the LIVE object `id` between frames; the object stays live.  ITS SEEDED VOXELS CARRY NO
+     *  FOREGROUND COUNT UNTIL THE NEXT MASK FRAME: until then they are neither raycast nor released (the release of this
+     *  call gives up what the object held as foreground before).  Refuses (EMF_E_ARG) an unknown id, the background and
+     *  an object this rank does not own. */
+    LiftEvent liftObject(int id);
+    const std::vector<LiftEvent>& lifted() const { return liftLog_; }
+    /** writeResults also writes lifted.txt (writeLifted); without it no output byte changes. */
+    void setLiftedOutput(bool on) { expLifted_ = on; }
+    void writeLifted(const std::string& dir);
     /** The result of groundMap(): the frame, the pose "ground metres -> world" and the arrays left on the device. */
     struct GroundMap {
         QueryBox box;
@@ -1361,6 +1400,19 @@ private:
     bool expAbsorbed_ = false;       // setAbsorbedOutput
     void absorbInto(ObjTSDF& obj);   // the launch and the log entry, on main; the caller has quiesced
     void absorbFinish();             // volumesWritten once after the last absorption, before rebuildModelTable()
+    // the covering box of the object's cube in background voxels and whether the background's cube clips it
+    void absorbBox(const ObjTSDF& obj, const float R[9], const float t[3], int32_t lo[3], int32_t size[3], bool& clipped);
+    // ---- lifting objects (setLiftObjects, liftObject; EMFusionLift.cpp): never in a checkpoint; with the switch off no
+    // launch of the frame changes
+    bool liftOn_ = false;            // setLiftObjects
+    std::vector<LiftEvent> liftLog_;
+    std::vector<LiftEvent> liftPending_;  // seeded in this frame, the release still owed
+    DeviceBuffer liftRecord_;        // one emf_seed_t, then one emf_release_t
+    bool expLifted_ = false;         // setLiftedOutput
+    void liftSeed(ObjTSDF& obj, LiftEvent& e);     // the launch on main; the caller has quiesced
+    void liftRelease(ObjTSDF& obj, LiftEvent& e);  // the launch on main and the log entry; the caller has quiesced
+    void liftSeedCreated();          // runSchedule: after integrateDepth(), before integrateMasks()
+    void liftReleaseCreated();       // runSchedule: after integrateMasks(), before cleanUpObjs
 };
 
 /**

@@ -23,14 +23,9 @@ void EMFusion::setAbsorbObjects(bool on) {
     absorbOn_ = on;
 }
 
-// The launch and the log entry.  The caller has quiesced and joined the background's integration: the front copy is
-// current and nothing of this instance is in flight.
-void EMFusion::absorbInto(ObjTSDF& obj) {
-    AbsorbEvent e;
-    e.id = obj.getID();
-    e.frame = frameCount;
-    const Affine3f bg = background.getPose(), op = obj.getPose();
-    absorbPose(bg.rotation().val, bg.translation().val, op.rotation().val, op.translation().val, e.R, e.t);
+// The covering box of the whole object in background voxels under (R, t) = the object's volume frame <- the background's,
+// and whether the background's cube clips the object.
+void EMFusion::absorbBox(const ObjTSDF& obj, const float R[9], const float t[3], int32_t lo[3], int32_t size[3], bool& clipped) {
     const Vec3i n = background.getVolumeRes(), r = obj.getVolumeRes();
     // the covering box of the whole object, and the same box against a background with kPad more voxels on every side
     // (the same centre): that one, less the helper's one voxel of margin, is the extent of the object's cube in
@@ -40,8 +35,8 @@ void EMFusion::absorbInto(ObjTSDF& obj) {
     emf_occ_object_t o{};
     for (int i = 0; i < 3; ++i) o.res[i] = r[i];
     o.voxelSize = obj.getVoxelSize();
-    std::copy(e.R, e.R + 9, o.R);
-    std::copy(e.t, e.t + 3, o.t);
+    std::copy(R, R + 9, o.R);
+    std::copy(t, t + 3, o.t);
     emf_occ_object_t wide = o;
     const int32_t padded[3] = {n[0] + 2 * kPad, n[1] + 2 * kPad, n[2] + 2 * kPad};
     emfCheck(emf_hip_occupancyObjectBox(&o, n.val, background.getVoxelSize()), "EMFusion::absorb (box)");
@@ -49,11 +44,23 @@ void EMFusion::absorbInto(ObjTSDF& obj) {
     const bool everywhere = wide.lo[0] == 0 && wide.lo[1] == 0 && wide.lo[2] == 0 && wide.size[0] == padded[0] &&
                             wide.size[1] == padded[1] && wide.size[2] == padded[2];
     for (int i = 0; i < 3; ++i) {
-        e.lo[i] = o.lo[i];
-        e.size[i] = o.size[i];
+        lo[i] = o.lo[i];
+        size[i] = o.size[i];
         const int first = wide.lo[i] - kPad + 1, last = wide.lo[i] - kPad + wide.size[i] - 2;  // without the margin
-        if (!everywhere && (wide.size[i] <= 0 || first < 0 || last > n[i] - 1)) e.clipped = true;
+        if (!everywhere && (wide.size[i] <= 0 || first < 0 || last > n[i] - 1)) clipped = true;
     }
+}
+
+// The launch and the log entry.  The caller has quiesced and joined the background's integration: the front copy is
+// current and nothing of this instance is in flight.
+void EMFusion::absorbInto(ObjTSDF& obj) {
+    AbsorbEvent e;
+    e.id = obj.getID();
+    e.frame = frameCount;
+    const Affine3f bg = background.getPose(), op = obj.getPose();
+    absorbPose(bg.rotation().val, bg.translation().val, op.rotation().val, op.translation().val, e.R, e.t);
+    const Vec3i n = background.getVolumeRes(), r = obj.getVolumeRes();
+    absorbBox(obj, e.R, e.t, e.lo, e.size, e.clipped);
     emf_absorb_source_t s{};
     s.tsdf = obj.tsdfPtr();
     s.weights = obj.weightsPtr();

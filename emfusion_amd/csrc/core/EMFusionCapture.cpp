@@ -48,6 +48,7 @@ void EMFusion::writeResults(const std::string& dir, bool volumes) {
     if (expPlanes_.on) writePlanes(dir);        // planes.txt of the whole background (5.25)
     if (expContacts_) writeContacts(dir);       // contacts.txt of the live objects and the background (5.27)
     if (expAbsorbed_) writeAbsorbed(dir);       // absorbed.txt, the session's log of absorbed objects (5.29)
+    if (expLifted_) writeLifted(dir);           // lifted.txt, the session's log of lifted objects (5.30)
     if (expFrameMeshes_) {  // writeFrameMeshes (EMFusion.cpp:1158-1185); the reference creates frame_meshes/ always
         auto writeAll = [](const std::string& d, const std::map<int, Mesh>& log) {
             io::createDirectories(d);

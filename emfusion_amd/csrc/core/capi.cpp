@@ -1127,6 +1127,54 @@ int emf_fusion_set_absorbed_output(emf_fusion_t* h, int on) {
     return guarded([&] { h->impl->setAbsorbedOutput(on != 0); });
 }
 
+static_assert(sizeof(emf_lift_event_t) == 304, "mirrored by emfusion_amd/pipeline.py");
+
+static emf_lift_event_t liftEvent(const EMFusion::LiftEvent& e) {
+    emf_lift_event_t o{};
+    o.id = e.id, o.frame = e.frame, o.clipped = e.clipped ? 1 : 0;
+    std::copy(e.seedR, e.seedR + 9, o.seed_R);
+    std::copy(e.seedT, e.seedT + 3, o.seed_t);
+    std::copy(e.releaseR, e.releaseR + 9, o.release_R);
+    std::copy(e.releaseT, e.releaseT + 3, o.release_t);
+    std::copy(e.lo, e.lo + 3, o.lo);
+    std::copy(e.size, e.size + 3, o.size);
+    o.seed = e.seed;
+    o.release = e.release;
+    return o;
+}
+
+int emf_fusion_set_lift_objects(emf_fusion_t* h, int on) {
+    REQ(h);
+    return guarded([&] { h->impl->setLiftObjects(on != 0); });
+}
+
+int emf_fusion_lift_object(emf_fusion_t* h, int32_t id, emf_lift_event_t* event) {
+    REQ(h);
+    return guarded([&] {
+        const EMFusion::LiftEvent e = h->impl->liftObject(id);
+        if (event) *event = liftEvent(e);
+    });
+}
+
+int emf_fusion_lifted(emf_fusion_t* h, emf_lift_event_t* events, int32_t capacity, int32_t* count) {
+    REQ(h);
+    REQ(count);
+    if (capacity < 0 || (capacity > 0 && !events)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_lifted: capacity %d without a list", capacity);
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const std::vector<EMFusion::LiftEvent>& log = h->impl->lifted();
+        *count = static_cast<int32_t>(log.size());
+        for (size_t k = 0; k < log.size() && k < static_cast<size_t>(capacity); ++k) events[k] = liftEvent(log[k]);
+    });
+}
+
+int emf_fusion_set_lifted_output(emf_fusion_t* h, int on) {
+    REQ(h);
+    return guarded([&] { h->impl->setLiftedOutput(on != 0); });
+}
+
 int emf_fusion_planes(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], const emf_plane_params_t* params,
                       int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3], uint32_t counters[4], uint32_t* min_votes,
                       emf_plane_t* planes, int32_t capacity, int32_t* count) {

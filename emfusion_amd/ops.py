@@ -2126,6 +2126,75 @@ def absorb_volume(dst, src, pose, box=None, out=None, lib=None, stream=None):
     return record.numpy()[0] if out is None else out
 
 
+# ---- lifting a volume (include/emf_hip.h "Lifting a volume") ---------------------------------------
+
+SEED_DTYPE = np.dtype(_lib.SEED_DTYPE)
+RELEASE_DTYPE = np.dtype(_lib.RELEASE_DTYPE)
+assert SEED_DTYPE.itemsize == 88 and RELEASE_DTYPE.itemsize == 80
+
+
+def seed_volume(dst, src, pose, box=None, out=None, lib=None, stream=None):
+    """emf_hip_seedVolume: `dst` takes the signed-distance band of `src`, resampled through pose = (R, t) (f32, source
+    frame <- destination frame), ONLY WHERE IT HAS NO OBSERVATION OF ITS OWN (weights not > 0), in place, and only values
+    inside its own band: no clamped +-1 is written.  dst, src, box and out as in absorb_volume (box None: the covering
+    box of the whole source).  Returns the record (a 0-d numpy array of SEED_DTYPE: visited = kept + outside + unknown +
+    masked + saturated + seeded; solid; lo, hi of the seeded voxels), or with out= that array."""
+    L = _L if lib is None else lib
+    tsdf, weights = _vol(dst["tsdf"], np.float32), _vol(dst["weights"], np.float32)
+    stsdf, sweights = _vol(src["tsdf"], np.float32), _vol(src["weights"], np.float32)
+    assert weights.shape == tsdf.shape and sweights.shape == stsdf.shape
+    res = (tsdf.shape[2], tsdf.shape[1], tsdf.shape[0])
+    s = _lib.EmfAbsorbSource()
+    s.tsdf, s.weights = stsdf.ptr, sweights.ptr
+    if src.get("fg_mask") is not None:
+        assert src["fg_mask"].shape == stsdf.shape
+        s.fgVolMask = _vol(src["fg_mask"], np.uint8).ptr
+    if src.get("unseen_tiles") is not None:
+        s.unseenTiles = src["unseen_tiles"].ptr
+    s.res = _i3((stsdf.shape[2], stsdf.shape[1], stsdf.shape[0]))
+    s.voxelSize, s.truncdist = float(np.float32(src["voxel_size"])), float(np.float32(src["truncdist"]))
+    if box is None:
+        box = absorb_box(res, dst["voxel_size"], tuple(s.res), src["voxel_size"], pose)
+    lo, size = _box(res, box)
+    record = DeviceArray((1,), SEED_DTYPE) if out is None else out
+    assert record.dtype == SEED_DTYPE and record.shape[0] >= 1
+    check("emf_hip_seedVolume",
+          L.emf_hip_seedVolume(_ptr(tsdf), _ptr(weights), _i3(res), float(np.float32(dst["voxel_size"])),
+                               float(np.float32(dst["truncdist"])), float(np.float32(dst["max_weight"])), C.byref(s),
+                               _f(pose[0], 9), _f(pose[1], 3), _i3(lo), _i3(size), _ptr(record), _stream(stream)))
+    return record.numpy()[0] if out is None else out
+
+
+def release_volume(dst, claim, pose, box=None, out=None, lib=None, stream=None):
+    """emf_hip_releaseVolume: `dst` gives up, in place, the band voxels (weights > 0, |tsdf| < 1) that the claimant holds:
+    tsdf and weights become +0.0.  dst: dict(tsdf=, weights=, voxel_size=); claim: dict(fg_mask=, voxel_size=) with a
+    (Nz, Ny, Nx) u8 device volume, or dict(fg_mask=None, res=(nx, ny, nz), voxel_size=): everything inside the
+    claimant's cube; pose = (R, t), claimant frame <- destination frame.  box: (lo, size) in destination voxels, None: the
+    covering box of the claimant's cube (absorb_box).  Returns the record (RELEASE_DTYPE: visited = empty + free_space +
+    outside + unclaimed + released; solid; lo, hi of the released voxels), or with out= that array."""
+    L = _L if lib is None else lib
+    tsdf, weights = _vol(dst["tsdf"], np.float32), _vol(dst["weights"], np.float32)
+    assert weights.shape == tsdf.shape
+    res = (tsdf.shape[2], tsdf.shape[1], tsdf.shape[0])
+    mask = claim.get("fg_mask")
+    if mask is not None:
+        mask = _vol(mask, np.uint8)
+        cres = (mask.shape[2], mask.shape[1], mask.shape[0])
+        assert claim.get("res") is None or tuple(int(v) for v in claim["res"]) == cres
+    else:
+        cres = tuple(int(v) for v in claim["res"])
+    if box is None:
+        box = absorb_box(res, dst["voxel_size"], cres, claim["voxel_size"], pose)
+    lo, size = _box(res, box)
+    record = DeviceArray((1,), RELEASE_DTYPE) if out is None else out
+    assert record.dtype == RELEASE_DTYPE and record.shape[0] >= 1
+    check("emf_hip_releaseVolume",
+          L.emf_hip_releaseVolume(_ptr(tsdf), _ptr(weights), _i3(res), float(np.float32(dst["voxel_size"])), _ptr(mask),
+                                  _i3(cres), float(np.float32(claim["voxel_size"])), _f(pose[0], 9), _f(pose[1], 3), _i3(lo),
+                                  _i3(size), _ptr(record), _stream(stream)))
+    return record.numpy()[0] if out is None else out
+
+
 # ---- ground map (include/emf_hip.h "Ground map", DESIGN.md 5.24) -------------------------------------------------
 
 GROUND_CELL_DTYPE = np.dtype(_lib.GROUND_CELL_DTYPE)

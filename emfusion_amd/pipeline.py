@@ -191,6 +191,10 @@ def load() -> C.CDLL:
         "emf_fusion_absorb_object": [vp, C.c_int32, C.c_void_p],
         "emf_fusion_absorbed": [vp, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
         "emf_fusion_set_absorbed_output": [vp, C.c_int],
+        "emf_fusion_set_lift_objects": [vp, C.c_int],
+        "emf_fusion_lift_object": [vp, C.c_int32, C.c_void_p],
+        "emf_fusion_lifted": [vp, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
+        "emf_fusion_set_lifted_output": [vp, C.c_int],
         "emf_fusion_planes": [vp, ip, ip, C.c_void_p, ip, ip, fp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                               C.POINTER(C.c_int32)],
         "emf_fusion_copy_plane_labels": [vp, C.c_void_p, C.c_void_p, C.c_int64],
@@ -689,6 +693,30 @@ def absorbed_line(event):
         [int(r[k]) for k in ("visited", "outside", "unknown", "masked", "saturated", "fused", "fresh", "solid")] + \
         [int(v) for v in r["lo"]] + [int(v) for v in r["hi"]]
     floats = [float(v) for v in np.asarray(event["R"], np.float32).reshape(9)] + [float(v) for v in event["t"]]
+    return " ".join([str(int(v)) for v in ints] + ["%.9g" % v for v in floats])
+
+
+def _lift_event_dtype():
+    """emf_lift_event_t (include/emf_fusion.h): 304 bytes."""
+    from . import _lib as hip
+    d = np.dtype([("id", "<i4"), ("frame", "<i4"), ("clipped", "<i4"), ("reserved", "<i4"), ("seed_R", "<f4", 9), ("seed_t", "<f4", 3),
+                  ("release_R", "<f4", 9), ("release_t", "<f4", 3), ("lo", "<i4", 3), ("size", "<i4", 3),
+                  ("seed", np.dtype(hip.SEED_DTYPE)), ("release", np.dtype(hip.RELEASE_DTYPE))])
+    assert d.itemsize == 304
+    return d
+
+
+def lifted_line(event):
+    """One line of lifted.txt (without the newline) from an event of Fusion.lifted()."""
+    s, r = event["seed"], event["release"]
+    ints = [event["id"], event["frame"], int(event["clipped"]), *event["lo"], *event["size"]] + \
+        [int(s[k]) for k in ("visited", "kept", "outside", "unknown", "masked", "saturated", "seeded", "solid")] + \
+        [int(v) for v in s["lo"]] + [int(v) for v in s["hi"]] + \
+        [int(r[k]) for k in ("visited", "empty", "free_space", "outside", "unclaimed", "released", "solid")] + \
+        [int(v) for v in r["lo"]] + [int(v) for v in r["hi"]]
+    floats = []
+    for k in ("seed_R", "seed_t", "release_R", "release_t"):
+        floats += [float(v) for v in np.asarray(event[k], np.float32).reshape(-1)]
     return " ".join([str(int(v)) for v in ints] + ["%.9g" % v for v in floats])
 
 
@@ -1975,6 +2003,50 @@ class Fusion:
         _check("emf_fusion_absorbed", load().emf_fusion_absorbed(self._h, events.ctypes.data, n.value, C.byref(n)))
         return [self._absorb_event(events[k]) for k in range(n.value)]
 
+    @staticmethod
+    def _lift_event(e):
+        return dict(id=int(e["id"]), frame=int(e["frame"]), clipped=bool(e["clipped"]), seed_R=e["seed_R"].reshape(3, 3).copy(),
+                    seed_t=e["seed_t"].copy(), release_R=e["release_R"].reshape(3, 3).copy(), release_t=e["release_t"].copy(),
+                    lo=tuple(int(v) for v in e["lo"]), size=tuple(int(v) for v in e["size"]), seed=e["seed"].copy(),
+                    release=e["release"].copy())
+
+    def set_lift_objects(self, on=True):
+        """Lift new objects out of the background, the other half of set_absorb_objects.  Sticky, off by
+        default.  On: every object a frame creates from a mask is SEEDED, after the frame's integration and before its
+        masks are integrated, with the band the background holds inside its cube -- only where the object has no
+        observation of its own -- and after the masks the background RELEASES the band voxels the object holds as
+        foreground (its fgmask), so that one surface has one explanation and no ghost stays when the object moves.  The
+        frame's own mask classifies the seeded voxels: under it they are foreground at once; seeded table or floor inside
+        the cube becomes background and is never raycast.
+
+        WHAT IT DOES NOT DO: colour is not touched (seeded voxels have none, released voxels keep their entry); a voxel
+        behind the object along a mask ray inside the cube is claimed and released too (a hole in the table under a cup);
+        an object discovered by motion masks sits where the background holds free space: the seed finds nothing there
+        and the ghost at the OLD place is not addressed.  Neither the switch nor the log (lifted()) is written to a
+        checkpoint: no checkpoint byte changes.  Off: no launch and no output byte changes.  Refused on the sharded
+        path."""
+        _check("emf_fusion_set_lift_objects", load().emf_fusion_set_lift_objects(self._h, int(bool(on))))
+
+    def lift_object(self, obj_id):
+        """Seed, then release, for the LIVE object obj_id now (see set_lift_objects; the switch need not be on); the
+        object stays live.  ITS SEEDED VOXELS CARRY NO FOREGROUND COUNT UNTIL THE NEXT MASK FRAME: until then they are
+        neither raycast nor released.  Returns the event: dict(id, frame, clipped, seed_R, seed_t (background volume frame
+        <- object volume frame), release_R, release_t (the opposite), lo, size (the box of background voxels the release
+        covered), seed (ops.SEED_DTYPE), release (ops.RELEASE_DTYPE)).  An unknown id, the background (0) and an object
+        this rank does not own raise; refused on the sharded path."""
+        e = np.zeros((), _lift_event_dtype())
+        _check("emf_fusion_lift_object", load().emf_fusion_lift_object(self._h, int(obj_id), e.ctypes.data))
+        return self._lift_event(e)
+
+    def lifted(self):
+        """The session's log of lifted objects, oldest first: a list of the events of lift_object().  Session state
+        only: reset() and a loaded checkpoint start it empty, and it is never written to a checkpoint."""
+        n = C.c_int32(0)
+        _check("emf_fusion_lifted", load().emf_fusion_lifted(self._h, None, 0, C.byref(n)))
+        events = np.zeros(max(n.value, 1), _lift_event_dtype())
+        _check("emf_fusion_lifted", load().emf_fusion_lifted(self._h, events.ctypes.data, n.value, C.byref(n)))
+        return [self._lift_event(events[k]) for k in range(n.value)]
+
     def planes(self, box=None, size=None, k=15, angle=20.0, separation=None, bin=None, band=None, min_votes=None, refine=1,
                up_hint=None, floor_angle=30.0, kind_angle=10.0, max_planes=64, labels=False, patches=False, patch_reach=1,
                patch_min_voxels=None):
@@ -2481,7 +2553,7 @@ class Fusion:
                      ground_up=None, ground_cell=None, ground_bin=None, ground_band=(-1.5, 0.5), ground_robot_height=0.3,
                      ground_max_step=0.05, exp_planes=False, planes_angle=20.0, planes_min_votes=None,
                      exp_plane_patches=False, plane_patch_reach=1, plane_patch_min=None, exp_object_contacts=False,
-                     contact_touch=None, exp_absorbed=False):
+                     contact_touch=None, exp_absorbed=False, exp_lifted=False):
         """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
         the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
         the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh();
@@ -2518,7 +2590,9 @@ class Fusion:
         ids, the eight counts, then in %.9g min_s and the world contact point and normal of that record
         (include/emf_fusion.h emf_fusion_set_contacts_output);
         exp_absorbed: write_results also writes absorbed.txt, after a comment line one line per event of absorbed():
-        absorbed_line() of it (include/emf_fusion.h emf_fusion_set_absorbed_output)."""
+        absorbed_line() of it (include/emf_fusion.h emf_fusion_set_absorbed_output).
+        exp_lifted: write_results also writes lifted.txt, after a comment line one line per event of lifted():
+        lifted_line() of it (include/emf_fusion.h emf_fusion_set_lifted_output)."""
         if contact_touch is not None and not exp_object_contacts:
             raise ValueError("setup_output: contact_touch is the threshold of contacts.txt and needs exp_object_contacts")
         if exp_plan_shortcut and not exp_plan:
@@ -2563,6 +2637,8 @@ class Fusion:
                    load().emf_fusion_set_contacts_output(self._h, 1, -1.0 if contact_touch is None else float(contact_touch)))
         if exp_absorbed:  # off: no new call
             _check("emf_fusion_set_absorbed_output", load().emf_fusion_set_absorbed_output(self._h, 1))
+        if exp_lifted:  # off: no new call
+            _check("emf_fusion_set_lifted_output", load().emf_fusion_set_lifted_output(self._h, 1))
         if exp_ground_map:  # off: no new call
             up = None if ground_up is None or up_floor else np.ascontiguousarray(ground_up, np.float64).reshape(3)
             _check("emf_fusion_set_ground_output",

@@ -515,6 +515,42 @@ int emf_fusion_set_absorb_objects(emf_fusion_t* h, int on);
 int emf_fusion_absorb_object(emf_fusion_t* h, int32_t id, emf_absorb_event_t* event);
 int emf_fusion_absorbed(emf_fusion_t* h, emf_absorb_event_t* events, int32_t capacity, int32_t* count);
 int emf_fusion_set_absorbed_output(emf_fusion_t* h, int on);
+/* Lifting objects out of the background (include/emf_hip.h "Lifting a volume"; new behaviour, opt-in):
+ * the other half of absorbing.  A new object is SEEDED with the band the background already holds inside its cube, only
+ * where it has no observation of its own, and the background RELEASES the band voxels the object then holds as
+ * foreground, so that one surface has one explanation and no ghost stays behind when the object moves.  COLOUR IS NOT
+ * TOUCHED; a voxel behind the object along a mask ray inside the cube is released too; an object discovered by motion
+ * masks sits in free space: the seed finds nothing there and the ghost at the OLD place is not addressed.
+ *   set_lift_objects   sticky, off by default.  On: every object a frame creates from a mask is seeded after the frame's
+ *                   integration and before its masks are integrated (so the frame's own mask classifies the seeded
+ *                   voxels), and released after them; several creations of a frame run in list order.  Neither the
+ *                   switch nor the log is written to a checkpoint; with it off no launch, no output byte and no
+ *                   checkpoint byte changes.
+ *   lift_object     seed, then release, for the LIVE object `id` now; the object stays live.  Its seeded voxels carry no
+ *                   foreground count until the next mask frame: until then they are neither raycast nor released.
+ *                   `event` may be NULL.  EMF_E_ARG: an unknown id, id 0, an object of another rank.
+ *   lifted          the session's log, oldest first: the first min(capacity, *count) events; *count is the number logged.
+ *                   reset() and a loaded checkpoint start it empty.
+ *   set_lifted_output  setup_output's exp_lifted: emf_fusion_write_results also writes lifted.txt, after a comment line
+ *                   one line per event: id frame clipped, box_lo (3), box_size (3), the seed's eight counts, lo (3), hi
+ *                   (3), the release's seven counts, lo (3), hi (3), then the seed's R (9) and t (3) and the release's R
+ *                   (9) and t (3) in %.9g.  Off: the set of result files and every byte of them as before.
+ * set_lift_objects (on) and lift_object are EMF_E_ARG on the sharded path. */
+typedef struct emf_lift_event {
+    int32_t id;             /* the lifted object */
+    int32_t frame;          /* the frame index at which it happened */
+    int32_t clipped;        /* as emf_absorb_event_t.clipped */
+    int32_t reserved;       /* 0 */
+    float seed_R[9], seed_t[3];       /* the seed's pose: the background's volume frame <- the object's volume frame */
+    float release_R[9], release_t[3]; /* the release's pose: the object's volume frame <- the background's */
+    int32_t lo[3], size[3]; /* the box of background voxels the release covered */
+    emf_seed_t seed;        /* include/emf_hip.h "Lifting a volume" */
+    emf_release_t release;
+} emf_lift_event_t;         /* 304 bytes */
+int emf_fusion_set_lift_objects(emf_fusion_t* h, int on);
+int emf_fusion_lift_object(emf_fusion_t* h, int32_t id, emf_lift_event_t* event);
+int emf_fusion_lifted(emf_fusion_t* h, emf_lift_event_t* events, int32_t capacity, int32_t* count);
+int emf_fusion_set_lifted_output(emf_fusion_t* h, int on);
 /* Planes (include/emf_hip.h "Planes"; new behaviour, opt-in): the dominant planes of a box of the
  * background (box_lo / box_size NULL: all of it) -- floor, walls, table tops.  A plane is the plane of the SHELL's voxel
  * centres: up to one voxel behind the surface, and nothing corrects that.

@@ -2463,6 +2463,75 @@ int emf_hip_absorbVolume(float* dst_tsdf, float* dst_weights, const int32_t dst_
                          float max_weight, const emf_absorb_source_t* source, const float R[9], const float t[3],
                          const int32_t box_lo[3], const int32_t box_size[3], emf_absorb_t* record_dev, emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Lifting a volume (new behaviour: DESIGN.md 5.30).  Opt-in; nothing above is touched.  The opposite direction of
+ * "Absorbing a volume", in two passes: a new object is SEEDED from what the background already holds of it, and the
+ * background RELEASES what the object then holds as foreground.  Everything "Absorbing a volume" lays down holds here
+ * word for word: dense (z, y, x) volumes, x fastest, res = (nx, ny, nz); R[9], t[3] (f32, row-major) = the SOURCE's (the
+ * claimant's) volume frame <- the DESTINATION's volume frame; per destination voxel v of the box [box_lo, box_lo +
+ * box_size) the sample-point arithmetic p_d, p_s, q, l, f; the pad-1 OUTSIDE rule; the blend in x pairs, then y, then z;
+ * every float step a single float32 operation without contraction, everything else integer; the classes in the order
+ * given, the first match wins; of tsdf[v] and weights[v] only the words whose bits change are stored.  pw, pt: the
+ * destination's weight and tsdf at v.  Colour is not touched by either pass.
+ *
+ * emf_hip_seedVolume: THE DESTINATION TAKES THE SOURCE'S BAND ONLY WHERE IT HAS NO OBSERVATION OF ITS OWN.
+ *     KEPT       pw > 0.  Decided before anything of the source is read; the voxel is not written.  (A new object has
+ *                integrated the frame that the source integrated too: a running average there would count one
+ *                measurement twice.)
+ *     OUTSIDE, UNKNOWN, MASKED    exactly as in "Absorbing a volume" (source->fgVolMask, source->unseenTiles included:
+ *                the bytes are the same with the unseen-tile map and without it)
+ *     SATURATED  !(fabsf(s) < 1) or !(fabsf(u) < 1) with u = s * ratio, ratio = truncdist_s / truncdist_d (one float32
+ *                division, made once on the host): only values inside the destination's own band are carried, which is
+ *                what its own integration would have produced.  No clamped +-1 is ever written.
+ *     SEEDED     nt = u, nw = min(w_o, maxWeight), w_o the minimum of the eight corner weights
+ *                SOLID: SEEDED and !(nt > 0).
+ * emf_seed_t: visited = kept + outside + unknown + masked + saturated + seeded (the voxels of the box); solid <= seeded;
+ * lo, hi: the inclusive bounds of the SEEDED voxels in the destination, res_d and -1 without one.
+ *
+ * emf_hip_releaseVolume: THE DESTINATION GIVES UP THE BAND VOXELS THAT THE CLAIMANT HOLDS.  claim_mask: a u8 volume of
+ * claim_res on the claimant's lattice (an object's fgVolMask), or NULL: everything inside the claimant's cube.
+ *     EMPTY      !(pw > 0)
+ *     FREE       !(fabsf(pt) < 1): free space and NaN stay; it releases the band, not the free space around it
+ *     OUTSIDE    the pad-1 rule on q against claim_res
+ *     UNCLAIMED  claim_mask is not NULL and is 0 at (rint(q_0), rint(q_1), rint(q_2)), ties to even: the addressing of
+ *                MASKED
+ *     RELEASED   tsdf[v] and weights[v] become the bits of +0.0f, what an unseen voxel holds after a reset
+ *                SOLID: RELEASED and !(pt > 0) of the old value.
+ * emf_release_t: visited = empty + free_space + outside + unclaimed + released; solid <= released; lo, hi: the inclusive
+ * bounds of the RELEASED voxels.  EMPTY and FREE come first: most voxels of a covering box cost 8 bytes and no transform.
+ *
+ * In both, every destination voxel reads and writes only itself: the passes are in place, and the bytes are a pure
+ * function of the inputs whatever order lanes and workgroups run in.  A second seed finds its seeded voxels KEPT, a second
+ * release finds its released voxels EMPTY.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct emf_seed {
+    uint64_t visited, kept, outside, unknown, masked, saturated, seeded, solid; /* counts */
+    int32_t lo[3], hi[3];       /* bounds of the seeded voxels; res_d and -1 without one */
+} emf_seed_t;                   /* 88 bytes */
+
+typedef struct emf_release {
+    uint64_t visited, empty, free_space, outside, unclaimed, released, solid;   /* counts */
+    int32_t lo[3], hi[3];       /* bounds of the released voxels; res_d and -1 without one */
+} emf_release_t;                /* 80 bytes */
+
+/* The arguments, the record, the launch shape (one workgroup of 256 lanes per 32 x 8 x 8 destination tile that meets the
+ * box, after a launch that sets the neutral record), the empty box (EMF_OK, the neutral record, nothing else written)
+ * and the refusals are those of emf_hip_absorbVolume.  Refused with EMF_E_ARG or EMF_E_LIMIT and nothing enqueued: a NULL
+ * or misaligned pointer; a destination array that shares a byte with the other, with an array of the source or with the
+ * record; an axis below 1 or above EMF_DF_MAX_AXIS or more than 2^31 - 1 voxels, of either volume; a voxel size, a
+ * truncation distance, maxWeight or the ratio of the truncation distances that is not finite and > 0; a negative box
+ * size or a box that leaves the destination.  Nothing allocates, copies to the host or waits. */
+int emf_hip_seedVolume(float* dst_tsdf, float* dst_weights, const int32_t dst_res[3], float dst_voxel_size, float dst_truncdist,
+                       float max_weight, const emf_absorb_source_t* source, const float R[9], const float t[3],
+                       const int32_t box_lo[3], const int32_t box_size[3], emf_seed_t* record_dev, emf_stream_t stream);
+
+/* claim_mask may be NULL, claim_res may not.  The refusals are those above with the claimant's mask in the source's
+ * place; there is no truncation distance and no maxWeight to refuse. */
+int emf_hip_releaseVolume(float* dst_tsdf, float* dst_weights, const int32_t dst_res[3], float dst_voxel_size,
+                          const uint8_t* claim_mask, const int32_t claim_res[3], float claim_voxel_size, const float R[9],
+                          const float t[3], const int32_t box_lo[3], const int32_t box_size[3], emf_release_t* record_dev,
+                          emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
