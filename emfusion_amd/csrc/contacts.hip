@@ -10,25 +10,24 @@
 //                A wave without a surface voxel leaves.  Then the wave loops over the pairs that name this probe -- the
 //                host passes, per probe, the first and the last index of the pair list at which it occurs, so a list
 //                grouped by probe is walked without a miss and any other order gives the same bytes -- and each lane
-//                samples the field at its surface voxels: 8 + 8 dependent gathers per voxel inside the field.  The
+//                samples the field at its surface voxels (rs_source of resample.hpp, the sampler of volume_transfer.hip
+//                too): 8 + 8 dependent gathers per voxel inside the field.  The
 //                pair and the field's table entry are wave-uniform (scalar loads).  Per pair and wave: wave_reduce
 //                of what is not zero anywhere in the wave, then one integer atomic per non-zero quantity from lane
 //                0.  A wave in which no lane sampled issues only its outside / unknown / masked counts (and their sum).
-//                No LDS, no barrier.
+//                No LDS, no barrier.  94 to 103 VGPRs depending on how the sampler is spelled: the kernel asks for the
+//                5 waves per SIMD it has always had (95 VGPRs, no scratch).
 //   k_ct_init / k_ct_finish  one lane per record: the neutral records before the pass, the key of min_s -> f32 bits
 //                after it.
 // Every float step is one float32 operation: the _rn intrinsics, and every product that feeds a sum goes through an
 // identity DPP move (mul_rounded of wave_ops.hpp), so that a build with -ffp-contract=fast has no product left to fuse (DESIGN.md 5.26
 // "CONTRACTION").  Integer atomics only: the records do not depend on the order of lanes, waves or workgroups.
-#include "common.hpp"
-#include "wave_ops.hpp"
+#include "resample.hpp"
 
 namespace emf_hip {
 namespace {
 
-constexpr int kCtBlock = 256;
-constexpr int kCtTileX = 32, kCtTileY = 8, kCtTileZ = 8;  // the tile of emf_model_t.unseenTiles
-constexpr unsigned kCtKeyInf = 0xff800000u;               // the key of +inf
+constexpr unsigned kCtKeyInf = 0xff800000u;  // the key of +inf
 
 static_assert(sizeof(emf_contact_t) == 144 && sizeof(emf_contact_pair_t) == 64, "mirrored by emfusion_amd/_lib.py");
 static_assert(EMF_MAX_MODELS <= 256 && EMF_CONTACT_MAX_PAIRS <= 65535, "ContactArgs keeps slots and pair indices in 16 bits");
@@ -63,18 +62,18 @@ __device__ __forceinline__ unsigned ct_key_bits(unsigned k) { return (k & 0x8000
 
 __device__ __forceinline__ bool ct_finite(float v) { return fabsf(v) < __uint_as_float(0x7f800000u); }  // false for NaN
 
-__global__ __launch_bounds__(kCtBlock) void k_ct_probe(const ContactArgs a) {
+__global__ __launch_bounds__(kRsBlock) __attribute__((amdgpu_waves_per_eu(5))) void k_ct_probe(const ContactArgs a) {
     const unsigned p = probe_of(a.start, a.nProbes, blockIdx.x);
     const unsigned sa = a.slot[p];
     const emf_model_t& ma = a.models[sa];
     const I3 n{ma.res[0], ma.res[1], ma.res[2]};
-    const unsigned ntx = (n.x + kCtTileX - 1) / kCtTileX, nty = (n.y + kCtTileY - 1) / kCtTileY;
+    const unsigned ntx = (n.x + kRsTileX - 1) / kRsTileX, nty = (n.y + kRsTileY - 1) / kRsTileY;
     const unsigned b = blockIdx.x - a.start[p];
     if (ma.unseenTiles != nullptr && ma.unseenTiles[b] != 0) return;  // every weight is 0: no solid, no surface voxel
     const unsigned tz = b / (ntx * nty), r = b - tz * ntx * nty, ty = r / ntx, tx = r - ty * ntx;
-    const int x = static_cast<int>(tx) * kCtTileX + static_cast<int>(threadIdx.x & 31u);
-    const int y = static_cast<int>(ty) * kCtTileY + static_cast<int>(threadIdx.x >> 5);
-    const int z0 = static_cast<int>(tz) * kCtTileZ;
+    const int x = static_cast<int>(tx) * kRsTileX + static_cast<int>(threadIdx.x & 31u);
+    const int y = static_cast<int>(ty) * kRsTileY + static_cast<int>(threadIdx.x >> 5);
+    const int z0 = static_cast<int>(tz) * kRsTileZ;
     const float* __restrict__ ta = ma.tsdf;
     const float* __restrict__ wa = ma.weights;
     const uint8_t* __restrict__ fa = ma.fgVolMask;
@@ -84,7 +83,7 @@ __global__ __launch_bounds__(kCtBlock) void k_ct_probe(const ContactArgs a) {
     unsigned surf = 0u;
     if (x < n.x && y < n.y) {
 #pragma unroll
-        for (int k = 0; k < kCtTileZ; ++k) {
+        for (int k = 0; k < kRsTileZ; ++k) {
             const int z = z0 + k;
             if (z >= n.z) break;
             const size_t v = static_cast<size_t>(z) * sz + static_cast<size_t>(y) * sy + x;
@@ -103,9 +102,7 @@ __global__ __launch_bounds__(kCtBlock) void k_ct_probe(const ContactArgs a) {
 
     const unsigned lane = threadIdx.x & 63u;
     const float voxA = ma.voxelSize;
-    const float pax = __fmul_rn(__fsub_rn(static_cast<float>(x), static_cast<float>(n.x - 1) / 2.f), voxA);
-    const float pay = __fmul_rn(__fsub_rn(static_cast<float>(y), static_cast<float>(n.y - 1) / 2.f), voxA);
-    const float halfAz = static_cast<float>(n.z - 1) / 2.f;
+    const float pax = rs_pd(x, n.x, voxA), pay = rs_pd(y, n.y, voxA);
 
     for (unsigned k = a.first[p]; k <= a.last[p]; ++k) {
         const emf_contact_pair_t& pr = a.pairs[k];  // wave-uniform
@@ -113,64 +110,24 @@ __global__ __launch_bounds__(kCtBlock) void k_ct_probe(const ContactArgs a) {
         const unsigned sb = static_cast<unsigned>(pr.b);
         if (sb >= a.nModels || sb == sa) continue;  // refused on the host; never followed here
         const emf_model_t& mb = a.models[sb];
-        const I3 nb{mb.res[0], mb.res[1], mb.res[2]};
-        const float* __restrict__ tb = mb.tsdf;
-        const float* __restrict__ wb = mb.weights;
-        const uint8_t* __restrict__ fb = mb.fgVolMask;
-        const size_t by = static_cast<size_t>(nb.x), bz = by * nb.y;
+        // the field: its unseen-tile map is not consulted, a cell in an unseen tile reads UNKNOWN by its weights
+        const RsVolume field = rs_volume(mb.tsdf, mb.weights, mb.fgVolMask, nullptr, I3{mb.res[0], mb.res[1], mb.res[2]});
         const float voxB = mb.voxelSize, touch = pr.touch;
-        const V3 halfB = half_extent(nb);
-        const float fnx = static_cast<float>(nb.x), fny = static_cast<float>(nb.y), fnz = static_cast<float>(nb.z);
-        // the first two products of every row, summed left to right
-        const float r0 = __fadd_rn(mul_rounded(pr.R[0], pax), mul_rounded(pr.R[1], pay));
-        const float r1 = __fadd_rn(mul_rounded(pr.R[3], pax), mul_rounded(pr.R[4], pay));
-        const float r2 = __fadd_rn(mul_rounded(pr.R[6], pax), mul_rounded(pr.R[7], pay));
+        const RsRows rows = rs_rows(pr.R, pax, pay);
 
         unsigned cOut = 0u, cUnk = 0u, cMask = 0u, cSam = 0u, cIn = 0u, cTouch = 0u, cNorm = 0u;
         unsigned sx = 0u, sy1 = 0u, sz1 = 0u, key = 0xffffffffu;
         int g0 = 0, g1 = 0, g2 = 0;
-        int lox = n.x, loy = n.y, loz = n.z, hix = -1, hiy = -1, hiz = -1;
+        RsBounds touching(n);
 
         for (unsigned bits = surf; bits != 0u; bits &= bits - 1u) {
             const int z = z0 + (__ffs(bits) - 1);
-            const float paz = __fmul_rn(__fsub_rn(static_cast<float>(z), halfAz), voxA);
-            const float pbx = __fadd_rn(__fadd_rn(r0, mul_rounded(pr.R[2], paz)), pr.t[0]);
-            const float pby = __fadd_rn(__fadd_rn(r1, mul_rounded(pr.R[5], paz)), pr.t[1]);
-            const float pbz = __fadd_rn(__fadd_rn(r2, mul_rounded(pr.R[8], paz)), pr.t[2]);
-            const float qx = __fadd_rn(__fdiv_rn(pbx, voxB), halfB.x);
-            const float qy = __fadd_rn(__fdiv_rn(pby, voxB), halfB.y);
-            const float qz = __fadd_rn(__fdiv_rn(pbz, voxB), halfB.z);
-            // the pad-1 rule of outside(), a NaN first: all eight corners of an inside cell lie in the volume
-            if (!(qx == qx) || !(qy == qy) || !(qz == qz) || qx < 0.f || __fadd_rn(qx, 1.f) >= fnx || qy < 0.f ||
-                __fadd_rn(qy, 1.f) >= fny || qz < 0.f || __fadd_rn(qz, 1.f) >= fnz) {
-                cOut += 1u;
-                continue;
-            }
-            const int lx = static_cast<int>(qx), ly = static_cast<int>(qy), lz = static_cast<int>(qz);
-            const float fx = __fsub_rn(qx, static_cast<float>(lx)), fy = __fsub_rn(qy, static_cast<float>(ly)),
-                        fz = __fsub_rn(qz, static_cast<float>(lz));
-            const size_t c = (static_cast<size_t>(lz) * nb.y + ly) * by + lx;
-            const float w0 = wb[c], w1 = wb[c + 1], w2 = wb[c + by], w3 = wb[c + by + 1], w4 = wb[c + bz], w5 = wb[c + bz + 1],
-                        w6 = wb[c + bz + by], w7 = wb[c + bz + by + 1];
-            const float t0 = tb[c], t1 = tb[c + 1], t2 = tb[c + by], t3 = tb[c + by + 1], t4 = tb[c + bz], t5 = tb[c + bz + 1],
-                        t6 = tb[c + bz + by], t7 = tb[c + bz + by + 1];
-            const bool seen = w0 > 0.f && w1 > 0.f && w2 > 0.f && w3 > 0.f && w4 > 0.f && w5 > 0.f && w6 > 0.f && w7 > 0.f;
-            // blend8 of common.hpp, its products made opaque: x pairs, then y, then z
-            const float gx = __fsub_rn(1.f, fx), gy = __fsub_rn(1.f, fy), gz = __fsub_rn(1.f, fz);
-            const float a0 = lerp_rounded(gx, fx, t0, t1), a1 = lerp_rounded(gx, fx, t2, t3), a2 = lerp_rounded(gx, fx, t4, t5),
-                        a3 = lerp_rounded(gx, fx, t6, t7);
-            const float b0 = lerp_rounded(gy, fy, a0, a1), b1 = lerp_rounded(gy, fy, a2, a3);
-            const float s = lerp_rounded(gz, fz, b0, b1);
-            if (!seen || !(s == s)) {
-                cUnk += 1u;
-                continue;
-            }
-            if (fb != nullptr) {  // the voxel nearest to q, ties to even: inside the volume by the rule above
-                const int rx = __float2int_rn(qx), ry = __float2int_rn(qy), rz = __float2int_rn(qz);
-                if (fb[(static_cast<size_t>(rz) * nb.y + ry) * by + rx] == 0) {
-                    cMask += 1u;
-                    continue;
-                }
+            float s, w[8];
+            switch (rs_source(field, rs_sample(rows, pr.R, pr.t, rs_pd(z, n.z, voxA), voxB, field.half), s, w)) {
+                case RsClass::Outside: cOut += 1u; continue;
+                case RsClass::Unknown: cUnk += 1u; continue;
+                case RsClass::Masked: cMask += 1u; continue;
+                case RsClass::Value: break;
             }
             cSam += 1u;
             key = min(key, ct_float_key(s));
@@ -178,9 +135,7 @@ __global__ __launch_bounds__(kCtBlock) void k_ct_probe(const ContactArgs a) {
             if (!(s <= touch)) continue;
             cTouch += 1u;
             sx += static_cast<unsigned>(x), sy1 += static_cast<unsigned>(y), sz1 += static_cast<unsigned>(z);
-            lox = min(lox, x), hix = max(hix, x);
-            loy = min(loy, y), hiy = max(hiy, y);
-            loz = min(loz, z), hiz = max(hiz, z);
+            touching.include(x, y, z);
             if (x > 0 && x + 1 < n.x && y > 0 && y + 1 < n.y && z > 0 && z + 1 < n.z) {
                 const size_t v = static_cast<size_t>(z) * sz + static_cast<size_t>(y) * sy + x;
                 if (wa[v - 1] > 0.f && wa[v + 1] > 0.f && wa[v - sy] > 0.f && wa[v + sy] > 0.f && wa[v - sz] > 0.f &&
@@ -199,7 +154,7 @@ __global__ __launch_bounds__(kCtBlock) void k_ct_probe(const ContactArgs a) {
 
         // a lane holds at most 8 voxels, a wave 512: every wave sum fits 32 bits (512 * 2047, 512 * 8192)
         cOut = wave_reduce<OpAdd>(cOut), cUnk = wave_reduce<OpAdd>(cUnk), cMask = wave_reduce<OpAdd>(cMask);
-        const bool anySampled = __ballot(cSam != 0u) != 0ull, anyTouch = __ballot(cTouch != 0u) != 0ull;  // wave-uniform
+        const bool anySampled = __ballot(cSam != 0u) != 0ull, anyTouch = touching.any();  // wave-uniform
         if (anySampled) {
             cSam = wave_reduce<OpAdd>(cSam), cIn = wave_reduce<OpAdd>(cIn);
             key = wave_reduce<OpMin>(key);
@@ -208,29 +163,24 @@ __global__ __launch_bounds__(kCtBlock) void k_ct_probe(const ContactArgs a) {
             cTouch = wave_reduce<OpAdd>(cTouch), cNorm = wave_reduce<OpAdd>(cNorm);
             sx = wave_reduce<OpAdd>(sx), sy1 = wave_reduce<OpAdd>(sy1), sz1 = wave_reduce<OpAdd>(sz1);
             g0 = wave_reduce<OpAdd>(g0), g1 = wave_reduce<OpAdd>(g1), g2 = wave_reduce<OpAdd>(g2);
-            lox = wave_reduce<OpMin>(lox), loy = wave_reduce<OpMin>(loy), loz = wave_reduce<OpMin>(loz);
-            hix = wave_reduce<OpMax>(hix), hiy = wave_reduce<OpMax>(hiy), hiz = wave_reduce<OpMax>(hiz);
+            touching.reduce();
         }
         if (lane == 0u) {
             emf_contact_t* out = a.records + k;
-            auto add = [](uint64_t* q, unsigned long long v) {
-                if (v) atomicAdd(reinterpret_cast<unsigned long long*>(q), v);
-            };
-            add(&out->surface, static_cast<unsigned long long>(cOut) + cUnk + cMask + cSam);  // the wave has a surface voxel
-            add(&out->outside, cOut), add(&out->unknown, cUnk), add(&out->masked, cMask);
+            rs_add64(&out->surface, static_cast<unsigned long long>(cOut) + cUnk + cMask + cSam);  // the wave has a surface voxel
+            rs_add64(&out->outside, cOut), rs_add64(&out->unknown, cUnk), rs_add64(&out->masked, cMask);
             if (anySampled) {
-                add(&out->sampled, cSam), add(&out->inside, cIn);
+                rs_add64(&out->sampled, cSam), rs_add64(&out->inside, cIn);
                 atomicMin(reinterpret_cast<unsigned*>(&out->min_s), key);  // a key until k_ct_finish
             }
             if (anyTouch) {
-                add(&out->touching, cTouch), add(&out->normals, cNorm);
-                add(&out->sum[0], sx), add(&out->sum[1], sy1), add(&out->sum[2], sz1);
+                rs_add64(&out->touching, cTouch), rs_add64(&out->normals, cNorm);
+                rs_add64(&out->sum[0], sx), rs_add64(&out->sum[1], sy1), rs_add64(&out->sum[2], sz1);
                 // two's complement: the wrap of the unsigned sum is the signed sum
-                add(reinterpret_cast<uint64_t*>(&out->gsum[0]), static_cast<unsigned long long>(static_cast<long long>(g0)));
-                add(reinterpret_cast<uint64_t*>(&out->gsum[1]), static_cast<unsigned long long>(static_cast<long long>(g1)));
-                add(reinterpret_cast<uint64_t*>(&out->gsum[2]), static_cast<unsigned long long>(static_cast<long long>(g2)));
-                atomicMin(&out->lo[0], lox), atomicMin(&out->lo[1], loy), atomicMin(&out->lo[2], loz);
-                atomicMax(&out->hi[0], hix), atomicMax(&out->hi[1], hiy), atomicMax(&out->hi[2], hiz);
+                rs_add64(reinterpret_cast<uint64_t*>(&out->gsum[0]), static_cast<unsigned long long>(static_cast<long long>(g0)));
+                rs_add64(reinterpret_cast<uint64_t*>(&out->gsum[1]), static_cast<unsigned long long>(static_cast<long long>(g1)));
+                rs_add64(reinterpret_cast<uint64_t*>(&out->gsum[2]), static_cast<unsigned long long>(static_cast<long long>(g2)));
+                touching.commit(out);
             }
         }
     }
@@ -306,8 +256,8 @@ int emf_hip_contactProbe(const emf_model_t* models_dev, const int32_t* res_host,
             a.slot[p] = static_cast<unsigned short>(pa);
             a.first[p] = static_cast<unsigned short>(k);
             a.start[p] = static_cast<unsigned>(blocks);
-            blocks += static_cast<unsigned long long>((r[0] + kCtTileX - 1) / kCtTileX) * ((r[1] + kCtTileY - 1) / kCtTileY) *
-                      ((r[2] + kCtTileZ - 1) / kCtTileZ);
+            blocks += static_cast<unsigned long long>((r[0] + kRsTileX - 1) / kRsTileX) * ((r[1] + kRsTileY - 1) / kRsTileY) *
+                      ((r[2] + kRsTileZ - 1) / kRsTileZ);
             if (blocks > 0xffffffull) return fail(EMF_E_LIMIT, "contactProbe: more than 2^24 - 1 probe tiles in one call");
         }
         a.last[p] = static_cast<unsigned short>(k);
@@ -320,7 +270,7 @@ int emf_hip_contactProbe(const emf_model_t* models_dev, const int32_t* res_host,
     a.nPairs = static_cast<unsigned>(n_pairs);
     const hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(k_ct_init, dim3(ceil_div(a.nPairs, 256)), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_ct_probe, dim3(a.start[a.nProbes]), dim3(kCtBlock), 0, s, a);
+    hipLaunchKernelGGL(k_ct_probe, dim3(a.start[a.nProbes]), dim3(kRsBlock), 0, s, a);
     hipLaunchKernelGGL(k_ct_finish, dim3(ceil_div(a.nPairs, 256)), dim3(256), 0, s, a);
     return launch_status("contactProbe");
 }

@@ -1400,6 +1400,30 @@ private:
     bool expAbsorbed_ = false;       // setAbsorbedOutput
     void absorbInto(ObjTSDF& obj);   // the launch and the log entry, on main; the caller has quiesced
     void absorbFinish();             // volumesWritten once after the last absorption, before rebuildModelTable()
+    // the live object `id` of this rank for absorbObject / liftObject, or the HipError (EMF_E_ARG) that says why not:
+    // `background` for id 0, "not owned by this rank", "no object"
+    std::list<ObjTSDF>::iterator ownedObjectOrThrow(const char* who, int id, const char* background);
+    // Runs `write`, which writes the background's front copy or an object's volume from outside the integration, and
+    // renews what is derived from them -- absorbFinish(), rebuildModelTable() -- whether it returns or throws.
+    template <typename Write>
+    void writeThenRenew(Write&& write) {
+        try {
+            write();
+        } catch (...) {
+            absorbFinish();
+            rebuildModelTable();
+            throw;
+        }
+        absorbFinish();
+        rebuildModelTable();
+    }
+    // a pass's launch on main (its return code), the copy of its record to the host, the wait
+    template <typename Record>
+    void launchedRecord(int rc, const char* what, const Record* dev, Record* host) {
+        emfCheck(rc, what);
+        hipCheck(hipMemcpyAsync(host, dev, sizeof(Record), hipMemcpyDeviceToHost, main.get()), what);
+        main.waitForCompletion();
+    }
     // the covering box of the object's cube in background voxels and whether the background's cube clips it
     void absorbBox(const ObjTSDF& obj, const float R[9], const float t[3], int32_t lo[3], int32_t size[3], bool& clipped);
     // ---- lifting objects (setLiftObjects, liftObject; EMFusionLift.cpp): never in a checkpoint; with the switch off no

@@ -6,7 +6,7 @@
 // it; colour is not touched; what lies outside the background's cube is clipped and lost.
 // absorbPose is float64 in the fixed operation order of include/emf_hip.h "Object contacts" (the pose of a pair with
 // a = the destination, b = the source) and needs no device.  This unit is compiled with a*b+c contraction off.
-#include "EMFusion.hpp"
+#include "EMFusionDetail.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -70,12 +70,10 @@ void EMFusion::absorbInto(ObjTSDF& obj) {
     s.truncdist = obj.getTruncDist();
     absorbRecord_.reserve(sizeof(emf_absorb_t));
     emf_absorb_t* rec = absorbRecord_.as<emf_absorb_t>();
-    emfCheck(emf_hip_absorbVolume(const_cast<float*>(background.tsdfPtr()), const_cast<float*>(background.weightsPtr()), n.val,
-                                  background.getVoxelSize(), background.getTruncDist(), params.tsdfParams.maxTSDFWeight, &s, e.R,
-                                  e.t, e.lo, e.size, rec, main.abi()),
-             "EMFusion::absorb");
-    hipCheck(hipMemcpyAsync(&e.record, rec, sizeof(emf_absorb_t), hipMemcpyDeviceToHost, main.get()), "EMFusion::absorb (record)");
-    main.waitForCompletion();
+    launchedRecord(emf_hip_absorbVolume(const_cast<float*>(background.tsdfPtr()), const_cast<float*>(background.weightsPtr()), n.val,
+                                        background.getVoxelSize(), background.getTruncDist(), params.tsdfParams.maxTSDFWeight, &s,
+                                        e.R, e.t, e.lo, e.size, rec, main.abi()),
+                   "EMFusion::absorb", rec, &e.record);
     absorbDirty_ = true;
     absorbLog_.push_back(e);
 }
@@ -94,29 +92,28 @@ void EMFusion::absorbFinish() {
     absorbDirty_ = false;
 }
 
-EMFusion::AbsorbEvent EMFusion::absorbObject(int id) {
-    if (sharded || world > 1)
-        throw HipError("EMFusion::absorbObject: absorbing objects is not supported on the sharded path", EMF_E_ARG);
-    if (id == 0) throw HipError("EMFusion::absorbObject: the background cannot be absorbed into itself", EMF_E_ARG);
+std::list<ObjTSDF>::iterator EMFusion::ownedObjectOrThrow(const char* who, int id, const char* background) {
+    const std::string w = std::string("EMFusion::") + who;
+    if (id == 0) throw HipError(w + ": " + background, EMF_E_ARG);
     auto it = std::find_if(objects.begin(), objects.end(), [&](const ObjTSDF& o) { return o.getID() == id; });
     if (it == objects.end()) {
         if (std::find(allIds.begin(), allIds.end(), id) != allIds.end())
-            throw HipError("EMFusion::absorbObject: object " + std::to_string(id) + " is not owned by this rank", EMF_E_ARG);
-        throw HipError("EMFusion::absorbObject: no object " + std::to_string(id), EMF_E_ARG);
+            throw HipError(w + ": object " + std::to_string(id) + " is not owned by this rank", EMF_E_ARG);
+        throw HipError(w + ": no object " + std::to_string(id), EMF_E_ARG);
     }
+    return it;
+}
+
+EMFusion::AbsorbEvent EMFusion::absorbObject(int id) {
+    if (sharded || world > 1)
+        throw HipError("EMFusion::absorbObject: absorbing objects is not supported on the sharded path", EMF_E_ARG);
+    auto it = ownedObjectOrThrow("absorbObject", id, "the background cannot be absorbed into itself");
     // An explicit call absorbs what it names, a person under ignore_person too: the caller asked for this object.
     drainForQuery();
     absorbInto(*it);
     const AbsorbEvent e = absorbLog_.back();
-    try {
-        deleteOwned(it);  // the kept mesh and the exp_vols copy as for any deletion
-    } catch (...) {  // the front copy is written: what is derived from it is renewed whatever became of the deletion
-        absorbFinish();
-        rebuildModelTable();
-        throw;
-    }
-    absorbFinish();
-    rebuildModelTable();
+    // the front copy is written: what is derived from it is renewed whatever becomes of the deletion
+    writeThenRenew([&] { deleteOwned(it); });  // the kept mesh and the exp_vols copy as for any deletion
     return e;
 }
 
@@ -131,14 +128,10 @@ void EMFusion::writeAbsorbed(const std::string& dir) {
     for (const AbsorbEvent& e : absorbLog_) {
         const emf_absorb_t& r = e.record;
         std::fprintf(file, "%d %d %d", e.id, e.frame, e.clipped ? 1 : 0);
-        for (int i = 0; i < 3; ++i) std::fprintf(file, " %d", e.lo[i]);
-        for (int i = 0; i < 3; ++i) std::fprintf(file, " %d", e.size[i]);
-        for (const uint64_t v : {r.visited, r.outside, r.unknown, r.masked, r.saturated, r.fused, r.fresh, r.solid})
-            std::fprintf(file, " %llu", static_cast<unsigned long long>(v));
-        for (int i = 0; i < 3; ++i) std::fprintf(file, " %d", r.lo[i]);
-        for (int i = 0; i < 3; ++i) std::fprintf(file, " %d", r.hi[i]);
-        for (int i = 0; i < 9; ++i) std::fprintf(file, " %.9g", static_cast<double>(e.R[i]));
-        for (int i = 0; i < 3; ++i) std::fprintf(file, " %.9g", static_cast<double>(e.t[i]));
+        detail::printInts(file, e.lo), detail::printInts(file, e.size);
+        detail::printCounts(file, {r.visited, r.outside, r.unknown, r.masked, r.saturated, r.fused, r.fresh, r.solid});
+        detail::printInts(file, r.lo), detail::printInts(file, r.hi);
+        detail::printFloats(file, e.R), detail::printFloats(file, e.t);
         std::fprintf(file, "\n");
     }
     std::fclose(file);

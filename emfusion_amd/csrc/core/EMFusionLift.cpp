@@ -7,7 +7,7 @@
 // voxels the object holds as foreground (emf_hip_releaseVolume).  One launch each on the main stream.  Colour is not
 // touched.  The poses are absorbPose (float64 in a fixed order, rounded once): this unit is compiled with a*b+c
 // contraction off.
-#include "EMFusion.hpp"
+#include "EMFusionDetail.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -38,12 +38,10 @@ void EMFusion::liftSeed(ObjTSDF& obj, LiftEvent& e) {
     const int32_t lo[3] = {0, 0, 0};
     liftRecord_.reserve(sizeof(emf_seed_t) + sizeof(emf_release_t));
     emf_seed_t* rec = liftRecord_.as<emf_seed_t>();
-    emfCheck(emf_hip_seedVolume(const_cast<float*>(obj.tsdfPtr()), const_cast<float*>(obj.weightsPtr()), r.val, obj.getVoxelSize(),
-                                obj.getTruncDist(), params.tsdfParams.maxTSDFWeight, &s, e.seedR, e.seedT, lo, r.val, rec,
-                                main.abi()),
-             "EMFusion::lift (seed)");
-    hipCheck(hipMemcpyAsync(&e.seed, rec, sizeof(emf_seed_t), hipMemcpyDeviceToHost, main.get()), "EMFusion::lift (seed record)");
-    main.waitForCompletion();
+    launchedRecord(emf_hip_seedVolume(const_cast<float*>(obj.tsdfPtr()), const_cast<float*>(obj.weightsPtr()), r.val, obj.getVoxelSize(),
+                                      obj.getTruncDist(), params.tsdfParams.maxTSDFWeight, &s, e.seedR, e.seedT, lo, r.val, rec,
+                                      main.abi()),
+                   "EMFusion::lift (seed)", rec, &e.seed);
     obj.volumesWritten(main);  // brick flags, sign maps, gradients, the foreground probabilities
 }
 
@@ -55,12 +53,10 @@ void EMFusion::liftRelease(ObjTSDF& obj, LiftEvent& e) {
     const Vec3i n = background.getVolumeRes(), r = obj.getVolumeRes();
     liftRecord_.reserve(sizeof(emf_seed_t) + sizeof(emf_release_t));
     emf_release_t* rec = reinterpret_cast<emf_release_t*>(liftRecord_.as<char>() + sizeof(emf_seed_t));
-    emfCheck(emf_hip_releaseVolume(const_cast<float*>(background.tsdfPtr()), const_cast<float*>(background.weightsPtr()), n.val,
-                                   background.getVoxelSize(), obj.fgVolMaskPtr(), r.val, obj.getVoxelSize(), e.releaseR, e.releaseT,
-                                   e.lo, e.size, rec, main.abi()),
-             "EMFusion::lift (release)");
-    hipCheck(hipMemcpyAsync(&e.release, rec, sizeof(emf_release_t), hipMemcpyDeviceToHost, main.get()), "EMFusion::lift (release record)");
-    main.waitForCompletion();
+    launchedRecord(emf_hip_releaseVolume(const_cast<float*>(background.tsdfPtr()), const_cast<float*>(background.weightsPtr()), n.val,
+                                         background.getVoxelSize(), obj.fgVolMaskPtr(), r.val, obj.getVoxelSize(), e.releaseR,
+                                         e.releaseT, e.lo, e.size, rec, main.abi()),
+                   "EMFusion::lift (release)", rec, &e.release);
     absorbDirty_ = true;  // the background's front copy was written: absorbFinish() renews what is derived from it
     liftLog_.push_back(e);
 }
@@ -85,44 +81,26 @@ void EMFusion::liftSeedCreated() {
 void EMFusion::liftReleaseCreated() {
     if (liftPending_.empty()) return;
     quiesce();
-    try {
-        for (LiftEvent& e : liftPending_) {
+    // the front copy may be written: what is derived from it is renewed whatever becomes of the rest
+    writeThenRenew([&] {
+        std::vector<LiftEvent> pending;
+        pending.swap(liftPending_);  // nothing stays owed, whatever becomes of the releases
+        for (LiftEvent& e : pending) {
             auto it = std::find_if(objects.begin(), objects.end(), [&](const ObjTSDF& o) { return o.getID() == e.id; });
             if (it != objects.end()) liftRelease(*it, e);
         }
-    } catch (...) {  // the front copy may be written: what is derived from it is renewed whatever became of the rest
-        liftPending_.clear();
-        absorbFinish();
-        rebuildModelTable();
-        throw;
-    }
-    liftPending_.clear();
-    absorbFinish();
-    rebuildModelTable();
+    });
 }
 
 EMFusion::LiftEvent EMFusion::liftObject(int id) {
     if (sharded || world > 1)
         throw HipError("EMFusion::liftObject: lifting objects is not supported on the sharded path", EMF_E_ARG);
-    if (id == 0) throw HipError("EMFusion::liftObject: the background cannot be lifted out of itself", EMF_E_ARG);
-    auto it = std::find_if(objects.begin(), objects.end(), [&](const ObjTSDF& o) { return o.getID() == id; });
-    if (it == objects.end()) {
-        if (std::find(allIds.begin(), allIds.end(), id) != allIds.end())
-            throw HipError("EMFusion::liftObject: object " + std::to_string(id) + " is not owned by this rank", EMF_E_ARG);
-        throw HipError("EMFusion::liftObject: no object " + std::to_string(id), EMF_E_ARG);
-    }
+    auto it = ownedObjectOrThrow("liftObject", id, "the background cannot be lifted out of itself");
     drainForQuery();
     LiftEvent e;
     liftSeed(*it, e);
-    try {
-        liftRelease(*it, e);
-    } catch (...) {  // the object's volume is written: the table describes it again before the exception goes on
-        absorbFinish();
-        rebuildModelTable();
-        throw;
-    }
-    absorbFinish();
-    rebuildModelTable();
+    // the object's volume is written: the table describes it again whatever becomes of the release
+    writeThenRenew([&] { liftRelease(*it, e); });
     return e;
 }
 
@@ -140,20 +118,13 @@ void EMFusion::writeLifted(const std::string& dir) {
         const emf_seed_t& s = e.seed;
         const emf_release_t& r = e.release;
         std::fprintf(file, "%d %d %d", e.id, e.frame, e.clipped ? 1 : 0);
-        for (int i = 0; i < 3; ++i) std::fprintf(file, " %d", e.lo[i]);
-        for (int i = 0; i < 3; ++i) std::fprintf(file, " %d", e.size[i]);
-        for (const uint64_t v : {s.visited, s.kept, s.outside, s.unknown, s.masked, s.saturated, s.seeded, s.solid})
-            std::fprintf(file, " %llu", static_cast<unsigned long long>(v));
-        for (int i = 0; i < 3; ++i) std::fprintf(file, " %d", s.lo[i]);
-        for (int i = 0; i < 3; ++i) std::fprintf(file, " %d", s.hi[i]);
-        for (const uint64_t v : {r.visited, r.empty, r.free_space, r.outside, r.unclaimed, r.released, r.solid})
-            std::fprintf(file, " %llu", static_cast<unsigned long long>(v));
-        for (int i = 0; i < 3; ++i) std::fprintf(file, " %d", r.lo[i]);
-        for (int i = 0; i < 3; ++i) std::fprintf(file, " %d", r.hi[i]);
-        for (int i = 0; i < 9; ++i) std::fprintf(file, " %.9g", static_cast<double>(e.seedR[i]));
-        for (int i = 0; i < 3; ++i) std::fprintf(file, " %.9g", static_cast<double>(e.seedT[i]));
-        for (int i = 0; i < 9; ++i) std::fprintf(file, " %.9g", static_cast<double>(e.releaseR[i]));
-        for (int i = 0; i < 3; ++i) std::fprintf(file, " %.9g", static_cast<double>(e.releaseT[i]));
+        detail::printInts(file, e.lo), detail::printInts(file, e.size);
+        detail::printCounts(file, {s.visited, s.kept, s.outside, s.unknown, s.masked, s.saturated, s.seeded, s.solid});
+        detail::printInts(file, s.lo), detail::printInts(file, s.hi);
+        detail::printCounts(file, {r.visited, r.empty, r.free_space, r.outside, r.unclaimed, r.released, r.solid});
+        detail::printInts(file, r.lo), detail::printInts(file, r.hi);
+        detail::printFloats(file, e.seedR), detail::printFloats(file, e.seedT);
+        detail::printFloats(file, e.releaseR), detail::printFloats(file, e.releaseT);
         std::fprintf(file, "\n");
     }
     std::fclose(file);

@@ -1,0 +1,260 @@
+// volume_transfer.hip -- the passes that hand the signed-distance band of one volume to another through a rigid pose, in
+// place in the DESTINATION (include/emf_hip.h "Absorbing a volume" and "Lifting a volume").
+//   k_ab_absorb   the band of the SOURCE, fused into the destination by the destination's running average.
+//   k_lf_seed     the destination takes the source's band only where it has no observation of its own.
+//   k_lf_release  the destination gives up the band voxels that a claimant holds.
+// One workgroup per 32 x 8 x 8 destination tile that meets the box, 256 lanes = 32 along x, 8 rows; a lane walks the tile's
+// z planes with the x and y parts of the three pose rows hoisted.  A wave whose lanes all lie outside the box leaves.
+// Absorb and seed are one walk (rs_transfer) under two policies resolved at compile time: per voxel what the policy asks
+// of the destination first, then the sample point and what the source holds there (rs_source of resample.hpp: the
+// outside rule, 8 + 8 dependent gathers, the mask byte), then the policy's band rule and store.  The release reads its
+// own weight and tsdf first -- EMPTY and FREE cost 8 bytes and no transform -- then the sample point, the outside rule
+// and the claimant's mask byte at the nearest voxel.  A destination voxel reads and writes only itself: the passes are in
+// place.  Only the words whose bits change are stored.  Per wave: wave_reduce of what is not zero anywhere in the wave,
+// then one integer atomic per non-zero quantity from lane 0; the record does not depend on the order of lanes, waves or
+// workgroups.  No float atomics, no LDS, no barrier.  Every float step is one float32 operation (resample.hpp).
+#include "resample.hpp"
+
+namespace emf_hip {
+namespace {
+
+static_assert(sizeof(emf_absorb_t) == 88 && sizeof(emf_absorb_source_t) == 56, "mirrored by emfusion_amd/_lib.py");
+static_assert(sizeof(emf_seed_t) == 88 && sizeof(emf_release_t) == 80, "mirrored by emfusion_amd/_lib.py");
+
+// A policy of rs_transfer holds a lane's counts beyond outside / unknown / masked and says
+//   wants(a, v)       what the destination voxel v decides before anything of the source is read: false = done;
+//   take(a, v, s, w)  what becomes of a VALUE s with the corner weights w: true = the voxel was written and counts for
+//                     the bounds;
+//   reduce(any)       the wave sums of its counts (those of the written voxels only where `any` lane wrote one);
+//   commit(out, any)  lane 0: its counts into the record; returns how many voxels they stand for.
+
+struct AbsorbPolicy {
+    using Record = emf_absorb_t;
+    unsigned cSat = 0u, cFused = 0u, cFresh = 0u, cSolid = 0u;
+
+    __device__ __forceinline__ bool wants(const ResampleArgs<Record>&, size_t) { return true; }
+    __device__ __forceinline__ bool take(const ResampleArgs<Record>& a, size_t v, float s, const float (&w)[8]) {
+        if (!(fabsf(s) < 1.f)) {  // "at least one source truncation away": no value the destination can fuse
+            cSat += 1u;
+            return false;
+        }
+        const float u = fminf(fmaxf(__fmul_rn(s, a.ratio), -1.f), 1.f);
+        const float wo = rs_min8(w);
+        const float pw = a.dstWeights[v], pt = a.dstTsdf[v];
+        float nt, nw;
+        if (!(pw > 0.f)) {  // a select: whatever an unseen voxel holds goes nowhere
+            nt = u;
+            nw = fminf(wo, a.maxWeight);
+            cFresh += 1u;
+        } else {
+            nt = __fdiv_rn(__fadd_rn(mul_rounded(pw, pt), mul_rounded(wo, u)), __fadd_rn(pw, wo));
+            nw = fminf(__fadd_rn(pw, wo), a.maxWeight);
+        }
+        cFused += 1u;
+        if (!(nt > 0.f)) cSolid += 1u;
+        if (__float_as_uint(nt) != __float_as_uint(pt)) a.dstTsdf[v] = nt;
+        if (__float_as_uint(nw) != __float_as_uint(pw)) a.dstWeights[v] = nw;
+        return true;
+    }
+    __device__ __forceinline__ void reduce(bool any) {
+        cSat = wave_reduce<OpAdd>(cSat);
+        if (any) cFused = wave_reduce<OpAdd>(cFused), cFresh = wave_reduce<OpAdd>(cFresh), cSolid = wave_reduce<OpAdd>(cSolid);
+    }
+    __device__ __forceinline__ unsigned long long commit(Record* out, bool any) const {
+        rs_add64(&out->saturated, cSat);
+        if (any) rs_add64(&out->fused, cFused), rs_add64(&out->fresh, cFresh), rs_add64(&out->solid, cSolid);
+        return static_cast<unsigned long long>(cSat) + (any ? cFused : 0u);
+    }
+};
+
+struct SeedPolicy {
+    using Record = emf_seed_t;
+    unsigned cKept = 0u, cSat = 0u, cSeed = 0u, cSolid = 0u;
+    float pw = 0.f;  // the voxel's own weight
+
+    __device__ __forceinline__ bool wants(const ResampleArgs<Record>& a, size_t v) {
+        pw = a.dstWeights[v];
+        if (pw > 0.f) cKept += 1u;  // its own observation stands: nothing of the source is read
+        return !(pw > 0.f);
+    }
+    __device__ __forceinline__ bool take(const ResampleArgs<Record>& a, size_t v, float s, const float (&w)[8]) {
+        const float u = __fmul_rn(s, a.ratio);
+        if (!(fabsf(s) < 1.f) || !(fabsf(u) < 1.f)) {  // outside the source's band or the destination's own
+            cSat += 1u;
+            return false;
+        }
+        const float nw = fminf(rs_min8(w), a.maxWeight);
+        const float pt = a.dstTsdf[v];
+        cSeed += 1u;
+        if (!(u > 0.f)) cSolid += 1u;
+        if (__float_as_uint(u) != __float_as_uint(pt)) a.dstTsdf[v] = u;
+        if (__float_as_uint(nw) != __float_as_uint(pw)) a.dstWeights[v] = nw;
+        return true;
+    }
+    __device__ __forceinline__ void reduce(bool any) {
+        cKept = wave_reduce<OpAdd>(cKept), cSat = wave_reduce<OpAdd>(cSat);
+        if (any) cSeed = wave_reduce<OpAdd>(cSeed), cSolid = wave_reduce<OpAdd>(cSolid);
+    }
+    __device__ __forceinline__ unsigned long long commit(Record* out, bool any) const {
+        rs_add64(&out->kept, cKept), rs_add64(&out->saturated, cSat);
+        if (any) rs_add64(&out->seeded, cSeed), rs_add64(&out->solid, cSolid);
+        return static_cast<unsigned long long>(cKept) + cSat + (any ? cSeed : 0u);
+    }
+};
+
+template <typename Policy>
+__device__ __forceinline__ void rs_transfer(const ResampleArgs<typename Policy::Record>& a) {
+    const RsLane ln = rs_lane(a.t0, a.ntx, a.nty, a.lo, a.hi);
+    const int x = ln.x, y = ln.y;
+    if (__ballot(ln.mine) == 0ull) return;  // wave-uniform; the kernel has no barrier
+
+    const I3 nd = a.nd;
+    const size_t dy = static_cast<size_t>(nd.x), dz = dy * nd.y;
+    const RsVolume src = rs_volume(a.srcTsdf, a.srcWeights, a.srcMask, a.srcUnseen, a.ns);
+    const RsRows rows = rs_rows(a.R, rs_pd(x, nd.x, a.voxD), rs_pd(y, nd.y, a.voxD));
+
+    Policy p;
+    unsigned cOut = 0u, cUnk = 0u, cMask = 0u;
+    RsBounds written(nd);
+
+    if (ln.mine) {
+        for (int z = ln.z0; z < ln.z1; ++z) {
+            const size_t v = static_cast<size_t>(z) * dz + static_cast<size_t>(y) * dy + x;
+            if (!p.wants(a, v)) continue;
+            float s, w[8];
+            switch (rs_source(src, rs_sample(rows, a.R, a.t, rs_pd(z, nd.z, a.voxD), a.voxS, src.half), s, w)) {
+                case RsClass::Outside: cOut += 1u; break;
+                case RsClass::Unknown: cUnk += 1u; break;
+                case RsClass::Masked: cMask += 1u; break;
+                case RsClass::Value:
+                    if (p.take(a, v, s, w)) written.include(x, y, z);
+            }
+        }
+    }
+
+    // a lane holds at most 8 voxels, a wave 512: every wave sum fits 32 bits
+    cOut = wave_reduce<OpAdd>(cOut), cUnk = wave_reduce<OpAdd>(cUnk), cMask = wave_reduce<OpAdd>(cMask);
+    const bool any = written.any();
+    p.reduce(any);
+    if (any) written.reduce();
+    if ((threadIdx.x & 63u) == 0u) {
+        typename Policy::Record* out = a.record;
+        rs_add64(&out->visited, static_cast<unsigned long long>(cOut) + cUnk + cMask + p.commit(out, any));
+        rs_add64(&out->outside, cOut), rs_add64(&out->unknown, cUnk), rs_add64(&out->masked, cMask);
+        if (any) written.commit(out);
+    }
+}
+
+__global__ __launch_bounds__(kRsBlock) void k_ab_absorb(const ResampleArgs<emf_absorb_t> a) { rs_transfer<AbsorbPolicy>(a); }
+
+__global__ __launch_bounds__(kRsBlock) void k_lf_seed(const ResampleArgs<emf_seed_t> a) { rs_transfer<SeedPolicy>(a); }
+
+// the source is the claimant: its mask (or NULL: everything inside its cube), its resolution and voxel size
+__global__ __launch_bounds__(kRsBlock) void k_lf_release(const ResampleArgs<emf_release_t> a) {
+    const RsLane ln = rs_lane(a.t0, a.ntx, a.nty, a.lo, a.hi);
+    const int x = ln.x, y = ln.y;
+    if (__ballot(ln.mine) == 0ull) return;  // wave-uniform; the kernel has no barrier
+
+    const I3 nd = a.nd;
+    const size_t dy = static_cast<size_t>(nd.x), dz = dy * nd.y;
+    const RsVolume claim = rs_volume(nullptr, nullptr, a.srcMask, nullptr, a.ns);
+    const RsRows rows = rs_rows(a.R, rs_pd(x, nd.x, a.voxD), rs_pd(y, nd.y, a.voxD));
+
+    unsigned cEmpty = 0u, cFree = 0u, cOut = 0u, cUncl = 0u, cRel = 0u, cSolid = 0u;
+    RsBounds released(nd);
+
+    if (ln.mine) {
+        for (int z = ln.z0; z < ln.z1; ++z) {
+            const size_t v = static_cast<size_t>(z) * dz + static_cast<size_t>(y) * dy + x;
+            const float pw = a.dstWeights[v], pt = a.dstTsdf[v];
+            if (!(pw > 0.f)) {
+                cEmpty += 1u;
+                continue;
+            }
+            if (!(fabsf(pt) < 1.f)) {  // free space and NaN stay: only the band is released
+                cFree += 1u;
+                continue;
+            }
+            const V3 q = rs_sample(rows, a.R, a.t, rs_pd(z, nd.z, a.voxD), a.voxS, claim.half);
+            if (rs_outside(q, claim.fn)) {
+                cOut += 1u;
+                continue;
+            }
+            if (rs_masked(claim, q)) {
+                cUncl += 1u;
+                continue;
+            }
+            cRel += 1u;
+            if (!(pt > 0.f)) cSolid += 1u;
+            released.include(x, y, z);
+            // what TSDF::reset leaves in an unseen voxel; pw > 0, so its word always changes
+            if (__float_as_uint(pt) != 0u) a.dstTsdf[v] = 0.f;
+            a.dstWeights[v] = 0.f;
+        }
+    }
+
+    cEmpty = wave_reduce<OpAdd>(cEmpty), cFree = wave_reduce<OpAdd>(cFree), cOut = wave_reduce<OpAdd>(cOut);
+    cUncl = wave_reduce<OpAdd>(cUncl);
+    const bool any = released.any();
+    if (any) {
+        cRel = wave_reduce<OpAdd>(cRel), cSolid = wave_reduce<OpAdd>(cSolid);
+        released.reduce();
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        emf_release_t* out = a.record;
+        rs_add64(&out->visited, static_cast<unsigned long long>(cEmpty) + cFree + cOut + cUncl + (any ? cRel : 0u));
+        rs_add64(&out->empty, cEmpty), rs_add64(&out->free_space, cFree), rs_add64(&out->outside, cOut), rs_add64(&out->unclaimed, cUncl);
+        if (any) {
+            rs_add64(&out->released, cRel), rs_add64(&out->solid, cSolid);
+            released.commit(out);
+        }
+    }
+}
+
+}  // namespace
+}  // namespace emf_hip
+
+using namespace emf_hip;
+
+extern "C" {
+
+int emf_hip_absorbVolume(float* dst_tsdf, float* dst_weights, const int32_t dst_res[3], float dst_voxel_size, float dst_truncdist,
+                         float max_weight, const emf_absorb_source_t* source, const float R[9], const float t[3],
+                         const int32_t box_lo[3], const int32_t box_size[3], emf_absorb_t* record_dev, emf_stream_t stream) {
+    ResampleArgs<emf_absorb_t> a{};
+    unsigned tiles = 0;
+    EMF_TRY(rs_check_transfer("absorbVolume", &a, &tiles, dst_tsdf, dst_weights, dst_res, dst_voxel_size, dst_truncdist, max_weight, source,
+                              R, t, box_lo, box_size, record_dev));
+    return rs_launch("absorbVolume", k_ab_absorb, a, tiles, stream);
+}
+
+int emf_hip_seedVolume(float* dst_tsdf, float* dst_weights, const int32_t dst_res[3], float dst_voxel_size, float dst_truncdist,
+                       float max_weight, const emf_absorb_source_t* source, const float R[9], const float t[3],
+                       const int32_t box_lo[3], const int32_t box_size[3], emf_seed_t* record_dev, emf_stream_t stream) {
+    ResampleArgs<emf_seed_t> a{};
+    unsigned tiles = 0;
+    EMF_TRY(rs_check_transfer("seedVolume", &a, &tiles, dst_tsdf, dst_weights, dst_res, dst_voxel_size, dst_truncdist, max_weight, source, R,
+                              t, box_lo, box_size, record_dev));
+    return rs_launch("seedVolume", k_lf_seed, a, tiles, stream);
+}
+
+int emf_hip_releaseVolume(float* dst_tsdf, float* dst_weights, const int32_t dst_res[3], float dst_voxel_size,
+                          const uint8_t* claim_mask, const int32_t claim_res[3], float claim_voxel_size, const float R[9],
+                          const float t[3], const int32_t box_lo[3], const int32_t box_size[3], emf_release_t* record_dev,
+                          emf_stream_t stream) {
+    EMF_TRY(rs_check_destination("releaseVolume", dst_tsdf, dst_weights, dst_res, R, t, box_lo, box_size, record_dev));
+    if (!claim_res) return fail(EMF_E_ARG, "releaseVolume: the claimant's resolution is NULL");
+    unsigned long long nDst = 0, nClaim = 0;
+    EMF_TRY(rs_check_volume("releaseVolume", dst_res, "destination", &nDst));
+    EMF_TRY(rs_check_volume("releaseVolume", claim_res, "claimant", &nClaim));
+    ResampleArgs<emf_release_t> a{};
+    unsigned tiles = 0;
+    const void* others[1] = {claim_mask};
+    const size_t otherBytes[1] = {static_cast<size_t>(nClaim)};
+    EMF_TRY(rs_check_layout("releaseVolume", &a, &tiles, dst_tsdf, dst_weights, dst_res, nDst, dst_voxel_size, "claimant's mask", claim_res,
+                            claim_voxel_size, others, otherBytes, 1, R, t, box_lo, box_size, record_dev));
+    a.srcMask = claim_mask;
+    return rs_launch("releaseVolume", k_lf_release, a, tiles, stream);
+}
+
+}  // extern "C"

@@ -2090,6 +2090,41 @@ def absorb_box(dst_res, dst_voxel_size, src_res, src_voxel_size, pose):
     return tuple(o.lo), tuple(o.size)
 
 
+def _transfer_call(dst, other_res, other_voxel_size, pose, box, out, dtype):
+    """What the passes over a box of `dst` share: the destination's arguments (tsdf, weights, res, voxel size), the box
+    (lo, size) -- None: the covering box of the whole other volume (absorb_box) -- and the record array."""
+    tsdf, weights = _vol(dst["tsdf"], np.float32), _vol(dst["weights"], np.float32)
+    assert weights.shape == tsdf.shape
+    res = (tsdf.shape[2], tsdf.shape[1], tsdf.shape[0])
+    if box is None:
+        box = absorb_box(res, dst["voxel_size"], other_res, other_voxel_size, pose)
+    lo, size = _box(res, box)
+    record = DeviceArray((1,), dtype) if out is None else out
+    assert record.dtype == dtype and record.shape[0] >= 1
+    return (_ptr(tsdf), _ptr(weights), _i3(res), float(np.float32(dst["voxel_size"]))), (_i3(lo), _i3(size)), record
+
+
+def _transfer_volume(entry, dtype, dst, src, pose, box, out, lib, stream):
+    """absorb_volume and seed_volume: emf_hip_<entry> of a whole source into dst."""
+    stsdf, sweights = _vol(src["tsdf"], np.float32), _vol(src["weights"], np.float32)
+    assert sweights.shape == stsdf.shape
+    s = _lib.EmfAbsorbSource()
+    s.tsdf, s.weights = stsdf.ptr, sweights.ptr
+    if src.get("fg_mask") is not None:
+        assert src["fg_mask"].shape == stsdf.shape
+        s.fgVolMask = _vol(src["fg_mask"], np.uint8).ptr
+    if src.get("unseen_tiles") is not None:
+        s.unseenTiles = src["unseen_tiles"].ptr
+    s.res = _i3((stsdf.shape[2], stsdf.shape[1], stsdf.shape[0]))
+    s.voxelSize, s.truncdist = float(np.float32(src["voxel_size"])), float(np.float32(src["truncdist"]))
+    d, b, record = _transfer_call(dst, tuple(s.res), src["voxel_size"], pose, box, out, dtype)
+    check("emf_hip_" + entry,
+          getattr(_L if lib is None else lib, "emf_hip_" + entry)(
+              *d, float(np.float32(dst["truncdist"])), float(np.float32(dst["max_weight"])), C.byref(s), _f(pose[0], 9),
+              _f(pose[1], 3), *b, _ptr(record), _stream(stream)))
+    return record.numpy()[0] if out is None else out
+
+
 def absorb_volume(dst, src, pose, box=None, out=None, lib=None, stream=None):
     """emf_hip_absorbVolume: the signed-distance band of `src` resampled through pose = (R, t) (f32, source frame <-
     destination frame) into `dst` and fused there, in place, by dst's running average.
@@ -2100,30 +2135,7 @@ def absorb_volume(dst, src, pose, box=None, out=None, lib=None, stream=None):
     fresh, solid; lo, hi of the fused voxels), or with out= (a device array of at least one record) that array.
     IT CARRIES THE BAND, NOT THE FREE SPACE AROUND IT: saturated source samples are left alone.  lib: another build of
     the kernel library (_lib.load_variant)."""
-    L = _L if lib is None else lib
-    tsdf, weights = _vol(dst["tsdf"], np.float32), _vol(dst["weights"], np.float32)
-    stsdf, sweights = _vol(src["tsdf"], np.float32), _vol(src["weights"], np.float32)
-    assert weights.shape == tsdf.shape and sweights.shape == stsdf.shape
-    res = (tsdf.shape[2], tsdf.shape[1], tsdf.shape[0])
-    s = _lib.EmfAbsorbSource()
-    s.tsdf, s.weights = stsdf.ptr, sweights.ptr
-    if src.get("fg_mask") is not None:
-        assert src["fg_mask"].shape == stsdf.shape
-        s.fgVolMask = _vol(src["fg_mask"], np.uint8).ptr
-    if src.get("unseen_tiles") is not None:
-        s.unseenTiles = src["unseen_tiles"].ptr
-    s.res = _i3((stsdf.shape[2], stsdf.shape[1], stsdf.shape[0]))
-    s.voxelSize, s.truncdist = float(np.float32(src["voxel_size"])), float(np.float32(src["truncdist"]))
-    if box is None:
-        box = absorb_box(res, dst["voxel_size"], tuple(s.res), src["voxel_size"], pose)
-    lo, size = _box(res, box)
-    record = DeviceArray((1,), ABSORB_DTYPE) if out is None else out
-    assert record.dtype == ABSORB_DTYPE and record.shape[0] >= 1
-    check("emf_hip_absorbVolume",
-          L.emf_hip_absorbVolume(_ptr(tsdf), _ptr(weights), _i3(res), float(np.float32(dst["voxel_size"])),
-                                 float(np.float32(dst["truncdist"])), float(np.float32(dst["max_weight"])), C.byref(s),
-                                 _f(pose[0], 9), _f(pose[1], 3), _i3(lo), _i3(size), _ptr(record), _stream(stream)))
-    return record.numpy()[0] if out is None else out
+    return _transfer_volume("absorbVolume", ABSORB_DTYPE, dst, src, pose, box, out, lib, stream)
 
 
 # ---- lifting a volume (include/emf_hip.h "Lifting a volume", DESIGN.md 5.30) ---------------------------------------
@@ -2139,30 +2151,7 @@ def seed_volume(dst, src, pose, box=None, out=None, lib=None, stream=None):
     inside its own band: no clamped +-1 is written.  dst, src, box and out as in absorb_volume (box None: the covering
     box of the whole source).  Returns the record (a 0-d numpy array of SEED_DTYPE: visited = kept + outside + unknown +
     masked + saturated + seeded; solid; lo, hi of the seeded voxels), or with out= that array."""
-    L = _L if lib is None else lib
-    tsdf, weights = _vol(dst["tsdf"], np.float32), _vol(dst["weights"], np.float32)
-    stsdf, sweights = _vol(src["tsdf"], np.float32), _vol(src["weights"], np.float32)
-    assert weights.shape == tsdf.shape and sweights.shape == stsdf.shape
-    res = (tsdf.shape[2], tsdf.shape[1], tsdf.shape[0])
-    s = _lib.EmfAbsorbSource()
-    s.tsdf, s.weights = stsdf.ptr, sweights.ptr
-    if src.get("fg_mask") is not None:
-        assert src["fg_mask"].shape == stsdf.shape
-        s.fgVolMask = _vol(src["fg_mask"], np.uint8).ptr
-    if src.get("unseen_tiles") is not None:
-        s.unseenTiles = src["unseen_tiles"].ptr
-    s.res = _i3((stsdf.shape[2], stsdf.shape[1], stsdf.shape[0]))
-    s.voxelSize, s.truncdist = float(np.float32(src["voxel_size"])), float(np.float32(src["truncdist"]))
-    if box is None:
-        box = absorb_box(res, dst["voxel_size"], tuple(s.res), src["voxel_size"], pose)
-    lo, size = _box(res, box)
-    record = DeviceArray((1,), SEED_DTYPE) if out is None else out
-    assert record.dtype == SEED_DTYPE and record.shape[0] >= 1
-    check("emf_hip_seedVolume",
-          L.emf_hip_seedVolume(_ptr(tsdf), _ptr(weights), _i3(res), float(np.float32(dst["voxel_size"])),
-                               float(np.float32(dst["truncdist"])), float(np.float32(dst["max_weight"])), C.byref(s),
-                               _f(pose[0], 9), _f(pose[1], 3), _i3(lo), _i3(size), _ptr(record), _stream(stream)))
-    return record.numpy()[0] if out is None else out
+    return _transfer_volume("seedVolume", SEED_DTYPE, dst, src, pose, box, out, lib, stream)
 
 
 def release_volume(dst, claim, pose, box=None, out=None, lib=None, stream=None):
@@ -2173,9 +2162,6 @@ def release_volume(dst, claim, pose, box=None, out=None, lib=None, stream=None):
     covering box of the claimant's cube (absorb_box).  Returns the record (RELEASE_DTYPE: visited = empty + free_space +
     outside + unclaimed + released; solid; lo, hi of the released voxels), or with out= that array."""
     L = _L if lib is None else lib
-    tsdf, weights = _vol(dst["tsdf"], np.float32), _vol(dst["weights"], np.float32)
-    assert weights.shape == tsdf.shape
-    res = (tsdf.shape[2], tsdf.shape[1], tsdf.shape[0])
     mask = claim.get("fg_mask")
     if mask is not None:
         mask = _vol(mask, np.uint8)
@@ -2183,15 +2169,10 @@ def release_volume(dst, claim, pose, box=None, out=None, lib=None, stream=None):
         assert claim.get("res") is None or tuple(int(v) for v in claim["res"]) == cres
     else:
         cres = tuple(int(v) for v in claim["res"])
-    if box is None:
-        box = absorb_box(res, dst["voxel_size"], cres, claim["voxel_size"], pose)
-    lo, size = _box(res, box)
-    record = DeviceArray((1,), RELEASE_DTYPE) if out is None else out
-    assert record.dtype == RELEASE_DTYPE and record.shape[0] >= 1
+    d, b, record = _transfer_call(dst, cres, claim["voxel_size"], pose, box, out, RELEASE_DTYPE)
     check("emf_hip_releaseVolume",
-          L.emf_hip_releaseVolume(_ptr(tsdf), _ptr(weights), _i3(res), float(np.float32(dst["voxel_size"])), _ptr(mask),
-                                  _i3(cres), float(np.float32(claim["voxel_size"])), _f(pose[0], 9), _f(pose[1], 3), _i3(lo),
-                                  _i3(size), _ptr(record), _stream(stream)))
+          L.emf_hip_releaseVolume(*d, _ptr(mask), _i3(cres), float(np.float32(claim["voxel_size"])), _f(pose[0], 9),
+                                  _f(pose[1], 3), *b, _ptr(record), _stream(stream)))
     return record.numpy()[0] if out is None else out
 
 

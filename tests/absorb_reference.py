@@ -49,6 +49,16 @@ def ratio_of(src, dst):
 
 # ---- the device stage, vectorised ----------------------------------------------------------------------------------
 
+def outside_of(q, res):
+    """The pad-1 outside rule, a NaN first, of sample points q = (qx, qy, qz) in a volume of res (x, y, z)."""
+    with np.errstate(all="ignore"):
+        outside = np.zeros(len(q[0]), bool)
+        for j in range(3):
+            up = q[j] + f32(1)
+            outside |= np.isnan(q[j]) | (q[j] < 0) | (up >= f32(res[j]))
+    return outside
+
+
 def absorb(dst, src, pose, box=None):
     """(tsdf, weights, record) of the destination after the pass over box = (lo, size), both (x, y, z)."""
     td, wd = dst["tsdf"].copy(), dst["weights"].copy()
@@ -66,10 +76,7 @@ def absorb(dst, src, pose, box=None):
     q = sample_points((x, y, z), res_d, dst["voxel_size"], R, t, res_s, src["voxel_size"])
     ratio, max_weight = ratio_of(src, dst), f32(dst["max_weight"])
     with np.errstate(all="ignore"):
-        outside = np.zeros(len(x), bool)
-        for j in range(3):
-            up = q[j] + f32(1)
-            outside |= np.isnan(q[j]) | (q[j] < 0) | (up >= f32(res_s[j]))
+        outside = outside_of(q, res_s)
         out["outside"] = int(outside.sum())
         keep = ~outside
         x, y, z = x[keep], y[keep], z[keep]
@@ -120,6 +127,22 @@ def absorb(dst, src, pose, box=None):
 
 # ---- the device stage, voxel by voxel --------------------------------------------------------------------------------
 
+def at(arr, v):
+    return arr[v[2], v[1], v[0]]
+
+
+def sample_loop(v, nd, voxd, R, t, ns, voxs):
+    """The sample point q of destination voxel v and whether it lies outside; np.float32 scalars, one operation a step."""
+    pd = [(f32(v[j]) - f32(nd[j] - 1) / f32(2)) * voxd for j in range(3)]
+    q = []
+    for i in range(3):
+        s = R[3 * i] * pd[0] + R[3 * i + 1] * pd[1]
+        s = s + R[3 * i + 2] * pd[2]
+        s = s + t[i]
+        q.append(s / voxs + f32(ns[i] - 1) / f32(2))
+    return q, any(np.isnan(q[j]) or q[j] < 0 or q[j] + f32(1) >= f32(ns[j]) for j in range(3))
+
+
 def absorb_loop(dst, src, pose, box=None):
     """The same by a plain loop over the box; every float step an np.float32 scalar operation."""
     td, wd = dst["tsdf"].copy(), dst["weights"].copy()
@@ -134,23 +157,14 @@ def absorb_loop(dst, src, pose, box=None):
     c = dict.fromkeys(COUNTS, 0)
     blo, bhi = list(nd), [-1, -1, -1]
 
-    def at(arr, v):
-        return arr[v[2], v[1], v[0]]
-
     with np.errstate(all="ignore"):
         for z in range(lo[2], lo[2] + max(size[2], 0)):
             for y in range(lo[1], lo[1] + max(size[1], 0)):
                 for x in range(lo[0], lo[0] + max(size[0], 0)):
                     v = (x, y, z)
                     c["visited"] += 1
-                    pd = [(f32(v[j]) - f32(nd[j] - 1) / f32(2)) * voxd for j in range(3)]
-                    q = []
-                    for i in range(3):
-                        s = R[3 * i] * pd[0] + R[3 * i + 1] * pd[1]
-                        s = s + R[3 * i + 2] * pd[2]
-                        s = s + t[i]
-                        q.append(s / voxs + f32(ns[i] - 1) / f32(2))
-                    if any(np.isnan(q[j]) or q[j] < 0 or q[j] + f32(1) >= f32(ns[j]) for j in range(3)):
+                    q, outside = sample_loop(v, nd, voxd, R, t, ns, voxs)
+                    if outside:
                         c["outside"] += 1
                         continue
                     l = [int(q[j]) for j in range(3)]

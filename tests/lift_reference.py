@@ -37,15 +37,6 @@ def _box_voxels(lo, size):
     return x.reshape(-1), y.reshape(-1), z.reshape(-1)
 
 
-def _outside(q, res):
-    with np.errstate(all="ignore"):
-        outside = np.zeros(len(q[0]), bool)
-        for j in range(3):
-            up = q[j] + f32(1)
-            outside |= np.isnan(q[j]) | (q[j] < 0) | (up >= f32(res[j]))
-    return outside
-
-
 # ---- the device stages, vectorised ---------------------------------------------------------------------------------
 
 def seed(dst, src, pose, box=None):
@@ -67,7 +58,7 @@ def seed(dst, src, pose, box=None):
         out["kept"] = int(kept.sum())
         x, y, z = x[~kept], y[~kept], z[~kept]
         q = sample_points((x, y, z), res_d, dst["voxel_size"], R, t, res_s, src["voxel_size"])
-        outside = _outside(q, res_s)
+        outside = ar.outside_of(q, res_s)
         out["outside"] = int(outside.sum())
         keep = ~outside
         x, y, z = x[keep], y[keep], z[keep]
@@ -128,7 +119,7 @@ def release(dst, claim, pose, box=None):
         band = ~empty & ~free
         x, y, z, pt = x[band], y[band], z[band], pt[band]
         q = sample_points((x, y, z), res_d, dst["voxel_size"], R, t, res_c, claim["voxel_size"])
-        outside = _outside(q, res_c)
+        outside = ar.outside_of(q, res_c)
         out["outside"] = int(outside.sum())
         unclaimed = np.zeros(len(x), bool)
         if cb is not None:
@@ -149,27 +140,12 @@ def release(dst, claim, pose, box=None):
 
 # ---- the device stages, voxel by voxel -------------------------------------------------------------------------------
 
-def _sample_loop(v, nd, voxd, R, t, ns, voxs):
-    pd = [(f32(v[j]) - f32(nd[j] - 1) / f32(2)) * voxd for j in range(3)]
-    q = []
-    for i in range(3):
-        s = R[3 * i] * pd[0] + R[3 * i + 1] * pd[1]
-        s = s + R[3 * i + 2] * pd[2]
-        s = s + t[i]
-        q.append(s / voxs + f32(ns[i] - 1) / f32(2))
-    return q, any(np.isnan(q[j]) or q[j] < 0 or q[j] + f32(1) >= f32(ns[j]) for j in range(3))
-
-
 def _record(dtype, names, c, blo, bhi):
     out = np.zeros((), dtype)
     for k in names:
         out[k] = c[k]
     out["lo"], out["hi"] = blo, bhi
     return out
-
-
-def _at(arr, v):
-    return arr[v[2], v[1], v[0]]
 
 
 def seed_loop(dst, src, pose, box=None):
@@ -191,25 +167,25 @@ def seed_loop(dst, src, pose, box=None):
                 for x in range(lo[0], lo[0] + max(size[0], 0)):
                     v = (x, y, z)
                     c["visited"] += 1
-                    if f32(_at(wd, v)) > 0:
+                    if f32(ar.at(wd, v)) > 0:
                         c["kept"] += 1
                         continue
-                    q, outside = _sample_loop(v, nd, voxd, R, t, ns, voxs)
+                    q, outside = ar.sample_loop(v, nd, voxd, R, t, ns, voxs)
                     if outside:
                         c["outside"] += 1
                         continue
                     l = [int(q[j]) for j in range(3)]
                     f = [q[j] - f32(l[j]) for j in range(3)]
                     corners = [(l[0] + dx, l[1] + dy, l[2] + dz) for dz in (0, 1) for dy in (0, 1) for dx in (0, 1)]
-                    vals = [f32(_at(tb, k)) for k in corners]
+                    vals = [f32(ar.at(tb, k)) for k in corners]
                     for j in range(3):  # x pairs, then y, then z
                         vals = [(f32(1) - f[j]) * vals[2 * k] + f[j] * vals[2 * k + 1] for k in range(len(vals) // 2)]
                     s = vals[0]
-                    ws = [f32(_at(wb, k)) for k in corners]
+                    ws = [f32(ar.at(wb, k)) for k in corners]
                     if not all(w > 0 for w in ws) or np.isnan(s):
                         c["unknown"] += 1
                         continue
-                    if fb is not None and _at(fb, [int(np.rint(q[j])) for j in range(3)]) == 0:
+                    if fb is not None and ar.at(fb, [int(np.rint(q[j])) for j in range(3)]) == 0:
                         c["masked"] += 1
                         continue
                     u = s * ratio
@@ -241,18 +217,18 @@ def release_loop(dst, claim, pose, box=None):
                 for x in range(lo[0], lo[0] + max(size[0], 0)):
                     v = (x, y, z)
                     c["visited"] += 1
-                    pw, pt = f32(_at(wd, v)), f32(_at(td, v))
+                    pw, pt = f32(ar.at(wd, v)), f32(ar.at(td, v))
                     if not pw > 0:
                         c["empty"] += 1
                         continue
                     if not abs(pt) < f32(1):
                         c["free_space"] += 1
                         continue
-                    q, outside = _sample_loop(v, nd, voxd, R, t, nc, voxc)
+                    q, outside = ar.sample_loop(v, nd, voxd, R, t, nc, voxc)
                     if outside:
                         c["outside"] += 1
                         continue
-                    if cb is not None and _at(cb, [int(np.rint(q[j])) for j in range(3)]) == 0:
+                    if cb is not None and ar.at(cb, [int(np.rint(q[j])) for j in range(3)]) == 0:
                         c["unclaimed"] += 1
                         continue
                     c["released"] += 1

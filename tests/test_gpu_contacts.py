@@ -13,24 +13,16 @@ import pytest
 from tests import contacts_reference as cr
 from tests import shape_reference as sr
 from tests.parity_util import to_dev
+from tests.resample_util import POISON, lib_for, upload_src
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-POISON = 0xA5
 E_ARG, E_LIMIT = -4, -5  # include/emf_hip.h EMF_E_ARG, EMF_E_LIMIT
 EXTRA = 3  # records of room behind the ones a call writes
 SHAPES = [(1, 1, 1), (5, 3, 2), (33, 17, 9), (64, 8, 8), (40, 24, 20)]
 CONTENTS = ["unobserved", "all_solid", "half_shell", "random", "gated_block"]
 TOUCHES = (-1.0, -0.0, 0.0, 0.25, 1.0, np.inf)
-_libs = {}
-
-
-def lib_for(variant):
-    from emfusion_amd import _lib
-    if variant not in _libs:
-        _libs[variant] = _lib.load() if variant == "" else _lib.load_variant(variant)
-    return _libs[variant]
 
 
 def host_volume(shape, content, masked, voxel):
@@ -44,19 +36,7 @@ def poisoned(n, dtype):
 
 
 def upload(volumes, maps=False):
-    from emfusion_amd import ops
-    from emfusion_amd.devmem import DeviceArray
-    out = []
-    for v in volumes:
-        d = dict(tsdf=to_dev(v["tsdf"]), weights=to_dev(v["weights"]), voxel_size=v["voxel_size"],
-                 fg_mask=None if v["fg"] is None else to_dev(v["fg"]))
-        nz, ny, nx = v["tsdf"].shape
-        if maps and min(nx, ny, nz) >= 2:  # the map's builder takes no thinner volume
-            tiles = DeviceArray((ops.unseen_tile_bytes((nx, ny, nz)),), np.uint8).fill_bytes_(POISON)
-            ops.rebuild_unseen_tiles(d["tsdf"], d["weights"], tiles)
-            d["unseen_tiles"] = tiles
-        out.append(d)
-    return out
+    return [upload_src(v, maps) for v in volumes]
 
 
 def run(volumes, pairs, variants=("", "_fma"), maps=(False,), want=None):
