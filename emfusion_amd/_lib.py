@@ -15,6 +15,7 @@ LIB_PATH = PKG_DIR / "libemf_hip.so"
 HEADER_PATH = REPO_ROOT / "include" / "emf_hip.h"
 
 EMF_OK = 0
+EMF_E_NULL, EMF_E_SHAPE, EMF_E_PITCH, EMF_E_ARG, EMF_E_LIMIT = -1, -2, -3, -4, -5
 
 
 class EmfImage(C.Structure):
@@ -22,6 +23,17 @@ class EmfImage(C.Structure):
 
     _fields_ = [("data", C.c_void_p), ("pitch", C.c_size_t), ("width", C.c_int32),
                 ("height", C.c_int32)]
+
+
+MAX_PEERS = 8  # EMF_MAX_PEERS
+
+
+class EmfPeer(C.Structure):
+    """Mirror of emf_peer_t: what one rank of a direct peer-write exchange group knows about the group."""
+
+    _fields_ = [("rank", C.c_int32), ("world", C.c_int32), ("slots", C.c_void_p * MAX_PEERS),
+                ("flags", C.c_void_p * MAX_PEERS), ("slotBytes", C.c_size_t), ("error", C.c_void_p),
+                ("timeoutMs", C.c_uint32), ("waitInFront", C.c_uint32), ("systemFences", C.c_uint32)]
 
 
 class EmfHipError(RuntimeError):

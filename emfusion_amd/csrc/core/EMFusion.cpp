@@ -61,6 +61,16 @@ EMFusion::EMFusion(const Params& _params, TSDF::Gradients gradients,
       visibleDev(sizeof(int32_t) * EMF_MAX_MODELS),
       integrateStatsDev(sizeof(uint64_t)) {
     if (comm) {
+        // The direct peer-write transport moves whole 16-byte units and its float reduce whole float4s: a session over
+        // it needs width * height % 4 == 0.  Refused HERE, from the replicated frame size alone
+        // -- the same answer on every rank, before the first exchange -- and not by the transport in mid-sequence,
+        // when a 17th association map or a small slot sends a frame down the unfused route.  The host-staged and RCCL
+        // transports take any size.
+        if (comm->peerGroup() && params.frameSize.area() % 4 != 0)
+            throw HipError("EMFusion: a direct peer-write communicator needs width * height % 4 == 0 (its exchanges move "
+                           "whole 16-byte units); " + std::to_string(params.frameSize.width) + " x " +
+                           std::to_string(params.frameSize.height) + " is not: use the host-staged or RCCL transport",
+                           EMF_E_SHAPE);
         rank = comm->rank();
         world = comm->size();
         hitKeys = DeviceBuffer(params.frameSize.area() * sizeof(uint64_t));
@@ -76,6 +86,14 @@ EMFusion::EMFusion(const Params& _params, TSDF::Gradients gradients,
         const emf_peer_t* pg = comm->peerGroup();
         peerFused = pg && sw.peerFused &&
                     pg->slotBytes >= emf_hip_peerRaycastSlotBytes(params.frameSize.width, params.frameSize.height);
+        // Unfused (EMF_PEER_FUSED=0, or slots too small for the fused raycast exchange) the raycast's band gather goes
+        // through the transport's own collectives, whose messages are the bands of the u8 hit mask: the last band has
+        // height % 16 rows, whole 16-byte units only if width * height % 16 == 0.  Refused here for the same reason.
+        if (pg && !peerFused && params.frameSize.area() % 16 != 0)
+            throw HipError("EMFusion: the unfused exchanges of a direct peer-write communicator (EMF_PEER_FUSED=0, or slots "
+                           "smaller than emf_hip_peerRaycastSlotBytes) need width * height % 16 == 0; " +
+                           std::to_string(params.frameSize.width) + " x " + std::to_string(params.frameSize.height) +
+                           " is not: use larger slots or the host-staged or RCCL transport", EMF_E_SHAPE);
     }
     visCountsHost = PinnedBuffer(sizeof(int32_t) * EMF_MAX_MODELS);
     visibleHost = PinnedBuffer(sizeof(int32_t) * EMF_MAX_MODELS);

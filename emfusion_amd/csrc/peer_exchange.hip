@@ -22,7 +22,10 @@
 // s (stream order): nobody is still reading what is overwritten.  Every exchange signals and waits all-to-all,
 // also a broadcast, so that this argument needs no case analysis.
 // Untested on xGMI (no multi-GPU box in the build environment): exercised with one rank, with 2-4 ranks on
-// threads of one process and with 2-3 ranks in separate processes over hipIpc, all sharing one GPU.
+// threads of one process and with 2-3 ranks in separate processes over hipIpc, all sharing one GPU; and kernel by
+// kernel with 1, 2, 3 and 8 EMULATED ranks played in sequence on one stream -- every producer, the flags, every
+// consumer, no kernel waiting for another -- at ragged image sizes, byte for byte, receive buffers and guard regions
+// included (tests/peer_emulation.py, tests/test_gpu_peer_kernels.py).
 #include "peer_core.hpp"
 
 #include <algorithm>

@@ -619,6 +619,105 @@ def visibility_flags_indexed(vis_counts, count_index, thresh, visible, stream=No
                                             _stream(stream)))
 
 
+# ---- direct peer-write exchanges (include/emf_hip.h; `group` is an _lib.EmfPeer) ------------------------
+
+def peer_buffer_bytes(world, slot_bytes) -> int:
+    return int(_L.emf_hip_peerBufferBytes(int(world), int(slot_bytes)))
+
+
+def peer_raycast_slot_bytes(width, height) -> int:
+    return int(_L.emf_hip_peerRaycastSlotBytes(int(width), int(height)))
+
+
+def _at(t, byte_offset=0) -> C.c_void_p:
+    """Device address `byte_offset` bytes into a device array (or a raw address)."""
+    return C.c_void_p((t.ptr if isinstance(t, DeviceArray) else int(t)) + int(byte_offset))
+
+
+def peer_scatter(group, src, nbytes, dst_offset, seq, src_offset=0, stream=None):
+    check("emf_hip_peerScatter",
+          _L.emf_hip_peerScatter(C.byref(group), _at(src, src_offset), int(nbytes), int(dst_offset), int(seq),
+                                 _stream(stream)))
+
+
+def peer_signal_wait(group, seq, timeout_ms=0, stream=None):
+    check("emf_hip_peerSignalWait", _L.emf_hip_peerSignalWait(C.byref(group), int(seq), int(timeout_ms), _stream(stream)))
+
+
+def peer_reduce_sum_f32(group, seq, count, out, wait=False, stream=None):
+    """out := sum over the slots in rank order; wait: the peerWait* form, which signals and waits itself."""
+    name = "emf_hip_peerWaitReduceSumF32" if wait else "emf_hip_peerReduceSumF32"
+    check(name, getattr(_L, name)(C.byref(group), int(seq), int(count), _at(out), _stream(stream)))
+
+
+def peer_reduce_min_u64(group, seq, count, out, wait=False, stream=None):
+    name = "emf_hip_peerWaitReduceMinU64" if wait else "emf_hip_peerReduceMinU64"
+    check(name, getattr(_L, name)(C.byref(group), int(seq), int(count), _at(out), _stream(stream)))
+
+
+def peer_copy_from_slot(group, seq, sender, src_offset, dst, nbytes, dst_offset=0, stream=None):
+    check("emf_hip_peerCopyFromSlot",
+          _L.emf_hip_peerCopyFromSlot(C.byref(group), int(seq), int(sender), int(src_offset), _at(dst, dst_offset),
+                                      int(nbytes), _stream(stream)))
+
+
+def peer_wait_copy_from_slots(group, seq, parts, stream=None):
+    """parts: (sender, slot offset, destination array, destination offset, bytes) each, copied in one launch behind the wait."""
+    n = len(parts)
+    senders = (C.c_int32 * max(n, 1))(*[int(p[0]) for p in parts])
+    offsets = (C.c_size_t * max(n, 1))(*[int(p[1]) for p in parts])
+    dsts = (C.c_void_p * max(n, 1))(*[_at(p[2], p[3]).value for p in parts])
+    sizes = (C.c_size_t * max(n, 1))(*[int(p[4]) for p in parts])
+    check("emf_hip_peerWaitCopyFromSlots",
+          _L.emf_hip_peerWaitCopyFromSlots(C.byref(group), int(seq), n, senders, offsets, dsts, sizes, _stream(stream)))
+
+
+def estep_batched_peer(models_dev, poses_co, points, group, seq, depth=None, K=None, stream=None):
+    """estep_batched(normalize=False) whose per-pixel sum of the object maps goes into this rank's slot on every peer."""
+    check("emf_hip_estepBatchedPeer",
+          _L.emf_hip_estepBatchedPeer(_ptr(models_dev), _poses(poses_co), len(poses_co),
+                                      C.byref(image_view(depth)) if depth is not None else None,
+                                      _f(K, 9) if K is not None else None, C.byref(image_view(points)), C.byref(group),
+                                      int(seq), _stream(stream)))
+
+
+def peer_normalize_association(group, seq, maps, obj_sum=None, norm=None, stream=None):
+    check("emf_hip_peerNormalizeAssociation",
+          _L.emf_hip_peerNormalizeAssociation(C.byref(group), int(seq), _views(maps), len(maps),
+                                              C.byref(image_view(obj_sum)) if obj_sum is not None else None,
+                                              C.byref(image_view(norm)) if norm is not None else None, _stream(stream)))
+
+
+def pack_hit_keys_peer(list_pos, obj_ray, obj_seg, bg_ray, bg_mask, band_row0, band_rows, group, seq, stream=None):
+    n = len(list_pos)
+    pos = (C.c_int32 * max(n, 1))(*[int(p) for p in list_pos])
+    check("emf_hip_packHitKeysPeer",
+          _L.emf_hip_packHitKeysPeer(n, pos, _views(obj_ray), _views(obj_seg), C.byref(image_view(bg_ray)),
+                                     C.byref(image_view(bg_mask)), int(band_row0), int(band_rows), C.byref(group), int(seq),
+                                     _stream(stream)))
+
+
+def composite_from_keys_peer(group, seq, band_rows_per_rank, ids_all, list_pos, obj_ray, obj_vert, obj_norm, bg_ray,
+                             bg_vert, bg_norm, bg_mask, ray, vert, norm, seg, diff, no_obj, boundary, vis_counts,
+                             stream=None):
+    nall, n = len(ids_all), len(list_pos)
+    ids = (C.c_int32 * max(nall, 1))(*[int(i) for i in ids_all])
+    pos = (C.c_int32 * max(n, 1))(*[int(p) for p in list_pos])
+    check("emf_hip_compositeFromKeysPeer",
+          _L.emf_hip_compositeFromKeysPeer(C.byref(group), int(seq), int(band_rows_per_rank), nall, ids, n, pos,
+                                           _views(obj_ray), _views(obj_vert), _views(obj_norm),
+                                           *_frame_refs(bg_ray, bg_vert, bg_norm, bg_mask, ray, vert, norm, seg, diff, no_obj),
+                                           int(boundary), _ptr(vis_counts), _stream(stream)))
+
+
+def visibility_flags_mirror(vis_counts, nall, count_index, thresh, visible, mirror=None, stream=None):
+    n = len(count_index)
+    idx = (C.c_int32 * max(n, 1))(*[int(i) for i in count_index])
+    check("emf_hip_visibilityFlagsMirror",
+          _L.emf_hip_visibilityFlagsMirror(_ptr(vis_counts), int(nall), n, idx, int(thresh), _ptr(visible), _ptr(mirror),
+                                           _stream(stream)))
+
+
 # ---- tracking (SURVEY f-1) ----------------------------------------------------------------------
 
 def compute_pose_gradients(tsdf, grads, points, R_CO, t_CO, voxel_size, out, stream=None):

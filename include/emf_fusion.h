@@ -943,7 +943,10 @@ int emf_comm_create_local_group(int world, emf_comm_t** out);
  *   ..._peer            : one process per rank; the receive buffers are mapped into every peer through
  *                         hipIpc*, the 128 handle bytes per rank travel through `all_gather` (0 = success;
  *                         all[r * bytes ...] := rank r's block), e.g. torch.distributed over gloo.
- * Untested on xGMI (no multi-GPU box in the build environment); exercised on one GPU. */
+ * Untested on xGMI (no multi-GPU box in the build environment); exercised on one GPU.
+ * Image sizes: the transport moves whole 16-byte units, so emf_fusion_create* refuses such a communicator with
+ * EMF_E_SHAPE unless width * height % 4 == 0 (% 16 with slots below emf_hip_peerRaycastSlotBytes, which exchange
+ * unfused) -- on every rank alike, before any exchange.  The other transports take any size. */
 typedef int (*emf_allgather_fn)(void* user, const void* mine, size_t bytes, void* all);
 int emf_comm_create_peer_local_group(int world, size_t slot_bytes, emf_comm_t** out);
 int emf_comm_create_peer(int rank, int world, size_t slot_bytes, emf_allgather_fn all_gather, void* user,

@@ -170,3 +170,22 @@ def test_background_bands_partition_the_rows():
                 assert r0 % 16 == 0 and n >= 0
                 rows += list(range(r0, r0 + n))
             assert rows == list(range(height)), (height, world)
+
+
+def test_background_bands_at_every_height_and_world():
+    """sharding.bg_band for every height 1..200 and world 1..8: the bands are disjoint and cover [0, h) in rank order, every
+    first row is a multiple of 16, and so is every band's length but the last non-empty one's (the fused raycast exchange
+    finds a row's owner as y / rows-per-rank, and the peer transport's band messages are whole 16-row blocks but the last)."""
+    from emfusion_amd import sharding
+    for height in range(1, 201):
+        for world in range(1, 9):
+            bands = [sharding.bg_band(rank, world, height) for rank in range(world)]
+            rows, filled = [], [k for k, (_, n) in enumerate(bands) if n > 0]
+            per_rank = (((height + 15) // 16 + world - 1) // world) * 16  # Communicator.hpp bgBandRows
+            for rank, (r0, n) in enumerate(bands):
+                assert r0 % 16 == 0 and n >= 0, (height, world, rank)
+                assert n % 16 == 0 or rank == filled[-1], (height, world, rank)
+                assert n == 0 or (r0 == rank * per_rank and n <= per_rank), (height, world, rank)
+                rows += list(range(r0, r0 + n))
+            assert rows == list(range(height)), (height, world)  # disjoint, complete, in rank order
+            assert filled == list(range(len(filled))), (height, world)  # empty bands trail

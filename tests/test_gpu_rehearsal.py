@@ -16,9 +16,12 @@ W, H = 160, 120
 NFRAMES, MASK_EVERY = 6, 3
 
 
-def run_job(world, nobj, depth_broadcast, track=False):
+def run_job(world, nobj, depth_broadcast, track=False, size=None, transport="host"):
+    """size: (width, height), by default this module's 160 x 120 (tests/test_gpu_sharded_edges.py: ragged sizes);
+    transport "peer": the direct peer-write communicators with slots that hold the fused raycast exchange."""
     from emfusion_amd import pipeline
     from emfusion_amd.ops import image_view
+    W, H = size or (globals()["W"], globals()["H"])
     prm = pipeline.make_params(W, H, 64, 0.04, 32, visibility_thresh=100, boundary=5, mask_frames=MASK_EVERY)
     K = np.array(prm.K, np.float32)
     synth = pipeline.SyntheticStream(W, H, K, nobj, seed=0xE3F5)
@@ -30,7 +33,12 @@ def run_job(world, nobj, depth_broadcast, track=False):
     spheres = [[synth.sphere(k, f)[0] for f in range(NFRAMES)] for k in range(nobj)]
     first = [synth.sphere(k, 0) for k in range(nobj)]
     synth.close()
-    comms = pipeline.Communicator.local_group(world) if world > 1 else [None]
+    if world == 1:
+        comms = [None]
+    elif transport == "peer":
+        comms = pipeline.Communicator.local_group(world, "peer", W * H * 16)
+    else:
+        comms = pipeline.Communicator.local_group(world)
     out, errors = [None] * world, []
     ready = threading.Barrier(world)  # the ranks enter their first frame together (a bounded wait sits in the peer transport)
 
@@ -54,7 +62,8 @@ def run_job(world, nobj, depth_broadcast, track=False):
                     fus.set_tracking(camera=True, objects=True)  # frame 0 defines the world frame
                 fus.process_frame(image_view(d), R, t, poses, {i: image_view(m) for i, m in masks.items()}, rm)
             fus.synchronize()
-            res = dict(mine=mine, seg=fus.image("segmentation"), ray=fus.image("raylengths"),
+            res = dict(mine=mine, exchanges=comms[r].exchanges() if comms[r] is not None else 0,
+                       seg=fus.image("segmentation"), ray=fus.image("raylengths"),
                        bg_ray=fus.image("bg_raylengths"), bg_assoc=fus.image("bg_assoc"),
                        bg_tsdf=fus.volume("tsdf", 0), bg_w=fus.volume("weights", 0),
                        vis=sorted(fus.visible_objects()), cam=fus.pose(0), poses={i: fus.pose(i) for i in mine},
@@ -82,6 +91,12 @@ def test_sharded_job_on_threads_equals_single_gpu(dev, world, depth_broadcast):
     nobj = 4
     single = run_job(1, nobj, False)[0]
     ranks = run_job(world, nobj, depth_broadcast)
+    check_against_single(ranks, single, nobj, world)
+
+
+def check_against_single(ranks, single, nobj, world):
+    """The ranks' replicas are identical, the joint result equals the single-GPU run within the bounds below, and the scene
+    is not degenerate (also used, with these bounds, at ragged sizes: tests/test_gpu_sharded_edges.py)."""
     assert sorted(i for r in ranks for i in r["mine"]) == list(range(1, nobj + 1))
     assert all(len(r["mine"]) >= 1 for r in ranks[:min(world, nobj)])
     def close(a, b, what):  # the sharded normaliser sums in another order: values move by ulps, and a
