@@ -255,6 +255,14 @@ SIGNATURES = {
                            C.POINTER(C.c_float), _I3, _I3, _FP, _STREAM],
     "emf_hip_releaseVolume": [_FP, _FP, _I3, C.c_float, _FP, _I3, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), _I3,
                               _I3, _FP, _STREAM],
+    # the colour variants: dst_color behind the destination's weights, src_color behind the source, the colour record
+    # behind the record
+    "emf_hip_absorbVolumeColor": [_FP, _FP, _FP, _I3, C.c_float, C.c_float, C.c_float, C.c_void_p, _FP, C.POINTER(C.c_float),
+                                  C.POINTER(C.c_float), _I3, _I3, _FP, _FP, _STREAM],
+    "emf_hip_seedVolumeColor": [_FP, _FP, _FP, _I3, C.c_float, C.c_float, C.c_float, C.c_void_p, _FP, C.POINTER(C.c_float),
+                                C.POINTER(C.c_float), _I3, _I3, _FP, _FP, _STREAM],
+    "emf_hip_releaseVolumeColor": [_FP, _FP, _FP, _I3, C.c_float, _FP, _I3, C.c_float, C.POINTER(C.c_float),
+                                   C.POINTER(C.c_float), _I3, _I3, _FP, _FP, _STREAM],
 }
 
 
@@ -399,6 +407,8 @@ SEED_DTYPE = [("visited", "<u8"), ("kept", "<u8"), ("outside", "<u8"), ("unknown
               ("seeded", "<u8"), ("solid", "<u8"), ("lo", "<i4", 3), ("hi", "<i4", 3)]
 RELEASE_DTYPE = [("visited", "<u8"), ("empty", "<u8"), ("free_space", "<u8"), ("outside", "<u8"), ("unclaimed", "<u8"),
                  ("released", "<u8"), ("solid", "<u8"), ("lo", "<i4", 3), ("hi", "<i4", 3)]
+# include/emf_hip.h "Absorbing a volume": emf_color_moved_t (16 bytes), the second record of the colour entries
+COLOR_MOVED_DTYPE = [("colored", "<u8"), ("uncolored", "<u8")]
 CONTACT_UNSEEN, CONTACT_APART, CONTACT_TOUCHING, CONTACT_PENETRATING = 0, 1, 2, 3
 CONTACT_STATES = ("unseen", "apart", "touching", "penetrating")
 RAY_REACHED, RAY_BLOCKED, RAY_LEFT, RAY_OUTSIDE, RAY_INVALID = 0, 1, 2, 3, 4

@@ -609,6 +609,7 @@ public:
         int32_t lo[3], size[3]; // the box of background voxels the launch covered
         bool clipped = false;   // the object's cube (background voxels, rounded outwards) leaves the background's: lost
         emf_absorb_t record;    // include/emf_hip.h "Absorbing a volume"
+        emf_color_moved_t color{};  // the colour entries that went with the fused voxels; zeros in a colourless session
     };
     /**
      * Absorbing objects into the background (include/emf_hip.h "Absorbing a volume").  Off by default and
@@ -617,7 +618,8 @@ public:
      * background's running average, before it is erased -- so that the distance field, the planner, the ground map,
      * the world mesh, the tile store and a checkpoint keep what the robot mapped a second ago.  Objects deleted as
      * spurious (low existence, association mass below assocThresh) and a person under ignore_person are not absorbed.
-     * IT CARRIES THE BAND ONLY, not the free space around it; colour is not touched; an absorbed object that later moves
+     * IT CARRIES THE BAND ONLY, not the free space around it; in a coloured session (enableColor) the colour entry of every
+     * fused voxel goes with it (emf_hip_absorbVolumeColor); an absorbed object that later moves
      * leaves a ghost until free space carves it; what lies outside the background's cube is clipped and lost.
      * The log (absorbed()) is session state: neither it nor the switch is written to a checkpoint, reset() clears the
      * log.  With the switch off no launch, no output byte and no checkpoint byte changes.  Refused (EMF_E_ARG) on the
@@ -643,6 +645,7 @@ public:
         bool clipped = false;          // the object's cube leaves the background's (as AbsorbEvent::clipped)
         emf_seed_t seed;               // include/emf_hip.h "Lifting a volume"
         emf_release_t release;
+        emf_color_moved_t seedColor{}, releaseColor{};  // the colour entries of the seeded / released voxels; zeros without colour
     };
     /**
      * Lifting objects out of the background (include/emf_hip.h "Lifting a volume"): the other half of
@@ -654,7 +657,8 @@ public:
      * classifies the seeded voxels: under the instance mask they are foreground at once; seeded table or floor inside the
      * cube becomes background and is never raycast.  Several creations of a frame run in list order; the background's
      * derived state is renewed once after the last (absorbFinish), then the model table is rebuilt.
-     * COLOUR IS NOT TOUCHED: seeded voxels have none, released voxels keep their entry.  A voxel behind the object along
+     * In a coloured session (enableColor) the seeded voxels take the background's colour entries and the released voxels'
+     * entries are cleared (emf_hip_seedVolumeColor, emf_hip_releaseVolumeColor).  A voxel behind the object along
      * a mask ray inside the cube is claimed and released too (a hole in the table under a cup).  An object discovered by
      * motion masks sits where the background holds free space: the seed finds nothing, and the ghost at the OLD place
      * is not addressed.  The log (lifted()) is session state: neither it nor the switch is written to a checkpoint,
@@ -1396,7 +1400,7 @@ private:
     bool absorbOn_ = false;          // setAbsorbObjects
     bool absorbDirty_ = false;       // the background's front copy was written and volumesWritten() is still owed
     std::vector<AbsorbEvent> absorbLog_;
-    DeviceBuffer absorbRecord_;      // one emf_absorb_t
+    DeviceBuffer absorbRecord_;      // one emf_absorb_t, then one emf_color_moved_t
     bool expAbsorbed_ = false;       // setAbsorbedOutput
     void absorbInto(ObjTSDF& obj);   // the launch and the log entry, on main; the caller has quiesced
     void absorbFinish();             // volumesWritten once after the last absorption, before rebuildModelTable()
@@ -1417,11 +1421,14 @@ private:
         absorbFinish();
         rebuildModelTable();
     }
-    // a pass's launch on main (its return code), the copy of its record to the host, the wait
+    // a pass's launch on main (its return code), the copy of its record to the host -- and of its colour record, where it
+    // has one -- and the wait
     template <typename Record>
-    void launchedRecord(int rc, const char* what, const Record* dev, Record* host) {
+    void launchedRecord(int rc, const char* what, const Record* dev, Record* host, const emf_color_moved_t* colorDev = nullptr,
+                        emf_color_moved_t* colorHost = nullptr) {
         emfCheck(rc, what);
         hipCheck(hipMemcpyAsync(host, dev, sizeof(Record), hipMemcpyDeviceToHost, main.get()), what);
+        if (colorDev) hipCheck(hipMemcpyAsync(colorHost, colorDev, sizeof(emf_color_moved_t), hipMemcpyDeviceToHost, main.get()), what);
         main.waitForCompletion();
     }
     // the covering box of the object's cube in background voxels and whether the background's cube clips it
@@ -1431,7 +1438,7 @@ private:
     bool liftOn_ = false;            // setLiftObjects
     std::vector<LiftEvent> liftLog_;
     std::vector<LiftEvent> liftPending_;  // seeded in this frame, the release still owed
-    DeviceBuffer liftRecord_;        // one emf_seed_t, then one emf_release_t
+    DeviceBuffer liftRecord_;        // one emf_seed_t, one emf_release_t, then their two emf_color_moved_t
     bool expLifted_ = false;         // setLiftedOutput
     void liftSeed(ObjTSDF& obj, LiftEvent& e);     // the launch on main; the caller has quiesced
     void liftRelease(ObjTSDF& obj, LiftEvent& e);  // the launch on main and the log entry; the caller has quiesced

@@ -3,7 +3,8 @@
 // With the switch on, the band of its signed-distance volume is first resampled through the relative pose into the
 // background's front copy and fused there by the background's running average (emf_hip_absorbVolume, one launch on the
 // main stream), so that every reader of the background keeps it.  It carries the band only, not the free space around
-// it; colour is not touched; what lies outside the background's cube is clipped and lost.
+// it; with colour on the colour entries of the fused voxels go with it (emf_hip_absorbVolumeColor), with
+// colour off the plain entry is called exactly as before; what lies outside the background's cube is clipped and lost.
 // absorbPose is float64 in the fixed operation order of include/emf_hip.h "Object contacts" (the pose of a pair with
 // a = the destination, b = the source) and needs no device.  This unit is compiled with a*b+c contraction off.
 #include "EMFusionDetail.hpp"
@@ -68,12 +69,23 @@ void EMFusion::absorbInto(ObjTSDF& obj) {
     for (int i = 0; i < 3; ++i) s.res[i] = r[i];
     s.voxelSize = obj.getVoxelSize();
     s.truncdist = obj.getTruncDist();
-    absorbRecord_.reserve(sizeof(emf_absorb_t));
+    absorbRecord_.reserve(sizeof(emf_absorb_t) + sizeof(emf_color_moved_t));
     emf_absorb_t* rec = absorbRecord_.as<emf_absorb_t>();
-    launchedRecord(emf_hip_absorbVolume(const_cast<float*>(background.tsdfPtr()), const_cast<float*>(background.weightsPtr()), n.val,
-                                        background.getVoxelSize(), background.getTruncDist(), params.tsdfParams.maxTSDFWeight, &s,
-                                        e.R, e.t, e.lo, e.size, rec, main.abi()),
-                   "EMFusion::absorb", rec, &e.record);
+    if (colorOn) {  // both volumes carry colour since the table that held them was built; a no-op then
+        background.enableColor();
+        obj.enableColor();
+        emf_color_moved_t* crec = reinterpret_cast<emf_color_moved_t*>(rec + 1);
+        launchedRecord(emf_hip_absorbVolumeColor(const_cast<float*>(background.tsdfPtr()), const_cast<float*>(background.weightsPtr()),
+                                                 background.colorPtr(), n.val, background.getVoxelSize(), background.getTruncDist(),
+                                                 params.tsdfParams.maxTSDFWeight, &s, obj.colorPtr(), e.R, e.t, e.lo, e.size, rec, crec,
+                                                 main.abi()),
+                       "EMFusion::absorb (colour)", rec, &e.record, crec, &e.color);
+    } else {
+        launchedRecord(emf_hip_absorbVolume(const_cast<float*>(background.tsdfPtr()), const_cast<float*>(background.weightsPtr()), n.val,
+                                            background.getVoxelSize(), background.getTruncDist(), params.tsdfParams.maxTSDFWeight, &s,
+                                            e.R, e.t, e.lo, e.size, rec, main.abi()),
+                       "EMFusion::absorb", rec, &e.record);
+    }
     absorbDirty_ = true;
     absorbLog_.push_back(e);
 }
@@ -118,13 +130,15 @@ EMFusion::AbsorbEvent EMFusion::absorbObject(int id) {
 }
 
 // absorbed.txt (setAbsorbedOutput): after a comment line one line per event of the log: id frame clipped, the box
-// (lo, size), the eight counts and the bounds of the fused voxels, then R (9) and t (3) in %.9g.
+// (lo, size), the eight counts and the bounds of the fused voxels, then R (9) and t (3) in %.9g; in a coloured session the
+// two colour counts follow and the comment line names them.  A colourless session writes the bytes it always wrote.
 void EMFusion::writeAbsorbed(const std::string& dir) {
     const std::string path = dir + "/absorbed.txt";
     std::FILE* file = std::fopen(path.c_str(), "w");
     if (!file) throw std::runtime_error("EMFusion::writeAbsorbed: cannot create " + path);
     std::fprintf(file, "# id frame clipped box_lo(3) box_size(3) visited outside unknown masked saturated fused fresh solid lo(3) hi(3) "
-                       "R(9) t(3): object frame <- background frame; the band only, not the free space around it\n");
+                       "R(9) t(3): object frame <- background frame; the band only, not the free space around it%s\n",
+                 colorOn ? "; colored uncolored: the colour entries of the fused voxels" : "");
     for (const AbsorbEvent& e : absorbLog_) {
         const emf_absorb_t& r = e.record;
         std::fprintf(file, "%d %d %d", e.id, e.frame, e.clipped ? 1 : 0);
@@ -132,6 +146,7 @@ void EMFusion::writeAbsorbed(const std::string& dir) {
         detail::printCounts(file, {r.visited, r.outside, r.unknown, r.masked, r.saturated, r.fused, r.fresh, r.solid});
         detail::printInts(file, r.lo), detail::printInts(file, r.hi);
         detail::printFloats(file, e.R), detail::printFloats(file, e.t);
+        if (colorOn) detail::printCounts(file, {e.color.colored, e.color.uncolored});
         std::fprintf(file, "\n");
     }
     std::fclose(file);

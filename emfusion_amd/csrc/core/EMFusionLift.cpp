@@ -4,8 +4,10 @@
 // -- and the background keeps that geometry as a second explanation of the same surface.  With the switch on the new
 // object is SEEDED from the background's front copy where it has no observation of its own (emf_hip_seedVolume), the
 // frame's own integrateMask then classifies the seeded voxels by the instance mask, and the background RELEASES the band
-// voxels the object holds as foreground (emf_hip_releaseVolume).  One launch each on the main stream.  Colour is not
-// touched.  The poses are absorbPose (float64 in a fixed order, rounded once): this unit is compiled with a*b+c
+// voxels the object holds as foreground (emf_hip_releaseVolume).  One launch each on the main stream.  With colour on
+// the seeded voxels take the background's colour entries and the released voxels' entries are cleared
+// (emf_hip_seedVolumeColor, emf_hip_releaseVolumeColor); with colour off the plain entries are called
+// exactly as before.  The poses are absorbPose (float64 in a fixed order, rounded once): this unit is compiled with a*b+c
 // contraction off.
 #include "EMFusionDetail.hpp"
 
@@ -13,6 +15,10 @@
 #include <cstdio>
 
 namespace emf {
+
+// liftRecord_: one emf_seed_t, one emf_release_t, then the colour records of the seed and of the release
+static constexpr size_t kLiftRecordBytes = sizeof(emf_seed_t) + sizeof(emf_release_t) + 2 * sizeof(emf_color_moved_t);
+static_assert((sizeof(emf_seed_t) + sizeof(emf_release_t)) % 8 == 0, "the colour records are 8-byte aligned");
 
 void EMFusion::setLiftObjects(bool on) {
     if (on && (sharded || world > 1))
@@ -36,12 +42,22 @@ void EMFusion::liftSeed(ObjTSDF& obj, LiftEvent& e) {
     s.voxelSize = background.getVoxelSize();
     s.truncdist = background.getTruncDist();
     const int32_t lo[3] = {0, 0, 0};
-    liftRecord_.reserve(sizeof(emf_seed_t) + sizeof(emf_release_t));
+    liftRecord_.reserve(kLiftRecordBytes);
     emf_seed_t* rec = liftRecord_.as<emf_seed_t>();
-    launchedRecord(emf_hip_seedVolume(const_cast<float*>(obj.tsdfPtr()), const_cast<float*>(obj.weightsPtr()), r.val, obj.getVoxelSize(),
-                                      obj.getTruncDist(), params.tsdfParams.maxTSDFWeight, &s, e.seedR, e.seedT, lo, r.val, rec,
-                                      main.abi()),
-                   "EMFusion::lift (seed)", rec, &e.seed);
+    if (colorOn) {  // both volumes carry colour since the table that held them was built; a no-op then
+        background.enableColor();
+        obj.enableColor();
+        emf_color_moved_t* crec = reinterpret_cast<emf_color_moved_t*>(liftRecord_.as<char>() + sizeof(emf_seed_t) + sizeof(emf_release_t));
+        launchedRecord(emf_hip_seedVolumeColor(const_cast<float*>(obj.tsdfPtr()), const_cast<float*>(obj.weightsPtr()), obj.colorPtr(),
+                                               r.val, obj.getVoxelSize(), obj.getTruncDist(), params.tsdfParams.maxTSDFWeight, &s,
+                                               background.colorPtr(), e.seedR, e.seedT, lo, r.val, rec, crec, main.abi()),
+                       "EMFusion::lift (seed, colour)", rec, &e.seed, crec, &e.seedColor);
+    } else {
+        launchedRecord(emf_hip_seedVolume(const_cast<float*>(obj.tsdfPtr()), const_cast<float*>(obj.weightsPtr()), r.val,
+                                          obj.getVoxelSize(), obj.getTruncDist(), params.tsdfParams.maxTSDFWeight, &s, e.seedR, e.seedT,
+                                          lo, r.val, rec, main.abi()),
+                       "EMFusion::lift (seed)", rec, &e.seed);
+    }
     obj.volumesWritten(main);  // brick flags, sign maps, gradients, the foreground probabilities
 }
 
@@ -51,12 +67,21 @@ void EMFusion::liftRelease(ObjTSDF& obj, LiftEvent& e) {
     absorbPose(bg.rotation().val, bg.translation().val, op.rotation().val, op.translation().val, e.releaseR, e.releaseT);
     absorbBox(obj, e.releaseR, e.releaseT, e.lo, e.size, e.clipped);
     const Vec3i n = background.getVolumeRes(), r = obj.getVolumeRes();
-    liftRecord_.reserve(sizeof(emf_seed_t) + sizeof(emf_release_t));
+    liftRecord_.reserve(kLiftRecordBytes);
     emf_release_t* rec = reinterpret_cast<emf_release_t*>(liftRecord_.as<char>() + sizeof(emf_seed_t));
-    launchedRecord(emf_hip_releaseVolume(const_cast<float*>(background.tsdfPtr()), const_cast<float*>(background.weightsPtr()), n.val,
-                                         background.getVoxelSize(), obj.fgVolMaskPtr(), r.val, obj.getVoxelSize(), e.releaseR,
-                                         e.releaseT, e.lo, e.size, rec, main.abi()),
-                   "EMFusion::lift (release)", rec, &e.release);
+    if (colorOn) {
+        background.enableColor();
+        emf_color_moved_t* crec = reinterpret_cast<emf_color_moved_t*>(liftRecord_.as<char>() + sizeof(emf_seed_t) + sizeof(emf_release_t)) + 1;
+        launchedRecord(emf_hip_releaseVolumeColor(const_cast<float*>(background.tsdfPtr()), const_cast<float*>(background.weightsPtr()),
+                                                  background.colorPtr(), n.val, background.getVoxelSize(), obj.fgVolMaskPtr(), r.val,
+                                                  obj.getVoxelSize(), e.releaseR, e.releaseT, e.lo, e.size, rec, crec, main.abi()),
+                       "EMFusion::lift (release, colour)", rec, &e.release, crec, &e.releaseColor);
+    } else {
+        launchedRecord(emf_hip_releaseVolume(const_cast<float*>(background.tsdfPtr()), const_cast<float*>(background.weightsPtr()), n.val,
+                                             background.getVoxelSize(), obj.fgVolMaskPtr(), r.val, obj.getVoxelSize(), e.releaseR,
+                                             e.releaseT, e.lo, e.size, rec, main.abi()),
+                       "EMFusion::lift (release)", rec, &e.release);
+    }
     absorbDirty_ = true;  // the background's front copy was written: absorbFinish() renews what is derived from it
     liftLog_.push_back(e);
 }
@@ -106,14 +131,16 @@ EMFusion::LiftEvent EMFusion::liftObject(int id) {
 
 // lifted.txt (setLiftedOutput): after a comment line one line per event of the log: id frame clipped, the release's box
 // (lo, size), the seed's eight counts and bounds, the release's seven counts and bounds, then the seed's R (9) and t (3)
-// and the release's R (9) and t (3) in %.9g.
+// and the release's R (9) and t (3) in %.9g; in a coloured session the colour counts of the seed and of the release follow
+// and the comment line names them.  A colourless session writes the bytes it always wrote.
 void EMFusion::writeLifted(const std::string& dir) {
     const std::string path = dir + "/lifted.txt";
     std::FILE* file = std::fopen(path.c_str(), "w");
     if (!file) throw std::runtime_error("EMFusion::writeLifted: cannot create " + path);
     std::fprintf(file, "# id frame clipped box_lo(3) box_size(3) seed: visited kept outside unknown masked saturated seeded solid lo(3) "
                        "hi(3) release: visited empty free outside unclaimed released solid lo(3) hi(3) seed R(9) t(3): background "
-                       "frame <- object frame; release R(9) t(3): object frame <- background frame\n");
+                       "frame <- object frame; release R(9) t(3): object frame <- background frame%s\n",
+                 colorOn ? "; seed: colored uncolored release: colored uncolored: the colour entries of the seeded / released voxels" : "");
     for (const LiftEvent& e : liftLog_) {
         const emf_seed_t& s = e.seed;
         const emf_release_t& r = e.release;
@@ -125,6 +152,7 @@ void EMFusion::writeLifted(const std::string& dir) {
         detail::printInts(file, r.lo), detail::printInts(file, r.hi);
         detail::printFloats(file, e.seedR), detail::printFloats(file, e.seedT);
         detail::printFloats(file, e.releaseR), detail::printFloats(file, e.releaseT);
+        if (colorOn) detail::printCounts(file, {e.seedColor.colored, e.seedColor.uncolored, e.releaseColor.colored, e.releaseColor.uncolored});
         std::fprintf(file, "\n");
     }
     std::fclose(file);

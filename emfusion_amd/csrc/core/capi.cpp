@@ -1122,6 +1122,20 @@ int emf_fusion_absorbed(emf_fusion_t* h, emf_absorb_event_t* events, int32_t cap
     });
 }
 
+int emf_fusion_absorbed_colors(emf_fusion_t* h, emf_color_moved_t* records, int32_t capacity, int32_t* count) {
+    REQ(h);
+    REQ(count);
+    if (capacity < 0 || (capacity > 0 && !records)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_absorbed_colors: capacity %d without a list", capacity);
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const std::vector<EMFusion::AbsorbEvent>& log = h->impl->absorbed();
+        *count = static_cast<int32_t>(log.size());
+        for (size_t k = 0; k < log.size() && k < static_cast<size_t>(capacity); ++k) records[k] = log[k].color;
+    });
+}
+
 int emf_fusion_set_absorbed_output(emf_fusion_t* h, int on) {
     REQ(h);
     return guarded([&] { h->impl->setAbsorbedOutput(on != 0); });
@@ -1167,6 +1181,21 @@ int emf_fusion_lifted(emf_fusion_t* h, emf_lift_event_t* events, int32_t capacit
         const std::vector<EMFusion::LiftEvent>& log = h->impl->lifted();
         *count = static_cast<int32_t>(log.size());
         for (size_t k = 0; k < log.size() && k < static_cast<size_t>(capacity); ++k) events[k] = liftEvent(log[k]);
+    });
+}
+
+int emf_fusion_lifted_colors(emf_fusion_t* h, emf_color_moved_t* records, int32_t capacity, int32_t* count) {
+    REQ(h);
+    REQ(count);
+    if (capacity < 0 || (capacity > 0 && !records)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_lifted_colors: capacity %d without a list", capacity);
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const std::vector<EMFusion::LiftEvent>& log = h->impl->lifted();
+        *count = static_cast<int32_t>(log.size());
+        for (size_t k = 0; k < log.size() && k < static_cast<size_t>(capacity); ++k)
+            records[2 * k] = log[k].seedColor, records[2 * k + 1] = log[k].releaseColor;
     });
 }
 

@@ -2,12 +2,14 @@
 // (include/emf_hip.h "Object contacts", "Absorbing a volume" and "Lifting a volume"; contacts.hip and
 // volume_transfer.hip).  On the device: the tile walk, the sample point, what the source holds there (rs_source: the
 // pad-1 outside rule, the unseen-tile byte, the corner gathers, the blend, the mask byte at the nearest voxel), and the
-// record epilogue (RsBounds, rs_add64, rs_init_record).  On the host: the argument checks, the kernel arguments and the
-// launch of a pass over a box of the destination.  Every float step is one float32 operation: the _rn intrinsics, and
+// record epilogue (RsBounds, rs_add64, rs_init_record), and for the passes that carry colour with the band the colour
+// entry as one 8-byte word and its exact integer blend (rs_color_*).  On the host: the argument checks, the kernel
+// arguments and the launch of a pass over a box of the destination.  Every float step is one float32 operation: the _rn intrinsics, and
 // every product that feeds a sum goes through mul_rounded / lerp_rounded of wave_ops.hpp, so that a build with
 // -ffp-contract=fast has no product left to fuse.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 
 #include "common.hpp"
@@ -35,6 +37,17 @@ struct ResampleArgs {
     unsigned ntx, nty;         // tiles of the box along x and y
     float voxD, voxS, ratio, maxWeight;
     float R[9], t[3];          // source frame <- destination frame
+};
+
+// What the colour variant of a pass is handed on top: the destination's colour volume (uint16_t[4] per voxel, an entry
+// = one 8-byte word), the source's (or NULL: every source entry is (0, 0, 0, 0); a release has none), the colour
+// record and the weight cap in 8.8 fixed point.  The plain kernels keep ResampleArgs: their arguments do not change.
+template <typename Record>
+struct ResampleColorArgs : ResampleArgs<Record> {
+    uint2* dstColor;
+    const uint2* srcColor;
+    emf_color_moved_t* colorRecord;
+    unsigned capq;
 };
 
 // ---- device --------------------------------------------------------------------------------------------------------
@@ -194,6 +207,32 @@ struct RsBounds {
     }
 };
 
+// ---- colour entries (include/emf_hip.h "Per-voxel colour"): R | G << 16 in .x, B | Wc << 16 in .y, all integer ----
+
+__device__ __forceinline__ unsigned rs_color_weight(const uint2& e) { return e.y >> 16; }
+
+// the source entry at the voxel nearest to an inside q (the addressing of MASKED); without a source colour volume (0, 0, 0, 0)
+__device__ __forceinline__ uint2 rs_color_source(const uint2* __restrict__ color, const V3& q, int ny, size_t by) {
+    return color != nullptr ? color[rs_nearest(q, ny, by)] : make_uint2(0u, 0u);
+}
+
+// (de * dc + sw * sc + (de + sw) / 2) / (de + sw), floor, exact for every u16 input with de + sw > 0.  The two products
+// fit 32 bits each, their sum does not: each is divided on its own and the remainders, below den each, are divided with
+// the half -- three 32-bit divisions by one divisor instead of one 64-bit division.
+__device__ __forceinline__ unsigned rs_color_blend(unsigned de, unsigned dc, unsigned sw, unsigned sc, unsigned den) {
+    const unsigned a = de * dc, b = sw * sc;
+    return a / den + b / den + (a % den + b % den + den / 2u) / den;
+}
+
+// D blended with the COLOURED source entry S under the destination weight de (0 for a FRESH voxel): a copy of Sc then
+__device__ __forceinline__ uint2 rs_color_fuse(const uint2& D, const uint2& S, unsigned de, unsigned capq) {
+    const unsigned sw = rs_color_weight(S), den = de + sw;
+    const unsigned r = rs_color_blend(de, D.x & 0xffffu, sw, S.x & 0xffffu, den);
+    const unsigned g = rs_color_blend(de, D.x >> 16, sw, S.x >> 16, den);
+    const unsigned b = rs_color_blend(de, D.y & 0xffffu, sw, S.y & 0xffffu, den);
+    return make_uint2(r | g << 16, b | min(den, capq) << 16);
+}
+
 // a count of the record: an atomic only where there is something to add
 __device__ __forceinline__ void rs_add64(uint64_t* q, unsigned long long v) {
     if (v) atomicAdd(reinterpret_cast<unsigned long long*>(q), v);
@@ -207,6 +246,17 @@ __global__ void rs_init_record(Record* record, I3 nd) {
     r.lo[0] = nd.x, r.lo[1] = nd.y, r.lo[2] = nd.z;
     r.hi[0] = r.hi[1] = r.hi[2] = -1;
     *record = r;
+}
+
+// one lane: both neutral records before a colour pass
+template <typename Record>
+__global__ void rs_init_records(Record* record, I3 nd, emf_color_moved_t* colorRecord) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    Record r{};
+    r.lo[0] = nd.x, r.lo[1] = nd.y, r.lo[2] = nd.z;
+    r.hi[0] = r.hi[1] = r.hi[2] = -1;
+    *record = r;
+    *colorRecord = emf_color_moved_t{0u, 0u};
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
@@ -331,12 +381,59 @@ inline int rs_check_transfer(const char* who, ResampleArgs<Record>* a, unsigned*
     return EMF_OK;
 }
 
+// The weight cap of a colour pass in 8.8 fixed point, from the destination's maxWeight (finite and > 0).
+inline unsigned rs_color_cap(float max_weight) {
+    if (max_weight * 256.f >= 65535.f) return 65535u;
+    return static_cast<unsigned>(std::max(std::lrintf(max_weight * 256.f), 1l));
+}
+
+// The checks a colour pass adds once its sibling's have passed and `a` holds the resolutions: the destination's colour
+// volume and the colour record are there, 8-byte aligned (the source's colour volume too, where there is one) and share
+// no byte with each other or with any other array of the call.  others / otherBytes: the other party's arrays as the
+// sibling's check saw them (NULL entries skipped).  Fills the colour part of the arguments but the cap.
+template <typename Record>
+inline int rs_check_color(const char* who, ResampleColorArgs<Record>* a, uint16_t* dst_color, const uint16_t* src_color,
+                          emf_color_moved_t* color_record_dev, const void* const* others, const size_t* otherBytes, int nOthers) {
+    if (!dst_color) return fail(EMF_E_ARG, "%s: the destination's colour volume is NULL (the plain entry takes none)", who);
+    if (!color_record_dev) return fail(EMF_E_ARG, "%s: the colour record is NULL", who);
+    if ((reinterpret_cast<uintptr_t>(dst_color) | reinterpret_cast<uintptr_t>(src_color) | reinterpret_cast<uintptr_t>(color_record_dev)) & 7u)
+        return fail(EMF_E_ARG, "%s: a misaligned colour volume or colour record", who);
+    const size_t nDst = static_cast<size_t>(a->nd.x) * a->nd.y * a->nd.z, nSrc = static_cast<size_t>(a->ns.x) * a->ns.y * a->ns.z;
+    // everything else the call names: the destination's two arrays, the record, the other party's arrays, its colour
+    const void* all[8] = {a->dstTsdf, a->dstWeights, a->record, src_color};
+    size_t allBytes[8] = {nDst * sizeof(float), nDst * sizeof(float), sizeof(Record), nSrc * 8u};
+    int n = 4;
+    for (int k = 0; k < nOthers && n < 8; ++k) all[n] = others[k], allBytes[n++] = otherBytes[k];
+    for (int k = 0; k < n; ++k) {
+        if (all[k] == nullptr) continue;
+        if (rs_overlap(dst_color, nDst * 8u, all[k], allBytes[k]))
+            return fail(EMF_E_ARG, "%s: the destination's colour volume overlaps another array of the call", who);
+        if (rs_overlap(color_record_dev, sizeof(emf_color_moved_t), all[k], allBytes[k]))
+            return fail(EMF_E_ARG, "%s: the colour record overlaps another array of the call", who);
+    }
+    if (rs_overlap(color_record_dev, sizeof(emf_color_moved_t), dst_color, nDst * 8u))
+        return fail(EMF_E_ARG, "%s: the colour record overlaps the destination's colour volume", who);
+    a->dstColor = reinterpret_cast<uint2*>(dst_color), a->srcColor = reinterpret_cast<const uint2*>(src_color);
+    a->colorRecord = color_record_dev, a->capq = 0u;
+    return EMF_OK;
+}
+
 // The neutral record, then -- unless the box is empty -- the pass, one workgroup per tile.  Everything that refuses a
 // call has happened before.
 template <typename Record>
 inline int rs_launch(const char* who, void (*pass)(ResampleArgs<Record>), const ResampleArgs<Record>& a, unsigned tiles, emf_stream_t stream) {
     const hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(rs_init_record<Record>, dim3(1), dim3(64), 0, s, a.record, a.nd);
+    if (tiles != 0u) hipLaunchKernelGGL(pass, dim3(tiles), dim3(kRsBlock), 0, s, a);
+    return launch_status(who);
+}
+
+// The same for a colour pass: both neutral records in the one init launch.
+template <typename Record>
+inline int rs_launch(const char* who, void (*pass)(ResampleColorArgs<Record>), const ResampleColorArgs<Record>& a, unsigned tiles,
+                     emf_stream_t stream) {
+    const hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(rs_init_records<Record>, dim3(1), dim3(64), 0, s, a.record, a.nd, a.colorRecord);
     if (tiles != 0u) hipLaunchKernelGGL(pass, dim3(tiles), dim3(kRsBlock), 0, s, a);
     return launch_status(who);
 }

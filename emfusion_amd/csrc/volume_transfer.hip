@@ -13,6 +13,11 @@
 // place.  Only the words whose bits change are stored.  Per wave: wave_reduce of what is not zero anywhere in the wave,
 // then one integer atomic per non-zero quantity from lane 0; the record does not depend on the order of lanes, waves or
 // workgroups.  No float atomics, no LDS, no barrier.  Every float step is one float32 operation (resample.hpp).
+// Each kernel has a COLOUR variant (k_ab_absorb_color, k_lf_seed_color, k_lf_release<true>), the same walk with a template flag resolved at compile
+// time: on the FUSED / SEEDED / RELEASED path alone the voxel's colour entry -- one 8-byte word -- follows the band, from
+// the source's entry at the nearest voxel, in exact integer arithmetic, and two more counts go into a second record.
+#include <type_traits>
+
 #include "resample.hpp"
 
 namespace emf_hip {
@@ -20,20 +25,46 @@ namespace {
 
 static_assert(sizeof(emf_absorb_t) == 88 && sizeof(emf_absorb_source_t) == 56, "mirrored by emfusion_amd/_lib.py");
 static_assert(sizeof(emf_seed_t) == 88 && sizeof(emf_release_t) == 80, "mirrored by emfusion_amd/_lib.py");
+static_assert(sizeof(emf_color_moved_t) == 16 && sizeof(uint2) == 4 * sizeof(uint16_t), "mirrored by emfusion_amd/_lib.py");
+
+// the arguments of a pass: with colour, the colour volumes, the colour record and the cap behind the plain ones
+template <typename Record, bool Color>
+using TransferArgs = std::conditional_t<Color, ResampleColorArgs<Record>, ResampleArgs<Record>>;
+
+// the colour counts of a lane and their way into the colour record; empty without colour
+template <bool Color>
+struct ColorCounts {
+    __device__ __forceinline__ void reduce() {}
+    template <typename Args>
+    __device__ __forceinline__ void commit(const Args&) const {}
+};
+
+template <>
+struct ColorCounts<true> {
+    unsigned cCol = 0u, cUncol = 0u;
+    __device__ __forceinline__ void reduce() { cCol = wave_reduce<OpAdd>(cCol), cUncol = wave_reduce<OpAdd>(cUncol); }
+    template <typename Args>
+    __device__ __forceinline__ void commit(const Args& a) const {
+        rs_add64(&a.colorRecord->colored, cCol), rs_add64(&a.colorRecord->uncolored, cUncol);
+    }
+};
 
 // A policy of rs_transfer holds a lane's counts beyond outside / unknown / masked and says
 //   wants(a, v)       what the destination voxel v decides before anything of the source is read: false = done;
-//   take(a, v, s, w)  what becomes of a VALUE s with the corner weights w: true = the voxel was written and counts for
-//                     the bounds;
+//   take(a, v, q, s, w)  what becomes of a VALUE s at the sample point q with the corner weights w: true = the voxel was
+//                     written and counts for the bounds; with colour, the voxel's colour entry follows here;
 //   reduce(any)       the wave sums of its counts (those of the written voxels only where `any` lane wrote one);
-//   commit(out, any)  lane 0: its counts into the record; returns how many voxels they stand for.
+//   commit(a, any)    lane 0: its counts into the record(s); returns how many voxels they stand for.
 
+template <bool Color>
 struct AbsorbPolicy {
     using Record = emf_absorb_t;
+    using Args = TransferArgs<Record, Color>;
     unsigned cSat = 0u, cFused = 0u, cFresh = 0u, cSolid = 0u;
+    ColorCounts<Color> color;
 
-    __device__ __forceinline__ bool wants(const ResampleArgs<Record>&, size_t) { return true; }
-    __device__ __forceinline__ bool take(const ResampleArgs<Record>& a, size_t v, float s, const float (&w)[8]) {
+    __device__ __forceinline__ bool wants(const Args&, size_t) { return true; }
+    __device__ __forceinline__ bool take(const Args& a, size_t v, const V3& q, float s, const float (&w)[8]) {
         if (!(fabsf(s) < 1.f)) {  // "at least one source truncation away": no value the destination can fuse
             cSat += 1u;
             return false;
@@ -54,30 +85,47 @@ struct AbsorbPolicy {
         if (!(nt > 0.f)) cSolid += 1u;
         if (__float_as_uint(nt) != __float_as_uint(pt)) a.dstTsdf[v] = nt;
         if (__float_as_uint(nw) != __float_as_uint(pw)) a.dstWeights[v] = nw;
+        if constexpr (Color) {
+            const uint2 S = rs_color_source(a.srcColor, q, a.ns.y, static_cast<size_t>(a.ns.x));
+            const bool fresh = !(pw > 0.f);
+            if (rs_color_weight(S) == 0u) {  // UNCOLOURED: an unobserved voxel's entry is not evidence, any other stays
+                color.cUncol += 1u;
+                if (fresh) a.dstColor[v] = make_uint2(0u, 0u);
+            } else {  // COLOURED: the entry is read once, as one word, before anything of it is written
+                color.cCol += 1u;
+                const uint2 D = a.dstColor[v];
+                const uint2 N = rs_color_fuse(D, S, fresh ? 0u : rs_color_weight(D), a.capq);
+                if (N.x != D.x || N.y != D.y) a.dstColor[v] = N;
+            }
+        }
         return true;
     }
     __device__ __forceinline__ void reduce(bool any) {
         cSat = wave_reduce<OpAdd>(cSat);
-        if (any) cFused = wave_reduce<OpAdd>(cFused), cFresh = wave_reduce<OpAdd>(cFresh), cSolid = wave_reduce<OpAdd>(cSolid);
+        if (any) cFused = wave_reduce<OpAdd>(cFused), cFresh = wave_reduce<OpAdd>(cFresh), cSolid = wave_reduce<OpAdd>(cSolid), color.reduce();
     }
-    __device__ __forceinline__ unsigned long long commit(Record* out, bool any) const {
+    __device__ __forceinline__ unsigned long long commit(const Args& a, bool any) const {
+        Record* out = a.record;
         rs_add64(&out->saturated, cSat);
-        if (any) rs_add64(&out->fused, cFused), rs_add64(&out->fresh, cFresh), rs_add64(&out->solid, cSolid);
+        if (any) rs_add64(&out->fused, cFused), rs_add64(&out->fresh, cFresh), rs_add64(&out->solid, cSolid), color.commit(a);
         return static_cast<unsigned long long>(cSat) + (any ? cFused : 0u);
     }
 };
 
+template <bool Color>
 struct SeedPolicy {
     using Record = emf_seed_t;
+    using Args = TransferArgs<Record, Color>;
     unsigned cKept = 0u, cSat = 0u, cSeed = 0u, cSolid = 0u;
     float pw = 0.f;  // the voxel's own weight
+    ColorCounts<Color> color;
 
-    __device__ __forceinline__ bool wants(const ResampleArgs<Record>& a, size_t v) {
+    __device__ __forceinline__ bool wants(const Args& a, size_t v) {
         pw = a.dstWeights[v];
         if (pw > 0.f) cKept += 1u;  // its own observation stands: nothing of the source is read
         return !(pw > 0.f);
     }
-    __device__ __forceinline__ bool take(const ResampleArgs<Record>& a, size_t v, float s, const float (&w)[8]) {
+    __device__ __forceinline__ bool take(const Args& a, size_t v, const V3& q, float s, const float (&w)[8]) {
         const float u = __fmul_rn(s, a.ratio);
         if (!(fabsf(s) < 1.f) || !(fabsf(u) < 1.f)) {  // outside the source's band or the destination's own
             cSat += 1u;
@@ -89,21 +137,33 @@ struct SeedPolicy {
         if (!(u > 0.f)) cSolid += 1u;
         if (__float_as_uint(u) != __float_as_uint(pt)) a.dstTsdf[v] = u;
         if (__float_as_uint(nw) != __float_as_uint(pw)) a.dstWeights[v] = nw;
+        if constexpr (Color) {  // the voxel had no observation: its entry is the source's, capped, or none; not read
+            const uint2 S = rs_color_source(a.srcColor, q, a.ns.y, static_cast<size_t>(a.ns.x));
+            const unsigned sw = rs_color_weight(S);
+            if (sw == 0u) {
+                color.cUncol += 1u;
+                a.dstColor[v] = make_uint2(0u, 0u);
+            } else {
+                color.cCol += 1u;
+                a.dstColor[v] = make_uint2(S.x, (S.y & 0xffffu) | min(sw, a.capq) << 16);
+            }
+        }
         return true;
     }
     __device__ __forceinline__ void reduce(bool any) {
         cKept = wave_reduce<OpAdd>(cKept), cSat = wave_reduce<OpAdd>(cSat);
-        if (any) cSeed = wave_reduce<OpAdd>(cSeed), cSolid = wave_reduce<OpAdd>(cSolid);
+        if (any) cSeed = wave_reduce<OpAdd>(cSeed), cSolid = wave_reduce<OpAdd>(cSolid), color.reduce();
     }
-    __device__ __forceinline__ unsigned long long commit(Record* out, bool any) const {
+    __device__ __forceinline__ unsigned long long commit(const Args& a, bool any) const {
+        Record* out = a.record;
         rs_add64(&out->kept, cKept), rs_add64(&out->saturated, cSat);
-        if (any) rs_add64(&out->seeded, cSeed), rs_add64(&out->solid, cSolid);
+        if (any) rs_add64(&out->seeded, cSeed), rs_add64(&out->solid, cSolid), color.commit(a);
         return static_cast<unsigned long long>(cKept) + cSat + (any ? cSeed : 0u);
     }
 };
 
 template <typename Policy>
-__device__ __forceinline__ void rs_transfer(const ResampleArgs<typename Policy::Record>& a) {
+__device__ __forceinline__ void rs_transfer(const typename Policy::Args& a) {
     const RsLane ln = rs_lane(a.t0, a.ntx, a.nty, a.lo, a.hi);
     const int x = ln.x, y = ln.y;
     if (__ballot(ln.mine) == 0ull) return;  // wave-uniform; the kernel has no barrier
@@ -122,12 +182,13 @@ __device__ __forceinline__ void rs_transfer(const ResampleArgs<typename Policy::
             const size_t v = static_cast<size_t>(z) * dz + static_cast<size_t>(y) * dy + x;
             if (!p.wants(a, v)) continue;
             float s, w[8];
-            switch (rs_source(src, rs_sample(rows, a.R, a.t, rs_pd(z, nd.z, a.voxD), a.voxS, src.half), s, w)) {
+            const V3 q = rs_sample(rows, a.R, a.t, rs_pd(z, nd.z, a.voxD), a.voxS, src.half);
+            switch (rs_source(src, q, s, w)) {
                 case RsClass::Outside: cOut += 1u; break;
                 case RsClass::Unknown: cUnk += 1u; break;
                 case RsClass::Masked: cMask += 1u; break;
                 case RsClass::Value:
-                    if (p.take(a, v, s, w)) written.include(x, y, z);
+                    if (p.take(a, v, q, s, w)) written.include(x, y, z);
             }
         }
     }
@@ -139,18 +200,31 @@ __device__ __forceinline__ void rs_transfer(const ResampleArgs<typename Policy::
     if (any) written.reduce();
     if ((threadIdx.x & 63u) == 0u) {
         typename Policy::Record* out = a.record;
-        rs_add64(&out->visited, static_cast<unsigned long long>(cOut) + cUnk + cMask + p.commit(out, any));
+        rs_add64(&out->visited, static_cast<unsigned long long>(cOut) + cUnk + cMask + p.commit(a, any));
         rs_add64(&out->outside, cOut), rs_add64(&out->unknown, cUnk), rs_add64(&out->masked, cMask);
         if (any) written.commit(out);
     }
 }
 
-__global__ __launch_bounds__(kRsBlock) void k_ab_absorb(const ResampleArgs<emf_absorb_t> a) { rs_transfer<AbsorbPolicy>(a); }
+__global__ __launch_bounds__(kRsBlock) void k_ab_absorb(const ResampleArgs<emf_absorb_t> a) { rs_transfer<AbsorbPolicy<false>>(a); }
 
-__global__ __launch_bounds__(kRsBlock) void k_lf_seed(const ResampleArgs<emf_seed_t> a) { rs_transfer<SeedPolicy>(a); }
+// Left alone the colour variants of the walk come out at 72 and 69 VGPRs, 7 waves per SIMD; held to the plain kernels' 8
+// waves they allocate 60 and 63 like them, without scratch (as k_render_view and k_ct_probe are held).
+__global__ __launch_bounds__(kRsBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_ab_absorb_color(
+    const ResampleColorArgs<emf_absorb_t> a) {
+    rs_transfer<AbsorbPolicy<true>>(a);
+}
+
+__global__ __launch_bounds__(kRsBlock) void k_lf_seed(const ResampleArgs<emf_seed_t> a) { rs_transfer<SeedPolicy<false>>(a); }
+
+__global__ __launch_bounds__(kRsBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_lf_seed_color(
+    const ResampleColorArgs<emf_seed_t> a) {
+    rs_transfer<SeedPolicy<true>>(a);
+}
 
 // the source is the claimant: its mask (or NULL: everything inside its cube), its resolution and voxel size
-__global__ __launch_bounds__(kRsBlock) void k_lf_release(const ResampleArgs<emf_release_t> a) {
+template <bool Color>
+__global__ __launch_bounds__(kRsBlock) void k_lf_release(const TransferArgs<emf_release_t, Color> a) {
     const RsLane ln = rs_lane(a.t0, a.ntx, a.nty, a.lo, a.hi);
     const int x = ln.x, y = ln.y;
     if (__ballot(ln.mine) == 0ull) return;  // wave-uniform; the kernel has no barrier
@@ -161,6 +235,7 @@ __global__ __launch_bounds__(kRsBlock) void k_lf_release(const ResampleArgs<emf_
     const RsRows rows = rs_rows(a.R, rs_pd(x, nd.x, a.voxD), rs_pd(y, nd.y, a.voxD));
 
     unsigned cEmpty = 0u, cFree = 0u, cOut = 0u, cUncl = 0u, cRel = 0u, cSolid = 0u;
+    ColorCounts<Color> color;
     RsBounds released(nd);
 
     if (ln.mine) {
@@ -190,6 +265,15 @@ __global__ __launch_bounds__(kRsBlock) void k_lf_release(const ResampleArgs<emf_
             // what TSDF::reset leaves in an unseen voxel; pw > 0, so its word always changes
             if (__float_as_uint(pt) != 0u) a.dstTsdf[v] = 0.f;
             a.dstWeights[v] = 0.f;
+            if constexpr (Color) {  // and no colour: COLOURED counts the entries that held something
+                const uint2 D = a.dstColor[v];
+                if ((D.x | D.y) != 0u) {
+                    color.cCol += 1u;
+                    a.dstColor[v] = make_uint2(0u, 0u);
+                } else {
+                    color.cUncol += 1u;
+                }
+            }
         }
     }
 
@@ -198,6 +282,7 @@ __global__ __launch_bounds__(kRsBlock) void k_lf_release(const ResampleArgs<emf_
     const bool any = released.any();
     if (any) {
         cRel = wave_reduce<OpAdd>(cRel), cSolid = wave_reduce<OpAdd>(cSolid);
+        color.reduce();
         released.reduce();
     }
     if ((threadIdx.x & 63u) == 0u) {
@@ -206,9 +291,46 @@ __global__ __launch_bounds__(kRsBlock) void k_lf_release(const ResampleArgs<emf_
         rs_add64(&out->empty, cEmpty), rs_add64(&out->free_space, cFree), rs_add64(&out->outside, cOut), rs_add64(&out->unclaimed, cUncl);
         if (any) {
             rs_add64(&out->released, cRel), rs_add64(&out->solid, cSolid);
+            color.commit(a);
             released.commit(out);
         }
     }
+}
+
+
+// absorbVolumeColor and seedVolumeColor: every check of the sibling, then those of the colour arguments, then the launch
+template <typename Record>
+int transfer_color(const char* who, void (*pass)(ResampleColorArgs<Record>), float* dst_tsdf, float* dst_weights, uint16_t* dst_color,
+                   const int32_t* dst_res, float dst_voxel_size, float dst_truncdist, float max_weight, const emf_absorb_source_t* source,
+                   const uint16_t* src_color, const float* R, const float* t, const int32_t* box_lo, const int32_t* box_size,
+                   Record* record_dev, emf_color_moved_t* color_record_dev, emf_stream_t stream) {
+    ResampleColorArgs<Record> a{};
+    unsigned tiles = 0;
+    EMF_TRY(rs_check_transfer(who, static_cast<ResampleArgs<Record>*>(&a), &tiles, dst_tsdf, dst_weights, dst_res, dst_voxel_size,
+                              dst_truncdist, max_weight, source, R, t, box_lo, box_size, record_dev));
+    const size_t nSrc = static_cast<size_t>(a.ns.x) * a.ns.y * a.ns.z;
+    const void* others[4] = {source->tsdf, source->weights, source->fgVolMask, source->unseenTiles};
+    const size_t otherBytes[4] = {nSrc * sizeof(float), nSrc * sizeof(float), nSrc, emf_hip_unseenTileBytes(source->res)};
+    EMF_TRY(rs_check_color(who, &a, dst_color, src_color, color_record_dev, others, otherBytes, 4));
+    a.capq = rs_color_cap(max_weight);
+    return rs_launch(who, pass, a, tiles, stream);
+}
+
+// every check of the release but those of the colour arguments; fills the arguments
+int check_release(const char* who, ResampleArgs<emf_release_t>* a, unsigned* tiles, float* dst_tsdf, float* dst_weights,
+                  const int32_t* dst_res, float dst_voxel_size, const uint8_t* claim_mask, const int32_t* claim_res, float claim_voxel_size,
+                  const float* R, const float* t, const int32_t* box_lo, const int32_t* box_size, emf_release_t* record_dev) {
+    EMF_TRY(rs_check_destination(who, dst_tsdf, dst_weights, dst_res, R, t, box_lo, box_size, record_dev));
+    if (!claim_res) return fail(EMF_E_ARG, "%s: the claimant's resolution is NULL", who);
+    unsigned long long nDst = 0, nClaim = 0;
+    EMF_TRY(rs_check_volume(who, dst_res, "destination", &nDst));
+    EMF_TRY(rs_check_volume(who, claim_res, "claimant", &nClaim));
+    const void* others[1] = {claim_mask};
+    const size_t otherBytes[1] = {static_cast<size_t>(nClaim)};
+    EMF_TRY(rs_check_layout(who, a, tiles, dst_tsdf, dst_weights, dst_res, nDst, dst_voxel_size, "claimant's mask", claim_res,
+                            claim_voxel_size, others, otherBytes, 1, R, t, box_lo, box_size, record_dev));
+    a->srcMask = claim_mask;
+    return EMF_OK;
 }
 
 }  // namespace
@@ -228,6 +350,14 @@ int emf_hip_absorbVolume(float* dst_tsdf, float* dst_weights, const int32_t dst_
     return rs_launch("absorbVolume", k_ab_absorb, a, tiles, stream);
 }
 
+int emf_hip_absorbVolumeColor(float* dst_tsdf, float* dst_weights, uint16_t* dst_color, const int32_t dst_res[3], float dst_voxel_size,
+                              float dst_truncdist, float max_weight, const emf_absorb_source_t* source, const uint16_t* src_color,
+                              const float R[9], const float t[3], const int32_t box_lo[3], const int32_t box_size[3],
+                              emf_absorb_t* record_dev, emf_color_moved_t* color_record_dev, emf_stream_t stream) {
+    return transfer_color("absorbVolumeColor", k_ab_absorb_color, dst_tsdf, dst_weights, dst_color, dst_res, dst_voxel_size, dst_truncdist,
+                          max_weight, source, src_color, R, t, box_lo, box_size, record_dev, color_record_dev, stream);
+}
+
 int emf_hip_seedVolume(float* dst_tsdf, float* dst_weights, const int32_t dst_res[3], float dst_voxel_size, float dst_truncdist,
                        float max_weight, const emf_absorb_source_t* source, const float R[9], const float t[3],
                        const int32_t box_lo[3], const int32_t box_size[3], emf_seed_t* record_dev, emf_stream_t stream) {
@@ -238,23 +368,37 @@ int emf_hip_seedVolume(float* dst_tsdf, float* dst_weights, const int32_t dst_re
     return rs_launch("seedVolume", k_lf_seed, a, tiles, stream);
 }
 
+int emf_hip_seedVolumeColor(float* dst_tsdf, float* dst_weights, uint16_t* dst_color, const int32_t dst_res[3], float dst_voxel_size,
+                            float dst_truncdist, float max_weight, const emf_absorb_source_t* source, const uint16_t* src_color,
+                            const float R[9], const float t[3], const int32_t box_lo[3], const int32_t box_size[3],
+                            emf_seed_t* record_dev, emf_color_moved_t* color_record_dev, emf_stream_t stream) {
+    return transfer_color("seedVolumeColor", k_lf_seed_color, dst_tsdf, dst_weights, dst_color, dst_res, dst_voxel_size, dst_truncdist,
+                          max_weight, source, src_color, R, t, box_lo, box_size, record_dev, color_record_dev, stream);
+}
+
 int emf_hip_releaseVolume(float* dst_tsdf, float* dst_weights, const int32_t dst_res[3], float dst_voxel_size,
                           const uint8_t* claim_mask, const int32_t claim_res[3], float claim_voxel_size, const float R[9],
                           const float t[3], const int32_t box_lo[3], const int32_t box_size[3], emf_release_t* record_dev,
                           emf_stream_t stream) {
-    EMF_TRY(rs_check_destination("releaseVolume", dst_tsdf, dst_weights, dst_res, R, t, box_lo, box_size, record_dev));
-    if (!claim_res) return fail(EMF_E_ARG, "releaseVolume: the claimant's resolution is NULL");
-    unsigned long long nDst = 0, nClaim = 0;
-    EMF_TRY(rs_check_volume("releaseVolume", dst_res, "destination", &nDst));
-    EMF_TRY(rs_check_volume("releaseVolume", claim_res, "claimant", &nClaim));
     ResampleArgs<emf_release_t> a{};
     unsigned tiles = 0;
+    EMF_TRY(check_release("releaseVolume", &a, &tiles, dst_tsdf, dst_weights, dst_res, dst_voxel_size, claim_mask, claim_res,
+                          claim_voxel_size, R, t, box_lo, box_size, record_dev));
+    return rs_launch("releaseVolume", k_lf_release<false>, a, tiles, stream);
+}
+
+int emf_hip_releaseVolumeColor(float* dst_tsdf, float* dst_weights, uint16_t* dst_color, const int32_t dst_res[3], float dst_voxel_size,
+                               const uint8_t* claim_mask, const int32_t claim_res[3], float claim_voxel_size, const float R[9],
+                               const float t[3], const int32_t box_lo[3], const int32_t box_size[3], emf_release_t* record_dev,
+                               emf_color_moved_t* color_record_dev, emf_stream_t stream) {
+    ResampleColorArgs<emf_release_t> a{};
+    unsigned tiles = 0;
+    EMF_TRY(check_release("releaseVolumeColor", &a, &tiles, dst_tsdf, dst_weights, dst_res, dst_voxel_size, claim_mask, claim_res,
+                          claim_voxel_size, R, t, box_lo, box_size, record_dev));
     const void* others[1] = {claim_mask};
-    const size_t otherBytes[1] = {static_cast<size_t>(nClaim)};
-    EMF_TRY(rs_check_layout("releaseVolume", &a, &tiles, dst_tsdf, dst_weights, dst_res, nDst, dst_voxel_size, "claimant's mask", claim_res,
-                            claim_voxel_size, others, otherBytes, 1, R, t, box_lo, box_size, record_dev));
-    a.srcMask = claim_mask;
-    return rs_launch("releaseVolume", k_lf_release, a, tiles, stream);
+    const size_t otherBytes[1] = {static_cast<size_t>(a.ns.x) * a.ns.y * a.ns.z};
+    EMF_TRY(rs_check_color("releaseVolumeColor", &a, dst_color, nullptr, color_record_dev, others, otherBytes, 1));
+    return rs_launch("releaseVolumeColor", k_lf_release<true>, a, tiles, stream);
 }
 
 }  // extern "C"

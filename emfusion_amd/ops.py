@@ -2174,7 +2174,8 @@ def contact_probe(volumes, pairs, out=None, stream=None, lib=None):
 # ---- absorbing a volume (include/emf_hip.h "Absorbing a volume") -----------------------------------
 
 ABSORB_DTYPE = np.dtype(_lib.ABSORB_DTYPE)
-assert ABSORB_DTYPE.itemsize == 88 and C.sizeof(_lib.EmfAbsorbSource) == 56
+COLOR_MOVED_DTYPE = np.dtype(_lib.COLOR_MOVED_DTYPE)
+assert ABSORB_DTYPE.itemsize == 88 and C.sizeof(_lib.EmfAbsorbSource) == 56 and COLOR_MOVED_DTYPE.itemsize == 16
 
 
 def absorb_box(dst_res, dst_voxel_size, src_res, src_voxel_size, pose):
@@ -2203,8 +2204,30 @@ def _transfer_call(dst, other_res, other_voxel_size, pose, box, out, dtype):
     return (_ptr(tsdf), _ptr(weights), _i3(res), float(np.float32(dst["voxel_size"]))), (_i3(lo), _i3(size)), record
 
 
-def _transfer_volume(entry, dtype, dst, src, pose, box, out, lib, stream):
-    """absorb_volume and seed_volume: emf_hip_<entry> of a whole source into dst."""
+def _transfer_color(dst, color_out):
+    """The colour arguments of a pass into a destination with a colour volume (dst["color"], (Nz, Ny, Nx, 4) u16): its
+    pointer and the colour record array; (None, None) for a destination without one -- the plain entry."""
+    if dst.get("color") is None:
+        assert color_out is None, "a colour record without a colour volume"
+        return None, None
+    color = _vol(dst["color"], np.uint16, 4)
+    assert color.shape[:3] == dst["tsdf"].shape
+    crec = DeviceArray((1,), COLOR_MOVED_DTYPE) if color_out is None else color_out
+    assert crec.dtype == COLOR_MOVED_DTYPE and crec.shape[0] >= 1
+    return color, crec
+
+
+def _transfer_result(record, out, crec, color_out):
+    """The record of a plain pass; (record, colour record) of a colour pass; numpy records, or the arrays given."""
+    rec = record.numpy()[0] if out is None else out
+    if crec is None:
+        return rec
+    return rec, (crec.numpy()[0] if color_out is None else color_out)
+
+
+def _transfer_volume(entry, dtype, dst, src, pose, box, out, lib, stream, color_out=None):
+    """absorb_volume and seed_volume: emf_hip_<entry> of a whole source into dst; emf_hip_<entry>Color where dst has a
+    colour volume."""
     stsdf, sweights = _vol(src["tsdf"], np.float32), _vol(src["weights"], np.float32)
     assert sweights.shape == stsdf.shape
     s = _lib.EmfAbsorbSource()
@@ -2217,14 +2240,24 @@ def _transfer_volume(entry, dtype, dst, src, pose, box, out, lib, stream):
     s.res = _i3((stsdf.shape[2], stsdf.shape[1], stsdf.shape[0]))
     s.voxelSize, s.truncdist = float(np.float32(src["voxel_size"])), float(np.float32(src["truncdist"]))
     d, b, record = _transfer_call(dst, tuple(s.res), src["voxel_size"], pose, box, out, dtype)
-    check("emf_hip_" + entry,
-          getattr(_L if lib is None else lib, "emf_hip_" + entry)(
-              *d, float(np.float32(dst["truncdist"])), float(np.float32(dst["max_weight"])), C.byref(s), _f(pose[0], 9),
-              _f(pose[1], 3), *b, _ptr(record), _stream(stream)))
-    return record.numpy()[0] if out is None else out
+    color, crec = _transfer_color(dst, color_out)
+    if color is None:
+        check("emf_hip_" + entry,
+              getattr(_L if lib is None else lib, "emf_hip_" + entry)(
+                  *d, float(np.float32(dst["truncdist"])), float(np.float32(dst["max_weight"])), C.byref(s), _f(pose[0], 9),
+                  _f(pose[1], 3), *b, _ptr(record), _stream(stream)))
+    else:
+        scolor = src.get("color")
+        if scolor is not None:
+            assert _vol(scolor, np.uint16, 4).shape[:3] == stsdf.shape
+        check("emf_hip_" + entry + "Color",
+              getattr(_L if lib is None else lib, "emf_hip_" + entry + "Color")(
+                  d[0], d[1], _ptr(color), d[2], d[3], float(np.float32(dst["truncdist"])), float(np.float32(dst["max_weight"])),
+                  C.byref(s), _ptr(scolor), _f(pose[0], 9), _f(pose[1], 3), *b, _ptr(record), _ptr(crec), _stream(stream)))
+    return _transfer_result(record, out, crec, color_out)
 
 
-def absorb_volume(dst, src, pose, box=None, out=None, lib=None, stream=None):
+def absorb_volume(dst, src, pose, box=None, out=None, lib=None, stream=None, color_out=None):
     """emf_hip_absorbVolume: the signed-distance band of `src` resampled through pose = (R, t) (f32, source frame <-
     destination frame) into `dst` and fused there, in place, by dst's running average.
     dst: dict(tsdf=, weights=, voxel_size=, truncdist=, max_weight=), (Nz, Ny, Nx) f32 device arrays of any shape from
@@ -2233,8 +2266,13 @@ def absorb_volume(dst, src, pose, box=None, out=None, lib=None, stream=None):
     Returns the record (a 0-d numpy array of ABSORB_DTYPE: visited = outside + unknown + masked + saturated + fused;
     fresh, solid; lo, hi of the fused voxels), or with out= (a device array of at least one record) that array.
     IT CARRIES THE BAND, NOT THE FREE SPACE AROUND IT: saturated source samples are left alone.  lib: another build of
-    the kernel library (_lib.load_variant)."""
-    return _transfer_volume("absorbVolume", ABSORB_DTYPE, dst, src, pose, box, out, lib, stream)
+    the kernel library (_lib.load_variant).
+    COLOUR: with dst["color"] (an (Nz, Ny, Nx, 4) u16 device colour volume) the call is
+    emf_hip_absorbVolumeColor -- the same tsdf, weights and record, and the colour entry of every fused voxel blended
+    with the entry of src["color"] (or None: no source colour) at the nearest source voxel -- and returns the pair
+    (record, colour record), the second of COLOR_MOVED_DTYPE (colored + uncolored == fused), or with color_out= (a device
+    array of at least one such record) that array in its place.  Without dst["color"] the call is what it was."""
+    return _transfer_volume("absorbVolume", ABSORB_DTYPE, dst, src, pose, box, out, lib, stream, color_out)
 
 
 # ---- lifting a volume (include/emf_hip.h "Lifting a volume", DESIGN.md 5.30) ---------------------------------------
@@ -2244,22 +2282,26 @@ RELEASE_DTYPE = np.dtype(_lib.RELEASE_DTYPE)
 assert SEED_DTYPE.itemsize == 88 and RELEASE_DTYPE.itemsize == 80
 
 
-def seed_volume(dst, src, pose, box=None, out=None, lib=None, stream=None):
+def seed_volume(dst, src, pose, box=None, out=None, lib=None, stream=None, color_out=None):
     """emf_hip_seedVolume: `dst` takes the signed-distance band of `src`, resampled through pose = (R, t) (f32, source
     frame <- destination frame), ONLY WHERE IT HAS NO OBSERVATION OF ITS OWN (weights not > 0), in place, and only values
     inside its own band: no clamped +-1 is written.  dst, src, box and out as in absorb_volume (box None: the covering
     box of the whole source).  Returns the record (a 0-d numpy array of SEED_DTYPE: visited = kept + outside + unknown +
-    masked + saturated + seeded; solid; lo, hi of the seeded voxels), or with out= that array."""
-    return _transfer_volume("seedVolume", SEED_DTYPE, dst, src, pose, box, out, lib, stream)
+    masked + saturated + seeded; solid; lo, hi of the seeded voxels), or with out= that array.
+    With dst["color"]: emf_hip_seedVolumeColor -- every seeded voxel takes the entry of src["color"] (or None) at the
+    nearest source voxel, its weight capped, or (0, 0, 0, 0) -- and the pair (record, colour record) as absorb_volume."""
+    return _transfer_volume("seedVolume", SEED_DTYPE, dst, src, pose, box, out, lib, stream, color_out)
 
 
-def release_volume(dst, claim, pose, box=None, out=None, lib=None, stream=None):
+def release_volume(dst, claim, pose, box=None, out=None, lib=None, stream=None, color_out=None):
     """emf_hip_releaseVolume: `dst` gives up, in place, the band voxels (weights > 0, |tsdf| < 1) that the claimant holds:
     tsdf and weights become +0.0.  dst: dict(tsdf=, weights=, voxel_size=); claim: dict(fg_mask=, voxel_size=) with a
     (Nz, Ny, Nx) u8 device volume, or dict(fg_mask=None, res=(nx, ny, nz), voxel_size=): everything inside the
     claimant's cube; pose = (R, t), claimant frame <- destination frame.  box: (lo, size) in destination voxels, None: the
     covering box of the claimant's cube (absorb_box).  Returns the record (RELEASE_DTYPE: visited = empty + free_space +
-    outside + unclaimed + released; solid; lo, hi of the released voxels), or with out= that array."""
+    outside + unclaimed + released; solid; lo, hi of the released voxels), or with out= that array.
+    With dst["color"]: emf_hip_releaseVolumeColor -- the colour entry of every released voxel becomes (0, 0, 0, 0) -- and
+    the pair (record, colour record) as absorb_volume (colored: the entries that held something)."""
     L = _L if lib is None else lib
     mask = claim.get("fg_mask")
     if mask is not None:
@@ -2269,10 +2311,17 @@ def release_volume(dst, claim, pose, box=None, out=None, lib=None, stream=None):
     else:
         cres = tuple(int(v) for v in claim["res"])
     d, b, record = _transfer_call(dst, cres, claim["voxel_size"], pose, box, out, RELEASE_DTYPE)
-    check("emf_hip_releaseVolume",
-          L.emf_hip_releaseVolume(*d, _ptr(mask), _i3(cres), float(np.float32(claim["voxel_size"])), _f(pose[0], 9),
-                                  _f(pose[1], 3), *b, _ptr(record), _stream(stream)))
-    return record.numpy()[0] if out is None else out
+    color, crec = _transfer_color(dst, color_out)
+    if color is None:
+        check("emf_hip_releaseVolume",
+              L.emf_hip_releaseVolume(*d, _ptr(mask), _i3(cres), float(np.float32(claim["voxel_size"])), _f(pose[0], 9),
+                                      _f(pose[1], 3), *b, _ptr(record), _stream(stream)))
+    else:
+        check("emf_hip_releaseVolumeColor",
+              L.emf_hip_releaseVolumeColor(d[0], d[1], _ptr(color), d[2], d[3], _ptr(mask), _i3(cres),
+                                           float(np.float32(claim["voxel_size"])), _f(pose[0], 9), _f(pose[1], 3), *b, _ptr(record),
+                                           _ptr(crec), _stream(stream)))
+    return _transfer_result(record, out, crec, color_out)
 
 
 # ---- ground map (include/emf_hip.h "Ground map") -------------------------------------------------

@@ -190,10 +190,12 @@ def load() -> C.CDLL:
         "emf_fusion_set_absorb_objects": [vp, C.c_int],
         "emf_fusion_absorb_object": [vp, C.c_int32, C.c_void_p],
         "emf_fusion_absorbed": [vp, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
+        "emf_fusion_absorbed_colors": [vp, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
         "emf_fusion_set_absorbed_output": [vp, C.c_int],
         "emf_fusion_set_lift_objects": [vp, C.c_int],
         "emf_fusion_lift_object": [vp, C.c_int32, C.c_void_p],
         "emf_fusion_lifted": [vp, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
+        "emf_fusion_lifted_colors": [vp, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
         "emf_fusion_set_lifted_output": [vp, C.c_int],
         "emf_fusion_planes": [vp, ip, ip, C.c_void_p, ip, ip, fp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                               C.POINTER(C.c_int32)],
@@ -686,8 +688,16 @@ def absorb_pose(pose_bg, pose_obj):
     return R.reshape(3, 3), t
 
 
-def absorbed_line(event):
-    """One line of absorbed.txt (without the newline) from an event of Fusion.absorbed()."""
+def _color_fields(records):
+    """The trailing fields of a line of a coloured session: colored and uncolored of each colour record."""
+    return "".join(" %d %d" % (int(c["colored"]), int(c["uncolored"])) for c in records)
+
+
+def absorbed_line(event, color=None):
+    """One line of absorbed.txt (without the newline) from an event of Fusion.absorbed().  color: the event's record of
+    Fusion.absorbed_colors() in a coloured session -- its two counts follow as trailing fields -- or None."""
+    if color is not None:
+        return absorbed_line(event) + _color_fields([color])
     r = event["record"]
     ints = [event["id"], event["frame"], int(event["clipped"]), *event["lo"], *event["size"]] + \
         [int(r[k]) for k in ("visited", "outside", "unknown", "masked", "saturated", "fused", "fresh", "solid")] + \
@@ -706,8 +716,11 @@ def _lift_event_dtype():
     return d
 
 
-def lifted_line(event):
-    """One line of lifted.txt (without the newline) from an event of Fusion.lifted()."""
+def lifted_line(event, color=None):
+    """One line of lifted.txt (without the newline) from an event of Fusion.lifted().  color: the event's pair (seed,
+    release) of Fusion.lifted_colors() in a coloured session -- four trailing fields -- or None."""
+    if color is not None:
+        return lifted_line(event) + _color_fields(color)
     s, r = event["seed"], event["release"]
     ints = [event["id"], event["frame"], int(event["clipped"]), *event["lo"], *event["size"]] + \
         [int(s[k]) for k in ("visited", "kept", "outside", "unknown", "masked", "saturated", "seeded", "solid")] + \
@@ -1977,7 +1990,8 @@ class Fusion:
         mass below assocThresh) and a person under set_ignore_person are not absorbed.
 
         WHAT IT DOES NOT DO: it carries the band, not the free space around it (saturated samples are left alone);
-        colour is not touched; an absorbed object that later moves leaves a ghost until free space carves it; what lies
+        in a coloured session (enable_color) the colour entries of the fused voxels go with it and absorbed_colors() counts
+        them, in a colourless one no call changes; an absorbed object that later moves leaves a ghost until free space carves it; what lies
         outside the background's cube is clipped and lost; objects are not merged with each other and none is seeded
         from the background.  Neither the switch nor the log (absorbed()) is written to a checkpoint: no checkpoint byte
         changes.  Off: no launch and no output byte changes.  Refused on the sharded path."""
@@ -2003,6 +2017,17 @@ class Fusion:
         _check("emf_fusion_absorbed", load().emf_fusion_absorbed(self._h, events.ctypes.data, n.value, C.byref(n)))
         return [self._absorb_event(events[k]) for k in range(n.value)]
 
+    def absorbed_colors(self):
+        """The colour records of absorbed(), one per event in its order (numpy records of ops.COLOR_MOVED_DTYPE: colored +
+        uncolored == the event's fused voxels): how many colour entries went into the background with the band
+        (DESIGN.md 5.31).  Zeros for the events of a colourless session.  Session state like the log."""
+        from . import _lib as hip
+        n = C.c_int32(0)
+        _check("emf_fusion_absorbed_colors", load().emf_fusion_absorbed_colors(self._h, None, 0, C.byref(n)))
+        records = np.zeros(max(n.value, 1), np.dtype(hip.COLOR_MOVED_DTYPE))
+        _check("emf_fusion_absorbed_colors", load().emf_fusion_absorbed_colors(self._h, records.ctypes.data, n.value, C.byref(n)))
+        return [records[k].copy() for k in range(n.value)]
+
     @staticmethod
     def _lift_event(e):
         return dict(id=int(e["id"]), frame=int(e["frame"]), clipped=bool(e["clipped"]), seed_R=e["seed_R"].reshape(3, 3).copy(),
@@ -2019,7 +2044,8 @@ class Fusion:
         frame's own mask classifies the seeded voxels: under it they are foreground at once; seeded table or floor inside
         the cube becomes background and is never raycast.
 
-        WHAT IT DOES NOT DO: colour is not touched (seeded voxels have none, released voxels keep their entry); a voxel
+        In a coloured session (enable_color) the seeded voxels take the background's colour entries, the released voxels'
+        entries are cleared and lifted_colors() counts both.  WHAT IT DOES NOT DO: a voxel
         behind the object along a mask ray inside the cube is claimed and released too (a hole in the table under a cup);
         an object discovered by motion masks sits where the background holds free space: the seed finds nothing there
         and the ghost at the OLD place is not addressed.  Neither the switch nor the log (lifted()) is written to a
@@ -2046,6 +2072,17 @@ class Fusion:
         events = np.zeros(max(n.value, 1), _lift_event_dtype())
         _check("emf_fusion_lifted", load().emf_fusion_lifted(self._h, events.ctypes.data, n.value, C.byref(n)))
         return [self._lift_event(events[k]) for k in range(n.value)]
+
+    def lifted_colors(self):
+        """The colour records of lifted(), one pair (seed, release) per event in its order (numpy records of
+        ops.COLOR_MOVED_DTYPE: colored + uncolored == the seeded / the released voxels): the colour entries the new object
+        took from the background and those the background gave up.  Zeros for a colourless session."""
+        from . import _lib as hip
+        n = C.c_int32(0)
+        _check("emf_fusion_lifted_colors", load().emf_fusion_lifted_colors(self._h, None, 0, C.byref(n)))
+        records = np.zeros(2 * max(n.value, 1), np.dtype(hip.COLOR_MOVED_DTYPE))
+        _check("emf_fusion_lifted_colors", load().emf_fusion_lifted_colors(self._h, records.ctypes.data, n.value, C.byref(n)))
+        return [(records[2 * k].copy(), records[2 * k + 1].copy()) for k in range(n.value)]
 
     def planes(self, box=None, size=None, k=15, angle=20.0, separation=None, bin=None, band=None, min_votes=None, refine=1,
                up_hint=None, floor_angle=30.0, kind_angle=10.0, max_planes=64, labels=False, patches=False, patch_reach=1,

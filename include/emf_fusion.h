@@ -477,8 +477,10 @@ int emf_fusion_set_contacts_output(emf_fusion_t* h, int on, double touch_m);
  * An object that leaves view is deleted, as in the reference, and every scene query forgets it.  With the switch on its
  * signed-distance band is first resampled through the relative pose into the background volume and fused there by the
  * background's own running average, so that the distance field, plans, the ground map, the world mesh, the tile store and
- * a checkpoint keep it.  IT CARRIES THE BAND ONLY, not the free space around it; colour is not touched (absorbed voxels
- * keep the background's colour entries); an absorbed object that later moves leaves a ghost until free space carves it;
+ * a checkpoint keep it.  IT CARRIES THE BAND ONLY, not the free space around it; in a coloured session
+ * (emf_fusion_enable_color) the colour entry of every fused voxel goes with it, blended into the background's by the
+ * colour weights (emf_hip_absorbVolumeColor), in a colourless one the plain entry is called as before;
+ * an absorbed object that later moves leaves a ghost until free space carves it;
  * what lies outside the background's cube is clipped and lost.
  *   absorb_pose     needs no device and no handle: (R, t) taking the DESTINATION's volume frame into the SOURCE's from the
  *                   poses (world <- volume) of the destination d and the source s; float64 in the fixed order of
@@ -498,7 +500,12 @@ int emf_fusion_set_contacts_output(emf_fusion_t* h, int on, double touch_m);
  *                   emf_fusion_reset and a loaded checkpoint start it empty.
  *   set_absorbed_output  setup_output's exp_absorbed: emf_fusion_write_results also writes absorbed.txt, after a comment
  *                   line one line per event: id frame clipped, box_lo (3), box_size (3), the eight counts, lo (3), hi (3),
- *                   then R (9) and t (3) in %.9g.  Off: the set of result files and every byte of them as before.
+ *                   then R (9) and t (3) in %.9g.  Off: the set of result files and every byte of them as before.  In a
+ *                   coloured session each line ends with the event's colored and uncolored counts and the comment line
+ *                   names them; a colourless session writes the bytes it always wrote.
+ *   absorbed_colors the colour records of the log, parallel to `absorbed` (emf_absorb_event_t keeps its layout): the first
+ *                   min(capacity, *count) of them, colored + uncolored == record.fused; zeros for the events of a
+ *                   colourless session.  Like the log they are session state and in no checkpoint.
  * set_absorb_objects (on) and absorb_object are EMF_E_ARG on the sharded path. */
 typedef struct emf_absorb_event {
     int32_t id;             /* the absorbed object */
@@ -514,12 +521,15 @@ int emf_fusion_absorb_pose(const float Rd[9], const float td[3], const float Rs[
 int emf_fusion_set_absorb_objects(emf_fusion_t* h, int on);
 int emf_fusion_absorb_object(emf_fusion_t* h, int32_t id, emf_absorb_event_t* event);
 int emf_fusion_absorbed(emf_fusion_t* h, emf_absorb_event_t* events, int32_t capacity, int32_t* count);
+int emf_fusion_absorbed_colors(emf_fusion_t* h, emf_color_moved_t* records, int32_t capacity, int32_t* count);
 int emf_fusion_set_absorbed_output(emf_fusion_t* h, int on);
 /* Lifting objects out of the background (include/emf_hip.h "Lifting a volume"; new behaviour, opt-in):
  * the other half of absorbing.  A new object is SEEDED with the band the background already holds inside its cube, only
  * where it has no observation of its own, and the background RELEASES the band voxels the object then holds as
- * foreground, so that one surface has one explanation and no ghost stays behind when the object moves.  COLOUR IS NOT
- * TOUCHED; a voxel behind the object along a mask ray inside the cube is released too; an object discovered by motion
+ * foreground, so that one surface has one explanation and no ghost stays behind when the object moves.  In a coloured
+ * session the seeded voxels take the background's colour entries (the nearest voxel's, its weight capped) and the released
+ * voxels' entries are cleared (emf_hip_seedVolumeColor, emf_hip_releaseVolumeColor); in a colourless one
+ * the plain entries are called as before.  A voxel behind the object along a mask ray inside the cube is released too; an object discovered by motion
  * masks sits in free space: the seed finds nothing there and the ghost at the OLD place is not addressed.
  *   set_lift_objects   sticky, off by default.  On: every object a frame creates from a mask is seeded after the frame's
  *                   integration and before its masks are integrated (so the frame's own mask classifies the seeded
@@ -534,7 +544,12 @@ int emf_fusion_set_absorbed_output(emf_fusion_t* h, int on);
  *   set_lifted_output  setup_output's exp_lifted: emf_fusion_write_results also writes lifted.txt, after a comment line
  *                   one line per event: id frame clipped, box_lo (3), box_size (3), the seed's eight counts, lo (3), hi
  *                   (3), the release's seven counts, lo (3), hi (3), then the seed's R (9) and t (3) and the release's R
- *                   (9) and t (3) in %.9g.  Off: the set of result files and every byte of them as before.
+ *                   (9) and t (3) in %.9g.  Off: the set of result files and every byte of them as before.  In a coloured
+ *                   session each line ends with the colored and uncolored counts of the seed, then of the release, and
+ *                   the comment line names them; a colourless session writes the bytes it always wrote.
+ *   lifted_colors   the colour records of the log, parallel to `lifted` (emf_lift_event_t keeps its layout), TWO per event:
+ *                   records[2 k] the seed's (colored + uncolored == seed.seeded), records[2 k + 1] the release's
+ *                   (== release.released); `capacity` and *count are in events.  Zeros for a colourless session.
  * set_lift_objects (on) and lift_object are EMF_E_ARG on the sharded path. */
 typedef struct emf_lift_event {
     int32_t id;             /* the lifted object */
@@ -550,6 +565,7 @@ typedef struct emf_lift_event {
 int emf_fusion_set_lift_objects(emf_fusion_t* h, int on);
 int emf_fusion_lift_object(emf_fusion_t* h, int32_t id, emf_lift_event_t* event);
 int emf_fusion_lifted(emf_fusion_t* h, emf_lift_event_t* events, int32_t capacity, int32_t* count);
+int emf_fusion_lifted_colors(emf_fusion_t* h, emf_color_moved_t* records, int32_t capacity, int32_t* count);
 int emf_fusion_set_lifted_output(emf_fusion_t* h, int on);
 /* Planes (include/emf_hip.h "Planes"; new behaviour, opt-in): the dominant planes of a box of the
  * background (box_lo / box_size NULL: all of it) -- floor, walls, table tops.  A plane is the plane of the SHELL's voxel

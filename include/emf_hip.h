@@ -2401,7 +2401,8 @@ int emf_hip_contactProbe(const emf_model_t* models_dev, const int32_t* res_host,
  * copyValues move whole voxels on one lattice).
  * IT CARRIES THE BAND, NOT THE FREE SPACE AROUND IT: a saturated source sample (|s| == 1) only says "at least one
  * source truncation distance away", which with another truncation distance is no value the destination can fuse; such
- * a voxel is left alone.  Colour is not touched.
+ * a voxel is left alone.  emf_hip_absorbVolume does not touch colour; emf_hip_absorbVolumeColor (below) carries the
+ * voxel's colour entry with the band.
  * Volumes are dense, (z, y, x) order, x fastest, res = (nx, ny, nz); a voxel is v = (x, y, z).  R[9], t[3] (f32,
  * row-major): the source's volume frame <- the destination's volume frame.  Per destination voxel v of the box
  * [box_lo, box_lo + box_size), every float step a single float32 operation without contraction, in this order;
@@ -2463,6 +2464,38 @@ int emf_hip_absorbVolume(float* dst_tsdf, float* dst_weights, const int32_t dst_
                          float max_weight, const emf_absorb_source_t* source, const float R[9], const float t[3],
                          const int32_t box_lo[3], const int32_t box_size[3], emf_absorb_t* record_dev, emf_stream_t stream);
 
+/* Colour with the band.  emf_hip_absorbVolumeColor is emf_hip_absorbVolume -- the same walk, the same
+ * classes, and for the same inputs byte for byte the same tsdf, weights and emf_absorb_t -- that also carries the colour
+ * ENTRY of "Per-voxel colour" (uint16_t[4] per voxel: R, G, B, Wc in 8.8 fixed point, in the voxel order of the tsdf) of
+ * every FUSED voxel; the entry of every other voxel is neither read nor written.  All colour arithmetic is integer and
+ * exact: contraction cannot touch it.
+ *   SOURCE ENTRY  S = (Sc[3], Sw): src_color at (rint(q_0), rint(q_1), rint(q_2)), ties to even -- the voxel MASKED
+ *                 addresses, and the "nearest voxel, no interpolation" rule of emf_hip_sampleColor.  src_color == NULL:
+ *                 every source entry is (0, 0, 0, 0).
+ *   WEIGHT CAP    capq, made once on the host from max_weight: 65535 if max_weight * 256 >= 65535, otherwise
+ *                 lrintf(max_weight * 256.f), and at least 1.
+ *   With D = (Dc[3], Dw) the destination's entry at v, read once before any channel is written, and De = 0 if the voxel
+ *   is FRESH (!(pw > 0): an unobserved voxel's entry is not evidence), otherwise De = Dw:
+ *     UNCOLOURED  Sw == 0: the entry becomes (0, 0, 0, 0) if the voxel is FRESH and stays as it is otherwise.
+ *     COLOURED    Sw > 0, per channel:  Dc' = (De * Dc + Sw * Sc + (De + Sw) / 2) / (De + Sw), floor division, exact for
+ *                 every u16 input (the products and their sum do not fit 32 bits);  Dw' = min(De + Sw, capq).  With
+ *                 De == 0 this is a copy of Sc.
+ * emf_color_moved_t: a second device record, neutral at (0, 0) and set by the call's own init launch;
+ * colored + uncolored == fused.  An entry whose four values do not change need not be stored. */
+typedef struct emf_color_moved {
+    uint64_t colored, uncolored;
+} emf_color_moved_t;            /* 16 bytes */
+
+/* The arguments of emf_hip_absorbVolume plus dst_color (the destination's colour volume, written in place), src_color
+ * (the source's, only read, or NULL) and color_record_dev (device, 8-byte aligned).  Refused with nothing enqueued,
+ * on top of everything emf_hip_absorbVolume refuses and with its codes: dst_color NULL (the plain entry is the one to
+ * call) or color_record_dev NULL; a colour pointer or the colour record not 8-byte aligned; dst_color or the colour
+ * record sharing a byte with any other array of the call.  An empty box: EMF_OK and both neutral records. */
+int emf_hip_absorbVolumeColor(float* dst_tsdf, float* dst_weights, uint16_t* dst_color, const int32_t dst_res[3], float dst_voxel_size,
+                              float dst_truncdist, float max_weight, const emf_absorb_source_t* source, const uint16_t* src_color,
+                              const float R[9], const float t[3], const int32_t box_lo[3], const int32_t box_size[3],
+                              emf_absorb_t* record_dev, emf_color_moved_t* color_record_dev, emf_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Lifting a volume (new behaviour: DESIGN.md 5.30).  Opt-in; nothing above is touched.  The opposite direction of
  * "Absorbing a volume", in two passes: a new object is SEEDED from what the background already holds of it, and the
@@ -2472,7 +2505,8 @@ int emf_hip_absorbVolume(float* dst_tsdf, float* dst_weights, const int32_t dst_
  * box_size) the sample-point arithmetic p_d, p_s, q, l, f; the pad-1 OUTSIDE rule; the blend in x pairs, then y, then z;
  * every float step a single float32 operation without contraction, everything else integer; the classes in the order
  * given, the first match wins; of tsdf[v] and weights[v] only the words whose bits change are stored.  pw, pt: the
- * destination's weight and tsdf at v.  Colour is not touched by either pass.
+ * destination's weight and tsdf at v.  Colour is not touched by either pass; emf_hip_seedVolumeColor and
+ * emf_hip_releaseVolumeColor (below) carry it.
  *
  * emf_hip_seedVolume: THE DESTINATION TAKES THE SOURCE'S BAND ONLY WHERE IT HAS NO OBSERVATION OF ITS OWN.
  *     KEPT       pw > 0.  Decided before anything of the source is read; the voxel is not written.  (A new object has
@@ -2531,6 +2565,25 @@ int emf_hip_releaseVolume(float* dst_tsdf, float* dst_weights, const int32_t dst
                           const uint8_t* claim_mask, const int32_t claim_res[3], float claim_voxel_size, const float R[9],
                           const float t[3], const int32_t box_lo[3], const int32_t box_size[3], emf_release_t* record_dev,
                           emf_stream_t stream);
+
+/* Colour with the band: the two passes as emf_hip_absorbVolumeColor states them -- the same walk, for
+ * the same inputs byte for byte the same tsdf, weights and geometry record as the plain entry, the colour entry, the
+ * SOURCE ENTRY S = (Sc[3], Sw) at the nearest voxel, capq and emf_color_moved_t of "Absorbing a volume", integer and
+ * exact.  Only the entry of a SEEDED (RELEASED) voxel is written; every other voxel's is neither read nor written.
+ *   SEED      a SEEDED voxel's entry becomes (Sc, min(Sw, capq)) if Sw > 0 (COLOURED), else (0, 0, 0, 0) (UNCOLOURED);
+ *             colored + uncolored == seeded.  A second seed finds the voxel KEPT and changes no colour byte.
+ *   RELEASE   a RELEASED voxel's entry becomes (0, 0, 0, 0), what TSDF::reset leaves.  COLOURED counts the entries that
+ *             held a non-zero value, UNCOLOURED those already zero; colored + uncolored == released.
+ * The arguments of the plain entries plus dst_color, src_color (the seed; may be NULL: every source entry is
+ * (0, 0, 0, 0)) and color_record_dev; the additional refusals are those of emf_hip_absorbVolumeColor. */
+int emf_hip_seedVolumeColor(float* dst_tsdf, float* dst_weights, uint16_t* dst_color, const int32_t dst_res[3], float dst_voxel_size,
+                            float dst_truncdist, float max_weight, const emf_absorb_source_t* source, const uint16_t* src_color,
+                            const float R[9], const float t[3], const int32_t box_lo[3], const int32_t box_size[3],
+                            emf_seed_t* record_dev, emf_color_moved_t* color_record_dev, emf_stream_t stream);
+int emf_hip_releaseVolumeColor(float* dst_tsdf, float* dst_weights, uint16_t* dst_color, const int32_t dst_res[3], float dst_voxel_size,
+                               const uint8_t* claim_mask, const int32_t claim_res[3], float claim_voxel_size, const float R[9],
+                               const float t[3], const int32_t box_lo[3], const int32_t box_size[3], emf_release_t* record_dev,
+                               emf_color_moved_t* color_record_dev, emf_stream_t stream);
 
 #ifdef __cplusplus
 }
