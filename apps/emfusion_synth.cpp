@@ -9,6 +9,7 @@
 //                  [--frontiers] [--frontier-min-voxels N] [--frontier-clearance M]
 //                  [--plan] [--plan-clearance M] [--plan-through-unknown] [--plan-shortcut W] [--object-shapes]
 //                  [--object-contacts] [--contact-touch M] [--absorb-objects] [--turn-away F] [--lift-objects]
+//                  [--merge-objects] [--merge-overlap F] [--merge-max-res N]
 //                  [--ground-map] [--ground-up X,Y,Z] [--ground-cell M] [--ground-bin M] [--ground-band LO,HI]
 //                  [--ground-robot-height M] [--ground-max-step M] [--planes] [--planes-angle DEG] [--planes-min-votes N]
 //                  [--plane-patches] [--plane-patch-reach R] [--plane-patch-min N]
@@ -143,6 +144,12 @@ static bool absorbObjects = false;
 // writes OUT/lifted.txt, one line per lifted object; without it no output byte changes.  Objects are created from masks
 // on a dataset and with --autonomous; on the synthetic stream with given poses the switch would do nothing and is refused.
 static bool liftObjects = false;
+// --merge-objects [--merge-overlap F] [--merge-max-res N] (needs --out): duplicate objects -- one physical thing with two
+// volumes -- are merged at the end of every mask frame, the older object stays; writeResults also writes
+// OUT/merged.txt, one line per merge; without it no output byte changes.  Valid where objects are created from masks, as
+// --lift-objects is.  F (default 0.5) and N (default 256) are policy values.
+static bool mergeObjects = false, mergeParamGiven = false;
+static emf::EMFusion::MergeParams mergeParams;
 // --turn-away F (synthetic stream with given poses, not --autonomous): from frame F on the camera pose handed in looks
 // the other way (half a turn about its y axis) and the clean-up runs, so every object leaves view and is deleted at F
 static int turnAway = -1;
@@ -292,6 +299,7 @@ static int runSequence(const std::string& seq, bool cofusion, const std::string&
     if (objectContactsOut) emf.setContactsOutput(true, contactTouch);
     if (absorbObjects) emf.setAbsorbObjects(true), emf.setAbsorbedOutput(true);  // (not stored in a checkpoint: set again on --resume)
     if (liftObjects) emf.setLiftObjects(true), emf.setLiftedOutput(true);          // (nor is this)
+    if (mergeObjects) emf.setMergeObjects(true, mergeParams), emf.setMergedOutput(true);  // (nor this)
     if (groundOut.on) emf.setGroundOutput(groundOut);
     if (groundUpFloor) emf.setGroundUpFloor(true);
     if (planesOut.on) emf.setPlanesOutput(planesOut);
@@ -409,6 +417,9 @@ int main(int argc, char** argv) {
         else if (a == "--object-contacts") objectContactsOut = true;
         else if (a == "--absorb-objects") absorbObjects = true;
         else if (a == "--lift-objects") liftObjects = true;
+        else if (a == "--merge-objects") mergeObjects = true;
+        else if (a == "--merge-overlap" && i + 1 < argc) mergeParamGiven = true, mergeParams.minOverlap = std::atof(argv[++i]);
+        else if (a == "--merge-max-res" && i + 1 < argc) mergeParamGiven = true, mergeParams.maxRes = std::atoi(argv[++i]);
         else if (a == "--turn-away" && i + 1 < argc) turnAway = std::atoi(argv[++i]);
         else if (a == "--contact-touch" && i + 1 < argc) contactTouchGiven = true, contactTouch = std::atof(argv[++i]);
         else if (a == "--ground-map") groundOut.on = true;
@@ -491,6 +502,19 @@ int main(int argc, char** argv) {
     }
     if (absorbObjects && outDir.empty()) {
         std::fprintf(stderr, "usage: emfusion_synth: --absorb-objects writes absorbed.txt and needs --out DIR\n");
+        return 2;
+    }
+    if (mergeParamGiven && !mergeObjects) {
+        std::fprintf(stderr, "usage: emfusion_synth: --merge-overlap F and --merge-max-res N are parameters of --merge-objects\n");
+        return 2;
+    }
+    if (mergeObjects && outDir.empty()) {
+        std::fprintf(stderr, "usage: emfusion_synth: --merge-objects writes merged.txt and needs --out DIR\n");
+        return 2;
+    }
+    if (mergeObjects && sequence.empty() && dataDir.empty() && !autonomous) {
+        std::fprintf(stderr, "usage: emfusion_synth: --merge-objects acts where objects are created from masks: with --sequence / "
+                             "--dir or --autonomous; on the synthetic stream with given poses it would do nothing\n");
         return 2;
     }
     if (liftObjects && outDir.empty()) {
@@ -608,6 +632,7 @@ int main(int argc, char** argv) {
         if (objectContactsOut) emf.setContactsOutput(true, contactTouch);
         if (absorbObjects) emf.setAbsorbObjects(true), emf.setAbsorbedOutput(true);
         if (liftObjects) emf.setLiftObjects(true), emf.setLiftedOutput(true);
+        if (mergeObjects) emf.setMergeObjects(true, mergeParams), emf.setMergedOutput(true);
         if (groundOut.on) emf.setGroundOutput(groundOut);
         if (groundUpFloor) emf.setGroundUpFloor(true);
         if (planesOut.on) emf.setPlanesOutput(planesOut);
@@ -688,6 +713,7 @@ int main(int argc, char** argv) {
                     emf.visibleObjects().size(), emf.usesBatchedLaunches() ? "yes" : "no");
         if (absorbObjects) std::printf("absorbed into the background: %zu objects\n", emf.absorbed().size());
         if (liftObjects) std::printf("lifted out of the background: %zu objects\n", emf.lifted().size());
+        if (mergeObjects) std::printf("merged into other objects: %zu objects\n", emf.merged().size());
         if (!outDir.empty()) {
             emf.writeResults(outDir, false);  // volumes follow setupOutput, as in the reference
             const emf::Mesh bg = emf.getMesh(0);

@@ -111,6 +111,15 @@ def main():
                     help="seed an object created from a mask with the band the background already holds inside its cube, "
                          "let the background release what the object then holds as foreground, and also write "
                          "OUT/lifted.txt: one line per lifted object")
+    ap.add_argument("--merge-objects", dest="merge_objects", action="store_true",
+                    help="merge duplicate objects at the end of every mask frame (one physical thing with two volumes: the "
+                         "contact probe over all object pairs, the older object stays) and also write OUT/merged.txt: one "
+                         "line per merge")
+    ap.add_argument("--merge-overlap", dest="merge_overlap", type=float, default=None, metavar="F",
+                    help="with --merge-objects: the share of one object's surface that has to lie on the other's (default "
+                         "0.5, a policy value)")
+    ap.add_argument("--merge-max-res", dest="merge_max_res", type=int, default=None, metavar="N",
+                    help="with --merge-objects: the largest resolution per axis a merge grows an object to (default 256)")
     ap.add_argument("--contact-touch", dest="contact_touch", type=float, default=None, metavar="M",
                     help="with --object-contacts: the touching threshold in metres (default: one voxel of the probe)")
     ap.add_argument("--ground-map", dest="ground_map", action="store_true",
@@ -174,6 +183,8 @@ def main():
     args = ap.parse_args()
     if args.motion_masks and args.masks:  # (before the device is opened)
         ap.error("--motion-masks and --masks exclude each other")
+    if (args.merge_overlap is not None or args.merge_max_res is not None) and not args.merge_objects:
+        ap.error("--merge-overlap F and --merge-max-res N are parameters of --merge-objects")
     if args.distance_nearest and not args.distance_field:
         ap.error("--distance-nearest writes nearest.bin beside distance.bin and needs --distance-field")
     if args.plan_shortcut and not args.plan:
@@ -257,6 +268,9 @@ def main():
         fus.set_absorb_objects(True)
     if args.lift_objects:
         fus.set_lift_objects(True)
+    if args.merge_objects:
+        fus.set_merge_objects(True, min_overlap=0.5 if args.merge_overlap is None else args.merge_overlap,
+                              max_res=256 if args.merge_max_res is None else args.merge_max_res)
     fus.set_preprocess(True)
     fus.set_cleanup(True)
     fus.setup_output(args.frame_meshes, args.volumes, args.world_mesh, exp_distance_field=args.distance_field,
@@ -266,7 +280,7 @@ def main():
                      plan_clearance=max(args.plan_clearance, 0.0), plan_through_unknown=args.plan_through_unknown,
                      exp_distance_nearest=args.distance_nearest, exp_plan_shortcut=args.plan_shortcut,
                      exp_object_shapes=args.object_shapes, exp_object_contacts=args.object_contacts,
-                     contact_touch=args.contact_touch, exp_absorbed=args.absorb_objects, exp_lifted=args.lift_objects, exp_ground_map=args.ground_map,
+                     contact_touch=args.contact_touch, exp_absorbed=args.absorb_objects, exp_lifted=args.lift_objects, exp_merged=args.merge_objects, exp_ground_map=args.ground_map,
                      ground_up=None if args.ground_up is None else "floor" if args.ground_up == "floor"
                      else [float(v) for v in args.ground_up.split(",")],
                      exp_planes=args.planes, planes_angle=args.planes_angle, planes_min_votes=args.planes_min_votes,

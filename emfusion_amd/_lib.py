@@ -263,6 +263,12 @@ SIGNATURES = {
                                 C.POINTER(C.c_float), _I3, _I3, _FP, _FP, _STREAM],
     "emf_hip_releaseVolumeColor": [_FP, _FP, _FP, _I3, C.c_float, _FP, _I3, C.c_float, C.POINTER(C.c_float),
                                    C.POINTER(C.c_float), _I3, _I3, _FP, _FP, _STREAM],
+    # merging: dst_fgbg behind the destination's weights, src_fgbg behind the source, the count record behind the record;
+    # with colour dst_color behind dst_fgbg, src_color behind src_fgbg and the colour record last
+    "emf_hip_mergeVolume": [_FP, _FP, _FP, _I3, C.c_float, C.c_float, C.c_float, C.c_void_p, _FP, C.POINTER(C.c_float),
+                            C.POINTER(C.c_float), _I3, _I3, _FP, _FP, _STREAM],
+    "emf_hip_mergeVolumeColor": [_FP, _FP, _FP, _FP, _I3, C.c_float, C.c_float, C.c_float, C.c_void_p, _FP, _FP,
+                                 C.POINTER(C.c_float), C.POINTER(C.c_float), _I3, _I3, _FP, _FP, _FP, _STREAM],
 }
 
 
@@ -409,6 +415,8 @@ RELEASE_DTYPE = [("visited", "<u8"), ("empty", "<u8"), ("free_space", "<u8"), ("
                  ("released", "<u8"), ("solid", "<u8"), ("lo", "<i4", 3), ("hi", "<i4", 3)]
 # include/emf_hip.h "Absorbing a volume": emf_color_moved_t (16 bytes), the second record of the colour entries
 COLOR_MOVED_DTYPE = [("colored", "<u8"), ("uncolored", "<u8")]
+# include/emf_hip.h "Merging a volume": emf_merge_counts_t (16 bytes), the second record of the count pairs
+MERGE_COUNTS_DTYPE = [("foreground", "<u8"), ("gained", "<u8")]
 CONTACT_UNSEEN, CONTACT_APART, CONTACT_TOUCHING, CONTACT_PENETRATING = 0, 1, 2, 3
 CONTACT_STATES = ("unseen", "apart", "touching", "penetrating")
 RAY_REACHED, RAY_BLOCKED, RAY_LEFT, RAY_OUTSIDE, RAY_INVALID = 0, 1, 2, 3, 4

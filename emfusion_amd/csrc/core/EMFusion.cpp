@@ -149,6 +149,7 @@ void EMFusion::reset() {
     absorbDirty_ = false;
     liftLog_.clear();  // session state; the switch stays
     liftPending_.clear();
+    mergeLog_.clear();  // session state
     colorImageSet = false;
     motionInfo.clear();
     motionFired = false;
@@ -644,6 +645,7 @@ void EMFusion::runSchedule(const emf_image_t& depthDev, const FrameInputs& in) {
             for (auto& obj : objects) obj.updateExProb(masks.count(obj.getID()) != 0);
         lastDeleted = cleanUpObjs(in.runMasks || instances, masks);
     }
+    if (mergeOn_ && (in.runMasks || instances) && objects.size() >= 2) mergeDuplicates();
     stamp(kMasks);
 
     if (timingsOn) {

@@ -676,6 +676,72 @@ public:
     /** writeResults also writes lifted.txt (writeLifted); without it no output byte changes. */
     void setLiftedOutput(bool on) { expLifted_ = on; }
     void writeLifted(const std::string& dir);
+    /** One merge: which object went into which, through what, and what became of the voxels of the box. */
+    struct MergeEvent {
+        int dst = 0, src = 0;       // the object that stays and the one that went into it
+        int frame = 0;              // the frame index (frames()) at which it happened
+        float dstR[9], dstT[3];     // the destination's pose (volume -> world) as the merge used it: after the growth
+        float srcR[9], srcT[3];     // the source's pose
+        float R[9], t[3];           // the pose used: the source's volume frame <- the destination's volume frame
+        int32_t lo[3], size[3];     // the box of destination voxels the launch covered
+        bool clipped = false;       // the source's cube (destination voxels, rounded outwards) leaves the destination's: lost
+        bool automatic = false;     // merged by setMergeObjects at the end of a mask frame, not by a call
+        double overlap[2] = {0.0, 0.0};  // what decided an automatic merge (dst -> src, src -> dst); 0 for an explicit call
+        int resBefore = 0, resAfter = 0;  // the destination's resolution per axis before and after the growth
+        emf_absorb_t record;        // include/emf_hip.h "Merging a volume"
+        emf_merge_counts_t counts{};
+        emf_color_moved_t color{};  // zeros in a colourless session
+    };
+    /**
+     * Merging an object into another object (include/emf_hip.h "Merging a volume"), between frames: the
+     * repair for one physical thing that ended up with two volumes.  Three steps.
+     * GROW: the destination's cube must hold what the source holds.  The inclusive bounds lo, hi (voxels) of the OBSERVED
+     * SOLID BAND of both objects come from one emf_hip_shapeMoments launch; a bound v on axis j is the coordinate
+     * c_j = (v_j - (N_j - 1) / 2) * voxelSize of its volume frame; the eight corners of the source's bounds go through
+     * (R', t') = absorbPose(source pose, destination pose) -- the destination's frame <- the source's, float32 -- as
+     * x_i = ((R'_i0 * c_0 + R'_i1 * c_1) + R'_i2 * c_2) + t'_i; the minimum and maximum over them and the destination's own
+     * two bounds, per axis, rounded to float32 once, go to ObjTSDF::resize(lo, hi, volPad).  Everything float64, every line
+     * a single operation in that order.  An object without a solid voxel adds nothing to the union.  MergeParams::maxRes
+     * caps the grown resolution per axis (default 256: a policy value, the largest object volume of BASELINE.json's
+     * configs, not a measurement); where the growth would pass it the destination is not grown.
+     * MERGE: absorbPose(destination pose, source pose), the covering box (absorbBox; `clipped` as 5.29 computes it), one
+     * emf_hip_mergeVolume on the main stream -- emf_hip_mergeVolumeColor in a coloured session -- then the destination's
+     * volumesWritten(): fgProbs / fgVolMask from the summed counts.  THE POSES ARE TAKEN AS THEY ARE: the two volumes are not
+     * registered first, a drifted duplicate merges blurred.  It carries the band, not the free space around it.
+     * BOOKKEEPING: the destination keeps its id and its tracking state, and its pose but for the shift of the growth (logged
+     * as a resize is); its existence counts become the sums of both, its class scores the element-wise sums.  The source
+     * is deleted; ITS KEPT MESH AND exp_vols COPY ARE NOT KEPT -- its geometry lives on in the destination.
+     * Refuses (EMF_E_ARG) id 0, an unknown id, dstId == srcId, an object this rank does not own and the sharded path.
+     * The log (merged()) is session state: not in checkpoints, emptied by reset() and by a loaded checkpoint.  Without a
+     * call no launch, no output byte and no checkpoint byte changes.
+     */
+    MergeEvent mergeObjects(int dstId, int srcId);
+    const std::vector<MergeEvent>& merged() const { return mergeLog_; }
+    /** What decides an automatic merge.  THE DEFAULTS ARE POLICY, NOT MEASUREMENTS. */
+    struct MergeParams {
+        double minOverlap = 0.5;   // a pair qualifies when max(overlap(a -> b), overlap(b -> a)) >= minOverlap
+        int64_t minSurface = 64;   // ... and both surfaces hold at least this many voxels
+        double touch = -1.0;       // metres; < 0: half a truncation distance of the first live object (through contactTouch)
+        int maxRes = 256;          // the cap of the growth, of explicit calls too
+    };
+    /**
+     * Merging DUPLICATES automatically.  Sticky, off by default; the parameters are kept either way (an
+     * explicit mergeObjects grows up to maxRes).  When on, at the end of every mask frame, after cleanUpObjs, with at least
+     * two live objects: one emf_hip_contactProbe launch over all ordered object pairs (objectContacts without the
+     * background); overlap(a -> b) = touching / surface of the record a -> b, a float64 quotient, 0 for an empty surface; a
+     * pair qualifies by MergeParams; qualifying pairs are merged in descending max overlap, ties to the smaller pair of
+     * ids; the older object (smaller id) is the destination; an object takes part in at most one merge per frame.
+     * IT FINDS DUPLICATES: two halves that merely abut reach no sensible overlap and are merged by the explicit call or by
+     * a caller's own rule on objectContacts().  Neither the switch nor the log is written to a checkpoint.  With the
+     * switch off no launch, no output byte and no checkpoint byte changes.  Refused (EMF_E_ARG) on the sharded path.
+     */
+    void setMergeObjects(bool on, const MergeParams& p);
+    void setMergeObjects(bool on) { setMergeObjects(on, mergeParams_); }
+    bool mergeObjectsOn() const { return mergeOn_; }
+    const MergeParams& mergeParams() const { return mergeParams_; }
+    /** writeResults also writes merged.txt (writeMerged); without it no output byte changes. */
+    void setMergedOutput(bool on) { expMerged_ = on; }
+    void writeMerged(const std::string& dir);
     /** The result of groundMap(): the frame, the pose "ground metres -> world" and the arrays left on the device. */
     struct GroundMap {
         QueryBox box;
@@ -1243,7 +1309,8 @@ private:
     DeviceBuffer lifecycleMsg;  // sharded: the 16-byte messages of initNewObjVolume / updateObject
     void deleteObj(int id);
     // cleanUpObjs' removal of an object of this rank; absorb: into the background first (setAbsorbObjects)
-    void deleteOwned(std::list<ObjTSDF>::iterator it, bool absorb = false);
+    // keep = false (mergeObjects): neither its mesh nor its exp_vols copy is kept
+    void deleteOwned(std::list<ObjTSDF>::iterator it, bool absorb = false, bool keep = true);
     void ensureLifecycleBuffers();
     // layout of lifecycleHost: emf_point_stats_t / 513 x u32 / EMF_MAX_MODELS x emf_mask_mass_t, then EMF_MAX_MODELS
     // floats (verdicts, messages), then EMF_MAX_MODELS int32 (gate)
@@ -1431,8 +1498,8 @@ private:
         if (colorDev) hipCheck(hipMemcpyAsync(colorHost, colorDev, sizeof(emf_color_moved_t), hipMemcpyDeviceToHost, main.get()), what);
         main.waitForCompletion();
     }
-    // the covering box of the object's cube in background voxels and whether the background's cube clips it
-    void absorbBox(const ObjTSDF& obj, const float R[9], const float t[3], int32_t lo[3], int32_t size[3], bool& clipped);
+    // the covering box of the object's cube in the voxels of dst (the background, or another object) and whether dst's cube clips it
+    void absorbBox(const TSDF& dst, const ObjTSDF& obj, const float R[9], const float t[3], int32_t lo[3], int32_t size[3], bool& clipped);
     // ---- lifting objects (setLiftObjects, liftObject; EMFusionLift.cpp): never in a checkpoint; with the switch off no
     // launch of the frame changes
     bool liftOn_ = false;            // setLiftObjects
@@ -1444,6 +1511,15 @@ private:
     void liftRelease(ObjTSDF& obj, LiftEvent& e);  // the launch on main and the log entry; the caller has quiesced
     void liftSeedCreated();          // runSchedule: after integrateDepth(), before integrateMasks()
     void liftReleaseCreated();       // runSchedule: after integrateMasks(), before cleanUpObjs
+    // ---- merging objects (mergeObjects, setMergeObjects; EMFusionMerge.cpp): never in a checkpoint; with the switch off
+    // and no call nothing changes
+    bool mergeOn_ = false;           // setMergeObjects
+    bool expMerged_ = false;         // setMergedOutput
+    MergeParams mergeParams_;
+    MergeEvent mergeInto(int dstId, int srcId, bool automatic, double overlapDS, double overlapSD);
+    void mergeDuplicates();          // runSchedule: the end of a mask frame, after cleanUpObjs
+    std::vector<MergeEvent> mergeLog_;
+    DeviceBuffer mergeRecord_;       // one emf_absorb_t, one emf_merge_counts_t, one emf_color_moved_t; the growth's table and moments
 };
 
 /**
@@ -1523,6 +1599,18 @@ void contactPose(const float Ra[9], const float ta[3], const float Rb[9], const 
  * b = s, rounded to f32 once: R_ij = float((Rs_0i * Rd_0j + Rs_1i * Rd_1j) + Rs_2i * Rd_2j), t likewise from td - ts.
  */
 void absorbPose(const float Rd[9], const float td[3], const float Rs[9], const float ts[3], float R[9], float t[3]);
+/**
+ * The growth of a merge (EMFusion::mergeObjects), without a device: the box of the destination's volume
+ * frame, in metres, that holds the destination's band and the source's.  dLo, dHi / sLo, sHi: the inclusive bounds in
+ * voxels of the two bands (emf_shape_moments_t lo, hi; hi[0] < 0: no solid voxel, the object adds nothing); (R, t): the
+ * destination's volume frame <- the source's, float32.  Float64, every line a single operation in this order:
+ *     c_j = (double(v_j) - (double(N_j) - 1.0) / 2.0) * double(voxelSize)       a bound on axis j
+ *     x_i = ((R_i0 * c_0 + R_i1 * c_1) + R_i2 * c_2) + t_i                       each of the source's eight corners
+ *     lo_i, hi_i = the minimum and the maximum over those and the destination's own c, rounded to float32 once
+ * Returns false, lo and hi untouched, where neither object has a solid voxel.
+ */
+bool mergeUnion(const int32_t dLo[3], const int32_t dHi[3], const int32_t dRes[3], float dVoxel, const int32_t sLo[3],
+                const int32_t sHi[3], const int32_t sRes[3], float sVoxel, const float R[9], const float t[3], float lo[3], float hi[3]);
 float contactTouch(double touchMetres, float truncdistB);
 void contactSummary(const emf_contact_t& ab, const emf_contact_t* ba, const emf_contact_side_t& a, const emf_contact_side_t& b,
                     emf_contact_summary_t& out);

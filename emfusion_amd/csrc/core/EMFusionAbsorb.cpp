@@ -24,10 +24,11 @@ void EMFusion::setAbsorbObjects(bool on) {
     absorbOn_ = on;
 }
 
-// The covering box of the whole object in background voxels under (R, t) = the object's volume frame <- the background's,
-// and whether the background's cube clips the object.
-void EMFusion::absorbBox(const ObjTSDF& obj, const float R[9], const float t[3], int32_t lo[3], int32_t size[3], bool& clipped) {
-    const Vec3i n = background.getVolumeRes(), r = obj.getVolumeRes();
+// The covering box of the whole object in the voxels of dst -- the background, or another object --
+// under (R, t) = the object's volume frame <- dst's, and whether dst's cube clips the object.  "Background" below is dst.
+void EMFusion::absorbBox(const TSDF& dst, const ObjTSDF& obj, const float R[9], const float t[3], int32_t lo[3], int32_t size[3],
+                         bool& clipped) {
+    const Vec3i n = dst.getVolumeRes(), r = obj.getVolumeRes();
     // the covering box of the whole object, and the same box against a background with kPad more voxels on every side
     // (the same centre): that one, less the helper's one voxel of margin, is the extent of the object's cube in
     // background voxels (rounded outwards); where it leaves [0, n - 1] the background's cube clips the object.  A pose
@@ -40,8 +41,8 @@ void EMFusion::absorbBox(const ObjTSDF& obj, const float R[9], const float t[3],
     std::copy(t, t + 3, o.t);
     emf_occ_object_t wide = o;
     const int32_t padded[3] = {n[0] + 2 * kPad, n[1] + 2 * kPad, n[2] + 2 * kPad};
-    emfCheck(emf_hip_occupancyObjectBox(&o, n.val, background.getVoxelSize()), "EMFusion::absorb (box)");
-    emfCheck(emf_hip_occupancyObjectBox(&wide, padded, background.getVoxelSize()), "EMFusion::absorb (unclipped box)");
+    emfCheck(emf_hip_occupancyObjectBox(&o, n.val, dst.getVoxelSize()), "EMFusion::absorb (box)");
+    emfCheck(emf_hip_occupancyObjectBox(&wide, padded, dst.getVoxelSize()), "EMFusion::absorb (unclipped box)");
     const bool everywhere = wide.lo[0] == 0 && wide.lo[1] == 0 && wide.lo[2] == 0 && wide.size[0] == padded[0] &&
                             wide.size[1] == padded[1] && wide.size[2] == padded[2];
     for (int i = 0; i < 3; ++i) {
@@ -61,7 +62,7 @@ void EMFusion::absorbInto(ObjTSDF& obj) {
     const Affine3f bg = background.getPose(), op = obj.getPose();
     absorbPose(bg.rotation().val, bg.translation().val, op.rotation().val, op.translation().val, e.R, e.t);
     const Vec3i n = background.getVolumeRes(), r = obj.getVolumeRes();
-    absorbBox(obj, e.R, e.t, e.lo, e.size, e.clipped);
+    absorbBox(background, obj, e.R, e.t, e.lo, e.size, e.clipped);
     emf_absorb_source_t s{};
     s.tsdf = obj.tsdfPtr();
     s.weights = obj.weightsPtr();

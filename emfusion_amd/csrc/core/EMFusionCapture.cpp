@@ -49,6 +49,7 @@ void EMFusion::writeResults(const std::string& dir, bool volumes) {
     if (expContacts_) writeContacts(dir);       // contacts.txt of the live objects and the background (5.27)
     if (expAbsorbed_) writeAbsorbed(dir);       // absorbed.txt, the session's log of absorbed objects (5.29)
     if (expLifted_) writeLifted(dir);           // lifted.txt, the session's log of lifted objects (5.30)
+    if (expMerged_) writeMerged(dir);           // merged.txt, the session's log of merged objects (5.32)
     if (expFrameMeshes_) {  // writeFrameMeshes (EMFusion.cpp:1158-1185); the reference creates frame_meshes/ always
         auto writeAll = [](const std::string& d, const std::map<int, Mesh>& log) {
             io::createDirectories(d);

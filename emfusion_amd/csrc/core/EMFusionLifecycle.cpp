@@ -436,13 +436,13 @@ void EMFusion::deleteObj(int id) {  // reference EMFusion.cpp:982-989
 }
 
 // The deletion of an object of this rank (EMFusion.cpp:951-976); the caller rebuilds the table afterwards.
-void EMFusion::deleteOwned(std::list<ObjTSDF>::iterator it, bool absorb) {
+void EMFusion::deleteOwned(std::list<ObjTSDF>::iterator it, bool absorb, bool keep) {
     const int id = it->getID();
     quiesce();  // nothing in flight may still use the volume
     // gone from view with setAbsorbObjects on: its band goes into the background first
     if (absorb && !(ignorePerson && isPerson(*it))) absorbInto(*it);
     deleteObj(id);
-    if (poseLog && !(ignorePerson && isPerson(*it))) {
+    if (keep && poseLog && !(ignorePerson && isPerson(*it))) {
         meshes[id] = it->getMesh();  // saveOutput: EMFusion.cpp:962-966
         if (expVols) savedVolumes[id] = saveVolumes(*it);  // EMFusion.cpp:967-973
     }

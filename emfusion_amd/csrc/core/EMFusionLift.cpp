@@ -65,7 +65,7 @@ void EMFusion::liftSeed(ObjTSDF& obj, LiftEvent& e) {
 void EMFusion::liftRelease(ObjTSDF& obj, LiftEvent& e) {
     const Affine3f bg = background.getPose(), op = obj.getPose();
     absorbPose(bg.rotation().val, bg.translation().val, op.rotation().val, op.translation().val, e.releaseR, e.releaseT);
-    absorbBox(obj, e.releaseR, e.releaseT, e.lo, e.size, e.clipped);
+    absorbBox(background, obj, e.releaseR, e.releaseT, e.lo, e.size, e.clipped);
     const Vec3i n = background.getVolumeRes(), r = obj.getVolumeRes();
     liftRecord_.reserve(kLiftRecordBytes);
     emf_release_t* rec = reinterpret_cast<emf_release_t*>(liftRecord_.as<char>() + sizeof(emf_seed_t));

@@ -142,6 +142,18 @@ Vec3f ObjTSDF::resize(const Vec3f& p10, const Vec3f& p90, float volPad, Stream& 
     return newCenter;
 }
 
+int ObjTSDF::resizedRes(const Vec3f& p10, const Vec3f& p90, float volPad) const {  // the lines of resize() that decide
+    bool contained = true;
+    for (int i = 0; i < 3 && contained; ++i) {
+        const float half = (static_cast<float>(volumeRes[i]) - 1.f) * .5f * voxelSize;
+        contained = !(p10[i] < -half || p90[i] > half);
+    }
+    if (contained) return 0;
+    const Vec3f dims = p90 - p10;
+    const float newVolSize = volPad * std::max(dims[0], std::max(dims[1], dims[2])) / voxelSize;
+    return (static_cast<int>(std::ceil(newVolSize)) + 1) / 2 * 2;
+}
+
 void ObjTSDF::volumesWritten(Stream& stream) {
     TSDF::volumesWritten(stream);
     computeFgProbs(stream);

@@ -64,6 +64,9 @@ public:
      * centre shift in the old volume frame (0 if the box was contained and nothing changed).
      */
     Vec3f resize(const Vec3f& p10, const Vec3f& p90, float volPad, Stream& stream = Stream::Null());
+    /** The cubic resolution resize(p10, p90, volPad) would give the volume; 0 where the box is contained and nothing
+     *  would change.  Changes nothing. */
+    int resizedRes(const Vec3f& p10, const Vec3f& p90, float volPad) const;
 
     /** Mesh of the foreground part only (reference ObjTSDF::getMesh, ObjTSDF.cpp:247-268). */
     Mesh getMesh() override;

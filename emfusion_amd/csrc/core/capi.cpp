@@ -1204,6 +1204,102 @@ int emf_fusion_set_lifted_output(emf_fusion_t* h, int on) {
     return guarded([&] { h->impl->setLiftedOutput(on != 0); });
 }
 
+static_assert(sizeof(emf_merge_event_t) == 336, "mirrored by emfusion_amd/pipeline.py");
+
+static emf_merge_event_t mergeEvent(const EMFusion::MergeEvent& e) {
+    emf_merge_event_t o{};
+    o.dst = e.dst, o.src = e.src, o.frame = e.frame, o.clipped = e.clipped ? 1 : 0, o.automatic = e.automatic ? 1 : 0;
+    o.res_before = e.resBefore, o.res_after = e.resAfter;
+    std::copy(e.dstR, e.dstR + 9, o.dst_R);
+    std::copy(e.dstT, e.dstT + 3, o.dst_t);
+    std::copy(e.srcR, e.srcR + 9, o.src_R);
+    std::copy(e.srcT, e.srcT + 3, o.src_t);
+    std::copy(e.R, e.R + 9, o.R);
+    std::copy(e.t, e.t + 3, o.t);
+    std::copy(e.lo, e.lo + 3, o.lo);
+    std::copy(e.size, e.size + 3, o.size);
+    o.overlap[0] = e.overlap[0], o.overlap[1] = e.overlap[1];
+    o.record = e.record;
+    o.counts = e.counts;
+    o.color = e.color;
+    return o;
+}
+
+int emf_fusion_merge_union(const int32_t dst_lo[3], const int32_t dst_hi[3], const int32_t dst_res[3], float dst_voxel_size,
+                           const int32_t src_lo[3], const int32_t src_hi[3], const int32_t src_res[3], float src_voxel_size,
+                           const float R[9], const float t[3], float lo[3], float hi[3], int32_t* any) {
+    REQ(dst_lo);
+    REQ(dst_hi);
+    REQ(dst_res);
+    REQ(src_lo);
+    REQ(src_hi);
+    REQ(src_res);
+    REQ(R);
+    REQ(t);
+    REQ(lo);
+    REQ(hi);
+    REQ(any);
+    return guarded([&] {
+        *any = mergeUnion(dst_lo, dst_hi, dst_res, dst_voxel_size, src_lo, src_hi, src_res, src_voxel_size, R, t, lo, hi) ? 1 : 0;
+    });
+}
+
+int emf_fusion_set_merge_objects(emf_fusion_t* h, int on, double min_overlap, int64_t min_surface, double touch_m, int32_t max_res) {
+    REQ(h);
+    return guarded([&] {
+        EMFusion::MergeParams p;
+        p.minOverlap = min_overlap, p.minSurface = min_surface, p.touch = touch_m, p.maxRes = max_res;
+        h->impl->setMergeObjects(on != 0, p);
+    });
+}
+
+int emf_fusion_object_bookkeeping(emf_fusion_t* h, int32_t id, int32_t* exists, int32_t* not_exists, double* scores, int32_t capacity,
+                                  int32_t* count) {
+    REQ(h);
+    REQ(exists);
+    REQ(not_exists);
+    REQ(count);
+    if (capacity < 0 || (capacity > 0 && !scores)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_object_bookkeeping: capacity %d without a list", capacity);
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const ObjTSDF* o = h->impl->getObject(id);
+        if (!o) throw HipError("object_bookkeeping: no object " + std::to_string(id), EMF_E_ARG);
+        *exists = o->existCount(), *not_exists = o->nonExistCount();
+        const std::vector<double>& s = o->classScores();
+        *count = static_cast<int32_t>(s.size());
+        std::copy(s.begin(), s.begin() + std::min<size_t>(s.size(), static_cast<size_t>(capacity)), scores);
+    });
+}
+
+int emf_fusion_set_merged_output(emf_fusion_t* h, int on) {
+    REQ(h);
+    return guarded([&] { h->impl->setMergedOutput(on != 0); });
+}
+
+int emf_fusion_merge_objects(emf_fusion_t* h, int32_t dst, int32_t src, emf_merge_event_t* event) {
+    REQ(h);
+    return guarded([&] {
+        const EMFusion::MergeEvent e = h->impl->mergeObjects(dst, src);
+        if (event) *event = mergeEvent(e);
+    });
+}
+
+int emf_fusion_merged(emf_fusion_t* h, emf_merge_event_t* events, int32_t capacity, int32_t* count) {
+    REQ(h);
+    REQ(count);
+    if (capacity < 0 || (capacity > 0 && !events)) {
+        std::snprintf(g_err, sizeof(g_err), "emf_fusion_merged: capacity %d without a list", capacity);
+        return EMF_E_ARG;
+    }
+    return guarded([&] {
+        const std::vector<EMFusion::MergeEvent>& log = h->impl->merged();
+        *count = static_cast<int32_t>(log.size());
+        for (size_t k = 0; k < log.size() && k < static_cast<size_t>(capacity); ++k) events[k] = mergeEvent(log[k]);
+    });
+}
+
 int emf_fusion_planes(emf_fusion_t* h, const int32_t box_lo[3], const int32_t box_size[3], const emf_plane_params_t* params,
                       int32_t lo_out[3], int32_t size_out[3], float R[9], float t[3], uint32_t counters[4], uint32_t* min_votes,
                       emf_plane_t* planes, int32_t capacity, int32_t* count) {

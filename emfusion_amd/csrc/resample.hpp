@@ -238,24 +238,27 @@ __device__ __forceinline__ void rs_add64(uint64_t* q, unsigned long long v) {
     if (v) atomicAdd(reinterpret_cast<unsigned long long*>(q), v);
 }
 
+// the neutral record: no count, the bounds at (n, -1)
+template <typename Record>
+__device__ __forceinline__ Record rs_neutral(const I3& nd) {
+    Record r{};
+    r.lo[0] = nd.x, r.lo[1] = nd.y, r.lo[2] = nd.z;
+    r.hi[0] = r.hi[1] = r.hi[2] = -1;
+    return r;
+}
+
 // one lane: the neutral record before a pass
 template <typename Record>
 __global__ void rs_init_record(Record* record, I3 nd) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    Record r{};
-    r.lo[0] = nd.x, r.lo[1] = nd.y, r.lo[2] = nd.z;
-    r.hi[0] = r.hi[1] = r.hi[2] = -1;
-    *record = r;
+    *record = rs_neutral<Record>(nd);
 }
 
 // one lane: both neutral records before a colour pass
 template <typename Record>
 __global__ void rs_init_records(Record* record, I3 nd, emf_color_moved_t* colorRecord) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    Record r{};
-    r.lo[0] = nd.x, r.lo[1] = nd.y, r.lo[2] = nd.z;
-    r.hi[0] = r.hi[1] = r.hi[2] = -1;
-    *record = r;
+    *record = rs_neutral<Record>(nd);
     *colorRecord = emf_color_moved_t{0u, 0u};
 }
 
@@ -400,10 +403,10 @@ inline int rs_check_color(const char* who, ResampleColorArgs<Record>* a, uint16_
         return fail(EMF_E_ARG, "%s: a misaligned colour volume or colour record", who);
     const size_t nDst = static_cast<size_t>(a->nd.x) * a->nd.y * a->nd.z, nSrc = static_cast<size_t>(a->ns.x) * a->ns.y * a->ns.z;
     // everything else the call names: the destination's two arrays, the record, the other party's arrays, its colour
-    const void* all[8] = {a->dstTsdf, a->dstWeights, a->record, src_color};
-    size_t allBytes[8] = {nDst * sizeof(float), nDst * sizeof(float), sizeof(Record), nSrc * 8u};
+    const void* all[12] = {a->dstTsdf, a->dstWeights, a->record, src_color};
+    size_t allBytes[12] = {nDst * sizeof(float), nDst * sizeof(float), sizeof(Record), nSrc * 8u};
     int n = 4;
-    for (int k = 0; k < nOthers && n < 8; ++k) all[n] = others[k], allBytes[n++] = otherBytes[k];
+    for (int k = 0; k < nOthers && n < 12; ++k) all[n] = others[k], allBytes[n++] = otherBytes[k];
     for (int k = 0; k < n; ++k) {
         if (all[k] == nullptr) continue;
         if (rs_overlap(dst_color, nDst * 8u, all[k], allBytes[k]))

@@ -1,11 +1,13 @@
 // volume_transfer.hip -- the passes that hand the signed-distance band of one volume to another through a rigid pose, in
-// place in the DESTINATION (include/emf_hip.h "Absorbing a volume" and "Lifting a volume").
+// place in the DESTINATION (include/emf_hip.h "Absorbing a volume", "Lifting a volume" and "Merging a volume", DESIGN.md
+// 5.29, 5.30 and 5.32).
 //   k_ab_absorb   the band of the SOURCE, fused into the destination by the destination's running average.
+//   k_mg_merge    the same into an object: the (fg, bg) counts of a fused voxel follow the band (MergePolicy).
 //   k_lf_seed     the destination takes the source's band only where it has no observation of its own.
 //   k_lf_release  the destination gives up the band voxels that a claimant holds.
 // One workgroup per 32 x 8 x 8 destination tile that meets the box, 256 lanes = 32 along x, 8 rows; a lane walks the tile's
 // z planes with the x and y parts of the three pose rows hoisted.  A wave whose lanes all lie outside the box leaves.
-// Absorb and seed are one walk (rs_transfer) under two policies resolved at compile time: per voxel what the policy asks
+// Absorb, merge and seed are one walk (rs_transfer) under three policies resolved at compile time: per voxel what the policy asks
 // of the destination first, then the sample point and what the source holds there (rs_source of resample.hpp: the
 // outside rule, 8 + 8 dependent gathers, the mask byte), then the policy's band rule and store.  The release reads its
 // own weight and tsdf first -- EMPTY and FREE cost 8 bytes and no transform -- then the sample point, the outside rule
@@ -26,6 +28,7 @@ namespace {
 static_assert(sizeof(emf_absorb_t) == 88 && sizeof(emf_absorb_source_t) == 56, "mirrored by emfusion_amd/_lib.py");
 static_assert(sizeof(emf_seed_t) == 88 && sizeof(emf_release_t) == 80, "mirrored by emfusion_amd/_lib.py");
 static_assert(sizeof(emf_color_moved_t) == 16 && sizeof(uint2) == 4 * sizeof(uint16_t), "mirrored by emfusion_amd/_lib.py");
+static_assert(sizeof(emf_merge_counts_t) == 16 && sizeof(float2) == 2 * sizeof(float), "mirrored by emfusion_amd/_lib.py");
 
 // the arguments of a pass: with colour, the colour volumes, the colour record and the cap behind the plain ones
 template <typename Record, bool Color>
@@ -65,6 +68,12 @@ struct AbsorbPolicy {
 
     __device__ __forceinline__ bool wants(const Args&, size_t) { return true; }
     __device__ __forceinline__ bool take(const Args& a, size_t v, const V3& q, float s, const float (&w)[8]) {
+        return take(a, v, q, s, w, [](bool) {});
+    }
+    // between(fresh): what a policy built on this one does to a FUSED voxel once its band is written, before its colour
+    // follows; fresh: the voxel had no observation of its own
+    template <typename Between>
+    __device__ __forceinline__ bool take(const Args& a, size_t v, const V3& q, float s, const float (&w)[8], Between between) {
         if (!(fabsf(s) < 1.f)) {  // "at least one source truncation away": no value the destination can fuse
             cSat += 1u;
             return false;
@@ -73,7 +82,8 @@ struct AbsorbPolicy {
         const float wo = rs_min8(w);
         const float pw = a.dstWeights[v], pt = a.dstTsdf[v];
         float nt, nw;
-        if (!(pw > 0.f)) {  // a select: whatever an unseen voxel holds goes nowhere
+        const bool fresh = !(pw > 0.f);
+        if (fresh) {  // a select: whatever an unseen voxel holds goes nowhere
             nt = u;
             nw = fminf(wo, a.maxWeight);
             cFresh += 1u;
@@ -85,9 +95,9 @@ struct AbsorbPolicy {
         if (!(nt > 0.f)) cSolid += 1u;
         if (__float_as_uint(nt) != __float_as_uint(pt)) a.dstTsdf[v] = nt;
         if (__float_as_uint(nw) != __float_as_uint(pw)) a.dstWeights[v] = nw;
+        between(fresh);
         if constexpr (Color) {
             const uint2 S = rs_color_source(a.srcColor, q, a.ns.y, static_cast<size_t>(a.ns.x));
-            const bool fresh = !(pw > 0.f);
             if (rs_color_weight(S) == 0u) {  // UNCOLOURED: an unobserved voxel's entry is not evidence, any other stays
                 color.cUncol += 1u;
                 if (fresh) a.dstColor[v] = make_uint2(0u, 0u);
@@ -162,6 +172,48 @@ struct SeedPolicy {
     }
 };
 
+// What a merge is handed on top of an absorption: the (fg, bg) count pairs of both volumes, a pair = one 8-byte word, and
+// the record of the pairs that came out as foreground.
+template <bool Color>
+struct MergeArgs : TransferArgs<emf_absorb_t, Color> {
+    float2* dstFgbg;
+    const float2* srcFgbg;
+    emf_merge_counts_t* counts;
+};
+
+// The destination is an object: the absorption's band rule, unchanged, and on the FUSED path alone the voxel's count
+// pair follows the band -- the source's pair at the nearest voxel replaces that of a FRESH voxel and is added to any
+// other, one float32 sum per count.
+template <bool Color>
+struct MergePolicy {
+    using Record = emf_absorb_t;
+    using Args = MergeArgs<Color>;
+    AbsorbPolicy<Color> band;
+    unsigned cFg = 0u, cGained = 0u;
+
+    __device__ __forceinline__ bool wants(const Args&, size_t) { return true; }
+    __device__ __forceinline__ bool take(const Args& a, size_t v, const V3& q, float s, const float (&w)[8]) {
+        return band.take(a, v, q, s, w, [&](bool fresh) {
+            const float2 S = a.srcFgbg[rs_nearest(q, a.ns.y, static_cast<size_t>(a.ns.x))];
+            const float2 D = a.dstFgbg[v];  // read once, as one word, before anything of it is written
+            const float2 N = fresh ? S : make_float2(__fadd_rn(D.x, S.x), __fadd_rn(D.y, S.y));
+            if (N.x > N.y) {
+                cFg += 1u;
+                if (fresh || !(D.x > D.y)) cGained += 1u;
+            }
+            if (__float_as_uint(N.x) != __float_as_uint(D.x) || __float_as_uint(N.y) != __float_as_uint(D.y)) a.dstFgbg[v] = N;
+        });
+    }
+    __device__ __forceinline__ void reduce(bool any) {
+        band.reduce(any);
+        if (any) cFg = wave_reduce<OpAdd>(cFg), cGained = wave_reduce<OpAdd>(cGained);
+    }
+    __device__ __forceinline__ unsigned long long commit(const Args& a, bool any) const {
+        if (any) rs_add64(&a.counts->foreground, cFg), rs_add64(&a.counts->gained, cGained);
+        return band.commit(a, any);
+    }
+};
+
 template <typename Policy>
 __device__ __forceinline__ void rs_transfer(const typename Policy::Args& a) {
     const RsLane ln = rs_lane(a.t0, a.ntx, a.nty, a.lo, a.hi);
@@ -220,6 +272,25 @@ __global__ __launch_bounds__(kRsBlock) void k_lf_seed(const ResampleArgs<emf_see
 __global__ __launch_bounds__(kRsBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_lf_seed_color(
     const ResampleColorArgs<emf_seed_t> a) {
     rs_transfer<SeedPolicy<true>>(a);
+}
+
+// The merge carries one more gather and one more 8-byte word per fused voxel than the absorption; both variants are held
+// to the absorption's 8 waves per SIMD, without scratch.
+__global__ __launch_bounds__(kRsBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_mg_merge(const MergeArgs<false> a) {
+    rs_transfer<MergePolicy<false>>(a);
+}
+
+__global__ __launch_bounds__(kRsBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_mg_merge_color(const MergeArgs<true> a) {
+    rs_transfer<MergePolicy<true>>(a);
+}
+
+// one lane: the neutral records before a merge, the colour record among them where there is one
+template <bool Color>
+__global__ void k_mg_init(emf_absorb_t* record, I3 nd, emf_merge_counts_t* counts, emf_color_moved_t* colorRecord) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    *record = rs_neutral<emf_absorb_t>(nd);
+    *counts = emf_merge_counts_t{0u, 0u};
+    if constexpr (Color) *colorRecord = emf_color_moved_t{0u, 0u};
 }
 
 // the source is the claimant: its mask (or NULL: everything inside its cube), its resolution and voxel size
@@ -333,6 +404,48 @@ int check_release(const char* who, ResampleArgs<emf_release_t>* a, unsigned* til
     return EMF_OK;
 }
 
+// mergeVolume and mergeVolumeColor: the source's mask is there; every check of absorbVolume; with colour those of the
+// colour arguments, the count arrays among the other arrays of the call; then the count arrays and their record -- there,
+// 8-byte aligned, and no array the call writes shares a byte with any other array of the call -- then the launch.
+template <bool Color>
+int merge_volume(const char* who, void (*pass)(MergeArgs<Color>), float* dst_tsdf, float* dst_weights, float* dst_fgbg, uint16_t* dst_color,
+                 const int32_t* dst_res, float dst_voxel_size, float dst_truncdist, float max_weight, const emf_absorb_source_t* source,
+                 const float* src_fgbg, const uint16_t* src_color, const float* R, const float* t, const int32_t* box_lo,
+                 const int32_t* box_size, emf_absorb_t* record_dev, emf_merge_counts_t* counts_dev, emf_color_moved_t* color_record_dev,
+                 emf_stream_t stream) {
+    MergeArgs<Color> a{};
+    unsigned tiles = 0;
+    if (source && !source->fgVolMask)
+        return fail(EMF_E_ARG, "%s: the source has no fgVolMask (what the source itself calls background is no evidence)", who);
+    EMF_TRY(rs_check_transfer(who, static_cast<ResampleArgs<emf_absorb_t>*>(&a), &tiles, dst_tsdf, dst_weights, dst_res, dst_voxel_size,
+                              dst_truncdist, max_weight, source, R, t, box_lo, box_size, record_dev));
+    if (!dst_fgbg || !src_fgbg || !counts_dev) return fail(EMF_E_ARG, "%s: a count volume or the count record is NULL", who);
+    if ((reinterpret_cast<uintptr_t>(dst_fgbg) | reinterpret_cast<uintptr_t>(src_fgbg) | reinterpret_cast<uintptr_t>(counts_dev)) & 7u)
+        return fail(EMF_E_ARG, "%s: a misaligned count volume or count record", who);
+    const size_t nDst = static_cast<size_t>(a.nd.x) * a.nd.y * a.nd.z, nSrc = static_cast<size_t>(a.ns.x) * a.ns.y * a.ns.z;
+    // the first five are written, the rest only read
+    const void* all[11] = {dst_tsdf, dst_weights, record_dev, dst_fgbg, counts_dev, source->tsdf, source->weights, source->fgVolMask,
+                           source->unseenTiles, src_fgbg, Color ? src_color : nullptr};
+    const size_t allBytes[11] = {nDst * sizeof(float), nDst * sizeof(float), sizeof(emf_absorb_t), nDst * 8u, sizeof(emf_merge_counts_t),
+                                 nSrc * sizeof(float), nSrc * sizeof(float), nSrc, emf_hip_unseenTileBytes(source->res), nSrc * 8u,
+                                 Color ? nSrc * 8u : 0u};
+    for (int w = 0; w < 5; ++w)
+        for (int k = w + 1; k < 11; ++k)
+            if (all[k] != nullptr && rs_overlap(all[w], allBytes[w], all[k], allBytes[k]))
+                return fail(EMF_E_ARG, "%s: an array the call writes overlaps another array of the call", who);
+    emf_color_moved_t* colorRecord = nullptr;
+    if constexpr (Color) {
+        EMF_TRY(rs_check_color(who, &a, dst_color, src_color, color_record_dev, all + 3, allBytes + 3, 7));
+        a.capq = rs_color_cap(max_weight);
+        colorRecord = color_record_dev;
+    }
+    a.dstFgbg = reinterpret_cast<float2*>(dst_fgbg), a.srcFgbg = reinterpret_cast<const float2*>(src_fgbg), a.counts = counts_dev;
+    const hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(k_mg_init<Color>, dim3(1), dim3(64), 0, s, a.record, a.nd, a.counts, colorRecord);
+    if (tiles != 0u) hipLaunchKernelGGL(pass, dim3(tiles), dim3(kRsBlock), 0, s, a);
+    return launch_status(who);
+}
+
 }  // namespace
 }  // namespace emf_hip
 
@@ -399,6 +512,24 @@ int emf_hip_releaseVolumeColor(float* dst_tsdf, float* dst_weights, uint16_t* ds
     const size_t otherBytes[1] = {static_cast<size_t>(a.ns.x) * a.ns.y * a.ns.z};
     EMF_TRY(rs_check_color("releaseVolumeColor", &a, dst_color, nullptr, color_record_dev, others, otherBytes, 1));
     return rs_launch("releaseVolumeColor", k_lf_release<true>, a, tiles, stream);
+}
+
+int emf_hip_mergeVolume(float* dst_tsdf, float* dst_weights, float* dst_fgbg, const int32_t dst_res[3], float dst_voxel_size,
+                        float dst_truncdist, float max_weight, const emf_absorb_source_t* source, const float* src_fgbg, const float R[9],
+                        const float t[3], const int32_t box_lo[3], const int32_t box_size[3], emf_absorb_t* record_dev,
+                        emf_merge_counts_t* counts_dev, emf_stream_t stream) {
+    return merge_volume<false>("mergeVolume", k_mg_merge, dst_tsdf, dst_weights, dst_fgbg, nullptr, dst_res, dst_voxel_size, dst_truncdist,
+                               max_weight, source, src_fgbg, nullptr, R, t, box_lo, box_size, record_dev, counts_dev, nullptr, stream);
+}
+
+int emf_hip_mergeVolumeColor(float* dst_tsdf, float* dst_weights, float* dst_fgbg, uint16_t* dst_color, const int32_t dst_res[3],
+                             float dst_voxel_size, float dst_truncdist, float max_weight, const emf_absorb_source_t* source,
+                             const float* src_fgbg, const uint16_t* src_color, const float R[9], const float t[3], const int32_t box_lo[3],
+                             const int32_t box_size[3], emf_absorb_t* record_dev, emf_merge_counts_t* counts_dev,
+                             emf_color_moved_t* color_record_dev, emf_stream_t stream) {
+    return merge_volume<true>("mergeVolumeColor", k_mg_merge_color, dst_tsdf, dst_weights, dst_fgbg, dst_color, dst_res, dst_voxel_size,
+                              dst_truncdist, max_weight, source, src_fgbg, src_color, R, t, box_lo, box_size, record_dev, counts_dev,
+                              color_record_dev, stream);
 }
 
 }  // extern "C"

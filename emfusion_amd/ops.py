@@ -2225,9 +2225,10 @@ def _transfer_result(record, out, crec, color_out):
     return rec, (crec.numpy()[0] if color_out is None else color_out)
 
 
-def _transfer_volume(entry, dtype, dst, src, pose, box, out, lib, stream, color_out=None):
-    """absorb_volume and seed_volume: emf_hip_<entry> of a whole source into dst; emf_hip_<entry>Color where dst has a
-    colour volume."""
+def _transfer_volume(entry, dtype, dst, src, pose, box, out, lib, stream, color_out=None, counts=None):
+    """absorb_volume, seed_volume and merge_volume: emf_hip_<entry> of a whole source into dst; emf_hip_<entry>Color where
+    dst has a colour volume.  counts (merge_volume alone): (counts_out,) -- the call takes dst["fgbg"] and src["fgbg"],
+    (Nz, Ny, Nx, 2) f32, behind the weights and the source, and the count record behind the record."""
     stsdf, sweights = _vol(src["tsdf"], np.float32), _vol(src["weights"], np.float32)
     assert sweights.shape == stsdf.shape
     s = _lib.EmfAbsorbSource()
@@ -2241,20 +2242,29 @@ def _transfer_volume(entry, dtype, dst, src, pose, box, out, lib, stream, color_
     s.voxelSize, s.truncdist = float(np.float32(src["voxel_size"])), float(np.float32(src["truncdist"]))
     d, b, record = _transfer_call(dst, tuple(s.res), src["voxel_size"], pose, box, out, dtype)
     color, crec = _transfer_color(dst, color_out)
-    if color is None:
-        check("emf_hip_" + entry,
-              getattr(_L if lib is None else lib, "emf_hip_" + entry)(
-                  *d, float(np.float32(dst["truncdist"])), float(np.float32(dst["max_weight"])), C.byref(s), _f(pose[0], 9),
-                  _f(pose[1], 3), *b, _ptr(record), _stream(stream)))
-    else:
+    arrays, source, records = [d[0], d[1]], [C.byref(s)], [_ptr(record)]
+    cnt = None
+    if counts is not None:
+        dfgbg, sfgbg = _vol(dst["fgbg"], np.float32, 2), _vol(src["fgbg"], np.float32, 2)
+        assert dfgbg.shape[:3] == dst["tsdf"].shape and sfgbg.shape[:3] == stsdf.shape
+        cnt = DeviceArray((1,), MERGE_COUNTS_DTYPE) if counts[0] is None else counts[0]
+        assert cnt.dtype == MERGE_COUNTS_DTYPE and cnt.shape[0] >= 1
+        arrays.append(_ptr(dfgbg)), source.append(_ptr(sfgbg)), records.append(_ptr(cnt))
+    if color is not None:
         scolor = src.get("color")
         if scolor is not None:
             assert _vol(scolor, np.uint16, 4).shape[:3] == stsdf.shape
-        check("emf_hip_" + entry + "Color",
-              getattr(_L if lib is None else lib, "emf_hip_" + entry + "Color")(
-                  d[0], d[1], _ptr(color), d[2], d[3], float(np.float32(dst["truncdist"])), float(np.float32(dst["max_weight"])),
-                  C.byref(s), _ptr(scolor), _f(pose[0], 9), _f(pose[1], 3), *b, _ptr(record), _ptr(crec), _stream(stream)))
-    return _transfer_result(record, out, crec, color_out)
+        arrays.append(_ptr(color)), source.append(_ptr(scolor)), records.append(_ptr(crec))
+        entry += "Color"
+    check("emf_hip_" + entry,
+          getattr(_L if lib is None else lib, "emf_hip_" + entry)(
+              *arrays, d[2], d[3], float(np.float32(dst["truncdist"])), float(np.float32(dst["max_weight"])), *source, _f(pose[0], 9),
+              _f(pose[1], 3), *b, *records, _stream(stream)))
+    result = _transfer_result(record, out, crec, color_out)
+    if counts is None:
+        return result
+    cnt = cnt.numpy()[0] if counts[0] is None else cnt
+    return (result, cnt) if crec is None else (result[0], cnt, result[1])
 
 
 def absorb_volume(dst, src, pose, box=None, out=None, lib=None, stream=None, color_out=None):
@@ -2273,6 +2283,24 @@ def absorb_volume(dst, src, pose, box=None, out=None, lib=None, stream=None, col
     (record, colour record), the second of COLOR_MOVED_DTYPE (colored + uncolored == fused), or with color_out= (a device
     array of at least one such record) that array in its place.  Without dst["color"] the call is what it was."""
     return _transfer_volume("absorbVolume", ABSORB_DTYPE, dst, src, pose, box, out, lib, stream, color_out)
+
+
+# ---- merging a volume (include/emf_hip.h "Merging a volume", DESIGN.md 5.32) ---------------------------------------
+
+MERGE_COUNTS_DTYPE = np.dtype(_lib.MERGE_COUNTS_DTYPE)
+assert MERGE_COUNTS_DTYPE.itemsize == 16
+
+
+def merge_volume(dst, src, pose, box=None, out=None, lib=None, stream=None, counts_out=None, color_out=None):
+    """emf_hip_mergeVolume: absorb_volume into an OBJECT -- dst and src as there, each with fgbg= as well, a (Nz, Ny, Nx, 2)
+    f32 device volume of interleaved (fg, bg) counts, and src["fg_mask"] required.  tsdf, weights and the record are
+    absorb_volume's byte for byte; the count pair of every fused voxel becomes the source's pair at the nearest source
+    voxel where the voxel had no observation, and the sum of both otherwise.  Returns (record, counts), counts a 0-d numpy
+    array of MERGE_COUNTS_DTYPE (foreground: fused voxels whose new pair has fg > bg; gained: those of them that did not
+    before), or with out= / counts_out= (device arrays of at least one record) those arrays in their places.
+    With dst["color"]: emf_hip_mergeVolumeColor -- the colour entries as absorb_volume carries them -- and the triple
+    (record, counts, colour record); color_out= as there."""
+    return _transfer_volume("mergeVolume", ABSORB_DTYPE, dst, src, pose, box, out, lib, stream, color_out, counts=(counts_out,))
 
 
 # ---- lifting a volume (include/emf_hip.h "Lifting a volume", DESIGN.md 5.30) ---------------------------------------

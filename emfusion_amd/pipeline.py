@@ -192,6 +192,12 @@ def load() -> C.CDLL:
         "emf_fusion_absorbed": [vp, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
         "emf_fusion_absorbed_colors": [vp, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
         "emf_fusion_set_absorbed_output": [vp, C.c_int],
+        "emf_fusion_merge_union": [ip, ip, ip, C.c_float, ip, ip, ip, C.c_float, fp, fp, fp, fp, ip],
+        "emf_fusion_set_merge_objects": [vp, C.c_int, C.c_double, C.c_int64, C.c_double, C.c_int32],
+        "emf_fusion_merge_objects": [vp, C.c_int32, C.c_int32, C.c_void_p],
+        "emf_fusion_set_merged_output": [vp, C.c_int],
+        "emf_fusion_object_bookkeeping": [vp, C.c_int32, ip, ip, C.POINTER(C.c_double), C.c_int32, ip],
+        "emf_fusion_merged": [vp, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
         "emf_fusion_set_lift_objects": [vp, C.c_int],
         "emf_fusion_lift_object": [vp, C.c_int32, C.c_void_p],
         "emf_fusion_lifted": [vp, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
@@ -729,6 +735,53 @@ def lifted_line(event, color=None):
         [int(v) for v in r["lo"]] + [int(v) for v in r["hi"]]
     floats = []
     for k in ("seed_R", "seed_t", "release_R", "release_t"):
+        floats += [float(v) for v in np.asarray(event[k], np.float32).reshape(-1)]
+    return " ".join([str(int(v)) for v in ints] + ["%.9g" % v for v in floats])
+
+
+def _merge_event_dtype():
+    """emf_merge_event_t (include/emf_fusion.h): 336 bytes."""
+    from . import _lib as hip
+    d = np.dtype([("dst", "<i4"), ("src", "<i4"), ("frame", "<i4"), ("clipped", "<i4"), ("automatic", "<i4"), ("res_before", "<i4"),
+                  ("res_after", "<i4"), ("reserved", "<i4"), ("dst_R", "<f4", 9), ("dst_t", "<f4", 3), ("src_R", "<f4", 9),
+                  ("src_t", "<f4", 3), ("R", "<f4", 9), ("t", "<f4", 3), ("lo", "<i4", 3), ("size", "<i4", 3), ("overlap", "<f8", 2),
+                  ("record", np.dtype(hip.ABSORB_DTYPE)), ("counts", np.dtype(hip.MERGE_COUNTS_DTYPE)),
+                  ("color", np.dtype(hip.COLOR_MOVED_DTYPE))])
+    assert d.itemsize == 336
+    return d
+
+
+def merge_union(dst_bounds, dst_res, dst_voxel_size, src_bounds, src_res, src_voxel_size, pose):
+    """emf_fusion_merge_union, on the host without a device: the box (lo, hi) in metres of the
+    destination's volume frame that holds the bands of both objects -- what merge_objects hands to the destination's
+    resize.  *_bounds: (lo, hi), inclusive voxel bounds of an object's observed solid band (object_shapes() moments; hi[0] <
+    0: no solid voxel); pose = (R, t), f32, the destination's volume frame <- the source's.  Float64 in a fixed operation
+    order, rounded to f32 once.  None where neither object has a solid voxel."""
+    def i3(v):
+        return (C.c_int32 * 3)(*[int(x) for x in v])
+    lo, hi, any_ = np.zeros(3, np.float32), np.zeros(3, np.float32), C.c_int32(0)
+    p = C.POINTER(C.c_float)
+    _check("emf_fusion_merge_union",
+           load().emf_fusion_merge_union(i3(dst_bounds[0]), i3(dst_bounds[1]), i3(dst_res), float(np.float32(dst_voxel_size)),
+                                         i3(src_bounds[0]), i3(src_bounds[1]), i3(src_res), float(np.float32(src_voxel_size)),
+                                         _farr(pose[0], 9), _farr(pose[1], 3), lo.ctypes.data_as(p), hi.ctypes.data_as(p),
+                                         C.byref(any_)))
+    return (lo, hi) if any_.value else None
+
+
+def merged_line(event):
+    """One line of a merge log (without the newline) from an event of Fusion.merged(): dst src frame clipped automatic
+    res_before res_after, the box (lo, size), the eight counts and the bounds of the fused voxels, foreground gained, colored
+    uncolored, then the two overlaps, the destination's pose R (9) t (3), the source's, and the pose used R (9) t (3), all
+    in %.9g."""
+    r = event["record"]
+    ints = [event["dst"], event["src"], event["frame"], int(event["clipped"]), int(event["automatic"]), event["res_before"],
+            event["res_after"], *event["lo"], *event["size"]] + \
+        [int(r[k]) for k in ("visited", "outside", "unknown", "masked", "saturated", "fused", "fresh", "solid")] + \
+        [int(v) for v in r["lo"]] + [int(v) for v in r["hi"]] + \
+        [int(event["counts"]["foreground"]), int(event["counts"]["gained"]), int(event["color"]["colored"]), int(event["color"]["uncolored"])]
+    floats = [float(v) for v in event["overlap"]]
+    for k in ("dst_R", "dst_t", "src_R", "src_t", "R", "t"):
         floats += [float(v) for v in np.asarray(event[k], np.float32).reshape(-1)]
     return " ".join([str(int(v)) for v in ints] + ["%.9g" % v for v in floats])
 
@@ -2084,6 +2137,73 @@ class Fusion:
         _check("emf_fusion_lifted_colors", load().emf_fusion_lifted_colors(self._h, records.ctypes.data, n.value, C.byref(n)))
         return [(records[2 * k].copy(), records[2 * k + 1].copy()) for k in range(n.value)]
 
+    @staticmethod
+    def _merge_event(e):
+        out = dict(dst=int(e["dst"]), src=int(e["src"]), frame=int(e["frame"]), clipped=bool(e["clipped"]),
+                   automatic=bool(e["automatic"]), res_before=int(e["res_before"]), res_after=int(e["res_after"]),
+                   lo=tuple(int(v) for v in e["lo"]), size=tuple(int(v) for v in e["size"]), overlap=e["overlap"].copy(),
+                   record=e["record"].copy(), counts=e["counts"].copy(), color=e["color"].copy())
+        for k in ("dst_R", "src_R", "R"):
+            out[k] = e[k].reshape(3, 3).copy()
+        for k in ("dst_t", "src_t", "t"):
+            out[k] = e[k].copy()
+        return out
+
+    def set_merge_objects(self, on=True, min_overlap=0.5, min_surface=64, touch=None, max_res=256):
+        """Merge DUPLICATE objects automatically.  Sticky, off by default; the parameters are kept either
+        way (merge_objects grows up to max_res).  On: at the end of every mask frame, after the clean-up, with at least two
+        live objects, one contact-probe launch over all ordered object pairs (object_contacts without the background);
+        overlap(a -> b) = touching / surface of the record; a pair qualifies when max(overlap(a -> b), overlap(b -> a)) >=
+        min_overlap and both surfaces hold at least min_surface voxels; qualifying pairs are merged in descending overlap,
+        ties to the smaller pair of ids, the older object (smaller id) the destination, an object at most once per frame.
+        THE DEFAULTS ARE POLICY, NOT MEASUREMENTS: min_overlap 0.5, min_surface 64, touch None = half a truncation
+        distance (metres otherwise), max_res 256.
+        IT FINDS DUPLICATES.  Two halves that merely abut reach no sensible overlap: merge them with merge_objects or by
+        a rule of your own on object_contacts().  Neither the switch nor the log is written to a checkpoint.  Off: no
+        launch, no output byte, no checkpoint byte changes.  Refused on the sharded path."""
+        _check("emf_fusion_set_merge_objects",
+               load().emf_fusion_set_merge_objects(self._h, int(bool(on)), float(min_overlap), int(min_surface),
+                                                   -1.0 if touch is None else float(touch), int(max_res)))
+
+    def merge_objects(self, dst, src):
+        """Merge the LIVE object src into the LIVE object dst now, between frames: the repair for one
+        physical thing that ended up with two volumes.  GROWS dst's cube until it holds src's band (the resize of the union
+        of both bands, merge_union; set_merge_objects' max_res caps the grown resolution per axis -- 256, a policy value,
+        not a measurement -- and beyond it dst is not grown and `clipped` says so), MERGES src's band into dst through the relative pose and
+        dst's running average, the (fg, bg) counts of every fused voxel following the band (ops.merge_volume; with colour
+        in a coloured session), and sums the existence counts and the class scores.  dst keeps its id and its tracking
+        state; src is deleted and NEITHER ITS MESH NOR ITS exp_vols COPY IS KEPT: its geometry lives on in dst.
+
+        WHAT IT DOES NOT DO: the poses are taken as they are -- the volumes are not registered first, a drifted duplicate
+        merges blurred; it carries the band, not the free space around it.
+        Returns the event: dict(dst, src, frame, clipped, automatic (False here), res_before, res_after, dst_R, dst_t, src_R, src_t
+        (the poses used, dst's after the growth), R, t (src volume frame <- dst volume frame), lo, size (the box of dst's
+        voxels), overlap, record (ops.ABSORB_DTYPE), counts (ops.MERGE_COUNTS_DTYPE), color (ops.COLOR_MOVED_DTYPE)).  Id
+        0, an unknown id, dst == src and an object this rank does not own raise; refused on the sharded path."""
+        e = np.zeros((), _merge_event_dtype())
+        _check("emf_fusion_merge_objects", load().emf_fusion_merge_objects(self._h, int(dst), int(src), e.ctypes.data))
+        return self._merge_event(e)
+
+    def object_bookkeeping(self, obj_id):
+        """(exists, not exists, class scores) of the live object obj_id: the frames it was matched and was not, and its
+        accumulated class scores (a float64 array, empty before any score) -- what a merge sums."""
+        ex, non, n = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        fn = load().emf_fusion_object_bookkeeping
+        _check("emf_fusion_object_bookkeeping", fn(self._h, int(obj_id), C.byref(ex), C.byref(non), None, 0, C.byref(n)))
+        scores = np.zeros(max(n.value, 1), np.float64)
+        _check("emf_fusion_object_bookkeeping",
+               fn(self._h, int(obj_id), C.byref(ex), C.byref(non), scores.ctypes.data_as(C.POINTER(C.c_double)), n.value, C.byref(n)))
+        return ex.value, non.value, scores[:n.value]
+
+    def merged(self):
+        """The session's log of merges, oldest first: a list of the events of merge_objects().  Session state only:
+        reset() and a loaded checkpoint start it empty, and it is never written to a checkpoint."""
+        n = C.c_int32(0)
+        _check("emf_fusion_merged", load().emf_fusion_merged(self._h, None, 0, C.byref(n)))
+        events = np.zeros(max(n.value, 1), _merge_event_dtype())
+        _check("emf_fusion_merged", load().emf_fusion_merged(self._h, events.ctypes.data, n.value, C.byref(n)))
+        return [self._merge_event(events[k]) for k in range(n.value)]
+
     def planes(self, box=None, size=None, k=15, angle=20.0, separation=None, bin=None, band=None, min_votes=None, refine=1,
                up_hint=None, floor_angle=30.0, kind_angle=10.0, max_planes=64, labels=False, patches=False, patch_reach=1,
                patch_min_voxels=None):
@@ -2590,7 +2710,7 @@ class Fusion:
                      ground_up=None, ground_cell=None, ground_bin=None, ground_band=(-1.5, 0.5), ground_robot_height=0.3,
                      ground_max_step=0.05, exp_planes=False, planes_angle=20.0, planes_min_votes=None,
                      exp_plane_patches=False, plane_patch_reach=1, plane_patch_min=None, exp_object_contacts=False,
-                     contact_touch=None, exp_absorbed=False, exp_lifted=False):
+                     contact_touch=None, exp_absorbed=False, exp_lifted=False, exp_merged=False):
         """Reference EMFusion::setupOutput: log on; exp_vols keeps deleted objects' volumes too; exp_frame_meshes meshes
         the background and every shown object at the end of every frame for write_results' frame_meshes/ (refused on
         the sharded path); exp_world_mesh: write_results also writes world.ply, write_mesh of world_mesh();
@@ -2629,7 +2749,9 @@ class Fusion:
         exp_absorbed: write_results also writes absorbed.txt, after a comment line one line per event of absorbed():
         absorbed_line() of it (include/emf_fusion.h emf_fusion_set_absorbed_output).
         exp_lifted: write_results also writes lifted.txt, after a comment line one line per event of lifted():
-        lifted_line() of it (include/emf_fusion.h emf_fusion_set_lifted_output)."""
+        lifted_line() of it (include/emf_fusion.h emf_fusion_set_lifted_output).
+        exp_merged: write_results also writes merged.txt, after a comment line one line per event of merged():
+        merged_line() of it (include/emf_fusion.h emf_fusion_set_merged_output)."""
         if contact_touch is not None and not exp_object_contacts:
             raise ValueError("setup_output: contact_touch is the threshold of contacts.txt and needs exp_object_contacts")
         if exp_plan_shortcut and not exp_plan:
@@ -2676,6 +2798,8 @@ class Fusion:
             _check("emf_fusion_set_absorbed_output", load().emf_fusion_set_absorbed_output(self._h, 1))
         if exp_lifted:  # off: no new call
             _check("emf_fusion_set_lifted_output", load().emf_fusion_set_lifted_output(self._h, 1))
+        if exp_merged:  # off: no new call
+            _check("emf_fusion_set_merged_output", load().emf_fusion_set_merged_output(self._h, 1))
         if exp_ground_map:  # off: no new call
             up = None if ground_up is None or up_floor else np.ascontiguousarray(ground_up, np.float64).reshape(3)
             _check("emf_fusion_set_ground_output",

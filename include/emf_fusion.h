@@ -567,6 +567,67 @@ int emf_fusion_lift_object(emf_fusion_t* h, int32_t id, emf_lift_event_t* event)
 int emf_fusion_lifted(emf_fusion_t* h, emf_lift_event_t* events, int32_t capacity, int32_t* count);
 int emf_fusion_lifted_colors(emf_fusion_t* h, emf_color_moved_t* records, int32_t capacity, int32_t* count);
 int emf_fusion_set_lifted_output(emf_fusion_t* h, int on);
+/* Merging an object into another object (include/emf_hip.h "Merging a volume"; new behaviour, opt-in): the
+ * repair for one physical thing that ended up with two volumes -- an instance segmenter that cut it into two masks, a
+ * re-detection from its other side, a drifted track.  With the switch off and no call nothing of a session changes.
+ *   set_merge_objects  sticky, off by default; the parameters are kept either way.  On: at the end of every mask frame,
+ *                   after the clean-up, with at least two live objects, one emf_hip_contactProbe launch over all ordered
+ *                   object pairs (no background); overlap(a -> b) = touching / surface of the record, a float64 quotient;
+ *                   a pair qualifies when max(overlap(a -> b), overlap(b -> a)) >= min_overlap and both surfaces hold at
+ *                   least min_surface voxels; qualifying pairs are merged in descending overlap, ties to the smaller pair
+ *                   of ids, the older object (smaller id) the destination, an object at most once per frame.  min_overlap
+ *                   0.5, min_surface 64, touch_m < 0 = half a truncation distance (through contact_touch) and max_res 256
+ *                   ARE POLICY, NOT MEASUREMENTS.  IT FINDS DUPLICATES: two halves that merely abut reach no sensible
+ *                   overlap; they are merged by merge_objects or by a caller's own rule on object_contacts.  EMF_E_ARG: a
+ *                   NaN, min_surface < 0, max_res < 2; on the sharded path (on).
+ *   merge_union     needs no device and no handle: the box (metres, the destination's volume frame) that holds the bands
+ *                   of both objects, from their inclusive voxel bounds (emf_shape_moments_t lo, hi; hi[0] < 0: none), their
+ *                   resolutions and voxel sizes and (R, t) = the destination's volume frame <- the source's.  Float64 in
+ *                   the fixed operation order core/EMFusion.hpp states for mergeUnion, rounded to f32 once.  *any == 0, lo
+ *                   and hi untouched, where neither object has a solid voxel.
+ *   merge_objects   between frames: GROWS the destination's cube until it holds the source's band (the existing resize of
+ *                   the union above; set_merge_objects' max_res caps the grown resolution per axis -- 256, a policy value,
+ *                   the largest object volume of BASELINE.json's configs; beyond it the destination is not grown and
+ *                   `clipped` says so), MERGES the source's band into it through absorb_pose(destination, source) as they are -- the
+ *                   volumes are not registered first, a drifted duplicate merges blurred -- the (fg, bg) counts of every
+ *                   fused voxel following the band (emf_hip_mergeVolume; emf_hip_mergeVolumeColor in a coloured session),
+ *                   and sums the BOOKKEEPING: existence counts and class scores.  The destination keeps its id and its
+ *                   tracking state; the source is deleted and NEITHER ITS MESH NOR ITS exp_vols COPY IS KEPT: its
+ *                   geometry lives on in the destination.  `event` may be NULL.  EMF_E_ARG: id 0, an unknown id, dst ==
+ *                   src, an object of another rank, the sharded path.
+ *   merged          the session's log, oldest first: the first min(capacity, *count) events; *count is the number logged.
+ *                   Not in a checkpoint; reset() and a loaded checkpoint start it empty.
+ *   set_merged_output  setup_output's exp_merged: emf_fusion_write_results also writes merged.txt, after a comment line one
+ *                   line per event: dst src frame clipped automatic res_before res_after, box_lo (3), box_size (3), the
+ *                   eight counts, lo (3), hi (3), foreground gained colored uncolored, then the two overlaps, the
+ *                   destination's R (9) t (3), the source's and the pose used in %.9g.  Off: every result byte as before. */
+typedef struct emf_merge_event {
+    int32_t dst, src;       /* the object that stays and the one that went into it */
+    int32_t frame;          /* the frame index at which it happened */
+    int32_t clipped;        /* the source's cube leaves the destination's (as emf_absorb_event_t.clipped) */
+    int32_t automatic;      /* 1: merged by set_merge_objects at the end of a mask frame */
+    int32_t res_before, res_after;  /* the destination's resolution per axis before and after the growth */
+    int32_t reserved;       /* 0 */
+    float dst_R[9], dst_t[3];       /* the destination's pose (volume -> world) after the growth */
+    float src_R[9], src_t[3];       /* the source's pose */
+    float R[9], t[3];       /* the pose used: the source's volume frame <- the destination's */
+    int32_t lo[3], size[3]; /* the box of destination voxels the launch covered */
+    double overlap[2];      /* what decided an automatic merge: dst -> src, src -> dst; 0 for an explicit call */
+    emf_absorb_t record;    /* include/emf_hip.h "Merging a volume" */
+    emf_merge_counts_t counts;
+    emf_color_moved_t color;        /* zeros in a colourless session */
+} emf_merge_event_t;        /* 336 bytes */
+int emf_fusion_merge_union(const int32_t dst_lo[3], const int32_t dst_hi[3], const int32_t dst_res[3], float dst_voxel_size,
+                           const int32_t src_lo[3], const int32_t src_hi[3], const int32_t src_res[3], float src_voxel_size,
+                           const float R[9], const float t[3], float lo[3], float hi[3], int32_t* any);
+int emf_fusion_set_merge_objects(emf_fusion_t* h, int on, double min_overlap, int64_t min_surface, double touch_m, int32_t max_res);
+int emf_fusion_merge_objects(emf_fusion_t* h, int32_t dst, int32_t src, emf_merge_event_t* event);
+int emf_fusion_set_merged_output(emf_fusion_t* h, int on);
+/* What a merge sums: the existence counts of the live object `id` (frames it was matched / was not) and its accumulated
+ * class scores, the first min(capacity, *count) of them; *count is their number.  EMF_E_ARG: no such object. */
+int emf_fusion_object_bookkeeping(emf_fusion_t* h, int32_t id, int32_t* exists, int32_t* not_exists, double* scores, int32_t capacity,
+                                  int32_t* count);
+int emf_fusion_merged(emf_fusion_t* h, emf_merge_event_t* events, int32_t capacity, int32_t* count);
 /* Planes (include/emf_hip.h "Planes"; new behaviour, opt-in): the dominant planes of a box of the
  * background (box_lo / box_size NULL: all of it) -- floor, walls, table tops.  A plane is the plane of the SHELL's voxel
  * centres: up to one voxel behind the surface, and nothing corrects that.

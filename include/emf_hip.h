@@ -2585,6 +2585,53 @@ int emf_hip_releaseVolumeColor(float* dst_tsdf, float* dst_weights, uint16_t* ds
                                const float t[3], const int32_t box_lo[3], const int32_t box_size[3], emf_release_t* record_dev,
                                emf_color_moved_t* color_record_dev, emf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Merging a volume (new behaviour: DESIGN.md 5.32).  Opt-in; nothing above is touched.  An absorption whose DESTINATION
+ * IS AN OBJECT: a signed-distance volume plus the per-voxel (fg, bg) counts its foreground mask is derived from.
+ * Everything "Absorbing a volume" lays down holds here word for word: dense (z, y, x) volumes, x fastest, res = (nx, ny,
+ * nz); R[9], t[3] (f32, row-major) = the SOURCE's volume frame <- the DESTINATION's volume frame; per destination voxel
+ * v of the box the sample-point arithmetic p_d, p_s, q, l, f; the pad-1 OUTSIDE rule; the blend in x pairs, then y, then
+ * z; every float step a single float32 operation without contraction, everything else integer; the classes OUTSIDE,
+ * UNKNOWN, MASKED, SATURATED, FUSED in that order, the first match wins; only the words whose bits change are stored.
+ * The tsdf and the weights of a FUSED voxel are the absorption's (u, w_o, FRESH, the running average, the cap at
+ * maxWeight): for the same inputs the tsdf, the weights and the whole emf_absorb_t of emf_hip_mergeVolume equal
+ * emf_hip_absorbVolume's byte for byte.
+ * source->fgVolMask IS REQUIRED: a source voxel the source itself calls background is no evidence about the destination.
+ * COUNTS.  dst_fgbg, src_fgbg: res_d (res_s) pairs of f32, interleaved (fg, bg), in the voxel order of the tsdf -- the
+ * layout of emf_hip_updateFgBgProbs -- a pair read and written as one 8-byte word.  Only the pair of a FUSED voxel is
+ * read or written.  With (sf, sb) the source's pair at (rint(q_0), rint(q_1), rint(q_2)), ties to even (the addressing of
+ * MASKED), and (df, db) the destination's own at v, read once before either is written:
+ *     FRESH (!(pw > 0)):  (nf, nb) = (sf, sb)            an unobserved voxel's counts are not evidence
+ *     else:               (nf, nb) = (df + sf, db + sb)  one float32 sum each
+ * and the pair is stored only where its bits change.
+ * emf_merge_counts_t: a second device record, neutral at (0, 0) and set by the call's own init launch.  foreground: the
+ * FUSED voxels with nf > nb; gained: those of them that were FRESH or had !(df > db).  gained <= foreground <= fused.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct emf_merge_counts {
+    uint64_t foreground, gained;
+} emf_merge_counts_t;           /* 16 bytes */
+
+/* The arguments of emf_hip_absorbVolume plus dst_fgbg (written in place), src_fgbg (only read) and counts_dev (device,
+ * 8-byte aligned).  The record, the launch shape and the empty box (EMF_OK, both neutral records, nothing else written)
+ * are those of emf_hip_absorbVolume.  Refused with nothing enqueued, on top of everything emf_hip_absorbVolume refuses and
+ * with its codes: source->fgVolMask, dst_fgbg, src_fgbg or counts_dev NULL; a count volume or the count record not
+ * 8-byte aligned; an array the call writes (the destination's three, the two records) sharing a byte with any other
+ * array of the call. */
+int emf_hip_mergeVolume(float* dst_tsdf, float* dst_weights, float* dst_fgbg, const int32_t dst_res[3], float dst_voxel_size,
+                        float dst_truncdist, float max_weight, const emf_absorb_source_t* source, const float* src_fgbg, const float R[9],
+                        const float t[3], const int32_t box_lo[3], const int32_t box_size[3], emf_absorb_t* record_dev,
+                        emf_merge_counts_t* counts_dev, emf_stream_t stream);
+
+/* Colour with the band: the colour entry of every FUSED voxel exactly as emf_hip_absorbVolumeColor carries it (SOURCE
+ * ENTRY, capq, UNCOLOURED / COLOURED, emf_color_moved_t), on top of the above; for the same inputs tsdf, weights, counts
+ * and both other records equal the plain entry's.  dst_color, src_color (or NULL) and color_record_dev as there, with
+ * its additional refusals; an empty box: EMF_OK and the three neutral records. */
+int emf_hip_mergeVolumeColor(float* dst_tsdf, float* dst_weights, float* dst_fgbg, uint16_t* dst_color, const int32_t dst_res[3],
+                             float dst_voxel_size, float dst_truncdist, float max_weight, const emf_absorb_source_t* source,
+                             const float* src_fgbg, const uint16_t* src_color, const float R[9], const float t[3], const int32_t box_lo[3],
+                             const int32_t box_size[3], emf_absorb_t* record_dev, emf_merge_counts_t* counts_dev,
+                             emf_color_moved_t* color_record_dev, emf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
